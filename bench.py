@@ -14,18 +14,23 @@ the environment; launched plainly (`python bench.py --gpus N`) the script starts
 processes itself, before anything touches a GPU.  Default "weak" scaling: every rank runs its own
 K frames (frame sharding, no data-path collective), value = all ranks' slice-steps / max-over-ranks
 time.  `--scaling strong`: every step is one round of --frames-per-step frames sharded over the
-ranks, so the total work is fixed as N grows.  After the timed region the end-of-run exchanges
+ranks, so the total work is fixed as N grows.  With --full, after the timed region the end-of-run exchanges
 of the sharded path are timed on the frames just computed and reported as `exchange_ms`:
 gather of the frame shards on rank 0 (WFData), and all-to-all frames->probes + device time FFT +
 gather of the intensities (TACAW).
 
-Prints ONE JSON line on rank 0 with the throughput plus
+Prints ONE JSON line on rank 0 with the throughput (`value`, `ms_per_step`) plus
   roofline     -- dominant slice-loop kernel: algorithmic bytes per launch / mean launch duration
                   (HIP events on the library's stream, taken inside the timed region)
+and, with --full only (a plain run sets up, warms up, times the steps, dumps and prints):
   tacaw        -- (N=1) the time->frequency FFT over T=256 resident frame slots (BASELINE C3's T)
+  c3_full      -- (N=1) the remaining slots filled with real frames, the time FFT on them, checked
   cpu_baseline -- the NumPy oracle (port of the reference's NumPy path) timed on this host on a
                   bounded sample of the same workload (rank 0, N=1 only): single thread, and
-                  `cpu_baseline_allcores` with scipy.fft workers + threaded BLAS.
+                  `cpu_baseline_allcores` with scipy.fft workers + threaded BLAS
+  exchange_ms  -- (N>1) the end-of-run exchanges.
+--dump-outputs DIR writes the last timed step's exit waves (see dump_outputs) for output-for-output
+comparison of two builds; the inputs depend only on the arguments.
 """
 import argparse
 import json
@@ -79,6 +84,13 @@ def parse():
     ap.add_argument("--no-launch-timing", action="store_true",
                     help="run the library as production does (no per-launch HIP events, frames queue asynchronously); "
                          "the roofline block is then null")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: N=1 the TACAW leg over --tacaw-frames slots, the c3_full block and "
+                         "the CPU baselines; N>1 the end-of-run exchanges.  Without it a run sets up, warms up, times the steps, "
+                         "writes --dump-outputs and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step (rank 0's exit waves) "
+                         "as DIR/<name>.npy, float32 / float64, at most 64 MB (a fixed, seeded sample of larger outputs)")
     return ap.parse_args()
 
 
@@ -231,11 +243,11 @@ def run(a):
     side = int(round(P ** 0.5))
     pp = stem_probe_grid(side) if side * side == P else np.random.default_rng(0).random((P, 2)) * [lx, ly]
 
-    # N=1: hold T = 256 frame slots like the full C3 run (137 GB of spectra + 69 GB of intensities at 64 probes x 1024^2)
+    # N=1 with --full: hold T = 256 frame slots like the full C3 run (137 GB of spectra + 69 GB of intensities at 64 probes x 1024^2)
     # when the device has the room, so that the TACAW leg runs the kernel a C3 run uses
     slots = max(1, n_local)
     tacaw_T = None
-    if world == 1 and not a.no_tacaw and n_local >= 2:
+    if world == 1 and a.full and not a.no_tacaw and n_local >= 2:
         free_b, _ = torch.cuda.mem_get_info(local_rank)
         want = max(a.tacaw_frames, n_local)
         if 12.0 * P * want * npix + 24e9 < free_b and n_local <= a.tacaw_frames:
@@ -407,6 +419,15 @@ def run(a):
         if stream_done is not None:
             stream_done.set()
     wf_view = torch.as_tensor(eng.result_view(_native.BUF_WAVEFUNCTION, "<c8"), device=dev).reshape(P, slots, eng.wx * eng.wy)
+    if a.dump_outputs and rank == 0:
+        # the last timed step's frames, before anything after the timed region writes a slot (streaming: their places in the ring)
+        last = my_frames[a.warmup + a.steps - 1]
+        if stream:
+            n_timed = sum(len(my_frames[s]) for s in range(a.warmup, a.warmup + a.steps))
+            last_slots = [(n_timed - len(last) + i) % slots for i in range(len(last))]
+        else:
+            last_slots = [slot_of[f] for f in last]
+        dump_outputs(a.dump_outputs, wf_view, last_slots, eng.wx, eng.wy)
 
     # ---- BASELINE C3 as configured (N=1, after the timed region): every frame slot holds a REAL frame, the time FFT runs on them
     c3 = None
@@ -592,7 +613,7 @@ def run(a):
         if stream_ms is not None:
             out["stream_ms"] = stream_ms
             out["config"]["streaming_tacaw"] = {"ring": slots, "k_window": kw, "k_bin": a.k_bin, "frames_folded": world * n_local}
-        if world == 1 and not a.no_cpu_baseline:
+        if world == 1 and a.full and not a.no_cpu_baseline:
             out["cpu_baseline"], V = cpu_baseline(n, nz, P, a.aperture, a.cpu_slices)
             try:
                 out["cpu_baseline_allcores"] = cpu_baseline_allcores(n, nz, P, a.aperture, a.cpu_slices, V)
@@ -600,7 +621,7 @@ def run(a):
                 out["cpu_baseline_allcores"] = {"error": repr(exc)}
     else:
         out = None
-    if world > 1 and not a.no_exchange and not stream:
+    if world > 1 and a.full and not a.no_exchange and not stream:
         # The timed region is over and its line is complete.  The exchanges move tens of GB between the ranks over a backend
         # this build could not exercise on real multi-GPU hardware: if they stall, every rank's watchdog ends its process after
         # `--exchange-timeout` seconds and rank 0 still prints the line, with the failure recorded instead of the timings.
@@ -644,6 +665,39 @@ def run(a):
         except Exception:
             pass
         t.cancel()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SAMPLE = 1 << 21          # complex values drawn from an output too large to write whole
+DUMP_SEED = 20240917
+
+
+def dump_outputs(path, wf_view, slots, wx, wy):
+    """What the timed path returns for its last step: the exit waves (P, F, wx, wy) complex64 of the step's F frames.
+    Whole when they fit in 48 MB, as `wavefunction.npy` (P, F, wx, wy, 2) float32; else probe 0's image of the last frame
+    (when it fits in 16 MB) and a fixed sample of DUMP_SAMPLE flat indices drawn with DUMP_SEED, values (M, 2) float32 and
+    indices float64.  Always `intensity_sum.npy` (P, F) float64: sum |psi|^2 over every pixel."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    w = torch.stack([wf_view[:, s] for s in slots], dim=1)                 # (P, F, K) complex64, contiguous copy
+    P, F, K = w.shape
+    wr = torch.view_as_real(w)
+    files = {"intensity_sum": wr.double().square().sum(dim=(2, 3)).cpu().numpy()}
+    if w.numel() * 8 <= 48 << 20:
+        files["wavefunction"] = wr.reshape(P, F, wx, wy, 2).cpu().numpy()
+    else:
+        if K * 8 <= 16 << 20:
+            files["wavefunction_probe0"] = wr[0, -1].reshape(wx, wy, 2).cpu().numpy()
+        idx = np.unique(np.random.default_rng(DUMP_SEED).integers(0, w.numel(), size=DUMP_SAMPLE))
+        files["wavefunction_sample"] = wr.reshape(-1, 2)[torch.from_numpy(idx).to(w.device)].cpu().numpy()
+        files["wavefunction_sample_index"] = idx.astype(np.float64)
+    total = sum(v.nbytes for v in files.values())
+    assert total <= DUMP_LIMIT_BYTES, total
+    for name, v in files.items():
+        assert v.dtype in (np.float32, np.float64), (name, v.dtype)
+        np.save(os.path.join(path, name + ".npy"), v)
+    print(f"[bench] wrote {', '.join(sorted(files))} ({total / 2**20:.1f} MB) to {path}", file=sys.stderr)
 
 
 def _tacaw_kernel_name(T, npix):

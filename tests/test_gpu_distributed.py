@@ -224,7 +224,7 @@ def test_ranks_frame_sharded_streaming_tacaw(world):
 
 
 def test_bench_two_ranks_gloo_rehearsal(tmp_path):
-    """`python bench.py --gpus 2` starts its own two ranks (both on this one GPU, gloo instead of RCCL), reports
+    """`python bench.py --gpus 2 --full` starts its own two ranks (both on this one GPU, gloo instead of RCCL), reports
     n_gpus = 2 and times the end-of-run exchanges."""
     import json
     import subprocess
@@ -234,7 +234,7 @@ def test_bench_two_ranks_gloo_rehearsal(tmp_path):
     env["MSL_BENCH_BACKEND"] = "gloo"
     for extra in ([], ["--scaling", "strong", "--frames-per-step", "4"]):
         r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "2", "--grid", "256", "--slices", "6",
-                            "--probes", "4", "--steps", "2", "--warmup", "1"] + extra, env=env, capture_output=True, text=True, timeout=600)
+                            "--probes", "4", "--steps", "2", "--warmup", "1", "--full"] + extra, env=env, capture_output=True, text=True, timeout=600)
         assert r.returncode == 0, r.stderr[-2000:]
         line = [l for l in r.stdout.splitlines() if l.startswith("{")]
         assert len(line) == 1, r.stdout
@@ -285,7 +285,7 @@ def test_bench_line_survives_a_stalled_exchange():
     env["MSL_BENCH_TEST_STALL"] = "1"
     t0 = time.time()
     r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "2", "--grid", "256", "--slices", "6", "--probes", "4",
-                        "--steps", "2", "--warmup", "1", "--exchange-timeout", "8"], env=env, capture_output=True, text=True, timeout=300)
+                        "--steps", "2", "--warmup", "1", "--exchange-timeout", "8", "--full"], env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 3, (r.returncode, r.stderr[-2000:])
     assert time.time() - t0 < 200
     line = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -295,7 +295,7 @@ def test_bench_line_survives_a_stalled_exchange():
 
 
 def test_bench_single_gpu_line_and_c3_full_block():
-    """`python bench.py` at N = 1 in small: one JSON line with the roofline and cpu_baseline objects, and the c3_full block --
+    """`python bench.py --full` at N = 1 in small: one JSON line with the roofline and cpu_baseline objects, and the c3_full block --
     after the timed region the remaining frame slots are filled with REAL frames, the time FFT runs on them, Parseval over the
     frequency axis holds, sampled time series agree with a float64 FFT and the trajectory's phonon peaks are found (timestep
     0.005 ps, 64 frames: 3.1 THz per bin)."""
@@ -305,7 +305,7 @@ def test_bench_single_gpu_line_and_c3_full_block():
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--grid", "256", "--slices", "8", "--probes", "4", "--steps", "8",
-                        "--warmup", "4", "--tacaw-frames", "64", "--cpu-slices", "4"], env=env, capture_output=True, text=True, timeout=600)
+                        "--warmup", "4", "--tacaw-frames", "64", "--cpu-slices", "4", "--full"], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(line) == 1, r.stdout
@@ -317,6 +317,46 @@ def test_bench_single_gpu_line_and_c3_full_block():
     assert c3["parseval_rel"] < 1e-4 and c3["time_fft_worst_series_rel_l2"] < 2e-4
     assert j["tacaw"]["frames"] == 64 and "real frames" in j["tacaw"]["note"]
     assert len(c3["spectrum_peak_THz"]) == 3 and min(abs(p - 25.0) for p in c3["spectrum_peak_THz"]) <= c3["frequency_resolution_THz"]
+
+
+def test_bench_plain_run_is_lean_and_dumps_the_last_step(tmp_path):
+    """A plain `python bench.py` run (no --full) times exactly --steps steps, prints the headline line without the TACAW leg,
+    c3_full or CPU baselines, and with --dump-outputs writes the last timed step's exit waves; the same arguments with --full
+    compute the same outputs (the inputs depend only on the arguments)."""
+    import json
+    import subprocess
+    import sys
+    from conftest import rel_l2
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    args = [sys.executable, os.path.join(repo, "bench.py"), "--gpus", "1", "--grid", "256", "--slices", "6", "--probes", "4",
+            "--steps", "3", "--warmup", "2"]
+    lines, dumps = [], []
+    for extra in ([], ["--full", "--tacaw-frames", "16", "--no-cpu-baseline"]):
+        d = tmp_path / ("full" if extra else "plain")
+        r = subprocess.run(args + ["--dump-outputs", str(d)] + extra, env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(line) == 1, r.stdout
+        lines.append(json.loads(line[0]))
+        dumps.append({f.stem: np.load(f) for f in d.glob("*.npy")})
+    plain, full = lines
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert plain.get(k) is not None, k
+    assert plain["unit"] == "slice-steps/s" and plain["higher_is_better"] is True and plain["value"] > 0
+    assert plain["steps"] == 3 and plain["config"]["frames_timed"] == 3 and plain["config"]["frame_slots"] == 5
+    assert abs(plain["value"] - 3 * 4 * 6 / (plain["ms_per_step"] * 3e-3)) <= 1e-2 * plain["value"]
+    assert not any(k in plain for k in ("tacaw", "c3_full", "cpu_baseline", "cpu_baseline_allcores"))
+    assert full["c3_full"]["frames"] == 16 and full["tacaw"]["frames"] == 16
+    a, b = dumps
+    assert sorted(a) == sorted(b) == ["intensity_sum", "wavefunction"]
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    wf = a["wavefunction"]
+    assert wf.dtype == np.float32 and wf.shape == (4, 1, 256, 256, 2) and np.isfinite(wf).all()
+    assert a["intensity_sum"].dtype == np.float64 and a["intensity_sum"].shape == (4, 1)
+    assert np.allclose(a["intensity_sum"], (wf.astype(np.float64) ** 2).sum(axis=(2, 3, 4)), rtol=1e-6)
+    assert (a["intensity_sum"] > 0).all()
+    assert rel_l2(b["wavefunction"], wf) < 1e-5 and rel_l2(b["intensity_sum"], a["intensity_sum"]) < 1e-5
 
 
 _RCCL_LOOPBACK = r'''
