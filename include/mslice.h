@@ -87,7 +87,9 @@ typedef enum {
     MSL_BUF_STREAM_ACC = 7,    /* (P,n_bins,K) c64  sum_t (Psi[p,t,k] - ref[p,k]) exp(-2 pi i u t / T) over the frames pushed so far */
     MSL_BUF_STREAM_S1 = 8,     /* (P,K) 2 x f64     sum_t Psi */
     MSL_BUF_STREAM_S2 = 9,     /* (P,K) f64         sum_t |Psi|^2 */
-    MSL_BUF_STREAM_REF = 10    /* (P,K) c64         the reference pattern (msl_tacaw_stream_set_reference), NULL when none is set */
+    MSL_BUF_STREAM_REF = 10,   /* (P,K) c64         the reference pattern (msl_tacaw_stream_set_reference), NULL when none is set */
+    MSL_BUF_LAYERS = 11        /* (L,P,T_local,pitch) c64  the spectra of every layer (msl_set_layers), the exit wave last; L = 1 without
+                                *                    layers (then the same memory as MSL_BUF_WAVEFUNCTION) */
 } msl_buffer;
 
 typedef struct {
@@ -250,9 +252,26 @@ int  msl_tacaw_dispersion(msl_handle* h, const void* d_src_f32, int64_t B, int64
  *   Replaces the masked |.| sum and frame mean of HAADFData.calculateADF (haadf_data.py:72-94). */
 int  msl_adf(msl_handle* h, const void* d_src_c64, int64_t B, int64_t T, int64_t K, int64_t ld, const uint8_t* mask, double* out);
 
+/* ---- thickness series: spectra of intermediate layers of the stack ----
+ * msl_set_layers: `n` strictly increasing slice indices k in [0, nz-1).  Layer k is the wave after the transmission of slice k and
+ * before the propagation that follows it -- the exit wave of the stack cut after slice k.  Every fused slice loop then also writes
+ * fftshift(fft2(layer k)) (k-window, binning and frame batching as the exit) into block l of ONE (n+1, P, T_local, pitch) c64
+ * result; MSL_BUF_WAVEFUNCTION is its last block (the exit), so every call that reads the wavefunction buffer keeps working on the
+ * exit wave.  The result buffer is replaced (zeros).  n = 0 restores the single-layer buffer.  MSL_ERR_INVALID for bad indices,
+ * MSL_ERR_STATE with n_frames == 0 or while a stream is open, MSL_ERR_NOMEM when the device cannot hold the result.
+ * The reference writes a single layer (calculators.py:221) into WFData's layer axis (wf_data.py:12-27). */
+int  msl_set_layers(msl_handle* h, const int32_t* slices, int32_t n);
+/* The layered result as the reference's host array (P, n_frames_used, wx, wy, L) complex128: layers interleaved and widened on
+ * the device chunk by chunk, then linear copies.  dst: P * n_frames_used * wx * wy * L complex128. */
+int  msl_download_layers_c128(msl_handle* h, int32_t n_frames_used, void* dst_c128, size_t bytes);
+/* msl_tacaw with d_src == NULL on block `layer` of the layered result (TACAWData(wf, layer_index=layer), tacaw_data.py:61-89):
+ * the intensity goes to the handle's own buffer, for the reductions with d_src == NULL. */
+int  msl_tacaw_layer(msl_handle* h, int32_t layer);
+
 /* Copy a device buffer to the host (dst must hold `bytes` = full buffer size, see msl_buffer_bytes).
  * For MSL_BUF_WAVEFUNCTION / MSL_BUF_INTENSITY the host copy is dense -- (P,T,wx,wy), bytes = P*T*wx*wy*8 or *4, the pixel
- * pitch of the device buffer (msl_result_pitch) is dropped on the way -- and `first`/`count` select a probe range (count==0: all). */
+ * pitch of the device buffer (msl_result_pitch) is dropped on the way -- and `first`/`count` select a probe range (count==0: all).
+ * MSL_BUF_LAYERS: dense (L,P,T,wx,wy), no range. */
 int  msl_download(msl_handle* h, msl_buffer what, void* dst, size_t bytes, int64_t first, int64_t count);
 /* The (P, T_local, nx, ny) result as complex128 -- the dtype the reference returns (calculators.py:161, 284-290: its arrays are
  * torch.complex128) -- for the frames [0, n_frames_used) of every probe: widened on the device chunk by chunk and copied out as

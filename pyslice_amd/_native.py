@@ -16,7 +16,7 @@ LIB_PATH = os.environ.get("MSL_LIB") or os.path.join(_HERE, "libmslice.so")
 ABI_VERSION = 3          # include/mslice.h: MSL_ABI_VERSION
 MSL_OK, MSL_ERR_INVALID, MSL_ERR_HIP, MSL_ERR_UNSUPPORTED, MSL_ERR_STATE, MSL_ERR_NOMEM = 0, -1, -2, -3, -4, -5
 (BUF_PROBES, BUF_EXIT, BUF_POTENTIAL, BUF_TRANSMISSION, BUF_WAVEFUNCTION, BUF_INTENSITY, BUF_FORMFACTOR,
- BUF_STREAM_ACC, BUF_STREAM_S1, BUF_STREAM_S2, BUF_STREAM_REF) = range(11)
+ BUF_STREAM_ACC, BUF_STREAM_S1, BUF_STREAM_S2, BUF_STREAM_REF, BUF_LAYERS) = range(12)
 
 EXPORTS = [
     "msl_abi_version", "msl_line_kernel_class", "msl_last_error", "msl_create", "msl_destroy", "msl_set_kirkland", "msl_set_slices",
@@ -29,6 +29,7 @@ EXPORTS = [
     "msl_select_batch_slot", "msl_propagate_frames", "msl_frame_batch", "msl_build_potentials",
     "msl_tacaw_stream_begin", "msl_tacaw_stream_push", "msl_tacaw_stream_finish",
     "msl_tacaw_stream_set_reference", "msl_tacaw_stream_finish_range",
+    "msl_set_layers", "msl_download_layers_c128", "msl_tacaw_layer",
 ]
 
 
@@ -108,6 +109,9 @@ def load():
         "msl_tacaw_stream_finish": (C.c_int, [vp, vp]),
         "msl_tacaw_stream_set_reference": (C.c_int, [vp, vp, i32]),
         "msl_tacaw_stream_finish_range": (C.c_int, [vp, i32, i32, vp, vp]),
+        "msl_set_layers": (C.c_int, [vp, vp, i32]),
+        "msl_download_layers_c128": (C.c_int, [vp, i32, vp, C.c_size_t]),
+        "msl_tacaw_layer": (C.c_int, [vp, i32]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -172,6 +176,7 @@ class Engine:
             self.wx //= max(1, int(k_bin[0]))
             self.wy //= max(1, int(k_bin[1]))
         self.intensity_F = 0               # frequency bins of the resident intensity buffer
+        self.layers = []                   # slice indices of the intermediate layers (set_layers); the exit wave is the last layer
         self.frame_batch = int(self._lib.msl_frame_batch(self._h))      # frames that share one sequence of launches
 
     # -- lifetime
@@ -284,6 +289,33 @@ class Engine:
         if not src_ptr:
             self.intensity_F = self.n_frames
 
+    @property
+    def n_layers(self):
+        return len(self.layers) + 1
+
+    def set_layers(self, slices):
+        """record fftshift(fft2(.)) of the waves after the transmission of these slices (strictly increasing, < nz - 1) next to the
+        exit wave: the result becomes (L, P, T_local, pitch) with the exit last (msl_set_layers; [] = exit only)"""
+        s = np.ascontiguousarray(slices, dtype=np.int32).reshape(-1)
+        self._chk(self._lib.msl_set_layers(self._h, _ptr(s) if s.size else None, int(s.size)))
+        self.layers = [int(v) for v in s]
+
+    def tacaw_layer(self, layer):
+        """msl_tacaw on block `layer` of the layered result into the handle's intensity buffer"""
+        self._chk(self._lib.msl_tacaw_layer(self._h, int(layer)))
+        self.intensity_F = self.n_frames
+
+    def layers_c128(self, n_frames_used=0):
+        """(P, n_frames_used, wx, wy, L) complex128: the reference's WFData array, interleaved and widened on the device"""
+        T = int(n_frames_used) if n_frames_used else self.n_frames
+        out = np.empty((self.n_probes, T, self.wx, self.wy, self.n_layers), dtype=np.complex128)
+        self._chk(self._lib.msl_download_layers_c128(self._h, T, _ptr(out), out.nbytes))
+        return out
+
+    def layers_c64(self):
+        """(L, P, n_frames, wx, wy) complex64, dense"""
+        return self.download(BUF_LAYERS, np.complex64, (self.n_layers, self.n_probes, self.n_frames, self.wx, self.wy))
+
     # -- streaming TACAW: accumulate the time->frequency transform for chosen bins, tile of frames by tile of frames
     def tacaw_stream_begin(self, T_total, bins=None):
         b = None if bins is None else np.ascontiguousarray(bins, dtype=np.int32).reshape(-1)
@@ -340,6 +372,14 @@ class Engine:
         es = int(typestr[2:])
         strides = (rows * pitch * es, pitch * es, self.wy * es, es)
         return DeviceArray(self.device_ptr(what), (self.n_probes, rows, self.wx, self.wy), typestr, owner=self, strides=strides)
+
+    def layers_view(self):
+        """DeviceArray of the layered result as (L, P, n_frames, wx, wy) c64 with the library's image pitch in its strides"""
+        pitch, es = self.result_pitch(BUF_LAYERS), 8
+        T = self.n_frames
+        strides = (self.n_probes * T * pitch * es, T * pitch * es, pitch * es, self.wy * es, es)
+        return DeviceArray(self.device_ptr(BUF_LAYERS), (self.n_layers, self.n_probes, T, self.wx, self.wy), "<c8", owner=self,
+                           strides=strides)
 
     def tacaw_spectrum(self, mask=None, src=None):
         """(B,F) float64: sum over k of the (masked) intensity."""

@@ -80,7 +80,7 @@ def _widen_to_host(view, chunk_bytes=1 << 30):
 class MultisliceCalculator:
 
     def __init__(self, device=None, force_cpu=False, *, output="host", dtype="complex128", progress=True,
-                 gather="rank0", cache=False, k_window=None, frame_batch=None, k_bin=None, stream_tile=None):
+                 gather="rank0", cache=False, k_window=None, frame_batch=None, k_bin=None, stream_tile=None, layers=None):
         """
         device / force_cpu: as the reference (calculators.py:41).  There is no CPU path here, so
         force_cpu=True raises.  Keyword-only extras (not in the reference):
@@ -97,6 +97,10 @@ class MultisliceCalculator:
                    around k = 0).  wavefunction_data becomes (P,T,wx,wy,1), kxs/kys are cropped to match,
                    and TACAWData / HAADFData work on the window.  Cuts the resident result by nx*ny/(wx*wy) -- the way
                    to hold 2048^2 x 1024-frame runs at all -- and the exit FFT only transforms the columns kept.
+          layers   thickness series: 0-based slice indices k whose wave (after the transmission of slice k, before the
+                   propagation that follows it: the exit wave of the stack cut after slice k) is recorded as well.  setup()
+                   sorts them, drops duplicates and appends nz - 1 (the exit wave, always the last layer); wavefunction_data
+                   becomes (P,T,wx,wy,L) and WFData.layer holds the slice indices.  Not with cache, stream_tile or several ranks.
         """
         if force_cpu:
             raise NotImplementedError("pyslice_amd has no CPU path (force_cpu=True): use the reference for CPU runs")
@@ -131,6 +135,14 @@ class MultisliceCalculator:
         if frame_batch is not None and int(frame_batch) < 1:
             raise ValueError("frame_batch must be a positive frame count")
         self._frame_batch = None if frame_batch is None else int(frame_batch)
+        if layers is not None:
+            if cache:
+                raise ValueError("the frame cache has no layer axis: cache=True cannot be combined with layers")
+            if stream_tile is not None:
+                raise ValueError("streaming TACAW keeps the exit wave only: stream_tile cannot be combined with layers")
+            layers = list(layers)
+        self._layers_arg = layers
+        self._layers = None                     # validated slice indices (setup), nz - 1 last
         self._engine = None
         # reference calculators.py:70-76 (display names for Z <= 36)
         self.element_map = {
@@ -186,6 +198,7 @@ class MultisliceCalculator:
         self.nx, self.ny, self.nz = nx, ny, nz
         self.dx = xs[1] - xs[0]
         self.dy = ys[1] - ys[0]
+        self._layers = self._check_layers(len([xs, ys, zs][slice_axis]), distributed.rank_world()[1])
         # (not in the reference) a line length without a slice-loop kernel of its own costs 2-4 x: name a nearby sampling that has one
         hint = suggest_sampling(trajectory, sampling)
         self.grid_hint = None if hint is None else (
@@ -243,10 +256,11 @@ class MultisliceCalculator:
                 n_atoms = len(trajectory.atom_types)
                 tables = min(6e9, batch * n_atoms * (nx // 2 + ny // 2 + 2) * 8.0)
                 later = tables + 4.0 * stored + (24.0 * stored / slots if self._stream_tile is not None else 0.0)
-                fixed = 8.0 * stored + later + 2e9
+                fixed = 8.0 * stored * len(self._layers) + later + 2e9        # (one result block per layer)
                 per_frame = 16.0 * n_slices * nx * ny + 24.0 * nx * ny * self.n_probes
                 while batch > 1 and fixed + batch * per_frame > 0.95 * free_b:
                     batch = max(1, batch // 2)
+        self._check_layer_memory(dev, nx, ny, slots)
         # The frame batch costs batch x (two orientations of the transmission stack + three work buffers): when the device cannot
         # hold it next to the (P, T_local, wx, wy) result -- a result near capacity, a shared or smaller GPU -- halve it down to one
         # frame per launch sequence instead of failing a run that fits without batching (an explicit frame_batch is honoured as is)
@@ -264,11 +278,46 @@ class MultisliceCalculator:
                 if self._stream_tile is not None:
                     batch = min(batch, slots)
                 logger.info(f"device memory: frame batch reduced to {batch}")
+        if len(self._layers) > 1:
+            self._engine.set_layers(self._layers[:-1])
         self._engine.set_kirkland(loadKirkland())
         lo, hi = slice_edges(slice_coords)
         self._engine.set_slices(lo, hi)
         self._engine.set_probes(self.aperture, np.asarray(self.probe_positions, dtype=np.float64))
         self._Z = np.asarray(trajectory.atom_types, dtype=np.int32)
+
+    def _check_layers(self, n_slices, world):
+        """the `layers` argument -> sorted unique slice indices with n_slices - 1 last (before any device work)"""
+        if self._layers_arg is None:
+            return [n_slices - 1]
+        if world > 1:
+            raise NotImplementedError("layers: runs over several ranks gather the exit wave only")
+        out = set()
+        for k in self._layers_arg:
+            if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, np.integer)):
+                raise ValueError(f"layers must be integer slice indices, got {k!r}")
+            if not 0 <= int(k) <= n_slices - 1:
+                raise ValueError(f"layer slice index {k} outside [0, {n_slices - 1}]")
+            out.add(int(k))
+        out.discard(n_slices - 1)
+        return sorted(out) + [n_slices - 1]
+
+    def _check_layer_memory(self, dev, nx, ny, slots):
+        """L result blocks (P, T_local, pitch) c64 must fit in the device's free memory: fail before anything is allocated"""
+        L = len(self._layers)
+        if L == 1 or not (TORCH_AVAILABLE and torch.cuda.is_available()):
+            return
+        wx, wy = self._k_window if self._k_window is not None else (nx, ny)
+        bx, by = self._k_bin if self._k_bin is not None else (1, 1)
+        pitch = ((wx // bx) * (wy // by) + 31) // 32 * 32
+        need = 8.0 * L * self.n_probes * slots * pitch
+        try:
+            free_b = float(torch.cuda.mem_get_info(_device_index(dev))[0])
+        except Exception:                                  # pragma: no cover  (no device visible to torch: msl_set_layers decides)
+            return
+        if need > free_b:
+            raise MemoryError(f"layers: {L} layers of {self.n_probes} probes x {slots} frames need {need / 1e9:.1f} GB of device memory, "
+                              f"{free_b / 1e9:.1f} GB are free")
 
     def run(self) -> WFData:
         """reference calculators.py:163-250: all frames, then pack WFData."""
@@ -322,7 +371,7 @@ class MultisliceCalculator:
         # reference calculators.py:218-221 (quirk Q2: `sampling`, not dx; torch default float32)
         kxs, kys = self._k_axes()
         time_array = np.arange(self.n_frames) * self.trajectory.timestep
-        layer_array = np.array([0])
+        layer_array = np.array([0]) if self._layers_arg is None else np.asarray(self._layers, dtype=np.int64)   # (layers: slice indices)
 
         data, resident = self._collect()
         self.wavefunction_data = data
@@ -364,6 +413,8 @@ class MultisliceCalculator:
             raise RuntimeError("call setup() before run_streaming_tacaw()")
         if self._stream_tile is None:
             raise RuntimeError("run_streaming_tacaw() needs MultisliceCalculator(stream_tile=Tt)")
+        if self._layers is not None and len(self._layers) > 1:
+            raise ValueError("run_streaming_tacaw() keeps the exit wave only: no layers")
         eng, T = self._engine, self.n_frames
         if T < 2:
             raise ValueError("TACAW needs at least 2 frames")
@@ -481,6 +532,15 @@ class MultisliceCalculator:
         eng = self._engine
         P, nx, ny = self.n_probes, eng.wx, eng.wy          # stored spectrum shape (the k-window, or the grid)
         T_local = len(self._frames)
+        if eng.n_layers > 1:
+            # (layers: single-process runs only) the (L, P, T, wx, wy) device result -> the reference's (P, T, wx, wy, L)
+            if self._output == "device":
+                view = torch.as_tensor(eng.layers_view(), device=f"cuda:{eng.device}")
+                return view.permute(1, 2, 3, 4, 0)[:, :T_local], T_local == eng.n_frames
+            if self._dtype == "complex128":
+                return _as_tensor(eng.layers_c128(T_local)), T_local == eng.n_frames
+            local = eng.layers_c64()[:, :, :T_local]
+            return _as_tensor(np.ascontiguousarray(np.moveaxis(local, 0, -1))), T_local == eng.n_frames
         if self._world == 1 or self._gather == "none":
             if self._output == "device":
                 # (the images sit at the library's line-aligned pixel pitch: a strided view when nx*ny is not a multiple of 32)

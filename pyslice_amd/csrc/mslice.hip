@@ -20,6 +20,7 @@
 #include "stream.h"
 #include "tacaw_time.h"
 #include "tacaw_launch.h"
+#include "layer_tap.h"
 
 using namespace msl;
 
@@ -118,6 +119,15 @@ struct msl_handle {
     size_t intensity_elems = 0;
     float2* pxt = nullptr;      // exp(-i pi lambda dz kx^2)/nx
     float2* pyt = nullptr;
+    // thickness series (msl_set_layers): result block of every slice (-1: not a layer), the (L, P, T_local, wpitch) result whose last
+    // block is wf, the natural-order image set the layer tap transforms (FB * P images, psi's layout) and the unscaled conjugate
+    // propagator factors conj(Px), conj(Py) of the tap
+    std::vector<int> layer_block;
+    std::vector<int> layer_slices;
+    float2* layers = nullptr;
+    float2* tap = nullptr;
+    float2* tap_cx = nullptr;
+    float2* tap_cy = nullptr;
     double* d_abcd = nullptr;
     double* d_lo = nullptr;
     double* d_hi = nullptr;
@@ -618,42 +628,107 @@ int fft2_inplace(msl_handle* h, float2* buf, int images, int dir, float scale, i
 // scatter into slot `slot` of the (P, T_local, wx, wy) result (calculators.py:284-290).  With a k-window only the
 // columns inside it are transformed and only the rows inside it are stored.
 // staged full-resolution windows of `groups` frames x P probes -> binned frame slots slot .. slot+groups-1
-int bin_frames(msl_handle* h, int slot, int groups) {
+int bin_frames(msl_handle* h, int slot, int groups, float2* result) {
     const msl_config& c = h->cfg;
     const long long total = (long long)h->wpix * c.n_probes * groups;
-    hipLaunchKernelGGL(bin_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, h->bin_stage, h->wf, c.n_probes, groups,
+    hipLaunchKernelGGL(bin_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, h->bin_stage, result, c.n_probes, groups,
                        c.n_frames, slot, h->wx, h->wy, h->bx, h->by, (long long)h->wpitch);
     HIPCHK(h, hipGetLastError());
     return mark_launch(h, K_OTHER);
 }
 
-int epilogue_x_pass(msl_handle* h, int slot, int groups = 1) {
+// src: y-transformed waves in psi's layout (default psi); result: (P, T_local, wpitch) block (default wf); px: weight of the x
+// frequencies after the FFT (the layer tap), or null
+int epilogue_x_pass(msl_handle* h, int slot, int groups = 1, const float2* src = nullptr, float2* result = nullptr, const float2* px = nullptr) {
     const msl_config& c = h->cfg;
+    if (!src) src = h->psi;
+    if (!result) result = h->wf;
     const int P = c.n_probes * groups;               // image = frame-of-batch * n_probes + probe -> wf[probe][slot + frame]
     const bool binned = h->bin_stage != nullptr;
     // binning: the full-resolution window of every image goes to the staging buffer (image-major), bin_kernel sums it
     // into the frame slots -- 16 B/pixel/(probe, frame) extra against 16 B/pixel/slice-step of the loop
-    float2* dst = binned ? h->bin_stage : h->wf + (size_t)slot * h->wpitch;
+    float2* dst = binned ? h->bin_stage : result + (size_t)slot * h->wpitch;
     const long long out_is = binned ? (long long)h->wx * h->wy : (long long)c.n_frames * h->wpitch;
     const int og = binned ? 1 : groups;               // staged images stay image-major; bin_kernel regroups them by frame
     const bool windowed = (h->wx != c.nx) || (h->wy != c.ny);
     const bool fast_ok = h->Rx && (!windowed || (c.ny % 32 == 0 && h->wy % 32 == 0));
     if (fast_ok) {
-        ColJob k = col_job(h, h->psi, dst, P, h->pitch, h->wy);
+        ColJob k = col_job(h, src, dst, P, h->pitch, h->wy);
         k.flags = COL_FWD | COL_SHIFT; k.out_image_stride = out_is;
+        if (px) { k.px = px; k.flags |= COL_MULPX; }
         if (og > 1) { k.out_group = c.n_probes; k.out_group_stride = (long long)h->wpitch; }
         if (windowed) { k.win_c0 = h->wy0; k.win_nc = h->wy; k.win_x0 = h->wx0; k.win_nx = h->wx; }
         int rc = launch_col_fast(h, k, K_OTHER);
-        return (rc || !binned) ? rc : bin_frames(h, slot, groups);
+        return (rc || !binned) ? rc : bin_frames(h, slot, groups, result);
     }
-    LineArgs k = col_args(h, h->psi, dst, P, h->pitch, h->wy);
+    LineArgs k = col_args(h, src, dst, P, h->pitch, h->wy);
     k.fft1 = +1;
+    if (px) { k.m1_kind = MUL_VEC; k.m1 = px; }
     k.out_is = out_is;
     if (og > 1) { k.group = c.n_probes; k.out_gs = (long long)h->wpitch; }
     k.shift_n = c.nx / 2; k.shift_r = c.ny / 2;
     if (windowed) { k.win_n0 = h->wx0; k.win_nn = h->wx; k.win_r0 = h->wy0; k.win_nr = h->wy; }
     int rc = launch_lines(h, h->plan_x, k, K_OTHER);
-    return (rc || !binned) ? rc : bin_frames(h, slot, groups);
+    return (rc || !binned) ? rc : bin_frames(h, slot, groups, result);
+}
+
+// ---- thickness series: the layer tap ---------------------------------------
+// After the pass that applied t_k the work buffer holds, in the layout that pass wrote,
+//   one-pass loops:  S = A_d psi_k  (A_d = ifft_d P_d fft_d, d = the pass's axis)   ->  fft2(psi_k) = conj(P_d)[k_d] fft2(S)
+//   two-pass loop:   S = (P_y / ny) fft_y psi_k                                      ->  fft_y(psi_k) = ny conj(P_y)[k_y] S
+// The tap copies S into natural order (layer_tap_gather_kernel; the two-pass loop's weight applied there), transforms along y (with
+// conj(P_y) when d = y), and runs the exit epilogue into block `layer_block[k]` (with conj(P_x) after the x-FFT when d = x).
+// The passes of the loop are untouched.  axis: 0 = the pass ran along y, 1 = along x, 2 = two-pass loop.
+constexpr int TAP_MAX_LAUNCHES = 4;                  // gather, row FFT, column epilogue, binning
+
+int n_taps(const msl_handle* h) { return (int)h->layer_slices.size(); }
+
+size_t layer_block_elems(const msl_handle* h) { return h->wpitch * (size_t)h->cfg.n_probes * h->cfg.n_frames; }
+
+int layer_tap(msl_handle* h, int k, int slot, int groups, const float2* buf, bool transposed, int order, int rp, int axis) {
+    if (slot < 0 || h->layer_block.empty() || h->layer_block[k] < 0) return MSL_OK;
+    const msl_config& c = h->cfg;
+    const int P = c.n_probes * groups;
+    TapGatherJob g{};
+    g.src = buf; g.dst = h->tap;
+    g.wy = axis == 2 ? h->tap_cy : nullptr; g.wscale = (float)c.ny;
+    g.src_is = transposed ? (long long)c.ny * h->pitchT : (long long)c.nx * h->pitch;
+    g.dst_is = (long long)c.nx * h->pitch;
+    g.src_pitch = transposed ? h->pitchT : h->pitch; g.dst_pitch = h->pitch;
+    g.nx = c.nx; g.ny = c.ny; g.transposed = transposed ? 1 : 0; g.order = order; g.rp = rp;
+    const int n_lines = transposed ? c.ny : c.nx, len = transposed ? c.nx : c.ny;
+    hipLaunchKernelGGL((layer_tap_gather_kernel<32, 64>), dim3((len + 63) / 64, (n_lines + 31) / 32, P), dim3(256), 0, h->stream, g);
+    HIPCHK(h, hipGetLastError());
+    int rc = mark_launch(h, K_OTHER);
+    if (rc) return rc;
+    if (axis != 2) {
+        if (h->Ry) {
+            RowJob r = row_job(h, h->tap, P, h->pitch);
+            r.do_fft = true; r.py = axis == 0 ? h->tap_cy : nullptr;
+            rc = launch_row_fast(h, r, K_OTHER);
+        } else {
+            LineArgs r = row_args(h, h->tap, h->tap, P, h->pitch);
+            r.fft1 = +1;
+            if (axis == 0) { r.m1_kind = MUL_VEC; r.m1 = h->tap_cy; }
+            rc = launch_lines(h, h->plan_y, r, K_OTHER);
+        }
+        if (rc) return rc;
+    }
+    if ((rc = epilogue_x_pass(h, slot, groups, h->tap, h->layers + (size_t)h->layer_block[k] * layer_block_elems(h), axis == 1 ? h->tap_cx : nullptr)))
+        return rc;
+    // read S, write + read the copy (twice with the row FFT), write the layer's spectra
+    const uint64_t img = (uint64_t)c.nx * c.ny * 8ull;
+    h->ctr.algorithmic_bytes += (uint64_t)P * (img * (axis == 2 ? 3 : 5) + (uint64_t)h->wpix * 8ull);
+    return MSL_OK;
+}
+
+// line order of the output of a transposing pass of direction `o` launched with `flags` / `perm_shift` (launch_rowT_dir)
+int tap_order(const msl_handle::OpDir& o, int flags, int perm_shift, int* rp) {
+    *rp = 8 << perm_shift;
+    if (!(flags & P2_OUT_PAIRED) || o.mixed || o.generic) return TAP_NATURAL;
+    if (o.wave2k) return TAP_PAIRED;
+    if (!(o.two || (o.R && !o.breg && !o.breg2 && !o.breg4))) return TAP_NATURAL;
+    return TAP_INTERLEAVED;
 }
 
 // ---- one-pass-per-slice path ------------------------------------------------------------------------
@@ -893,7 +968,7 @@ int slice_loop_onepass_b(msl_handle* h, int fused_slot, int groups, int first_gr
     const long long isA = (long long)c.nx * h->pitch, isB = (long long)c.ny * h->pitchT;
     const bool fused = fused_slot >= 0;
     int rc;
-    if ((rc = begin_timed(h, nz + 4))) return rc;
+    if ((rc = begin_timed(h, nz + 4 + (fused ? TAP_MAX_LAUNCHES * n_taps(h) : 0)))) return rc;
     for (int k = 0; k < nz; ++k) {
         RowTJob j{};
         j.flags = (k > 0 ? P2_PRE_A : 0) | (k < nz - 1 ? P2_POST_A : 0);
@@ -920,6 +995,11 @@ int slice_loop_onepass_b(msl_handle* h, int fused_slot, int groups, int first_gr
             rc = launch_rowT_dir(h, h->opx, j, K_COL);
         }
         if (rc) return rc;
+        if (k < nz - 1) {
+            int rp = 0;
+            const int order = tap_order((k & 1) ? h->opx : h->opy, j.flags, j.perm_shift, &rp);
+            if ((rc = layer_tap(h, k, fused_slot, groups, (k & 1) ? h->psi : h->psiT, !(k & 1), order, rp, (k & 1) ? 1 : 0))) return rc;
+        }
     }
     if (nz & 1) {
         dim3 grid((c.nx + 31) / 32, (c.ny + 31) / 32, P);
@@ -976,7 +1056,7 @@ int slice_loop_onepass(msl_handle* h, int fused_slot, int groups, int first_grou
     int rc;
     if (nz == 1)
         HIPCHK(h, hipMemcpyAsync(h->psi, h->psi0, (size_t)P * isA * sizeof(float2), hipMemcpyDeviceToDevice, h->stream));
-    if ((rc = begin_timed(h, nz + 2))) return rc;
+    if ((rc = begin_timed(h, nz + 2 + (fused ? TAP_MAX_LAUNCHES * n_taps(h) : 0)))) return rc;
     for (int k = 0; k < nz; ++k) {
         const bool last = (k == nz - 1);
         int flags = (k > 0 ? P2_PRE_A : 0) | (!last ? P2_POST_A : 0) | ((last && fused) ? P2_POST_F : 0);
@@ -1010,6 +1090,8 @@ int slice_loop_onepass(msl_handle* h, int fused_slot, int groups, int first_grou
             rc = h->Rx == 32 ? launch_rowT_r<32>(h, j, K_COL) : launch_rowT_r<16>(h, j, K_COL);
         }
         if (rc) return rc;
+        const int order = (j.flags & P2_OUT_PAIRED) ? TAP_INTERLEAVED : TAP_NATURAL;
+        if ((rc = layer_tap(h, k, fused_slot, groups, along_y ? h->psiT : h->psi, along_y, order, 8 << j.perm_shift, along_y ? 0 : 1))) return rc;
     }
     if (fused && (rc = epilogue_x_pass(h, fused_slot, groups))) return rc;
     h->cur = nullptr;
@@ -1046,9 +1128,9 @@ int slice_loop(msl_handle* h, int fused_slot, int groups, int first_group) {
     const size_t npix = (size_t)c.nx * c.ny;
     const size_t toff = (size_t)first_group * c.nz * npix;
     HIPCHK(h, hipMemcpyAsync(h->psi, h->psi0, (size_t)P * c.nx * h->pitch * sizeof(float2), hipMemcpyDeviceToDevice, h->stream));
-    int rc = begin_timed(h, 2 * nz + 2);
-    if (rc) return rc;
     const bool fused = fused_slot >= 0;
+    int rc = begin_timed(h, 2 * nz + 2 + (fused ? TAP_MAX_LAUNCHES * n_taps(h) : 0));
+    if (rc) return rc;
     for (int z = 0; z < nz; ++z) {
         const bool last = (z == nz - 1);
         if (h->Ry) {
@@ -1066,6 +1148,7 @@ int slice_loop(msl_handle* h, int fused_slot, int groups, int first_group) {
             else if (fused) { r.fft2 = +1; }
             if ((rc = launch_lines(h, h->plan_y, r, K_ROW))) return rc;
         }
+        if (!last && (rc = layer_tap(h, z, fused_slot, groups, h->psi, false, TAP_NATURAL, 8, 2))) return rc;
         if (!last) {
             if (h->Rx) {
                 ColJob k = col_job(h, h->psi, h->psi, P, h->pitch, h->pitch);
@@ -1108,6 +1191,21 @@ int fill_propagator(msl_handle* h) {
     int rc = fill(h->pxt, c.nx, c.dx);
     if (rc) return rc;
     if ((rc = fill(h->pyt, c.ny, c.dy))) return rc;
+    // the layer tap's conj(P), unscaled: exp(+i pi lambda dz k^2)
+    auto fill_conj = [&](float2* dst, int n, double d) -> int {
+        std::vector<float2> v(n);
+        for (int m = 0; m < n; ++m) {
+            const int f = (m < (n + 1) / 2) ? m : m - n;
+            const double k = f * (1.0 / (n * d));
+            const double ph = M_PI * c.wavelength * c.dz * k * k;
+            v[m] = make_float2((float)cos(ph), (float)sin(ph));
+        }
+        HIPCHK(h, hipMemcpyAsync(dst, v.data(), n * sizeof(float2), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        return MSL_OK;
+    };
+    if ((rc = fill_conj(h->tap_cx, c.nx, c.dx))) return rc;
+    if ((rc = fill_conj(h->tap_cy, c.ny, c.dy))) return rc;
     // split-order copies for the 2R^2 kernels: entry [b*R^2 + k] = P[2k + b]
     auto fill_split = [&](float2* dst, int n, double d) -> int {
         if (!dst) return MSL_OK;
@@ -1534,6 +1632,8 @@ int msl_create(const msl_config* cfg, msl_handle** out) {
     }
     if ((rc = dalloc(h, &h->pxt, (size_t)cfg->nx))) return bail(rc);
     if ((rc = dalloc(h, &h->pyt, (size_t)cfg->ny))) return bail(rc);
+    if ((rc = dalloc(h, &h->tap_cx, (size_t)cfg->nx))) return bail(rc);
+    if ((rc = dalloc(h, &h->tap_cy, (size_t)cfg->ny))) return bail(rc);
     if ((rc = dalloc(h, &h->d_lo, (size_t)cfg->nz))) return bail(rc);
     if ((rc = dalloc(h, &h->d_hi, (size_t)cfg->nz))) return bail(rc);
     if ((rc = dalloc(h, &h->d_abcd, (size_t)103 * 12))) return bail(rc);
@@ -1551,7 +1651,8 @@ int msl_destroy(msl_handle* h) {
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     for (auto& s : h->ring) for (auto e : s.ev) (void)hipEventDestroy(e);
     for (auto& st : h->stage) { if (st.ev) (void)hipEventDestroy(st.ev); if (st.buf) (void)hipHostFree(st.buf); }
-    void* bufs[] = {h->psi0, h->psi, h->trans, h->V, h->wf, h->intensity, h->pxt, h->pyt, h->d_abcd, h->d_lo, h->d_hi,
+    if (h->layers) { (void)hipFree(h->layers); h->layers = nullptr; h->wf = nullptr; }      // (wf is its last block)
+    void* bufs[] = {h->psi0, h->psi, h->trans, h->V, h->wf, h->intensity, h->pxt, h->pyt, h->tap, h->tap_cx, h->tap_cy, h->d_abcd, h->d_lo, h->d_hi,
                     h->d_pos, h->d_Z, h->d_key, h->d_order, h->d_u1, h->d_u2, h->d_ex, h->d_ey, h->d_counts, h->d_start,
                     h->d_z2s, h->d_species, h->d_ff, h->d_xy, h->plan_x.tw, h->plan_y.tw, h->plan_t.tw, h->tw4_x, h->tw4_y,
                     h->scratch, h->psiT, h->psi0T, h->transT, h->bin_stage, h->st_acc, h->st_s1, h->st_s2, h->st_tw, h->st_bins, h->st_ref, h->opx.tw2, h->opx.ptab, h->opy.tw2, h->opy.ptab,
@@ -2388,13 +2489,14 @@ size_t msl_buffer_bytes(const msl_handle* h, msl_buffer what) {
         case MSL_BUF_STREAM_S1: return (h->st_open && h->st_s1) ? h->wpix * c.n_probes * 16 : 0;
         case MSL_BUF_STREAM_S2: return (h->st_open && h->st_s2) ? h->wpix * c.n_probes * 8 : 0;
         case MSL_BUF_STREAM_REF: return (h->st_open && h->st_have_ref) ? h->wpix * c.n_probes * 8 : 0;
+        case MSL_BUF_LAYERS: return h->wf ? (n_taps(h) + 1) * layer_block_elems(h) * 8 : 0;
     }
     return 0;
 }
 
 int64_t msl_result_pitch(const msl_handle* h, msl_buffer what) {
     if (!h) return 0;
-    if (what == MSL_BUF_WAVEFUNCTION) return h->wf ? (int64_t)h->wpitch : 0;
+    if (what == MSL_BUF_WAVEFUNCTION || what == MSL_BUF_LAYERS) return h->wf ? (int64_t)h->wpitch : 0;
     if (what == MSL_BUF_INTENSITY) return h->intensity ? (int64_t)h->intensity_ld : 0;
     return 0;
 }
@@ -2413,6 +2515,7 @@ void* msl_device_ptr(msl_handle* h, msl_buffer what) {
         case MSL_BUF_STREAM_S1: return h->st_open ? h->st_s1 : nullptr;
         case MSL_BUF_STREAM_S2: return h->st_open ? h->st_s2 : nullptr;
         case MSL_BUF_STREAM_REF: return (h->st_open && h->st_have_ref) ? h->st_ref : nullptr;
+        case MSL_BUF_LAYERS: return h->layers ? h->layers : h->wf;
     }
     return nullptr;
 }
@@ -2603,6 +2706,16 @@ int msl_download(msl_handle* h, msl_buffer what, void* dst, size_t bytes, int64_
     size_t off = 0, len = total;
     if (count > 0 && what != MSL_BUF_WAVEFUNCTION && what != MSL_BUF_INTENSITY)
         return fail(h, MSL_ERR_INVALID, "msl_download: ranges only for wavefunction/intensity");
+    if (what == MSL_BUF_LAYERS) {
+        // (L, P, T, wpitch) on the device -> dense (L, P, T, wx*wy) on the host
+        const size_t rows = total / sizeof(float2) / h->wpitch;
+        len = rows * h->wpix * sizeof(float2);
+        if (bytes != len) return fail(h, MSL_ERR_INVALID, "msl_download: dst holds %zu bytes, buffer is %zu", bytes, len);
+        HIPCHK(h, hipMemcpy2DAsync(dst, h->wpix * sizeof(float2), src, h->wpitch * sizeof(float2), h->wpix * sizeof(float2), rows,
+                                   hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        return MSL_OK;
+    }
     if (what == MSL_BUF_WAVEFUNCTION || what == MSL_BUF_INTENSITY) {
         // (P, rows, ld) on the device -> dense (P, rows, wx*wy) on the host
         const size_t es = what == MSL_BUF_WAVEFUNCTION ? sizeof(float2) : sizeof(float);
@@ -2690,6 +2803,99 @@ int msl_download_wavefunction_c128(msl_handle* h, int32_t n_frames_used, void* d
         }
     }
     return MSL_OK;
+}
+
+int msl_set_layers(msl_handle* h, const int32_t* slices, int32_t n) {
+    if (!h) return fail(h, MSL_ERR_INVALID, "null handle");
+    const msl_config& c = h->cfg;
+    if (n < 0 || (n > 0 && !slices)) return fail(h, MSL_ERR_INVALID, "msl_set_layers: %d slice indices", n);
+    for (int i = 0; i < n; ++i) {
+        if (slices[i] < 0 || slices[i] >= c.nz - 1)
+            return fail(h, MSL_ERR_INVALID, "msl_set_layers: slice %d outside [0, %d) (the exit wave nz - 1 is always the last layer)", slices[i], c.nz - 1);
+        if (i > 0 && slices[i] <= slices[i - 1]) return fail(h, MSL_ERR_INVALID, "msl_set_layers: slice indices must increase strictly");
+    }
+    if (!h->wf) return fail(h, MSL_ERR_STATE, "msl_set_layers: handle created with n_frames == 0");
+    if (h->st_open) return fail(h, MSL_ERR_STATE, "msl_set_layers: a TACAW stream is open");
+    HIPCHK(h, hipSetDevice(c.device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    const size_t block = layer_block_elems(h);
+    const size_t images = (size_t)c.n_probes * h->FB;
+    const size_t tap_elems = n > 0 ? (size_t)c.nx * h->pitch * images : 0;
+    {
+        size_t free_b = 0, total_b = 0;
+        HIPCHK(h, hipMemGetInfo(&free_b, &total_b));
+        const size_t have = free_b + block * 8 * (n_taps(h) + 1) + (h->tap ? (size_t)c.nx * h->pitch * images * 8 : 0);
+        const size_t need = block * 8 * (n + 1) + tap_elems * 8;
+        if (need > have)
+            return fail(h, MSL_ERR_NOMEM, "msl_set_layers: %d layers need %zu bytes, the device has %zu", n + 1, need, have);
+    }
+    // the old result goes first: at full size two of them would not fit
+    if (h->layers) { (void)hipFree(h->layers); h->layers = nullptr; } else if (h->wf) { (void)hipFree(h->wf); }
+    h->wf = nullptr;
+    h->layer_slices.clear(); h->layer_block.clear();
+    int rc = dalloc(h, &h->tap, tap_elems);
+    if (!rc) rc = dalloc(h, n > 0 ? &h->layers : &h->wf, block * (n + 1));
+    if (rc) {                                                   // back to a single-layer result, if that still fits
+        (void)dalloc(h, &h->tap, 0);
+        h->layers = nullptr;
+        if (dalloc(h, &h->wf, block) == MSL_OK) (void)hipMemsetAsync(h->wf, 0, block * sizeof(float2), h->stream);
+        return fail(h, MSL_ERR_NOMEM, "msl_set_layers: %d layers of %zu bytes do not fit", n + 1, block * 8);
+    }
+    if (n > 0) {
+        h->wf = h->layers + (size_t)n * block;
+        h->layer_slices.assign(slices, slices + n);
+        h->layer_block.assign(c.nz, -1);
+        for (int i = 0; i < n; ++i) h->layer_block[slices[i]] = i;
+    }
+    HIPCHK(h, hipMemsetAsync(n > 0 ? h->layers : h->wf, 0, block * (n + 1) * sizeof(float2), h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return MSL_OK;
+}
+
+int msl_download_layers_c128(msl_handle* h, int32_t n_frames_used, void* dst, size_t bytes) {
+    if (!h || !dst) return fail(h, MSL_ERR_INVALID, "msl_download_layers_c128: null argument");
+    const msl_config& c = h->cfg;
+    if (!h->wf) return fail(h, MSL_ERR_STATE, "msl_download_layers_c128: no wavefunction buffer");
+    if (n_frames_used < 1 || n_frames_used > c.n_frames) return fail(h, MSL_ERR_INVALID, "msl_download_layers_c128: %d of %d frames", n_frames_used, c.n_frames);
+    const int L = n_taps(h) + 1;
+    const size_t per_probe = (size_t)n_frames_used * h->wpix;             // dense (T_used, wx*wy) offsets of a probe, L values each
+    if (bytes != (size_t)c.n_probes * per_probe * L * sizeof(double2))
+        return fail(h, MSL_ERR_INVALID, "msl_download_layers_c128: dst holds %zu bytes, the result has %zu", bytes, (size_t)c.n_probes * per_probe * L * sizeof(double2));
+    HIPCHK(h, hipSetDevice(c.device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    const float2* base = h->layers ? h->layers : h->wf;
+    const size_t block = layer_block_elems(h);
+    // chunks of at most 256 MB of complex128 through the scratch buffer, as msl_download_wavefunction_c128
+    size_t chunk = std::max<size_t>(1, std::min<size_t>(per_probe, (size_t)(256u << 20) / sizeof(double2) / L));
+    if (const char* e = dbg_env("MSL_C128_CHUNK")) chunk = std::max<size_t>(1, std::min<size_t>(chunk, (size_t)atoll(e)));
+    int rc = ensure_scratch(h, chunk * L * sizeof(double2));
+    if (rc) return rc;
+    for (int p = 0; p < c.n_probes; ++p) {
+        double2* out = (double2*)dst + (size_t)p * per_probe * L;
+        for (size_t o = 0; o < per_probe; o += chunk) {
+            const size_t n = std::min(chunk, per_probe - o);
+            const int grid = (int)std::min<size_t>((n * L + 255) / 256, (size_t)h->n_cus * 8);
+            hipLaunchKernelGGL(layer_tap_c128_kernel, dim3(grid), dim3(256), 0, h->stream, base, (double2*)h->scratch, (long long)o, (long long)n, L,
+                               (long long)block, (long long)p * c.n_frames * h->wpitch, (long long)h->wpix, (long long)h->wpitch);
+            HIPCHK(h, hipGetLastError());
+            HIPCHK(h, hipMemcpyAsync(out + o * L, h->scratch, n * L * sizeof(double2), hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(h, hipStreamSynchronize(h->stream));
+        }
+    }
+    return MSL_OK;
+}
+
+int msl_tacaw_layer(msl_handle* h, int32_t layer) {
+    if (!h) return fail(h, MSL_ERR_INVALID, "null handle");
+    if (!h->wf) return fail(h, MSL_ERR_STATE, "msl_tacaw_layer: no wavefunction buffer");
+    const int L = n_taps(h) + 1;
+    if (layer < 0 || layer >= L) return fail(h, MSL_ERR_INVALID, "msl_tacaw_layer: layer %d outside [0, %d)", layer, L);
+    if (layer == L - 1) return msl_tacaw(h, nullptr, nullptr, 0, 0, 0);
+    float2* exit_block = h->wf;
+    h->wf = h->layers + (size_t)layer * layer_block_elems(h);         // msl_tacaw(NULL ..) on that block
+    const int rc = msl_tacaw(h, nullptr, nullptr, 0, 0, 0);
+    h->wf = exit_block;
+    return rc;
 }
 
 int msl_download_frame(msl_handle* h, int32_t slot, void* dst, size_t bytes) { return frame_copy(h, slot, dst, bytes, true); }

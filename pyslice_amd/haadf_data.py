@@ -34,8 +34,8 @@ class HAADFData(WFData):
         radius = (collection_angle * 1e-3) / self.probe.wavelength
         mask = (q > radius)
         eng = self.__dict__.get("_engine")
-        if eng is not None and self.__dict__.get("_resident", False) and len(self.layer) == 1:
-            per_probe = eng.adf(mask)                                  # resident exit waves of run()
+        if eng is not None and self.__dict__.get("_resident", False):
+            per_probe = eng.adf(mask)                                  # resident exit waves of run() (the last layer)
         else:
             if not TORCH_AVAILABLE or not torch.cuda.is_available():
                 raise RuntimeError("HAADFData needs the HIP device (no CPU path in pyslice_amd)")

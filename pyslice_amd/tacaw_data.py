@@ -43,15 +43,18 @@ class TACAWData(WFData):
         self.frequencies = np.fft.fftshift(np.fft.fftfreq(n_freq, d=dt))
 
         eng = self.__dict__.get("_engine")
-        resident = eng is not None and self.__dict__.get("_resident", False) and len(self.layer) == 1
+        resident = eng is not None and self.__dict__.get("_resident", False)      # every layer of run()'s result is on the device
         shard = self.__dict__.get("_frame_shard")
-        if shard is not None and eng is not None and len(self.layer) == 1:
+        if shard is not None and eng is not None:
             # multi-process run with frame-sharded exit waves still on the devices (gather="none"):
             # all-to-all to probe shards, local time FFT, gather of the intensities on rank 0
             self.intensity = self._tacaw_sharded(eng, shard)
             return
         if resident:
-            eng.tacaw()
+            if eng.n_layers > 1:
+                eng.tacaw_layer(layer_index)                # thickness series: that layer's block of the resident result
+            else:
+                eng.tacaw()
             self._intensity_src = (eng, None)          # reductions read the library's own buffer
             if self.__dict__.get("_output") == "device":
                 self.intensity = torch.as_tensor(eng.result_view(_native.BUF_INTENSITY, "<f4"), device=f"cuda:{eng.device}")
