@@ -41,6 +41,22 @@ struct FftPlan {
 
 enum LaunchKind { K_ROW = 0, K_COL = 1, K_OTHER = 2, K_NKINDS = 3 };
 
+// What the slice loop runs along one axis (plan_axis_kind), and the tables of msl_handle::OpDir each kind reads:
+//   AX_FOURSTEP  R^2 = 256 / 1024 points, the four-step register kernel (tw4_x / tw4_y)
+//   AX_TWO       2 R^2 = 512 points (tw = the R^2 table, tw2 = W_512^m, ptab = the split-order Fresnel table)
+//   AX_WAVE2K    2048 points, one wave per line (tw = T[k1*64+n2], tw2 = W_64)
+//   AX_MIXED     smooth length A * B or 2 A * B on rowTM_pass_kernel (mtw = its two twiddle tables)
+//   AX_CONV      any length <= R^2/2: the propagation as a zero-padded cyclic convolution on the R^2 register FFTs (filter qf, cz)
+//   AX_CONV2K    513..1024 points: the same on the wave-per-line 2048-point FFT (filter qf, cz)
+//   AX_CONV4K    1025..2047 points: cyclic convolution of length 4096 (tw, tw2 as AX_WAVE2K, bw = W_4096^i, qf in rowTC2's split order)
+//   AX_GENERIC   the generic LDS kernel with a transposing store
+enum AxisKind { AX_NONE, AX_FOURSTEP, AX_TWO, AX_WAVE2K, AX_MIXED, AX_CONV, AX_CONV2K, AX_CONV4K, AX_GENERIC };
+
+// Chirp-z tables of n points on a register FFT of length M: R = 16 / 32 (M = R^2, tw = make_tw4's table) or 64 (the wave-per-line
+// 2048-point FFT: tw = T[k1*64+n2], tw2 = W_64), chirp bw (M/2 entries) and its filter bf (M/2 + 2), made by make_cz_tables.  The
+// convolution passes of the slice loop, the potential's inverse transform (ifftTB_kernel / ifftTB2_kernel) and time_cz_kernel read them.
+struct CzTables { int R = 0; float2* tw = nullptr; float2* tw2 = nullptr; float2* bf = nullptr; float2* bw = nullptr; };
+
 struct EventSet {
     std::vector<hipEvent_t> ev;
     std::vector<int> kind;      // kind[i] = kind of the launch between ev[i] and ev[i+1]
@@ -79,16 +95,14 @@ struct msl_handle {
     size_t scratch_bytes = 0;
     bool onepass = false;
     bool scheme_b = false;         // a direction of 2R^2 points: every pass transposes, first pass along y, final transpose if nz is odd
-    // one-pass kernel per direction: R^2 register kernel, 2 R^2 (two) register kernel with its tables, or the generic LDS kernel
-    // (breg: any length <= R^2/2 by Bluestein's chirp-z on the R^2 register FFTs, with its filter bf and chirp bw)
-    // (breg2: lengths 513..1024 by the same scheme on the wave-per-line 2048-point FFT; tw = T[k1*64+n2], tw2 = W_64 table)
-    struct OpDir { int R = 0; bool two = false; bool generic = false; bool mixed = false; float2* mtw = nullptr;   // mixed: smooth length A * B on rowTM_pass_kernel, mtw = its two twiddle tables
-         bool breg = false; bool breg2 = false; bool breg4 = false; bool wave2k = false; float2* tw = nullptr; float2* tw2 = nullptr; float2* qf = nullptr;
-        // chirp-z tables of an axis whose slice-loop kernel is not a chirp / convolution kernel (a power of two next to another length):
-        // only the potential's inverse transform uses them (ifftTB_kernel / ifftTB2_kernel).  cz_R: 16 / 32 (M = R^2) or 64 (the 2048-point wave FFT)
-        int cz_R = 0; float2* cz_tw = nullptr; float2* cz_tw2 = nullptr; float2* cz_bf = nullptr; float2* cz_bw = nullptr;
-                   float2* ptab = nullptr; float2* bf = nullptr; float2* bw = nullptr; } opx, opy;
-    OpDir opt;                     // chirp-z tables of the TACAW time axis (cz_* only), made for opt_T frames (time_cz_kernel)
+    // one-pass kernel of one axis (AxisKind) and its tables: n = line length, R = radix of the base kind's register FFT (0: none).
+    // `base` is the kind the axis has without the mixed-radix pass (== kind otherwise): a MIXED axis keeps the tables of its base
+    // kind, on which the potential's inverse transform, the probes and the exit FFT still run, and the loop is one-pass iff both
+    // bases are not AX_NONE.  cz: the chirp-z tables of a CONV / CONV2K base, or of an axis of 33..1024 points next to one (only the
+    // potential's inverse transform uses those).  Every table is owned by the OpDir.
+    struct OpDir { AxisKind kind = AX_NONE, base = AX_NONE; int n = 0; int R = 0; float2* mtw = nullptr; float2* tw = nullptr; float2* tw2 = nullptr;
+                   float2* qf = nullptr; float2* bw = nullptr; float2* ptab = nullptr; CzTables cz; } opx, opy;
+    CzTables opt;                  // chirp-z tables of the TACAW time axis, made for opt_T frames (time_cz_kernel)
     int opt_T = 0;
     float2* tsplit_tw = nullptr;   // W_T^n, n < T: cross-wave butterflies of time_split_kernel, made for tsplit_T frames
     int tsplit_T = 0;
@@ -229,6 +243,20 @@ void host_fft_pow2(std::vector<double>& re, std::vector<double>& im) {
     }
 }
 
+// Bluestein's chirp of n points, w[i] = exp(-i pi i^2 / n) (w holds n or more entries, the rest untouched), and its filter: the FFT of
+// length M (a power of two >= 2n - 1) of the conjugate chirp wrapped to negative lags, unscaled, in (fr, fi)
+void host_chirp(int n, int M, std::vector<float2>& w, std::vector<double>& fr, std::vector<double>& fi) {
+    fr.assign(M, 0.0); fi.assign(M, 0.0);
+    for (int i = 0; i < n; ++i) {
+        const long long q = ((long long)i * i) % (2LL * n);
+        const double a = -M_PI * (double)q / (double)n;
+        w[i] = make_float2((float)cos(a), (float)sin(a));
+        fr[i] = cos(a); fi[i] = -sin(a);
+        if (i) { fr[M - i] = fr[i]; fi[M - i] = fi[i]; }
+    }
+    host_fft_pow2(fr, fi);
+}
+
 int make_plan(msl_handle* h, FftPlan& pl, int N) {
     if (pl.ok && pl.N == N) return MSL_OK;
     pl.ok = false;
@@ -259,15 +287,8 @@ int make_plan(msl_handle* h, FftPlan& pl, int N) {
     HIPCHK(h, hipStreamSynchronize(h->stream));
     if (!native) {
         std::vector<float2> chirp(N);
-        std::vector<double> br(M, 0.0), bi(M, 0.0);
-        for (int n = 0; n < N; ++n) {
-            const long long q = ((long long)n * n) % (2LL * N);
-            const double a = -M_PI * (double)q / (double)N;
-            chirp[n] = make_float2((float)cos(a), (float)sin(a));
-            br[n] = cos(a); bi[n] = -sin(a);                 // conj chirp
-            if (n) { br[M - n] = br[n]; bi[M - n] = bi[n]; }
-        }
-        host_fft_pow2(br, bi);
+        std::vector<double> br, bi;
+        host_chirp(N, M, chirp, br, bi);
         std::vector<float2> bf(M);
         for (int j = 0; j < M; ++j) bf[j] = make_float2((float)(br[j] / M), (float)(bi[j] / M));
         if ((rc = dalloc(h, &pl.chirp, (size_t)N))) return rc;
@@ -467,56 +488,52 @@ int choose_pchunk(long long line_blocks, int n_images, long long slots, int t_gr
     return best;
 }
 
+// Persistent grid of a chunked row kernel over `line_blocks` work items per image chunk on `slots` workgroups: sets job.pchunk
+// (choose_pchunk, or the MSL_ROW_PCHUNK override kept inside one frame) and returns the grid
+template <typename Job>
+int chunked_grid(const msl_handle* h, Job& job, long long line_blocks, long long slots) {
+    int pc = choose_pchunk(line_blocks, job.n_images, slots, job.t_group);
+    if (h->row_pchunk > 0) { pc = std::min(h->row_pchunk, job.n_images); if (job.t_group > 0) while (job.t_group % pc) --pc; }
+    job.pchunk = pc;
+    const long long items = line_blocks * ((job.n_images + pc - 1) / pc);
+    return (int)std::min<long long>(items, slots);
+}
+
+// frame batching: the images of a launch are frame-of-batch * n_probes + probe, each frame with its own transmission stack
+template <typename Job>
+void set_frame_groups(const msl_handle* h, Job& j, int groups) {
+    const msl_config& c = h->cfg;
+    if (groups > 1) { j.t_group = c.n_probes; j.t_magic = (unsigned)((1ull << 32) / (unsigned)c.n_probes + 1); j.t_stride = (long long)c.nz * c.nx * c.ny; }
+}
+
+// counters after a slice loop of P images: `bytes` per pixel and slice-step, plus the transmission reads and the fused epilogue
+void count_slice_loop(msl_handle* h, int P, int groups, bool fused, uint64_t bytes) {
+    const msl_config& c = h->cfg;
+    const size_t npix = (size_t)c.nx * c.ny;
+    h->cur = nullptr;
+    h->ctr.slice_steps += (uint64_t)P * c.nz;
+    h->ctr.frames += groups;
+    h->ctr.algorithmic_bytes += (uint64_t)P * c.nz * bytes * npix + (uint64_t)groups * c.nz * 8ull * npix + (fused ? (uint64_t)P * 16ull * npix : 0ull);
+}
+
 // ---- four-step fast path ------------------------------------------------------------------------
 int fast_radix(int n) { return n == 1024 ? 32 : (n == 256 ? 16 : 0); }
 
-int make_tw4(msl_handle* h, float2** dst, int R);
-
-// chirp-z tables for inverse transforms of n points (33 <= n <= 1024) on the register FFTs, see OpDir::cz_*
-int make_cz_tables(msl_handle* h, msl_handle::OpDir& o, int n) {
-    const bool wave = n > 512;
-    const int R = wave ? 32 : (n <= 128 ? 16 : 32), M = wave ? 2048 : R * R, NH = M / 2;
-    int r;
-    if (wave) {
-        std::vector<float2> T(M), W(64);
-        for (int k1 = 0; k1 < 32; ++k1)
-            for (int n2 = 0; n2 < 64; ++n2) {
-                const double a = -2.0 * M_PI * (double)(k1 * n2) / (double)M;
-                T[k1 * 64 + n2] = make_float2((float)cos(a), (float)sin(a));
-            }
-        for (int m = 0; m < 32; ++m) {
-            const double a = -2.0 * M_PI * m / 64.0;
-            W[m] = make_float2(1.f, 0.f);
-            W[32 + m] = make_float2((float)cos(a), (float)sin(a));
-        }
-        if ((r = dalloc(h, &o.cz_tw, (size_t)M))) return r;
-        if ((r = dalloc(h, &o.cz_tw2, (size_t)64))) return r;
-        if (hipMemcpy(o.cz_tw, T.data(), M * sizeof(float2), hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(o.cz_tw2, W.data(), 64 * sizeof(float2), hipMemcpyHostToDevice) != hipSuccess)
-            return fail(h, MSL_ERR_HIP, "chirp-z twiddle upload failed (%d points)", n);
-    } else if ((r = make_tw4(h, &o.cz_tw, R))) {
-        return r;
-    }
-    std::vector<float2> bw(NH, make_float2(0.f, 0.f)), bf(NH + 2, make_float2(0.f, 0.f));
-    std::vector<double> cr(M, 0.0), ci(M, 0.0);
-    for (int i = 0; i < n; ++i) {
-        const long long q = ((long long)i * i) % (2LL * n);
-        const double a = -M_PI * (double)q / (double)n;
-        bw[i] = make_float2((float)cos(a), (float)sin(a));
-        cr[i] = cos(a); ci[i] = -sin(a);
-        if (i) { cr[M - i] = cr[i]; ci[M - i] = ci[i]; }
-    }
-    host_fft_pow2(cr, ci);
-    for (int j = 0; j <= NH; ++j) bf[j] = make_float2((float)(cr[j] / M), (float)(ci[j] / M));
-    if ((r = dalloc(h, &o.cz_bw, (size_t)NH))) return r;
-    if ((r = dalloc(h, &o.cz_bf, (size_t)NH + 2))) return r;
-    if (hipMemcpy(o.cz_bw, bw.data(), NH * sizeof(float2), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(o.cz_bf, bf.data(), (NH + 2) * sizeof(float2), hipMemcpyHostToDevice) != hipSuccess)
-        return fail(h, MSL_ERR_HIP, "chirp-z table upload failed (%d points)", n);
-    o.cz_R = wave ? 64 : R;
+// ---- host tables -------------------------------------------------------------------------------------
+// copy a host table into the device buffer dst (allocated by the caller)
+int copy_table(msl_handle* h, float2* dst, const std::vector<float2>& v) {
+    HIPCHK(h, hipMemcpyAsync(dst, v.data(), v.size() * sizeof(float2), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
     return MSL_OK;
 }
 
+// a host table in a device buffer of its own
+int upload(msl_handle* h, float2** dst, const std::vector<float2>& v) {
+    int rc = dalloc(h, dst, v.size());
+    return rc ? rc : copy_table(h, *dst, v);
+}
+
+// twiddles of the four-step R^2-point FFT: t[k1*R + n2] = W_{R^2}^{k1 n2}
 int make_tw4(msl_handle* h, float2** dst, int R) {
     const int N = R * R;
     std::vector<float2> t(N);
@@ -525,10 +542,39 @@ int make_tw4(msl_handle* h, float2** dst, int R) {
             double a = -2.0 * M_PI * (double)((k1 * n2) % N) / (double)N;
             t[k1 * R + n2] = make_float2((float)cos(a), (float)sin(a));
         }
-    int rc = dalloc(h, dst, (size_t)N);
-    if (rc) return rc;
-    HIPCHK(h, hipMemcpyAsync(*dst, t.data(), N * sizeof(float2), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return upload(h, dst, t);
+}
+
+// tables of the wave-per-line 2048-point FFT: T[k1*64+n2] = W_2048^{k1 n2}, and W_64 (even lane of a pair: no twiddle; odd lane: W_64^m)
+int make_wave2k_tables(msl_handle* h, float2** tw, float2** tw2) {
+    constexpr int M = 2048;
+    std::vector<float2> T(M), W(64);
+    for (int k1 = 0; k1 < 32; ++k1)
+        for (int n2 = 0; n2 < 64; ++n2) {
+            const double a = -2.0 * M_PI * (double)(k1 * n2) / (double)M;
+            T[k1 * 64 + n2] = make_float2((float)cos(a), (float)sin(a));
+        }
+    for (int m = 0; m < 32; ++m) {
+        const double a = -2.0 * M_PI * m / 64.0;
+        W[m] = make_float2(1.f, 0.f);
+        W[32 + m] = make_float2((float)cos(a), (float)sin(a));
+    }
+    int rc = upload(h, tw, T);
+    return rc ? rc : upload(h, tw2, W);
+}
+
+// chirp-z tables of n points (CzTables): M = 256 up to 128 points, 1024 up to 512, else the 2048-point wave FFT
+int make_cz_tables(msl_handle* h, CzTables& o, int n) {
+    const bool wave = n > 512;
+    const int R = wave ? 32 : (n <= 128 ? 16 : 32), M = wave ? 2048 : R * R, NH = M / 2;
+    int r = wave ? make_wave2k_tables(h, &o.tw, &o.tw2) : make_tw4(h, &o.tw, R);
+    if (r) return r;
+    std::vector<float2> bw(NH, make_float2(0.f, 0.f)), bf(NH + 2, make_float2(0.f, 0.f));
+    std::vector<double> cr, ci;
+    host_chirp(n, M, bw, cr, ci);
+    for (int j = 0; j <= NH; ++j) bf[j] = make_float2((float)(cr[j] / M), (float)(ci[j] / M));
+    if ((r = upload(h, &o.bw, bw)) || (r = upload(h, &o.bf, bf))) return r;
+    o.R = wave ? 64 : R;
     return MSL_OK;
 }
 
@@ -722,13 +768,15 @@ int layer_tap(msl_handle* h, int k, int slot, int groups, const float2* buf, boo
     return MSL_OK;
 }
 
+// only the 256 / 512 / 1024-point kernels read and write the interleaved line order (16-byte loads in the reader) between two passes
+bool interleaves(const msl_handle::OpDir& o) { return o.kind == AX_FOURSTEP || o.kind == AX_TWO; }
+
 // line order of the output of a transposing pass of direction `o` launched with `flags` / `perm_shift` (launch_rowT_dir)
 int tap_order(const msl_handle::OpDir& o, int flags, int perm_shift, int* rp) {
     *rp = 8 << perm_shift;
-    if (!(flags & P2_OUT_PAIRED) || o.mixed || o.generic) return TAP_NATURAL;
-    if (o.wave2k) return TAP_PAIRED;
-    if (!(o.two || (o.R && !o.breg && !o.breg2 && !o.breg4))) return TAP_NATURAL;
-    return TAP_INTERLEAVED;
+    if (!(flags & P2_OUT_PAIRED)) return TAP_NATURAL;
+    if (o.kind == AX_WAVE2K) return TAP_PAIRED;
+    return interleaves(o) ? TAP_INTERLEAVED : TAP_NATURAL;
 }
 
 // ---- one-pass-per-slice path ------------------------------------------------------------------------
@@ -780,16 +828,19 @@ int launch_rowT_r(msl_handle* h, RowTJob job, int kind) {
     // R = 32: ~235 VGPRs, 152 KB -> one workgroup per CU; R = 16: 138 VGPRs, 41 KB -> three
     const int cap = (R == 16) ? 3 : 2;
     const int per_cu = std::max(1, std::min(cap, (int)((size_t)h->lds_limit / lds)));
-    const long long slots = (long long)h->n_cus * per_cu;
-    const long long lb = job.n_lines / LINES;
-    int pc = choose_pchunk(lb, job.n_images, slots, job.t_group);
-    if (h->row_pchunk > 0) { pc = std::min(h->row_pchunk, job.n_images); if (job.t_group > 0) while (job.t_group % pc) --pc; }
-    job.pchunk = pc;
-    const long long items = lb * ((job.n_images + pc - 1) / pc);
-    const int grid = (int)std::min<long long>(items, slots);
+    const int grid = chunked_grid(h, job, job.n_lines / LINES, (long long)h->n_cus * per_cu);
     if (!rowT_launch(R, job, grid, (size_t)h->lds_limit, h->stream)) return fail(h, MSL_ERR_STATE, "transposing pass: no kernel for flags %d", job.flags);
     HIPCHK(h, hipGetLastError());
     return mark_launch(h, kind);
+}
+
+// the paired-lines flags of a job as the template arguments <IN_P, OUT_P> of `launch`
+template <typename F>
+int paired_dispatch(const RowTJob& job, F&& launch) {
+    using T = std::true_type; using N = std::false_type;
+    const bool in_p = job.flags & P2_IN_PAIRED, out_p = job.flags & P2_OUT_PAIRED;
+    if (in_p) return out_p ? launch(T{}, T{}) : launch(T{}, N{});
+    return out_p ? launch(N{}, T{}) : launch(N{}, N{});
 }
 
 // lines of 2 R^2 = 512 points
@@ -798,22 +849,11 @@ int launch_rowT2_io(msl_handle* h, RowTJob job, int kind) {
     constexpr int R = 16, N2 = R * R, N = 2 * N2;
     const size_t lds = ((size_t)2 * N2 + N + (size_t)16 * (N + 2)) * 8;
     const int per_cu = std::max(1, std::min(2, (int)((size_t)h->lds_limit / lds)));
-    const long long slots = (long long)h->n_cus * per_cu;
-    const long long lb = job.n_lines / 16;
-    int pc = choose_pchunk(lb, job.n_images, slots, job.t_group);
-    if (h->row_pchunk > 0) { pc = std::min(h->row_pchunk, job.n_images); if (job.t_group > 0) while (job.t_group % pc) --pc; }
-    job.pchunk = pc;
-    const long long items = lb * ((job.n_images + pc - 1) / pc);
-    const int grid = (int)std::min<long long>(items, slots);
+    const int grid = chunked_grid(h, job, job.n_lines / 16, (long long)h->n_cus * per_cu);
     (void)hipFuncSetAttribute((const void*)rowT2_pass_kernel<R, IN_P, OUT_P>, hipFuncAttributeMaxDynamicSharedMemorySize, h->lds_limit);
     hipLaunchKernelGGL((rowT2_pass_kernel<R, IN_P, OUT_P>), dim3(grid), dim3(16 * R), lds, h->stream, job);
     HIPCHK(h, hipGetLastError());
     return mark_launch(h, kind);
-}
-int launch_rowT2(msl_handle* h, const RowTJob& job, int kind) {
-    const bool in_p = job.flags & P2_IN_PAIRED, out_p = job.flags & P2_OUT_PAIRED;
-    if (in_p) return out_p ? launch_rowT2_io<true, true>(h, job, kind) : launch_rowT2_io<true, false>(h, job, kind);
-    return out_p ? launch_rowT2_io<false, true>(h, job, kind) : launch_rowT2_io<false, false>(h, job, kind);
 }
 
 // lines of any length <= R^2/2: zero-padded cyclic convolution on the register FFTs
@@ -822,13 +862,7 @@ int launch_rowTB_r(msl_handle* h, RowTJob job, int kind) {
     constexpr int M = R * R, NH = M / 2, CS = R * (R + 1) + 2;
     const size_t lds = ((size_t)M + NH + 2 + (size_t)16 * CS) * 8;
     const int per_cu = std::max(1, std::min(R == 16 ? 4 : 1, (int)((size_t)h->lds_limit / lds)));
-    const long long slots = (long long)h->n_cus * per_cu;
-    const long long lb = (job.n_lines + 15) / 16;
-    int pc = choose_pchunk(lb, job.n_images, slots, job.t_group);
-    if (h->row_pchunk > 0) { pc = std::min(h->row_pchunk, job.n_images); if (job.t_group > 0) while (job.t_group % pc) --pc; }
-    job.pchunk = pc;
-    const long long items = lb * ((job.n_images + pc - 1) / pc);
-    const int grid = (int)std::min<long long>(items, slots);
+    const int grid = chunked_grid(h, job, (job.n_lines + 15) / 16, (long long)h->n_cus * per_cu);
     (void)hipFuncSetAttribute((const void*)rowTB_pass_kernel<R>, hipFuncAttributeMaxDynamicSharedMemorySize, h->lds_limit);
     hipLaunchKernelGGL((rowTB_pass_kernel<R>), dim3(grid), dim3(16 * R), lds, h->stream, job);
     HIPCHK(h, hipGetLastError());
@@ -840,13 +874,7 @@ template <bool IN_P, bool OUT_P>
 int launch_rowTB2_io(msl_handle* h, RowTJob job, int kind) {
     constexpr int M = 2048, NH = M / 2, RS = (32 * W2K_PITCH) / 2 + 1;
     const size_t lds = ((size_t)M + 64 + NH + 2 + (size_t)8 * RS) * 8;
-    const long long slots = h->n_cus;
-    const long long lb = (job.n_lines + 7) / 8;
-    int pc = choose_pchunk(lb, job.n_images, slots, job.t_group);
-    if (h->row_pchunk > 0) { pc = std::min(h->row_pchunk, job.n_images); if (job.t_group > 0) while (job.t_group % pc) --pc; }
-    job.pchunk = pc;
-    const long long items = lb * ((job.n_images + pc - 1) / pc);
-    const int grid = (int)std::min<long long>(items, slots);
+    const int grid = chunked_grid(h, job, (job.n_lines + 7) / 8, h->n_cus);
     (void)hipFuncSetAttribute((const void*)rowTB2_pass_kernel<IN_P, OUT_P>, hipFuncAttributeMaxDynamicSharedMemorySize, h->lds_limit);
     hipLaunchKernelGGL((rowTB2_pass_kernel<IN_P, OUT_P>), dim3(grid), dim3(512), lds, h->stream, job);
     HIPCHK(h, hipGetLastError());
@@ -858,53 +886,39 @@ template <bool IN_P, bool OUT_P>
 int launch_rowTW_io(msl_handle* h, RowTJob job, int kind) {
     constexpr int N = 2048;
     const size_t lds = ((size_t)N + 64 + N / 2 + 64 + (size_t)8 * (N + 1)) * 8;
-    const long long slots = h->n_cus;
-    const long long lb = job.n_lines / 8;
-    int pc = choose_pchunk(lb, job.n_images, slots, job.t_group);
-    if (h->row_pchunk > 0) { pc = std::min(h->row_pchunk, job.n_images); if (job.t_group > 0) while (job.t_group % pc) --pc; }
-    job.pchunk = pc;
-    const long long items = lb * ((job.n_images + pc - 1) / pc);
-    const int grid = (int)std::min<long long>(items, slots);
+    const int grid = chunked_grid(h, job, job.n_lines / 8, h->n_cus);
     (void)hipFuncSetAttribute((const void*)rowTW_pass_kernel<IN_P, OUT_P>, hipFuncAttributeMaxDynamicSharedMemorySize, h->lds_limit);
     hipLaunchKernelGGL((rowTW_pass_kernel<IN_P, OUT_P>), dim3(grid), dim3(512), lds, h->stream, job);
     HIPCHK(h, hipGetLastError());
     return mark_launch(h, kind);
 }
-int launch_rowTW(msl_handle* h, const RowTJob& job, int kind) {
-    const bool in_p = job.flags & P2_IN_PAIRED, out_p = job.flags & P2_OUT_PAIRED;
-    if (in_p) return out_p ? launch_rowTW_io<true, true>(h, job, kind) : launch_rowTW_io<true, false>(h, job, kind);
-    return out_p ? launch_rowTW_io<false, true>(h, job, kind) : launch_rowTW_io<false, false>(h, job, kind);
-}
 
 // lines of a smooth length A * B (A, B <= 32; G = 16 / 32 lanes per line) or 2 A * B (G = 64: one wave per line, tiles of 8 lines):
 // direct mixed-radix transform (rowtm_pass.h)
 int launch_rowTM(msl_handle* h, const msl_handle::OpDir& o, RowTJob job, int kind) {
-    const int n = (&o == &h->opx) ? h->cfg.nx : h->cfg.ny;
+    const int n = o.n;
     int A = 0, B = 0, G = 0;
     if (!rowTM_factors(n, &A, &B, &G)) return fail(h, MSL_ERR_STATE, "mixed-radix pass: no kernel for %d points", n);
     const size_t lds = G == 64 ? rowTM2_lds_bytes(A, B) : rowTM_lds_bytes(A, B);
     if (lds > (size_t)h->lds_limit) return fail(h, MSL_ERR_STATE, "mixed-radix pass: %zu bytes of LDS for %d points", lds, n);
     // ~230 VGPRs: two waves per SIMD, i.e. one workgroup of 512 threads or two of 256 per CU
     const int per_cu = std::max(1, std::min(G == 16 ? 2 : 1, (int)((size_t)h->lds_limit / lds)));
-    const long long slots = (long long)h->n_cus * per_cu;
     const int lines = G == 64 ? 8 : 16;
-    const long long lb = (job.n_lines + lines - 1) / lines;
-    int pc = choose_pchunk(lb, job.n_images, slots, job.t_group);
-    if (h->row_pchunk > 0) { pc = std::min(h->row_pchunk, job.n_images); if (job.t_group > 0) while (job.t_group % pc) --pc; }
-    job.pchunk = pc;
-    job.tw = o.mtw; job.flags &= ~(P2_IN_PAIRED | P2_OUT_PAIRED);
-    const long long items = lb * ((job.n_images + pc - 1) / pc);
-    const int grid = (int)std::min<long long>(items, slots);
+    const int grid = chunked_grid(h, job, (job.n_lines + lines - 1) / lines, (long long)h->n_cus * per_cu);
+    job.tw = o.mtw;
     if (!rowTM_launch(n, job, grid, (size_t)h->lds_limit, h->stream)) return fail(h, MSL_ERR_STATE, "mixed-radix pass: no kernel for %d points", n);
     HIPCHK(h, hipGetLastError());
     return mark_launch(h, kind);
 }
 
-// one transposing pass along direction `o`: register kernels for R^2 and 2 R^2 points, else the generic LDS kernel
-// running the same program (fft, x P, ifft, x t, fft, x P, ifft) with a transposing store
+// one transposing pass along direction `o`: the kernel of its kind, running the program (fft, x P, ifft, x t, fft, x P, ifft)
+// with a transposing store
 int launch_rowT_dir(msl_handle* h, const msl_handle::OpDir& o, RowTJob job, int kind) {
-    if (o.mixed) return launch_rowTM(h, o, job, kind);
-    if (o.generic) {
+    if (!interleaves(o) && o.kind != AX_WAVE2K) job.flags &= ~(P2_IN_PAIRED | P2_OUT_PAIRED);
+    switch (o.kind) {
+    case AX_MIXED:
+        return launch_rowTM(h, o, job, kind);
+    case AX_GENERIC: {
         const FftPlan& pl = (&o == &h->opx) ? h->plan_x : h->plan_y;
         LineArgs a;
         a.in = job.in; a.out = job.out;
@@ -928,12 +942,12 @@ int launch_rowT_dir(msl_handle* h, const msl_handle::OpDir& o, RowTJob job, int 
         a.n_steps = n;
         return launch_lines(h, pl, a, kind);
     }
-    job.tw = o.tw;
-    if (o.wave2k) { job.tw2 = o.tw2; return launch_rowTW(h, job, kind); }
-    if (!(o.two || (o.R && !o.breg && !o.breg2 && !o.breg4))) job.flags &= ~(P2_IN_PAIRED | P2_OUT_PAIRED);    // (only the 256 / 512 / 1024-point kernels read and write the interleaved order)
-    if (o.breg4) {                          // 1025 .. 2047 points: cyclic convolution of length 4096, two waves per line
-        job.n_line = (&o == &h->opx) ? h->cfg.nx : h->cfg.ny;
-        job.tw2 = o.tw2; job.bf = o.qf; job.bw = o.bw; job.pl = nullptr;
+    case AX_WAVE2K:
+        job.tw = o.tw; job.tw2 = o.tw2;
+        return paired_dispatch(job, [&](auto in_p, auto out_p) { return launch_rowTW_io<decltype(in_p)::value, decltype(out_p)::value>(h, job, kind); });
+    case AX_CONV4K: {                       // 1025 .. 2047 points: cyclic convolution of length 4096, two waves per line
+        job.n_line = o.n;
+        job.tw = o.tw; job.tw2 = o.tw2; job.bf = o.qf; job.bw = o.bw; job.pl = nullptr;
         constexpr int RS = (32 * W2K_PITCH) / 2 + 1;
         const size_t lds = ((size_t)2048 + 64 + 2048 + 2052 + (size_t)8 * RS) * 8;
         job.pchunk = 1;
@@ -944,17 +958,21 @@ int launch_rowT_dir(msl_handle* h, const msl_handle::OpDir& o, RowTJob job, int 
         HIPCHK(h, hipGetLastError());
         return mark_launch(h, kind);
     }
-    if (o.breg || o.breg2) {                // A as one cyclic convolution of length M (two FFTs); bf = its filter
-        job.n_line = (&o == &h->opx) ? h->cfg.nx : h->cfg.ny;
-        job.pl = nullptr; job.bf = o.qf; job.bw = nullptr;
-        if (o.breg2) { job.tw2 = o.tw2; return launch_rowTB2_io<false, false>(h, job, kind); }
+    case AX_CONV:                           // A as one cyclic convolution of length M (two FFTs); bf = its filter
+    case AX_CONV2K:
+        job.n_line = o.n;
+        job.tw = o.cz.tw; job.pl = nullptr; job.bf = o.qf; job.bw = nullptr;
+        if (o.kind == AX_CONV2K) { job.tw2 = o.cz.tw2; return launch_rowTB2_io<false, false>(h, job, kind); }
         return o.R == 32 ? launch_rowTB_r<32>(h, job, kind) : launch_rowTB_r<16>(h, job, kind);
+    case AX_TWO:
+        job.tw = o.tw; job.tw2 = o.tw2; job.pl = o.ptab;
+        return paired_dispatch(job, [&](auto in_p, auto out_p) { return launch_rowT2_io<decltype(in_p)::value, decltype(out_p)::value>(h, job, kind); });
+    case AX_FOURSTEP:
+        job.tw = (&o == &h->opx) ? h->tw4_x : h->tw4_y;
+        return o.R == 32 ? launch_rowT_r<32>(h, job, kind) : launch_rowT_r<16>(h, job, kind);
+    default:
+        return fail(h, MSL_ERR_STATE, "transposing pass: the axis has no one-pass kernel");
     }
-    if (o.two) {
-        job.tw2 = o.tw2; job.pl = o.ptab;
-        return launch_rowT2(h, job, kind);
-    }
-    return o.R == 32 ? launch_rowT_r<32>(h, job, kind) : launch_rowT_r<16>(h, job, kind);
 }
 
 // Slice loop when a grid length is 2 R^2: every pass transposes (there is no in-place kernel for those lengths).
@@ -974,12 +992,11 @@ int slice_loop_onepass_b(msl_handle* h, int fused_slot, int groups, int first_gr
         j.flags = (k > 0 ? P2_PRE_A : 0) | (k < nz - 1 ? P2_POST_A : 0);
         if (h->debug_flags_mask >= 0) j.flags &= h->debug_flags_mask;
         j.n_images = P;
-        if (groups > 1) { j.t_group = c.n_probes; j.t_magic = (unsigned)((1ull << 32) / (unsigned)c.n_probes + 1); j.t_stride = (long long)c.nz * npix; }
-        if (h->opx.wave2k && h->opy.wave2k)               // work buffers between two of these passes: paired-lines layout
+        set_frame_groups(h, j, groups);
+        if (h->opx.kind == AX_WAVE2K && h->opy.kind == AX_WAVE2K)     // work buffers between two of these passes: paired-lines layout
             j.flags |= (k > 0 ? P2_IN_PAIRED : 0) | (k < nz - 1 ? P2_OUT_PAIRED : 0);
         // 512-point lines next to 512 / 256 / 1024-point ones: interleaved line order between two passes (16-byte loads)
-        auto il_kernel = [](const msl_handle::OpDir& o) { return o.R && !o.generic && !o.breg && !o.breg2 && !o.breg4 && !o.wave2k; };
-        if (il_kernel(h->opx) && il_kernel(h->opy) && !dbg_env("MSL_NO_INTERLEAVE") && h->debug_flags_mask < 0) {
+        if (interleaves(h->opx) && interleaves(h->opy) && !dbg_env("MSL_NO_INTERLEAVE") && h->debug_flags_mask < 0) {
             j.flags |= (k > 0 ? P2_IN_PAIRED : 0) | (k < nz - 1 ? P2_OUT_PAIRED : 0);
             j.perm_shift = (((k & 1) ? h->opy : h->opx).R == 32) ? 2 : 1;       // radix of the kernel that reads this pass's output
         }
@@ -1019,10 +1036,7 @@ int slice_loop_onepass_b(msl_handle* h, int fused_slot, int groups, int first_gr
         }
         if ((rc = epilogue_x_pass(h, fused_slot, groups))) return rc;
     }
-    h->cur = nullptr;
-    h->ctr.slice_steps += (uint64_t)P * nz;
-    h->ctr.frames += groups;
-    h->ctr.algorithmic_bytes += (uint64_t)P * nz * 16ull * npix + (uint64_t)groups * nz * 8ull * npix + (fused ? (uint64_t)P * 16ull * npix : 0ull);
+    count_slice_loop(h, P, groups, fused, 16);
     return MSL_OK;
 }
 
@@ -1031,13 +1045,7 @@ int launch_row2_r(msl_handle* h, Row2Job job, int kind) {
     constexpr int N = R * R, G = 256 / R;
     const size_t lds = (size_t)N * 16 + (size_t)G * R * (R + 1) * 4;
     const int per_cu = std::max(1, std::min(2, (int)((size_t)h->lds_limit / lds)));
-    const long long slots = (long long)h->n_cus * per_cu;
-    const long long xg = job.nx / G;
-    int pc = choose_pchunk(xg, job.n_images, slots, job.t_group);
-    if (h->row_pchunk > 0) { pc = std::min(h->row_pchunk, job.n_images); if (job.t_group > 0) while (job.t_group % pc) --pc; }
-    job.pchunk = pc;
-    const long long items = xg * ((job.n_images + pc - 1) / pc);
-    const int grid = (int)std::min<long long>(items, slots);
+    const int grid = chunked_grid(h, job, job.nx / G, (long long)h->n_cus * per_cu);
     hipLaunchKernelGGL(row_pass2_kernel<R>, dim3(grid), dim3(256), lds, h->stream, job);
     HIPCHK(h, hipGetLastError());
     return mark_launch(h, kind);
@@ -1065,7 +1073,7 @@ int slice_loop_onepass(msl_handle* h, int fused_slot, int groups, int first_grou
             Row2Job j{};
             j.psi = h->psi; j.trans = h->trans + toff + (size_t)k * npix; j.py = h->pyt; j.tw = h->tw4_y;
             j.image_stride = isA; j.pitch = h->pitch; j.nx = c.nx; j.n_images = P; j.flags = flags;
-            if (groups > 1) { j.t_group = c.n_probes; j.t_magic = (unsigned)((1ull << 32) / (unsigned)c.n_probes + 1); j.t_stride = (long long)c.nz * npix; }
+            set_frame_groups(h, j, groups);
             rc = h->Ry == 32 ? launch_row2_r<32>(h, j, K_ROW) : launch_row2_r<16>(h, j, K_ROW);
             if (rc) return rc;
             break;
@@ -1077,7 +1085,7 @@ int slice_loop_onepass(msl_handle* h, int fused_slot, int groups, int first_grou
         if (!dbg_env("MSL_NO_INTERLEAVE") && h->debug_flags_mask < 0) flags |= (k > 0 ? P2_IN_PAIRED : 0) | (k < nz - 2 ? P2_OUT_PAIRED : 0);
         j.flags = flags; j.n_images = P;
         j.perm_shift = ((along_y ? h->Rx : h->Ry) == 32) ? 2 : 1;             // radix of the kernel that reads this pass's output: log2(R' / 8)
-        if (groups > 1) { j.t_group = c.n_probes; j.t_magic = (unsigned)((1ull << 32) / (unsigned)c.n_probes + 1); j.t_stride = (long long)c.nz * npix; }
+        set_frame_groups(h, j, groups);
         if (along_y) {
             j.in = (k == 0) ? h->psi0 : h->psi; j.out = h->psiT;
             j.trans = h->trans + toff + (size_t)k * npix; j.pl = h->pyt; j.tw = h->tw4_y;
@@ -1094,10 +1102,7 @@ int slice_loop_onepass(msl_handle* h, int fused_slot, int groups, int first_grou
         if ((rc = layer_tap(h, k, fused_slot, groups, along_y ? h->psiT : h->psi, along_y, order, 8 << j.perm_shift, along_y ? 0 : 1))) return rc;
     }
     if (fused && (rc = epilogue_x_pass(h, fused_slot, groups))) return rc;
-    h->cur = nullptr;
-    h->ctr.slice_steps += (uint64_t)P * nz;
-    h->ctr.frames += groups;
-    h->ctr.algorithmic_bytes += (uint64_t)P * nz * 16ull * npix + (uint64_t)groups * nz * 8ull * npix + (fused ? (uint64_t)P * 16ull * npix : 0ull);
+    count_slice_loop(h, P, groups, fused, 16);
     return MSL_OK;
 }
 
@@ -1137,7 +1142,7 @@ int slice_loop(msl_handle* h, int fused_slot, int groups, int first_group) {
             RowJob r = row_job(h, h->psi, P, h->pitch);
             r.do_ifft = z > 0; r.trans = h->trans + toff + (size_t)z * npix;
             r.do_fft = (!last || fused); r.py = last ? nullptr : h->pyt;
-            if (groups > 1) { r.t_group = c.n_probes; r.t_magic = (unsigned)((1ull << 32) / (unsigned)c.n_probes + 1); r.t_stride = (long long)c.nz * npix; }
+            set_frame_groups(h, r, groups);
             if ((rc = launch_row_fast(h, r, K_ROW))) return rc;
         } else {
             LineArgs r = row_args(h, h->psi, h->psi, P, h->pitch);
@@ -1165,11 +1170,50 @@ int slice_loop(msl_handle* h, int fused_slot, int groups, int first_group) {
         // epilogue: fft along x, fftshift both axes, scatter into (P, T_local, nx, ny)
         if ((rc = epilogue_x_pass(h, fused_slot, groups))) return rc;
     }
-    h->cur = nullptr;
-    h->ctr.slice_steps += (uint64_t)P * nz;
-    h->ctr.frames += groups;
-    h->ctr.algorithmic_bytes += (uint64_t)P * nz * 32ull * npix + (uint64_t)groups * nz * 8ull * npix + (fused ? (uint64_t)P * 16ull * npix : 0ull);
+    count_slice_loop(h, P, groups, fused, 32);
     return MSL_OK;
+}
+
+// cyclic length of the convolution that IS the propagation along an axis of a convolution kind (0: none), and the entries of its filter qf
+int conv_len(const msl_handle::OpDir& o) { return o.base == AX_CONV ? o.R * o.R : o.base == AX_CONV2K ? 2048 : o.base == AX_CONV4K ? 4096 : 0; }
+size_t conv_filter_entries(const msl_handle::OpDir& o) { return o.base == AX_CONV4K ? 2052 : (size_t)conv_len(o) / 2 + 2; }
+
+// Filter of that convolution for n points of spacing d: a = ifft_n(P) (float64), wrapped to the cyclic length M, filter = FFT_M(a) / M,
+// stored as its first half + 1 (NH + 2 entries, rowTB / rowTB2), or for M = 4096 in the split order of rowTC2_pass_kernel (even
+// entries 0..1024, odd entries from 1026)
+int fill_conv_filter(msl_handle* h, const msl_handle::OpDir& o, double d) {
+    const msl_config& c = h->cfg;
+    const int n = o.n, M = conv_len(o), NH = M / 2;
+    std::vector<double> pr(n), pi(n), er(n), ei(n), qr(M, 0.0), qi(M, 0.0);
+    for (int m = 0; m < n; ++m) {
+        const int f = (m < (n + 1) / 2) ? m : m - n;
+        const double k = f * (1.0 / (n * d));
+        const double ph = -M_PI * c.wavelength * c.dz * k * k;
+        pr[m] = cos(ph); pi[m] = sin(ph);
+        const double a = 2.0 * M_PI * (double)m / (double)n;
+        er[m] = cos(a); ei[m] = sin(a);
+    }
+    for (int j = 0; j < n; ++j) {                      // a[j] = (1/n) sum_m P[m] e^{+2 pi i m j / n}
+        double sr = 0.0, si = 0.0;
+        long long t = 0;
+        for (int m = 0; m < n; ++m) {
+            sr += pr[m] * er[t] - pi[m] * ei[t];
+            si += pr[m] * ei[t] + pi[m] * er[t];
+            t += j; if (t >= n) t -= n;
+        }
+        sr /= n; si /= n;
+        qr[j] = sr; qi[j] = si;                         // lag +j
+        if (j) { qr[M - n + j] = sr; qi[M - n + j] = si; }   // lag j - n  (M - (n - j))
+    }
+    host_fft_pow2(qr, qi);
+    std::vector<float2> qf(conv_filter_entries(o), make_float2(0.f, 0.f));
+    if (o.base == AX_CONV4K) {
+        for (int k = 0; k <= 1024; ++k) qf[k] = make_float2((float)(qr[2 * k] / M), (float)(qi[2 * k] / M));
+        for (int k = 0; k < 1024; ++k) qf[1026 + k] = make_float2((float)(qr[2 * k + 1] / M), (float)(qi[2 * k + 1] / M));
+    } else {
+        for (int j = 0; j <= NH; ++j) qf[j] = make_float2((float)(qr[j] / M), (float)(qi[j] / M));
+    }
+    return copy_table(h, o.qf, qf);
 }
 
 // Fresnel propagator, separable: P[kx,ky] = exp(-i pi lambda dz kx^2) * exp(-i pi lambda dz ky^2)
@@ -1184,9 +1228,7 @@ int fill_propagator(msl_handle* h) {
             double ph = -M_PI * c.wavelength * c.dz * k * k;
             v[m] = make_float2((float)(cos(ph) / n), (float)(sin(ph) / n));
         }
-        HIPCHK(h, hipMemcpyAsync(dst, v.data(), n * sizeof(float2), hipMemcpyHostToDevice, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        return MSL_OK;
+        return copy_table(h, dst, v);
     };
     int rc = fill(h->pxt, c.nx, c.dx);
     if (rc) return rc;
@@ -1200,15 +1242,12 @@ int fill_propagator(msl_handle* h) {
             const double ph = M_PI * c.wavelength * c.dz * k * k;
             v[m] = make_float2((float)cos(ph), (float)sin(ph));
         }
-        HIPCHK(h, hipMemcpyAsync(dst, v.data(), n * sizeof(float2), hipMemcpyHostToDevice, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        return MSL_OK;
+        return copy_table(h, dst, v);
     };
     if ((rc = fill_conj(h->tap_cx, c.nx, c.dx))) return rc;
     if ((rc = fill_conj(h->tap_cy, c.ny, c.dy))) return rc;
     // split-order copies for the 2R^2 kernels: entry [b*R^2 + k] = P[2k + b]
     auto fill_split = [&](float2* dst, int n, double d) -> int {
-        if (!dst) return MSL_OK;
         std::vector<float2> v(n);
         for (int b = 0; b < 2; ++b)
             for (int k = 0; k < n / 2; ++k) {
@@ -1218,83 +1257,120 @@ int fill_propagator(msl_handle* h) {
                 const double ph = -M_PI * c.wavelength * c.dz * kk * kk;
                 v[b * (n / 2) + k] = make_float2((float)(cos(ph) / n), (float)(sin(ph) / n));
             }
-        HIPCHK(h, hipMemcpyAsync(dst, v.data(), n * sizeof(float2), hipMemcpyHostToDevice, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        return MSL_OK;
+        return copy_table(h, dst, v);
     };
-    if (h->opx.two && (rc = fill_split(h->opx.ptab, c.nx, c.dx))) return rc;
-    if (h->opy.two && (rc = fill_split(h->opy.ptab, c.ny, c.dy))) return rc;
-    // any-length register kernels: filter of the zero-padded cyclic convolution that IS the propagation along one axis
-    auto fill_padded = [&](const msl_handle::OpDir& o, int n, double d) -> int {
-        const int NH = o.breg2 ? 1024 : o.R * o.R / 2;
-        // convolution form: a = ifft_n(P) (float64), wrapped to the cyclic length M = 2 NH, filter = FFT_M(q) / M, first half + 1
-        {
-            const int M = 2 * NH;
-            std::vector<double> pr(n), pi(n), er(n), ei(n), qr(M, 0.0), qi(M, 0.0);
-            for (int m = 0; m < n; ++m) {
-                const int f = (m < (n + 1) / 2) ? m : m - n;
-                const double k = f * (1.0 / (n * d));
-                const double ph = -M_PI * c.wavelength * c.dz * k * k;
-                pr[m] = cos(ph); pi[m] = sin(ph);
-                const double a = 2.0 * M_PI * (double)m / (double)n;
-                er[m] = cos(a); ei[m] = sin(a);
+    for (const msl_handle::OpDir* o : {&h->opx, &h->opy}) {
+        const double d = (o == &h->opx) ? c.dx : c.dy;
+        if (o->base == AX_TWO && (rc = fill_split(o->ptab, o->n, d))) return rc;
+        // convolution kinds: filter of the zero-padded cyclic convolution that IS the propagation along the axis
+        if (conv_len(*o) && (rc = fill_conv_filter(h, *o, d))) return rc;
+    }
+    return MSL_OK;
+}
+
+// ---- axis planning ----------------------------------------------------------------------------------
+// The kind of the slice loop's pass along an axis of n points (n_other lines per image; Rfast = the four-step radix of the axis or 0;
+// plan_M = the length of its generic plan, > n for a Bluestein plan).  want = false (two-pass loop asked for): no one-pass kind.
+void plan_axis_kind(const msl_handle* h, msl_handle::OpDir& o, int n, int n_other, int Rfast, int plan_M, bool want) {
+    const bool lines_ok = (n_other % 16 == 0);          // the register kernels take 16 lines at a time
+    AxisKind base = AX_NONE;
+    if (!want) {
+    } else if (Rfast && lines_ok) {
+        base = AX_FOURSTEP;
+    } else if ((n == 512 || n == 2048) && lines_ok && !dbg_env("MSL_NO_TWO")) {
+        // 512 = 2 R^2 points on the R = 16 register kernels; 2048-point lines on the wave-per-line FFT
+        base = n == 512 ? AX_TWO : AX_WAVE2K;
+    } else if (n >= 33 && n <= 512 && (n <= 128 || n >= 192 || plan_M != n) && !dbg_env("MSL_NO_BLUESTEIN_REG")) {
+        // zero-padded cyclic convolution (or, MSL_CHIRPZ=1, chirp-z) on the register FFTs of length M = R^2 >= 2n - 1.  A line
+        // costs the same whatever n is, so against the generic Stockham kernel (cost ~ n log n) it wins for n <= 128 (M = 256)
+        // and from n ~ 190 up (M = 1024; 64 probes x 50 slices: 160^2 1.83 M vs 1.72 M slice-steps/s, 200^2 1.23 vs 1.31 M,
+        // 240^2 0.84 vs 1.13 M), and everywhere the generic kernel would need its own LDS-resident Bluestein transform
+        base = AX_CONV;
+    } else if (n >= 513 && n <= 1024 && !dbg_env("MSL_NO_BLUESTEIN_REG")) {
+        // 513..1024: the same on the wave-per-line 2048-point register FFT, every length (convolution form against the
+        // Stockham kernel: 540^2 102 k -> 186 k slice-steps/s, 600^2 85 k -> 160 k, 768^2 73 k -> 130 k)
+        base = AX_CONV2K;
+    } else if (n >= 1025 && n <= 2047 && !dbg_env("MSL_NO_CONV4096") && !dbg_env("MSL_NO_BLUESTEIN_REG")) {
+        // 1025..2047: cyclic convolution of length 4096 on pairs of 2048-point wave FFTs, the two branches of the radix-2
+        // step on two waves (rowTC2_pass_kernel): 16 probes x 20 slices, slice-steps/s against the generic two-pass loop:
+        // 1100^2 19.6 k -> 27.5 k, 1500^2 12.6 k -> 18.3 k, 2000^2 6.8 k -> 11.4 k.  MSL_CONV4096=1 selects the first
+        // version, both branches in one wave (rowTC_pass_kernel): two 64-register line sets plus the transform's
+        // temporaries spill 916 B per lane and it is no faster than the generic loop (20.0 k at 1100^2).
+        base = AX_CONV4K;
+    } else if (plan_M <= 1024 && !dbg_env("MSL_NO_GENERIC_ONEPASS")) {
+        // generic LDS kernel with a transposing store: tiles of >= 8 lines keep the stores at 64 bytes or more
+        base = AX_GENERIC;
+    }
+    // smooth lengths A * B (A, B <= 32) or 2 A * B (up to 1728) with a compiled kernel: direct mixed-radix passes in the slice
+    // loop (600^2: 163 k -> 330 k slice-steps/s, 1500^2: 18 k -> 55 k), over the base kind the length gets otherwise
+    int mA = 0, mB = 0, mG = 0;
+    const bool mixed = want && base != AX_FOURSTEP && base != AX_TWO && base != AX_WAVE2K && rowTM_factors(n, &mA, &mB, &mG) &&
+                       !dbg_env("MSL_NO_MIXED") && (mG == 64 ? rowTM2_lds_bytes(mA, mB) : rowTM_lds_bytes(mA, mB)) <= (size_t)h->lds_limit;
+    o.n = n;
+    o.base = base;
+    o.kind = mixed ? AX_MIXED : base;
+    o.R = base == AX_FOURSTEP ? Rfast : base == AX_TWO ? 16 : base == AX_CONV ? (n <= 128 ? 16 : 32) :
+          (base == AX_WAVE2K || base == AX_CONV2K || base == AX_CONV4K) ? 32 : 0;
+}
+
+// The tables of axis o (msl_handle::OpDir); `other` = the other axis, planned
+int make_axis_tables(msl_handle* h, msl_handle::OpDir& o, const msl_handle::OpDir& other) {
+    const int n = o.n;
+    int rc = MSL_OK;
+    if (o.kind == AX_MIXED) {
+        int mA = 0, mB = 0, mG = 0;
+        rowTM_factors(n, &mA, &mB, &mG);
+        const int lanes1 = mG == 64 ? 2 * mA : mA;           // lanes of layout 1 (rowtm_pass.h)
+        std::vector<float2> T(2 * (size_t)n + (mG == 64 ? 2 * mA : 0));
+        for (int k2 = 0; k2 < mB; ++k2)
+            for (int n1 = 0; n1 < lanes1; ++n1) {
+                const double a = -2.0 * M_PI * (double)((k2 * n1) % n) / (double)n;
+                const float2 w = make_float2((float)cos(a), (float)sin(a));
+                T[k2 * lanes1 + n1] = w;
+                if (mG == 64) T[n + (n1 % mA) * 2 * mB + 2 * k2 + n1 / mA] = w;      // lane order of layout 2: [m 2B + 2 k2 + h], n1 = m + A h
+                else T[n + n1 * mB + k2] = w;
             }
-            for (int j = 0; j < n; ++j) {                      // a[j] = (1/n) sum_m P[m] e^{+2 pi i m j / n}
-                double sr = 0.0, si = 0.0;
-                long long t = 0;
-                for (int m = 0; m < n; ++m) {
-                    sr += pr[m] * er[t] - pi[m] * ei[t];
-                    si += pr[m] * ei[t] + pi[m] * er[t];
-                    t += j; if (t >= n) t -= n;
-                }
-                sr /= n; si /= n;
-                qr[j] = sr; qi[j] = si;                         // lag +j
-                if (j) { qr[M - n + j] = sr; qi[M - n + j] = si; }   // lag j - n  (M - (n - j))
+        if (mG == 64)
+            for (int m = 0; m < mA; ++m) {
+                const double a = -2.0 * M_PI * (double)m / (double)(2 * mA);
+                T[2 * n + m] = make_float2(1.f, 0.f);
+                T[2 * n + mA + m] = make_float2((float)cos(a), (float)sin(a));
             }
-            host_fft_pow2(qr, qi);
-            std::vector<float2> qf(NH + 2, make_float2(0.f, 0.f));
-            for (int j = 0; j <= NH; ++j) qf[j] = make_float2((float)(qr[j] / M), (float)(qi[j] / M));
-            HIPCHK(h, hipMemcpyAsync(o.qf, qf.data(), (NH + 2) * sizeof(float2), hipMemcpyHostToDevice, h->stream));
-            HIPCHK(h, hipStreamSynchronize(h->stream));
+        if ((rc = upload(h, &o.mtw, T))) return rc;
+    }
+    switch (o.base) {
+    case AX_TWO: {
+        std::vector<float2> t(o.R * o.R);
+        for (int m = 0; m < o.R * o.R; ++m) {
+            const double a = -2.0 * M_PI * (double)m / (double)n;
+            t[m] = make_float2((float)cos(a), (float)sin(a));
         }
-        return MSL_OK;
-    };
-    if ((h->opx.breg || h->opx.breg2) && (rc = fill_padded(h->opx, c.nx, c.dx))) return rc;
-    if ((h->opy.breg || h->opy.breg2) && (rc = fill_padded(h->opy, c.ny, c.dy))) return rc;
-    // 1025..2047 points: filter of the cyclic convolution of length 4096 in the split order of rowTC_pass_kernel
-    auto fill_conv4 = [&](const msl_handle::OpDir& o, int n, double d) -> int {
-        const int M = 4096;
-        std::vector<double> pr(n), pi(n), er(n), ei(n), qr(M, 0.0), qi(M, 0.0);
-        for (int m = 0; m < n; ++m) {
-            const int f = (m < (n + 1) / 2) ? m : m - n;
-            const double k = f * (1.0 / (n * d));
-            const double ph = -M_PI * c.wavelength * c.dz * k * k;
-            pr[m] = cos(ph); pi[m] = sin(ph);
-            const double a = 2.0 * M_PI * (double)m / (double)n;
-            er[m] = cos(a); ei[m] = sin(a);
+        if ((rc = make_tw4(h, &o.tw, o.R)) || (rc = upload(h, &o.tw2, t)) || (rc = dalloc(h, &o.ptab, (size_t)n))) return rc;
+        break;
+    }
+    case AX_WAVE2K:
+        if ((rc = make_wave2k_tables(h, &o.tw, &o.tw2))) return rc;
+        break;
+    case AX_CONV:
+    case AX_CONV2K:
+        if ((rc = make_cz_tables(h, o.cz, n)) || (rc = dalloc(h, &o.qf, conv_filter_entries(o)))) return rc;
+        break;
+    case AX_CONV4K: {
+        std::vector<float2> wq(2048);
+        for (int i = 0; i < 2048; ++i) {
+            const double a = -2.0 * M_PI * (double)i / 4096.0;
+            wq[i] = make_float2((float)cos(a), (float)sin(a));
         }
-        for (int j = 0; j < n; ++j) {
-            double sr = 0.0, si = 0.0;
-            long long t = 0;
-            for (int m = 0; m < n; ++m) {
-                sr += pr[m] * er[t] - pi[m] * ei[t];
-                si += pr[m] * ei[t] + pi[m] * er[t];
-                t += j; if (t >= n) t -= n;
-            }
-            sr /= n; si /= n;
-            qr[j] = sr; qi[j] = si;
-            if (j) { qr[M - n + j] = sr; qi[M - n + j] = si; }
-        }
-        host_fft_pow2(qr, qi);
-        std::vector<float2> qf(2052, make_float2(0.f, 0.f));
-        for (int k = 0; k <= 1024; ++k) qf[k] = make_float2((float)(qr[2 * k] / M), (float)(qi[2 * k] / M));
-        for (int k = 0; k < 1024; ++k) qf[1026 + k] = make_float2((float)(qr[2 * k + 1] / M), (float)(qi[2 * k + 1] / M));
-        HIPCHK(h, hipMemcpyAsync(o.qf, qf.data(), qf.size() * sizeof(float2), hipMemcpyHostToDevice, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        return MSL_OK;
-    };
-    if (h->opx.breg4 && (rc = fill_conv4(h->opx, c.nx, c.dx))) return rc;
-    if (h->opy.breg4 && (rc = fill_conv4(h->opy, c.ny, c.dy))) return rc;
+        if ((rc = make_wave2k_tables(h, &o.tw, &o.tw2)) || (rc = upload(h, &o.bw, wq)) || (rc = dalloc(h, &o.qf, conv_filter_entries(o)))) return rc;
+        break;
+    }
+    default:
+        break;
+    }
+    // an axis of at most 1024 points next to a convolution axis gets chirp-z tables too, so that the potential's inverse transform
+    // runs on the register kernels along both (512 x 300, 349 x 1024 ...)
+    auto conv = [](const msl_handle::OpDir& d) { return d.base == AX_CONV || d.base == AX_CONV2K; };
+    if (!conv(o) && conv(other) && n >= 33 && n <= 1024) return make_cz_tables(h, o.cz, n);
     return MSL_OK;
 }
 
@@ -1413,197 +1489,11 @@ int msl_create(const msl_config* cfg, msl_handle** out) {
     {
         const char* e = dbg_env("MSL_SLICE_PATH");           // 2 = force the two-pass four-step loop
         const bool want = cfg->fft_path == 0 && !(e && atoi(e) == 2);
-        // n = line length of the direction, n_other = number of lines per image (the register kernels take 16 at a time)
-        auto setup_dir = [&](msl_handle::OpDir& o, int n, int n_other, int Rfast, float2* tw4) -> int {
-            const bool lines_ok = (n_other % 16 == 0);
-            if (Rfast && lines_ok) { o.R = Rfast; o.two = false; o.tw = tw4; return MSL_OK; }
-            const int R2 = (n == 512) ? 16 : (n == 2048 ? 32 : 0);
-            const bool two_ok = R2 && lines_ok && want && !dbg_env("MSL_NO_TWO");
-            if (n == 2048 && two_ok) {
-                // 2048-point lines on the wave-per-line FFT (tables: T[k1*64+n2], W_64; the natural Fresnel table serves as is)
-                o.R = 32; o.wave2k = true;
-                std::vector<float2> T(2048), W(64);
-                for (int k1 = 0; k1 < 32; ++k1)
-                    for (int n2 = 0; n2 < 64; ++n2) {
-                        const double a = -2.0 * M_PI * (double)(k1 * n2) / 2048.0;
-                        T[k1 * 64 + n2] = make_float2((float)cos(a), (float)sin(a));
-                    }
-                for (int m = 0; m < 32; ++m) {
-                    const double a = -2.0 * M_PI * m / 64.0;
-                    W[m] = make_float2(1.f, 0.f);
-                    W[32 + m] = make_float2((float)cos(a), (float)sin(a));
-                }
-                int r;
-                if ((r = dalloc(h, &o.tw, (size_t)2048))) return r;
-                if ((r = dalloc(h, &o.tw2, (size_t)64))) return r;
-                if (hipMemcpy(o.tw, T.data(), 2048 * sizeof(float2), hipMemcpyHostToDevice) != hipSuccess ||
-                    hipMemcpy(o.tw2, W.data(), 64 * sizeof(float2), hipMemcpyHostToDevice) != hipSuccess)
-                    return fail(h, MSL_ERR_HIP, "twiddle upload failed");
-                return MSL_OK;
-            }
-            // smooth lengths A * B (A, B <= 32) or 2 A * B (up to 1728) with a compiled kernel: direct mixed-radix passes in the slice
-            // loop (600^2: 163 k -> 330 k slice-steps/s, 1500^2: 18 k -> 55 k).  The tables of the convolution / generic branches below are made all the same: the potential's
-            // inverse transform, the probes and the exit FFT of such a grid still run on those kernels.
-            {
-                int mA = 0, mB = 0, mG = 0;
-                if (!two_ok && want && rowTM_factors(n, &mA, &mB, &mG) && !dbg_env("MSL_NO_MIXED") &&
-                    (mG == 64 ? rowTM2_lds_bytes(mA, mB) : rowTM_lds_bytes(mA, mB)) <= (size_t)h->lds_limit) {
-                    const int lanes1 = mG == 64 ? 2 * mA : mA;           // lanes of layout 1 (rowtm_pass.h)
-                    std::vector<float2> T(2 * (size_t)n + (mG == 64 ? 2 * mA : 0));
-                    for (int k2 = 0; k2 < mB; ++k2)
-                        for (int n1 = 0; n1 < lanes1; ++n1) {
-                            const double a = -2.0 * M_PI * (double)((k2 * n1) % n) / (double)n;
-                            const float2 w = make_float2((float)cos(a), (float)sin(a));
-                            T[k2 * lanes1 + n1] = w;
-                            if (mG == 64) T[n + (n1 % mA) * 2 * mB + 2 * k2 + n1 / mA] = w;      // lane order of layout 2: [m 2B + 2 k2 + h], n1 = m + A h
-                            else T[n + n1 * mB + k2] = w;
-                        }
-                    if (mG == 64)
-                        for (int m = 0; m < mA; ++m) {
-                            const double a = -2.0 * M_PI * (double)m / (double)(2 * mA);
-                            T[2 * n + m] = make_float2(1.f, 0.f);
-                            T[2 * n + mA + m] = make_float2((float)cos(a), (float)sin(a));
-                        }
-                    int r;
-                    if ((r = dalloc(h, &o.mtw, T.size()))) return r;
-                    if (hipMemcpy(o.mtw, T.data(), T.size() * sizeof(float2), hipMemcpyHostToDevice) != hipSuccess)
-                        return fail(h, MSL_ERR_HIP, "twiddle upload failed");
-                    o.mixed = true;
-                }
-            }
-            // zero-padded cyclic convolution (or, MSL_CHIRPZ=1, chirp-z) on the register FFTs of length M = R^2 >= 2n - 1.  A line
-            // costs the same whatever n is, so against the generic Stockham kernel (cost ~ n log n) it wins for n <= 128 (M = 256)
-            // and from n ~ 190 up (M = 1024; 64 probes x 50 slices: 160^2 1.83 M vs 1.72 M slice-steps/s, 200^2 1.23 vs 1.31 M,
-            // 240^2 0.84 vs 1.13 M), and everywhere the generic kernel would need its own LDS-resident Bluestein transform
-            const bool smooth = ((&o == &h->opx) ? h->plan_x : h->plan_y).M == n;
-            if (!two_ok && want && n >= 33 && n <= 512 && (n <= 128 || n >= 192 || !smooth) && !dbg_env("MSL_NO_BLUESTEIN_REG")) {
-                const int Rb = (n <= 128) ? 16 : 32, M = Rb * Rb, NH = M / 2;
-                o.R = Rb; o.breg = true;
-                int r = make_tw4(h, &o.tw, Rb);
-                if (r) return r;
-                std::vector<float2> bw(NH, make_float2(0.f, 0.f)), bf(NH + 2, make_float2(0.f, 0.f));
-                std::vector<double> cr(M, 0.0), ci(M, 0.0);
-                for (int i = 0; i < n; ++i) {
-                    const long long q = ((long long)i * i) % (2LL * n);
-                    const double a = -M_PI * (double)q / (double)n;              // w[i] = exp(-i pi i^2 / n)
-                    bw[i] = make_float2((float)cos(a), (float)sin(a));
-                    cr[i] = cos(a); ci[i] = -sin(a);                              // conj chirp, wrapped to negative lags
-                    if (i) { cr[M - i] = cr[i]; ci[M - i] = ci[i]; }
-                }
-                host_fft_pow2(cr, ci);
-                for (int j = 0; j <= NH; ++j) bf[j] = make_float2((float)(cr[j] / M), (float)(ci[j] / M));
-                if ((r = dalloc(h, &o.bw, (size_t)NH))) return r;
-                if ((r = dalloc(h, &o.bf, (size_t)NH + 2))) return r;
-                if ((r = dalloc(h, &o.qf, (size_t)NH + 2))) return r;
-                if (hipMemcpy(o.bw, bw.data(), NH * sizeof(float2), hipMemcpyHostToDevice) != hipSuccess ||
-                    hipMemcpy(o.bf, bf.data(), (NH + 2) * sizeof(float2), hipMemcpyHostToDevice) != hipSuccess)
-                    return fail(h, MSL_ERR_HIP, "chirp table upload failed");
-                return MSL_OK;
-            }
-            if (!two_ok && want && n >= 513 && n <= 1024 && !dbg_env("MSL_NO_BLUESTEIN_REG")) {
-                // 513..1024: the same on the wave-per-line 2048-point register FFT, every length (convolution form against the
-                // Stockham kernel: 540^2 102 k -> 186 k slice-steps/s, 600^2 85 k -> 160 k, 768^2 73 k -> 130 k)
-                constexpr int M = 2048, NH = 1024;
-                o.R = 32; o.breg2 = true;
-                std::vector<float2> T(M), W(64), bw(NH, make_float2(0.f, 0.f)), bf(NH + 2, make_float2(0.f, 0.f));
-                for (int k1 = 0; k1 < 32; ++k1)
-                    for (int n2 = 0; n2 < 64; ++n2) {
-                        const double a = -2.0 * M_PI * (double)(k1 * n2) / (double)M;
-                        T[k1 * 64 + n2] = make_float2((float)cos(a), (float)sin(a));
-                    }
-                for (int m = 0; m < 32; ++m) {
-                    const double a = -2.0 * M_PI * m / 64.0;
-                    W[m] = make_float2(1.f, 0.f);                                   // even lane of a pair: no twiddle
-                    W[32 + m] = make_float2((float)cos(a), (float)sin(a));          // odd lane: W_64^m
-                }
-                std::vector<double> cr(M, 0.0), ci(M, 0.0);
-                for (int i = 0; i < n; ++i) {
-                    const long long q = ((long long)i * i) % (2LL * n);
-                    const double a = -M_PI * (double)q / (double)n;
-                    bw[i] = make_float2((float)cos(a), (float)sin(a));
-                    cr[i] = cos(a); ci[i] = -sin(a);
-                    if (i) { cr[M - i] = cr[i]; ci[M - i] = ci[i]; }
-                }
-                host_fft_pow2(cr, ci);
-                for (int j = 0; j <= NH; ++j) bf[j] = make_float2((float)(cr[j] / M), (float)(ci[j] / M));
-                int r;
-                if ((r = dalloc(h, &o.tw, (size_t)M))) return r;
-                if ((r = dalloc(h, &o.tw2, (size_t)64))) return r;
-                if ((r = dalloc(h, &o.bw, (size_t)NH))) return r;
-                if ((r = dalloc(h, &o.bf, (size_t)NH + 2))) return r;
-                if ((r = dalloc(h, &o.qf, (size_t)NH + 2))) return r;
-                if (hipMemcpy(o.tw, T.data(), M * sizeof(float2), hipMemcpyHostToDevice) != hipSuccess ||
-                    hipMemcpy(o.tw2, W.data(), 64 * sizeof(float2), hipMemcpyHostToDevice) != hipSuccess ||
-                    hipMemcpy(o.bw, bw.data(), NH * sizeof(float2), hipMemcpyHostToDevice) != hipSuccess ||
-                    hipMemcpy(o.bf, bf.data(), (NH + 2) * sizeof(float2), hipMemcpyHostToDevice) != hipSuccess)
-                    return fail(h, MSL_ERR_HIP, "chirp table upload failed");
-                return MSL_OK;
-            }
-            if (!two_ok && want && n >= 1025 && n <= 2047 && !dbg_env("MSL_NO_CONV4096") && !dbg_env("MSL_NO_BLUESTEIN_REG")) {
-                // 1025..2047: cyclic convolution of length 4096 on pairs of 2048-point wave FFTs, the two branches of the radix-2
-                // step on two waves (rowTC2_pass_kernel): 16 probes x 20 slices, slice-steps/s against the generic two-pass loop:
-                // 1100^2 19.6 k -> 27.5 k, 1500^2 12.6 k -> 18.3 k, 2000^2 6.8 k -> 11.4 k.  MSL_CONV4096=1 selects the first
-                // version, both branches in one wave (rowTC_pass_kernel): two 64-register line sets plus the transform's
-                // temporaries spill 916 B per lane and it is no faster than the generic loop (20.0 k at 1100^2).
-                constexpr int M = 2048;
-                o.R = 32; o.breg4 = true;
-                std::vector<float2> T(M), W(64), wq(M);
-                for (int k1 = 0; k1 < 32; ++k1)
-                    for (int n2 = 0; n2 < 64; ++n2) {
-                        const double a = -2.0 * M_PI * (double)(k1 * n2) / (double)M;
-                        T[k1 * 64 + n2] = make_float2((float)cos(a), (float)sin(a));
-                    }
-                for (int m = 0; m < 32; ++m) {
-                    const double a = -2.0 * M_PI * m / 64.0;
-                    W[m] = make_float2(1.f, 0.f);
-                    W[32 + m] = make_float2((float)cos(a), (float)sin(a));
-                }
-                for (int i = 0; i < M; ++i) {
-                    const double a = -2.0 * M_PI * (double)i / 4096.0;
-                    wq[i] = make_float2((float)cos(a), (float)sin(a));
-                }
-                int r;
-                if ((r = dalloc(h, &o.tw, (size_t)M))) return r;
-                if ((r = dalloc(h, &o.tw2, (size_t)64))) return r;
-                if ((r = dalloc(h, &o.bw, (size_t)M))) return r;
-                if ((r = dalloc(h, &o.qf, (size_t)2052))) return r;
-                if (hipMemcpy(o.tw, T.data(), M * sizeof(float2), hipMemcpyHostToDevice) != hipSuccess ||
-                    hipMemcpy(o.tw2, W.data(), 64 * sizeof(float2), hipMemcpyHostToDevice) != hipSuccess ||
-                    hipMemcpy(o.bw, wq.data(), M * sizeof(float2), hipMemcpyHostToDevice) != hipSuccess)
-                    return fail(h, MSL_ERR_HIP, "twiddle upload failed");
-                return MSL_OK;
-            }
-            if (!two_ok) {
-                // generic LDS kernel with a transposing store: tiles of >= 8 lines keep the stores at 64 bytes or more
-                const int M = (&o == &h->opx) ? h->plan_x.M : h->plan_y.M;
-                o.generic = want && M <= 1024 && !dbg_env("MSL_NO_GENERIC_ONEPASS");
-                return MSL_OK;
-            }
-            o.R = R2; o.two = true;
-            int r = make_tw4(h, &o.tw, R2);
-            if (r) return r;
-            std::vector<float2> t(R2 * R2);
-            for (int m = 0; m < R2 * R2; ++m) {
-                const double a = -2.0 * M_PI * (double)m / (double)n;
-                t[m] = make_float2((float)cos(a), (float)sin(a));
-            }
-            if ((r = dalloc(h, &o.tw2, (size_t)R2 * R2))) return r;
-            if (hipMemcpy(o.tw2, t.data(), t.size() * sizeof(float2), hipMemcpyHostToDevice) != hipSuccess)
-                return fail(h, MSL_ERR_HIP, "twiddle upload failed");
-            return dalloc(h, &o.ptab, (size_t)n);
-        };
-        if ((rc = setup_dir(h->opx, cfg->nx, cfg->ny, h->Rx, h->tw4_x))) return bail(rc);
-        if ((rc = setup_dir(h->opy, cfg->ny, cfg->nx, h->Ry, h->tw4_y))) return bail(rc);
-        // a chirp / convolution axis next to another kind of axis of at most 1024 points: the other one gets chirp-z tables too, so
-        // that the potential's inverse transform runs on the register kernels along both (512 x 300, 349 x 1024 ...)
-        {
-            auto cz_axis = [](const msl_handle::OpDir& o) { return o.breg || o.breg2; };
-            if (want && cz_axis(h->opx) && !cz_axis(h->opy) && cfg->ny >= 33 && cfg->ny <= 1024 && (rc = make_cz_tables(h, h->opy, cfg->ny))) return bail(rc);
-            if (want && cz_axis(h->opy) && !cz_axis(h->opx) && cfg->nx >= 33 && cfg->nx <= 1024 && (rc = make_cz_tables(h, h->opx, cfg->nx))) return bail(rc);
-        }
-        h->onepass = want && (h->opx.R || h->opx.generic) && (h->opy.R || h->opy.generic);
-        h->scheme_b = h->onepass && (h->opx.two || h->opy.two || h->opx.generic || h->opy.generic || h->opx.breg || h->opy.breg ||
-                                     h->opx.breg2 || h->opy.breg2 || h->opx.breg4 || h->opy.breg4 || h->opx.wave2k || h->opy.wave2k);
+        plan_axis_kind(h, h->opx, cfg->nx, cfg->ny, h->Rx, h->plan_x.M, want);
+        plan_axis_kind(h, h->opy, cfg->ny, cfg->nx, h->Ry, h->plan_y.M, want);
+        if ((rc = make_axis_tables(h, h->opx, h->opy)) || (rc = make_axis_tables(h, h->opy, h->opx))) return bail(rc);
+        h->onepass = h->opx.base != AX_NONE && h->opy.base != AX_NONE;
+        h->scheme_b = h->onepass && !(h->opx.kind == AX_FOURSTEP && h->opy.kind == AX_FOURSTEP);
         if (h->pitch == cfg->ny && h->onepass) h->pitch = cfg->ny + 16;        // pad the work buffers of 2R^2 grids too
         if (h->onepass && (h->pitch & 1)) ++h->pitch;                          // even pitches: the transposed stores write two lines (16 bytes) at a time
         const size_t images = (size_t)cfg->n_probes * h->FB;
@@ -1655,11 +1545,13 @@ int msl_destroy(msl_handle* h) {
     void* bufs[] = {h->psi0, h->psi, h->trans, h->V, h->wf, h->intensity, h->pxt, h->pyt, h->tap, h->tap_cx, h->tap_cy, h->d_abcd, h->d_lo, h->d_hi,
                     h->d_pos, h->d_Z, h->d_key, h->d_order, h->d_u1, h->d_u2, h->d_ex, h->d_ey, h->d_counts, h->d_start,
                     h->d_z2s, h->d_species, h->d_ff, h->d_xy, h->plan_x.tw, h->plan_y.tw, h->plan_t.tw, h->tw4_x, h->tw4_y,
-                    h->scratch, h->psiT, h->psi0T, h->transT, h->bin_stage, h->st_acc, h->st_s1, h->st_s2, h->st_tw, h->st_bins, h->st_ref, h->opx.tw2, h->opx.ptab, h->opy.tw2, h->opy.ptab,
-                    ((h->opx.two || h->opx.breg || h->opx.breg2 || h->opx.breg4 || h->opx.wave2k) ? h->opx.tw : nullptr), ((h->opy.two || h->opy.breg || h->opy.breg2 || h->opy.breg4 || h->opy.wave2k) ? h->opy.tw : nullptr),
-                    h->opx.bf, h->opx.bw, h->opy.bf, h->opy.bw, h->opx.qf, h->opy.qf, h->opx.mtw, h->opy.mtw, h->opx.cz_tw, h->opx.cz_tw2, h->opx.cz_bf, h->opx.cz_bw,
-                    h->opy.cz_tw, h->opy.cz_tw2, h->opy.cz_bf, h->opy.cz_bw, h->opt.cz_tw, h->opt.cz_tw2, h->opt.cz_bf, h->opt.cz_bw, h->tsplit_tw, h->plan_x.chirp, h->plan_x.bfilt, h->plan_y.chirp, h->plan_y.bfilt, h->plan_t.chirp, h->plan_t.bfilt};
+                    h->scratch, h->psiT, h->psi0T, h->transT, h->bin_stage, h->st_acc, h->st_s1, h->st_s2, h->st_tw, h->st_bins, h->st_ref,
+                    h->opt.tw, h->opt.tw2, h->opt.bf, h->opt.bw, h->tsplit_tw, h->plan_x.chirp, h->plan_x.bfilt, h->plan_y.chirp, h->plan_y.bfilt, h->plan_t.chirp, h->plan_t.bfilt};
     for (void* b : bufs) if (b) (void)hipFree(b);
+    for (const msl_handle::OpDir* o : {&h->opx, &h->opy}) {
+        void* tabs[] = {o->mtw, o->tw, o->tw2, o->qf, o->bw, o->ptab, o->cz.tw, o->cz.tw2, o->cz.bf, o->cz.bw};
+        for (void* b : tabs) if (b) (void)hipFree(b);
+    }
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
     return MSL_OK;
@@ -1837,22 +1729,15 @@ static int build_potentials(msl_handle* h, const double* pos, const int32_t* Z, 
     if ((rc = ensure_atoms(h, (size_t)n * G, (size_t)n * G + (size_t)(SF_ALIGN - 1) * nkeys_cap))) return rc;
     // R_s is Hermitian (real V): only the rows kx <= nx/2 are written and row-transformed when the inverse transform mirrors them
     // itself (every register-kernel path: col_pass_kernel<.., HERM>, ifftT2 / ifftTB / ifftTW with job.herm)
-    const bool tw_axes = h->onepass && h->opx.wave2k && h->opy.wave2k && !h->V && h->transT;
-    const bool t2_axes = h->onepass && h->opx.two && h->opy.two && h->opx.R == 16 && h->opy.R == 16 && !h->V;
-    const bool tb_axes = h->onepass && !h->V && h->transT &&
-                         (h->opx.breg || h->opx.breg2 || h->opx.cz_R) && (h->opy.breg || h->opy.breg2 || h->opy.cz_R);
+    const bool tw_axes = h->onepass && h->opx.base == AX_WAVE2K && h->opy.base == AX_WAVE2K && !h->V && h->transT;
+    const bool t2_axes = h->onepass && h->opx.base == AX_TWO && h->opy.base == AX_TWO && !h->V;
+    const bool tb_axes = h->onepass && !h->V && h->transT && h->opx.cz.R && h->opy.cz.R;      // chirp-z tables along both axes
     const bool herm_ifft = h->Rx && h->Ry;                      // four-step kernels on both axes (256 / 1024)
     const bool herm_tb = tb_axes, herm_t2 = t2_axes, herm_tw = tw_axes;
     const bool half_rows = herm_ifft || herm_tb || herm_t2 || herm_tw;
     const float vscale = (float)(1.0 / ((double)c.nx * c.ny) / (c.dx * c.dx * c.dy * c.dy));
-    struct CzRef { int R; const float2 *tw, *tw2, *bf, *bw; };      // R = 64: the 2048-point wave FFT
-    auto cz_of = [](const msl_handle::OpDir& o) -> CzRef {
-        if (o.breg2) return {64, o.tw, o.tw2, o.bf, o.bw};
-        if (o.breg) return {o.R, o.tw, nullptr, o.bf, o.bw};
-        return {o.cz_R, o.cz_tw, o.cz_tw2, o.cz_bf, o.cz_bw};
-    };
     const bool ifft_t2 = t2_axes;
-    const bool ifft_tb = h->onepass && cz_of(h->opx).R && cz_of(h->opy).R && !h->V && h->transT;
+    const bool ifft_tb = tb_axes;
     const bool ifft_tw = tw_axes;
     bool maps_sent = false;
     for (int f0 = 0; f0 < count; f0 += G) {
@@ -1987,7 +1872,7 @@ static int build_potentials(msl_handle* h, const double* pos, const int32_t* Z, 
             b.scale = vscale; b.sigma_over_pi = (float)(c.sigma / M_PI);
             if ((rc = passw(h->opx, b))) return rc;
         } else if (ifft_tb) {
-            auto pass = [&](const CzRef& o, IfftTBJob j) -> int {
+            auto pass = [&](const CzTables& o, IfftTBJob j) -> int {
                 if (o.R == 64) {                                // 513 .. 1024 points: the wave-per-line 2048-point FFT
                     constexpr int M2 = 2048, NH2 = 1024, RS = (32 * W2K_PITCH) / 2 + 1;
                     const size_t lds2 = ((size_t)M2 + 64 + NH2 + 2 + NH2 + (size_t)8 * RS) * 8;
@@ -2037,14 +1922,14 @@ static int build_potentials(msl_handle* h, const double* pos, const int32_t* Z, 
             a.in_is = a.out_t_is = (long long)npix; a.in_pitch = c.ny; a.out_t_pitch = c.nx; a.n_lines = c.nx; a.n_line = c.ny; a.n_images = n_slices;
             a.potential = 0; a.rows_parity = -1; a.slice_mod = c.nz;
             if (herm_tb) a.n_lines = c.nx / 2 + 1;                  // the other rows are their mirror images (taken by the second pass's loads)
-            if ((rc = pass(cz_of(h->opy), a))) return rc;
+            if ((rc = pass(h->opy.cz, a))) return rc;
             IfftTBJob b{};
             b.in = TRT; b.out_t = TR; b.out_rows = TRT;
             b.in_is = b.out_t_is = b.out_rows_is = (long long)npix; b.in_pitch = c.nx; b.out_t_pitch = c.ny; b.out_rows_pitch = c.nx;
             b.n_lines = c.ny; b.n_line = c.nx; b.n_images = n_slices; b.potential = 1; b.herm = herm_tb ? 1 : 0; b.slice_mod = c.nz;
             b.rows_parity = slice_is_transposed(h, 1) ? 1 : 0;       // the slices a pass along x reads stay in TRT as rows
             b.scale = vscale; b.sigma_over_pi = (float)(c.sigma / M_PI);
-            if ((rc = pass(cz_of(h->opx), b))) return rc;
+            if ((rc = pass(h->opx.cz, b))) return rc;
         } else if (ifft_t2) {
             // 512 x 512 grids: two transposing inverse-FFT passes on the register kernels (TR -> TRT along y, TRT -> TR / TRT along
             // x with the potential epilogue; slices a pass along x reads stay in TRT as rows)
@@ -2268,23 +2153,7 @@ int msl_tacaw(msl_handle* h, const void* d_src, void* d_dst, int64_t batch, int3
     } else if (cz_t) {
         if (h->opt_T != T) {
             h->opt_T = 0;
-            if ((rc = make_cz_tables(h, h->opt, T < 33 ? 33 : T))) return rc;       // (the table builder's R rule starts at 33 points)
-            if (T < 33) {                                                             // chirp of the real T: redo the two T-dependent tables
-                const int M = 256, NH = 128;
-                std::vector<float2> bw(NH, make_float2(0.f, 0.f)), bf(NH + 2, make_float2(0.f, 0.f));
-                std::vector<double> cr(M, 0.0), ci(M, 0.0);
-                for (int i = 0; i < T; ++i) {
-                    const long long q = ((long long)i * i) % (2LL * T);
-                    const double a = -M_PI * (double)q / (double)T;
-                    bw[i] = make_float2((float)cos(a), (float)sin(a));
-                    cr[i] = cos(a); ci[i] = -sin(a);
-                    if (i) { cr[M - i] = cr[i]; ci[M - i] = ci[i]; }
-                }
-                host_fft_pow2(cr, ci);
-                for (int j = 0; j <= NH; ++j) bf[j] = make_float2((float)(cr[j] / M), (float)(ci[j] / M));
-                HIPCHK(h, hipMemcpy(h->opt.cz_bw, bw.data(), NH * sizeof(float2), hipMemcpyHostToDevice));
-                HIPCHK(h, hipMemcpy(h->opt.cz_bf, bf.data(), (NH + 2) * sizeof(float2), hipMemcpyHostToDevice));
-            }
+            if ((rc = make_cz_tables(h, h->opt, T))) return rc;                   // (M = 256 below 33 frames as well)
             h->opt_T = T;
         }
     } else if ((rc = make_plan(h, h->plan_t, T))) {
@@ -2318,7 +2187,7 @@ int msl_tacaw(msl_handle* h, const void* d_src, void* d_dst, int64_t batch, int3
         if ((rc = launch_time_split(h, j))) return rc;
     } else if (cz_t) {
         TimeJob j{};
-        j.in = src; j.out = dst; j.tw = h->opt.cz_tw; j.bf = h->opt.cz_bf; j.bw = h->opt.cz_bw;
+        j.in = src; j.out = dst; j.tw = h->opt.tw; j.bf = h->opt.bf; j.bw = h->opt.bw;
         j.image_stride = (long long)T * npix; j.npix = (int)npix; j.n_images = (int)batch; j.T = T;
         auto launch = [&](auto r_c, auto cols_c, auto vec_c) -> int {
             constexpr int R = decltype(r_c)::value, COLS = decltype(cols_c)::value;
@@ -2335,7 +2204,7 @@ int msl_tacaw(msl_handle* h, const void* d_src, void* d_dst, int64_t batch, int3
         };
         using I16 = std::integral_constant<int, 16>; using I32 = std::integral_constant<int, 32>;
         const bool even = (npix % 2 == 0);
-        if (h->opt.cz_R == 16) rc = even ? launch(I16{}, I32{}, std::true_type{}) : launch(I16{}, I32{}, std::false_type{});
+        if (h->opt.R == 16) rc = even ? launch(I16{}, I32{}, std::true_type{}) : launch(I16{}, I32{}, std::false_type{});
         else rc = even ? launch(I32{}, I16{}, std::true_type{}) : launch(I32{}, I16{}, std::false_type{});
         if (rc) return rc;
     } else {
