@@ -252,6 +252,25 @@ int  msl_tacaw_dispersion(msl_handle* h, const void* d_src_f32, int64_t B, int64
  *   Replaces the masked |.| sum and frame mean of HAADFData.calculateADF (haadf_data.py:72-94). */
 int  msl_adf(msl_handle* h, const void* d_src_c64, int64_t B, int64_t T, int64_t K, int64_t ld, const uint8_t* mask, double* out);
 
+/* ---- STEM detectors: per-image detector signals, so that a scan can stream over probe batches ----
+ * msl_set_detectors: n (1..16) detectors over the handle's stored pixels (the k-window / bins, K = wx*wy of the stored spectrum):
+ *   member_K = K host uint16, bit d set <=> pixel k lies in detector d (bits >= n are ignored); signal_n = n MSL_DET_* values;
+ *   kx_wx / ky_wy = the stored k axes (wx and wy floats, WFData.kxs / kys).  Uploaded once; MSL_ERR_INVALID for n outside [1, 16]
+ *   or an unknown signal.
+ * msl_detect: out[(b*count + j)*n + d] = sum_k w_d(k) f_d(Psi[b, t0+j, k]) over a (B,T,K) complex64 array with row pitch ld,
+ *   f_d = |Psi|^2, |Psi| (the convention of HAADFData.calculateADF, haadf_data.py:50, 63), kx(k)|Psi|^2 or ky(k)|Psi|^2 with
+ *   kx(k) = kx_wx[k / wy], ky(k) = ky_wy[k % wy].  d_src == NULL: the handle's wavefunction buffer (T = n_frames, K = stored pixels,
+ *   ld = msl_result_pitch); B <= 0 there means n_probes, a smaller B leaves the last probes out (a padded probe batch).  out is HOST
+ *   memory, B*count*n float64.  One launch over every row and detector plus one float64 finishing launch; fp32 partials over at most
+ *   1024 pixels, float64 from there on, no atomics (bitwise reproducible).
+ *   Replaces, per probe batch, the masked sums of HAADFData.calculateADF (haadf_data.py:44-94) without the (P,T,nx,ny) array. */
+#define MSL_DET_INTENSITY 0
+#define MSL_DET_AMPLITUDE 1
+#define MSL_DET_COM_X 2
+#define MSL_DET_COM_Y 3
+int  msl_set_detectors(msl_handle* h, int32_t n, const uint16_t* member_K, const int32_t* signal_n, const float* kx_wx, const float* ky_wy);
+int  msl_detect(msl_handle* h, const void* d_src_c64, int64_t B, int64_t T, int64_t K, int64_t ld, int32_t t0, int32_t count, double* out);
+
 /* ---- thickness series: spectra of intermediate layers of the stack ----
  * msl_set_layers: `n` strictly increasing slice indices k in [0, nz-1).  Layer k is the wave after the transmission of slice k and
  * before the propagation that follows it -- the exit wave of the stack cut after slice k.  Every fused slice loop then also writes

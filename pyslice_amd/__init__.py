@@ -11,8 +11,9 @@ from .multislice import Probe, Propagate, create_batched_probes, probe_grid, wav
 from .calculators import MultisliceCalculator
 from .tacaw_data import TACAWData
 from .haadf_data import HAADFData
+from .stem_data import Detector, STEMData
 
 __all__ = ["Trajectory", "WFData", "Potential", "gridFromTrajectory", "getZfromElementName", "loadKirkland",
            "Probe", "Propagate", "create_batched_probes", "probe_grid", "wavelength", "m_effective",
-           "MultisliceCalculator", "TACAWData", "HAADFData"]
+           "MultisliceCalculator", "TACAWData", "HAADFData", "Detector", "STEMData"]
 __version__ = "0.1.0"

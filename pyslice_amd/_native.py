@@ -30,7 +30,9 @@ EXPORTS = [
     "msl_tacaw_stream_begin", "msl_tacaw_stream_push", "msl_tacaw_stream_finish",
     "msl_tacaw_stream_set_reference", "msl_tacaw_stream_finish_range",
     "msl_set_layers", "msl_download_layers_c128", "msl_tacaw_layer",
+    "msl_set_detectors", "msl_detect",
 ]
+DET_SIGNALS = {"intensity": 0, "amplitude": 1, "com_x": 2, "com_y": 3}      # include/mslice.h: MSL_DET_*
 
 
 class MslConfig(C.Structure):
@@ -112,6 +114,8 @@ def load():
         "msl_set_layers": (C.c_int, [vp, vp, i32]),
         "msl_download_layers_c128": (C.c_int, [vp, i32, vp, C.c_size_t]),
         "msl_tacaw_layer": (C.c_int, [vp, i32]),
+        "msl_set_detectors": (C.c_int, [vp, i32, vp, vp, vp, vp]),
+        "msl_detect": (C.c_int, [vp, vp, i64, i64, i64, i64, i32, i32, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -433,6 +437,34 @@ class Engine:
         out = np.empty(B, dtype=np.float64)
         p, b, t, k, ld = self._src(src)
         self._chk(self._lib.msl_adf(self._h, p, b, t, k, ld, _ptr(m), _ptr(out)))
+        return out
+
+    # -- STEM detectors (msl_set_detectors / msl_detect)
+    def set_detectors(self, member, signals, kxs, kys):
+        """member: (wx*wy,) uint16 bitmask per stored pixel (bit d: pixel in detector d); signals: one DET_SIGNALS name or
+        number per detector; kxs / kys: the stored k axes (wx and wy floats)"""
+        m = np.ascontiguousarray(np.asarray(member).reshape(-1), dtype=np.uint16)
+        if m.size != self.wx * self.wy:
+            raise ValueError(f"detector mask has {m.size} entries, the stored spectrum has {self.wx * self.wy}")
+        sig = np.ascontiguousarray([DET_SIGNALS.get(v, -1) if isinstance(v, str) else int(v) for v in signals], dtype=np.int32)
+        kx = np.ascontiguousarray(kxs, dtype=np.float32).reshape(-1)
+        ky = np.ascontiguousarray(kys, dtype=np.float32).reshape(-1)
+        if kx.size != self.wx or ky.size != self.wy:
+            raise ValueError(f"k axes of {kx.size} x {ky.size} values, the stored spectrum is {self.wx} x {self.wy}")
+        self._chk(self._lib.msl_set_detectors(self._h, int(sig.size), _ptr(m), _ptr(sig), _ptr(kx), _ptr(ky)))
+        self.n_detectors = int(sig.size)
+
+    def detect(self, t0=0, count=None, B=None, src=None):
+        """(B, count, n_detectors) float64 detector signals of frame slots [t0, t0+count).  src = None: the handle's own
+        wavefunction buffer (B = n_probes or fewer: the first B probes); else (device pointer, B, T, K[, ld]) of a caller's
+        complex64 array"""
+        if src is None:
+            p, b, T, k, ld = None, int(B) if B else self.n_probes, self.n_frames, self.wx * self.wy, 0
+        else:
+            p, b, T, k, ld = self._src(src)
+        count = (T - int(t0)) if count is None else int(count)
+        out = np.empty((max(b, 0), max(count, 0), getattr(self, "n_detectors", 0)), dtype=np.float64)
+        self._chk(self._lib.msl_detect(self._h, p, b, T, k, ld, int(t0), count, _ptr(out)))
         return out
 
     # -- results

@@ -80,7 +80,8 @@ def _widen_to_host(view, chunk_bytes=1 << 30):
 class MultisliceCalculator:
 
     def __init__(self, device=None, force_cpu=False, *, output="host", dtype="complex128", progress=True,
-                 gather="rank0", cache=False, k_window=None, frame_batch=None, k_bin=None, stream_tile=None, layers=None):
+                 gather="rank0", cache=False, k_window=None, frame_batch=None, k_bin=None, stream_tile=None, layers=None,
+                 detectors=None, probe_batch=None):
         """
         device / force_cpu: as the reference (calculators.py:41).  There is no CPU path here, so
         force_cpu=True raises.  Keyword-only extras (not in the reference):
@@ -101,6 +102,13 @@ class MultisliceCalculator:
                    propagation that follows it: the exit wave of the stack cut after slice k) is recorded as well.  setup()
                    sorts them, drops duplicates and appends nz - 1 (the exit wave, always the last layer); wavefunction_data
                    becomes (P,T,wx,wy,L) and WFData.layer holds the slice indices.  Not with cache, stream_tile or several ranks.
+          detectors   STEM mode: a list of up to 16 stem_data.Detector.  run_detectors() then streams the probes through the
+                   device in batches and reduces every exit spectrum to its detector values there (msl_detect), so device memory
+                   does not grow with the number of probe positions; run() is refused.  Not with cache, layers, stream_tile,
+                   k_bin (a bin sums complex pixels: |Psi|^2 of a bin is no detector signal) or several ranks; k_window is
+                   allowed (the detectors see the window only).
+          probe_batch probes per batch of run_detectors() (default: chosen in setup() from free device memory, about 256
+                   images per launch with the frame batch).  Needs detectors.
         """
         if force_cpu:
             raise NotImplementedError("pyslice_amd has no CPU path (force_cpu=True): use the reference for CPU runs")
@@ -142,6 +150,20 @@ class MultisliceCalculator:
                 raise ValueError("streaming TACAW keeps the exit wave only: stream_tile cannot be combined with layers")
             layers = list(layers)
         self._layers_arg = layers
+        if probe_batch is not None and detectors is None:
+            raise ValueError("probe_batch applies to detector runs only: give detectors=[...]")
+        if probe_batch is not None and int(probe_batch) < 1:
+            raise ValueError("probe_batch must be a positive probe count")
+        if detectors is not None:
+            from .stem_data import check_detectors
+            for what, val in (("cache", cache), ("layers", layers is not None), ("stream_tile", stream_tile is not None),
+                              ("k_bin", k_bin is not None)):
+                if val:
+                    raise ValueError(f"detectors cannot be combined with {what}" +
+                                     (" (a bin sums complex pixels: |Psi|^2 of a bin is no detector signal)" if what == "k_bin" else ""))
+            detectors = check_detectors(detectors)
+        self._detectors = detectors
+        self._probe_batch = None if probe_batch is None else int(probe_batch)
         self._layers = None                     # validated slice indices (setup), nz - 1 last
         self._engine = None
         # reference calculators.py:70-76 (display names for Z <= 36)
@@ -209,6 +231,9 @@ class MultisliceCalculator:
 
         if self.probe_positions is None:
             self.probe_positions = [(lx / 2, ly / 2)]
+        if self._detectors is not None:
+            self._setup_detectors(trajectory, slice_axis)
+            return
         self.base_probe = Probe(xs, ys, self.aperture, self.voltage_eV, device=self.device)
 
         self.n_frames = trajectory.n_frames
@@ -286,6 +311,119 @@ class MultisliceCalculator:
         self._engine.set_probes(self.aperture, np.asarray(self.probe_positions, dtype=np.float64))
         self._Z = np.asarray(trajectory.atom_types, dtype=np.int32)
 
+    def _setup_detectors(self, trajectory, slice_axis):
+        """setup() of a detector run: the memberships on the host, then an engine of Pc <= P probes x one frame batch of slots"""
+        from .stem_data import detector_bitmask
+        nx, ny = self.nx, self.ny
+        self._rank, self._world = distributed.rank_world()
+        if self._world > 1:
+            raise NotImplementedError("detectors: runs over several ranks are not supported (run_detectors() is single-process)")
+        lam = wavelength(self.voltage_eV)
+        kxs, kys = self._k_axes()
+        bits = detector_bitmask(self._detectors, kxs, kys, lam)
+        for d, det in enumerate(self._detectors):
+            if not ((bits >> d) & 1).any():
+                raise ValueError(f"detector {det.name!r} contains no stored pixel of the {len(kxs)} x {len(kys)} spectrum")
+        self._det_bits = bits
+        self.base_probe = Probe(self.xs, self.ys, self.aperture, self.voltage_eV, device=self.device)
+        self.n_frames = trajectory.n_frames
+        self.n_probes = len(self.probe_positions)
+        self.wavefunction_data = None
+        self._frames = list(range(self.n_frames))
+        dev = self.device
+        slice_coords = np.asarray([self.xs, self.ys, self.zs][slice_axis], dtype=np.float64)
+        n_slices = len(slice_coords)
+        dz = self.zs[1] - self.zs[0] if self.nz > 1 else 0.5
+        self._engine = None
+        P, T = self.n_probes, self.n_frames
+        wx, wy = self._k_window if self._k_window is not None else (nx, ny)
+        pitch = (wx * wy + 31) // 32 * 32
+        # Pc x frame batch near the ~256 images per launch of default_frame_batch: 256 probes x 1 frame for a scan, all probes x
+        # ceil(256 / P) frames for a few; halved while the three work buffers and the result ring of Pc x B images, the B
+        # transmission stacks and the phase tables (up to 6 GB) do not fit in 0.9 x the free device memory
+        Pc = min(P, self._probe_batch if self._probe_batch is not None else 256)
+        batch = self._frame_batch if self._frame_batch is not None else default_frame_batch(Pc, n_slices, nx, ny)
+        batch = max(1, min(batch, T))
+        auto = self._probe_batch is None
+        if auto and TORCH_AVAILABLE and torch.cuda.is_available():
+            try:
+                free_b = float(torch.cuda.mem_get_info(_device_index(dev))[0])
+            except Exception:                              # pragma: no cover  (no device visible to torch: msl_create decides)
+                free_b = None
+            if free_b is not None:
+                tables = min(6e9, batch * len(trajectory.atom_types) * (nx // 2 + ny // 2 + 2) * 8.0)
+                while Pc > 1 and Pc * batch * (32.0 * nx * ny + 8.0 * pitch) + batch * 16.0 * n_slices * nx * ny + tables + 1e9 > 0.9 * free_b:
+                    Pc = max(1, Pc // 2)
+        while True:
+            try:
+                self._engine = _native.Engine(nx, ny, n_slices, self.dx, self.dy, dz, lam, interaction_sigma(self.voltage_eV),
+                                              n_probes=Pc, n_frames=batch, device=_device_index(dev), window=self._k_window,
+                                              frame_batch=batch)
+                break
+            except MemoryError:
+                if not auto or (Pc <= 1 and batch <= 1):
+                    raise
+                if Pc > 1:
+                    Pc = max(1, Pc // 2)
+                else:
+                    batch = max(1, batch // 2)
+                logger.info(f"device memory: probe batch {Pc}, frame batch {batch}")
+        self.probe_batch = Pc
+        self._engine.set_kirkland(loadKirkland())
+        lo, hi = slice_edges(slice_coords)
+        self._engine.set_slices(lo, hi)
+        self._engine.set_detectors(bits.reshape(-1), [d.signal for d in self._detectors], kxs, kys)
+        self._Z = np.asarray(trajectory.atom_types, dtype=np.int32)
+
+    def run_detectors(self):
+        """STEM detector signals of every probe and frame: for each frame batch the potentials are built once, then every probe
+        batch goes through the slice loop and msl_detect reduces its exit spectra to the detector values.  -> STEMData with
+        signals (P, T, D) float64."""
+        from .stem_data import STEMData
+        if self._engine is None:
+            raise RuntimeError("call setup() before run_detectors()")
+        if self._detectors is None:
+            raise RuntimeError("run_detectors() needs MultisliceCalculator(detectors=[...])")
+        eng = self._engine
+        t0 = time.time()
+        P, T, D = self.n_probes, self.n_frames, len(self._detectors)
+        Pc, B = eng.n_probes, eng.frame_batch
+        pos = np.asarray(self.probe_positions, dtype=np.float64).reshape(-1, 2)
+        signals = np.zeros((P, T, D), dtype=np.float64)
+        bar = None
+        if self._progress:
+            try:
+                from tqdm import tqdm
+                bar = tqdm(total=T, desc="Processing frames", unit="frame")
+            except ImportError:
+                bar = None
+        for s0 in range(0, T, B):
+            n = min(B, T - s0)
+            if B > 1:
+                eng.build_potentials(self.trajectory.positions[s0:s0 + n], self._Z, self.slice_axis)
+            else:
+                eng.build_potential(self.trajectory.positions[s0], self._Z, self.slice_axis)
+            for p0 in range(0, P, Pc):
+                real = min(Pc, P - p0)
+                xy = pos[p0:p0 + real]
+                if real < Pc:                                  # last batch: pad by repeating its last position
+                    xy = np.concatenate([xy, np.repeat(xy[-1:], Pc - real, axis=0)])
+                eng.set_probes(self.aperture, xy)
+                if B > 1:
+                    eng.propagate_frames(0, n)
+                else:
+                    eng.propagate_frame(0)
+                signals[p0:p0 + real, s0:s0 + n] = eng.detect(0, n, B=real)
+            if bar is not None:
+                bar.update(n)
+        if bar is not None:
+            bar.close()
+        self.elapsed = time.time() - t0
+        self.frames_computed, self.frames_cached = T, 0
+        kxs, kys = self._k_axes()
+        return STEMData(signals=signals, detectors=list(self._detectors), probe_positions=self.probe_positions,
+                        time=np.arange(T) * self.trajectory.timestep, kxs=_as_tensor(kxs), kys=_as_tensor(kys), probe=self.base_probe)
+
     def _check_layers(self, n_slices, world):
         """the `layers` argument -> sorted unique slice indices with n_slices - 1 last (before any device work)"""
         if self._layers_arg is None:
@@ -321,6 +459,8 @@ class MultisliceCalculator:
 
     def run(self) -> WFData:
         """reference calculators.py:163-250: all frames, then pack WFData."""
+        if self._detectors is not None:
+            raise RuntimeError("detectors are set: the device holds one probe batch at a time -- call run_detectors()")
         if self._engine is None:
             raise RuntimeError("call setup() before run()")
         if self._stream_tile is not None:

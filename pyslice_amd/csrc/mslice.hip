@@ -21,6 +21,7 @@
 #include "tacaw_time.h"
 #include "tacaw_launch.h"
 #include "layer_tap.h"
+#include "detect.h"
 
 using namespace msl;
 
@@ -142,6 +143,13 @@ struct msl_handle {
     float2* tap = nullptr;
     float2* tap_cx = nullptr;
     float2* tap_cy = nullptr;
+    // STEM detectors (msl_set_detectors): membership bits per stored pixel, the stored k axes, the signal of every detector
+    uint16_t* det_mask = nullptr;
+    float* det_kx = nullptr;
+    float* det_ky = nullptr;
+    int det_n = 0, det_wy = 0;
+    size_t det_K = 0;
+    uint32_t det_amp = 0, det_cx = 0, det_cy = 0;
     double* d_abcd = nullptr;
     double* d_lo = nullptr;
     double* d_hi = nullptr;
@@ -1546,7 +1554,7 @@ int msl_destroy(msl_handle* h) {
                     h->d_pos, h->d_Z, h->d_key, h->d_order, h->d_u1, h->d_u2, h->d_ex, h->d_ey, h->d_counts, h->d_start,
                     h->d_z2s, h->d_species, h->d_ff, h->d_xy, h->plan_x.tw, h->plan_y.tw, h->plan_t.tw, h->tw4_x, h->tw4_y,
                     h->scratch, h->psiT, h->psi0T, h->transT, h->bin_stage, h->st_acc, h->st_s1, h->st_s2, h->st_tw, h->st_bins, h->st_ref,
-                    h->opt.tw, h->opt.tw2, h->opt.bf, h->opt.bw, h->tsplit_tw, h->plan_x.chirp, h->plan_x.bfilt, h->plan_y.chirp, h->plan_y.bfilt, h->plan_t.chirp, h->plan_t.bfilt};
+                    h->opt.tw, h->opt.tw2, h->opt.bf, h->opt.bw, h->tsplit_tw, h->det_mask, h->det_kx, h->det_ky, h->plan_x.chirp, h->plan_x.bfilt, h->plan_y.chirp, h->plan_y.bfilt, h->plan_t.chirp, h->plan_t.bfilt};
     for (void* b : bufs) if (b) (void)hipFree(b);
     for (const msl_handle::OpDir* o : {&h->opx, &h->opy}) {
         void* tabs[] = {o->mtw, o->tw, o->tw2, o->qf, o->bw, o->ptab, o->cz.tw, o->cz.tw2, o->cz.bf, o->cz.bw};
@@ -2502,6 +2510,105 @@ int msl_adf(msl_handle* h, const void* d_src_c64, int64_t B, int64_t T, int64_t 
         for (double v : rows) s += v;
         out[b] = s / (double)T;                // mean over frames of the annulus sum (haadf_data.py:80)
     }
+    return MSL_OK;
+}
+
+// ---- STEM detectors (detect.h) ----------------------------------------------------------------------------
+int msl_set_detectors(msl_handle* h, int32_t n, const uint16_t* member_K, const int32_t* signal_n, const float* kx_wx, const float* ky_wy) {
+    if (!h || !member_K || !signal_n || !kx_wx || !ky_wy) return fail(h, MSL_ERR_INVALID, "msl_set_detectors: null argument");
+    if (n < 1 || n > DET_MAX) return fail(h, MSL_ERR_INVALID, "msl_set_detectors: %d detectors outside [1,%d]", n, DET_MAX);
+    uint32_t amp = 0, cx = 0, cy = 0;
+    for (int d = 0; d < n; ++d) {
+        switch (signal_n[d]) {
+            case MSL_DET_INTENSITY: break;
+            case MSL_DET_AMPLITUDE: amp |= 1u << d; break;
+            case MSL_DET_COM_X: cx |= 1u << d; break;
+            case MSL_DET_COM_Y: cy |= 1u << d; break;
+            default: return fail(h, MSL_ERR_INVALID, "msl_set_detectors: detector %d has unknown signal %d", d, signal_n[d]);
+        }
+    }
+    const int sx = h->wx / h->bx, sy = h->wy / h->by;         // stored k axes: the (binned) window
+    const size_t K = h->wpix;
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    std::vector<uint16_t> m(member_K, member_K + K);
+    const uint16_t keep = (uint16_t)((1u << n) - 1u);
+    for (auto& v : m) v &= keep;                               // bits of absent detectors never count
+    int rc;
+    if ((rc = dalloc(h, &h->det_mask, K)) || (rc = dalloc(h, &h->det_kx, (size_t)sx)) || (rc = dalloc(h, &h->det_ky, (size_t)sy))) {
+        h->det_n = 0;
+        return rc;
+    }
+    HIPCHK(h, hipMemcpyAsync(h->det_mask, m.data(), K * sizeof(uint16_t), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->det_kx, kx_wx, (size_t)sx * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->det_ky, ky_wy, (size_t)sy * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    h->det_n = n; h->det_K = K; h->det_wy = sy;
+    h->det_amp = amp; h->det_cx = cx; h->det_cy = cy;
+    return MSL_OK;
+}
+
+extern "C++" template <int ND>
+static void launch_detect(msl_handle* h, int mode, bool vec, dim3 grid, const float2* src, long long T, long long t0, long long count, long long ld,
+                          long long K, long long rows, int rows_per_wg, float* part) {
+#define MSL_DET_LAUNCH(M, V)                                                                                                       \
+    hipLaunchKernelGGL((detect_tile_kernel<ND, M, V>), grid, dim3(256), 0, h->stream, src, T, t0, count, ld, K, rows, rows_per_wg, \
+                       h->det_mask, h->det_kx, h->det_ky, h->det_wy, h->det_amp, h->det_cx, h->det_cy, part)
+    if (vec) {
+        if (mode == 0) MSL_DET_LAUNCH(0, true); else if (mode == 1) MSL_DET_LAUNCH(1, true); else MSL_DET_LAUNCH(2, true);
+    } else {
+        if (mode == 0) MSL_DET_LAUNCH(0, false); else if (mode == 1) MSL_DET_LAUNCH(1, false); else MSL_DET_LAUNCH(2, false);
+    }
+#undef MSL_DET_LAUNCH
+}
+
+int msl_detect(msl_handle* h, const void* d_src_c64, int64_t B, int64_t T, int64_t K, int64_t ld, int32_t t0, int32_t count, double* out) {
+    if (!h || !out) return fail(h, MSL_ERR_INVALID, "msl_detect: null argument");
+    if (h->det_n == 0) return fail(h, MSL_ERR_STATE, "msl_detect: no detectors (call msl_set_detectors)");
+    if (!d_src_c64) {
+        if (!h->wf) return fail(h, MSL_ERR_STATE, "msl_detect: no wavefunction buffer");
+        if (B < 1) B = h->cfg.n_probes;
+        if (B > h->cfg.n_probes) return fail(h, MSL_ERR_INVALID, "msl_detect: %lld probes, the handle has %d", (long long)B, h->cfg.n_probes);
+        d_src_c64 = h->wf; T = h->cfg.n_frames; K = (int64_t)h->wpix; ld = (int64_t)h->wpitch;
+    } else if (ld == 0) {
+        ld = K;
+    }
+    if (B < 1 || T < 1 || K < 1 || ld < K) return fail(h, MSL_ERR_INVALID, "msl_detect: bad shape (%lld,%lld,%lld) ld %lld", (long long)B, (long long)T,
+                                                     (long long)K, (long long)ld);
+    if ((size_t)K != h->det_K) return fail(h, MSL_ERR_INVALID, "msl_detect: rows of %lld pixels, the detectors cover %zu", (long long)K, h->det_K);
+    if (count < 1 || t0 < 0 || (int64_t)t0 + count > T)
+        return fail(h, MSL_ERR_INVALID, "msl_detect: frame slots [%d,%d) outside [0,%lld)", t0, t0 + count, (long long)T);
+    const int64_t rows = B * count;
+    if (rows > 0x7fffffffLL) return fail(h, MSL_ERR_UNSUPPORTED, "msl_detect: more than 2^31 rows");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    const int n = h->det_n;
+    const int ND = n <= 4 ? 4 : (n <= 8 ? 8 : 16);
+    const int64_t TP = 64 * (64 / ND);
+    const int64_t n_tiles = (K + TP - 1) / TP;
+    if (n_tiles > 0x7fffffffLL) return fail(h, MSL_ERR_UNSUPPORTED, "msl_detect: rows too long");
+    // rows per workgroup: the tile's coefficients are built once per row block; at most 65535 row blocks (grid.y)
+    int64_t per = std::min<int64_t>(64, (rows + 3) / 4 * 4);
+    per = std::max<int64_t>(per, ((rows + 65534) / 65535 + 3) / 4 * 4);
+    const int64_t blocks_y = (rows + per - 1) / per;
+    const size_t part_bytes = ((size_t)rows * n_tiles * ND * sizeof(float) + 255) & ~(size_t)255;
+    const size_t out_bytes = (size_t)rows * n * sizeof(double);
+    int rc = ensure_scratch(h, part_bytes + out_bytes);
+    if (rc) return rc;
+    float* d_part = (float*)h->scratch;
+    double* d_out = (double*)(h->scratch + part_bytes);
+    const int mode = h->det_amp == 0 ? 0 : (h->det_amp == (1u << n) - 1u ? 1 : 2);
+    const bool vec = (ld % 2 == 0) && (((uintptr_t)d_src_c64 & 15) == 0);
+    const dim3 grid((unsigned)n_tiles, (unsigned)blocks_y);
+    const float2* src = (const float2*)d_src_c64;
+    if (ND == 4) launch_detect<4>(h, mode, vec, grid, src, T, t0, count, ld, K, rows, (int)per, d_part);
+    else if (ND == 8) launch_detect<8>(h, mode, vec, grid, src, T, t0, count, ld, K, rows, (int)per, d_part);
+    else launch_detect<16>(h, mode, vec, grid, src, T, t0, count, ld, K, rows, (int)per, d_part);
+    HIPCHK(h, hipGetLastError());
+    if (ND == 4) hipLaunchKernelGGL(detect_finish_kernel<4>, dim3((unsigned)rows), dim3(256), 0, h->stream, d_part, (long long)n_tiles, n, d_out);
+    else if (ND == 8) hipLaunchKernelGGL(detect_finish_kernel<8>, dim3((unsigned)rows), dim3(256), 0, h->stream, d_part, (long long)n_tiles, n, d_out);
+    else hipLaunchKernelGGL(detect_finish_kernel<16>, dim3((unsigned)rows), dim3(256), 0, h->stream, d_part, (long long)n_tiles, n, d_out);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
     return MSL_OK;
 }
 

@@ -1,0 +1,117 @@
+"""STEM detector runs (MultisliceCalculator(detectors=...).run_detectors()): slice-steps/s of a scan streamed over probe batches,
+the device time of the detector pass (msl_detect) and its share of the run, and the engine's device memory.  One JSON line per
+probe batch.  --detect-only times msl_detect alone on resident images and reports its HBM rate against 8 TB/s.
+    python tools/stem_bench.py [--scan 64] [--n 1024] [--slices 200] [--frames 1] [--probe-batch 64 256] [--detectors 8]
+    python tools/stem_bench.py --detect-only [--images 256] [--n 1024] [--detectors 8] [--reps 20]"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import pyslice_amd as ps  # noqa: E402
+from pyslice_amd import _native  # noqa: E402
+from pyslice_amd.multislice import wavelength  # noqa: E402
+from pyslice_amd.stem_data import detector_bitmask  # noqa: E402
+
+HBM_PEAK = 8e12
+
+
+def detectors(n):
+    """BF, ABF, ADF, HAADF (|Psi|), four DPC segments of the BF disc, then CoM x / y, ... up to n"""
+    D = ps.Detector
+    a = 30.0
+    dets = [D("bf", outer=a), D("abf", inner=a / 2, outer=a), D("adf", inner=1.5 * a, outer=150.0), D("haadf", inner=1.5 * a, signal="amplitude"),
+            D("dpc0", outer=a, azimuth=(0, 90)), D("dpc1", outer=a, azimuth=(90, 180)), D("dpc2", outer=a, azimuth=(180, 270)),
+            D("dpc3", outer=a, azimuth=(270, 360)), D("comx", signal="com_x"), D("comy", signal="com_y")]
+    dets += [D(f"ring{i}", inner=10.0 * i, outer=10.0 * i + 10.0) for i in range(16)]
+    return dets[:n]
+
+
+def detect_only(args):
+    import torch
+    n, B = args.n, args.images
+    dets = detectors(args.detectors)
+    eng = _native.Engine(n, n, 1, 0.1, 0.1, 0.5, wavelength(100e3), 0.0, n_probes=1, n_frames=0)
+    kx = np.fft.fftshift(np.fft.fftfreq(n, 0.1)).astype(np.float32)
+    eng.set_detectors(detector_bitmask(dets, kx, kx, wavelength(100e3)).reshape(-1), [d.signal for d in dets], kx, kx)
+    g = torch.Generator(device="cuda").manual_seed(1)
+    W = torch.randn((B, 1, n * n), dtype=torch.complex64, device="cuda", generator=g)
+    torch.cuda.synchronize()
+    src = (W.data_ptr(), B, 1, n * n)
+    eng.detect(src=src)                                   # warm-up
+    times = []
+    for _ in range(args.reps):
+        t0 = time.perf_counter()
+        eng.detect(src=src)                               # one launch + the finishing launch + 8 B x B x D back, synchronous
+        times.append(time.perf_counter() - t0)
+    dt = float(np.median(times))
+    nbytes = B * n * n * 8
+    print(json.dumps({"case": "detect_only", "images": B, "grid": n, "detectors": len(dets), "ms_median": round(dt * 1e3, 4),
+                      "ms_min": round(min(times) * 1e3, 4), "GB_per_s": round(nbytes / dt / 1e9, 1),
+                      "fraction_of_8TBps": round(nbytes / dt / HBM_PEAK, 3)}), flush=True)
+    eng.close()
+
+
+def scan(args, pb):
+    import torch
+    from pyslice_amd.synthetic import synthetic_trajectory
+    tr = synthetic_trajectory(args.n, args.slices, args.frames, seed=5)
+    xs, ys, zs, lx, ly, lz = ps.gridFromTrajectory(tr)
+    s = args.scan
+    pp = [(x, y) for x in np.linspace(0.25 * lx, 0.75 * lx, s) for y in np.linspace(0.25 * ly, 0.75 * ly, s)]
+    free0 = torch.cuda.mem_get_info()[0]
+    calc = ps.MultisliceCalculator(progress=False, detectors=detectors(args.detectors), probe_batch=pb)
+    calc.setup(tr, aperture=30.0, voltage_eV=100e3, probe_positions=pp)
+    eng = calc._engine
+    used = free0 - torch.cuda.mem_get_info()[0]
+    buf = {name: eng.buffer_bytes(getattr(_native, "BUF_" + name)) for name in ("PROBES", "EXIT", "TRANSMISSION", "WAVEFUNCTION")}
+    # time every detector pass on its own: wait for the slice loop, then the (synchronous) msl_detect
+    spent = []
+    plain_detect = eng.detect
+
+    def timed_detect(*a, **k):
+        eng.synchronize()
+        t0 = time.perf_counter()
+        out = plain_detect(*a, **k)
+        spent.append(time.perf_counter() - t0)
+        return out
+    eng.detect = timed_detect
+    t0 = time.perf_counter()
+    st = calc.run_detectors()
+    dt = time.perf_counter() - t0
+    steps = len(pp) * args.frames * args.slices
+    print(json.dumps({"case": "scan", "scan": f"{s}x{s}", "grid": args.n, "slices": args.slices, "frames": args.frames,
+                      "probe_batch": eng.n_probes, "frame_batch": eng.frame_batch, "detectors": len(st.detectors),
+                      "s_total": round(dt, 3), "slice_steps_per_s": round(steps / dt),
+                      "detect_ms_per_batch": round(1e3 * float(np.median(spent)), 4), "detect_share_pct": round(100.0 * sum(spent) / dt, 3),
+                      "engine_buffer_bytes": buf, "device_bytes_after_setup": int(used),
+                      "signals_finite": bool(np.isfinite(st.signals).all())}), flush=True)
+    calc._engine = None
+    eng.close()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--detect-only", action="store_true")
+    ap.add_argument("--scan", type=int, default=64)
+    ap.add_argument("--n", type=int, default=1024)
+    ap.add_argument("--slices", type=int, default=200)
+    ap.add_argument("--frames", type=int, default=1)
+    ap.add_argument("--probe-batch", type=int, nargs="+", default=[64, 256])
+    ap.add_argument("--detectors", type=int, default=8)
+    ap.add_argument("--images", type=int, default=256)
+    ap.add_argument("--reps", type=int, default=20)
+    args = ap.parse_args()
+    if args.detect_only:
+        detect_only(args)
+        return
+    for pb in args.probe_batch:
+        scan(args, pb)
+
+
+if __name__ == "__main__":
+    main()
