@@ -271,6 +271,18 @@ int  msl_adf(msl_handle* h, const void* d_src_c64, int64_t B, int64_t T, int64_t
 int  msl_set_detectors(msl_handle* h, int32_t n, const uint16_t* member_K, const int32_t* signal_n, const float* kx_wx, const float* ky_wy);
 int  msl_detect(msl_handle* h, const void* d_src_c64, int64_t B, int64_t T, int64_t K, int64_t ld, int32_t t0, int32_t count, double* out);
 
+/* ---- diffraction patterns: frame-summed |Psi|^2 on a pixelated detector (CBED / 4D-STEM), per probe batch ----
+ * msl_diffract: out[(b*mx + ix)*my + iy] = sum_{j<count} sum_{a<bx} sum_{c<by} |Psi[b, t0+j, (ix*bx+a)*wy + iy*by+c]|^2 over a (B,T,K = wx*wy)
+ *   complex64 array with row pitch ld, mx = wx/bx, my = wy/by: the SUM over the count frame slots (the caller divides for the
+ *   frozen-phonon mean) of the intensity in every bx x by detector pixel.  Source arguments as msl_detect: d_src == NULL is the handle's
+ *   wavefunction buffer (T = n_frames, K = stored pixels, ld = msl_result_pitch, wx x wy must be the stored window, B <= 0 means
+ *   n_probes, a smaller B leaves the padded probes out).  out is HOST memory, B*mx*my float64.  MSL_ERR_INVALID when bx does not
+ *   divide wx or by not wy, wx*wy != K, ld < K, or [t0, t0+count) leaves [0, T).  Needs no set-up and keeps no state.
+ *   One launch, every complex value read once; fp32 |Psi|^2 and fp32 partial sums of at most 8 addends, float64 from there on, no
+ *   atomics (bitwise reproducible).  Unlike bin_nx / bin_ny of the configuration, which add complex pixels, these bins add intensities. */
+int  msl_diffract(msl_handle* h, const void* d_src_c64, int64_t B, int64_t T, int64_t K, int64_t ld, int32_t t0, int32_t count, int32_t wx, int32_t wy,
+                  int32_t bx, int32_t by, double* out);
+
 /* ---- thickness series: spectra of intermediate layers of the stack ----
  * msl_set_layers: `n` strictly increasing slice indices k in [0, nz-1).  Layer k is the wave after the transmission of slice k and
  * before the propagation that follows it -- the exit wave of the stack cut after slice k.  Every fused slice loop then also writes

@@ -12,8 +12,9 @@ from .calculators import MultisliceCalculator
 from .tacaw_data import TACAWData
 from .haadf_data import HAADFData
 from .stem_data import Detector, STEMData
+from .diffraction_data import Diffraction, DiffractionData
 
 __all__ = ["Trajectory", "WFData", "Potential", "gridFromTrajectory", "getZfromElementName", "loadKirkland",
            "Probe", "Propagate", "create_batched_probes", "probe_grid", "wavelength", "m_effective",
-           "MultisliceCalculator", "TACAWData", "HAADFData", "Detector", "STEMData"]
+           "MultisliceCalculator", "TACAWData", "HAADFData", "Detector", "STEMData", "Diffraction", "DiffractionData"]
 __version__ = "0.1.0"

@@ -30,7 +30,7 @@ EXPORTS = [
     "msl_tacaw_stream_begin", "msl_tacaw_stream_push", "msl_tacaw_stream_finish",
     "msl_tacaw_stream_set_reference", "msl_tacaw_stream_finish_range",
     "msl_set_layers", "msl_download_layers_c128", "msl_tacaw_layer",
-    "msl_set_detectors", "msl_detect",
+    "msl_set_detectors", "msl_detect", "msl_diffract",
 ]
 DET_SIGNALS = {"intensity": 0, "amplitude": 1, "com_x": 2, "com_y": 3}      # include/mslice.h: MSL_DET_*
 
@@ -116,6 +116,7 @@ def load():
         "msl_tacaw_layer": (C.c_int, [vp, i32]),
         "msl_set_detectors": (C.c_int, [vp, i32, vp, vp, vp, vp]),
         "msl_detect": (C.c_int, [vp, vp, i64, i64, i64, i64, i32, i32, vp]),
+        "msl_diffract": (C.c_int, [vp, vp, i64, i64, i64, i64, i32, i32, i32, i32, i32, i32, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -465,6 +466,24 @@ class Engine:
         count = (T - int(t0)) if count is None else int(count)
         out = np.empty((max(b, 0), max(count, 0), getattr(self, "n_detectors", 0)), dtype=np.float64)
         self._chk(self._lib.msl_detect(self._h, p, b, T, k, ld, int(t0), count, _ptr(out)))
+        return out
+
+    # -- diffraction patterns (msl_diffract)
+    def diffract(self, t0=0, count=None, B=None, bin=(1, 1), src=None):
+        """(B, wx/bx, wy/by) float64: |Psi|^2 summed over the frame slots [t0, t0+count) and over every bx x by block of pixels
+        (a SUM over the frames: divide by count for the mean).  src = None: the handle's own wavefunction buffer (B = n_probes or
+        fewer: the first B probes); else (device pointer, B, T, wx, wy[, ld]) of a caller's complex64 (B, T, wx*wy) array"""
+        bx, by = int(bin[0]), int(bin[1])
+        if src is None:
+            p, b, T, wx, wy, ld = None, int(B) if B else self.n_probes, self.n_frames, self.wx, self.wy, 0
+        else:
+            ptr, b, T, wx, wy = src[:5]
+            p, b, T, wx, wy = C.c_void_p(int(ptr)), int(b), int(T), int(wx), int(wy)
+            ld = int(src[5]) if len(src) > 5 else wx * wy
+        count = (T - int(t0)) if count is None else int(count)
+        ok = bx > 0 and by > 0 and wx > 0 and wy > 0 and wx % bx == 0 and wy % by == 0       # (else the library refuses: no output is read)
+        out = np.empty((max(b, 0), wx // bx, wy // by) if ok else (1,), dtype=np.float64)
+        self._chk(self._lib.msl_diffract(self._h, p, b, T, wx * wy, ld, int(t0), count, wx, wy, bx, by, _ptr(out)))
         return out
 
     # -- results

@@ -81,7 +81,7 @@ class MultisliceCalculator:
 
     def __init__(self, device=None, force_cpu=False, *, output="host", dtype="complex128", progress=True,
                  gather="rank0", cache=False, k_window=None, frame_batch=None, k_bin=None, stream_tile=None, layers=None,
-                 detectors=None, probe_batch=None):
+                 detectors=None, probe_batch=None, diffraction=None):
         """
         device / force_cpu: as the reference (calculators.py:41).  There is no CPU path here, so
         force_cpu=True raises.  Keyword-only extras (not in the reference):
@@ -107,8 +107,14 @@ class MultisliceCalculator:
                    does not grow with the number of probe positions; run() is refused.  Not with cache, layers, stream_tile,
                    k_bin (a bin sums complex pixels: |Psi|^2 of a bin is no detector signal) or several ranks; k_window is
                    allowed (the detectors see the window only).
-          probe_batch probes per batch of run_detectors() (default: chosen in setup() from free device memory, about 256
-                   images per launch with the frame batch).  Needs detectors.
+          diffraction 4D-STEM mode: a diffraction_data.Diffraction(bin=(bx, by)).  run_diffraction() streams the probes through
+                   the device as run_detectors() does and reduces every probe batch, there (msl_diffract), to |Psi|^2 summed over
+                   the frames of the batch and over every bx x by block of stored pixels: the result is the frame-averaged
+                   pattern of every probe position on a pixelated detector, (P, wx/bx, wy/by) float64 on the host.  Same
+                   refusals as detectors (k_bin adds complex pixels, the bin here adds intensities); with detectors as well, one
+                   propagation feeds both.  setup() raises ValueError when the bin does not divide the stored spectrum.
+          probe_batch probes per batch of run_detectors() / run_diffraction() (default: chosen in setup() from free device
+                   memory, about 256 images per launch with the frame batch).  Needs detectors or diffraction.
         """
         if force_cpu:
             raise NotImplementedError("pyslice_amd has no CPU path (force_cpu=True): use the reference for CPU runs")
@@ -150,8 +156,8 @@ class MultisliceCalculator:
                 raise ValueError("streaming TACAW keeps the exit wave only: stream_tile cannot be combined with layers")
             layers = list(layers)
         self._layers_arg = layers
-        if probe_batch is not None and detectors is None:
-            raise ValueError("probe_batch applies to detector runs only: give detectors=[...]")
+        if probe_batch is not None and detectors is None and diffraction is None:
+            raise ValueError("probe_batch applies to detector and diffraction runs only: give detectors=[...] or diffraction=Diffraction(...)")
         if probe_batch is not None and int(probe_batch) < 1:
             raise ValueError("probe_batch must be a positive probe count")
         if detectors is not None:
@@ -163,6 +169,16 @@ class MultisliceCalculator:
                                      (" (a bin sums complex pixels: |Psi|^2 of a bin is no detector signal)" if what == "k_bin" else ""))
             detectors = check_detectors(detectors)
         self._detectors = detectors
+        if diffraction is not None:
+            from .diffraction_data import Diffraction
+            if not isinstance(diffraction, Diffraction):
+                raise ValueError(f"diffraction: expected a Diffraction object, got {diffraction!r}")
+            for what, val in (("cache", cache), ("layers", layers is not None), ("stream_tile", stream_tile is not None),
+                              ("k_bin", k_bin is not None)):
+                if val:
+                    raise ValueError(f"diffraction cannot be combined with {what}" +
+                                     (" (a bin sums complex pixels; Diffraction(bin=...) sums their intensities)" if what == "k_bin" else ""))
+        self._diffraction = diffraction
         self._probe_batch = None if probe_batch is None else int(probe_batch)
         self._layers = None                     # validated slice indices (setup), nz - 1 last
         self._engine = None
@@ -231,8 +247,22 @@ class MultisliceCalculator:
 
         if self.probe_positions is None:
             self.probe_positions = [(lx / 2, ly / 2)]
-        if self._detectors is not None:
-            self._setup_detectors(trajectory, slice_axis)
+        if self._detectors is not None or self._diffraction is not None:
+            # probe-batch runs: every check on the host first, then an engine of Pc <= P probes x one frame batch of result slots
+            self._rank, self._world = distributed.rank_world()
+            if self._world > 1:
+                mode = "detectors" if self._detectors is not None else "diffraction"
+                raise NotImplementedError(f"{mode}: runs over several ranks are not supported (run_detectors() / run_diffraction() are "
+                                          "single-process)")
+            if self._diffraction is not None:
+                wx, wy = self._k_window if self._k_window is not None else (nx, ny)
+                bx, by = self._diffraction.bin
+                if wx % bx or wy % by:
+                    raise ValueError(f"the stored spectrum {wx} x {wy} is not a multiple of the diffraction bin {bx} x {by}")
+            if self._detectors is not None:
+                self._setup_detectors(trajectory, slice_axis)
+            else:
+                self._setup_probe_batches(trajectory, slice_axis)
             return
         self.base_probe = Probe(xs, ys, self.aperture, self.voltage_eV, device=self.device)
 
@@ -312,12 +342,8 @@ class MultisliceCalculator:
         self._Z = np.asarray(trajectory.atom_types, dtype=np.int32)
 
     def _setup_detectors(self, trajectory, slice_axis):
-        """setup() of a detector run: the memberships on the host, then an engine of Pc <= P probes x one frame batch of slots"""
+        """setup() of a detector run: the memberships on the host, then the probe-batch engine, then the memberships onto it"""
         from .stem_data import detector_bitmask
-        nx, ny = self.nx, self.ny
-        self._rank, self._world = distributed.rank_world()
-        if self._world > 1:
-            raise NotImplementedError("detectors: runs over several ranks are not supported (run_detectors() is single-process)")
         lam = wavelength(self.voltage_eV)
         kxs, kys = self._k_axes()
         bits = detector_bitmask(self._detectors, kxs, kys, lam)
@@ -325,6 +351,13 @@ class MultisliceCalculator:
             if not ((bits >> d) & 1).any():
                 raise ValueError(f"detector {det.name!r} contains no stored pixel of the {len(kxs)} x {len(kys)} spectrum")
         self._det_bits = bits
+        self._setup_probe_batches(trajectory, slice_axis)
+        self._engine.set_detectors(bits.reshape(-1), [d.signal for d in self._detectors], kxs, kys)
+
+    def _setup_probe_batches(self, trajectory, slice_axis):
+        """the engine of a run that streams probe batches (detectors, diffraction): Pc <= P probes x one frame batch of slots"""
+        nx, ny = self.nx, self.ny
+        lam = wavelength(self.voltage_eV)
         self.base_probe = Probe(self.xs, self.ys, self.aperture, self.voltage_eV, device=self.device)
         self.n_frames = trajectory.n_frames
         self.n_probes = len(self.probe_positions)
@@ -372,24 +405,17 @@ class MultisliceCalculator:
         self._engine.set_kirkland(loadKirkland())
         lo, hi = slice_edges(slice_coords)
         self._engine.set_slices(lo, hi)
-        self._engine.set_detectors(bits.reshape(-1), [d.signal for d in self._detectors], kxs, kys)
         self._Z = np.asarray(trajectory.atom_types, dtype=np.int32)
 
-    def run_detectors(self):
-        """STEM detector signals of every probe and frame: for each frame batch the potentials are built once, then every probe
-        batch goes through the slice loop and msl_detect reduces its exit spectra to the detector values.  -> STEMData with
-        signals (P, T, D) float64."""
-        from .stem_data import STEMData
-        if self._engine is None:
-            raise RuntimeError("call setup() before run_detectors()")
-        if self._detectors is None:
-            raise RuntimeError("run_detectors() needs MultisliceCalculator(detectors=[...])")
+    def _probe_batch_loop(self, reduce_batch):
+        """The pass of run_detectors() / run_diffraction(): frame batches outside (the potentials of a batch are built once), probe
+        batches inside (the last one padded by repeating its last position); after the slice loop of each,
+        reduce_batch(p0, real, s0, n) reads the engine's result ring: probes p0 .. p0+real-1 in its first `real` rows, frames
+        s0 .. s0+n-1 in frame slots 0 .. n-1."""
         eng = self._engine
-        t0 = time.time()
-        P, T, D = self.n_probes, self.n_frames, len(self._detectors)
+        P, T = self.n_probes, self.n_frames
         Pc, B = eng.n_probes, eng.frame_batch
         pos = np.asarray(self.probe_positions, dtype=np.float64).reshape(-1, 2)
-        signals = np.zeros((P, T, D), dtype=np.float64)
         bar = None
         if self._progress:
             try:
@@ -413,16 +439,70 @@ class MultisliceCalculator:
                     eng.propagate_frames(0, n)
                 else:
                     eng.propagate_frame(0)
-                signals[p0:p0 + real, s0:s0 + n] = eng.detect(0, n, B=real)
+                reduce_batch(p0, real, s0, n)
             if bar is not None:
                 bar.update(n)
         if bar is not None:
             bar.close()
+
+    def _stem_data(self, signals):
+        from .stem_data import STEMData
+        kxs, kys = self._k_axes()
+        return STEMData(signals=signals, detectors=list(self._detectors), probe_positions=self.probe_positions,
+                        time=np.arange(self.n_frames) * self.trajectory.timestep, kxs=_as_tensor(kxs), kys=_as_tensor(kys),
+                        probe=self.base_probe)
+
+    def run_diffraction(self):
+        """Frame-averaged diffraction pattern of every probe position (4D-STEM / CBED): the loop of run_detectors(); msl_diffract
+        reduces the exit spectra of every probe batch to (real, mx, my) float64 -- |Psi|^2 summed over the frames of the batch and
+        the pixels of each bin -- which is added into the host result and divided by the number of frames at the end.
+        -> DiffractionData with intensity (P, mx, my) float64; with detectors as well, .stem is the STEMData run_detectors()
+        returns, from the same propagation.  Device memory does not depend on the number of probe positions; the host holds
+        8 * P * mx * my bytes (537 MB for 64 x 64 positions x 128 x 128 detector pixels), which is not checked against anything."""
+        from .diffraction_data import DiffractionData, bin_centres
+        if self._diffraction is None:
+            raise RuntimeError("run_diffraction() needs MultisliceCalculator(diffraction=Diffraction(...))")
+        if self._engine is None:
+            raise RuntimeError("call setup() before run_diffraction()")
+        eng = self._engine
+        t0 = time.time()
+        P, T = self.n_probes, self.n_frames
+        bx, by = self._diffraction.bin
+        acc = np.zeros((P, eng.wx // bx, eng.wy // by), dtype=np.float64)
+        signals = None if self._detectors is None else np.zeros((P, T, len(self._detectors)), dtype=np.float64)
+
+        def reduce_batch(p0, real, s0, n):
+            acc[p0:p0 + real] += eng.diffract(0, n, B=real, bin=(bx, by))
+            if signals is not None:
+                signals[p0:p0 + real, s0:s0 + n] = eng.detect(0, n, B=real)
+        self._probe_batch_loop(reduce_batch)
+        acc /= T
         self.elapsed = time.time() - t0
         self.frames_computed, self.frames_cached = T, 0
         kxs, kys = self._k_axes()
-        return STEMData(signals=signals, detectors=list(self._detectors), probe_positions=self.probe_positions,
-                        time=np.arange(T) * self.trajectory.timestep, kxs=_as_tensor(kxs), kys=_as_tensor(kys), probe=self.base_probe)
+        return DiffractionData(intensity=acc, kxs=_as_tensor(bin_centres(kxs, bx)), kys=_as_tensor(bin_centres(kys, by)), bin=(bx, by),
+                               n_frames=T, probe_positions=self.probe_positions, probe=self.base_probe,
+                               stem=None if signals is None else self._stem_data(signals))
+
+    def run_detectors(self):
+        """STEM detector signals of every probe and frame: for each frame batch the potentials are built once, then every probe
+        batch goes through the slice loop and msl_detect reduces its exit spectra to the detector values.  -> STEMData with
+        signals (P, T, D) float64."""
+        if self._engine is None:
+            raise RuntimeError("call setup() before run_detectors()")
+        if self._detectors is None:
+            raise RuntimeError("run_detectors() needs MultisliceCalculator(detectors=[...])")
+        eng = self._engine
+        t0 = time.time()
+        P, T, D = self.n_probes, self.n_frames, len(self._detectors)
+        signals = np.zeros((P, T, D), dtype=np.float64)
+
+        def reduce_batch(p0, real, s0, n):
+            signals[p0:p0 + real, s0:s0 + n] = eng.detect(0, n, B=real)
+        self._probe_batch_loop(reduce_batch)
+        self.elapsed = time.time() - t0
+        self.frames_computed, self.frames_cached = T, 0
+        return self._stem_data(signals)
 
     def _check_layers(self, n_slices, world):
         """the `layers` argument -> sorted unique slice indices with n_slices - 1 last (before any device work)"""
@@ -461,6 +541,8 @@ class MultisliceCalculator:
         """reference calculators.py:163-250: all frames, then pack WFData."""
         if self._detectors is not None:
             raise RuntimeError("detectors are set: the device holds one probe batch at a time -- call run_detectors()")
+        if self._diffraction is not None:
+            raise RuntimeError("diffraction is set: the device holds one probe batch at a time -- call run_diffraction()")
         if self._engine is None:
             raise RuntimeError("call setup() before run()")
         if self._stream_tile is not None:

@@ -22,6 +22,7 @@
 #include "tacaw_launch.h"
 #include "layer_tap.h"
 #include "detect.h"
+#include "diffract.h"
 
 using namespace msl;
 
@@ -150,6 +151,9 @@ struct msl_handle {
     int det_n = 0, det_wy = 0;
     size_t det_K = 0;
     uint32_t det_amp = 0, det_cx = 0, det_cy = 0;
+    // diffraction patterns (msl_diffract): (B, mx, my) float64 staging, grown on demand
+    double* diff_out = nullptr;
+    size_t diff_cap = 0;
     double* d_abcd = nullptr;
     double* d_lo = nullptr;
     double* d_hi = nullptr;
@@ -1554,7 +1558,7 @@ int msl_destroy(msl_handle* h) {
                     h->d_pos, h->d_Z, h->d_key, h->d_order, h->d_u1, h->d_u2, h->d_ex, h->d_ey, h->d_counts, h->d_start,
                     h->d_z2s, h->d_species, h->d_ff, h->d_xy, h->plan_x.tw, h->plan_y.tw, h->plan_t.tw, h->tw4_x, h->tw4_y,
                     h->scratch, h->psiT, h->psi0T, h->transT, h->bin_stage, h->st_acc, h->st_s1, h->st_s2, h->st_tw, h->st_bins, h->st_ref,
-                    h->opt.tw, h->opt.tw2, h->opt.bf, h->opt.bw, h->tsplit_tw, h->det_mask, h->det_kx, h->det_ky, h->plan_x.chirp, h->plan_x.bfilt, h->plan_y.chirp, h->plan_y.bfilt, h->plan_t.chirp, h->plan_t.bfilt};
+                    h->opt.tw, h->opt.tw2, h->opt.bf, h->opt.bw, h->tsplit_tw, h->det_mask, h->det_kx, h->det_ky, h->diff_out, h->plan_x.chirp, h->plan_x.bfilt, h->plan_y.chirp, h->plan_y.bfilt, h->plan_t.chirp, h->plan_t.bfilt};
     for (void* b : bufs) if (b) (void)hipFree(b);
     for (const msl_handle::OpDir* o : {&h->opx, &h->opy}) {
         void* tabs[] = {o->mtw, o->tw, o->tw2, o->qf, o->bw, o->ptab, o->cz.tw, o->cz.tw2, o->cz.bf, o->cz.bw};
@@ -2608,6 +2612,72 @@ int msl_detect(msl_handle* h, const void* d_src_c64, int64_t B, int64_t T, int64
     else hipLaunchKernelGGL(detect_finish_kernel<16>, dim3((unsigned)rows), dim3(256), 0, h->stream, d_part, (long long)n_tiles, n, d_out);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return MSL_OK;
+}
+
+// ---- diffraction patterns (diffract.h) --------------------------------------------------------------------
+extern "C++" template <int MODE>
+static void launch_diffract(msl_handle* h, bool vec, unsigned grid, unsigned threads, size_t lds, const float2* src, long long T, long long t0, int count,
+                            long long ld, int wx, int wy, int bx, int by, long long strips, int per, double* out) {
+    if (vec) hipLaunchKernelGGL((diffract_kernel<MODE, true>), dim3(grid), dim3(threads), lds, h->stream, src, T, t0, count, ld, wx, wy, bx, by, strips, per, out);
+    else hipLaunchKernelGGL((diffract_kernel<MODE, false>), dim3(grid), dim3(threads), lds, h->stream, src, T, t0, count, ld, wx, wy, bx, by, strips, per, out);
+}
+
+int msl_diffract(msl_handle* h, const void* d_src_c64, int64_t B, int64_t T, int64_t K, int64_t ld, int32_t t0, int32_t count, int32_t wx, int32_t wy,
+                 int32_t bx, int32_t by, double* out) {
+    if (!h || !out) return fail(h, MSL_ERR_INVALID, "msl_diffract: null argument");
+    if (!d_src_c64) {
+        if (!h->wf) return fail(h, MSL_ERR_STATE, "msl_diffract: no wavefunction buffer");
+        if (B < 1) B = h->cfg.n_probes;
+        if (B > h->cfg.n_probes) return fail(h, MSL_ERR_INVALID, "msl_diffract: %lld probes, the handle has %d", (long long)B, h->cfg.n_probes);
+        if (wx != h->wx / h->bx || wy != h->wy / h->by)
+            return fail(h, MSL_ERR_INVALID, "msl_diffract: window %d x %d, the handle stores %d x %d", wx, wy, h->wx / h->bx, h->wy / h->by);
+        d_src_c64 = h->wf; T = h->cfg.n_frames; K = (int64_t)h->wpix; ld = (int64_t)h->wpitch;
+    } else if (ld == 0) {
+        ld = K;
+    }
+    if (B < 1 || T < 1 || K < 1 || ld < K) return fail(h, MSL_ERR_INVALID, "msl_diffract: bad shape (%lld,%lld,%lld) ld %lld", (long long)B, (long long)T,
+                                                     (long long)K, (long long)ld);
+    if (wx < 1 || wy < 1 || (int64_t)wx * wy != K) return fail(h, MSL_ERR_INVALID, "msl_diffract: window %d x %d over rows of %lld pixels", wx, wy, (long long)K);
+    if (bx < 1 || by < 1 || wx % bx || wy % by) return fail(h, MSL_ERR_INVALID, "msl_diffract: bin %d x %d does not divide the window %d x %d", bx, by, wx, wy);
+    if (count < 1 || t0 < 0 || (int64_t)t0 + count > T)
+        return fail(h, MSL_ERR_INVALID, "msl_diffract: frame slots [%d,%d) outside [0,%lld)", t0, t0 + count, (long long)T);
+    const int mx = wx / bx, my = wy / by;
+    const int64_t strips = B * mx;                               // one row of bins of one probe
+    if ((int64_t)count * bx > 0x3fffffffLL) return fail(h, MSL_ERR_UNSUPPORTED, "msl_diffract: more than 2^30 rows per bin");
+    const bool pow2 = (by & (by - 1)) == 0;
+    const int mode = by == 1 ? DIFF_DIRECT : (pow2 && by <= 64 ? DIFF_SHFL : DIFF_LDS);
+    const size_t lds = mode == DIFF_LDS ? (size_t)wy * sizeof(double) : 0;
+    if (lds > 64u * 1024u) return fail(h, MSL_ERR_UNSUPPORTED, "msl_diffract: bin %d of rows of %d pixels needs %zu bytes of LDS", by, wy, lds);
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    const size_t n_out = (size_t)strips * my;
+    if (n_out > h->diff_cap) {
+        h->diff_cap = 0;
+        int rc = dalloc(h, &h->diff_out, n_out);
+        if (rc) return rc;
+        h->diff_cap = n_out;
+    }
+    // 16-byte loads need every row to start on 16 bytes: base, image pitch and row length even in pixels
+    const bool vec = (ld % 2 == 0) && (wy % 2 == 0) && (((uintptr_t)d_src_c64 & 15) == 0);
+    const int cols = vec ? (wy + 1) / 2 : wy;
+    const unsigned threads = (unsigned)std::min(256, std::max(64, (cols + 63) / 64 * 64));
+    // strips per workgroup: about 64 KB of reads each, but at least 4096 workgroups while there are that many strips
+    const int64_t strip_bytes = (int64_t)count * bx * wy * 8;
+    int64_t per = std::max<int64_t>(1, 65536 / strip_bytes);
+    per = std::max<int64_t>(1, std::min<int64_t>(per, strips / 4096));
+    per = std::max<int64_t>(per, (strips + 0x7ffffffeLL) / 0x7fffffffLL);
+    const unsigned grid = (unsigned)((strips + per - 1) / per);
+    int rc = begin_timed(h, 1);
+    if (rc) return rc;
+    const float2* src = (const float2*)d_src_c64;
+    if (mode == DIFF_DIRECT) launch_diffract<DIFF_DIRECT>(h, vec, grid, threads, lds, src, T, t0, count, ld, wx, wy, bx, by, strips, (int)per, h->diff_out);
+    else if (mode == DIFF_SHFL) launch_diffract<DIFF_SHFL>(h, vec, grid, threads, lds, src, T, t0, count, ld, wx, wy, bx, by, strips, (int)per, h->diff_out);
+    else launch_diffract<DIFF_LDS>(h, vec, grid, threads, lds, src, T, t0, count, ld, wx, wy, bx, by, strips, (int)per, h->diff_out);
+    HIPCHK(h, hipGetLastError());
+    if ((rc = mark_launch(h, K_OTHER))) return rc;
+    h->ctr.algorithmic_bytes += 8ull * (uint64_t)K * (uint64_t)B * (uint64_t)count;
+    HIPCHK(h, hipMemcpyAsync(out, h->diff_out, n_out * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return MSL_OK;
 }

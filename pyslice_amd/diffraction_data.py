@@ -1,0 +1,96 @@
+"""Frame-averaged diffraction patterns per probe position (CBED / 4D-STEM), streamed over probe batches
+(MultisliceCalculator(diffraction=Diffraction(bin=...)).run_diffraction()).
+
+The HIP pass msl_diffract (pyslice_amd/csrc/diffract.h) turns the exit spectra of a probe batch into |Psi|^2 summed over the
+frames of the batch and over every bx x by block of stored pixels -- the intensity a pixelated detector records, not the
+coherent block sum of k_bin -- as soon as the slice loop has written them.  A scan therefore needs no (P, T, nx, ny) array:
+DiffractionData holds the (P, mx, my) frozen-phonon mean only, and everything below is NumPy on that small result.
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass
+from typing import Any, Optional, Tuple
+
+import numpy as np
+
+from .stem_data import Detector, STEMData, scan_axes, scan_image
+
+
+class Diffraction:
+    """The request: bin=(bx, by) stored pixels per detector pixel along kx and ky (both must divide the stored spectrum)."""
+
+    def __init__(self, bin=(1, 1)):
+        try:
+            ok = len(bin) == 2 and all(isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_)) and int(v) >= 1 for v in bin)
+        except TypeError:
+            ok = False
+        if not ok:
+            raise ValueError(f"Diffraction: bin must be two positive integers (bx, by), got {bin!r}")
+        self.bin = (int(bin[0]), int(bin[1]))
+
+    def __repr__(self):
+        return f"Diffraction(bin={self.bin})"
+
+
+def bin_centres(axis, b):
+    """bin-centre axis: the mean of every b consecutive values of a stored k axis, float32 (as MultisliceCalculator's k_bin axes)"""
+    a = np.asarray(axis.detach().cpu().numpy() if hasattr(axis, "detach") else axis, dtype=np.float32)
+    if a.size % b:
+        raise ValueError(f"an axis of {a.size} values is not a multiple of the bin {b}")
+    return a.reshape(-1, b).mean(axis=1).astype(np.float32)
+
+
+def _np(a):
+    return a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+
+
+@dataclass
+class DiffractionData:
+    """Result of MultisliceCalculator.run_diffraction(): intensity (P, mx, my) float64 -- the mean over the n_frames MD frames of
+    |Psi|^2 in detector pixel (ix, iy) at probe p --, the bin-centre axes kxs / kys (float32), the bin, the run's
+    probe_positions / probe / wavelength, the scan axes xs / ys, and `stem`: the STEMData of the same pass when the run had detectors."""
+    intensity: np.ndarray
+    kxs: Any
+    kys: Any
+    bin: Tuple[int, int]
+    n_frames: int
+    probe_positions: Any
+    probe: Any
+    stem: Optional[STEMData] = None
+    wavelength: Optional[float] = None      # Angstrom; None: the probe's
+    xs: np.ndarray = None
+    ys: np.ndarray = None
+
+    def __post_init__(self):
+        if self.wavelength is None and self.probe is not None:
+            self.wavelength = float(self.probe.wavelength)
+        if self.xs is None or self.ys is None:
+            self.xs, self.ys = scan_axes(self.probe_positions)
+
+    def pacbed(self) -> np.ndarray:
+        """(mx, my): position-averaged pattern, the mean over the probes"""
+        return self.intensity.mean(axis=0)
+
+    def member(self, detector: Detector) -> np.ndarray:
+        """(mx, my) bool: the detector pixels whose CENTRE lies in `detector` (its member() on the bin-centre axes)"""
+        if not isinstance(detector, Detector):
+            raise ValueError(f"expected a Detector, got {detector!r}")
+        if detector.signal != "intensity":
+            raise ValueError(f"detector {detector.name!r}: patterns hold |Psi|^2 only, signal {detector.signal!r} cannot be formed from them")
+        if self.wavelength is None:
+            raise ValueError("DiffractionData has neither a probe nor a wavelength: detector angles cannot be turned into k")
+        return detector.member(_np(self.kxs), _np(self.kys), self.wavelength)
+
+    def virtual(self, detector: Detector) -> np.ndarray:
+        """(P,): the virtual detector chosen after the run -- sum of the detector pixels inside `detector`"""
+        m = self.member(detector)
+        return (self.intensity * m[None].astype(np.float64)).sum(axis=(-2, -1))
+
+    def image(self, detector: Detector) -> np.ndarray:
+        """(len(xs), len(ys)) scan image of virtual(detector): every scan point takes its nearest probe's value (STEMData.image)"""
+        return scan_image(self.virtual(detector), self.probe_positions, self.xs, self.ys)
+
+    def pattern(self, x: float, y: float) -> np.ndarray:
+        """(mx, my): the pattern of the probe nearest to (x, y)"""
+        pp = np.asarray(self.probe_positions, dtype=np.float64).reshape(-1, 2)
+        return self.intensity[int(np.argmin(((pp - np.array([x, y])[None, :]) ** 2).sum(axis=1)))]

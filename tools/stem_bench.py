@@ -1,8 +1,10 @@
 """STEM detector runs (MultisliceCalculator(detectors=...).run_detectors()): slice-steps/s of a scan streamed over probe batches,
 the device time of the detector pass (msl_detect) and its share of the run, and the engine's device memory.  One JSON line per
 probe batch.  --detect-only times msl_detect alone on resident images and reports its HBM rate against 8 TB/s.
-    python tools/stem_bench.py [--scan 64] [--n 1024] [--slices 200] [--frames 1] [--probe-batch 64 256] [--detectors 8]
-    python tools/stem_bench.py --detect-only [--images 256] [--n 1024] [--detectors 8] [--reps 20]"""
+--diffraction BX,BY adds the diffraction-pattern leg: with --detect-only msl_diffract alone on the same resident images, otherwise
+the scan through run_diffraction() (with --detectors 0 the patterns alone, else patterns and detectors in one pass).
+    python tools/stem_bench.py [--scan 64] [--n 1024] [--slices 200] [--frames 1] [--probe-batch 64 256] [--detectors 8] [--diffraction 8,8]
+    python tools/stem_bench.py --detect-only [--images 256] [--n 1024] [--detectors 8] [--reps 20] [--diffraction 8,8]"""
 import argparse
 import json
 import os
@@ -53,6 +55,19 @@ def detect_only(args):
     print(json.dumps({"case": "detect_only", "images": B, "grid": n, "detectors": len(dets), "ms_median": round(dt * 1e3, 4),
                       "ms_min": round(min(times) * 1e3, 4), "GB_per_s": round(nbytes / dt / 1e9, 1),
                       "fraction_of_8TBps": round(nbytes / dt / HBM_PEAK, 3)}), flush=True)
+    if args.diffraction:
+        bx, by = args.diffraction
+        dsrc = (W.data_ptr(), B, 1, n, n)
+        eng.diffract(bin=(bx, by), src=dsrc)              # warm-up (allocates the staging array)
+        times = []
+        for _ in range(args.reps):
+            t0 = time.perf_counter()
+            eng.diffract(bin=(bx, by), src=dsrc)          # one launch + 8 B x B x mx x my back, synchronous
+            times.append(time.perf_counter() - t0)
+        dt = float(np.median(times))
+        print(json.dumps({"case": "diffract_only", "images": B, "grid": n, "bin": [bx, by], "ms_median_with_copy": round(dt * 1e3, 4),
+                          "ms_min_with_copy": round(min(times) * 1e3, 4), "bytes_read": nbytes, "bytes_copied_back": B * (n // bx) * (n // by) * 8}),
+              flush=True)
     eng.close()
 
 
@@ -64,6 +79,9 @@ def scan(args, pb):
     s = args.scan
     pp = [(x, y) for x in np.linspace(0.25 * lx, 0.75 * lx, s) for y in np.linspace(0.25 * ly, 0.75 * ly, s)]
     free0 = torch.cuda.mem_get_info()[0]
+    if args.diffraction:
+        scan_diffraction(args, pb, tr, pp, free0)
+        return
     calc = ps.MultisliceCalculator(progress=False, detectors=detectors(args.detectors), probe_batch=pb)
     calc.setup(tr, aperture=30.0, voltage_eV=100e3, probe_positions=pp)
     eng = calc._engine
@@ -94,6 +112,50 @@ def scan(args, pb):
     eng.close()
 
 
+def scan_diffraction(args, pb, tr, pp, free0):
+    """the scan through run_diffraction(): slice-steps/s, the synchronous msl_diffract per batch, the host accumulate per batch"""
+    import torch
+    dets = detectors(args.detectors) if args.detectors > 0 else None
+    calc = ps.MultisliceCalculator(progress=False, diffraction=ps.Diffraction(bin=args.diffraction), detectors=dets, probe_batch=pb)
+    calc.setup(tr, aperture=30.0, voltage_eV=100e3, probe_positions=pp)
+    eng = calc._engine
+    used = free0 - torch.cuda.mem_get_info()[0]
+    spent = []
+    plain = eng.diffract
+
+    def timed(*a, **k):
+        eng.synchronize()
+        t0 = time.perf_counter()
+        out = plain(*a, **k)
+        spent.append(time.perf_counter() - t0)
+        return out
+    eng.diffract = timed
+    t0 = time.perf_counter()
+    dd = calc.run_diffraction()
+    dt = time.perf_counter() - t0
+    steps = len(pp) * args.frames * args.slices
+    block = np.ones((eng.n_probes,) + dd.intensity.shape[1:])
+    acc = []
+    for i in range(5):                                     # the += of one batch into the host result, on the result itself
+        t1 = time.perf_counter()
+        dd.intensity[:eng.n_probes] += block
+        acc.append(time.perf_counter() - t1)
+    print(json.dumps({"case": "scan_diffraction", "scan": f"{args.scan}x{args.scan}", "grid": args.n, "slices": args.slices, "frames": args.frames,
+                      "probe_batch": eng.n_probes, "frame_batch": eng.frame_batch, "bin": list(args.diffraction),
+                      "detectors": 0 if dets is None else len(dets), "pattern_shape": list(dd.intensity.shape),
+                      "s_total": round(dt, 3), "slice_steps_per_s": round(steps / dt),
+                      "diffract_ms_per_batch": round(1e3 * float(np.median(spent)), 4), "diffract_share_pct": round(100.0 * sum(spent) / dt, 3),
+                      "accumulate_ms_per_batch": round(1e3 * float(np.median(acc)), 4), "host_result_bytes": int(dd.intensity.nbytes),
+                      "device_bytes_after_setup": int(used)}), flush=True)
+    calc._engine = None
+    eng.close()
+
+
+def _bin(text):
+    bx, by = (int(v) for v in text.split(","))
+    return bx, by
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--detect-only", action="store_true")
@@ -105,6 +167,7 @@ def main():
     ap.add_argument("--detectors", type=int, default=8)
     ap.add_argument("--images", type=int, default=256)
     ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--diffraction", type=_bin, default=None, metavar="BX,BY")
     args = ap.parse_args()
     if args.detect_only:
         detect_only(args)
