@@ -54,6 +54,13 @@ enum LaunchKind { K_ROW = 0, K_COL = 1, K_OTHER = 2, K_NKINDS = 3 };
 //   AX_GENERIC   the generic LDS kernel with a transposing store
 enum AxisKind { AX_NONE, AX_FOURSTEP, AX_TWO, AX_WAVE2K, AX_MIXED, AX_CONV, AX_CONV2K, AX_CONV4K, AX_GENERIC };
 
+// How the potential build inverse-transforms the structure factors and applies exp(i sigma V) (plan_pot_ifft, potential_ifft):
+//   PI_LINES   in place, each axis on its own: the four-step kernel where the axis has one (Ry / Rx), launch_lines otherwise
+//   PI_TWO     512 x 512 (both axes AX_TWO): ifftT2_kernel
+//   PI_CHIRPZ  chirp-z tables along both axes (OpDir::cz): ifftTB_two / ifftTB / ifftTB2_kernel
+//   PI_WAVE2K  2048 x 2048 (both axes AX_WAVE2K): ifftTW_kernel
+enum PotIfft { PI_LINES, PI_TWO, PI_CHIRPZ, PI_WAVE2K };
+
 // Chirp-z tables of n points on a register FFT of length M: R = 16 / 32 (M = R^2, tw = make_tw4's table) or 64 (the wave-per-line
 // 2048-point FFT: tw = T[k1*64+n2], tw2 = W_64), chirp bw (M/2 entries) and its filter bf (M/2 + 2), made by make_cz_tables.  The
 // convolution passes of the slice loop, the potential's inverse transform (ifftTB_kernel / ifftTB2_kernel) and time_cz_kernel read them.
@@ -97,6 +104,7 @@ struct msl_handle {
     size_t scratch_bytes = 0;
     bool onepass = false;
     bool scheme_b = false;         // a direction of 2R^2 points: every pass transposes, first pass along y, final transpose if nz is odd
+    PotIfft pot_ifft = PI_LINES;   // inverse transform of the potential build, fixed at msl_create
     // one-pass kernel of one axis (AxisKind) and its tables: n = line length, R = radix of the base kind's register FFT (0: none).
     // `base` is the kind the axis has without the mixed-radix pass (== kind otherwise): a MIXED axis keeps the tables of its base
     // kind, on which the potential's inverse transform, the probes and the exit FFT still run, and the loop is one-pass iff both
@@ -358,6 +366,21 @@ int mark_launch(msl_handle* h, int kind) {
     return MSL_OK;
 }
 
+// a kernel's dynamic LDS may go up to the whole LDS of a CU (the default limit is 64 KB)
+template <typename K>
+void allow_lds(const msl_handle* h, K kernel) {
+    (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, h->lds_limit);
+}
+
+// launch of a kernel with `lds` bytes of dynamic LDS on the handle's stream, as a timed launch of `kind`
+template <typename K, typename... A>
+int launch_lds(msl_handle* h, K kernel, dim3 grid, dim3 block, size_t lds, int kind, const A&... args) {
+    allow_lds(h, kernel);
+    hipLaunchKernelGGL(kernel, grid, block, lds, h->stream, args...);
+    HIPCHK(h, hipGetLastError());
+    return mark_launch(h, kind);
+}
+
 int resolve_all(msl_handle* h) {
     for (auto& s : h->ring) { int rc = resolve_set(h, s); if (rc) return rc; }
     h->cur = nullptr;
@@ -477,10 +500,25 @@ LineArgs col_args(const msl_handle* h, const float2* in, float2* out, int images
     return a;
 }
 
-// timing events of one call, destroyed on every exit path
+// Timing bracket of one call: end() waits for the stream and adds the device time since begin() to *ms_total; without begin() it does
+// nothing (the call only queued work).  The events are destroyed on every exit path.
 struct EventPair {
     hipEvent_t a = nullptr, b = nullptr;
     ~EventPair() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
+    int begin(msl_handle* h) {
+        HIPCHK(h, hipEventCreate(&a)); HIPCHK(h, hipEventCreate(&b));
+        HIPCHK(h, hipEventRecord(a, h->stream));
+        return MSL_OK;
+    }
+    int end(msl_handle* h, double* ms_total) {
+        if (!b) return MSL_OK;
+        HIPCHK(h, hipEventRecord(b, h->stream));
+        HIPCHK(h, hipEventSynchronize(b));
+        float ms = 0.f;
+        HIPCHK(h, hipEventElapsedTime(&ms, a, b));
+        *ms_total += ms;
+        return MSL_OK;
+    }
 };
 
 // Probes per work item of the chunked kernels (a work item = 16 lines x a chunk of probes that share the t_k lines in
@@ -611,33 +649,21 @@ int launch_row_fast_r(msl_handle* h, const RowJob& job, int kind) {
     return mark_launch(h, kind);
 }
 
-template <int R>
+// HERM: column pass of the potential build on the rows kx <= nx/2 of a Hermitian spectrum
+template <int R, bool HERM = false>
 int launch_col_fast_r(msl_handle* h, const ColJob& job, int kind) {
     constexpr int N = R * R, CS = R * (R + 1) + 1;
     const size_t lds = ((size_t)2 * N + (size_t)16 * CS) * 8;
     const long long tiles = (long long)(job.ny / 16) * job.n_images;
     const int per_cu = std::max(1, (int)((size_t)h->lds_limit / lds));
     const int grid = (int)std::min<long long>(tiles, (long long)h->n_cus * std::min(per_cu, 2));
+    if (HERM) return launch_lds(h, col_pass_kernel<R, 16, true>, dim3(grid), dim3(16 * R), lds, kind, job);
     hipLaunchKernelGGL(col_pass_kernel<R>, dim3(grid), dim3(16 * R), lds, h->stream, job);
     HIPCHK(h, hipGetLastError());
     return mark_launch(h, kind);
 }
-
-// column pass of the potential build on the rows kx <= nx/2 of a Hermitian spectrum
-template <int R>
-int launch_col_herm_r(msl_handle* h, const ColJob& job, int kind) {
-    constexpr int N = R * R, CS = R * (R + 1) + 1;
-    const size_t lds = ((size_t)2 * N + (size_t)16 * CS) * 8;
-    const long long tiles = (long long)(job.ny / 16) * job.n_images;
-    const int per_cu = std::max(1, (int)((size_t)h->lds_limit / lds));
-    const int grid = (int)std::min<long long>(tiles, (long long)h->n_cus * std::min(per_cu, 2));
-    (void)hipFuncSetAttribute((const void*)col_pass_kernel<R, 16, true>, hipFuncAttributeMaxDynamicSharedMemorySize, h->lds_limit);
-    hipLaunchKernelGGL((col_pass_kernel<R, 16, true>), dim3(grid), dim3(16 * R), lds, h->stream, job);
-    HIPCHK(h, hipGetLastError());
-    return mark_launch(h, kind);
-}
 int launch_col_herm(msl_handle* h, const ColJob& job, int kind) {
-    return h->Rx == 32 ? launch_col_herm_r<32>(h, job, kind) : launch_col_herm_r<16>(h, job, kind);
+    return h->Rx == 32 ? launch_col_fast_r<32, true>(h, job, kind) : launch_col_fast_r<16, true>(h, job, kind);
 }
 
 int launch_row_fast(msl_handle* h, const RowJob& job, int kind) {
@@ -862,10 +888,7 @@ int launch_rowT2_io(msl_handle* h, RowTJob job, int kind) {
     const size_t lds = ((size_t)2 * N2 + N + (size_t)16 * (N + 2)) * 8;
     const int per_cu = std::max(1, std::min(2, (int)((size_t)h->lds_limit / lds)));
     const int grid = chunked_grid(h, job, job.n_lines / 16, (long long)h->n_cus * per_cu);
-    (void)hipFuncSetAttribute((const void*)rowT2_pass_kernel<R, IN_P, OUT_P>, hipFuncAttributeMaxDynamicSharedMemorySize, h->lds_limit);
-    hipLaunchKernelGGL((rowT2_pass_kernel<R, IN_P, OUT_P>), dim3(grid), dim3(16 * R), lds, h->stream, job);
-    HIPCHK(h, hipGetLastError());
-    return mark_launch(h, kind);
+    return launch_lds(h, rowT2_pass_kernel<R, IN_P, OUT_P>, dim3(grid), dim3(16 * R), lds, kind, job);
 }
 
 // lines of any length <= R^2/2: zero-padded cyclic convolution on the register FFTs
@@ -875,10 +898,7 @@ int launch_rowTB_r(msl_handle* h, RowTJob job, int kind) {
     const size_t lds = ((size_t)M + NH + 2 + (size_t)16 * CS) * 8;
     const int per_cu = std::max(1, std::min(R == 16 ? 4 : 1, (int)((size_t)h->lds_limit / lds)));
     const int grid = chunked_grid(h, job, (job.n_lines + 15) / 16, (long long)h->n_cus * per_cu);
-    (void)hipFuncSetAttribute((const void*)rowTB_pass_kernel<R>, hipFuncAttributeMaxDynamicSharedMemorySize, h->lds_limit);
-    hipLaunchKernelGGL((rowTB_pass_kernel<R>), dim3(grid), dim3(16 * R), lds, h->stream, job);
-    HIPCHK(h, hipGetLastError());
-    return mark_launch(h, kind);
+    return launch_lds(h, rowTB_pass_kernel<R>, dim3(grid), dim3(16 * R), lds, kind, job);
 }
 
 // lines of 513..1024 points: the same convolution on the wave-per-line 2048-point register FFT
@@ -887,10 +907,7 @@ int launch_rowTB2_io(msl_handle* h, RowTJob job, int kind) {
     constexpr int M = 2048, NH = M / 2, RS = (32 * W2K_PITCH) / 2 + 1;
     const size_t lds = ((size_t)M + 64 + NH + 2 + (size_t)8 * RS) * 8;
     const int grid = chunked_grid(h, job, (job.n_lines + 7) / 8, h->n_cus);
-    (void)hipFuncSetAttribute((const void*)rowTB2_pass_kernel<IN_P, OUT_P>, hipFuncAttributeMaxDynamicSharedMemorySize, h->lds_limit);
-    hipLaunchKernelGGL((rowTB2_pass_kernel<IN_P, OUT_P>), dim3(grid), dim3(512), lds, h->stream, job);
-    HIPCHK(h, hipGetLastError());
-    return mark_launch(h, kind);
+    return launch_lds(h, rowTB2_pass_kernel<IN_P, OUT_P>, dim3(grid), dim3(512), lds, kind, job);
 }
 
 // 2048-point lines, one wave per line (fft2048_wave)
@@ -899,10 +916,7 @@ int launch_rowTW_io(msl_handle* h, RowTJob job, int kind) {
     constexpr int N = 2048;
     const size_t lds = ((size_t)N + 64 + N / 2 + 64 + (size_t)8 * (N + 1)) * 8;
     const int grid = chunked_grid(h, job, job.n_lines / 8, h->n_cus);
-    (void)hipFuncSetAttribute((const void*)rowTW_pass_kernel<IN_P, OUT_P>, hipFuncAttributeMaxDynamicSharedMemorySize, h->lds_limit);
-    hipLaunchKernelGGL((rowTW_pass_kernel<IN_P, OUT_P>), dim3(grid), dim3(512), lds, h->stream, job);
-    HIPCHK(h, hipGetLastError());
-    return mark_launch(h, kind);
+    return launch_lds(h, rowTW_pass_kernel<IN_P, OUT_P>, dim3(grid), dim3(512), lds, kind, job);
 }
 
 // lines of a smooth length A * B (A, B <= 32; G = 16 / 32 lanes per line) or 2 A * B (G = 64: one wave per line, tiles of 8 lines):
@@ -965,10 +979,7 @@ int launch_rowT_dir(msl_handle* h, const msl_handle::OpDir& o, RowTJob job, int 
         job.pchunk = 1;
         const long long items2 = (long long)((job.n_lines + 3) / 4) * job.n_images;
         const int grid2 = (int)std::min<long long>(items2, (long long)h->n_cus);
-        (void)hipFuncSetAttribute((const void*)rowTC2_pass_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, h->lds_limit);
-        hipLaunchKernelGGL(rowTC2_pass_kernel, dim3(grid2), dim3(512), lds, h->stream, job);
-        HIPCHK(h, hipGetLastError());
-        return mark_launch(h, kind);
+        return launch_lds(h, rowTC2_pass_kernel, dim3(grid2), dim3(512), lds, kind, job);
     }
     case AX_CONV:                           // A as one cyclic convolution of length M (two FFTs); bf = its filter
     case AX_CONV2K:
@@ -1386,6 +1397,331 @@ int make_axis_tables(msl_handle* h, msl_handle::OpDir& o, const msl_handle::OpDi
     return MSL_OK;
 }
 
+// ---- potential build ----------------------------------------------------------
+// The form of the potential's inverse transform for the planned axes.  A transposing form stores the slices a pass along x reads
+// into transT itself, which a kept V rules out (V is written by the untransposed store only).
+PotIfft plan_pot_ifft(const msl_handle* h) {
+    if (!h->onepass || h->V) return PI_LINES;
+    if (h->opx.base == AX_WAVE2K && h->opy.base == AX_WAVE2K && h->transT) return PI_WAVE2K;
+    if (h->transT && h->opx.cz.R && h->opy.cz.R) return PI_CHIRPZ;                     // chirp-z tables along both axes
+    if (h->opx.base == AX_TWO && h->opy.base == AX_TWO) return PI_TWO;
+    return PI_LINES;
+}
+
+// R_s is Hermitian (real V): only the rows kx <= nx/2 are written and row-transformed when the inverse transform mirrors them itself
+// (every register-kernel path: col_pass_kernel<.., HERM> with four-step kernels on both axes, ifftT2 / ifftTB / ifftTW with job.herm)
+bool pot_half_rows(const msl_handle* h) { return h->pot_ifft != PI_LINES || (h->Rx && h->Ry); }
+
+// what the stages of build_potentials share: the constants of the call and the group of g frames they work on
+struct PotGroup {
+    int z2s[104], species[104], nsp;    // species present, sorted ascending like np.unique: z2s[Z] = index into species, -1 where Z does not occur
+    int64_t n; int32_t ax1, ax2, axs;   // atoms per frame; the axes the caller's positions are read along
+    int keys_per_frame;             // (slice, species) bins per frame
+    int cx, cy; float vscale;       // table columns the quadrant kernel reads: the frequencies 0 .. n/2
+    bool half_rows, sf_stream;      // pot_half_rows; many atoms per bin: the streaming structure-factor kernel, whose bins are padded to whole half-trips
+    int g, slot, n_slices, nkeys;   // frames, first batch slot, slices and bins of the group
+    long long rows, rows_pad;       // atoms of the group; sorted table rows at most: every bin padded to SF_ALIGN
+    float2* TR; float2* TRT;        // batch slots this group's stacks go to (trans, transT)
+};
+
+int map_species(msl_handle* h, const int32_t* Z, int64_t n, PotGroup& m) {
+    for (int i = 0; i < 104; ++i) m.z2s[i] = -1;
+    for (int64_t a = 0; a < n; ++a) {
+        if (Z[a] < 1 || Z[a] > 103) return fail(h, MSL_ERR_INVALID, "msl_build_potential: atomic number %d out of 1..103", Z[a]);
+        m.z2s[Z[a]] = 0;
+    }
+    m.nsp = 0;
+    for (int z = 1; z <= 103; ++z) if (m.z2s[z] == 0) { m.z2s[z] = m.nsp; m.species[m.nsp++] = z; }
+    return MSL_OK;
+}
+
+// Per-frame inputs of a group, host -> device: the positions `pos` of its frames and, with the first group of a call, the species
+// maps and Z.  They go through pinned staging (msl_handle::HostStage) so that no pointer into caller memory is kept.
+int stage_atoms(msl_handle* h, const PotGroup& p, const double* pos, const int32_t* Z, bool send_maps) {
+    msl_handle::HostStage& st = h->stage[h->stage_pos++ & 1];
+    if (!st.ev) HIPCHK(h, hipEventCreateWithFlags(&st.ev, hipEventDisableTiming));
+    if (st.used) HIPCHK(h, hipEventSynchronize(st.ev));            // the copies queued from this slot two calls ago
+    const size_t z_bytes = (size_t)p.n * sizeof(int), pos_bytes = (size_t)p.rows * 3 * sizeof(double);
+    const size_t off_sp = sizeof p.z2s, off_Z = (off_sp + sizeof p.species + 7) & ~(size_t)7;
+    const size_t off_pos = (off_Z + z_bytes + 7) & ~(size_t)7, need = off_pos + pos_bytes;
+    if (need > st.bytes) {
+        if (st.buf) (void)hipHostFree(st.buf);
+        st.buf = nullptr; st.bytes = 0;
+        const size_t cap = need + need / 4;
+        if (hipHostMalloc((void**)&st.buf, cap, hipHostMallocDefault) != hipSuccess)
+            return fail(h, MSL_ERR_NOMEM, "hipHostMalloc(%zu bytes) failed", cap);
+        st.bytes = cap;
+    }
+    memcpy(st.buf + off_pos, pos, pos_bytes);
+    if (send_maps) {
+        memcpy(st.buf, p.z2s, sizeof p.z2s);
+        memcpy(st.buf + off_sp, p.species, sizeof p.species);
+        memcpy(st.buf + off_Z, Z, z_bytes);
+        HIPCHK(h, hipMemcpyAsync(h->d_z2s, st.buf, sizeof p.z2s, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(h->d_species, st.buf + off_sp, p.nsp * sizeof(int), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(h->d_Z, st.buf + off_Z, z_bytes, hipMemcpyHostToDevice, h->stream));
+    }
+    HIPCHK(h, hipMemcpyAsync(h->d_pos, st.buf + off_pos, pos_bytes, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipEventRecord(st.ev, h->stream));
+    st.used = true;
+    return MSL_OK;
+}
+
+// Atoms of a group -> phase tables in sorted order: slice bins (atom_prep_kernel), stable counting sort with keys = frame x slice x
+// species (bin_scan / bin_fill), the phase tables of both axes
+int bin_atoms(msl_handle* h, const PotGroup& p) {
+    const msl_config& c = h->cfg;
+    const int nsp = p.nsp;
+    HIPCHK(h, hipMemsetAsync(h->d_counts, 0, ((size_t)p.nkeys + 1) * sizeof(int), h->stream));
+    const double lx = c.nx * c.dx, ly = c.ny * c.dy;
+    // f_Z(q^2) depends on the grid and the species only (potentials.py:283-293 recomputes it per frame): build the table
+    // when the species list changes, i.e. once per run
+    if (nsp != h->ff_n || memcmp(p.species, h->ff_species, nsp * sizeof(int)) != 0) {
+        long long tot = (long long)c.nx * c.ny * nsp;
+        hipLaunchKernelGGL(formfactor_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, h->stream, h->d_ff, h->d_abcd,
+                           h->d_species, nsp, c.nx, c.ny, 1.0 / lx, 1.0 / ly);
+        memcpy(h->ff_species, p.species, nsp * sizeof(int));
+        h->ff_n = nsp;
+    }
+    hipLaunchKernelGGL(atom_prep_kernel, dim3((unsigned)((p.rows + 255) / 256)), dim3(256), 0, h->stream, h->d_pos, h->d_Z,
+                       (long long)p.n, p.g, h->d_z2s, h->d_lo, h->d_hi, c.nz, nsp, p.ax1, p.ax2, p.axs, 1.0 / lx, 1.0 / ly, h->d_key,
+                       h->d_u1, h->d_u2, h->d_counts);
+    hipLaunchKernelGGL(bin_scan_kernel, dim3(1), dim3(1024), 0, h->stream, h->d_counts, h->d_start, p.nkeys, p.sf_stream ? SF_ALIGN : 1);
+    hipLaunchKernelGGL(bin_fill_kernel, dim3(p.nkeys), dim3(1024), 0, h->stream, h->d_key, (long long)p.n, p.keys_per_frame, h->d_start, h->d_order);
+    HIPCHK(h, hipGetLastError());
+    // atoms that fell into a slice: d_start[nkeys], read by the kernels themselves (grids sized for all atoms of the group)
+    const int* n_sorted = h->d_start + p.nkeys;
+    if (p.rows_pad > 0x7fffffffLL) return fail(h, MSL_ERR_INVALID, "msl_build_potentials: %lld padded table rows in one group exceed 2^31", p.rows_pad);
+    const long long tx = p.rows_pad * p.cx, ty = p.rows_pad * p.cy;
+    hipLaunchKernelGGL(phase_table_kernel, dim3((unsigned)((tx + 255) / 256)), dim3(256), 0, h->stream, h->d_ex, h->d_u1,
+                       h->d_order, n_sorted, c.nx, p.cx, p.cx);
+    hipLaunchKernelGGL(phase_table_kernel, dim3((unsigned)((ty + 255) / 256)), dim3(256), 0, h->stream, h->d_ey, h->d_u2,
+                       h->d_order, n_sorted, c.ny, p.cy, p.cy);
+    return MSL_OK;
+}
+
+// Structure factors R_s of a group's slices into TR: matrix-core kernel over the quadrant of non-negative frequencies 0 .. n/2 in
+// 32 x 32 tiles; on power-of-two grids (n/2 + 1 = 32 k + 1) the Nyquist row / column goes to the edge kernel instead of a tile row
+// of its own
+int launch_structure_factor(msl_handle* h, const PotGroup& p) {
+    const msl_config& c = h->cfg;
+    const int cx = p.cx, cy = p.cy, nsp = p.nsp, n_slices = p.n_slices, full_rows = p.half_rows ? 0 : 1;
+    const bool edge_x = (c.nx % 2 == 0) && (cx % 32 == 1) && cx > 1, edge_y = (c.ny % 2 == 0) && (cy % 32 == 1) && cy > 1;
+    const int tiles_x = edge_x ? cx / 32 : (cx + 31) / 32, tiles_y = edge_y ? cy / 32 : (cy + 31) / 32;
+    const int n_tiles = tiles_x * tiles_y, wg_per_slice = (n_tiles + 3) / 4;
+    const long long n_wg = (long long)wg_per_slice * ((n_slices + 7) / 8 * 8);
+    if (n_wg > 0x7fffffffLL) return fail(h, MSL_ERR_UNSUPPORTED, "structure factor: too many workgroups");
+    if (p.sf_stream) {
+        // persistent form, one wave per SIMD: one workgroup per CU, a multiple of 8 (XCD-local slices)
+        const int n_pers = std::max(8, h->n_cus / 8 * 8);
+        auto stream = [&](auto kernel, size_t lds, int tiles) {
+            hipLaunchKernelGGL(kernel, dim3((unsigned)n_pers), dim3(256), lds, h->stream, p.TR, h->d_ex, h->d_ey, h->d_ff, h->d_start, nsp,
+                               c.nx, c.ny, tiles_y, tiles, (int)p.rows_pad, full_rows, cx, cy, n_slices);
+        };
+        if (dbg_env("MSL_SF_F32"))                   // the exact-f32 matrix instruction (A/B against the split-bf16 form)
+            stream(structure_factor_stream_kernel, 0, n_tiles);
+        // two kx tiles per wave sharing the ey planes (potential.h) where a slice's tables outgrow an XCD's L2: 2048^2 x 50 potential
+        // 8.67 -> 8.17 ms per frame, 1024^2 (C3) 3.72 -> 3.69 (kept on the one-tile kernel)
+        else if ((n_tiles >= 512 || (tiles_x >= 2 && dbg_env("MSL_SF_TWO_TILES"))) && !dbg_env("MSL_SF_ONE_TILE"))
+            stream(structure_factor_stream_bf16x2_kernel, 4 * 128 * 64 * sizeof(float), ((tiles_x + 1) / 2) * tiles_y);
+        else
+            stream(structure_factor_stream_bf16_kernel, 0, n_tiles);
+    } else
+        hipLaunchKernelGGL(structure_factor_quad_kernel, dim3((unsigned)n_wg), dim3(256), 0, h->stream, p.TR, h->d_ex, h->d_ey, h->d_ff,
+                           h->d_start, nsp, c.nx, c.ny, tiles_y, n_tiles, (int)p.rows_pad, full_rows, cx, cy, n_slices, wg_per_slice);
+    if (edge_x || edge_y) {
+        const int bins = (edge_x ? cy : 0) + (edge_y ? (edge_x ? cx - 1 : cx) : 0);
+        for (int s0 = 0; s0 < n_slices; s0 += 65535) {
+            const int ns = std::min(65535, n_slices - s0);
+            hipLaunchKernelGGL(structure_factor_edge_kernel, dim3((bins + 127) / 128, ns), dim3(128), 0, h->stream,
+                               p.TR + (size_t)s0 * c.nx * c.ny, h->d_ex, h->d_ey, h->d_ff, h->d_start + (size_t)s0 * nsp, nsp, c.nx, c.ny,
+                               edge_x ? 1 : 0, edge_y ? 1 : 0, full_rows, cx, cy);
+        }
+    }
+    HIPCHK(h, hipGetLastError());
+    return MSL_OK;
+}
+
+// One transposing pass of the potential's inverse transform along direction `o`, on the kernel of a PotIfft form:
+// 2048-point lines, one wave per line (fft2048_wave)
+int launch_ifftTW(msl_handle* h, const msl_handle::OpDir& o, IfftTBJob j) {
+    constexpr int N2 = 2048;
+    const size_t lds = ((size_t)N2 + 64 + (size_t)8 * (N2 + 1)) * 8;
+    const long long items = (long long)(j.n_lines / 8) * j.n_images;
+    const int grid = (int)std::min<long long>(items, (long long)h->n_cus);
+    j.tw = o.tw; j.tw2 = o.tw2;
+    return launch_lds(h, ifftTW_kernel, dim3(grid), dim3(512), lds, K_OTHER, j);
+}
+
+// lines of any length up to 1024 by chirp-z on the register FFTs (o.cz)
+int launch_ifftTB(msl_handle* h, const msl_handle::OpDir& o, IfftTBJob j) {
+    const CzTables& t = o.cz;
+    j.tw = t.tw; j.bf = t.bf; j.bw = t.bw;
+    if (t.R == 64) {                                // 513 .. 1024 points: the wave-per-line 2048-point FFT
+        constexpr int M2 = 2048, NH2 = 1024, RS = (32 * W2K_PITCH) / 2 + 1;
+        const size_t lds2 = ((size_t)M2 + 64 + NH2 + 2 + NH2 + (size_t)8 * RS) * 8;
+        const long long items2 = (long long)((j.n_lines + 7) / 8) * j.n_images;
+        const int grid2 = (int)std::min<long long>(items2, (long long)h->n_cus);
+        j.tw2 = t.tw2;
+        return launch_lds(h, ifftTB2_kernel, dim3(grid2), dim3(512), lds2, K_OTHER, j);
+    }
+    const int R = t.R, M = R * R, NH = M / 2, CS = R * (R + 1) + 2;
+    const size_t lds = ((size_t)M + NH + 2 + NH + (size_t)16 * CS) * 8;
+    const int per_cu = std::max(1, std::min(R == 16 ? 4 : 1, (int)((size_t)h->lds_limit / lds)));
+    // first pass (no epilogue): two lines per group and tile round
+    if (R == 32 && !j.potential && !dbg_env("MSL_NO_TWO_LINE_IFFT")) {
+        constexpr int CSN = 514;
+        const size_t lds2 = ((size_t)M + NH + 2 + NH + (size_t)32 * CSN) * 8;
+        const long long items2 = (long long)((j.n_lines + 31) / 32) * j.n_images;
+        const int grid2 = (int)std::min<long long>(items2, (long long)h->n_cus);
+        return launch_lds(h, ifftTB_two_kernel, dim3(grid2), dim3(512), lds2, K_OTHER, j);
+    }
+    // second pass on a half spectrum: two real lines per transform (32-line work items)
+    const bool pair = R == 32 && j.herm && j.potential && !dbg_env("MSL_NO_PAIRED_IFFT");
+    const long long items = (long long)((j.n_lines + (pair ? 31 : 15)) / (pair ? 32 : 16)) * j.n_images;
+    const dim3 grid((unsigned)std::min<long long>(items, (long long)h->n_cus * per_cu));
+    if (pair) return launch_lds(h, ifftTB_kernel<32, true>, grid, dim3(512), lds, K_OTHER, j);
+    if (R == 32) return launch_lds(h, ifftTB_kernel<32>, grid, dim3(512), lds, K_OTHER, j);
+    return launch_lds(h, ifftTB_kernel<16>, grid, dim3(256), lds, K_OTHER, j);
+}
+
+// lines of 2 R^2 = 512 points
+int launch_ifftT2(msl_handle* h, const msl_handle::OpDir& o, IfftT2Job j) {
+    constexpr int R = 16, N2 = R * R, N = 2 * N2;
+    const size_t lds = ((size_t)2 * N2 + (size_t)16 * (N + 1)) * 8;
+    const int per_cu = std::max(1, std::min(2, (int)((size_t)h->lds_limit / lds)));
+    // second pass on a half spectrum: two real lines per transform (32-line work items)
+    const bool pair = j.herm && j.potential && j.n_lines % 32 == 0 && !dbg_env("MSL_NO_PAIRED_IFFT");
+    const long long items = (long long)(j.n_lines / (pair ? 32 : 16)) * j.n_images;
+    const dim3 grid((unsigned)std::min<long long>(items, (long long)h->n_cus * per_cu));
+    j.tw = o.tw; j.tw2 = o.tw2;
+    if (pair) return launch_lds(h, ifftT2_kernel<16, true>, grid, dim3(256), lds, K_OTHER, j);
+    return launch_lds(h, ifftT2_kernel<16>, grid, dim3(256), lds, K_OTHER, j);
+}
+
+// The transposing forms: TR -> TRT along y on the rows kx <= nx/2 (the others are their mirror images, taken by the second pass's
+// loads) in whole blocks of `line_block` lines (the surplus rows are never read), then TRT -> TR / TRT along x with the potential
+// epilogue: the slices a pass along x reads stay in TRT as rows.  Job = IfftTBJob or IfftT2Job (the same fields but n_line).
+template <typename Job>
+int ifft_transposed(msl_handle* h, const PotGroup& p, int line_block, int (*launch)(msl_handle*, const msl_handle::OpDir&, Job)) {
+    const msl_config& c = h->cfg;
+    const long long npix = (long long)c.nx * c.ny;
+    Job a{};
+    a.in = p.TR; a.out_t = p.TRT; a.out_rows = nullptr;
+    a.in_is = a.out_t_is = npix; a.in_pitch = c.ny; a.out_t_pitch = c.nx; a.n_images = p.n_slices;
+    a.n_lines = (c.nx / 2 + 1 + line_block - 1) / line_block * line_block;
+    a.potential = 0; a.rows_parity = -1; a.slice_mod = c.nz;
+    Job b{};
+    b.in = p.TRT; b.out_t = p.TR; b.out_rows = p.TRT;
+    b.in_is = b.out_t_is = b.out_rows_is = npix; b.in_pitch = c.nx; b.out_t_pitch = c.ny; b.out_rows_pitch = c.nx;
+    b.n_lines = c.ny; b.n_images = p.n_slices; b.potential = 1; b.herm = 1; b.slice_mod = c.nz;
+    b.rows_parity = slice_is_transposed(h, 1) ? 1 : 0;       // (scheme b: slice s is read along x iff s is odd)
+    b.scale = p.vscale; b.sigma_over_pi = (float)(c.sigma / M_PI);
+    if constexpr (std::is_same<Job, IfftTBJob>::value) { a.n_line = c.ny; b.n_line = c.nx; }
+    const int rc = launch(h, h->opy, a);
+    return rc ? rc : launch(h, h->opx, b);
+}
+
+// PI_LINES: rows, then columns with the epilogue, in place; slices a pass along x reads are transposed by the column kernel (COL_TPOT) or afterwards
+int ifft_inplace(msl_handle* h, const PotGroup& p) {
+    const msl_config& c = h->cfg;
+    int rc;
+    if (h->Ry) {
+        RowJob r = row_job(h, p.TR, p.n_slices, c.ny);
+        r.do_ifft = 1;
+        if (p.half_rows) { const int Gr = 256 / h->Ry; r.nx = (c.nx / 2 + 1 + Gr - 1) / Gr * Gr; }     // whole row groups (the surplus rows are never read)
+        if ((rc = launch_row_fast(h, r, K_OTHER))) return rc;
+    } else {
+        LineArgs r = row_args(h, p.TR, p.TR, p.n_slices, c.ny);
+        r.fft1 = -1;
+        if ((rc = launch_lines(h, h->plan_y, r, K_OTHER))) return rc;
+    }
+    if (h->Rx) {
+        ColJob k = col_job(h, p.TR, p.TR, p.n_slices, c.ny, c.ny);
+        k.flags = COL_INV | COL_POTENTIAL; k.scale = p.vscale; k.sigma = (float)c.sigma; k.out_real = h->V; k.slice_mod = c.nz;
+        // (a kept V is written by the untransposed store only: with keep_potential the x-pass slices are transposed afterwards)
+        if (h->onepass && !h->V) { k.flags |= COL_TPOT; k.tparity = h->scheme_b ? 0 : ((c.nz - 1) & 1); k.out_t = p.TRT; }
+        if ((rc = p.half_rows ? launch_col_herm(h, k, K_OTHER) : launch_col_fast(h, k, K_OTHER))) return rc;
+        return (h->onepass && h->V) ? transpose_odd_slices(h) : MSL_OK;
+    }
+    LineArgs k = col_args(h, p.TR, p.TR, p.n_slices, c.ny, c.ny);
+    k.fft1 = -1; k.scale = p.vscale;
+    k.store_mode = STORE_POTENTIAL; k.out_real = h->V; k.sigma = (float)c.sigma;
+    if ((rc = launch_lines(h, h->plan_x, k, K_OTHER))) return rc;
+    const int saved = h->cur_batch;                         // one-pass loop on such a grid: x-pass slices transposed, stack by stack
+    for (int f = 0; f < p.g && rc == MSL_OK; ++f) { h->cur_batch = p.slot + f; rc = transpose_odd_slices(h); }
+    h->cur_batch = saved;
+    return rc;
+}
+
+// V_s = Re ifft2(R_s) / (dx^2 dy^2);  t_s = exp(i sigma V_s)  -- in place over the (frames, nz, nx, ny) stacks of the group.
+// Slices a pass along x reads are kept transposed (scheme b: odd slices; alternating scheme: odd distance to the last one):
+// with several frames per launch the slice number is the image index modulo nz (slice_mod).
+int potential_ifft(msl_handle* h, const PotGroup& p) {
+    h->cur = nullptr;
+    switch (h->pot_ifft) {
+    case PI_WAVE2K: return ifft_transposed(h, p, 8, launch_ifftTW);
+    case PI_CHIRPZ: return ifft_transposed(h, p, 1, launch_ifftTB);
+    case PI_TWO:    return ifft_transposed(h, p, 16, launch_ifftT2);
+    default:        return ifft_inplace(h, p);
+    }
+}
+
+// Projected potentials + transmission functions of `count` MD frames (the same atoms, `count` sets of positions) into the batch
+// slots first_slot .. first_slot + count - 1: ONE launch each of the atom preparation, the stable counting sort (keys = frame x
+// slice x species), the two phase tables, the structure factor and the two inverse-transform passes for as many frames as the
+// phase tables of a group may take (6 GB), instead of that sequence per frame.  The reference builds one Potential per frame
+// (calculators.py:172-186, potentials.py:188-348); with its default single probe that build IS the frame (round 2: 0.43 of
+// 0.62 ms at 512^2 x 100 slices, of which ~110 us were launches of 5-15 us kernels and four small copies per frame).
+int build_potentials(msl_handle* h, const double* pos, const int32_t* Z, int64_t n, int count, int first_slot, int32_t ax1, int32_t ax2, int32_t axs) {
+    const msl_config& c = h->cfg;
+    const size_t npix = (size_t)c.nx * c.ny;
+    PotGroup p{};
+    int rc = map_species(h, Z, n, p);
+    if (rc) return rc;
+    // with launch timing off the call only queues work: no event, no host wait (the frames of a run pipeline on the stream)
+    EventPair timer;
+    if (c.launch_timing && (rc = timer.begin(h))) return rc;
+    if (p.nsp > h->ff_species_cap) {
+        if ((rc = dalloc(h, &h->d_ff, npix * p.nsp))) return rc;
+        h->ff_species_cap = p.nsp;
+        h->ff_n = 0;
+    }
+    p.n = n; p.ax1 = ax1; p.ax2 = ax2; p.axs = axs;
+    p.cx = c.nx / 2 + 1; p.cy = c.ny / 2 + 1; p.keys_per_frame = c.nz * std::max(p.nsp, 1);
+    p.half_rows = pot_half_rows(h);
+    p.sf_stream = (double)n / std::max(1, p.keys_per_frame) >= 128.0 && !dbg_env("MSL_SF_TILED");
+    p.vscale = (float)(1.0 / ((double)c.nx * c.ny) / (c.dx * c.dx * c.dy * c.dy));
+    // frames per group: the phase tables of a group (n atoms x (nx/2 + 1 + ny/2 + 1) x 8 bytes per frame) stay under 6 GB
+    const size_t table_bytes_per_frame = std::max<size_t>(1, (size_t)n * (size_t)(p.cx + p.cy) * sizeof(float2));
+    const int G = (int)std::max<size_t>(1, std::min<size_t>((size_t)count, (size_t)6e9 / table_bytes_per_frame));
+    const int nkeys_cap = p.keys_per_frame * G;
+    if (nkeys_cap > h->keys_cap) {
+        if ((rc = dalloc(h, &h->d_counts, (size_t)nkeys_cap + 1))) return rc;
+        if ((rc = dalloc(h, &h->d_start, (size_t)nkeys_cap + 1))) return rc;
+        h->keys_cap = nkeys_cap;
+    }
+    if ((rc = ensure_atoms(h, (size_t)n * G, (size_t)n * G + (size_t)(SF_ALIGN - 1) * nkeys_cap))) return rc;
+    for (int f0 = 0; f0 < count; f0 += G) {
+        p.g = std::min(G, count - f0); p.slot = first_slot + f0;
+        p.TR = h->trans + (size_t)p.slot * c.nz * npix;
+        p.TRT = h->transT ? h->transT + (size_t)p.slot * c.nz * npix : nullptr;
+        p.n_slices = c.nz * p.g; p.nkeys = p.keys_per_frame * p.g;
+        p.rows = (long long)n * p.g; p.rows_pad = p.rows + (long long)(SF_ALIGN - 1) * p.nkeys;
+        if (n > 0 && p.nsp > 0) {
+            if ((rc = stage_atoms(h, p, pos + (size_t)f0 * n * 3, Z, f0 == 0)) || (rc = bin_atoms(h, p)) || (rc = launch_structure_factor(h, p)))
+                return rc;
+        } else {
+            HIPCHK(h, hipMemsetAsync(p.TR, 0, npix * p.n_slices * sizeof(float2), h->stream));
+        }
+        if ((rc = potential_ifft(h, p))) return rc;
+    }
+    h->n_species = p.nsp;
+    if ((rc = timer.end(h, &h->ctr.ms_potential))) return rc;
+    h->have_potential = true;
+    return MSL_OK;
+}
+
 }  // namespace
 
 // The per-lane / wave-split time kernels (70 instantiations) are compiled in translation units of their own (tacaw_direct.hip,
@@ -1463,11 +1799,11 @@ int msl_create(const msl_config* cfg, msl_handle** out) {
     auto bail = [&](int rc) { g_create_error = h->err; msl_destroy(h); return rc; };
     if (hipSetDevice(cfg->device) != hipSuccess) return bail(fail(h, MSL_ERR_HIP, "hipSetDevice(%d) failed", cfg->device));
     if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) return bail(fail(h, MSL_ERR_HIP, "hipStreamCreate failed"));
-    (void)hipFuncSetAttribute((const void*)line_fft_kernel<0, false>, hipFuncAttributeMaxDynamicSharedMemorySize, h->lds_limit);
-    (void)hipFuncSetAttribute((const void*)line_fft_kernel<1, false>, hipFuncAttributeMaxDynamicSharedMemorySize, h->lds_limit);
-    (void)hipFuncSetAttribute((const void*)line_fft_kernel<1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, h->lds_limit);
-    (void)hipFuncSetAttribute((const void*)line_fft_kernel<2, false>, hipFuncAttributeMaxDynamicSharedMemorySize, h->lds_limit);
-    (void)hipFuncSetAttribute((const void*)line_fft_kernel<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, h->lds_limit);
+    allow_lds(h, line_fft_kernel<0, false>);
+    allow_lds(h, line_fft_kernel<1, false>);
+    allow_lds(h, line_fft_kernel<1, true>);
+    allow_lds(h, line_fft_kernel<2, false>);
+    allow_lds(h, line_fft_kernel<2, true>);
     int rc;
     {   // the lane <-> register exchange of every register kernel rests on inline asm the compiler cannot check: test it once per process
         static int exchange_ok = -1;
@@ -1486,10 +1822,10 @@ int msl_create(const msl_config* cfg, msl_handle** out) {
         if (ry && cfg->nx % (256 / ry) == 0) { h->Ry = ry; if ((rc = make_tw4(h, &h->tw4_y, ry))) return bail(rc); }
         if (rx && cfg->ny % 16 == 0 && cfg->ny >= 32) { h->Rx = rx; if ((rc = make_tw4(h, &h->tw4_x, rx))) return bail(rc); }
         { const char* e = dbg_env("MSL_ROW_PCHUNK"); if (e) h->row_pchunk = atoi(e); }
-        (void)hipFuncSetAttribute((const void*)row_pass_pf_kernel<32>, hipFuncAttributeMaxDynamicSharedMemorySize, h->lds_limit);
-        (void)hipFuncSetAttribute((const void*)row_pass_pf_kernel<16>, hipFuncAttributeMaxDynamicSharedMemorySize, h->lds_limit);
-        (void)hipFuncSetAttribute((const void*)col_pass_kernel<32>, hipFuncAttributeMaxDynamicSharedMemorySize, h->lds_limit);
-        (void)hipFuncSetAttribute((const void*)col_pass_kernel<16>, hipFuncAttributeMaxDynamicSharedMemorySize, h->lds_limit);
+        allow_lds(h, row_pass_pf_kernel<32>);
+        allow_lds(h, row_pass_pf_kernel<16>);
+        allow_lds(h, col_pass_kernel<32>);
+        allow_lds(h, col_pass_kernel<16>);
     }
     const size_t npix = (size_t)cfg->nx * cfg->ny;
     {
@@ -1520,12 +1856,13 @@ int msl_create(const msl_config* cfg, msl_handle** out) {
             if (h->need_psi0T && (rc = dalloc(h, &h->psi0T, (size_t)cfg->ny * h->pitchT * images))) return bail(rc);
             if ((rc = dalloc(h, &h->transT, npix * cfg->nz * h->FB))) return bail(rc);
             { const char* ev = dbg_env("MSL_DEBUG_FLAGS_MASK"); if (ev) h->debug_flags_mask = atoi(ev); }
-            (void)hipFuncSetAttribute((const void*)row_pass2_kernel<32>, hipFuncAttributeMaxDynamicSharedMemorySize, h->lds_limit);
-            (void)hipFuncSetAttribute((const void*)row_pass2_kernel<16>, hipFuncAttributeMaxDynamicSharedMemorySize, h->lds_limit);
+            allow_lds(h, row_pass2_kernel<32>);
+            allow_lds(h, row_pass2_kernel<16>);
         }
     }
     if ((rc = dalloc(h, &h->trans, npix * cfg->nz * h->FB))) return bail(rc);
     if (cfg->keep_potential && (rc = dalloc(h, &h->V, npix * cfg->nz))) return bail(rc);
+    h->pot_ifft = plan_pot_ifft(h);
     if (cfg->n_frames > 0) {
         if ((h->bx > 1 || h->by > 1) && (rc = dalloc(h, &h->bin_stage, (size_t)h->wx * h->wy * cfg->n_probes * h->FB))) return bail(rc);
         if ((rc = dalloc(h, &h->wf, h->wpitch * cfg->n_probes * cfg->n_frames))) return bail(rc);
@@ -1695,331 +2032,6 @@ int msl_upload_probes(msl_handle* h, const float* c64, int32_t n_probes) {
     return MSL_OK;
 }
 
-// Projected potentials + transmission functions of `count` MD frames (the same atoms, `count` sets of positions) into the batch
-// slots first_slot .. first_slot + count - 1: ONE launch each of the atom preparation, the stable counting sort (keys = frame x
-// slice x species), the two phase tables, the structure factor and the two inverse-transform passes for as many frames as the
-// phase tables of a group may take (6 GB), instead of that sequence per frame.  The reference builds one Potential per frame
-// (calculators.py:172-186, potentials.py:188-348); with its default single probe that build IS the frame (round 2: 0.43 of
-// 0.62 ms at 512^2 x 100 slices, of which ~110 us were launches of 5-15 us kernels and four small copies per frame).
-static int build_potentials(msl_handle* h, const double* pos, const int32_t* Z, int64_t n, int count, int first_slot, int32_t ax1,
-                            int32_t ax2, int32_t axs) {
-    const msl_config& c = h->cfg;
-    const size_t npix = (size_t)c.nx * c.ny;
-    // species present (sorted ascending, like np.unique)
-    int z2s[104];
-    for (int i = 0; i < 104; ++i) z2s[i] = -1;
-    for (int64_t a = 0; a < n; ++a) {
-        if (Z[a] < 1 || Z[a] > 103) return fail(h, MSL_ERR_INVALID, "msl_build_potential: atomic number %d out of 1..103", Z[a]);
-        z2s[Z[a]] = 0;
-    }
-    int species[104], nsp = 0;
-    for (int z = 1; z <= 103; ++z) if (z2s[z] == 0) { z2s[z] = nsp; species[nsp++] = z; }
-    int rc;
-    // with launch timing off the call only queues work: no event, no host wait (the frames of a run pipeline on the stream)
-    const bool timed = h->cfg.launch_timing != 0;
-    EventPair evp_; hipEvent_t &e0 = evp_.a, &e1 = evp_.b;
-    if (timed) {
-        HIPCHK(h, hipEventCreate(&e0)); HIPCHK(h, hipEventCreate(&e1));
-        HIPCHK(h, hipEventRecord(e0, h->stream));
-    }
-    if (nsp > h->ff_species_cap) {
-        if ((rc = dalloc(h, &h->d_ff, npix * nsp))) return rc;
-        h->ff_species_cap = nsp;
-        h->ff_n = 0;
-    }
-    // frames per group: the phase tables of a group (n atoms x (nx/2 + 1 + ny/2 + 1) x 8 bytes per frame) stay under 6 GB
-    const int cx = c.nx / 2 + 1, cy = c.ny / 2 + 1;             // table columns the quadrant kernel reads
-    const size_t table_bytes_per_frame = std::max<size_t>(1, (size_t)n * (size_t)(cx + cy) * sizeof(float2));
-    const int G = (int)std::max<size_t>(1, std::min<size_t>((size_t)count, (size_t)6e9 / table_bytes_per_frame));
-    const int keys_per_frame = c.nz * std::max(nsp, 1);
-    const int nkeys_cap = keys_per_frame * G;
-    if (nkeys_cap > h->keys_cap) {
-        if ((rc = dalloc(h, &h->d_counts, (size_t)nkeys_cap + 1))) return rc;
-        if ((rc = dalloc(h, &h->d_start, (size_t)nkeys_cap + 1))) return rc;
-        h->keys_cap = nkeys_cap;
-    }
-    if ((rc = ensure_atoms(h, (size_t)n * G, (size_t)n * G + (size_t)(SF_ALIGN - 1) * nkeys_cap))) return rc;
-    // R_s is Hermitian (real V): only the rows kx <= nx/2 are written and row-transformed when the inverse transform mirrors them
-    // itself (every register-kernel path: col_pass_kernel<.., HERM>, ifftT2 / ifftTB / ifftTW with job.herm)
-    const bool tw_axes = h->onepass && h->opx.base == AX_WAVE2K && h->opy.base == AX_WAVE2K && !h->V && h->transT;
-    const bool t2_axes = h->onepass && h->opx.base == AX_TWO && h->opy.base == AX_TWO && !h->V;
-    const bool tb_axes = h->onepass && !h->V && h->transT && h->opx.cz.R && h->opy.cz.R;      // chirp-z tables along both axes
-    const bool herm_ifft = h->Rx && h->Ry;                      // four-step kernels on both axes (256 / 1024)
-    const bool herm_tb = tb_axes, herm_t2 = t2_axes, herm_tw = tw_axes;
-    const bool half_rows = herm_ifft || herm_tb || herm_t2 || herm_tw;
-    const float vscale = (float)(1.0 / ((double)c.nx * c.ny) / (c.dx * c.dx * c.dy * c.dy));
-    const bool ifft_t2 = t2_axes;
-    const bool ifft_tb = tb_axes;
-    const bool ifft_tw = tw_axes;
-    bool maps_sent = false;
-    for (int f0 = 0; f0 < count; f0 += G) {
-        const int g = std::min(G, count - f0);
-        const int slot = first_slot + f0;
-        float2* const TR = h->trans + (size_t)slot * c.nz * npix;                 // batch slots this group's stacks go to
-        float2* const TRT = h->transT ? h->transT + (size_t)slot * c.nz * npix : nullptr;
-        const int n_slices = c.nz * g, nkeys = keys_per_frame * g;
-        const long long rows = (long long)n * g;
-        bool recip_written = false;
-        if (n > 0 && nsp > 0) {
-            {
-                msl_handle::HostStage& st = h->stage[h->stage_pos++ & 1];
-                if (!st.ev) HIPCHK(h, hipEventCreateWithFlags(&st.ev, hipEventDisableTiming));
-                if (st.used) HIPCHK(h, hipEventSynchronize(st.ev));            // the copies queued from this slot two calls ago
-                const size_t off_sp = sizeof z2s, off_Z = (off_sp + sizeof species + 7) & ~(size_t)7;
-                const size_t off_pos = (off_Z + (size_t)n * sizeof(int) + 7) & ~(size_t)7, need = off_pos + (size_t)rows * 3 * sizeof(double);
-                if (need > st.bytes) {
-                    if (st.buf) (void)hipHostFree(st.buf);
-                    st.buf = nullptr; st.bytes = 0;
-                    const size_t cap = need + need / 4;
-                    if (hipHostMalloc((void**)&st.buf, cap, hipHostMallocDefault) != hipSuccess)
-                        return fail(h, MSL_ERR_NOMEM, "hipHostMalloc(%zu bytes) failed", cap);
-                    st.bytes = cap;
-                }
-                memcpy(st.buf + off_pos, pos + (size_t)f0 * n * 3, (size_t)rows * 3 * sizeof(double));
-                if (!maps_sent) {
-                    memcpy(st.buf, z2s, sizeof z2s);
-                    memcpy(st.buf + off_sp, species, sizeof species);
-                    memcpy(st.buf + off_Z, Z, (size_t)n * sizeof(int));
-                    HIPCHK(h, hipMemcpyAsync(h->d_z2s, st.buf, sizeof z2s, hipMemcpyHostToDevice, h->stream));
-                    HIPCHK(h, hipMemcpyAsync(h->d_species, st.buf + off_sp, nsp * sizeof(int), hipMemcpyHostToDevice, h->stream));
-                    HIPCHK(h, hipMemcpyAsync(h->d_Z, st.buf + off_Z, (size_t)n * sizeof(int), hipMemcpyHostToDevice, h->stream));
-                    maps_sent = true;
-                }
-                HIPCHK(h, hipMemcpyAsync(h->d_pos, st.buf + off_pos, (size_t)rows * 3 * sizeof(double), hipMemcpyHostToDevice, h->stream));
-                HIPCHK(h, hipEventRecord(st.ev, h->stream));
-                st.used = true;
-            }
-            HIPCHK(h, hipMemsetAsync(h->d_counts, 0, ((size_t)nkeys + 1) * sizeof(int), h->stream));
-            const double lx = c.nx * c.dx, ly = c.ny * c.dy;
-            // f_Z(q^2) depends on the grid and the species only (potentials.py:283-293 recomputes it per frame): build the table
-            // when the species list changes, i.e. once per run
-            if (nsp != h->ff_n || memcmp(species, h->ff_species, nsp * sizeof(int)) != 0) {
-                long long tot = (long long)npix * nsp;
-                hipLaunchKernelGGL(formfactor_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, h->stream, h->d_ff, h->d_abcd,
-                                   h->d_species, nsp, c.nx, c.ny, 1.0 / lx, 1.0 / ly);
-                memcpy(h->ff_species, species, nsp * sizeof(int));
-                h->ff_n = nsp;
-            }
-            hipLaunchKernelGGL(atom_prep_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, h->stream, h->d_pos, h->d_Z,
-                               (long long)n, g, h->d_z2s, h->d_lo, h->d_hi, c.nz, nsp, ax1, ax2, axs, 1.0 / lx, 1.0 / ly, h->d_key,
-                               h->d_u1, h->d_u2, h->d_counts);
-            // many atoms per (slice, species): the streaming structure-factor kernel, whose bins are padded to whole half-trips
-            const bool sf_stream = (double)n / std::max(1, keys_per_frame) >= 128.0 && !dbg_env("MSL_SF_TILED");
-            hipLaunchKernelGGL(bin_scan_kernel, dim3(1), dim3(1024), 0, h->stream, h->d_counts, h->d_start, nkeys, sf_stream ? SF_ALIGN : 1);
-            hipLaunchKernelGGL(bin_fill_kernel, dim3(nkeys), dim3(1024), 0, h->stream, h->d_key, (long long)n, keys_per_frame, h->d_start, h->d_order);
-            HIPCHK(h, hipGetLastError());
-            // atoms that fell into a slice: d_start[nkeys], read by the kernels themselves (grids sized for all atoms of the group)
-            const int* n_sorted = h->d_start + nkeys;
-            recip_written = true;
-            const long long rows_pad = rows + (long long)(SF_ALIGN - 1) * nkeys;          // sorted rows at most: every bin padded to SF_ALIGN
-            if (rows_pad > 0x7fffffffLL) return fail(h, MSL_ERR_INVALID, "msl_build_potentials: %lld padded table rows in one group exceed 2^31", rows_pad);
-            const long long tx = rows_pad * cx, ty = rows_pad * cy;
-            hipLaunchKernelGGL(phase_table_kernel, dim3((unsigned)((tx + 255) / 256)), dim3(256), 0, h->stream, h->d_ex, h->d_u1,
-                               h->d_order, n_sorted, c.nx, cx, cx);
-            hipLaunchKernelGGL(phase_table_kernel, dim3((unsigned)((ty + 255) / 256)), dim3(256), 0, h->stream, h->d_ey, h->d_u2,
-                               h->d_order, n_sorted, c.ny, cy, cy);
-            // matrix-core kernel over the quadrant of non-negative frequencies 0 .. n/2 in 32 x 32 tiles; on power-of-two grids
-            // (n/2 + 1 = 32 k + 1) the Nyquist row / column goes to the edge kernel instead of a tile row of its own
-            const bool edge_x = (c.nx % 2 == 0) && (cx % 32 == 1) && cx > 1, edge_y = (c.ny % 2 == 0) && (cy % 32 == 1) && cy > 1;
-            const int tiles_x = edge_x ? cx / 32 : (cx + 31) / 32, tiles_y = edge_y ? cy / 32 : (cy + 31) / 32;
-            const int n_tiles = tiles_x * tiles_y, wg_per_slice = (n_tiles + 3) / 4;
-            const long long n_wg = (long long)wg_per_slice * ((n_slices + 7) / 8 * 8);
-            if (n_wg > 0x7fffffffLL) return fail(h, MSL_ERR_UNSUPPORTED, "structure factor: too many workgroups");
-            if (sf_stream) {
-                // persistent form, one wave per SIMD: one workgroup per CU, a multiple of 8 (XCD-local slices)
-                const int n_pers = std::max(8, h->n_cus / 8 * 8);
-                if (dbg_env("MSL_SF_F32"))                   // the exact-f32 matrix instruction (A/B against the split-bf16 form)
-                    hipLaunchKernelGGL(structure_factor_stream_kernel, dim3((unsigned)n_pers), dim3(256), 0, h->stream, TR, h->d_ex, h->d_ey, h->d_ff,
-                                       h->d_start, nsp, c.nx, c.ny, tiles_y, n_tiles, (int)rows_pad, half_rows ? 0 : 1, cx, cy, n_slices);
-                // two kx tiles per wave sharing the ey planes (potential.h) where a slice's tables outgrow an XCD's L2: 2048^2 x 50 potential
-                // 8.67 -> 8.17 ms per frame, 1024^2 (C3) 3.72 -> 3.69 (kept on the one-tile kernel)
-                else if ((n_tiles >= 512 || (tiles_x >= 2 && dbg_env("MSL_SF_TWO_TILES"))) && !dbg_env("MSL_SF_ONE_TILE"))
-                    hipLaunchKernelGGL(structure_factor_stream_bf16x2_kernel, dim3((unsigned)n_pers), dim3(256), 4 * 128 * 64 * sizeof(float), h->stream, TR, h->d_ex, h->d_ey, h->d_ff,
-                                       h->d_start, nsp, c.nx, c.ny, tiles_y, ((tiles_x + 1) / 2) * tiles_y, (int)rows_pad, half_rows ? 0 : 1, cx, cy, n_slices);
-                else
-                    hipLaunchKernelGGL(structure_factor_stream_bf16_kernel, dim3((unsigned)n_pers), dim3(256), 0, h->stream, TR, h->d_ex, h->d_ey, h->d_ff,
-                                       h->d_start, nsp, c.nx, c.ny, tiles_y, n_tiles, (int)rows_pad, half_rows ? 0 : 1, cx, cy, n_slices);
-            } else
-                hipLaunchKernelGGL(structure_factor_quad_kernel, dim3((unsigned)n_wg), dim3(256), 0, h->stream, TR, h->d_ex, h->d_ey, h->d_ff,
-                                   h->d_start, nsp, c.nx, c.ny, tiles_y, n_tiles, (int)rows_pad, half_rows ? 0 : 1, cx, cy, n_slices, wg_per_slice);
-            if (edge_x || edge_y) {
-                const int bins = (edge_x ? cy : 0) + (edge_y ? (edge_x ? cx - 1 : cx) : 0);
-                for (int s0 = 0; s0 < n_slices; s0 += 65535) {
-                    const int ns = std::min(65535, n_slices - s0);
-                    hipLaunchKernelGGL(structure_factor_edge_kernel, dim3((bins + 127) / 128, ns), dim3(128), 0, h->stream,
-                                       TR + (size_t)s0 * npix, h->d_ex, h->d_ey, h->d_ff, h->d_start + (size_t)s0 * nsp, nsp, c.nx, c.ny,
-                                       edge_x ? 1 : 0, edge_y ? 1 : 0, half_rows ? 0 : 1, cx, cy);
-                }
-            }
-            HIPCHK(h, hipGetLastError());
-        }
-        if (!recip_written) HIPCHK(h, hipMemsetAsync(TR, 0, npix * n_slices * sizeof(float2), h->stream));
-        // V_s = Re ifft2(R_s) / (dx^2 dy^2);  t_s = exp(i sigma V_s)  -- in place over the (frames, nz, nx, ny) stacks of the group.
-        // Slices a pass along x reads are kept transposed (scheme b: odd slices; alternating scheme: odd distance to the last one):
-        // with several frames per launch the slice number is the image index modulo nz (slice_mod).
-        h->cur = nullptr;
-        if (ifft_tw) {
-            auto passw = [&](const msl_handle::OpDir& o, IfftTBJob j) -> int {
-                constexpr int N2 = 2048;
-                const size_t lds = ((size_t)N2 + 64 + (size_t)8 * (N2 + 1)) * 8;
-                const long long items = (long long)(j.n_lines / 8) * j.n_images;
-                const int grid = (int)std::min<long long>(items, (long long)h->n_cus);
-                j.tw = o.tw; j.tw2 = o.tw2;
-                (void)hipFuncSetAttribute((const void*)ifftTW_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, h->lds_limit);
-                hipLaunchKernelGGL(ifftTW_kernel, dim3(grid), dim3(512), lds, h->stream, j);
-                HIPCHK(h, hipGetLastError());
-                return mark_launch(h, K_OTHER);
-            };
-            IfftTBJob a{};
-            a.in = TR; a.out_t = TRT; a.out_rows = nullptr;
-            a.in_is = a.out_t_is = (long long)npix; a.in_pitch = c.ny; a.out_t_pitch = c.nx; a.n_lines = c.nx; a.n_line = c.ny; a.n_images = n_slices;
-            a.potential = 0; a.rows_parity = -1; a.slice_mod = c.nz;
-            if (herm_tw) a.n_lines = (c.nx / 2 + 1 + 7) / 8 * 8;
-            if ((rc = passw(h->opy, a))) return rc;
-            IfftTBJob b{};
-            b.in = TRT; b.out_t = TR; b.out_rows = TRT;
-            b.in_is = b.out_t_is = b.out_rows_is = (long long)npix; b.in_pitch = c.nx; b.out_t_pitch = c.ny; b.out_rows_pitch = c.nx;
-            b.n_lines = c.ny; b.n_line = c.nx; b.n_images = n_slices; b.potential = 1; b.herm = herm_tw ? 1 : 0; b.slice_mod = c.nz;
-            b.rows_parity = slice_is_transposed(h, 1) ? 1 : 0;
-            b.scale = vscale; b.sigma_over_pi = (float)(c.sigma / M_PI);
-            if ((rc = passw(h->opx, b))) return rc;
-        } else if (ifft_tb) {
-            auto pass = [&](const CzTables& o, IfftTBJob j) -> int {
-                if (o.R == 64) {                                // 513 .. 1024 points: the wave-per-line 2048-point FFT
-                    constexpr int M2 = 2048, NH2 = 1024, RS = (32 * W2K_PITCH) / 2 + 1;
-                    const size_t lds2 = ((size_t)M2 + 64 + NH2 + 2 + NH2 + (size_t)8 * RS) * 8;
-                    const long long items2 = (long long)((j.n_lines + 7) / 8) * j.n_images;
-                    const int grid2 = (int)std::min<long long>(items2, (long long)h->n_cus);
-                    j.tw = o.tw; j.tw2 = o.tw2; j.bf = o.bf; j.bw = o.bw;
-                    (void)hipFuncSetAttribute((const void*)ifftTB2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, h->lds_limit);
-                    hipLaunchKernelGGL(ifftTB2_kernel, dim3(grid2), dim3(512), lds2, h->stream, j);
-                    HIPCHK(h, hipGetLastError());
-                    return mark_launch(h, K_OTHER);
-                }
-                const int R = o.R, M = R * R, NH = M / 2, CS = R * (R + 1) + 2;
-                const size_t lds = ((size_t)M + NH + 2 + NH + (size_t)16 * CS) * 8;
-                const int per_cu = std::max(1, std::min(R == 16 ? 4 : 1, (int)((size_t)h->lds_limit / lds)));
-                // first pass (no epilogue): two lines per group and tile round
-                if (R == 32 && !j.potential && !dbg_env("MSL_NO_TWO_LINE_IFFT")) {
-                    constexpr int CSN = 514;
-                    const size_t lds2 = ((size_t)M + NH + 2 + NH + (size_t)32 * CSN) * 8;
-                    const long long items2 = (long long)((j.n_lines + 31) / 32) * j.n_images;
-                    const int grid2 = (int)std::min<long long>(items2, (long long)h->n_cus);
-                    j.tw = o.tw; j.bf = o.bf; j.bw = o.bw;
-                    (void)hipFuncSetAttribute((const void*)ifftTB_two_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, h->lds_limit);
-                    hipLaunchKernelGGL(ifftTB_two_kernel, dim3(grid2), dim3(512), lds2, h->stream, j);
-                    HIPCHK(h, hipGetLastError());
-                    return mark_launch(h, K_OTHER);
-                }
-                // second pass on a half spectrum: two real lines per transform (32-line work items)
-                const bool pair = R == 32 && j.herm && j.potential && !dbg_env("MSL_NO_PAIRED_IFFT");
-                const long long items = (long long)((j.n_lines + (pair ? 31 : 15)) / (pair ? 32 : 16)) * j.n_images;
-                const int grid = (int)std::min<long long>(items, (long long)h->n_cus * per_cu);
-                j.tw = o.tw; j.bf = o.bf; j.bw = o.bw;
-                if (pair) {
-                    (void)hipFuncSetAttribute((const void*)ifftTB_kernel<32, true>, hipFuncAttributeMaxDynamicSharedMemorySize, h->lds_limit);
-                    hipLaunchKernelGGL((ifftTB_kernel<32, true>), dim3(grid), dim3(512), lds, h->stream, j);
-                } else if (R == 32) {
-                    (void)hipFuncSetAttribute((const void*)ifftTB_kernel<32>, hipFuncAttributeMaxDynamicSharedMemorySize, h->lds_limit);
-                    hipLaunchKernelGGL(ifftTB_kernel<32>, dim3(grid), dim3(512), lds, h->stream, j);
-                } else {
-                    (void)hipFuncSetAttribute((const void*)ifftTB_kernel<16>, hipFuncAttributeMaxDynamicSharedMemorySize, h->lds_limit);
-                    hipLaunchKernelGGL(ifftTB_kernel<16>, dim3(grid), dim3(256), lds, h->stream, j);
-                }
-                HIPCHK(h, hipGetLastError());
-                return mark_launch(h, K_OTHER);
-            };
-            IfftTBJob a{};
-            a.in = TR; a.out_t = TRT; a.out_rows = nullptr;
-            a.in_is = a.out_t_is = (long long)npix; a.in_pitch = c.ny; a.out_t_pitch = c.nx; a.n_lines = c.nx; a.n_line = c.ny; a.n_images = n_slices;
-            a.potential = 0; a.rows_parity = -1; a.slice_mod = c.nz;
-            if (herm_tb) a.n_lines = c.nx / 2 + 1;                  // the other rows are their mirror images (taken by the second pass's loads)
-            if ((rc = pass(h->opy.cz, a))) return rc;
-            IfftTBJob b{};
-            b.in = TRT; b.out_t = TR; b.out_rows = TRT;
-            b.in_is = b.out_t_is = b.out_rows_is = (long long)npix; b.in_pitch = c.nx; b.out_t_pitch = c.ny; b.out_rows_pitch = c.nx;
-            b.n_lines = c.ny; b.n_line = c.nx; b.n_images = n_slices; b.potential = 1; b.herm = herm_tb ? 1 : 0; b.slice_mod = c.nz;
-            b.rows_parity = slice_is_transposed(h, 1) ? 1 : 0;       // the slices a pass along x reads stay in TRT as rows
-            b.scale = vscale; b.sigma_over_pi = (float)(c.sigma / M_PI);
-            if ((rc = pass(h->opx.cz, b))) return rc;
-        } else if (ifft_t2) {
-            // 512 x 512 grids: two transposing inverse-FFT passes on the register kernels (TR -> TRT along y, TRT -> TR / TRT along
-            // x with the potential epilogue; slices a pass along x reads stay in TRT as rows)
-            auto pass = [&](const IfftT2Job& j) -> int {
-                constexpr int R = 16, N2 = R * R, N = 2 * N2;
-                const size_t lds = ((size_t)2 * N2 + (size_t)16 * (N + 1)) * 8;
-                const int per_cu = std::max(1, std::min(2, (int)((size_t)h->lds_limit / lds)));
-                // second pass on a half spectrum: two real lines per transform (32-line work items)
-                const bool pair = j.herm && j.potential && j.n_lines % 32 == 0 && !dbg_env("MSL_NO_PAIRED_IFFT");
-                const long long items = (long long)(j.n_lines / (pair ? 32 : 16)) * j.n_images;
-                const int grid = (int)std::min<long long>(items, (long long)h->n_cus * per_cu);
-                if (pair) {
-                    (void)hipFuncSetAttribute((const void*)ifftT2_kernel<16, true>, hipFuncAttributeMaxDynamicSharedMemorySize, h->lds_limit);
-                    hipLaunchKernelGGL((ifftT2_kernel<16, true>), dim3(grid), dim3(256), lds, h->stream, j);
-                    HIPCHK(h, hipGetLastError());
-                    return mark_launch(h, K_OTHER);
-                }
-                (void)hipFuncSetAttribute((const void*)ifftT2_kernel<16>, hipFuncAttributeMaxDynamicSharedMemorySize, h->lds_limit);
-                hipLaunchKernelGGL(ifftT2_kernel<16>, dim3(grid), dim3(256), lds, h->stream, j);
-                HIPCHK(h, hipGetLastError());
-                return mark_launch(h, K_OTHER);
-            };
-            IfftT2Job a{};
-            a.in = TR; a.out_t = TRT; a.out_rows = nullptr; a.tw = h->opy.tw; a.tw2 = h->opy.tw2;
-            a.in_is = a.out_t_is = (long long)npix; a.in_pitch = c.ny; a.out_t_pitch = c.nx; a.n_lines = c.nx; a.n_images = n_slices;
-            a.potential = 0; a.rows_parity = -1; a.slice_mod = c.nz;
-            if (herm_t2) a.n_lines = (c.nx / 2 + 1 + 15) / 16 * 16;        // rows kx <= nx/2 in whole 16-line blocks (the surplus rows are never read)
-            if ((rc = pass(a))) return rc;
-            IfftT2Job b{};
-            b.in = TRT; b.out_t = TR; b.out_rows = TRT; b.tw = h->opx.tw; b.tw2 = h->opx.tw2;
-            b.in_is = b.out_t_is = b.out_rows_is = (long long)npix; b.in_pitch = c.nx; b.out_t_pitch = c.ny; b.out_rows_pitch = c.nx;
-            b.n_lines = c.ny; b.n_images = n_slices; b.potential = 1; b.rows_parity = 1; b.slice_mod = c.nz;      // scheme b: slice s is read along x iff s is odd
-            b.herm = herm_t2 ? 1 : 0;
-            b.scale = vscale; b.sigma_over_pi = (float)(c.sigma / M_PI);
-            if ((rc = pass(b))) return rc;
-        } else if (h->Ry) {
-            RowJob r = row_job(h, TR, n_slices, c.ny);
-            r.do_ifft = 1;
-            if (herm_ifft) { const int Gr = 256 / h->Ry; r.nx = (c.nx / 2 + 1 + Gr - 1) / Gr * Gr; }     // whole row groups (the surplus rows are never read)
-            if ((rc = launch_row_fast(h, r, K_OTHER))) return rc;
-        } else {
-            LineArgs r = row_args(h, TR, TR, n_slices, c.ny);
-            r.fft1 = -1;
-            if ((rc = launch_lines(h, h->plan_y, r, K_OTHER))) return rc;
-        }
-        if (ifft_t2 || ifft_tb || ifft_tw) {
-            // (both passes done above)
-        } else if (h->Rx) {
-            ColJob k = col_job(h, TR, TR, n_slices, c.ny, c.ny);
-            k.flags = COL_INV | COL_POTENTIAL; k.scale = vscale; k.sigma = (float)c.sigma; k.out_real = h->V; k.slice_mod = c.nz;
-            // (a kept V is written by the untransposed store only: with keep_potential the x-pass slices are transposed afterwards)
-            if (h->onepass && !h->V) { k.flags |= COL_TPOT; k.tparity = h->scheme_b ? 0 : ((c.nz - 1) & 1); k.out_t = TRT; }
-            if ((rc = herm_ifft ? launch_col_herm(h, k, K_OTHER) : launch_col_fast(h, k, K_OTHER))) return rc;
-            if (h->onepass && h->V && (rc = transpose_odd_slices(h))) return rc;
-        } else {
-            LineArgs k = col_args(h, TR, TR, n_slices, c.ny, c.ny);
-            k.fft1 = -1;
-            k.scale = vscale;
-            k.store_mode = STORE_POTENTIAL; k.out_real = h->V; k.sigma = (float)c.sigma;
-            if ((rc = launch_lines(h, h->plan_x, k, K_OTHER))) return rc;
-            const int saved = h->cur_batch;                         // one-pass loop on such a grid: x-pass slices transposed, stack by stack
-            for (int f = 0; f < g && rc == MSL_OK; ++f) { h->cur_batch = slot + f; rc = transpose_odd_slices(h); }
-            h->cur_batch = saved;
-            if (rc) return rc;
-        }
-    }
-    h->n_species = nsp;
-    if (timed) {
-        HIPCHK(h, hipEventRecord(e1, h->stream));
-        HIPCHK(h, hipEventSynchronize(e1));
-        float ms = 0.f;
-        HIPCHK(h, hipEventElapsedTime(&ms, e0, e1));
-        h->ctr.ms_potential += ms;
-    }
-    h->have_potential = true;
-    return MSL_OK;
-}
-
 static int check_potential_args(msl_handle* h, const char* who, const double* pos, const int32_t* Z, int64_t n, int32_t ax1, int32_t ax2, int32_t axs) {
     if (!h || (n > 0 && (!pos || !Z))) return fail(h, MSL_ERR_INVALID, "%s: null argument", who);
     if (!h->have_kirkland) return fail(h, MSL_ERR_STATE, "%s: call msl_set_kirkland first", who);
@@ -2074,17 +2086,10 @@ static int run_loop(msl_handle* h, int slot, int groups = 1) {
     if (!h->have_potential) return fail(h, MSL_ERR_STATE, "propagate: no potential (msl_build_potential / msl_upload_potential)");
     HIPCHK(h, hipSetDevice(h->cfg.device));
     if (!h->cfg.launch_timing) return slice_loop(h, slot, groups, first_group);         // queued; msl_synchronize / msl_download wait for it
-    EventPair evp_; hipEvent_t &e0 = evp_.a, &e1 = evp_.b;
-    HIPCHK(h, hipEventCreate(&e0)); HIPCHK(h, hipEventCreate(&e1));
-    HIPCHK(h, hipEventRecord(e0, h->stream));
-    int rc = slice_loop(h, slot, groups, first_group);
-    if (rc) return rc;
-    HIPCHK(h, hipEventRecord(e1, h->stream));
-    HIPCHK(h, hipEventSynchronize(e1));
-    float ms = 0.f;
-    HIPCHK(h, hipEventElapsedTime(&ms, e0, e1));
-    h->ctr.ms_propagate += ms;
-    return MSL_OK;
+    EventPair timer;
+    int rc;
+    if ((rc = timer.begin(h)) || (rc = slice_loop(h, slot, groups, first_group))) return rc;
+    return timer.end(h, &h->ctr.ms_propagate);
 }
 
 int msl_propagate(msl_handle* h) {
@@ -2171,9 +2176,8 @@ int msl_tacaw(msl_handle* h, const void* d_src, void* d_dst, int64_t batch, int3
     } else if ((rc = make_plan(h, h->plan_t, T))) {
         return rc;
     }
-    EventPair evp_; hipEvent_t &e0 = evp_.a, &e1 = evp_.b;
-    HIPCHK(h, hipEventCreate(&e0)); HIPCHK(h, hipEventCreate(&e1));
-    HIPCHK(h, hipEventRecord(e0, h->stream));
+    EventPair timer;
+    if ((rc = timer.begin(h))) return rc;
     h->cur = nullptr;
     if (fast_t) {
         // time lines are "columns" of a (T, npix) image per probe: 16 neighbouring pixels per tile
@@ -2209,10 +2213,7 @@ int msl_tacaw(msl_handle* h, const void* d_src, void* d_dst, int64_t batch, int3
             const long long tiles = ((npix + COLS - 1) / COLS) * batch;
             const int per_cu = std::max(1, std::min(2, (int)((size_t)h->lds_limit / lds)));
             const int grid = (int)std::min<long long>(tiles, (long long)h->n_cus * per_cu);
-            (void)hipFuncSetAttribute((const void*)time_cz_kernel<R, COLS, VEC>, hipFuncAttributeMaxDynamicSharedMemorySize, h->lds_limit);
-            hipLaunchKernelGGL((time_cz_kernel<R, COLS, VEC>), dim3(grid), dim3(COLS * R), lds, h->stream, j);
-            HIPCHK(h, hipGetLastError());
-            return mark_launch(h, K_OTHER);
+            return launch_lds(h, time_cz_kernel<R, COLS, VEC>, dim3(grid), dim3(COLS * R), lds, K_OTHER, j);
         };
         using I16 = std::integral_constant<int, 16>; using I32 = std::integral_constant<int, 32>;
         const bool even = (npix % 2 == 0);
@@ -2227,13 +2228,9 @@ int msl_tacaw(msl_handle* h, const void* d_src, void* d_dst, int64_t batch, int3
         a.contiguous_lines = 1; a.fft1 = +1; a.store_mode = STORE_INTENSITY; a.shift_n = T / 2;
         if ((rc = launch_lines(h, h->plan_t, a, K_OTHER))) return rc;
     }
-    HIPCHK(h, hipEventRecord(e1, h->stream));
-    HIPCHK(h, hipEventSynchronize(e1));
-    float ms = 0.f;
-    HIPCHK(h, hipEventElapsedTime(&ms, e0, e1));
-    h->ctr.ms_tacaw += ms;
+    rc = timer.end(h, &h->ctr.ms_tacaw);
     if (tw4_t) (void)hipFree(tw4_t);
-    return MSL_OK;
+    return rc;
 }
 
 static int ensure_scratch(msl_handle* h, size_t bytes);
