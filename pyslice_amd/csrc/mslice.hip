@@ -30,14 +30,41 @@ namespace {
 
 thread_local std::string g_create_error;
 
+int fail(msl_handle* h, int code, const char* fmt, ...);
+
+// Device memory of n elements of T with one owner: freed by the destructor, moved but never copied.  Reads as a T* wherever a
+// pointer is wanted (arithmetic, job structs, kernel arguments).  Every device allocation of this file is a DevBuf.
+template <typename T>
+struct DevBuf {
+    T* p = nullptr;
+    size_t n = 0;
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept : p(o.p), n(o.n) { o.p = nullptr; o.n = 0; }
+    DevBuf& operator=(DevBuf&& o) noexcept { std::swap(p, o.p); std::swap(n, o.n); return *this; }
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { release(); }
+    operator T*() const { return p; }
+    void release() { if (p) (void)hipFree(p); p = nullptr; n = 0; }
+    // free, then allocate exactly `count` elements (0: stays empty); on failure the buffer is empty and the handle's error is set
+    int alloc(msl_handle* h, size_t count) {
+        release();
+        if (count == 0) return MSL_OK;
+        hipError_t e = hipMalloc((void**)&p, count * sizeof(T));
+        if (e != hipSuccess) { p = nullptr; return fail(h, MSL_ERR_NOMEM, "hipMalloc(%zu bytes) failed: %s", count * sizeof(T), hipGetErrorString(e)); }
+        n = count;
+        return MSL_OK;
+    }
+    int reserve(msl_handle* h, size_t count) { return count <= n ? MSL_OK : alloc(h, count); }     // grow only
+};
+
 struct FftPlan {
     int M = 0;                  // length the Stockham stages run on (N, or a power of two >= 2N-1: Bluestein)
-    float2* chirp = nullptr;
-    float2* bfilt = nullptr;
+    DevBuf<float2> chirp, bfilt;
     int N = 0;
     int n_stages = 0;
     int radix[MSL_MAX_STAGES] = {0};
-    float2* tw = nullptr;       // device twiddles
+    DevBuf<float2> tw;          // device twiddles
     bool ok = false;
 };
 
@@ -64,7 +91,7 @@ enum PotIfft { PI_LINES, PI_TWO, PI_CHIRPZ, PI_WAVE2K };
 // Chirp-z tables of n points on a register FFT of length M: R = 16 / 32 (M = R^2, tw = make_tw4's table) or 64 (the wave-per-line
 // 2048-point FFT: tw = T[k1*64+n2], tw2 = W_64), chirp bw (M/2 entries) and its filter bf (M/2 + 2), made by make_cz_tables.  The
 // convolution passes of the slice loop, the potential's inverse transform (ifftTB_kernel / ifftTB2_kernel) and time_cz_kernel read them.
-struct CzTables { int R = 0; float2* tw = nullptr; float2* tw2 = nullptr; float2* bf = nullptr; float2* bw = nullptr; };
+struct CzTables { int R = 0; DevBuf<float2> tw, tw2, bf, bw; };
 
 struct EventSet {
     std::vector<hipEvent_t> ev;
@@ -83,8 +110,7 @@ struct msl_handle {
     FftPlan plan_x, plan_y, plan_t;
     // four-step (register-resident) kernels: R = 32 (N=1024) or 16 (N=256); 0 = use the generic kernel
     int Rx = 0, Ry = 0;
-    float2* tw4_x = nullptr;
-    float2* tw4_y = nullptr;
+    DevBuf<float2> tw4_x, tw4_y;
     int n_cus = 256;
     // one-pass-per-slice path (transposing passes): second work buffer in (P, ny, nx+pad) layout, transposed
     // probes and the transposed transmission slices
@@ -94,14 +120,13 @@ struct msl_handle {
                                    // time kernels they are pixels like any other), include/mslice.h: msl_result_pitch
     size_t intensity_ld = 0;       // pixel pitch of the resident intensity buffer: wpitch after msl_tacaw, wpix after a stream
     int bx = 1, by = 1;            // detector binning: stored pixel = sum of bx x by neighbouring pixels of the window
-    float2* bin_stage = nullptr;   // binning: full-resolution window of the frames of one launch sequence, (FB*P, wx, wy)
+    DevBuf<float2> bin_stage;      // binning: full-resolution window of the frames of one launch sequence, (FB*P, wx, wy)
     // streaming TACAW
-    float2* st_acc = nullptr; double2* st_s1 = nullptr; double* st_s2 = nullptr; float2* st_tw = nullptr; int* st_bins = nullptr;
-    float2* st_ref = nullptr; bool st_have_ref = false;      // reference pattern subtracted before folding (msl_tacaw_stream_set_reference)
+    DevBuf<float2> st_acc, st_tw; DevBuf<double2> st_s1; DevBuf<double> st_s2; DevBuf<int> st_bins;
+    DevBuf<float2> st_ref; bool st_have_ref = false;         // reference pattern subtracted before folding (msl_tacaw_stream_set_reference)
     int st_T = 0, st_F = 0; bool st_open = false;
     int64_t intensity_F = 0;       // frequency bins of the resident intensity buffer (T after msl_tacaw, n_bins after a stream)
-    char* scratch = nullptr;       // reductions: partial sums / masks / index lists
-    size_t scratch_bytes = 0;
+    DevBuf<char> scratch;          // reductions: partial sums / masks / index lists (grown on demand)
     bool onepass = false;
     bool scheme_b = false;         // a direction of 2R^2 points: every pass transposes, first pass along y, final transpose if nz is odd
     PotIfft pot_ifft = PI_LINES;   // inverse transform of the potential build, fixed at msl_create
@@ -110,21 +135,20 @@ struct msl_handle {
     // kind, on which the potential's inverse transform, the probes and the exit FFT still run, and the loop is one-pass iff both
     // bases are not AX_NONE.  cz: the chirp-z tables of a CONV / CONV2K base, or of an axis of 33..1024 points next to one (only the
     // potential's inverse transform uses those).  Every table is owned by the OpDir.
-    struct OpDir { AxisKind kind = AX_NONE, base = AX_NONE; int n = 0; int R = 0; float2* mtw = nullptr; float2* tw = nullptr; float2* tw2 = nullptr;
-                   float2* qf = nullptr; float2* bw = nullptr; float2* ptab = nullptr; CzTables cz; } opx, opy;
+    struct OpDir { AxisKind kind = AX_NONE, base = AX_NONE; int n = 0; int R = 0; DevBuf<float2> mtw, tw, tw2, qf, bw, ptab;
+                   CzTables cz; } opx, opy;
     CzTables opt;                  // chirp-z tables of the TACAW time axis, made for opt_T frames (time_cz_kernel)
     int opt_T = 0;
-    float2* tsplit_tw = nullptr;   // W_T^n, n < T: cross-wave butterflies of time_split_kernel, made for tsplit_T frames
+    DevBuf<float2> tsplit_tw;      // W_T^n, n < T: cross-wave butterflies of time_split_kernel, made for tsplit_T frames
     int tsplit_T = 0;
-    float2* psiT = nullptr;
-    float2* psi0T = nullptr;
+    DevBuf<float2> psiT, psi0T;
     bool need_psi0T = false;
     int keys_cap = 0;              // capacity of d_counts / d_start (slice x species bins)
     // pinned host staging for the per-frame inputs (species maps, Z, positions), two slots used alternately: the call
     // copies the caller's arrays here and returns; the H2D copies run on the stream (no pointer into caller memory is kept)
     struct HostStage { char* buf = nullptr; size_t bytes = 0; hipEvent_t ev = nullptr; bool used = false; } stage[2];
     unsigned stage_pos = 0;
-    float2* transT = nullptr;
+    DevBuf<float2> transT;
     int pitchT = 0;
     int debug_flags_mask = -1;
     int row_pchunk = 0;         // 0 = auto (MSL_ROW_PCHUNK, debug)
@@ -134,59 +158,41 @@ struct msl_handle {
     // replicated once per frame of the batch), trans / transT hold FB stacks; cur_batch = stack the next potential goes to.
     int FB = 1, cur_batch = 0;
     // device buffers
-    float2* psi0 = nullptr;
-    float2* psi = nullptr;
-    float2* trans = nullptr;
-    float* V = nullptr;
-    float2* wf = nullptr;
-    float* intensity = nullptr;
-    size_t intensity_elems = 0;
-    float2* pxt = nullptr;      // exp(-i pi lambda dz kx^2)/nx
-    float2* pyt = nullptr;
-    // thickness series (msl_set_layers): result block of every slice (-1: not a layer), the (L, P, T_local, wpitch) result whose last
-    // block is wf, the natural-order image set the layer tap transforms (FB * P images, psi's layout) and the unscaled conjugate
+    DevBuf<float2> psi0, psi, trans;
+    DevBuf<float> V;
+    DevBuf<float> intensity;
+    DevBuf<float2> pxt, pyt;    // exp(-i pi lambda dz kx^2)/nx
+    // the result, (L, P, T_local, wpitch) with L = 1 + the layers of a thickness series (msl_set_layers): `layers` owns it for every
+    // L, wf is a view of its last block, the exit waves.  layer_block: result block of every slice (-1: not a layer); tap: the
+    // natural-order image set the layer tap transforms (FB * P images, psi's layout); tap_cx / tap_cy: the unscaled conjugate
     // propagator factors conj(Px), conj(Py) of the tap
     std::vector<int> layer_block;
     std::vector<int> layer_slices;
-    float2* layers = nullptr;
-    float2* tap = nullptr;
-    float2* tap_cx = nullptr;
-    float2* tap_cy = nullptr;
+    DevBuf<float2> layers;
+    float2* wf = nullptr;
+    DevBuf<float2> tap, tap_cx, tap_cy;
     // STEM detectors (msl_set_detectors): membership bits per stored pixel, the stored k axes, the signal of every detector
-    uint16_t* det_mask = nullptr;
-    float* det_kx = nullptr;
-    float* det_ky = nullptr;
+    DevBuf<uint16_t> det_mask;
+    DevBuf<float> det_kx, det_ky;
     int det_n = 0, det_wy = 0;
     size_t det_K = 0;
     uint32_t det_amp = 0, det_cx = 0, det_cy = 0;
     // diffraction patterns (msl_diffract): (B, mx, my) float64 staging, grown on demand
-    double* diff_out = nullptr;
-    size_t diff_cap = 0;
-    double* d_abcd = nullptr;
-    double* d_lo = nullptr;
-    double* d_hi = nullptr;
+    DevBuf<double> diff_out;
+    DevBuf<double> d_abcd, d_lo, d_hi;
     bool have_kirkland = false, have_slices = false, have_probes = false, have_potential = false, have_exit = false;
     int frames_done = 0;
     // potential scratch (grown on demand)
     size_t atom_cap = 0;
-    double* d_pos = nullptr;
-    int* d_Z = nullptr;
-    int* d_key = nullptr;
-    int* d_order = nullptr;
-    double* d_u1 = nullptr;
-    double* d_u2 = nullptr;
-    float2* d_ex = nullptr;
-    float2* d_ey = nullptr;
-    int* d_counts = nullptr;
-    int* d_start = nullptr;
-    int* d_z2s = nullptr;
-    int* d_species = nullptr;
-    float* d_ff = nullptr;
+    DevBuf<double> d_pos, d_u1, d_u2;
+    DevBuf<int> d_Z, d_key, d_order, d_counts, d_start, d_z2s, d_species;
+    DevBuf<float2> d_ex, d_ey;
+    DevBuf<float> d_ff;
     int ff_species_cap = 0;
     int n_species = 0;
     int ff_species[104] = {0};     // species list the resident form-factor table was computed for (frame-invariant: computed once per run)
     int ff_n = 0;
-    double* d_xy = nullptr;
+    DevBuf<double> d_xy;
     // counters
     msl_counters ctr{};
     double ms_kind[K_NKINDS] = {0, 0, 0};
@@ -219,15 +225,6 @@ const char* dbg_env(const char* name) { return getenv("MSL_DEBUG") ? getenv(name
         if (_e != hipSuccess)                                                                        \
             return fail(h, MSL_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
     } while (0)
-
-template <typename T>
-int dalloc(msl_handle* h, T** p, size_t n) {
-    if (*p) { (void)hipFree(*p); *p = nullptr; }
-    if (n == 0) return MSL_OK;
-    hipError_t e = hipMalloc((void**)p, n * sizeof(T));
-    if (e != hipSuccess) { *p = nullptr; return fail(h, MSL_ERR_NOMEM, "hipMalloc(%zu bytes) failed: %s", n * sizeof(T), hipGetErrorString(e)); }
-    return MSL_OK;
-}
 
 bool factorize(int N, FftPlan& pl) {
     static const int cand[] = {8, 4, 2, 3, 5, 7, 11, 13};
@@ -301,7 +298,7 @@ int make_plan(msl_handle* h, FftPlan& pl, int N) {
         double a = -2.0 * M_PI * (double)j / (double)M;
         tw[j] = make_float2((float)cos(a), (float)sin(a));
     }
-    int rc = dalloc(h, &pl.tw, (size_t)M);
+    int rc = pl.tw.alloc(h, (size_t)M);
     if (rc) return rc;
     HIPCHK(h, hipMemcpyAsync(pl.tw, tw.data(), M * sizeof(float2), hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -311,8 +308,7 @@ int make_plan(msl_handle* h, FftPlan& pl, int N) {
         host_chirp(N, M, chirp, br, bi);
         std::vector<float2> bf(M);
         for (int j = 0; j < M; ++j) bf[j] = make_float2((float)(br[j] / M), (float)(bi[j] / M));
-        if ((rc = dalloc(h, &pl.chirp, (size_t)N))) return rc;
-        if ((rc = dalloc(h, &pl.bfilt, (size_t)M))) return rc;
+        if ((rc = pl.chirp.alloc(h, (size_t)N)) || (rc = pl.bfilt.alloc(h, (size_t)M))) return rc;
         HIPCHK(h, hipMemcpyAsync(pl.chirp, chirp.data(), N * sizeof(float2), hipMemcpyHostToDevice, h->stream));
         HIPCHK(h, hipMemcpyAsync(pl.bfilt, bf.data(), M * sizeof(float2), hipMemcpyHostToDevice, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -578,13 +574,13 @@ int copy_table(msl_handle* h, float2* dst, const std::vector<float2>& v) {
 }
 
 // a host table in a device buffer of its own
-int upload(msl_handle* h, float2** dst, const std::vector<float2>& v) {
-    int rc = dalloc(h, dst, v.size());
-    return rc ? rc : copy_table(h, *dst, v);
+int upload(msl_handle* h, DevBuf<float2>& dst, const std::vector<float2>& v) {
+    int rc = dst.alloc(h, v.size());
+    return rc ? rc : copy_table(h, dst, v);
 }
 
 // twiddles of the four-step R^2-point FFT: t[k1*R + n2] = W_{R^2}^{k1 n2}
-int make_tw4(msl_handle* h, float2** dst, int R) {
+int make_tw4(msl_handle* h, DevBuf<float2>& dst, int R) {
     const int N = R * R;
     std::vector<float2> t(N);
     for (int k1 = 0; k1 < R; ++k1)
@@ -596,7 +592,7 @@ int make_tw4(msl_handle* h, float2** dst, int R) {
 }
 
 // tables of the wave-per-line 2048-point FFT: T[k1*64+n2] = W_2048^{k1 n2}, and W_64 (even lane of a pair: no twiddle; odd lane: W_64^m)
-int make_wave2k_tables(msl_handle* h, float2** tw, float2** tw2) {
+int make_wave2k_tables(msl_handle* h, DevBuf<float2>& tw, DevBuf<float2>& tw2) {
     constexpr int M = 2048;
     std::vector<float2> T(M), W(64);
     for (int k1 = 0; k1 < 32; ++k1)
@@ -617,13 +613,13 @@ int make_wave2k_tables(msl_handle* h, float2** tw, float2** tw2) {
 int make_cz_tables(msl_handle* h, CzTables& o, int n) {
     const bool wave = n > 512;
     const int R = wave ? 32 : (n <= 128 ? 16 : 32), M = wave ? 2048 : R * R, NH = M / 2;
-    int r = wave ? make_wave2k_tables(h, &o.tw, &o.tw2) : make_tw4(h, &o.tw, R);
+    int r = wave ? make_wave2k_tables(h, o.tw, o.tw2) : make_tw4(h, o.tw, R);
     if (r) return r;
     std::vector<float2> bw(NH, make_float2(0.f, 0.f)), bf(NH + 2, make_float2(0.f, 0.f));
     std::vector<double> cr, ci;
     host_chirp(n, M, bw, cr, ci);
     for (int j = 0; j <= NH; ++j) bf[j] = make_float2((float)(cr[j] / M), (float)(ci[j] / M));
-    if ((r = upload(h, &o.bw, bw)) || (r = upload(h, &o.bf, bf))) return r;
+    if ((r = upload(h, o.bw, bw)) || (r = upload(h, o.bf, bf))) return r;
     o.R = wave ? 64 : R;
     return MSL_OK;
 }
@@ -839,8 +835,8 @@ inline bool slice_is_transposed(const msl_handle* h, int s) {
     return h->scheme_b ? ((s & 1) != 0) : (((h->cfg.nz - 1 - s) & 1) != 0);
 }
 
-// natural t (nz,nx,ny) -> transposed copies of the odd-distance slices in transT (upload / set_beam paths)
-int transpose_odd_slices(msl_handle* h) {
+// natural t (nz,nx,ny) of the stack in batch slot `slot` -> transposed copies of the odd-distance slices in transT (upload / set_beam paths)
+int transpose_odd_slices(msl_handle* h, int slot) {
     if (!h->onepass) return MSL_OK;
     const msl_config& c = h->cfg;
     const size_t npix = (size_t)c.nx * c.ny;
@@ -850,7 +846,7 @@ int transpose_odd_slices(msl_handle* h) {
     for (int z0 = 0; z0 < count; z0 += 65535) {
         const int nzb = std::min(65535, count - z0);
         dim3 grid((c.ny + 31) / 32, (c.nx + 31) / 32, nzb);
-        const size_t off = (size_t)h->cur_batch * c.nz * npix + (size_t)(first + 2 * z0) * npix;
+        const size_t off = (size_t)slot * c.nz * npix + (size_t)(first + 2 * z0) * npix;
         hipLaunchKernelGGL(transpose_kernel, grid, dim3(256), 0, h->stream, h->trans + off, h->transT + off, c.nx, c.ny,
                            c.ny, c.nx, (long long)(2 * npix), (long long)(2 * npix));
     }
@@ -1135,15 +1131,10 @@ int ensure_atoms(msl_handle* h, size_t n, size_t rows) {
     (void)n;
     size_t cap = std::max<size_t>(rows, h->atom_cap * 3 / 2 + 1024);
     int rc;
-    if ((rc = dalloc(h, &h->d_pos, cap * 3))) return rc;
-    if ((rc = dalloc(h, &h->d_Z, cap))) return rc;
-    if ((rc = dalloc(h, &h->d_key, cap))) return rc;
-    if ((rc = dalloc(h, &h->d_order, cap))) return rc;
-    if ((rc = dalloc(h, &h->d_u1, cap))) return rc;
-    if ((rc = dalloc(h, &h->d_u2, cap))) return rc;
+    if ((rc = h->d_pos.alloc(h, cap * 3)) || (rc = h->d_Z.alloc(h, cap)) || (rc = h->d_key.alloc(h, cap)) || (rc = h->d_order.alloc(h, cap)) ||
+        (rc = h->d_u1.alloc(h, cap)) || (rc = h->d_u2.alloc(h, cap))) return rc;
     // phase tables: the quadrant kernel reads the columns 0 .. n/2 only
-    if ((rc = dalloc(h, &h->d_ex, cap * (size_t)(h->cfg.nx / 2 + 1)))) return rc;
-    if ((rc = dalloc(h, &h->d_ey, cap * (size_t)(h->cfg.ny / 2 + 1)))) return rc;
+    if ((rc = h->d_ex.alloc(h, cap * (size_t)(h->cfg.nx / 2 + 1))) || (rc = h->d_ey.alloc(h, cap * (size_t)(h->cfg.ny / 2 + 1)))) return rc;
     h->atom_cap = cap;
     return MSL_OK;
 }
@@ -1359,7 +1350,7 @@ int make_axis_tables(msl_handle* h, msl_handle::OpDir& o, const msl_handle::OpDi
                 T[2 * n + m] = make_float2(1.f, 0.f);
                 T[2 * n + mA + m] = make_float2((float)cos(a), (float)sin(a));
             }
-        if ((rc = upload(h, &o.mtw, T))) return rc;
+        if ((rc = upload(h, o.mtw, T))) return rc;
     }
     switch (o.base) {
     case AX_TWO: {
@@ -1368,15 +1359,15 @@ int make_axis_tables(msl_handle* h, msl_handle::OpDir& o, const msl_handle::OpDi
             const double a = -2.0 * M_PI * (double)m / (double)n;
             t[m] = make_float2((float)cos(a), (float)sin(a));
         }
-        if ((rc = make_tw4(h, &o.tw, o.R)) || (rc = upload(h, &o.tw2, t)) || (rc = dalloc(h, &o.ptab, (size_t)n))) return rc;
+        if ((rc = make_tw4(h, o.tw, o.R)) || (rc = upload(h, o.tw2, t)) || (rc = o.ptab.alloc(h, (size_t)n))) return rc;
         break;
     }
     case AX_WAVE2K:
-        if ((rc = make_wave2k_tables(h, &o.tw, &o.tw2))) return rc;
+        if ((rc = make_wave2k_tables(h, o.tw, o.tw2))) return rc;
         break;
     case AX_CONV:
     case AX_CONV2K:
-        if ((rc = make_cz_tables(h, o.cz, n)) || (rc = dalloc(h, &o.qf, conv_filter_entries(o)))) return rc;
+        if ((rc = make_cz_tables(h, o.cz, n)) || (rc = o.qf.alloc(h, conv_filter_entries(o)))) return rc;
         break;
     case AX_CONV4K: {
         std::vector<float2> wq(2048);
@@ -1384,7 +1375,7 @@ int make_axis_tables(msl_handle* h, msl_handle::OpDir& o, const msl_handle::OpDi
             const double a = -2.0 * M_PI * (double)i / 4096.0;
             wq[i] = make_float2((float)cos(a), (float)sin(a));
         }
-        if ((rc = make_wave2k_tables(h, &o.tw, &o.tw2)) || (rc = upload(h, &o.bw, wq)) || (rc = dalloc(h, &o.qf, conv_filter_entries(o)))) return rc;
+        if ((rc = make_wave2k_tables(h, o.tw, o.tw2)) || (rc = upload(h, o.bw, wq)) || (rc = o.qf.alloc(h, conv_filter_entries(o)))) return rc;
         break;
     }
     default:
@@ -1642,15 +1633,13 @@ int ifft_inplace(msl_handle* h, const PotGroup& p) {
         // (a kept V is written by the untransposed store only: with keep_potential the x-pass slices are transposed afterwards)
         if (h->onepass && !h->V) { k.flags |= COL_TPOT; k.tparity = h->scheme_b ? 0 : ((c.nz - 1) & 1); k.out_t = p.TRT; }
         if ((rc = p.half_rows ? launch_col_herm(h, k, K_OTHER) : launch_col_fast(h, k, K_OTHER))) return rc;
-        return (h->onepass && h->V) ? transpose_odd_slices(h) : MSL_OK;
+        return (h->onepass && h->V) ? transpose_odd_slices(h, p.slot) : MSL_OK;
     }
     LineArgs k = col_args(h, p.TR, p.TR, p.n_slices, c.ny, c.ny);
     k.fft1 = -1; k.scale = p.vscale;
     k.store_mode = STORE_POTENTIAL; k.out_real = h->V; k.sigma = (float)c.sigma;
     if ((rc = launch_lines(h, h->plan_x, k, K_OTHER))) return rc;
-    const int saved = h->cur_batch;                         // one-pass loop on such a grid: x-pass slices transposed, stack by stack
-    for (int f = 0; f < p.g && rc == MSL_OK; ++f) { h->cur_batch = p.slot + f; rc = transpose_odd_slices(h); }
-    h->cur_batch = saved;
+    for (int f = 0; f < p.g && rc == MSL_OK; ++f) rc = transpose_odd_slices(h, p.slot + f);     // one-pass loop on such a grid: x-pass slices transposed, stack by stack
     return rc;
 }
 
@@ -1683,7 +1672,7 @@ int build_potentials(msl_handle* h, const double* pos, const int32_t* Z, int64_t
     EventPair timer;
     if (c.launch_timing && (rc = timer.begin(h))) return rc;
     if (p.nsp > h->ff_species_cap) {
-        if ((rc = dalloc(h, &h->d_ff, npix * p.nsp))) return rc;
+        if ((rc = h->d_ff.alloc(h, npix * p.nsp))) return rc;
         h->ff_species_cap = p.nsp;
         h->ff_n = 0;
     }
@@ -1697,8 +1686,7 @@ int build_potentials(msl_handle* h, const double* pos, const int32_t* Z, int64_t
     const int G = (int)std::max<size_t>(1, std::min<size_t>((size_t)count, (size_t)6e9 / table_bytes_per_frame));
     const int nkeys_cap = p.keys_per_frame * G;
     if (nkeys_cap > h->keys_cap) {
-        if ((rc = dalloc(h, &h->d_counts, (size_t)nkeys_cap + 1))) return rc;
-        if ((rc = dalloc(h, &h->d_start, (size_t)nkeys_cap + 1))) return rc;
+        if ((rc = h->d_counts.alloc(h, (size_t)nkeys_cap + 1)) || (rc = h->d_start.alloc(h, (size_t)nkeys_cap + 1))) return rc;
         h->keys_cap = nkeys_cap;
     }
     if ((rc = ensure_atoms(h, (size_t)n * G, (size_t)n * G + (size_t)(SF_ALIGN - 1) * nkeys_cap))) return rc;
@@ -1724,28 +1712,150 @@ int build_potentials(msl_handle* h, const double* pos, const int32_t* Z, int64_t
 
 }  // namespace
 
-// The per-lane / wave-split time kernels (70 instantiations) are compiled in translation units of their own (tacaw_direct.hip,
+// ---- TACAW time transform -----------------------------------------------------
+// The kernel that transforms T frames of images of npix pixels along time (plan_time), in the order of precedence:
+//   TK_FOURSTEP  1024 frames of images beyond the wave-split kernel's 32-bit offsets: the four-step column kernel, R = 32 (it served
+//                256 and 1024 frames until the split kernel overtook it: T = 256, 64 probes x 1024^2 40.2 -> 39.7 ms, 16 x 2048^2
+//                44.7 -> 40.7 ms; T = 1024, 8 x 1024^2 33.7 -> 29.3 ms)
+//   TK_DIRECT    smooth counts from 16 to 128 (100 = 4.5.5 ...): a lane per pixel, the whole time line in its registers (time_direct_kernel)
+//   TK_SPLIT     smooth counts up to 1024: the register network split over the waves of a workgroup (time_split_kernel; tsplit_tw)
+//   TK_CHIRPZ    any other count up to 512: chirp-z on the register FFTs (time_cz_kernel; the tables `opt`)
+//   TK_GENERIC   the generic LDS kernel (plan_t)
+// The per-lane / wave-split kernels (70 instantiations) are compiled in translation units of their own (tacaw_direct.hip,
 // tacaw_split.hip, tacaw_split2.hip: built in parallel with this file); tacaw_launch.h declares their launchers.
-static int launch_time_direct(msl_handle* h, const TimeJob& j) {
-    if (!time_direct_launch(j, h->n_cus, h->stream)) return fail(h, MSL_ERR_UNSUPPORTED, "no per-lane time kernel for %d frames", j.T);
-    HIPCHK(h, hipGetLastError());
-    return mark_launch(h, K_OTHER);
+enum TimeKind { TK_FOURSTEP, TK_DIRECT, TK_SPLIT, TK_CHIRPZ, TK_GENERIC };
+
+static TimeKind plan_time(const msl_handle* h, int T, int64_t npix) {
+    if (h->cfg.fft_path != 0 || dbg_env("MSL_TACAW_GENERIC")) return TK_GENERIC;
+    const bool regs = !dbg_env("MSL_TACAW_CHIRPZ");                  // the per-lane and the wave-split register kernels
+    // 32-bit offsets: the buffer unit adds the lane offset and the scalar row offset in 32 bits (measured: the sum wraps) --
+    // pixel + up to 64 rows with one block per wave, pixel + TP + (TP + 1) / 2 rows with two; time_split_launch falls back from the
+    // two-block shape to the one-block shape of the same L where there is one (L = 2, 4: up to 512 frames)
+    const bool split = regs && time_split_fits(T, npix) && !(T == 1024 && dbg_env("MSL_TACAW_FOURSTEP"));
+    if (T == 1024 && !split && npix % 16 == 0 && npix >= 32) return TK_FOURSTEP;
+    if (regs && time_direct_has(T) && (unsigned long long)((T + 1) / 2) * (unsigned long long)npix * 8ull < (1ull << 32)) return TK_DIRECT;
+    if (split) return TK_SPLIT;
+    return T <= 512 ? TK_CHIRPZ : TK_GENERIC;
 }
-static int launch_time_split(msl_handle* h, TimeJob j) {
+
+// W_T^n, n < T, for the cross-wave butterflies of time_split_kernel (the cache is invalid while it is rebuilt)
+static int make_tsplit_table(msl_handle* h, int T) {
+    if (h->tsplit_T == T) return MSL_OK;
+    h->tsplit_T = 0;
+    std::vector<float2> w(T);
+    for (int n = 0; n < T; ++n) { const double a = -2.0 * M_PI * (double)n / (double)T; w[n] = make_float2((float)cos(a), (float)sin(a)); }
+    int rc = h->tsplit_tw.alloc(h, (size_t)T);
+    if (rc) return rc;
+    HIPCHK(h, hipMemcpy(h->tsplit_tw, w.data(), (size_t)T * sizeof(float2), hipMemcpyHostToDevice));
+    h->tsplit_T = T;
+    return MSL_OK;
+}
+
+static int launch_time_cz(msl_handle* h, const TimeJob& j) {
     const int T = j.T;
-    if (h->tsplit_T != T) {
-        h->tsplit_T = 0;
-        std::vector<float2> w(T);
-        for (int n = 0; n < T; ++n) { const double a = -2.0 * M_PI * (double)n / (double)T; w[n] = make_float2((float)cos(a), (float)sin(a)); }
-        int rc = dalloc(h, &h->tsplit_tw, (size_t)T);
-        if (rc) return rc;
-        HIPCHK(h, hipMemcpy(h->tsplit_tw, w.data(), (size_t)T * sizeof(float2), hipMemcpyHostToDevice));
-        h->tsplit_T = T;
+    const long long npix = j.npix, batch = j.n_images;
+    auto launch = [&](auto r_c, auto cols_c, auto vec_c) -> int {
+        constexpr int R = decltype(r_c)::value, COLS = decltype(cols_c)::value;
+        constexpr bool VEC = decltype(vec_c)::value;
+        constexpr int M = R * R, NH = M / 2;
+        const size_t lds = ((size_t)M + NH + 2 + NH + (size_t)2 * COLS * tcz_stride(R, T)) * 8;          // two tile buffers
+        const long long tiles = ((npix + COLS - 1) / COLS) * batch;
+        const int per_cu = std::max(1, std::min(2, (int)((size_t)h->lds_limit / lds)));
+        const int grid = (int)std::min<long long>(tiles, (long long)h->n_cus * per_cu);
+        return launch_lds(h, time_cz_kernel<R, COLS, VEC>, dim3(grid), dim3(COLS * R), lds, K_OTHER, j);
+    };
+    using I16 = std::integral_constant<int, 16>; using I32 = std::integral_constant<int, 32>;
+    const bool even = (npix % 2 == 0);
+    if (h->opt.R == 16) return even ? launch(I16{}, I32{}, std::true_type{}) : launch(I16{}, I32{}, std::false_type{});
+    return even ? launch(I32{}, I16{}, std::true_type{}) : launch(I32{}, I16{}, std::false_type{});
+}
+
+// |FFT_t|^2 of `batch` (T, npix) blocks of complex spectra src -> dst (float32), DC removed and fftshifted (msl_tacaw)
+static int tacaw_run(msl_handle* h, const float2* src, float* dst, int64_t batch, int32_t T, int64_t npix) {
+    if (T < 2) return fail(h, MSL_ERR_INVALID, "msl_tacaw: needs at least 2 frames (got %d)", T);
+    if (batch < 1 || npix < 1) return fail(h, MSL_ERR_INVALID, "msl_tacaw: bad batch/npix");
+    if (npix > 0x7fffffffLL) return fail(h, MSL_ERR_UNSUPPORTED, "msl_tacaw: npix too large");
+    const TimeKind kind = plan_time(h, T, npix);
+    int rc = MSL_OK;
+    DevBuf<float2> tw4_t;
+    switch (kind) {
+    case TK_FOURSTEP: rc = make_tw4(h, tw4_t, 32); break;
+    case TK_DIRECT:   break;
+    case TK_SPLIT:    rc = make_tsplit_table(h, T); break;
+    case TK_CHIRPZ:
+        if (h->opt_T != T) {
+            h->opt_T = 0;
+            if ((rc = make_cz_tables(h, h->opt, T))) return rc;                   // (M = 256 below 33 frames as well)
+            h->opt_T = T;
+        }
+        break;
+    case TK_GENERIC:  rc = make_plan(h, h->plan_t, T); break;
     }
-    j.tw = h->tsplit_tw;
-    if (!time_split_launch(j, h->n_cus, (size_t)h->lds_limit, h->stream)) return fail(h, MSL_ERR_UNSUPPORTED, "no wave-split time kernel for %d frames", T);
-    HIPCHK(h, hipGetLastError());
-    return mark_launch(h, K_OTHER);
+    if (rc) return rc;
+    TimeJob j{};
+    j.in = src; j.out = dst;
+    j.image_stride = (long long)T * npix; j.npix = (int)npix; j.n_images = (int)batch; j.T = T;
+    EventPair timer;
+    if ((rc = timer.begin(h))) return rc;
+    h->cur = nullptr;
+    switch (kind) {
+    case TK_FOURSTEP: {
+        // time lines are "columns" of a (T, npix) image per probe: 16 neighbouring pixels per tile
+        ColJob c{};
+        c.in = src; c.out = nullptr; c.px = nullptr; c.tw = tw4_t; c.out_real = dst;
+        c.in_image_stride = c.out_image_stride = j.image_stride;
+        c.in_pitch = c.out_pitch = (int)npix; c.ny = (int)npix; c.n_images = (int)batch;
+        c.flags = COL_FWD | COL_INTENSITY; c.scale = 1.f;
+        rc = launch_col_fast_r<32>(h, c, K_OTHER);
+        break;
+    }
+    case TK_DIRECT:
+        if (!time_direct_launch(j, h->n_cus, h->stream)) return fail(h, MSL_ERR_UNSUPPORTED, "no per-lane time kernel for %d frames", T);
+        HIPCHK(h, hipGetLastError());
+        rc = mark_launch(h, K_OTHER);
+        break;
+    case TK_SPLIT:
+        j.tw = h->tsplit_tw;
+        if (!time_split_launch(j, h->n_cus, (size_t)h->lds_limit, h->stream)) return fail(h, MSL_ERR_UNSUPPORTED, "no wave-split time kernel for %d frames", T);
+        HIPCHK(h, hipGetLastError());
+        rc = mark_launch(h, K_OTHER);
+        break;
+    case TK_CHIRPZ:
+        j.tw = h->opt.tw; j.bf = h->opt.bf; j.bw = h->opt.bw;
+        rc = launch_time_cz(h, j);
+        break;
+    case TK_GENERIC: {
+        LineArgs a;
+        a.in = src; a.out = nullptr; a.out_real = dst;
+        a.n_lines = (long long)batch * npix; a.lines_per_image = (int)npix;
+        a.in_es = a.out_es = npix; a.in_ls = a.out_ls = 1; a.in_is = a.out_is = j.image_stride;
+        a.contiguous_lines = 1; a.fft1 = +1; a.store_mode = STORE_INTENSITY; a.shift_n = T / 2;
+        rc = launch_lines(h, h->plan_t, a, K_OTHER);
+        break;
+    }
+    }
+    return rc ? rc : timer.end(h, &h->ctr.ms_tacaw);
+}
+
+// msl_tacaw on one (P, T, wpitch) block of the resident result, into the handle's intensity buffer
+static int tacaw_resident(msl_handle* h, const float2* block) {
+    const msl_config& c = h->cfg;
+    // the pad pixels of an image are pixels like any other here (zeros in, zeros out)
+    const size_t need = (size_t)c.n_probes * c.n_frames * h->wpitch;
+    int rc;
+    if (h->intensity.n != need && (rc = h->intensity.alloc(h, need))) return rc;
+    h->intensity_F = c.n_frames; h->intensity_ld = h->wpitch;
+    return tacaw_run(h, block, h->intensity, c.n_probes, c.n_frames, (int64_t)h->wpitch);
+}
+
+// The work buffers sized by the probe count (FB frames of n_probes images each; pitch, pitchT, onepass and need_psi0T are set)
+static int alloc_probe_buffers(msl_handle* h, int n_probes) {
+    const msl_config& c = h->cfg;
+    const size_t images = (size_t)n_probes * h->FB, elems = (size_t)c.nx * h->pitch * images, elemsT = (size_t)c.ny * h->pitchT * images;
+    int rc;
+    if ((rc = h->psi0.alloc(h, elems)) || (rc = h->psi.alloc(h, elems))) return rc;
+    if (h->onepass && ((rc = h->psiT.alloc(h, elemsT)) || (h->need_psi0T && (rc = h->psi0T.alloc(h, elemsT))))) return rc;
+    return h->d_xy.alloc(h, (size_t)2 * n_probes);
 }
 
 extern "C" {
@@ -1819,8 +1929,8 @@ int msl_create(const msl_config* cfg, msl_handle** out) {
     if (cfg->fft_path == 0) {
         // row kernel: rows of length ny, 256/R rows per workgroup;  column kernel: columns of length nx, 16 per tile
         int ry = fast_radix(cfg->ny), rx = fast_radix(cfg->nx);
-        if (ry && cfg->nx % (256 / ry) == 0) { h->Ry = ry; if ((rc = make_tw4(h, &h->tw4_y, ry))) return bail(rc); }
-        if (rx && cfg->ny % 16 == 0 && cfg->ny >= 32) { h->Rx = rx; if ((rc = make_tw4(h, &h->tw4_x, rx))) return bail(rc); }
+        if (ry && cfg->nx % (256 / ry) == 0) { h->Ry = ry; if ((rc = make_tw4(h, h->tw4_y, ry))) return bail(rc); }
+        if (rx && cfg->ny % 16 == 0 && cfg->ny >= 32) { h->Rx = rx; if ((rc = make_tw4(h, h->tw4_x, rx))) return bail(rc); }
         { const char* e = dbg_env("MSL_ROW_PCHUNK"); if (e) h->row_pchunk = atoi(e); }
         allow_lds(h, row_pass_pf_kernel<32>);
         allow_lds(h, row_pass_pf_kernel<16>);
@@ -1844,42 +1954,34 @@ int msl_create(const msl_config* cfg, msl_handle** out) {
         h->scheme_b = h->onepass && !(h->opx.kind == AX_FOURSTEP && h->opy.kind == AX_FOURSTEP);
         if (h->pitch == cfg->ny && h->onepass) h->pitch = cfg->ny + 16;        // pad the work buffers of 2R^2 grids too
         if (h->onepass && (h->pitch & 1)) ++h->pitch;                          // even pitches: the transposed stores write two lines (16 bytes) at a time
-        const size_t images = (size_t)cfg->n_probes * h->FB;
-        if ((rc = dalloc(h, &h->psi0, (size_t)cfg->nx * h->pitch * images))) return bail(rc);
-        if ((rc = dalloc(h, &h->psi, (size_t)cfg->nx * h->pitch * images))) return bail(rc);
         if (h->onepass) {
             h->pitchT = cfg->nx + 16 + (cfg->nx & 1);
             if (h->pitch - cfg->ny > 16 && !(cfg->nx & 1)) h->pitchT = cfg->nx + (h->pitch - cfg->ny);
-            if ((rc = dalloc(h, &h->psiT, (size_t)cfg->ny * h->pitchT * images))) return bail(rc);
             // transposed probes: only when the first pass runs along x (alternating scheme with an even slice count)
             h->need_psi0T = !h->scheme_b && (cfg->nz % 2 == 0);
-            if (h->need_psi0T && (rc = dalloc(h, &h->psi0T, (size_t)cfg->ny * h->pitchT * images))) return bail(rc);
-            if ((rc = dalloc(h, &h->transT, npix * cfg->nz * h->FB))) return bail(rc);
+        }
+        if ((rc = alloc_probe_buffers(h, cfg->n_probes))) return bail(rc);
+        if (h->onepass) {
+            if ((rc = h->transT.alloc(h, npix * cfg->nz * h->FB))) return bail(rc);
             { const char* ev = dbg_env("MSL_DEBUG_FLAGS_MASK"); if (ev) h->debug_flags_mask = atoi(ev); }
             allow_lds(h, row_pass2_kernel<32>);
             allow_lds(h, row_pass2_kernel<16>);
         }
     }
-    if ((rc = dalloc(h, &h->trans, npix * cfg->nz * h->FB))) return bail(rc);
-    if (cfg->keep_potential && (rc = dalloc(h, &h->V, npix * cfg->nz))) return bail(rc);
+    if ((rc = h->trans.alloc(h, npix * cfg->nz * h->FB))) return bail(rc);
+    if (cfg->keep_potential && (rc = h->V.alloc(h, npix * cfg->nz))) return bail(rc);
     h->pot_ifft = plan_pot_ifft(h);
     if (cfg->n_frames > 0) {
-        if ((h->bx > 1 || h->by > 1) && (rc = dalloc(h, &h->bin_stage, (size_t)h->wx * h->wy * cfg->n_probes * h->FB))) return bail(rc);
-        if ((rc = dalloc(h, &h->wf, h->wpitch * cfg->n_probes * cfg->n_frames))) return bail(rc);
-        if (hipMemsetAsync(h->wf, 0, h->wpitch * cfg->n_probes * cfg->n_frames * sizeof(float2), h->stream) != hipSuccess)
+        if ((h->bx > 1 || h->by > 1) && (rc = h->bin_stage.alloc(h, (size_t)h->wx * h->wy * cfg->n_probes * h->FB))) return bail(rc);
+        if ((rc = h->layers.alloc(h, layer_block_elems(h)))) return bail(rc);           // a single block: the exit waves
+        h->wf = h->layers;
+        if (hipMemsetAsync(h->wf, 0, layer_block_elems(h) * sizeof(float2), h->stream) != hipSuccess)
             return bail(fail(h, MSL_ERR_HIP, "memset failed"));
     }
-    if ((rc = dalloc(h, &h->pxt, (size_t)cfg->nx))) return bail(rc);
-    if ((rc = dalloc(h, &h->pyt, (size_t)cfg->ny))) return bail(rc);
-    if ((rc = dalloc(h, &h->tap_cx, (size_t)cfg->nx))) return bail(rc);
-    if ((rc = dalloc(h, &h->tap_cy, (size_t)cfg->ny))) return bail(rc);
-    if ((rc = dalloc(h, &h->d_lo, (size_t)cfg->nz))) return bail(rc);
-    if ((rc = dalloc(h, &h->d_hi, (size_t)cfg->nz))) return bail(rc);
-    if ((rc = dalloc(h, &h->d_abcd, (size_t)103 * 12))) return bail(rc);
-    if ((rc = dalloc(h, &h->d_z2s, (size_t)104))) return bail(rc);
-    if ((rc = dalloc(h, &h->d_species, (size_t)104))) return bail(rc);
-    if ((rc = dalloc(h, &h->d_xy, (size_t)2 * cfg->n_probes))) return bail(rc);
-    if ((rc = fill_propagator(h))) return bail(rc);
+    if ((rc = h->pxt.alloc(h, (size_t)cfg->nx)) || (rc = h->pyt.alloc(h, (size_t)cfg->ny)) || (rc = h->tap_cx.alloc(h, (size_t)cfg->nx)) ||
+        (rc = h->tap_cy.alloc(h, (size_t)cfg->ny)) || (rc = h->d_lo.alloc(h, (size_t)cfg->nz)) || (rc = h->d_hi.alloc(h, (size_t)cfg->nz)) ||
+        (rc = h->d_abcd.alloc(h, (size_t)103 * 12)) || (rc = h->d_z2s.alloc(h, (size_t)104)) || (rc = h->d_species.alloc(h, (size_t)104)) ||
+        (rc = fill_propagator(h))) return bail(rc);
     *out = h;
     return MSL_OK;
 }
@@ -1890,19 +1992,9 @@ int msl_destroy(msl_handle* h) {
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     for (auto& s : h->ring) for (auto e : s.ev) (void)hipEventDestroy(e);
     for (auto& st : h->stage) { if (st.ev) (void)hipEventDestroy(st.ev); if (st.buf) (void)hipHostFree(st.buf); }
-    if (h->layers) { (void)hipFree(h->layers); h->layers = nullptr; h->wf = nullptr; }      // (wf is its last block)
-    void* bufs[] = {h->psi0, h->psi, h->trans, h->V, h->wf, h->intensity, h->pxt, h->pyt, h->tap, h->tap_cx, h->tap_cy, h->d_abcd, h->d_lo, h->d_hi,
-                    h->d_pos, h->d_Z, h->d_key, h->d_order, h->d_u1, h->d_u2, h->d_ex, h->d_ey, h->d_counts, h->d_start,
-                    h->d_z2s, h->d_species, h->d_ff, h->d_xy, h->plan_x.tw, h->plan_y.tw, h->plan_t.tw, h->tw4_x, h->tw4_y,
-                    h->scratch, h->psiT, h->psi0T, h->transT, h->bin_stage, h->st_acc, h->st_s1, h->st_s2, h->st_tw, h->st_bins, h->st_ref,
-                    h->opt.tw, h->opt.tw2, h->opt.bf, h->opt.bw, h->tsplit_tw, h->det_mask, h->det_kx, h->det_ky, h->diff_out, h->plan_x.chirp, h->plan_x.bfilt, h->plan_y.chirp, h->plan_y.bfilt, h->plan_t.chirp, h->plan_t.bfilt};
-    for (void* b : bufs) if (b) (void)hipFree(b);
-    for (const msl_handle::OpDir* o : {&h->opx, &h->opy}) {
-        void* tabs[] = {o->mtw, o->tw, o->tw2, o->qf, o->bw, o->ptab, o->cz.tw, o->cz.tw2, o->cz.bf, o->cz.bw};
-        for (void* b : tabs) if (b) (void)hipFree(b);
-    }
-    if (h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;
+    const hipStream_t stream = h->stream;
+    delete h;                                               // the stream is idle: every DevBuf of the handle frees its memory
+    if (stream) (void)hipStreamDestroy(stream);
     return MSL_OK;
 }
 
@@ -1943,7 +2035,7 @@ int msl_set_beam(msl_handle* h, double wavelength, double sigma, double dz) {
         hipLaunchKernelGGL(transmission_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->trans, h->V,
                            (long long)n, (float)sigma);
         HIPCHK(h, hipGetLastError());
-        if ((rc = transpose_odd_slices(h))) return rc;
+        if ((rc = transpose_odd_slices(h, h->cur_batch))) return rc;
         HIPCHK(h, hipStreamSynchronize(h->stream));
     }
     return MSL_OK;
@@ -1956,15 +2048,8 @@ int msl_resize_probes(msl_handle* h, int32_t n_probes) {
     if (n_probes == h->cfg.n_probes) return MSL_OK;
     HIPCHK(h, hipSetDevice(h->cfg.device));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    int rc;
-    const size_t images = (size_t)n_probes * h->FB;
-    if ((rc = dalloc(h, &h->psi0, (size_t)h->cfg.nx * h->pitch * images))) return rc;
-    if ((rc = dalloc(h, &h->psi, (size_t)h->cfg.nx * h->pitch * images))) return rc;
-    if (h->onepass) {
-        if ((rc = dalloc(h, &h->psiT, (size_t)h->cfg.ny * h->pitchT * images))) return rc;
-        if (h->need_psi0T && (rc = dalloc(h, &h->psi0T, (size_t)h->cfg.ny * h->pitchT * images))) return rc;
-    }
-    if ((rc = dalloc(h, &h->d_xy, (size_t)2 * n_probes))) return rc;
+    const int rc = alloc_probe_buffers(h, n_probes);
+    if (rc) return rc;
     h->cfg.n_probes = n_probes;
     h->have_probes = false; h->have_exit = false;
     return MSL_OK;
@@ -1976,8 +2061,8 @@ int msl_shift_probes(msl_handle* h, const float* base, const double* xy, int32_t
     const msl_config& c = h->cfg;
     HIPCHK(h, hipSetDevice(c.device));
     const size_t npix = (size_t)c.nx * c.ny;
-    float2* bk = nullptr;
-    int rc = dalloc(h, &bk, npix);
+    DevBuf<float2> bk;
+    int rc = bk.alloc(h, npix);
     if (rc) return rc;
     HIPCHK(h, hipMemcpyAsync(bk, base, npix * sizeof(float2), hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemcpyAsync(h->d_xy, xy, 2 * sizeof(double) * n_probes, hipMemcpyHostToDevice, h->stream));
@@ -1992,7 +2077,6 @@ int msl_shift_probes(msl_handle* h, const float* base, const double* xy, int32_t
     if (rc == MSL_OK) rc = fft2_inplace(h, h->psi0, n_probes, -1, 1.0f / ((float)c.nx * (float)c.ny), h->pitch);
     if (rc == MSL_OK) rc = transpose_probes(h);
     hipError_t e = hipStreamSynchronize(h->stream);
-    (void)hipFree(bk);
     if (rc) return rc;
     if (e != hipSuccess) return fail(h, MSL_ERR_HIP, "msl_shift_probes: %s", hipGetErrorString(e));
     h->have_probes = true;
@@ -2066,22 +2150,20 @@ int msl_upload_potential(msl_handle* h, const float* V) {
     HIPCHK(h, hipSetDevice(c.device));
     const size_t n = (size_t)c.nx * c.ny * c.nz;
     float* dst = h->V;
-    float* tmp = nullptr;
-    if (!dst) { int rc = dalloc(h, &tmp, n); if (rc) return rc; dst = tmp; }
+    DevBuf<float> tmp;
+    if (!dst) { int rc = tmp.alloc(h, n); if (rc) return rc; dst = tmp; }
     HIPCHK(h, hipMemcpyAsync(dst, V, n * sizeof(float), hipMemcpyHostToDevice, h->stream));
     hipLaunchKernelGGL(transmission_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->trans + (size_t)h->cur_batch * n, dst,
                        (long long)n, (float)c.sigma);
     HIPCHK(h, hipGetLastError());
-    { int rc = transpose_odd_slices(h); if (rc) return rc; }
+    { int rc = transpose_odd_slices(h, h->cur_batch); if (rc) return rc; }
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (tmp) (void)hipFree(tmp);
     h->have_potential = true;
     return MSL_OK;
 }
 
-static int run_loop(msl_handle* h, int slot, int groups = 1) {
-    if (!h) return fail(h, MSL_ERR_INVALID, "null handle");
-    const int first_group = groups > 1 ? 0 : h->cur_batch;
+// slice loop of `groups` frames whose transmission stacks start at batch slot `first_group`
+static int run_loop(msl_handle* h, int slot, int groups, int first_group) {
     if (!h->have_probes) return fail(h, MSL_ERR_STATE, "propagate: no probes (msl_set_probes / msl_upload_probes)");
     if (!h->have_potential) return fail(h, MSL_ERR_STATE, "propagate: no potential (msl_build_potential / msl_upload_potential)");
     HIPCHK(h, hipSetDevice(h->cfg.device));
@@ -2093,7 +2175,8 @@ static int run_loop(msl_handle* h, int slot, int groups = 1) {
 }
 
 int msl_propagate(msl_handle* h) {
-    int rc = run_loop(h, -1);
+    if (!h) return fail(h, MSL_ERR_INVALID, "null handle");
+    int rc = run_loop(h, -1, 1, h->cur_batch);
     if (rc == MSL_OK) h->have_exit = true;
     return rc;
 }
@@ -2102,7 +2185,7 @@ int msl_propagate_frame(msl_handle* h, int32_t slot) {
     if (!h) return fail(h, MSL_ERR_INVALID, "null handle");
     if (!h->wf) return fail(h, MSL_ERR_STATE, "msl_propagate_frame: handle created with n_frames == 0");
     if (slot < 0 || slot >= h->cfg.n_frames) return fail(h, MSL_ERR_INVALID, "msl_propagate_frame: slot %d out of range [0,%d)", slot, h->cfg.n_frames);
-    return run_loop(h, slot);
+    return run_loop(h, slot, 1, h->cur_batch);
 }
 
 int msl_select_batch_slot(msl_handle* h, int32_t b) {
@@ -2120,120 +2203,19 @@ int msl_propagate_frames(msl_handle* h, int32_t first_slot, int32_t count) {
     if (count < 1 || count > h->FB) return fail(h, MSL_ERR_INVALID, "msl_propagate_frames: count %d outside [1,%d] (msl_config.frame_batch)", count, h->FB);
     if (first_slot < 0 || first_slot + count > h->cfg.n_frames)
         return fail(h, MSL_ERR_INVALID, "msl_propagate_frames: slots [%d,%d) outside [0,%d)", first_slot, first_slot + count, h->cfg.n_frames);
-    if (count == 1) { const int saved = h->cur_batch; h->cur_batch = 0; int rc = run_loop(h, first_slot, 1); h->cur_batch = saved; return rc; }
-    return run_loop(h, first_slot, count);
+    return run_loop(h, first_slot, count, 0);
 }
 
 int msl_tacaw(msl_handle* h, const void* d_src, void* d_dst, int64_t batch, int32_t T, int64_t npix) {
     if (!h) return fail(h, MSL_ERR_INVALID, "null handle");
-    const msl_config& c = h->cfg;
-    HIPCHK(h, hipSetDevice(c.device));
-    const float2* src = (const float2*)d_src;
-    float* dst = (float*)d_dst;
-    if (!src) {
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    if (!d_src) {
         if (!h->wf) return fail(h, MSL_ERR_STATE, "msl_tacaw: no wavefunction buffer");
-        // the pad pixels of an image are pixels like any other here (zeros in, zeros out)
-        src = h->wf; batch = c.n_probes; T = c.n_frames; npix = (int64_t)h->wpitch;
-        size_t need = (size_t)batch * T * npix;
-        if (h->intensity_elems != need) {
-            int rc = dalloc(h, &h->intensity, need);
-            if (rc) return rc;
-            h->intensity_elems = need;
-        }
-        h->intensity_F = T; h->intensity_ld = h->wpitch;
-        dst = h->intensity;
-    } else if (!dst) {
-        return fail(h, MSL_ERR_INVALID, "msl_tacaw: src given without dst");
+        return tacaw_resident(h, h->wf);
     }
-    if (T < 2) return fail(h, MSL_ERR_INVALID, "msl_tacaw: needs at least 2 frames (got %d)", T);
-    if (batch < 1 || npix < 1) return fail(h, MSL_ERR_INVALID, "msl_tacaw: bad batch/npix");
-    if (npix > 0x7fffffffLL) return fail(h, MSL_ERR_UNSUPPORTED, "msl_tacaw: npix too large");
-    // smooth counts up to 1024: the register network split over the waves of a workgroup (time_split_kernel)
-    // 32-bit offsets: the buffer unit adds the lane offset and the scalar row offset in 32 bits (measured: the sum wraps) --
-    // pixel + up to 64 rows with one block per wave, pixel + TP + (TP + 1) / 2 rows with two; time_split_launch falls back from the
-    // two-block shape to the one-block shape of the same L where there is one (L = 2, 4: up to 512 frames)
-    const bool split_t = c.fft_path == 0 && time_split_fits(T, npix)
-                         && !dbg_env("MSL_TACAW_GENERIC") && !dbg_env("MSL_TACAW_CHIRPZ") && !(T == 1024 && dbg_env("MSL_TACAW_FOURSTEP"));
-    // 1024 frames of images too large for that: the four-step column kernel (it served 256 and 1024 frames until the split kernel
-    // overtook it: T = 256, 64 probes x 1024^2 40.2 -> 39.7 ms, 16 x 2048^2 44.7 -> 40.7 ms; T = 1024, 8 x 1024^2 33.7 -> 29.3 ms)
-    const int Rt = (c.fft_path == 0 && T == 1024 && !split_t) ? fast_radix(T) : 0;
-    const bool fast_t = Rt && (npix % 16 == 0) && npix >= 32 && !dbg_env("MSL_TACAW_GENERIC");
-    // smooth frame counts from 16 to 128 (100 = 4.5.5 ...): a lane per pixel, the whole time line in its registers (time_direct_kernel)
-    const bool direct_t = !fast_t && c.fft_path == 0 && time_direct_has(T) && (unsigned long long)((T + 1) / 2) * (unsigned long long)npix * 8ull < (1ull << 32)
-                          && !dbg_env("MSL_TACAW_GENERIC") && !dbg_env("MSL_TACAW_CHIRPZ");
-    const bool cz_t = !fast_t && !direct_t && !split_t && c.fft_path == 0 && T <= 512 && !dbg_env("MSL_TACAW_GENERIC");
-    int rc = MSL_OK;
-    float2* tw4_t = nullptr;
-    if (fast_t) {
-        if ((rc = make_tw4(h, &tw4_t, Rt))) return rc;
-    } else if (direct_t || split_t) {
-    } else if (cz_t) {
-        if (h->opt_T != T) {
-            h->opt_T = 0;
-            if ((rc = make_cz_tables(h, h->opt, T))) return rc;                   // (M = 256 below 33 frames as well)
-            h->opt_T = T;
-        }
-    } else if ((rc = make_plan(h, h->plan_t, T))) {
-        return rc;
-    }
-    EventPair timer;
-    if ((rc = timer.begin(h))) return rc;
-    h->cur = nullptr;
-    if (fast_t) {
-        // time lines are "columns" of a (T, npix) image per probe: 16 neighbouring pixels per tile
-        ColJob j{};
-        j.in = src; j.out = nullptr; j.px = nullptr; j.tw = tw4_t; j.out_real = dst;
-        j.in_image_stride = j.out_image_stride = (long long)T * npix;
-        j.in_pitch = j.out_pitch = (int)npix; j.ny = (int)npix; j.n_images = (int)batch;
-        j.flags = COL_FWD | COL_INTENSITY; j.scale = 1.f;
-        const int saved = h->Rx;
-        h->Rx = Rt;
-        rc = launch_col_fast(h, j, K_OTHER);
-        h->Rx = saved;
-        if (rc) { (void)hipFree(tw4_t); return rc; }
-    } else if (direct_t) {
-        TimeJob j{};
-        j.in = src; j.out = dst;
-        j.image_stride = (long long)T * npix; j.npix = (int)npix; j.n_images = (int)batch; j.T = T;
-        if ((rc = launch_time_direct(h, j))) return rc;
-    } else if (split_t) {
-        TimeJob j{};
-        j.in = src; j.out = dst;
-        j.image_stride = (long long)T * npix; j.npix = (int)npix; j.n_images = (int)batch; j.T = T;
-        if ((rc = launch_time_split(h, j))) return rc;
-    } else if (cz_t) {
-        TimeJob j{};
-        j.in = src; j.out = dst; j.tw = h->opt.tw; j.bf = h->opt.bf; j.bw = h->opt.bw;
-        j.image_stride = (long long)T * npix; j.npix = (int)npix; j.n_images = (int)batch; j.T = T;
-        auto launch = [&](auto r_c, auto cols_c, auto vec_c) -> int {
-            constexpr int R = decltype(r_c)::value, COLS = decltype(cols_c)::value;
-            constexpr bool VEC = decltype(vec_c)::value;
-            constexpr int M = R * R, NH = M / 2;
-            const size_t lds = ((size_t)M + NH + 2 + NH + (size_t)2 * COLS * tcz_stride(R, T)) * 8;          // two tile buffers
-            const long long tiles = ((npix + COLS - 1) / COLS) * batch;
-            const int per_cu = std::max(1, std::min(2, (int)((size_t)h->lds_limit / lds)));
-            const int grid = (int)std::min<long long>(tiles, (long long)h->n_cus * per_cu);
-            return launch_lds(h, time_cz_kernel<R, COLS, VEC>, dim3(grid), dim3(COLS * R), lds, K_OTHER, j);
-        };
-        using I16 = std::integral_constant<int, 16>; using I32 = std::integral_constant<int, 32>;
-        const bool even = (npix % 2 == 0);
-        if (h->opt.R == 16) rc = even ? launch(I16{}, I32{}, std::true_type{}) : launch(I16{}, I32{}, std::false_type{});
-        else rc = even ? launch(I32{}, I16{}, std::true_type{}) : launch(I32{}, I16{}, std::false_type{});
-        if (rc) return rc;
-    } else {
-        LineArgs a;
-        a.in = src; a.out = nullptr; a.out_real = dst;
-        a.n_lines = (long long)batch * npix; a.lines_per_image = (int)npix;
-        a.in_es = a.out_es = npix; a.in_ls = a.out_ls = 1; a.in_is = a.out_is = (long long)T * npix;
-        a.contiguous_lines = 1; a.fft1 = +1; a.store_mode = STORE_INTENSITY; a.shift_n = T / 2;
-        if ((rc = launch_lines(h, h->plan_t, a, K_OTHER))) return rc;
-    }
-    rc = timer.end(h, &h->ctr.ms_tacaw);
-    if (tw4_t) (void)hipFree(tw4_t);
-    return rc;
+    if (!d_dst) return fail(h, MSL_ERR_INVALID, "msl_tacaw: src given without dst");
+    return tacaw_run(h, (const float2*)d_src, (float*)d_dst, batch, T, npix);
 }
-
-static int ensure_scratch(msl_handle* h, size_t bytes);
 
 int msl_tacaw_stream_begin(msl_handle* h, int32_t T_total, int32_t n_bins, const int32_t* bins) {
     if (!h) return fail(h, MSL_ERR_INVALID, "null handle");
@@ -2250,11 +2232,8 @@ int msl_tacaw_stream_begin(msl_handle* h, int32_t T_total, int32_t n_bins, const
     HIPCHK(h, hipSetDevice(c.device));
     const size_t PK = (size_t)c.n_probes * h->wpix;
     int rc;
-    if ((rc = dalloc(h, &h->st_acc, PK * n_bins))) return rc;
-    if ((rc = dalloc(h, &h->st_s1, PK))) return rc;
-    if ((rc = dalloc(h, &h->st_s2, PK))) return rc;
-    if ((rc = dalloc(h, &h->st_tw, (size_t)T_total))) return rc;
-    if ((rc = dalloc(h, &h->st_bins, (size_t)n_bins))) return rc;
+    if ((rc = h->st_acc.alloc(h, PK * n_bins)) || (rc = h->st_s1.alloc(h, PK)) || (rc = h->st_s2.alloc(h, PK)) ||
+        (rc = h->st_tw.alloc(h, (size_t)T_total)) || (rc = h->st_bins.alloc(h, (size_t)n_bins))) return rc;
     std::vector<float2> tw(T_total);
     for (int m = 0; m < T_total; ++m) { const double a = -2.0 * M_PI * m / T_total; tw[m] = make_float2((float)cos(a), (float)sin(a)); }
     HIPCHK(h, hipMemcpyAsync(h->st_tw, tw.data(), tw.size() * sizeof(float2), hipMemcpyHostToDevice, h->stream));
@@ -2276,7 +2255,7 @@ int msl_tacaw_stream_set_reference(msl_handle* h, const void* d_ref_c64, int32_t
     HIPCHK(h, hipSetDevice(c.device));
     const size_t K = h->wpix;
     int rc;
-    if (!h->st_ref && (rc = dalloc(h, &h->st_ref, (size_t)c.n_probes * K))) return rc;
+    if (!h->st_ref && (rc = h->st_ref.alloc(h, (size_t)c.n_probes * K))) return rc;
     if (d_ref_c64) {
         HIPCHK(h, hipMemcpyAsync(h->st_ref, d_ref_c64, (size_t)c.n_probes * K * sizeof(float2), hipMemcpyDeviceToDevice, h->stream));
     } else {
@@ -2298,7 +2277,7 @@ int msl_tacaw_stream_push(msl_handle* h, int32_t first_slot, int32_t count, int3
     HIPCHK(h, hipSetDevice(c.device));
     FoldJob j{};
     j.wf = h->wf; j.acc = h->st_acc; j.s1 = h->st_s1; j.s2 = h->st_s2; j.tw = h->st_tw; j.bins = h->st_bins;
-    j.ref = h->st_have_ref ? h->st_ref : nullptr;
+    j.ref = h->st_have_ref ? h->st_ref.p : nullptr;
     j.K = (long long)h->wpix; j.wfK = (long long)h->wpitch; j.ring = c.n_frames; j.first_slot = first_slot; j.count = count; j.t0 = t0; j.T = h->st_T; j.F = h->st_F;
     const dim3 grid((unsigned)((h->wpix + 255) / 256), c.n_probes);
     for (int f0 = 0; f0 < h->st_F; f0 += MSL_FOLD_FCH) {
@@ -2322,10 +2301,7 @@ int msl_tacaw_stream_finish_range(msl_handle* h, int32_t p0, int32_t count, void
     int rc;
     float* dst = (float*)d_dst_f32;
     if (!dst && count > 0) {
-        if (h->intensity_elems != need) {
-            if ((rc = dalloc(h, &h->intensity, need))) return rc;
-            h->intensity_elems = need;
-        }
+        if (h->intensity.n != need && (rc = h->intensity.alloc(h, need))) return rc;
         h->intensity_F = h->st_F; h->intensity_ld = h->wpix;
         dst = h->intensity;
     }
@@ -2335,14 +2311,14 @@ int msl_tacaw_stream_finish_range(msl_handle* h, int32_t p0, int32_t count, void
         HIPCHK(h, hipGetLastError());
     }
     if (total_host && PK) {
-        if ((rc = ensure_scratch(h, PK * sizeof(double)))) return rc;
+        if ((rc = h->scratch.reserve(h, PK * sizeof(double)))) return rc;
         hipLaunchKernelGGL(tacaw_stream_total_kernel, dim3((unsigned)((PK + 255) / 256)), dim3(256), 0, h->stream, h->st_s1 + (size_t)p0 * h->wpix,
-                           h->st_s2 + (size_t)p0 * h->wpix, (double)h->st_T, (long long)PK, (double*)h->scratch);
+                           h->st_s2 + (size_t)p0 * h->wpix, (double)h->st_T, (long long)PK, (double*)h->scratch.p);
         HIPCHK(h, hipGetLastError());
         HIPCHK(h, hipMemcpyAsync(total_host, h->scratch, PK * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     }
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    (void)hipFree(h->st_acc); h->st_acc = nullptr;           // the accumulators are the big part: give them back
+    h->st_acc.release();                                    // the accumulators are the big part: give them back
     h->st_open = false;
     return MSL_OK;
 }
@@ -2361,7 +2337,7 @@ size_t msl_buffer_bytes(const msl_handle* h, msl_buffer what) {
         case MSL_BUF_POTENTIAL: return h->V ? npix * c.nz * 4 : 0;
         case MSL_BUF_TRANSMISSION: return npix * c.nz * 8;
         case MSL_BUF_WAVEFUNCTION: return h->wf ? h->wpitch * c.n_probes * c.n_frames * 8 : 0;
-        case MSL_BUF_INTENSITY: return h->intensity_elems * 4;
+        case MSL_BUF_INTENSITY: return h->intensity.n * 4;
         case MSL_BUF_FORMFACTOR: return npix * h->n_species * 4;
         case MSL_BUF_STREAM_ACC: return (h->st_open && h->st_acc) ? h->wpix * c.n_probes * (size_t)h->st_F * 8 : 0;
         case MSL_BUF_STREAM_S1: return (h->st_open && h->st_s1) ? h->wpix * c.n_probes * 16 : 0;
@@ -2389,28 +2365,21 @@ void* msl_device_ptr(msl_handle* h, msl_buffer what) {
         case MSL_BUF_WAVEFUNCTION: return h->wf;
         case MSL_BUF_INTENSITY: return h->intensity;
         case MSL_BUF_FORMFACTOR: return h->d_ff;
-        case MSL_BUF_STREAM_ACC: return h->st_open ? h->st_acc : nullptr;
-        case MSL_BUF_STREAM_S1: return h->st_open ? h->st_s1 : nullptr;
-        case MSL_BUF_STREAM_S2: return h->st_open ? h->st_s2 : nullptr;
-        case MSL_BUF_STREAM_REF: return (h->st_open && h->st_have_ref) ? h->st_ref : nullptr;
-        case MSL_BUF_LAYERS: return h->layers ? h->layers : h->wf;
+        case MSL_BUF_STREAM_ACC: return h->st_open ? h->st_acc.p : nullptr;
+        case MSL_BUF_STREAM_S1: return h->st_open ? h->st_s1.p : nullptr;
+        case MSL_BUF_STREAM_S2: return h->st_open ? h->st_s2.p : nullptr;
+        case MSL_BUF_STREAM_REF: return (h->st_open && h->st_have_ref) ? h->st_ref.p : nullptr;
+        case MSL_BUF_LAYERS: return h->layers;
     }
     return nullptr;
 }
 
 // ---- reductions over resident results (reduce.h) ------------------------------------------------------
-static int ensure_scratch(msl_handle* h, size_t bytes) {
-    if (bytes <= h->scratch_bytes) return MSL_OK;
-    int rc = dalloc(h, &h->scratch, bytes);
-    h->scratch_bytes = rc ? 0 : bytes;
-    return rc;
-}
-
 // resolve (src, B, F, K, ld) for the TACAW reductions: NULL = the handle's intensity buffer
 static int intensity_source(msl_handle* h, const char* who, const void** src, int64_t* B, int64_t* F, int64_t* K, int64_t* ld) {
     if (!h) return fail(h, MSL_ERR_INVALID, "null handle");
     if (!*src) {
-        if (!h->intensity || h->intensity_elems == 0) return fail(h, MSL_ERR_STATE, "%s: no intensity (call msl_tacaw)", who);
+        if (!h->intensity) return fail(h, MSL_ERR_STATE, "%s: no intensity (call msl_tacaw)", who);
         *src = h->intensity; *B = h->cfg.n_probes; *F = h->intensity_F; *K = (int64_t)h->wpix; *ld = (int64_t)h->intensity_ld;
     } else if (*ld == 0) {
         *ld = *K;
@@ -2421,6 +2390,31 @@ static int intensity_source(msl_handle* h, const char* who, const void** src, in
     return MSL_OK;
 }
 
+// the same for the reductions over complex results: NULL = the exit block of the handle's resident result, of which *B < 1 asks
+// for every probe
+static int resident_wavefunction(msl_handle* h, const char* who, const void** src, int64_t* B, int64_t* T, int64_t* K, int64_t* ld) {
+    if (!*src) {
+        if (!h->wf) return fail(h, MSL_ERR_STATE, "%s: no wavefunction buffer", who);
+        if (*B < 1) *B = h->cfg.n_probes;
+        if (*B > h->cfg.n_probes) return fail(h, MSL_ERR_INVALID, "%s: %lld probes, the handle has %d", who, (long long)*B, h->cfg.n_probes);
+        *src = h->wf; *T = h->cfg.n_frames; *K = (int64_t)h->wpix; *ld = (int64_t)h->wpitch;
+    } else if (*ld == 0) {
+        *ld = *K;
+    }
+    if (*B < 1 || *T < 1 || *K < 1 || *ld < *K) return fail(h, MSL_ERR_INVALID, "%s: bad shape (%lld,%lld,%lld) ld %lld", who, (long long)*B, (long long)*T,
+                                                            (long long)*K, (long long)*ld);
+    return MSL_OK;
+}
+
+// out[r] = the sum of the n_chunks partial sums of row r
+static void sum_row_parts(const std::vector<double>& part, int64_t rows, int n_chunks, double* out) {
+    for (int64_t r = 0; r < rows; ++r) {
+        double s = 0;
+        for (int c = 0; c < n_chunks; ++c) s += part[(size_t)r * n_chunks + c];
+        out[r] = s;
+    }
+}
+
 // sum over K of rows of a (rows, K) array (row pitch ld) with an optional host mask; float64 result per row on the host
 static int reduce_rows(msl_handle* h, const void* src, bool complex_abs, int64_t rows, int64_t K, int64_t ld, const uint8_t* mask, double* out) {
     HIPCHK(h, hipSetDevice(h->cfg.device));
@@ -2428,9 +2422,9 @@ static int reduce_rows(msl_handle* h, const void* src, bool complex_abs, int64_t
     int n_chunks = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(quads / 1024, 4096 / rows), 64));
     const size_t mask_bytes = mask ? (((size_t)K + 15) & ~(size_t)15) + 16 : 0;
     const size_t part_bytes = (size_t)rows * n_chunks * sizeof(double);
-    int rc = ensure_scratch(h, mask_bytes + part_bytes);
+    int rc = h->scratch.reserve(h, mask_bytes + part_bytes);
     if (rc) return rc;
-    uint8_t* d_mask = mask ? (uint8_t*)h->scratch : nullptr;
+    uint8_t* d_mask = mask ? (uint8_t*)h->scratch.p : nullptr;
     double* d_part = (double*)(h->scratch + mask_bytes);
     if (mask) {
         HIPCHK(h, hipMemsetAsync(d_mask, 0, mask_bytes, h->stream));
@@ -2443,11 +2437,7 @@ static int reduce_rows(msl_handle* h, const void* src, bool complex_abs, int64_t
     std::vector<double> part((size_t)rows * n_chunks);
     HIPCHK(h, hipMemcpyAsync(part.data(), d_part, part_bytes, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    for (int64_t r = 0; r < rows; ++r) {
-        double s = 0;
-        for (int c = 0; c < n_chunks; ++c) s += part[(size_t)r * n_chunks + c];
-        out[r] = s;
-    }
+    sum_row_parts(part, rows, n_chunks, out);
     return MSL_OK;
 }
 
@@ -2472,8 +2462,8 @@ int msl_tacaw_spectrum_weighted(msl_handle* h, const void* d_src_f32, int64_t B,
     const int64_t rows_per = std::min<int64_t>(B * F, 32768);
     const int n_chunks = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(K / 4096, 4096 / std::max<int64_t>(1, rows_per)), 64));
     const size_t w_bytes = (size_t)K * sizeof(double), part_bytes = (size_t)rows_per * n_chunks * sizeof(double);
-    if ((rc = ensure_scratch(h, w_bytes + part_bytes))) return rc;
-    double* d_w = (double*)h->scratch;
+    if ((rc = h->scratch.reserve(h, w_bytes + part_bytes))) return rc;
+    double* d_w = (double*)h->scratch.p;
     double* d_part = (double*)(h->scratch + w_bytes);
     HIPCHK(h, hipMemcpyAsync(d_w, weight, w_bytes, hipMemcpyHostToDevice, h->stream));
     std::vector<double> part((size_t)rows_per * n_chunks);
@@ -2484,24 +2474,17 @@ int msl_tacaw_spectrum_weighted(msl_handle* h, const void* d_src_f32, int64_t B,
         HIPCHK(h, hipGetLastError());
         HIPCHK(h, hipMemcpyAsync(part.data(), d_part, (size_t)rows * n_chunks * sizeof(double), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
-        for (int64_t r = 0; r < rows; ++r) {
-            double s = 0;
-            for (int c = 0; c < n_chunks; ++c) s += part[(size_t)r * n_chunks + c];
-            out[r0 + r] = s;
-        }
+        sum_row_parts(part, rows, n_chunks, out + r0);
     }
     return MSL_OK;
 }
 
 int msl_adf(msl_handle* h, const void* d_src_c64, int64_t B, int64_t T, int64_t K, int64_t ld, const uint8_t* mask, double* out) {
     if (!h || !out) return fail(h, MSL_ERR_INVALID, "msl_adf: null argument");
-    if (!d_src_c64) {
-        if (!h->wf) return fail(h, MSL_ERR_STATE, "msl_adf: no wavefunction buffer");
-        d_src_c64 = h->wf; B = h->cfg.n_probes; T = h->cfg.n_frames; K = (int64_t)h->wpix; ld = (int64_t)h->wpitch;
-    } else if (ld == 0) {
-        ld = K;
-    }
-    if (B < 1 || T < 1 || K < 1 || ld < K) return fail(h, MSL_ERR_INVALID, "msl_adf: bad shape");
+    if (!d_src_c64) B = 0;                      // the resident result: always every probe
+    const int rc0 = resident_wavefunction(h, "msl_adf", &d_src_c64, &B, &T, &K, &ld);
+    if (rc0 == MSL_ERR_INVALID) return fail(h, rc0, "msl_adf: bad shape");        // (its message carries no numbers)
+    if (rc0) return rc0;
     if (T > 65535) return fail(h, MSL_ERR_UNSUPPORTED, "msl_adf: more than 65535 frames");
     std::vector<double> rows((size_t)T);
     for (int64_t b = 0; b < B; ++b) {
@@ -2535,7 +2518,7 @@ int msl_set_detectors(msl_handle* h, int32_t n, const uint16_t* member_K, const 
     const uint16_t keep = (uint16_t)((1u << n) - 1u);
     for (auto& v : m) v &= keep;                               // bits of absent detectors never count
     int rc;
-    if ((rc = dalloc(h, &h->det_mask, K)) || (rc = dalloc(h, &h->det_kx, (size_t)sx)) || (rc = dalloc(h, &h->det_ky, (size_t)sy))) {
+    if ((rc = h->det_mask.alloc(h, K)) || (rc = h->det_kx.alloc(h, (size_t)sx)) || (rc = h->det_ky.alloc(h, (size_t)sy))) {
         h->det_n = 0;
         return rc;
     }
@@ -2565,16 +2548,8 @@ static void launch_detect(msl_handle* h, int mode, bool vec, dim3 grid, const fl
 int msl_detect(msl_handle* h, const void* d_src_c64, int64_t B, int64_t T, int64_t K, int64_t ld, int32_t t0, int32_t count, double* out) {
     if (!h || !out) return fail(h, MSL_ERR_INVALID, "msl_detect: null argument");
     if (h->det_n == 0) return fail(h, MSL_ERR_STATE, "msl_detect: no detectors (call msl_set_detectors)");
-    if (!d_src_c64) {
-        if (!h->wf) return fail(h, MSL_ERR_STATE, "msl_detect: no wavefunction buffer");
-        if (B < 1) B = h->cfg.n_probes;
-        if (B > h->cfg.n_probes) return fail(h, MSL_ERR_INVALID, "msl_detect: %lld probes, the handle has %d", (long long)B, h->cfg.n_probes);
-        d_src_c64 = h->wf; T = h->cfg.n_frames; K = (int64_t)h->wpix; ld = (int64_t)h->wpitch;
-    } else if (ld == 0) {
-        ld = K;
-    }
-    if (B < 1 || T < 1 || K < 1 || ld < K) return fail(h, MSL_ERR_INVALID, "msl_detect: bad shape (%lld,%lld,%lld) ld %lld", (long long)B, (long long)T,
-                                                     (long long)K, (long long)ld);
+    int rc = resident_wavefunction(h, "msl_detect", &d_src_c64, &B, &T, &K, &ld);
+    if (rc) return rc;
     if ((size_t)K != h->det_K) return fail(h, MSL_ERR_INVALID, "msl_detect: rows of %lld pixels, the detectors cover %zu", (long long)K, h->det_K);
     if (count < 1 || t0 < 0 || (int64_t)t0 + count > T)
         return fail(h, MSL_ERR_INVALID, "msl_detect: frame slots [%d,%d) outside [0,%lld)", t0, t0 + count, (long long)T);
@@ -2592,9 +2567,8 @@ int msl_detect(msl_handle* h, const void* d_src_c64, int64_t B, int64_t T, int64
     const int64_t blocks_y = (rows + per - 1) / per;
     const size_t part_bytes = ((size_t)rows * n_tiles * ND * sizeof(float) + 255) & ~(size_t)255;
     const size_t out_bytes = (size_t)rows * n * sizeof(double);
-    int rc = ensure_scratch(h, part_bytes + out_bytes);
-    if (rc) return rc;
-    float* d_part = (float*)h->scratch;
+    if ((rc = h->scratch.reserve(h, part_bytes + out_bytes))) return rc;
+    float* d_part = (float*)h->scratch.p;
     double* d_out = (double*)(h->scratch + part_bytes);
     const int mode = h->det_amp == 0 ? 0 : (h->det_amp == (1u << n) - 1u ? 1 : 2);
     const bool vec = (ld % 2 == 0) && (((uintptr_t)d_src_c64 & 15) == 0);
@@ -2624,18 +2598,11 @@ static void launch_diffract(msl_handle* h, bool vec, unsigned grid, unsigned thr
 int msl_diffract(msl_handle* h, const void* d_src_c64, int64_t B, int64_t T, int64_t K, int64_t ld, int32_t t0, int32_t count, int32_t wx, int32_t wy,
                  int32_t bx, int32_t by, double* out) {
     if (!h || !out) return fail(h, MSL_ERR_INVALID, "msl_diffract: null argument");
-    if (!d_src_c64) {
-        if (!h->wf) return fail(h, MSL_ERR_STATE, "msl_diffract: no wavefunction buffer");
-        if (B < 1) B = h->cfg.n_probes;
-        if (B > h->cfg.n_probes) return fail(h, MSL_ERR_INVALID, "msl_diffract: %lld probes, the handle has %d", (long long)B, h->cfg.n_probes);
-        if (wx != h->wx / h->bx || wy != h->wy / h->by)
-            return fail(h, MSL_ERR_INVALID, "msl_diffract: window %d x %d, the handle stores %d x %d", wx, wy, h->wx / h->bx, h->wy / h->by);
-        d_src_c64 = h->wf; T = h->cfg.n_frames; K = (int64_t)h->wpix; ld = (int64_t)h->wpitch;
-    } else if (ld == 0) {
-        ld = K;
-    }
-    if (B < 1 || T < 1 || K < 1 || ld < K) return fail(h, MSL_ERR_INVALID, "msl_diffract: bad shape (%lld,%lld,%lld) ld %lld", (long long)B, (long long)T,
-                                                     (long long)K, (long long)ld);
+    const bool resident = !d_src_c64;
+    int rc = resident_wavefunction(h, "msl_diffract", &d_src_c64, &B, &T, &K, &ld);
+    if (rc) return rc;
+    if (resident && (wx != h->wx / h->bx || wy != h->wy / h->by))
+        return fail(h, MSL_ERR_INVALID, "msl_diffract: window %d x %d, the handle stores %d x %d", wx, wy, h->wx / h->bx, h->wy / h->by);
     if (wx < 1 || wy < 1 || (int64_t)wx * wy != K) return fail(h, MSL_ERR_INVALID, "msl_diffract: window %d x %d over rows of %lld pixels", wx, wy, (long long)K);
     if (bx < 1 || by < 1 || wx % bx || wy % by) return fail(h, MSL_ERR_INVALID, "msl_diffract: bin %d x %d does not divide the window %d x %d", bx, by, wx, wy);
     if (count < 1 || t0 < 0 || (int64_t)t0 + count > T)
@@ -2649,12 +2616,7 @@ int msl_diffract(msl_handle* h, const void* d_src_c64, int64_t B, int64_t T, int
     if (lds > 64u * 1024u) return fail(h, MSL_ERR_UNSUPPORTED, "msl_diffract: bin %d of rows of %d pixels needs %zu bytes of LDS", by, wy, lds);
     HIPCHK(h, hipSetDevice(h->cfg.device));
     const size_t n_out = (size_t)strips * my;
-    if (n_out > h->diff_cap) {
-        h->diff_cap = 0;
-        int rc = dalloc(h, &h->diff_out, n_out);
-        if (rc) return rc;
-        h->diff_cap = n_out;
-    }
+    if ((rc = h->diff_out.reserve(h, n_out))) return rc;
     // 16-byte loads need every row to start on 16 bytes: base, image pitch and row length even in pixels
     const bool vec = (ld % 2 == 0) && (wy % 2 == 0) && (((uintptr_t)d_src_c64 & 15) == 0);
     const int cols = vec ? (wy + 1) / 2 : wy;
@@ -2665,8 +2627,7 @@ int msl_diffract(msl_handle* h, const void* d_src_c64, int64_t B, int64_t T, int
     per = std::max<int64_t>(1, std::min<int64_t>(per, strips / 4096));
     per = std::max<int64_t>(per, (strips + 0x7ffffffeLL) / 0x7fffffffLL);
     const unsigned grid = (unsigned)((strips + per - 1) / per);
-    int rc = begin_timed(h, 1);
-    if (rc) return rc;
+    if ((rc = begin_timed(h, 1))) return rc;
     const float2* src = (const float2*)d_src_c64;
     if (mode == DIFF_DIRECT) launch_diffract<DIFF_DIRECT>(h, vec, grid, threads, lds, src, T, t0, count, ld, wx, wy, bx, by, strips, (int)per, h->diff_out);
     else if (mode == DIFF_SHFL) launch_diffract<DIFF_SHFL>(h, vec, grid, threads, lds, src, T, t0, count, ld, wx, wy, bx, by, strips, (int)per, h->diff_out);
@@ -2688,8 +2649,8 @@ int msl_tacaw_diffraction(msl_handle* h, const void* d_src_f32, int64_t B, int64
         return fail(h, MSL_ERR_INVALID, "msl_tacaw_diffraction: range [%lld,%lld) x [%lld,%lld) outside (%lld,%lld)", (long long)b0,
                     (long long)b1, (long long)f0, (long long)f1, (long long)B, (long long)F);
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    if ((rc = ensure_scratch(h, (size_t)K * sizeof(double)))) return rc;
-    double* d_out = (double*)h->scratch;
+    if ((rc = h->scratch.reserve(h, (size_t)K * sizeof(double)))) return rc;
+    double* d_out = (double*)h->scratch.p;
     const bool vec = (K % 4 == 0) && (ld % 4 == 0);
     const long long threads = vec ? K / 4 : K;
     const unsigned grid = (unsigned)((threads + 255) / 256);
@@ -2712,8 +2673,8 @@ int msl_tacaw_dispersion(msl_handle* h, const void* d_src_f32, int64_t B, int64_
         if (idx[i] < 0 || idx[i] >= K) return fail(h, MSL_ERR_INVALID, "msl_tacaw_dispersion: index %lld outside [0,%lld)", (long long)idx[i], (long long)K);
     HIPCHK(h, hipSetDevice(h->cfg.device));
     const size_t idx_bytes = (size_t)n * sizeof(int64_t), out_bytes = (size_t)B * F * n * sizeof(float);
-    if ((rc = ensure_scratch(h, idx_bytes + out_bytes))) return rc;
-    long long* d_idx = (long long*)h->scratch;
+    if ((rc = h->scratch.reserve(h, idx_bytes + out_bytes))) return rc;
+    long long* d_idx = (long long*)h->scratch.p;
     float* d_out = (float*)(h->scratch + idx_bytes);
     HIPCHK(h, hipMemcpyAsync(d_idx, idx, idx_bytes, hipMemcpyHostToDevice, h->stream));
     const long long tot = (long long)B * F * n;
@@ -2827,7 +2788,7 @@ int msl_download_wavefunction_c128(msl_handle* h, int32_t n_frames_used, void* d
     size_t chunk = std::min<size_t>(per_probe, (size_t)(256u << 20) / sizeof(double2));
     if (chunk > h->wpix) chunk -= chunk % h->wpix;
     if (const char* e = dbg_env("MSL_C128_CHUNK")) chunk = std::max<size_t>(1, std::min<size_t>(chunk, (size_t)atoll(e)));      // (tests: several chunks per probe)
-    int rc = ensure_scratch(h, chunk * sizeof(double2));
+    int rc = h->scratch.reserve(h, chunk * sizeof(double2));
     if (rc) return rc;
     for (int p = 0; p < c.n_probes; ++p) {
         const float2* src = h->wf + (size_t)p * c.n_frames * h->wpitch;
@@ -2837,10 +2798,10 @@ int msl_download_wavefunction_c128(msl_handle* h, int32_t n_frames_used, void* d
             const size_t img = o / h->wpix, px = o % h->wpix;
             const size_t n = std::min(px ? std::min(chunk, h->wpix - px) : chunk, per_probe - o);
             const int grid = (int)std::min<size_t>((n + 255) / 256, (size_t)h->n_cus * 8);
-            hipLaunchKernelGGL(widen_c64_kernel, dim3(grid), dim3(256), 0, h->stream, src + img * h->wpitch + px, (double2*)h->scratch, (long long)n,
+            hipLaunchKernelGGL(widen_c64_kernel, dim3(grid), dim3(256), 0, h->stream, src + img * h->wpitch + px, (double2*)h->scratch.p, (long long)n,
                                (long long)h->wpix, (long long)h->wpitch);
             HIPCHK(h, hipGetLastError());
-            HIPCHK(h, hipMemcpyAsync(out + o, h->scratch, n * sizeof(double2), hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(h, hipMemcpyAsync(out + o, h->scratch.p, n * sizeof(double2), hipMemcpyDeviceToHost, h->stream));
             HIPCHK(h, hipStreamSynchronize(h->stream));
             o += n;
         }
@@ -2867,30 +2828,30 @@ int msl_set_layers(msl_handle* h, const int32_t* slices, int32_t n) {
     {
         size_t free_b = 0, total_b = 0;
         HIPCHK(h, hipMemGetInfo(&free_b, &total_b));
-        const size_t have = free_b + block * 8 * (n_taps(h) + 1) + (h->tap ? (size_t)c.nx * h->pitch * images * 8 : 0);
+        const size_t have = free_b + (h->layers.n + h->tap.n) * 8;           // what the old result and tap give back
         const size_t need = block * 8 * (n + 1) + tap_elems * 8;
         if (need > have)
             return fail(h, MSL_ERR_NOMEM, "msl_set_layers: %d layers need %zu bytes, the device has %zu", n + 1, need, have);
     }
     // the old result goes first: at full size two of them would not fit
-    if (h->layers) { (void)hipFree(h->layers); h->layers = nullptr; } else if (h->wf) { (void)hipFree(h->wf); }
+    h->layers.release();
     h->wf = nullptr;
     h->layer_slices.clear(); h->layer_block.clear();
-    int rc = dalloc(h, &h->tap, tap_elems);
-    if (!rc) rc = dalloc(h, n > 0 ? &h->layers : &h->wf, block * (n + 1));
+    int rc = h->tap.alloc(h, tap_elems);
+    if (!rc) rc = h->layers.alloc(h, block * (n + 1));
     if (rc) {                                                   // back to a single-layer result, if that still fits
-        (void)dalloc(h, &h->tap, 0);
-        h->layers = nullptr;
-        if (dalloc(h, &h->wf, block) == MSL_OK) (void)hipMemsetAsync(h->wf, 0, block * sizeof(float2), h->stream);
+        h->tap.release();
+        if (h->layers.alloc(h, block) == MSL_OK) (void)hipMemsetAsync(h->layers, 0, block * sizeof(float2), h->stream);
+        h->wf = h->layers;
         return fail(h, MSL_ERR_NOMEM, "msl_set_layers: %d layers of %zu bytes do not fit", n + 1, block * 8);
     }
+    h->wf = h->layers + (size_t)n * block;
     if (n > 0) {
-        h->wf = h->layers + (size_t)n * block;
         h->layer_slices.assign(slices, slices + n);
         h->layer_block.assign(c.nz, -1);
         for (int i = 0; i < n; ++i) h->layer_block[slices[i]] = i;
     }
-    HIPCHK(h, hipMemsetAsync(n > 0 ? h->layers : h->wf, 0, block * (n + 1) * sizeof(float2), h->stream));
+    HIPCHK(h, hipMemsetAsync(h->layers, 0, block * (n + 1) * sizeof(float2), h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return MSL_OK;
 }
@@ -2906,19 +2867,18 @@ int msl_download_layers_c128(msl_handle* h, int32_t n_frames_used, void* dst, si
         return fail(h, MSL_ERR_INVALID, "msl_download_layers_c128: dst holds %zu bytes, the result has %zu", bytes, (size_t)c.n_probes * per_probe * L * sizeof(double2));
     HIPCHK(h, hipSetDevice(c.device));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    const float2* base = h->layers ? h->layers : h->wf;
     const size_t block = layer_block_elems(h);
     // chunks of at most 256 MB of complex128 through the scratch buffer, as msl_download_wavefunction_c128
     size_t chunk = std::max<size_t>(1, std::min<size_t>(per_probe, (size_t)(256u << 20) / sizeof(double2) / L));
     if (const char* e = dbg_env("MSL_C128_CHUNK")) chunk = std::max<size_t>(1, std::min<size_t>(chunk, (size_t)atoll(e)));
-    int rc = ensure_scratch(h, chunk * L * sizeof(double2));
+    int rc = h->scratch.reserve(h, chunk * L * sizeof(double2));
     if (rc) return rc;
     for (int p = 0; p < c.n_probes; ++p) {
         double2* out = (double2*)dst + (size_t)p * per_probe * L;
         for (size_t o = 0; o < per_probe; o += chunk) {
             const size_t n = std::min(chunk, per_probe - o);
             const int grid = (int)std::min<size_t>((n * L + 255) / 256, (size_t)h->n_cus * 8);
-            hipLaunchKernelGGL(layer_tap_c128_kernel, dim3(grid), dim3(256), 0, h->stream, base, (double2*)h->scratch, (long long)o, (long long)n, L,
+            hipLaunchKernelGGL(layer_tap_c128_kernel, dim3(grid), dim3(256), 0, h->stream, h->layers.p, (double2*)h->scratch.p, (long long)o, (long long)n, L,
                                (long long)block, (long long)p * c.n_frames * h->wpitch, (long long)h->wpix, (long long)h->wpitch);
             HIPCHK(h, hipGetLastError());
             HIPCHK(h, hipMemcpyAsync(out + o * L, h->scratch, n * L * sizeof(double2), hipMemcpyDeviceToHost, h->stream));
@@ -2933,12 +2893,8 @@ int msl_tacaw_layer(msl_handle* h, int32_t layer) {
     if (!h->wf) return fail(h, MSL_ERR_STATE, "msl_tacaw_layer: no wavefunction buffer");
     const int L = n_taps(h) + 1;
     if (layer < 0 || layer >= L) return fail(h, MSL_ERR_INVALID, "msl_tacaw_layer: layer %d outside [0, %d)", layer, L);
-    if (layer == L - 1) return msl_tacaw(h, nullptr, nullptr, 0, 0, 0);
-    float2* exit_block = h->wf;
-    h->wf = h->layers + (size_t)layer * layer_block_elems(h);         // msl_tacaw(NULL ..) on that block
-    const int rc = msl_tacaw(h, nullptr, nullptr, 0, 0, 0);
-    h->wf = exit_block;
-    return rc;
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    return tacaw_resident(h, h->layers + (size_t)layer * layer_block_elems(h));         // (the last block is wf)
 }
 
 int msl_download_frame(msl_handle* h, int32_t slot, void* dst, size_t bytes) { return frame_copy(h, slot, dst, bytes, true); }
@@ -2980,8 +2936,8 @@ int msl_fft2_host(msl_handle* h, const float* in, float* out, int32_t batch, int
     const msl_config& c = h->cfg;
     HIPCHK(h, hipSetDevice(c.device));
     const size_t n = (size_t)batch * c.nx * c.ny;
-    float2* buf = nullptr;
-    int rc = dalloc(h, &buf, n);
+    DevBuf<float2> buf;
+    int rc = buf.alloc(h, n);
     if (rc) return rc;
     HIPCHK(h, hipMemcpyAsync(buf, in, n * sizeof(float2), hipMemcpyHostToDevice, h->stream));
     h->cur = nullptr;
@@ -2991,7 +2947,6 @@ int msl_fft2_host(msl_handle* h, const float* in, float* out, int32_t batch, int
         if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
         if (e != hipSuccess) rc = fail(h, MSL_ERR_HIP, "msl_fft2_host copy back: %s", hipGetErrorString(e));
     }
-    (void)hipFree(buf);
     return rc;
 }
 

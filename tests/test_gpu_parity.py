@@ -1483,6 +1483,68 @@ def test_result_release_returns_the_device_memory(ps, orc):
     assert free0 - torch.cuda.mem_get_info(0)[0] < 512 << 20        # (code objects, the staged copy `wf` still holds, allocator slack)
 
 
+def test_handle_teardown_returns_all_device_memory(ps):
+    """Create, use and destroy a handle three times in one process: a thickness series (msl_set_layers), a TACAW call of every
+    kind of time kernel (four-step, per-lane, wave-split, chirp-z, generic: each with tables of its own in the handle), the
+    resident and the layer TACAW, a stream begin / push / finish, detectors and a diffraction call.  Every device buffer of the
+    handle must come back with msl_destroy: the free device memory after the third cycle is within ONE per-probe work buffer of
+    this configuration (1024 x 1024 x 16 probes x 8 bytes = 128 MB without its row padding, far above allocator granularity) of
+    the value after the first.  Only normal teardown is watched: nothing here fails an allocation."""
+    import gc
+    import torch
+    from pyslice_amd import _native
+    from pyslice_amd.synthetic import synthetic_trajectory
+    from pyslice_amd.potentials import slice_edges
+    n, nz, P, T = 1024, 2, 16, 2
+    dev = torch.device("cuda", 0)
+    tr = synthetic_trajectory(n, nz, 1, density=0.02, seed=3)
+    xs, ys, zs, lx, ly, lz = ps.gridFromTrajectory(tr)
+    pp = np.random.default_rng(2).random((P, 2)) * [lx, ly]
+    kirkland = ps.loadKirkland()
+    # the caller's TACAW buffers live through all cycles (torch's caching allocator stays out of the comparison)
+    npix = 4096
+    time_cases = [(100, {}), (256, {}), (1024, {"MSL_TACAW_FOURSTEP": "1"}), (97, {}), (1030, {})]   # direct, split, four-step, chirp-z, generic
+    src = torch.view_as_complex(torch.randn((1, 1030, npix, 2), device=dev))
+    dst = torch.empty((1, 1030, npix), dtype=torch.float32, device=dev)
+    k = np.fft.fftshift(np.fft.fftfreq(n, 0.1)).astype(np.float32)
+    member = np.ones(n * n, dtype=np.uint16)
+    torch.cuda.synchronize()
+
+    def cycle():
+        eng = _native.Engine(n, n, nz, xs[1] - xs[0], ys[1] - ys[0], zs[1] - zs[0], 0.0370144, 9.24396e-4, n_probes=P, n_frames=T)
+        eng.set_kirkland(kirkland)
+        eng.set_slices(*slice_edges(zs))
+        eng.set_probes(30.0, pp)
+        eng.set_layers([0])
+        eng.build_potential(tr.positions[0], tr.atom_types.astype(np.int32))
+        for t in range(T):
+            eng.propagate_frame(t)
+        eng.tacaw()
+        eng.tacaw_layer(0)
+        for frames, switches in time_cases:
+            env = dict(switches, MSL_DEBUG="1") if switches else {}
+            os.environ.update(env)
+            try:
+                eng.tacaw(src.data_ptr(), dst.data_ptr(), 1, frames, npix)
+            finally:
+                for name in env:
+                    del os.environ[name]
+        eng.tacaw_stream_begin(T)
+        eng.tacaw_stream_push(0, T, 0)
+        assert eng.tacaw_stream_finish().shape == (P, n, n)
+        eng.set_detectors(member, ["intensity"], k, k)
+        assert eng.detect().shape == (P, T, 1)
+        assert eng.diffract(bin=(4, 4)).shape == (P, n // 4, n // 4)
+        eng.synchronize()
+        eng.close()
+        gc.collect()
+        return torch.cuda.mem_get_info(0)[0]
+
+    free = [cycle() for _ in range(3)]
+    print(f"free device memory after each cycle: {free}, third - first = {free[2] - free[0]} bytes")
+    assert abs(free[2] - free[0]) < n * n * P * 8, free
+
+
 def test_tacaw_time_axis_256_frames(ps, orc):
     """T = 256 frames (BASELINE C3's frame count) through the calculator: the wave-split register kernel (2 x 128; the
     four-step column kernel until round 3), DC zeroed, fftshifted |.|^2; compare with the oracle and with the generic kernel."""
