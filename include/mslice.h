@@ -142,6 +142,19 @@ int  msl_resize_probes(msl_handle* h, int32_t n_probes);
  * Replaces Probe.__init__ + create_batched_probes (multislice.py:112-124, 198-235). */
 int  msl_set_probes(msl_handle* h, double mrad, const double* xy, int32_t n_probes);
 
+/* Aberration function of the probe-forming lens: every later msl_set_probes builds
+ *     psi0[p] = ifft2(mask * ramp_p * exp(-i chi(k))),
+ *     chi(k) = (2 pi / lambda) sum_nm C_nm / (n+1) * alpha^(n+1) * cos(m (phi - phi_nm)),  alpha = lambda |k|, phi = atan2(ky, kx).
+ * polar = n_terms x 2 doubles (magnitude C_nm in Angstrom, angle phi_nm in radians; the angle is ignored for m == 0) in the order
+ *     C10 C12 C21 C23 C30 C32 C34 C41 C43 C45 C50 C52 C54 C56.
+ * n_terms must be 14, or 0 to clear (polar is then not read and may be NULL).  Non-finite values are MSL_ERR_INVALID.  C10 = +dz is the
+ * reference's Probe.defocus(dz) for dz > 0 (exp(-i pi lambda dz k^2), multislice.py:183-190); a negative C10 is the conjugate
+ * phase.  The state stays on the handle until it is set again or cleared, and uses the wavelength the handle has when
+ * msl_set_probes runs.  All magnitudes zero is the same as cleared: msl_set_probes then runs exactly as without this call.
+ * Plane waves (mrad == 0) have chi(0) = 0 and are not changed.  msl_upload_probes and msl_shift_probes, whose arrays come from
+ * the caller, ignore the aberrations. */
+int  msl_set_aberrations(msl_handle* h, const double* polar, int32_t n_terms);
+
 /* Upload arbitrary initial waves (P,nx,ny) c64 (used when a caller hands Propagate() a
  * Probe built from its own array, multislice.py:104-109). */
 int  msl_upload_probes(msl_handle* h, const float* c64, int32_t n_probes);

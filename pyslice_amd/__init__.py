@@ -13,8 +13,10 @@ from .tacaw_data import TACAWData
 from .haadf_data import HAADFData
 from .stem_data import Detector, STEMData
 from .diffraction_data import Diffraction, DiffractionData
+from .aberrations import Aberrations, scherzer_defocus
 
 __all__ = ["Trajectory", "WFData", "Potential", "gridFromTrajectory", "getZfromElementName", "loadKirkland",
            "Probe", "Propagate", "create_batched_probes", "probe_grid", "wavelength", "m_effective",
-           "MultisliceCalculator", "TACAWData", "HAADFData", "Detector", "STEMData", "Diffraction", "DiffractionData"]
+           "MultisliceCalculator", "TACAWData", "HAADFData", "Detector", "STEMData", "Diffraction", "DiffractionData",
+           "Aberrations", "scherzer_defocus"]
 __version__ = "0.1.0"

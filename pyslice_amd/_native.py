@@ -20,7 +20,7 @@ MSL_OK, MSL_ERR_INVALID, MSL_ERR_HIP, MSL_ERR_UNSUPPORTED, MSL_ERR_STATE, MSL_ER
 
 EXPORTS = [
     "msl_abi_version", "msl_line_kernel_class", "msl_last_error", "msl_create", "msl_destroy", "msl_set_kirkland", "msl_set_slices",
-    "msl_set_beam", "msl_resize_probes", "msl_set_probes", "msl_upload_probes", "msl_shift_probes",
+    "msl_set_beam", "msl_resize_probes", "msl_set_probes", "msl_set_aberrations", "msl_upload_probes", "msl_shift_probes",
     "msl_build_potential", "msl_upload_potential", "msl_propagate", "msl_propagate_frame", "msl_tacaw",
     "msl_download", "msl_download_wavefunction_c128", "msl_download_frame", "msl_upload_frame", "msl_buffer_bytes", "msl_result_pitch", "msl_device_ptr", "msl_synchronize",
     "msl_get_counters",
@@ -79,6 +79,7 @@ def load():
         "msl_set_beam": (C.c_int, [vp, dbl, dbl, dbl]),
         "msl_resize_probes": (C.c_int, [vp, i32]),
         "msl_set_probes": (C.c_int, [vp, dbl, vp, i32]),
+        "msl_set_aberrations": (C.c_int, [vp, vp, i32]),
         "msl_upload_probes": (C.c_int, [vp, vp, i32]),
         "msl_shift_probes": (C.c_int, [vp, vp, vp, i32]),
         "msl_build_potential": (C.c_int, [vp, vp, vp, i64, i32, i32, i32]),
@@ -224,6 +225,17 @@ class Engine:
     def set_probes(self, mrad, xy):
         xy = np.ascontiguousarray(xy, dtype=np.float64).reshape(-1, 2)
         self._chk(self._lib.msl_set_probes(self._h, float(mrad), _ptr(xy), xy.shape[0]))
+
+    def set_aberrations(self, aberrations):
+        """aberration function of every later set_probes (msl_set_aberrations): an aberrations.Aberrations, or None to clear.
+        Sticky on the handle; upload_probes / shift_probes ignore it"""
+        if aberrations is None:
+            self._chk(self._lib.msl_set_aberrations(self._h, None, 0))
+            return
+        polar = np.ascontiguousarray(aberrations.as_polar(), dtype=np.float64)
+        if polar.shape != (14, 2):
+            raise ValueError(f"aberrations must give (14, 2) polar coefficients, got {polar.shape}")
+        self._chk(self._lib.msl_set_aberrations(self._h, _ptr(polar), 14))
 
     def upload_probes(self, arr):
         a = np.ascontiguousarray(arr, dtype=np.complex64)

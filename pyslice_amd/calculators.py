@@ -22,6 +22,7 @@ from typing import List, Optional, Tuple
 import numpy as np
 
 from . import _native, distributed
+from .aberrations import Aberrations
 from .multislice import Probe, interaction_sigma, wavelength
 from .potentials import TORCH_AVAILABLE, _as_tensor, _device_index, gridFromTrajectory, loadKirkland, slice_edges, suggest_sampling
 from .trajectory import Trajectory
@@ -81,7 +82,7 @@ class MultisliceCalculator:
 
     def __init__(self, device=None, force_cpu=False, *, output="host", dtype="complex128", progress=True,
                  gather="rank0", cache=False, k_window=None, frame_batch=None, k_bin=None, stream_tile=None, layers=None,
-                 detectors=None, probe_batch=None, diffraction=None):
+                 detectors=None, probe_batch=None, diffraction=None, aberrations=None):
         """
         device / force_cpu: as the reference (calculators.py:41).  There is no CPU path here, so
         force_cpu=True raises.  Keyword-only extras (not in the reference):
@@ -115,6 +116,11 @@ class MultisliceCalculator:
                    propagation feeds both.  setup() raises ValueError when the bin does not divide the stored spectrum.
           probe_batch probes per batch of run_detectors() / run_diffraction() (default: chosen in setup() from free device
                    memory, about 256 images per launch with the frame batch).  Needs detectors or diffraction.
+          aberrations an aberrations.Aberrations: every probe of run(), run_streaming_tacaw(), run_detectors() and
+                   run_diffraction() is ifft2(mask * ramp * exp(-i chi(k))), built on the device with the probes themselves.
+                   Aberrations(defocus=dz) is the reference's Probe.defocus(dz) for dz > 0 (the opposite sign of abTEM's
+                   defocus = -C10).  setup(defocus=...) stays stored-only, as in the reference.  No effect on plane waves
+                   (aperture == 0).  With cache=True a non-zero set joins the cache key.
         """
         if force_cpu:
             raise NotImplementedError("pyslice_amd has no CPU path (force_cpu=True): use the reference for CPU runs")
@@ -179,6 +185,9 @@ class MultisliceCalculator:
                     raise ValueError(f"diffraction cannot be combined with {what}" +
                                      (" (a bin sums complex pixels; Diffraction(bin=...) sums their intensities)" if what == "k_bin" else ""))
         self._diffraction = diffraction
+        if aberrations is not None and not isinstance(aberrations, Aberrations):
+            raise ValueError(f"aberrations: expected an Aberrations object, got {aberrations!r}")
+        self._aberrations = aberrations
         self._probe_batch = None if probe_batch is None else int(probe_batch)
         self._layers = None                     # validated slice indices (setup), nz - 1 last
         self._engine = None
@@ -196,6 +205,9 @@ class MultisliceCalculator:
             'box_matrix': trajectory.box_matrix.tolist(), 'atom_types': trajectory.atom_types.tolist(),
             'aperture': aperture, 'voltage_eV': voltage_eV, 'slice_thickness': slice_thickness,
             'sampling': sampling, 'probe_positions': probe_positions, 'backend': 'pytorch'}
+        ab = getattr(self, "_aberrations", None)
+        if ab is not None and not ab.is_zero:           # (without aberrations the key stays the one the reference computes)
+            params['aberrations'] = tuple(map(tuple, ab.as_polar().tolist()))
         return hashlib.md5(str(sorted(params.items())).encode()).hexdigest()[:12]
 
     def setup(
@@ -264,7 +276,7 @@ class MultisliceCalculator:
             else:
                 self._setup_probe_batches(trajectory, slice_axis)
             return
-        self.base_probe = Probe(xs, ys, self.aperture, self.voltage_eV, device=self.device)
+        self.base_probe = Probe(xs, ys, self.aperture, self.voltage_eV, device=self.device, aberrations=self._aberrations)
 
         self.n_frames = trajectory.n_frames
         self.n_probes = len(self.probe_positions)
@@ -338,6 +350,7 @@ class MultisliceCalculator:
         self._engine.set_kirkland(loadKirkland())
         lo, hi = slice_edges(slice_coords)
         self._engine.set_slices(lo, hi)
+        self._engine.set_aberrations(self._aberrations)
         self._engine.set_probes(self.aperture, np.asarray(self.probe_positions, dtype=np.float64))
         self._Z = np.asarray(trajectory.atom_types, dtype=np.int32)
 
@@ -358,7 +371,7 @@ class MultisliceCalculator:
         """the engine of a run that streams probe batches (detectors, diffraction): Pc <= P probes x one frame batch of slots"""
         nx, ny = self.nx, self.ny
         lam = wavelength(self.voltage_eV)
-        self.base_probe = Probe(self.xs, self.ys, self.aperture, self.voltage_eV, device=self.device)
+        self.base_probe = Probe(self.xs, self.ys, self.aperture, self.voltage_eV, device=self.device, aberrations=self._aberrations)
         self.n_frames = trajectory.n_frames
         self.n_probes = len(self.probe_positions)
         self.wavefunction_data = None
@@ -405,6 +418,7 @@ class MultisliceCalculator:
         self._engine.set_kirkland(loadKirkland())
         lo, hi = slice_edges(slice_coords)
         self._engine.set_slices(lo, hi)
+        self._engine.set_aberrations(self._aberrations)         # read by the set_probes of every probe batch
         self._Z = np.asarray(trajectory.atom_types, dtype=np.int32)
 
     def _probe_batch_loop(self, reduce_batch):

@@ -193,6 +193,9 @@ struct msl_handle {
     int ff_species[104] = {0};     // species list the resident form-factor table was computed for (frame-invariant: computed once per run)
     int ff_n = 0;
     DevBuf<double> d_xy;
+    // probe aberrations (msl_set_aberrations): (magnitude, angle) of the fourteen terms; read by every msl_set_probes
+    double aberr_polar[14][2] = {};
+    bool have_aberr = false;       // some magnitude is non-zero: msl_set_probes launches probe_kspace_aberr_kernel
     // counters
     msl_counters ctr{};
     double ms_kind[K_NKINDS] = {0, 0, 0};
@@ -2083,6 +2086,25 @@ int msl_shift_probes(msl_handle* h, const float* base, const double* xy, int32_t
     return MSL_OK;
 }
 
+int msl_set_aberrations(msl_handle* h, const double* polar, int32_t n_terms) {
+    if (!h) return fail(h, MSL_ERR_INVALID, "null handle");
+    if (n_terms == 0) {
+        memset(h->aberr_polar, 0, sizeof(h->aberr_polar));
+        h->have_aberr = false;
+        return MSL_OK;
+    }
+    if (n_terms != 14) return fail(h, MSL_ERR_INVALID, "msl_set_aberrations: %d terms, need 14 (or 0 to clear)", n_terms);
+    if (!polar) return fail(h, MSL_ERR_INVALID, "msl_set_aberrations: null argument");
+    bool any = false;
+    for (int k = 0; k < 28; ++k) {
+        if (!std::isfinite(polar[k])) return fail(h, MSL_ERR_INVALID, "msl_set_aberrations: value %d is not finite", k);
+        if (!(k & 1) && polar[k] != 0) any = true;
+    }
+    memcpy(h->aberr_polar, polar, sizeof(h->aberr_polar));
+    h->have_aberr = any;
+    return MSL_OK;
+}
+
 int msl_set_probes(msl_handle* h, double mrad, const double* xy, int32_t n_probes) {
     if (!h || !xy) return fail(h, MSL_ERR_INVALID, "msl_set_probes: null argument");
     if (n_probes != h->cfg.n_probes) return fail(h, MSL_ERR_INVALID, "msl_set_probes: %d probes, handle has %d", n_probes, h->cfg.n_probes);
@@ -2092,9 +2114,23 @@ int msl_set_probes(msl_handle* h, double mrad, const double* xy, int32_t n_probe
     HIPCHK(h, hipMemcpyAsync(h->d_xy, xy, 2 * sizeof(double) * n_probes, hipMemcpyHostToDevice, h->stream));
     const long long total = (long long)c.nx * c.ny * n_probes;
     const double lx = c.nx * c.dx, ly = c.ny * c.dy;
-    hipLaunchKernelGGL(probe_kspace_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, h->psi0, h->d_xy,
-                       n_probes, c.nx, c.ny, h->pitch, 1.0 / lx, 1.0 / ly, 1.0 / (c.nx * c.dx), 1.0 / (c.ny * c.dy),
-                       (mrad * 1e-3) / c.wavelength, mrad == 0 ? 1 : 0);
+    if (h->have_aberr && mrad != 0) {
+        // (a, b) = C (cos, sin)(m phi) / ((n + 1) lambda): the kernel's polynomial then gives chi / (2 pi) in turns
+        static const int term_n[14] = {1, 1, 2, 2, 3, 3, 3, 4, 4, 4, 5, 5, 5, 5}, term_m[14] = {0, 2, 1, 3, 0, 2, 4, 1, 3, 5, 0, 2, 4, 6};
+        ProbeAberrations ab;
+        for (int k = 0; k < 14; ++k) {
+            const double w = h->aberr_polar[k][0] / ((term_n[k] + 1) * c.wavelength);
+            ab.a[k] = term_m[k] ? w * cos(term_m[k] * h->aberr_polar[k][1]) : w;
+            ab.b[k] = term_m[k] ? w * sin(term_m[k] * h->aberr_polar[k][1]) : 0.0;
+        }
+        hipLaunchKernelGGL(probe_kspace_aberr_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, h->psi0, h->d_xy,
+                           n_probes, c.nx, c.ny, h->pitch, 1.0 / lx, 1.0 / ly, 1.0 / (c.nx * c.dx), 1.0 / (c.ny * c.dy),
+                           (mrad * 1e-3) / c.wavelength, c.wavelength, ab);
+    } else {
+        hipLaunchKernelGGL(probe_kspace_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, h->psi0, h->d_xy,
+                           n_probes, c.nx, c.ny, h->pitch, 1.0 / lx, 1.0 / ly, 1.0 / (c.nx * c.dx), 1.0 / (c.ny * c.dy),
+                           (mrad * 1e-3) / c.wavelength, mrad == 0 ? 1 : 0);
+    }
     HIPCHK(h, hipGetLastError());
     int rc = fft2_inplace(h, h->psi0, n_probes, -1, 1.0f / ((float)c.nx * (float)c.ny), h->pitch);
     if (rc) return rc;

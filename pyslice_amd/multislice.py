@@ -9,6 +9,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import _native
+from .aberrations import Aberrations
 from .potentials import TORCH_AVAILABLE, _as_tensor, _device_index
 
 if TORCH_AVAILABLE:
@@ -53,9 +54,20 @@ class Probe:
     `array` is computed on the device on first access: ifftshift(ifft2(mask)) for mrad > 0,
     real ones for mrad == 0 (quirk Q5).  A probe made by create_batched_probes() remembers its
     recipe (mrad, positions) so Propagate() can rebuild it on the device without a host copy.
+
+    aberrations (not in the reference): an aberrations.Aberrations; the analytic probe becomes
+    ifft2(mask * ramp * exp(-i chi(k))), evaluated on the device, and the recipe carries it through
+    create_batched_probes() and Propagate().  Aberrations(defocus=dz) is defocus(dz) of a fresh probe for dz > 0 (the opposite
+    sign of abTEM's defocus = -C10); a negative value is the conjugate phase, without quirk Q19.  A plane wave (mrad == 0) is
+    not changed (chi(0) = 0).  Not with `array`: a caller's array is used as it is.
     """
 
-    def __init__(self, xs, ys, mrad, eV, array=None, device=None):
+    def __init__(self, xs, ys, mrad, eV, array=None, device=None, aberrations=None):
+        if aberrations is not None and array is not None:
+            raise ValueError("aberrations apply to the analytic probe only, not to a caller-supplied array")
+        if aberrations is not None and not isinstance(aberrations, Aberrations):
+            raise ValueError(f"aberrations: expected an Aberrations object, got {aberrations!r}")
+        self.aberrations = aberrations
         self.device = device
         self.use_torch = TORCH_AVAILABLE
         self.xs = xs
@@ -87,6 +99,7 @@ class Probe:
         pos = [(0.0, 0.0)] if self._positions is None else self._positions
         eng = self._engine_for(len(pos))
         try:
+            eng.set_aberrations(self.aberrations)
             eng.set_probes(self.mrad, pos)
             a = eng.probes().astype(np.complex128)
         finally:
@@ -151,6 +164,7 @@ def create_batched_probes(base_probe, probe_positions, device=None):
     pos = [(float(px), float(py)) for px, py in probe_positions]
     out = Probe(base_probe.xs, base_probe.ys, base_probe.mrad, base_probe.eV, device=base_probe.device)
     if not base_probe._custom:
+        out.aberrations = base_probe.aberrations
         out._positions = pos
         return out
     base = _to_numpy(base_probe.array)
@@ -179,6 +193,7 @@ def Propagate(probe, potential, device=None):
     eng.set_beam(probe.wavelength, interaction_sigma(probe.eV), dz)
     eng.resize_probes(len(payload))
     if kind == "analytic":
+        eng.set_aberrations(probe.aberrations)     # always: the potential's engine is shared and the state stays on it
         eng.set_probes(probe.mrad, payload)
     else:
         if payload.shape[1:] != (eng.nx, eng.ny):

@@ -4,7 +4,12 @@ probe batch.  --detect-only times msl_detect alone on resident images and report
 --diffraction BX,BY adds the diffraction-pattern leg: with --detect-only msl_diffract alone on the same resident images, otherwise
 the scan through run_diffraction() (with --detectors 0 the patterns alone, else patterns and detectors in one pass).
     python tools/stem_bench.py [--scan 64] [--n 1024] [--slices 200] [--frames 1] [--probe-batch 64 256] [--detectors 8] [--diffraction 8,8]
-    python tools/stem_bench.py --detect-only [--images 256] [--n 1024] [--detectors 8] [--reps 20] [--diffraction 8,8]"""
+    python tools/stem_bench.py --detect-only [--images 256] [--n 1024] [--detectors 8] [--reps 20] [--diffraction 8,8]
+--aberrations runs the scan with an aberrated probe (all fourteen terms non-zero) for an A/B against the plain run in one session.
+--probes-only rebuilds --images probes, plain and aberrated in turn, --reps times each: the two probe kernels side by side for a
+kernel trace (rocprofv3 --kernel-trace --stats -- python tools/stem_bench.py --probes-only); the wall times it prints include the
+inverse FFT, the transposed copy and the synchronisation.
+    python tools/stem_bench.py --probes-only [--images 256] [--n 1024] [--reps 20]"""
 import argparse
 import json
 import os
@@ -31,6 +36,32 @@ def detectors(n):
             D("dpc3", outer=a, azimuth=(270, 360)), D("comx", signal="com_x"), D("comy", signal="com_y")]
     dets += [D(f"ring{i}", inner=10.0 * i, outer=10.0 * i + 10.0) for i in range(16)]
     return dets[:n]
+
+
+def all_aberrations():
+    """every term non-zero: Cs = 1 mm (344 rad at the edge of the 30 mrad aperture at 100 kV), -600 A of defocus (-46 rad), the
+    others 0.6 - 3 rad each"""
+    return ps.Aberrations(defocus=-600.0, astigmatism=40.0, astigmatism_angle=0.3, coma=900.0, coma_angle=1.1, C23=700.0, phi23=0.2,
+                          Cs=1e7, C32=2e4, phi32=0.5, C34=2e4, phi34=0.1, C41=8e5, phi41=2.0, C43=8e5, phi43=0.4, C45=8e5, phi45=0.3,
+                          C5=5e7, C52=3e7, phi52=1.0, C54=3e7, phi54=0.2, C56=3e7, phi56=0.1)
+
+
+def probes_only(args):
+    n, P = args.n, args.images
+    eng = _native.Engine(n, n, 1, 0.1, 0.1, 0.5, wavelength(100e3), 0.0, n_probes=P, n_frames=0)
+    xy = np.random.default_rng(3).random((P, 2)) * n * 0.1
+    ab = all_aberrations()
+    times = {"plain": [], "aberrated": []}
+    for rep in range(args.reps + 1):
+        for name, a in (("plain", None), ("aberrated", ab)):
+            eng.set_aberrations(a)
+            t0 = time.perf_counter()
+            eng.set_probes(30.0, xy)                      # synchronous
+            if rep:                                       # (the first round is the warm-up)
+                times[name].append(time.perf_counter() - t0)
+    print(json.dumps({"case": "probes_only", "probes": P, "grid": n, "reps": args.reps,
+                      "set_probes_ms_median": {k: round(1e3 * float(np.median(v)), 4) for k, v in times.items()}}), flush=True)
+    eng.close()
 
 
 def detect_only(args):
@@ -82,7 +113,8 @@ def scan(args, pb):
     if args.diffraction:
         scan_diffraction(args, pb, tr, pp, free0)
         return
-    calc = ps.MultisliceCalculator(progress=False, detectors=detectors(args.detectors), probe_batch=pb)
+    calc = ps.MultisliceCalculator(progress=False, detectors=detectors(args.detectors), probe_batch=pb,
+                                   aberrations=all_aberrations() if args.aberrations else None)
     calc.setup(tr, aperture=30.0, voltage_eV=100e3, probe_positions=pp)
     eng = calc._engine
     used = free0 - torch.cuda.mem_get_info()[0]
@@ -104,6 +136,7 @@ def scan(args, pb):
     steps = len(pp) * args.frames * args.slices
     print(json.dumps({"case": "scan", "scan": f"{s}x{s}", "grid": args.n, "slices": args.slices, "frames": args.frames,
                       "probe_batch": eng.n_probes, "frame_batch": eng.frame_batch, "detectors": len(st.detectors),
+                      "aberrations": bool(args.aberrations),
                       "s_total": round(dt, 3), "slice_steps_per_s": round(steps / dt),
                       "detect_ms_per_batch": round(1e3 * float(np.median(spent)), 4), "detect_share_pct": round(100.0 * sum(spent) / dt, 3),
                       "engine_buffer_bytes": buf, "device_bytes_after_setup": int(used),
@@ -116,7 +149,8 @@ def scan_diffraction(args, pb, tr, pp, free0):
     """the scan through run_diffraction(): slice-steps/s, the synchronous msl_diffract per batch, the host accumulate per batch"""
     import torch
     dets = detectors(args.detectors) if args.detectors > 0 else None
-    calc = ps.MultisliceCalculator(progress=False, diffraction=ps.Diffraction(bin=args.diffraction), detectors=dets, probe_batch=pb)
+    calc = ps.MultisliceCalculator(progress=False, diffraction=ps.Diffraction(bin=args.diffraction), detectors=dets, probe_batch=pb,
+                                   aberrations=all_aberrations() if args.aberrations else None)
     calc.setup(tr, aperture=30.0, voltage_eV=100e3, probe_positions=pp)
     eng = calc._engine
     used = free0 - torch.cuda.mem_get_info()[0]
@@ -141,7 +175,7 @@ def scan_diffraction(args, pb, tr, pp, free0):
         dd.intensity[:eng.n_probes] += block
         acc.append(time.perf_counter() - t1)
     print(json.dumps({"case": "scan_diffraction", "scan": f"{args.scan}x{args.scan}", "grid": args.n, "slices": args.slices, "frames": args.frames,
-                      "probe_batch": eng.n_probes, "frame_batch": eng.frame_batch, "bin": list(args.diffraction),
+                      "probe_batch": eng.n_probes, "frame_batch": eng.frame_batch, "bin": list(args.diffraction), "aberrations": bool(args.aberrations),
                       "detectors": 0 if dets is None else len(dets), "pattern_shape": list(dd.intensity.shape),
                       "s_total": round(dt, 3), "slice_steps_per_s": round(steps / dt),
                       "diffract_ms_per_batch": round(1e3 * float(np.median(spent)), 4), "diffract_share_pct": round(100.0 * sum(spent) / dt, 3),
@@ -168,7 +202,12 @@ def main():
     ap.add_argument("--images", type=int, default=256)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--diffraction", type=_bin, default=None, metavar="BX,BY")
+    ap.add_argument("--aberrations", action="store_true")
+    ap.add_argument("--probes-only", action="store_true")
     args = ap.parse_args()
+    if args.probes_only:
+        probes_only(args)
+        return
     if args.detect_only:
         detect_only(args)
         return
