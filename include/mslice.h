@@ -296,6 +296,26 @@ int  msl_detect(msl_handle* h, const void* d_src_c64, int64_t B, int64_t T, int6
 int  msl_diffract(msl_handle* h, const void* d_src_c64, int64_t B, int64_t T, int64_t K, int64_t ld, int32_t t0, int32_t count, int32_t wx, int32_t wy,
                   int32_t bx, int32_t by, double* out);
 
+/* ---- coherent frame sums: the elastic part |<Psi>|^2 of a frozen-phonon run, per probe batch ----
+ * The handle owns one accumulator, (B, pitch) float64 complex with pitch = msl_result_pitch's value (stored pixels rounded up to 32), 16 * pitch
+ * bytes per probe, freed with the handle.
+ * msl_coherent_reset: sizes the accumulator for B probes (B <= 0: n_probes; it only grows) and zeroes it on the handle's stream.
+ * msl_coherent_add: acc[b, k] += sum_{j<count} Psi[b, t0+j, k] for k < K, over a (B,T,K) complex64 array with row pitch ld.  Source
+ *   arguments as msl_detect: d_src == NULL is the handle's wavefunction buffer (B <= 0 means n_probes, a smaller B leaves the padded
+ *   probes out).  MSL_ERR_INVALID when ld < K, when [t0, t0+count) leaves [0, T), when B or K exceeds what the last reset sized (K > pitch)
+ *   or when K differs from the K of an earlier add since the reset.  One launch, queued on the stream (no wait); every complex value
+ *   read once and widened to float64 BEFORE it is added, the frames in order, no atomics: the sum does not depend on how the frames are
+ *   split over calls, and repeated sequences are bitwise equal.
+ * msl_coherent_finish: out[(b*mx + ix)*my + iy] = sum_{a<bx} sum_{c<by} |acc[b, (ix*bx+a)*wy + iy*by+c]|^2 / n^2, mx = wx/bx, my = wy/by:
+ *   with n = the number of frames added (n >= 1), |mean over the frames of Psi|^2 summed over every bx x by detector pixel -- the
+ *   coherent mean first, the bin adds intensities as msl_diffract's.  out is HOST memory, B*mx*my float64 (B <= 0: the B of the last
+ *   reset).  MSL_ERR_INVALID when bx does not divide wx or by not wy, when wx*wy is not the K of the adds, for n < 1 or B beyond the
+ *   last reset.  The accumulator is left as it is.
+ *   Not in the reference, which holds every frame: there the same numbers are |wavefunction_data.mean(frame axis)|^2. */
+int  msl_coherent_reset(msl_handle* h, int64_t B);
+int  msl_coherent_add(msl_handle* h, const void* d_src_c64, int64_t B, int64_t T, int64_t K, int64_t ld, int32_t t0, int32_t count);
+int  msl_coherent_finish(msl_handle* h, int64_t B, int32_t n, int32_t wx, int32_t wy, int32_t bx, int32_t by, double* out);
+
 /* ---- thickness series: spectra of intermediate layers of the stack ----
  * msl_set_layers: `n` strictly increasing slice indices k in [0, nz-1).  Layer k is the wave after the transmission of slice k and
  * before the propagation that follows it -- the exit wave of the stack cut after slice k.  Every fused slice loop then also writes

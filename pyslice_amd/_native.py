@@ -31,6 +31,7 @@ EXPORTS = [
     "msl_tacaw_stream_set_reference", "msl_tacaw_stream_finish_range",
     "msl_set_layers", "msl_download_layers_c128", "msl_tacaw_layer",
     "msl_set_detectors", "msl_detect", "msl_diffract",
+    "msl_coherent_reset", "msl_coherent_add", "msl_coherent_finish",
 ]
 DET_SIGNALS = {"intensity": 0, "amplitude": 1, "com_x": 2, "com_y": 3}      # include/mslice.h: MSL_DET_*
 
@@ -118,6 +119,9 @@ def load():
         "msl_set_detectors": (C.c_int, [vp, i32, vp, vp, vp, vp]),
         "msl_detect": (C.c_int, [vp, vp, i64, i64, i64, i64, i32, i32, vp]),
         "msl_diffract": (C.c_int, [vp, vp, i64, i64, i64, i64, i32, i32, i32, i32, i32, i32, vp]),
+        "msl_coherent_reset": (C.c_int, [vp, i64]),
+        "msl_coherent_add": (C.c_int, [vp, vp, i64, i64, i64, i64, i32, i32]),
+        "msl_coherent_finish": (C.c_int, [vp, i64, i32, i32, i32, i32, i32, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -496,6 +500,36 @@ class Engine:
         ok = bx > 0 and by > 0 and wx > 0 and wy > 0 and wx % bx == 0 and wy % by == 0       # (else the library refuses: no output is read)
         out = np.empty((max(b, 0), wx // bx, wy // by) if ok else (1,), dtype=np.float64)
         self._chk(self._lib.msl_diffract(self._h, p, b, T, wx * wy, ld, int(t0), count, wx, wy, bx, by, _ptr(out)))
+        return out
+
+    # -- coherent frame sums (msl_coherent_reset / msl_coherent_add / msl_coherent_finish)
+    def coherent_reset(self, B=None):
+        """size the handle's float64 complex accumulator for B probes (None: n_probes) and zero it"""
+        self._coherent_B = 0
+        self._chk(self._lib.msl_coherent_reset(self._h, int(B) if B else 0))
+        self._coherent_B = int(B) if B else self.n_probes
+
+    def coherent_add(self, t0=0, count=None, B=None, src=None):
+        """acc[b, k] += the sum of Psi[b, t, k] over the frame slots [t0, t0+count), every addend widened to float64 first.  Source
+        as detect(): None is the handle's own wavefunction buffer (B = n_probes or fewer: the first B probes); else (device
+        pointer, B, T, K[, ld]) of a caller's complex64 array.  Queued on the handle's stream."""
+        if src is None:
+            p, b, T, k, ld = None, int(B) if B else self.n_probes, self.n_frames, self.wx * self.wy, 0
+        else:
+            p, b, T, k, ld = self._src(src)
+        count = (T - int(t0)) if count is None else int(count)
+        self._chk(self._lib.msl_coherent_add(self._h, p, b, T, k, ld, int(t0), count))
+
+    def coherent_finish(self, n, B=None, bin=(1, 1), shape=None):
+        """(B, wx/bx, wy/by) float64: |acc / n|^2 summed over every bx x by block of pixels -- after n frames were added, the
+        elastic pattern |<Psi>|^2 on the detector pixels of diffract().  shape = (wx, wy) of the rows that were added (None: the
+        handle's stored spectrum); B = None: every probe of the last coherent_reset.  The accumulator is left as it is."""
+        bx, by = int(bin[0]), int(bin[1])
+        wx, wy = (self.wx, self.wy) if shape is None else (int(shape[0]), int(shape[1]))
+        b = int(B) if B else getattr(self, "_coherent_B", 0)
+        ok = bx > 0 and by > 0 and wx > 0 and wy > 0 and wx % bx == 0 and wy % by == 0       # (else the library refuses: no output is read)
+        out = np.empty((max(b, 0), wx // bx, wy // by) if ok and b > 0 else (1,), dtype=np.float64)
+        self._chk(self._lib.msl_coherent_finish(self._h, b, int(n), wx, wy, bx, by, _ptr(out)))
         return out
 
     # -- results

@@ -114,6 +114,8 @@ class MultisliceCalculator:
                    pattern of every probe position on a pixelated detector, (P, wx/bx, wy/by) float64 on the host.  Same
                    refusals as detectors (k_bin adds complex pixels, the bin here adds intensities); with detectors as well, one
                    propagation feeds both.  setup() raises ValueError when the bin does not divide the stored spectrum.
+                   Diffraction(bin, split=True) also returns the elastic part |<Psi>|^2 of every pattern (and the thermal
+                   diffuse rest), at the price of one potential build per probe batch and frame (run_diffraction).
           probe_batch probes per batch of run_detectors() / run_diffraction() (default: chosen in setup() from free device
                    memory, about 256 images per launch with the frame batch).  Needs detectors or diffraction.
           aberrations an aberrations.Aberrations: every probe of run(), run_streaming_tacaw(), run_detectors() and
@@ -398,7 +400,10 @@ class MultisliceCalculator:
                 free_b = None
             if free_b is not None:
                 tables = min(6e9, batch * len(trajectory.atom_types) * (nx // 2 + ny // 2 + 2) * 8.0)
-                while Pc > 1 and Pc * batch * (32.0 * nx * ny + 8.0 * pitch) + batch * 16.0 * n_slices * nx * ny + tables + 1e9 > 0.9 * free_b:
+                # (the split adds the coherent accumulator: 16 * pitch bytes per probe)
+                coh = 16.0 * pitch if self._diffraction is not None and self._diffraction.split else 0.0
+                while Pc > 1 and (Pc * batch * (32.0 * nx * ny + 8.0 * pitch) + Pc * coh + batch * 16.0 * n_slices * nx * ny + tables + 1e9
+                                  > 0.9 * free_b):
                     Pc = max(1, Pc // 2)
         while True:
             try:
@@ -459,6 +464,57 @@ class MultisliceCalculator:
         if bar is not None:
             bar.close()
 
+    def _frames_inside_loop(self, reduce_batch, finish_batch):
+        """The other loop order, for the elastic / thermal-diffuse split of run_diffraction(): probe batches outside, frame batches
+        inside, because |<Psi>|^2 needs the coherent sum over ALL frames of a probe while its accumulator (16 * pitch bytes per
+        probe) is on the device.  Per probe batch: set_probes once (a potential build leaves the probes alone), coherent_reset;
+        per frame batch inside it the potentials, the slice loop, reduce_batch(p0, real, s0, n) as in _probe_batch_loop and
+        coherent_add of the n new frames; then finish_batch(p0, real).  The price: the potentials of every frame are built once
+        per probe batch, ceil(P / Pc) times instead of once -- except when the whole trajectory is one frame batch, which is
+        built once before the probe loop."""
+        eng = self._engine
+        P, T = self.n_probes, self.n_frames
+        Pc, B = eng.n_probes, eng.frame_batch
+        pos = np.asarray(self.probe_positions, dtype=np.float64).reshape(-1, 2)
+        bar = None
+        if self._progress:
+            try:
+                from tqdm import tqdm
+                bar = tqdm(total=-(-P // Pc) * T, desc="Processing frames", unit="frame")
+            except ImportError:
+                bar = None
+
+        def build(s0, n):
+            if B > 1:
+                eng.build_potentials(self.trajectory.positions[s0:s0 + n], self._Z, self.slice_axis)
+            else:
+                eng.build_potential(self.trajectory.positions[s0], self._Z, self.slice_axis)
+        once = T <= B
+        if once:
+            build(0, T)
+        for p0 in range(0, P, Pc):
+            real = min(Pc, P - p0)
+            xy = pos[p0:p0 + real]
+            if real < Pc:                                      # last batch: pad by repeating its last position
+                xy = np.concatenate([xy, np.repeat(xy[-1:], Pc - real, axis=0)])
+            eng.set_probes(self.aperture, xy)
+            eng.coherent_reset()
+            for s0 in range(0, T, B):
+                n = min(B, T - s0)
+                if not once:
+                    build(s0, n)
+                if B > 1:
+                    eng.propagate_frames(0, n)
+                else:
+                    eng.propagate_frame(0)
+                reduce_batch(p0, real, s0, n)
+                eng.coherent_add(0, n, B=real)
+                if bar is not None:
+                    bar.update(n)
+            finish_batch(p0, real)
+        if bar is not None:
+            bar.close()
+
     def _stem_data(self, signals):
         from .stem_data import STEMData
         kxs, kys = self._k_axes()
@@ -472,7 +528,11 @@ class MultisliceCalculator:
         the pixels of each bin -- which is added into the host result and divided by the number of frames at the end.
         -> DiffractionData with intensity (P, mx, my) float64; with detectors as well, .stem is the STEMData run_detectors()
         returns, from the same propagation.  Device memory does not depend on the number of probe positions; the host holds
-        8 * P * mx * my bytes (537 MB for 64 x 64 positions x 128 x 128 detector pixels), which is not checked against anything."""
+        8 * P * mx * my bytes (537 MB for 64 x 64 positions x 128 x 128 detector pixels), which is not checked against anything.
+        With Diffraction(split=True) the result also carries `elastic`, |<Psi>|^2 summed over each bin (and .tds, .part()): the
+        run then takes the other loop order (_frames_inside_loop: probe batches outside, every frame of a probe added into a
+        float64 accumulator on the device), which builds the potentials of every frame once per probe batch instead of once, and
+        the host holds a second (P, mx, my) array.  intensity and stem are computed by the same calls as without the split."""
         from .diffraction_data import DiffractionData, bin_centres
         if self._diffraction is None:
             raise RuntimeError("run_diffraction() needs MultisliceCalculator(diffraction=Diffraction(...))")
@@ -489,14 +549,22 @@ class MultisliceCalculator:
             acc[p0:p0 + real] += eng.diffract(0, n, B=real, bin=(bx, by))
             if signals is not None:
                 signals[p0:p0 + real, s0:s0 + n] = eng.detect(0, n, B=real)
-        self._probe_batch_loop(reduce_batch)
+        elastic = None
+        if self._diffraction.split:
+            elastic = np.zeros_like(acc)
+
+            def finish_batch(p0, real):
+                elastic[p0:p0 + real] = eng.coherent_finish(T, B=real, bin=(bx, by))
+            self._frames_inside_loop(reduce_batch, finish_batch)
+        else:
+            self._probe_batch_loop(reduce_batch)
         acc /= T
         self.elapsed = time.time() - t0
         self.frames_computed, self.frames_cached = T, 0
         kxs, kys = self._k_axes()
         return DiffractionData(intensity=acc, kxs=_as_tensor(bin_centres(kxs, bx)), kys=_as_tensor(bin_centres(kys, by)), bin=(bx, by),
                                n_frames=T, probe_positions=self.probe_positions, probe=self.base_probe,
-                               stem=None if signals is None else self._stem_data(signals))
+                               stem=None if signals is None else self._stem_data(signals), elastic=elastic)
 
     def run_detectors(self):
         """STEM detector signals of every probe and frame: for each frame batch the potentials are built once, then every probe

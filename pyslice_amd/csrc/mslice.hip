@@ -23,6 +23,7 @@
 #include "layer_tap.h"
 #include "detect.h"
 #include "diffract.h"
+#include "coherent.h"
 
 using namespace msl;
 
@@ -179,6 +180,10 @@ struct msl_handle {
     uint32_t det_amp = 0, det_cx = 0, det_cy = 0;
     // diffraction patterns (msl_diffract): (B, mx, my) float64 staging, grown on demand
     DevBuf<double> diff_out;
+    // coherent frame sums (msl_coherent_reset / _add / _finish): (coh_B, wpitch) float64 complex, grown on demand; coh_K = the row
+    // length of the adds since the last reset (0: none yet)
+    DevBuf<double2> coh_acc;
+    int64_t coh_B = 0, coh_K = 0;
     DevBuf<double> d_abcd, d_lo, d_hi;
     bool have_kirkland = false, have_slices = false, have_probes = false, have_potential = false, have_exit = false;
     int frames_done = 0;
@@ -2672,6 +2677,77 @@ int msl_diffract(msl_handle* h, const void* d_src_c64, int64_t B, int64_t T, int
     if ((rc = mark_launch(h, K_OTHER))) return rc;
     h->ctr.algorithmic_bytes += 8ull * (uint64_t)K * (uint64_t)B * (uint64_t)count;
     HIPCHK(h, hipMemcpyAsync(out, h->diff_out, n_out * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return MSL_OK;
+}
+
+// ---- coherent frame sums (coherent.h) ---------------------------------------------------------------------
+int msl_coherent_reset(msl_handle* h, int64_t B) {
+    if (!h) return fail(h, MSL_ERR_INVALID, "msl_coherent_reset: null handle");
+    if (B < 1) B = h->cfg.n_probes;
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    h->coh_B = 0; h->coh_K = 0;
+    const size_t n = (size_t)B * h->wpitch;
+    int rc = h->coh_acc.reserve(h, n);
+    if (rc) return rc;
+    HIPCHK(h, hipMemsetAsync(h->coh_acc, 0, n * sizeof(double2), h->stream));
+    h->coh_B = B;
+    return MSL_OK;
+}
+
+int msl_coherent_add(msl_handle* h, const void* d_src_c64, int64_t B, int64_t T, int64_t K, int64_t ld, int32_t t0, int32_t count) {
+    if (!h) return fail(h, MSL_ERR_INVALID, "msl_coherent_add: null handle");
+    int rc = resident_wavefunction(h, "msl_coherent_add", &d_src_c64, &B, &T, &K, &ld);
+    if (rc) return rc;
+    if (B > h->coh_B || K > (int64_t)h->wpitch)
+        return fail(h, MSL_ERR_INVALID, "msl_coherent_add: %lld probes of %lld pixels, the last msl_coherent_reset sized %lld of up to %zu", (long long)B,
+                    (long long)K, (long long)h->coh_B, h->wpitch);
+    if (h->coh_K && K != h->coh_K)
+        return fail(h, MSL_ERR_INVALID, "msl_coherent_add: rows of %lld pixels after rows of %lld (msl_coherent_reset starts a new sum)", (long long)K,
+                    (long long)h->coh_K);
+    if (count < 1 || t0 < 0 || (int64_t)t0 + count > T)
+        return fail(h, MSL_ERR_INVALID, "msl_coherent_add: frame slots [%d,%d) outside [0,%lld)", t0, t0 + count, (long long)T);
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    // 16-byte loads need every image to start on 16 bytes and to end with a whole column pair
+    const bool vec = (ld % 2 == 0) && (K % 2 == 0) && (((uintptr_t)d_src_c64 & 15) == 0);
+    const int64_t lanes = vec ? K / 2 : K;
+    const dim3 grid((unsigned)((lanes + 255) / 256), (unsigned)std::min<int64_t>(B, 65535));
+    if ((rc = begin_timed(h, 1))) return rc;
+    const float2* src = (const float2*)d_src_c64;
+    if (vec) hipLaunchKernelGGL(coherent_add_kernel<true>, grid, dim3(256), 0, h->stream, src, (long long)B, (long long)T, (long long)t0, (int)count,
+                                (long long)ld, (long long)K, (long long)h->wpitch, h->coh_acc.p);
+    else hipLaunchKernelGGL(coherent_add_kernel<false>, grid, dim3(256), 0, h->stream, src, (long long)B, (long long)T, (long long)t0, (int)count,
+                            (long long)ld, (long long)K, (long long)h->wpitch, h->coh_acc.p);
+    HIPCHK(h, hipGetLastError());
+    if ((rc = mark_launch(h, K_OTHER))) return rc;
+    h->coh_K = K;
+    h->ctr.algorithmic_bytes += (uint64_t)K * (uint64_t)B * (8ull * (uint64_t)count + 32ull);
+    return MSL_OK;
+}
+
+int msl_coherent_finish(msl_handle* h, int64_t B, int32_t n, int32_t wx, int32_t wy, int32_t bx, int32_t by, double* out) {
+    if (!h || !out) return fail(h, MSL_ERR_INVALID, "msl_coherent_finish: null argument");
+    if (B < 1) B = h->coh_B;
+    if (B < 1 || B > h->coh_B) return fail(h, MSL_ERR_INVALID, "msl_coherent_finish: %lld probes, the last msl_coherent_reset sized %lld", (long long)B, (long long)h->coh_B);
+    if (n < 1) return fail(h, MSL_ERR_INVALID, "msl_coherent_finish: %d frames", n);
+    const int64_t K = (int64_t)wx * wy;
+    if (wx < 1 || wy < 1 || K > (int64_t)h->wpitch || (h->coh_K && K != h->coh_K))
+        return fail(h, MSL_ERR_INVALID, "msl_coherent_finish: window %d x %d over rows of %lld pixels", wx, wy, (long long)(h->coh_K ? h->coh_K : (int64_t)h->wpitch));
+    if (bx < 1 || by < 1 || wx % bx || wy % by) return fail(h, MSL_ERR_INVALID, "msl_coherent_finish: bin %d x %d does not divide the window %d x %d", bx, by, wx, wy);
+    if ((int64_t)bx * by > 0x7fffffffLL) return fail(h, MSL_ERR_UNSUPPORTED, "msl_coherent_finish: more than 2^31 pixels per bin");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    const int mx = wx / bx, my = wy / by;
+    const int64_t bins = B * mx * my;
+    int rc = h->diff_out.reserve(h, (size_t)bins);              // the staging of msl_diffract: both calls leave it read
+    if (rc) return rc;
+    int L = 1;                                                   // lanes per bin: the largest power of two <= min(64, bx * by)
+    while (L < 64 && 2 * (int64_t)L <= (int64_t)bx * by) L *= 2;
+    const int64_t blocks = (bins * L + 255) / 256;
+    if (blocks > 0x7fffffffLL) return fail(h, MSL_ERR_UNSUPPORTED, "msl_coherent_finish: too many detector pixels");
+    hipLaunchKernelGGL(coherent_finish_kernel, dim3((unsigned)blocks), dim3(256), 0, h->stream, h->coh_acc.p, (long long)h->wpitch, (long long)bins, (int)wy,
+                       mx, my, (int)bx, (int)by, L, (double)n * (double)n, h->diff_out.p);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(out, h->diff_out, (size_t)bins * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return MSL_OK;
 }

@@ -8,7 +8,7 @@ DiffractionData holds the (P, mx, my) frozen-phonon mean only, and everything be
 """
 from __future__ import annotations
 
-from dataclasses import dataclass
+from dataclasses import dataclass, replace
 from typing import Any, Optional, Tuple
 
 import numpy as np
@@ -17,19 +17,24 @@ from .stem_data import Detector, STEMData, scan_axes, scan_image
 
 
 class Diffraction:
-    """The request: bin=(bx, by) stored pixels per detector pixel along kx and ky (both must divide the stored spectrum)."""
+    """The request: bin=(bx, by) stored pixels per detector pixel along kx and ky (both must divide the stored spectrum);
+    split=True also asks for the elastic part |<Psi>|^2 of every pattern (DiffractionData.elastic / .tds), which costs one
+    potential build per probe batch and frame instead of one per frame (MultisliceCalculator.run_diffraction)."""
 
-    def __init__(self, bin=(1, 1)):
+    def __init__(self, bin=(1, 1), split=False):
         try:
             ok = len(bin) == 2 and all(isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_)) and int(v) >= 1 for v in bin)
         except TypeError:
             ok = False
         if not ok:
             raise ValueError(f"Diffraction: bin must be two positive integers (bx, by), got {bin!r}")
+        if not isinstance(split, (bool, np.bool_)):
+            raise ValueError(f"Diffraction: split must be True or False, got {split!r}")
         self.bin = (int(bin[0]), int(bin[1]))
+        self.split = bool(split)
 
     def __repr__(self):
-        return f"Diffraction(bin={self.bin})"
+        return f"Diffraction(bin={self.bin}, split=True)" if self.split else f"Diffraction(bin={self.bin})"
 
 
 def bin_centres(axis, b):
@@ -48,7 +53,10 @@ def _np(a):
 class DiffractionData:
     """Result of MultisliceCalculator.run_diffraction(): intensity (P, mx, my) float64 -- the mean over the n_frames MD frames of
     |Psi|^2 in detector pixel (ix, iy) at probe p --, the bin-centre axes kxs / kys (float32), the bin, the run's
-    probe_positions / probe / wavelength, the scan axes xs / ys, and `stem`: the STEMData of the same pass when the run had detectors."""
+    probe_positions / probe / wavelength, the scan axes xs / ys, and `stem`: the STEMData of the same pass when the run had detectors.
+    With Diffraction(split=True), `elastic` (P, mx, my) float64 is |<Psi>|^2 -- the coherent mean over the frames, squared, then
+    summed over the pixels of the bin (a bin adds intensities) --, `tds` the thermal diffuse rest, and part() gives either as a
+    DiffractionData of its own; `elastic` is None otherwise."""
     intensity: np.ndarray
     kxs: Any
     kys: Any
@@ -60,12 +68,34 @@ class DiffractionData:
     wavelength: Optional[float] = None      # Angstrom; None: the probe's
     xs: np.ndarray = None
     ys: np.ndarray = None
+    elastic: Optional[np.ndarray] = None
 
     def __post_init__(self):
+        if self.elastic is not None and np.shape(self.elastic) != np.shape(self.intensity):
+            raise ValueError(f"elastic has shape {np.shape(self.elastic)}, intensity {np.shape(self.intensity)}")
         if self.wavelength is None and self.probe is not None:
             self.wavelength = float(self.probe.wavelength)
         if self.xs is None or self.ys is None:
             self.xs, self.ys = scan_axes(self.probe_positions)
+
+    @property
+    def tds(self) -> np.ndarray:
+        """(P, mx, my): the thermal diffuse part <|Psi|^2> - |<Psi>|^2, the energy-integrated TACAW intensity divided by T^2.
+        Not clamped: where nothing is diffuse (one frame, no displacements) the float32 rounding of the pattern pass, about
+        1e-7 of the total per addend, can leave it that far below zero."""
+        if self.elastic is None:
+            raise ValueError("this DiffractionData has no elastic part: run with Diffraction(split=True)")
+        return self.intensity - self.elastic
+
+    def part(self, name: str) -> "DiffractionData":
+        """the DiffractionData whose intensity is the "total", "elastic" or "tds" part (axes, probes and stem shared; its own
+        `elastic` is None), so that pacbed(), virtual(), image() and pattern() work on each part"""
+        if name not in ("total", "elastic", "tds"):
+            raise ValueError(f"part: expected 'total', 'elastic' or 'tds', got {name!r}")
+        if self.elastic is None:
+            raise ValueError("this DiffractionData has no elastic part: run with Diffraction(split=True)")
+        arr = {"total": self.intensity, "elastic": self.elastic, "tds": None}[name]
+        return replace(self, intensity=self.tds if arr is None else arr, elastic=None)
 
     def pacbed(self) -> np.ndarray:
         """(mx, my): position-averaged pattern, the mean over the probes"""

@@ -5,6 +5,10 @@ probe batch.  --detect-only times msl_detect alone on resident images and report
 the scan through run_diffraction() (with --detectors 0 the patterns alone, else patterns and detectors in one pass).
     python tools/stem_bench.py [--scan 64] [--n 1024] [--slices 200] [--frames 1] [--probe-batch 64 256] [--detectors 8] [--diffraction 8,8]
     python tools/stem_bench.py --detect-only [--images 256] [--n 1024] [--detectors 8] [--reps 20] [--diffraction 8,8]
+--split (with --diffraction) adds the elastic / thermal-diffuse split: with --detect-only the coherent accumulation pass
+(msl_coherent_add, count = 1) alone on the same resident images, next to msl_diffract for a kernel trace of both in one run
+(--diffraction 1,1 is the yardstick of equal traffic per byte); otherwise the scan through run_diffraction() with
+Diffraction(split=True), whose JSON line also carries the time of the potential builds and of the coherent pass.
 --aberrations runs the scan with an aberrated probe (all fourteen terms non-zero) for an A/B against the plain run in one session.
 --probes-only rebuilds --images probes, plain and aberrated in turn, --reps times each: the two probe kernels side by side for a
 kernel trace (rocprofv3 --kernel-trace --stats -- python tools/stem_bench.py --probes-only); the wall times it prints include the
@@ -99,6 +103,19 @@ def detect_only(args):
         print(json.dumps({"case": "diffract_only", "images": B, "grid": n, "bin": [bx, by], "ms_median_with_copy": round(dt * 1e3, 4),
                           "ms_min_with_copy": round(min(times) * 1e3, 4), "bytes_read": nbytes, "bytes_copied_back": B * (n // bx) * (n // by) * 8}),
               flush=True)
+    if args.diffraction and args.split:
+        eng.coherent_reset(B)                             # (B, pitch) float64 complex: 16 B per pixel
+        eng.coherent_add(src=src)                         # warm-up
+        eng.synchronize()
+        times = []
+        for _ in range(args.reps):
+            t0 = time.perf_counter()
+            eng.coherent_add(src=src)                     # one launch, queued: the wait is ours
+            eng.synchronize()
+            times.append(time.perf_counter() - t0)
+        dt = float(np.median(times))
+        print(json.dumps({"case": "coherent_add_only", "images": B, "grid": n, "count": 1, "ms_median": round(dt * 1e3, 4),
+                          "ms_min": round(min(times) * 1e3, 4), "bytes_moved": 5 * nbytes, "GB_per_s": round(5 * nbytes / dt / 1e9, 1)}), flush=True)
     eng.close()
 
 
@@ -149,7 +166,7 @@ def scan_diffraction(args, pb, tr, pp, free0):
     """the scan through run_diffraction(): slice-steps/s, the synchronous msl_diffract per batch, the host accumulate per batch"""
     import torch
     dets = detectors(args.detectors) if args.detectors > 0 else None
-    calc = ps.MultisliceCalculator(progress=False, diffraction=ps.Diffraction(bin=args.diffraction), detectors=dets, probe_batch=pb,
+    calc = ps.MultisliceCalculator(progress=False, diffraction=ps.Diffraction(bin=args.diffraction, split=args.split), detectors=dets, probe_batch=pb,
                                    aberrations=all_aberrations() if args.aberrations else None)
     calc.setup(tr, aperture=30.0, voltage_eV=100e3, probe_positions=pp)
     eng = calc._engine
@@ -164,6 +181,21 @@ def scan_diffraction(args, pb, tr, pp, free0):
         spent.append(time.perf_counter() - t0)
         return out
     eng.diffract = timed
+    # the potential builds and the coherent pass, each between two waits of its own (a handful per probe batch)
+    built, added = [], []
+
+    def between_waits(fn, into):
+        def call(*a, **k):
+            eng.synchronize()
+            t1 = time.perf_counter()
+            out = fn(*a, **k)
+            eng.synchronize()
+            into.append(time.perf_counter() - t1)
+            return out
+        return call
+    eng.build_potential = between_waits(eng.build_potential, built)
+    eng.build_potentials = between_waits(eng.build_potentials, built)
+    eng.coherent_add = between_waits(eng.coherent_add, added)
     t0 = time.perf_counter()
     dd = calc.run_diffraction()
     dt = time.perf_counter() - t0
@@ -180,6 +212,10 @@ def scan_diffraction(args, pb, tr, pp, free0):
                       "s_total": round(dt, 3), "slice_steps_per_s": round(steps / dt),
                       "diffract_ms_per_batch": round(1e3 * float(np.median(spent)), 4), "diffract_share_pct": round(100.0 * sum(spent) / dt, 3),
                       "accumulate_ms_per_batch": round(1e3 * float(np.median(acc)), 4), "host_result_bytes": int(dd.intensity.nbytes),
+                      "split": bool(args.split), "potential_builds": len(built), "potential_ms_per_build": round(1e3 * float(np.median(built)), 3),
+                      "potential_share_pct": round(100.0 * sum(built) / dt, 3), "coherent_add_calls": len(added),
+                      "coherent_add_ms_per_call": round(1e3 * float(np.median(added)), 4) if added else None,
+                      "coherent_add_share_pct": round(100.0 * sum(added) / dt, 3),
                       "device_bytes_after_setup": int(used)}), flush=True)
     calc._engine = None
     eng.close()
@@ -202,9 +238,12 @@ def main():
     ap.add_argument("--images", type=int, default=256)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--diffraction", type=_bin, default=None, metavar="BX,BY")
+    ap.add_argument("--split", action="store_true")
     ap.add_argument("--aberrations", action="store_true")
     ap.add_argument("--probes-only", action="store_true")
     args = ap.parse_args()
+    if args.split and not args.diffraction:
+        ap.error("--split needs --diffraction BX,BY")
     if args.probes_only:
         probes_only(args)
         return
