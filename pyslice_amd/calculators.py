@@ -78,6 +78,48 @@ def _widen_to_host(view, chunk_bytes=1 << 30):
     return out
 
 
+def _free_device_bytes(dev):
+    """free memory of the device in bytes, or None when torch or a device is not there (then the library's allocations decide)"""
+    if not (TORCH_AVAILABLE and torch.cuda.is_available()):
+        return None
+    try:
+        return float(torch.cuda.mem_get_info(_device_index(dev))[0])
+    except Exception:                                      # pragma: no cover  (no device visible to torch)
+        return None
+
+
+def _positive_pair(name, value, what, cache):
+    """k_window / k_bin: None, or two positive integers (not with the frame cache)"""
+    if value is None:
+        return None
+    if len(value) != 2 or int(value[0]) < 1 or int(value[1]) < 1:
+        raise ValueError(f"{name} must be two positive pixel counts {what}")
+    if cache:
+        raise ValueError(f"the frame cache stores full (P,nx,ny,1,1) frames: cache=True cannot be combined with {name}")
+    return (int(value[0]), int(value[1]))
+
+
+class _Progress:
+    """the tqdm bar over `total` frames; nothing when it is switched off or tqdm is not installed"""
+
+    def __init__(self, on, total):
+        self._bar = None
+        if on:
+            try:
+                from tqdm import tqdm
+                self._bar = tqdm(total=total, desc="Processing frames", unit="frame")
+            except ImportError:
+                pass
+
+    def update(self, n):
+        if self._bar is not None:
+            self._bar.update(n)
+
+    def close(self):
+        if self._bar is not None:
+            self._bar.close()
+
+
 class MultisliceCalculator:
 
     def __init__(self, device=None, force_cpu=False, *, output="host", dtype="complex128", progress=True,
@@ -135,20 +177,8 @@ class MultisliceCalculator:
         self.device = device
         self._output, self._dtype, self._progress, self._gather = output, dtype, progress, gather
         self._cache = bool(cache)
-        if k_window is not None:
-            if len(k_window) != 2 or int(k_window[0]) < 1 or int(k_window[1]) < 1:
-                raise ValueError("k_window must be two positive pixel counts (wx, wy)")
-            if cache:
-                raise ValueError("the frame cache stores full (P,nx,ny,1,1) frames: cache=True cannot be combined with k_window")
-            k_window = (int(k_window[0]), int(k_window[1]))
-        self._k_window = k_window
-        if k_bin is not None:
-            if len(k_bin) != 2 or int(k_bin[0]) < 1 or int(k_bin[1]) < 1:
-                raise ValueError("k_bin must be two positive pixel counts (bx, by)")
-            if cache:
-                raise ValueError("the frame cache stores full (P,nx,ny,1,1) frames: cache=True cannot be combined with k_bin")
-            k_bin = (int(k_bin[0]), int(k_bin[1]))
-        self._k_bin = k_bin
+        self._k_window = k_window = _positive_pair("k_window", k_window, "(wx, wy)", cache)
+        self._k_bin = k_bin = _positive_pair("k_bin", k_bin, "(bx, by)", cache)
         if stream_tile is not None and int(stream_tile) < 1:
             raise ValueError("stream_tile must be a positive frame count")
         if stream_tile is not None and cache:
@@ -168,25 +198,22 @@ class MultisliceCalculator:
             raise ValueError("probe_batch applies to detector and diffraction runs only: give detectors=[...] or diffraction=Diffraction(...)")
         if probe_batch is not None and int(probe_batch) < 1:
             raise ValueError("probe_batch must be a positive probe count")
-        if detectors is not None:
-            from .stem_data import check_detectors
-            for what, val in (("cache", cache), ("layers", layers is not None), ("stream_tile", stream_tile is not None),
-                              ("k_bin", k_bin is not None)):
-                if val:
-                    raise ValueError(f"detectors cannot be combined with {what}" +
-                                     (" (a bin sums complex pixels: |Psi|^2 of a bin is no detector signal)" if what == "k_bin" else ""))
-            detectors = check_detectors(detectors)
-        self._detectors = detectors
         if diffraction is not None:
             from .diffraction_data import Diffraction
             if not isinstance(diffraction, Diffraction):
                 raise ValueError(f"diffraction: expected a Diffraction object, got {diffraction!r}")
+        # the probe-batch modes keep one probe batch x one frame batch of full complex spectra on the device, and nothing else
+        for mode, given, why_not_k_bin in (
+                ("detectors", detectors, " (a bin sums complex pixels: |Psi|^2 of a bin is no detector signal)"),
+                ("diffraction", diffraction, " (a bin sums complex pixels; Diffraction(bin=...) sums their intensities)")):
             for what, val in (("cache", cache), ("layers", layers is not None), ("stream_tile", stream_tile is not None),
                               ("k_bin", k_bin is not None)):
-                if val:
-                    raise ValueError(f"diffraction cannot be combined with {what}" +
-                                     (" (a bin sums complex pixels; Diffraction(bin=...) sums their intensities)" if what == "k_bin" else ""))
-        self._diffraction = diffraction
+                if given is not None and val:
+                    raise ValueError(f"{mode} cannot be combined with {what}" + (why_not_k_bin if what == "k_bin" else ""))
+        if detectors is not None:
+            from .stem_data import check_detectors
+            detectors = check_detectors(detectors)
+        self._detectors, self._diffraction = detectors, diffraction
         if aberrations is not None and not isinstance(aberrations, Aberrations):
             raise ValueError(f"aberrations: expected an Aberrations object, got {aberrations!r}")
         self._aberrations = aberrations
@@ -261,43 +288,16 @@ class MultisliceCalculator:
 
         if self.probe_positions is None:
             self.probe_positions = [(lx / 2, ly / 2)]
-        if self._detectors is not None or self._diffraction is not None:
-            # probe-batch runs: every check on the host first, then an engine of Pc <= P probes x one frame batch of result slots
-            self._rank, self._world = distributed.rank_world()
-            if self._world > 1:
-                mode = "detectors" if self._detectors is not None else "diffraction"
-                raise NotImplementedError(f"{mode}: runs over several ranks are not supported (run_detectors() / run_diffraction() are "
-                                          "single-process)")
-            if self._diffraction is not None:
-                wx, wy = self._k_window if self._k_window is not None else (nx, ny)
-                bx, by = self._diffraction.bin
-                if wx % bx or wy % by:
-                    raise ValueError(f"the stored spectrum {wx} x {wy} is not a multiple of the diffraction bin {bx} x {by}")
-            if self._detectors is not None:
-                self._setup_detectors(trajectory, slice_axis)
-            else:
-                self._setup_probe_batches(trajectory, slice_axis)
-            return
-        self.base_probe = Probe(xs, ys, self.aperture, self.voltage_eV, device=self.device, aberrations=self._aberrations)
-
-        self.n_frames = trajectory.n_frames
-        self.n_probes = len(self.probe_positions)
-        self.wavefunction_data = None           # filled by run(); the device holds (P,T_local,nx,ny) meanwhile
-
-        # frame shard of this rank (contiguous block) and the device that serves it
         self._rank, self._world = distributed.rank_world()
+        if self._detectors is not None or self._diffraction is not None:
+            self._setup_probe_batches(trajectory, slice_axis)
+            return
+        n_slices = self._setup_run(trajectory, slice_axis)
+        # frame shard of this rank (contiguous block) and the device that serves it
         self._frames = distributed.shard_frames(self.n_frames, self._world, self._rank)
         dev = self.device
         if dev is None and self._world > 1:
             dev = int(os.environ.get("LOCAL_RANK", self._rank))
-        # slice coordinates follow the slice axis (potentials.py:241-245); the Fresnel step uses zs (multislice.py:266)
-        slice_coords = np.asarray([xs, ys, zs][slice_axis], dtype=np.float64)
-        n_slices = len(slice_coords)
-        dz = zs[1] - zs[0] if nz > 1 else 0.5
-        # A previous run's WFData (and zero-copy device views of its buffers) may still hold the old engine: drop our
-        # reference and let the last owner free it, instead of closing it under them.  (A caller that keeps an earlier result
-        # and only needs its host arrays frees the device side with result.release().)
-        self._engine = None
         batch = self._frame_batch
         if batch is None:
             batch = default_frame_batch(self.n_probes, n_slices, nx, ny)
@@ -307,162 +307,205 @@ class MultisliceCalculator:
             slots = max(1, min(self._stream_tile, slots))
             batch = min(batch, slots)
         if self._k_bin is not None:
-            wx, wy = self._k_window if self._k_window is not None else (nx, ny)
+            wx, wy = self._stored_window()
             if wx % self._k_bin[0] or wy % self._k_bin[1]:
                 raise ValueError(f"the stored spectrum {wx} x {wy} is not a multiple of k_bin {self._k_bin}")
-        # Headroom for what is allocated AFTER the engine exists: the phase tables of a frame group (up to 6 GB), the TACAW
-        # intensity array (4 B per stored complex value), the streaming accumulators.  A default batch that passes msl_create
-        # could otherwise run out of memory in the middle of a run (an explicit frame_batch is honoured as is).
-        if self._frame_batch is None and batch > 1 and TORCH_AVAILABLE and torch.cuda.is_available():
-            try:
-                free_b = float(torch.cuda.mem_get_info(_device_index(dev))[0])
-            except Exception:                              # pragma: no cover  (no device visible to torch: msl_create decides)
-                free_b = None
+        if self._frame_batch is None and batch > 1:            # (an explicit frame_batch is honoured as is)
+            free_b = _free_device_bytes(dev)
             if free_b is not None:
-                wx, wy = self._k_window if self._k_window is not None else (nx, ny)
-                bx, by = self._k_bin if self._k_bin is not None else (1, 1)
-                stored = float(self.n_probes) * slots * (wx // bx) * (wy // by)
-                n_atoms = len(trajectory.atom_types)
-                tables = min(6e9, batch * n_atoms * (nx // 2 + ny // 2 + 2) * 8.0)
-                later = tables + 4.0 * stored + (24.0 * stored / slots if self._stream_tile is not None else 0.0)
-                fixed = 8.0 * stored * len(self._layers) + later + 2e9        # (one result block per layer)
-                per_frame = 16.0 * n_slices * nx * ny + 24.0 * nx * ny * self.n_probes
-                while batch > 1 and fixed + batch * per_frame > 0.95 * free_b:
-                    batch = max(1, batch // 2)
-        self._check_layer_memory(dev, nx, ny, slots)
+                batch = self._fit_frame_batch(free_b, batch, slots)
+        self._check_layer_memory(dev, slots)
+
         # The frame batch costs batch x (two orientations of the transmission stack + three work buffers): when the device cannot
         # hold it next to the (P, T_local, wx, wy) result -- a result near capacity, a shared or smaller GPU -- halve it down to one
         # frame per launch sequence instead of failing a run that fits without batching (an explicit frame_batch is honoured as is)
-        while True:
-            try:
-                self._engine = _native.Engine(nx, ny, n_slices, self.dx, self.dy, dz, wavelength(voltage_eV),
-                                              interaction_sigma(voltage_eV), n_probes=self.n_probes,
-                                              n_frames=slots, device=_device_index(dev),
-                                              window=self._k_window, frame_batch=batch, k_bin=self._k_bin)
-                break
-            except MemoryError:
-                if self._frame_batch is not None or batch <= 1:
-                    raise
-                batch = max(1, batch // 2)
-                if self._stream_tile is not None:
-                    batch = min(batch, slots)
-                logger.info(f"device memory: frame batch reduced to {batch}")
+        def shrink(n_probes, slots, batch):
+            if self._frame_batch is not None or batch <= 1:
+                return None
+            batch = max(1, batch // 2)
+            if self._stream_tile is not None:
+                batch = min(batch, slots)
+            logger.info(f"device memory: frame batch reduced to {batch}")
+            return n_probes, slots, batch
+        self._create_engine(self.n_probes, slots, batch, shrink, device=_device_index(dev), k_bin=self._k_bin)
         if len(self._layers) > 1:
             self._engine.set_layers(self._layers[:-1])
-        self._engine.set_kirkland(loadKirkland())
-        lo, hi = slice_edges(slice_coords)
-        self._engine.set_slices(lo, hi)
-        self._engine.set_aberrations(self._aberrations)
+        self._configure_engine()
         self._engine.set_probes(self.aperture, np.asarray(self.probe_positions, dtype=np.float64))
-        self._Z = np.asarray(trajectory.atom_types, dtype=np.int32)
-
-    def _setup_detectors(self, trajectory, slice_axis):
-        """setup() of a detector run: the memberships on the host, then the probe-batch engine, then the memberships onto it"""
-        from .stem_data import detector_bitmask
-        lam = wavelength(self.voltage_eV)
-        kxs, kys = self._k_axes()
-        bits = detector_bitmask(self._detectors, kxs, kys, lam)
-        for d, det in enumerate(self._detectors):
-            if not ((bits >> d) & 1).any():
-                raise ValueError(f"detector {det.name!r} contains no stored pixel of the {len(kxs)} x {len(kys)} spectrum")
-        self._det_bits = bits
-        self._setup_probe_batches(trajectory, slice_axis)
-        self._engine.set_detectors(bits.reshape(-1), [d.signal for d in self._detectors], kxs, kys)
 
     def _setup_probe_batches(self, trajectory, slice_axis):
-        """the engine of a run that streams probe batches (detectors, diffraction): Pc <= P probes x one frame batch of slots"""
-        nx, ny = self.nx, self.ny
-        lam = wavelength(self.voltage_eV)
+        """setup() of a run that streams probe batches (detectors, diffraction): every check on the host first, then an engine of
+        Pc <= P probes x one frame batch of result slots, then the detector memberships onto it"""
+        if self._world > 1:
+            mode = "detectors" if self._detectors is not None else "diffraction"
+            raise NotImplementedError(f"{mode}: runs over several ranks are not supported (run_detectors() / run_diffraction() are "
+                                      "single-process)")
+        if self._diffraction is not None:
+            wx, wy = self._stored_window()
+            bx, by = self._diffraction.bin
+            if wx % bx or wy % by:
+                raise ValueError(f"the stored spectrum {wx} x {wy} is not a multiple of the diffraction bin {bx} x {by}")
+        if self._detectors is not None:
+            from .stem_data import detector_bitmask
+            kxs, kys = self._k_axes()
+            bits = detector_bitmask(self._detectors, kxs, kys, wavelength(self.voltage_eV))
+            for d, det in enumerate(self._detectors):
+                if not ((bits >> d) & 1).any():
+                    raise ValueError(f"detector {det.name!r} contains no stored pixel of the {len(kxs)} x {len(kys)} spectrum")
+            self._det_bits = bits
+        n_slices = self._setup_run(trajectory, slice_axis)
+        self._frames = list(range(self.n_frames))
+        # Pc x frame batch near the ~256 images per launch of default_frame_batch: 256 probes x 1 frame for a scan, all probes x
+        # ceil(256 / P) frames for a few (an explicit probe_batch is honoured as is)
+        auto = self._probe_batch is None
+        Pc = min(self.n_probes, 256 if auto else self._probe_batch)
+        batch = self._frame_batch if self._frame_batch is not None else default_frame_batch(Pc, n_slices, self.nx, self.ny)
+        batch = max(1, min(batch, self.n_frames))
+        free_b = _free_device_bytes(self.device) if auto else None
+        if free_b is not None:
+            Pc = self._fit_probe_batch(free_b, Pc, batch)
+
+        def shrink(Pc, slots, batch):                           # the probe batch first, then the frame batch and with it the ring
+            if not auto or (Pc <= 1 and batch <= 1):
+                return None
+            if Pc > 1:
+                Pc = max(1, Pc // 2)
+            else:
+                batch = max(1, batch // 2)
+            logger.info(f"device memory: probe batch {Pc}, frame batch {batch}")
+            return Pc, batch, batch
+        self._create_engine(Pc, batch, batch, shrink, device=_device_index(self.device))
+        self.probe_batch = self._engine.n_probes
+        self._configure_engine()                                # (the aberrations are read by the set_probes of every probe batch)
+        if self._detectors is not None:
+            self._engine.set_detectors(bits.reshape(-1), [d.signal for d in self._detectors], kxs, kys)
+
+    def _setup_run(self, trajectory, slice_axis):
+        """what every engine set-up takes from the trajectory and the slice axis, stored once -> the number of slices"""
         self.base_probe = Probe(self.xs, self.ys, self.aperture, self.voltage_eV, device=self.device, aberrations=self._aberrations)
         self.n_frames = trajectory.n_frames
         self.n_probes = len(self.probe_positions)
-        self.wavefunction_data = None
-        self._frames = list(range(self.n_frames))
-        dev = self.device
-        slice_coords = np.asarray([self.xs, self.ys, self.zs][slice_axis], dtype=np.float64)
-        n_slices = len(slice_coords)
-        dz = self.zs[1] - self.zs[0] if self.nz > 1 else 0.5
+        self.wavefunction_data = None           # filled by run(); the device holds (P,T_local,nx,ny) meanwhile
+        # slice coordinates follow the slice axis (potentials.py:241-245); the Fresnel step uses zs (multislice.py:266)
+        self._slice_coords = np.asarray([self.xs, self.ys, self.zs][slice_axis], dtype=np.float64)
+        self._dz = self.zs[1] - self.zs[0] if self.nz > 1 else 0.5
+        self._Z = np.asarray(trajectory.atom_types, dtype=np.int32)
+        # A previous run's WFData (and zero-copy device views of its buffers) may still hold the old engine: drop our
+        # reference and let the last owner free it, instead of closing it under them.  (A caller that keeps an earlier result
+        # and only needs its host arrays frees the device side with result.release().)
         self._engine = None
-        P, T = self.n_probes, self.n_frames
-        wx, wy = self._k_window if self._k_window is not None else (nx, ny)
-        pitch = (wx * wy + 31) // 32 * 32
-        # Pc x frame batch near the ~256 images per launch of default_frame_batch: 256 probes x 1 frame for a scan, all probes x
-        # ceil(256 / P) frames for a few; halved while the three work buffers and the result ring of Pc x B images, the B
-        # transmission stacks and the phase tables (up to 6 GB) do not fit in 0.9 x the free device memory
-        Pc = min(P, self._probe_batch if self._probe_batch is not None else 256)
-        batch = self._frame_batch if self._frame_batch is not None else default_frame_batch(Pc, n_slices, nx, ny)
-        batch = max(1, min(batch, T))
-        auto = self._probe_batch is None
-        if auto and TORCH_AVAILABLE and torch.cuda.is_available():
-            try:
-                free_b = float(torch.cuda.mem_get_info(_device_index(dev))[0])
-            except Exception:                              # pragma: no cover  (no device visible to torch: msl_create decides)
-                free_b = None
-            if free_b is not None:
-                tables = min(6e9, batch * len(trajectory.atom_types) * (nx // 2 + ny // 2 + 2) * 8.0)
-                # (the split adds the coherent accumulator: 16 * pitch bytes per probe)
-                coh = 16.0 * pitch if self._diffraction is not None and self._diffraction.split else 0.0
-                while Pc > 1 and (Pc * batch * (32.0 * nx * ny + 8.0 * pitch) + Pc * coh + batch * 16.0 * n_slices * nx * ny + tables + 1e9
-                                  > 0.9 * free_b):
-                    Pc = max(1, Pc // 2)
+        return len(self._slice_coords)
+
+    def _stored_window(self):
+        """(wx, wy) of the spectrum kept of every exit wave: the k-window, or the grid"""
+        return self._k_window if self._k_window is not None else (self.nx, self.ny)
+
+    def _stored_shape(self):
+        """(sx, sy, pitch): the stored window divided by the detector bin, and the pixels between two images of the result (whole
+        lines of 32)"""
+        wx, wy = self._stored_window()
+        bx, by = self._k_bin if self._k_bin is not None else (1, 1)
+        return wx // bx, wy // by, ((wx // bx) * (wy // by) + 31) // 32 * 32
+
+    def _phase_table_bytes(self, batch):
+        """the phase tables of a frame group, allocated by the first potential build: up to 6 GB"""
+        return min(6e9, batch * len(self.trajectory.atom_types) * (self.nx // 2 + self.ny // 2 + 2) * 8.0)
+
+    def _fit_frame_batch(self, free_b, batch, slots):
+        """Resident and streaming-TACAW runs: the default frame batch, halved while the result, the batch and what is allocated
+        AFTER the engine exists -- the phase tables, the TACAW intensity array (4 B per stored complex value), the streaming
+        accumulators -- exceed 0.95 x the free device memory.  A default batch that passes msl_create could otherwise run out of
+        memory in the middle of a run."""
+        nx, ny, n_slices = self.nx, self.ny, len(self._slice_coords)
+        sx, sy, _ = self._stored_shape()
+        stored = float(self.n_probes) * slots * sx * sy
+        later = self._phase_table_bytes(batch) + 4.0 * stored + (24.0 * stored / slots if self._stream_tile is not None else 0.0)
+        fixed = 8.0 * stored * len(self._layers) + later + 2e9        # (one result block per layer)
+        per_frame = 16.0 * n_slices * nx * ny + 24.0 * nx * ny * self.n_probes
+        while batch > 1 and fixed + batch * per_frame > 0.95 * free_b:
+            batch = max(1, batch // 2)
+        return batch
+
+    def _fit_probe_batch(self, free_b, Pc, batch):
+        """Probe-batch runs: the default probe batch, halved while the three work buffers and the result ring of Pc x batch images,
+        the coherent accumulator of a split run (16 * pitch bytes per probe), the transmission stacks of the batch and the phase
+        tables exceed 0.9 x the free device memory."""
+        nx, ny, n_slices = self.nx, self.ny, len(self._slice_coords)
+        pitch = self._stored_shape()[2]
+        tables = self._phase_table_bytes(batch)
+        coh = 16.0 * pitch if self._diffraction is not None and self._diffraction.split else 0.0
+        while Pc > 1 and (Pc * batch * (32.0 * nx * ny + 8.0 * pitch) + Pc * coh + batch * 16.0 * n_slices * nx * ny + tables + 1e9
+                          > 0.9 * free_b):
+            Pc = max(1, Pc // 2)
+        return Pc
+
+    def _create_engine(self, n_probes, slots, batch, shrink, **engine_kw):
+        """The engine of n_probes probes x slots result slots at a frame batch.  When the device cannot hold it,
+        shrink(n_probes, slots, batch) names the next smaller one to try, or None to give up."""
         while True:
             try:
-                self._engine = _native.Engine(nx, ny, n_slices, self.dx, self.dy, dz, lam, interaction_sigma(self.voltage_eV),
-                                              n_probes=Pc, n_frames=batch, device=_device_index(dev), window=self._k_window,
-                                              frame_batch=batch)
-                break
+                self._engine = _native.Engine(self.nx, self.ny, len(self._slice_coords), self.dx, self.dy, self._dz,
+                                              wavelength(self.voltage_eV), interaction_sigma(self.voltage_eV), n_probes=n_probes,
+                                              n_frames=slots, window=self._k_window, frame_batch=batch, **engine_kw)
+                return
             except MemoryError:
-                if not auto or (Pc <= 1 and batch <= 1):
+                smaller = shrink(n_probes, slots, batch)
+                if smaller is None:
                     raise
-                if Pc > 1:
-                    Pc = max(1, Pc // 2)
-                else:
-                    batch = max(1, batch // 2)
-                logger.info(f"device memory: probe batch {Pc}, frame batch {batch}")
-        self.probe_batch = Pc
-        self._engine.set_kirkland(loadKirkland())
-        lo, hi = slice_edges(slice_coords)
-        self._engine.set_slices(lo, hi)
-        self._engine.set_aberrations(self._aberrations)         # read by the set_probes of every probe batch
-        self._Z = np.asarray(trajectory.atom_types, dtype=np.int32)
+                n_probes, slots, batch = smaller
+
+    def _configure_engine(self):
+        eng = self._engine
+        eng.set_kirkland(loadKirkland())
+        eng.set_slices(*slice_edges(self._slice_coords))
+        eng.set_aberrations(self._aberrations)
+
+    def _build_and_propagate(self, first_frame, n, first_slot, build=True, propagate=True):
+        """The potentials of MD frames first_frame .. first_frame+n-1 into the batch slots, then the slice loop of every probe
+        through them into result slots first_slot ..; the engine's singular calls at a frame batch of 1.  The probe-batch loops
+        take the two halves apart: one build, one slice loop per probe batch."""
+        eng, positions = self._engine, self.trajectory.positions
+        if eng.frame_batch > 1:
+            if build:
+                eng.build_potentials(positions[first_frame:first_frame + n], self._Z, self.slice_axis)
+            if propagate:
+                eng.propagate_frames(first_slot, n)
+        else:
+            if build:
+                eng.build_potential(positions[first_frame], self._Z, self.slice_axis)
+            if propagate:
+                eng.propagate_frame(first_slot)
+
+    def _frame_batches(self):
+        """(s0, n) per frame batch of a probe-batch run: frames s0 .. s0+n-1 go into frame slots 0 .. n-1"""
+        B = self._engine.frame_batch
+        return [(s0, min(B, self.n_frames - s0)) for s0 in range(0, self.n_frames, B)]
+
+    def _probe_batches(self):
+        """(p0, real, xy) per probe batch: probes p0 .. p0+real-1, and their positions padded to the engine's probe count by
+        repeating the last one"""
+        Pc = self._engine.n_probes
+        pos = np.asarray(self.probe_positions, dtype=np.float64).reshape(-1, 2)
+        for p0 in range(0, self.n_probes, Pc):
+            xy = pos[p0:p0 + Pc]
+            real = len(xy)
+            if real < Pc:
+                xy = np.concatenate([xy, np.repeat(xy[-1:], Pc - real, axis=0)])
+            yield p0, real, xy
 
     def _probe_batch_loop(self, reduce_batch):
         """The pass of run_detectors() / run_diffraction(): frame batches outside (the potentials of a batch are built once), probe
-        batches inside (the last one padded by repeating its last position); after the slice loop of each,
-        reduce_batch(p0, real, s0, n) reads the engine's result ring: probes p0 .. p0+real-1 in its first `real` rows, frames
-        s0 .. s0+n-1 in frame slots 0 .. n-1."""
-        eng = self._engine
-        P, T = self.n_probes, self.n_frames
-        Pc, B = eng.n_probes, eng.frame_batch
-        pos = np.asarray(self.probe_positions, dtype=np.float64).reshape(-1, 2)
-        bar = None
-        if self._progress:
-            try:
-                from tqdm import tqdm
-                bar = tqdm(total=T, desc="Processing frames", unit="frame")
-            except ImportError:
-                bar = None
-        for s0 in range(0, T, B):
-            n = min(B, T - s0)
-            if B > 1:
-                eng.build_potentials(self.trajectory.positions[s0:s0 + n], self._Z, self.slice_axis)
-            else:
-                eng.build_potential(self.trajectory.positions[s0], self._Z, self.slice_axis)
-            for p0 in range(0, P, Pc):
-                real = min(Pc, P - p0)
-                xy = pos[p0:p0 + real]
-                if real < Pc:                                  # last batch: pad by repeating its last position
-                    xy = np.concatenate([xy, np.repeat(xy[-1:], Pc - real, axis=0)])
-                eng.set_probes(self.aperture, xy)
-                if B > 1:
-                    eng.propagate_frames(0, n)
-                else:
-                    eng.propagate_frame(0)
+        batches inside; after the slice loop of each, reduce_batch(p0, real, s0, n) reads the engine's result ring: probes
+        p0 .. p0+real-1 in its first `real` rows, frames s0 .. s0+n-1 in frame slots 0 .. n-1."""
+        bar = _Progress(self._progress, self.n_frames)
+        for s0, n in self._frame_batches():
+            self._build_and_propagate(s0, n, 0, propagate=False)
+            for p0, real, xy in self._probe_batches():
+                self._engine.set_probes(self.aperture, xy)
+                self._build_and_propagate(s0, n, 0, build=False)
                 reduce_batch(p0, real, s0, n)
-            if bar is not None:
-                bar.update(n)
-        if bar is not None:
-            bar.close()
+            bar.update(n)
+        bar.close()
 
     def _frames_inside_loop(self, reduce_batch, finish_batch):
         """The other loop order, for the elastic / thermal-diffuse split of run_diffraction(): probe batches outside, frame batches
@@ -472,48 +515,21 @@ class MultisliceCalculator:
         coherent_add of the n new frames; then finish_batch(p0, real).  The price: the potentials of every frame are built once
         per probe batch, ceil(P / Pc) times instead of once -- except when the whole trajectory is one frame batch, which is
         built once before the probe loop."""
-        eng = self._engine
-        P, T = self.n_probes, self.n_frames
-        Pc, B = eng.n_probes, eng.frame_batch
-        pos = np.asarray(self.probe_positions, dtype=np.float64).reshape(-1, 2)
-        bar = None
-        if self._progress:
-            try:
-                from tqdm import tqdm
-                bar = tqdm(total=-(-P // Pc) * T, desc="Processing frames", unit="frame")
-            except ImportError:
-                bar = None
-
-        def build(s0, n):
-            if B > 1:
-                eng.build_potentials(self.trajectory.positions[s0:s0 + n], self._Z, self.slice_axis)
-            else:
-                eng.build_potential(self.trajectory.positions[s0], self._Z, self.slice_axis)
-        once = T <= B
+        eng, batches = self._engine, self._frame_batches()
+        bar = _Progress(self._progress, -(-self.n_probes // eng.n_probes) * self.n_frames)
+        once = self.n_frames <= eng.frame_batch
         if once:
-            build(0, T)
-        for p0 in range(0, P, Pc):
-            real = min(Pc, P - p0)
-            xy = pos[p0:p0 + real]
-            if real < Pc:                                      # last batch: pad by repeating its last position
-                xy = np.concatenate([xy, np.repeat(xy[-1:], Pc - real, axis=0)])
+            self._build_and_propagate(0, self.n_frames, 0, propagate=False)
+        for p0, real, xy in self._probe_batches():
             eng.set_probes(self.aperture, xy)
             eng.coherent_reset()
-            for s0 in range(0, T, B):
-                n = min(B, T - s0)
-                if not once:
-                    build(s0, n)
-                if B > 1:
-                    eng.propagate_frames(0, n)
-                else:
-                    eng.propagate_frame(0)
+            for s0, n in batches:
+                self._build_and_propagate(s0, n, 0, build=not once)
                 reduce_batch(p0, real, s0, n)
                 eng.coherent_add(0, n, B=real)
-                if bar is not None:
-                    bar.update(n)
+                bar.update(n)
             finish_batch(p0, real)
-        if bar is not None:
-            bar.close()
+        bar.close()
 
     def _stem_data(self, signals):
         from .stem_data import STEMData
@@ -602,19 +618,13 @@ class MultisliceCalculator:
         out.discard(n_slices - 1)
         return sorted(out) + [n_slices - 1]
 
-    def _check_layer_memory(self, dev, nx, ny, slots):
+    def _check_layer_memory(self, dev, slots):
         """L result blocks (P, T_local, pitch) c64 must fit in the device's free memory: fail before anything is allocated"""
         L = len(self._layers)
-        if L == 1 or not (TORCH_AVAILABLE and torch.cuda.is_available()):
+        free_b = None if L == 1 else _free_device_bytes(dev)
+        if free_b is None:                                  # (the exit wave only, or no device visible: msl_set_layers decides)
             return
-        wx, wy = self._k_window if self._k_window is not None else (nx, ny)
-        bx, by = self._k_bin if self._k_bin is not None else (1, 1)
-        pitch = ((wx // bx) * (wy // by) + 31) // 32 * 32
-        need = 8.0 * L * self.n_probes * slots * pitch
-        try:
-            free_b = float(torch.cuda.mem_get_info(_device_index(dev))[0])
-        except Exception:                                  # pragma: no cover  (no device visible to torch: msl_set_layers decides)
-            return
+        need = 8.0 * L * self.n_probes * slots * self._stored_shape()[2]
         if need > free_b:
             raise MemoryError(f"layers: {L} layers of {self.n_probes} probes x {slots} frames need {need / 1e9:.1f} GB of device memory, "
                               f"{free_b / 1e9:.1f} GB are free")
@@ -632,43 +642,30 @@ class MultisliceCalculator:
         eng = self._engine
         t0 = time.time()
         frames = self._frames
-        bar = None
-        if self._progress and self._rank == 0:
-            try:
-                from tqdm import tqdm
-                bar = tqdm(total=len(frames), desc="Processing frames", unit="frame")
-            except ImportError:
-                bar = None
+        bar = _Progress(self._progress and self._rank == 0, len(frames))
         self.frames_computed = self.frames_cached = 0
-        B = eng.frame_batch
-        if B > 1:
-            # batches of B frames: B potentials into the batch slots, then one slice loop over B x P images
-            for s0 in range(0, len(frames), B):
-                chunk = frames[s0:s0 + B]
-                eng.build_potentials(self.trajectory.positions[chunk[0]:chunk[-1] + 1], self._Z, self.slice_axis)
-                eng.propagate_frames(s0, len(chunk))
-                self.frames_computed += len(chunk)
-                if bar is not None:
-                    bar.update(len(chunk))
-            frames_iter = []
-        else:
-            frames_iter = list(enumerate(frames))
-        for slot, frame_idx in frames_iter:
-            cache_file = self.output_dir / f"frame_{frame_idx}.npy"
-            if self._cache and cache_file.exists():
-                eng.upload_frame(slot, np.load(cache_file)[:, :, :, 0, 0])
-                self.frames_cached += 1
-            else:
-                eng.build_potential(self.trajectory.positions[frame_idx], self._Z, self.slice_axis)
-                eng.propagate_frame(slot)
-                self.frames_computed += 1
-                if self._cache:
+        if self._cache:
+            # frame by frame (setup() gave the engine a frame batch of 1): a frame found in the cache is loaded, the others are written
+            for slot, frame_idx in enumerate(frames):
+                cache_file = self.output_dir / f"frame_{frame_idx}.npy"
+                if cache_file.exists():
+                    eng.upload_frame(slot, np.load(cache_file)[:, :, :, 0, 0])
+                    self.frames_cached += 1
+                else:
+                    eng.build_potential(self.trajectory.positions[frame_idx], self._Z, self.slice_axis)
+                    eng.propagate_frame(slot)
+                    self.frames_computed += 1
                     np.save(cache_file, eng.frame(slot).astype(np.complex128)[:, :, :, None, None])
-            if bar is not None:
                 bar.update(1)
+        else:
+            # batches of B frames: B potentials into the batch slots, then one slice loop over B x P images
+            for s0 in range(0, len(frames), eng.frame_batch):
+                chunk = frames[s0:s0 + eng.frame_batch]          # (a rank's frames are one contiguous block)
+                self._build_and_propagate(chunk[0], len(chunk), s0)
+                self.frames_computed += len(chunk)
+                bar.update(len(chunk))
         eng.synchronize()
-        if bar is not None:
-            bar.close()
+        bar.close()
         self.elapsed = time.time() - t0
         logger.info(f"Simulation completed in {self.elapsed:.2f}s ({self.frames_computed} computed, {self.frames_cached} cached)")
 
@@ -747,12 +744,7 @@ class MultisliceCalculator:
             tile = frames[tile0:tile0 + ring]
             for s0 in range(0, len(tile), B):
                 chunk = tile[s0:s0 + B]
-                if B > 1:
-                    eng.build_potentials(self.trajectory.positions[chunk[0]:chunk[-1] + 1], self._Z, self.slice_axis)
-                    eng.propagate_frames(s0, len(chunk))
-                else:
-                    eng.build_potential(self.trajectory.positions[chunk[0]], self._Z, self.slice_axis)
-                    eng.propagate_frame(s0)
+                self._build_and_propagate(chunk[0], len(chunk), s0)
             if not have_ref:
                 self._stream_reference(eng)
                 have_ref = True

@@ -6,6 +6,8 @@ import re
 import numpy as np
 import pytest
 
+from recording_engine import RecordingEngine
+
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LAM = 0.037
 
@@ -138,25 +140,6 @@ def test_elastic_must_have_the_shape_of_the_intensity():
 
 
 # ------------------------------------------------------------------ 4. the frames-inside loop, on an engine that only records its calls
-class _RecordingEngine:
-    def __init__(self, nx, ny, nz, *a, n_probes=1, n_frames=0, frame_batch=1, window=None, **k):
-        self.n_probes, self.n_frames, self.frame_batch = n_probes, n_frames, frame_batch
-        self.wx, self.wy = window if window else (nx, ny)
-        self.calls = []
-
-    def __getattr__(self, name):
-        if name.startswith("_"):
-            raise AttributeError(name)
-
-        def call(*a, **k):
-            self.calls.append((name, a, k))
-            if name == "diffract":
-                return np.ones((k["B"], self.wx // k["bin"][0], self.wy // k["bin"][1])) * a[1]
-            if name == "coherent_finish":
-                return np.full((k["B"], self.wx // k["bin"][0], self.wy // k["bin"][1]), 0.25)
-        return call
-
-
 @pytest.mark.parametrize("n_frames,frame_batch,builds", [(5, 2, 9), (2, 2, 1), (3, 1, 9)])
 def test_frames_inside_loop_order(monkeypatch, n_frames, frame_batch, builds):
     """probe batches outside, frame batches inside: one set_probes and one reset per probe batch, an add after every slice loop, one
@@ -165,7 +148,7 @@ def test_frames_inside_loop_order(monkeypatch, n_frames, frame_batch, builds):
     from pyslice_amd import Diffraction, _native
     from pyslice_amd.calculators import MultisliceCalculator
     from pyslice_amd.synthetic import synthetic_trajectory
-    monkeypatch.setattr(_native, "Engine", _RecordingEngine)
+    monkeypatch.setattr(_native, "Engine", RecordingEngine)
     tr = synthetic_trajectory(32, 3, n_frames, density=0.05, seed=4)
     pp = [(0.3 * i, 0.2 * i) for i in range(7)]
     calc = MultisliceCalculator(progress=False, diffraction=Diffraction(bin=(4, 8), split=True), probe_batch=3, frame_batch=frame_batch)
