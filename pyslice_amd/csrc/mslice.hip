@@ -739,7 +739,8 @@ int epilogue_x_pass(msl_handle* h, int slot, int groups = 1, const float2* src =
     const long long out_is = binned ? (long long)h->wx * h->wy : (long long)c.n_frames * h->wpitch;
     const int og = binned ? 1 : groups;               // staged images stay image-major; bin_kernel regroups them by frame
     const bool windowed = (h->wx != c.nx) || (h->wy != c.ny);
-    const bool fast_ok = h->Rx && (!windowed || (c.ny % 32 == 0 && h->wy % 32 == 0));
+    // the shifted scatter moves whole tiles of 16 columns by ny/2: ny % 32 == 16 would put half of one tile past the end of the rows
+    const bool fast_ok = h->Rx && c.ny % 32 == 0 && (!windowed || h->wy % 32 == 0);
     if (fast_ok) {
         ColJob k = col_job(h, src, dst, P, h->pitch, h->wy);
         k.flags = COL_FWD | COL_SHIFT; k.out_image_stride = out_is;
