@@ -316,6 +316,35 @@ int  msl_coherent_reset(msl_handle* h, int64_t B);
 int  msl_coherent_add(msl_handle* h, const void* d_src_c64, int64_t B, int64_t T, int64_t K, int64_t ld, int32_t t0, int32_t count);
 int  msl_coherent_finish(msl_handle* h, int64_t B, int32_t n, int32_t wx, int32_t wy, int32_t bx, int32_t by, double* out);
 
+/* ---- images through an objective lens (HRTEM, focal series): frame-accumulated |psi|^2 in the image plane, per probe batch ----
+ * For probe b and the frames j of a call
+ *     I[first + b*stride](r) += weight * sum_{j<count} | ifft2( ifftshift(Psi[b, t0+j]) * H )(r) |^2,
+ *     H(k) = A(k) exp(-i chi(k)),   A(k) = 1 for |k| < aperture_k (strict, the rule of msl_set_probes) or without an aperture, else 0,
+ * with Psi the stored exit spectrum fftshift(fft2(exit)), unnormalised, ifft2 NumPy's (1/(nx*ny)), and chi the aberration function of
+ * msl_set_aberrations: the same fourteen terms, order and sign, evaluated in float64 on the device.  Sign of defocus: C10 = +dz gives
+ * H = exp(-i pi lambda dz k^2), the Fresnel factor of the slice loop (multislice.py:262-275), so the image at C10 = +dz is the intensity
+ * a distance dz DOWNSTREAM of the exit surface -- the opposite of abTEM's defocus = -C10, as for the probe.  A focal series is one call
+ * per defocus, a focal spread one call per quadrature node with its weight; the caller divides by the number of frames.
+ * The handle owns one accumulator, (n_images, nx*ny) float64, dense, freed with the handle.
+ * msl_image_reset: sizes the accumulator for n_images images (it only grows) and zeroes it on the handle's stream.
+ * msl_image_add: source arguments as msl_detect over a (B,T,K = nx*ny) complex64 array with row pitch ld (0: K): d_src == NULL is the
+ *   handle's wavefunction buffer (B <= 0 means n_probes, a smaller B leaves the padded probes out).  polar14x2 has the layout of
+ *   msl_set_aberrations (NULL: chi = 0); aperture_k in 1/Angstrom (<= 0: no aperture).  Probe b goes to accumulator image first + b*stride.
+ *   Three launches per chunk of frames, queued on the stream (no wait): the lens into the work buffer of the slice loop, the inverse
+ *   transform in place, the accumulation -- fp32 |psi|^2 widened to float64, times weight, added in frame order, no atomics: without
+ *   a focal spread the sum does not depend on how the frames are split over calls, and repeated sequences are bitwise equal.  The work
+ *   buffer holds n_probes x frame_batch images: when B*count exceeds that, the call walks the frames in chunks that fit.  MSL_BUF_EXIT
+ *   is consumed (msl_download of it is MSL_ERR_STATE until the next msl_propagate).
+ *   MSL_ERR_INVALID for a handle with a k-window or bins, ld < nx*ny, [t0, t0+count) outside [0, T), count < 1, non-finite polar, weight or
+ *   aperture_k, stride < 0 (or 0 with B > 1), first + (B-1)*stride beyond the last reset, B above the images of the work buffer;
+ *   MSL_ERR_STATE with d_src == NULL and no result ring.
+ * msl_image_download: images [first, first+n) to HOST memory, n*nx*ny float64, dense; waits for the stream.
+ *   Not in the reference, which has no imaging mode. */
+int  msl_image_reset(msl_handle* h, int64_t n_images);
+int  msl_image_add(msl_handle* h, const void* d_src_c64, int64_t B, int64_t T, int64_t ld, int32_t t0, int32_t count,
+                   const double* polar14x2, double aperture_k, double weight, int64_t first, int64_t stride);
+int  msl_image_download(msl_handle* h, int64_t first, int64_t n, double* out);
+
 /* ---- thickness series: spectra of intermediate layers of the stack ----
  * msl_set_layers: `n` strictly increasing slice indices k in [0, nz-1).  Layer k is the wave after the transmission of slice k and
  * before the propagation that follows it -- the exit wave of the stack cut after slice k.  Every fused slice loop then also writes

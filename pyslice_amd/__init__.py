@@ -14,9 +14,11 @@ from .haadf_data import HAADFData
 from .stem_data import Detector, STEMData
 from .diffraction_data import Diffraction, DiffractionData
 from .aberrations import Aberrations, scherzer_defocus
+from .imaging import Imaging
+from .image_data import ImageData
 
 __all__ = ["Trajectory", "WFData", "Potential", "gridFromTrajectory", "getZfromElementName", "loadKirkland",
            "Probe", "Propagate", "create_batched_probes", "probe_grid", "wavelength", "m_effective",
            "MultisliceCalculator", "TACAWData", "HAADFData", "Detector", "STEMData", "Diffraction", "DiffractionData",
-           "Aberrations", "scherzer_defocus"]
+           "Aberrations", "scherzer_defocus", "Imaging", "ImageData"]
 __version__ = "0.1.0"

@@ -32,6 +32,7 @@ EXPORTS = [
     "msl_set_layers", "msl_download_layers_c128", "msl_tacaw_layer",
     "msl_set_detectors", "msl_detect", "msl_diffract",
     "msl_coherent_reset", "msl_coherent_add", "msl_coherent_finish",
+    "msl_image_reset", "msl_image_add", "msl_image_download",
 ]
 DET_SIGNALS = {"intensity": 0, "amplitude": 1, "com_x": 2, "com_y": 3}      # include/mslice.h: MSL_DET_*
 
@@ -122,6 +123,9 @@ def load():
         "msl_coherent_reset": (C.c_int, [vp, i64]),
         "msl_coherent_add": (C.c_int, [vp, vp, i64, i64, i64, i64, i32, i32]),
         "msl_coherent_finish": (C.c_int, [vp, i64, i32, i32, i32, i32, i32, vp]),
+        "msl_image_reset": (C.c_int, [vp, i64]),
+        "msl_image_add": (C.c_int, [vp, vp, i64, i64, i64, i32, i32, vp, dbl, dbl, i64, i64]),
+        "msl_image_download": (C.c_int, [vp, i64, i64, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -530,6 +534,37 @@ class Engine:
         ok = bx > 0 and by > 0 and wx > 0 and wy > 0 and wx % bx == 0 and wy % by == 0       # (else the library refuses: no output is read)
         out = np.empty((max(b, 0), wx // bx, wy // by) if ok and b > 0 else (1,), dtype=np.float64)
         self._chk(self._lib.msl_coherent_finish(self._h, b, int(n), wx, wy, bx, by, _ptr(out)))
+        return out
+
+    # -- images through an objective lens (msl_image_reset / msl_image_add / msl_image_download)
+    def image_reset(self, n):
+        """size the handle's float64 image accumulator for n images of (nx, ny) and zero it"""
+        self._chk(self._lib.msl_image_reset(self._h, int(n)))
+
+    def image_add(self, t0=0, count=None, polar=None, aperture_k=0.0, weight=1.0, first=0, stride=1, B=None, src=None):
+        """image[first + b * stride] += weight * the sum over the frame slots [t0, t0+count) of |ifft2(ifftshift(Psi[b, t]) * H)|^2,
+        H = A(k) exp(-i chi(k)): polar = the (14, 2) array of Aberrations.as_polar() (None: chi = 0), aperture_k in 1/Angstrom
+        (<= 0: none).  Source as detect(): None is the handle's own wavefunction buffer (B = n_probes or fewer: the first B probes);
+        else (device pointer, B, T[, ld]) of a caller's complex64 (B, T, nx*ny) array of full-grid spectra.  Queued on the
+        handle's stream; consumes the real-space exit waves."""
+        if src is None:
+            p, b, T, ld = None, int(B) if B else self.n_probes, self.n_frames, 0
+        else:
+            p, b, T = C.c_void_p(int(src[0])), int(src[1]), int(src[2])
+            ld = int(src[3]) if len(src) > 3 else self.nx * self.ny
+        count = (T - int(t0)) if count is None else int(count)
+        pol = None
+        if polar is not None:
+            pol = np.ascontiguousarray(polar, dtype=np.float64)
+            if pol.shape != (14, 2):
+                raise ValueError(f"polar must be (14, 2) coefficients, got {pol.shape}")
+        self._chk(self._lib.msl_image_add(self._h, p, b, T, ld, int(t0), count, _ptr(pol) if pol is not None else None, float(aperture_k),
+                                          float(weight), int(first), int(stride)))
+
+    def image_download(self, first, n):
+        """(n, nx, ny) float64: accumulator images [first, first+n); waits for the stream"""
+        out = np.empty((max(int(n), 1), self.nx, self.ny), dtype=np.float64)
+        self._chk(self._lib.msl_image_download(self._h, int(first), int(n), _ptr(out)))
         return out
 
     # -- results

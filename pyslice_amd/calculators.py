@@ -124,7 +124,7 @@ class MultisliceCalculator:
 
     def __init__(self, device=None, force_cpu=False, *, output="host", dtype="complex128", progress=True,
                  gather="rank0", cache=False, k_window=None, frame_batch=None, k_bin=None, stream_tile=None, layers=None,
-                 detectors=None, probe_batch=None, diffraction=None, aberrations=None):
+                 detectors=None, probe_batch=None, diffraction=None, aberrations=None, imaging=None):
         """
         device / force_cpu: as the reference (calculators.py:41).  There is no CPU path here, so
         force_cpu=True raises.  Keyword-only extras (not in the reference):
@@ -165,6 +165,14 @@ class MultisliceCalculator:
                    Aberrations(defocus=dz) is the reference's Probe.defocus(dz) for dz > 0 (the opposite sign of abTEM's
                    defocus = -C10).  setup(defocus=...) stays stored-only, as in the reference.  No effect on plane waves
                    (aperture == 0).  With cache=True a non-zero set joins the cache key.
+          imaging  HRTEM mode: an imaging.Imaging (objective aberrations and aperture, a defocus series, a focal spread).
+                   run_images() streams the probes through the device as run_detectors() does and, per probe batch and frame batch,
+                   applies the lens to the exit spectra, transforms back and adds |psi|^2 into a float64 accumulator on the device
+                   (msl_image_add): the result is the frame-averaged image of every probe and defocus, (P, 1, F, nx, ny) float64 on
+                   the host.  A plane-wave run is aperture = 0 in setup().  Imaging(defocus_series=[dz]) is the intensity dz
+                   DOWNSTREAM of the exit surface (C10 = +dz, the opposite sign of abTEM's defocus).  run() is refused.  Not with
+                   k_window, k_bin, cache, stream_tile, detectors, diffraction, layers (imaging of a thickness series is not built)
+                   or several ranks; probe_batch applies.
         """
         if force_cpu:
             raise NotImplementedError("pyslice_amd has no CPU path (force_cpu=True): use the reference for CPU runs")
@@ -194,7 +202,7 @@ class MultisliceCalculator:
                 raise ValueError("streaming TACAW keeps the exit wave only: stream_tile cannot be combined with layers")
             layers = list(layers)
         self._layers_arg = layers
-        if probe_batch is not None and detectors is None and diffraction is None:
+        if probe_batch is not None and detectors is None and diffraction is None and imaging is None:
             raise ValueError("probe_batch applies to detector and diffraction runs only: give detectors=[...] or diffraction=Diffraction(...)")
         if probe_batch is not None and int(probe_batch) < 1:
             raise ValueError("probe_batch must be a positive probe count")
@@ -214,6 +222,19 @@ class MultisliceCalculator:
             from .stem_data import check_detectors
             detectors = check_detectors(detectors)
         self._detectors, self._diffraction = detectors, diffraction
+        if imaging is not None:
+            from .imaging import Imaging
+            if not isinstance(imaging, Imaging):
+                raise ValueError(f"imaging: expected an Imaging object, got {imaging!r}")
+            # an image needs every pixel of the exit spectrum, and its own loop over the probe batches
+            for what, val in (("k_window", k_window is not None), ("k_bin", k_bin is not None), ("cache", cache),
+                              ("stream_tile", stream_tile is not None), ("detectors", detectors is not None),
+                              ("diffraction", diffraction is not None)):
+                if val:
+                    raise ValueError(f"imaging cannot be combined with {what}")
+            if layers is not None:
+                raise ValueError("imaging of thickness-series layers is not built")
+        self._imaging = imaging
         if aberrations is not None and not isinstance(aberrations, Aberrations):
             raise ValueError(f"aberrations: expected an Aberrations object, got {aberrations!r}")
         self._aberrations = aberrations
@@ -289,7 +310,7 @@ class MultisliceCalculator:
         if self.probe_positions is None:
             self.probe_positions = [(lx / 2, ly / 2)]
         self._rank, self._world = distributed.rank_world()
-        if self._detectors is not None or self._diffraction is not None:
+        if self._detectors is not None or self._diffraction is not None or self._imaging is not None:
             self._setup_probe_batches(trajectory, slice_axis)
             return
         n_slices = self._setup_run(trajectory, slice_axis)
@@ -337,7 +358,7 @@ class MultisliceCalculator:
         """setup() of a run that streams probe batches (detectors, diffraction): every check on the host first, then an engine of
         Pc <= P probes x one frame batch of result slots, then the detector memberships onto it"""
         if self._world > 1:
-            mode = "detectors" if self._detectors is not None else "diffraction"
+            mode = "detectors" if self._detectors is not None else ("diffraction" if self._diffraction is not None else "imaging")
             raise NotImplementedError(f"{mode}: runs over several ranks are not supported (run_detectors() / run_diffraction() are "
                                       "single-process)")
         if self._diffraction is not None:
@@ -428,12 +449,15 @@ class MultisliceCalculator:
 
     def _fit_probe_batch(self, free_b, Pc, batch):
         """Probe-batch runs: the default probe batch, halved while the three work buffers and the result ring of Pc x batch images,
-        the coherent accumulator of a split run (16 * pitch bytes per probe), the transmission stacks of the batch and the phase
-        tables exceed 0.9 x the free device memory."""
+        the coherent accumulator of a split run (16 * pitch bytes per probe), the image accumulator of an imaging run (8 * nx * ny
+        bytes per probe, layer and defocus), the transmission stacks of the batch and the phase tables exceed 0.9 x the free device
+        memory."""
         nx, ny, n_slices = self.nx, self.ny, len(self._slice_coords)
         pitch = self._stored_shape()[2]
         tables = self._phase_table_bytes(batch)
         coh = 16.0 * pitch if self._diffraction is not None and self._diffraction.split else 0.0
+        if self._imaging is not None:
+            coh = 8.0 * nx * ny * len(self._layers) * len(self._imaging.defocus_series)
         while Pc > 1 and (Pc * batch * (32.0 * nx * ny + 8.0 * pitch) + Pc * coh + batch * 16.0 * n_slices * nx * ny + tables + 1e9
                           > 0.9 * free_b):
             Pc = max(1, Pc // 2)
@@ -507,14 +531,15 @@ class MultisliceCalculator:
             bar.update(n)
         bar.close()
 
-    def _frames_inside_loop(self, reduce_batch, finish_batch):
+    def _frames_inside_loop(self, reduce_batch, finish_batch, coherent=True):
         """The other loop order, for the elastic / thermal-diffuse split of run_diffraction(): probe batches outside, frame batches
         inside, because |<Psi>|^2 needs the coherent sum over ALL frames of a probe while its accumulator (16 * pitch bytes per
         probe) is on the device.  Per probe batch: set_probes once (a potential build leaves the probes alone), coherent_reset;
         per frame batch inside it the potentials, the slice loop, reduce_batch(p0, real, s0, n) as in _probe_batch_loop and
         coherent_add of the n new frames; then finish_batch(p0, real).  The price: the potentials of every frame are built once
         per probe batch, ceil(P / Pc) times instead of once -- except when the whole trajectory is one frame batch, which is
-        built once before the probe loop."""
+        built once before the probe loop.  run_images() takes the same order with coherent=False (its accumulator holds one probe
+        batch too): no coherent_* call is made."""
         eng, batches = self._engine, self._frame_batches()
         bar = _Progress(self._progress, -(-self.n_probes // eng.n_probes) * self.n_frames)
         once = self.n_frames <= eng.frame_batch
@@ -522,11 +547,13 @@ class MultisliceCalculator:
             self._build_and_propagate(0, self.n_frames, 0, propagate=False)
         for p0, real, xy in self._probe_batches():
             eng.set_probes(self.aperture, xy)
-            eng.coherent_reset()
+            if coherent:
+                eng.coherent_reset()
             for s0, n in batches:
                 self._build_and_propagate(s0, n, 0, build=not once)
                 reduce_batch(p0, real, s0, n)
-                eng.coherent_add(0, n, B=real)
+                if coherent:
+                    eng.coherent_add(0, n, B=real)
                 bar.update(n)
             finish_batch(p0, real)
         bar.close()
@@ -582,6 +609,44 @@ class MultisliceCalculator:
                                n_frames=T, probe_positions=self.probe_positions, probe=self.base_probe,
                                stem=None if signals is None else self._stem_data(signals), elastic=elastic)
 
+    def run_images(self):
+        """Frame-averaged images behind the objective lens (HRTEM, focal series), for every probe: probe batches outside, frame
+        batches inside (_frames_inside_loop without its coherent sums), because the float64 accumulator on the device,
+        (real, L, F, nx, ny), holds one probe batch.  Per probe batch it is reset; per frame batch, after the slice loop, one
+        msl_image_add for every defocus f and focal-spread node i (weight w_i, image l * F + f of every probe, stride L * F) applies
+        the lens to the n new exit spectra, transforms back and adds |psi|^2; after the last frame batch the images are downloaded
+        and divided by the number of frames.  -> ImageData with intensity (P, L, F, nx, ny) float64, L = 1.  As for the split of
+        run_diffraction(), the potentials of every frame are built once per probe batch unless the trajectory is one frame batch."""
+        from .image_data import ImageData
+        if self._imaging is None:
+            raise RuntimeError("run_images() needs MultisliceCalculator(imaging=Imaging(...))")
+        if self._engine is None:
+            raise RuntimeError("call setup() before run_images()")
+        eng, im = self._engine, self._imaging
+        t0 = time.time()
+        P, T, L, F = self.n_probes, self.n_frames, len(self._layers), len(im.defocus_series)
+        lam = wavelength(self.voltage_eV)
+        k_ap = im.aperture_k(lam)
+        deltas, weights = im.nodes()
+        polars = [[im.polar(f, i) for i in range(len(deltas))] for f in range(F)]
+        out = np.zeros((P, L, F, eng.wx, eng.wy), dtype=np.float64)       # (imaging stores the full grid: wx, wy = nx, ny)
+
+        def reduce_batch(p0, real, s0, n):
+            if s0 == 0:
+                eng.image_reset(real * L * F)
+            for f in range(F):
+                for i, w in enumerate(weights):
+                    eng.image_add(0, n, polar=polars[f][i], aperture_k=k_ap, weight=float(w), first=(L - 1) * F + f, stride=L * F, B=real)
+
+        def finish_batch(p0, real):
+            out[p0:p0 + real] = np.asarray(eng.image_download(0, real * L * F)).reshape(real, L, F, eng.wx, eng.wy) / T
+        self._frames_inside_loop(reduce_batch, finish_batch, coherent=False)
+        self.elapsed = time.time() - t0
+        self.frames_computed, self.frames_cached = T, 0
+        return ImageData(intensity=out, xs=np.asarray(self.xs, dtype=np.float64), ys=np.asarray(self.ys, dtype=np.float64),
+                         defocus=np.asarray(im.defocus_series, dtype=np.float64), layer=np.asarray(self._layers, dtype=np.int64),
+                         n_frames=T, probe_positions=self.probe_positions, imaging=im)
+
     def run_detectors(self):
         """STEM detector signals of every probe and frame: for each frame batch the potentials are built once, then every probe
         batch goes through the slice loop and msl_detect reduces its exit spectra to the detector values.  -> STEMData with
@@ -635,6 +700,8 @@ class MultisliceCalculator:
             raise RuntimeError("detectors are set: the device holds one probe batch at a time -- call run_detectors()")
         if self._diffraction is not None:
             raise RuntimeError("diffraction is set: the device holds one probe batch at a time -- call run_diffraction()")
+        if self._imaging is not None:
+            raise RuntimeError("imaging is set: the device holds one probe batch at a time -- call run_images()")
         if self._engine is None:
             raise RuntimeError("call setup() before run()")
         if self._stream_tile is not None:

@@ -24,6 +24,7 @@
 #include "detect.h"
 #include "diffract.h"
 #include "coherent.h"
+#include "image.h"
 
 using namespace msl;
 
@@ -184,6 +185,9 @@ struct msl_handle {
     // length of the adds since the last reset (0: none yet)
     DevBuf<double2> coh_acc;
     int64_t coh_B = 0, coh_K = 0;
+    // image accumulator (msl_image_reset / _add / _download): (img_n, nx * ny) float64, grown on demand
+    DevBuf<double> img_acc;
+    int64_t img_n = 0;
     DevBuf<double> d_abcd, d_lo, d_hi;
     bool have_kirkland = false, have_slices = false, have_probes = false, have_potential = false, have_exit = false;
     int frames_done = 0;
@@ -2749,6 +2753,110 @@ int msl_coherent_finish(msl_handle* h, int64_t B, int32_t n, int32_t wx, int32_t
                        mx, my, (int)bx, (int)by, L, (double)n * (double)n, h->diff_out.p);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipMemcpyAsync(out, h->diff_out, (size_t)bins * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return MSL_OK;
+}
+
+// ---- images through an objective lens (image.h) -----------------------------------------------------------
+static int image_full_grid(msl_handle* h, const char* who) {
+    if (h->wpix != (size_t)h->cfg.nx * h->cfg.ny || h->bx != 1 || h->by != 1)
+        return fail(h, MSL_ERR_INVALID, "%s: the handle stores a k-window or bins; an image needs the full %d x %d spectrum", who, h->cfg.nx, h->cfg.ny);
+    return MSL_OK;
+}
+
+int msl_image_reset(msl_handle* h, int64_t n_images) {
+    if (!h) return fail(h, MSL_ERR_INVALID, "msl_image_reset: null handle");
+    int rc = image_full_grid(h, "msl_image_reset");
+    if (rc) return rc;
+    if (n_images < 1) return fail(h, MSL_ERR_INVALID, "msl_image_reset: %lld images", (long long)n_images);
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    h->img_n = 0;
+    const size_t n = (size_t)n_images * h->cfg.nx * h->cfg.ny;
+    if ((rc = h->img_acc.reserve(h, n))) return rc;
+    HIPCHK(h, hipMemsetAsync(h->img_acc, 0, n * sizeof(double), h->stream));
+    h->img_n = n_images;
+    return MSL_OK;
+}
+
+int msl_image_add(msl_handle* h, const void* d_src_c64, int64_t B, int64_t T, int64_t ld, int32_t t0, int32_t count, const double* polar14x2,
+                  double aperture_k, double weight, int64_t first, int64_t stride) {
+    if (!h) return fail(h, MSL_ERR_INVALID, "msl_image_add: null handle");
+    int rc = image_full_grid(h, "msl_image_add");
+    if (rc) return rc;
+    const msl_config& c = h->cfg;
+    int64_t K = (int64_t)c.nx * c.ny;
+    if ((rc = resident_wavefunction(h, "msl_image_add", &d_src_c64, &B, &T, &K, &ld))) return rc;
+    if (count < 1 || t0 < 0 || (int64_t)t0 + count > T)
+        return fail(h, MSL_ERR_INVALID, "msl_image_add: frame slots [%d,%d) outside [0,%lld)", t0, t0 + count, (long long)T);
+    if (!std::isfinite(weight) || !std::isfinite(aperture_k)) return fail(h, MSL_ERR_INVALID, "msl_image_add: weight or aperture is not finite");
+    bool has_chi = false;
+    for (int k = 0; polar14x2 && k < 28; ++k) {
+        if (!std::isfinite(polar14x2[k])) return fail(h, MSL_ERR_INVALID, "msl_image_add: aberration value %d is not finite", k);
+        if (!(k & 1) && polar14x2[k] != 0) has_chi = true;
+    }
+    if (first < 0 || stride < 0 || (stride == 0 && B > 1) || first + (B - 1) * stride >= h->img_n)
+        return fail(h, MSL_ERR_INVALID, "msl_image_add: images %lld + b * %lld of %lld probes, the last msl_image_reset sized %lld", (long long)first,
+                    (long long)stride, (long long)B, (long long)h->img_n);
+    // the work buffer is psi: n_probes x frame batch images, which the slice loop has finished with
+    const int64_t cap = (int64_t)c.n_probes * h->FB;
+    if (B > cap) return fail(h, MSL_ERR_INVALID, "msl_image_add: %lld probes, the work buffer holds %lld images", (long long)B, (long long)cap);
+    HIPCHK(h, hipSetDevice(c.device));
+    ProbeAberrations ab{};
+    if (has_chi) {
+        // (a, b) = C (cos, sin)(m phi) / ((n + 1) lambda), as msl_set_probes: the kernel's polynomial gives chi / (2 pi) in turns
+        static const int term_n[14] = {1, 1, 2, 2, 3, 3, 3, 4, 4, 4, 5, 5, 5, 5}, term_m[14] = {0, 2, 1, 3, 0, 2, 4, 1, 3, 5, 0, 2, 4, 6};
+        for (int k = 0; k < 14; ++k) {
+            const double w = polar14x2[2 * k] / ((term_n[k] + 1) * c.wavelength);
+            ab.a[k] = term_m[k] ? w * cos(term_m[k] * polar14x2[2 * k + 1]) : w;
+            ab.b[k] = term_m[k] ? w * sin(term_m[k] * polar14x2[2 * k + 1]) : 0.0;
+        }
+    }
+    const float2* src = (const float2*)d_src_c64 + (int64_t)t0 * ld;
+    const bool pitch_even = h->pitch % 2 == 0;
+    // 16-byte accesses: an even column maps to an even shifted column and the pair does not wrap (ny, ny / 2 even), every image and row starts on 16 bytes
+    const bool vec_lens = c.ny % 4 == 0 && ld % 2 == 0 && pitch_even && (((uintptr_t)d_src_c64 & 15) == 0);
+    const bool vec_acc = c.ny % 2 == 0 && pitch_even;
+    const int64_t lanes_lens = (int64_t)c.nx * (vec_lens ? c.ny / 2 : c.ny), lanes_acc = (int64_t)c.nx * (vec_acc ? c.ny / 2 : c.ny);
+    const unsigned gx_lens = (unsigned)((lanes_lens + 255) / 256), gx_acc = (unsigned)((lanes_acc + 255) / 256);
+    const int64_t per = cap / B;                                 // frames per chunk
+    const double radius = aperture_k > 0 ? aperture_k : 0.0;
+    const float scale = 1.0f / ((float)c.nx * (float)c.ny);
+    if ((rc = begin_timed(h, (int)std::min<int64_t>(8 * ((count + per - 1) / per), 4096)))) return rc;
+    h->have_exit = false;                                        // MSL_BUF_EXIT is consumed
+    for (int64_t j0 = 0; j0 < count; j0 += per) {
+        const int64_t n = std::min<int64_t>(per, count - j0), images = n * B;
+        // about 4096 workgroups: H is evaluated once per lane and reused for the images the lane walks
+        const unsigned gy = (unsigned)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(images, 65535), (4096 + gx_lens - 1) / gx_lens));
+        const float2* s = src + j0 * ld;
+        if (vec_lens) hipLaunchKernelGGL(lens_apply_kernel<true>, dim3(gx_lens, gy), dim3(256), 0, h->stream, s, (long long)B, (long long)T, (long long)ld,
+                                         (long long)images, c.nx, c.ny, h->pitch, 1.0 / (c.nx * c.dx), 1.0 / (c.ny * c.dy), radius, c.wavelength,
+                                         (int)has_chi, ab, h->psi.p);
+        else hipLaunchKernelGGL(lens_apply_kernel<false>, dim3(gx_lens, gy), dim3(256), 0, h->stream, s, (long long)B, (long long)T, (long long)ld,
+                                (long long)images, c.nx, c.ny, h->pitch, 1.0 / (c.nx * c.dx), 1.0 / (c.ny * c.dy), radius, c.wavelength,
+                                (int)has_chi, ab, h->psi.p);
+        HIPCHK(h, hipGetLastError());
+        if ((rc = mark_launch(h, K_OTHER))) return rc;
+        if ((rc = fft2_inplace(h, h->psi, (int)images, -1, scale, h->pitch))) return rc;
+        const dim3 grid_acc(gx_acc, (unsigned)std::min<int64_t>(B, 65535));
+        if (vec_acc) hipLaunchKernelGGL(image_accumulate_kernel<true>, grid_acc, dim3(256), 0, h->stream, (const float2*)h->psi.p, (long long)B, (int)n, c.nx,
+                                        c.ny, h->pitch, weight, (long long)first, (long long)stride, h->img_acc.p);
+        else hipLaunchKernelGGL(image_accumulate_kernel<false>, grid_acc, dim3(256), 0, h->stream, (const float2*)h->psi.p, (long long)B, (int)n, c.nx,
+                                c.ny, h->pitch, weight, (long long)first, (long long)stride, h->img_acc.p);
+        HIPCHK(h, hipGetLastError());
+        if ((rc = mark_launch(h, K_OTHER))) return rc;
+    }
+    h->ctr.algorithmic_bytes += (uint64_t)K * (uint64_t)B * (56ull * (uint64_t)count + 16ull);
+    return MSL_OK;
+}
+
+int msl_image_download(msl_handle* h, int64_t first, int64_t n, double* out) {
+    if (!h || !out) return fail(h, MSL_ERR_INVALID, "msl_image_download: null argument");
+    if (first < 0 || n < 1 || first + n > h->img_n)
+        return fail(h, MSL_ERR_INVALID, "msl_image_download: images [%lld,%lld), the last msl_image_reset sized %lld", (long long)first, (long long)(first + n),
+                    (long long)h->img_n);
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    const size_t npix = (size_t)h->cfg.nx * h->cfg.ny;
+    HIPCHK(h, hipMemcpyAsync(out, h->img_acc + (size_t)first * npix, (size_t)n * npix * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return MSL_OK;
 }
