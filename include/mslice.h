@@ -88,8 +88,9 @@ typedef enum {
     MSL_BUF_STREAM_S1 = 8,     /* (P,K) 2 x f64     sum_t Psi */
     MSL_BUF_STREAM_S2 = 9,     /* (P,K) f64         sum_t |Psi|^2 */
     MSL_BUF_STREAM_REF = 10,   /* (P,K) c64         the reference pattern (msl_tacaw_stream_set_reference), NULL when none is set */
-    MSL_BUF_LAYERS = 11        /* (L,P,T_local,pitch) c64  the spectra of every layer (msl_set_layers), the exit wave last; L = 1 without
+    MSL_BUF_LAYERS = 11,       /* (L,P,T_local,pitch) c64  the spectra of every layer (msl_set_layers), the exit wave last; L = 1 without
                                 *                    layers (then the same memory as MSL_BUF_WAVEFUNCTION) */
+    MSL_BUF_SMATRIX = 12       /* (Bm,nx,ny) c64    the PRISM S-matrix of the last msl_smatrix_build: the exit waves of the Bm beams */
 } msl_buffer;
 
 typedef struct {
@@ -344,6 +345,39 @@ int  msl_image_reset(msl_handle* h, int64_t n_images);
 int  msl_image_add(msl_handle* h, const void* d_src_c64, int64_t B, int64_t T, int64_t ld, int32_t t0, int32_t count,
                    const double* polar14x2, double aperture_k, double weight, int64_t first, int64_t stride);
 int  msl_image_download(msl_handle* h, int64_t first, int64_t n, double* out);
+
+/* ---- PRISM (Ophus 2017): plane-wave S-matrix and probe synthesis, for scans of many probe positions ----
+ * The slice loop is linear in the incident wave and applies no band limit, so a probe is a sum of plane waves, one per reciprocal-lattice
+ * point inside its aperture.  With the unshifted pixel (mx, my), h = its signed index (fftfreq order) and k = h / (n d):
+ *   beams:  the pixels with hx % fx == 0, hy % fy == 0 and sqrt(kx^2 + ky^2) < mrad * 1e-3 / lambda (strict, float64: the rule of
+ *           msl_set_probes), in row-major order of (mx, my); Bm of them.
+ *   S_b  =  Propagate(pw_b) through the current transmission stack, pw_b[i, j] = exp(2 pi i (hx i / nx + hy j / ny)).
+ *   c[p,b] = (fx fy / (nx ny)) exp(2 pi i [hx (floor(nx/2)/nx + px/Lx) + hy (floor(ny/2)/ny + py/Ly)]) exp(-i chi(k_b)),
+ *           chi the aberration function of msl_set_aberrations (zero when cleared).
+ *   psi_p(r) = W_p(r) sum_b c[p,b] S_b(r),  W_p = 1 on the (nx/fx) x (ny/fy) periodic window centred on pixel
+ *           ((-floor(nx/2) - rint(px/dx)) mod nx, likewise y) -- where the probe of msl_set_probes peaks -- and 0 elsewhere:
+ *           pixel i is inside when ((i - cx + floor(wx/2)) mod nx) < wx, wx = nx/fx.
+ * At f = (1, 1) psi_p is the exit wave msl_set_probes + msl_propagate give (to fp32 rounding); at f > 1 it is PRISM's approximation.
+ * msl_smatrix_begin:  enumerates the beams and allocates S, (Bm, nx, ny) c64, and c.  MSL_ERR_INVALID for mrad <= 0, f < 1 or f not
+ *   dividing its axis; MSL_ERR_NOMEM when S does not fit.  A second begin replaces the first.
+ * msl_smatrix_beams:  returns Bm (MSL_ERR_STATE before begin) and, when hxhy is not NULL, fills Bm x 2 signed indices (hx, hy).
+ * msl_smatrix_build:  propagates the beams, in chunks of n_probes, through the current potential into S (one unfused slice loop per
+ *   chunk, counted in the counters).  MSL_ERR_STATE without a potential or before begin.  Overwrites the probe buffer (probes must be
+ *   set again before msl_propagate) and MSL_BUF_EXIT.  Call it again after every new potential.
+ * msl_smatrix_probes: c, psi_p and fftshift(fft2(psi_p)) -- on the full grid, zeros outside the window -- into frame slot `slot` of the
+ *   result, k-window and binning as for msl_propagate_frame: every consumer of the result (msl_detect, msl_diffract, msl_tacaw, the
+ *   downloads) works on it with the normalisation of a multislice run.  The pixels at multiples of (fx, fy) are native PRISM's pattern,
+ *   the others its sinc interpolation.  xy = n_probes x 2 doubles; n_probes must be the handle's.  MSL_ERR_STATE without a built
+ *   S-matrix or with n_frames == 0.  MSL_BUF_EXIT then holds psi_p; the probe buffer is overwritten and marked unset.  Four launches,
+ *   queued on the stream; no atomics: repeated calls are bitwise equal.
+ * msl_smatrix_end:    frees S, c and the beams; msl_destroy and msl_set_beam (the wavelength changes the beam set) do the same,
+ *   msl_resize_probes keeps S.
+ *   Not in the reference, which propagates every probe position through every slice. */
+int  msl_smatrix_begin(msl_handle* h, int32_t fx, int32_t fy, double mrad);
+int  msl_smatrix_beams(const msl_handle* h, int32_t* hxhy_or_null);
+int  msl_smatrix_build(msl_handle* h);
+int  msl_smatrix_probes(msl_handle* h, const double* xy, int32_t n_probes, int32_t slot);
+int  msl_smatrix_end(msl_handle* h);
 
 /* ---- thickness series: spectra of intermediate layers of the stack ----
  * msl_set_layers: `n` strictly increasing slice indices k in [0, nz-1).  Layer k is the wave after the transmission of slice k and

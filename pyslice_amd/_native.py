@@ -16,7 +16,7 @@ LIB_PATH = os.environ.get("MSL_LIB") or os.path.join(_HERE, "libmslice.so")
 ABI_VERSION = 3          # include/mslice.h: MSL_ABI_VERSION
 MSL_OK, MSL_ERR_INVALID, MSL_ERR_HIP, MSL_ERR_UNSUPPORTED, MSL_ERR_STATE, MSL_ERR_NOMEM = 0, -1, -2, -3, -4, -5
 (BUF_PROBES, BUF_EXIT, BUF_POTENTIAL, BUF_TRANSMISSION, BUF_WAVEFUNCTION, BUF_INTENSITY, BUF_FORMFACTOR,
- BUF_STREAM_ACC, BUF_STREAM_S1, BUF_STREAM_S2, BUF_STREAM_REF, BUF_LAYERS) = range(12)
+ BUF_STREAM_ACC, BUF_STREAM_S1, BUF_STREAM_S2, BUF_STREAM_REF, BUF_LAYERS, BUF_SMATRIX) = range(13)
 
 EXPORTS = [
     "msl_abi_version", "msl_line_kernel_class", "msl_last_error", "msl_create", "msl_destroy", "msl_set_kirkland", "msl_set_slices",
@@ -33,6 +33,7 @@ EXPORTS = [
     "msl_set_detectors", "msl_detect", "msl_diffract",
     "msl_coherent_reset", "msl_coherent_add", "msl_coherent_finish",
     "msl_image_reset", "msl_image_add", "msl_image_download",
+    "msl_smatrix_begin", "msl_smatrix_beams", "msl_smatrix_build", "msl_smatrix_probes", "msl_smatrix_end",
 ]
 DET_SIGNALS = {"intensity": 0, "amplitude": 1, "com_x": 2, "com_y": 3}      # include/mslice.h: MSL_DET_*
 
@@ -126,6 +127,11 @@ def load():
         "msl_image_reset": (C.c_int, [vp, i64]),
         "msl_image_add": (C.c_int, [vp, vp, i64, i64, i64, i32, i32, vp, dbl, dbl, i64, i64]),
         "msl_image_download": (C.c_int, [vp, i64, i64, vp]),
+        "msl_smatrix_begin": (C.c_int, [vp, i32, i32, dbl]),
+        "msl_smatrix_beams": (C.c_int, [vp, vp]),
+        "msl_smatrix_build": (C.c_int, [vp]),
+        "msl_smatrix_probes": (C.c_int, [vp, vp, i32, i32]),
+        "msl_smatrix_end": (C.c_int, [vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -566,6 +572,42 @@ class Engine:
         out = np.empty((max(int(n), 1), self.nx, self.ny), dtype=np.float64)
         self._chk(self._lib.msl_image_download(self._h, int(first), int(n), _ptr(out)))
         return out
+
+    # -- PRISM: plane-wave S-matrix and probe synthesis (msl_smatrix_*)
+    def smatrix_begin(self, interpolation, mrad):
+        """enumerate the beams of aperture `mrad` at interpolation (fx, fy) and allocate the S-matrix, (Bm, nx, ny) complex64
+        -> Bm"""
+        fx, fy = (int(interpolation[0]), int(interpolation[1]))
+        self._chk(self._lib.msl_smatrix_begin(self._h, fx, fy, float(mrad)))
+        return self.smatrix_beams().shape[0]
+
+    def smatrix_beams(self):
+        """(Bm, 2) int32: the signed reciprocal-lattice indices (hx, hy) of the beams, in the order of the S-matrix"""
+        n = int(self._lib.msl_smatrix_beams(self._h, None))
+        if n < 0:
+            _raise(n, "msl_smatrix_beams: call smatrix_begin first")
+        out = np.empty((n, 2), dtype=np.int32)
+        self._lib.msl_smatrix_beams(self._h, _ptr(out))
+        return out
+
+    def smatrix_build(self):
+        """propagate every beam through the current potential into the S-matrix (chunks of n_probes beams per slice loop);
+        overwrites the probe buffer"""
+        self._chk(self._lib.msl_smatrix_build(self._h))
+
+    def smatrix_probes(self, xy, slot):
+        """synthesise the exit waves of n_probes probe positions from the S-matrix (exit_waves() downloads them) and write their
+        spectra into frame slot `slot`; xy: (n_probes, 2) Angstrom"""
+        xy = np.ascontiguousarray(xy, dtype=np.float64).reshape(-1, 2)
+        self._chk(self._lib.msl_smatrix_probes(self._h, _ptr(xy), xy.shape[0], int(slot)))
+
+    def smatrix_end(self):
+        """free the S-matrix (close(), set_beam() do the same)"""
+        self._chk(self._lib.msl_smatrix_end(self._h))
+
+    def smatrix(self):
+        """(Bm, nx, ny) complex64: the S-matrix of the last smatrix_build"""
+        return self.download(BUF_SMATRIX, np.complex64, (self.smatrix_beams().shape[0], self.nx, self.ny))
 
     # -- results
     def buffer_bytes(self, what):

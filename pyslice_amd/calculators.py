@@ -24,6 +24,7 @@ import numpy as np
 from . import _native, distributed
 from .aberrations import Aberrations
 from .multislice import Probe, interaction_sigma, wavelength
+from .prism import Prism, beams as prism_beams
 from .potentials import TORCH_AVAILABLE, _as_tensor, _device_index, gridFromTrajectory, loadKirkland, slice_edges, suggest_sampling
 from .trajectory import Trajectory
 from .wf_data import WFData
@@ -124,7 +125,7 @@ class MultisliceCalculator:
 
     def __init__(self, device=None, force_cpu=False, *, output="host", dtype="complex128", progress=True,
                  gather="rank0", cache=False, k_window=None, frame_batch=None, k_bin=None, stream_tile=None, layers=None,
-                 detectors=None, probe_batch=None, diffraction=None, aberrations=None, imaging=None):
+                 detectors=None, probe_batch=None, diffraction=None, aberrations=None, imaging=None, prism=None):
         """
         device / force_cpu: as the reference (calculators.py:41).  There is no CPU path here, so
         force_cpu=True raises.  Keyword-only extras (not in the reference):
@@ -173,6 +174,14 @@ class MultisliceCalculator:
                    DOWNSTREAM of the exit surface (C10 = +dz, the opposite sign of abTEM's defocus).  run() is refused.  Not with
                    k_window, k_bin, cache, stream_tile, detectors, diffraction, layers (imaging of a thickness series is not built)
                    or several ranks; probe_batch applies.
+          prism    a prism.Prism(interpolation): run(), run_detectors() and run_diffraction() build, per frame, the S-matrix of the
+                   Bm plane waves inside the aperture (one slice loop per beam instead of one per probe position) and synthesise
+                   the exit wave of every probe position from it (msl_smatrix_build / msl_smatrix_probes).  Prism(1) gives the
+                   multislice result to fp32 rounding and pays off once there are more probe positions than beams; Prism(f > 1)
+                   keeps every f-th beam and a window of 1/f of the cell around each probe -- PRISM's approximation.  The spectra
+                   stay on the full grid (zeros outside the window), so k_window, k_bin, aberrations, detectors and probe_batch
+                   work as before.  Needs aperture > 0 and an interpolation that divides the grid (setup() raises ValueError).
+                   Not built: Diffraction(split=True), imaging, layers, stream_tile, cache, several ranks.
         """
         if force_cpu:
             raise NotImplementedError("pyslice_amd has no CPU path (force_cpu=True): use the reference for CPU runs")
@@ -202,6 +211,17 @@ class MultisliceCalculator:
                 raise ValueError("streaming TACAW keeps the exit wave only: stream_tile cannot be combined with layers")
             layers = list(layers)
         self._layers_arg = layers
+        if prism is not None:
+            if not isinstance(prism, Prism):
+                raise ValueError(f"prism: expected a Prism object, got {prism!r}")
+            for what, val in (("cache", cache), ("layers", layers is not None), ("stream_tile", stream_tile is not None),
+                              ("imaging", imaging is not None)):
+                if val:
+                    raise NotImplementedError(f"prism with {what} is not built")
+            if diffraction is not None and getattr(diffraction, "split", False):
+                raise NotImplementedError("prism with Diffraction(split=True) is not built: the elastic / thermal-diffuse split of "
+                                          "PRISM waves")
+        self._prism = prism
         if probe_batch is not None and detectors is None and diffraction is None and imaging is None:
             raise ValueError("probe_batch applies to detector and diffraction runs only: give detectors=[...] or diffraction=Diffraction(...)")
         if probe_batch is not None and int(probe_batch) < 1:
@@ -299,6 +319,9 @@ class MultisliceCalculator:
         self.dx = xs[1] - xs[0]
         self.dy = ys[1] - ys[0]
         self._layers = self._check_layers(len([xs, ys, zs][slice_axis]), distributed.rank_world()[1])
+        self._prism_Bm = 0
+        if self._prism is not None:
+            self._check_prism(nx, ny, distributed.rank_world()[1])
         # (not in the reference) a line length without a slice-loop kernel of its own costs 2-4 x: name a nearby sampling that has one
         hint = suggest_sampling(trajectory, sampling)
         self.grid_hint = None if hint is None else (
@@ -322,7 +345,7 @@ class MultisliceCalculator:
         batch = self._frame_batch
         if batch is None:
             batch = default_frame_batch(self.n_probes, n_slices, nx, ny)
-        batch = 1 if self._cache else max(1, min(batch, len(self._frames)))
+        batch = 1 if (self._cache or self._prism is not None) else max(1, min(batch, len(self._frames)))
         slots = max(1, len(self._frames))
         if self._stream_tile is not None:
             slots = max(1, min(self._stream_tile, slots))
@@ -352,6 +375,9 @@ class MultisliceCalculator:
         if len(self._layers) > 1:
             self._engine.set_layers(self._layers[:-1])
         self._configure_engine()
+        if self._prism is not None:                             # (the probes are synthesised from the S-matrix: none to set)
+            self._engine.smatrix_begin(self._prism.interpolation, self.aperture)
+            return
         self._engine.set_probes(self.aperture, np.asarray(self.probe_positions, dtype=np.float64))
 
     def _setup_probe_batches(self, trajectory, slice_axis):
@@ -381,7 +407,7 @@ class MultisliceCalculator:
         auto = self._probe_batch is None
         Pc = min(self.n_probes, 256 if auto else self._probe_batch)
         batch = self._frame_batch if self._frame_batch is not None else default_frame_batch(Pc, n_slices, self.nx, self.ny)
-        batch = max(1, min(batch, self.n_frames))
+        batch = 1 if self._prism is not None else max(1, min(batch, self.n_frames))     # (the S-matrix holds one frame)
         free_b = _free_device_bytes(self.device) if auto else None
         if free_b is not None:
             Pc = self._fit_probe_batch(free_b, Pc, batch)
@@ -400,6 +426,8 @@ class MultisliceCalculator:
         self._configure_engine()                                # (the aberrations are read by the set_probes of every probe batch)
         if self._detectors is not None:
             self._engine.set_detectors(bits.reshape(-1), [d.signal for d in self._detectors], kxs, kys)
+        if self._prism is not None:
+            self._engine.smatrix_begin(self._prism.interpolation, self.aperture)
 
     def _setup_run(self, trajectory, slice_axis):
         """what every engine set-up takes from the trajectory and the slice axis, stored once -> the number of slices"""
@@ -458,7 +486,8 @@ class MultisliceCalculator:
         coh = 16.0 * pitch if self._diffraction is not None and self._diffraction.split else 0.0
         if self._imaging is not None:
             coh = 8.0 * nx * ny * len(self._layers) * len(self._imaging.defocus_series)
-        while Pc > 1 and (Pc * batch * (32.0 * nx * ny + 8.0 * pitch) + Pc * coh + batch * 16.0 * n_slices * nx * ny + tables + 1e9
+        smatrix = 8.0 * getattr(self, "_prism_Bm", 0) * nx * ny       # the S-matrix of a PRISM run, (Bm, nx, ny) complex64
+        while Pc > 1 and (Pc * batch * (32.0 * nx * ny + 8.0 * pitch) + Pc * coh + batch * 16.0 * n_slices * nx * ny + tables + smatrix + 1e9
                           > 0.9 * free_b):
             Pc = max(1, Pc // 2)
         return Pc
@@ -531,6 +560,32 @@ class MultisliceCalculator:
             bar.update(n)
         bar.close()
 
+    def _check_prism(self, nx, ny, world):
+        """setup() of a PRISM run, before any device work: the aperture, the interpolation against the grid, one rank -> Bm"""
+        fx, fy = self._prism.interpolation
+        if world > 1:
+            raise NotImplementedError("prism: runs over several ranks are not built (sharding of beams or probes)")
+        if not self.aperture > 0:
+            raise ValueError("prism needs a convergent probe: setup(aperture > 0) (a plane wave is one beam: run it without prism)")
+        if nx % fx or ny % fy:
+            raise ValueError(f"prism: interpolation ({fx}, {fy}) does not divide the {nx} x {ny} grid; pick a sampling whose grid it "
+                             f"divides (potentials.suggest_sampling() names grid sizes near a sampling)")
+        self._prism_Bm = len(prism_beams(nx, ny, self.dx, self.dy, self.aperture, wavelength(self.voltage_eV), (fx, fy)))
+
+    def _prism_loop(self, reduce_batch):
+        """The pass of run_detectors() / run_diffraction() with prism: per frame one potential and one S-matrix (Bm slice loops
+        instead of P), then every probe batch synthesised from it into frame slot 0 and reduced as in _probe_batch_loop."""
+        eng = self._engine
+        bar = _Progress(self._progress, self.n_frames)
+        for s in range(self.n_frames):
+            eng.build_potential(self.trajectory.positions[s], self._Z, self.slice_axis)
+            eng.smatrix_build()
+            for p0, real, xy in self._probe_batches():
+                eng.smatrix_probes(xy, 0)
+                reduce_batch(p0, real, s, 1)
+            bar.update(1)
+        bar.close()
+
     def _frames_inside_loop(self, reduce_batch, finish_batch, coherent=True):
         """The other loop order, for the elastic / thermal-diffuse split of run_diffraction(): probe batches outside, frame batches
         inside, because |<Psi>|^2 needs the coherent sum over ALL frames of a probe while its accumulator (16 * pitch bytes per
@@ -599,6 +654,8 @@ class MultisliceCalculator:
             def finish_batch(p0, real):
                 elastic[p0:p0 + real] = eng.coherent_finish(T, B=real, bin=(bx, by))
             self._frames_inside_loop(reduce_batch, finish_batch)
+        elif self._prism is not None:
+            self._prism_loop(reduce_batch)
         else:
             self._probe_batch_loop(reduce_batch)
         acc /= T
@@ -662,7 +719,10 @@ class MultisliceCalculator:
 
         def reduce_batch(p0, real, s0, n):
             signals[p0:p0 + real, s0:s0 + n] = eng.detect(0, n, B=real)
-        self._probe_batch_loop(reduce_batch)
+        if self._prism is not None:
+            self._prism_loop(reduce_batch)
+        else:
+            self._probe_batch_loop(reduce_batch)
         self.elapsed = time.time() - t0
         self.frames_computed, self.frames_cached = T, 0
         return self._stem_data(signals)
@@ -723,6 +783,15 @@ class MultisliceCalculator:
                     eng.propagate_frame(slot)
                     self.frames_computed += 1
                     np.save(cache_file, eng.frame(slot).astype(np.complex128)[:, :, :, None, None])
+                bar.update(1)
+        elif self._prism is not None:
+            # per frame: the potential, the S-matrix of its Bm beams, every probe synthesised from it into the frame's slot
+            xy = np.asarray(self.probe_positions, dtype=np.float64).reshape(-1, 2)
+            for slot, frame_idx in enumerate(frames):
+                eng.build_potential(self.trajectory.positions[frame_idx], self._Z, self.slice_axis)
+                eng.smatrix_build()
+                eng.smatrix_probes(xy, slot)
+                self.frames_computed += 1
                 bar.update(1)
         else:
             # batches of B frames: B potentials into the batch slots, then one slice loop over B x P images

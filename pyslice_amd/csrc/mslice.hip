@@ -25,6 +25,7 @@
 #include "diffract.h"
 #include "coherent.h"
 #include "image.h"
+#include "smatrix.h"
 
 using namespace msl;
 
@@ -188,6 +189,13 @@ struct msl_handle {
     // image accumulator (msl_image_reset / _add / _download): (img_n, nx * ny) float64, grown on demand
     DevBuf<double> img_acc;
     int64_t img_n = 0;
+    // PRISM (msl_smatrix_*): the beams (hx, hy) on the host and the device, S (sm_Bm, nx, ny) c64 dense, the coefficients c (P, sm_Bm)
+    // of the last probe batch; sm_open between begin and end, sm_built once msl_smatrix_build has filled S
+    std::vector<int32_t> sm_h;
+    DevBuf<int2> sm_beams;
+    DevBuf<float2> sm_S, sm_c;
+    int sm_fx = 0, sm_fy = 0, sm_Bm = 0;
+    bool sm_open = false, sm_built = false;
     DevBuf<double> d_abcd, d_lo, d_hi;
     bool have_kirkland = false, have_slices = false, have_probes = false, have_potential = false, have_exit = false;
     int frames_done = 0;
@@ -1861,6 +1869,14 @@ static int tacaw_resident(msl_handle* h, const float2* block) {
     return tacaw_run(h, block, h->intensity, c.n_probes, c.n_frames, (int64_t)h->wpitch);
 }
 
+// PRISM: free S, the beams and the coefficients (the stream is idle)
+static void smatrix_release(msl_handle* h) {
+    h->sm_S.release(); h->sm_c.release(); h->sm_beams.release();
+    h->sm_h.clear();
+    h->sm_fx = h->sm_fy = h->sm_Bm = 0;
+    h->sm_open = h->sm_built = false;
+}
+
 // The work buffers sized by the probe count (FB frames of n_probes images each; pitch, pitchT, onepass and need_psi0T are set)
 static int alloc_probe_buffers(msl_handle* h, int n_probes) {
     const msl_config& c = h->cfg;
@@ -2040,6 +2056,10 @@ int msl_set_beam(msl_handle* h, double wavelength, double sigma, double dz) {
     if (!(wavelength > 0)) return fail(h, MSL_ERR_INVALID, "msl_set_beam: wavelength must be positive");
     HIPCHK(h, hipSetDevice(h->cfg.device));
     h->cfg.wavelength = wavelength; h->cfg.sigma = sigma; h->cfg.dz = dz;
+    if (h->sm_open) {                                       // the wavelength changes the beam set
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        smatrix_release(h);
+    }
     int rc = fill_propagator(h);
     if (rc) return rc;
     if (h->have_potential) {
@@ -2252,6 +2272,158 @@ int msl_propagate_frames(msl_handle* h, int32_t first_slot, int32_t count) {
     return run_loop(h, first_slot, count, 0);
 }
 
+// ---- PRISM: plane-wave S-matrix and probe synthesis (smatrix.h) --------------------------------------------
+int msl_smatrix_begin(msl_handle* h, int32_t fx, int32_t fy, double mrad) {
+    if (!h) return fail(h, MSL_ERR_INVALID, "msl_smatrix_begin: null handle");
+    const msl_config& c = h->cfg;
+    if (!(mrad > 0) || !std::isfinite(mrad)) return fail(h, MSL_ERR_INVALID, "msl_smatrix_begin: the aperture must be positive (a plane wave needs no S-matrix)");
+    if (fx < 1 || fy < 1 || c.nx % fx || c.ny % fy)
+        return fail(h, MSL_ERR_INVALID, "msl_smatrix_begin: interpolation (%d, %d) must be positive and divide the %d x %d grid", fx, fy, c.nx, c.ny);
+    HIPCHK(h, hipSetDevice(c.device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    smatrix_release(h);
+    // the beams: unshifted pixels inside the aperture (the rule of probe_kspace_kernel) whose signed indices are multiples of f
+    const double kfx = 1.0 / (c.nx * c.dx), kfy = 1.0 / (c.ny * c.dy), radius = (mrad * 1e-3) / c.wavelength;
+    auto freq = [](int m, int n) { return (m < (n + 1) / 2) ? m : m - n; };
+    std::vector<int32_t> hb;
+    for (int mx = 0; mx < c.nx; ++mx) {
+        const int hx = freq(mx, c.nx);
+        if (hx % fx) continue;
+        for (int my = 0; my < c.ny; ++my) {
+            const int hy = freq(my, c.ny);
+            if (hy % fy) continue;
+            const double kx = hx * kfx, ky = hy * kfy;
+            if (sqrt(kx * kx + ky * ky) < radius) { hb.push_back(hx); hb.push_back(hy); }
+        }
+    }
+    const size_t Bm = hb.size() / 2;                        // >= 1: the beam (0, 0) is inside every positive aperture
+    if (Bm > 0x7fffffffull / 2) return fail(h, MSL_ERR_INVALID, "msl_smatrix_begin: %zu beams", Bm);
+    int rc;
+    if ((rc = h->sm_S.alloc(h, Bm * (size_t)c.nx * c.ny)) || (rc = h->sm_beams.alloc(h, Bm)) || (rc = h->sm_c.alloc(h, Bm * (size_t)c.n_probes))) {
+        smatrix_release(h);
+        return rc;
+    }
+    HIPCHK(h, hipMemcpyAsync(h->sm_beams, hb.data(), Bm * sizeof(int2), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    h->sm_h.swap(hb);
+    h->sm_fx = fx; h->sm_fy = fy; h->sm_Bm = (int)Bm;
+    h->sm_open = true;
+    return MSL_OK;
+}
+
+int msl_smatrix_beams(const msl_handle* h, int32_t* hxhy) {
+    if (!h) return MSL_ERR_INVALID;
+    if (!h->sm_open) return MSL_ERR_STATE;
+    if (hxhy) memcpy(hxhy, h->sm_h.data(), h->sm_h.size() * sizeof(int32_t));
+    return h->sm_Bm;
+}
+
+int msl_smatrix_build(msl_handle* h) {
+    if (!h) return fail(h, MSL_ERR_INVALID, "msl_smatrix_build: null handle");
+    if (!h->sm_open) return fail(h, MSL_ERR_STATE, "msl_smatrix_build: call msl_smatrix_begin first");
+    if (!h->have_potential) return fail(h, MSL_ERR_STATE, "msl_smatrix_build: no potential (msl_build_potential / msl_upload_potential)");
+    const msl_config& c = h->cfg;
+    HIPCHK(h, hipSetDevice(c.device));
+    EventPair timer;
+    int rc;
+    if (c.launch_timing && (rc = timer.begin(h))) return rc;
+    h->have_probes = false; h->have_exit = false; h->sm_built = false;      // the probe and work buffers carry the beams
+    const int P = c.n_probes;
+    const long long total = (long long)c.nx * c.ny * P;
+    const size_t row = (size_t)c.ny * sizeof(float2);
+    for (int b0 = 0; b0 < h->sm_Bm; b0 += P) {
+        const int count = std::min(P, h->sm_Bm - b0);
+        hipLaunchKernelGGL(plane_wave_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, h->psi0.p, (const int2*)h->sm_beams.p, b0, count, P,
+                           c.nx, c.ny, h->pitch);
+        HIPCHK(h, hipGetLastError());
+        if ((rc = transpose_probes(h)) || (rc = slice_loop(h, -1, 1, h->cur_batch))) return rc;
+        // the unfused loop leaves the exit waves in natural order at the work pitch (what msl_download(MSL_BUF_EXIT) reads)
+        HIPCHK(h, hipMemcpy2DAsync(h->sm_S + (size_t)b0 * c.nx * c.ny, row, h->psi, (size_t)h->pitch * sizeof(float2), row, (size_t)count * c.nx,
+                                   hipMemcpyDeviceToDevice, h->stream));
+        h->ctr.algorithmic_bytes += (uint64_t)count * c.nx * c.ny * 16ull;
+    }
+    h->sm_built = true;
+    return c.launch_timing ? timer.end(h, &h->ctr.ms_propagate) : MSL_OK;
+}
+
+extern "C++" template <int G>
+static void launch_synth(msl_handle* h, bool vec, int win_x, int win_y) {
+    const msl_config& c = h->cfg;
+    const int lanes_y = vec ? c.ny / 2 : c.ny;
+    const dim3 grid((unsigned)((c.n_probes + G - 1) / G), (unsigned)((c.nx + SM_TILE_ROWS - 1) / SM_TILE_ROWS), (unsigned)((lanes_y + SM_TILE_LANES - 1) / SM_TILE_LANES));
+    if (vec) hipLaunchKernelGGL((smatrix_synth_kernel<G, true>), grid, dim3(256), 0, h->stream, (const float2*)h->sm_S.p, (const float2*)h->sm_c.p, (const double*)h->d_xy.p,
+                                c.n_probes, h->sm_Bm, c.nx, c.ny, h->pitch, win_x, win_y, c.dx, c.dy, h->psi.p, h->psi0.p);
+    else hipLaunchKernelGGL((smatrix_synth_kernel<G, false>), grid, dim3(256), 0, h->stream, (const float2*)h->sm_S.p, (const float2*)h->sm_c.p, (const double*)h->d_xy.p,
+                            c.n_probes, h->sm_Bm, c.nx, c.ny, h->pitch, win_x, win_y, c.dx, c.dy, h->psi.p, h->psi0.p);
+}
+
+int msl_smatrix_probes(msl_handle* h, const double* xy, int32_t n_probes, int32_t slot) {
+    if (!h || !xy) return fail(h, MSL_ERR_INVALID, "msl_smatrix_probes: null argument");
+    const msl_config& c = h->cfg;
+    if (n_probes != c.n_probes) return fail(h, MSL_ERR_INVALID, "msl_smatrix_probes: %d probes, handle has %d", n_probes, c.n_probes);
+    if (!h->sm_built) return fail(h, MSL_ERR_STATE, "msl_smatrix_probes: no S-matrix (msl_smatrix_begin, msl_smatrix_build)");
+    if (!h->wf) return fail(h, MSL_ERR_STATE, "msl_smatrix_probes: handle created with n_frames == 0");
+    if (slot < 0 || slot >= c.n_frames) return fail(h, MSL_ERR_INVALID, "msl_smatrix_probes: slot %d out of range [0,%d)", slot, c.n_frames);
+    for (int k = 0; k < 2 * n_probes; ++k)
+        if (!std::isfinite(xy[k])) return fail(h, MSL_ERR_INVALID, "msl_smatrix_probes: position value %d is not finite", k);
+    HIPCHK(h, hipSetDevice(c.device));
+    int rc;
+    if ((rc = h->sm_c.reserve(h, (size_t)h->sm_Bm * n_probes))) return rc;       // (msl_resize_probes keeps S)
+    HIPCHK(h, hipMemcpyAsync(h->d_xy, xy, 2 * sizeof(double) * n_probes, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));             // xy is the caller's memory: read before the call returns
+    EventPair timer;
+    if (c.launch_timing && (rc = timer.begin(h))) return rc;
+    if ((rc = begin_timed(h, 8))) return rc;
+    ProbeAberrations ab{};
+    if (h->have_aberr) {
+        // (a, b) = C (cos, sin)(m phi) / ((n + 1) lambda), as msl_set_probes: the kernel's polynomial gives chi / (2 pi) in turns
+        static const int term_n[14] = {1, 1, 2, 2, 3, 3, 3, 4, 4, 4, 5, 5, 5, 5}, term_m[14] = {0, 2, 1, 3, 0, 2, 4, 1, 3, 5, 0, 2, 4, 6};
+        for (int k = 0; k < 14; ++k) {
+            const double w = h->aberr_polar[k][0] / ((term_n[k] + 1) * c.wavelength);
+            ab.a[k] = term_m[k] ? w * cos(term_m[k] * h->aberr_polar[k][1]) : w;
+            ab.b[k] = term_m[k] ? w * sin(term_m[k] * h->aberr_polar[k][1]) : 0.0;
+        }
+    }
+    const long long nc = (long long)n_probes * h->sm_Bm;
+    const float scale = (float)((double)h->sm_fx * h->sm_fy / ((double)c.nx * c.ny));
+    hipLaunchKernelGGL(smatrix_coeff_kernel, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, h->stream, h->sm_c.p, (const double*)h->d_xy.p,
+                       (const int2*)h->sm_beams.p, n_probes, h->sm_Bm, c.nx, c.ny, 1.0 / (c.nx * c.dx), 1.0 / (c.ny * c.dy), 1.0 / (c.nx * c.dx),
+                       1.0 / (c.ny * c.dy), c.wavelength, scale, (int)h->have_aberr, ab);
+    HIPCHK(h, hipGetLastError());
+    if ((rc = mark_launch(h, K_OTHER))) return rc;
+    // the synthesised waves go to the work buffer (MSL_BUF_EXIT) and to the probe buffer, which the spectrum transform consumes
+    h->have_probes = false;
+    const bool vec = c.ny % 2 == 0 && h->pitch % 2 == 0;
+    if (n_probes > 8) launch_synth<16>(h, vec, c.nx / h->sm_fx, c.ny / h->sm_fy);
+    else launch_synth<8>(h, vec, c.nx / h->sm_fx, c.ny / h->sm_fy);
+    HIPCHK(h, hipGetLastError());
+    if ((rc = mark_launch(h, K_OTHER))) return rc;
+    h->have_exit = true;
+    // fftshift(fft2(.)) into the frame slot: the row transform along y, then the exit epilogue -- the sequence of the layer tap
+    if (h->Ry) {
+        RowJob r = row_job(h, h->psi0, n_probes, h->pitch);
+        r.do_fft = true;
+        rc = launch_row_fast(h, r, K_OTHER);
+    } else {
+        LineArgs r = row_args(h, h->psi0, h->psi0, n_probes, h->pitch);
+        r.fft1 = +1;
+        rc = launch_lines(h, h->plan_y, r, K_OTHER);
+    }
+    if (rc || (rc = epilogue_x_pass(h, slot, 1, h->psi0))) return rc;
+    h->cur = nullptr;
+    const uint64_t img = (uint64_t)c.nx * c.ny * 8ull;
+    h->ctr.algorithmic_bytes += (uint64_t)h->sm_Bm * img * (uint64_t)((n_probes + 7) / 8) + (uint64_t)n_probes * (img * 4 + (uint64_t)h->wpix * 8ull);
+    return c.launch_timing ? timer.end(h, &h->ctr.ms_propagate) : MSL_OK;
+}
+
+int msl_smatrix_end(msl_handle* h) {
+    if (!h) return fail(h, MSL_ERR_INVALID, "msl_smatrix_end: null handle");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    smatrix_release(h);
+    return MSL_OK;
+}
+
 int msl_tacaw(msl_handle* h, const void* d_src, void* d_dst, int64_t batch, int32_t T, int64_t npix) {
     if (!h) return fail(h, MSL_ERR_INVALID, "null handle");
     HIPCHK(h, hipSetDevice(h->cfg.device));
@@ -2390,6 +2562,7 @@ size_t msl_buffer_bytes(const msl_handle* h, msl_buffer what) {
         case MSL_BUF_STREAM_S2: return (h->st_open && h->st_s2) ? h->wpix * c.n_probes * 8 : 0;
         case MSL_BUF_STREAM_REF: return (h->st_open && h->st_have_ref) ? h->wpix * c.n_probes * 8 : 0;
         case MSL_BUF_LAYERS: return h->wf ? (n_taps(h) + 1) * layer_block_elems(h) * 8 : 0;
+        case MSL_BUF_SMATRIX: return h->sm_built ? npix * (size_t)h->sm_Bm * 8 : 0;
     }
     return 0;
 }
@@ -2416,6 +2589,7 @@ void* msl_device_ptr(msl_handle* h, msl_buffer what) {
         case MSL_BUF_STREAM_S2: return h->st_open ? h->st_s2.p : nullptr;
         case MSL_BUF_STREAM_REF: return (h->st_open && h->st_have_ref) ? h->st_ref.p : nullptr;
         case MSL_BUF_LAYERS: return h->layers;
+        case MSL_BUF_SMATRIX: return h->sm_S;
     }
     return nullptr;
 }
