@@ -285,6 +285,21 @@ int  msl_adf(msl_handle* h, const void* d_src_c64, int64_t B, int64_t T, int64_t
 int  msl_set_detectors(msl_handle* h, int32_t n, const uint16_t* member_K, const int32_t* signal_n, const float* kx_wx, const float* ky_wy);
 int  msl_detect(msl_handle* h, const void* d_src_c64, int64_t B, int64_t T, int64_t K, int64_t ld, int32_t t0, int32_t count, double* out);
 
+/* ---- spectrum detectors: energy-resolved detector signals of a TACAW intensity, per probe batch ----
+ * msl_spectrum_detect: out[(b*count + j)*n + d] = sum_k w_d(k) I[b, f0+j, k] over a (B,F,K) float32 intensity with row pitch ld (0: K),
+ *   w_d the memberships of the n detectors of the last msl_set_detectors: every detector in ONE pass over the intensity, where
+ *   msl_tacaw_spectrum takes one pass and one host round trip per mask.  d_src == NULL: the handle's intensity buffer as left by
+ *   msl_tacaw / msl_tacaw_layer / a finished stream (F its frequency count, K = stored pixels, ld its own pitch); B <= 0 there means
+ *   n_probes, a smaller B leaves the last probes out (a padded probe batch).  out is HOST memory, B*count*n float64.
+ *   MSL_ERR_STATE without detectors, or with d_src == NULL and no intensity.  MSL_ERR_INVALID when a detector's signal is not
+ *   MSL_DET_INTENSITY (an amplitude or centre-of-mass weight of a TACAW intensity is not defined here), when K is not the K of the
+ *   detector set-up, ld < K, count < 1 or [f0, f0+count) leaves [0, F).  One launch over every row and detector plus the float64
+ *   finishing launch of msl_detect; 16-byte loads when ld % 4 == 0 and the base is 16-byte aligned (else 8 or 4 bytes), the pad
+ *   pixels [K, ld) are never read; fp32 partials over at most 1024 pixels (non-negative addends), float64 from there on, no atomics
+ *   (bitwise reproducible).
+ *   Replaces, per probe batch, the loop of TACAWData.spectrum_image (tacaw_data.py:145-179) over a (P,F,nx,ny) array. */
+int  msl_spectrum_detect(msl_handle* h, const void* d_src_f32, int64_t B, int64_t F, int64_t K, int64_t ld, int32_t f0, int32_t count, double* out);
+
 /* ---- diffraction patterns: frame-summed |Psi|^2 on a pixelated detector (CBED / 4D-STEM), per probe batch ----
  * msl_diffract: out[(b*mx + ix)*my + iy] = sum_{j<count} sum_{a<bx} sum_{c<by} |Psi[b, t0+j, (ix*bx+a)*wy + iy*by+c]|^2 over a (B,T,K = wx*wy)
  *   complex64 array with row pitch ld, mx = wx/bx, my = wy/by: the SUM over the count frame slots (the caller divides for the

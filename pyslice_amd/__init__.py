@@ -16,9 +16,11 @@ from .diffraction_data import Diffraction, DiffractionData
 from .aberrations import Aberrations, scherzer_defocus
 from .imaging import Imaging
 from .image_data import ImageData
+from .spectroscopy import Spectroscopy
+from .spectrum_image_data import SpectrumImageData
 
 __all__ = ["Trajectory", "WFData", "Potential", "gridFromTrajectory", "getZfromElementName", "loadKirkland",
            "Probe", "Propagate", "create_batched_probes", "probe_grid", "wavelength", "m_effective",
            "MultisliceCalculator", "TACAWData", "HAADFData", "Detector", "STEMData", "Diffraction", "DiffractionData",
-           "Aberrations", "scherzer_defocus", "Imaging", "ImageData"]
+           "Aberrations", "scherzer_defocus", "Imaging", "ImageData", "Spectroscopy", "SpectrumImageData"]
 __version__ = "0.1.0"

@@ -30,7 +30,7 @@ EXPORTS = [
     "msl_tacaw_stream_begin", "msl_tacaw_stream_push", "msl_tacaw_stream_finish",
     "msl_tacaw_stream_set_reference", "msl_tacaw_stream_finish_range",
     "msl_set_layers", "msl_download_layers_c128", "msl_tacaw_layer",
-    "msl_set_detectors", "msl_detect", "msl_diffract",
+    "msl_set_detectors", "msl_detect", "msl_spectrum_detect", "msl_diffract",
     "msl_coherent_reset", "msl_coherent_add", "msl_coherent_finish",
     "msl_image_reset", "msl_image_add", "msl_image_download",
     "msl_smatrix_begin", "msl_smatrix_beams", "msl_smatrix_build", "msl_smatrix_probes", "msl_smatrix_end",
@@ -120,6 +120,7 @@ def load():
         "msl_tacaw_layer": (C.c_int, [vp, i32]),
         "msl_set_detectors": (C.c_int, [vp, i32, vp, vp, vp, vp]),
         "msl_detect": (C.c_int, [vp, vp, i64, i64, i64, i64, i32, i32, vp]),
+        "msl_spectrum_detect": (C.c_int, [vp, vp, i64, i64, i64, i64, i32, i32, vp]),
         "msl_diffract": (C.c_int, [vp, vp, i64, i64, i64, i64, i32, i32, i32, i32, i32, i32, vp]),
         "msl_coherent_reset": (C.c_int, [vp, i64]),
         "msl_coherent_add": (C.c_int, [vp, vp, i64, i64, i64, i64, i32, i32]),
@@ -492,6 +493,20 @@ class Engine:
         count = (T - int(t0)) if count is None else int(count)
         out = np.empty((max(b, 0), max(count, 0), getattr(self, "n_detectors", 0)), dtype=np.float64)
         self._chk(self._lib.msl_detect(self._h, p, b, T, k, ld, int(t0), count, _ptr(out)))
+        return out
+
+    # -- spectrum detectors (msl_spectrum_detect)
+    def spectrum_detect(self, f0=0, count=None, B=None, src=None):
+        """(B, count, n_detectors) float64: the intensity inside every detector at the frequency bins [f0, f0+count), all detectors
+        in one pass.  src = None: the handle's own intensity buffer (after tacaw() / a finished stream; B = n_probes or fewer: the
+        first B probes); else (device pointer, B, F, K[, ld]) of a caller's float32 (B, F, K) intensity"""
+        if src is None:
+            p, b, F, k, ld = None, int(B) if B else self.n_probes, self.intensity_F, self.wx * self.wy, 0
+        else:
+            p, b, F, k, ld = self._src(src)
+        count = (F - int(f0)) if count is None else int(count)
+        out = np.empty((max(b, 0), max(count, 0), getattr(self, "n_detectors", 0)), dtype=np.float64)
+        self._chk(self._lib.msl_spectrum_detect(self._h, p, b, F, k, ld, int(f0), count, _ptr(out)))
         return out
 
     # -- diffraction patterns (msl_diffract)

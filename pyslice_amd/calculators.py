@@ -125,7 +125,8 @@ class MultisliceCalculator:
 
     def __init__(self, device=None, force_cpu=False, *, output="host", dtype="complex128", progress=True,
                  gather="rank0", cache=False, k_window=None, frame_batch=None, k_bin=None, stream_tile=None, layers=None,
-                 detectors=None, probe_batch=None, diffraction=None, aberrations=None, imaging=None, prism=None):
+                 detectors=None, probe_batch=None, diffraction=None, aberrations=None, imaging=None, prism=None,
+                 spectroscopy=None):
         """
         device / force_cpu: as the reference (calculators.py:41).  There is no CPU path here, so
         force_cpu=True raises.  Keyword-only extras (not in the reference):
@@ -182,6 +183,15 @@ class MultisliceCalculator:
                    stay on the full grid (zeros outside the window), so k_window, k_bin, aberrations, detectors and probe_batch
                    work as before.  Needs aperture > 0 and an interpolation that divides the grid (setup() raises ValueError).
                    Not built: Diffraction(split=True), imaging, layers, stream_tile, cache, several ranks.
+          spectroscopy spectrum-image mode: a spectroscopy.Spectroscopy(detectors=[...]).  run_spectrum_image() streams the probes
+                   through the device in batches; per probe batch ALL T frames go into a ring of T frame slots, msl_tacaw turns the
+                   ring into the TACAW intensity and msl_spectrum_detect sums it over every detector in one pass: the result is
+                   the spectrum of every detector at every probe position, (P, T, D) float64 on the host, and device memory does
+                   not grow with the number of probe positions.  The ring and its intensity cost 12 * Pc * T * stored pixels
+                   bytes: k_window is the way to make the T frames of a probe fit (the detectors see the window only), setup()
+                   halves the probe batch while they do not and raises MemoryError at one probe.  run() and the other run modes
+                   are refused.  Allowed with k_window, aberrations, frame_batch, probe_batch; not with detectors, diffraction,
+                   imaging, prism, layers, cache, stream_tile, k_bin or several ranks.  Needs at least 2 frames.
         """
         if force_cpu:
             raise NotImplementedError("pyslice_amd has no CPU path (force_cpu=True): use the reference for CPU runs")
@@ -211,6 +221,18 @@ class MultisliceCalculator:
                 raise ValueError("streaming TACAW keeps the exit wave only: stream_tile cannot be combined with layers")
             layers = list(layers)
         self._layers_arg = layers
+        if spectroscopy is not None:
+            from .spectroscopy import Spectroscopy
+            if not isinstance(spectroscopy, Spectroscopy):
+                raise ValueError(f"spectroscopy: expected a Spectroscopy object, got {spectroscopy!r}")
+            # a spectrum image owns the detectors and the result ring (T slots of one probe batch), and needs the exit wave of
+            # every frame of a probe at once
+            for what, val in (("detectors", detectors is not None), ("diffraction", diffraction is not None),
+                              ("imaging", imaging is not None), ("prism", prism is not None), ("layers", layers is not None),
+                              ("cache", cache), ("stream_tile", stream_tile is not None), ("k_bin", k_bin is not None)):
+                if val:
+                    raise ValueError(f"spectroscopy cannot be combined with {what}")
+        self._spectroscopy = spectroscopy
         if prism is not None:
             if not isinstance(prism, Prism):
                 raise ValueError(f"prism: expected a Prism object, got {prism!r}")
@@ -222,7 +244,7 @@ class MultisliceCalculator:
                 raise NotImplementedError("prism with Diffraction(split=True) is not built: the elastic / thermal-diffuse split of "
                                           "PRISM waves")
         self._prism = prism
-        if probe_batch is not None and detectors is None and diffraction is None and imaging is None:
+        if probe_batch is not None and detectors is None and diffraction is None and imaging is None and spectroscopy is None:
             raise ValueError("probe_batch applies to detector and diffraction runs only: give detectors=[...] or diffraction=Diffraction(...)")
         if probe_batch is not None and int(probe_batch) < 1:
             raise ValueError("probe_batch must be a positive probe count")
@@ -333,6 +355,9 @@ class MultisliceCalculator:
         if self.probe_positions is None:
             self.probe_positions = [(lx / 2, ly / 2)]
         self._rank, self._world = distributed.rank_world()
+        if self._spectroscopy is not None:
+            self._setup_spectrum_image(trajectory, slice_axis)
+            return
         if self._detectors is not None or self._diffraction is not None or self._imaging is not None:
             self._setup_probe_batches(trajectory, slice_axis)
             return
@@ -429,6 +454,46 @@ class MultisliceCalculator:
         if self._prism is not None:
             self._engine.smatrix_begin(self._prism.interpolation, self.aperture)
 
+    def _setup_spectrum_image(self, trajectory, slice_axis):
+        """setup() of run_spectrum_image(): every check on the host first, then an engine of Pc <= P probes whose result ring has
+        T frame slots (every frame of a probe batch is on the device when msl_tacaw runs) and whose potentials use a frame batch,
+        then the detector memberships onto it"""
+        if self._world > 1:
+            raise NotImplementedError("spectroscopy: runs over several ranks are not supported (run_spectrum_image() is single-process)")
+        if trajectory.n_frames < 2:
+            raise ValueError(f"spectroscopy: TACAW needs at least 2 frames, the trajectory has {trajectory.n_frames}")
+        from .stem_data import detector_bitmask
+        dets = self._spectroscopy.detectors
+        kxs, kys = self._k_axes()
+        bits = detector_bitmask(dets, kxs, kys, wavelength(self.voltage_eV))
+        for d, det in enumerate(dets):
+            if not ((bits >> d) & 1).any():
+                raise ValueError(f"detector {det.name!r} contains no stored pixel of the {len(kxs)} x {len(kys)} spectrum")
+        n_slices = self._setup_run(trajectory, slice_axis)
+        self._frames = list(range(self.n_frames))
+        T = self.n_frames
+        auto = self._probe_batch is None
+        Pc = min(self.n_probes, 256 if auto else self._probe_batch)
+        batch = self._frame_batch if self._frame_batch is not None else default_frame_batch(Pc, n_slices, self.nx, self.ny)
+        batch = max(1, min(batch, T))
+        free_b = _free_device_bytes(self.device) if auto else None
+        if free_b is not None:                                  # (an explicit probe_batch is honoured as is)
+            Pc = self._fit_spectrum_batch(free_b, Pc, batch)
+
+        def shrink(Pc, slots, batch):                           # the probe batch first, then the frame batch; the ring keeps T slots
+            if not auto or (Pc <= 1 and batch <= 1):
+                return None
+            if Pc > 1:
+                Pc = max(1, Pc // 2)
+            else:
+                batch = max(1, batch // 2)
+            logger.info(f"device memory: probe batch {Pc}, frame batch {batch}")
+            return Pc, slots, batch
+        self._create_engine(Pc, T, batch, shrink, device=_device_index(self.device))
+        self.probe_batch = self._engine.n_probes
+        self._configure_engine()                                # (the aberrations are read by the set_probes of every probe batch)
+        self._engine.set_detectors(bits.reshape(-1), [d.signal for d in dets], kxs, kys)
+
     def _setup_run(self, trajectory, slice_axis):
         """what every engine set-up takes from the trajectory and the slice axis, stored once -> the number of slices"""
         self.base_probe = Probe(self.xs, self.ys, self.aperture, self.voltage_eV, device=self.device, aberrations=self._aberrations)
@@ -490,6 +555,24 @@ class MultisliceCalculator:
         while Pc > 1 and (Pc * batch * (32.0 * nx * ny + 8.0 * pitch) + Pc * coh + batch * 16.0 * n_slices * nx * ny + tables + smatrix + 1e9
                           > 0.9 * free_b):
             Pc = max(1, Pc // 2)
+        return Pc
+
+    def _fit_spectrum_batch(self, free_b, Pc, batch):
+        """Spectrum-image runs: the default probe batch, halved while the result ring of Pc x T images and its TACAW intensity
+        ((8 + 4) * pitch bytes per probe and frame), the three work buffers of Pc x batch images, the transmission stacks of the
+        frame batch and the phase tables exceed 0.9 x the free device memory.  When one probe does not fit either, MemoryError: a
+        smaller k_window is what shrinks the T frames of a probe."""
+        nx, ny, n_slices, T = self.nx, self.ny, len(self._slice_coords), self.n_frames
+        pitch = self._stored_shape()[2]
+        tables = self._phase_table_bytes(batch)
+
+        def need(Pc):
+            return Pc * T * pitch * (8.0 + 4.0) + Pc * batch * 32.0 * nx * ny + batch * 16.0 * n_slices * nx * ny + tables + 1e9
+        while Pc > 1 and need(Pc) > 0.9 * free_b:
+            Pc = max(1, Pc // 2)
+        if need(Pc) > 0.9 * free_b:
+            raise MemoryError(f"spectroscopy: one probe x {T} frames of {pitch} stored pixels needs {need(1) / 1e9:.2f} GB of device memory, "
+                              f"{free_b / 1e9:.2f} GB are free: keep fewer pixels with k_window=(wx, wy)")
         return Pc
 
     def _create_engine(self, n_probes, slots, batch, shrink, **engine_kw):
@@ -586,7 +669,7 @@ class MultisliceCalculator:
             bar.update(1)
         bar.close()
 
-    def _frames_inside_loop(self, reduce_batch, finish_batch, coherent=True):
+    def _frames_inside_loop(self, reduce_batch, finish_batch, coherent=True, own_slots=False):
         """The other loop order, for the elastic / thermal-diffuse split of run_diffraction(): probe batches outside, frame batches
         inside, because |<Psi>|^2 needs the coherent sum over ALL frames of a probe while its accumulator (16 * pitch bytes per
         probe) is on the device.  Per probe batch: set_probes once (a potential build leaves the probes alone), coherent_reset;
@@ -594,7 +677,9 @@ class MultisliceCalculator:
         coherent_add of the n new frames; then finish_batch(p0, real).  The price: the potentials of every frame are built once
         per probe batch, ceil(P / Pc) times instead of once -- except when the whole trajectory is one frame batch, which is
         built once before the probe loop.  run_images() takes the same order with coherent=False (its accumulator holds one probe
-        batch too): no coherent_* call is made."""
+        batch too): no coherent_* call is made.  own_slots=True (run_spectrum_image(), whose ring has a slot for every frame): frame
+        batch s0 goes to result slots s0 .. s0+n-1 instead of 0 .. n-1, so that all T frames of the probe batch are in the ring when
+        finish_batch runs."""
         eng, batches = self._engine, self._frame_batches()
         bar = _Progress(self._progress, -(-self.n_probes // eng.n_probes) * self.n_frames)
         once = self.n_frames <= eng.frame_batch
@@ -605,7 +690,7 @@ class MultisliceCalculator:
             if coherent:
                 eng.coherent_reset()
             for s0, n in batches:
-                self._build_and_propagate(s0, n, 0, build=not once)
+                self._build_and_propagate(s0, n, s0 if own_slots else 0, build=not once)
                 reduce_batch(p0, real, s0, n)
                 if coherent:
                     eng.coherent_add(0, n, B=real)
@@ -632,6 +717,8 @@ class MultisliceCalculator:
         float64 accumulator on the device), which builds the potentials of every frame once per probe batch instead of once, and
         the host holds a second (P, mx, my) array.  intensity and stem are computed by the same calls as without the split."""
         from .diffraction_data import DiffractionData, bin_centres
+        if self._spectroscopy is not None:
+            raise RuntimeError("spectroscopy is set: the device holds one probe batch at a time -- call run_spectrum_image()")
         if self._diffraction is None:
             raise RuntimeError("run_diffraction() needs MultisliceCalculator(diffraction=Diffraction(...))")
         if self._engine is None:
@@ -675,6 +762,8 @@ class MultisliceCalculator:
         and divided by the number of frames.  -> ImageData with intensity (P, L, F, nx, ny) float64, L = 1.  As for the split of
         run_diffraction(), the potentials of every frame are built once per probe batch unless the trajectory is one frame batch."""
         from .image_data import ImageData
+        if self._spectroscopy is not None:
+            raise RuntimeError("spectroscopy is set: the device holds one probe batch at a time -- call run_spectrum_image()")
         if self._imaging is None:
             raise RuntimeError("run_images() needs MultisliceCalculator(imaging=Imaging(...))")
         if self._engine is None:
@@ -704,10 +793,54 @@ class MultisliceCalculator:
                          defocus=np.asarray(im.defocus_series, dtype=np.float64), layer=np.asarray(self._layers, dtype=np.int64),
                          n_frames=T, probe_positions=self.probe_positions, imaging=im)
 
+    def run_spectrum_image(self):
+        """Energy-resolved detector signals of every probe position: probe batches outside, frame batches inside
+        (_frames_inside_loop), because the time transform needs ALL frames of a probe.  Per probe batch: set_probes once; per frame
+        batch the potentials and the slice loop into the ring's frame slots s0 ..; then msl_tacaw turns the (Pc, T, pitch) ring into
+        its intensity, | fftshift_t fft_t(Psi - <Psi>_t) |^2 (tacaw_data.py:89-104; the zero-frequency bin is zero), and ONE
+        msl_spectrum_detect pass sums it over the stored pixels of every detector -> rows p0 .. p0+real-1 of the result.  With
+        Spectroscopy(stem=True) msl_detect reads the same ring for the per-frame signals run_detectors() returns.
+        -> SpectrumImageData with spectra (P, T, D) float64.  Device memory does not depend on the number of probe positions.  As for
+        the split of run_diffraction(), the potentials of every frame are built once per probe batch, ceil(P / Pc) times instead of
+        once, unless the whole trajectory is one frame batch, which is built once before the probe loop."""
+        from .spectrum_image_data import SpectrumImageData
+        if self._spectroscopy is None:
+            raise RuntimeError("run_spectrum_image() needs MultisliceCalculator(spectroscopy=Spectroscopy(...))")
+        if self._engine is None:
+            raise RuntimeError("call setup() before run_spectrum_image()")
+        eng, dets = self._engine, self._spectroscopy.detectors
+        t0 = time.time()
+        P, T, D = self.n_probes, self.n_frames, len(dets)
+        spectra = np.zeros((P, T, D), dtype=np.float64)
+        signals = np.zeros((P, T, D), dtype=np.float64) if self._spectroscopy.stem else None
+
+        def reduce_batch(p0, real, s0, n):                      # (nothing per frame batch: the transform needs every frame)
+            pass
+
+        def finish_batch(p0, real):
+            eng.tacaw()
+            spectra[p0:p0 + real] = eng.spectrum_detect(B=real)
+            if signals is not None:
+                signals[p0:p0 + real] = eng.detect(0, T, B=real)
+        self._frames_inside_loop(reduce_batch, finish_batch, coherent=False, own_slots=True)
+        self.elapsed = time.time() - t0
+        self.frames_computed, self.frames_cached = T, 0
+        stem = None
+        if signals is not None:
+            from .stem_data import STEMData
+            kxs, kys = self._k_axes()
+            stem = STEMData(signals=signals, detectors=list(dets), probe_positions=self.probe_positions,
+                            time=np.arange(T) * self.trajectory.timestep, kxs=_as_tensor(kxs), kys=_as_tensor(kys), probe=self.base_probe)
+        freqs = np.fft.fftshift(np.fft.fftfreq(T, d=self.trajectory.timestep))
+        return SpectrumImageData(spectra=spectra, frequencies=freqs, detectors=list(dets), probe_positions=self.probe_positions,
+                                 n_frames=T, stem=stem)
+
     def run_detectors(self):
         """STEM detector signals of every probe and frame: for each frame batch the potentials are built once, then every probe
         batch goes through the slice loop and msl_detect reduces its exit spectra to the detector values.  -> STEMData with
         signals (P, T, D) float64."""
+        if self._spectroscopy is not None:
+            raise RuntimeError("spectroscopy is set: the device holds one probe batch at a time -- call run_spectrum_image()")
         if self._engine is None:
             raise RuntimeError("call setup() before run_detectors()")
         if self._detectors is None:
@@ -762,6 +895,8 @@ class MultisliceCalculator:
             raise RuntimeError("diffraction is set: the device holds one probe batch at a time -- call run_diffraction()")
         if self._imaging is not None:
             raise RuntimeError("imaging is set: the device holds one probe batch at a time -- call run_images()")
+        if self._spectroscopy is not None:
+            raise RuntimeError("spectroscopy is set: the device holds one probe batch at a time -- call run_spectrum_image()")
         if self._engine is None:
             raise RuntimeError("call setup() before run()")
         if self._stream_tile is not None:

@@ -22,6 +22,7 @@
 #include "tacaw_launch.h"
 #include "layer_tap.h"
 #include "detect.h"
+#include "spectrum_detect.h"
 #include "diffract.h"
 #include "coherent.h"
 #include "image.h"
@@ -2801,6 +2802,70 @@ int msl_detect(msl_handle* h, const void* d_src_c64, int64_t B, int64_t T, int64
     if (ND == 4) hipLaunchKernelGGL(detect_finish_kernel<4>, dim3((unsigned)rows), dim3(256), 0, h->stream, d_part, (long long)n_tiles, n, d_out);
     else if (ND == 8) hipLaunchKernelGGL(detect_finish_kernel<8>, dim3((unsigned)rows), dim3(256), 0, h->stream, d_part, (long long)n_tiles, n, d_out);
     else hipLaunchKernelGGL(detect_finish_kernel<16>, dim3((unsigned)rows), dim3(256), 0, h->stream, d_part, (long long)n_tiles, n, d_out);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return MSL_OK;
+}
+
+// ---- spectrum detectors (spectrum_detect.h) ---------------------------------------------------------------
+extern "C++" template <int ND>
+static void launch_spectrum_detect(msl_handle* h, int vw, dim3 grid, const float* src, long long F, long long f0, long long count, long long ld,
+                                   long long K, long long rows, int rows_per_wg, float* part, int n, double* out) {
+#define MSL_SPD_LAUNCH(V)                                                                                                          \
+    hipLaunchKernelGGL((spectrum_tile_kernel<ND, V>), grid, dim3(256), 0, h->stream, src, F, f0, count, ld, K, rows, rows_per_wg, \
+                       h->det_mask, part)
+    if (vw == 4) MSL_SPD_LAUNCH(4); else if (vw == 2) MSL_SPD_LAUNCH(2); else MSL_SPD_LAUNCH(1);
+#undef MSL_SPD_LAUNCH
+    hipLaunchKernelGGL(detect_finish_kernel<ND>, dim3((unsigned)rows), dim3(256), 0, h->stream, part, (long long)grid.x, n, out);
+}
+
+int msl_spectrum_detect(msl_handle* h, const void* d_src_f32, int64_t B, int64_t F, int64_t K, int64_t ld, int32_t f0, int32_t count, double* out) {
+    if (!h || !out) return fail(h, MSL_ERR_INVALID, "msl_spectrum_detect: null argument");
+    if (h->det_n == 0) return fail(h, MSL_ERR_STATE, "msl_spectrum_detect: no detectors (call msl_set_detectors)");
+    if (h->det_amp | h->det_cx | h->det_cy)
+        return fail(h, MSL_ERR_INVALID, "msl_spectrum_detect: every detector must have the intensity signal (an amplitude or centre-of-mass "
+                                        "weight of a TACAW intensity is not defined)");
+    if (!d_src_f32) {
+        if (!h->intensity) return fail(h, MSL_ERR_STATE, "msl_spectrum_detect: no intensity (call msl_tacaw)");
+        if (B < 1) B = h->cfg.n_probes;
+        if (B > h->cfg.n_probes) return fail(h, MSL_ERR_INVALID, "msl_spectrum_detect: %lld probes, the handle has %d", (long long)B, h->cfg.n_probes);
+        d_src_f32 = h->intensity; F = h->intensity_F; K = (int64_t)h->wpix; ld = (int64_t)h->intensity_ld;
+    } else if (ld == 0) {
+        ld = K;
+    }
+    if (B < 1 || F < 1 || K < 1 || ld < K)
+        return fail(h, MSL_ERR_INVALID, "msl_spectrum_detect: bad shape (%lld,%lld,%lld) ld %lld", (long long)B, (long long)F, (long long)K, (long long)ld);
+    if ((size_t)K != h->det_K)
+        return fail(h, MSL_ERR_INVALID, "msl_spectrum_detect: rows of %lld pixels, the detectors cover %zu", (long long)K, h->det_K);
+    if (count < 1 || f0 < 0 || (int64_t)f0 + count > F)
+        return fail(h, MSL_ERR_INVALID, "msl_spectrum_detect: frequency bins [%d,%lld) outside [0,%lld)", f0, (long long)f0 + count, (long long)F);
+    const int64_t rows = B * count;
+    if (rows > 0x7fffffffLL) return fail(h, MSL_ERR_UNSUPPORTED, "msl_spectrum_detect: more than 2^31 rows");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    const int n = h->det_n;
+    const int ND = n <= 4 ? 4 : (n <= 8 ? 8 : 16);
+    const int64_t TP = 64 * (64 / ND);
+    const int64_t n_tiles = (K + TP - 1) / TP;
+    if (n_tiles > 0x7fffffffLL) return fail(h, MSL_ERR_UNSUPPORTED, "msl_spectrum_detect: rows too long");
+    // rows per workgroup as in msl_detect: the tile's coefficients are built once per row block; at most 65535 row blocks (grid.y)
+    int64_t per = std::min<int64_t>(64, (rows + 3) / 4 * 4);
+    per = std::max<int64_t>(per, ((rows + 65534) / 65535 + 3) / 4 * 4);
+    const int64_t blocks_y = (rows + per - 1) / per;
+    const size_t part_bytes = ((size_t)rows * n_tiles * ND * sizeof(float) + 255) & ~(size_t)255;
+    const size_t out_bytes = (size_t)rows * n * sizeof(double);
+    int rc;
+    if ((rc = h->scratch.reserve(h, part_bytes + out_bytes))) return rc;
+    float* d_part = (float*)h->scratch.p;
+    double* d_out = (double*)(h->scratch + part_bytes);
+    // pixels per load: the rows start at src + row * ld floats, the tiles at multiples of 256 pixels
+    const uintptr_t base = (uintptr_t)d_src_f32;
+    const int vw = (ld % 4 == 0 && (base & 15) == 0) ? 4 : ((ld % 2 == 0 && (base & 7) == 0) ? 2 : 1);
+    const dim3 grid((unsigned)n_tiles, (unsigned)blocks_y);
+    const float* src = (const float*)d_src_f32;
+    if (ND == 4) launch_spectrum_detect<4>(h, vw, grid, src, F, f0, count, ld, K, rows, (int)per, d_part, n, d_out);
+    else if (ND == 8) launch_spectrum_detect<8>(h, vw, grid, src, F, f0, count, ld, K, rows, (int)per, d_part, n, d_out);
+    else launch_spectrum_detect<16>(h, vw, grid, src, F, f0, count, ld, K, rows, (int)per, d_part, n, d_out);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
