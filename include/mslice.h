@@ -212,6 +212,27 @@ int  msl_frame_batch(const msl_handle* h);
  * Replaces TACAWData.fft_from_wf_data (tacaw_data.py:89-104). */
 int  msl_tacaw(msl_handle* h, const void* d_src_c64, void* d_dst_f32, int64_t batch, int32_t T, int64_t npix);
 
+/* Windowed, segment-averaged (Welch) TACAW spectra.  For every pixel's time line x[0..T), with segment length L, hop (1 <= hop <= L),
+ * S = 1 + (T - L) / hop segments (frames past the last full segment are dropped) and a window w[0..L):
+ *     r_s[n] = x[s hop + n] - x[s hop]
+ *     y_s[n] = g[n] (r_s[n] - mean_n r_s[n]),      g = w sqrt(L / (S sum w^2))       (float64 here, a float32 table on the device)
+ *     I[f]   = sum_s | sum_n y_s[n] exp(-2 pi i f n / L) |^2,      I[0] := 0 exactly
+ * stored fftshifted along f: (batch, L, npix) float32; frequencies = fftshift(fftfreq(L, dt)).  L = T, hop = T and a boxcar window
+ * give msl_tacaw's intensity; otherwise it is scipy.signal.welch(x, window=w, nperseg=L, noverlap=L-hop, detrend='constant',
+ * return_onesided=False, scaling='density') * L outside f = 0.
+ * Pointers as msl_tacaw: both NULL = the handle's own wavefunction buffer into its own intensity buffer, which then holds (P, L, pitch)
+ * (the reductions with d_src == NULL see F = L).  window_L = L non-negative host doubles with sum w^2 > 0, NULL = boxcar.
+ * MSL_ERR_INVALID for T < 2, L > T, hop outside [1, L], a negative, non-finite or all-zero window; MSL_ERR_UNSUPPORTED for an L
+ * without a kernel (msl_tacaw_welch_has) or an image whose rows leave the kernel's 32-bit offsets ((L + 1) / 2 * npix * 8 >= 2^32).
+ * One launch, no atomics: repeated calls are bitwise equal.  The counters take the device time (ms_tacaw) and the bytes the call
+ * reads and writes, batch * npix * (8 S L + 4 L) (algorithmic_bytes).
+ * msl_tacaw_welch_has: 1 if a kernel exists for segment length L (the 2-3-5-7-smooth lengths 16 ... 128), else 0.  No handle, no
+ * device needed.
+ * Not in the reference, whose transform is the bare periodogram (tacaw_data.py:89-104). */
+int  msl_tacaw_welch_has(int32_t L);
+int  msl_tacaw_welch(msl_handle* h, const void* d_src_c64, void* d_dst_f32, int64_t batch, int32_t T, int64_t npix,
+                     int32_t L, int32_t hop, const double* window_L);
+
 /* Streaming TACAW: the time -> frequency transform accumulated tile of frames by tile of frames, for n_bins
  * chosen frequency bins, so that the handle holds a ring of frame slots (msl_config.n_frames = tile length) and the
  * accumulators instead of every frame (the reference needs the whole (P,T,nx,ny) array: tacaw_data.py:94-96).
@@ -409,6 +430,8 @@ int  msl_download_layers_c128(msl_handle* h, int32_t n_frames_used, void* dst_c1
 /* msl_tacaw with d_src == NULL on block `layer` of the layered result (TACAWData(wf, layer_index=layer), tacaw_data.py:61-89):
  * the intensity goes to the handle's own buffer, for the reductions with d_src == NULL. */
 int  msl_tacaw_layer(msl_handle* h, int32_t layer);
+/* msl_tacaw_welch with d_src == NULL on block `layer` of the layered result. */
+int  msl_tacaw_welch_layer(msl_handle* h, int32_t layer, int32_t L, int32_t hop, const double* window_L);
 
 /* Copy a device buffer to the host (dst must hold `bytes` = full buffer size, see msl_buffer_bytes).
  * For MSL_BUF_WAVEFUNCTION / MSL_BUF_INTENSITY the host copy is dense -- (P,T,wx,wy), bytes = P*T*wx*wy*8 or *4, the pixel

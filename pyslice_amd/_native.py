@@ -34,6 +34,7 @@ EXPORTS = [
     "msl_coherent_reset", "msl_coherent_add", "msl_coherent_finish",
     "msl_image_reset", "msl_image_add", "msl_image_download",
     "msl_smatrix_begin", "msl_smatrix_beams", "msl_smatrix_build", "msl_smatrix_probes", "msl_smatrix_end",
+    "msl_tacaw_welch_has", "msl_tacaw_welch", "msl_tacaw_welch_layer",
 ]
 DET_SIGNALS = {"intensity": 0, "amplitude": 1, "com_x": 2, "com_y": 3}      # include/mslice.h: MSL_DET_*
 
@@ -133,6 +134,9 @@ def load():
         "msl_smatrix_build": (C.c_int, [vp]),
         "msl_smatrix_probes": (C.c_int, [vp, vp, i32, i32]),
         "msl_smatrix_end": (C.c_int, [vp]),
+        "msl_tacaw_welch_has": (C.c_int, [i32]),
+        "msl_tacaw_welch": (C.c_int, [vp, vp, vp, i64, i32, i64, i32, i32, vp]),
+        "msl_tacaw_welch_layer": (C.c_int, [vp, i32, i32, i32, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -153,6 +157,11 @@ def line_kernel_class(n: int) -> int:
 def fast_lengths(lo: int = 129, hi: int = 2048):
     """line lengths in [lo, hi] that run on a direct slice-loop kernel"""
     return [n for n in range(int(lo), int(hi) + 1) if line_kernel_class(n) > 0]
+
+
+def welch_has(L: int) -> bool:
+    """is there a device kernel for Welch segment length L (msl_tacaw_welch_has)"""
+    return bool(load().msl_tacaw_welch_has(int(L)))
 
 
 def _raise(rc, msg):
@@ -320,6 +329,31 @@ class Engine:
                                       C.c_void_p(dst_ptr) if dst_ptr else None, int(batch), int(T), int(npix)))
         if not src_ptr:
             self.intensity_F = self.n_frames
+
+    @staticmethod
+    def _welch_window(window, L):
+        """the window argument of msl_tacaw_welch: None (boxcar) or L float64 values"""
+        if window is None:
+            return None
+        w = np.ascontiguousarray(window, dtype=np.float64).reshape(-1)
+        if w.size != int(L):
+            raise ValueError(f"tacaw_welch: window of {w.size} values for segment length {int(L)}")
+        return w
+
+    def tacaw_welch(self, L, hop, window=None, src_ptr=None, dst_ptr=None, batch=0, T=0, npix=0):
+        """windowed, segment-averaged spectra (msl_tacaw_welch): segments of L frames at distance hop, window = None (boxcar) or L
+        non-negative floats.  Pointers as tacaw(): none = the handle's wavefunction buffer into its intensity buffer, (P, L, pitch)"""
+        w = self._welch_window(window, L)
+        self._chk(self._lib.msl_tacaw_welch(self._h, C.c_void_p(src_ptr) if src_ptr else None, C.c_void_p(dst_ptr) if dst_ptr else None,
+                                            int(batch), int(T), int(npix), int(L), int(hop), _ptr(w) if w is not None else None))
+        if not src_ptr:
+            self.intensity_F = int(L)
+
+    def tacaw_welch_layer(self, layer, L, hop, window=None):
+        """msl_tacaw_welch on block `layer` of the layered result into the handle's intensity buffer"""
+        w = self._welch_window(window, L)
+        self._chk(self._lib.msl_tacaw_welch_layer(self._h, int(layer), int(L), int(hop), _ptr(w) if w is not None else None))
+        self.intensity_F = int(L)
 
     @property
     def n_layers(self):

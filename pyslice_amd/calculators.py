@@ -462,6 +462,9 @@ class MultisliceCalculator:
             raise NotImplementedError("spectroscopy: runs over several ranks are not supported (run_spectrum_image() is single-process)")
         if trajectory.n_frames < 2:
             raise ValueError(f"spectroscopy: TACAW needs at least 2 frames, the trajectory has {trajectory.n_frames}")
+        if self._spectroscopy.segment is not None:
+            from . import welch
+            welch.check_segment(self._spectroscopy.segment, trajectory.n_frames, what="spectroscopy")
         from .stem_data import detector_bitmask
         dets = self._spectroscopy.detectors
         kxs, kys = self._k_axes()
@@ -800,7 +803,8 @@ class MultisliceCalculator:
         its intensity, | fftshift_t fft_t(Psi - <Psi>_t) |^2 (tacaw_data.py:89-104; the zero-frequency bin is zero), and ONE
         msl_spectrum_detect pass sums it over the stored pixels of every detector -> rows p0 .. p0+real-1 of the result.  With
         Spectroscopy(stem=True) msl_detect reads the same ring for the per-frame signals run_detectors() returns.
-        -> SpectrumImageData with spectra (P, T, D) float64.  Device memory does not depend on the number of probe positions.  As for
+        With Spectroscopy(segment=L) msl_tacaw_welch takes msl_tacaw's place and the spectra have L bins.
+        -> SpectrumImageData with spectra (P, T, D) float64 ((P, L, D) with a segment).  Device memory does not depend on the number of probe positions.  As for
         the split of run_diffraction(), the potentials of every frame are built once per probe batch, ceil(P / Pc) times instead of
         once, unless the whole trajectory is one frame batch, which is built once before the probe loop."""
         from .spectrum_image_data import SpectrumImageData
@@ -809,16 +813,21 @@ class MultisliceCalculator:
         if self._engine is None:
             raise RuntimeError("call setup() before run_spectrum_image()")
         eng, dets = self._engine, self._spectroscopy.detectors
+        sp = self._spectroscopy
         t0 = time.time()
         P, T, D = self.n_probes, self.n_frames, len(dets)
-        spectra = np.zeros((P, T, D), dtype=np.float64)
+        F = T if sp.segment is None else sp.segment             # (segment=L: Welch's estimate, L frequency bins; msl_tacaw_welch)
+        spectra = np.zeros((P, F, D), dtype=np.float64)
         signals = np.zeros((P, T, D), dtype=np.float64) if self._spectroscopy.stem else None
 
         def reduce_batch(p0, real, s0, n):                      # (nothing per frame batch: the transform needs every frame)
             pass
 
         def finish_batch(p0, real):
-            eng.tacaw()
+            if sp.segment is None:
+                eng.tacaw()
+            else:
+                eng.tacaw_welch(sp.segment, sp.hop, sp.window)
             spectra[p0:p0 + real] = eng.spectrum_detect(B=real)
             if signals is not None:
                 signals[p0:p0 + real] = eng.detect(0, T, B=real)
@@ -831,7 +840,7 @@ class MultisliceCalculator:
             kxs, kys = self._k_axes()
             stem = STEMData(signals=signals, detectors=list(dets), probe_positions=self.probe_positions,
                             time=np.arange(T) * self.trajectory.timestep, kxs=_as_tensor(kxs), kys=_as_tensor(kys), probe=self.base_probe)
-        freqs = np.fft.fftshift(np.fft.fftfreq(T, d=self.trajectory.timestep))
+        freqs = np.fft.fftshift(np.fft.fftfreq(F, d=self.trajectory.timestep))
         return SpectrumImageData(spectra=spectra, frequencies=freqs, detectors=list(dets), probe_positions=self.probe_positions,
                                  n_frames=T, stem=stem)
 

@@ -20,6 +20,7 @@
 #include "stream.h"
 #include "tacaw_time.h"
 #include "tacaw_launch.h"
+#include "tacaw_welch.h"
 #include "layer_tap.h"
 #include "detect.h"
 #include "spectrum_detect.h"
@@ -145,6 +146,8 @@ struct msl_handle {
     int opt_T = 0;
     DevBuf<float2> tsplit_tw;      // W_T^n, n < T: cross-wave butterflies of time_split_kernel, made for tsplit_T frames
     int tsplit_T = 0;
+    DevBuf<float> welch_g;         // msl_tacaw_welch: the window x normalisation table of the last call (welch_g_host, what the device holds)
+    std::vector<float> welch_g_host;
     DevBuf<float2> psiT, psi0T;
     bool need_psi0T = false;
     int keys_cap = 0;              // capacity of d_counts / d_start (slice x species bins)
@@ -1870,6 +1873,71 @@ static int tacaw_resident(msl_handle* h, const float2* block) {
     return tacaw_run(h, block, h->intensity, c.n_probes, c.n_frames, (int64_t)h->wpitch);
 }
 
+// ---- windowed, segment-averaged spectra (tacaw_welch.h) ----
+// the checks of msl_tacaw_welch that need no device, and g = w sqrt(L / (S sum w^2)) in float64 -> float32
+static int welch_table(msl_handle* h, int32_t T, int32_t L, int32_t hop, const double* window, int* S_out, std::vector<float>& g) {
+    if (T < 2) return fail(h, MSL_ERR_INVALID, "msl_tacaw_welch: needs at least 2 frames (got %d)", T);
+    if (L > T) return fail(h, MSL_ERR_INVALID, "msl_tacaw_welch: segment length %d exceeds the %d frames", L, T);
+    if (L < 1 || hop < 1 || hop > L) return fail(h, MSL_ERR_INVALID, "msl_tacaw_welch: hop %d outside [1, %d]", hop, L);
+    double sw2 = 0.0;
+    for (int n = 0; n < L; ++n) {
+        const double w = window ? window[n] : 1.0;
+        if (!(w >= 0.0) || !std::isfinite(w)) return fail(h, MSL_ERR_INVALID, "msl_tacaw_welch: window[%d] = %g is negative or not finite", n, w);
+        sw2 += w * w;
+    }
+    if (!(sw2 > 0.0)) return fail(h, MSL_ERR_INVALID, "msl_tacaw_welch: the window is zero everywhere");
+    if (!time_welch_has(L)) return fail(h, MSL_ERR_UNSUPPORTED, "msl_tacaw_welch: no kernel for segment length %d (2-3-5-7-smooth lengths 16 ... 128)", L);
+    const int S = 1 + (T - L) / hop;
+    const double norm = std::sqrt((double)L / ((double)S * sw2));
+    g.resize(L);
+    for (int n = 0; n < L; ++n) g[n] = (float)((window ? window[n] : 1.0) * norm);
+    *S_out = S;
+    return MSL_OK;
+}
+
+// `batch` (T, npix) blocks of complex spectra src -> (L, npix) blocks of float32 Welch intensities dst (msl_tacaw_welch)
+static int welch_run(msl_handle* h, const float2* src, float* dst, int64_t batch, int32_t T, int64_t npix, int32_t L, int32_t hop, int S,
+                     const std::vector<float>& g) {
+    if (batch < 1 || npix < 1) return fail(h, MSL_ERR_INVALID, "msl_tacaw_welch: bad batch/npix");
+    if (npix > 0x7fffffffLL || batch > 0x7fffffffLL) return fail(h, MSL_ERR_UNSUPPORTED, "msl_tacaw_welch: npix or batch too large");
+    // 32-bit offsets, as for time_direct_kernel: the lane's pixel plus up to (L + 1) / 2 rows through one descriptor
+    if ((unsigned long long)((L + 1) / 2) * (unsigned long long)npix * 8ull >= (1ull << 32))
+        return fail(h, MSL_ERR_UNSUPPORTED, "msl_tacaw_welch: images of %lld pixels leave the 32-bit row offsets at segment length %d", (long long)npix, L);
+    int rc;
+    if (h->welch_g_host != g || !h->welch_g) {
+        // (an earlier launch on the stream may still read the old table)
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        h->welch_g_host.clear();
+        if ((rc = h->welch_g.reserve(h, (size_t)TDIR_MAX))) return rc;
+        HIPCHK(h, hipMemcpy(h->welch_g, g.data(), (size_t)L * sizeof(float), hipMemcpyHostToDevice));
+        h->welch_g_host = g;
+    }
+    WelchJob j{};
+    j.in = src; j.out = dst; j.g = h->welch_g;
+    j.in_image_stride = (long long)T * npix; j.out_image_stride = (long long)L * npix;
+    j.npix = (int)npix; j.n_images = (int)batch; j.L = L; j.hop = hop; j.S = S;
+    EventPair timer;
+    if ((rc = timer.begin(h))) return rc;
+    h->cur = nullptr;
+    if (!time_welch_launch(j, h->n_cus, h->stream)) return fail(h, MSL_ERR_UNSUPPORTED, "msl_tacaw_welch: no kernel for segment length %d", L);
+    HIPCHK(h, hipGetLastError());
+    if ((rc = mark_launch(h, K_OTHER))) return rc;
+    h->ctr.algorithmic_bytes += (uint64_t)batch * (uint64_t)npix * (8ull * (uint64_t)S * (uint64_t)L + 4ull * (uint64_t)L);
+    return timer.end(h, &h->ctr.ms_tacaw);
+}
+
+// msl_tacaw_welch on one (P, T, wpitch) block of the resident result, into the handle's intensity buffer: (P, L, wpitch)
+static int welch_resident(msl_handle* h, const float2* block, int32_t L, int32_t hop, const double* window) {
+    const msl_config& c = h->cfg;
+    int S = 0, rc;
+    std::vector<float> g;
+    if ((rc = welch_table(h, c.n_frames, L, hop, window, &S, g))) return rc;
+    const size_t need = (size_t)c.n_probes * L * h->wpitch;
+    if (h->intensity.n != need && (rc = h->intensity.alloc(h, need))) return rc;
+    h->intensity_F = L; h->intensity_ld = h->wpitch;
+    return welch_run(h, block, h->intensity, c.n_probes, c.n_frames, (int64_t)h->wpitch, L, hop, S, g);
+}
+
 // PRISM: free S, the beams and the coefficients (the stream is idle)
 static void smatrix_release(msl_handle* h) {
     h->sm_S.release(); h->sm_c.release(); h->sm_beams.release();
@@ -2434,6 +2502,24 @@ int msl_tacaw(msl_handle* h, const void* d_src, void* d_dst, int64_t batch, int3
     }
     if (!d_dst) return fail(h, MSL_ERR_INVALID, "msl_tacaw: src given without dst");
     return tacaw_run(h, (const float2*)d_src, (float*)d_dst, batch, T, npix);
+}
+
+int msl_tacaw_welch_has(int32_t L) { return time_welch_has(L) ? 1 : 0; }
+
+int msl_tacaw_welch(msl_handle* h, const void* d_src, void* d_dst, int64_t batch, int32_t T, int64_t npix, int32_t L, int32_t hop,
+                    const double* window_L) {
+    if (!h) return fail(h, MSL_ERR_INVALID, "null handle");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    if (!d_src) {
+        if (!h->wf) return fail(h, MSL_ERR_STATE, "msl_tacaw_welch: no wavefunction buffer");
+        if (d_dst) return fail(h, MSL_ERR_INVALID, "msl_tacaw_welch: dst given without src");
+        return welch_resident(h, h->wf, L, hop, window_L);
+    }
+    if (!d_dst) return fail(h, MSL_ERR_INVALID, "msl_tacaw_welch: src given without dst");
+    int S = 0, rc;
+    std::vector<float> g;
+    if ((rc = welch_table(h, T, L, hop, window_L, &S, g))) return rc;
+    return welch_run(h, (const float2*)d_src, (float*)d_dst, batch, T, npix, L, hop, S, g);
 }
 
 int msl_tacaw_stream_begin(msl_handle* h, int32_t T_total, int32_t n_bins, const int32_t* bins) {
@@ -3355,6 +3441,15 @@ int msl_tacaw_layer(msl_handle* h, int32_t layer) {
     if (layer < 0 || layer >= L) return fail(h, MSL_ERR_INVALID, "msl_tacaw_layer: layer %d outside [0, %d)", layer, L);
     HIPCHK(h, hipSetDevice(h->cfg.device));
     return tacaw_resident(h, h->layers + (size_t)layer * layer_block_elems(h));         // (the last block is wf)
+}
+
+int msl_tacaw_welch_layer(msl_handle* h, int32_t layer, int32_t L, int32_t hop, const double* window_L) {
+    if (!h) return fail(h, MSL_ERR_INVALID, "null handle");
+    if (!h->wf) return fail(h, MSL_ERR_STATE, "msl_tacaw_welch_layer: no wavefunction buffer");
+    const int n = n_taps(h) + 1;
+    if (layer < 0 || layer >= n) return fail(h, MSL_ERR_INVALID, "msl_tacaw_welch_layer: layer %d outside [0, %d)", layer, n);
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    return welch_resident(h, h->layers + (size_t)layer * layer_block_elems(h), L, hop, window_L);         // (the last block is wf)
 }
 
 int msl_download_frame(msl_handle* h, int32_t slot, void* dst, size_t bytes) { return frame_copy(h, slot, dst, bytes, true); }

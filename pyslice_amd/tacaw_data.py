@@ -1,6 +1,6 @@
 """TACAWData -- host mirror of src/postprocessing/tacaw_data.py.
 
-`TACAWData(wfdata, layer_index=None)` keeps the reference behaviour (re-classes itself and aliases
+`TACAWData(wfdata, layer_index=None, segment=None, overlap=0.5, window="hann")` keeps the reference behaviour (re-classes itself and aliases
 `wfdata.__dict__`, quirk Q16) but the time->frequency transform
     intensity[p,w,kx,ky] = | fftshift_t fft_t( Psi - <Psi>_t ) |^2          (tacaw_data.py:89-104)
 runs in the HIP library (msl_tacaw).  When the WFData came from MultisliceCalculator.run() the
@@ -8,6 +8,10 @@ exit waves are still resident on the device and are transformed in place there; 
 array is staged through torch device memory.  The reductions below (spectrum, diffraction, ...;
 tacaw_data.py:109-353) stream the device copy of the intensity once through the library's
 reduction kernels (msl_tacaw_spectrum / _diffraction / _dispersion) and return small host arrays.
+
+With segment=L the transform is Welch's estimate instead of the bare periodogram (welch.py, msl_tacaw_welch): segments of L frames
+at a hop of max(1, L - int(overlap L)), each with its mean removed and multiplied by `window`, their periodograms averaged.  The
+frequency axis then has L entries and the intensity is (P, L, kx, ky); every reduction works on it unchanged.
 """
 from __future__ import annotations
 
@@ -15,7 +19,7 @@ from typing import List, Optional
 
 import numpy as np
 
-from . import _native
+from . import _native, welch
 from .potentials import TORCH_AVAILABLE, _as_tensor
 from .wf_data import WFData
 
@@ -28,33 +32,48 @@ def _np(a):
 
 
 class TACAWData(WFData):
-    def __init__(self, WFData, layer_index: int = None):
+    def __init__(self, WFData, layer_index: int = None, segment: int = None, overlap: float = 0.5, window="hann"):
         # reference tacaw_data.py:39-42: alias the WFData's dict (in-place mutation of the source object)
         self.__dict__ = WFData.__dict__
-        self.fft_from_wf_data(layer_index)
+        self.fft_from_wf_data(layer_index, segment=segment, overlap=overlap, window=window)
 
-    def fft_from_wf_data(self, layer_index: int = None):
+    def fft_from_wf_data(self, layer_index: int = None, segment: int = None, overlap: float = 0.5, window="hann"):
         if layer_index is None:
             layer_index = len(self.layer) - 1
         if layer_index < 0 or layer_index >= len(self.layer):
             raise ValueError(f"layer_index {layer_index} out of range [0, {len(self.layer)-1}]")
         n_freq = len(self.time)
         dt = self.time[1] - self.time[0]
+        wel = None                                  # (L, hop, window values) of a segmented transform
+        if segment is not None:
+            # every rule of the request on the host, before any device work
+            L = welch.check_segment(segment, n_freq, what="TACAWData")
+            hop = welch.hop_of(L, overlap)
+            wel = (L, hop, welch.window(window, L))
+            n_freq = L
         self.frequencies = np.fft.fftshift(np.fft.fftfreq(n_freq, d=dt))
+        self.segment = None if wel is None else wel[0]
+        self.hop = None if wel is None else wel[1]
+        self.n_segments = None if wel is None else welch.segments(len(self.time), wel[0], wel[1])
+        self.window = None if wel is None else (window if isinstance(window, str) else wel[2])
 
         eng = self.__dict__.get("_engine")
         resident = eng is not None and self.__dict__.get("_resident", False)      # every layer of run()'s result is on the device
         shard = self.__dict__.get("_frame_shard")
         if shard is not None and eng is not None:
+            if wel is not None:
+                raise NotImplementedError("TACAWData(segment=...) on a frame-sharded multi-rank result is not built")
             # multi-process run with frame-sharded exit waves still on the devices (gather="none"):
             # all-to-all to probe shards, local time FFT, gather of the intensities on rank 0
             self.intensity = self._tacaw_sharded(eng, shard)
             return
         if resident:
-            if eng.n_layers > 1:
-                eng.tacaw_layer(layer_index)                # thickness series: that layer's block of the resident result
-            else:
+            if eng.n_layers > 1:                            # thickness series: that layer's block of the resident result
+                eng.tacaw_layer(layer_index) if wel is None else eng.tacaw_welch_layer(layer_index, *wel)
+            elif wel is None:
                 eng.tacaw()
+            else:
+                eng.tacaw_welch(*wel)
             self._intensity_src = (eng, None)          # reductions read the library's own buffer
             if self.__dict__.get("_output") == "device":
                 self.intensity = torch.as_tensor(eng.result_view(_native.BUF_INTENSITY, "<f4"), device=f"cuda:{eng.device}")
@@ -70,11 +89,14 @@ class TACAWData(WFData):
         P, T, nx, ny = layer.shape
         dev = torch.device("cuda", torch.cuda.current_device())
         src = layer.to(device=dev, dtype=torch.complex64).contiguous()
-        dst = torch.empty((P, T, nx, ny), dtype=torch.float32, device=dev)
+        dst = torch.empty((P, n_freq, nx, ny), dtype=torch.float32, device=dev)
         torch.cuda.synchronize(dev)
         helper = _native.Engine(2, 2, 1, 1.0, 1.0, 1.0, 1.0, 0.0, n_probes=1, n_frames=0, device=dev.index)
         try:
-            helper.tacaw(src.data_ptr(), dst.data_ptr(), P, T, nx * ny)
+            if wel is None:
+                helper.tacaw(src.data_ptr(), dst.data_ptr(), P, T, nx * ny)
+            else:
+                helper.tacaw_welch(*wel, src_ptr=src.data_ptr(), dst_ptr=dst.data_ptr(), batch=P, T=T, npix=nx * ny)
         finally:
             helper.close()
         self._intensity_src = (None, dst)               # device copy kept for the reductions
