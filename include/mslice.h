@@ -205,6 +205,31 @@ int  msl_build_potentials(msl_handle* h, const double* pos, const int32_t* Z, in
                           int32_t ax1, int32_t ax2, int32_t axs);
 int  msl_frame_batch(const msl_handle* h);
 
+/* ---- frozen phonons: Einstein-model configurations generated on the device ----
+ * A configuration is a pure function of (seed, configuration index c, atom index i) -- pyslice_amd/thermal.py is the definition:
+ *   x0..x3 = Philox-4x32-10(counter (i, c & 0xffffffff, c >> 32, 0), key (seed & 0xffffffff, seed >> 32)),  u_j = (x_j + 0.5) 2^-32,
+ *   pos = pos0 + sigma_i * (sqrt(-2 ln u0) cos(2 pi u1), sqrt(-2 ln u0) sin(2 pi u1), sqrt(-2 ln u2) cos(2 pi u3))
+ * in columns 0, 1, 2 of the positions whatever the axes are, in float64, not wrapped and not clipped: the slice rule of
+ * msl_build_potential treats the result as it treats an MD frame (an atom pushed out of the stack is dropped).
+ * msl_set_structure:  uploads ONCE the base positions pos0 (n_atoms x 3 doubles), the atomic numbers Z (1..103), the rms displacement
+ *   sigma per atom and Cartesian axis (Angstrom, finite and >= 0) and the species maps; they stay resident on the handle until the
+ *   next msl_set_structure or msl_destroy.  Axes as msl_build_potential.  MSL_ERR_INVALID names a bad Z or sigma.  Synchronous: no
+ *   pointer into caller memory is kept.
+ * msl_build_thermal:  the potentials and transmission functions of the configurations first_config .. first_config + count - 1
+ *   (1 <= count <= frame_batch, first_config >= 0) into the batch slots 0 .. count-1, as msl_build_potentials fed those positions; at
+ *   a frame batch of 1 into the selected slot, as msl_build_potential.  The same sequence of launches with one stage exchanged:
+ *   thermal_positions_kernel writes the positions where msl_build_potentials copies them to, so nothing per frame crosses PCIe or
+ *   is staged on the host, and the result is bit for bit that of msl_build_potentials given msl_thermal_positions' arrays.
+ *   MSL_ERR_INVALID without msl_set_structure.  Queued on the stream like msl_build_potential.
+ * msl_thermal_positions: the positions the device generates for one configuration, n_atoms x 3 doubles, downloaded (waits for the
+ *   stream).
+ * Not built: anisotropic or per-axis widths, correlated (phonon-mode) displacements, wrapping at the entrance and exit surfaces.
+ * Not in the reference, whose Trajectory.generate_random_displacements (trajectory.py:226) fabricates uniform noise on the host. */
+int  msl_set_structure(msl_handle* h, const double* pos0, const int32_t* Z, const double* sigma, int64_t n_atoms,
+                       int32_t ax1, int32_t ax2, int32_t axs);
+int  msl_build_thermal(msl_handle* h, uint64_t seed, int64_t first_config, int32_t count);
+int  msl_thermal_positions(msl_handle* h, uint64_t seed, int64_t config, double* out);
+
 /* TACAW: intensity[p,w,kx,ky] = | fftshift_t fft_t( Psi - <Psi>_t ) |^2 over a (B,T,npix) c64 device
  * array.  src == NULL uses the handle's own wavefunction buffer (B=P, T=T_local, npix=nx*ny) and
  * its own intensity buffer.  With src/dst given (device pointers, e.g. the output of an RCCL

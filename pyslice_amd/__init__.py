@@ -5,6 +5,7 @@ FFT / transmission / Fresnel slice loop, exit-wave FFT, TACAW time FFT) runs in 
 library `libmslice.so` (include/mslice.h, pyslice_amd/csrc).  There is no CPU fallback.
 """
 from .trajectory import Trajectory
+from .thermal import FrozenPhonons, sigma_from_B
 from .wf_data import WFData
 from .potentials import Potential, gridFromTrajectory, getZfromElementName, loadKirkland
 from .multislice import Probe, Propagate, create_batched_probes, probe_grid, wavelength, m_effective
@@ -19,7 +20,7 @@ from .image_data import ImageData
 from .spectroscopy import Spectroscopy
 from .spectrum_image_data import SpectrumImageData
 
-__all__ = ["Trajectory", "WFData", "Potential", "gridFromTrajectory", "getZfromElementName", "loadKirkland",
+__all__ = ["Trajectory", "FrozenPhonons", "sigma_from_B", "WFData", "Potential", "gridFromTrajectory", "getZfromElementName", "loadKirkland",
            "Probe", "Propagate", "create_batched_probes", "probe_grid", "wavelength", "m_effective",
            "MultisliceCalculator", "TACAWData", "HAADFData", "Detector", "STEMData", "Diffraction", "DiffractionData",
            "Aberrations", "scherzer_defocus", "Imaging", "ImageData", "Spectroscopy", "SpectrumImageData"]

@@ -35,6 +35,7 @@ EXPORTS = [
     "msl_image_reset", "msl_image_add", "msl_image_download",
     "msl_smatrix_begin", "msl_smatrix_beams", "msl_smatrix_build", "msl_smatrix_probes", "msl_smatrix_end",
     "msl_tacaw_welch_has", "msl_tacaw_welch", "msl_tacaw_welch_layer",
+    "msl_set_structure", "msl_build_thermal", "msl_thermal_positions",
 ]
 DET_SIGNALS = {"intensity": 0, "amplitude": 1, "com_x": 2, "com_y": 3}      # include/mslice.h: MSL_DET_*
 
@@ -137,6 +138,9 @@ def load():
         "msl_tacaw_welch_has": (C.c_int, [i32]),
         "msl_tacaw_welch": (C.c_int, [vp, vp, vp, i64, i32, i64, i32, i32, vp]),
         "msl_tacaw_welch_layer": (C.c_int, [vp, i32, i32, i32, vp]),
+        "msl_set_structure": (C.c_int, [vp, vp, vp, vp, i64, i32, i32, i32]),
+        "msl_build_thermal": (C.c_int, [vp, C.c_uint64, i64, i32]),
+        "msl_thermal_positions": (C.c_int, [vp, C.c_uint64, i64, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -303,6 +307,39 @@ class Engine:
             raise ValueError(f"slice_axis must be 0, 1 or 2, got {slice_axis}")
         axes.remove(slice_axis)
         self._chk(self._lib.msl_build_potentials(self._h, _ptr(pos), _ptr(z), pos.shape[1], pos.shape[0], axes[0], axes[1], slice_axis))
+
+    # -- frozen phonons (msl_set_structure / msl_build_thermal / msl_thermal_positions; the definition is thermal.py)
+    def set_structure(self, positions, Z, sigma, slice_axis=2):
+        """the base structure of the configurations, resident on the handle from here on: positions (n_atoms, 3), Z, and the rms
+        displacement sigma of every atom along each Cartesian axis"""
+        pos = np.ascontiguousarray(positions, dtype=np.float64)
+        if pos.ndim != 2 or pos.shape[1] != 3:
+            raise ValueError(f"positions must be (n_atoms,3), got {pos.shape}")
+        z = np.ascontiguousarray(Z, dtype=np.int32)
+        sg = np.ascontiguousarray(sigma, dtype=np.float64)
+        if z.shape != (pos.shape[0],):
+            raise ValueError("one atomic number per atom required")
+        if sg.shape != (pos.shape[0],):
+            raise ValueError("one width per atom required")
+        axes = [0, 1, 2]
+        if slice_axis not in axes:
+            raise ValueError(f"slice_axis must be 0, 1 or 2, got {slice_axis}")
+        axes.remove(slice_axis)
+        self._structure_atoms = None
+        self._chk(self._lib.msl_set_structure(self._h, _ptr(pos), _ptr(z), _ptr(sg), pos.shape[0], axes[0], axes[1], slice_axis))
+        self._structure_atoms = pos.shape[0]
+
+    def build_thermal(self, seed, first_config, count=1):
+        """potentials of the configurations first_config .. first_config+count-1 of the structure (count <= frame_batch) into the
+        batch slots 0..count-1 (the selected slot at a frame batch of 1), their positions generated on the device"""
+        self._chk(self._lib.msl_build_thermal(self._h, int(seed), int(first_config), int(count)))
+
+    def thermal_positions(self, seed, config):
+        """(n_atoms, 3) float64: the positions the device generates for one configuration"""
+        n = getattr(self, "_structure_atoms", None)
+        out = np.empty((n or 0, 3), dtype=np.float64)
+        self._chk(self._lib.msl_thermal_positions(self._h, int(seed), int(config), _ptr(out) if out.size else None))
+        return out
 
     def upload_potential(self, V_nz_nx_ny):
         v = np.ascontiguousarray(V_nz_nx_ny, dtype=np.float32)

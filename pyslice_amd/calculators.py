@@ -25,7 +25,9 @@ from . import _native, distributed
 from .aberrations import Aberrations
 from .multislice import Probe, interaction_sigma, wavelength
 from .prism import Prism, beams as prism_beams
-from .potentials import TORCH_AVAILABLE, _as_tensor, _device_index, gridFromTrajectory, loadKirkland, slice_edges, suggest_sampling
+from .potentials import (TORCH_AVAILABLE, _as_tensor, _device_index, atomic_numbers_of, gridFromTrajectory, loadKirkland, slice_edges,
+                         suggest_sampling)
+from .thermal import FrozenPhonons
 from .trajectory import Trajectory
 from .wf_data import WFData
 
@@ -316,7 +318,18 @@ class MultisliceCalculator:
         cleanup_temp_files: bool = False,
         slice_axis: int = 2,
     ):
-        """reference calculators.py:96-161 -- same arguments, same defaults, same attributes."""
+        """reference calculators.py:96-161 -- same arguments, same defaults, same attributes.
+
+        (not in the reference) `trajectory` may be a thermal.FrozenPhonons: its n_configs Einstein-model configurations take the
+        place of the MD frames in every run mode, generated on the device from the resident base structure (msl_set_structure
+        once, msl_build_thermal per frame batch) instead of being copied from a (T, n_atoms, 3) host array.  Not built with it:
+        cache=True, stream_tile / run_streaming_tacaw(), several ranks (NotImplementedError)."""
+        self._thermal = trajectory if isinstance(trajectory, FrozenPhonons) else None
+        if self._thermal is not None:
+            for what, val in (("cache=True", self._cache), ("stream_tile / run_streaming_tacaw()", self._stream_tile is not None),
+                              ("a run over several ranks", distributed.rank_world()[1] > 1)):
+                if val:
+                    raise NotImplementedError(f"frozen phonons: {what} is not built")
         self.trajectory = trajectory
         self.aperture = aperture
         self.voltage_eV = voltage_eV
@@ -506,7 +519,8 @@ class MultisliceCalculator:
         # slice coordinates follow the slice axis (potentials.py:241-245); the Fresnel step uses zs (multislice.py:266)
         self._slice_coords = np.asarray([self.xs, self.ys, self.zs][slice_axis], dtype=np.float64)
         self._dz = self.zs[1] - self.zs[0] if self.nz > 1 else 0.5
-        self._Z = np.asarray(trajectory.atom_types, dtype=np.int32)
+        self._Z = (atomic_numbers_of(trajectory.atom_types) if self._thermal is not None
+                   else np.asarray(trajectory.atom_types, dtype=np.int32))
         # A previous run's WFData (and zero-copy device views of its buffers) may still hold the old engine: drop our
         # reference and let the last owner free it, instead of closing it under them.  (A caller that keeps an earlier result
         # and only needs its host arrays frees the device side with result.release().)
@@ -598,21 +612,31 @@ class MultisliceCalculator:
         eng.set_kirkland(loadKirkland())
         eng.set_slices(*slice_edges(self._slice_coords))
         eng.set_aberrations(self._aberrations)
+        if self._thermal is not None:                           # the base structure, once: every build is a generation by index
+            eng.set_structure(self._thermal.positions, self._Z, self._thermal.sigma, self.slice_axis)
+
+    def _build(self, first_frame, n):
+        """The potentials of the frames first_frame .. first_frame+n-1 into the batch slots (the engine's singular call at a frame
+        batch of 1): MD frames from the trajectory's host array, frozen-phonon configurations generated on the device by index."""
+        eng = self._engine
+        if self._thermal is not None:
+            eng.build_thermal(self._thermal.seed, first_frame, n)
+        elif eng.frame_batch > 1:
+            eng.build_potentials(self.trajectory.positions[first_frame:first_frame + n], self._Z, self.slice_axis)
+        else:
+            eng.build_potential(self.trajectory.positions[first_frame], self._Z, self.slice_axis)
 
     def _build_and_propagate(self, first_frame, n, first_slot, build=True, propagate=True):
         """The potentials of MD frames first_frame .. first_frame+n-1 into the batch slots, then the slice loop of every probe
         through them into result slots first_slot ..; the engine's singular calls at a frame batch of 1.  The probe-batch loops
         take the two halves apart: one build, one slice loop per probe batch."""
-        eng, positions = self._engine, self.trajectory.positions
-        if eng.frame_batch > 1:
-            if build:
-                eng.build_potentials(positions[first_frame:first_frame + n], self._Z, self.slice_axis)
-            if propagate:
+        eng = self._engine
+        if build:
+            self._build(first_frame, n)
+        if propagate:
+            if eng.frame_batch > 1:
                 eng.propagate_frames(first_slot, n)
-        else:
-            if build:
-                eng.build_potential(positions[first_frame], self._Z, self.slice_axis)
-            if propagate:
+            else:
                 eng.propagate_frame(first_slot)
 
     def _frame_batches(self):
@@ -664,7 +688,7 @@ class MultisliceCalculator:
         eng = self._engine
         bar = _Progress(self._progress, self.n_frames)
         for s in range(self.n_frames):
-            eng.build_potential(self.trajectory.positions[s], self._Z, self.slice_axis)
+            self._build(s, 1)
             eng.smatrix_build()
             for p0, real, xy in self._probe_batches():
                 eng.smatrix_probes(xy, 0)
@@ -923,7 +947,7 @@ class MultisliceCalculator:
                     eng.upload_frame(slot, np.load(cache_file)[:, :, :, 0, 0])
                     self.frames_cached += 1
                 else:
-                    eng.build_potential(self.trajectory.positions[frame_idx], self._Z, self.slice_axis)
+                    self._build(frame_idx, 1)
                     eng.propagate_frame(slot)
                     self.frames_computed += 1
                     np.save(cache_file, eng.frame(slot).astype(np.complex128)[:, :, :, None, None])
@@ -932,7 +956,7 @@ class MultisliceCalculator:
             # per frame: the potential, the S-matrix of its Bm beams, every probe synthesised from it into the frame's slot
             xy = np.asarray(self.probe_positions, dtype=np.float64).reshape(-1, 2)
             for slot, frame_idx in enumerate(frames):
-                eng.build_potential(self.trajectory.positions[frame_idx], self._Z, self.slice_axis)
+                self._build(frame_idx, 1)
                 eng.smatrix_build()
                 eng.smatrix_probes(xy, slot)
                 self.frames_computed += 1

@@ -16,6 +16,7 @@
 #include "fft_pow2.h"
 #include "rowtm_pass.h"
 #include "potential.h"
+#include "thermal.h"
 #include "reduce.h"
 #include "stream.h"
 #include "tacaw_time.h"
@@ -213,6 +214,15 @@ struct msl_handle {
     int n_species = 0;
     int ff_species[104] = {0};     // species list the resident form-factor table was computed for (frame-invariant: computed once per run)
     int ff_n = 0;
+    // frozen phonons (msl_set_structure): the base structure resident on the device -- positions (n, 3), widths, Z and the species
+    // maps that stage_atoms sends per call -- with the host's copy of the maps and the axes; msl_build_thermal generates the
+    // positions of any configuration from it (thermal_positions_kernel), so no per-frame array and no caller pointer is kept
+    DevBuf<double> th_pos0, th_sigma;
+    DevBuf<int> th_Z, th_z2s, th_species;
+    int th_map_z2s[104] = {0}, th_map_species[104] = {0}, th_nsp = 0;
+    int64_t th_n = 0;
+    int32_t th_ax1 = 0, th_ax2 = 1, th_axs = 2;
+    bool have_structure = false;
     DevBuf<double> d_xy;
     // probe aberrations (msl_set_aberrations): (magnitude, angle) of the fourteen terms; read by every msl_set_probes
     double aberr_polar[14][2] = {};
@@ -1483,6 +1493,24 @@ int stage_atoms(msl_handle* h, const PotGroup& p, const double* pos, const int32
     return MSL_OK;
 }
 
+// The frozen-phonon source of build_potentials: configurations first_config .. of the handle's resident structure
+struct ThermalSource { uint64_t seed; uint64_t first_config; };
+
+// stage_atoms for a group of configurations: the positions are generated into d_pos on the device (thermal_positions_kernel, one
+// thread per configuration and atom); with the first group of a call the resident species maps and Z are copied, device to device,
+// to where stage_atoms puts them.  No pinned staging, no host copy.
+int stage_thermal(msl_handle* h, const PotGroup& p, uint64_t seed, uint64_t first_config, bool send_maps) {
+    if (send_maps) {
+        HIPCHK(h, hipMemcpyAsync(h->d_z2s, h->th_z2s, sizeof p.z2s, hipMemcpyDeviceToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(h->d_species, h->th_species, p.nsp * sizeof(int), hipMemcpyDeviceToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(h->d_Z, h->th_Z, (size_t)p.n * sizeof(int), hipMemcpyDeviceToDevice, h->stream));
+    }
+    hipLaunchKernelGGL(thermal_positions_kernel, dim3((unsigned)((p.rows + 255) / 256)), dim3(256), 0, h->stream, h->th_pos0, h->th_sigma,
+                       (long long)p.n, p.g, (unsigned long long)seed, (unsigned long long)first_config, h->d_pos);
+    HIPCHK(h, hipGetLastError());
+    return MSL_OK;
+}
+
 // Atoms of a group -> phase tables in sorted order: slice bins (atom_prep_kernel), stable counting sort with keys = frame x slice x
 // species (bin_scan / bin_fill), the phase tables of both axes
 int bin_atoms(msl_handle* h, const PotGroup& p) {
@@ -1687,11 +1715,21 @@ int potential_ifft(msl_handle* h, const PotGroup& p) {
 // phase tables of a group may take (6 GB), instead of that sequence per frame.  The reference builds one Potential per frame
 // (calculators.py:172-186, potentials.py:188-348); with its default single probe that build IS the frame (round 2: 0.43 of
 // 0.62 ms at 512^2 x 100 slices, of which ~110 us were launches of 5-15 us kernels and four small copies per frame).
-int build_potentials(msl_handle* h, const double* pos, const int32_t* Z, int64_t n, int count, int first_slot, int32_t ax1, int32_t ax2, int32_t axs) {
+// With `th` the frames are configurations of the resident structure (msl_build_thermal): pos and Z are not read, the species maps are
+// the ones msl_set_structure made, and stage_thermal takes the place of stage_atoms; everything behind d_pos is the same.
+int build_potentials(msl_handle* h, const double* pos, const int32_t* Z, int64_t n, int count, int first_slot, int32_t ax1, int32_t ax2, int32_t axs,
+                     const ThermalSource* th = nullptr) {
     const msl_config& c = h->cfg;
     const size_t npix = (size_t)c.nx * c.ny;
     PotGroup p{};
-    int rc = map_species(h, Z, n, p);
+    int rc = MSL_OK;
+    if (th) {
+        memcpy(p.z2s, h->th_map_z2s, sizeof p.z2s);
+        memcpy(p.species, h->th_map_species, sizeof p.species);
+        p.nsp = h->th_nsp;
+    } else {
+        rc = map_species(h, Z, n, p);
+    }
     if (rc) return rc;
     // with launch timing off the call only queues work: no event, no host wait (the frames of a run pipeline on the stream)
     EventPair timer;
@@ -1722,8 +1760,9 @@ int build_potentials(msl_handle* h, const double* pos, const int32_t* Z, int64_t
         p.n_slices = c.nz * p.g; p.nkeys = p.keys_per_frame * p.g;
         p.rows = (long long)n * p.g; p.rows_pad = p.rows + (long long)(SF_ALIGN - 1) * p.nkeys;
         if (n > 0 && p.nsp > 0) {
-            if ((rc = stage_atoms(h, p, pos + (size_t)f0 * n * 3, Z, f0 == 0)) || (rc = bin_atoms(h, p)) || (rc = launch_structure_factor(h, p)))
-                return rc;
+            rc = th ? stage_thermal(h, p, th->seed, th->first_config + (uint64_t)f0, f0 == 0)
+                    : stage_atoms(h, p, pos + (size_t)f0 * n * 3, Z, f0 == 0);
+            if (rc || (rc = bin_atoms(h, p)) || (rc = launch_structure_factor(h, p))) return rc;
         } else {
             HIPCHK(h, hipMemsetAsync(p.TR, 0, npix * p.n_slices * sizeof(float2), h->stream));
         }
@@ -2277,6 +2316,81 @@ int msl_build_potentials(msl_handle* h, const double* pos, const int32_t* Z, int
     rc = build_potentials(h, pos, Z, n, count, 0, ax1, ax2, axs);
     if (rc == MSL_OK) h->cur_batch = count - 1;         // the current stack (MSL_BUF_TRANSMISSION, msl_propagate) is the last frame's, as after `count` single builds
     return rc;
+}
+
+// ---- frozen phonons ----------------------------------------------------------
+int msl_set_structure(msl_handle* h, const double* pos0, const int32_t* Z, const double* sigma, int64_t n, int32_t ax1, int32_t ax2, int32_t axs) {
+    if (!h || (n > 0 && (!pos0 || !Z || !sigma))) return fail(h, MSL_ERR_INVALID, "msl_set_structure: null argument");
+    if (n < 0 || n > 0x7fffffff) return fail(h, MSL_ERR_INVALID, "msl_set_structure: bad atom count");
+    if (ax1 < 0 || ax1 > 2 || ax2 < 0 || ax2 > 2 || axs < 0 || axs > 2 || ((1 << ax1) | (1 << ax2) | (1 << axs)) != 7)
+        return fail(h, MSL_ERR_INVALID, "msl_set_structure: axes must be a permutation of 0,1,2");
+    PotGroup m{};
+    for (int i = 0; i < 104; ++i) m.z2s[i] = -1;
+    for (int64_t a = 0; a < n; ++a) {
+        if (Z[a] < 1 || Z[a] > 103) return fail(h, MSL_ERR_INVALID, "msl_set_structure: atomic number %d out of 1..103", Z[a]);
+        if (!(sigma[a] >= 0.0) || !std::isfinite(sigma[a]))
+            return fail(h, MSL_ERR_INVALID, "msl_set_structure: width %g of atom %lld is not a finite number >= 0", sigma[a], (long long)a);
+        m.z2s[Z[a]] = 0;
+    }
+    m.nsp = 0;
+    for (int z = 1; z <= 103; ++z) if (m.z2s[z] == 0) { m.z2s[z] = m.nsp; m.species[m.nsp++] = z; }
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));          // a build queued from the previous structure still reads its buffers
+    h->have_structure = false;
+    int rc;
+    if ((rc = h->th_pos0.alloc(h, (size_t)n * 3)) || (rc = h->th_sigma.alloc(h, (size_t)n)) || (rc = h->th_Z.alloc(h, (size_t)n)) ||
+        (rc = h->th_z2s.alloc(h, (size_t)104)) || (rc = h->th_species.alloc(h, (size_t)104))) return rc;
+    if (n > 0) {
+        HIPCHK(h, hipMemcpy(h->th_pos0, pos0, (size_t)n * 3 * sizeof(double), hipMemcpyHostToDevice));
+        HIPCHK(h, hipMemcpy(h->th_sigma, sigma, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
+        HIPCHK(h, hipMemcpy(h->th_Z, Z, (size_t)n * sizeof(int), hipMemcpyHostToDevice));
+    }
+    HIPCHK(h, hipMemcpy(h->th_z2s, m.z2s, sizeof m.z2s, hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(h->th_species, m.species, sizeof m.species, hipMemcpyHostToDevice));
+    memcpy(h->th_map_z2s, m.z2s, sizeof m.z2s);
+    memcpy(h->th_map_species, m.species, sizeof m.species);
+    h->th_nsp = m.nsp; h->th_n = n; h->th_ax1 = ax1; h->th_ax2 = ax2; h->th_axs = axs;
+    h->have_structure = true;
+    return MSL_OK;
+}
+
+int msl_build_thermal(msl_handle* h, uint64_t seed, int64_t first_config, int32_t count) {
+    if (!h) return fail(h, MSL_ERR_INVALID, "msl_build_thermal: null handle");
+    if (!h->have_structure) return fail(h, MSL_ERR_INVALID, "msl_build_thermal: no structure (call msl_set_structure first)");
+    if (!h->have_kirkland) return fail(h, MSL_ERR_STATE, "msl_build_thermal: call msl_set_kirkland first");
+    if (!h->have_slices) return fail(h, MSL_ERR_STATE, "msl_build_thermal: call msl_set_slices first");
+    if (count < 1 || count > h->FB) return fail(h, MSL_ERR_INVALID, "msl_build_thermal: count %d outside [1,%d] (msl_config.frame_batch)", count, h->FB);
+    if (first_config < 0 || first_config > INT64_MAX - count)
+        return fail(h, MSL_ERR_INVALID, "msl_build_thermal: configurations %lld .. outside [0, 2^63)", (long long)first_config);
+    if (h->th_n * count > 0x7fffffffLL) return fail(h, MSL_ERR_INVALID, "msl_build_thermal: more than 2^31 atoms in one batch");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    const ThermalSource th{seed, (uint64_t)first_config};
+    // a frame batch of 1: the selected slot, as msl_build_potential; else the slots 0 .. count-1, as msl_build_potentials
+    const int first_slot = h->FB > 1 ? 0 : h->cur_batch;
+    int rc = build_potentials(h, nullptr, nullptr, h->th_n, count, first_slot, h->th_ax1, h->th_ax2, h->th_axs, &th);
+    if (rc == MSL_OK && h->FB > 1) h->cur_batch = count - 1;
+    return rc;
+}
+
+int msl_thermal_positions(msl_handle* h, uint64_t seed, int64_t config, double* out) {
+    if (!h) return fail(h, MSL_ERR_INVALID, "msl_thermal_positions: null handle");
+    if (!h->have_structure) return fail(h, MSL_ERR_INVALID, "msl_thermal_positions: no structure (call msl_set_structure first)");
+    if (config < 0) return fail(h, MSL_ERR_INVALID, "msl_thermal_positions: configuration %lld is negative", (long long)config);
+    const int64_t n = h->th_n;
+    if (n == 0) return MSL_OK;
+    if (!out) return fail(h, MSL_ERR_INVALID, "msl_thermal_positions: null argument");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    DevBuf<double> tmp;                                   // (not d_pos: a queued build may still read it)
+    int rc = tmp.alloc(h, (size_t)n * 3);
+    if (rc) return rc;
+    hipLaunchKernelGGL(thermal_positions_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->th_pos0, h->th_sigma,
+                       (long long)n, 1, (unsigned long long)seed, (unsigned long long)config, tmp.p);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(out, tmp, (size_t)n * 3 * sizeof(double), hipMemcpyDeviceToHost, h->stream);
+    const hipError_t es = hipStreamSynchronize(h->stream);      // on every path: nothing queued reads tmp when it is freed below
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) return fail(h, MSL_ERR_HIP, "msl_thermal_positions failed: %s", hipGetErrorString(e));
+    return MSL_OK;
 }
 
 int msl_upload_potential(msl_handle* h, const float* V) {

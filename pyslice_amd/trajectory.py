@@ -3,7 +3,8 @@
 Mirrors the reference dataclass (src/multislice/trajectory.py:8-50): same field names, same
 shape validation and the same ValueError messages, so scripts that build a Trajectory from
 arrays work unchanged.  The tile/slice/displace helpers of the reference are pure NumPy
-slicing off the timed path and are not restated here.
+slicing off the timed path and are not restated here; what its
+generate_random_displacements is used for -- thermal configurations of a structure -- is thermal.FrozenPhonons.
 """
 from __future__ import annotations
 
