@@ -17,12 +17,15 @@
 
 // Ablation switches of tools/rowt_bench.hip (timing experiments on this pass; wrong results): 1 = no prefetch loads, 2 = no
 // global stores (the tile reads stay), 4 = no lane <-> register exchanges, 8 = no transforms at all, 16 = one table entry instead
-// of the table reads, 32 = no tile write / barriers / store phase.  Never set in the library.
+// of the table reads (the Fresnel factors and the twiddles that are not kept in registers), 32 = no tile write / barriers / store phase.  Never set in the library.
 #ifndef MSL_ABL2
 #define MSL_ABL2 0
 #endif
+#ifndef MSL_TW_LDS
+#define MSL_TW_LDS 0            // 1: the inter-FFT twiddles are read from the LDS table in every transform (the form before the register column)
+#endif
 #ifndef MSL_DIT_LCH
-#define MSL_DIT_LCH 8           // leaf butterflies per chunk of table reads (4: 13 VGPRs fewer, 1 % slower)
+#define MSL_DIT_LCH 8           // leaf butterflies per chunk of table reads where no twiddle is kept in registers (4: 13 VGPRs fewer, 1 % slower)
 #endif
 #ifndef MSL_DIT_FENCE
 #define MSL_DIT_FENCE 0         // butterflies between two scheduling barriers in the upper levels (0: none; 1, 2: no faster)
@@ -144,6 +147,25 @@ __device__ __forceinline__ void dit_leaf_chunks(const float2* in, float2* v, Tab
     }
 }
 
+// leaf butterflies [0, K) of the R-point network with their weights in registers: those of elements I and I + q C (C = leaf count)
+// in w[I + q K]
+template <int R, bool INV, int WMODE, int K, int I>
+__device__ __forceinline__ void dit_leaves_regs_part(const float2* in, float2* v, const float2* w) {
+    if constexpr (I < K) {
+        constexpr int LR = dit_leaf_radix(R);
+        float2 ww[4];
+        ww[0] = w[I]; ww[1] = w[I + K];
+        if constexpr (LR == 4) { ww[2] = w[I + 2 * K]; ww[3] = w[I + 3 * K]; }
+        dit_leaf<R, INV, WMODE, I>(in, v, ww);
+        dit_leaves_regs_part<R, INV, WMODE, K, I + 1>(in, v, w);
+    }
+}
+// how many leaf butterflies of a twiddle-weighted transform take their weights from registers (rowT_pass_kernel): 8 of the 16 at
+// R = 32 with compile-time pass flags -- what the register file holds beside the lines, see twr -- and the table reads then come
+// in chunks of 4 butterflies
+constexpr int rowT_tw_reg_leaves(int R, int FL) { return (!MSL_TW_LDS && R == 32 && FL >= 0) ? 8 : 0; }
+constexpr int ROWT_TW_REG_LCH = 4;
+
 // ---- the kernel -------------------------------------------------------------------------------------------------------------------
 // Work item = (block of 16 lines, chunk of `pchunk` images that share t_k): the t_k lines stay in registers across the chunk.
 //
@@ -158,8 +180,9 @@ __device__ __forceinline__ void dit_leaf_chunks(const float2* in, float2* v, Tab
 // job.perm_shift = log2(R' / 8).
 //
 // FL: the P2_PRE_A / P2_POST_A bits of job.flags as a compile-time value (3 = both: every pass but the first and the last of a
-// stack), or -1 = read them from the job.  With both halves unconditional the body needs 234 VGPRs; with branches around them the
-// allocator spills the t_k line (272 bytes per lane) -- only the rarely used combinations are compiled that way (slice_pass.hip).
+// stack), or -1 = read them from the job.  With both halves unconditional the body needs 234 VGPRs (R = 32: 249 with half of the
+// twiddle column in registers, see twr); with branches around them the allocator spills the t_k line (272 bytes per lane) -- only
+// the rarely used combinations are compiled that way (slice_pass.hip), and they keep every twiddle in the table.
 template <int R, int LINES, bool IN_P, bool OUT_P, int FL>
 __global__ void __launch_bounds__(LINES * R, (R == 16) ? 3 : 2) rowT_pass_kernel(RowTJob job) {
     constexpr int N = R * R;
@@ -170,10 +193,14 @@ __global__ void __launch_bounds__(LINES * R, (R == 16) ? 3 : 2) rowT_pass_kernel
     constexpr int TPS = LINES / 2;                    // threads (16 B = 2 lines each) per output segment of LINES*8 bytes
     constexpr int POS_PER_IT = NT / TPS;
     constexpr int NIT = N / POS_PER_IT;
-    constexpr int LCHL = MSL_DIT_LCH < dit_leaf_count(R) ? MSL_DIT_LCH : dit_leaf_count(R);      // leaf butterflies per chunk of table reads
+    // TWK > 0: the twiddles of the first TWK leaf butterflies live in registers for the whole kernel (see twr below)
+    constexpr int TWK = rowT_tw_reg_leaves(R, FL), LRW = dit_leaf_radix(R);
+    constexpr bool TWR = TWK > 0;
+    constexpr int LCH0 = TWR ? ROWT_TW_REG_LCH : MSL_DIT_LCH;
+    constexpr int LCHL = LCH0 < dit_leaf_count(R) ? LCH0 : dit_leaf_count(R);      // leaf butterflies per chunk of table reads
     constexpr int FN = MSL_DIT_FENCE;
     static_assert(LINES == 16, "16 lines = 128-byte transposed segments (8 lines / 64 bytes measured 1.6x slower)");
-    static_assert(dit_leaf_count(R) % LCHL == 0, "whole chunks");
+    static_assert(dit_leaf_count(R) % LCHL == 0 && TWK % LCHL == 0 && TWK < dit_leaf_count(R), "whole chunks");
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     float2* tw = reinterpret_cast<float2*>(smem_raw);
     float2* pl = tw + N;
@@ -182,6 +209,17 @@ __global__ void __launch_bounds__(LINES * R, (R == 16) ? 3 : 2) rowT_pass_kernel
     for (int i = tid; i < N; i += NT) { tw[i] = job.tw[i]; pl[i] = job.pl[i]; }
     __syncthreads();
     const int grp = tid / R, ln = tid % R;
+    // The four twiddle-weighted transforms of an iteration all weight element n of lane ln by tw[n R + ln]: the same R values in
+    // every transform of every iteration.  The weights of the first TWK leaf butterflies are read once, here, and stay in registers;
+    // the others, and the Fresnel factors, still come from the table in chunks.  The whole column does not fit: v, the prefetched line
+    // vn, the t_k line tv and R weights are 4 x 64 = 256 registers at the end of an iteration, before any address (allocator: 64-104
+    // bytes of scratch per lane in every R = 32 instantiation, at any chunk size; 12 of 16 butterflies: 28-40 bytes; 8: none).
+    float2 twr[TWR ? LRW * TWK : 1];
+    if constexpr (TWR) {
+#pragma unroll
+        for (int i = 0; i < LRW * TWK; ++i) twr[i] = tw[((i % TWK) + (i / TWK) * dit_leaf_count(R)) * R + ln];
+        pin_all(twr);
+    }
     const int q = tid % TPS, r0 = tid / TPS;
     const int l64 = tid & 63;
     float2* myrow = tile + grp * CS;
@@ -279,16 +317,22 @@ __global__ void __launch_bounds__(LINES * R, (R == 16) ? 3 : 2) rowT_pass_kernel
         // one register transform with the table `TAB` folded into its leaf level, two prefetch slots
 #define MSL_HALF_TAB(INV, WM, TAB, I0) do { dit_leaf_chunks<R, INV, WM, R, LCHL, 0>(v, v, TAB, ln); pfx(MSL_IC(I0)); \
                                             dit_upper<R, INV, FN>(v); pin_all(v); pfx(MSL_IC((I0) + 1)); } while (0)
+        // ... with the inter-FFT twiddles: the first TWK butterflies from registers (WM 2: conjugated, as sign flips inside the FMAs)
+#define MSL_HALF_TW(INV, WM, I0) do { \
+            if constexpr (TWR) { dit_leaves_regs_part<R, INV, WM, TWK, 0>(v, v, twr); \
+                                 dit_leaf_chunks<R, INV, WM, R, LCHL, TWK>(v, v, tw, ln); pin_all(v); pfx(MSL_IC(I0)); \
+                                 dit_upper<R, INV, FN>(v); pin_all(v); pfx(MSL_IC((I0) + 1)); } \
+            else MSL_HALF_TAB(INV, WM, tw, I0); } while (0)
         if (pre_a) {
             dit_leaves_plain<R, false, 0>(vn, v); pin_all(v);       // reads the prefetched line; vn is free from here on
             pfx(MSL_IC(0));
             dit_upper<R, false, FN>(v); pin_all(v);
             pfx(MSL_IC(1));
             exchange_addtid<R>(v, wscr, wscr_lds, ln, l64);
-            MSL_HALF_TAB(false, 1, tw, 2);
+            MSL_HALF_TW(false, 1, 2);
             MSL_HALF_TAB(true, 1, pl, 4);
             exchange_addtid<R>(v, wscr, wscr_lds, ln, l64);
-            MSL_HALF_TAB(true, 2, tw, 6);
+            MSL_HALF_TW(true, 2, 6);
         } else {
 #pragma unroll
             for (int j = 0; j < R; ++j) v[j] = vn[j];
@@ -301,15 +345,16 @@ __global__ void __launch_bounds__(LINES * R, (R == 16) ? 3 : 2) rowT_pass_kernel
             dit_upper<R, false, FN>(v); pin_all(v);
             pfx(MSL_IC(9));
             exchange_addtid<R>(v, wscr, wscr_lds, ln, l64);
-            MSL_HALF_TAB(false, 1, tw, 10);
+            MSL_HALF_TW(false, 1, 10);
             MSL_HALF_TAB(true, 1, pl, 12);
             exchange_addtid<R>(v, wscr, wscr_lds, ln, l64);
-            MSL_HALF_TAB(true, 2, tw, 14);
+            MSL_HALF_TW(true, 2, 14);
         } else {
 #pragma unroll
             for (int j = 0; j < R; ++j) v[j] = cmulf(v[j], tv[j]);
             pfx(MSL_IC(8)); pfx(MSL_IC(9)); pfx(MSL_IC(10)); pfx(MSL_IC(11)); pfx(MSL_IC(12)); pfx(MSL_IC(13)); pfx(MSL_IC(14)); pfx(MSL_IC(15));
         }
+#undef MSL_HALF_TW
 #undef MSL_HALF_TAB
         if constexpr (MSL_ABL2 & 32) {
             float acc = 0.f;

@@ -6,6 +6,7 @@
 //         -o tools/bin/rowt_bench tools/rowt_bench.hip
 //   tools/bin/rowt_bench [launches [zero]]      zero = 1: all-zero waves and transmission functions (same instructions, less switching)
 // -DMSL_CLOCK: in-kernel clock (s_memtime / s_memrealtime around the item loop); -DMSL_ABL2: ablations, see rowt_pass.h.
+// -DMSL_TW_LDS=1: every inter-FFT twiddle from the LDS table (the form before the register twiddles), for a same-binary-family A/B.
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include <complex>
