@@ -462,6 +462,23 @@ class Engine:
     def _bfk(self, src):
         return (self.n_probes, self.intensity_F, self.wx * self.wy) if src is None else tuple(int(v) for v in src[1:4])
 
+    def _rows(self, src, B, rows, first, count):
+        """(p, b, rows, k, ld, count) of a call over the slots [first, first+count) of the row axis: src = None is the handle's
+        own buffer of `rows` frame slots or frequency bins (B = n_probes or fewer), else _src(src); count = None: to the last"""
+        if src is None:
+            p, b, k, ld = None, int(B) if B else self.n_probes, self.wx * self.wy, 0
+        else:
+            p, b, rows, k, ld = self._src(src)
+        return p, b, rows, k, ld, (rows - int(first)) if count is None else int(count)
+
+    @staticmethod
+    def _mask(mask, K):
+        """a boolean mask over k-space as K uint8"""
+        m = np.ascontiguousarray(np.asarray(mask).reshape(-1) != 0, dtype=np.uint8)
+        if m.size != K:
+            raise ValueError(f"mask has {m.size} entries, k-space has {K}")
+        return m
+
     def result_pitch(self, what=BUF_WAVEFUNCTION):
         """pixel pitch of the images of the wavefunction / intensity buffer (>= wx*wy, include/mslice.h: msl_result_pitch)"""
         return int(self._lib.msl_result_pitch(self._h, int(what)))
@@ -487,11 +504,7 @@ class Engine:
     def tacaw_spectrum(self, mask=None, src=None):
         """(B,F) float64: sum over k of the (masked) intensity."""
         B, F, K = self._bfk(src)
-        m = None
-        if mask is not None:
-            m = np.ascontiguousarray(np.asarray(mask).reshape(-1) != 0, dtype=np.uint8)
-            if m.size != K:
-                raise ValueError(f"mask has {m.size} entries, k-space has {K}")
+        m = None if mask is None else self._mask(mask, K)
         out = np.empty((B, F), dtype=np.float64)
         p, b, f, k, ld = self._src(src)
         self._chk(self._lib.msl_tacaw_spectrum(self._h, p, b, f, k, ld, _ptr(m) if m is not None else None, _ptr(out)))
@@ -530,9 +543,7 @@ class Engine:
     def adf(self, mask, src=None):
         """(B,) float64: mean over frames of sum_k mask |Psi|."""
         B, T, K = self._bfk(src)
-        m = np.ascontiguousarray(np.asarray(mask).reshape(-1) != 0, dtype=np.uint8)
-        if m.size != K:
-            raise ValueError(f"mask has {m.size} entries, k-space has {K}")
+        m = self._mask(mask, K)
         out = np.empty(B, dtype=np.float64)
         p, b, t, k, ld = self._src(src)
         self._chk(self._lib.msl_adf(self._h, p, b, t, k, ld, _ptr(m), _ptr(out)))
@@ -557,11 +568,7 @@ class Engine:
         """(B, count, n_detectors) float64 detector signals of frame slots [t0, t0+count).  src = None: the handle's own
         wavefunction buffer (B = n_probes or fewer: the first B probes); else (device pointer, B, T, K[, ld]) of a caller's
         complex64 array"""
-        if src is None:
-            p, b, T, k, ld = None, int(B) if B else self.n_probes, self.n_frames, self.wx * self.wy, 0
-        else:
-            p, b, T, k, ld = self._src(src)
-        count = (T - int(t0)) if count is None else int(count)
+        p, b, T, k, ld, count = self._rows(src, B, self.n_frames, t0, count)
         out = np.empty((max(b, 0), max(count, 0), getattr(self, "n_detectors", 0)), dtype=np.float64)
         self._chk(self._lib.msl_detect(self._h, p, b, T, k, ld, int(t0), count, _ptr(out)))
         return out
@@ -571,11 +578,7 @@ class Engine:
         """(B, count, n_detectors) float64: the intensity inside every detector at the frequency bins [f0, f0+count), all detectors
         in one pass.  src = None: the handle's own intensity buffer (after tacaw() / a finished stream; B = n_probes or fewer: the
         first B probes); else (device pointer, B, F, K[, ld]) of a caller's float32 (B, F, K) intensity"""
-        if src is None:
-            p, b, F, k, ld = None, int(B) if B else self.n_probes, self.intensity_F, self.wx * self.wy, 0
-        else:
-            p, b, F, k, ld = self._src(src)
-        count = (F - int(f0)) if count is None else int(count)
+        p, b, F, k, ld, count = self._rows(src, B, self.intensity_F, f0, count)
         out = np.empty((max(b, 0), max(count, 0), getattr(self, "n_detectors", 0)), dtype=np.float64)
         self._chk(self._lib.msl_spectrum_detect(self._h, p, b, F, k, ld, int(f0), count, _ptr(out)))
         return out
@@ -586,16 +589,11 @@ class Engine:
         (a SUM over the frames: divide by count for the mean).  src = None: the handle's own wavefunction buffer (B = n_probes or
         fewer: the first B probes); else (device pointer, B, T, wx, wy[, ld]) of a caller's complex64 (B, T, wx*wy) array"""
         bx, by = int(bin[0]), int(bin[1])
-        if src is None:
-            p, b, T, wx, wy, ld = None, int(B) if B else self.n_probes, self.n_frames, self.wx, self.wy, 0
-        else:
-            ptr, b, T, wx, wy = src[:5]
-            p, b, T, wx, wy = C.c_void_p(int(ptr)), int(b), int(T), int(wx), int(wy)
-            ld = int(src[5]) if len(src) > 5 else wx * wy
-        count = (T - int(t0)) if count is None else int(count)
+        wx, wy = (self.wx, self.wy) if src is None else (int(src[3]), int(src[4]))
+        p, b, T, k, ld, count = self._rows(None if src is None else (*src[:3], wx * wy, *src[5:]), B, self.n_frames, t0, count)
         ok = bx > 0 and by > 0 and wx > 0 and wy > 0 and wx % bx == 0 and wy % by == 0       # (else the library refuses: no output is read)
         out = np.empty((max(b, 0), wx // bx, wy // by) if ok else (1,), dtype=np.float64)
-        self._chk(self._lib.msl_diffract(self._h, p, b, T, wx * wy, ld, int(t0), count, wx, wy, bx, by, _ptr(out)))
+        self._chk(self._lib.msl_diffract(self._h, p, b, T, k, ld, int(t0), count, wx, wy, bx, by, _ptr(out)))
         return out
 
     # -- coherent frame sums (msl_coherent_reset / msl_coherent_add / msl_coherent_finish)
@@ -609,11 +607,7 @@ class Engine:
         """acc[b, k] += the sum of Psi[b, t, k] over the frame slots [t0, t0+count), every addend widened to float64 first.  Source
         as detect(): None is the handle's own wavefunction buffer (B = n_probes or fewer: the first B probes); else (device
         pointer, B, T, K[, ld]) of a caller's complex64 array.  Queued on the handle's stream."""
-        if src is None:
-            p, b, T, k, ld = None, int(B) if B else self.n_probes, self.n_frames, self.wx * self.wy, 0
-        else:
-            p, b, T, k, ld = self._src(src)
-        count = (T - int(t0)) if count is None else int(count)
+        p, b, T, k, ld, count = self._rows(src, B, self.n_frames, t0, count)
         self._chk(self._lib.msl_coherent_add(self._h, p, b, T, k, ld, int(t0), count))
 
     def coherent_finish(self, n, B=None, bin=(1, 1), shape=None):
@@ -639,12 +633,7 @@ class Engine:
         (<= 0: none).  Source as detect(): None is the handle's own wavefunction buffer (B = n_probes or fewer: the first B probes);
         else (device pointer, B, T[, ld]) of a caller's complex64 (B, T, nx*ny) array of full-grid spectra.  Queued on the
         handle's stream; consumes the real-space exit waves."""
-        if src is None:
-            p, b, T, ld = None, int(B) if B else self.n_probes, self.n_frames, 0
-        else:
-            p, b, T = C.c_void_p(int(src[0])), int(src[1]), int(src[2])
-            ld = int(src[3]) if len(src) > 3 else self.nx * self.ny
-        count = (T - int(t0)) if count is None else int(count)
+        p, b, T, _, ld, count = self._rows(None if src is None else (*src[:3], self.nx * self.ny, *src[3:]), B, self.n_frames, t0, count)
         pol = None
         if polar is not None:
             pol = np.ascontiguousarray(polar, dtype=np.float64)

@@ -9,6 +9,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/mslice.h"
@@ -903,13 +904,23 @@ int launch_rowT_r(msl_handle* h, RowTJob job, int kind) {
     return mark_launch(h, kind);
 }
 
+// A runtime value as a template argument: f(std::bool_constant<v>{}), and f(std::integral_constant<int, V>{}) for the V of the
+// list that equals v (the last of the list when none does, as the else of the ladder this replaces).  f is a generic lambda that
+// reads the value back with decltype(arg)::value, so a kernel's argument list is written once for all its instantiations.
+template <typename F>
+auto with_bool(bool v, F&& f) {
+    return v ? f(std::true_type{}) : f(std::false_type{});
+}
+template <int V0, int... Vs, typename F>
+auto with_int(int v, F&& f) {
+    if constexpr (sizeof...(Vs) == 0) return f(std::integral_constant<int, V0>{});
+    else return v == V0 ? f(std::integral_constant<int, V0>{}) : with_int<Vs...>(v, f);
+}
+
 // the paired-lines flags of a job as the template arguments <IN_P, OUT_P> of `launch`
 template <typename F>
 int paired_dispatch(const RowTJob& job, F&& launch) {
-    using T = std::true_type; using N = std::false_type;
-    const bool in_p = job.flags & P2_IN_PAIRED, out_p = job.flags & P2_OUT_PAIRED;
-    if (in_p) return out_p ? launch(T{}, T{}) : launch(T{}, N{});
-    return out_p ? launch(N{}, T{}) : launch(N{}, N{});
+    return with_bool(job.flags & P2_IN_PAIRED, [&](auto in_p) { return with_bool(job.flags & P2_OUT_PAIRED, [&](auto out_p) { return launch(in_p, out_p); }); });
 }
 
 // lines of 2 R^2 = 512 points
@@ -2796,34 +2807,56 @@ void* msl_device_ptr(msl_handle* h, msl_buffer what) {
 }
 
 // ---- reductions over resident results (reduce.h) ------------------------------------------------------
-// resolve (src, B, F, K, ld) for the TACAW reductions: NULL = the handle's intensity buffer
-static int intensity_source(msl_handle* h, const char* who, const void** src, int64_t* B, int64_t* F, int64_t* K, int64_t* ld) {
+// The rows a reduction reads: (B, R, K) elements at p, R the frame or frequency axis, rows ld elements apart.
+struct Rows { const void* p; int64_t B, R, K, ld; };
+
+// what a NULL source means, and what else resolve_rows() refuses
+enum : unsigned {
+    SRC_INTENSITY = 0,         // NULL = the handle's intensity buffer (after msl_tacaw)
+    SRC_WAVEFUNCTION = 1,      // NULL = the exit block of the handle's resident result
+    SRC_FIRST_B = 2,           // NULL reads the first B probes (B < 1: every probe); without it, always every probe
+    SRC_INT32_ROWS = 4,        // B * R must fit 31 bits
+};
+
+// The one source convention of every reduction: r holds the caller's (src, B, R, K, ld).  src = NULL asks for the resident
+// buffer that `flags` names, with its own R, K and pitch; a pointer with ld = 0 has rows of pitch K.
+static int resolve_rows(msl_handle* h, const char* who, unsigned flags, Rows* r) {
     if (!h) return fail(h, MSL_ERR_INVALID, "null handle");
-    if (!*src) {
-        if (!h->intensity) return fail(h, MSL_ERR_STATE, "%s: no intensity (call msl_tacaw)", who);
-        *src = h->intensity; *B = h->cfg.n_probes; *F = h->intensity_F; *K = (int64_t)h->wpix; *ld = (int64_t)h->intensity_ld;
-    } else if (*ld == 0) {
-        *ld = *K;
+    if (!r->p) {
+        const bool wf = flags & SRC_WAVEFUNCTION;
+        if (!(wf ? (const void*)h->wf : (const void*)h->intensity.p))
+            return fail(h, MSL_ERR_STATE, wf ? "%s: no wavefunction buffer" : "%s: no intensity (call msl_tacaw)", who);
+        if (!(flags & SRC_FIRST_B) || r->B < 1) r->B = h->cfg.n_probes;
+        if (r->B > h->cfg.n_probes) return fail(h, MSL_ERR_INVALID, "%s: %lld probes, the handle has %d", who, (long long)r->B, h->cfg.n_probes);
+        if (wf) *r = Rows{h->wf, r->B, h->cfg.n_frames, (int64_t)h->wpix, (int64_t)h->wpitch};
+        else *r = Rows{h->intensity.p, r->B, h->intensity_F, (int64_t)h->wpix, (int64_t)h->intensity_ld};
+    } else if (r->ld == 0) {
+        r->ld = r->K;
     }
-    if (*B < 1 || *F < 1 || *K < 1) return fail(h, MSL_ERR_INVALID, "%s: bad shape (%lld,%lld,%lld)", who, (long long)*B, (long long)*F, (long long)*K);
-    if (*ld < *K) return fail(h, MSL_ERR_INVALID, "%s: row pitch %lld below the row length %lld", who, (long long)*ld, (long long)*K);
-    if (*B * *F > 0x7fffffffLL) return fail(h, MSL_ERR_UNSUPPORTED, "%s: more than 2^31 rows", who);
+    if (r->B < 1 || r->R < 1 || r->K < 1) return fail(h, MSL_ERR_INVALID, "%s: bad shape (%lld,%lld,%lld)", who, (long long)r->B, (long long)r->R, (long long)r->K);
+    if (r->ld < r->K) return fail(h, MSL_ERR_INVALID, "%s: row pitch %lld below the row length %lld", who, (long long)r->ld, (long long)r->K);
+    if ((flags & SRC_INT32_ROWS) && r->B * r->R > 0x7fffffffLL) return fail(h, MSL_ERR_UNSUPPORTED, "%s: more than 2^31 rows", who);
     return MSL_OK;
 }
 
-// the same for the reductions over complex results: NULL = the exit block of the handle's resident result, of which *B < 1 asks
-// for every probe
-static int resident_wavefunction(msl_handle* h, const char* who, const void** src, int64_t* B, int64_t* T, int64_t* K, int64_t* ld) {
-    if (!*src) {
-        if (!h->wf) return fail(h, MSL_ERR_STATE, "%s: no wavefunction buffer", who);
-        if (*B < 1) *B = h->cfg.n_probes;
-        if (*B > h->cfg.n_probes) return fail(h, MSL_ERR_INVALID, "%s: %lld probes, the handle has %d", who, (long long)*B, h->cfg.n_probes);
-        *src = h->wf; *T = h->cfg.n_frames; *K = (int64_t)h->wpix; *ld = (int64_t)h->wpitch;
-    } else if (*ld == 0) {
-        *ld = *K;
-    }
-    if (*B < 1 || *T < 1 || *K < 1 || *ld < *K) return fail(h, MSL_ERR_INVALID, "%s: bad shape (%lld,%lld,%lld) ld %lld", who, (long long)*B, (long long)*T,
-                                                            (long long)*K, (long long)*ld);
+// rows [t0, t0 + count) of an axis of n `what` ("frame slots", "frequency bins")
+static int check_slots(msl_handle* h, const char* who, const char* what, int64_t t0, int64_t count, int64_t n) {
+    if (count < 1 || t0 < 0 || t0 + count > n)
+        return fail(h, MSL_ERR_INVALID, "%s: %s [%lld,%lld) outside [0,%lld)", who, what, (long long)t0, (long long)(t0 + count), (long long)n);
+    return MSL_OK;
+}
+
+// a bx x by bin that divides a wx x wy window
+static int check_window_bin(msl_handle* h, const char* who, int wx, int wy, int bx, int by) {
+    if (wx < 1 || wy < 1) return fail(h, MSL_ERR_INVALID, "%s: window %d x %d", who, wx, wy);
+    if (bx < 1 || by < 1 || wx % bx || wy % by) return fail(h, MSL_ERR_INVALID, "%s: bin %d x %d does not divide the window %d x %d", who, bx, by, wx, wy);
+    return MSL_OK;
+}
+
+// device to host on the handle's stream, and wait for it
+static int download_sync(msl_handle* h, void* dst, const void* src, size_t bytes) {
+    HIPCHK(h, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
     return MSL_OK;
 }
 
@@ -2851,50 +2884,51 @@ static int reduce_rows(msl_handle* h, const void* src, bool complex_abs, int64_t
         HIPCHK(h, hipMemsetAsync(d_mask, 0, mask_bytes, h->stream));
         HIPCHK(h, hipMemcpyAsync(d_mask, mask, (size_t)K, hipMemcpyHostToDevice, h->stream));
     }
-    dim3 grid(n_chunks, (unsigned)rows);
-    if (complex_abs) hipLaunchKernelGGL(reduce_k_kernel<true>, grid, dim3(256), 0, h->stream, src, d_mask, (long long)K, (long long)ld, n_chunks, d_part);
-    else hipLaunchKernelGGL(reduce_k_kernel<false>, grid, dim3(256), 0, h->stream, src, d_mask, (long long)K, (long long)ld, n_chunks, d_part);
+    with_bool(complex_abs, [&](auto c_abs) {
+        hipLaunchKernelGGL(reduce_k_kernel<decltype(c_abs)::value>, dim3(n_chunks, (unsigned)rows), dim3(256), 0, h->stream, src, d_mask, (long long)K,
+                           (long long)ld, n_chunks, d_part);
+    });
     HIPCHK(h, hipGetLastError());
     std::vector<double> part((size_t)rows * n_chunks);
-    HIPCHK(h, hipMemcpyAsync(part.data(), d_part, part_bytes, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if ((rc = download_sync(h, part.data(), d_part, part_bytes))) return rc;
     sum_row_parts(part, rows, n_chunks, out);
     return MSL_OK;
 }
 
 int msl_tacaw_spectrum(msl_handle* h, const void* d_src_f32, int64_t B, int64_t F, int64_t K, int64_t ld, const uint8_t* mask, double* out) {
     if (!out) return fail(h, MSL_ERR_INVALID, "msl_tacaw_spectrum: null output");
-    int rc = intensity_source(h, "msl_tacaw_spectrum", &d_src_f32, &B, &F, &K, &ld);
+    Rows r{d_src_f32, B, F, K, ld};
+    int rc = resolve_rows(h, "msl_tacaw_spectrum", SRC_INTENSITY | SRC_INT32_ROWS, &r);
     if (rc) return rc;
-    if (B * F > 65535) {                       // grid.y limit: go probe by probe
-        if (F > 65535) return fail(h, MSL_ERR_UNSUPPORTED, "msl_tacaw_spectrum: more than 65535 frequencies");
-        for (int64_t b = 0; b < B; ++b)
-            if ((rc = reduce_rows(h, (const float*)d_src_f32 + b * F * ld, false, F, K, ld, mask, out + b * F))) return rc;
+    if (r.B * r.R > 65535) {                   // grid.y limit: go probe by probe
+        if (r.R > 65535) return fail(h, MSL_ERR_UNSUPPORTED, "msl_tacaw_spectrum: more than 65535 frequencies");
+        for (int64_t b = 0; b < r.B; ++b)
+            if ((rc = reduce_rows(h, (const float*)r.p + b * r.R * r.ld, false, r.R, r.K, r.ld, mask, out + b * r.R))) return rc;
         return MSL_OK;
     }
-    return reduce_rows(h, d_src_f32, false, B * F, K, ld, mask, out);
+    return reduce_rows(h, r.p, false, r.B * r.R, r.K, r.ld, mask, out);
 }
 
 int msl_tacaw_spectrum_weighted(msl_handle* h, const void* d_src_f32, int64_t B, int64_t F, int64_t K, int64_t ld, const double* weight, double* out) {
     if (!out || !weight) return fail(h, MSL_ERR_INVALID, "msl_tacaw_spectrum_weighted: null argument");
-    int rc = intensity_source(h, "msl_tacaw_spectrum_weighted", &d_src_f32, &B, &F, &K, &ld);
+    Rows r{d_src_f32, B, F, K, ld};
+    int rc = resolve_rows(h, "msl_tacaw_spectrum_weighted", SRC_INTENSITY | SRC_INT32_ROWS, &r);
     if (rc) return rc;
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    const int64_t rows_per = std::min<int64_t>(B * F, 32768);
-    const int n_chunks = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(K / 4096, 4096 / std::max<int64_t>(1, rows_per)), 64));
-    const size_t w_bytes = (size_t)K * sizeof(double), part_bytes = (size_t)rows_per * n_chunks * sizeof(double);
+    const int64_t all = r.B * r.R, rows_per = std::min<int64_t>(all, 32768);
+    const int n_chunks = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(r.K / 4096, 4096 / std::max<int64_t>(1, rows_per)), 64));
+    const size_t w_bytes = (size_t)r.K * sizeof(double), part_bytes = (size_t)rows_per * n_chunks * sizeof(double);
     if ((rc = h->scratch.reserve(h, w_bytes + part_bytes))) return rc;
     double* d_w = (double*)h->scratch.p;
     double* d_part = (double*)(h->scratch + w_bytes);
     HIPCHK(h, hipMemcpyAsync(d_w, weight, w_bytes, hipMemcpyHostToDevice, h->stream));
     std::vector<double> part((size_t)rows_per * n_chunks);
-    for (int64_t r0 = 0; r0 < B * F; r0 += rows_per) {
-        const int64_t rows = std::min<int64_t>(rows_per, B * F - r0);
-        hipLaunchKernelGGL(reduce_kw_kernel, dim3(n_chunks, (unsigned)rows), dim3(256), 0, h->stream, (const float*)d_src_f32 + r0 * ld, d_w,
-                           (long long)K, (long long)ld, n_chunks, d_part);
+    for (int64_t r0 = 0; r0 < all; r0 += rows_per) {
+        const int64_t rows = std::min<int64_t>(rows_per, all - r0);
+        hipLaunchKernelGGL(reduce_kw_kernel, dim3(n_chunks, (unsigned)rows), dim3(256), 0, h->stream, (const float*)r.p + r0 * r.ld, d_w,
+                           (long long)r.K, (long long)r.ld, n_chunks, d_part);
         HIPCHK(h, hipGetLastError());
-        HIPCHK(h, hipMemcpyAsync(part.data(), d_part, (size_t)rows * n_chunks * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
+        if ((rc = download_sync(h, part.data(), d_part, (size_t)rows * n_chunks * sizeof(double)))) return rc;
         sum_row_parts(part, rows, n_chunks, out + r0);
     }
     return MSL_OK;
@@ -2902,18 +2936,16 @@ int msl_tacaw_spectrum_weighted(msl_handle* h, const void* d_src_f32, int64_t B,
 
 int msl_adf(msl_handle* h, const void* d_src_c64, int64_t B, int64_t T, int64_t K, int64_t ld, const uint8_t* mask, double* out) {
     if (!h || !out) return fail(h, MSL_ERR_INVALID, "msl_adf: null argument");
-    if (!d_src_c64) B = 0;                      // the resident result: always every probe
-    const int rc0 = resident_wavefunction(h, "msl_adf", &d_src_c64, &B, &T, &K, &ld);
-    if (rc0 == MSL_ERR_INVALID) return fail(h, rc0, "msl_adf: bad shape");        // (its message carries no numbers)
-    if (rc0) return rc0;
-    if (T > 65535) return fail(h, MSL_ERR_UNSUPPORTED, "msl_adf: more than 65535 frames");
-    std::vector<double> rows((size_t)T);
-    for (int64_t b = 0; b < B; ++b) {
-        int rc = reduce_rows(h, (const float2*)d_src_c64 + b * T * ld, true, T, K, ld, mask, rows.data());
-        if (rc) return rc;
+    Rows r{d_src_c64, B, T, K, ld};
+    int rc = resolve_rows(h, "msl_adf", SRC_WAVEFUNCTION, &r);              // the resident result: always every probe
+    if (rc) return rc;
+    if (r.R > 65535) return fail(h, MSL_ERR_UNSUPPORTED, "msl_adf: more than 65535 frames");
+    std::vector<double> rows((size_t)r.R);
+    for (int64_t b = 0; b < r.B; ++b) {
+        if ((rc = reduce_rows(h, (const float2*)r.p + b * r.R * r.ld, true, r.R, r.K, r.ld, mask, rows.data()))) return rc;
         double s = 0;
         for (double v : rows) s += v;
-        out[b] = s / (double)T;                // mean over frames of the annulus sum (haadf_data.py:80)
+        out[b] = s / (double)r.R;              // mean over frames of the annulus sum (haadf_data.py:80)
     }
     return MSL_OK;
 }
@@ -2952,148 +2984,115 @@ int msl_set_detectors(msl_handle* h, int32_t n, const uint16_t* member_K, const 
     return MSL_OK;
 }
 
-extern "C++" template <int ND>
-static void launch_detect(msl_handle* h, int mode, bool vec, dim3 grid, const float2* src, long long T, long long t0, long long count, long long ld,
-                          long long K, long long rows, int rows_per_wg, float* part) {
-#define MSL_DET_LAUNCH(M, V)                                                                                                       \
-    hipLaunchKernelGGL((detect_tile_kernel<ND, M, V>), grid, dim3(256), 0, h->stream, src, T, t0, count, ld, K, rows, rows_per_wg, \
-                       h->det_mask, h->det_kx, h->det_ky, h->det_wy, h->det_amp, h->det_cx, h->det_cy, part)
-    if (vec) {
-        if (mode == 0) MSL_DET_LAUNCH(0, true); else if (mode == 1) MSL_DET_LAUNCH(1, true); else MSL_DET_LAUNCH(2, true);
-    } else {
-        if (mode == 0) MSL_DET_LAUNCH(0, false); else if (mode == 1) MSL_DET_LAUNCH(1, false); else MSL_DET_LAUNCH(2, false);
-    }
-#undef MSL_DET_LAUNCH
+// The tiling of a detector pass (detect.h) over `rows` rows of K pixels with n detectors: every workgroup of the tile kernel
+// writes ND partial sums per row and tile to d_part, detect_finish_kernel<ND> adds them to the (rows, n) float64 at d_out.
+struct DetTiling {
+    int n, ND;                                  // detectors, and their padded count: 4, 8 or 16
+    int64_t rows, n_tiles, per, blocks_y;       // tiles of 64 * (64 / ND) pixels along a row; rows per workgroup; grid.y
+    size_t part_bytes, out_bytes;
+    float* d_part;
+    double* d_out;
+    dim3 grid() const { return dim3((unsigned)n_tiles, (unsigned)blocks_y); }
+};
+
+// the arithmetic of it, which needs no device
+static DetTiling det_tiling(int64_t rows, int64_t K, int n) {
+    DetTiling t{};
+    t.n = n; t.rows = rows;
+    t.ND = n <= 4 ? 4 : (n <= 8 ? 8 : 16);
+    const int64_t TP = 64 * (64 / t.ND);
+    t.n_tiles = (K + TP - 1) / TP;
+    // rows per workgroup: the tile's coefficients are built once per row block; at most 65535 row blocks (grid.y)
+    t.per = std::min<int64_t>(64, (rows + 3) / 4 * 4);
+    t.per = std::max<int64_t>(t.per, ((rows + 65534) / 65535 + 3) / 4 * 4);
+    t.blocks_y = (rows + t.per - 1) / t.per;
+    t.part_bytes = ((size_t)rows * t.n_tiles * t.ND * sizeof(float) + 255) & ~(size_t)255;
+    t.out_bytes = (size_t)rows * n * sizeof(double);
+    return t;
+}
+
+// the preconditions that msl_detect and msl_spectrum_detect share, then the tiling of the `count` rows per probe from t0 on,
+// with its two pieces of h->scratch
+static int plan_detect(msl_handle* h, const char* who, const Rows& r, const char* what, int32_t t0, int32_t count, DetTiling* t) {
+    if ((size_t)r.K != h->det_K) return fail(h, MSL_ERR_INVALID, "%s: rows of %lld pixels, the detectors cover %zu", who, (long long)r.K, h->det_K);
+    int rc = check_slots(h, who, what, t0, count, r.R);
+    if (rc) return rc;
+    if (r.B * count > 0x7fffffffLL) return fail(h, MSL_ERR_UNSUPPORTED, "%s: more than 2^31 rows", who);
+    *t = det_tiling(r.B * count, r.K, h->det_n);
+    if (t->n_tiles > 0x7fffffffLL) return fail(h, MSL_ERR_UNSUPPORTED, "%s: rows too long", who);
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    if ((rc = h->scratch.reserve(h, t->part_bytes + t->out_bytes))) return rc;
+    t->d_part = (float*)h->scratch.p;
+    t->d_out = (double*)(h->scratch + t->part_bytes);
+    return MSL_OK;
+}
+
+// after the tile kernel: the sums over the tiles, and the result to the host
+static int detect_finish(msl_handle* h, const DetTiling& t, double* out) {
+    HIPCHK(h, hipGetLastError());
+    with_int<4, 8, 16>(t.ND, [&](auto nd) {
+        hipLaunchKernelGGL(detect_finish_kernel<decltype(nd)::value>, dim3((unsigned)t.rows), dim3(256), 0, h->stream, t.d_part, (long long)t.n_tiles, t.n,
+                           t.d_out);
+    });
+    HIPCHK(h, hipGetLastError());
+    return download_sync(h, out, t.d_out, t.out_bytes);
 }
 
 int msl_detect(msl_handle* h, const void* d_src_c64, int64_t B, int64_t T, int64_t K, int64_t ld, int32_t t0, int32_t count, double* out) {
     if (!h || !out) return fail(h, MSL_ERR_INVALID, "msl_detect: null argument");
     if (h->det_n == 0) return fail(h, MSL_ERR_STATE, "msl_detect: no detectors (call msl_set_detectors)");
-    int rc = resident_wavefunction(h, "msl_detect", &d_src_c64, &B, &T, &K, &ld);
-    if (rc) return rc;
-    if ((size_t)K != h->det_K) return fail(h, MSL_ERR_INVALID, "msl_detect: rows of %lld pixels, the detectors cover %zu", (long long)K, h->det_K);
-    if (count < 1 || t0 < 0 || (int64_t)t0 + count > T)
-        return fail(h, MSL_ERR_INVALID, "msl_detect: frame slots [%d,%d) outside [0,%lld)", t0, t0 + count, (long long)T);
-    const int64_t rows = B * count;
-    if (rows > 0x7fffffffLL) return fail(h, MSL_ERR_UNSUPPORTED, "msl_detect: more than 2^31 rows");
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    const int n = h->det_n;
-    const int ND = n <= 4 ? 4 : (n <= 8 ? 8 : 16);
-    const int64_t TP = 64 * (64 / ND);
-    const int64_t n_tiles = (K + TP - 1) / TP;
-    if (n_tiles > 0x7fffffffLL) return fail(h, MSL_ERR_UNSUPPORTED, "msl_detect: rows too long");
-    // rows per workgroup: the tile's coefficients are built once per row block; at most 65535 row blocks (grid.y)
-    int64_t per = std::min<int64_t>(64, (rows + 3) / 4 * 4);
-    per = std::max<int64_t>(per, ((rows + 65534) / 65535 + 3) / 4 * 4);
-    const int64_t blocks_y = (rows + per - 1) / per;
-    const size_t part_bytes = ((size_t)rows * n_tiles * ND * sizeof(float) + 255) & ~(size_t)255;
-    const size_t out_bytes = (size_t)rows * n * sizeof(double);
-    if ((rc = h->scratch.reserve(h, part_bytes + out_bytes))) return rc;
-    float* d_part = (float*)h->scratch.p;
-    double* d_out = (double*)(h->scratch + part_bytes);
-    const int mode = h->det_amp == 0 ? 0 : (h->det_amp == (1u << n) - 1u ? 1 : 2);
-    const bool vec = (ld % 2 == 0) && (((uintptr_t)d_src_c64 & 15) == 0);
-    const dim3 grid((unsigned)n_tiles, (unsigned)blocks_y);
-    const float2* src = (const float2*)d_src_c64;
-    if (ND == 4) launch_detect<4>(h, mode, vec, grid, src, T, t0, count, ld, K, rows, (int)per, d_part);
-    else if (ND == 8) launch_detect<8>(h, mode, vec, grid, src, T, t0, count, ld, K, rows, (int)per, d_part);
-    else launch_detect<16>(h, mode, vec, grid, src, T, t0, count, ld, K, rows, (int)per, d_part);
-    HIPCHK(h, hipGetLastError());
-    if (ND == 4) hipLaunchKernelGGL(detect_finish_kernel<4>, dim3((unsigned)rows), dim3(256), 0, h->stream, d_part, (long long)n_tiles, n, d_out);
-    else if (ND == 8) hipLaunchKernelGGL(detect_finish_kernel<8>, dim3((unsigned)rows), dim3(256), 0, h->stream, d_part, (long long)n_tiles, n, d_out);
-    else hipLaunchKernelGGL(detect_finish_kernel<16>, dim3((unsigned)rows), dim3(256), 0, h->stream, d_part, (long long)n_tiles, n, d_out);
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return MSL_OK;
+    Rows r{d_src_c64, B, T, K, ld};
+    DetTiling t;
+    int rc;
+    if ((rc = resolve_rows(h, "msl_detect", SRC_WAVEFUNCTION | SRC_FIRST_B, &r)) || (rc = plan_detect(h, "msl_detect", r, "frame slots", t0, count, &t))) return rc;
+    const int mode = h->det_amp == 0 ? 0 : (h->det_amp == (1u << t.n) - 1u ? 1 : 2);
+    const bool vec = (r.ld % 2 == 0) && (((uintptr_t)r.p & 15) == 0);
+    with_int<4, 8, 16>(t.ND, [&](auto nd) { with_int<0, 1, 2>(mode, [&](auto m) { with_bool(vec, [&](auto v) {
+        hipLaunchKernelGGL((detect_tile_kernel<decltype(nd)::value, decltype(m)::value, decltype(v)::value>), t.grid(), dim3(256), 0, h->stream,
+                           (const float2*)r.p, (long long)r.R, (long long)t0, (long long)count, (long long)r.ld, (long long)r.K, (long long)t.rows, (int)t.per,
+                           h->det_mask.p, h->det_kx.p, h->det_ky.p, h->det_wy, h->det_amp, h->det_cx, h->det_cy, t.d_part);
+    }); }); });
+    return detect_finish(h, t, out);
 }
 
 // ---- spectrum detectors (spectrum_detect.h) ---------------------------------------------------------------
-extern "C++" template <int ND>
-static void launch_spectrum_detect(msl_handle* h, int vw, dim3 grid, const float* src, long long F, long long f0, long long count, long long ld,
-                                   long long K, long long rows, int rows_per_wg, float* part, int n, double* out) {
-#define MSL_SPD_LAUNCH(V)                                                                                                          \
-    hipLaunchKernelGGL((spectrum_tile_kernel<ND, V>), grid, dim3(256), 0, h->stream, src, F, f0, count, ld, K, rows, rows_per_wg, \
-                       h->det_mask, part)
-    if (vw == 4) MSL_SPD_LAUNCH(4); else if (vw == 2) MSL_SPD_LAUNCH(2); else MSL_SPD_LAUNCH(1);
-#undef MSL_SPD_LAUNCH
-    hipLaunchKernelGGL(detect_finish_kernel<ND>, dim3((unsigned)rows), dim3(256), 0, h->stream, part, (long long)grid.x, n, out);
-}
-
 int msl_spectrum_detect(msl_handle* h, const void* d_src_f32, int64_t B, int64_t F, int64_t K, int64_t ld, int32_t f0, int32_t count, double* out) {
     if (!h || !out) return fail(h, MSL_ERR_INVALID, "msl_spectrum_detect: null argument");
     if (h->det_n == 0) return fail(h, MSL_ERR_STATE, "msl_spectrum_detect: no detectors (call msl_set_detectors)");
     if (h->det_amp | h->det_cx | h->det_cy)
         return fail(h, MSL_ERR_INVALID, "msl_spectrum_detect: every detector must have the intensity signal (an amplitude or centre-of-mass "
                                         "weight of a TACAW intensity is not defined)");
-    if (!d_src_f32) {
-        if (!h->intensity) return fail(h, MSL_ERR_STATE, "msl_spectrum_detect: no intensity (call msl_tacaw)");
-        if (B < 1) B = h->cfg.n_probes;
-        if (B > h->cfg.n_probes) return fail(h, MSL_ERR_INVALID, "msl_spectrum_detect: %lld probes, the handle has %d", (long long)B, h->cfg.n_probes);
-        d_src_f32 = h->intensity; F = h->intensity_F; K = (int64_t)h->wpix; ld = (int64_t)h->intensity_ld;
-    } else if (ld == 0) {
-        ld = K;
-    }
-    if (B < 1 || F < 1 || K < 1 || ld < K)
-        return fail(h, MSL_ERR_INVALID, "msl_spectrum_detect: bad shape (%lld,%lld,%lld) ld %lld", (long long)B, (long long)F, (long long)K, (long long)ld);
-    if ((size_t)K != h->det_K)
-        return fail(h, MSL_ERR_INVALID, "msl_spectrum_detect: rows of %lld pixels, the detectors cover %zu", (long long)K, h->det_K);
-    if (count < 1 || f0 < 0 || (int64_t)f0 + count > F)
-        return fail(h, MSL_ERR_INVALID, "msl_spectrum_detect: frequency bins [%d,%lld) outside [0,%lld)", f0, (long long)f0 + count, (long long)F);
-    const int64_t rows = B * count;
-    if (rows > 0x7fffffffLL) return fail(h, MSL_ERR_UNSUPPORTED, "msl_spectrum_detect: more than 2^31 rows");
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    const int n = h->det_n;
-    const int ND = n <= 4 ? 4 : (n <= 8 ? 8 : 16);
-    const int64_t TP = 64 * (64 / ND);
-    const int64_t n_tiles = (K + TP - 1) / TP;
-    if (n_tiles > 0x7fffffffLL) return fail(h, MSL_ERR_UNSUPPORTED, "msl_spectrum_detect: rows too long");
-    // rows per workgroup as in msl_detect: the tile's coefficients are built once per row block; at most 65535 row blocks (grid.y)
-    int64_t per = std::min<int64_t>(64, (rows + 3) / 4 * 4);
-    per = std::max<int64_t>(per, ((rows + 65534) / 65535 + 3) / 4 * 4);
-    const int64_t blocks_y = (rows + per - 1) / per;
-    const size_t part_bytes = ((size_t)rows * n_tiles * ND * sizeof(float) + 255) & ~(size_t)255;
-    const size_t out_bytes = (size_t)rows * n * sizeof(double);
+    Rows r{d_src_f32, B, F, K, ld};
+    DetTiling t;
     int rc;
-    if ((rc = h->scratch.reserve(h, part_bytes + out_bytes))) return rc;
-    float* d_part = (float*)h->scratch.p;
-    double* d_out = (double*)(h->scratch + part_bytes);
+    if ((rc = resolve_rows(h, "msl_spectrum_detect", SRC_INTENSITY | SRC_FIRST_B, &r)) ||
+        (rc = plan_detect(h, "msl_spectrum_detect", r, "frequency bins", f0, count, &t))) return rc;
     // pixels per load: the rows start at src + row * ld floats, the tiles at multiples of 256 pixels
-    const uintptr_t base = (uintptr_t)d_src_f32;
-    const int vw = (ld % 4 == 0 && (base & 15) == 0) ? 4 : ((ld % 2 == 0 && (base & 7) == 0) ? 2 : 1);
-    const dim3 grid((unsigned)n_tiles, (unsigned)blocks_y);
-    const float* src = (const float*)d_src_f32;
-    if (ND == 4) launch_spectrum_detect<4>(h, vw, grid, src, F, f0, count, ld, K, rows, (int)per, d_part, n, d_out);
-    else if (ND == 8) launch_spectrum_detect<8>(h, vw, grid, src, F, f0, count, ld, K, rows, (int)per, d_part, n, d_out);
-    else launch_spectrum_detect<16>(h, vw, grid, src, F, f0, count, ld, K, rows, (int)per, d_part, n, d_out);
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return MSL_OK;
+    const uintptr_t base = (uintptr_t)r.p;
+    const int vw = (r.ld % 4 == 0 && (base & 15) == 0) ? 4 : ((r.ld % 2 == 0 && (base & 7) == 0) ? 2 : 1);
+    with_int<4, 8, 16>(t.ND, [&](auto nd) { with_int<4, 2, 1>(vw, [&](auto w) {
+        hipLaunchKernelGGL((spectrum_tile_kernel<decltype(nd)::value, decltype(w)::value>), t.grid(), dim3(256), 0, h->stream, (const float*)r.p,
+                           (long long)r.R, (long long)f0, (long long)count, (long long)r.ld, (long long)r.K, (long long)t.rows, (int)t.per, h->det_mask.p,
+                           t.d_part);
+    }); });
+    return detect_finish(h, t, out);
 }
 
 // ---- diffraction patterns (diffract.h) --------------------------------------------------------------------
-extern "C++" template <int MODE>
-static void launch_diffract(msl_handle* h, bool vec, unsigned grid, unsigned threads, size_t lds, const float2* src, long long T, long long t0, int count,
-                            long long ld, int wx, int wy, int bx, int by, long long strips, int per, double* out) {
-    if (vec) hipLaunchKernelGGL((diffract_kernel<MODE, true>), dim3(grid), dim3(threads), lds, h->stream, src, T, t0, count, ld, wx, wy, bx, by, strips, per, out);
-    else hipLaunchKernelGGL((diffract_kernel<MODE, false>), dim3(grid), dim3(threads), lds, h->stream, src, T, t0, count, ld, wx, wy, bx, by, strips, per, out);
-}
-
 int msl_diffract(msl_handle* h, const void* d_src_c64, int64_t B, int64_t T, int64_t K, int64_t ld, int32_t t0, int32_t count, int32_t wx, int32_t wy,
                  int32_t bx, int32_t by, double* out) {
     if (!h || !out) return fail(h, MSL_ERR_INVALID, "msl_diffract: null argument");
     const bool resident = !d_src_c64;
-    int rc = resident_wavefunction(h, "msl_diffract", &d_src_c64, &B, &T, &K, &ld);
+    Rows r{d_src_c64, B, T, K, ld};
+    int rc = resolve_rows(h, "msl_diffract", SRC_WAVEFUNCTION | SRC_FIRST_B, &r);
     if (rc) return rc;
     if (resident && (wx != h->wx / h->bx || wy != h->wy / h->by))
         return fail(h, MSL_ERR_INVALID, "msl_diffract: window %d x %d, the handle stores %d x %d", wx, wy, h->wx / h->bx, h->wy / h->by);
-    if (wx < 1 || wy < 1 || (int64_t)wx * wy != K) return fail(h, MSL_ERR_INVALID, "msl_diffract: window %d x %d over rows of %lld pixels", wx, wy, (long long)K);
-    if (bx < 1 || by < 1 || wx % bx || wy % by) return fail(h, MSL_ERR_INVALID, "msl_diffract: bin %d x %d does not divide the window %d x %d", bx, by, wx, wy);
-    if (count < 1 || t0 < 0 || (int64_t)t0 + count > T)
-        return fail(h, MSL_ERR_INVALID, "msl_diffract: frame slots [%d,%d) outside [0,%lld)", t0, t0 + count, (long long)T);
+    if ((rc = check_window_bin(h, "msl_diffract", wx, wy, bx, by))) return rc;
+    if ((int64_t)wx * wy != r.K) return fail(h, MSL_ERR_INVALID, "msl_diffract: window %d x %d over rows of %lld pixels", wx, wy, (long long)r.K);
+    if ((rc = check_slots(h, "msl_diffract", "frame slots", t0, count, r.R))) return rc;
     const int mx = wx / bx, my = wy / by;
-    const int64_t strips = B * mx;                               // one row of bins of one probe
+    const int64_t strips = r.B * mx;                             // one row of bins of one probe
     if ((int64_t)count * bx > 0x3fffffffLL) return fail(h, MSL_ERR_UNSUPPORTED, "msl_diffract: more than 2^30 rows per bin");
     const bool pow2 = (by & (by - 1)) == 0;
     const int mode = by == 1 ? DIFF_DIRECT : (pow2 && by <= 64 ? DIFF_SHFL : DIFF_LDS);
@@ -3103,7 +3102,7 @@ int msl_diffract(msl_handle* h, const void* d_src_c64, int64_t B, int64_t T, int
     const size_t n_out = (size_t)strips * my;
     if ((rc = h->diff_out.reserve(h, n_out))) return rc;
     // 16-byte loads need every row to start on 16 bytes: base, image pitch and row length even in pixels
-    const bool vec = (ld % 2 == 0) && (wy % 2 == 0) && (((uintptr_t)d_src_c64 & 15) == 0);
+    const bool vec = (r.ld % 2 == 0) && (wy % 2 == 0) && (((uintptr_t)r.p & 15) == 0);
     const int cols = vec ? (wy + 1) / 2 : wy;
     const unsigned threads = (unsigned)std::min(256, std::max(64, (cols + 63) / 64 * 64));
     // strips per workgroup: about 64 KB of reads each, but at least 4096 workgroups while there are that many strips
@@ -3113,16 +3112,15 @@ int msl_diffract(msl_handle* h, const void* d_src_c64, int64_t B, int64_t T, int
     per = std::max<int64_t>(per, (strips + 0x7ffffffeLL) / 0x7fffffffLL);
     const unsigned grid = (unsigned)((strips + per - 1) / per);
     if ((rc = begin_timed(h, 1))) return rc;
-    const float2* src = (const float2*)d_src_c64;
-    if (mode == DIFF_DIRECT) launch_diffract<DIFF_DIRECT>(h, vec, grid, threads, lds, src, T, t0, count, ld, wx, wy, bx, by, strips, (int)per, h->diff_out);
-    else if (mode == DIFF_SHFL) launch_diffract<DIFF_SHFL>(h, vec, grid, threads, lds, src, T, t0, count, ld, wx, wy, bx, by, strips, (int)per, h->diff_out);
-    else launch_diffract<DIFF_LDS>(h, vec, grid, threads, lds, src, T, t0, count, ld, wx, wy, bx, by, strips, (int)per, h->diff_out);
+    with_int<DIFF_DIRECT, DIFF_SHFL, DIFF_LDS>(mode, [&](auto m) { with_bool(vec, [&](auto v) {
+        hipLaunchKernelGGL((diffract_kernel<decltype(m)::value, decltype(v)::value>), dim3(grid), dim3(threads), lds, h->stream, (const float2*)r.p,
+                           (long long)r.R, (long long)t0, (int)count, (long long)r.ld, (int)wx, (int)wy, (int)bx, (int)by, (long long)strips, (int)per,
+                           h->diff_out.p);
+    }); });
     HIPCHK(h, hipGetLastError());
     if ((rc = mark_launch(h, K_OTHER))) return rc;
-    h->ctr.algorithmic_bytes += 8ull * (uint64_t)K * (uint64_t)B * (uint64_t)count;
-    HIPCHK(h, hipMemcpyAsync(out, h->diff_out, n_out * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return MSL_OK;
+    h->ctr.algorithmic_bytes += 8ull * (uint64_t)r.K * (uint64_t)r.B * (uint64_t)count;
+    return download_sync(h, out, h->diff_out, n_out * sizeof(double));
 }
 
 // ---- coherent frame sums (coherent.h) ---------------------------------------------------------------------
@@ -3141,31 +3139,30 @@ int msl_coherent_reset(msl_handle* h, int64_t B) {
 
 int msl_coherent_add(msl_handle* h, const void* d_src_c64, int64_t B, int64_t T, int64_t K, int64_t ld, int32_t t0, int32_t count) {
     if (!h) return fail(h, MSL_ERR_INVALID, "msl_coherent_add: null handle");
-    int rc = resident_wavefunction(h, "msl_coherent_add", &d_src_c64, &B, &T, &K, &ld);
+    Rows r{d_src_c64, B, T, K, ld};
+    int rc = resolve_rows(h, "msl_coherent_add", SRC_WAVEFUNCTION | SRC_FIRST_B, &r);
     if (rc) return rc;
-    if (B > h->coh_B || K > (int64_t)h->wpitch)
-        return fail(h, MSL_ERR_INVALID, "msl_coherent_add: %lld probes of %lld pixels, the last msl_coherent_reset sized %lld of up to %zu", (long long)B,
-                    (long long)K, (long long)h->coh_B, h->wpitch);
-    if (h->coh_K && K != h->coh_K)
-        return fail(h, MSL_ERR_INVALID, "msl_coherent_add: rows of %lld pixels after rows of %lld (msl_coherent_reset starts a new sum)", (long long)K,
+    if (r.B > h->coh_B || r.K > (int64_t)h->wpitch)
+        return fail(h, MSL_ERR_INVALID, "msl_coherent_add: %lld probes of %lld pixels, the last msl_coherent_reset sized %lld of up to %zu", (long long)r.B,
+                    (long long)r.K, (long long)h->coh_B, h->wpitch);
+    if (h->coh_K && r.K != h->coh_K)
+        return fail(h, MSL_ERR_INVALID, "msl_coherent_add: rows of %lld pixels after rows of %lld (msl_coherent_reset starts a new sum)", (long long)r.K,
                     (long long)h->coh_K);
-    if (count < 1 || t0 < 0 || (int64_t)t0 + count > T)
-        return fail(h, MSL_ERR_INVALID, "msl_coherent_add: frame slots [%d,%d) outside [0,%lld)", t0, t0 + count, (long long)T);
+    if ((rc = check_slots(h, "msl_coherent_add", "frame slots", t0, count, r.R))) return rc;
     HIPCHK(h, hipSetDevice(h->cfg.device));
     // 16-byte loads need every image to start on 16 bytes and to end with a whole column pair
-    const bool vec = (ld % 2 == 0) && (K % 2 == 0) && (((uintptr_t)d_src_c64 & 15) == 0);
-    const int64_t lanes = vec ? K / 2 : K;
-    const dim3 grid((unsigned)((lanes + 255) / 256), (unsigned)std::min<int64_t>(B, 65535));
+    const bool vec = (r.ld % 2 == 0) && (r.K % 2 == 0) && (((uintptr_t)r.p & 15) == 0);
+    const int64_t lanes = vec ? r.K / 2 : r.K;
+    const dim3 grid((unsigned)((lanes + 255) / 256), (unsigned)std::min<int64_t>(r.B, 65535));
     if ((rc = begin_timed(h, 1))) return rc;
-    const float2* src = (const float2*)d_src_c64;
-    if (vec) hipLaunchKernelGGL(coherent_add_kernel<true>, grid, dim3(256), 0, h->stream, src, (long long)B, (long long)T, (long long)t0, (int)count,
-                                (long long)ld, (long long)K, (long long)h->wpitch, h->coh_acc.p);
-    else hipLaunchKernelGGL(coherent_add_kernel<false>, grid, dim3(256), 0, h->stream, src, (long long)B, (long long)T, (long long)t0, (int)count,
-                            (long long)ld, (long long)K, (long long)h->wpitch, h->coh_acc.p);
+    with_bool(vec, [&](auto v) {
+        hipLaunchKernelGGL(coherent_add_kernel<decltype(v)::value>, grid, dim3(256), 0, h->stream, (const float2*)r.p, (long long)r.B, (long long)r.R,
+                           (long long)t0, (int)count, (long long)r.ld, (long long)r.K, (long long)h->wpitch, h->coh_acc.p);
+    });
     HIPCHK(h, hipGetLastError());
     if ((rc = mark_launch(h, K_OTHER))) return rc;
-    h->coh_K = K;
-    h->ctr.algorithmic_bytes += (uint64_t)K * (uint64_t)B * (8ull * (uint64_t)count + 32ull);
+    h->coh_K = r.K;
+    h->ctr.algorithmic_bytes += (uint64_t)r.K * (uint64_t)r.B * (8ull * (uint64_t)count + 32ull);
     return MSL_OK;
 }
 
@@ -3174,16 +3171,16 @@ int msl_coherent_finish(msl_handle* h, int64_t B, int32_t n, int32_t wx, int32_t
     if (B < 1) B = h->coh_B;
     if (B < 1 || B > h->coh_B) return fail(h, MSL_ERR_INVALID, "msl_coherent_finish: %lld probes, the last msl_coherent_reset sized %lld", (long long)B, (long long)h->coh_B);
     if (n < 1) return fail(h, MSL_ERR_INVALID, "msl_coherent_finish: %d frames", n);
+    int rc = check_window_bin(h, "msl_coherent_finish", wx, wy, bx, by);
+    if (rc) return rc;
     const int64_t K = (int64_t)wx * wy;
-    if (wx < 1 || wy < 1 || K > (int64_t)h->wpitch || (h->coh_K && K != h->coh_K))
+    if (K > (int64_t)h->wpitch || (h->coh_K && K != h->coh_K))
         return fail(h, MSL_ERR_INVALID, "msl_coherent_finish: window %d x %d over rows of %lld pixels", wx, wy, (long long)(h->coh_K ? h->coh_K : (int64_t)h->wpitch));
-    if (bx < 1 || by < 1 || wx % bx || wy % by) return fail(h, MSL_ERR_INVALID, "msl_coherent_finish: bin %d x %d does not divide the window %d x %d", bx, by, wx, wy);
     if ((int64_t)bx * by > 0x7fffffffLL) return fail(h, MSL_ERR_UNSUPPORTED, "msl_coherent_finish: more than 2^31 pixels per bin");
     HIPCHK(h, hipSetDevice(h->cfg.device));
     const int mx = wx / bx, my = wy / by;
     const int64_t bins = B * mx * my;
-    int rc = h->diff_out.reserve(h, (size_t)bins);              // the staging of msl_diffract: both calls leave it read
-    if (rc) return rc;
+    if ((rc = h->diff_out.reserve(h, (size_t)bins))) return rc;  // the staging of msl_diffract: both calls leave it read
     int L = 1;                                                   // lanes per bin: the largest power of two <= min(64, bx * by)
     while (L < 64 && 2 * (int64_t)L <= (int64_t)bx * by) L *= 2;
     const int64_t blocks = (bins * L + 255) / 256;
@@ -3191,9 +3188,7 @@ int msl_coherent_finish(msl_handle* h, int64_t B, int32_t n, int32_t wx, int32_t
     hipLaunchKernelGGL(coherent_finish_kernel, dim3((unsigned)blocks), dim3(256), 0, h->stream, h->coh_acc.p, (long long)h->wpitch, (long long)bins, (int)wy,
                        mx, my, (int)bx, (int)by, L, (double)n * (double)n, h->diff_out.p);
     HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipMemcpyAsync(out, h->diff_out, (size_t)bins * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return MSL_OK;
+    return download_sync(h, out, h->diff_out, (size_t)bins * sizeof(double));
 }
 
 // ---- images through an objective lens (image.h) -----------------------------------------------------------
@@ -3223,10 +3218,10 @@ int msl_image_add(msl_handle* h, const void* d_src_c64, int64_t B, int64_t T, in
     int rc = image_full_grid(h, "msl_image_add");
     if (rc) return rc;
     const msl_config& c = h->cfg;
-    int64_t K = (int64_t)c.nx * c.ny;
-    if ((rc = resident_wavefunction(h, "msl_image_add", &d_src_c64, &B, &T, &K, &ld))) return rc;
-    if (count < 1 || t0 < 0 || (int64_t)t0 + count > T)
-        return fail(h, MSL_ERR_INVALID, "msl_image_add: frame slots [%d,%d) outside [0,%lld)", t0, t0 + count, (long long)T);
+    Rows r{d_src_c64, B, T, (int64_t)c.nx * c.ny, ld};
+    if ((rc = resolve_rows(h, "msl_image_add", SRC_WAVEFUNCTION | SRC_FIRST_B, &r)) || (rc = check_slots(h, "msl_image_add", "frame slots", t0, count, r.R))) return rc;
+    B = r.B; T = r.R; ld = r.ld;
+    const int64_t K = r.K;
     if (!std::isfinite(weight) || !std::isfinite(aperture_k)) return fail(h, MSL_ERR_INVALID, "msl_image_add: weight or aperture is not finite");
     bool has_chi = false;
     for (int k = 0; polar14x2 && k < 28; ++k) {
@@ -3250,10 +3245,10 @@ int msl_image_add(msl_handle* h, const void* d_src_c64, int64_t B, int64_t T, in
             ab.b[k] = term_m[k] ? w * sin(term_m[k] * polar14x2[2 * k + 1]) : 0.0;
         }
     }
-    const float2* src = (const float2*)d_src_c64 + (int64_t)t0 * ld;
+    const float2* src = (const float2*)r.p + (int64_t)t0 * ld;
     const bool pitch_even = h->pitch % 2 == 0;
     // 16-byte accesses: an even column maps to an even shifted column and the pair does not wrap (ny, ny / 2 even), every image and row starts on 16 bytes
-    const bool vec_lens = c.ny % 4 == 0 && ld % 2 == 0 && pitch_even && (((uintptr_t)d_src_c64 & 15) == 0);
+    const bool vec_lens = c.ny % 4 == 0 && ld % 2 == 0 && pitch_even && (((uintptr_t)r.p & 15) == 0);
     const bool vec_acc = c.ny % 2 == 0 && pitch_even;
     const int64_t lanes_lens = (int64_t)c.nx * (vec_lens ? c.ny / 2 : c.ny), lanes_acc = (int64_t)c.nx * (vec_acc ? c.ny / 2 : c.ny);
     const unsigned gx_lens = (unsigned)((lanes_lens + 255) / 256), gx_acc = (unsigned)((lanes_acc + 255) / 256);
@@ -3267,20 +3262,19 @@ int msl_image_add(msl_handle* h, const void* d_src_c64, int64_t B, int64_t T, in
         // about 4096 workgroups: H is evaluated once per lane and reused for the images the lane walks
         const unsigned gy = (unsigned)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(images, 65535), (4096 + gx_lens - 1) / gx_lens));
         const float2* s = src + j0 * ld;
-        if (vec_lens) hipLaunchKernelGGL(lens_apply_kernel<true>, dim3(gx_lens, gy), dim3(256), 0, h->stream, s, (long long)B, (long long)T, (long long)ld,
-                                         (long long)images, c.nx, c.ny, h->pitch, 1.0 / (c.nx * c.dx), 1.0 / (c.ny * c.dy), radius, c.wavelength,
-                                         (int)has_chi, ab, h->psi.p);
-        else hipLaunchKernelGGL(lens_apply_kernel<false>, dim3(gx_lens, gy), dim3(256), 0, h->stream, s, (long long)B, (long long)T, (long long)ld,
-                                (long long)images, c.nx, c.ny, h->pitch, 1.0 / (c.nx * c.dx), 1.0 / (c.ny * c.dy), radius, c.wavelength,
-                                (int)has_chi, ab, h->psi.p);
+        with_bool(vec_lens, [&](auto v) {
+            hipLaunchKernelGGL(lens_apply_kernel<decltype(v)::value>, dim3(gx_lens, gy), dim3(256), 0, h->stream, s, (long long)B, (long long)T, (long long)ld,
+                               (long long)images, c.nx, c.ny, h->pitch, 1.0 / (c.nx * c.dx), 1.0 / (c.ny * c.dy), radius, c.wavelength, (int)has_chi, ab,
+                               h->psi.p);
+        });
         HIPCHK(h, hipGetLastError());
         if ((rc = mark_launch(h, K_OTHER))) return rc;
         if ((rc = fft2_inplace(h, h->psi, (int)images, -1, scale, h->pitch))) return rc;
         const dim3 grid_acc(gx_acc, (unsigned)std::min<int64_t>(B, 65535));
-        if (vec_acc) hipLaunchKernelGGL(image_accumulate_kernel<true>, grid_acc, dim3(256), 0, h->stream, (const float2*)h->psi.p, (long long)B, (int)n, c.nx,
-                                        c.ny, h->pitch, weight, (long long)first, (long long)stride, h->img_acc.p);
-        else hipLaunchKernelGGL(image_accumulate_kernel<false>, grid_acc, dim3(256), 0, h->stream, (const float2*)h->psi.p, (long long)B, (int)n, c.nx,
-                                c.ny, h->pitch, weight, (long long)first, (long long)stride, h->img_acc.p);
+        with_bool(vec_acc, [&](auto v) {
+            hipLaunchKernelGGL(image_accumulate_kernel<decltype(v)::value>, grid_acc, dim3(256), 0, h->stream, (const float2*)h->psi.p, (long long)B, (int)n,
+                               c.nx, c.ny, h->pitch, weight, (long long)first, (long long)stride, h->img_acc.p);
+        });
         HIPCHK(h, hipGetLastError());
         if ((rc = mark_launch(h, K_OTHER))) return rc;
     }
@@ -3295,16 +3289,16 @@ int msl_image_download(msl_handle* h, int64_t first, int64_t n, double* out) {
                     (long long)h->img_n);
     HIPCHK(h, hipSetDevice(h->cfg.device));
     const size_t npix = (size_t)h->cfg.nx * h->cfg.ny;
-    HIPCHK(h, hipMemcpyAsync(out, h->img_acc + (size_t)first * npix, (size_t)n * npix * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return MSL_OK;
+    return download_sync(h, out, h->img_acc + (size_t)first * npix, (size_t)n * npix * sizeof(double));
 }
 
 int msl_tacaw_diffraction(msl_handle* h, const void* d_src_f32, int64_t B, int64_t F, int64_t K, int64_t ld, int64_t b0, int64_t b1,
                           int64_t f0, int64_t f1, double scale, double* out) {
     if (!out) return fail(h, MSL_ERR_INVALID, "msl_tacaw_diffraction: null output");
-    int rc = intensity_source(h, "msl_tacaw_diffraction", &d_src_f32, &B, &F, &K, &ld);
+    Rows r{d_src_f32, B, F, K, ld};
+    int rc = resolve_rows(h, "msl_tacaw_diffraction", SRC_INTENSITY | SRC_INT32_ROWS, &r);
     if (rc) return rc;
+    B = r.B; F = r.R; K = r.K; ld = r.ld;
     if (b0 < 0 || b1 > B || b0 >= b1 || f0 < 0 || f1 > F || f0 >= f1)
         return fail(h, MSL_ERR_INVALID, "msl_tacaw_diffraction: range [%lld,%lld) x [%lld,%lld) outside (%lld,%lld)", (long long)b0,
                     (long long)b1, (long long)f0, (long long)f1, (long long)B, (long long)F);
@@ -3314,20 +3308,20 @@ int msl_tacaw_diffraction(msl_handle* h, const void* d_src_f32, int64_t B, int64
     const bool vec = (K % 4 == 0) && (ld % 4 == 0);
     const long long threads = vec ? K / 4 : K;
     const unsigned grid = (unsigned)((threads + 255) / 256);
-    if (vec) hipLaunchKernelGGL(reduce_bf_kernel<true>, dim3(grid), dim3(256), 0, h->stream, (const float*)d_src_f32, (long long)F, (long long)K,
-                                (long long)ld, (long long)b0, (long long)b1, (long long)f0, (long long)f1, scale, d_out);
-    else hipLaunchKernelGGL(reduce_bf_kernel<false>, dim3(grid), dim3(256), 0, h->stream, (const float*)d_src_f32, (long long)F, (long long)K,
-                            (long long)ld, (long long)b0, (long long)b1, (long long)f0, (long long)f1, scale, d_out);
+    with_bool(vec, [&](auto v) {
+        hipLaunchKernelGGL(reduce_bf_kernel<decltype(v)::value>, dim3(grid), dim3(256), 0, h->stream, (const float*)r.p, (long long)F, (long long)K,
+                           (long long)ld, (long long)b0, (long long)b1, (long long)f0, (long long)f1, scale, d_out);
+    });
     HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipMemcpyAsync(out, d_out, (size_t)K * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return MSL_OK;
+    return download_sync(h, out, d_out, (size_t)K * sizeof(double));
 }
 
 int msl_tacaw_dispersion(msl_handle* h, const void* d_src_f32, int64_t B, int64_t F, int64_t K, int64_t ld, const int64_t* idx, int64_t n, float* out) {
     if (!out || !idx) return fail(h, MSL_ERR_INVALID, "msl_tacaw_dispersion: null argument");
-    int rc = intensity_source(h, "msl_tacaw_dispersion", &d_src_f32, &B, &F, &K, &ld);
+    Rows r{d_src_f32, B, F, K, ld};
+    int rc = resolve_rows(h, "msl_tacaw_dispersion", SRC_INTENSITY | SRC_INT32_ROWS, &r);
     if (rc) return rc;
+    B = r.B; F = r.R; K = r.K; ld = r.ld;
     if (n < 1) return fail(h, MSL_ERR_INVALID, "msl_tacaw_dispersion: empty path");
     for (int64_t i = 0; i < n; ++i)
         if (idx[i] < 0 || idx[i] >= K) return fail(h, MSL_ERR_INVALID, "msl_tacaw_dispersion: index %lld outside [0,%lld)", (long long)idx[i], (long long)K);
@@ -3338,12 +3332,10 @@ int msl_tacaw_dispersion(msl_handle* h, const void* d_src_f32, int64_t B, int64_
     float* d_out = (float*)(h->scratch + idx_bytes);
     HIPCHK(h, hipMemcpyAsync(d_idx, idx, idx_bytes, hipMemcpyHostToDevice, h->stream));
     const long long tot = (long long)B * F * n;
-    hipLaunchKernelGGL(gather_k_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, h->stream, (const float*)d_src_f32,
+    hipLaunchKernelGGL(gather_k_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, h->stream, (const float*)r.p,
                        (long long)(B * F), (long long)ld, d_idx, (long long)n, d_out);
     HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return MSL_OK;
+    return download_sync(h, out, d_out, out_bytes);
 }
 
 int msl_download(msl_handle* h, msl_buffer what, void* dst, size_t bytes, int64_t first, int64_t count) {
