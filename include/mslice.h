@@ -223,12 +223,40 @@ int  msl_frame_batch(const msl_handle* h);
  *   MSL_ERR_INVALID without msl_set_structure.  Queued on the stream like msl_build_potential.
  * msl_thermal_positions: the positions the device generates for one configuration, n_atoms x 3 doubles, downloaded (waits for the
  *   stream).
- * Not built: anisotropic or per-axis widths, correlated (phonon-mode) displacements, wrapping at the entrance and exit surfaces.
+ * Not built: anisotropic or per-axis widths, wrapping at the entrance and exit surfaces.  Correlated (phonon-mode) displacements:
+ * msl_set_modes, below.
  * Not in the reference, whose Trajectory.generate_random_displacements (trajectory.py:226) fabricates uniform noise on the host. */
 int  msl_set_structure(msl_handle* h, const double* pos0, const int32_t* Z, const double* sigma, int64_t n_atoms,
                        int32_t ax1, int32_t ax2, int32_t axs);
 int  msl_build_thermal(msl_handle* h, uint64_t seed, int64_t first_config, int32_t count);
 int  msl_thermal_positions(msl_handle* h, uint64_t seed, int64_t config, double* out);
+
+/* ---- phonon modes: lattice-dynamics frames synthesised on the device ----
+ * A frame is a pure function of (seed, frame index c) -- pyslice_amd/phonons.py is the definition.  M modes, each with a wave vector
+ * q_m (Cartesian, cycles / Angstrom, columns 0, 1, 2 like the positions whatever the axes are), a phase advance tau_m (cycles per
+ * frame) and a complex displacement W[m, b, :] (Angstrom) of every basis atom b; atom i is basis atom b_i at the base position r_i:
+ *   g_m(k) = sqrt(-ln u0) exp(2 pi i u1),  u from Philox-4x32-10(counter (m, k & 0xffffffff, k >> 32, 1), key as msl_build_thermal)
+ *   dynamic: k = 0, theta = tau_m c (a time-coherent record)      else: k = c, theta = 0 (independent snapshots)
+ *   C[c,m] = g_m(k) exp(-2 pi i frac(theta)),  E = exp(2 pi i frac((q0 r0 + q1 r1) + q2 r2)),  frac(y) = y - rint(y)
+ *   pos = r_i + sum_m Re[(C[c,m] E) W[m, b_i, :]]      in float64, summed in mode order, not wrapped and not clipped
+ * msl_set_modes:  requires msl_set_structure (whose sigma the mode builds ignore); uploads ONCE basis_index (n_atoms int32 in
+ *   [0, n_basis)), q (n_modes x 3 doubles), tau (n_modes doubles, finite and >= 0), W (n_modes x n_basis x 3 complex doubles, re/im
+ *   interleaved) and the frame rule; they stay resident until the next msl_set_modes, msl_set_structure (which drops them) or
+ *   msl_destroy.  n_atoms is the length of basis_index and must be the structure's atom count.  MSL_ERR_INVALID names what was
+ *   wrong: a bad index, a non-finite value, a negative tau, n_modes < 1, n_basis < 1, an atom count that disagrees with the
+ *   structure.  A refused call leaves the resident modes as they were.  Synchronous: no pointer into caller memory is kept.
+ * msl_build_modes:  the mirror of msl_build_thermal -- the potentials and transmission functions of the frames first_frame ..
+ *   first_frame + count - 1 (1 <= count <= frame_batch, first_frame >= 0; first_frame + count <= 2^31 when dynamic) into the same
+ *   batch slots, by the same sequence of launches with the position stage exchanged: mode_coefficients_kernel fills the (count, M)
+ *   table C, mode_positions_kernel writes the positions where msl_build_potentials copies them to.  Bit for bit
+ *   msl_build_potentials given msl_mode_positions' arrays.  MSL_ERR_INVALID without msl_set_modes.  Queued on the stream.
+ * msl_mode_positions: the positions the device generates for one frame, n_atoms x 3 doubles, downloaded (waits for the stream).
+ * Not built: Einstein widths on top of the modes, anharmonic or damped modes, occupations that change over time, fp32 or
+ * table-driven phases.  Not in the reference. */
+int  msl_set_modes(msl_handle* h, const int32_t* basis_index, int64_t n_atoms, int32_t n_basis, const double* q, const double* tau,
+                   const double* W, int32_t n_modes, int32_t dynamic);
+int  msl_build_modes(msl_handle* h, uint64_t seed, int64_t first_frame, int32_t count);
+int  msl_mode_positions(msl_handle* h, uint64_t seed, int64_t frame, double* out);
 
 /* TACAW: intensity[p,w,kx,ky] = | fftshift_t fft_t( Psi - <Psi>_t ) |^2 over a (B,T,npix) c64 device
  * array.  src == NULL uses the handle's own wavefunction buffer (B=P, T=T_local, npix=nx*ny) and

@@ -6,6 +6,7 @@ library `libmslice.so` (include/mslice.h, pyslice_amd/csrc).  There is no CPU fa
 """
 from .trajectory import Trajectory
 from .thermal import FrozenPhonons, sigma_from_B
+from .phonons import PhononModes
 from .wf_data import WFData
 from .potentials import Potential, gridFromTrajectory, getZfromElementName, loadKirkland
 from .multislice import Probe, Propagate, create_batched_probes, probe_grid, wavelength, m_effective
@@ -20,7 +21,7 @@ from .image_data import ImageData
 from .spectroscopy import Spectroscopy
 from .spectrum_image_data import SpectrumImageData
 
-__all__ = ["Trajectory", "FrozenPhonons", "sigma_from_B", "WFData", "Potential", "gridFromTrajectory", "getZfromElementName", "loadKirkland",
+__all__ = ["Trajectory", "FrozenPhonons", "sigma_from_B", "PhononModes", "WFData", "Potential", "gridFromTrajectory", "getZfromElementName", "loadKirkland",
            "Probe", "Propagate", "create_batched_probes", "probe_grid", "wavelength", "m_effective",
            "MultisliceCalculator", "TACAWData", "HAADFData", "Detector", "STEMData", "Diffraction", "DiffractionData",
            "Aberrations", "scherzer_defocus", "Imaging", "ImageData", "Spectroscopy", "SpectrumImageData"]

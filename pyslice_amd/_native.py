@@ -36,6 +36,7 @@ EXPORTS = [
     "msl_smatrix_begin", "msl_smatrix_beams", "msl_smatrix_build", "msl_smatrix_probes", "msl_smatrix_end",
     "msl_tacaw_welch_has", "msl_tacaw_welch", "msl_tacaw_welch_layer",
     "msl_set_structure", "msl_build_thermal", "msl_thermal_positions",
+    "msl_set_modes", "msl_build_modes", "msl_mode_positions",
 ]
 DET_SIGNALS = {"intensity": 0, "amplitude": 1, "com_x": 2, "com_y": 3}      # include/mslice.h: MSL_DET_*
 
@@ -141,6 +142,9 @@ def load():
         "msl_set_structure": (C.c_int, [vp, vp, vp, vp, i64, i32, i32, i32]),
         "msl_build_thermal": (C.c_int, [vp, C.c_uint64, i64, i32]),
         "msl_thermal_positions": (C.c_int, [vp, C.c_uint64, i64, vp]),
+        "msl_set_modes": (C.c_int, [vp, vp, i64, i32, vp, vp, vp, i32, i32]),
+        "msl_build_modes": (C.c_int, [vp, C.c_uint64, i64, i32]),
+        "msl_mode_positions": (C.c_int, [vp, C.c_uint64, i64, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -339,6 +343,38 @@ class Engine:
         n = getattr(self, "_structure_atoms", None)
         out = np.empty((n or 0, 3), dtype=np.float64)
         self._chk(self._lib.msl_thermal_positions(self._h, int(seed), int(config), _ptr(out) if out.size else None))
+        return out
+
+    # -- phonon modes (msl_set_modes / msl_build_modes / msl_mode_positions; the definition is phonons.py)
+    def set_modes(self, basis_index, wavevectors, tau, displacements, dynamic=True):
+        """the modes that move the resident structure (set_structure first; its sigma is not used by the mode builds): basis_index
+        (n_atoms,), wavevectors (M, 3) in cycles / Angstrom, tau (M,) in cycles per frame, displacements (M, n_basis, 3) complex in
+        Angstrom; dynamic: a time-coherent record, else independent snapshots"""
+        W = np.ascontiguousarray(displacements, dtype=np.complex128)
+        if W.ndim != 3 or W.shape[2] != 3:
+            raise ValueError(f"displacements must be (n_modes,n_basis,3), got {W.shape}")
+        b = np.ascontiguousarray(basis_index, dtype=np.int32)
+        q = np.ascontiguousarray(wavevectors, dtype=np.float64)
+        t = np.ascontiguousarray(tau, dtype=np.float64)
+        if b.ndim != 1:
+            raise ValueError(f"basis_index must be (n_atoms,), got {b.shape}")
+        if q.shape != (W.shape[0], 3):
+            raise ValueError(f"wavevectors must be ({W.shape[0]},3), got {q.shape}")
+        if t.shape != (W.shape[0],):
+            raise ValueError(f"tau must be ({W.shape[0]},), got {t.shape}")
+        self._chk(self._lib.msl_set_modes(self._h, _ptr(b) if b.size else None, b.shape[0], W.shape[1], _ptr(q) if q.size else None,
+                                          _ptr(t) if t.size else None, _ptr(W) if W.size else None, W.shape[0], int(bool(dynamic))))
+
+    def build_modes(self, seed, first_frame, count=1):
+        """potentials of the frames first_frame .. first_frame+count-1 of the modes (count <= frame_batch) into the batch slots
+        0..count-1 (the selected slot at a frame batch of 1), their positions synthesised on the device"""
+        self._chk(self._lib.msl_build_modes(self._h, int(seed), int(first_frame), int(count)))
+
+    def mode_positions(self, seed, frame):
+        """(n_atoms, 3) float64: the positions the device synthesises for one frame"""
+        n = getattr(self, "_structure_atoms", None)
+        out = np.empty((n or 0, 3), dtype=np.float64)
+        self._chk(self._lib.msl_mode_positions(self._h, int(seed), int(frame), _ptr(out) if out.size else None))
         return out
 
     def upload_potential(self, V_nz_nx_ny):

@@ -28,6 +28,7 @@ from .prism import Prism, beams as prism_beams
 from .potentials import (TORCH_AVAILABLE, _as_tensor, _device_index, atomic_numbers_of, gridFromTrajectory, loadKirkland, slice_edges,
                          suggest_sampling)
 from .thermal import FrozenPhonons
+from .phonons import PhononModes
 from .trajectory import Trajectory
 from .wf_data import WFData
 
@@ -323,13 +324,19 @@ class MultisliceCalculator:
         (not in the reference) `trajectory` may be a thermal.FrozenPhonons: its n_configs Einstein-model configurations take the
         place of the MD frames in every run mode, generated on the device from the resident base structure (msl_set_structure
         once, msl_build_thermal per frame batch) instead of being copied from a (T, n_atoms, 3) host array.  Not built with it:
-        cache=True, stream_tile / run_streaming_tacaw(), several ranks (NotImplementedError)."""
-        self._thermal = trajectory if isinstance(trajectory, FrozenPhonons) else None
-        if self._thermal is not None:
+        cache=True, stream_tile / run_streaming_tacaw(), several ranks (NotImplementedError).
+
+        It may also be a phonons.PhononModes: its n_frames frames, synthesised on the device from a set of phonon modes
+        (msl_set_structure and msl_set_modes once, msl_build_modes per frame batch) -- a time-coherent record whose TACAW spectrum
+        shows the dispersion, or independent correlated snapshots.  The same run modes, the same three refusals."""
+        # a generated source: frames made on the device by index from a resident structure, never read from a host array
+        self._generated = trajectory if isinstance(trajectory, (FrozenPhonons, PhononModes)) else None
+        if self._generated is not None:
+            kind = "phonon modes" if isinstance(trajectory, PhononModes) else "frozen phonons"
             for what, val in (("cache=True", self._cache), ("stream_tile / run_streaming_tacaw()", self._stream_tile is not None),
                               ("a run over several ranks", distributed.rank_world()[1] > 1)):
                 if val:
-                    raise NotImplementedError(f"frozen phonons: {what} is not built")
+                    raise NotImplementedError(f"{kind}: {what} is not built")
         self.trajectory = trajectory
         self.aperture = aperture
         self.voltage_eV = voltage_eV
@@ -519,7 +526,7 @@ class MultisliceCalculator:
         # slice coordinates follow the slice axis (potentials.py:241-245); the Fresnel step uses zs (multislice.py:266)
         self._slice_coords = np.asarray([self.xs, self.ys, self.zs][slice_axis], dtype=np.float64)
         self._dz = self.zs[1] - self.zs[0] if self.nz > 1 else 0.5
-        self._Z = (atomic_numbers_of(trajectory.atom_types) if self._thermal is not None
+        self._Z = (atomic_numbers_of(trajectory.atom_types) if self._generated is not None
                    else np.asarray(trajectory.atom_types, dtype=np.int32))
         # A previous run's WFData (and zero-copy device views of its buffers) may still hold the old engine: drop our
         # reference and let the last owner free it, instead of closing it under them.  (A caller that keeps an earlier result
@@ -612,15 +619,21 @@ class MultisliceCalculator:
         eng.set_kirkland(loadKirkland())
         eng.set_slices(*slice_edges(self._slice_coords))
         eng.set_aberrations(self._aberrations)
-        if self._thermal is not None:                           # the base structure, once: every build is a generation by index
-            eng.set_structure(self._thermal.positions, self._Z, self._thermal.sigma, self.slice_axis)
+        src = self._generated
+        if src is not None:                                     # the base structure, once: every build is a generation by index
+            modes = isinstance(src, PhononModes)                # (the mode builds do not read the widths)
+            eng.set_structure(src.positions, self._Z, np.zeros(src.n_atoms) if modes else src.sigma, self.slice_axis)
+            if modes:
+                eng.set_modes(src.basis_index, src.wavevectors, src.tau, src.displacements, src.dynamic)
 
     def _build(self, first_frame, n):
         """The potentials of the frames first_frame .. first_frame+n-1 into the batch slots (the engine's singular call at a frame
-        batch of 1): MD frames from the trajectory's host array, frozen-phonon configurations generated on the device by index."""
+        batch of 1): MD frames from the trajectory's host array, frozen-phonon configurations and phonon-mode frames generated on
+        the device by index."""
         eng = self._engine
-        if self._thermal is not None:
-            eng.build_thermal(self._thermal.seed, first_frame, n)
+        src = self._generated
+        if src is not None:
+            (eng.build_modes if isinstance(src, PhononModes) else eng.build_thermal)(src.seed, first_frame, n)
         elif eng.frame_batch > 1:
             eng.build_potentials(self.trajectory.positions[first_frame:first_frame + n], self._Z, self.slice_axis)
         else:

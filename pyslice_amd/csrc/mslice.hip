@@ -18,6 +18,7 @@
 #include "rowtm_pass.h"
 #include "potential.h"
 #include "thermal.h"
+#include "phonons.h"
 #include "reduce.h"
 #include "stream.h"
 #include "tacaw_time.h"
@@ -224,6 +225,13 @@ struct msl_handle {
     int64_t th_n = 0;
     int32_t th_ax1 = 0, th_ax2 = 1, th_axs = 2;
     bool have_structure = false;
+    // phonon modes (msl_set_modes) on top of the resident structure: the basis atom of every atom, q (M, 3), tau (M), W (M, nb, 3)
+    // complex, and the coefficient table C (frame_batch, M) that mode_coefficients_kernel fills for every build
+    DevBuf<int> md_basis;
+    DevBuf<double> md_q, md_tau, md_W;
+    DevBuf<double2> md_C;
+    int md_M = 0, md_nb = 0;
+    bool md_dynamic = true, have_modes = false;
     DevBuf<double> d_xy;
     // probe aberrations (msl_set_aberrations): (magnitude, angle) of the fourteen terms; read by every msl_set_probes
     double aberr_polar[14][2] = {};
@@ -1461,6 +1469,13 @@ struct PotGroup {
     float2* TR; float2* TRT;        // batch slots this group's stacks go to (trans, transT)
 };
 
+// Forget the phonon modes and return their device memory (the stream is idle: the callers have synchronised)
+void drop_modes(msl_handle* h) {
+    h->have_modes = false;
+    h->md_basis.release(); h->md_q.release(); h->md_tau.release(); h->md_W.release(); h->md_C.release();
+    h->md_M = h->md_nb = 0;
+}
+
 int map_species(msl_handle* h, const int32_t* Z, int64_t n, PotGroup& m) {
     for (int i = 0; i < 104; ++i) m.z2s[i] = -1;
     for (int64_t a = 0; a < n; ++a) {
@@ -1504,22 +1519,60 @@ int stage_atoms(msl_handle* h, const PotGroup& p, const double* pos, const int32
     return MSL_OK;
 }
 
-// The frozen-phonon source of build_potentials: configurations first_config .. of the handle's resident structure
-struct ThermalSource { uint64_t seed; uint64_t first_config; };
+// The generated source of build_potentials: frames first .. of the handle's resident structure, Einstein-model configurations
+// (msl_build_thermal) or, with `modes`, frames synthesised from the resident phonon modes (msl_build_modes)
+struct GeneratedSource { bool modes; uint64_t seed; uint64_t first; };
+
+// What stage_atoms sends with the first group of a call, for a generated source: the resident species maps and Z, device to device
+int stage_resident_maps(msl_handle* h, const PotGroup& p) {
+    HIPCHK(h, hipMemcpyAsync(h->d_z2s, h->th_z2s, sizeof p.z2s, hipMemcpyDeviceToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->d_species, h->th_species, p.nsp * sizeof(int), hipMemcpyDeviceToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->d_Z, h->th_Z, (size_t)p.n * sizeof(int), hipMemcpyDeviceToDevice, h->stream));
+    return MSL_OK;
+}
 
 // stage_atoms for a group of configurations: the positions are generated into d_pos on the device (thermal_positions_kernel, one
 // thread per configuration and atom); with the first group of a call the resident species maps and Z are copied, device to device,
 // to where stage_atoms puts them.  No pinned staging, no host copy.
 int stage_thermal(msl_handle* h, const PotGroup& p, uint64_t seed, uint64_t first_config, bool send_maps) {
-    if (send_maps) {
-        HIPCHK(h, hipMemcpyAsync(h->d_z2s, h->th_z2s, sizeof p.z2s, hipMemcpyDeviceToDevice, h->stream));
-        HIPCHK(h, hipMemcpyAsync(h->d_species, h->th_species, p.nsp * sizeof(int), hipMemcpyDeviceToDevice, h->stream));
-        HIPCHK(h, hipMemcpyAsync(h->d_Z, h->th_Z, (size_t)p.n * sizeof(int), hipMemcpyDeviceToDevice, h->stream));
-    }
+    int rc;
+    if (send_maps && (rc = stage_resident_maps(h, p))) return rc;
     hipLaunchKernelGGL(thermal_positions_kernel, dim3((unsigned)((p.rows + 255) / 256)), dim3(256), 0, h->stream, h->th_pos0, h->th_sigma,
                        (long long)p.n, p.g, (unsigned long long)seed, (unsigned long long)first_config, h->d_pos);
     HIPCHK(h, hipGetLastError());
     return MSL_OK;
+}
+
+// The frames first_frame .. first_frame + count - 1 of the resident modes into `pos` (count, n, 3): the coefficient table C
+// (mode_coefficients_kernel, count x M threads), then one thread per atom and tile of 8 frames -- of 2 for a group of one or two
+// frames -- (mode_positions_kernel).
+// count <= frame_batch rows of md_C; n >= 1.  Queued on the stream: C is rewritten by the next call behind this one's readers.
+int launch_mode_positions(msl_handle* h, long long n, int count, uint64_t seed, uint64_t first_frame, double* pos) {
+    const int M = h->md_M, nb = h->md_nb;
+    hipLaunchKernelGGL(mode_coefficients_kernel, dim3((unsigned)(((long long)M * count + 255) / 256)), dim3(256), 0, h->stream, h->md_tau, M,
+                       count, (unsigned long long)seed, (unsigned long long)first_frame, h->md_dynamic ? 1 : 0, h->md_C);
+    HIPCHK(h, hipGetLastError());
+    auto launch = [&](auto kernel, int tile) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)((n + 255) / 256), (unsigned)((count + tile - 1) / tile)), dim3(256),
+                           mode_positions_lds_bytes(nb, tile), h->stream, h->th_pos0, h->md_basis, h->md_q, h->md_C, h->md_W, n, nb, M, count, pos);
+    };
+    const bool lds = nb <= MODE_LDS_BASIS;
+    if (count <= MODE_TILE_SMALL) {
+        if (lds) launch(mode_positions_kernel<true, MODE_TILE_SMALL>, MODE_TILE_SMALL);
+        else launch(mode_positions_kernel<false, MODE_TILE_SMALL>, MODE_TILE_SMALL);
+    } else {
+        if (lds) launch(mode_positions_kernel<true, MODE_TILE>, MODE_TILE);
+        else launch(mode_positions_kernel<false, MODE_TILE>, MODE_TILE);
+    }
+    HIPCHK(h, hipGetLastError());
+    return MSL_OK;
+}
+
+// stage_thermal for a group of phonon-mode frames
+int stage_modes(msl_handle* h, const PotGroup& p, uint64_t seed, uint64_t first_frame, bool send_maps) {
+    int rc;
+    if (send_maps && (rc = stage_resident_maps(h, p))) return rc;
+    return launch_mode_positions(h, p.n, p.g, seed, first_frame, h->d_pos);
 }
 
 // Atoms of a group -> phase tables in sorted order: slice bins (atom_prep_kernel), stable counting sort with keys = frame x slice x
@@ -1726,10 +1779,11 @@ int potential_ifft(msl_handle* h, const PotGroup& p) {
 // phase tables of a group may take (6 GB), instead of that sequence per frame.  The reference builds one Potential per frame
 // (calculators.py:172-186, potentials.py:188-348); with its default single probe that build IS the frame (round 2: 0.43 of
 // 0.62 ms at 512^2 x 100 slices, of which ~110 us were launches of 5-15 us kernels and four small copies per frame).
-// With `th` the frames are configurations of the resident structure (msl_build_thermal): pos and Z are not read, the species maps are
-// the ones msl_set_structure made, and stage_thermal takes the place of stage_atoms; everything behind d_pos is the same.
+// With `th` the frames are generated from the resident structure (msl_build_thermal, msl_build_modes): pos and Z are not read, the
+// species maps are the ones msl_set_structure made, and stage_thermal or stage_modes takes the place of stage_atoms; everything
+// behind d_pos is the same.
 int build_potentials(msl_handle* h, const double* pos, const int32_t* Z, int64_t n, int count, int first_slot, int32_t ax1, int32_t ax2, int32_t axs,
-                     const ThermalSource* th = nullptr) {
+                     const GeneratedSource* th = nullptr) {
     const msl_config& c = h->cfg;
     const size_t npix = (size_t)c.nx * c.ny;
     PotGroup p{};
@@ -1771,8 +1825,9 @@ int build_potentials(msl_handle* h, const double* pos, const int32_t* Z, int64_t
         p.n_slices = c.nz * p.g; p.nkeys = p.keys_per_frame * p.g;
         p.rows = (long long)n * p.g; p.rows_pad = p.rows + (long long)(SF_ALIGN - 1) * p.nkeys;
         if (n > 0 && p.nsp > 0) {
-            rc = th ? stage_thermal(h, p, th->seed, th->first_config + (uint64_t)f0, f0 == 0)
-                    : stage_atoms(h, p, pos + (size_t)f0 * n * 3, Z, f0 == 0);
+            rc = !th ? stage_atoms(h, p, pos + (size_t)f0 * n * 3, Z, f0 == 0)
+                 : th->modes ? stage_modes(h, p, th->seed, th->first + (uint64_t)f0, f0 == 0)
+                             : stage_thermal(h, p, th->seed, th->first + (uint64_t)f0, f0 == 0);
             if (rc || (rc = bin_atoms(h, p)) || (rc = launch_structure_factor(h, p))) return rc;
         } else {
             HIPCHK(h, hipMemsetAsync(p.TR, 0, npix * p.n_slices * sizeof(float2), h->stream));
@@ -2348,6 +2403,7 @@ int msl_set_structure(msl_handle* h, const double* pos0, const int32_t* Z, const
     HIPCHK(h, hipSetDevice(h->cfg.device));
     HIPCHK(h, hipStreamSynchronize(h->stream));          // a build queued from the previous structure still reads its buffers
     h->have_structure = false;
+    drop_modes(h);                                       // they belong to the atoms of the structure they were set on
     int rc;
     if ((rc = h->th_pos0.alloc(h, (size_t)n * 3)) || (rc = h->th_sigma.alloc(h, (size_t)n)) || (rc = h->th_Z.alloc(h, (size_t)n)) ||
         (rc = h->th_z2s.alloc(h, (size_t)104)) || (rc = h->th_species.alloc(h, (size_t)104))) return rc;
@@ -2365,22 +2421,30 @@ int msl_set_structure(msl_handle* h, const double* pos0, const int32_t* Z, const
     return MSL_OK;
 }
 
-int msl_build_thermal(msl_handle* h, uint64_t seed, int64_t first_config, int32_t count) {
-    if (!h) return fail(h, MSL_ERR_INVALID, "msl_build_thermal: null handle");
-    if (!h->have_structure) return fail(h, MSL_ERR_INVALID, "msl_build_thermal: no structure (call msl_set_structure first)");
-    if (!h->have_kirkland) return fail(h, MSL_ERR_STATE, "msl_build_thermal: call msl_set_kirkland first");
-    if (!h->have_slices) return fail(h, MSL_ERR_STATE, "msl_build_thermal: call msl_set_slices first");
-    if (count < 1 || count > h->FB) return fail(h, MSL_ERR_INVALID, "msl_build_thermal: count %d outside [1,%d] (msl_config.frame_batch)", count, h->FB);
-    if (first_config < 0 || first_config > INT64_MAX - count)
-        return fail(h, MSL_ERR_INVALID, "msl_build_thermal: configurations %lld .. outside [0, 2^63)", (long long)first_config);
-    if (h->th_n * count > 0x7fffffffLL) return fail(h, MSL_ERR_INVALID, "msl_build_thermal: more than 2^31 atoms in one batch");
+// msl_build_thermal / msl_build_modes: the state and count checks, then build_potentials on the generated source
+static int build_generated(msl_handle* h, const char* who, bool modes, uint64_t seed, int64_t first, int32_t count) {
+    if (!h) return fail(h, MSL_ERR_INVALID, "%s: null handle", who);
+    if (!h->have_structure) return fail(h, MSL_ERR_INVALID, "%s: no structure (call msl_set_structure first)", who);
+    if (modes && !h->have_modes) return fail(h, MSL_ERR_INVALID, "%s: no modes (call msl_set_modes first)", who);
+    if (!h->have_kirkland) return fail(h, MSL_ERR_STATE, "%s: call msl_set_kirkland first", who);
+    if (!h->have_slices) return fail(h, MSL_ERR_STATE, "%s: call msl_set_slices first", who);
+    if (count < 1 || count > h->FB) return fail(h, MSL_ERR_INVALID, "%s: count %d outside [1,%d] (msl_config.frame_batch)", who, count, h->FB);
+    if (first < 0 || first > INT64_MAX - count)
+        return fail(h, MSL_ERR_INVALID, "%s: %s %lld .. outside [0, 2^63)", who, modes ? "frames" : "configurations", (long long)first);
+    if (modes && h->md_dynamic && first + count > (1LL << 31))
+        return fail(h, MSL_ERR_INVALID, "%s: frames %lld .. %lld of a dynamic record outside [0, 2^31)", who, (long long)first, (long long)(first + count - 1));
+    if (h->th_n * count > 0x7fffffffLL) return fail(h, MSL_ERR_INVALID, "%s: more than 2^31 atoms in one batch", who);
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    const ThermalSource th{seed, (uint64_t)first_config};
+    const GeneratedSource src{modes, seed, (uint64_t)first};
     // a frame batch of 1: the selected slot, as msl_build_potential; else the slots 0 .. count-1, as msl_build_potentials
     const int first_slot = h->FB > 1 ? 0 : h->cur_batch;
-    int rc = build_potentials(h, nullptr, nullptr, h->th_n, count, first_slot, h->th_ax1, h->th_ax2, h->th_axs, &th);
+    int rc = build_potentials(h, nullptr, nullptr, h->th_n, count, first_slot, h->th_ax1, h->th_ax2, h->th_axs, &src);
     if (rc == MSL_OK && h->FB > 1) h->cur_batch = count - 1;
     return rc;
+}
+
+int msl_build_thermal(msl_handle* h, uint64_t seed, int64_t first_config, int32_t count) {
+    return build_generated(h, "msl_build_thermal", false, seed, first_config, count);
 }
 
 int msl_thermal_positions(msl_handle* h, uint64_t seed, int64_t config, double* out) {
@@ -2401,6 +2465,72 @@ int msl_thermal_positions(msl_handle* h, uint64_t seed, int64_t config, double* 
     const hipError_t es = hipStreamSynchronize(h->stream);      // on every path: nothing queued reads tmp when it is freed below
     if (e == hipSuccess) e = es;
     if (e != hipSuccess) return fail(h, MSL_ERR_HIP, "msl_thermal_positions failed: %s", hipGetErrorString(e));
+    return MSL_OK;
+}
+
+// ---- phonon modes ------------------------------------------------------------
+int msl_set_modes(msl_handle* h, const int32_t* basis_index, int64_t n_atoms, int32_t n_basis, const double* q, const double* tau,
+                  const double* W, int32_t n_modes, int32_t dynamic) {
+    if (!h) return fail(h, MSL_ERR_INVALID, "msl_set_modes: null handle");
+    if (!h->have_structure) return fail(h, MSL_ERR_INVALID, "msl_set_modes: no structure (call msl_set_structure first)");
+    if (n_atoms != h->th_n)
+        return fail(h, MSL_ERR_INVALID, "msl_set_modes: %lld atoms, the structure has %lld", (long long)n_atoms, (long long)h->th_n);
+    if (n_modes < 1) return fail(h, MSL_ERR_INVALID, "msl_set_modes: n_modes %d is below 1", n_modes);
+    if (n_basis < 1) return fail(h, MSL_ERR_INVALID, "msl_set_modes: n_basis %d is below 1", n_basis);
+    if (!q || !tau || !W || (n_atoms > 0 && !basis_index)) return fail(h, MSL_ERR_INVALID, "msl_set_modes: null argument");
+    const size_t M = (size_t)n_modes, nW = M * (size_t)n_basis * 6;
+    if ((long long)n_modes * h->FB > 0x7fffffffLL) return fail(h, MSL_ERR_INVALID, "msl_set_modes: n_modes x frame_batch exceeds 2^31");
+    if (nW > (size_t)1 << 40) return fail(h, MSL_ERR_INVALID, "msl_set_modes: n_modes x n_basis is too large");
+    for (int64_t a = 0; a < n_atoms; ++a)
+        if (basis_index[a] < 0 || basis_index[a] >= n_basis)
+            return fail(h, MSL_ERR_INVALID, "msl_set_modes: basis index %d of atom %lld outside [0,%d)", basis_index[a], (long long)a, n_basis);
+    for (size_t m = 0; m < M; ++m) {
+        if (!std::isfinite(tau[m]) || !(tau[m] >= 0.0))
+            return fail(h, MSL_ERR_INVALID, "msl_set_modes: tau %g of mode %zu is not a finite number >= 0", tau[m], m);
+        if (!std::isfinite(q[m * 3]) || !std::isfinite(q[m * 3 + 1]) || !std::isfinite(q[m * 3 + 2]))
+            return fail(h, MSL_ERR_INVALID, "msl_set_modes: wave vector of mode %zu is not finite", m);
+    }
+    for (size_t k = 0; k < nW; ++k)
+        if (!std::isfinite(W[k])) return fail(h, MSL_ERR_INVALID, "msl_set_modes: displacement vector of mode %zu is not finite", k / ((size_t)n_basis * 6));
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));          // a build queued from the previous modes still reads their buffers
+    drop_modes(h);
+    int rc;
+    if ((rc = h->md_basis.alloc(h, (size_t)n_atoms)) || (rc = h->md_q.alloc(h, M * 3)) || (rc = h->md_tau.alloc(h, M)) ||
+        (rc = h->md_W.alloc(h, nW)) || (rc = h->md_C.alloc(h, M * (size_t)std::max(1, h->FB)))) { drop_modes(h); return rc; }
+    if (n_atoms > 0) HIPCHK(h, hipMemcpy(h->md_basis, basis_index, (size_t)n_atoms * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(h->md_q, q, M * 3 * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(h->md_tau, tau, M * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(h->md_W, W, nW * sizeof(double), hipMemcpyHostToDevice));
+    h->md_M = n_modes; h->md_nb = n_basis; h->md_dynamic = dynamic != 0;
+    h->have_modes = true;
+    return MSL_OK;
+}
+
+int msl_build_modes(msl_handle* h, uint64_t seed, int64_t first_frame, int32_t count) {
+    return build_generated(h, "msl_build_modes", true, seed, first_frame, count);
+}
+
+int msl_mode_positions(msl_handle* h, uint64_t seed, int64_t frame, double* out) {
+    if (!h) return fail(h, MSL_ERR_INVALID, "msl_mode_positions: null handle");
+    if (!h->have_structure) return fail(h, MSL_ERR_INVALID, "msl_mode_positions: no structure (call msl_set_structure first)");
+    if (!h->have_modes) return fail(h, MSL_ERR_INVALID, "msl_mode_positions: no modes (call msl_set_modes first)");
+    if (frame < 0 || (h->md_dynamic && frame >= (1LL << 31)))
+        return fail(h, MSL_ERR_INVALID, "msl_mode_positions: frame %lld outside [0, %s)", (long long)frame, h->md_dynamic ? "2^31" : "2^63");
+    const int64_t n = h->th_n;
+    if (n == 0) return MSL_OK;
+    if (!out) return fail(h, MSL_ERR_INVALID, "msl_mode_positions: null argument");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    DevBuf<double> tmp;                                   // (not d_pos: a queued build may still read it)
+    int rc = tmp.alloc(h, (size_t)n * 3);
+    if (rc) return rc;
+    rc = launch_mode_positions(h, n, 1, seed, (uint64_t)frame, tmp.p);
+    hipError_t e = hipSuccess;
+    if (rc == MSL_OK) e = hipMemcpyAsync(out, tmp, (size_t)n * 3 * sizeof(double), hipMemcpyDeviceToHost, h->stream);
+    const hipError_t es = hipStreamSynchronize(h->stream);      // on every path: nothing queued reads tmp when it is freed below
+    if (rc) return rc;
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) return fail(h, MSL_ERR_HIP, "msl_mode_positions failed: %s", hipGetErrorString(e));
     return MSL_OK;
 }
 

@@ -16,7 +16,7 @@ slice rule of the potential treats a configuration exactly as it treats a trajec
 along the slice axis is dropped (leave a few sigma of vacuum at the entrance and exit surfaces) and the in-plane axes are periodic
 anyway.
 
-Not built: anisotropic or per-axis widths, correlated (phonon-mode) displacements, wrapping at the surfaces.
+Not built: anisotropic or per-axis widths, wrapping at the surfaces.  Correlated (phonon-mode) displacements are phonons.PhononModes.
 """
 from __future__ import annotations
 
