@@ -359,6 +359,30 @@ int  msl_adf(msl_handle* h, const void* d_src_c64, int64_t B, int64_t T, int64_t
 int  msl_set_detectors(msl_handle* h, int32_t n, const uint16_t* member_K, const int32_t* signal_n, const float* kx_wx, const float* ky_wy);
 int  msl_detect(msl_handle* h, const void* d_src_c64, int64_t B, int64_t T, int64_t K, int64_t ld, int32_t t0, int32_t count, double* out);
 
+/* ---- polar detector: every exit spectrum summed into radial rings x azimuthal sectors, per probe batch ----
+ * A bin map gives every stored pixel (K = wx*wy of the stored spectrum) a bin id below n_bins, or MSL_POLAR_NONE for a pixel in no bin;
+ * the caller forms it (pyslice_amd/polar_data.py: polar_bins, bin = ring * sectors + sector).  Any annular, segmented or DPC detector
+ * is then a sum of bins chosen after the run, where msl_detect needs its at most 16 regions before it.
+ * msl_polar_layout: host only, no handle and no device.  Stable counting sort of the K pixels by bin: order_K (room for K entries) lists
+ *   the pixel indices of bin 0 ascending, then bin 1, ...; pixels with MSL_POLAR_NONE are left out.  seg_n1 has n_bins + 1 entries:
+ *   seg[b] .. seg[b+1] is the slice of order for bin b, seg[n_bins] the number of pixels in any bin.  MSL_ERR_INVALID for a null argument,
+ *   K < 0, n_bins outside [1, MSL_POLAR_MAX_BINS] or a bin id >= n_bins other than MSL_POLAR_NONE.
+ * msl_set_polar: bin_K = K host uint16 over the handle's stored pixels; runs the layout and uploads order and seg (4 * K + 8 * (n_bins + 1)
+ *   bytes on the device).  Same errors; a failed call leaves no map set.
+ * msl_polar_detect: out[(b*count + j)*n_bins + i] = sum over the pixels k of bin i of |Psi[b, t0+j, k]|^2 over a (B,T,K) complex64 array with
+ *   row pitch ld.  Source arguments as msl_detect: d_src == NULL is the handle's wavefunction buffer (T = n_frames, K = stored pixels,
+ *   ld = msl_result_pitch; B <= 0 means n_probes, a smaller B leaves the padded probes out).  out is HOST memory, B*count*n_bins float64;
+ *   the device stages it in 8 * B*count*n_bins bytes of scratch.  MSL_ERR_STATE before msl_set_polar; MSL_ERR_INVALID when K is not the K
+ *   of the map, ld < K, count < 1 or [t0, t0+count) leaves [0, T).  One launch, a bin-sorted gather: one wave per bin and block of rows,
+ *   fp32 |Psi|^2 added in float64 in the order of the layout, a fixed xor tree over the wave; the pad pixels [K, ld) are never read; an
+ *   empty bin gives exactly 0; no atomics (bitwise reproducible).
+ *   Not in the reference, which holds every frame: there the same numbers are masked sums of |wavefunction_data|^2. */
+#define MSL_POLAR_NONE 0xFFFF
+#define MSL_POLAR_MAX_BINS 4096
+int  msl_polar_layout(const uint16_t* bin_K, int64_t K, int32_t n_bins, uint32_t* order_K, int64_t* seg_n1);
+int  msl_set_polar(msl_handle* h, int32_t n_bins, const uint16_t* bin_K);
+int  msl_polar_detect(msl_handle* h, const void* d_src_c64, int64_t B, int64_t T, int64_t K, int64_t ld, int32_t t0, int32_t count, double* out);
+
 /* ---- spectrum detectors: energy-resolved detector signals of a TACAW intensity, per probe batch ----
  * msl_spectrum_detect: out[(b*count + j)*n + d] = sum_k w_d(k) I[b, f0+j, k] over a (B,F,K) float32 intensity with row pitch ld (0: K),
  *   w_d the memberships of the n detectors of the last msl_set_detectors: every detector in ONE pass over the intensity, where

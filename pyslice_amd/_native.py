@@ -31,6 +31,7 @@ EXPORTS = [
     "msl_tacaw_stream_set_reference", "msl_tacaw_stream_finish_range",
     "msl_set_layers", "msl_download_layers_c128", "msl_tacaw_layer",
     "msl_set_detectors", "msl_detect", "msl_spectrum_detect", "msl_diffract",
+    "msl_polar_layout", "msl_set_polar", "msl_polar_detect",
     "msl_coherent_reset", "msl_coherent_add", "msl_coherent_finish",
     "msl_image_reset", "msl_image_add", "msl_image_download",
     "msl_smatrix_begin", "msl_smatrix_beams", "msl_smatrix_build", "msl_smatrix_probes", "msl_smatrix_end",
@@ -39,6 +40,7 @@ EXPORTS = [
     "msl_set_modes", "msl_build_modes", "msl_mode_positions",
 ]
 DET_SIGNALS = {"intensity": 0, "amplitude": 1, "com_x": 2, "com_y": 3}      # include/mslice.h: MSL_DET_*
+POLAR_NONE, POLAR_MAX_BINS = 0xFFFF, 4096                                  # include/mslice.h: MSL_POLAR_*
 
 
 class MslConfig(C.Structure):
@@ -124,6 +126,9 @@ def load():
         "msl_set_detectors": (C.c_int, [vp, i32, vp, vp, vp, vp]),
         "msl_detect": (C.c_int, [vp, vp, i64, i64, i64, i64, i32, i32, vp]),
         "msl_spectrum_detect": (C.c_int, [vp, vp, i64, i64, i64, i64, i32, i32, vp]),
+        "msl_polar_layout": (C.c_int, [vp, i64, i32, vp, vp]),
+        "msl_set_polar": (C.c_int, [vp, i32, vp]),
+        "msl_polar_detect": (C.c_int, [vp, vp, i64, i64, i64, i64, i32, i32, vp]),
         "msl_diffract": (C.c_int, [vp, vp, i64, i64, i64, i64, i32, i32, i32, i32, i32, i32, vp]),
         "msl_coherent_reset": (C.c_int, [vp, i64]),
         "msl_coherent_add": (C.c_int, [vp, vp, i64, i64, i64, i64, i32, i32]),
@@ -170,6 +175,18 @@ def fast_lengths(lo: int = 129, hi: int = 2048):
 def welch_has(L: int) -> bool:
     """is there a device kernel for Welch segment length L (msl_tacaw_welch_has)"""
     return bool(load().msl_tacaw_welch_has(int(L)))
+
+
+def polar_layout(bins, n_bins):
+    """(order, seg) of a bin map (msl_polar_layout; host only, no device): order = the indices of the pixels in a bin, sorted by bin
+    and stably within it (uint32), seg (n_bins + 1,) int64 with order[seg[b]:seg[b + 1]] the pixels of bin b"""
+    b = np.ascontiguousarray(np.asarray(bins).reshape(-1), dtype=np.uint16)
+    order = np.empty(max(b.size, 1), dtype=np.uint32)
+    seg = np.empty(max(int(n_bins), 0) + 1, dtype=np.int64)
+    rc = load().msl_polar_layout(_ptr(b), b.size, int(n_bins), _ptr(order), _ptr(seg))
+    if rc != MSL_OK:
+        _raise(rc, (load().msl_last_error(None) or b"msl_polar_layout failed").decode())
+    return order[:int(seg[-1])], seg
 
 
 def _raise(rc, msg):
@@ -607,6 +624,25 @@ class Engine:
         p, b, T, k, ld, count = self._rows(src, B, self.n_frames, t0, count)
         out = np.empty((max(b, 0), max(count, 0), getattr(self, "n_detectors", 0)), dtype=np.float64)
         self._chk(self._lib.msl_detect(self._h, p, b, T, k, ld, int(t0), count, _ptr(out)))
+        return out
+
+    # -- polar detector (msl_set_polar / msl_polar_detect; the definition is polar_data.py)
+    def set_polar(self, bins, n_bins):
+        """bins: (wx*wy,) uint16 bin id per stored pixel, POLAR_NONE for a pixel in no bin; n_bins: 1 .. POLAR_MAX_BINS"""
+        b = np.ascontiguousarray(np.asarray(bins).reshape(-1), dtype=np.uint16)
+        if b.size != self.wx * self.wy:
+            raise ValueError(f"bin map has {b.size} entries, the stored spectrum has {self.wx * self.wy}")
+        self.n_polar_bins = 0
+        self._chk(self._lib.msl_set_polar(self._h, int(n_bins), _ptr(b)))
+        self.n_polar_bins = int(n_bins)
+
+    def polar_detect(self, t0=0, count=None, B=None, src=None):
+        """(B, count, n_bins) float64: |Psi|^2 summed over the pixels of every bin, frame slots [t0, t0+count).  Source as
+        detect(): None is the handle's own wavefunction buffer (B = n_probes or fewer: the first B probes); else (device pointer,
+        B, T, K[, ld]) of a caller's complex64 array"""
+        p, b, T, k, ld, count = self._rows(src, B, self.n_frames, t0, count)
+        out = np.empty((max(b, 0), max(count, 0), getattr(self, "n_polar_bins", 0)), dtype=np.float64)
+        self._chk(self._lib.msl_polar_detect(self._h, p, b, T, k, ld, int(t0), count, _ptr(out)))
         return out
 
     # -- spectrum detectors (msl_spectrum_detect)

@@ -129,7 +129,7 @@ class MultisliceCalculator:
     def __init__(self, device=None, force_cpu=False, *, output="host", dtype="complex128", progress=True,
                  gather="rank0", cache=False, k_window=None, frame_batch=None, k_bin=None, stream_tile=None, layers=None,
                  detectors=None, probe_batch=None, diffraction=None, aberrations=None, imaging=None, prism=None,
-                 spectroscopy=None):
+                 spectroscopy=None, polar=None):
         """
         device / force_cpu: as the reference (calculators.py:41).  There is no CPU path here, so
         force_cpu=True raises.  Keyword-only extras (not in the reference):
@@ -163,8 +163,16 @@ class MultisliceCalculator:
                    propagation feeds both.  setup() raises ValueError when the bin does not divide the stored spectrum.
                    Diffraction(bin, split=True) also returns the elastic part |<Psi>|^2 of every pattern (and the thermal
                    diffuse rest), at the price of one potential build per probe batch and frame (run_diffraction).
-          probe_batch probes per batch of run_detectors() / run_diffraction() (default: chosen in setup() from free device
-                   memory, about 256 images per launch with the frame batch).  Needs detectors or diffraction.
+          polar    polar-detector mode: a polar_data.PolarDetector(outer, step, inner, n_azimuthal, rotation, per_frame).
+                   run_polar() streams the probes through the device as run_detectors() does and reduces every exit spectrum,
+                   there (msl_polar_detect), to |Psi|^2 summed over R rings x A sectors: (P, R, A) float64 on the host, the mean
+                   over the frames ((P, T, R, A) with per_frame=True), from which any annular, segmented or DPC detector on ring
+                   edges is a sum of bins chosen after the run (PolarData.integrate / image / to_stem).  Same refusals as
+                   detectors, and not with diffraction, imaging or spectroscopy; with detectors as well, one propagation feeds
+                   both (PolarData.stem).  k_window, aberrations, frame_batch, probe_batch and prism are allowed.  setup() raises
+                   ValueError when no stored pixel lies in any bin; single empty bins are legal (PolarData.counts).
+          probe_batch probes per batch of run_detectors() / run_diffraction() / run_polar() (default: chosen in setup() from free
+                   device memory, about 256 images per launch with the frame batch).  Needs detectors, diffraction or polar.
           aberrations an aberrations.Aberrations: every probe of run(), run_streaming_tacaw(), run_detectors() and
                    run_diffraction() is ifft2(mask * ramp * exp(-i chi(k))), built on the device with the probes themselves.
                    Aberrations(defocus=dz) is the reference's Probe.defocus(dz) for dz > 0 (the opposite sign of abTEM's
@@ -224,6 +232,18 @@ class MultisliceCalculator:
                 raise ValueError("streaming TACAW keeps the exit wave only: stream_tile cannot be combined with layers")
             layers = list(layers)
         self._layers_arg = layers
+        if polar is not None:
+            from .polar_data import PolarDetector
+            if not isinstance(polar, PolarDetector):
+                raise ValueError(f"polar: expected a PolarDetector object, got {polar!r}")
+            # a probe-batch mode like detectors; the modes with a result loop of their own are not fed from its pass
+            for what, val in (("cache", cache), ("layers", layers is not None), ("stream_tile", stream_tile is not None),
+                              ("k_bin", k_bin is not None), ("diffraction", diffraction is not None), ("imaging", imaging is not None),
+                              ("spectroscopy", spectroscopy is not None)):
+                if val:
+                    raise ValueError(f"polar cannot be combined with {what}"
+                                     + (" (a bin sums complex pixels: |Psi|^2 of a bin is no detector signal)" if what == "k_bin" else ""))
+        self._polar = polar
         if spectroscopy is not None:
             from .spectroscopy import Spectroscopy
             if not isinstance(spectroscopy, Spectroscopy):
@@ -247,7 +267,8 @@ class MultisliceCalculator:
                 raise NotImplementedError("prism with Diffraction(split=True) is not built: the elastic / thermal-diffuse split of "
                                           "PRISM waves")
         self._prism = prism
-        if probe_batch is not None and detectors is None and diffraction is None and imaging is None and spectroscopy is None:
+        if (probe_batch is not None and detectors is None and diffraction is None and imaging is None and spectroscopy is None
+                and polar is None):
             raise ValueError("probe_batch applies to detector and diffraction runs only: give detectors=[...] or diffraction=Diffraction(...)")
         if probe_batch is not None and int(probe_batch) < 1:
             raise ValueError("probe_batch must be a positive probe count")
@@ -378,7 +399,7 @@ class MultisliceCalculator:
         if self._spectroscopy is not None:
             self._setup_spectrum_image(trajectory, slice_axis)
             return
-        if self._detectors is not None or self._diffraction is not None or self._imaging is not None:
+        if self._detectors is not None or self._diffraction is not None or self._imaging is not None or self._polar is not None:
             self._setup_probe_batches(trajectory, slice_axis)
             return
         n_slices = self._setup_run(trajectory, slice_axis)
@@ -426,12 +447,13 @@ class MultisliceCalculator:
         self._engine.set_probes(self.aperture, np.asarray(self.probe_positions, dtype=np.float64))
 
     def _setup_probe_batches(self, trajectory, slice_axis):
-        """setup() of a run that streams probe batches (detectors, diffraction): every check on the host first, then an engine of
-        Pc <= P probes x one frame batch of result slots, then the detector memberships onto it"""
+        """setup() of a run that streams probe batches (detectors, diffraction, polar): every check on the host first, then an
+        engine of Pc <= P probes x one frame batch of result slots, then the detector memberships and the polar bin map onto it"""
         if self._world > 1:
-            mode = "detectors" if self._detectors is not None else ("diffraction" if self._diffraction is not None else "imaging")
-            raise NotImplementedError(f"{mode}: runs over several ranks are not supported (run_detectors() / run_diffraction() are "
-                                      "single-process)")
+            mode = "detectors" if self._detectors is not None else ("diffraction" if self._diffraction is not None else
+                                                                    ("polar" if self._polar is not None else "imaging"))
+            raise NotImplementedError(f"{mode}: runs over several ranks are not supported (run_detectors() / run_diffraction() / "
+                                      "run_polar() are single-process)")
         if self._diffraction is not None:
             wx, wy = self._stored_window()
             bx, by = self._diffraction.bin
@@ -445,6 +467,14 @@ class MultisliceCalculator:
                 if not ((bits >> d) & 1).any():
                     raise ValueError(f"detector {det.name!r} contains no stored pixel of the {len(kxs)} x {len(kys)} spectrum")
             self._det_bits = bits
+        if self._polar is not None:
+            from .polar_data import bin_counts, polar_bins
+            pkx, pky = self._k_axes()
+            self._polar_bins = polar_bins(self._polar, pkx, pky, wavelength(self.voltage_eV))
+            self._polar_counts = bin_counts(self._polar_bins, self._polar.n_bins)
+            if not self._polar_counts.any():
+                raise ValueError(f"polar: no stored pixel of the {len(pkx)} x {len(pky)} spectrum lies between {self._polar.inner:g} and "
+                                 f"{self._polar.edges[-1]:g} mrad")
         n_slices = self._setup_run(trajectory, slice_axis)
         self._frames = list(range(self.n_frames))
         # Pc x frame batch near the ~256 images per launch of default_frame_batch: 256 probes x 1 frame for a scan, all probes x
@@ -471,6 +501,8 @@ class MultisliceCalculator:
         self._configure_engine()                                # (the aberrations are read by the set_probes of every probe batch)
         if self._detectors is not None:
             self._engine.set_detectors(bits.reshape(-1), [d.signal for d in self._detectors], kxs, kys)
+        if self._polar is not None:
+            self._engine.set_polar(self._polar_bins.reshape(-1), self._polar.n_bins)
         if self._prism is not None:
             self._engine.smatrix_begin(self._prism.interpolation, self.aperture)
 
@@ -567,8 +599,8 @@ class MultisliceCalculator:
     def _fit_probe_batch(self, free_b, Pc, batch):
         """Probe-batch runs: the default probe batch, halved while the three work buffers and the result ring of Pc x batch images,
         the coherent accumulator of a split run (16 * pitch bytes per probe), the image accumulator of an imaging run (8 * nx * ny
-        bytes per probe, layer and defocus), the transmission stacks of the batch and the phase tables exceed 0.9 x the free device
-        memory."""
+        bytes per probe, layer and defocus), the output scratch of a polar run (8 * n_bins bytes per image), the transmission stacks
+        of the batch and the phase tables exceed 0.9 x the free device memory."""
         nx, ny, n_slices = self.nx, self.ny, len(self._slice_coords)
         pitch = self._stored_shape()[2]
         tables = self._phase_table_bytes(batch)
@@ -576,7 +608,8 @@ class MultisliceCalculator:
         if self._imaging is not None:
             coh = 8.0 * nx * ny * len(self._layers) * len(self._imaging.defocus_series)
         smatrix = 8.0 * getattr(self, "_prism_Bm", 0) * nx * ny       # the S-matrix of a PRISM run, (Bm, nx, ny) complex64
-        while Pc > 1 and (Pc * batch * (32.0 * nx * ny + 8.0 * pitch) + Pc * coh + batch * 16.0 * n_slices * nx * ny + tables + smatrix + 1e9
+        polar = 8.0 * self._polar.n_bins if self._polar is not None else 0.0
+        while Pc > 1 and (Pc * batch * (32.0 * nx * ny + 8.0 * pitch + polar) + Pc * coh + batch * 16.0 * n_slices * nx * ny + tables + smatrix + 1e9
                           > 0.9 * free_b):
             Pc = max(1, Pc // 2)
         return Pc
@@ -889,6 +922,8 @@ class MultisliceCalculator:
             raise RuntimeError("spectroscopy is set: the device holds one probe batch at a time -- call run_spectrum_image()")
         if self._engine is None:
             raise RuntimeError("call setup() before run_detectors()")
+        if self._detectors is None and self._polar is not None:
+            raise RuntimeError("polar is set and detectors are not: call run_polar()")
         if self._detectors is None:
             raise RuntimeError("run_detectors() needs MultisliceCalculator(detectors=[...])")
         eng = self._engine
@@ -905,6 +940,47 @@ class MultisliceCalculator:
         self.elapsed = time.time() - t0
         self.frames_computed, self.frames_cached = T, 0
         return self._stem_data(signals)
+
+    def run_polar(self):
+        """Polar-detector signals of every probe position: the loop of run_detectors(); msl_polar_detect reduces the exit spectra of
+        every probe batch to (real, n, R * A) float64 -- |Psi|^2 summed over the pixels of each ring x sector bin, frame by frame --
+        which is stored (PolarDetector(per_frame=True)) or summed over the n frames into the host result and divided by the number of
+        frames at the end.  -> PolarData with signals (P, R, A) float64, (P, T, R, A) per frame; with detectors as well, .stem is
+        the STEMData run_detectors() returns, from the same propagation.  Device memory does not depend on the number of probe
+        positions; the host holds 8 * P * R * A bytes (times T per frame)."""
+        from .polar_data import PolarData
+        if self._spectroscopy is not None:
+            raise RuntimeError("spectroscopy is set: the device holds one probe batch at a time -- call run_spectrum_image()")
+        if self._polar is None:
+            raise RuntimeError("run_polar() needs MultisliceCalculator(polar=PolarDetector(...))")
+        if self._engine is None:
+            raise RuntimeError("call setup() before run_polar()")
+        eng, pol = self._engine, self._polar
+        t0 = time.time()
+        P, T, R, A = self.n_probes, self.n_frames, pol.n_rings, pol.n_azimuthal
+        acc = np.zeros((P, T, R * A) if pol.per_frame else (P, R * A), dtype=np.float64)
+        signals = None if self._detectors is None else np.zeros((P, T, len(self._detectors)), dtype=np.float64)
+
+        def reduce_batch(p0, real, s0, n):
+            got = eng.polar_detect(0, n, B=real)
+            if pol.per_frame:
+                acc[p0:p0 + real, s0:s0 + n] = got
+            else:
+                acc[p0:p0 + real] += got.sum(axis=1)
+            if signals is not None:
+                signals[p0:p0 + real, s0:s0 + n] = eng.detect(0, n, B=real)
+        if self._prism is not None:
+            self._prism_loop(reduce_batch)
+        else:
+            self._probe_batch_loop(reduce_batch)
+        if not pol.per_frame:
+            acc /= T
+        self.elapsed = time.time() - t0
+        self.frames_computed, self.frames_cached = T, 0
+        kxs, kys = self._k_axes()
+        return PolarData(signals=acc.reshape(acc.shape[:-1] + (R, A)), polar=pol, counts=self._polar_counts.reshape(R, A), edges=pol.edges,
+                         probe_positions=self.probe_positions, time=np.arange(T) * self.trajectory.timestep, kxs=_as_tensor(kxs),
+                         kys=_as_tensor(kys), probe=self.base_probe, stem=None if signals is None else self._stem_data(signals))
 
     def _check_layers(self, n_slices, world):
         """the `layers` argument -> sorted unique slice indices with n_slices - 1 last (before any device work)"""
@@ -943,6 +1019,8 @@ class MultisliceCalculator:
             raise RuntimeError("imaging is set: the device holds one probe batch at a time -- call run_images()")
         if self._spectroscopy is not None:
             raise RuntimeError("spectroscopy is set: the device holds one probe batch at a time -- call run_spectrum_image()")
+        if self._polar is not None:
+            raise RuntimeError("polar is set: the device holds one probe batch at a time -- call run_polar()")
         if self._engine is None:
             raise RuntimeError("call setup() before run()")
         if self._stream_tile is not None:

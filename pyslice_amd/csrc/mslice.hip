@@ -26,6 +26,7 @@
 #include "tacaw_welch.h"
 #include "layer_tap.h"
 #include "detect.h"
+#include "polar.h"
 #include "spectrum_detect.h"
 #include "diffract.h"
 #include "coherent.h"
@@ -187,6 +188,11 @@ struct msl_handle {
     int det_n = 0, det_wy = 0;
     size_t det_K = 0;
     uint32_t det_amp = 0, det_cx = 0, det_cy = 0;
+    // polar detector (msl_set_polar): the pixels sorted by bin and the bins' slices of that list (polar.h); pol_bins = 0: no map
+    DevBuf<uint32_t> pol_order;
+    DevBuf<long long> pol_seg;
+    int pol_bins = 0;
+    size_t pol_K = 0;
     // diffraction patterns (msl_diffract): (B, mx, my) float64 staging, grown on demand
     DevBuf<double> diff_out;
     // coherent frame sums (msl_coherent_reset / _add / _finish): (coh_B, wpitch) float64 complex, grown on demand; coh_K = the row
@@ -3183,6 +3189,70 @@ int msl_detect(msl_handle* h, const void* d_src_c64, int64_t B, int64_t T, int64
                            h->det_mask.p, h->det_kx.p, h->det_ky.p, h->det_wy, h->det_amp, h->det_cx, h->det_cy, t.d_part);
     }); }); });
     return detect_finish(h, t, out);
+}
+
+// ---- polar detector (polar.h) -----------------------------------------------------------------------------
+static int check_polar_map(msl_handle* h, const char* who, const uint16_t* bin_K, int64_t K, int32_t n_bins) {
+    if (!bin_K) return fail(h, MSL_ERR_INVALID, "%s: null argument", who);
+    if (K < 0) return fail(h, MSL_ERR_INVALID, "%s: %lld pixels", who, (long long)K);
+    if (n_bins < 1 || n_bins > POLAR_MAX_BINS) return fail(h, MSL_ERR_INVALID, "%s: %d bins outside [1,%d]", who, n_bins, POLAR_MAX_BINS);
+    return MSL_OK;
+}
+
+int msl_polar_layout(const uint16_t* bin_K, int64_t K, int32_t n_bins, uint32_t* order_K, int64_t* seg_n1) {
+    int rc = check_polar_map(nullptr, "msl_polar_layout", bin_K, K, n_bins);
+    if (rc) return rc;
+    if (!order_K || !seg_n1) return fail(nullptr, MSL_ERR_INVALID, "msl_polar_layout: null argument");
+    if (!polar_layout(bin_K, K, n_bins, order_K, seg_n1))
+        return fail(nullptr, MSL_ERR_INVALID, "msl_polar_layout: a bin id outside [0,%d) that is not MSL_POLAR_NONE", n_bins);
+    return MSL_OK;
+}
+
+int msl_set_polar(msl_handle* h, int32_t n_bins, const uint16_t* bin_K) {
+    if (!h) return fail(h, MSL_ERR_INVALID, "msl_set_polar: null handle");
+    const size_t K = h->wpix;
+    int rc = check_polar_map(h, "msl_set_polar", bin_K, (int64_t)K, n_bins);
+    if (rc) return rc;
+    if (K > 0xffffffffull) return fail(h, MSL_ERR_UNSUPPORTED, "msl_set_polar: more than 2^32 stored pixels");
+    h->pol_bins = 0;
+    std::vector<uint32_t> order(std::max<size_t>(K, 1));
+    std::vector<int64_t> seg((size_t)n_bins + 1);
+    if (!polar_layout(bin_K, (int64_t)K, n_bins, order.data(), seg.data()))
+        return fail(h, MSL_ERR_INVALID, "msl_set_polar: a bin id outside [0,%d) that is not MSL_POLAR_NONE", n_bins);
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    if ((rc = h->pol_order.alloc(h, order.size())) || (rc = h->pol_seg.alloc(h, seg.size()))) return rc;
+    HIPCHK(h, hipMemcpyAsync(h->pol_order, order.data(), order.size() * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->pol_seg, seg.data(), seg.size() * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    h->pol_bins = n_bins; h->pol_K = K;
+    return MSL_OK;
+}
+
+int msl_polar_detect(msl_handle* h, const void* d_src_c64, int64_t B, int64_t T, int64_t K, int64_t ld, int32_t t0, int32_t count, double* out) {
+    if (!h || !out) return fail(h, MSL_ERR_INVALID, "msl_polar_detect: null argument");
+    if (h->pol_bins == 0) return fail(h, MSL_ERR_STATE, "msl_polar_detect: no bin map (call msl_set_polar)");
+    Rows r{d_src_c64, B, T, K, ld};
+    int rc;
+    if ((rc = resolve_rows(h, "msl_polar_detect", SRC_WAVEFUNCTION | SRC_FIRST_B, &r))) return rc;
+    if ((size_t)r.K != h->pol_K) return fail(h, MSL_ERR_INVALID, "msl_polar_detect: rows of %lld pixels, the bin map covers %zu", (long long)r.K, h->pol_K);
+    if ((rc = check_slots(h, "msl_polar_detect", "frame slots", t0, count, r.R))) return rc;
+    const int64_t rows = r.B * count, n_bins = h->pol_bins;
+    if (rows > 0x7fffffffLL) return fail(h, MSL_ERR_UNSUPPORTED, "msl_polar_detect: more than 2^31 rows");
+    // rows per workgroup: a wave reads its bin's pixel list once per POLAR_ROWS rows; whole groups of them while that leaves about
+    // 64 k waves to spread over the device, and as many as the grid's 2^31 workgroups need
+    const int64_t bin_groups = (n_bins + POLAR_WAVES - 1) / POLAR_WAVES;
+    int64_t per = std::max<int64_t>(1, std::min<int64_t>(16, rows * n_bins / 65536 / POLAR_ROWS)) * POLAR_ROWS;
+    per = std::max<int64_t>(per, ((rows * bin_groups + 0x7ffffffeLL) / 0x7fffffffLL + POLAR_ROWS - 1) / POLAR_ROWS * POLAR_ROWS);
+    const int64_t row_blocks = (rows + per - 1) / per;
+    const size_t out_bytes = (size_t)rows * n_bins * sizeof(double);
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    if ((rc = h->scratch.reserve(h, out_bytes))) return rc;
+    double* d_out = (double*)h->scratch.p;
+    hipLaunchKernelGGL(polar_gather_kernel, dim3((unsigned)(row_blocks * bin_groups)), dim3(64 * POLAR_WAVES), 0, h->stream, (const float2*)r.p,
+                       (long long)r.R, (long long)t0, (unsigned)count, (long long)r.ld, (long long)rows, (int)per, (int)n_bins, (unsigned)bin_groups,
+                       h->pol_order.p, h->pol_seg.p, d_out);
+    HIPCHK(h, hipGetLastError());
+    return download_sync(h, out, d_out, out_bytes);
 }
 
 // ---- spectrum detectors (spectrum_detect.h) ---------------------------------------------------------------
