@@ -510,6 +510,49 @@ int  msl_tacaw_layer(msl_handle* h, int32_t layer);
 /* msl_tacaw_welch with d_src == NULL on block `layer` of the layered result. */
 int  msl_tacaw_welch_layer(msl_handle* h, int32_t layer, int32_t L, int32_t hop, const double* window_L);
 
+/* ---- thickness series of the probe-batch modes: detector, polar and pattern signals of every tapped layer ----
+ * msl_set_layers keeps one full block of spectra per layer; a scan that streams probe batches wants the REDUCED signals of every
+ * thickness and no spectra.  Here every tap goes to ONE reused block, which is reduced at once, inside the launch sequence of the
+ * slice loop, into a float64 staging area, so that device memory does not grow with the number of thicknesses.
+ * msl_set_layer_reduce: `n` strictly increasing slice indices k in [0, nz-1), layer k as for msl_set_layers; the exit wave is
+ *   layer n, L = n + 1.  what = MSL_LR_* bits: DETECT (the detectors of msl_set_detectors), POLAR (the bin map of msl_set_polar),
+ *   DIFFRACT (patterns of bx x by stored pixels, as msl_diffract), PACBED (the same patterns summed over the probes on the device);
+ *   bx, by are read with DIFFRACT or PACBED only.  Allocates the tap buffer, one block of the size of MSL_BUF_WAVEFUNCTION, the
+ *   partial slab of the detector tiles, and 8 * [L * P * T * D (DETECT) + L * P * T * n_bins (POLAR) + L * P * mx * my (DIFFRACT or
+ *   PACBED) + L * mx * my (PACBED)] bytes of staging, P = n_probes, T = n_frames, mx x my = the binned stored window.
+ *   MSL_ERR_STATE for DETECT without detectors or POLAR without a bin map, with n_frames == 0, while a stream is open, or while
+ *   msl_set_layers holds layers (and msl_set_layers is MSL_ERR_STATE while this mode is on); MSL_ERR_INVALID for bad slices, bits or
+ *   bins; MSL_ERR_NOMEM with the old state intact.  n = 0 or what = 0 turns the mode off and frees the buffers.
+ *   The staging has rows of the detector and bin counts of this call: while the mode is on, msl_set_detectors with another n (DETECT)
+ *   and msl_set_polar with another n_bins (POLAR) are MSL_ERR_STATE; other memberships or another bin map of the same count are fine.
+ *   Should a failed one of those calls leave no detectors or no map, the next slice loop is MSL_ERR_STATE and queues nothing.
+ *   While the mode is on, msl_propagate_frame / msl_propagate_frames queue, behind the tap of every listed slice and behind the exit
+ *   epilogue, the reductions of that layer over the frame slots of the call, for all n_probes rows (a padded probe is reduced too),
+ *   with the launches of msl_detect, msl_polar_detect and msl_diffract (the frame sum covers the frames of the call) and no host
+ *   synchronisation: the numbers are bit for bit those calls' on the same spectra.  MSL_BUF_LAYERS stays the single exit block.
+ * msl_layer_fetch: after one stream synchronisation, the results of the last sequence for the first B probes (B <= 0: n_probes):
+ *   det_out (L, B, count, D), polar_out (L, B, count, n_bins), pattern_out (L, B, mx, my) float64 HOST memory, each NULL when not
+ *   wanted; count must be the frame count of that sequence.  MSL_ERR_INVALID for an output whose reduction is not on (patterns are
+ *   fetched with DIFFRACT only); MSL_ERR_STATE before the first sequence.
+ * msl_layer_pacbed_reset / _add / _download (PACBED): the accumulator (L, mx, my) float64 is zeroed; receives, per layer, the sum
+ *   over the first B probes of the patterns of the last sequence -- one launch, float64, in probe order, no atomics: repeated runs are
+ *   bitwise equal; is copied to HOST memory (waits for the stream).  reset and add are queued.
+ * msl_layer_reduce_bytes: bytes of the block, the tap buffer or the staging area (MSL_LR_BYTES_*), 0 while the mode is off.
+ *   Not in the reference, which holds every frame of a single layer. */
+#define MSL_LR_DETECT 1u
+#define MSL_LR_POLAR 2u
+#define MSL_LR_DIFFRACT 4u
+#define MSL_LR_PACBED 8u
+#define MSL_LR_BYTES_BLOCK 0
+#define MSL_LR_BYTES_TAP 1
+#define MSL_LR_BYTES_STAGING 2
+int  msl_set_layer_reduce(msl_handle* h, const int32_t* slices, int32_t n, uint32_t what, int32_t bx, int32_t by);
+int  msl_layer_fetch(msl_handle* h, int64_t B, int32_t count, double* det_out, double* polar_out, double* pattern_out);
+int  msl_layer_pacbed_reset(msl_handle* h);
+int  msl_layer_pacbed_add(msl_handle* h, int64_t B);
+int  msl_layer_pacbed_download(msl_handle* h, double* out);
+size_t msl_layer_reduce_bytes(const msl_handle* h, int32_t which);
+
 /* Copy a device buffer to the host (dst must hold `bytes` = full buffer size, see msl_buffer_bytes).
  * For MSL_BUF_WAVEFUNCTION / MSL_BUF_INTENSITY the host copy is dense -- (P,T,wx,wy), bytes = P*T*wx*wy*8 or *4, the pixel
  * pitch of the device buffer (msl_result_pitch) is dropped on the way -- and `first`/`count` select a probe range (count==0: all).

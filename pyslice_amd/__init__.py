@@ -16,6 +16,7 @@ from .haadf_data import HAADFData
 from .stem_data import Detector, STEMData
 from .diffraction_data import Diffraction, DiffractionData
 from .polar_data import PolarDetector, PolarData, polar_bins, polar_signals
+from .thickness import Thickness
 from .aberrations import Aberrations, scherzer_defocus
 from .imaging import Imaging
 from .image_data import ImageData
@@ -25,6 +26,6 @@ from .spectrum_image_data import SpectrumImageData
 __all__ = ["Trajectory", "FrozenPhonons", "sigma_from_B", "PhononModes", "WFData", "Potential", "gridFromTrajectory", "getZfromElementName", "loadKirkland",
            "Probe", "Propagate", "create_batched_probes", "probe_grid", "wavelength", "m_effective",
            "MultisliceCalculator", "TACAWData", "HAADFData", "Detector", "STEMData", "Diffraction", "DiffractionData",
-           "PolarDetector", "PolarData", "polar_bins", "polar_signals",
+           "PolarDetector", "PolarData", "polar_bins", "polar_signals", "Thickness",
            "Aberrations", "scherzer_defocus", "Imaging", "ImageData", "Spectroscopy", "SpectrumImageData"]
 __version__ = "0.1.0"

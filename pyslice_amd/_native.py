@@ -38,9 +38,13 @@ EXPORTS = [
     "msl_tacaw_welch_has", "msl_tacaw_welch", "msl_tacaw_welch_layer",
     "msl_set_structure", "msl_build_thermal", "msl_thermal_positions",
     "msl_set_modes", "msl_build_modes", "msl_mode_positions",
+    "msl_set_layer_reduce", "msl_layer_fetch", "msl_layer_pacbed_reset", "msl_layer_pacbed_add", "msl_layer_pacbed_download",
+    "msl_layer_reduce_bytes",
 ]
 DET_SIGNALS = {"intensity": 0, "amplitude": 1, "com_x": 2, "com_y": 3}      # include/mslice.h: MSL_DET_*
 POLAR_NONE, POLAR_MAX_BINS = 0xFFFF, 4096                                  # include/mslice.h: MSL_POLAR_*
+LR_DETECT, LR_POLAR, LR_DIFFRACT, LR_PACBED = 1, 2, 4, 8                   # include/mslice.h: MSL_LR_*
+LR_BYTES_BLOCK, LR_BYTES_TAP, LR_BYTES_STAGING = 0, 1, 2                   # include/mslice.h: MSL_LR_BYTES_*
 
 
 class MslConfig(C.Structure):
@@ -150,6 +154,12 @@ def load():
         "msl_set_modes": (C.c_int, [vp, vp, i64, i32, vp, vp, vp, i32, i32]),
         "msl_build_modes": (C.c_int, [vp, C.c_uint64, i64, i32]),
         "msl_mode_positions": (C.c_int, [vp, C.c_uint64, i64, vp]),
+        "msl_set_layer_reduce": (C.c_int, [vp, vp, i32, C.c_uint32, i32, i32]),
+        "msl_layer_fetch": (C.c_int, [vp, i64, i32, vp, vp, vp]),
+        "msl_layer_pacbed_reset": (C.c_int, [vp]),
+        "msl_layer_pacbed_add": (C.c_int, [vp, i64]),
+        "msl_layer_pacbed_download": (C.c_int, [vp, vp]),
+        "msl_layer_reduce_bytes": (C.c_size_t, [vp, i32]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -467,6 +477,53 @@ class Engine:
         out = np.empty((self.n_probes, T, self.wx, self.wy, self.n_layers), dtype=np.complex128)
         self._chk(self._lib.msl_download_layers_c128(self._h, T, _ptr(out), out.nbytes))
         return out
+
+    # -- thickness series of the probe-batch modes (msl_set_layer_reduce / msl_layer_fetch / msl_layer_pacbed_*)
+    def set_layer_reduce(self, slices, what, bin=(1, 1)):
+        """reduce the waves after these slices (strictly increasing, < nz - 1) and the exit wave, inside every slice loop, to the
+        signals `what` asks for (LR_* bits: detectors, polar bins, patterns of `bin` stored pixels, their sum over the probes); one
+        reused block of spectra whatever the number of slices.  [] or what = 0 turns the mode off."""
+        s = np.ascontiguousarray(slices, dtype=np.int32).reshape(-1)
+        bx, by = int(bin[0]), int(bin[1])
+        self._chk(self._lib.msl_set_layer_reduce(self._h, _ptr(s) if s.size else None, int(s.size), int(what), bx, by))
+        # (a refused call leaves the handle's mode as it was: so does this mirror)
+        on = bool(s.size and what)
+        self.reduce_layers, self._lr_what, self._lr_bin = ([int(v) for v in s], int(what), (bx, by)) if on else (None, 0, (1, 1))
+
+    def layer_fetch(self, count, B=None):
+        """(det, polar, patterns) of the last slice loop, which ran `count` frames, for the first B probes and every layer, the exit
+        last: (L, B, count, D), (L, B, count, n_bins), (L, B, wx/bx, wy/by) float64, None for what set_layer_reduce did not ask for
+        (the patterns of a pacbed-only set-up stay on the device).  One wait for the stream."""
+        if not getattr(self, "reduce_layers", None):
+            raise RuntimeError("layer_fetch: call set_layer_reduce first")
+        L, b, n, what = len(self.reduce_layers) + 1, int(B) if B else self.n_probes, int(count), self._lr_what
+        bx, by = self._lr_bin
+        det = np.empty((L, b, n, getattr(self, "n_detectors", 0)), dtype=np.float64) if what & LR_DETECT else None
+        pol = np.empty((L, b, n, getattr(self, "n_polar_bins", 0)), dtype=np.float64) if what & LR_POLAR else None
+        pat = np.empty((L, b, self.wx // bx, self.wy // by), dtype=np.float64) if what & LR_DIFFRACT else None
+        self._chk(self._lib.msl_layer_fetch(self._h, b, n, *(None if a is None else _ptr(a) for a in (det, pol, pat))))
+        return det, pol, pat
+
+    def layer_pacbed_reset(self):
+        """zero the (L, wx/bx, wy/by) float64 accumulator of the position-averaged patterns (queued)"""
+        self._chk(self._lib.msl_layer_pacbed_reset(self._h))
+
+    def layer_pacbed_add(self, B=None):
+        """add the patterns of the first B probes of the last slice loop, layer by layer, into the accumulator (queued)"""
+        self._chk(self._lib.msl_layer_pacbed_add(self._h, int(B) if B else 0))
+
+    def layer_pacbed(self):
+        """(L, wx/bx, wy/by) float64: the accumulator; waits for the stream"""
+        if not getattr(self, "reduce_layers", None):
+            raise RuntimeError("layer_pacbed: call set_layer_reduce first")
+        bx, by = self._lr_bin
+        out = np.empty((len(self.reduce_layers) + 1, self.wx // bx, self.wy // by), dtype=np.float64)
+        self._chk(self._lib.msl_layer_pacbed_download(self._h, _ptr(out)))
+        return out
+
+    def layer_reduce_bytes(self, which):
+        """device bytes of the reduce mode's block, tap buffer or staging area (LR_BYTES_*); 0 while the mode is off"""
+        return int(self._lib.msl_layer_reduce_bytes(self._h, int(which)))
 
     def layers_c64(self):
         """(L, P, n_frames, wx, wy) complex64, dense"""

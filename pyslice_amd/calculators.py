@@ -28,6 +28,7 @@ from .prism import Prism, beams as prism_beams
 from .potentials import (TORCH_AVAILABLE, _as_tensor, _device_index, atomic_numbers_of, gridFromTrajectory, loadKirkland, slice_edges,
                          suggest_sampling)
 from .thermal import FrozenPhonons
+from .thickness import as_thickness
 from .phonons import PhononModes
 from .trajectory import Trajectory
 from .wf_data import WFData
@@ -129,7 +130,7 @@ class MultisliceCalculator:
     def __init__(self, device=None, force_cpu=False, *, output="host", dtype="complex128", progress=True,
                  gather="rank0", cache=False, k_window=None, frame_batch=None, k_bin=None, stream_tile=None, layers=None,
                  detectors=None, probe_batch=None, diffraction=None, aberrations=None, imaging=None, prism=None,
-                 spectroscopy=None, polar=None):
+                 spectroscopy=None, polar=None, thickness=None):
         """
         device / force_cpu: as the reference (calculators.py:41).  There is no CPU path here, so
         force_cpu=True raises.  Keyword-only extras (not in the reference):
@@ -203,6 +204,16 @@ class MultisliceCalculator:
                    halves the probe batch while they do not and raises MemoryError at one probe.  run() and the other run modes
                    are refused.  Allowed with k_window, aberrations, frame_batch, probe_batch; not with detectors, diffraction,
                    imaging, prism, layers, cache, stream_tile, k_bin or several ranks.  Needs at least 2 frames.
+          thickness thickness series of the probe-batch modes: a list of 0-based slice indices, or a thickness.Thickness(slices=[...] |
+                   every=n, patterns="position" | "pacbed").  Entry k is the wave after the transmission of slice k (the definition
+                   of `layers`); setup() sorts the entries, drops duplicates and appends nz - 1, the exit wave.  run_detectors(),
+                   run_polar() and run_diffraction() then return, from ONE scan, the signals of every entry on a last axis of
+                   length L -- (P, T, D, L), (P, R, A, L), (P, mx, my, L); (mx, my, L) with patterns="pacbed", summed over the
+                   probes on the device -- with .layer, .thickness (Angstrom) and .at(i) on the results.  Every tapped layer is
+                   reduced on the device at once (msl_set_layer_reduce): one reused block of spectra and a small float64 staging
+                   area, whatever L and P.  Needs detectors, polar or diffraction; allowed with k_window, aberrations, probe_batch,
+                   frame_batch, FrozenPhonons / PhononModes; not with layers, cache, stream_tile, k_bin, imaging, spectroscopy,
+                   prism, Diffraction(split=True) or several ranks.
         """
         if force_cpu:
             raise NotImplementedError("pyslice_amd has no CPU path (force_cpu=True): use the reference for CPU runs")
@@ -232,6 +243,21 @@ class MultisliceCalculator:
                 raise ValueError("streaming TACAW keeps the exit wave only: stream_tile cannot be combined with layers")
             layers = list(layers)
         self._layers_arg = layers
+        if thickness is not None:
+            thickness = as_thickness(thickness)
+            if detectors is None and polar is None and diffraction is None:
+                raise ValueError("thickness applies to run_detectors(), run_polar() and run_diffraction(): give detectors=[...], "
+                                 "polar=PolarDetector(...) or diffraction=Diffraction(...) (layers=[...] keeps the spectra of run())")
+            for what, val in (("layers", layers is not None), ("cache", cache), ("stream_tile", stream_tile is not None),
+                              ("k_bin", k_bin is not None)):
+                if val:
+                    raise ValueError(f"thickness cannot be combined with {what}")
+            for what, val in (("imaging", imaging is not None), ("spectroscopy", spectroscopy is not None), ("prism", prism is not None),
+                              ("Diffraction(split=True)", getattr(diffraction, "split", False))):
+                if val:
+                    raise NotImplementedError(f"thickness with {what} is not built")
+        self._thickness_arg = thickness
+        self._thickness = None                  # validated slice indices (setup), nz - 1 last; None without a thickness series
         if polar is not None:
             from .polar_data import PolarDetector
             if not isinstance(polar, PolarDetector):
@@ -449,6 +475,8 @@ class MultisliceCalculator:
     def _setup_probe_batches(self, trajectory, slice_axis):
         """setup() of a run that streams probe batches (detectors, diffraction, polar): every check on the host first, then an
         engine of Pc <= P probes x one frame batch of result slots, then the detector memberships and the polar bin map onto it"""
+        if self._world > 1 and self._thickness_arg is not None:
+            raise NotImplementedError("thickness: runs over several ranks are not built")
         if self._world > 1:
             mode = "detectors" if self._detectors is not None else ("diffraction" if self._diffraction is not None else
                                                                     ("polar" if self._polar is not None else "imaging"))
@@ -477,6 +505,7 @@ class MultisliceCalculator:
                                  f"{self._polar.edges[-1]:g} mrad")
         n_slices = self._setup_run(trajectory, slice_axis)
         self._frames = list(range(self.n_frames))
+        self._thickness = None if self._thickness_arg is None else self._thickness_arg.resolve(n_slices)
         # Pc x frame batch near the ~256 images per launch of default_frame_batch: 256 probes x 1 frame for a scan, all probes x
         # ceil(256 / P) frames for a few (an explicit probe_batch is honoured as is)
         auto = self._probe_batch is None
@@ -496,15 +525,25 @@ class MultisliceCalculator:
                 batch = max(1, batch // 2)
             logger.info(f"device memory: probe batch {Pc}, frame batch {batch}")
             return Pc, batch, batch
-        self._create_engine(Pc, batch, batch, shrink, device=_device_index(self.device))
+
+        def furnish():
+            """what the engine of a probe-batch run allocates after msl_create, inside the shrink-and-retry of _create_engine: a
+            thickness series whose block, tap buffer and staging do not fit is tried again at the next smaller probe batch"""
+            self._configure_engine()                            # (the aberrations are read by the set_probes of every probe batch)
+            if self._detectors is not None:
+                self._engine.set_detectors(bits.reshape(-1), [d.signal for d in self._detectors], kxs, kys)
+            if self._polar is not None:
+                self._engine.set_polar(self._polar_bins.reshape(-1), self._polar.n_bins)
+            if self._thickness is not None and len(self._thickness) > 1:    # (the exit wave alone needs no tap: the plain reductions)
+                pacbed = self._diffraction is not None and self._thickness_arg.patterns == "pacbed"
+                what = ((_native.LR_DETECT if self._detectors is not None else 0) | (_native.LR_POLAR if self._polar is not None else 0)
+                        | (0 if self._diffraction is None else (_native.LR_PACBED if pacbed else _native.LR_DIFFRACT)))
+                self._engine.set_layer_reduce(self._thickness[:-1], what,
+                                              bin=(1, 1) if self._diffraction is None else self._diffraction.bin)
+            if self._prism is not None:
+                self._engine.smatrix_begin(self._prism.interpolation, self.aperture)
+        self._create_engine(Pc, batch, batch, shrink, furnish=furnish, device=_device_index(self.device))
         self.probe_batch = self._engine.n_probes
-        self._configure_engine()                                # (the aberrations are read by the set_probes of every probe batch)
-        if self._detectors is not None:
-            self._engine.set_detectors(bits.reshape(-1), [d.signal for d in self._detectors], kxs, kys)
-        if self._polar is not None:
-            self._engine.set_polar(self._polar_bins.reshape(-1), self._polar.n_bins)
-        if self._prism is not None:
-            self._engine.smatrix_begin(self._prism.interpolation, self.aperture)
 
     def _setup_spectrum_image(self, trajectory, slice_axis):
         """setup() of run_spectrum_image(): every check on the host first, then an engine of Pc <= P probes whose result ring has
@@ -597,7 +636,8 @@ class MultisliceCalculator:
         return batch
 
     def _fit_probe_batch(self, free_b, Pc, batch):
-        """Probe-batch runs: the default probe batch, halved while the three work buffers and the result ring of Pc x batch images,
+        """Probe-batch runs: the default probe batch, halved while the three work buffers and the result ring of Pc x batch images
+        (with a thickness series also its one block, the tap buffer and the staging of every entry),
         the coherent accumulator of a split run (16 * pitch bytes per probe), the image accumulator of an imaging run (8 * nx * ny
         bytes per probe, layer and defocus), the output scratch of a polar run (8 * n_bins bytes per image), the transmission stacks
         of the batch and the phase tables exceed 0.9 x the free device memory."""
@@ -609,7 +649,16 @@ class MultisliceCalculator:
             coh = 8.0 * nx * ny * len(self._layers) * len(self._imaging.defocus_series)
         smatrix = 8.0 * getattr(self, "_prism_Bm", 0) * nx * ny       # the S-matrix of a PRISM run, (Bm, nx, ny) complex64
         polar = 8.0 * self._polar.n_bins if self._polar is not None else 0.0
-        while Pc > 1 and (Pc * batch * (32.0 * nx * ny + 8.0 * pitch + polar) + Pc * coh + batch * 16.0 * n_slices * nx * ny + tables + smatrix + 1e9
+        series = 0.0
+        if self._thickness is not None and len(self._thickness) > 1:
+            # the thickness series: per image one more block of the ring, the tap buffer and the detector and polar rows of every
+            # entry in the float64 staging (the plain polar scratch is in `polar`); per probe the patterns of every entry
+            L = len(self._thickness)
+            sx, sy, _ = self._stored_shape()
+            bx, by = self._diffraction.bin if self._diffraction is not None else (1, 1)
+            series = 8.0 * pitch + 8.0 * nx * ny + L * polar + 8.0 * L * (len(self._detectors) if self._detectors is not None else 0)
+            coh += 8.0 * L * (sx // bx) * (sy // by) if self._diffraction is not None else 0.0
+        while Pc > 1 and (Pc * batch * (32.0 * nx * ny + 8.0 * pitch + polar + series) + Pc * coh + batch * 16.0 * n_slices * nx * ny + tables + smatrix + 1e9
                           > 0.9 * free_b):
             Pc = max(1, Pc // 2)
         return Pc
@@ -632,16 +681,22 @@ class MultisliceCalculator:
                               f"{free_b / 1e9:.2f} GB are free: keep fewer pixels with k_window=(wx, wy)")
         return Pc
 
-    def _create_engine(self, n_probes, slots, batch, shrink, **engine_kw):
-        """The engine of n_probes probes x slots result slots at a frame batch.  When the device cannot hold it,
-        shrink(n_probes, slots, batch) names the next smaller one to try, or None to give up."""
+    def _create_engine(self, n_probes, slots, batch, shrink, furnish=None, **engine_kw):
+        """The engine of n_probes probes x slots result slots at a frame batch, then furnish(): the set-up calls that allocate on
+        it.  When the device cannot hold either, shrink(n_probes, slots, batch) names the next smaller one to try, or None to
+        give up."""
         while True:
             try:
                 self._engine = _native.Engine(self.nx, self.ny, len(self._slice_coords), self.dx, self.dy, self._dz,
                                               wavelength(self.voltage_eV), interaction_sigma(self.voltage_eV), n_probes=n_probes,
                                               n_frames=slots, window=self._k_window, frame_batch=batch, **engine_kw)
+                if furnish is not None:
+                    furnish()
                 return
             except MemoryError:
+                if self._engine is not None:                    # (furnish() ran out of memory: this engine goes before the next)
+                    self._engine.close()
+                    self._engine = None
                 smaller = shrink(n_probes, slots, batch)
                 if smaller is None:
                     raise
@@ -776,7 +831,54 @@ class MultisliceCalculator:
         kxs, kys = self._k_axes()
         return STEMData(signals=signals, detectors=list(self._detectors), probe_positions=self.probe_positions,
                         time=np.arange(self.n_frames) * self.trajectory.timestep, kxs=_as_tensor(kxs), kys=_as_tensor(kys),
-                        probe=self.base_probe)
+                        probe=self.base_probe, **self._layer_fields())
+
+    def _layer_fields(self):
+        """layer / thickness of a result with a thickness axis: the slice indices, and the depth in Angstrom at the exit side of each
+        slice, from the slice edges the engine was given"""
+        if self._thickness is None:
+            return {}
+        lo, hi = slice_edges(self._slice_coords)
+        ks = np.asarray(self._thickness, dtype=np.int64)
+        return dict(layer=ks, thickness=hi[ks] - lo[0])
+
+    def _layered(self, shape):
+        """host result of `shape`, with the thickness axis last when there is one"""
+        return np.zeros(shape + ((len(self._thickness),) if self._thickness is not None else ()), dtype=np.float64)
+
+    def _position_batch(self, acc, p0, real, n, want_det):
+        """run_diffraction() with a thickness series, one probe batch: the patterns of every entry, summed over the n frames, into
+        rows p0 .. of acc (P, mx, my, L) -> the detector signals (L, real, n, D) of the same fetch, or None"""
+        det, _, pat = self._layer_signals(real, n)
+        acc[p0:p0 + real] += np.moveaxis(pat, 0, -1)
+        return det
+
+    def _pacbed_batch(self, acc, p0, real, n, want_det):
+        """The same with patterns="pacbed", acc (mx, my, L): the device sums the patterns over the probes of a frame batch -- reset
+        before its first probe batch, one add per probe batch, one download after its last -- and the host adds the frame batches.
+        The fetch is made for the detector signals only.  (The exit wave alone has no accumulator: its patterns are summed here.)"""
+        eng = self._engine
+        if len(self._thickness) == 1:
+            det, _, pat = self._layer_signals(real, n)
+            acc += np.moveaxis(pat.sum(axis=1), 0, -1)
+            return det
+        if p0 == 0:
+            eng.layer_pacbed_reset()
+        eng.layer_pacbed_add(real)
+        if p0 + real == self.n_probes:
+            acc += np.moveaxis(eng.layer_pacbed(), 0, -1)
+        return self._layer_signals(real, n)[0] if want_det else None
+
+    def _layer_signals(self, real, n):
+        """(det, polar, patterns) of the slice loop that just ran n frames, for the first `real` probes and every thickness entry:
+        (L, real, n, D), (L, real, n, n_bins), (L, real, mx, my), None for what the run does not form (and for the patterns of a
+        pacbed run, which stay on the device).  One fetch; the exit wave alone (L = 1) has no tap and takes the plain reductions."""
+        eng = self._engine
+        if len(self._thickness) > 1:
+            return eng.layer_fetch(n, B=real)
+        return (None if self._detectors is None else eng.detect(0, n, B=real)[None],
+                None if self._polar is None else eng.polar_detect(0, n, B=real)[None],
+                None if self._diffraction is None else eng.diffract(0, n, B=real, bin=self._diffraction.bin)[None])
 
     def run_diffraction(self):
         """Frame-averaged diffraction pattern of every probe position (4D-STEM / CBED): the loop of run_detectors(); msl_diffract
@@ -800,10 +902,16 @@ class MultisliceCalculator:
         t0 = time.time()
         P, T = self.n_probes, self.n_frames
         bx, by = self._diffraction.bin
-        acc = np.zeros((P, eng.wx // bx, eng.wy // by), dtype=np.float64)
-        signals = None if self._detectors is None else np.zeros((P, T, len(self._detectors)), dtype=np.float64)
+        pacbed = self._thickness is not None and self._thickness_arg.patterns == "pacbed"
+        acc = self._layered((eng.wx // bx, eng.wy // by) if pacbed else (P, eng.wx // bx, eng.wy // by))
+        signals = None if self._detectors is None else self._layered((P, T, len(self._detectors)))
 
         def reduce_batch(p0, real, s0, n):
+            if self._thickness is not None:
+                det = (self._pacbed_batch if pacbed else self._position_batch)(acc, p0, real, n, signals is not None)
+                if signals is not None:
+                    signals[p0:p0 + real, s0:s0 + n] = np.moveaxis(det, 0, -1)
+                return
             acc[p0:p0 + real] += eng.diffract(0, n, B=real, bin=(bx, by))
             if signals is not None:
                 signals[p0:p0 + real, s0:s0 + n] = eng.detect(0, n, B=real)
@@ -818,13 +926,14 @@ class MultisliceCalculator:
             self._prism_loop(reduce_batch)
         else:
             self._probe_batch_loop(reduce_batch)
-        acc /= T
+        acc /= (P * T) if pacbed else T
         self.elapsed = time.time() - t0
         self.frames_computed, self.frames_cached = T, 0
         kxs, kys = self._k_axes()
         return DiffractionData(intensity=acc, kxs=_as_tensor(bin_centres(kxs, bx)), kys=_as_tensor(bin_centres(kys, by)), bin=(bx, by),
                                n_frames=T, probe_positions=self.probe_positions, probe=self.base_probe,
-                               stem=None if signals is None else self._stem_data(signals), elastic=elastic)
+                               stem=None if signals is None else self._stem_data(signals), elastic=elastic,
+                               patterns="pacbed" if pacbed else "position", **self._layer_fields())
 
     def run_images(self):
         """Frame-averaged images behind the objective lens (HRTEM, focal series), for every probe: probe batches outside, frame
@@ -929,9 +1038,12 @@ class MultisliceCalculator:
         eng = self._engine
         t0 = time.time()
         P, T, D = self.n_probes, self.n_frames, len(self._detectors)
-        signals = np.zeros((P, T, D), dtype=np.float64)
+        signals = self._layered((P, T, D))
 
         def reduce_batch(p0, real, s0, n):
+            if self._thickness is not None:
+                signals[p0:p0 + real, s0:s0 + n] = np.moveaxis(self._layer_signals(real, n)[0], 0, -1)
+                return
             signals[p0:p0 + real, s0:s0 + n] = eng.detect(0, n, B=real)
         if self._prism is not None:
             self._prism_loop(reduce_batch)
@@ -958,10 +1070,20 @@ class MultisliceCalculator:
         eng, pol = self._engine, self._polar
         t0 = time.time()
         P, T, R, A = self.n_probes, self.n_frames, pol.n_rings, pol.n_azimuthal
-        acc = np.zeros((P, T, R * A) if pol.per_frame else (P, R * A), dtype=np.float64)
-        signals = None if self._detectors is None else np.zeros((P, T, len(self._detectors)), dtype=np.float64)
+        acc = self._layered((P, T, R * A) if pol.per_frame else (P, R * A))
+        signals = None if self._detectors is None else self._layered((P, T, len(self._detectors)))
 
         def reduce_batch(p0, real, s0, n):
+            if self._thickness is not None:
+                det, got, _ = self._layer_signals(real, n)
+                got = np.moveaxis(got, 0, -1)                   # (real, n, R * A, L)
+                if pol.per_frame:
+                    acc[p0:p0 + real, s0:s0 + n] = got
+                else:
+                    acc[p0:p0 + real] += got.sum(axis=1)
+                if signals is not None:
+                    signals[p0:p0 + real, s0:s0 + n] = np.moveaxis(det, 0, -1)
+                return
             got = eng.polar_detect(0, n, B=real)
             if pol.per_frame:
                 acc[p0:p0 + real, s0:s0 + n] = got
@@ -978,9 +1100,14 @@ class MultisliceCalculator:
         self.elapsed = time.time() - t0
         self.frames_computed, self.frames_cached = T, 0
         kxs, kys = self._k_axes()
-        return PolarData(signals=acc.reshape(acc.shape[:-1] + (R, A)), polar=pol, counts=self._polar_counts.reshape(R, A), edges=pol.edges,
+        if self._thickness is not None:
+            acc = acc.reshape(acc.shape[:-2] + (R, A, acc.shape[-1]))
+        else:
+            acc = acc.reshape(acc.shape[:-1] + (R, A))
+        return PolarData(signals=acc, polar=pol, counts=self._polar_counts.reshape(R, A), edges=pol.edges,
                          probe_positions=self.probe_positions, time=np.arange(T) * self.trajectory.timestep, kxs=_as_tensor(kxs),
-                         kys=_as_tensor(kys), probe=self.base_probe, stem=None if signals is None else self._stem_data(signals))
+                         kys=_as_tensor(kys), probe=self.base_probe, stem=None if signals is None else self._stem_data(signals),
+                         **self._layer_fields())
 
     def _check_layers(self, n_slices, world):
         """the `layers` argument -> sorted unique slice indices with n_slices - 1 last (before any device work)"""

@@ -25,6 +25,7 @@
 #include "tacaw_launch.h"
 #include "tacaw_welch.h"
 #include "layer_tap.h"
+#include "layer_reduce.h"
 #include "detect.h"
 #include "polar.h"
 #include "spectrum_detect.h"
@@ -182,6 +183,16 @@ struct msl_handle {
     DevBuf<float2> layers;
     float2* wf = nullptr;
     DevBuf<float2> tap, tap_cx, tap_cy;
+    // thickness series of the probe-batch modes (msl_set_layer_reduce, layer_reduce.h): the taps of layer_slices go to the ONE
+    // block lr_block, which is reduced at once into layer l's part of the float64 staging lr_stage (layout lr_lay); `layers`
+    // stays the single exit block.  lr_what: MSL_LR_* bits; lr_bx, lr_by: the bin of the patterns; lr_slot / lr_count: the frame
+    // slots of the last sequence, whose results the staging holds (lr_count = 0: none)
+    bool lr_on = false;
+    unsigned lr_what = 0;
+    int lr_bx = 1, lr_by = 1, lr_slot = 0, lr_count = 0;
+    LrLayout lr_lay;
+    DevBuf<float2> lr_block;
+    DevBuf<double> lr_stage;
     // STEM detectors (msl_set_detectors): membership bits per stored pixel, the stored k axes, the signal of every detector
     DevBuf<uint16_t> det_mask;
     DevBuf<float> det_kx, det_ky;
@@ -810,8 +821,20 @@ int epilogue_x_pass(msl_handle* h, int slot, int groups = 1, const float2* src =
 // conj(P_y) when d = y), and runs the exit epilogue into block `layer_block[k]` (with conj(P_x) after the x-FFT when d = x).
 // The passes of the loop are untouched.  axis: 0 = the pass ran along y, 1 = along x, 2 = two-pass loop.
 constexpr int TAP_MAX_LAUNCHES = 4;                  // gather, row FFT, column epilogue, binning
+constexpr int LR_MAX_LAUNCHES = 4;                   // layer reductions: detector tiles, their finish, polar bins, patterns
 
 int n_taps(const msl_handle* h) { return (int)h->layer_slices.size(); }
+
+// blocks of the resident result: the reduce mode taps into a block of its own and keeps the exit block only
+int n_result_layers(const msl_handle* h) { return h->lr_on ? 1 : n_taps(h) + 1; }
+
+// timed launches the taps add to a fused slice loop; in the reduce mode also the reductions of every layer and of the exit
+int tap_launches(const msl_handle* h) {
+    return TAP_MAX_LAUNCHES * n_taps(h) + (h->lr_on ? LR_MAX_LAUNCHES * (n_taps(h) + 1) : 0);
+}
+
+// the reductions of layer l over the frame slots [slot, slot + count) of `block`, queued on the stream (defined with the reductions)
+int layer_reduce_queue(msl_handle* h, int l, const float2* block, int slot, int count);
 
 size_t layer_block_elems(const msl_handle* h) { return h->wpitch * (size_t)h->cfg.n_probes * h->cfg.n_frames; }
 
@@ -844,12 +867,21 @@ int layer_tap(msl_handle* h, int k, int slot, int groups, const float2* buf, boo
         }
         if (rc) return rc;
     }
-    if ((rc = epilogue_x_pass(h, slot, groups, h->tap, h->layers + (size_t)h->layer_block[k] * layer_block_elems(h), axis == 1 ? h->tap_cx : nullptr)))
+    float2* dst = h->lr_on ? h->lr_block.p : h->layers + (size_t)h->layer_block[k] * layer_block_elems(h);
+    if ((rc = epilogue_x_pass(h, slot, groups, h->tap, dst, axis == 1 ? h->tap_cx : nullptr)))
         return rc;
     // read S, write + read the copy (twice with the row FFT), write the layer's spectra
     const uint64_t img = (uint64_t)c.nx * c.ny * 8ull;
     h->ctr.algorithmic_bytes += (uint64_t)P * (img * (axis == 2 ? 3 : 5) + (uint64_t)h->wpix * 8ull);
     return MSL_OK;
+}
+
+// what a fused slice loop does after the pass of slice k: the tap, and in the reduce mode the layer's reductions right behind it --
+// stream order lets the next tap overwrite the block
+int tap_step(msl_handle* h, int k, int slot, int groups, const float2* buf, bool transposed, int order, int rp, int axis) {
+    int rc = layer_tap(h, k, slot, groups, buf, transposed, order, rp, axis);
+    if (rc || !h->lr_on || slot < 0 || h->layer_block[k] < 0) return rc;
+    return layer_reduce_queue(h, h->layer_block[k], h->lr_block, slot, groups);
 }
 
 // only the 256 / 512 / 1024-point kernels read and write the interleaved line order (16-byte loads in the reader) between two passes
@@ -1065,7 +1097,7 @@ int slice_loop_onepass_b(msl_handle* h, int fused_slot, int groups, int first_gr
     const long long isA = (long long)c.nx * h->pitch, isB = (long long)c.ny * h->pitchT;
     const bool fused = fused_slot >= 0;
     int rc;
-    if ((rc = begin_timed(h, nz + 4 + (fused ? TAP_MAX_LAUNCHES * n_taps(h) : 0)))) return rc;
+    if ((rc = begin_timed(h, nz + 4 + (fused ? tap_launches(h) : 0)))) return rc;
     for (int k = 0; k < nz; ++k) {
         RowTJob j{};
         j.flags = (k > 0 ? P2_PRE_A : 0) | (k < nz - 1 ? P2_POST_A : 0);
@@ -1094,7 +1126,7 @@ int slice_loop_onepass_b(msl_handle* h, int fused_slot, int groups, int first_gr
         if (k < nz - 1) {
             int rp = 0;
             const int order = tap_order((k & 1) ? h->opx : h->opy, j.flags, j.perm_shift, &rp);
-            if ((rc = layer_tap(h, k, fused_slot, groups, (k & 1) ? h->psi : h->psiT, !(k & 1), order, rp, (k & 1) ? 1 : 0))) return rc;
+            if ((rc = tap_step(h, k, fused_slot, groups, (k & 1) ? h->psi : h->psiT, !(k & 1), order, rp, (k & 1) ? 1 : 0))) return rc;
         }
     }
     if (nz & 1) {
@@ -1143,7 +1175,7 @@ int slice_loop_onepass(msl_handle* h, int fused_slot, int groups, int first_grou
     int rc;
     if (nz == 1)
         HIPCHK(h, hipMemcpyAsync(h->psi, h->psi0, (size_t)P * isA * sizeof(float2), hipMemcpyDeviceToDevice, h->stream));
-    if ((rc = begin_timed(h, nz + 2 + (fused ? TAP_MAX_LAUNCHES * n_taps(h) : 0)))) return rc;
+    if ((rc = begin_timed(h, nz + 2 + (fused ? tap_launches(h) : 0)))) return rc;
     for (int k = 0; k < nz; ++k) {
         const bool last = (k == nz - 1);
         int flags = (k > 0 ? P2_PRE_A : 0) | (!last ? P2_POST_A : 0) | ((last && fused) ? P2_POST_F : 0);
@@ -1178,7 +1210,7 @@ int slice_loop_onepass(msl_handle* h, int fused_slot, int groups, int first_grou
         }
         if (rc) return rc;
         const int order = (j.flags & P2_OUT_PAIRED) ? TAP_INTERLEAVED : TAP_NATURAL;
-        if ((rc = layer_tap(h, k, fused_slot, groups, along_y ? h->psiT : h->psi, along_y, order, 8 << j.perm_shift, along_y ? 0 : 1))) return rc;
+        if ((rc = tap_step(h, k, fused_slot, groups, along_y ? h->psiT : h->psi, along_y, order, 8 << j.perm_shift, along_y ? 0 : 1))) return rc;
     }
     if (fused && (rc = epilogue_x_pass(h, fused_slot, groups))) return rc;
     count_slice_loop(h, P, groups, fused, 16);
@@ -1208,7 +1240,7 @@ int slice_loop(msl_handle* h, int fused_slot, int groups, int first_group) {
     const size_t toff = (size_t)first_group * c.nz * npix;
     HIPCHK(h, hipMemcpyAsync(h->psi, h->psi0, (size_t)P * c.nx * h->pitch * sizeof(float2), hipMemcpyDeviceToDevice, h->stream));
     const bool fused = fused_slot >= 0;
-    int rc = begin_timed(h, 2 * nz + 2 + (fused ? TAP_MAX_LAUNCHES * n_taps(h) : 0));
+    int rc = begin_timed(h, 2 * nz + 2 + (fused ? tap_launches(h) : 0));
     if (rc) return rc;
     for (int z = 0; z < nz; ++z) {
         const bool last = (z == nz - 1);
@@ -1227,7 +1259,7 @@ int slice_loop(msl_handle* h, int fused_slot, int groups, int first_group) {
             else if (fused) { r.fft2 = +1; }
             if ((rc = launch_lines(h, h->plan_y, r, K_ROW))) return rc;
         }
-        if (!last && (rc = layer_tap(h, z, fused_slot, groups, h->psi, false, TAP_NATURAL, 8, 2))) return rc;
+        if (!last && (rc = tap_step(h, z, fused_slot, groups, h->psi, false, TAP_NATURAL, 8, 2))) return rc;
         if (!last) {
             if (h->Rx) {
                 ColJob k = col_job(h, h->psi, h->psi, P, h->pitch, h->pitch);
@@ -2563,10 +2595,16 @@ static int run_loop(msl_handle* h, int slot, int groups, int first_group) {
     if (!h->have_probes) return fail(h, MSL_ERR_STATE, "propagate: no probes (msl_set_probes / msl_upload_probes)");
     if (!h->have_potential) return fail(h, MSL_ERR_STATE, "propagate: no potential (msl_build_potential / msl_upload_potential)");
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    if (!h->cfg.launch_timing) return slice_loop(h, slot, groups, first_group);         // queued; msl_synchronize / msl_download wait for it
-    EventPair timer;
+    // the reduce mode: the exit block is the last layer, reduced behind the epilogue like every tapped one
+    const bool reduce = h->lr_on && slot >= 0;
     int rc;
+    if (!h->cfg.launch_timing) {                                                         // queued; msl_synchronize / msl_download wait for it
+        if ((rc = slice_loop(h, slot, groups, first_group)) || !reduce) return rc;
+        return layer_reduce_queue(h, n_taps(h), h->wf, slot, groups);
+    }
+    EventPair timer;
     if ((rc = timer.begin(h)) || (rc = slice_loop(h, slot, groups, first_group))) return rc;
+    if (reduce && (rc = layer_reduce_queue(h, n_taps(h), h->wf, slot, groups))) return rc;
     return timer.end(h, &h->ctr.ms_propagate);
 }
 
@@ -2909,7 +2947,7 @@ size_t msl_buffer_bytes(const msl_handle* h, msl_buffer what) {
         case MSL_BUF_STREAM_S1: return (h->st_open && h->st_s1) ? h->wpix * c.n_probes * 16 : 0;
         case MSL_BUF_STREAM_S2: return (h->st_open && h->st_s2) ? h->wpix * c.n_probes * 8 : 0;
         case MSL_BUF_STREAM_REF: return (h->st_open && h->st_have_ref) ? h->wpix * c.n_probes * 8 : 0;
-        case MSL_BUF_LAYERS: return h->wf ? (n_taps(h) + 1) * layer_block_elems(h) * 8 : 0;
+        case MSL_BUF_LAYERS: return h->wf ? n_result_layers(h) * layer_block_elems(h) * 8 : 0;
         case MSL_BUF_SMATRIX: return h->sm_built ? npix * (size_t)h->sm_Bm * 8 : 0;
     }
     return 0;
@@ -3090,6 +3128,10 @@ int msl_adf(msl_handle* h, const void* d_src_c64, int64_t B, int64_t T, int64_t 
 int msl_set_detectors(msl_handle* h, int32_t n, const uint16_t* member_K, const int32_t* signal_n, const float* kx_wx, const float* ky_wy) {
     if (!h || !member_K || !signal_n || !kx_wx || !ky_wy) return fail(h, MSL_ERR_INVALID, "msl_set_detectors: null argument");
     if (n < 1 || n > DET_MAX) return fail(h, MSL_ERR_INVALID, "msl_set_detectors: %d detectors outside [1,%d]", n, DET_MAX);
+    // the staging of the layer reductions has rows of the detector count it was set up with: other masks are fine, another count is not
+    if (h->lr_on && (h->lr_what & LR_DETECT) && n != (int)h->lr_lay.D)
+        return fail(h, MSL_ERR_STATE, "msl_set_detectors: %d detectors while the layer reductions are set up for %d (clear msl_set_layer_reduce first)",
+                    n, (int)h->lr_lay.D);
     uint32_t amp = 0, cx = 0, cy = 0;
     for (int d = 0; d < n; ++d) {
         switch (signal_n[d]) {
@@ -3148,8 +3190,9 @@ static DetTiling det_tiling(int64_t rows, int64_t K, int n) {
 }
 
 // the preconditions that msl_detect and msl_spectrum_detect share, then the tiling of the `count` rows per probe from t0 on,
-// with its two pieces of h->scratch
-static int plan_detect(msl_handle* h, const char* who, const Rows& r, const char* what, int32_t t0, int32_t count, DetTiling* t) {
+// with its two pieces of h->scratch; d_dst: a device destination of the (rows, n) result instead of the second piece
+static int plan_detect(msl_handle* h, const char* who, const Rows& r, const char* what, int32_t t0, int32_t count, DetTiling* t,
+                       double* d_dst = nullptr) {
     if ((size_t)r.K != h->det_K) return fail(h, MSL_ERR_INVALID, "%s: rows of %lld pixels, the detectors cover %zu", who, (long long)r.K, h->det_K);
     int rc = check_slots(h, who, what, t0, count, r.R);
     if (rc) return rc;
@@ -3157,21 +3200,34 @@ static int plan_detect(msl_handle* h, const char* who, const Rows& r, const char
     *t = det_tiling(r.B * count, r.K, h->det_n);
     if (t->n_tiles > 0x7fffffffLL) return fail(h, MSL_ERR_UNSUPPORTED, "%s: rows too long", who);
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    if ((rc = h->scratch.reserve(h, t->part_bytes + t->out_bytes))) return rc;
+    if ((rc = h->scratch.reserve(h, t->part_bytes + (d_dst ? 0 : t->out_bytes)))) return rc;
     t->d_part = (float*)h->scratch.p;
-    t->d_out = (double*)(h->scratch + t->part_bytes);
+    t->d_out = d_dst ? d_dst : (double*)(h->scratch + t->part_bytes);
     return MSL_OK;
 }
 
-// after the tile kernel: the sums over the tiles, and the result to the host
-static int detect_finish(msl_handle* h, const DetTiling& t, double* out) {
+// the tile kernel of msl_detect over the planned rows, queued
+static int detect_tiles(msl_handle* h, const Rows& r, int32_t t0, int32_t count, const DetTiling& t) {
+    const int mode = h->det_amp == 0 ? 0 : (h->det_amp == (1u << t.n) - 1u ? 1 : 2);
+    const bool vec = (r.ld % 2 == 0) && (((uintptr_t)r.p & 15) == 0);
+    with_int<4, 8, 16>(t.ND, [&](auto nd) { with_int<0, 1, 2>(mode, [&](auto m) { with_bool(vec, [&](auto v) {
+        hipLaunchKernelGGL((detect_tile_kernel<decltype(nd)::value, decltype(m)::value, decltype(v)::value>), t.grid(), dim3(256), 0, h->stream,
+                           (const float2*)r.p, (long long)r.R, (long long)t0, (long long)count, (long long)r.ld, (long long)r.K, (long long)t.rows, (int)t.per,
+                           h->det_mask.p, h->det_kx.p, h->det_ky.p, h->det_wy, h->det_amp, h->det_cx, h->det_cy, t.d_part);
+    }); }); });
+    HIPCHK(h, hipGetLastError());
+    return MSL_OK;
+}
+
+// after the tile kernel: the sums over the tiles into t.d_out, queued
+static int detect_finish(msl_handle* h, const DetTiling& t) {
     HIPCHK(h, hipGetLastError());
     with_int<4, 8, 16>(t.ND, [&](auto nd) {
         hipLaunchKernelGGL(detect_finish_kernel<decltype(nd)::value>, dim3((unsigned)t.rows), dim3(256), 0, h->stream, t.d_part, (long long)t.n_tiles, t.n,
                            t.d_out);
     });
     HIPCHK(h, hipGetLastError());
-    return download_sync(h, out, t.d_out, t.out_bytes);
+    return MSL_OK;
 }
 
 int msl_detect(msl_handle* h, const void* d_src_c64, int64_t B, int64_t T, int64_t K, int64_t ld, int32_t t0, int32_t count, double* out) {
@@ -3180,15 +3236,9 @@ int msl_detect(msl_handle* h, const void* d_src_c64, int64_t B, int64_t T, int64
     Rows r{d_src_c64, B, T, K, ld};
     DetTiling t;
     int rc;
-    if ((rc = resolve_rows(h, "msl_detect", SRC_WAVEFUNCTION | SRC_FIRST_B, &r)) || (rc = plan_detect(h, "msl_detect", r, "frame slots", t0, count, &t))) return rc;
-    const int mode = h->det_amp == 0 ? 0 : (h->det_amp == (1u << t.n) - 1u ? 1 : 2);
-    const bool vec = (r.ld % 2 == 0) && (((uintptr_t)r.p & 15) == 0);
-    with_int<4, 8, 16>(t.ND, [&](auto nd) { with_int<0, 1, 2>(mode, [&](auto m) { with_bool(vec, [&](auto v) {
-        hipLaunchKernelGGL((detect_tile_kernel<decltype(nd)::value, decltype(m)::value, decltype(v)::value>), t.grid(), dim3(256), 0, h->stream,
-                           (const float2*)r.p, (long long)r.R, (long long)t0, (long long)count, (long long)r.ld, (long long)r.K, (long long)t.rows, (int)t.per,
-                           h->det_mask.p, h->det_kx.p, h->det_ky.p, h->det_wy, h->det_amp, h->det_cx, h->det_cy, t.d_part);
-    }); }); });
-    return detect_finish(h, t, out);
+    if ((rc = resolve_rows(h, "msl_detect", SRC_WAVEFUNCTION | SRC_FIRST_B, &r)) || (rc = plan_detect(h, "msl_detect", r, "frame slots", t0, count, &t)) ||
+        (rc = detect_tiles(h, r, t0, count, t)) || (rc = detect_finish(h, t))) return rc;
+    return download_sync(h, out, t.d_out, t.out_bytes);
 }
 
 // ---- polar detector (polar.h) -----------------------------------------------------------------------------
@@ -3214,6 +3264,9 @@ int msl_set_polar(msl_handle* h, int32_t n_bins, const uint16_t* bin_K) {
     int rc = check_polar_map(h, "msl_set_polar", bin_K, (int64_t)K, n_bins);
     if (rc) return rc;
     if (K > 0xffffffffull) return fail(h, MSL_ERR_UNSUPPORTED, "msl_set_polar: more than 2^32 stored pixels");
+    if (h->lr_on && (h->lr_what & LR_POLAR) && n_bins != (int)h->lr_lay.n_bins)     // (as msl_set_detectors: the staging has rows of n_bins)
+        return fail(h, MSL_ERR_STATE, "msl_set_polar: %d bins while the layer reductions are set up for %d (clear msl_set_layer_reduce first)", n_bins,
+                    (int)h->lr_lay.n_bins);
     h->pol_bins = 0;
     std::vector<uint32_t> order(std::max<size_t>(K, 1));
     std::vector<int64_t> seg((size_t)n_bins + 1);
@@ -3228,12 +3281,10 @@ int msl_set_polar(msl_handle* h, int32_t n_bins, const uint16_t* bin_K) {
     return MSL_OK;
 }
 
-int msl_polar_detect(msl_handle* h, const void* d_src_c64, int64_t B, int64_t T, int64_t K, int64_t ld, int32_t t0, int32_t count, double* out) {
-    if (!h || !out) return fail(h, MSL_ERR_INVALID, "msl_polar_detect: null argument");
-    if (h->pol_bins == 0) return fail(h, MSL_ERR_STATE, "msl_polar_detect: no bin map (call msl_set_polar)");
-    Rows r{d_src_c64, B, T, K, ld};
+// the gather of msl_polar_detect over resolved rows, queued: the (rows, n_bins) float64 result goes to d_dst, or with d_dst == NULL
+// to h->scratch; *d_res / *res_bytes name it
+static int polar_launch(msl_handle* h, const Rows& r, int32_t t0, int32_t count, double* d_dst, double** d_res, size_t* res_bytes) {
     int rc;
-    if ((rc = resolve_rows(h, "msl_polar_detect", SRC_WAVEFUNCTION | SRC_FIRST_B, &r))) return rc;
     if ((size_t)r.K != h->pol_K) return fail(h, MSL_ERR_INVALID, "msl_polar_detect: rows of %lld pixels, the bin map covers %zu", (long long)r.K, h->pol_K);
     if ((rc = check_slots(h, "msl_polar_detect", "frame slots", t0, count, r.R))) return rc;
     const int64_t rows = r.B * count, n_bins = h->pol_bins;
@@ -3246,12 +3297,24 @@ int msl_polar_detect(msl_handle* h, const void* d_src_c64, int64_t B, int64_t T,
     const int64_t row_blocks = (rows + per - 1) / per;
     const size_t out_bytes = (size_t)rows * n_bins * sizeof(double);
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    if ((rc = h->scratch.reserve(h, out_bytes))) return rc;
-    double* d_out = (double*)h->scratch.p;
+    if (!d_dst && (rc = h->scratch.reserve(h, out_bytes))) return rc;
+    double* d_out = d_dst ? d_dst : (double*)h->scratch.p;
     hipLaunchKernelGGL(polar_gather_kernel, dim3((unsigned)(row_blocks * bin_groups)), dim3(64 * POLAR_WAVES), 0, h->stream, (const float2*)r.p,
                        (long long)r.R, (long long)t0, (unsigned)count, (long long)r.ld, (long long)rows, (int)per, (int)n_bins, (unsigned)bin_groups,
                        h->pol_order.p, h->pol_seg.p, d_out);
     HIPCHK(h, hipGetLastError());
+    *d_res = d_out; *res_bytes = out_bytes;
+    return MSL_OK;
+}
+
+int msl_polar_detect(msl_handle* h, const void* d_src_c64, int64_t B, int64_t T, int64_t K, int64_t ld, int32_t t0, int32_t count, double* out) {
+    if (!h || !out) return fail(h, MSL_ERR_INVALID, "msl_polar_detect: null argument");
+    if (h->pol_bins == 0) return fail(h, MSL_ERR_STATE, "msl_polar_detect: no bin map (call msl_set_polar)");
+    Rows r{d_src_c64, B, T, K, ld};
+    int rc;
+    double* d_out = nullptr;
+    size_t out_bytes = 0;
+    if ((rc = resolve_rows(h, "msl_polar_detect", SRC_WAVEFUNCTION | SRC_FIRST_B, &r)) || (rc = polar_launch(h, r, t0, count, nullptr, &d_out, &out_bytes))) return rc;
     return download_sync(h, out, d_out, out_bytes);
 }
 
@@ -3275,19 +3338,16 @@ int msl_spectrum_detect(msl_handle* h, const void* d_src_f32, int64_t B, int64_t
                            (long long)r.R, (long long)f0, (long long)count, (long long)r.ld, (long long)r.K, (long long)t.rows, (int)t.per, h->det_mask.p,
                            t.d_part);
     }); });
-    return detect_finish(h, t, out);
+    if ((rc = detect_finish(h, t))) return rc;
+    return download_sync(h, out, t.d_out, t.out_bytes);
 }
 
 // ---- diffraction patterns (diffract.h) --------------------------------------------------------------------
-int msl_diffract(msl_handle* h, const void* d_src_c64, int64_t B, int64_t T, int64_t K, int64_t ld, int32_t t0, int32_t count, int32_t wx, int32_t wy,
-                 int32_t bx, int32_t by, double* out) {
-    if (!h || !out) return fail(h, MSL_ERR_INVALID, "msl_diffract: null argument");
-    const bool resident = !d_src_c64;
-    Rows r{d_src_c64, B, T, K, ld};
-    int rc = resolve_rows(h, "msl_diffract", SRC_WAVEFUNCTION | SRC_FIRST_B, &r);
-    if (rc) return rc;
-    if (resident && (wx != h->wx / h->bx || wy != h->wy / h->by))
-        return fail(h, MSL_ERR_INVALID, "msl_diffract: window %d x %d, the handle stores %d x %d", wx, wy, h->wx / h->bx, h->wy / h->by);
+// the pattern pass of msl_diffract over resolved rows, queued as one timed launch: the (B, mx, my) float64 result goes to d_dst, or
+// with d_dst == NULL to h->diff_out; *d_res / *res_bytes name it
+static int diffract_launch(msl_handle* h, const Rows& r, int32_t t0, int32_t count, int32_t wx, int32_t wy, int32_t bx, int32_t by, double* d_dst,
+                           double** d_res, size_t* res_bytes) {
+    int rc;
     if ((rc = check_window_bin(h, "msl_diffract", wx, wy, bx, by))) return rc;
     if ((int64_t)wx * wy != r.K) return fail(h, MSL_ERR_INVALID, "msl_diffract: window %d x %d over rows of %lld pixels", wx, wy, (long long)r.K);
     if ((rc = check_slots(h, "msl_diffract", "frame slots", t0, count, r.R))) return rc;
@@ -3300,7 +3360,8 @@ int msl_diffract(msl_handle* h, const void* d_src_c64, int64_t B, int64_t T, int
     if (lds > 64u * 1024u) return fail(h, MSL_ERR_UNSUPPORTED, "msl_diffract: bin %d of rows of %d pixels needs %zu bytes of LDS", by, wy, lds);
     HIPCHK(h, hipSetDevice(h->cfg.device));
     const size_t n_out = (size_t)strips * my;
-    if ((rc = h->diff_out.reserve(h, n_out))) return rc;
+    if (!d_dst && (rc = h->diff_out.reserve(h, n_out))) return rc;
+    double* d_out = d_dst ? d_dst : h->diff_out.p;
     // 16-byte loads need every row to start on 16 bytes: base, image pitch and row length even in pixels
     const bool vec = (r.ld % 2 == 0) && (wy % 2 == 0) && (((uintptr_t)r.p & 15) == 0);
     const int cols = vec ? (wy + 1) / 2 : wy;
@@ -3311,16 +3372,31 @@ int msl_diffract(msl_handle* h, const void* d_src_c64, int64_t B, int64_t T, int
     per = std::max<int64_t>(1, std::min<int64_t>(per, strips / 4096));
     per = std::max<int64_t>(per, (strips + 0x7ffffffeLL) / 0x7fffffffLL);
     const unsigned grid = (unsigned)((strips + per - 1) / per);
-    if ((rc = begin_timed(h, 1))) return rc;
     with_int<DIFF_DIRECT, DIFF_SHFL, DIFF_LDS>(mode, [&](auto m) { with_bool(vec, [&](auto v) {
         hipLaunchKernelGGL((diffract_kernel<decltype(m)::value, decltype(v)::value>), dim3(grid), dim3(threads), lds, h->stream, (const float2*)r.p,
                            (long long)r.R, (long long)t0, (int)count, (long long)r.ld, (int)wx, (int)wy, (int)bx, (int)by, (long long)strips, (int)per,
-                           h->diff_out.p);
+                           d_out);
     }); });
     HIPCHK(h, hipGetLastError());
     if ((rc = mark_launch(h, K_OTHER))) return rc;
     h->ctr.algorithmic_bytes += 8ull * (uint64_t)r.K * (uint64_t)r.B * (uint64_t)count;
-    return download_sync(h, out, h->diff_out, n_out * sizeof(double));
+    *d_res = d_out; *res_bytes = n_out * sizeof(double);
+    return MSL_OK;
+}
+
+int msl_diffract(msl_handle* h, const void* d_src_c64, int64_t B, int64_t T, int64_t K, int64_t ld, int32_t t0, int32_t count, int32_t wx, int32_t wy,
+                 int32_t bx, int32_t by, double* out) {
+    if (!h || !out) return fail(h, MSL_ERR_INVALID, "msl_diffract: null argument");
+    const bool resident = !d_src_c64;
+    Rows r{d_src_c64, B, T, K, ld};
+    int rc = resolve_rows(h, "msl_diffract", SRC_WAVEFUNCTION | SRC_FIRST_B, &r);
+    if (rc) return rc;
+    if (resident && (wx != h->wx / h->bx || wy != h->wy / h->by))
+        return fail(h, MSL_ERR_INVALID, "msl_diffract: window %d x %d, the handle stores %d x %d", wx, wy, h->wx / h->bx, h->wy / h->by);
+    double* d_out = nullptr;
+    size_t out_bytes = 0;
+    if ((rc = begin_timed(h, 1)) || (rc = diffract_launch(h, r, t0, count, wx, wy, bx, by, nullptr, &d_out, &out_bytes))) return rc;
+    return download_sync(h, out, d_out, out_bytes);
 }
 
 // ---- coherent frame sums (coherent.h) ---------------------------------------------------------------------
@@ -3672,6 +3748,7 @@ int msl_set_layers(msl_handle* h, const int32_t* slices, int32_t n) {
     }
     if (!h->wf) return fail(h, MSL_ERR_STATE, "msl_set_layers: handle created with n_frames == 0");
     if (h->st_open) return fail(h, MSL_ERR_STATE, "msl_set_layers: a TACAW stream is open");
+    if (h->lr_on) return fail(h, MSL_ERR_STATE, "msl_set_layers: the layers are reduced on the device (msl_set_layer_reduce): clear that mode first");
     HIPCHK(h, hipSetDevice(c.device));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     const size_t block = layer_block_elems(h);
@@ -3713,7 +3790,7 @@ int msl_download_layers_c128(msl_handle* h, int32_t n_frames_used, void* dst, si
     const msl_config& c = h->cfg;
     if (!h->wf) return fail(h, MSL_ERR_STATE, "msl_download_layers_c128: no wavefunction buffer");
     if (n_frames_used < 1 || n_frames_used > c.n_frames) return fail(h, MSL_ERR_INVALID, "msl_download_layers_c128: %d of %d frames", n_frames_used, c.n_frames);
-    const int L = n_taps(h) + 1;
+    const int L = n_result_layers(h);
     const size_t per_probe = (size_t)n_frames_used * h->wpix;             // dense (T_used, wx*wy) offsets of a probe, L values each
     if (bytes != (size_t)c.n_probes * per_probe * L * sizeof(double2))
         return fail(h, MSL_ERR_INVALID, "msl_download_layers_c128: dst holds %zu bytes, the result has %zu", bytes, (size_t)c.n_probes * per_probe * L * sizeof(double2));
@@ -3743,7 +3820,7 @@ int msl_download_layers_c128(msl_handle* h, int32_t n_frames_used, void* dst, si
 int msl_tacaw_layer(msl_handle* h, int32_t layer) {
     if (!h) return fail(h, MSL_ERR_INVALID, "null handle");
     if (!h->wf) return fail(h, MSL_ERR_STATE, "msl_tacaw_layer: no wavefunction buffer");
-    const int L = n_taps(h) + 1;
+    const int L = n_result_layers(h);
     if (layer < 0 || layer >= L) return fail(h, MSL_ERR_INVALID, "msl_tacaw_layer: layer %d outside [0, %d)", layer, L);
     HIPCHK(h, hipSetDevice(h->cfg.device));
     return tacaw_resident(h, h->layers + (size_t)layer * layer_block_elems(h));         // (the last block is wf)
@@ -3752,10 +3829,189 @@ int msl_tacaw_layer(msl_handle* h, int32_t layer) {
 int msl_tacaw_welch_layer(msl_handle* h, int32_t layer, int32_t L, int32_t hop, const double* window_L) {
     if (!h) return fail(h, MSL_ERR_INVALID, "null handle");
     if (!h->wf) return fail(h, MSL_ERR_STATE, "msl_tacaw_welch_layer: no wavefunction buffer");
-    const int n = n_taps(h) + 1;
+    const int n = n_result_layers(h);
     if (layer < 0 || layer >= n) return fail(h, MSL_ERR_INVALID, "msl_tacaw_welch_layer: layer %d outside [0, %d)", layer, n);
     HIPCHK(h, hipSetDevice(h->cfg.device));
     return welch_resident(h, h->layers + (size_t)layer * layer_block_elems(h), L, hop, window_L);         // (the last block is wf)
+}
+
+// ---- thickness series of the probe-batch modes: every tapped layer reduced at once (layer_reduce.h) ----------
+namespace {
+
+void lr_release(msl_handle* h) {
+    h->lr_on = false; h->lr_what = 0; h->lr_count = 0;
+    h->lr_block.release(); h->lr_stage.release(); h->tap.release();
+    h->layer_slices.clear(); h->layer_block.clear();
+}
+
+// Everything of the sequence is sized at set-up (the staging, the partial slab of the detector tiles in h->scratch), so that no
+// allocation -- which would wait for the device -- happens here.  The rows are all n_probes: a padded probe is reduced too.
+int layer_reduce_queue(msl_handle* h, int l, const float2* block, int slot, int count) {
+    const msl_config& c = h->cfg;
+    const Rows r{block, c.n_probes, c.n_frames, (int64_t)h->wpix, (int64_t)h->wpitch};
+    const LrLayout& y = h->lr_lay;
+    int rc;
+    // every write below is sized by the handle's detector and bin counts: they must still be the layout's (a failed msl_set_detectors
+    // or msl_set_polar leaves none)
+    if (((h->lr_what & LR_DETECT) && h->det_n != (int)y.D) || ((h->lr_what & LR_POLAR) && h->pol_bins != (int)y.n_bins))
+        return fail(h, MSL_ERR_STATE, "msl_propagate_frames: %d detectors / %d polar bins, the layer reductions are set up for %d / %d", h->det_n,
+                    h->pol_bins, (int)y.D, (int)y.n_bins);
+    if (h->lr_what & LR_DETECT) {
+        DetTiling t;
+        if ((rc = plan_detect(h, "msl_propagate_frames", r, "frame slots", slot, count, &t, h->lr_stage + y.det(l))) ||
+            (rc = detect_tiles(h, r, slot, count, t)) || (rc = mark_launch(h, K_OTHER)) || (rc = detect_finish(h, t)) || (rc = mark_launch(h, K_OTHER)))
+            return rc;
+        h->ctr.algorithmic_bytes += 8ull * (uint64_t)r.K * (uint64_t)r.B * (uint64_t)count;
+    }
+    double* d_res = nullptr;
+    size_t bytes = 0;
+    if (h->lr_what & LR_POLAR) {
+        if ((rc = polar_launch(h, r, slot, count, h->lr_stage + y.pol(l), &d_res, &bytes)) || (rc = mark_launch(h, K_OTHER))) return rc;
+        h->ctr.algorithmic_bytes += 8ull * (uint64_t)r.K * (uint64_t)r.B * (uint64_t)count;
+    }
+    if (h->lr_what & (LR_DIFFRACT | LR_PACBED)) {
+        if ((rc = diffract_launch(h, r, slot, count, h->wx / h->bx, h->wy / h->by, h->lr_bx, h->lr_by, h->lr_stage + y.diff(l), &d_res, &bytes))) return rc;
+    }
+    h->lr_slot = slot; h->lr_count = count;
+    return MSL_OK;
+}
+
+}  // namespace
+
+int msl_set_layer_reduce(msl_handle* h, const int32_t* slices, int32_t n, uint32_t what, int32_t bx, int32_t by) {
+    if (!h) return fail(h, MSL_ERR_INVALID, "null handle");
+    const msl_config& c = h->cfg;
+    if (n < 0 || (n > 0 && !slices)) return fail(h, MSL_ERR_INVALID, "msl_set_layer_reduce: %d slice indices", n);
+    if (n_taps(h) > 0 && !h->lr_on) return fail(h, MSL_ERR_STATE, "msl_set_layer_reduce: the handle keeps layers (msl_set_layers): clear them first");
+    HIPCHK(h, hipSetDevice(c.device));
+    if (n == 0 || what == 0) {                                  // clearing: back to a plain handle
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        if (h->lr_on) lr_release(h);
+        return MSL_OK;
+    }
+    if (what & ~(uint32_t)LR_ALL) return fail(h, MSL_ERR_INVALID, "msl_set_layer_reduce: unknown reduction bits 0x%x", what);
+    for (int i = 0; i < n; ++i) {
+        if (slices[i] < 0 || slices[i] >= c.nz - 1)
+            return fail(h, MSL_ERR_INVALID, "msl_set_layer_reduce: slice %d outside [0, %d) (the exit wave nz - 1 is always the last layer)", slices[i], c.nz - 1);
+        if (i > 0 && slices[i] <= slices[i - 1]) return fail(h, MSL_ERR_INVALID, "msl_set_layer_reduce: slice indices must increase strictly");
+    }
+    if (!h->wf) return fail(h, MSL_ERR_STATE, "msl_set_layer_reduce: handle created with n_frames == 0");
+    if (h->st_open) return fail(h, MSL_ERR_STATE, "msl_set_layer_reduce: a TACAW stream is open");
+    if ((what & LR_DETECT) && (h->det_n == 0 || h->det_K != h->wpix))
+        return fail(h, MSL_ERR_STATE, "msl_set_layer_reduce: no detectors (call msl_set_detectors first)");
+    if ((what & LR_POLAR) && (h->pol_bins == 0 || h->pol_K != h->wpix))
+        return fail(h, MSL_ERR_STATE, "msl_set_layer_reduce: no bin map (call msl_set_polar first)");
+    const bool patterns = what & (LR_DIFFRACT | LR_PACBED);
+    const int sx = h->wx / h->bx, sy = h->wy / h->by;
+    int rc;
+    if (patterns && (rc = check_window_bin(h, "msl_set_layer_reduce", sx, sy, bx, by))) return rc;
+    LrLayout y;
+    if (!lr_layout(what, (int64_t)n + 1, c.n_probes, c.n_frames, h->det_n, h->pol_bins, patterns ? sx / bx : 0, patterns ? sy / by : 0, &y))
+        return fail(h, MSL_ERR_INVALID, "msl_set_layer_reduce: %d layers of %d probes x %d frame slots are too large", n + 1, c.n_probes, c.n_frames);
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    // new buffers first, the old state stays as it is until all of them exist
+    DevBuf<float2> block, tap;
+    DevBuf<double> stage;
+    const size_t tap_elems = (size_t)c.nx * h->pitch * (size_t)c.n_probes * h->FB;
+    const bool keep_tap = h->lr_on && h->tap.n == tap_elems;
+    if ((rc = block.alloc(h, layer_block_elems(h))) || (!keep_tap && (rc = tap.alloc(h, tap_elems))) || (rc = stage.alloc(h, y.total)))
+        return fail(h, MSL_ERR_NOMEM, "msl_set_layer_reduce: the layer block, the tap buffer and %zu bytes of staging do not fit", y.total * sizeof(double));
+    if (what & LR_DETECT) {                                     // the partial slab of the detector tiles, for the largest sequence
+        const DetTiling t = det_tiling((int64_t)c.n_probes * std::min(h->FB, c.n_frames), (int64_t)h->wpix, h->det_n);
+        if ((rc = h->scratch.reserve(h, t.part_bytes))) return rc;
+    }
+    HIPCHK(h, hipMemsetAsync(block, 0, block.n * sizeof(float2), h->stream));
+    HIPCHK(h, hipMemsetAsync(stage, 0, stage.n * sizeof(double), h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    h->lr_block = std::move(block);
+    h->lr_stage = std::move(stage);
+    if (!keep_tap) h->tap = std::move(tap);
+    h->layer_slices.assign(slices, slices + n);
+    h->layer_block.assign(c.nz, -1);
+    for (int i = 0; i < n; ++i) h->layer_block[slices[i]] = i;
+    h->lr_lay = y; h->lr_what = what; h->lr_bx = patterns ? bx : 1; h->lr_by = patterns ? by : 1;
+    h->lr_count = 0;
+    h->lr_on = true;
+    return MSL_OK;
+}
+
+size_t msl_layer_reduce_bytes(const msl_handle* h, int32_t which) {
+    if (!h || !h->lr_on) return 0;
+    switch (which) {
+        case MSL_LR_BYTES_BLOCK: return h->lr_block.n * sizeof(float2);
+        case MSL_LR_BYTES_TAP: return h->tap.n * sizeof(float2);
+        case MSL_LR_BYTES_STAGING: return h->lr_stage.n * sizeof(double);
+    }
+    return 0;
+}
+
+int msl_layer_fetch(msl_handle* h, int64_t B, int32_t count, double* det_out, double* polar_out, double* pattern_out) {
+    if (!h) return fail(h, MSL_ERR_INVALID, "null handle");
+    if (!h->lr_on) return fail(h, MSL_ERR_STATE, "msl_layer_fetch: no layer reductions (call msl_set_layer_reduce)");
+    if (h->lr_count == 0) return fail(h, MSL_ERR_STATE, "msl_layer_fetch: no slice loop has run since msl_set_layer_reduce");
+    if (count != h->lr_count) return fail(h, MSL_ERR_INVALID, "msl_layer_fetch: %d frames, the last sequence reduced %d", count, h->lr_count);
+    if (B < 1) B = h->cfg.n_probes;
+    if (B > h->cfg.n_probes) return fail(h, MSL_ERR_INVALID, "msl_layer_fetch: %lld probes, the handle has %d", (long long)B, h->cfg.n_probes);
+    if ((det_out && !(h->lr_what & LR_DETECT)) || (polar_out && !(h->lr_what & LR_POLAR)) || (pattern_out && !(h->lr_what & LR_DIFFRACT)))
+        return fail(h, MSL_ERR_INVALID, "msl_layer_fetch: an output whose reduction msl_set_layer_reduce did not ask for");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    const LrLayout& y = h->lr_lay;
+    const size_t rows = (size_t)B * count;
+    for (int64_t l = 0; l < y.L; ++l) {
+        if (det_out)
+            HIPCHK(h, hipMemcpyAsync(det_out + (size_t)l * rows * y.D, h->lr_stage + y.det(l), rows * y.D * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        if (polar_out)
+            HIPCHK(h, hipMemcpyAsync(polar_out + (size_t)l * rows * y.n_bins, h->lr_stage + y.pol(l), rows * y.n_bins * sizeof(double), hipMemcpyDeviceToHost,
+                                     h->stream));
+        if (pattern_out)
+            HIPCHK(h, hipMemcpyAsync(pattern_out + (size_t)l * B * y.M, h->lr_stage + y.diff(l), (size_t)B * y.M * sizeof(double), hipMemcpyDeviceToHost,
+                                     h->stream));
+    }
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return MSL_OK;
+}
+
+int msl_layer_pacbed_reset(msl_handle* h) {
+    if (!h) return fail(h, MSL_ERR_INVALID, "null handle");
+    if (!h->lr_on || !(h->lr_what & LR_PACBED)) return fail(h, MSL_ERR_STATE, "msl_layer_pacbed_reset: no accumulator (msl_set_layer_reduce with MSL_LR_PACBED)");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    const LrLayout& y = h->lr_lay;
+    HIPCHK(h, hipMemsetAsync(h->lr_stage + y.acc_off, 0, (size_t)y.L * y.M * sizeof(double), h->stream));
+    return MSL_OK;
+}
+
+int msl_layer_pacbed_add(msl_handle* h, int64_t B) {
+    if (!h) return fail(h, MSL_ERR_INVALID, "null handle");
+    if (!h->lr_on || !(h->lr_what & LR_PACBED)) return fail(h, MSL_ERR_STATE, "msl_layer_pacbed_add: no accumulator (msl_set_layer_reduce with MSL_LR_PACBED)");
+    if (h->lr_count == 0) return fail(h, MSL_ERR_STATE, "msl_layer_pacbed_add: no slice loop has run since msl_set_layer_reduce");
+    if (B < 1) B = h->cfg.n_probes;
+    if (B > h->cfg.n_probes) return fail(h, MSL_ERR_INVALID, "msl_layer_pacbed_add: %lld probes, the handle has %d", (long long)B, h->cfg.n_probes);
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    const LrLayout& y = h->lr_lay;
+    if (y.L > 65535) return fail(h, MSL_ERR_UNSUPPORTED, "msl_layer_pacbed_add: more than 65535 layers");
+    const double* src = h->lr_stage + y.diff_off;
+    double* acc = h->lr_stage + y.acc_off;
+    const bool pair = y.M % 2 == 0 && (((uintptr_t)src | (uintptr_t)acc) & 15) == 0;
+    const long long lanes = pair ? y.M / 2 : y.M;
+    int rc;
+    if ((rc = begin_timed(h, 1))) return rc;
+    with_bool(pair, [&](auto pr) {
+        hipLaunchKernelGGL(pacbed_add_kernel<decltype(pr)::value>, dim3((unsigned)((lanes + 255) / 256), (unsigned)y.L), dim3(256), 0, h->stream, src, acc,
+                           (int)B, (long long)y.P, (long long)y.M);
+    });
+    HIPCHK(h, hipGetLastError());
+    if ((rc = mark_launch(h, K_OTHER))) return rc;
+    h->ctr.algorithmic_bytes += 8ull * (uint64_t)y.L * (uint64_t)y.M * ((uint64_t)B + 2);
+    return MSL_OK;
+}
+
+int msl_layer_pacbed_download(msl_handle* h, double* out) {
+    if (!h || !out) return fail(h, MSL_ERR_INVALID, "msl_layer_pacbed_download: null argument");
+    if (!h->lr_on || !(h->lr_what & LR_PACBED))
+        return fail(h, MSL_ERR_STATE, "msl_layer_pacbed_download: no accumulator (msl_set_layer_reduce with MSL_LR_PACBED)");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    const LrLayout& y = h->lr_lay;
+    return download_sync(h, out, h->lr_stage + y.acc_off, (size_t)y.L * y.M * sizeof(double));
 }
 
 int msl_download_frame(msl_handle* h, int32_t slot, void* dst, size_t bytes) { return frame_copy(h, slot, dst, bytes, true); }

@@ -56,7 +56,12 @@ class DiffractionData:
     probe_positions / probe / wavelength, the scan axes xs / ys, and `stem`: the STEMData of the same pass when the run had detectors.
     With Diffraction(split=True), `elastic` (P, mx, my) float64 is |<Psi>|^2 -- the coherent mean over the frames, squared, then
     summed over the pixels of the bin (a bin adds intensities) --, `tds` the thermal diffuse rest, and part() gives either as a
-    DiffractionData of its own; `elastic` is None otherwise."""
+    DiffractionData of its own; `elastic` is None otherwise.
+    With MultisliceCalculator(thickness=...) intensity is (P, mx, my, L): `layer` holds the slice indices of the L thickness entries,
+    `thickness` the depth in Angstrom at the exit side of each slice, at(i) is the ordinary DiffractionData of entry i (its stem
+    too), and pacbed / virtual / image / pattern take layer=-1, the exit wave.  With Thickness(patterns="pacbed") only the
+    position-averaged pattern was kept: intensity is (mx, my, L) -- (mx, my) after at(i) -- which pacbed() returns and the
+    per-position methods refuse."""
     intensity: np.ndarray
     kxs: Any
     kys: Any
@@ -69,14 +74,37 @@ class DiffractionData:
     xs: np.ndarray = None
     ys: np.ndarray = None
     elastic: Optional[np.ndarray] = None
+    layer: Optional[np.ndarray] = None
+    thickness: Optional[np.ndarray] = None
+    patterns: str = "position"
 
     def __post_init__(self):
+        if self.patterns not in ("position", "pacbed"):
+            raise ValueError(f"patterns must be 'position' or 'pacbed', got {self.patterns!r}")
+        want = (3 if self.patterns == "position" else 2) + (self.layer is not None)
+        if (self.layer is not None or self.patterns == "pacbed") and (
+                np.ndim(self.intensity) != want or (self.layer is not None and np.shape(self.intensity)[-1] != len(self.layer))):
+            raise ValueError(f"intensity of shape {np.shape(self.intensity)} for patterns={self.patterns!r}"
+                             + ("" if self.layer is None else f" and {len(self.layer)} thickness entries"))
         if self.elastic is not None and np.shape(self.elastic) != np.shape(self.intensity):
             raise ValueError(f"elastic has shape {np.shape(self.elastic)}, intensity {np.shape(self.intensity)}")
         if self.wavelength is None and self.probe is not None:
             self.wavelength = float(self.probe.wavelength)
         if self.xs is None or self.ys is None:
             self.xs, self.ys = scan_axes(self.probe_positions)
+
+    def at(self, i: int) -> "DiffractionData":
+        """the un-layered DiffractionData of thickness entry i (negative from the end: -1 is the exit wave)"""
+        if self.layer is None:
+            raise ValueError("this DiffractionData has no thickness axis: run with MultisliceCalculator(thickness=...)")
+        from .thickness import entry
+        j = entry(self.layer, i)
+        return replace(self, intensity=self.intensity[..., j], layer=None, thickness=None,
+                       stem=None if self.stem is None else self.stem.at(j))
+
+    def _per_position(self, what):
+        if self.patterns != "position":
+            raise ValueError(f"{what}: this DiffractionData holds the position-averaged pattern only (Thickness(patterns='pacbed'))")
 
     @property
     def tds(self) -> np.ndarray:
@@ -97,9 +125,11 @@ class DiffractionData:
         arr = {"total": self.intensity, "elastic": self.elastic, "tds": None}[name]
         return replace(self, intensity=self.tds if arr is None else arr, elastic=None)
 
-    def pacbed(self) -> np.ndarray:
-        """(mx, my): position-averaged pattern, the mean over the probes"""
-        return self.intensity.mean(axis=0)
+    def pacbed(self, layer=-1) -> np.ndarray:
+        """(mx, my): position-averaged pattern, the mean over the probes; of thickness entry `layer` when there is a thickness axis"""
+        if self.layer is not None:
+            return self.at(layer).pacbed()
+        return self.intensity if self.patterns == "pacbed" else self.intensity.mean(axis=0)
 
     def member(self, detector: Detector) -> np.ndarray:
         """(mx, my) bool: the detector pixels whose CENTRE lies in `detector` (its member() on the bin-centre axes)"""
@@ -111,16 +141,22 @@ class DiffractionData:
             raise ValueError("DiffractionData has neither a probe nor a wavelength: detector angles cannot be turned into k")
         return detector.member(_np(self.kxs), _np(self.kys), self.wavelength)
 
-    def virtual(self, detector: Detector) -> np.ndarray:
+    def virtual(self, detector: Detector, layer=-1) -> np.ndarray:
         """(P,): the virtual detector chosen after the run -- sum of the detector pixels inside `detector`"""
+        if self.layer is not None:
+            return self.at(layer).virtual(detector)
+        self._per_position("virtual()")
         m = self.member(detector)
         return (self.intensity * m[None].astype(np.float64)).sum(axis=(-2, -1))
 
-    def image(self, detector: Detector) -> np.ndarray:
+    def image(self, detector: Detector, layer=-1) -> np.ndarray:
         """(len(xs), len(ys)) scan image of virtual(detector): every scan point takes its nearest probe's value (STEMData.image)"""
-        return scan_image(self.virtual(detector), self.probe_positions, self.xs, self.ys)
+        return scan_image(self.virtual(detector, layer), self.probe_positions, self.xs, self.ys)
 
-    def pattern(self, x: float, y: float) -> np.ndarray:
+    def pattern(self, x: float, y: float, layer=-1) -> np.ndarray:
         """(mx, my): the pattern of the probe nearest to (x, y)"""
+        if self.layer is not None:
+            return self.at(layer).pattern(x, y)
+        self._per_position("pattern()")
         pp = np.asarray(self.probe_positions, dtype=np.float64).reshape(-1, 2)
         return self.intensity[int(np.argmin(((pp - np.array([x, y])[None, :]) ** 2).sum(axis=1)))]

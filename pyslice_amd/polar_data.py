@@ -11,7 +11,7 @@ pixel (polar_bins, the rules of stem_data.Detector.member), the reference sums (
 from __future__ import annotations
 
 import math
-from dataclasses import dataclass
+from dataclasses import dataclass, replace
 from typing import Any, Optional, Sequence
 
 import numpy as np
@@ -137,7 +137,10 @@ class PolarData:
     """Result of MultisliceCalculator.run_polar(): signals (P, R, A) float64 -- the mean over the frames of |Psi|^2 in ring r,
     sector a at probe p -- or (P, T, R, A) with PolarDetector(per_frame=True); the request `polar`; counts (R, A) int64, the stored
     pixels of every bin (0: an empty bin, whose signal is 0); edges (R + 1,) in mrad; the run's probe_positions / time / kxs / kys /
-    probe, the scan axes xs / ys, and `stem`: the STEMData of the same pass when the run had detectors."""
+    probe, the scan axes xs / ys, and `stem`: the STEMData of the same pass when the run had detectors.
+    With MultisliceCalculator(thickness=...) signals is (P, R, A, L) or (P, T, R, A, L): `layer` holds the slice indices of the L
+    thickness entries, `thickness` the depth in Angstrom at the exit side of each slice, at(i) is the ordinary PolarData of entry i
+    (its stem too), and integrate / image / profile / to_stem take layer=-1, the exit wave."""
     signals: np.ndarray
     polar: PolarDetector
     counts: np.ndarray
@@ -150,15 +153,30 @@ class PolarData:
     xs: np.ndarray = None
     ys: np.ndarray = None
     stem: Optional[STEMData] = None
+    layer: Optional[np.ndarray] = None
+    thickness: Optional[np.ndarray] = None
 
     def __post_init__(self):
         R, A = self.polar.n_rings, self.polar.n_azimuthal
         want = 4 if self.polar.per_frame else 3
-        if np.ndim(self.signals) != want or np.shape(self.signals)[-2:] != (R, A):
+        if self.layer is not None:
+            if np.ndim(self.signals) != want + 1 or np.shape(self.signals)[-3:] != (R, A, len(self.layer)):
+                raise ValueError(f"signals of shape {np.shape(self.signals)} for {R} rings x {A} sectors x {len(self.layer)} thickness entries"
+                                 + (" per frame" if self.polar.per_frame else ""))
+        elif np.ndim(self.signals) != want or np.shape(self.signals)[-2:] != (R, A):
             raise ValueError(f"signals of shape {np.shape(self.signals)} for {R} rings x {A} sectors"
                              + (" per frame" if self.polar.per_frame else ""))
         if self.xs is None or self.ys is None:
             self.xs, self.ys = scan_axes(self.probe_positions)
+
+    def at(self, i: int) -> "PolarData":
+        """the un-layered PolarData of thickness entry i (negative from the end: -1 is the exit wave)"""
+        if self.layer is None:
+            raise ValueError("this PolarData has no thickness axis: run with MultisliceCalculator(thickness=...)")
+        from .thickness import entry
+        j = entry(self.layer, i)
+        return replace(self, signals=self.signals[..., j], layer=None, thickness=None,
+                       stem=None if self.stem is None else self.stem.at(j))
 
     def _edge(self, what, angle) -> int:
         e = np.asarray(self.edges, dtype=np.float64)
@@ -189,20 +207,24 @@ class PolarData:
         n = (a1 - a0) % A or A                                   # from boundary a0 round to boundary a1 (the whole circle: A sectors)
         return [(a0 + i) % A for i in range(n)]
 
-    def integrate(self, inner=0.0, outer=None, azimuth=None) -> np.ndarray:
+    def integrate(self, inner=0.0, outer=None, azimuth=None, layer=-1) -> np.ndarray:
         """(P,) -- (P, T) per frame: the sum of the bins between the ring edges `inner` and `outer` (None: the last edge) and, with
         azimuth=(phi0, phi1), of the sectors phi0 <= phi < phi1 (wrapping through 0 when phi0 > phi1, as Detector.azimuth): the
         intensity signal of Detector(inner=inner, outer=outer, azimuth=azimuth).  ValueError when an angle is not an edge within
-        1e-9 mrad, or not a sector boundary."""
+        1e-9 mrad, or not a sector boundary.  Of thickness entry `layer` when there is a thickness axis."""
+        if self.layer is not None:
+            return self.at(layer).integrate(inner, outer, azimuth)
         r0 = self._edge("inner", float(inner))
         r1 = len(self.edges) - 1 if outer is None else self._edge("outer", float(outer))
         if r1 <= r0:
             raise ValueError(f"outer angle {outer} must exceed the inner angle {inner}")
         return self.signals[..., r0:r1, :][..., self._sectors(azimuth)].sum(axis=(-2, -1))
 
-    def image(self, inner=0.0, outer=None, azimuth=None, frames=None) -> np.ndarray:
+    def image(self, inner=0.0, outer=None, azimuth=None, frames=None, layer=-1) -> np.ndarray:
         """(len(xs), len(ys)) scan image of integrate(inner, outer, azimuth): the mean over the frames (per_frame: all, or an index /
         slice / list of frame indices), every scan point taking its nearest probe's value (stem_data.scan_image)"""
+        if self.layer is not None:
+            return self.at(layer).image(inner, outer, azimuth, frames)
         s = self.integrate(inner, outer, azimuth)
         if self.polar.per_frame:
             if frames is not None:
@@ -214,16 +236,20 @@ class PolarData:
             raise ValueError("frames: this PolarData holds the frame mean only (run with PolarDetector(per_frame=True))")
         return scan_image(s, self.probe_positions, self.xs, self.ys)
 
-    def profile(self, probe_index=None) -> np.ndarray:
+    def profile(self, probe_index=None, layer=-1) -> np.ndarray:
         """(R,): the radial profile -- summed over the sectors, averaged over the frames -- of one probe, or the mean over all"""
+        if self.layer is not None:
+            return self.at(layer).profile(probe_index)
         s = self.signals.sum(axis=-1)
         if self.polar.per_frame:
             s = s.mean(axis=1)
         return s.mean(axis=0) if probe_index is None else s[int(probe_index)]
 
-    def to_stem(self, detectors: Sequence[Detector]) -> STEMData:
+    def to_stem(self, detectors: Sequence[Detector], layer=-1) -> STEMData:
         """STEMData of intensity detectors whose edges are ring edges and sector boundaries, chosen after the run: signals
         (P, T, D), so STEMData.image() and everything built on it applies.  Needs per_frame=True."""
+        if self.layer is not None:
+            return self.at(layer).to_stem(detectors)
         if not self.polar.per_frame:
             raise ValueError("to_stem() needs the signals of every frame: run with PolarDetector(per_frame=True)")
         dets = list(detectors)

@@ -8,7 +8,7 @@ as the slice loop has written it, so a scan needs no (P, T, nx, ny) array: STEMD
 """
 from __future__ import annotations
 
-from dataclasses import dataclass
+from dataclasses import dataclass, replace
 from typing import Any, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -110,7 +110,10 @@ def scan_image(per_probe, probe_positions, xs, ys) -> np.ndarray:
 @dataclass
 class STEMData:
     """Result of MultisliceCalculator.run_detectors(): signals (P, T, D) float64 -- detector d of frame t at probe p --, the
-    detectors, the run's probe_positions / time / kxs / kys / probe, and the scan axes xs, ys."""
+    detectors, the run's probe_positions / time / kxs / kys / probe, and the scan axes xs, ys.
+    With MultisliceCalculator(thickness=...) signals is (P, T, D, L): `layer` holds the slice indices of the L thickness entries,
+    `thickness` the depth in Angstrom at the exit side of each slice, at(i) is the ordinary STEMData of entry i, and image() takes
+    layer=-1, the exit wave."""
     signals: np.ndarray
     detectors: List[Detector]
     probe_positions: Any
@@ -120,10 +123,21 @@ class STEMData:
     probe: Any
     xs: np.ndarray = None
     ys: np.ndarray = None
+    layer: Optional[np.ndarray] = None
+    thickness: Optional[np.ndarray] = None
 
     def __post_init__(self):
         if self.xs is None or self.ys is None:
             self.xs, self.ys = scan_axes(self.probe_positions)
+        if self.layer is not None and (np.ndim(self.signals) != 4 or np.shape(self.signals)[-1] != len(self.layer)):
+            raise ValueError(f"signals of shape {np.shape(self.signals)} for {len(self.layer)} thickness entries")
+
+    def at(self, i: int) -> "STEMData":
+        """the un-layered STEMData of thickness entry i (negative from the end: -1 is the exit wave)"""
+        if self.layer is None:
+            raise ValueError("this STEMData has no thickness axis: run with MultisliceCalculator(thickness=...)")
+        from .thickness import entry
+        return replace(self, signals=self.signals[..., entry(self.layer, i)], layer=None, thickness=None)
 
     def index(self, name: str) -> int:
         for d, det in enumerate(self.detectors):
@@ -131,9 +145,12 @@ class STEMData:
                 return d
         raise KeyError(f"no detector named {name!r} (have {[d.name for d in self.detectors]})")
 
-    def image(self, name: str, frames=None) -> np.ndarray:
+    def image(self, name: str, frames=None, layer=-1) -> np.ndarray:
         """(len(xs), len(ys)) image of detector `name`: mean over the frames (all, or an index / slice / list of frame
-        indices) on the scan grid, every scan point taking its nearest probe's value as HAADFData does"""
+        indices) on the scan grid, every scan point taking its nearest probe's value as HAADFData does; of thickness entry
+        `layer` when there is a thickness axis"""
+        if self.layer is not None:
+            return self.at(layer).image(name, frames)
         s = self.signals[:, :, self.index(name)]
         if frames is not None:
             s = s[:, frames]
