@@ -11,6 +11,8 @@
 // ifft -> multiply -> fft chain never leaves registers except for the two transposes, and HBM is
 // touched exactly once per pass with 8R-byte (row pass) or 128-byte (column pass) contiguous
 // segments.  Index algebra is unit-tested on the host (tools/fft_regs_host.cpp).
+// This file holds the slice-loop passes and the register / wave FFTs; the inverse transforms of the potential build, which run
+// on the same FFTs, are in pot_ifft.h.
 #pragma once
 #include <type_traits>
 #include <utility>
@@ -1436,662 +1438,6 @@ __global__ void __launch_bounds__(16 * R, 2) rowT2_pass_kernel(RowTJob job) {   
         }
         lds_barrier();
         item = nitem; lb = nlb; pc = npc; k = nk;
-    }
-}
-
-// ---- stand-alone inverse FFT passes for lines of 2 R^2 = 512 points: the potential build on 512 x 512 grids ---------------------
-// V_s = Re ifft2(R_s) / (dx^2 dy^2), t_s = exp(i sigma V_s) (potentials.py:336-342, multislice.py:282) went through the generic LDS
-// kernel on these grids (two passes at 2.6 TB/s plus a transposition of every second slice; 0.35 of 0.73 ms per frame at 512^2 x
-// 100, which a single probe cannot amortise).  Two passes of this kernel instead: the line is loaded in the split order the
-// register transform wants -- slot k of set b is X[2k + b], i.e. one 16-byte load per lane and register -- inverse-transformed
-// (line2_transform) and stored transposed through the 16-line tile; the second pass applies the potential epilogue and writes a
-// slice either transposed back (natural orientation) or as rows (the orientation the passes along x read).
-struct IfftT2Job {
-    const float2* in;           // (n_images, n_lines, in_pitch): lines in natural frequency order
-    float2* out_t;              // transposed store: out_t[img][pos][line]
-    float2* out_rows;           // row store (potential epilogue only): out_rows[img][line][pos]
-    const float2* tw;
-    const float2* tw2;
-    long long in_is, out_t_is, out_rows_is;
-    int in_pitch, out_t_pitch, out_rows_pitch, n_lines, n_images;
-    int potential;              // 1: V = Re(.) * scale, out = exp(i sigma V)
-    int rows_parity;            // potential: images whose slice number has this parity are stored as rows, the others transposed; -1: none
-    int slice_mod;              // slice number of image img = img % slice_mod (several frames' stacks in one launch); 0: img itself
-    int herm;                   // 1: only elements 0 .. N/2 of an input line exist, the others are conj(line[N - e]) (spectrum of a real image)
-    float scale, sigma_over_pi;
-};
-
-// slice number of an image of a potential-build launch (the stacks of several frames follow each other)
-template <typename Job>
-__device__ __forceinline__ int slice_of(const Job& job, int img) { return job.slice_mod > 0 ? img % job.slice_mod : img; }
-
-// PAIR (second pass: job.herm and job.potential set, line count a multiple of 32): two real lines per complex transform,
-// Z = X_a + i X_b -> V_a + i V_b; a group takes the lines g and g + 16 of a 32-line block (ifftTB_kernel's note).  Line a of the
-// next item is prefetched in registers as before, line b arrives at the top of the item (two prefetched lines do not fit).
-template <int R, bool PAIR = false>
-__global__ void __launch_bounds__(16 * R, 2) ifftT2_kernel(IfftT2Job job) {
-    static_assert(R == 16, "512-point lines only (64 complex values per lane at R = 32 spill: 2048-point axes use ifftTW_kernel)");
-    constexpr int N2 = R * R, N = 2 * N2, NT = 16 * R;
-    constexpr int BL = PAIR ? 32 : 16;                             // lines per work item
-    constexpr int CPOS = N;
-    constexpr int CS = CPOS + 1;
-    constexpr int POS_PER_IT = NT / 8;
-    constexpr int NIT = CPOS / POS_PER_IT;
-    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    float2* tw = reinterpret_cast<float2*>(smem_raw);
-    float2* tw2 = tw + N2;
-    float2* tile = tw2 + N2;                                     // 16 * CS, also the transpose scratch
-    const int tid = threadIdx.x;
-    for (int i = tid; i < N2; i += NT) { tw[i] = job.tw[i]; tw2[i] = job.tw2[i]; }
-    __syncthreads();
-    const int grp = tid / R, ln = tid % R;
-    const int q = tid & 7, r0 = tid >> 3;
-    float* scratch = reinterpret_cast<float*>(tile + grp * CS);
-    const int lblocks = job.n_lines / BL;
-    const int n_items = lblocks * job.n_images;
-    // the next item's line is loaded into registers while the current one is transformed (two 256-thread workgroups per CU = two
-    // waves per SIMD: without it the loads of an item were exposed -- 193 us of a 0.33 ms potential per frame at 512^2 x 100)
-    float2 vn[2 * R];
-    // slot j of set b <- element 2 (j R + ln) + b of line `line`; with herm the mirrored element (conjugated unless RAW)
-    auto load_line = [&](int it, int line_in_block, float2 (&dst)[2 * R], auto raw_c) {
-        constexpr bool RAW = decltype(raw_c)::value;
-        const int img = it / lblocks, lb = it - img * lblocks;
-        const float2* src = job.in + (long long)img * job.in_is + (long long)(lb * BL + line_in_block) * job.in_pitch;
-        int lnl = ln;
-        asm volatile("" : "+v"(lnl));
-        if (job.herm) {                                     // workgroup-uniform: mirrored elements as two 8-byte loads
-#pragma unroll
-            for (int j = 0; j < R; ++j) {
-                const int e0 = 2 * (j * R + lnl), e1 = e0 + 1;
-                float2 a = src[e0 <= N / 2 ? e0 : N - e0], b = src[e1 <= N / 2 ? e1 : N - e1];
-                if (!RAW && e0 > N / 2) a.y = -a.y;
-                if (!RAW && e1 > N / 2) b.y = -b.y;
-                dst[j] = a; dst[R + j] = b;
-            }
-        } else {
-#pragma unroll
-            for (int j = 0; j < R; ++j) {
-                const float4 x = *reinterpret_cast<const float4*>(src + 2 * (j * R + lnl));
-                dst[j] = make_float2(x.x, x.y); dst[R + j] = make_float2(x.z, x.w);
-            }
-        }
-    };
-    using RawC = std::integral_constant<bool, PAIR>;
-    if ((int)blockIdx.x < n_items) load_line(blockIdx.x, grp, vn, RawC{});
-    for (int item = blockIdx.x; item < n_items; item += gridDim.x) {
-        const int img = item / lblocks, lb = item - img * lblocks;
-        int lnv = ln;                                       // laundered: keeps dozens of per-lane LDS / global addresses from being
-        asm volatile("" : "+v"(lnv));                       // hoisted out of the loop into registers the transform needs
-        float2 v[2 * R];
-        if constexpr (PAIR) {
-            float2 vb[2 * R];
-            load_line(item, 16 + grp, vb, RawC{});
-#pragma unroll
-            for (int j = 0; j < 2 * R; ++j) {               // element 2 ((j % R) R + ln) + j / R: a + i b, mirrored half conj(a) + i conj(b)
-                const int e = 2 * ((j % R) * R + lnv) + j / R;
-                float2 a = vn[j], b = vb[j];
-                if (e == N / 2) a.y = b.y = 0.f;            // (the Nyquist element is its own mirror image: ifftTB_kernel's note)
-                v[j] = (e <= N / 2) ? make_float2(a.x - b.y, a.y + b.x) : make_float2(a.x + b.y, b.x - a.y);
-            }
-        } else {
-#pragma unroll
-            for (int j = 0; j < 2 * R; ++j) v[j] = vn[j];
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        if (item + (int)gridDim.x < n_items) load_line(item + (int)gridDim.x, grp, vn, RawC{});
-        __builtin_amdgcn_sched_barrier(0);
-        float* scr = scratch;
-        asm volatile("" : "+v"(scr));
-        line2_transform<R, true>(v, scr, tw, tw2, lnv);
-        // exp(i sigma V) through sincospi: its range reduction is exact, where sincosf carries a slow path with a private
-        // array (scratch); sigma / pi is formed in double on the host.
-        auto trans_of = [&](float x) {
-            float sn, cs;
-            sincospif(job.sigma_over_pi * (x * job.scale), &sn, &cs);
-            return make_float2(cs, sn);
-        };
-        float vy[PAIR ? 2 * R : 1];
-        if constexpr (PAIR) {
-#pragma unroll
-            for (int j = 0; j < 2 * R; ++j) vy[j] = v[j].y;
-        }
-        const bool as_rows = job.potential && (slice_of(job, img) & 1) == job.rows_parity;       // workgroup-uniform
-#pragma unroll
-        for (int half = 0; half < (PAIR ? 2 : 1); ++half) {
-            if (job.potential) {
-#pragma unroll
-                for (int j = 0; j < 2 * R; ++j) {
-                    if (j % 4 == 0) __builtin_amdgcn_sched_barrier(0);          // four evaluations in flight, not all of them
-                    v[j] = trans_of(half == 0 ? v[j].x : vy[j]);
-                }
-            }
-            if (as_rows) {
-                float2* dst = job.out_rows + (long long)img * job.out_rows_is + (long long)(lb * BL + half * 16 + grp) * job.out_rows_pitch;
-#pragma unroll
-                for (int j = 0; j < 2 * R; ++j) dst[(j / R) * N2 + (j % R) * R + lnv] = v[j];
-                continue;
-            }
-            float2* dst = job.out_t + (long long)img * job.out_t_is + lb * BL + half * 16;
-            int off0 = 2 * q + r0 * job.out_t_pitch;
-            asm volatile("" : "+v"(off0));
-            const int ostep = POS_PER_IT * job.out_t_pitch;
-            lds_barrier();                             // the tile (and every group's scratch use) is free
-            float2* myrow = reinterpret_cast<float2*>(scr);
-#pragma unroll
-            for (int j = 0; j < CPOS / R; ++j) myrow[j * R + lnv] = v[j];
-            lds_barrier();
-#pragma unroll
-            for (int i = 0; i < NIT; ++i) {
-                const int pos = r0 + POS_PER_IT * i;
-                const float2 a = tile[(2 * q) * CS + pos], b = tile[(2 * q + 1) * CS + pos];
-                st_stream(dst + (off0 + i * ostep), a.x, a.y, b.x, b.y);
-            }
-        }
-        if (!as_rows) lds_barrier();
-    }
-}
-
-// Inverse transform of the potential build for grid lengths that are not powers of two (N <= R^2 / 2): every line an inverse
-// N-point DFT by chirp-z on the register FFTs, x = conj(w) . IFFT_M(FFT_M(pad(X conj(w))) conj(Bf)) (the inverse of
-// rowTB_pass_kernel's chirp-z form: same tables), stored TRANSPOSED through a 16-line tile -- two such passes give ifft2 with
-// the data back in its natural layout, the second one with the potential epilogue like ifftT2_kernel.  Replaces the generic
-// LDS-resident Bluestein kernel in that role (501^2 x 100 slices: 2 x 500 us -> 2 x ~90 us per frame: for the reference's
-// default single-probe runs the inverse transform of the potential WAS the frame).  The buffers are dense (pitch = line count,
-// any parity): stores are 8 bytes per line and guarded, a tile row still lands as one 128-byte run.
-struct IfftTBJob {
-    const float2* in;           // (n_images, n_lines, in_pitch): lines of n_line points in natural frequency order
-    float2* out_t;              // transposed store: out_t[img][pos][line]
-    float2* out_rows;           // row store (potential epilogue only): out_rows[img][line][pos]
-    const float2* tw;           // four-step twiddles of length M = R^2 (ifftTB2_kernel: the 2048-point wave FFT's T table)
-    const float2* tw2;          // ifftTB2_kernel: W_64 table
-    const float2* bf;           // chirp filter, first half + 1
-    const float2* bw;           // chirp, zero beyond n_line
-    long long in_is, out_t_is, out_rows_is;
-    int in_pitch, out_t_pitch, out_rows_pitch, n_lines, n_line, n_images;
-    int potential;              // 1: V = Re(.) * scale, out = exp(i sigma V)
-    int rows_parity;            // potential: images whose slice number has this parity are stored as rows, the others transposed; -1: none
-    int slice_mod;              // slice number of image img = img % slice_mod (several frames' stacks in one launch); 0: img itself
-    int herm;                   // 1: only elements 0 .. n_line/2 of an input line exist, the others are conj(line[n_line - e]) (spectrum of a real image)
-    float scale, sigma_over_pi;
-};
-
-// PAIR (second pass of the potential build: job.herm and job.potential set): the lines are spectra of REAL lines, so two of them
-// ride one complex transform, Z = X_a + i X_b -> V_a + i V_b -- half the transforms of this pass.  A group takes the lines
-// g and g + 16 of a 32-line block; both leave through one 32-row tile round (256-byte runs).
-template <int R, bool PAIR = false>
-__global__ void __launch_bounds__(16 * R, (R == 32) ? 2 : 4) ifftTB_kernel(IfftTBJob job) {
-    constexpr int M = R * R, H = R / 2, NH = M / 2, LINES = 16, NT = LINES * R, TCH = 8;
-    constexpr int BL = PAIR ? 2 * LINES : LINES;              // lines per work item
-    constexpr int CS = R * (R + 1) + 2;
-    constexpr int POS_PER_IT = NT / LINES, NIT = NH / POS_PER_IT;       // one thread per (position, line) of a tile row
-    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    float2* tw = reinterpret_cast<float2*>(smem_raw);         // M
-    float2* bf = tw + M;                                      // NH + 2
-    float2* bw = bf + NH + 2;                                 // NH
-    float2* tile = bw + NH;                                   // LINES * CS
-    const int tid = threadIdx.x;
-    const int N = job.n_line;
-    for (int i = tid; i < M; i += NT) tw[i] = job.tw[i];
-    for (int i = tid; i <= NH; i += NT) bf[i] = job.bf[i];
-    for (int i = tid; i < NH; i += NT) bw[i] = job.bw[i];
-    __syncthreads();
-    const int grp = tid / R, ln = tid % R;
-    const int li = tid % LINES, r0 = tid / LINES;             // store role: line li of the tile, positions r0 + POS_PER_IT * i
-    // PAIR: a 32-row tile of the N <= 512 positions (pitch CSP), row 2 g + h = line g + 16 h -- both lines leave in ONE round of
-    // 256-byte runs, and a wave's four contiguous rows hold its exchange scratch (ifftTB_two_kernel's layout)
-    constexpr int CSP = NH + 2;
-    static_assert(!PAIR || (R == 32 && 4 * CSP >= R * 68 / 2), "paired lines: 1024-point transforms only");
-    float2* myrow = PAIR ? tile + (2 * grp) * CSP : tile + grp * CS;
-    float2* const wtile = PAIR ? tile + (4 * (grp / 2)) * CSP : tile + (grp - grp % (64 / R)) * CS;
-    const float* wscr = reinterpret_cast<const float*>(wtile);
-    const unsigned wscr_lds = __builtin_amdgcn_readfirstlane((unsigned)(size_t)wtile);
-    const float2* fa = bf + ln;
-    const float2* fb = bf - ln;
-    const int lblocks = (job.n_lines + BL - 1) / BL;
-    const int n_items = lblocks * job.n_images;
-    // the next item's line is loaded into registers while the current one is transformed
-    float2 vn[PAIR ? R : H];
-    auto load_line = [&](int it) {
-        const int img = it / lblocks, lb = it - img * lblocks;
-        const int L = min(lb * BL + grp, job.n_lines - 1);                    // surplus lines of the last block repeat the last one
-        const float2* src = job.in + (long long)img * job.in_is + (long long)L * job.in_pitch;
-        const int hx = job.herm ? N / 2 : N;
-        if constexpr (PAIR) {
-            const int Lb = min(lb * BL + LINES + grp, job.n_lines - 1);
-            const float2* srcb = job.in + (long long)img * job.in_is + (long long)Lb * job.in_pitch;
-#pragma unroll
-            for (int j = 0; j < H; ++j) {
-                const int e = j * R + ln, m = e <= hx ? e : N - e;
-                vn[j] = (e < N) ? src[m] : make_float2(0.f, 0.f);
-                vn[H + j] = (e < N) ? srcb[m] : make_float2(0.f, 0.f);
-            }
-        } else {
-#pragma unroll
-            for (int j = 0; j < H; ++j) {
-                const int e = j * R + ln;
-                float2 x = (e < N) ? src[e <= hx ? e : N - e] : make_float2(0.f, 0.f);
-                if (e > hx) x.y = -x.y;
-                vn[j] = x;
-            }
-        }
-    };
-    if ((int)blockIdx.x < n_items) load_line(blockIdx.x);
-    for (int item = blockIdx.x; item < n_items; item += gridDim.x) {
-        const int img = item / lblocks, lb = item - img * lblocks;
-        const int L = min(lb * BL + grp, job.n_lines - 1);
-        float2 v[R];
-        if constexpr (PAIR) {
-            const int hx = N / 2;
-#pragma unroll
-            for (int j = 0; j < H; ++j) {                      // a + i b below the mirror point, conj(a) + i conj(b) above it
-                float2 a = vn[j], b = vn[H + j];
-                // the Nyquist element of an even length is its own mirror image: only its real part belongs to a real line (the
-                // unpaired kernel drops the rest with the imaginary part of its output; here it would land in the partner line)
-                if (2 * (j * R + ln) == N) a.y = b.y = 0.f;
-                v[j] = (j * R + ln <= hx) ? make_float2(a.x - b.y, a.y + b.x) : make_float2(a.x + b.y, b.x - a.y);
-            }
-        } else {
-#pragma unroll
-            for (int j = 0; j < H; ++j) v[j] = vn[j];
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        if (item + (int)gridDim.x < n_items) load_line(item + (int)gridDim.x);
-        __builtin_amdgcn_sched_barrier(0);
-        // x conj(w); the chirp table is zero beyond N, the upper half of the registers is padding
-        auto mul_chirp = [&]() {
-#pragma unroll
-            for (int c = 0; c < H; c += TCH) {
-                float2 w[TCH];
-#pragma unroll
-                for (int j = 0; j < TCH; ++j) w[j] = bw[(c + j) * R + ln];
-#pragma unroll
-                for (int j = 0; j < TCH; ++j) v[c + j] = cmulf_conj(v[c + j], w[j]);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-#pragma unroll
-            for (int j = H; j < R; ++j) v[j] = make_float2(0.f, 0.f);
-        };
-        mul_chirp();
-        fourstep_split_addtid<R, false, TCH>(v, wscr, wscr_lds, tw, ln, tid & 63);
-#pragma unroll
-        for (int c = 0; c < R; c += TCH) {
-            float2 w[TCH];
-#pragma unroll
-            for (int j = 0; j < TCH; ++j) w[j] = (c + j < H) ? fa[(c + j) * R] : fb[(R - (c + j)) * R];
-#pragma unroll
-            for (int j = 0; j < TCH; ++j) v[c + j] = cmulf_conj(v[c + j], w[j]);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        fourstep_split_addtid<R, true, TCH>(v, wscr, wscr_lds, tw, ln, tid & 63);
-        mul_chirp();
-        if constexpr (PAIR) {                                  // v[j] = V_a + i V_b: t_a into v[j], t_b into v[H + j]
-#pragma unroll
-            for (int j = 0; j < H; ++j) {
-                if (j % 4 == 0) __builtin_amdgcn_sched_barrier(0);
-                float sn, cs, sn2, cs2;
-                sincospif(job.sigma_over_pi * (v[j].x * job.scale), &sn, &cs);
-                sincospif(job.sigma_over_pi * (v[j].y * job.scale), &sn2, &cs2);
-                v[j] = make_float2(cs, sn);
-                v[H + j] = make_float2(cs2, sn2);
-            }
-        } else if (job.potential) {
-#pragma unroll
-            for (int j = 0; j < H; ++j) {
-                if (j % 4 == 0) __builtin_amdgcn_sched_barrier(0);
-                float sn, cs;
-                sincospif(job.sigma_over_pi * (v[j].x * job.scale), &sn, &cs);
-                v[j] = make_float2(cs, sn);
-            }
-        }
-        if (job.potential && (slice_of(job, img) & 1) == job.rows_parity) {       // workgroup-uniform: this slice is kept as rows
-            if (lb * BL + grp < job.n_lines) {
-                float2* dst = job.out_rows + (long long)img * job.out_rows_is + (long long)L * job.out_rows_pitch;
-#pragma unroll
-                for (int j = 0; j < H; ++j) if (j * R + ln < N) dst[j * R + ln] = v[j];
-            }
-            if constexpr (PAIR) {
-                if (lb * BL + LINES + grp < job.n_lines) {
-                    float2* dst = job.out_rows + (long long)img * job.out_rows_is + (long long)(lb * BL + LINES + grp) * job.out_rows_pitch;
-#pragma unroll
-                    for (int j = 0; j < H; ++j) if (j * R + ln < N) dst[j * R + ln] = v[H + j];
-                }
-            }
-            continue;
-        }
-        if constexpr (PAIR) {
-            wave_lds_fence();
-#pragma unroll
-            for (int j = 0; j < H; ++j) { myrow[j * R + ln] = v[j]; myrow[CSP + j * R + ln] = v[H + j]; }
-            lds_barrier();
-            const int l32 = tid % BL;
-            int p0 = tid / BL;                                  // (laundered: 32 row offsets of 64 bits would be kept across the loop)
-            asm volatile("" : "+v"(p0));
-            const int col = lb * BL + l32;
-            if (col < job.n_lines) {
-                float2* dst = job.out_t + (long long)img * job.out_t_is + col;
-                const float2* srow = tile + (2 * (l32 & 15) + (l32 >> 4)) * CSP;
-#pragma unroll
-                for (int i = 0; i < NH / (NT / BL); ++i) {
-                    const int pos = p0 + (NT / BL) * i;
-                    if (pos < N) dst[(long long)pos * job.out_t_pitch] = srow[pos];
-                }
-            }
-            lds_barrier();
-        } else {
-            wave_lds_fence();
-#pragma unroll
-            for (int j = 0; j < H; ++j) myrow[j * R + ln] = v[j];
-            lds_barrier();
-            const int col = lb * BL + li;
-            if (col < job.n_lines) {
-                float2* dst = job.out_t + (long long)img * job.out_t_is + col;
-#pragma unroll
-                for (int i = 0; i < NIT; ++i) {
-                    const int pos = r0 + POS_PER_IT * i;
-                    if (pos < N) dst[(long long)pos * job.out_t_pitch] = tile[li * CS + pos];
-                }
-            }
-            lds_barrier();
-        }
-    }
-}
-
-// First pass of the potential build (no epilogue) with TWO lines per group and item: ifftTB_kernel spends one tile round -- write,
-// barrier, 16 x (LDS read + store), barrier -- per transform, twice the share it has in the slice-loop kernels with their four
-// transforms per line, and its vector pipe idles half the time (50 % busy against rowTB_pass_kernel's 82 %, profiles/r03_*).  Here
-// a group transforms line g, parks the 16 result registers, transforms line g + 16, and ONE round stores the 32-line tile: 256-byte
-// runs, half the barriers per line.  Tile rows hold the N <= 512 positions only (pitch 514); row 2 g + h is line g + 16 h, so that a
-// wave's four rows are contiguous and hold its exchange scratch without reaching into another wave's rows.  Line a of the next
-// item is prefetched before the first transform, line b once the results are in the tile (it is needed a whole transform later).
-__global__ void __launch_bounds__(512, 2) ifftTB_two_kernel(IfftTBJob job) {
-    constexpr int R = 32, M = R * R, H = R / 2, NH = M / 2, GROUPS = 16, BL = 32, NT = GROUPS * R, TCH = 8;
-    constexpr int CSN = NH + 2;                               // tile row pitch (float2): 2 mod 32, as the 16-line tiles' 1058
-    constexpr int POS_PER_IT = NT / BL, NIT = NH / POS_PER_IT;          // one thread per (position, line): 16 positions per sweep
-    static_assert(4 * CSN >= R * 68 / 2, "a wave's four tile rows hold its exchange scratch (R rows x 68 floats)");
-    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    float2* tw = reinterpret_cast<float2*>(smem_raw);         // M
-    float2* bf = tw + M;                                      // NH + 2
-    float2* bw = bf + NH + 2;                                 // NH
-    float2* tile = bw + NH;                                   // BL * CSN
-    const int tid = threadIdx.x;
-    const int N = job.n_line;
-    for (int i = tid; i < M; i += NT) tw[i] = job.tw[i];
-    for (int i = tid; i <= NH; i += NT) bf[i] = job.bf[i];
-    for (int i = tid; i < NH; i += NT) bw[i] = job.bw[i];
-    __syncthreads();
-    const int grp = tid / R, ln = tid % R;
-    const int li = tid % BL, r0 = tid / BL;                   // store role: line li of the block, positions r0 + 16 i
-    float2* rowa = tile + (2 * grp) * CSN;                    // my two rows: lines grp and grp + 16
-    const float* wscr = reinterpret_cast<const float*>(tile + (4 * (grp / 2)) * CSN);
-    const unsigned wscr_lds = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(tile + (4 * (grp / 2)) * CSN));
-    const float2* fa = bf + ln;
-    const float2* fb = bf - ln;
-    const int lblocks = (job.n_lines + BL - 1) / BL;
-    const int n_items = lblocks * job.n_images;
-    float2 vna[H], vnb[H];
-    auto load_line = [&](int it, int h, float2 (&dst)[H]) {
-        const int img = it / lblocks, lb = it - img * lblocks;
-        const int L = min(lb * BL + h * GROUPS + grp, job.n_lines - 1);      // surplus lines of the last block repeat the last one
-        const float2* src = job.in + (long long)img * job.in_is + (long long)L * job.in_pitch;
-        const int hx = job.herm ? N / 2 : N;
-        int lnl = ln;                                       // laundered: the 16 element indices are the same for every item, and
-        asm volatile("" : "+v"(lnl));                       // the compiler would keep them all in registers across the loop (and spill)
-#pragma unroll
-        for (int j = 0; j < H; ++j) {
-            const int e = j * R + lnl;
-            float2 x = (e < N) ? src[e <= hx ? e : N - e] : make_float2(0.f, 0.f);
-            if (e > hx) x.y = -x.y;
-            dst[j] = x;
-        }
-    };
-    if ((int)blockIdx.x < n_items) { load_line(blockIdx.x, 0, vna); load_line(blockIdx.x, 1, vnb); }
-    for (int item = blockIdx.x; item < n_items; item += gridDim.x) {
-        const int img = item / lblocks, lb = item - img * lblocks;
-        // (the last item of a workgroup prefetches itself again: a conditional load would keep the old registers alive as the other
-        // arm of the merge)
-        const int nitem = item + (int)gridDim.x < n_items ? item + (int)gridDim.x : item;
-        float2 v[R];
-        auto mul_chirp = [&]() {
-#pragma unroll
-            for (int c = 0; c < H; c += TCH) {
-                float2 w[TCH];
-#pragma unroll
-                for (int j = 0; j < TCH; ++j) w[j] = bw[(c + j) * R + ln];
-#pragma unroll
-                for (int j = 0; j < TCH; ++j) v[c + j] = cmulf_conj(v[c + j], w[j]);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-#pragma unroll
-            for (int j = H; j < R; ++j) v[j] = make_float2(0.f, 0.f);
-        };
-        auto transform = [&]() __attribute__((always_inline)) {
-            mul_chirp();
-            fourstep_split_addtid<R, false, TCH>(v, wscr, wscr_lds, tw, ln, tid & 63);
-#pragma unroll
-            for (int c = 0; c < R; c += TCH) {
-                float2 w[TCH];
-#pragma unroll
-                for (int j = 0; j < TCH; ++j) w[j] = (c + j < H) ? fa[(c + j) * R] : fb[(R - (c + j)) * R];
-#pragma unroll
-                for (int j = 0; j < TCH; ++j) v[c + j] = cmulf_conj(v[c + j], w[j]);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            fourstep_split_addtid<R, true, TCH>(v, wscr, wscr_lds, tw, ln, tid & 63);
-            mul_chirp();
-        };
-#pragma unroll
-        for (int j = 0; j < H; ++j) v[j] = vna[j];
-        __builtin_amdgcn_sched_barrier(0);
-        load_line(nitem, 0, vna);
-        __builtin_amdgcn_sched_barrier(0);
-        transform();
-        float2 pa[H];
-#pragma unroll
-        for (int j = 0; j < H; ++j) { pa[j] = v[j]; v[j] = vnb[j]; }
-        __builtin_amdgcn_sched_barrier(0);
-        transform();
-        wave_lds_fence();
-#pragma unroll
-        for (int j = 0; j < H; ++j) { rowa[j * R + ln] = pa[j]; rowa[CSN + j * R + ln] = v[j]; }
-        __builtin_amdgcn_sched_barrier(0);
-        load_line(nitem, 1, vnb);                           // (needed a whole transform from now)
-        __builtin_amdgcn_sched_barrier(0);
-        lds_barrier();
-        const int col = lb * BL + li;
-        if (col < job.n_lines) {
-            float2* dst = job.out_t + (long long)img * job.out_t_is + col;
-            const float2* srow = tile + (2 * (li & 15) + (li >> 4)) * CSN;
-            int r0v = r0;                                   // (laundered like the lane index above: 32 row offsets of 64 bits)
-            asm volatile("" : "+v"(r0v));
-#pragma unroll
-            for (int i = 0; i < NIT; ++i) {
-                const int pos = r0v + POS_PER_IT * i;
-                if (pos < N) dst[(long long)pos * job.out_t_pitch] = srow[pos];
-            }
-        }
-        lds_barrier();
-    }
-}
-
-// The same for lines of 513..1024 points on the 2048-point wave-per-line FFT (tables of rowTB2_pass_kernel): one wave per line,
-// 8 lines per workgroup, 64-byte runs in the transposed store.
-__global__ void __launch_bounds__(512, 2) ifftTB2_kernel(IfftTBJob job) {
-    constexpr int R = 32, M = 2048, H = 16, NH = M / 2, LINES = 8, NT = 512, TCH = 8;
-    constexpr int RS = (R * W2K_PITCH) / 2 + 1;
-    constexpr int POS_PER_IT = NT / LINES, NIT = NH / POS_PER_IT;
-    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    float2* tw = reinterpret_cast<float2*>(smem_raw);         // 2048, lane order (lds_pos64)
-    float2* w64 = tw + M;                                     // 64
-    float2* bf = w64 + 64;                                    // NH + 2
-    float2* bw = bf + NH + 2;                                 // NH
-    float2* tile = bw + NH;                                   // LINES * RS
-    const int tid = threadIdx.x;
-    const int N = job.n_line;
-    for (int i = tid; i < M; i += NT) tw[lds_pos64(i)] = job.tw[i];
-    if (tid < 64) w64[tid] = job.tw2[tid];
-    for (int i = tid; i <= NH; i += NT) bf[i] = job.bf[i];
-    for (int i = tid; i < NH; i += NT) bw[i] = job.bw[i];
-    __syncthreads();
-    const int wv = tid >> 6, L = tid & 63, la = lam64(L);
-    const float sgn = (L & 1) ? -1.f : 1.f;
-    const int li = tid % LINES, r0 = tid / LINES;
-    float2* myrow = tile + wv * RS;
-    float* scr = reinterpret_cast<float*>(myrow);
-    const float2* fa = bf + la;
-    const float2* fb = bf - la;
-    const int lblocks = (job.n_lines + LINES - 1) / LINES;
-    const int n_items = lblocks * job.n_images;
-    float2 vn[H];
-    auto load_line = [&](int it) {
-        const int img = it / lblocks, lb = it - img * lblocks;
-        const int Lc = min(lb * LINES + wv, job.n_lines - 1);
-        const float2* src = job.in + (long long)img * job.in_is + (long long)Lc * job.in_pitch;
-        const int hx = job.herm ? N / 2 : N;
-#pragma unroll
-        for (int j = 0; j < H; ++j) {
-            const int e = j * 64 + la;
-            float2 x = (e < N) ? src[e <= hx ? e : N - e] : make_float2(0.f, 0.f);
-            if (e > hx) x.y = -x.y;
-            vn[j] = x;
-        }
-    };
-    if ((int)blockIdx.x < n_items) load_line(blockIdx.x);
-    for (int item = blockIdx.x; item < n_items; item += gridDim.x) {
-        const int img = item / lblocks, lb = item - img * lblocks;
-        const int Lc = min(lb * LINES + wv, job.n_lines - 1);
-        float2 v[R];
-#pragma unroll
-        for (int j = 0; j < H; ++j) v[j] = vn[j];
-        __builtin_amdgcn_sched_barrier(0);
-        if (item + (int)gridDim.x < n_items) load_line(item + (int)gridDim.x);
-        __builtin_amdgcn_sched_barrier(0);
-        auto mul_chirp = [&]() {
-#pragma unroll
-            for (int c = 0; c < H; c += TCH) {
-                float2 w[TCH];
-#pragma unroll
-                for (int j = 0; j < TCH; ++j) w[j] = bw[(c + j) * 64 + la];
-#pragma unroll
-                for (int j = 0; j < TCH; ++j) v[c + j] = cmulf_conj(v[c + j], w[j]);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-#pragma unroll
-            for (int j = H; j < R; ++j) v[j] = make_float2(0.f, 0.f);
-        };
-        mul_chirp();
-        fft2048_wave<false, TCH>(v, scr, tw, w64, L, la, sgn);
-#pragma unroll
-        for (int c = 0; c < R; c += TCH) {
-            float2 w[TCH];
-#pragma unroll
-            for (int j = 0; j < TCH; ++j) w[j] = (c + j < H) ? fa[(c + j) * 64] : fb[(R - (c + j)) * 64];
-#pragma unroll
-            for (int j = 0; j < TCH; ++j) v[c + j] = cmulf_conj(v[c + j], w[j]);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        fft2048_wave<true, TCH>(v, scr, tw, w64, L, la, sgn);
-        mul_chirp();
-        if (job.potential) {
-#pragma unroll
-            for (int j = 0; j < H; ++j) {
-                if (j % 4 == 0) __builtin_amdgcn_sched_barrier(0);
-                float sn, cs;
-                sincospif(job.sigma_over_pi * (v[j].x * job.scale), &sn, &cs);
-                v[j] = make_float2(cs, sn);
-            }
-        }
-        if (job.potential && (slice_of(job, img) & 1) == job.rows_parity) {
-            if (lb * LINES + wv < job.n_lines) {
-                float2* dst = job.out_rows + (long long)img * job.out_rows_is + (long long)Lc * job.out_rows_pitch;
-#pragma unroll
-                for (int j = 0; j < H; ++j) if (j * 64 + la < N) dst[j * 64 + la] = v[j];
-            }
-            continue;
-        }
-        wave_lds_fence();
-#pragma unroll
-        for (int j = 0; j < H; ++j) myrow[j * 64 + la] = v[j];
-        lds_barrier();
-        const int col = lb * LINES + li;
-        if (col < job.n_lines) {
-            float2* dst = job.out_t + (long long)img * job.out_t_is + col;
-#pragma unroll
-            for (int i = 0; i < NIT; ++i) {
-                const int pos = r0 + POS_PER_IT * i;
-                if (pos < N) dst[(long long)pos * job.out_t_pitch] = tile[li * RS + pos];
-            }
-        }
-        lds_barrier();
-    }
-}
-
-// Inverse transform of the potential build for 2048-point axes: one wave per line on fft2048_wave, stored transposed through an
-// 8-line tile (64-byte runs); two passes as ifftT2_kernel, the second with the potential epilogue.  (ifftT2_kernel<32>, the 2 R^2
-// layout with 64 complex per lane, spills and lost to the generic LDS kernel, which this one replaces.)  job.herm: as ifftTB_kernel.
-__global__ void __launch_bounds__(512, 2) ifftTW_kernel(IfftTBJob job) {
-    constexpr int R = 32, N = 2048, LINES = 8, NT = 512;
-    constexpr int RS = N + 1;
-    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    float2* tw = reinterpret_cast<float2*>(smem_raw);         // 2048, lane order
-    float2* w64 = tw + N;                                     // 64
-    float2* tile = w64 + 64;                                  // LINES * RS
-    const int tid = threadIdx.x;
-    for (int i = tid; i < N; i += NT) tw[lds_pos64(i)] = job.tw[i];
-    if (tid < 64) w64[tid] = job.tw2[tid];
-    __syncthreads();
-    const int wv = tid >> 6, L = tid & 63, la = lam64(L);
-    const float sgn = (L & 1) ? -1.f : 1.f;
-    const int li = tid % LINES, r0 = tid / LINES;
-    float2* myrow = tile + wv * RS;
-    float* scr = reinterpret_cast<float*>(myrow);
-    const int lblocks = job.n_lines / LINES;
-    const int n_items = lblocks * job.n_images;
-    float2 vn[R];
-    auto load_line = [&](int it) {
-        const int img = it / lblocks, lb = it - img * lblocks;
-        const float2* src = job.in + (long long)img * job.in_is + (long long)(lb * LINES + wv) * job.in_pitch;
-        const int hx = job.herm ? N / 2 : N;
-#pragma unroll
-        for (int j = 0; j < R; ++j) {
-            const int e = j * 64 + la;
-            float2 x = src[e <= hx ? e : N - e];
-            if (e > hx) x.y = -x.y;
-            vn[j] = x;
-        }
-    };
-    for (int item = blockIdx.x; item < n_items; item += gridDim.x) {      // (no register prefetch: 64 + 64 registers plus the transform spill)
-        const int img = item / lblocks, lb = item - img * lblocks;
-        load_line(item);
-        float2 (&v)[R] = vn;
-        fft2048_wave<true, 8>(v, scr, tw, w64, L, la, sgn);
-        if (job.potential) {
-#pragma unroll
-            for (int j = 0; j < R; ++j) {
-                if (j % 4 == 0) __builtin_amdgcn_sched_barrier(0);
-                float sn, cs;
-                sincospif(job.sigma_over_pi * (v[j].x * job.scale), &sn, &cs);
-                v[j] = make_float2(cs, sn);
-            }
-        }
-        if (job.potential && (slice_of(job, img) & 1) == job.rows_parity) {
-            float2* dst = job.out_rows + (long long)img * job.out_rows_is + (long long)(lb * LINES + wv) * job.out_rows_pitch;
-#pragma unroll
-            for (int j = 0; j < R; ++j) dst[j * 64 + la] = v[j];
-            continue;
-        }
-        wave_lds_fence();
-#pragma unroll
-        for (int j = 0; j < R; ++j) myrow[j * 64 + la] = v[j];
-        lds_barrier();
-        {
-            float2* dst = job.out_t + (long long)img * job.out_t_is + lb * LINES + li;
-#pragma unroll
-            for (int i = 0; i < N / (NT / LINES); ++i) {
-                const int pos = r0 + (NT / LINES) * i;
-                dst[(long long)pos * job.out_t_pitch] = tile[li * RS + pos];
-            }
-        }
-        lds_barrier();
     }
 }
 

@@ -15,6 +15,7 @@
 #include "../../include/mslice.h"
 #include "fft_generic.h"
 #include "fft_pow2.h"
+#include "pot_ifft.h"
 #include "rowtm_pass.h"
 #include "potential.h"
 #include "thermal.h"
@@ -1688,86 +1689,64 @@ int launch_structure_factor(msl_handle* h, const PotGroup& p) {
     return MSL_OK;
 }
 
-// One transposing pass of the potential's inverse transform along direction `o`, on the kernel of a PotIfft form:
+// One transposing pass of the potential's inverse transform along direction `o`, on the kernel of a PotIfft form; the LDS bytes and
+// the lines per work item are the kernel's own (pot_ifft.h: Ifft*Lds).
+template <typename Lds, typename Kernel>
+int launch_ifft(msl_handle* h, Kernel kernel, int per_cu, const IfftJob& j) {
+    const long long items = (long long)((j.n_lines + Lds::LINES - 1) / Lds::LINES) * j.n_images;
+    const long long slots = (long long)h->n_cus * std::max(1, std::min(per_cu, (int)((size_t)h->lds_limit / Lds::bytes)));
+    return launch_lds(h, kernel, dim3((unsigned)std::min(items, slots)), dim3(Lds::NT), Lds::bytes, K_OTHER, j);
+}
+
 // 2048-point lines, one wave per line (fft2048_wave)
-int launch_ifftTW(msl_handle* h, const msl_handle::OpDir& o, IfftTBJob j) {
-    constexpr int N2 = 2048;
-    const size_t lds = ((size_t)N2 + 64 + (size_t)8 * (N2 + 1)) * 8;
-    const long long items = (long long)(j.n_lines / 8) * j.n_images;
-    const int grid = (int)std::min<long long>(items, (long long)h->n_cus);
-    j.tw = o.tw; j.tw2 = o.tw2;
-    return launch_lds(h, ifftTW_kernel, dim3(grid), dim3(512), lds, K_OTHER, j);
+int launch_ifftTW(msl_handle* h, const msl_handle::OpDir& o, IfftJob j) {
+    j.tw = o.tw; j.tw2 = o.tw2; j.n_line = IfftTWLds::N;
+    return launch_ifft<IfftTWLds>(h, ifftTW_kernel, 1, j);
 }
 
 // lines of any length up to 1024 by chirp-z on the register FFTs (o.cz)
-int launch_ifftTB(msl_handle* h, const msl_handle::OpDir& o, IfftTBJob j) {
+int launch_ifftTB(msl_handle* h, const msl_handle::OpDir& o, IfftJob j) {
     const CzTables& t = o.cz;
-    j.tw = t.tw; j.bf = t.bf; j.bw = t.bw;
-    if (t.R == 64) {                                // 513 .. 1024 points: the wave-per-line 2048-point FFT
-        constexpr int M2 = 2048, NH2 = 1024, RS = (32 * W2K_PITCH) / 2 + 1;
-        const size_t lds2 = ((size_t)M2 + 64 + NH2 + 2 + NH2 + (size_t)8 * RS) * 8;
-        const long long items2 = (long long)((j.n_lines + 7) / 8) * j.n_images;
-        const int grid2 = (int)std::min<long long>(items2, (long long)h->n_cus);
-        j.tw2 = t.tw2;
-        return launch_lds(h, ifftTB2_kernel, dim3(grid2), dim3(512), lds2, K_OTHER, j);
-    }
-    const int R = t.R, M = R * R, NH = M / 2, CS = R * (R + 1) + 2;
-    const size_t lds = ((size_t)M + NH + 2 + NH + (size_t)16 * CS) * 8;
-    const int per_cu = std::max(1, std::min(R == 16 ? 4 : 1, (int)((size_t)h->lds_limit / lds)));
+    j.tw = t.tw; j.tw2 = t.tw2; j.bf = t.bf; j.bw = t.bw;
+    if (t.R == 64) return launch_ifft<IfftTB2Lds>(h, ifftTB2_kernel, 1, j);      // 513 .. 1024 points: the wave-per-line 2048-point FFT
+    if (t.R == 16) return launch_ifft<IfftTBLds<16>>(h, ifftTB_kernel<16>, 4, j);
     // first pass (no epilogue): two lines per group and tile round
-    if (R == 32 && !j.potential && !dbg_env("MSL_NO_TWO_LINE_IFFT")) {
-        constexpr int CSN = 514;
-        const size_t lds2 = ((size_t)M + NH + 2 + NH + (size_t)32 * CSN) * 8;
-        const long long items2 = (long long)((j.n_lines + 31) / 32) * j.n_images;
-        const int grid2 = (int)std::min<long long>(items2, (long long)h->n_cus);
-        return launch_lds(h, ifftTB_two_kernel, dim3(grid2), dim3(512), lds2, K_OTHER, j);
-    }
+    if (!j.potential && !dbg_env("MSL_NO_TWO_LINE_IFFT")) return launch_ifft<IfftTBTwoLds>(h, ifftTB_two_kernel, 1, j);
     // second pass on a half spectrum: two real lines per transform (32-line work items)
-    const bool pair = R == 32 && j.herm && j.potential && !dbg_env("MSL_NO_PAIRED_IFFT");
-    const long long items = (long long)((j.n_lines + (pair ? 31 : 15)) / (pair ? 32 : 16)) * j.n_images;
-    const dim3 grid((unsigned)std::min<long long>(items, (long long)h->n_cus * per_cu));
-    if (pair) return launch_lds(h, ifftTB_kernel<32, true>, grid, dim3(512), lds, K_OTHER, j);
-    if (R == 32) return launch_lds(h, ifftTB_kernel<32>, grid, dim3(512), lds, K_OTHER, j);
-    return launch_lds(h, ifftTB_kernel<16>, grid, dim3(256), lds, K_OTHER, j);
+    if (j.herm && j.potential && !dbg_env("MSL_NO_PAIRED_IFFT")) return launch_ifft<IfftTBLds<32, true>>(h, ifftTB_kernel<32, true>, 1, j);
+    return launch_ifft<IfftTBLds<32>>(h, ifftTB_kernel<32>, 1, j);
 }
 
 // lines of 2 R^2 = 512 points
-int launch_ifftT2(msl_handle* h, const msl_handle::OpDir& o, IfftT2Job j) {
-    constexpr int R = 16, N2 = R * R, N = 2 * N2;
-    const size_t lds = ((size_t)2 * N2 + (size_t)16 * (N + 1)) * 8;
-    const int per_cu = std::max(1, std::min(2, (int)((size_t)h->lds_limit / lds)));
+int launch_ifftT2(msl_handle* h, const msl_handle::OpDir& o, IfftJob j) {
+    j.tw = o.tw; j.tw2 = o.tw2; j.n_line = IfftT2Lds<16>::N;
     // second pass on a half spectrum: two real lines per transform (32-line work items)
-    const bool pair = j.herm && j.potential && j.n_lines % 32 == 0 && !dbg_env("MSL_NO_PAIRED_IFFT");
-    const long long items = (long long)(j.n_lines / (pair ? 32 : 16)) * j.n_images;
-    const dim3 grid((unsigned)std::min<long long>(items, (long long)h->n_cus * per_cu));
-    j.tw = o.tw; j.tw2 = o.tw2;
-    if (pair) return launch_lds(h, ifftT2_kernel<16, true>, grid, dim3(256), lds, K_OTHER, j);
-    return launch_lds(h, ifftT2_kernel<16>, grid, dim3(256), lds, K_OTHER, j);
+    if (j.herm && j.potential && j.n_lines % 32 == 0 && !dbg_env("MSL_NO_PAIRED_IFFT"))
+        return launch_ifft<IfftT2Lds<16, true>>(h, ifftT2_kernel<16, true>, 2, j);
+    return launch_ifft<IfftT2Lds<16>>(h, ifftT2_kernel<16>, 2, j);
 }
 
 // The transposing forms: TR -> TRT along y on the rows kx <= nx/2 (the others are their mirror images, taken by the second pass's
 // loads) in whole blocks of `line_block` lines (the surplus rows are never read), then TRT -> TR / TRT along x with the potential
-// epilogue: the slices a pass along x reads stay in TRT as rows.  Job = IfftTBJob or IfftT2Job (the same fields but n_line).
-template <typename Job>
-int ifft_transposed(msl_handle* h, const PotGroup& p, int line_block, int (*launch)(msl_handle*, const msl_handle::OpDir&, Job)) {
+// epilogue: the slices a pass along x reads stay in TRT as rows.
+int ifft_transposed(msl_handle* h, const PotGroup& p, int line_block, int (*launch)(msl_handle*, const msl_handle::OpDir&, IfftJob)) {
     const msl_config& c = h->cfg;
     const long long npix = (long long)c.nx * c.ny;
-    Job a{};
+    IfftJob a{};
     a.in = p.TR; a.out_t = p.TRT; a.out_rows = nullptr;
     a.in_is = a.out_t_is = npix; a.in_pitch = c.ny; a.out_t_pitch = c.nx; a.n_images = p.n_slices;
-    a.n_lines = (c.nx / 2 + 1 + line_block - 1) / line_block * line_block;
+    a.n_lines = (c.nx / 2 + 1 + line_block - 1) / line_block * line_block; a.n_line = c.ny;
     a.potential = 0; a.rows_parity = -1; a.slice_mod = c.nz;
-    Job b{};
+    IfftJob b{};
     b.in = p.TRT; b.out_t = p.TR; b.out_rows = p.TRT;
     b.in_is = b.out_t_is = b.out_rows_is = npix; b.in_pitch = c.nx; b.out_t_pitch = c.ny; b.out_rows_pitch = c.nx;
-    b.n_lines = c.ny; b.n_images = p.n_slices; b.potential = 1; b.herm = 1; b.slice_mod = c.nz;
+    b.n_lines = c.ny; b.n_line = c.nx; b.n_images = p.n_slices; b.potential = 1; b.herm = 1; b.slice_mod = c.nz;
     b.rows_parity = slice_is_transposed(h, 1) ? 1 : 0;       // (scheme b: slice s is read along x iff s is odd)
     // the epilogue takes sincospi(sigma_over_pi * (x * scale)): the two constants are multiplied in double here and rounded once (x * 1
     // is exact), instead of two rounded constants and two rounded products -- at a pixel with a phase of tens of radians each of
     // them is 2^-24 of the phase (white-potential parity, 2048 x 2048 x 3: E_pix 4.69e-5 with the constants apart)
     b.scale = 1.0f;
     b.sigma_over_pi = (float)(1.0 / ((double)c.nx * c.ny) / (c.dx * c.dx * c.dy * c.dy) * (c.sigma / M_PI));
-    if constexpr (std::is_same<Job, IfftTBJob>::value) { a.n_line = c.ny; b.n_line = c.nx; }
     const int rc = launch(h, h->opy, a);
     return rc ? rc : launch(h, h->opx, b);
 }
@@ -1808,9 +1787,9 @@ int ifft_inplace(msl_handle* h, const PotGroup& p) {
 int potential_ifft(msl_handle* h, const PotGroup& p) {
     h->cur = nullptr;
     switch (h->pot_ifft) {
-    case PI_WAVE2K: return ifft_transposed(h, p, 8, launch_ifftTW);
-    case PI_CHIRPZ: return ifft_transposed(h, p, 1, launch_ifftTB);
-    case PI_TWO:    return ifft_transposed(h, p, 16, launch_ifftT2);
+    case PI_WAVE2K: return ifft_transposed(h, p, IfftTWLds::LINE_BLOCK, launch_ifftTW);
+    case PI_CHIRPZ: return ifft_transposed(h, p, IfftTBLds<32>::LINE_BLOCK, launch_ifftTB);
+    case PI_TWO:    return ifft_transposed(h, p, IfftT2Lds<16>::LINE_BLOCK, launch_ifftT2);
     default:        return ifft_inplace(h, p);
     }
 }
