@@ -135,6 +135,28 @@ int  msl_set_slices(msl_handle* h, const double* lo, const double* hi);
  * potentials.py:188) be built first and Propagate() (multislice.py:258-275) supply the beam. */
 int  msl_set_beam(msl_handle* h, double wavelength, double sigma, double dz);
 
+/* Specimen tilt: the beam is inclined to the slice normal by (theta_x, theta_y), small-angle -- the specimen is
+ * sheared, not rotated -- so that free propagation through one slice moves the wave by (+dz tan_x, +dz tan_y), cyclically:
+ *     P(kx, ky) = exp(-i pi lambda dz kx^2) exp(-2 pi i dz kx tan_x)  x  exp(-i pi lambda dz ky^2) exp(-2 pi i dz ky tan_y).
+ * The pattern stays centred on the optic axis.  msl_set_tilt rewrites every propagator table of both axes (the plain tables, the
+ * split-order copy, the layer tap's conjugates, the filters of the convolution kinds) with kernels on the handle's stream: phases in
+ * float64, one rounding to float, no host table, no copy and no wait, so that a change of tilt is ordered behind the slice loops
+ * queued before it.  Valid any time after msl_create; the tilt stays on the handle, and a later msl_set_beam rebuilds the tables
+ * with it.  (0, 0) writes the untilted tables through the same kernels (equal to the host's up to one float rounding per entry);
+ * a handle on which msl_set_tilt was never called keeps the host tables and runs bit for bit as before.  A built S-matrix
+ * (msl_smatrix_build) belongs to the tilt it was built at and must be built again.  MSL_ERR_INVALID for a non-finite tangent; the
+ * small-angle limit (200 mrad in pyslice_amd/tilt.py) is the caller's.
+ * The one-pass kernels of a zero-padded convolution axis (msl_line_kernel_class 0, or a register length whose other axis is no
+ * multiple of 16) and the 2048-point wave kernel keep one half of an even table and mirror the other, which a tilted axis does not
+ * have.  While a non-zero tangent lies along such an axis the handle runs the two-pass loop (the loop of fft_path = 1 along that
+ * axis, on the plain tables) and builds its potentials in natural order; the stacks already built are carried over on the stream.
+ * That loop costs two launches per slice and the generic transform: lengths with a direct kernel (four-step, 2 R^2, mixed radix)
+ * next to a multiple of 16 keep the one-pass loop under any tilt.  A zero tangent along the axis brings the one-pass loop back.
+ * msl_get_tilt: tan_xy[0..1] = the tangents of the last msl_set_tilt, (0, 0) before the first.
+ * Not in the reference, whose propagator (multislice.py:262-275) has no tilt. */
+int  msl_set_tilt(msl_handle* h, double tan_x, double tan_y);
+int  msl_get_tilt(const msl_handle* h, double* tan_xy);
+
 /* Re-size the probe batch (re-allocates the (P,nx,ny) working buffers; probes must be set again). */
 int  msl_resize_probes(msl_handle* h, int32_t n_probes);
 

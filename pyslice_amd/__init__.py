@@ -22,10 +22,12 @@ from .imaging import Imaging
 from .image_data import ImageData
 from .spectroscopy import Spectroscopy
 from .spectrum_image_data import SpectrumImageData
+from .tilt import Tilt, Precession
 
 __all__ = ["Trajectory", "FrozenPhonons", "sigma_from_B", "PhononModes", "WFData", "Potential", "gridFromTrajectory", "getZfromElementName", "loadKirkland",
            "Probe", "Propagate", "create_batched_probes", "probe_grid", "wavelength", "m_effective",
            "MultisliceCalculator", "TACAWData", "HAADFData", "Detector", "STEMData", "Diffraction", "DiffractionData",
            "PolarDetector", "PolarData", "polar_bins", "polar_signals", "Thickness",
-           "Aberrations", "scherzer_defocus", "Imaging", "ImageData", "Spectroscopy", "SpectrumImageData"]
+           "Aberrations", "scherzer_defocus", "Imaging", "ImageData", "Spectroscopy", "SpectrumImageData",
+           "Tilt", "Precession"]
 __version__ = "0.1.0"

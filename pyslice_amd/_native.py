@@ -40,6 +40,7 @@ EXPORTS = [
     "msl_set_modes", "msl_build_modes", "msl_mode_positions",
     "msl_set_layer_reduce", "msl_layer_fetch", "msl_layer_pacbed_reset", "msl_layer_pacbed_add", "msl_layer_pacbed_download",
     "msl_layer_reduce_bytes",
+    "msl_set_tilt", "msl_get_tilt",
 ]
 DET_SIGNALS = {"intensity": 0, "amplitude": 1, "com_x": 2, "com_y": 3}      # include/mslice.h: MSL_DET_*
 POLAR_NONE, POLAR_MAX_BINS = 0xFFFF, 4096                                  # include/mslice.h: MSL_POLAR_*
@@ -160,6 +161,8 @@ def load():
         "msl_layer_pacbed_add": (C.c_int, [vp, i64]),
         "msl_layer_pacbed_download": (C.c_int, [vp, vp]),
         "msl_layer_reduce_bytes": (C.c_size_t, [vp, i32]),
+        "msl_set_tilt": (C.c_int, [vp, dbl, dbl]),
+        "msl_get_tilt": (C.c_int, [vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -276,6 +279,17 @@ class Engine:
 
     def set_beam(self, wavelength, sigma, dz):
         self._chk(self._lib.msl_set_beam(self._h, float(wavelength), float(sigma), float(dz)))
+
+    def set_tilt(self, tan_x, tan_y):
+        """specimen tilt (msl_set_tilt): the tangents of the beam's inclination along x and y.  Every propagator table is rewritten on
+        the device, on the handle's stream; the tilt stays on the handle"""
+        self._chk(self._lib.msl_set_tilt(self._h, float(tan_x), float(tan_y)))
+
+    def get_tilt(self):
+        """(tan_x, tan_y) of the last set_tilt, (0.0, 0.0) before the first (msl_get_tilt)"""
+        t = np.zeros(2, dtype=np.float64)
+        self._chk(self._lib.msl_get_tilt(self._h, _ptr(t)))
+        return float(t[0]), float(t[1])
 
     def resize_probes(self, n_probes):
         self._chk(self._lib.msl_resize_probes(self._h, int(n_probes)))

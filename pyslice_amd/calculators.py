@@ -29,6 +29,7 @@ from .potentials import (TORCH_AVAILABLE, _as_tensor, _device_index, atomic_numb
                          suggest_sampling)
 from .thermal import FrozenPhonons
 from .thickness import as_thickness
+from .tilt import Precession, Tilt
 from .phonons import PhononModes
 from .trajectory import Trajectory
 from .wf_data import WFData
@@ -130,7 +131,7 @@ class MultisliceCalculator:
     def __init__(self, device=None, force_cpu=False, *, output="host", dtype="complex128", progress=True,
                  gather="rank0", cache=False, k_window=None, frame_batch=None, k_bin=None, stream_tile=None, layers=None,
                  detectors=None, probe_batch=None, diffraction=None, aberrations=None, imaging=None, prism=None,
-                 spectroscopy=None, polar=None, thickness=None):
+                 spectroscopy=None, polar=None, thickness=None, tilt=None, precession=None):
         """
         device / force_cpu: as the reference (calculators.py:41).  There is no CPU path here, so
         force_cpu=True raises.  Keyword-only extras (not in the reference):
@@ -214,6 +215,20 @@ class MultisliceCalculator:
                    area, whatever L and P.  Needs detectors, polar or diffraction; allowed with k_window, aberrations, probe_batch,
                    frame_batch, FrozenPhonons / PhononModes; not with layers, cache, stream_tile, k_bin, imaging, spectroscopy,
                    prism, Diffraction(split=True) or several ranks.
+          tilt     a tilt.Tilt(x_mrad, y_mrad): the beam is inclined to the slice normal (small-angle: the specimen is sheared, free
+                   propagation through a slice of thickness dz moves the wave by dz tan(theta), cyclically; the pattern stays
+                   centred on the optic axis).  setup() has the device rewrite every propagator table (msl_set_tilt), so every run
+                   mode that goes through the slice loop honours it: run(), run_detectors(), run_polar(), run_diffraction() with
+                   and without split, run_images(), run_spectrum_image(), layers, thickness, prism, FrozenPhonons / PhononModes.
+                   Tilt() is no tilt: the run is bit for bit the one without the argument.  Not built with cache=True (the cache
+                   key does not carry the tilt).  |angle| <= 200 mrad.  A tilt along a grid length whose one-pass kernel is a
+                   zero-padded convolution or the 2048-point wave kernel runs on the slower two-pass loop (those kernels mirror half
+                   of an even table); lengths with a direct kernel next to a multiple of 16 keep the one-pass loop.
+          precession a tilt.Precession(angle_mrad, n_azimuth, phase0, centre): run_diffraction(), run_polar() and run_detectors()
+                   make one scan per tilt of the cone (one msl_set_tilt between two scans, ordered on the engine's stream) and
+                   return the mean of the single-tilt results, accumulated on the host in float64 in tilt order, with the tilts
+                   in `.tilts`.  Not with tilt (the cone has a centre).  Not built: the other run modes, stream_tile, cache,
+                   several ranks.
         """
         if force_cpu:
             raise NotImplementedError("pyslice_amd has no CPU path (force_cpu=True): use the reference for CPU runs")
@@ -331,6 +346,24 @@ class MultisliceCalculator:
             raise ValueError(f"aberrations: expected an Aberrations object, got {aberrations!r}")
         self._aberrations = aberrations
         self._probe_batch = None if probe_batch is None else int(probe_batch)
+        if tilt is not None and not isinstance(tilt, Tilt):
+            raise ValueError(f"tilt: expected a Tilt object, got {tilt!r}")
+        if precession is not None:
+            if not isinstance(precession, Precession):
+                raise ValueError(f"precession: expected a Precession object, got {precession!r}")
+            if tilt is not None:
+                raise ValueError("precession cannot be combined with tilt: the cone has a centre, Precession(..., centre=Tilt(...))")
+            for what, val in (("stream_tile", stream_tile is not None), ("cache=True", cache)):
+                if val:
+                    raise NotImplementedError(f"precession with {what} is not built")
+            if (detectors is None and diffraction is None and polar is None) or imaging is not None or spectroscopy is not None \
+                    or layers is not None:
+                raise NotImplementedError("precession with run(), layers, run_images(), run_spectrum_image() or run_streaming_tacaw() is not "
+                                          "built: give detectors=[...], polar=PolarDetector(...) or diffraction=Diffraction(...)")
+        if cache and tilt is not None and not tilt.is_zero:
+            raise NotImplementedError("cache=True with a tilt is not built: the cache key does not carry the tilt")
+        self._tilt, self._precession = tilt, precession
+        self._precessing = False                # inside the tilt loop of a precession run
         self._layers = None                     # validated slice indices (setup), nz - 1 last
         self._engine = None
         # reference calculators.py:70-76 (display names for Z <= 36)
@@ -422,6 +455,8 @@ class MultisliceCalculator:
         if self.probe_positions is None:
             self.probe_positions = [(lx / 2, ly / 2)]
         self._rank, self._world = distributed.rank_world()
+        if self._precession is not None and self._world > 1:
+            raise NotImplementedError("precession: a run over several ranks is not built")
         if self._spectroscopy is not None:
             self._setup_spectrum_image(trajectory, slice_axis)
             return
@@ -707,6 +742,8 @@ class MultisliceCalculator:
         eng.set_kirkland(loadKirkland())
         eng.set_slices(*slice_edges(self._slice_coords))
         eng.set_aberrations(self._aberrations)
+        if self._tilt is not None and not self._tilt.is_zero:   # (no tilt: the engine keeps the tables it was created with)
+            eng.set_tilt(*self._tilt.tangents)
         src = self._generated
         if src is not None:                                     # the base structure, once: every build is a generation by index
             modes = isinstance(src, PhononModes)                # (the mode builds do not read the widths)
@@ -880,6 +917,37 @@ class MultisliceCalculator:
                 None if self._polar is None else eng.polar_detect(0, n, B=real)[None],
                 None if self._diffraction is None else eng.diffract(0, n, B=real, bin=self._diffraction.bin)[None])
 
+    def _precess(self, run, fields):
+        """A precession run: one scan `run()` per tilt of the cone, the engine's tables rewritten in between (msl_set_tilt is ordered
+        on the stream behind the scan before it) -> the result of the last scan with every array named in `fields` (and the signals
+        of its .stem) replaced by the mean over the tilts, added in float64 in tilt order, and the tilts in .tilts"""
+        tilts = self._precession.tilts()
+        t0 = time.time()
+        sums, out = {}, None
+        self._precessing = True
+        try:
+            for t in tilts:
+                self._engine.set_tilt(*t.tangents)
+                out = run()
+                for owner, name in [(out, f) for f in fields] + ([(out.stem, "signals")] if getattr(out, "stem", None) is not None else []):
+                    val = getattr(owner, name)
+                    if val is None:
+                        continue
+                    key = (owner is out, name)
+                    if key in sums:
+                        sums[key] += val
+                    else:
+                        sums[key] = np.array(val, dtype=np.float64)
+        finally:
+            self._precessing = False
+        for (top, name), total in sums.items():
+            setattr(out if top else out.stem, name, total / len(tilts))
+        out.tilts = tilts
+        if getattr(out, "stem", None) is not None:
+            out.stem.tilts = tilts
+        self.elapsed = time.time() - t0
+        return out
+
     def run_diffraction(self):
         """Frame-averaged diffraction pattern of every probe position (4D-STEM / CBED): the loop of run_detectors(); msl_diffract
         reduces the exit spectra of every probe batch to (real, mx, my) float64 -- |Psi|^2 summed over the frames of the batch and
@@ -898,6 +966,8 @@ class MultisliceCalculator:
             raise RuntimeError("run_diffraction() needs MultisliceCalculator(diffraction=Diffraction(...))")
         if self._engine is None:
             raise RuntimeError("call setup() before run_diffraction()")
+        if self._precession is not None and not self._precessing:
+            return self._precess(self.run_diffraction, ('intensity', 'elastic'))
         eng = self._engine
         t0 = time.time()
         P, T = self.n_probes, self.n_frames
@@ -1035,6 +1105,8 @@ class MultisliceCalculator:
             raise RuntimeError("polar is set and detectors are not: call run_polar()")
         if self._detectors is None:
             raise RuntimeError("run_detectors() needs MultisliceCalculator(detectors=[...])")
+        if self._precession is not None and not self._precessing:
+            return self._precess(self.run_detectors, ('signals',))
         eng = self._engine
         t0 = time.time()
         P, T, D = self.n_probes, self.n_frames, len(self._detectors)
@@ -1067,6 +1139,8 @@ class MultisliceCalculator:
             raise RuntimeError("run_polar() needs MultisliceCalculator(polar=PolarDetector(...))")
         if self._engine is None:
             raise RuntimeError("call setup() before run_polar()")
+        if self._precession is not None and not self._precessing:
+            return self._precess(self.run_polar, ('signals',))
         eng, pol = self._engine, self._polar
         t0 = time.time()
         P, T, R, A = self.n_probes, self.n_frames, pol.n_rings, pol.n_azimuthal

@@ -34,6 +34,7 @@
 #include "coherent.h"
 #include "image.h"
 #include "smatrix.h"
+#include "propagator.h"
 
 using namespace msl;
 
@@ -139,8 +140,14 @@ struct msl_handle {
     int64_t intensity_F = 0;       // frequency bins of the resident intensity buffer (T after msl_tacaw, n_bins after a stream)
     DevBuf<char> scratch;          // reductions: partial sums / masks / index lists (grown on demand)
     bool onepass = false;
+    // onepass_planned: what msl_create planned; onepass: the loop that runs now -- false while a tilt lies along an axis whose one-pass
+    // kernel needs an even table (set_loop_mode, the only writer of onepass and pot_ifft after msl_create).  The invariant: whatever is
+    // SIZED or made once (psiT, psi0T and its transposed probes, transT, the pitches, scheme_b, need_psi0T) follows onepass_planned;
+    // whatever CHOOSES launches or the order of the stored slices (slice_loop, slice_is_transposed, transpose_odd_slices,
+    // restore_natural_slices, plan_pot_ifft, ifft_inplace, the transmission download) follows onepass.
+    bool onepass_planned = false;
     bool scheme_b = false;         // a direction of 2R^2 points: every pass transposes, first pass along y, final transpose if nz is odd
-    PotIfft pot_ifft = PI_LINES;   // inverse transform of the potential build, fixed at msl_create
+    PotIfft pot_ifft = PI_LINES;   // inverse transform of the potential build: planned at msl_create, PI_LINES while set_loop_mode has the two-pass loop on
     // one-pass kernel of one axis (AxisKind) and its tables: n = line length, R = radix of the base kind's register FFT (0: none).
     // `base` is the kind the axis has without the mixed-radix pass (== kind otherwise): a MIXED axis keeps the tables of its base
     // kind, on which the potential's inverse transform, the probes and the exit FFT still run, and the loop is one-pass iff both
@@ -175,6 +182,11 @@ struct msl_handle {
     DevBuf<float> V;
     DevBuf<float> intensity;
     DevBuf<float2> pxt, pyt;    // exp(-i pi lambda dz kx^2)/nx
+    // specimen tilt (msl_set_tilt): tan(theta) along x and y; once set, every propagator table is written on the device
+    // (fill_propagator_device) and tilt_work holds the float64 tables of its convolution sums.  Never set: the host tables, as ever
+    double tilt_tan[2] = {0.0, 0.0};
+    bool tilt_set = false;
+    DevBuf<double2> tilt_work;
     // the result, (L, P, T_local, wpitch) with L = 1 + the layers of a thickness series (msl_set_layers): `layers` owns it for every
     // L, wf is a view of its last block, the exit waves.  layer_block: result block of every slice (-1: not a layer); tap: the
     // natural-order image set the layer tap transforms (FB * P images, psi's layout); tap_cx / tap_cy: the unscaled conjugate
@@ -904,7 +916,7 @@ int transpose_probes(msl_handle* h) {
     const size_t group = (size_t)c.n_probes * c.nx * h->pitch;
     for (int f = 1; f < h->FB; ++f)
         HIPCHK(h, hipMemcpyAsync(h->psi0 + f * group, h->psi0, group * sizeof(float2), hipMemcpyDeviceToDevice, h->stream));
-    if (!h->onepass || !h->need_psi0T) return MSL_OK;       // the first pass runs along y, on layout A
+    if (!h->onepass_planned || !h->need_psi0T) return MSL_OK;       // the first pass runs along y, on layout A
     dim3 grid((c.ny + 31) / 32, (c.nx + 31) / 32, c.n_probes * h->FB);
     hipLaunchKernelGGL(transpose_kernel, grid, dim3(256), 0, h->stream, h->psi0, h->psi0T, c.nx, c.ny, h->pitch, h->pitchT,
                        (long long)c.nx * h->pitch, (long long)c.ny * h->pitchT);
@@ -932,6 +944,24 @@ int transpose_odd_slices(msl_handle* h, int slot) {
         const size_t off = (size_t)slot * c.nz * npix + (size_t)(first + 2 * z0) * npix;
         hipLaunchKernelGGL(transpose_kernel, grid, dim3(256), 0, h->stream, h->trans + off, h->transT + off, c.nx, c.ny,
                            c.ny, c.nx, (long long)(2 * npix), (long long)(2 * npix));
+    }
+    HIPCHK(h, hipGetLastError());
+    return MSL_OK;
+}
+
+// the reverse: the natural copies of the slices the one-pass loop keeps transposed, transT -> trans, of the stack in batch slot `slot`
+int restore_natural_slices(msl_handle* h, int slot) {
+    if (!h->onepass) return MSL_OK;
+    const msl_config& c = h->cfg;
+    const size_t npix = (size_t)c.nx * c.ny;
+    const int first = slice_is_transposed(h, 0) ? 0 : 1;
+    const int count = (c.nz - first + 1) / 2;
+    for (int z0 = 0; z0 < count; z0 += 65535) {
+        const int nzb = std::min(65535, count - z0);
+        dim3 grid((c.nx + 31) / 32, (c.ny + 31) / 32, nzb);
+        const size_t off = (size_t)slot * c.nz * npix + (size_t)(first + 2 * z0) * npix;
+        hipLaunchKernelGGL(transpose_kernel, grid, dim3(256), 0, h->stream, h->transT + off, h->trans + off, c.ny, c.nx, c.nx, c.ny,
+                           (long long)(2 * npix), (long long)(2 * npix));
     }
     HIPCHK(h, hipGetLastError());
     return MSL_OK;
@@ -1371,6 +1401,45 @@ int fill_propagator(msl_handle* h) {
         if (o->base == AX_TWO && (rc = fill_split(o->ptab, o->n, d))) return rc;
         // convolution kinds: filter of the zero-padded cyclic convolution that IS the propagation along the axis
         if (conv_len(*o) && (rc = fill_conv_filter(h, *o, d))) return rc;
+    }
+    return MSL_OK;
+}
+
+// The same tables with the tilt factor exp(-2 pi i dz tan(theta) k), written by the kernels of propagator.h on the handle's stream:
+// no host table, no copy and no wait, so a change of tilt is ordered behind the passes of the tilt before it.
+int fill_propagator_device(msl_handle* h) {
+    const msl_config& c = h->cfg;
+    size_t work = 0;                                        // float64 entries of the convolution sums: P, E (n each), q, W (M each)
+    for (const msl_handle::OpDir* o : {&h->opx, &h->opy})
+        if (conv_len(*o)) work = std::max(work, 2 * (size_t)o->n + 2 * (size_t)conv_len(*o));
+    int rc = h->tilt_work.reserve(h, work);
+    if (rc) return rc;
+    for (int axis = 0; axis < 2; ++axis) {
+        const msl_handle::OpDir& o = axis ? h->opy : h->opx;
+        const int n = axis ? c.ny : c.nx, M = conv_len(o);
+        const double d = axis ? c.dy : c.dx;
+        // the half-spectrum layout holds the filter of an even table only, and no pass reads qf under a tilted axis (set_loop_mode has
+        // the two-pass loop on, a mixed axis reads the plain table): the filter is written at a zero tangent, which every way back to
+        // the convolution pass goes through (msl_set_tilt with 0 along the axis)
+        const bool filter = M && h->tilt_tan[axis] == 0.0;
+        double2* Pd = filter ? (double2*)h->tilt_work : nullptr;
+        double2* Ed = filter ? Pd + n : nullptr;
+        double2* q = filter ? Ed + n : nullptr;
+        double2* Wd = filter ? q + M : nullptr;
+        float2* split = o.base == AX_TWO ? (float2*)o.ptab : nullptr;
+        const int lanes = filter ? std::max(n, M) : n;
+        hipLaunchKernelGGL(propagator_tables_kernel, dim3((unsigned)((lanes + PROP_BLOCK - 1) / PROP_BLOCK)), dim3(PROP_BLOCK), 0, h->stream,
+                           n, M, 1.0 / (n * d), 0.5 * c.wavelength * c.dz, c.dz * h->tilt_tan[axis], axis ? h->pyt : h->pxt, split,
+                           axis ? h->tap_cy : h->tap_cx, Pd, Ed, Wd);
+        HIPCHK(h, hipGetLastError());
+        if (!filter) continue;
+        const int gap = M - 2 * n + 1, entries = (int)conv_filter_entries(o);
+        hipLaunchKernelGGL(conv_lag_kernel, dim3((unsigned)(n + (gap + PROP_BLOCK - 1) / PROP_BLOCK)), dim3(PROP_BLOCK), 0, h->stream, n, M,
+                           Pd, Ed, q);
+        HIPCHK(h, hipGetLastError());
+        hipLaunchKernelGGL(conv_filter_kernel, dim3((unsigned)entries), dim3(PROP_BLOCK), 0, h->stream, n, M, entries,
+                           o.base == AX_CONV4K ? 1 : 0, q, Wd, (float2*)o.qf);
+        HIPCHK(h, hipGetLastError());
     }
     return MSL_OK;
 }
@@ -2078,7 +2147,7 @@ static int alloc_probe_buffers(msl_handle* h, int n_probes) {
     const size_t images = (size_t)n_probes * h->FB, elems = (size_t)c.nx * h->pitch * images, elemsT = (size_t)c.ny * h->pitchT * images;
     int rc;
     if ((rc = h->psi0.alloc(h, elems)) || (rc = h->psi.alloc(h, elems))) return rc;
-    if (h->onepass && ((rc = h->psiT.alloc(h, elemsT)) || (h->need_psi0T && (rc = h->psi0T.alloc(h, elemsT))))) return rc;
+    if (h->onepass_planned && ((rc = h->psiT.alloc(h, elemsT)) || (h->need_psi0T && (rc = h->psi0T.alloc(h, elemsT))))) return rc;
     return h->d_xy.alloc(h, (size_t)2 * n_probes);
 }
 
@@ -2174,7 +2243,7 @@ int msl_create(const msl_config* cfg, msl_handle** out) {
         plan_axis_kind(h, h->opx, cfg->nx, cfg->ny, h->Rx, h->plan_x.M, want);
         plan_axis_kind(h, h->opy, cfg->ny, cfg->nx, h->Ry, h->plan_y.M, want);
         if ((rc = make_axis_tables(h, h->opx, h->opy)) || (rc = make_axis_tables(h, h->opy, h->opx))) return bail(rc);
-        h->onepass = h->opx.base != AX_NONE && h->opy.base != AX_NONE;
+        h->onepass = h->onepass_planned = h->opx.base != AX_NONE && h->opy.base != AX_NONE;
         h->scheme_b = h->onepass && !(h->opx.kind == AX_FOURSTEP && h->opy.kind == AX_FOURSTEP);
         if (h->pitch == cfg->ny && h->onepass) h->pitch = cfg->ny + 16;        // pad the work buffers of 2R^2 grids too
         if (h->onepass && (h->pitch & 1)) ++h->pitch;                          // even pitches: the transposed stores write two lines (16 bytes) at a time
@@ -2255,7 +2324,7 @@ int msl_set_beam(msl_handle* h, double wavelength, double sigma, double dz) {
         HIPCHK(h, hipStreamSynchronize(h->stream));
         smatrix_release(h);
     }
-    int rc = fill_propagator(h);
+    int rc = h->tilt_set ? fill_propagator_device(h) : fill_propagator(h);      // a tilt stays on the handle
     if (rc) return rc;
     if (h->have_potential) {
         if (!h->V) return fail(h, MSL_ERR_STATE, "msl_set_beam: potential present but V not kept (keep_potential=0); rebuild the potential");
@@ -2266,6 +2335,60 @@ int msl_set_beam(msl_handle* h, double wavelength, double sigma, double dz) {
         if ((rc = transpose_odd_slices(h, h->cur_batch))) return rc;
         HIPCHK(h, hipStreamSynchronize(h->stream));
     }
+    return MSL_OK;
+}
+
+namespace {
+
+// The convolution passes keep the first half of their filter and mirror the rest (Q[M - k] = Q[k]), and the 2048-point wave kernel
+// reads its Fresnel factors the same way: both hold for an even table only, which a tilted axis does not have.  The direct kernels
+// (four-step, 2 R^2, mixed radix) read whole tables and take any tilt; so does the two-pass loop, on the plain tables.
+bool tilt_needs_two_pass(const msl_handle* h, double tan_x, double tan_y) {
+    auto even_only = [](const msl_handle::OpDir& o) { return o.kind == AX_CONV || o.kind == AX_CONV2K || o.kind == AX_CONV4K || o.kind == AX_WAVE2K; };
+    return (tan_x != 0.0 && even_only(h->opx)) || (tan_y != 0.0 && even_only(h->opy));
+}
+
+// Switch a handle planned for the one-pass loop to the two-pass loop and back, on the stream.  The two-pass loop and the potential
+// build next to it (PI_LINES, untransposed stores) read and write `trans` in natural order only; the one-pass loop keeps every second
+// slice transposed in transT.  The stacks a potential build has filled are carried over, every batch slot.
+int set_loop_mode(msl_handle* h, bool onepass) {
+    if (onepass == h->onepass) return MSL_OK;
+    int rc = MSL_OK;
+    if (!onepass) {
+        for (int f = 0; h->have_potential && f < h->FB && rc == MSL_OK; ++f) rc = restore_natural_slices(h, f);
+        if (rc) return rc;
+        h->onepass = false;
+        h->pot_ifft = PI_LINES;
+        return MSL_OK;
+    }
+    h->onepass = true;
+    h->pot_ifft = plan_pot_ifft(h);
+    for (int f = 0; h->have_potential && f < h->FB && rc == MSL_OK; ++f) rc = transpose_odd_slices(h, f);
+    return rc;
+}
+
+}  // namespace
+
+int msl_set_tilt(msl_handle* h, double tan_x, double tan_y) {
+    if (!h) return fail(h, MSL_ERR_INVALID, "null handle");
+    if (!std::isfinite(tan_x) || !std::isfinite(tan_y)) return fail(h, MSL_ERR_INVALID, "msl_set_tilt: tan_x and tan_y must be finite");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    {   // the loop that can run this tilt; a refused switch leaves the handle as it was
+        const int rc = set_loop_mode(h, h->onepass_planned && !tilt_needs_two_pass(h, tan_x, tan_y));
+        if (rc) return rc;
+    }
+    const double old[2] = {h->tilt_tan[0], h->tilt_tan[1]};
+    h->tilt_tan[0] = tan_x; h->tilt_tan[1] = tan_y;
+    const int rc = fill_propagator_device(h);
+    if (rc) { h->tilt_tan[0] = old[0]; h->tilt_tan[1] = old[1]; return rc; }
+    h->tilt_set = true;
+    h->sm_built = false;                                    // an S-matrix belongs to the tilt it was built at
+    return MSL_OK;
+}
+
+int msl_get_tilt(const msl_handle* h, double* tan_xy) {
+    if (!h || !tan_xy) return MSL_ERR_INVALID;
+    tan_xy[0] = h->tilt_tan[0]; tan_xy[1] = h->tilt_tan[1];
     return MSL_OK;
 }
 
@@ -3606,17 +3729,8 @@ int msl_download(msl_handle* h, msl_buffer what, void* dst, size_t bytes, int64_
     if (what == MSL_BUF_EXIT && !h->have_exit) return fail(h, MSL_ERR_STATE, "msl_download: no exit waves (call msl_propagate)");
     if (what == MSL_BUF_TRANSMISSION && h->onepass && h->have_potential) {
         // the one-pass loop keeps every second slice transposed in its own buffer: restore the natural copies
-        const size_t npix = (size_t)h->cfg.nx * h->cfg.ny;
-        const int first = slice_is_transposed(h, 0) ? 0 : 1;
-        const int count = (h->cfg.nz - first + 1) / 2;
-        for (int z0 = 0; z0 < count; z0 += 65535) {
-            const int nzb = std::min(65535, count - z0);
-            dim3 grid((h->cfg.nx + 31) / 32, (h->cfg.ny + 31) / 32, nzb);
-            const size_t off = (size_t)h->cur_batch * h->cfg.nz * npix + (size_t)(first + 2 * z0) * npix;
-            hipLaunchKernelGGL(transpose_kernel, grid, dim3(256), 0, h->stream, h->transT + off, h->trans + off,
-                               h->cfg.ny, h->cfg.nx, h->cfg.nx, h->cfg.ny, (long long)(2 * npix), (long long)(2 * npix));
-        }
-        HIPCHK(h, hipGetLastError());
+        const int rc = restore_natural_slices(h, h->cur_batch);
+        if (rc) return rc;
     }
     size_t off = 0, len = total;
     if (count > 0 && what != MSL_BUF_WAVEFUNCTION && what != MSL_BUF_INTENSITY)

@@ -77,6 +77,7 @@ class DiffractionData:
     layer: Optional[np.ndarray] = None
     thickness: Optional[np.ndarray] = None
     patterns: str = "position"
+    tilts: Optional[list] = None            # the tilt.Tilt of every run of a precession average (tilt order); None otherwise
 
     def __post_init__(self):
         if self.patterns not in ("position", "pacbed"):

@@ -11,6 +11,7 @@ import numpy as np
 from . import _native
 from .aberrations import Aberrations
 from .potentials import TORCH_AVAILABLE, _as_tensor, _device_index
+from .tilt import as_tilt
 
 if TORCH_AVAILABLE:
     import torch
@@ -180,17 +181,25 @@ def create_batched_probes(base_probe, probe_positions, device=None):
     return out
 
 
-def Propagate(probe, potential, device=None):
+def Propagate(probe, potential, device=None, tilt=None):
     """Multislice propagation (reference multislice.py:237-299).
 
     Returns the exit wave(s) as complex128, squeezed to (nx,ny) for a single probe, and -- like the
     reference -- leaves `probe.array` 3-D afterwards (quirk Q13).
+
+    tilt (not in the reference): a tilt.Tilt, the inclination of the beam to the slice normal; the propagator tables are rewritten
+    on the device (msl_set_tilt).  None or Tilt() is no tilt: on a potential that was never propagated with a tilt the call runs exactly
+    as without the argument (the host tables, no call).  After one tilted call on a potential its engine keeps device-written tables:
+    later untilted calls set (0, 0) through the same kernels, whose tables equal the host's up to one float rounding per entry.
     """
+    tilt = as_tilt(tilt, "Propagate: tilt")
     eng = potential._engine
     kind, payload = probe._recipe()
     zs = _to_numpy(potential.zs)
     dz = zs[1] - zs[0] if len(zs) > 1 else 0.5
     eng.set_beam(probe.wavelength, interaction_sigma(probe.eV), dz)
+    if not tilt.is_zero or eng.get_tilt() != (0.0, 0.0):    # the potential's engine is shared and the tilt stays on it
+        eng.set_tilt(*tilt.tangents)
     eng.resize_probes(len(payload))
     if kind == "analytic":
         eng.set_aberrations(probe.aberrations)     # always: the potential's engine is shared and the state stays on it

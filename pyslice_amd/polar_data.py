@@ -155,6 +155,7 @@ class PolarData:
     stem: Optional[STEMData] = None
     layer: Optional[np.ndarray] = None
     thickness: Optional[np.ndarray] = None
+    tilts: Optional[list] = None            # the tilt.Tilt of every run of a precession average (tilt order); None otherwise
 
     def __post_init__(self):
         R, A = self.polar.n_rings, self.polar.n_azimuthal

@@ -125,6 +125,7 @@ class STEMData:
     ys: np.ndarray = None
     layer: Optional[np.ndarray] = None
     thickness: Optional[np.ndarray] = None
+    tilts: Optional[list] = None            # the tilt.Tilt of every run of a precession average (tilt order); None otherwise
 
     def __post_init__(self):
         if self.xs is None or self.ys is None:
