@@ -90,7 +90,9 @@ typedef enum {
     MSL_BUF_STREAM_REF = 10,   /* (P,K) c64         the reference pattern (msl_tacaw_stream_set_reference), NULL when none is set */
     MSL_BUF_LAYERS = 11,       /* (L,P,T_local,pitch) c64  the spectra of every layer (msl_set_layers), the exit wave last; L = 1 without
                                 *                    layers (then the same memory as MSL_BUF_WAVEFUNCTION) */
-    MSL_BUF_SMATRIX = 12       /* (Bm,nx,ny) c64    the PRISM S-matrix of the last msl_smatrix_build: the exit waves of the Bm beams */
+    MSL_BUF_SMATRIX = 12,      /* (Bm,nx,ny) c64    the PRISM S-matrix of the last msl_smatrix_build: the exit waves of the Bm beams */
+    MSL_BUF_FORMFACTOR_ABS = 13, /* (n_species,nx,ny) f32 the absorptive tables g of the last build with msl_set_absorption(.., absorb != 0) */
+    MSL_BUF_ABSORPTION = 14    /* (nz,nx,ny) f32    Omega of the last build with msl_set_absorption(.., absorb != 0) */
 } msl_buffer;
 
 typedef struct {
@@ -279,6 +281,25 @@ int  msl_set_modes(msl_handle* h, const int32_t* basis_index, int64_t n_atoms, i
                    const double* W, int32_t n_modes, int32_t dynamic);
 int  msl_build_modes(msl_handle* h, uint64_t seed, int64_t first_frame, int32_t count);
 int  msl_mode_positions(msl_handle* h, uint64_t seed, int64_t frame, double* out);
+
+/* ---- absorptive potential: Debye-Waller damping and TDS absorption in one pass ----
+ * The thermal average of the elastic wave without an ensemble: every later msl_build_potential / msl_build_potentials makes
+ *     t_s = exp(i sigma Vbar_s - sigma^2 Omega_s)
+ * Vbar the Debye-Waller-smeared mean potential, Omega = 1/2 Var V under independent Gaussian displacements (the second cumulant of
+ * <exp(i sigma V)>; pyslice_amd/absorptive.py is the definition).  Per species, on the handle's grid, with D = exp(-2 pi^2 u^2 q^2):
+ *     Vbar1 = Re ifft2(f D) / (dx^2 dy^2),  Om1 = 1/2 (Re ifft2(D fft2(V1^2)) - Vbar1^2),  g = Re fft2(Om1) dx^2 dy^2
+ * and Vbar, Omega are the structure-factor sums of the potential build with the tables f D and g.
+ * u_by_Z_103: the rms displacement per Cartesian axis (Angstrom, finite and >= 0) of every atomic number 1..103 -- the sigma of
+ *   msl_set_structure; NULL clears absorption and frees its tables and stacks: the next build is that of a handle it was never set on.
+ * absorb == 0 keeps the Debye-Waller damping and leaves Omega out (|t| = 1).
+ * Every call drops the potential the handle holds (msl_propagate is MSL_ERR_STATE until the next build): the transmission functions
+ *   and the stacks of an earlier build belong to the widths and the flag they were built with.
+ * While it is set: MSL_BUF_FORMFACTOR is f D, MSL_BUF_FORMFACTOR_ABS g, MSL_BUF_POTENTIAL Vbar (also without keep_potential),
+ * MSL_BUF_ABSORPTION Omega, each of the current batch slot; msl_set_beam makes t again from the two resident stacks (Omega and g do not
+ * depend on sigma); msl_build_thermal / msl_build_modes return MSL_ERR_STATE -- the vibration would be counted twice.  Costs two
+ * float32 stacks (frame_batch, nz, nx, ny) and a second structure factor and inverse transform per build.  The model is the classical
+ * weak-fluctuation one: third order in sigma V per atom.  Synchronous.  Not in the reference. */
+int  msl_set_absorption(msl_handle* h, const double* u_by_Z_103, int32_t absorb);
 
 /* TACAW: intensity[p,w,kx,ky] = | fftshift_t fft_t( Psi - <Psi>_t ) |^2 over a (B,T,npix) c64 device
  * array.  src == NULL uses the handle's own wavefunction buffer (B=P, T=T_local, npix=nx*ny) and

@@ -7,6 +7,7 @@ library `libmslice.so` (include/mslice.h, pyslice_amd/csrc).  There is no CPU fa
 from .trajectory import Trajectory
 from .thermal import FrozenPhonons, sigma_from_B
 from .phonons import PhononModes
+from .absorptive import AbsorptivePotential, absorptive_tables, absorptive_transmission, mean_transmission_exact
 from .wf_data import WFData
 from .potentials import Potential, gridFromTrajectory, getZfromElementName, loadKirkland
 from .multislice import Probe, Propagate, create_batched_probes, probe_grid, wavelength, m_effective
@@ -24,7 +25,8 @@ from .spectroscopy import Spectroscopy
 from .spectrum_image_data import SpectrumImageData
 from .tilt import Tilt, Precession
 
-__all__ = ["Trajectory", "FrozenPhonons", "sigma_from_B", "PhononModes", "WFData", "Potential", "gridFromTrajectory", "getZfromElementName", "loadKirkland",
+__all__ = ["Trajectory", "FrozenPhonons", "sigma_from_B", "PhononModes", "AbsorptivePotential", "absorptive_tables",
+           "absorptive_transmission", "mean_transmission_exact", "WFData", "Potential", "gridFromTrajectory", "getZfromElementName", "loadKirkland",
            "Probe", "Propagate", "create_batched_probes", "probe_grid", "wavelength", "m_effective",
            "MultisliceCalculator", "TACAWData", "HAADFData", "Detector", "STEMData", "Diffraction", "DiffractionData",
            "PolarDetector", "PolarData", "polar_bins", "polar_signals", "Thickness",

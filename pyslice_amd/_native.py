@@ -16,7 +16,8 @@ LIB_PATH = os.environ.get("MSL_LIB") or os.path.join(_HERE, "libmslice.so")
 ABI_VERSION = 3          # include/mslice.h: MSL_ABI_VERSION
 MSL_OK, MSL_ERR_INVALID, MSL_ERR_HIP, MSL_ERR_UNSUPPORTED, MSL_ERR_STATE, MSL_ERR_NOMEM = 0, -1, -2, -3, -4, -5
 (BUF_PROBES, BUF_EXIT, BUF_POTENTIAL, BUF_TRANSMISSION, BUF_WAVEFUNCTION, BUF_INTENSITY, BUF_FORMFACTOR,
- BUF_STREAM_ACC, BUF_STREAM_S1, BUF_STREAM_S2, BUF_STREAM_REF, BUF_LAYERS, BUF_SMATRIX) = range(13)
+ BUF_STREAM_ACC, BUF_STREAM_S1, BUF_STREAM_S2, BUF_STREAM_REF, BUF_LAYERS, BUF_SMATRIX, BUF_FORMFACTOR_ABS,
+ BUF_ABSORPTION) = range(15)
 
 EXPORTS = [
     "msl_abi_version", "msl_line_kernel_class", "msl_last_error", "msl_create", "msl_destroy", "msl_set_kirkland", "msl_set_slices",
@@ -41,6 +42,7 @@ EXPORTS = [
     "msl_set_layer_reduce", "msl_layer_fetch", "msl_layer_pacbed_reset", "msl_layer_pacbed_add", "msl_layer_pacbed_download",
     "msl_layer_reduce_bytes",
     "msl_set_tilt", "msl_get_tilt",
+    "msl_set_absorption",
 ]
 DET_SIGNALS = {"intensity": 0, "amplitude": 1, "com_x": 2, "com_y": 3}      # include/mslice.h: MSL_DET_*
 POLAR_NONE, POLAR_MAX_BINS = 0xFFFF, 4096                                  # include/mslice.h: MSL_POLAR_*
@@ -151,6 +153,7 @@ def load():
         "msl_tacaw_welch_layer": (C.c_int, [vp, i32, i32, i32, vp]),
         "msl_set_structure": (C.c_int, [vp, vp, vp, vp, i64, i32, i32, i32]),
         "msl_build_thermal": (C.c_int, [vp, C.c_uint64, i64, i32]),
+        "msl_set_absorption": (C.c_int, [vp, vp, i32]),
         "msl_thermal_positions": (C.c_int, [vp, C.c_uint64, i64, vp]),
         "msl_set_modes": (C.c_int, [vp, vp, i64, i32, vp, vp, vp, i32, i32]),
         "msl_build_modes": (C.c_int, [vp, C.c_uint64, i64, i32]),
@@ -269,6 +272,18 @@ class Engine:
         if t.size != 103 * 12:
             raise ValueError(f"Kirkland table must hold 103x3x4 values, got shape {t.shape}")
         self._chk(self._lib.msl_set_kirkland(self._h, _ptr(t)))
+
+    def set_absorption(self, u_by_Z=None, absorb=True):
+        """absorptive potential (msl_set_absorption; the definition is absorptive.py): u_by_Z = 103 rms widths per Cartesian axis
+        (Angstrom), one per atomic number, for every later build_potential / build_potentials; None clears it.  absorb=False keeps
+        the Debye-Waller damping alone."""
+        if u_by_Z is None:
+            self._chk(self._lib.msl_set_absorption(self._h, None, 0))
+            return
+        u = np.ascontiguousarray(u_by_Z, dtype=np.float64)
+        if u.shape != (103,):
+            raise ValueError(f"u_by_Z must hold one width per atomic number 1..103, got shape {u.shape}")
+        self._chk(self._lib.msl_set_absorption(self._h, _ptr(u), int(bool(absorb))))
 
     def set_slices(self, lo, hi):
         lo = np.ascontiguousarray(lo, dtype=np.float64)
@@ -879,6 +894,14 @@ class Engine:
 
     def form_factors(self, n_species):
         return self.download(BUF_FORMFACTOR, np.float32, (n_species, self.nx, self.ny))
+
+    def form_factors_abs(self, n_species):
+        """the absorptive tables g of the last build with set_absorption(.., absorb=True)"""
+        return self.download(BUF_FORMFACTOR_ABS, np.float32, (n_species, self.nx, self.ny))
+
+    def absorption(self):
+        """Omega (nz, nx, ny) of the last build with set_absorption(.., absorb=True)"""
+        return self.download(BUF_ABSORPTION, np.float32, (self.nz, self.nx, self.ny))
 
     def synchronize(self):
         self._chk(self._lib.msl_synchronize(self._h))

@@ -31,6 +31,7 @@ from .thermal import FrozenPhonons
 from .thickness import as_thickness
 from .tilt import Precession, Tilt
 from .phonons import PhononModes
+from .absorptive import AbsorptivePotential
 from .trajectory import Trajectory
 from .wf_data import WFData
 
@@ -408,7 +409,11 @@ class MultisliceCalculator:
 
         It may also be a phonons.PhononModes: its n_frames frames, synthesised on the device from a set of phonon modes
         (msl_set_structure and msl_set_modes once, msl_build_modes per frame batch) -- a time-coherent record whose TACAW spectrum
-        shows the dispersion, or independent correlated snapshots.  The same run modes, the same three refusals."""
+        shows the dispersion, or independent correlated snapshots.  The same run modes, the same three refusals.
+
+        Or an absorptive.AbsorptivePotential: ONE frame whose transmission functions are the thermal average exp(i sigma Vbar -
+        sigma^2 Omega) (msl_set_absorption once; the build is the ordinary one of the host positions).  Every run mode but
+        spectroscopy; the same three refusals."""
         # a generated source: frames made on the device by index from a resident structure, never read from a host array
         self._generated = trajectory if isinstance(trajectory, (FrozenPhonons, PhononModes)) else None
         if self._generated is not None:
@@ -417,6 +422,14 @@ class MultisliceCalculator:
                               ("a run over several ranks", distributed.rank_world()[1] > 1)):
                 if val:
                     raise NotImplementedError(f"{kind}: {what} is not built")
+        # (not in the reference) an absorptive.AbsorptivePotential: one frame whose builds go through msl_set_absorption
+        self._absorptive = trajectory if isinstance(trajectory, AbsorptivePotential) else None
+        if self._absorptive is not None:
+            for what, val in (("cache=True", self._cache), ("stream_tile / run_streaming_tacaw()", self._stream_tile is not None),
+                              ("a run over several ranks", distributed.rank_world()[1] > 1),
+                              ("spectroscopy (one frame has no spectrum)", self._spectroscopy is not None)):
+                if val:
+                    raise NotImplementedError(f"absorptive potential: {what} is not built")
         self.trajectory = trajectory
         self.aperture = aperture
         self.voltage_eV = voltage_eV
@@ -632,7 +645,7 @@ class MultisliceCalculator:
         # slice coordinates follow the slice axis (potentials.py:241-245); the Fresnel step uses zs (multislice.py:266)
         self._slice_coords = np.asarray([self.xs, self.ys, self.zs][slice_axis], dtype=np.float64)
         self._dz = self.zs[1] - self.zs[0] if self.nz > 1 else 0.5
-        self._Z = (atomic_numbers_of(trajectory.atom_types) if self._generated is not None
+        self._Z = (atomic_numbers_of(trajectory.atom_types) if (self._generated is not None or self._absorptive is not None)
                    else np.asarray(trajectory.atom_types, dtype=np.int32))
         # A previous run's WFData (and zero-copy device views of its buffers) may still hold the old engine: drop our
         # reference and let the last owner free it, instead of closing it under them.  (A caller that keeps an earlier result
@@ -655,6 +668,11 @@ class MultisliceCalculator:
         """the phase tables of a frame group, allocated by the first potential build: up to 6 GB"""
         return min(6e9, batch * len(self.trajectory.atom_types) * (self.nx // 2 + self.ny // 2 + 2) * 8.0)
 
+    def _stack_bytes(self):
+        """device bytes per pixel, slice and frame of the batch: the two orientations of the transmission stack, and with an
+        absorptive potential the two float32 stacks Vbar and Omega that its first build allocates"""
+        return 24.0 if getattr(self, "_absorptive", None) is not None else 16.0
+
     def _fit_frame_batch(self, free_b, batch, slots):
         """Resident and streaming-TACAW runs: the default frame batch, halved while the result, the batch and what is allocated
         AFTER the engine exists -- the phase tables, the TACAW intensity array (4 B per stored complex value), the streaming
@@ -665,7 +683,7 @@ class MultisliceCalculator:
         stored = float(self.n_probes) * slots * sx * sy
         later = self._phase_table_bytes(batch) + 4.0 * stored + (24.0 * stored / slots if self._stream_tile is not None else 0.0)
         fixed = 8.0 * stored * len(self._layers) + later + 2e9        # (one result block per layer)
-        per_frame = 16.0 * n_slices * nx * ny + 24.0 * nx * ny * self.n_probes
+        per_frame = self._stack_bytes() * n_slices * nx * ny + 24.0 * nx * ny * self.n_probes
         while batch > 1 and fixed + batch * per_frame > 0.95 * free_b:
             batch = max(1, batch // 2)
         return batch
@@ -693,7 +711,7 @@ class MultisliceCalculator:
             bx, by = self._diffraction.bin if self._diffraction is not None else (1, 1)
             series = 8.0 * pitch + 8.0 * nx * ny + L * polar + 8.0 * L * (len(self._detectors) if self._detectors is not None else 0)
             coh += 8.0 * L * (sx // bx) * (sy // by) if self._diffraction is not None else 0.0
-        while Pc > 1 and (Pc * batch * (32.0 * nx * ny + 8.0 * pitch + polar + series) + Pc * coh + batch * 16.0 * n_slices * nx * ny + tables + smatrix + 1e9
+        while Pc > 1 and (Pc * batch * (32.0 * nx * ny + 8.0 * pitch + polar + series) + Pc * coh + batch * self._stack_bytes() * n_slices * nx * ny + tables + smatrix + 1e9
                           > 0.9 * free_b):
             Pc = max(1, Pc // 2)
         return Pc
@@ -744,6 +762,8 @@ class MultisliceCalculator:
         eng.set_aberrations(self._aberrations)
         if self._tilt is not None and not self._tilt.is_zero:   # (no tilt: the engine keeps the tables it was created with)
             eng.set_tilt(*self._tilt.tangents)
+        if self._absorptive is not None:                        # before the first build: its tables are f D and g
+            eng.set_absorption(self._absorptive.u_by_Z, self._absorptive.absorption)
         src = self._generated
         if src is not None:                                     # the base structure, once: every build is a generation by index
             modes = isinstance(src, PhononModes)                # (the mode builds do not read the widths)

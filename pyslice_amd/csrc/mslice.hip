@@ -18,6 +18,7 @@
 #include "pot_ifft.h"
 #include "rowtm_pass.h"
 #include "potential.h"
+#include "absorptive.h"
 #include "thermal.h"
 #include "phonons.h"
 #include "reduce.h"
@@ -246,6 +247,13 @@ struct msl_handle {
     int n_species = 0;
     int ff_species[104] = {0};     // species list the resident form-factor table was computed for (frame-invariant: computed once per run)
     int ff_n = 0;
+    // absorptive potential (msl_set_absorption, absorptive.h): the rms width per atomic number on the host and the device; while
+    // abs_on, d_ff holds f D and d_ffa the absorptive tables g (abs_absorb), and every build goes through the two real stacks abs_V
+    // (Vbar) and abs_O (Omega), (FB, nz, nx, ny) float32, allocated by the first such build and released when absorption is cleared.
+    // abs_built: the stacks hold the potential the transmission functions were made from (msl_set_beam, the downloads)
+    bool abs_on = false, abs_absorb = false, abs_built = false;
+    DevBuf<double> d_abs_u;
+    DevBuf<float> d_ffa, abs_V, abs_O;
     // frozen phonons (msl_set_structure): the base structure resident on the device -- positions (n, 3), widths, Z and the species
     // maps that stage_atoms sends per call -- with the host's copy of the maps and the axes; msl_build_thermal generates the
     // positions of any configuration from it (thermal_positions_kernel), so no per-frame array and no caller pointer is kept
@@ -1683,6 +1691,8 @@ int stage_modes(msl_handle* h, const PotGroup& p, uint64_t seed, uint64_t first_
     return launch_mode_positions(h, p.n, p.g, seed, first_frame, h->d_pos);
 }
 
+int absorptive_tables(msl_handle* h, int nsp);
+
 // Atoms of a group -> phase tables in sorted order: slice bins (atom_prep_kernel), stable counting sort with keys = frame x slice x
 // species (bin_scan / bin_fill), the phase tables of both axes
 int bin_atoms(msl_handle* h, const PotGroup& p) {
@@ -1694,10 +1704,12 @@ int bin_atoms(msl_handle* h, const PotGroup& p) {
     // when the species list changes, i.e. once per run
     if (nsp != h->ff_n || memcmp(p.species, h->ff_species, nsp * sizeof(int)) != 0) {
         long long tot = (long long)c.nx * c.ny * nsp;
-        hipLaunchKernelGGL(formfactor_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, h->stream, h->d_ff, h->d_abcd,
-                           h->d_species, nsp, c.nx, c.ny, 1.0 / lx, 1.0 / ly);
+        if (!h->abs_on)                                  // (absorptive_tables writes f D there itself)
+            hipLaunchKernelGGL(formfactor_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, h->stream, h->d_ff, h->d_abcd,
+                               h->d_species, nsp, c.nx, c.ny, 1.0 / lx, 1.0 / ly);
         memcpy(h->ff_species, p.species, nsp * sizeof(int));
         h->ff_n = nsp;
+        if (h->abs_on) { const int rc = absorptive_tables(h, nsp); if (rc) { h->ff_n = 0; return rc; } }
     }
     hipLaunchKernelGGL(atom_prep_kernel, dim3((unsigned)((p.rows + 255) / 256)), dim3(256), 0, h->stream, h->d_pos, h->d_Z,
                        (long long)p.n, p.g, h->d_z2s, h->d_lo, h->d_hi, c.nz, nsp, p.ax1, p.ax2, p.axs, 1.0 / lx, 1.0 / ly, h->d_key,
@@ -1719,8 +1731,9 @@ int bin_atoms(msl_handle* h, const PotGroup& p) {
 // Structure factors R_s of a group's slices into TR: matrix-core kernel over the quadrant of non-negative frequencies 0 .. n/2 in
 // 32 x 32 tiles; on power-of-two grids (n/2 + 1 = 32 k + 1) the Nyquist row / column goes to the edge kernel instead of a tile row
 // of its own
-int launch_structure_factor(msl_handle* h, const PotGroup& p) {
+int launch_structure_factor(msl_handle* h, const PotGroup& p, const float* table = nullptr) {
     const msl_config& c = h->cfg;
+    const float* ff = table ? table : h->d_ff.p;             // (the absorptive build runs it a second time, on d_ffa)
     const int cx = p.cx, cy = p.cy, nsp = p.nsp, n_slices = p.n_slices, full_rows = p.half_rows ? 0 : 1;
     const bool edge_x = (c.nx % 2 == 0) && (cx % 32 == 1) && cx > 1, edge_y = (c.ny % 2 == 0) && (cy % 32 == 1) && cy > 1;
     const int tiles_x = edge_x ? cx / 32 : (cx + 31) / 32, tiles_y = edge_y ? cy / 32 : (cy + 31) / 32;
@@ -1731,7 +1744,7 @@ int launch_structure_factor(msl_handle* h, const PotGroup& p) {
         // persistent form, one wave per SIMD: one workgroup per CU, a multiple of 8 (XCD-local slices)
         const int n_pers = std::max(8, h->n_cus / 8 * 8);
         auto stream = [&](auto kernel, size_t lds, int tiles) {
-            hipLaunchKernelGGL(kernel, dim3((unsigned)n_pers), dim3(256), lds, h->stream, p.TR, h->d_ex, h->d_ey, h->d_ff, h->d_start, nsp,
+            hipLaunchKernelGGL(kernel, dim3((unsigned)n_pers), dim3(256), lds, h->stream, p.TR, h->d_ex, h->d_ey, ff, h->d_start, nsp,
                                c.nx, c.ny, tiles_y, tiles, (int)p.rows_pad, full_rows, cx, cy, n_slices);
         };
         if (dbg_env("MSL_SF_F32"))                   // the exact-f32 matrix instruction (A/B against the split-bf16 form)
@@ -1743,14 +1756,14 @@ int launch_structure_factor(msl_handle* h, const PotGroup& p) {
         else
             stream(structure_factor_stream_bf16_kernel, 0, n_tiles);
     } else
-        hipLaunchKernelGGL(structure_factor_quad_kernel, dim3((unsigned)n_wg), dim3(256), 0, h->stream, p.TR, h->d_ex, h->d_ey, h->d_ff,
+        hipLaunchKernelGGL(structure_factor_quad_kernel, dim3((unsigned)n_wg), dim3(256), 0, h->stream, p.TR, h->d_ex, h->d_ey, ff,
                            h->d_start, nsp, c.nx, c.ny, tiles_y, n_tiles, (int)p.rows_pad, full_rows, cx, cy, n_slices, wg_per_slice);
     if (edge_x || edge_y) {
         const int bins = (edge_x ? cy : 0) + (edge_y ? (edge_x ? cx - 1 : cx) : 0);
         for (int s0 = 0; s0 < n_slices; s0 += 65535) {
             const int ns = std::min(65535, n_slices - s0);
             hipLaunchKernelGGL(structure_factor_edge_kernel, dim3((bins + 127) / 128, ns), dim3(128), 0, h->stream,
-                               p.TR + (size_t)s0 * c.nx * c.ny, h->d_ex, h->d_ey, h->d_ff, h->d_start + (size_t)s0 * nsp, nsp, c.nx, c.ny,
+                               p.TR + (size_t)s0 * c.nx * c.ny, h->d_ex, h->d_ey, ff, h->d_start + (size_t)s0 * nsp, nsp, c.nx, c.ny,
                                edge_x ? 1 : 0, edge_y ? 1 : 0, full_rows, cx, cy);
         }
     }
@@ -1863,6 +1876,106 @@ int potential_ifft(msl_handle* h, const PotGroup& p) {
     }
 }
 
+// ---- absorptive potential (absorptive.h) ----
+// The tables of the species in d_species, once per species list, grid or set of widths: d_ff = f D and, with absorption, d_ffa = g.
+// Four transforms of fft2_inplace over all species at once with the pointwise kernels between them; the work array lives for this
+// call only (the call waits for the stream: once per run).
+int absorptive_tables(msl_handle* h, int nsp) {
+    const msl_config& c = h->cfg;
+    const long long npix = (long long)c.nx * c.ny, tot = npix * nsp;
+    const double inv_lx = 1.0 / (c.nx * c.dx), inv_ly = 1.0 / (c.ny * c.dy), cell = c.dx * c.dx * c.dy * c.dy;
+    const dim3 grid((unsigned)((tot + 255) / 256)), block(256);
+    DevBuf<float2> W;
+    int rc;
+    if (h->abs_absorb && ((rc = W.alloc(h, (size_t)tot)) || (rc = h->d_ffa.reserve(h, (size_t)tot)))) return rc;
+    hipLaunchKernelGGL(absorptive_formfactor_kernel, grid, block, 0, h->stream, h->d_ff, W.p, h->d_abcd, h->d_abs_u, h->d_species, nsp,
+                       c.nx, c.ny, inv_lx, inv_ly);
+    HIPCHK(h, hipGetLastError());
+    if (!h->abs_absorb) return MSL_OK;
+    h->cur = nullptr;
+    if ((rc = fft2_inplace(h, W, nsp, -1, (float)(1.0 / (double)npix / cell), c.ny))) return rc;          // V1 + i Vbar1
+    hipLaunchKernelGGL(absorptive_square_kernel, grid, block, 0, h->stream, W.p, h->d_ffa, tot);
+    if ((rc = fft2_inplace(h, W, nsp, +1, 1.0f, c.ny))) return rc;
+    hipLaunchKernelGGL(absorptive_damp_kernel, grid, block, 0, h->stream, W.p, h->d_abs_u, h->d_species, nsp, c.nx, c.ny, inv_lx, inv_ly);
+    if ((rc = fft2_inplace(h, W, nsp, -1, (float)(1.0 / (double)npix), c.ny))) return rc;                 // <V1^2>
+    hipLaunchKernelGGL(absorptive_variance_kernel, grid, block, 0, h->stream, W.p, h->d_ffa, tot);
+    if ((rc = fft2_inplace(h, W, nsp, +1, 1.0f, c.ny))) return rc;
+    hipLaunchKernelGGL(absorptive_real_kernel, grid, block, 0, h->stream, h->d_ffa, W.p, tot, (float)cell);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipStreamSynchronize(h->stream));             // W is freed on return
+    return MSL_OK;
+}
+
+// ifft_inplace's two passes with the real store into `out_real` (the stacks of the group, natural order) and no transposed slices;
+// the t it leaves in TR (sigma = 0) is overwritten by the absorptive epilogue
+int absorptive_ifft(msl_handle* h, const PotGroup& p, float* out_real) {
+    const msl_config& c = h->cfg;
+    int rc;
+    if (h->Ry) {
+        RowJob r = row_job(h, p.TR, p.n_slices, c.ny);
+        r.do_ifft = 1;
+        if (p.half_rows) { const int Gr = 256 / h->Ry; r.nx = (c.nx / 2 + 1 + Gr - 1) / Gr * Gr; }
+        if ((rc = launch_row_fast(h, r, K_OTHER))) return rc;
+    } else {
+        LineArgs r = row_args(h, p.TR, p.TR, p.n_slices, c.ny);
+        r.fft1 = -1;
+        if ((rc = launch_lines(h, h->plan_y, r, K_OTHER))) return rc;
+    }
+    if (h->Rx) {
+        ColJob k = col_job(h, p.TR, p.TR, p.n_slices, c.ny, c.ny);
+        k.flags = COL_INV | COL_POTENTIAL; k.scale = p.vscale; k.sigma = 0.f; k.out_real = out_real; k.slice_mod = c.nz;
+        return p.half_rows ? launch_col_herm(h, k, K_OTHER) : launch_col_fast(h, k, K_OTHER);
+    }
+    LineArgs k = col_args(h, p.TR, p.TR, p.n_slices, c.ny, c.ny);
+    k.fft1 = -1; k.scale = p.vscale;
+    k.store_mode = STORE_POTENTIAL; k.out_real = out_real; k.sigma = 0.f;
+    return launch_lines(h, h->plan_x, k, K_OTHER);
+}
+
+// t = exp(i sigma Vbar - sigma^2 Omega) of the stacks in the batch slots slot .. slot + count - 1, from abs_V / abs_O into trans
+// (natural order), with the handle's current sigma
+int absorptive_transmission(msl_handle* h, int slot, int count) {
+    const msl_config& c = h->cfg;
+    const size_t stack = (size_t)c.nx * c.ny * c.nz, off = (size_t)slot * stack;
+    const long long n = (long long)(stack * count);
+    float2* t = h->trans + off;
+    const float* V = h->abs_V + off;
+    const float* Om = h->abs_absorb ? h->abs_O + off : nullptr;
+    const bool vec = (((uintptr_t)t | (uintptr_t)V | (uintptr_t)Om) & 15) == 0;
+    const float sop = (float)(c.sigma / M_PI), s2 = (float)(c.sigma * c.sigma);
+    const dim3 grid((unsigned)((n + 1023) / 1024)), block(256);
+    if (n > 0x7fffffffLL * 1024) return fail(h, MSL_ERR_UNSUPPORTED, "absorptive transmission: too many pixels");
+    if (Om) {
+        if (vec) hipLaunchKernelGGL((transmission_absorptive_kernel<true, true>), grid, block, 0, h->stream, t, V, Om, n, sop, s2);
+        else hipLaunchKernelGGL((transmission_absorptive_kernel<true, false>), grid, block, 0, h->stream, t, V, Om, n, sop, s2);
+    } else {
+        if (vec) hipLaunchKernelGGL((transmission_absorptive_kernel<false, true>), grid, block, 0, h->stream, t, V, Om, n, sop, s2);
+        else hipLaunchKernelGGL((transmission_absorptive_kernel<false, false>), grid, block, 0, h->stream, t, V, Om, n, sop, s2);
+    }
+    HIPCHK(h, hipGetLastError());
+    return MSL_OK;
+}
+
+// The absorptive build of a group whose atoms bin_atoms has sorted (`atoms` false: none, both stacks are zero): the structure factor
+// and the inverse transform twice, with d_ff into Vbar and with d_ffa into Omega, then the epilogue and the transposed copies of the
+// slices the one-pass loop reads along x
+int absorptive_group(msl_handle* h, const PotGroup& p, bool atoms) {
+    const msl_config& c = h->cfg;
+    const size_t stack = (size_t)c.nx * c.ny * c.nz, off = (size_t)p.slot * stack;
+    int rc;
+    h->cur = nullptr;
+    if (!atoms) {
+        HIPCHK(h, hipMemsetAsync(h->abs_V + off, 0, stack * p.g * sizeof(float), h->stream));
+        if (h->abs_absorb) HIPCHK(h, hipMemsetAsync(h->abs_O + off, 0, stack * p.g * sizeof(float), h->stream));
+    } else {
+        if ((rc = launch_structure_factor(h, p)) || (rc = absorptive_ifft(h, p, h->abs_V + off))) return rc;
+        if (h->abs_absorb && ((rc = launch_structure_factor(h, p, h->d_ffa)) || (rc = absorptive_ifft(h, p, h->abs_O + off)))) return rc;
+    }
+    if ((rc = absorptive_transmission(h, p.slot, p.g))) return rc;
+    for (int f = 0; f < p.g && rc == MSL_OK; ++f) rc = transpose_odd_slices(h, p.slot + f);
+    return rc;
+}
+
 // Projected potentials + transmission functions of `count` MD frames (the same atoms, `count` sets of positions) into the batch
 // slots first_slot .. first_slot + count - 1: ONE launch each of the atom preparation, the stable counting sort (keys = frame x
 // slice x species), the two phase tables, the structure factor and the two inverse-transform passes for as many frames as the
@@ -1897,6 +2010,19 @@ int build_potentials(msl_handle* h, const double* pos, const int32_t* Z, int64_t
     p.n = n; p.ax1 = ax1; p.ax2 = ax2; p.axs = axs;
     p.cx = c.nx / 2 + 1; p.cy = c.ny / 2 + 1; p.keys_per_frame = c.nz * std::max(p.nsp, 1);
     p.half_rows = pot_half_rows(h);
+    if (h->abs_on) {
+        // the absorptive build inverse-transforms with ifft_inplace's passes whatever pot_ifft is: half rows where those mirror them
+        p.half_rows = h->Rx && h->Ry;
+        const size_t stacks = npix * c.nz * h->FB;
+        if (!h->abs_V) {
+            if ((rc = h->abs_V.alloc(h, stacks))) return rc;
+            HIPCHK(h, hipMemsetAsync(h->abs_V, 0, stacks * sizeof(float), h->stream));
+        }
+        if (h->abs_absorb && !h->abs_O) {
+            if ((rc = h->abs_O.alloc(h, stacks))) return rc;
+            HIPCHK(h, hipMemsetAsync(h->abs_O, 0, stacks * sizeof(float), h->stream));
+        }
+    }
     p.sf_stream = (double)n / std::max(1, p.keys_per_frame) >= 128.0 && !dbg_env("MSL_SF_TILED");
     p.vscale = (float)(1.0 / ((double)c.nx * c.ny) / (c.dx * c.dx * c.dy * c.dy));
     // frames per group: the phase tables of a group (n atoms x (nx/2 + 1 + ny/2 + 1) x 8 bytes per frame) stay under 6 GB
@@ -1918,15 +2044,16 @@ int build_potentials(msl_handle* h, const double* pos, const int32_t* Z, int64_t
             rc = !th ? stage_atoms(h, p, pos + (size_t)f0 * n * 3, Z, f0 == 0)
                  : th->modes ? stage_modes(h, p, th->seed, th->first + (uint64_t)f0, f0 == 0)
                              : stage_thermal(h, p, th->seed, th->first + (uint64_t)f0, f0 == 0);
-            if (rc || (rc = bin_atoms(h, p)) || (rc = launch_structure_factor(h, p))) return rc;
-        } else {
+            if (rc || (rc = bin_atoms(h, p)) || (!h->abs_on && (rc = launch_structure_factor(h, p)))) return rc;
+        } else if (!h->abs_on) {
             HIPCHK(h, hipMemsetAsync(p.TR, 0, npix * p.n_slices * sizeof(float2), h->stream));
         }
-        if ((rc = potential_ifft(h, p))) return rc;
+        if ((rc = h->abs_on ? absorptive_group(h, p, n > 0 && p.nsp > 0) : potential_ifft(h, p))) return rc;
     }
     h->n_species = p.nsp;
     if ((rc = timer.end(h, &h->ctr.ms_potential))) return rc;
     h->have_potential = true;
+    h->abs_built = h->abs_on;
     return MSL_OK;
 }
 
@@ -2326,7 +2453,12 @@ int msl_set_beam(msl_handle* h, double wavelength, double sigma, double dz) {
     }
     int rc = h->tilt_set ? fill_propagator_device(h) : fill_propagator(h);      // a tilt stays on the handle
     if (rc) return rc;
-    if (h->have_potential) {
+    if (h->have_potential && h->abs_built) {
+        // an absorptive build keeps its two real stacks: t of every batch slot again, with the new sigma
+        if ((rc = absorptive_transmission(h, 0, h->FB))) return rc;
+        for (int f = 0; f < h->FB; ++f) if ((rc = transpose_odd_slices(h, f))) return rc;
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    } else if (h->have_potential) {
         if (!h->V) return fail(h, MSL_ERR_STATE, "msl_set_beam: potential present but V not kept (keep_potential=0); rebuild the potential");
         const size_t n = (size_t)h->cfg.nx * h->cfg.ny * h->cfg.nz;
         hipLaunchKernelGGL(transmission_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->trans, h->V,
@@ -2568,6 +2700,7 @@ int msl_set_structure(msl_handle* h, const double* pos0, const int32_t* Z, const
 // msl_build_thermal / msl_build_modes: the state and count checks, then build_potentials on the generated source
 static int build_generated(msl_handle* h, const char* who, bool modes, uint64_t seed, int64_t first, int32_t count) {
     if (!h) return fail(h, MSL_ERR_INVALID, "%s: null handle", who);
+    if (h->abs_on) return fail(h, MSL_ERR_STATE, "%s: absorption is set (msl_set_absorption): the vibration would be counted twice", who);
     if (!h->have_structure) return fail(h, MSL_ERR_INVALID, "%s: no structure (call msl_set_structure first)", who);
     if (modes && !h->have_modes) return fail(h, MSL_ERR_INVALID, "%s: no modes (call msl_set_modes first)", who);
     if (!h->have_kirkland) return fail(h, MSL_ERR_STATE, "%s: call msl_set_kirkland first", who);
@@ -2651,6 +2784,32 @@ int msl_set_modes(msl_handle* h, const int32_t* basis_index, int64_t n_atoms, in
     return MSL_OK;
 }
 
+// ---- absorptive potential ----------------------------------------------------
+int msl_set_absorption(msl_handle* h, const double* u_by_Z, int32_t absorb) {
+    if (!h) return fail(h, MSL_ERR_INVALID, "msl_set_absorption: null handle");
+    for (int z = 0; u_by_Z && z < 103; ++z)
+        if (!std::isfinite(u_by_Z[z]) || !(u_by_Z[z] >= 0.0))
+            return fail(h, MSL_ERR_INVALID, "msl_set_absorption: width %g of atomic number %d is not a finite number >= 0", u_by_Z[z], z + 1);
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));          // a queued build still reads the tables and the stacks
+    h->ff_n = 0;                                         // d_ff holds f or f D: the next build makes its table again
+    // the stacks of an earlier build no longer say what msl_set_beam should make of them (Omega kept or left out, other widths):
+    // the potential counts as not built until the next build
+    h->abs_built = false;
+    h->have_potential = false;
+    if (!u_by_Z) {
+        h->abs_on = h->abs_absorb = false;
+        h->d_abs_u.release(); h->d_ffa.release(); h->abs_V.release(); h->abs_O.release();
+        return MSL_OK;
+    }
+    int rc;
+    if (!h->d_abs_u && (rc = h->d_abs_u.alloc(h, (size_t)103))) return rc;
+    HIPCHK(h, hipMemcpy(h->d_abs_u, u_by_Z, 103 * sizeof(double), hipMemcpyHostToDevice));
+    h->abs_on = true;
+    h->abs_absorb = absorb != 0;
+    return MSL_OK;
+}
+
 int msl_build_modes(msl_handle* h, uint64_t seed, int64_t first_frame, int32_t count) {
     return build_generated(h, "msl_build_modes", true, seed, first_frame, count);
 }
@@ -2693,6 +2852,7 @@ int msl_upload_potential(msl_handle* h, const float* V) {
     { int rc = transpose_odd_slices(h, h->cur_batch); if (rc) return rc; }
     HIPCHK(h, hipStreamSynchronize(h->stream));
     h->have_potential = true;
+    h->abs_built = false;
     return MSL_OK;
 }
 
@@ -3044,7 +3204,7 @@ size_t msl_buffer_bytes(const msl_handle* h, msl_buffer what) {
     const size_t npix = (size_t)c.nx * c.ny;
     switch (what) {
         case MSL_BUF_PROBES: case MSL_BUF_EXIT: return npix * c.n_probes * 8;
-        case MSL_BUF_POTENTIAL: return h->V ? npix * c.nz * 4 : 0;
+        case MSL_BUF_POTENTIAL: return (h->V || h->abs_built) ? npix * c.nz * 4 : 0;
         case MSL_BUF_TRANSMISSION: return npix * c.nz * 8;
         case MSL_BUF_WAVEFUNCTION: return h->wf ? h->wpitch * c.n_probes * c.n_frames * 8 : 0;
         case MSL_BUF_INTENSITY: return h->intensity.n * 4;
@@ -3055,6 +3215,8 @@ size_t msl_buffer_bytes(const msl_handle* h, msl_buffer what) {
         case MSL_BUF_STREAM_REF: return (h->st_open && h->st_have_ref) ? h->wpix * c.n_probes * 8 : 0;
         case MSL_BUF_LAYERS: return h->wf ? n_result_layers(h) * layer_block_elems(h) * 8 : 0;
         case MSL_BUF_SMATRIX: return h->sm_built ? npix * (size_t)h->sm_Bm * 8 : 0;
+        case MSL_BUF_FORMFACTOR_ABS: return (h->abs_on && h->abs_absorb && h->d_ffa && h->ff_n > 0) ? npix * h->n_species * 4 : 0;
+        case MSL_BUF_ABSORPTION: return (h->abs_built && h->abs_absorb && h->abs_O) ? npix * c.nz * 4 : 0;
     }
     return 0;
 }
@@ -3071,7 +3233,7 @@ void* msl_device_ptr(msl_handle* h, msl_buffer what) {
     switch (what) {
         case MSL_BUF_PROBES: return h->psi0;
         case MSL_BUF_EXIT: return h->psi;
-        case MSL_BUF_POTENTIAL: return h->V;
+        case MSL_BUF_POTENTIAL: return h->abs_built ? h->abs_V + (size_t)h->cur_batch * h->cfg.nz * h->cfg.nx * h->cfg.ny : h->V.p;     // Vbar of the current stack
         case MSL_BUF_TRANSMISSION: return h->trans ? h->trans + (size_t)h->cur_batch * h->cfg.nz * h->cfg.nx * h->cfg.ny : nullptr;
         case MSL_BUF_WAVEFUNCTION: return h->wf;
         case MSL_BUF_INTENSITY: return h->intensity;
@@ -3082,6 +3244,8 @@ void* msl_device_ptr(msl_handle* h, msl_buffer what) {
         case MSL_BUF_STREAM_REF: return (h->st_open && h->st_have_ref) ? h->st_ref.p : nullptr;
         case MSL_BUF_LAYERS: return h->layers;
         case MSL_BUF_SMATRIX: return h->sm_S;
+        case MSL_BUF_FORMFACTOR_ABS: return h->d_ffa;
+        case MSL_BUF_ABSORPTION: return h->abs_O ? h->abs_O + (size_t)h->cur_batch * h->cfg.nz * h->cfg.nx * h->cfg.ny : nullptr;
     }
     return nullptr;
 }

@@ -182,6 +182,11 @@ class FrozenPhonons:
         """(n_atoms, 3) float64: configuration k >= 0 (any index: n_configs only says how many a run takes)"""
         return displaced(self.positions, self.sigma, self.seed, _u64("configuration index", k))
 
+    def absorptive(self, absorption=True):
+        """the absorptive.AbsorptivePotential of the same structure and widths: the ensemble's elastic average in one pass"""
+        from .absorptive import AbsorptivePotential
+        return AbsorptivePotential(self.atom_types, self.positions, self.box_matrix, self.sigma, absorption=absorption, timestep=self.timestep)
+
     def to_trajectory(self, configs=None):
         """The configurations (None: 0 .. n_configs - 1) as a Trajectory on the host, 24 B x n_atoms each: for tests and small
         cases."""
