@@ -2,8 +2,13 @@
 (the Fresnel factor is unit modulus too, so the waves stay white in both spaces through every slice), against the float64 oracle,
 per image, per line and per pixel.  tests/test_gpu_white_spectrum.py imports white_case(), the case lists and the bounds; run as
 a script it measures every case, on the one-pass kernels and on the generic two-pass loop (fft_path=1), and writes the worst
-figures per kernel family.  usage: python tools/white_parity.py [out.txt]"""
+figures per kernel family.
+
+With tilt=(tan_x, tan_y) the same cases run on the tables msl_set_tilt writes, which are not even in k (P[m] != P[n - m]), against
+the float64 definition of pyslice_amd/tilt.py: tests/test_gpu_white_tilt.py imports the TILT_* lists, and the script measures them
+into a second report.  usage: python tools/white_parity.py [out.txt [tilt_out.txt]], or --tilt-only [tilt_out.txt]"""
 import functools
+import math
 import os
 import re
 import sys
@@ -11,6 +16,15 @@ import numpy as np
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from oracle import multislice_oracle as orc
 from pyslice_amd import _native
+from pyslice_amd.tilt import Tilt, propagate_tilted
+
+
+def _smooth13(n):
+    for p in (2, 3, 5, 7, 11, 13):
+        while n % p == 0:
+            n //= p
+    return n == 1
+
 
 EV = 100e3
 DX = DY = 0.1
@@ -42,12 +56,33 @@ MANY_PROBE_CASES = [(600, 135, 3, 17), (600, 135, 3, 33), (1024, 144, 3, 17), (1
 SINGLE_SLICE_CASES = [(600, 135, 1), (256, 256, 1), (501, 37, 1)]
 FRAME_BATCH_CASE = (600, 135, 3)
 
-
-def _smooth13(n):
-    for p in (2, 3, 5, 7, 11, 13):
-        while n % p == 0:
-            n //= p
-    return n == 1
+# ---- tilted tables: tangents of 0.85 px and -0.55 px per slice (DX = 0.1, DZ = 0.5), fractional on both axes, inside 200 mrad
+TILT = (0.17, -0.11)
+TILT_X, TILT_Y = (0.17, 0.0), (0.0, -0.11)
+GENERIC_LENGTHS = [16, 32, 143, 169, 176, 182]
+# (nx, ny, nz, tilt).  Every mixed-radix length on both axes, both axes tilted: 135 is mixed itself, the loop stays one-pass
+TILT_MIXED_CASES = [c + (TILT,) for c in MIXED_CASES]
+# four-step R = 16 / 32 and the 2 R^2 kernel with its split-order table against a mixed cross axis, and paired with each other
+# (alternating scheme, interleaved work-buffer order); both axes tilted
+TILT_POW2_CASES = [c + (TILT,) for c in [(256, 144, 3), (144, 256, 2), (1024, 144, 3), (144, 1024, 2), (512, 144, 3), (144, 512, 2)] +
+                   [(nx, ny, nz) for nx, ny in ((256, 256), (1024, 256), (512, 512)) for nz in (2, 3)]]
+# the generic one-pass kernel (lengths below 33, 13-smooth lengths 129..191) on both axes, both tilted, against 135 lines (a partial
+# last tile) and 144 (whole tiles); every pair plans the one-pass loop
+TILT_GENERIC_CASES = [c + (TILT,) for n in GENERIC_LENGTHS for c in ((n, 135, 3), (135, n, 2), (n, 144, 3), (144, n, 2))]
+# the tilt along the direct axis (144) only: the loop stays one-pass, and the untilted axis -- every convolution length of
+# CONV_LENGTHS, and the 2048-point wave kernel -- reads the even table and the filter that msl_set_tilt wrote on the device
+TILT_CROSS_LENGTHS = [n for n in CONV_LENGTHS if n not in DIRECT_LENGTHS and n >= 33 and not (129 <= n <= 191 and _smooth13(n))] + [2048]
+TILT_CROSS_CASES = [c for n in TILT_CROSS_LENGTHS for c in ((n, 144, 3, TILT_Y), (144, n, 2, TILT_X))]
+# the tilt along an axis whose one-pass kernel needs an even table: msl_set_tilt moves the loop to the two-pass kernels.  The
+# transpose of 2047 x 144 x 2 has three slices: one shift of 0.55 px along a single axis leaves white noise correlated by
+# sinc(0.55) = 0.57, so at nz = 2 the float64 definition itself is only 0.93 away from the untilted wave, below the no-op threshold
+# of 1 (two propagations: 1.16); the two-pass loop runs the same two kernels per slice whatever nz is
+TILT_FALLBACK_CASES = [c + (TILT_X,) for c in ((501, 144, 3), (129, 144, 3), (1025, 144, 3), (2047, 144, 2), (2048, 144, 3))] + \
+                      [c + (TILT_Y,) for c in ((144, 501, 3), (144, 129, 3), (144, 1025, 3), (144, 2047, 3), (144, 2048, 3))]
+# (nx, ny, nz, tilt, layers): even and odd slices leave their pass on different axes, so the taps after slices 0, 1, 2 run the
+# one-pass taps along y and along x, in natural and interleaved line order; 501 x 144 with the tilt along x is the two-pass tap
+TILT_LAYER_CASES = [(nx, ny, 4, TILT, (0, 1, 2)) for nx, ny in ((600, 135), (135, 600), (256, 256), (512, 512), (1024, 144), (144, 1024))] + \
+                   [(501, 144, 4, TILT_X, (0, 1, 2))]
 
 
 def _mixed_groups():
@@ -84,11 +119,18 @@ def tolerance(nx, ny):
     return TOL_DIRECT if min(_native.line_kernel_class(nx), _native.line_kernel_class(ny)) >= 1 else TOL_CONV
 
 
-def bounds(nx, ny, nz, spectrum):
+def two_pass_tolerance(nx, ny):
+    """the two-pass loop is the kernel set of test_fft2_matches_numpy and gets its contract: 3e-6 with both lengths 13-smooth,
+    1e-5 with a Bluestein line (two transforms of >= 2n)"""
+    return TOL_DIRECT if _smooth13(nx) and _smooth13(ny) else TOL_CONV
+
+
+def bounds(nx, ny, nz, spectrum, layer=None, tol=None):
     """(E_img, E_line, E_pix) bounds: rounding adds in quadrature over the 2 (nz - 1) transforms of the loop, one more for the
-    fused spectrum; a single-slice exit wave has no transform and gets one tolerance"""
-    n_t = 2 * (nz - 1) + (1 if spectrum else 0)
-    b = tolerance(nx, ny) * np.sqrt(max(n_t, 1))
+    fused spectrum; a single-slice exit wave has no transform and gets one tolerance.  layer = k: the spectrum tapped after the
+    transmission of slice k, 2 k transforms of the loop and its own (the exit spectrum is layer nz - 1)"""
+    n_t = 2 * (nz - 1) + (1 if spectrum else 0) if layer is None else 2 * layer + 1
+    b = (tolerance(nx, ny) if tol is None else tol) * np.sqrt(max(n_t, 1))
     return b, LINE_FACTOR * b, PIXEL_FACTOR * b
 
 
@@ -100,11 +142,28 @@ def white_input(nx, ny, nz, P, seed=None, frames=1):
     return probes, V
 
 
-def reference(probes, V, nx, ny, nz):
-    """float64 exit waves and their fftshifted spectra for one potential V (nz, nx, ny)"""
-    xs, ys, zs = np.arange(nx) * DX, np.arange(ny) * DY, np.arange(nz) * DZ
-    ex = orc.propagate(probes, np.moveaxis(V.astype(np.float64), 0, 2), xs, ys, zs, EV)
-    return ex, np.fft.fftshift(np.fft.fft2(ex, axes=(-2, -1)), axes=(-2, -1))
+def _spectrum(psi):
+    return np.fft.fftshift(np.fft.fft2(psi, axes=(-2, -1)), axes=(-2, -1))
+
+
+def tilt_object(tilt):
+    """(tan_x, tan_y) -> the Tilt (mrad) with those tangents; None -> no tilt"""
+    return Tilt() if tilt is None else Tilt(math.atan(tilt[0]) * 1e3, math.atan(tilt[1]) * 1e3)
+
+
+def reference(probes, V, nx, ny, nz, tilt=None, layers=None):
+    """float64 exit waves and their fftshifted spectra for one potential V (nz, nx, ny).  tilt = (tan_x, tan_y): the loop is the
+    definition of pyslice_amd/tilt.py, on t = exp(i sigma V) of the float32 V widened to float64 as the oracle forms it; plain
+    NumPy, nothing of the device.  layers = slice indices: a third result, {k: spectrum of the wave after the transmission of slice k}"""
+    if tilt is None and layers is None:
+        xs, ys, zs = np.arange(nx) * DX, np.arange(ny) * DY, np.arange(nz) * DZ
+        ex = orc.propagate(probes, np.moveaxis(V.astype(np.float64), 0, 2), xs, ys, zs, EV)
+        return ex, _spectrum(ex)
+    t = np.exp(1j * orc.interaction_sigma(EV) * V.astype(np.float64))
+    out = propagate_tilted(probes, t, DX, DY, orc.wavelength(EV), DZ, tilt_object(tilt), layers=layers)
+    if layers is None:
+        return out, _spectrum(out)
+    return out[0], _spectrum(out[0]), {k: _spectrum(w) for k, w in out[1].items()}
 
 
 def metrics(got, want):
@@ -130,21 +189,68 @@ def case_data(nx, ny, nz, P):
     return (probes, V) + reference(probes, V[0], nx, ny, nz)
 
 
-def white_case(nx, ny, nz, P=2, fft_path=0):
-    """propagate() + exit_waves(), then propagate_frame(0) + wavefunction() on the same engine ->
-    dict(exit=(E_img, E_line, E_pix), spectrum=(...), one_pass=bool: the loop ran one kernel per slice)"""
-    probes, V, want_exit, want_spec = case_data(nx, ny, nz, P)
-    eng = engine(nx, ny, nz, P, fft_path=fft_path)
-    eng.upload_probes(probes)
-    eng.upload_potential(V[0])
+@functools.lru_cache(maxsize=1)
+def tilt_case_data(nx, ny, nz, P, tilt, layers):
+    """the same input, its float64 reference under the tilt and the untilted one (what a no-op of a tilt would give): each
+    (exit, spectrum) or, with layers, (exit, spectrum, {k: spectrum of the tap after slice k})"""
+    probes, V = case_data(nx, ny, nz, P)[:2]
+    return probes, V, reference(probes, V[0], nx, ny, nz, tilt, layers), reference(probes, V[0], nx, ny, nz, None, layers)
+
+
+def _rel_l2(got, want):
+    return float(np.linalg.norm(np.asarray(got).astype(np.complex128) - want) / np.linalg.norm(want))
+
+
+def _run(eng, nx, ny, nz, P, want_exit, want_spec):
+    """propagate() + exit_waves(), then propagate_frame(0) + wavefunction() -> the result dict of white_case and the exit waves"""
+    eng.reset_counters()
     eng.propagate()
     got_exit = eng.exit_waves()
-    # the one-pass loop moves 16 bytes per pixel and slice-step, the two-pass loop 32 (mslice.hip: count_slice_loop)
+    # the one-pass loop moves 16 bytes per pixel and slice-step, the two-pass loop 32 (mslice.hip: count_slice_loop); this call
+    # takes no layer tap (no frame slot), which would add its own
     one_pass = eng.counters()["algorithmic_bytes"] == (16 * P + 8) * nz * nx * ny
     eng.propagate_frame(0)
     got_spec = eng.wavefunction()[:, 0]
-    eng.close()
-    return dict(exit=metrics(got_exit, want_exit), spectrum=metrics(got_spec, want_spec), one_pass=one_pass)
+    return dict(exit=metrics(got_exit, want_exit), spectrum=metrics(got_spec, want_spec), one_pass=one_pass), got_exit
+
+
+def white_case(nx, ny, nz, P=2, fft_path=0, tilt=None, layers=None, restore=False):
+    """propagate() + exit_waves(), then propagate_frame(0) + wavefunction() on the same engine ->
+    dict(exit=(E_img, E_line, E_pix), spectrum=(...), one_pass=bool: the loop ran one kernel per slice).
+    tilt = (tan_x, tan_y): set_tilt() first, against the tilted float64 reference; adds moved = rel-L2 of the exit waves against the
+    UNTILTED reference (about 1.4 for both axes tilted: uncorrelated white fields).
+    layers = slice indices: set_layers(), propagate_frame(0), layers_c64(); adds layers = {k: metrics of the tap after slice k},
+    layers_moved = {k: rel-L2 against the untilted tap} and layers_untilted = {k: metrics against the untilted tap}.
+    restore: set_tilt(0, 0) on the same engine and the whole run again, against the untilted reference -> restored = dict(...)"""
+    if tilt is None and layers is None:
+        probes, V, want_exit, want_spec = case_data(nx, ny, nz, P)
+        flat = None
+    else:
+        probes, V, want, flat = tilt_case_data(nx, ny, nz, P, tilt, None if layers is None else tuple(layers))
+        want_exit, want_spec = want[:2]
+    eng = engine(nx, ny, nz, P, fft_path=fft_path)
+    try:
+        eng.upload_probes(probes)
+        eng.upload_potential(V[0])
+        if tilt is not None:
+            eng.set_tilt(*tilt)
+        res, got_exit = _run(eng, nx, ny, nz, P, want_exit, want_spec)
+        if flat is not None:
+            res["moved"] = _rel_l2(got_exit, flat[0])
+        if layers is not None:
+            eng.set_layers(list(layers))
+            eng.propagate_frame(0)
+            got = eng.layers_c64()[:, :, 0]                                     # (L, P, nx, ny): the taps, then the exit
+            res["layers"] = {k: metrics(got[i], want[2][k]) for i, k in enumerate(layers)}
+            res["layers_untilted"] = {k: metrics(got[i], flat[2][k]) for i, k in enumerate(layers)}
+            res["layers_moved"] = {k: _rel_l2(got[i], flat[2][k]) for i, k in enumerate(layers)}
+            res["layers_exit"] = metrics(got[len(layers)], want_spec)
+        if restore:
+            eng.set_tilt(0.0, 0.0)
+            res["restored"] = _run(eng, nx, ny, nz, P, *flat[:2])[0]
+    finally:
+        eng.close()
+    return res
 
 
 def frame_batch_case(nx, ny, nz, P=2):
@@ -205,5 +311,90 @@ def main(out_path):
     return 1 if bad else 0
 
 
+def tap_axis(nx, ny, nz, k, one_pass=True):
+    """the axis of the pass whose output the tap after slice k reads (mslice.hip: slice_is_transposed): "y" (layer_tap's axis 0),
+    "x" (axis 1) or "two-pass" (axis 2).  Two four-step axes alternate so that the last pass runs along y; every other pair
+    starts along y"""
+    if not one_pass:
+        return "two-pass"
+    fourstep = lambda n, other: n in (256, 1024) and other % 16 == 0
+    along_x = (nz - 1 - k) & 1 if fourstep(nx, ny) and fourstep(ny, nx) else k & 1
+    return "x" if along_x else "y"
+
+
+def tilt_main(out_path):
+    """every TILT_* case -> the worst figures per list and kernel family, in the form of main()'s report"""
+    worst, bad, n_cases = {}, 0, 0
+
+    def note(key, m, b, ok_extra=True):
+        nonlocal bad
+        ok = all(v <= lim for v, lim in zip(m, b)) and ok_extra
+        bad += not ok
+        w = worst.setdefault(key, [0.0] * 7)
+        for i in range(3):
+            w[i] = max(w[i], m[i])
+            w[3 + i] = max(w[3 + i], m[i] / b[i])
+        w[6] += 1
+        return " ".join(f"{v:.2e}" for v in m) + f" (bound {b[0]:.2e})" + ("" if ok else " <-- ABOVE")
+
+    def fam_of(nx, ny):
+        n, other = axis_under_test(nx, ny)
+        f = family(n, other)
+        return f + (" R=16" if n == 256 else " R=32") if f == "four-step" else f
+
+    lists = (("mixed", TILT_MIXED_CASES, True), ("pow2", TILT_POW2_CASES, True), ("generic", TILT_GENERIC_CASES, True),
+             ("even axis", TILT_CROSS_CASES, True), ("fallback", TILT_FALLBACK_CASES, False))
+    for lname, cases, want_one_pass in lists:
+        for nx, ny, nz, tilt in cases:
+            res = white_case(nx, ny, nz, tilt=tilt, restore=not want_one_pass)
+            fam = fam_of(nx, ny)
+            n_cases += 1
+            line = f"{lname:9s} {nx:4d} x {ny:4d} x {nz} tilt {tilt} {fam:18s}"
+            loop_ok = res["one_pass"] == want_one_pass and res["moved"] > 1.0
+            tol = None if want_one_pass else two_pass_tolerance(nx, ny)
+            for name in ("exit", "spectrum"):
+                line += f" | {name} " + note((lname, fam, name), res[name], bounds(nx, ny, nz, name == "spectrum", tol=tol), loop_ok)
+            if not want_one_pass:
+                for name in ("exit", "spectrum"):
+                    line += f" | (0, 0) again {name} " + note((lname, fam, "0:" + name), res["restored"][name],
+                                                               bounds(nx, ny, nz, name == "spectrum"), res["restored"]["one_pass"])
+            print(line + f" | moved {res['moved']:.2f}" + ("" if res["one_pass"] else "   (two-pass loop)"), flush=True)
+    for nx, ny, nz, tilt, layers in TILT_LAYER_CASES:
+        res = white_case(nx, ny, nz, tilt=tilt, layers=layers)
+        n_cases += 1
+        line = f"layers    {nx:4d} x {ny:4d} x {nz} tilt {tilt}"
+        for k in layers:
+            ax = tap_axis(nx, ny, nz, k, res["one_pass"])
+            ok = res["layers_moved"][k] > 1.0 if k else all(v <= b for v, b in zip(res["layers_untilted"][0], bounds(nx, ny, nz, True, 0)))
+            line += f" | tap {k} ({ax}) " + note(("layers", "tap, two-pass loop" if ax == "two-pass" else "tap, pass along " + ax, "layer"), res["layers"][k],
+                                                   bounds(nx, ny, nz, True, k), ok)
+        line += " | exit " + note(("layers", "exit of the tapped run", "layer"), res["layers_exit"], bounds(nx, ny, nz, True))
+        print(line, flush=True)
+    rows = ["White-spectrum parity under specimen tilt (tools/white_parity.py): the cases of white_spectrum_parity.txt on the propagator",
+            "tables msl_set_tilt writes for the tangents (0.17, -0.11) -- 0.85 px and -0.55 px per slice, tables that are not even in k --",
+            "against the float64 definition of pyslice_amd/tilt.py.  Worst figure of every case of a list and kernel family (the family of",
+            "the axis under test; the cross axis is 135 or 144 points).  'even axis': the tilt lies along the 144-point axis only, the",
+            "family is that of the UNTILTED axis, which reads the even table and the convolution filter the device wrote.  'fallback': the",
+            "tilt lies along an axis whose one-pass kernel needs an even table, the loop runs on the two-pass kernels; '0:' rows are the",
+            "same engine after set_tilt(0, 0), one-pass again, against the untilted reference.  'layers': the spectra tapped after slices",
+            "0, 1, 2 of 4, by the axis of the pass the tap reads.  E_img, E_line, E_pix and 'of bound' as in white_spectrum_parity.txt:",
+            "tol sqrt(n_t) x (1, 2, 10), tol = 3e-6 (direct axes) or 1e-5, n_t = 2 (nz - 1) (+ 1 for a spectrum), 2 k + 1 for the tap after",
+            "slice k.  The bounds of tests/test_gpu_white_tilt.py are not taken from this file.", "",
+            f"{'list':9s} {'family':24s} {'result':10s} {'cases':>5s} {'E_img':>9s} {'E_line':>9s} {'E_pix':>9s}   of bound: img  line   pix"]
+    for (lname, fam, name), w in sorted(worst.items()):
+        rows.append(f"{lname:9s} {fam:24s} {name:10s} {int(w[6]):5d} {w[0]:9.2e} {w[1]:9.2e} {w[2]:9.2e}            {w[3]:5.2f} {w[4]:5.2f} {w[5]:5.2f}")
+    rows += ["", f"{n_cases} cases, {bad} results above their bound, on the wrong loop or not moved by the tilt"]
+    text = "\n".join(rows) + "\n"
+    print(text)
+    if out_path:
+        with open(out_path, "w") as f:
+            f.write(text)
+    return 1 if bad else 0
+
+
 if __name__ == "__main__":
-    sys.exit(main(sys.argv[1] if len(sys.argv) > 1 else None))
+    args = [a for a in sys.argv[1:] if a != "--tilt-only"]
+    if "--tilt-only" in sys.argv[1:]:
+        sys.exit(tilt_main(args[0] if args else None))
+    rc = main(args[0] if args else None)
+    sys.exit(tilt_main(args[1] if len(args) > 1 else None) or rc)
