@@ -92,7 +92,9 @@ typedef enum {
                                 *                    layers (then the same memory as MSL_BUF_WAVEFUNCTION) */
     MSL_BUF_SMATRIX = 12,      /* (Bm,nx,ny) c64    the PRISM S-matrix of the last msl_smatrix_build: the exit waves of the Bm beams */
     MSL_BUF_FORMFACTOR_ABS = 13, /* (n_species,nx,ny) f32 the absorptive tables g of the last build with msl_set_absorption(.., absorb != 0) */
-    MSL_BUF_ABSORPTION = 14    /* (nz,nx,ny) f32    Omega of the last build with msl_set_absorption(.., absorb != 0) */
+    MSL_BUF_ABSORPTION = 14,   /* (nz,nx,ny) f32    Omega of the last build with msl_set_absorption(.., absorb != 0) */
+    MSL_BUF_FORMFACTOR_TDS = 15, /* (n_det,n_species,nx,ny) f32 the detector-restricted tables g_det of the last build with msl_set_tds */
+    MSL_BUF_TDS_WEIGHT = 16    /* (n_det,nz,nx,ny) f32 the TDS weights w = 1 - exp(-2 sigma^2 Omega_det) of the last build with msl_set_tds */
 } msl_buffer;
 
 typedef struct {
@@ -300,6 +302,30 @@ int  msl_mode_positions(msl_handle* h, uint64_t seed, int64_t frame, double* out
  * float32 stacks (frame_batch, nz, nx, ny) and a second structure factor and inverse transform per build.  The model is the classical
  * weak-fluctuation one: third order in sigma V per atom.  Synchronous.  Not in the reference. */
 int  msl_set_absorption(msl_handle* h, const double* u_by_Z_103, int32_t absorb);
+
+/* ---- TDS detector signal of the absorptive potential: HAADF from one pass ----
+ * What the absorption takes out of the elastic wave in slice s and detector d collects, in the local approximation (pyslice_amd/tds.py
+ * is the definition):
+ *     I[p, d, s] = sum_r |psi_p,s(r)|^2 w_d,s(r),   w_d,s = 1 - exp(-2 sigma^2 Omega_det,d,s),   psi_p,s = the wave arriving at slice s
+ * Omega_det the structure-factor sum with the detector-restricted tables g_det: per species, M_d the membership,
+ *     V1M = Re ifft2(M f) / (dx^2 dy^2),  Vbar1M = Re ifft2(M f D) / (dx^2 dy^2),
+ *     Om1det = 1/2 (Re ifft2(D fft2(V1 V1M)) - Vbar1 Vbar1M),  g_det = Re fft2(Om1det) dx^2 dy^2
+ * (M = 1: Om1 and g).  TDS electrons are not propagated further.
+ * msl_set_tds:  member_bits = (nx, ny) uint16 on the fftfreq grid, unshifted, bit d = detector d, 1 <= n_det <= 4; NULL or n_det = 0
+ *   clears it and frees its buffers.  MSL_ERR_STATE without msl_set_absorption(.., absorb != 0) (clearing or changing that to
+ *   absorb == 0 clears this too); MSL_ERR_UNSUPPORTED at a frame batch above 1.  Drops the potential as msl_set_absorption does: the
+ *   next build makes g_det (MSL_BUF_FORMFACTOR_TDS) and, per detector, one more structure factor and inverse transform into the
+ *   weight stack (MSL_BUF_TDS_WEIGHT), which msl_set_beam remakes for another sigma.  While it is set every msl_propagate* runs
+ *   the two-pass loop with the row step of each slice in two launches and the reduction between them: about 3.5 times the
+ *   one-pass loop's bytes.  The exit waves and spectra are those of the two-pass loop, bit for bit.  Synchronous.
+ * msl_tds_fetch:  after one stream synchronisation, I of the last slice loop for the first B probes (B <= 0: n_probes) as
+ *   (nz, B, n_det) float64 on the host.  MSL_ERR_STATE before the first loop.
+ * msl_tds_reduce:  the reduction alone, of the work buffer as the last slice loop left it (MSL_BUF_EXIT) against the weights of
+ *   `slice`: the tile kernel `reps` times between two events and the finishing sum once.  out (n_probes, n_det) float64 and
+ *   ms_reduce, the mean device time of one repeat in ms, may be NULL.  For benchmarks.  Not in the reference. */
+int  msl_set_tds(msl_handle* h, const uint16_t* member_bits, int32_t n_det);
+int  msl_tds_fetch(msl_handle* h, int32_t B, double* out);
+int  msl_tds_reduce(msl_handle* h, int32_t slice, int32_t reps, double* out, double* ms_reduce);
 
 /* TACAW: intensity[p,w,kx,ky] = | fftshift_t fft_t( Psi - <Psi>_t ) |^2 over a (B,T,npix) c64 device
  * array.  src == NULL uses the handle's own wavefunction buffer (B=P, T=T_local, npix=nx*ny) and

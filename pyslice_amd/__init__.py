@@ -8,6 +8,7 @@ from .trajectory import Trajectory
 from .thermal import FrozenPhonons, sigma_from_B
 from .phonons import PhononModes
 from .absorptive import AbsorptivePotential, absorptive_tables, absorptive_transmission, mean_transmission_exact
+from .tds import tds_tables, tds_weight, tds_signal
 from .wf_data import WFData
 from .potentials import Potential, gridFromTrajectory, getZfromElementName, loadKirkland
 from .multislice import Probe, Propagate, create_batched_probes, probe_grid, wavelength, m_effective
@@ -26,7 +27,7 @@ from .spectrum_image_data import SpectrumImageData
 from .tilt import Tilt, Precession
 
 __all__ = ["Trajectory", "FrozenPhonons", "sigma_from_B", "PhononModes", "AbsorptivePotential", "absorptive_tables",
-           "absorptive_transmission", "mean_transmission_exact", "WFData", "Potential", "gridFromTrajectory", "getZfromElementName", "loadKirkland",
+           "absorptive_transmission", "mean_transmission_exact", "tds_tables", "tds_weight", "tds_signal", "WFData", "Potential", "gridFromTrajectory", "getZfromElementName", "loadKirkland",
            "Probe", "Propagate", "create_batched_probes", "probe_grid", "wavelength", "m_effective",
            "MultisliceCalculator", "TACAWData", "HAADFData", "Detector", "STEMData", "Diffraction", "DiffractionData",
            "PolarDetector", "PolarData", "polar_bins", "polar_signals", "Thickness",

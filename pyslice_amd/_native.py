@@ -17,7 +17,8 @@ ABI_VERSION = 3          # include/mslice.h: MSL_ABI_VERSION
 MSL_OK, MSL_ERR_INVALID, MSL_ERR_HIP, MSL_ERR_UNSUPPORTED, MSL_ERR_STATE, MSL_ERR_NOMEM = 0, -1, -2, -3, -4, -5
 (BUF_PROBES, BUF_EXIT, BUF_POTENTIAL, BUF_TRANSMISSION, BUF_WAVEFUNCTION, BUF_INTENSITY, BUF_FORMFACTOR,
  BUF_STREAM_ACC, BUF_STREAM_S1, BUF_STREAM_S2, BUF_STREAM_REF, BUF_LAYERS, BUF_SMATRIX, BUF_FORMFACTOR_ABS,
- BUF_ABSORPTION) = range(15)
+ BUF_ABSORPTION, BUF_FORMFACTOR_TDS, BUF_TDS_WEIGHT) = range(17)
+TDS_MAX_DETECTORS = 4      # include/mslice.h: msl_set_tds
 
 EXPORTS = [
     "msl_abi_version", "msl_line_kernel_class", "msl_last_error", "msl_create", "msl_destroy", "msl_set_kirkland", "msl_set_slices",
@@ -43,6 +44,7 @@ EXPORTS = [
     "msl_layer_reduce_bytes",
     "msl_set_tilt", "msl_get_tilt",
     "msl_set_absorption",
+    "msl_set_tds", "msl_tds_fetch", "msl_tds_reduce",
 ]
 DET_SIGNALS = {"intensity": 0, "amplitude": 1, "com_x": 2, "com_y": 3}      # include/mslice.h: MSL_DET_*
 POLAR_NONE, POLAR_MAX_BINS = 0xFFFF, 4096                                  # include/mslice.h: MSL_POLAR_*
@@ -154,6 +156,9 @@ def load():
         "msl_set_structure": (C.c_int, [vp, vp, vp, vp, i64, i32, i32, i32]),
         "msl_build_thermal": (C.c_int, [vp, C.c_uint64, i64, i32]),
         "msl_set_absorption": (C.c_int, [vp, vp, i32]),
+        "msl_set_tds": (C.c_int, [vp, vp, i32]),
+        "msl_tds_fetch": (C.c_int, [vp, i32, vp]),
+        "msl_tds_reduce": (C.c_int, [vp, i32, i32, vp, vp]),
         "msl_thermal_positions": (C.c_int, [vp, C.c_uint64, i64, vp]),
         "msl_set_modes": (C.c_int, [vp, vp, i64, i32, vp, vp, vp, i32, i32]),
         "msl_build_modes": (C.c_int, [vp, C.c_uint64, i64, i32]),
@@ -284,6 +289,36 @@ class Engine:
         if u.shape != (103,):
             raise ValueError(f"u_by_Z must hold one width per atomic number 1..103, got shape {u.shape}")
         self._chk(self._lib.msl_set_absorption(self._h, _ptr(u), int(bool(absorb))))
+
+    def set_tds(self, member_bits=None, n_det=0):
+        """TDS detector signal of the absorptive potential (msl_set_tds; the definition is tds.py): member_bits (nx, ny) uint16 on the
+        fftfreq grid, unshifted, bit d = detector d, n_det in 1..4; None clears it.  After set_absorption(.., absorb=True), before the
+        build.  Every later slice loop runs on the two-pass loop and leaves the per-slice sums for tds_fetch()."""
+        if member_bits is None:
+            self._chk(self._lib.msl_set_tds(self._h, None, 0))
+            self.n_tds = 0
+            return
+        b = np.ascontiguousarray(member_bits, dtype=np.uint16)
+        if b.shape != (self.nx, self.ny):
+            raise ValueError(f"member_bits must be ({self.nx},{self.ny}), got {b.shape}")
+        self._chk(self._lib.msl_set_tds(self._h, _ptr(b), int(n_det)))
+        self.n_tds = int(n_det)
+
+    def tds_fetch(self, B=None):
+        """I[s, p, d] of the last slice loop, (nz, B, n_det) float64: the TDS generated in slice s that lands on detector d, for the
+        first B probes (msl_tds_fetch; one wait for the stream)"""
+        b = int(B) if B else self.n_probes
+        out = np.empty((self.nz, b, getattr(self, "n_tds", 0)), dtype=np.float64)
+        self._chk(self._lib.msl_tds_fetch(self._h, b, _ptr(out)))
+        return out
+
+    def tds_reduce(self, slice_index=0, reps=1):
+        """the TDS reduction alone, of the work buffer the last slice loop left against the weights of one slice (msl_tds_reduce) ->
+        (sums (n_probes, n_det) float64, mean device time of one of the `reps` repeats in ms)"""
+        out = np.empty((self.n_probes, getattr(self, "n_tds", 0)), dtype=np.float64)
+        ms = C.c_double(0.0)
+        self._chk(self._lib.msl_tds_reduce(self._h, int(slice_index), int(reps), _ptr(out), C.byref(ms)))
+        return out, float(ms.value)
 
     def set_slices(self, lo, hi):
         lo = np.ascontiguousarray(lo, dtype=np.float64)
@@ -902,6 +937,14 @@ class Engine:
     def absorption(self):
         """Omega (nz, nx, ny) of the last build with set_absorption(.., absorb=True)"""
         return self.download(BUF_ABSORPTION, np.float32, (self.nz, self.nx, self.ny))
+
+    def form_factors_tds(self, n_species):
+        """the detector-restricted tables g_det (n_det, n_species, nx, ny) of the last build with set_tds"""
+        return self.download(BUF_FORMFACTOR_TDS, np.float32, (self.n_tds, n_species, self.nx, self.ny))
+
+    def tds_weight(self):
+        """w = 1 - exp(-2 sigma^2 Omega_det), (n_det, nz, nx, ny), of the last build with set_tds"""
+        return self.download(BUF_TDS_WEIGHT, np.float32, (self.n_tds, self.nz, self.nx, self.ny))
 
     def synchronize(self):
         self._chk(self._lib.msl_synchronize(self._h))

@@ -25,8 +25,9 @@ The model is the classical weak-fluctuation one: its error is third order in sig
 and 0.1 A sampling max |t - <t>| is 1e-3; for gold at the same sampling, where sigma V reaches 7.5 rad at the atom centre, it is
 0.56 -- use the ensemble there.
 
-Not built: the TDS signal on a detector (for HAADF from one pass: detector-restricted absorptive tables and a per-slice |psi|^2
-reduction), per-atom widths inside one element, anisotropic u, the exact per-atom mean transmission in place of the second cumulant,
+The TDS signal that this absorption feeds to a detector (HAADF from the same pass) is tds.py.
+
+Not built: per-atom widths inside one element, anisotropic u, the exact per-atom mean transmission in place of the second cumulant,
 a fused one-pass structure factor for both tables.
 """
 from __future__ import annotations

@@ -132,7 +132,7 @@ class MultisliceCalculator:
     def __init__(self, device=None, force_cpu=False, *, output="host", dtype="complex128", progress=True,
                  gather="rank0", cache=False, k_window=None, frame_batch=None, k_bin=None, stream_tile=None, layers=None,
                  detectors=None, probe_batch=None, diffraction=None, aberrations=None, imaging=None, prism=None,
-                 spectroscopy=None, polar=None, thickness=None, tilt=None, precession=None):
+                 spectroscopy=None, polar=None, thickness=None, tilt=None, precession=None, tds=False):
         """
         device / force_cpu: as the reference (calculators.py:41).  There is no CPU path here, so
         force_cpu=True raises.  Keyword-only extras (not in the reference):
@@ -230,6 +230,15 @@ class MultisliceCalculator:
                    return the mean of the single-tilt results, accumulated on the host in float64 in tilt order, with the tilts
                    in `.tilts`.  Not with tilt (the cone has a centre).  Not built: the other run modes, stream_tile, cache,
                    several ranks.
+          tds      True, with detectors=[...] and an absorptive.AbsorptivePotential(absorption=True) in setup(): run_detectors() also
+                   returns what the absorption takes out of the elastic wave and each detector collects -- the thermal diffuse
+                   signal, which is most of HAADF -- from the same single pass (tds.py is the definition: the local approximation
+                   on top of the second-cumulant model).  STEMData.signals stays the elastic part; .tds_per_slice (P, 1, D, nz),
+                   .tds, .total = signals + tds and image(name, part="total" | "elastic" | "tds") carry the rest, with the
+                   thickness axis when there is one.  The slice loop then runs on the two-pass loop with a reduction of |psi|^2
+                   per slice (msl_set_tds): 3-5 times the time of the elastic scan.  Up to 4 detectors, annuli that read the
+                   intensity.  Allowed with tilt, aberrations, k_window, probe_batch, thickness; not built with prism, precession,
+                   polar, diffraction, imaging, spectroscopy, layers, cache, stream_tile or several ranks.
         """
         if force_cpu:
             raise NotImplementedError("pyslice_amd has no CPU path (force_cpu=True): use the reference for CPU runs")
@@ -364,6 +373,16 @@ class MultisliceCalculator:
         if cache and tilt is not None and not tilt.is_zero:
             raise NotImplementedError("cache=True with a tilt is not built: the cache key does not carry the tilt")
         self._tilt, self._precession = tilt, precession
+        self._tds = bool(tds)
+        if self._tds:
+            from .tds import check_tds_detectors
+            check_tds_detectors(detectors)
+            for what, val in (("prism", prism is not None), ("precession", precession is not None), ("polar", polar is not None),
+                              ("diffraction", diffraction is not None), ("imaging", imaging is not None),
+                              ("spectroscopy", spectroscopy is not None), ("layers", layers is not None), ("cache", cache),
+                              ("stream_tile", stream_tile is not None)):
+                if val:
+                    raise NotImplementedError(f"tds: {what} is not built")
         self._precessing = False                # inside the tilt loop of a precession run
         self._layers = None                     # validated slice indices (setup), nz - 1 last
         self._engine = None
@@ -430,6 +449,12 @@ class MultisliceCalculator:
                               ("spectroscopy (one frame has no spectrum)", self._spectroscopy is not None)):
                 if val:
                     raise NotImplementedError(f"absorptive potential: {what} is not built")
+        if getattr(self, "_tds", False):
+            if self._absorptive is None or not self._absorptive.absorption:
+                raise ValueError("tds=True needs an absorptive.AbsorptivePotential(absorption=True) in setup(): the TDS signal is what "
+                                 "its absorption takes out of the elastic wave")
+            if distributed.rank_world()[1] > 1:
+                raise NotImplementedError("tds: a run over several ranks is not built")
         self.trajectory = trajectory
         self.aperture = aperture
         self.voltage_eV = voltage_eV
@@ -580,6 +605,10 @@ class MultisliceCalculator:
             self._configure_engine()                            # (the aberrations are read by the set_probes of every probe batch)
             if self._detectors is not None:
                 self._engine.set_detectors(bits.reshape(-1), [d.signal for d in self._detectors], kxs, kys)
+            if self._tds:                                       # (before the first build: its tables are those of the detectors)
+                from .tds import tds_members
+                self._engine.set_tds(tds_members(self._detectors, self.nx, self.ny, self.dx, self.dy, wavelength(self.voltage_eV)),
+                                     len(self._detectors))
             if self._polar is not None:
                 self._engine.set_polar(self._polar_bins.reshape(-1), self._polar.n_bins)
             if self._thickness is not None and len(self._thickness) > 1:    # (the exit wave alone needs no tap: the plain reductions)
@@ -693,7 +722,8 @@ class MultisliceCalculator:
         (with a thickness series also its one block, the tap buffer and the staging of every entry),
         the coherent accumulator of a split run (16 * pitch bytes per probe), the image accumulator of an imaging run (8 * nx * ny
         bytes per probe, layer and defocus), the output scratch of a polar run (8 * n_bins bytes per image), the transmission stacks
-        of the batch and the phase tables exceed 0.9 x the free device memory."""
+        of the batch, the TDS weight stack (4 bytes per detector, slice and pixel) and the phase tables exceed 0.9 x the free device
+        memory."""
         nx, ny, n_slices = self.nx, self.ny, len(self._slice_coords)
         pitch = self._stored_shape()[2]
         tables = self._phase_table_bytes(batch)
@@ -701,6 +731,8 @@ class MultisliceCalculator:
         if self._imaging is not None:
             coh = 8.0 * nx * ny * len(self._layers) * len(self._imaging.defocus_series)
         smatrix = 8.0 * getattr(self, "_prism_Bm", 0) * nx * ny       # the S-matrix of a PRISM run, (Bm, nx, ny) complex64
+        if getattr(self, "_tds", False):                            # (a fixed cost like the S-matrix: the weight stack of every detector)
+            smatrix += 4.0 * len(self._detectors) * n_slices * nx * ny
         polar = 8.0 * self._polar.n_bins if self._polar is not None else 0.0
         series = 0.0
         if self._thickness is not None and len(self._thickness) > 1:
@@ -883,12 +915,12 @@ class MultisliceCalculator:
             finish_batch(p0, real)
         bar.close()
 
-    def _stem_data(self, signals):
+    def _stem_data(self, signals, tds_per_slice=None):
         from .stem_data import STEMData
         kxs, kys = self._k_axes()
         return STEMData(signals=signals, detectors=list(self._detectors), probe_positions=self.probe_positions,
                         time=np.arange(self.n_frames) * self.trajectory.timestep, kxs=_as_tensor(kxs), kys=_as_tensor(kys),
-                        probe=self.base_probe, **self._layer_fields())
+                        probe=self.base_probe, tds_per_slice=tds_per_slice, **self._layer_fields())
 
     def _layer_fields(self):
         """layer / thickness of a result with a thickness axis: the slice indices, and the depth in Angstrom at the exit side of each
@@ -1131,8 +1163,13 @@ class MultisliceCalculator:
         t0 = time.time()
         P, T, D = self.n_probes, self.n_frames, len(self._detectors)
         signals = self._layered((P, T, D))
+        tds = np.zeros((P, T, D, len(self._slice_coords)), dtype=np.float64) if self._tds else None
 
         def reduce_batch(p0, real, s0, n):
+            if tds is not None:
+                # (nz, real, D) of the slice loop that just ran, one frame, in the units of `signals`: the exit FFT is unnormalised,
+                # sum_k |Psi|^2 = nx ny sum_r |psi|^2
+                tds[p0:p0 + real, s0] = np.moveaxis(eng.tds_fetch(B=real), 0, -1) * float(self.nx * self.ny)
             if self._thickness is not None:
                 signals[p0:p0 + real, s0:s0 + n] = np.moveaxis(self._layer_signals(real, n)[0], 0, -1)
                 return
@@ -1143,7 +1180,7 @@ class MultisliceCalculator:
             self._probe_batch_loop(reduce_batch)
         self.elapsed = time.time() - t0
         self.frames_computed, self.frames_cached = T, 0
-        return self._stem_data(signals)
+        return self._stem_data(signals, tds)
 
     def run_polar(self):
         """Polar-detector signals of every probe position: the loop of run_detectors(); msl_polar_detect reduces the exit spectra of

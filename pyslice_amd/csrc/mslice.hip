@@ -19,6 +19,7 @@
 #include "rowtm_pass.h"
 #include "potential.h"
 #include "absorptive.h"
+#include "tds.h"
 #include "thermal.h"
 #include "phonons.h"
 #include "reduce.h"
@@ -254,6 +255,16 @@ struct msl_handle {
     bool abs_on = false, abs_absorb = false, abs_built = false;
     DevBuf<double> d_abs_u;
     DevBuf<float> d_ffa, abs_V, abs_O;
+    // TDS detector signal (msl_set_tds, tds.h): the memberships on the fft-order grid, the tables g_det
+    // (tds_n, n_species, nx, ny) next to d_ffa, the weight stack w (tds_n, nz, nx, ny) made with the interaction constant tds_sigma,
+    // the per-slice sums (nz, n_probes, tds_n) of the last slice loop (tds_have) and the slab of its partials.  While tds_on the
+    // handle runs slice_loop_tds, on the two-pass loop (set_loop_mode)
+    bool tds_on = false, tds_have = false;
+    int tds_n = 0;
+    double tds_sigma = 0.0;
+    DevBuf<uint16_t> tds_bits;
+    DevBuf<float> tds_g, tds_W;
+    DevBuf<double> tds_acc, tds_part;
     // frozen phonons (msl_set_structure): the base structure resident on the device -- positions (n, 3), widths, Z and the species
     // maps that stage_atoms sends per call -- with the host's copy of the maps and the axes; msl_build_thermal generates the
     // positions of any configuration from it (thermal_positions_kernel), so no per-frame array and no caller pointer is kept
@@ -1319,6 +1330,106 @@ int slice_loop(msl_handle* h, int fused_slot, int groups, int first_group) {
     return MSL_OK;
 }
 
+// ---- TDS detector signal (tds.h) ----
+// The reduction of P images at `psi` (the work buffers' layout) against the weights of slice z into dst (P, tds_n) float64, queued:
+// the tile kernel into the slab of partials, then the sums over the tiles.  reps > 1 repeats the tile kernel (msl_tds_reduce's timing).
+int tds_reduce_queue(msl_handle* h, const float2* psi, int P, int z, double* dst, int reps = 1) {
+    const msl_config& c = h->cfg;
+    const long long pairs = (long long)c.nx * ((c.ny + 1) / 2), n_tiles = (pairs + TDS_TILE - 1) / TDS_TILE;
+    if (n_tiles > 0x7fffffffLL) return fail(h, MSL_ERR_UNSUPPORTED, "tds: too many tiles");
+    int rc = h->tds_part.reserve(h, (size_t)n_tiles * P * h->tds_n);
+    if (rc) return rc;
+    // images per workgroup: as many as possible (the weights are loaded once per workgroup) while every slot still has a workgroup
+    const long long slots = (long long)h->n_cus * 8;
+    int pc = P;
+    while (pc > 1 && n_tiles * ((P + pc - 1) / pc) < slots) pc = (pc + 1) / 2;
+    while ((P + pc - 1) / pc > 65535) ++pc;
+    const size_t stack = (size_t)c.nx * c.ny * c.nz;
+    const float* w = h->tds_W + (size_t)z * c.nx * c.ny;
+    const bool vec = (h->pitch % 2 == 0) && (((uintptr_t)psi & 15) == 0);
+    const dim3 grid((unsigned)n_tiles, (unsigned)((P + pc - 1) / pc));
+    for (int r = 0; r < reps; ++r) {
+        with_int<1, 2, 3, 4>(h->tds_n, [&](auto nd) { with_bool(vec, [&](auto v) {
+            hipLaunchKernelGGL((tds_reduce_kernel<decltype(nd)::value, decltype(v)::value>), grid, dim3(256), 0, h->stream, psi, w, (long long)stack,
+                               c.nx, c.ny, h->pitch, P, pc, h->tds_part.p);
+        }); });
+        HIPCHK(h, hipGetLastError());
+        if (reps == 1 && (rc = mark_launch(h, K_OTHER))) return rc;
+    }
+    with_int<1, 2, 3, 4>(h->tds_n, [&](auto nd) {
+        hipLaunchKernelGGL(tds_finish_kernel<decltype(nd)::value>, dim3((unsigned)(((long long)P * h->tds_n + 255) / 256)), dim3(256), 0, h->stream,
+                           h->tds_part.p, n_tiles, P, h->tds_n, dst);
+    });
+    HIPCHK(h, hipGetLastError());
+    return reps == 1 ? mark_launch(h, K_OTHER) : MSL_OK;
+}
+
+// The slice loop while TDS is on: the two-pass loop with the row step of every slice issued as two launches of its own kernels --
+// the inverse y-transform alone, as fft2_inplace issues it, then t_s, the forward transform and P_y -- so that between them psi holds
+// psi_s in real space at its true scale, where the reduction is queued (at s = 0 psi is psi0).  Every elastic launch computes what
+// slice_loop's computes; the per-slice sums go to tds_acc (nz, P, tds_n).
+int slice_loop_tds(msl_handle* h, int fused_slot, int groups, int first_group) {
+    const msl_config& c = h->cfg;
+    if (groups != 1 || h->onepass) return fail(h, MSL_ERR_STATE, "tds: the slice loop needs one frame per launch on the two-pass loop");
+    if (!h->tds_W || !h->abs_built) return fail(h, MSL_ERR_STATE, "tds: no weight stack (build the potential after msl_set_tds)");
+    const int P = c.n_probes, nz = c.nz;
+    const size_t npix = (size_t)c.nx * c.ny;
+    const size_t toff = (size_t)first_group * c.nz * npix;
+    int rc = h->tds_acc.reserve(h, (size_t)nz * P * h->tds_n);
+    if (rc) return rc;
+    HIPCHK(h, hipMemcpyAsync(h->psi, h->psi0, (size_t)P * c.nx * h->pitch * sizeof(float2), hipMemcpyDeviceToDevice, h->stream));
+    const bool fused = fused_slot >= 0;
+    if ((rc = begin_timed(h, 5 * nz + 2 + (fused ? tap_launches(h) : 0)))) return rc;
+    for (int z = 0; z < nz; ++z) {
+        const bool last = (z == nz - 1);
+        if (z > 0) {
+            if (h->Ry) {
+                RowJob r = row_job(h, h->psi, P, h->pitch);
+                r.do_ifft = 1;
+                rc = launch_row_fast(h, r, K_ROW);
+            } else {
+                LineArgs r = row_args(h, h->psi, h->psi, P, h->pitch);
+                r.fft1 = -1;
+                rc = launch_lines(h, h->plan_y, r, K_ROW);
+            }
+            if (rc) return rc;
+        }
+        if ((rc = tds_reduce_queue(h, h->psi, P, z, h->tds_acc + (size_t)z * P * h->tds_n))) return rc;
+        if (h->Ry) {
+            RowJob r = row_job(h, h->psi, P, h->pitch);
+            r.trans = h->trans + toff + (size_t)z * npix;
+            r.do_fft = (!last || fused); r.py = last ? nullptr : h->pyt;
+            rc = launch_row_fast(h, r, K_ROW);
+        } else {
+            LineArgs r = row_args(h, h->psi, h->psi, P, h->pitch);
+            r.m1_kind = MUL_ARRAY; r.m1 = h->trans + toff + (size_t)z * npix; r.m1_ls = c.ny;
+            if (!last) { r.fft2 = +1; r.m2_kind = MUL_VEC; r.m2 = h->pyt; }
+            else if (fused) { r.fft2 = +1; }
+            rc = launch_lines(h, h->plan_y, r, K_ROW);
+        }
+        if (rc) return rc;
+        if (!last && (rc = tap_step(h, z, fused_slot, groups, h->psi, false, TAP_NATURAL, 8, 2))) return rc;
+        if (!last) {
+            if (h->Rx) {
+                ColJob k = col_job(h, h->psi, h->psi, P, h->pitch, h->pitch);
+                k.px = h->pxt; k.flags = COL_FWD | COL_MULPX | COL_INV;
+                rc = launch_col_fast(h, k, K_COL);
+            } else {
+                LineArgs k = col_args(h, h->psi, h->psi, P, h->pitch, h->pitch);
+                k.fft1 = +1; k.m1_kind = MUL_VEC; k.m1 = h->pxt; k.fft2 = -1;
+                rc = launch_lines(h, h->plan_x, k, K_COL);
+            }
+            if (rc) return rc;
+        }
+    }
+    if (fused && (rc = epilogue_x_pass(h, fused_slot, groups))) return rc;
+    h->tds_have = true;
+    // 16 B more per pixel and slice-step for the split row step, 8 for the reduction's read, and the weights once per image chunk
+    count_slice_loop(h, P, groups, fused, 32 + 16 + 8);
+    h->ctr.algorithmic_bytes += (uint64_t)nz * h->tds_n * 4ull * npix;
+    return MSL_OK;
+}
+
 // cyclic length of the convolution that IS the propagation along an axis of a convolution kind (0: none), and the entries of its filter qf
 int conv_len(const msl_handle::OpDir& o) { return o.base == AX_CONV ? o.R * o.R : o.base == AX_CONV2K ? 2048 : o.base == AX_CONV4K ? 4096 : 0; }
 size_t conv_filter_entries(const msl_handle::OpDir& o) { return o.base == AX_CONV4K ? 2052 : (size_t)conv_len(o) / 2 + 2; }
@@ -1885,15 +1996,20 @@ int absorptive_tables(msl_handle* h, int nsp) {
     const long long npix = (long long)c.nx * c.ny, tot = npix * nsp;
     const double inv_lx = 1.0 / (c.nx * c.dx), inv_ly = 1.0 / (c.ny * c.dy), cell = c.dx * c.dx * c.dy * c.dy;
     const dim3 grid((unsigned)((tot + 255) / 256)), block(256);
-    DevBuf<float2> W;
+    DevBuf<float2> W, F0, W0;           // F0 = f + i f D and W0 = V1 + i Vbar1 are kept for the detector tables only
+    DevBuf<float> vb;
     int rc;
     if (h->abs_absorb && ((rc = W.alloc(h, (size_t)tot)) || (rc = h->d_ffa.reserve(h, (size_t)tot)))) return rc;
+    if (h->tds_on && ((rc = F0.alloc(h, (size_t)tot)) || (rc = W0.alloc(h, (size_t)tot)) || (rc = vb.alloc(h, (size_t)tot)) ||
+                      (rc = h->tds_g.reserve(h, (size_t)tot * h->tds_n)))) return rc;
     hipLaunchKernelGGL(absorptive_formfactor_kernel, grid, block, 0, h->stream, h->d_ff, W.p, h->d_abcd, h->d_abs_u, h->d_species, nsp,
                        c.nx, c.ny, inv_lx, inv_ly);
     HIPCHK(h, hipGetLastError());
     if (!h->abs_absorb) return MSL_OK;
     h->cur = nullptr;
+    if (h->tds_on) HIPCHK(h, hipMemcpyAsync(F0, W, (size_t)tot * sizeof(float2), hipMemcpyDeviceToDevice, h->stream));
     if ((rc = fft2_inplace(h, W, nsp, -1, (float)(1.0 / (double)npix / cell), c.ny))) return rc;          // V1 + i Vbar1
+    if (h->tds_on) HIPCHK(h, hipMemcpyAsync(W0, W, (size_t)tot * sizeof(float2), hipMemcpyDeviceToDevice, h->stream));
     hipLaunchKernelGGL(absorptive_square_kernel, grid, block, 0, h->stream, W.p, h->d_ffa, tot);
     if ((rc = fft2_inplace(h, W, nsp, +1, 1.0f, c.ny))) return rc;
     hipLaunchKernelGGL(absorptive_damp_kernel, grid, block, 0, h->stream, W.p, h->d_abs_u, h->d_species, nsp, c.nx, c.ny, inv_lx, inv_ly);
@@ -1902,6 +2018,19 @@ int absorptive_tables(msl_handle* h, int nsp) {
     if ((rc = fft2_inplace(h, W, nsp, +1, 1.0f, c.ny))) return rc;
     hipLaunchKernelGGL(absorptive_real_kernel, grid, block, 0, h->stream, h->d_ffa, W.p, tot, (float)cell);
     HIPCHK(h, hipGetLastError());
+    // the detector tables g_det (tds.h): the same four transforms per detector, on M_d (f + i f D) and the products with V1, Vbar1
+    for (int d = 0; h->tds_on && d < h->tds_n; ++d) {
+        hipLaunchKernelGGL(tds_mask_kernel, grid, block, 0, h->stream, W.p, F0.p, h->tds_bits.p, d, npix, tot);
+        if ((rc = fft2_inplace(h, W, nsp, -1, (float)(1.0 / (double)npix / cell), c.ny))) return rc;      // V1M + i Vbar1M
+        hipLaunchKernelGGL(tds_product_kernel, grid, block, 0, h->stream, W.p, W0.p, vb.p, tot);
+        if ((rc = fft2_inplace(h, W, nsp, +1, 1.0f, c.ny))) return rc;
+        hipLaunchKernelGGL(absorptive_damp_kernel, grid, block, 0, h->stream, W.p, h->d_abs_u, h->d_species, nsp, c.nx, c.ny, inv_lx, inv_ly);
+        if ((rc = fft2_inplace(h, W, nsp, -1, (float)(1.0 / (double)npix), c.ny))) return rc;
+        hipLaunchKernelGGL(absorptive_variance_kernel, grid, block, 0, h->stream, W.p, vb.p, tot);
+        if ((rc = fft2_inplace(h, W, nsp, +1, 1.0f, c.ny))) return rc;
+        hipLaunchKernelGGL(absorptive_real_kernel, grid, block, 0, h->stream, h->tds_g + (size_t)d * tot, W.p, tot, (float)cell);
+        HIPCHK(h, hipGetLastError());
+    }
     HIPCHK(h, hipStreamSynchronize(h->stream));             // W is freed on return
     return MSL_OK;
 }
@@ -1956,21 +2085,44 @@ int absorptive_transmission(msl_handle* h, int slot, int count) {
     return MSL_OK;
 }
 
+// The TDS weight stack in place (tds_weight_kernel): from Omega_det with the handle's sigma (from_omega), or from the weights of the
+// beam it was made with (msl_set_beam)
+int tds_weights(msl_handle* h, bool from_omega) {
+    const msl_config& c = h->cfg;
+    const long long n = (long long)c.nx * c.ny * c.nz * h->tds_n;
+    const double a = 2.0 * c.sigma * c.sigma, a_old = 2.0 * h->tds_sigma * h->tds_sigma;
+    if (!from_omega && a_old == 0.0) {
+        if (a == 0.0) return MSL_OK;
+        return fail(h, MSL_ERR_STATE, "msl_set_beam: the TDS weights were made at sigma = 0 and hold nothing to remake; rebuild the potential");
+    }
+    hipLaunchKernelGGL(tds_weight_kernel, dim3((unsigned)((n + 1023) / 1024)), dim3(256), 0, h->stream, h->tds_W.p, n, (float)a,
+                       from_omega ? 0.f : (float)(a / a_old));
+    HIPCHK(h, hipGetLastError());
+    h->tds_sigma = c.sigma;
+    return MSL_OK;
+}
+
 // The absorptive build of a group whose atoms bin_atoms has sorted (`atoms` false: none, both stacks are zero): the structure factor
 // and the inverse transform twice, with d_ff into Vbar and with d_ffa into Omega, then the epilogue and the transposed copies of the
-// slices the one-pass loop reads along x
+// slices the one-pass loop reads along x.  With TDS on, once more per detector with its table g_det into the weight stack.
 int absorptive_group(msl_handle* h, const PotGroup& p, bool atoms) {
     const msl_config& c = h->cfg;
     const size_t stack = (size_t)c.nx * c.ny * c.nz, off = (size_t)p.slot * stack;
     int rc;
     h->cur = nullptr;
+    if (h->tds_on && !h->tds_W && (rc = h->tds_W.alloc(h, stack * h->tds_n))) return rc;
     if (!atoms) {
         HIPCHK(h, hipMemsetAsync(h->abs_V + off, 0, stack * p.g * sizeof(float), h->stream));
         if (h->abs_absorb) HIPCHK(h, hipMemsetAsync(h->abs_O + off, 0, stack * p.g * sizeof(float), h->stream));
+        if (h->tds_on) HIPCHK(h, hipMemsetAsync(h->tds_W, 0, stack * h->tds_n * sizeof(float), h->stream));
     } else {
         if ((rc = launch_structure_factor(h, p)) || (rc = absorptive_ifft(h, p, h->abs_V + off))) return rc;
         if (h->abs_absorb && ((rc = launch_structure_factor(h, p, h->d_ffa)) || (rc = absorptive_ifft(h, p, h->abs_O + off)))) return rc;
+        for (int d = 0; h->tds_on && d < h->tds_n; ++d)
+            if ((rc = launch_structure_factor(h, p, h->tds_g + (size_t)d * c.nx * c.ny * p.nsp)) ||
+                (rc = absorptive_ifft(h, p, h->tds_W + (size_t)d * stack))) return rc;
     }
+    if (h->tds_on && (rc = tds_weights(h, true))) return rc;
     if ((rc = absorptive_transmission(h, p.slot, p.g))) return rc;
     for (int f = 0; f < p.g && rc == MSL_OK; ++f) rc = transpose_odd_slices(h, p.slot + f);
     return rc;
@@ -2456,6 +2608,7 @@ int msl_set_beam(msl_handle* h, double wavelength, double sigma, double dz) {
     if (h->have_potential && h->abs_built) {
         // an absorptive build keeps its two real stacks: t of every batch slot again, with the new sigma
         if ((rc = absorptive_transmission(h, 0, h->FB))) return rc;
+        if (h->tds_on && h->tds_W && (rc = tds_weights(h, false))) return rc;       // and the TDS weights, which carry 2 sigma^2
         for (int f = 0; f < h->FB; ++f) if ((rc = transpose_odd_slices(h, f))) return rc;
         HIPCHK(h, hipStreamSynchronize(h->stream));
     } else if (h->have_potential) {
@@ -2499,6 +2652,15 @@ int set_loop_mode(msl_handle* h, bool onepass) {
     return rc;
 }
 
+// TDS off: its buffers freed, and the handle back on the loop its tilt allows
+int tds_clear(msl_handle* h) {
+    if (!h->tds_on) return MSL_OK;
+    h->tds_on = h->tds_have = false;
+    h->tds_n = 0;
+    h->tds_bits.release(); h->tds_g.release(); h->tds_W.release(); h->tds_acc.release(); h->tds_part.release();
+    return set_loop_mode(h, h->onepass_planned && !tilt_needs_two_pass(h, h->tilt_tan[0], h->tilt_tan[1]));
+}
+
 }  // namespace
 
 int msl_set_tilt(msl_handle* h, double tan_x, double tan_y) {
@@ -2506,7 +2668,7 @@ int msl_set_tilt(msl_handle* h, double tan_x, double tan_y) {
     if (!std::isfinite(tan_x) || !std::isfinite(tan_y)) return fail(h, MSL_ERR_INVALID, "msl_set_tilt: tan_x and tan_y must be finite");
     HIPCHK(h, hipSetDevice(h->cfg.device));
     {   // the loop that can run this tilt; a refused switch leaves the handle as it was
-        const int rc = set_loop_mode(h, h->onepass_planned && !tilt_needs_two_pass(h, tan_x, tan_y));
+        const int rc = set_loop_mode(h, h->onepass_planned && !h->tds_on && !tilt_needs_two_pass(h, tan_x, tan_y));
         if (rc) return rc;
     }
     const double old[2] = {h->tilt_tan[0], h->tilt_tan[1]};
@@ -2797,16 +2959,80 @@ int msl_set_absorption(msl_handle* h, const double* u_by_Z, int32_t absorb) {
     // the potential counts as not built until the next build
     h->abs_built = false;
     h->have_potential = false;
+    int rc;
+    if ((!u_by_Z || !absorb) && (rc = tds_clear(h))) return rc;      // the TDS signal is that of the absorption: it goes with it
     if (!u_by_Z) {
         h->abs_on = h->abs_absorb = false;
         h->d_abs_u.release(); h->d_ffa.release(); h->abs_V.release(); h->abs_O.release();
         return MSL_OK;
     }
-    int rc;
     if (!h->d_abs_u && (rc = h->d_abs_u.alloc(h, (size_t)103))) return rc;
     HIPCHK(h, hipMemcpy(h->d_abs_u, u_by_Z, 103 * sizeof(double), hipMemcpyHostToDevice));
     h->abs_on = true;
     h->abs_absorb = absorb != 0;
+    return MSL_OK;
+}
+
+// ---- TDS detector signal -----------------------------------------------------
+int msl_set_tds(msl_handle* h, const uint16_t* member_bits, int32_t n_det) {
+    if (!h) return fail(h, MSL_ERR_INVALID, "msl_set_tds: null handle");
+    const bool clear = !member_bits || n_det == 0;
+    if (!clear && (n_det < 1 || n_det > TDS_MAX)) return fail(h, MSL_ERR_INVALID, "msl_set_tds: %d detectors outside [1, %d]", n_det, TDS_MAX);
+    if (!clear && !(h->abs_on && h->abs_absorb))
+        return fail(h, MSL_ERR_STATE, "msl_set_tds: no absorption (call msl_set_absorption(.., absorb != 0) first)");
+    if (!clear && h->FB > 1) return fail(h, MSL_ERR_UNSUPPORTED, "msl_set_tds: a frame batch of %d (the weight stack is that of one frame)", h->FB);
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));          // a queued build or loop still reads the tables and the stacks
+    // as msl_set_absorption: the tables are made again by the next build, and the potential counts as not built until then
+    h->ff_n = 0;
+    h->abs_built = false;
+    h->have_potential = false;
+    int rc = tds_clear(h);
+    if (rc || clear) return rc;
+    const size_t npix = (size_t)h->cfg.nx * h->cfg.ny;
+    if ((rc = h->tds_bits.alloc(h, npix))) return rc;
+    HIPCHK(h, hipMemcpy(h->tds_bits, member_bits, npix * sizeof(uint16_t), hipMemcpyHostToDevice));
+    if ((rc = set_loop_mode(h, false))) { h->tds_bits.release(); return rc; }
+    h->tds_n = n_det;
+    h->tds_on = true;
+    return MSL_OK;
+}
+
+int msl_tds_fetch(msl_handle* h, int32_t B, double* out) {
+    if (!h || !out) return fail(h, MSL_ERR_INVALID, "msl_tds_fetch: null argument");
+    if (!h->tds_on || !h->tds_have) return fail(h, MSL_ERR_STATE, "msl_tds_fetch: no TDS sums (msl_set_tds, then a slice loop)");
+    const int P = h->cfg.n_probes, n = h->tds_n;
+    if (B <= 0) B = P;
+    if (B > P) return fail(h, MSL_ERR_INVALID, "msl_tds_fetch: %d probes, the handle has %d", B, P);
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    HIPCHK(h, hipMemcpy2DAsync(out, (size_t)B * n * sizeof(double), h->tds_acc, (size_t)P * n * sizeof(double), (size_t)B * n * sizeof(double),
+                               (size_t)h->cfg.nz, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return MSL_OK;
+}
+
+int msl_tds_reduce(msl_handle* h, int32_t slice, int32_t reps, double* out, double* ms_reduce) {
+    if (!h) return fail(h, MSL_ERR_INVALID, "msl_tds_reduce: null handle");
+    if (!h->tds_on || !h->tds_W || !h->abs_built) return fail(h, MSL_ERR_STATE, "msl_tds_reduce: no weight stack (msl_set_tds, then a build)");
+    if (slice < 0 || slice >= h->cfg.nz) return fail(h, MSL_ERR_INVALID, "msl_tds_reduce: slice %d outside [0, %d)", slice, h->cfg.nz);
+    if (reps < 1) return fail(h, MSL_ERR_INVALID, "msl_tds_reduce: reps must be positive");
+    const float2* src = h->psi.p;                       // MSL_BUF_EXIT: whatever the last slice loop left there
+    const int P = h->cfg.n_probes;
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    DevBuf<double> dst;
+    int rc = dst.alloc(h, (size_t)P * h->tds_n);
+    if (rc) return rc;
+    h->cur = nullptr;
+    // the timed launches run between two events of their own, after one untimed pass has sized the slab
+    if (reps > 1 && (rc = tds_reduce_queue(h, src, P, slice, dst))) return rc;
+    double ms = 0.0;
+    EventPair timer;
+    if ((rc = timer.begin(h)) || (rc = tds_reduce_queue(h, src, P, slice, dst, reps)) || (rc = timer.end(h, &ms))) {
+        (void)hipStreamSynchronize(h->stream);          // nothing queued reads dst when it is freed
+        return rc;
+    }
+    if (ms_reduce) *ms_reduce = ms / reps;              // (the one finishing sum of the call is in it: take reps large)
+    if (out) HIPCHK(h, hipMemcpy(out, dst, (size_t)P * h->tds_n * sizeof(double), hipMemcpyDeviceToHost));
     return MSL_OK;
 }
 
@@ -2865,11 +3091,11 @@ static int run_loop(msl_handle* h, int slot, int groups, int first_group) {
     const bool reduce = h->lr_on && slot >= 0;
     int rc;
     if (!h->cfg.launch_timing) {                                                         // queued; msl_synchronize / msl_download wait for it
-        if ((rc = slice_loop(h, slot, groups, first_group)) || !reduce) return rc;
+        if ((rc = (h->tds_on ? slice_loop_tds : slice_loop)(h, slot, groups, first_group)) || !reduce) return rc;
         return layer_reduce_queue(h, n_taps(h), h->wf, slot, groups);
     }
     EventPair timer;
-    if ((rc = timer.begin(h)) || (rc = slice_loop(h, slot, groups, first_group))) return rc;
+    if ((rc = timer.begin(h)) || (rc = (h->tds_on ? slice_loop_tds : slice_loop)(h, slot, groups, first_group))) return rc;
     if (reduce && (rc = layer_reduce_queue(h, n_taps(h), h->wf, slot, groups))) return rc;
     return timer.end(h, &h->ctr.ms_propagate);
 }
@@ -3217,6 +3443,8 @@ size_t msl_buffer_bytes(const msl_handle* h, msl_buffer what) {
         case MSL_BUF_SMATRIX: return h->sm_built ? npix * (size_t)h->sm_Bm * 8 : 0;
         case MSL_BUF_FORMFACTOR_ABS: return (h->abs_on && h->abs_absorb && h->d_ffa && h->ff_n > 0) ? npix * h->n_species * 4 : 0;
         case MSL_BUF_ABSORPTION: return (h->abs_built && h->abs_absorb && h->abs_O) ? npix * c.nz * 4 : 0;
+        case MSL_BUF_FORMFACTOR_TDS: return (h->tds_on && h->tds_g && h->ff_n > 0) ? npix * h->n_species * h->tds_n * 4 : 0;
+        case MSL_BUF_TDS_WEIGHT: return (h->tds_on && h->abs_built && h->tds_W) ? npix * c.nz * h->tds_n * 4 : 0;
     }
     return 0;
 }
@@ -3246,6 +3474,8 @@ void* msl_device_ptr(msl_handle* h, msl_buffer what) {
         case MSL_BUF_SMATRIX: return h->sm_S;
         case MSL_BUF_FORMFACTOR_ABS: return h->d_ffa;
         case MSL_BUF_ABSORPTION: return h->abs_O ? h->abs_O + (size_t)h->cur_batch * h->cfg.nz * h->cfg.nx * h->cfg.ny : nullptr;
+        case MSL_BUF_FORMFACTOR_TDS: return h->tds_g;
+        case MSL_BUF_TDS_WEIGHT: return h->tds_W;
     }
     return nullptr;
 }

@@ -113,7 +113,10 @@ class STEMData:
     detectors, the run's probe_positions / time / kxs / kys / probe, and the scan axes xs, ys.
     With MultisliceCalculator(thickness=...) signals is (P, T, D, L): `layer` holds the slice indices of the L thickness entries,
     `thickness` the depth in Angstrom at the exit side of each slice, at(i) is the ordinary STEMData of entry i, and image() takes
-    layer=-1, the exit wave."""
+    layer=-1, the exit wave.
+    With MultisliceCalculator(tds=True) signals is the elastic part and tds_per_slice (P, T, D, nz) the thermal diffuse signal that
+    every slice generates on every detector (tds.py, times nx ny: the units of the unnormalised spectra the signals sum): `tds` is its sum over the slices -- with a thickness axis its cumulative sum at
+    the entries, (P, T, D, L) --, `total` = signals + tds, and image() takes part="total" | "elastic" | "tds"."""
     signals: np.ndarray
     detectors: List[Detector]
     probe_positions: Any
@@ -126,6 +129,7 @@ class STEMData:
     layer: Optional[np.ndarray] = None
     thickness: Optional[np.ndarray] = None
     tilts: Optional[list] = None            # the tilt.Tilt of every run of a precession average (tilt order); None otherwise
+    tds_per_slice: Optional[np.ndarray] = None
 
     def __post_init__(self):
         if self.xs is None or self.ys is None:
@@ -138,7 +142,25 @@ class STEMData:
         if self.layer is None:
             raise ValueError("this STEMData has no thickness axis: run with MultisliceCalculator(thickness=...)")
         from .thickness import entry
-        return replace(self, signals=self.signals[..., entry(self.layer, i)], layer=None, thickness=None)
+        tps = self.tds_per_slice
+        if tps is not None:                 # the slices up to the entry: what has been generated by then
+            tps = tps[..., :int(self.layer[entry(self.layer, i)]) + 1]
+        return replace(self, signals=self.signals[..., entry(self.layer, i)], layer=None, thickness=None, tds_per_slice=tps)
+
+    @property
+    def tds(self) -> np.ndarray:
+        """(P, T, D), the TDS on every detector summed over the slices; (P, T, D, L) with a thickness axis: the cumulative sum at
+        the slice of every entry"""
+        if self.tds_per_slice is None:
+            raise ValueError("this STEMData has no TDS signal: run with MultisliceCalculator(tds=True)")
+        if self.layer is None:
+            return self.tds_per_slice.sum(axis=-1)
+        return np.cumsum(self.tds_per_slice, axis=-1)[..., np.asarray(self.layer, dtype=np.int64)]
+
+    @property
+    def total(self) -> np.ndarray:
+        """signals + tds: the elastic part and the thermal diffuse part of every detector"""
+        return self.signals + self.tds
 
     def index(self, name: str) -> int:
         for d, det in enumerate(self.detectors):
@@ -146,13 +168,20 @@ class STEMData:
                 return d
         raise KeyError(f"no detector named {name!r} (have {[d.name for d in self.detectors]})")
 
-    def image(self, name: str, frames=None, layer=-1) -> np.ndarray:
+    def image(self, name: str, frames=None, layer=-1, part=None) -> np.ndarray:
         """(len(xs), len(ys)) image of detector `name`: mean over the frames (all, or an index / slice / list of frame
         indices) on the scan grid, every scan point taking its nearest probe's value as HAADFData does; of thickness entry
-        `layer` when there is a thickness axis"""
+        `layer` when there is a thickness axis.  part: "elastic" (signals), "tds" or "total" of a run with tds=True; None is "total"
+        there and the signals otherwise."""
+        if part not in (None, "total", "elastic", "tds"):
+            raise ValueError(f"part must be 'total', 'elastic' or 'tds', got {part!r}")
+        if part in ("total", "tds") and self.tds_per_slice is None:
+            raise ValueError(f"part={part!r} needs a run with MultisliceCalculator(tds=True)")
         if self.layer is not None:
-            return self.at(layer).image(name, frames)
-        s = self.signals[:, :, self.index(name)]
+            return self.at(layer).image(name, frames, part=part)
+        if part is None:
+            part = "elastic" if self.tds_per_slice is None else "total"
+        s = {"elastic": lambda: self.signals, "tds": lambda: self.tds, "total": lambda: self.total}[part]()[:, :, self.index(name)]
         if frames is not None:
             s = s[:, frames]
             if s.ndim == 1:
