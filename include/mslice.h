@@ -161,6 +161,29 @@ int  msl_set_beam(msl_handle* h, double wavelength, double sigma, double dz);
 int  msl_set_tilt(msl_handle* h, double tan_x, double tan_y);
 int  msl_get_tilt(const msl_handle* h, double* tan_xy);
 
+/* Band limit (anti-aliasing): keep the signed FFT frequency indices |h_x| <= cut_x, |h_y| <= cut_y -- a
+ * rectangle M(kx, ky) = m_x(kx) m_y(ky), separable and even -- in BOTH factors of every product t_k psi:
+ *   - every propagator table of both axes is masked on the device (propagator_bandlimit_kernel, after the tables of msl_set_beam /
+ *     msl_set_tilt are written and before the filters of the convolution kinds are summed): P -> P M, under any tilt;
+ *   - every transmission stack is low-passed after its build, t_k -> ifft2(M fft2(t_k)), on the handle's stream with no host copy:
+ *     msl_build_potential, msl_build_potentials, msl_build_thermal, msl_build_modes, msl_upload_potential, the absorptive build, and
+ *     the stacks msl_set_beam re-derives.  MSL_BUF_TRANSMISSION downloads the limited stack, MSL_BUF_POTENTIAL stays the unlimited V.
+ * With 3 cut_d < n_d the run is alias-free per axis: wave and t_k live in |h| <= cut, their product in |h| <= 2 cut, its fold-back at
+ * |h| >= n - 2 cut > cut, which the next propagator zeroes.  The incident wave is not masked (the first propagator removes its
+ * out-of-band part), and neither is the exit wave: the last operation of the slice loop is a transmission, so the exit spectrum is the
+ * alias-free band |h| <= cut plus the product terms beyond it.  pyslice_amd/bandlimit.py is the definition and turns a fraction of
+ * Nyquist into the cuts; integers here keep host and device from disagreeing on a bin at the edge.
+ * Both cuts negative clear the limit: the tables of a handle without the call (the host tables when no tilt was ever set) and the
+ * build path of today, bit for bit; clearing a handle that has no limit does nothing.  MSL_ERR_INVALID: one cut negative and the other
+ * not, a cut below 1, 3 cut_d >= n_d.  Valid any time after msl_create; the limit stays on the handle.
+ * Every effective call invalidates a built S-matrix (as msl_set_tilt does) and the resident potential: with a kept V (keep_potential,
+ * no absorption; such a handle has one stack, frame_batch is ignored) the transmission functions are made again from it under the new limit, otherwise the potential is dropped
+ * (msl_propagate is MSL_ERR_STATE until the next build).  The layer tap (msl_set_layers) inverts the propagator with its conjugate,
+ * which a masked table does not have: the caller keeps the two apart (pyslice_amd refuses the combination).
+ * msl_get_bandlimit: cut_xy[0..1] = the cuts, (-1, -1) without a limit.  Not in the reference, which has no band limit (quirk Q8). */
+int  msl_set_bandlimit(msl_handle* h, int32_t cut_x, int32_t cut_y);
+int  msl_get_bandlimit(const msl_handle* h, int32_t* cut_xy);
+
 /* Re-size the probe batch (re-allocates the (P,nx,ny) working buffers; probes must be set again). */
 int  msl_resize_probes(msl_handle* h, int32_t n_probes);
 

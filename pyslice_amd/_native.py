@@ -43,6 +43,7 @@ EXPORTS = [
     "msl_set_layer_reduce", "msl_layer_fetch", "msl_layer_pacbed_reset", "msl_layer_pacbed_add", "msl_layer_pacbed_download",
     "msl_layer_reduce_bytes",
     "msl_set_tilt", "msl_get_tilt",
+    "msl_set_bandlimit", "msl_get_bandlimit",
     "msl_set_absorption",
     "msl_set_tds", "msl_tds_fetch", "msl_tds_reduce",
 ]
@@ -171,6 +172,8 @@ def load():
         "msl_layer_reduce_bytes": (C.c_size_t, [vp, i32]),
         "msl_set_tilt": (C.c_int, [vp, dbl, dbl]),
         "msl_get_tilt": (C.c_int, [vp, vp]),
+        "msl_set_bandlimit": (C.c_int, [vp, i32, i32]),
+        "msl_get_bandlimit": (C.c_int, [vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -340,6 +343,17 @@ class Engine:
         t = np.zeros(2, dtype=np.float64)
         self._chk(self._lib.msl_get_tilt(self._h, _ptr(t)))
         return float(t[0]), float(t[1])
+
+    def set_bandlimit(self, cut_x, cut_y):
+        """band limit (msl_set_bandlimit): keep the frequency indices |h_x| <= cut_x, |h_y| <= cut_y in every propagator table and
+        every transmission stack built from now on; (-1, -1) clears it.  bandlimit.BandLimit.cuts() makes the cuts"""
+        self._chk(self._lib.msl_set_bandlimit(self._h, int(cut_x), int(cut_y)))
+
+    def get_bandlimit(self):
+        """(cut_x, cut_y) of the last set_bandlimit, (-1, -1) without a limit (msl_get_bandlimit)"""
+        c = np.zeros(2, dtype=np.int32)
+        self._chk(self._lib.msl_get_bandlimit(self._h, _ptr(c)))
+        return int(c[0]), int(c[1])
 
     def resize_probes(self, n_probes):
         self._chk(self._lib.msl_resize_probes(self._h, int(n_probes)))

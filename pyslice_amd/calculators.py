@@ -23,6 +23,7 @@ import numpy as np
 
 from . import _native, distributed
 from .aberrations import Aberrations
+from .bandlimit import as_bandlimit
 from .multislice import Probe, interaction_sigma, wavelength
 from .prism import Prism, beams as prism_beams
 from .potentials import (TORCH_AVAILABLE, _as_tensor, _device_index, atomic_numbers_of, gridFromTrajectory, loadKirkland, slice_edges,
@@ -132,7 +133,7 @@ class MultisliceCalculator:
     def __init__(self, device=None, force_cpu=False, *, output="host", dtype="complex128", progress=True,
                  gather="rank0", cache=False, k_window=None, frame_batch=None, k_bin=None, stream_tile=None, layers=None,
                  detectors=None, probe_batch=None, diffraction=None, aberrations=None, imaging=None, prism=None,
-                 spectroscopy=None, polar=None, thickness=None, tilt=None, precession=None, tds=False):
+                 spectroscopy=None, polar=None, thickness=None, tilt=None, precession=None, tds=False, bandlimit=None):
         """
         device / force_cpu: as the reference (calculators.py:41).  There is no CPU path here, so
         force_cpu=True raises.  Keyword-only extras (not in the reference):
@@ -239,6 +240,15 @@ class MultisliceCalculator:
                    per slice (msl_set_tds): 3-5 times the time of the elastic scan.  Up to 4 detectors, annuli that read the
                    intensity.  Allowed with tilt, aberrations, k_window, probe_batch, thickness; not built with prism, precession,
                    polar, diffraction, imaging, spectroscopy, layers, cache, stream_tile or several ranks.
+          bandlimit a bandlimit.BandLimit(fraction = 2/3), or the fraction itself: anti-aliasing.  setup() has the device mask every
+                   propagator table and low-pass every transmission stack after its build (msl_set_bandlimit) to the spatial
+                   frequencies below fraction x the Nyquist frequency of the coarser axis; with fraction <= 2/3 no product t psi
+                   folds back into the kept band.  Every run mode, source (MD frames, FrozenPhonons, PhononModes,
+                   AbsorptivePotential) and tilt, precession, aberrations, k_window, k_bin, probe_batch, frame_batch carry it:
+                   it lives in the tables and the stack.  `band_limit_mrad` (after setup()) is the largest angle kept; an
+                   aperture beyond it is a ValueError.  The exit spectrum is alias-free inside the band and not zero outside
+                   it (bandlimit.propagate_bandlimited).  None: every output is bit for bit that of a run without the argument.
+                   Not built with layers, thickness, tds, prism, cache, stream_tile or several ranks.
         """
         if force_cpu:
             raise NotImplementedError("pyslice_amd has no CPU path (force_cpu=True): use the reference for CPU runs")
@@ -383,6 +393,15 @@ class MultisliceCalculator:
                               ("stream_tile", stream_tile is not None)):
                 if val:
                     raise NotImplementedError(f"tds: {what} is not built")
+        self._bandlimit = bandlimit = as_bandlimit(bandlimit)
+        if bandlimit is not None:
+            # layers / thickness: the tap inverts the propagator with conj(P), which a masked table does not have; tds: its weights
+            # come from the unlimited Omega; prism: the beams and the window do not state the limit; cache: the key does not carry it
+            for what, val in (("layers", layers is not None), ("thickness", thickness is not None), ("tds", self._tds),
+                              ("prism", prism is not None), ("cache=True", cache), ("stream_tile", stream_tile is not None)):
+                if val:
+                    raise NotImplementedError(f"bandlimit: {what} is not built")
+        self.band_limit_mrad = None             # setup(): the largest scattering angle the band limit keeps
         self._precessing = False                # inside the tilt loop of a precession run
         self._layers = None                     # validated slice indices (setup), nz - 1 last
         self._engine = None
@@ -478,6 +497,15 @@ class MultisliceCalculator:
         self.nx, self.ny, self.nz = nx, ny, nz
         self.dx = xs[1] - xs[0]
         self.dy = ys[1] - ys[0]
+        self._bl_cuts = None
+        if self._bandlimit is not None:
+            if distributed.rank_world()[1] > 1:
+                raise NotImplementedError("bandlimit: a run over several ranks is not built")
+            self._bl_cuts = self._bandlimit.cuts(nx, ny, self.dx, self.dy)
+            self.band_limit_mrad = self._bandlimit.max_angle_mrad(wavelength(voltage_eV), nx, ny, self.dx, self.dy)
+            if aperture > self.band_limit_mrad:
+                raise ValueError(f"bandlimit: the aperture of {aperture:g} mrad lies beyond the band limit of {self.band_limit_mrad:.4g} mrad "
+                                 "(band_limit_mrad): the probe would lose its outer zone at the first propagation")
         self._layers = self._check_layers(len([xs, ys, zs][slice_axis]), distributed.rank_world()[1])
         self._prism_Bm = 0
         if self._prism is not None:
@@ -794,6 +822,8 @@ class MultisliceCalculator:
         eng.set_aberrations(self._aberrations)
         if self._tilt is not None and not self._tilt.is_zero:   # (no tilt: the engine keeps the tables it was created with)
             eng.set_tilt(*self._tilt.tangents)
+        if self._bl_cuts is not None:                           # (no limit: no call, the tables and the builds of today)
+            eng.set_bandlimit(*self._bl_cuts)
         if self._absorptive is not None:                        # before the first build: its tables are f D and g
             eng.set_absorption(self._absorptive.u_by_Z, self._absorptive.absorption)
         src = self._generated

@@ -37,6 +37,7 @@
 #include "image.h"
 #include "smatrix.h"
 #include "propagator.h"
+#include "bandlimit.h"
 
 using namespace msl;
 
@@ -189,6 +190,12 @@ struct msl_handle {
     double tilt_tan[2] = {0.0, 0.0};
     bool tilt_set = false;
     DevBuf<double2> tilt_work;
+    // band limit (msl_set_bandlimit): the largest kept |frequency index| per axis (-1: none).  While bl_on every
+    // propagator table is written on the device and masked (fill_propagator_device), and every transmission stack is low-passed after
+    // its build (bandlimit_built) with the weight vectors bl_mx, bl_my = mask / n (bandlimit.h)
+    int bl_cut[2] = {-1, -1};
+    bool bl_on = false;
+    DevBuf<float2> bl_mx, bl_my;
     // the result, (L, P, T_local, wpitch) with L = 1 + the layers of a thickness series (msl_set_layers): `layers` owns it for every
     // L, wf is a view of its last block, the exit waves.  layer_block: result block of every slice (-1: not a layer); tap: the
     // natural-order image set the layer tap transforms (FB * P images, psi's layout); tap_cx / tap_cy: the unscaled conjugate
@@ -1551,6 +1558,11 @@ int fill_propagator_device(msl_handle* h) {
                            n, M, 1.0 / (n * d), 0.5 * c.wavelength * c.dz, c.dz * h->tilt_tan[axis], axis ? h->pyt : h->pxt, split,
                            axis ? h->tap_cy : h->tap_cx, Pd, Ed, Wd);
         HIPCHK(h, hipGetLastError());
+        if (h->bl_on) {                                     // the band limit: before the filter sums, which then see the masked table
+            hipLaunchKernelGGL(propagator_bandlimit_kernel, dim3((unsigned)((n + PROP_BLOCK - 1) / PROP_BLOCK)), dim3(PROP_BLOCK), 0, h->stream,
+                               n, h->bl_cut[axis], axis ? h->pyt : h->pxt, split, axis ? h->tap_cy : h->tap_cx, Pd);
+            HIPCHK(h, hipGetLastError());
+        }
         if (!filter) continue;
         const int gap = M - 2 * n + 1, entries = (int)conv_filter_entries(o);
         hipLaunchKernelGGL(conv_lag_kernel, dim3((unsigned)(n + (gap + PROP_BLOCK - 1) / PROP_BLOCK)), dim3(PROP_BLOCK), 0, h->stream, n, M,
@@ -2128,6 +2140,36 @@ int absorptive_group(msl_handle* h, const PotGroup& p, bool atoms) {
     return rc;
 }
 
+// ---- band-limited transmission functions (bandlimit.h) ----
+// t <- B_x B_y t of the `count` stacks from batch slot `slot` on, in place in `trans` in natural order: along each axis one launch of
+// the generic line kernel, forward transform, x mask / n, inverse transform -- the column step of the two-pass slice loop with the
+// mask in the place of the Fresnel table.  Queued on the stream, no host copy.
+int bandlimit_lowpass(msl_handle* h, int slot, int count) {
+    const msl_config& c = h->cfg;
+    float2* t = h->trans + (size_t)slot * c.nz * c.nx * c.ny;
+    const long long images = (long long)c.nz * count;
+    if (images > 0x7fffffff) return fail(h, MSL_ERR_UNSUPPORTED, "band limit: too many slices");
+    h->cur = nullptr;
+    LineArgs r = row_args(h, t, t, (int)images, c.ny);
+    r.fft1 = +1; r.m1_kind = MUL_VEC; r.m1 = h->bl_my; r.fft2 = -1;
+    int rc = launch_lines(h, h->plan_y, r, K_OTHER);
+    if (rc) return rc;
+    LineArgs k = col_args(h, t, t, (int)images, c.ny, c.ny);
+    k.fft1 = +1; k.m1_kind = MUL_VEC; k.m1 = h->bl_mx; k.fft2 = -1;
+    return launch_lines(h, h->plan_x, k, K_OTHER);
+}
+
+// The same for stacks a build has left in the order of the slice loop: the slices the one-pass loop keeps transposed come back to
+// natural order first and are transposed again afterwards (both are no-ops on the two-pass loop), so the stack is limited once, in one
+// orientation, whatever the loop is.
+int bandlimit_built(msl_handle* h, int slot, int count) {
+    int rc = MSL_OK;
+    for (int f = 0; f < count && rc == MSL_OK; ++f) rc = restore_natural_slices(h, slot + f);
+    if (rc || (rc = bandlimit_lowpass(h, slot, count))) return rc;
+    for (int f = 0; f < count && rc == MSL_OK; ++f) rc = transpose_odd_slices(h, slot + f);
+    return rc;
+}
+
 // Projected potentials + transmission functions of `count` MD frames (the same atoms, `count` sets of positions) into the batch
 // slots first_slot .. first_slot + count - 1: ONE launch each of the atom preparation, the stable counting sort (keys = frame x
 // slice x species), the two phase tables, the structure factor and the two inverse-transform passes for as many frames as the
@@ -2203,6 +2245,7 @@ int build_potentials(msl_handle* h, const double* pos, const int32_t* Z, int64_t
         if ((rc = h->abs_on ? absorptive_group(h, p, n > 0 && p.nsp > 0) : potential_ifft(h, p))) return rc;
     }
     h->n_species = p.nsp;
+    if (h->bl_on && (rc = bandlimit_built(h, first_slot, count))) return rc;
     if ((rc = timer.end(h, &h->ctr.ms_potential))) return rc;
     h->have_potential = true;
     h->abs_built = h->abs_on;
@@ -2603,11 +2646,12 @@ int msl_set_beam(msl_handle* h, double wavelength, double sigma, double dz) {
         HIPCHK(h, hipStreamSynchronize(h->stream));
         smatrix_release(h);
     }
-    int rc = h->tilt_set ? fill_propagator_device(h) : fill_propagator(h);      // a tilt stays on the handle
+    int rc = (h->tilt_set || h->bl_on) ? fill_propagator_device(h) : fill_propagator(h);      // a tilt and a band limit stay on the handle
     if (rc) return rc;
     if (h->have_potential && h->abs_built) {
         // an absorptive build keeps its two real stacks: t of every batch slot again, with the new sigma
         if ((rc = absorptive_transmission(h, 0, h->FB))) return rc;
+        if (h->bl_on && (rc = bandlimit_lowpass(h, 0, h->FB))) return rc;
         if (h->tds_on && h->tds_W && (rc = tds_weights(h, false))) return rc;       // and the TDS weights, which carry 2 sigma^2
         for (int f = 0; f < h->FB; ++f) if ((rc = transpose_odd_slices(h, f))) return rc;
         HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -2617,6 +2661,7 @@ int msl_set_beam(msl_handle* h, double wavelength, double sigma, double dz) {
         hipLaunchKernelGGL(transmission_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->trans, h->V,
                            (long long)n, (float)sigma);
         HIPCHK(h, hipGetLastError());
+        if (h->bl_on && (rc = bandlimit_lowpass(h, 0, 1))) return rc;
         if ((rc = transpose_odd_slices(h, h->cur_batch))) return rc;
         HIPCHK(h, hipStreamSynchronize(h->stream));
     }
@@ -2677,6 +2722,61 @@ int msl_set_tilt(msl_handle* h, double tan_x, double tan_y) {
     if (rc) { h->tilt_tan[0] = old[0]; h->tilt_tan[1] = old[1]; return rc; }
     h->tilt_set = true;
     h->sm_built = false;                                    // an S-matrix belongs to the tilt it was built at
+    return MSL_OK;
+}
+
+int msl_set_bandlimit(msl_handle* h, int32_t cut_x, int32_t cut_y) {
+    if (!h) return fail(h, MSL_ERR_INVALID, "null handle");
+    const msl_config& c = h->cfg;
+    const bool clear = cut_x < 0 && cut_y < 0;
+    if (!clear) {
+        if (cut_x < 1 || cut_y < 1)
+            return fail(h, MSL_ERR_INVALID, "msl_set_bandlimit: cuts (%d, %d): both at least 1, or both negative to clear", cut_x, cut_y);
+        if (3LL * cut_x >= c.nx || 3LL * cut_y >= c.ny)
+            return fail(h, MSL_ERR_INVALID, "msl_set_bandlimit: cuts (%d, %d) are not alias-free on the %d x %d grid (3 cut < n)", cut_x, cut_y,
+                        c.nx, c.ny);
+    }
+    if (clear && !h->bl_on) return MSL_OK;                  // never set: the tables and the stacks stay what they are
+    HIPCHK(h, hipSetDevice(c.device));
+    int rc;
+    if (!clear) {
+        if ((rc = h->bl_mx.reserve(h, (size_t)c.nx)) || (rc = h->bl_my.reserve(h, (size_t)c.ny))) return rc;
+        hipLaunchKernelGGL(bandlimit_mask_kernel, dim3((unsigned)((c.nx + BL_BLOCK - 1) / BL_BLOCK)), dim3(BL_BLOCK), 0, h->stream, c.nx, cut_x,
+                           h->bl_mx.p);
+        hipLaunchKernelGGL(bandlimit_mask_kernel, dim3((unsigned)((c.ny + BL_BLOCK - 1) / BL_BLOCK)), dim3(BL_BLOCK), 0, h->stream, c.ny, cut_y,
+                           h->bl_my.p);
+        HIPCHK(h, hipGetLastError());
+    }
+    const bool old_on = h->bl_on;
+    const int old_cut[2] = {h->bl_cut[0], h->bl_cut[1]};
+    h->bl_on = !clear;
+    h->bl_cut[0] = clear ? -1 : cut_x; h->bl_cut[1] = clear ? -1 : cut_y;
+    // cleared on a handle without a tilt: the host tables again, bit for bit those of msl_create / msl_set_beam
+    if ((rc = (h->tilt_set || h->bl_on) ? fill_propagator_device(h) : fill_propagator(h))) {
+        h->bl_on = old_on; h->bl_cut[0] = old_cut[0]; h->bl_cut[1] = old_cut[1];       // a refused call leaves the handle's state as it was
+        return rc;
+    }
+    h->sm_built = false;                                    // an S-matrix belongs to the tables and the stack it was built with
+    if (h->have_potential && h->V && !h->abs_built) {
+        // a kept V (keep_potential, which runs at a frame batch of 1: one stack, slot 0): the transmission functions again from it,
+        // as msl_set_beam makes them, under the new limit
+        const size_t n = (size_t)c.nx * c.ny * c.nz;
+        hipLaunchKernelGGL(transmission_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->trans, h->V, (long long)n,
+                           (float)c.sigma);
+        HIPCHK(h, hipGetLastError());
+        if (h->bl_on && (rc = bandlimit_lowpass(h, 0, 1))) return rc;
+        if ((rc = transpose_odd_slices(h, h->cur_batch))) return rc;
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        return MSL_OK;
+    }
+    h->have_potential = false;                              // no V to make them from: the stacks belong to the limit they were built
+    h->abs_built = false;                                   // under, and the next build makes them
+    return MSL_OK;
+}
+
+int msl_get_bandlimit(const msl_handle* h, int32_t* cut_xy) {
+    if (!h || !cut_xy) return MSL_ERR_INVALID;
+    cut_xy[0] = h->bl_cut[0]; cut_xy[1] = h->bl_cut[1];
     return MSL_OK;
 }
 
@@ -3075,6 +3175,7 @@ int msl_upload_potential(msl_handle* h, const float* V) {
     hipLaunchKernelGGL(transmission_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->trans + (size_t)h->cur_batch * n, dst,
                        (long long)n, (float)c.sigma);
     HIPCHK(h, hipGetLastError());
+    if (h->bl_on) { int rc = bandlimit_lowpass(h, h->cur_batch, 1); if (rc) return rc; }
     { int rc = transpose_odd_slices(h, h->cur_batch); if (rc) return rc; }
     HIPCHK(h, hipStreamSynchronize(h->stream));
     h->have_potential = true;

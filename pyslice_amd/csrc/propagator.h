@@ -4,7 +4,7 @@
 // +dz tan(theta) per slice.  The propagator stays separable, so the slice loop and the layer tap run unchanged on tables that carry
 // the extra factor.  The convolution passes hold the filter of an even table only: the two filter kernels run for an axis at a zero
 // tangent, and a tilt along such an axis runs on the two-pass loop (mslice.hip: set_loop_mode).  One to three launches per axis, all on
-// the handle's stream, no host copy:
+// the handle's stream, no host copy (one more, propagator_bandlimit_kernel below, under a band limit):
 //
 // propagator_tables_kernel: lane m forms the phase in turns in float64, t = -(lambda dz / 2 k^2 + dz tan k), reduces it to one turn
 //   (t - rint(t): the reduction is exact, the phase carries the float64 rounding of its products, ~1e-15 turns; dz tan / (n d) is no
@@ -55,6 +55,24 @@ __global__ void __launch_bounds__(PROP_BLOCK) propagator_tables_kernel(int n, in
         sincospi(-2.0 * ((double)m / (double)M), &sn, &cs);
         Wd[m] = make_double2(cs, sn);
     }
+}
+
+// Band limit (msl_set_bandlimit): runs after propagator_tables_kernel and before the two filter kernels, and
+// zeroes the entries with |f(m)| > cut of every table of the axis -- plain, split (in its permuted order), conj and, for a convolution
+// axis, the float64 copy Pd the filter sums read, so that the filter is that of the masked table.  A kept entry is not touched: with
+// no entry beyond the cut the tables are bit for bit those of propagator_tables_kernel.  split and Pd may be null.
+__global__ void __launch_bounds__(PROP_BLOCK) propagator_bandlimit_kernel(int n, int cut, float2* __restrict__ plain,
+                                                                          float2* __restrict__ split, float2* __restrict__ conj,
+                                                                          double2* __restrict__ Pd) {
+    const int m = blockIdx.x * blockDim.x + threadIdx.x;
+    if (m >= n) return;
+    const int f = signed_freq(m, n);
+    if ((f < 0 ? -f : f) <= cut) return;
+    const float2 zero = make_float2(0.f, 0.f);
+    plain[m] = zero;
+    if (split) split[(m & 1) * (n / 2) + (m >> 1)] = zero;
+    conj[m] = zero;
+    if (Pd) Pd[m] = make_double2(0.0, 0.0);
 }
 
 // sum of v over the block, in a fixed order; every lane of the block must call it

@@ -11,6 +11,7 @@ import numpy as np
 from . import _native
 from .aberrations import Aberrations
 from .potentials import TORCH_AVAILABLE, _as_tensor, _device_index
+from .bandlimit import as_bandlimit
 from .tilt import as_tilt
 
 if TORCH_AVAILABLE:
@@ -181,7 +182,7 @@ def create_batched_probes(base_probe, probe_positions, device=None):
     return out
 
 
-def Propagate(probe, potential, device=None, tilt=None):
+def Propagate(probe, potential, device=None, tilt=None, bandlimit=None):
     """Multislice propagation (reference multislice.py:237-299).
 
     Returns the exit wave(s) as complex128, squeezed to (nx,ny) for a single probe, and -- like the
@@ -191,15 +192,34 @@ def Propagate(probe, potential, device=None, tilt=None):
     on the device (msl_set_tilt).  None or Tilt() is no tilt: on a potential that was never propagated with a tilt the call runs exactly
     as without the argument (the host tables, no call).  After one tilted call on a potential its engine keeps device-written tables:
     later untilted calls set (0, 0) through the same kernels, whose tables equal the host's up to one float rounding per entry.
+
+    bandlimit (not in the reference): a bandlimit.BandLimit or a fraction of Nyquist (<= 2/3): the propagator tables are masked and
+    the transmission functions of the potential are made again from its V and low-passed (msl_set_bandlimit).  None clears a limit an
+    earlier call left on the potential's engine; on an engine that never had one the call runs exactly as without the argument.
+    The limit stays on the potential's engine: a call with the cuts it already carries makes no call of its own (msl_set_beam has
+    re-derived the limited stack).  An analytic probe whose aperture lies beyond the band (BandLimit.max_angle_mrad) is a ValueError.
     """
     tilt = as_tilt(tilt, "Propagate: tilt")
+    bandlimit = as_bandlimit(bandlimit, "Propagate: bandlimit")
     eng = potential._engine
     kind, payload = probe._recipe()
+    cuts = None
+    if bandlimit is not None:
+        xs, ys = _to_numpy(potential.xs), _to_numpy(potential.ys)
+        grid = (len(xs), len(ys), float(xs[1] - xs[0]), float(ys[1] - ys[0]))
+        cuts = bandlimit.cuts(*grid)
+        limit_mrad = bandlimit.max_angle_mrad(probe.wavelength, *grid)
+        if kind == "analytic" and probe.mrad > limit_mrad:
+            raise ValueError(f"Propagate: bandlimit: the aperture of {probe.mrad:g} mrad lies beyond the band limit of {limit_mrad:.4g} mrad: "
+                             "the probe would lose its outer zone at the first propagation")
     zs = _to_numpy(potential.zs)
     dz = zs[1] - zs[0] if len(zs) > 1 else 0.5
     eng.set_beam(probe.wavelength, interaction_sigma(probe.eV), dz)
     if not tilt.is_zero or eng.get_tilt() != (0.0, 0.0):    # the potential's engine is shared and the tilt stays on it
         eng.set_tilt(*tilt.tangents)
+    if cuts != getattr(potential, "_bandlimit_cuts", None):  # the potential's engine is shared and the limit stays on it
+        eng.set_bandlimit(*(cuts if cuts is not None else (-1, -1)))
+        potential._bandlimit_cuts = cuts
     eng.resize_probes(len(payload))
     if kind == "analytic":
         eng.set_aberrations(probe.aberrations)     # always: the potential's engine is shared and the state stays on it
