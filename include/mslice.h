@@ -575,6 +575,23 @@ int  msl_image_download(msl_handle* h, int64_t first, int64_t n, double* out);
  *   the others its sinc interpolation.  xy = n_probes x 2 doubles; n_probes must be the handle's.  MSL_ERR_STATE without a built
  *   S-matrix or with n_frames == 0.  MSL_BUF_EXIT then holds psi_p; the probe buffer is overwritten and marked unset.  Four launches,
  *   queued on the stream; no atomics: repeated calls are bitwise equal.
+ * msl_smatrix_probes_cropped: the same probes on PRISM's own (nx/fx) x (ny/fy) grid.  The window of probe p along x is wx = nx/fx
+ *   consecutive pixels modulo nx and wx divides nx, so i -> i mod wx maps it one-to-one onto [0, wx) (likewise y).  The folded wave
+ *   psi_c[i mod wx, j mod wy] = psi_p[i, j], (i, j) inside W_p, satisfies  fft2(psi_c)[m, n] = fft2(psi_p)[fx m, fy n]  exactly, with no
+ *   phase ramp, because exp(-2 pi i m (i mod wx) / wx) = exp(-2 pi i (fx m) i / nx).  In stored (fftshifted) order the cropped pixel
+ *   (a, b) is the full-grid pixel (floor(nx/2) + fx (a - floor(wx/2)), floor(ny/2) + fy (b - floor(wy/2))), which exists for odd and
+ *   even lengths alike: the cropped spectrum is msl_smatrix_probes's taken at every (fx, fy)-th pixel, value for value, not rescaled
+ *   (a sum over a region is about 1/(fx fy) of the full-grid sum: each cropped pixel stands for fx fy full ones).
+ *   `src` holds the built S-matrix (its n_probes only sets the chunk of msl_smatrix_build; it may have n_frames == 0; its aberrations
+ *   are the ones applied).  `dst` is an ordinary handle on the same device with nx = src.nx / fx, ny = src.ny / fy, the same dx, dy
+ *   and wavelength, created without any potential (nz = 1 will do); its k-grid h / (n d) is the cropped pattern's own, so its k-window,
+ *   bins, detectors and polar map apply unchanged.  n_probes must be dst's.  The coefficients run on src; the cropped synthesis writes
+ *   psi_c into dst's MSL_BUF_EXIT and probe buffer (every pixel exactly once, no zero fill); dst's row transform and exit epilogue
+ *   write frame slot `slot` of dst's result.  The two streams are ordered by events, both ways: dst's earlier work completes before
+ *   its buffers are overwritten, the synthesis before dst's transform; no device-wide wait.  MSL_ERR_INVALID for a null argument,
+ *   different devices, a dst grid that is not src's divided by its interpolation, different pixel sizes or wavelength, a probe-count
+ *   mismatch, a slot out of range or a non-finite position; MSL_ERR_STATE without a built S-matrix or with dst.n_frames == 0 (errors
+ *   are reported on src).  No atomics: repeated calls are bitwise equal.
  * msl_smatrix_end:    frees S, c and the beams; msl_destroy and msl_set_beam (the wavelength changes the beam set) do the same,
  *   msl_resize_probes keeps S.
  *   Not in the reference, which propagates every probe position through every slice. */
@@ -582,6 +599,7 @@ int  msl_smatrix_begin(msl_handle* h, int32_t fx, int32_t fy, double mrad);
 int  msl_smatrix_beams(const msl_handle* h, int32_t* hxhy_or_null);
 int  msl_smatrix_build(msl_handle* h);
 int  msl_smatrix_probes(msl_handle* h, const double* xy, int32_t n_probes, int32_t slot);
+int  msl_smatrix_probes_cropped(msl_handle* src, msl_handle* dst, const double* xy, int32_t n_probes, int32_t slot);
 int  msl_smatrix_end(msl_handle* h);
 
 /* ---- thickness series: spectra of intermediate layers of the stack ----

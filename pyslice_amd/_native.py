@@ -36,7 +36,8 @@ EXPORTS = [
     "msl_polar_layout", "msl_set_polar", "msl_polar_detect",
     "msl_coherent_reset", "msl_coherent_add", "msl_coherent_finish",
     "msl_image_reset", "msl_image_add", "msl_image_download",
-    "msl_smatrix_begin", "msl_smatrix_beams", "msl_smatrix_build", "msl_smatrix_probes", "msl_smatrix_end",
+    "msl_smatrix_begin", "msl_smatrix_beams", "msl_smatrix_build", "msl_smatrix_probes", "msl_smatrix_probes_cropped",
+    "msl_smatrix_end",
     "msl_tacaw_welch_has", "msl_tacaw_welch", "msl_tacaw_welch_layer",
     "msl_set_structure", "msl_build_thermal", "msl_thermal_positions",
     "msl_set_modes", "msl_build_modes", "msl_mode_positions",
@@ -150,6 +151,7 @@ def load():
         "msl_smatrix_beams": (C.c_int, [vp, vp]),
         "msl_smatrix_build": (C.c_int, [vp]),
         "msl_smatrix_probes": (C.c_int, [vp, vp, i32, i32]),
+        "msl_smatrix_probes_cropped": (C.c_int, [vp, vp, vp, i32, i32]),
         "msl_smatrix_end": (C.c_int, [vp]),
         "msl_tacaw_welch_has": (C.c_int, [i32]),
         "msl_tacaw_welch": (C.c_int, [vp, vp, vp, i64, i32, i64, i32, i32, vp]),
@@ -882,6 +884,14 @@ class Engine:
         spectra into frame slot `slot`; xy: (n_probes, 2) Angstrom"""
         xy = np.ascontiguousarray(xy, dtype=np.float64).reshape(-1, 2)
         self._chk(self._lib.msl_smatrix_probes(self._h, _ptr(xy), xy.shape[0], int(slot)))
+
+    def smatrix_probes_cropped(self, dst_engine, xy, slot):
+        """the same probes on the cropped (nx / fx, ny / fy) grid of `dst_engine` (an Engine of that grid on this device, with the same
+        pixel size and wavelength, n_probes = len(xy), n_frames > 0; it needs no potential): the folded exit waves psi_c[i mod wx,
+        j mod wy] = psi_p[i, j] go to its exit_waves() and their spectra -- this engine's smatrix_probes spectra at
+        prism.crop_index, value for value -- into its frame slot `slot`.  This engine holds the S-matrix and the aberrations."""
+        xy = np.ascontiguousarray(xy, dtype=np.float64).reshape(-1, 2)
+        self._chk(self._lib.msl_smatrix_probes_cropped(self._h, dst_engine._h, _ptr(xy), xy.shape[0], int(slot)))
 
     def smatrix_end(self):
         """free the S-matrix (close(), set_beam() do the same)"""

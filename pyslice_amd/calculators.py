@@ -198,6 +198,11 @@ class MultisliceCalculator:
                    stay on the full grid (zeros outside the window), so k_window, k_bin, aberrations, detectors and probe_batch
                    work as before.  Needs aperture > 0 and an interpolation that divides the grid (setup() raises ValueError).
                    Not built: Diffraction(split=True), imaging, layers, stream_tile, cache, several ranks.
+                   Prism(f, crop=True): every probe is synthesised, transformed, stored and reduced on the cropped (nx/fx, ny/fy)
+                   grid of a second, potential-less engine (msl_smatrix_probes_cropped).  The results are the uncropped run's
+                   spectra at every (fx, fy)-th pixel (prism.crop_index), value for value and NOT rescaled -- a sum over a region is
+                   about 1/(fx fy) of the uncropped run's, each cropped pixel standing for fx fy full ones -- on the cropped grid's
+                   k axes, with .prism_crop = (fx, fy); k_window, k_bin and Diffraction(bin=) are checked against the cropped grid.
           spectroscopy spectrum-image mode: a spectroscopy.Spectroscopy(detectors=[...]).  run_spectrum_image() streams the probes
                    through the device in batches; per probe batch ALL T frames go into a ring of T frame slots, msl_tacaw turns the
                    ring into the TACAW intensity and msl_spectrum_detect sums it over every detector in one pass: the result is
@@ -405,6 +410,8 @@ class MultisliceCalculator:
         self._precessing = False                # inside the tilt loop of a precession run
         self._layers = None                     # validated slice indices (setup), nz - 1 last
         self._engine = None
+        self._beam_engine = None                # Prism(f, crop=True): the full-grid engine of the S-matrix; _engine is the cropped one
+        self._crop = None                       # (fx, fy) of a cropped PRISM run (setup)
         # reference calculators.py:70-76 (display names for Z <= 36)
         self.element_map = {
             1: 'H', 2: 'He', 3: 'Li', 4: 'Be', 5: 'B', 6: 'C', 7: 'N', 8: 'O', 9: 'F', 10: 'Ne', 11: 'Na', 12: 'Mg',
@@ -508,6 +515,7 @@ class MultisliceCalculator:
                                  "(band_limit_mrad): the probe would lose its outer zone at the first propagation")
         self._layers = self._check_layers(len([xs, ys, zs][slice_axis]), distributed.rank_world()[1])
         self._prism_Bm = 0
+        self._crop = None
         if self._prism is not None:
             self._check_prism(nx, ny, distributed.rank_world()[1])
         # (not in the reference) a line length without a slice-loop kernel of its own costs 2-4 x: name a nearby sampling that has one
@@ -569,7 +577,7 @@ class MultisliceCalculator:
             self._engine.set_layers(self._layers[:-1])
         self._configure_engine()
         if self._prism is not None:                             # (the probes are synthesised from the S-matrix: none to set)
-            self._engine.smatrix_begin(self._prism.interpolation, self.aperture)
+            self._source_engine().smatrix_begin(self._prism.interpolation, self.aperture)
             return
         self._engine.set_probes(self.aperture, np.asarray(self.probe_positions, dtype=np.float64))
 
@@ -646,7 +654,7 @@ class MultisliceCalculator:
                 self._engine.set_layer_reduce(self._thickness[:-1], what,
                                               bin=(1, 1) if self._diffraction is None else self._diffraction.bin)
             if self._prism is not None:
-                self._engine.smatrix_begin(self._prism.interpolation, self.aperture)
+                self._source_engine().smatrix_begin(self._prism.interpolation, self.aperture)
         self._create_engine(Pc, batch, batch, shrink, furnish=furnish, device=_device_index(self.device))
         self.probe_batch = self._engine.n_probes
 
@@ -708,11 +716,23 @@ class MultisliceCalculator:
         # reference and let the last owner free it, instead of closing it under them.  (A caller that keeps an earlier result
         # and only needs its host arrays frees the device side with result.release().)
         self._engine = None
+        self._beam_engine = None
         return len(self._slice_coords)
 
+    def _result_grid(self):
+        """(nx, ny) of the grid the exit waves are transformed and stored on: the simulation grid, or with Prism(f, crop=True) the
+        cropped one, (nx / fx, ny / fy)"""
+        crop = getattr(self, "_crop", None)
+        return (self.nx, self.ny) if crop is None else (self.nx // crop[0], self.ny // crop[1])
+
+    def _source_engine(self):
+        """the engine that holds the potential, the slice loop and the S-matrix: with Prism(f, crop=True) the full-grid beam engine
+        (self._engine is then the result engine on the cropped grid), else the one engine of the run"""
+        return self._beam_engine if getattr(self, "_beam_engine", None) is not None else self._engine
+
     def _stored_window(self):
-        """(wx, wy) of the spectrum kept of every exit wave: the k-window, or the grid"""
-        return self._k_window if self._k_window is not None else (self.nx, self.ny)
+        """(wx, wy) of the spectrum kept of every exit wave: the k-window, or the grid (of a cropped PRISM run: the cropped one)"""
+        return self._k_window if self._k_window is not None else self._result_grid()
 
     def _stored_shape(self):
         """(sx, sy, pitch): the stored window divided by the detector bin, and the pixels between two images of the result (whole
@@ -751,8 +771,11 @@ class MultisliceCalculator:
         the coherent accumulator of a split run (16 * pitch bytes per probe), the image accumulator of an imaging run (8 * nx * ny
         bytes per probe, layer and defocus), the output scratch of a polar run (8 * n_bins bytes per image), the transmission stacks
         of the batch, the TDS weight stack (4 bytes per detector, slice and pixel) and the phase tables exceed 0.9 x the free device
-        memory."""
+        memory.  With Prism(f, crop=True) the work buffers and the ring of a probe are on the cropped grid (gx, gy); the S-matrix,
+        the stacks and the work buffers of the build chunk, min(Pc, Bm) beams on the beam engine, stay on the full one."""
         nx, ny, n_slices = self.nx, self.ny, len(self._slice_coords)
+        gx, gy = self._result_grid()
+        chunk = 32.0 * nx * ny * getattr(self, "_prism_Bm", 0) if getattr(self, "_crop", None) is not None else 0.0
         pitch = self._stored_shape()[2]
         tables = self._phase_table_bytes(batch)
         coh = 16.0 * pitch if self._diffraction is not None and self._diffraction.split else 0.0
@@ -771,8 +794,8 @@ class MultisliceCalculator:
             bx, by = self._diffraction.bin if self._diffraction is not None else (1, 1)
             series = 8.0 * pitch + 8.0 * nx * ny + L * polar + 8.0 * L * (len(self._detectors) if self._detectors is not None else 0)
             coh += 8.0 * L * (sx // bx) * (sy // by) if self._diffraction is not None else 0.0
-        while Pc > 1 and (Pc * batch * (32.0 * nx * ny + 8.0 * pitch + polar + series) + Pc * coh + batch * self._stack_bytes() * n_slices * nx * ny + tables + smatrix + 1e9
-                          > 0.9 * free_b):
+        while Pc > 1 and (Pc * batch * (32.0 * gx * gy + 8.0 * pitch + polar + series) + min(chunk, 32.0 * nx * ny * Pc) + Pc * coh
+                          + batch * self._stack_bytes() * n_slices * nx * ny + tables + smatrix + 1e9 > 0.9 * free_b):
             Pc = max(1, Pc // 2)
         return Pc
 
@@ -800,23 +823,37 @@ class MultisliceCalculator:
         give up."""
         while True:
             try:
-                self._engine = _native.Engine(self.nx, self.ny, len(self._slice_coords), self.dx, self.dy, self._dz,
-                                              wavelength(self.voltage_eV), interaction_sigma(self.voltage_eV), n_probes=n_probes,
-                                              n_frames=slots, window=self._k_window, frame_batch=batch, **engine_kw)
+                if self._crop is not None:
+                    # Prism(f, crop=True): the beam engine on the full grid -- the potential, the slice loop and S; no result
+                    # (n_frames = 0), and its probe count is the chunk of beams of one slice loop of smatrix_build -- and the result
+                    # engine on the cropped grid, which needs no potential (one slice) and owns the ring and every reduction
+                    gx, gy = self._result_grid()
+                    self._beam_engine = _native.Engine(self.nx, self.ny, len(self._slice_coords), self.dx, self.dy, self._dz,
+                                                       wavelength(self.voltage_eV), interaction_sigma(self.voltage_eV),
+                                                       n_probes=max(1, min(n_probes, self._prism_Bm)), n_frames=0, frame_batch=1,
+                                                       **{k: v for k, v in engine_kw.items() if k == "device"})
+                    self._engine = _native.Engine(gx, gy, 1, self.dx, self.dy, self._dz, wavelength(self.voltage_eV),
+                                                  interaction_sigma(self.voltage_eV), n_probes=n_probes, n_frames=slots,
+                                                  window=self._k_window, frame_batch=1, **engine_kw)
+                else:
+                    self._engine = _native.Engine(self.nx, self.ny, len(self._slice_coords), self.dx, self.dy, self._dz,
+                                                  wavelength(self.voltage_eV), interaction_sigma(self.voltage_eV), n_probes=n_probes,
+                                                  n_frames=slots, window=self._k_window, frame_batch=batch, **engine_kw)
                 if furnish is not None:
                     furnish()
                 return
             except MemoryError:
-                if self._engine is not None:                    # (furnish() ran out of memory: this engine goes before the next)
-                    self._engine.close()
-                    self._engine = None
+                for name in ("_engine", "_beam_engine"):        # (furnish() ran out of memory: these engines go before the next)
+                    if getattr(self, name) is not None:
+                        getattr(self, name).close()
+                        setattr(self, name, None)
                 smaller = shrink(n_probes, slots, batch)
                 if smaller is None:
                     raise
                 n_probes, slots, batch = smaller
 
     def _configure_engine(self):
-        eng = self._engine
+        eng = self._source_engine()         # (the result engine of a cropped PRISM run transforms and reduces: nothing to configure)
         eng.set_kirkland(loadKirkland())
         eng.set_slices(*slice_edges(self._slice_coords))
         eng.set_aberrations(self._aberrations)
@@ -837,7 +874,7 @@ class MultisliceCalculator:
         """The potentials of the frames first_frame .. first_frame+n-1 into the batch slots (the engine's singular call at a frame
         batch of 1): MD frames from the trajectory's host array, frozen-phonon configurations and phonon-mode frames generated on
         the device by index."""
-        eng = self._engine
+        eng = self._source_engine()
         src = self._generated
         if src is not None:
             (eng.build_modes if isinstance(src, PhononModes) else eng.build_thermal)(src.seed, first_frame, n)
@@ -901,17 +938,26 @@ class MultisliceCalculator:
             raise ValueError(f"prism: interpolation ({fx}, {fy}) does not divide the {nx} x {ny} grid; pick a sampling whose grid it "
                              f"divides (potentials.suggest_sampling() names grid sizes near a sampling)")
         self._prism_Bm = len(prism_beams(nx, ny, self.dx, self.dy, self.aperture, wavelength(self.voltage_eV), (fx, fy)))
+        if self._prism.cropped:             # (crop=True at (1, 1) runs as crop=False)
+            self._crop = (fx, fy)
+            if self._k_window is not None and (self._k_window[0] > nx // fx or self._k_window[1] > ny // fy):
+                raise ValueError(f"prism: k_window {self._k_window} lies outside the cropped {nx // fx} x {ny // fy} spectrum of "
+                                 f"Prism(({fx}, {fy}), crop=True)")
 
     def _prism_loop(self, reduce_batch):
         """The pass of run_detectors() / run_diffraction() with prism: per frame one potential and one S-matrix (Bm slice loops
-        instead of P), then every probe batch synthesised from it into frame slot 0 and reduced as in _probe_batch_loop."""
-        eng = self._engine
+        instead of P), then every probe batch synthesised from it into frame slot 0 and reduced as in _probe_batch_loop.  With
+        Prism(f, crop=True) the S-matrix is the beam engine's and the probes go to the result engine, which reduce_batch reads."""
+        eng = self._source_engine()
         bar = _Progress(self._progress, self.n_frames)
         for s in range(self.n_frames):
             self._build(s, 1)
             eng.smatrix_build()
             for p0, real, xy in self._probe_batches():
-                eng.smatrix_probes(xy, 0)
+                if self._crop is not None:
+                    eng.smatrix_probes_cropped(self._engine, xy, 0)
+                else:
+                    eng.smatrix_probes(xy, 0)
                 reduce_batch(p0, real, s, 1)
             bar.update(1)
         bar.close()
@@ -948,9 +994,16 @@ class MultisliceCalculator:
     def _stem_data(self, signals, tds_per_slice=None):
         from .stem_data import STEMData
         kxs, kys = self._k_axes()
-        return STEMData(signals=signals, detectors=list(self._detectors), probe_positions=self.probe_positions,
-                        time=np.arange(self.n_frames) * self.trajectory.timestep, kxs=_as_tensor(kxs), kys=_as_tensor(kys),
-                        probe=self.base_probe, tds_per_slice=tds_per_slice, **self._layer_fields())
+        return self._tag_crop(STEMData(signals=signals, detectors=list(self._detectors), probe_positions=self.probe_positions,
+                                       time=np.arange(self.n_frames) * self.trajectory.timestep, kxs=_as_tensor(kxs), kys=_as_tensor(kys),
+                                       probe=self.base_probe, tds_per_slice=tds_per_slice, **self._layer_fields()))
+
+    def _tag_crop(self, result):
+        """a result of a Prism(f, crop=True) run carries .prism_crop = (fx, fy): its pixels are the uncropped run's at
+        prism.crop_index, not rescaled, on the cropped grid's own k axes"""
+        if self._crop is not None:
+            result.prism_crop = self._crop
+        return result
 
     def _layer_fields(self):
         """layer / thickness of a result with a thickness axis: the slice indices, and the depth in Angstrom at the exit side of each
@@ -1009,7 +1062,7 @@ class MultisliceCalculator:
         self._precessing = True
         try:
             for t in tilts:
-                self._engine.set_tilt(*t.tangents)
+                self._source_engine().set_tilt(*t.tangents)
                 out = run()
                 for owner, name in [(out, f) for f in fields] + ([(out.stem, "signals")] if getattr(out, "stem", None) is not None else []):
                     val = getattr(owner, name)
@@ -1082,10 +1135,10 @@ class MultisliceCalculator:
         self.elapsed = time.time() - t0
         self.frames_computed, self.frames_cached = T, 0
         kxs, kys = self._k_axes()
-        return DiffractionData(intensity=acc, kxs=_as_tensor(bin_centres(kxs, bx)), kys=_as_tensor(bin_centres(kys, by)), bin=(bx, by),
-                               n_frames=T, probe_positions=self.probe_positions, probe=self.base_probe,
-                               stem=None if signals is None else self._stem_data(signals), elastic=elastic,
-                               patterns="pacbed" if pacbed else "position", **self._layer_fields())
+        return self._tag_crop(DiffractionData(intensity=acc, kxs=_as_tensor(bin_centres(kxs, bx)), kys=_as_tensor(bin_centres(kys, by)),
+                                              bin=(bx, by), n_frames=T, probe_positions=self.probe_positions, probe=self.base_probe,
+                                              stem=None if signals is None else self._stem_data(signals), elastic=elastic,
+                                              patterns="pacbed" if pacbed else "position", **self._layer_fields()))
 
     def run_images(self):
         """Frame-averaged images behind the objective lens (HRTEM, focal series), for every probe: probe batches outside, frame
@@ -1265,10 +1318,10 @@ class MultisliceCalculator:
             acc = acc.reshape(acc.shape[:-2] + (R, A, acc.shape[-1]))
         else:
             acc = acc.reshape(acc.shape[:-1] + (R, A))
-        return PolarData(signals=acc, polar=pol, counts=self._polar_counts.reshape(R, A), edges=pol.edges,
-                         probe_positions=self.probe_positions, time=np.arange(T) * self.trajectory.timestep, kxs=_as_tensor(kxs),
-                         kys=_as_tensor(kys), probe=self.base_probe, stem=None if signals is None else self._stem_data(signals),
-                         **self._layer_fields())
+        return self._tag_crop(PolarData(signals=acc, polar=pol, counts=self._polar_counts.reshape(R, A), edges=pol.edges,
+                                        probe_positions=self.probe_positions, time=np.arange(T) * self.trajectory.timestep,
+                                        kxs=_as_tensor(kxs), kys=_as_tensor(kys), probe=self.base_probe,
+                                        stem=None if signals is None else self._stem_data(signals), **self._layer_fields()))
 
     def _check_layers(self, n_slices, world):
         """the `layers` argument -> sorted unique slice indices with n_slices - 1 last (before any device work)"""
@@ -1334,10 +1387,14 @@ class MultisliceCalculator:
         elif self._prism is not None:
             # per frame: the potential, the S-matrix of its Bm beams, every probe synthesised from it into the frame's slot
             xy = np.asarray(self.probe_positions, dtype=np.float64).reshape(-1, 2)
+            src = self._source_engine()      # (Prism(f, crop=True): the beam engine; eng is the result engine on the cropped grid)
             for slot, frame_idx in enumerate(frames):
                 self._build(frame_idx, 1)
-                eng.smatrix_build()
-                eng.smatrix_probes(xy, slot)
+                src.smatrix_build()
+                if self._crop is not None:
+                    src.smatrix_probes_cropped(eng, xy, slot)
+                else:
+                    src.smatrix_probes(xy, slot)
                 self.frames_computed += 1
                 bar.update(1)
         else:
@@ -1362,6 +1419,7 @@ class MultisliceCalculator:
         wf = WFData(probe_positions=self.probe_positions, time=time_array, kxs=_as_tensor(kxs), kys=_as_tensor(kys),
                     layer=layer_array, wavefunction_data=data, probe=self.base_probe)
         # private riders: let TACAWData transform the device-resident copy without a host round trip
+        self._tag_crop(wf)
         wf._engine = eng
         wf._resident = resident
         wf._output = self._output
@@ -1371,12 +1429,14 @@ class MultisliceCalculator:
 
     def _k_axes(self):
         """kxs, kys of the stored spectra: reference calculators.py:218-219 (quirk Q2), cropped to the k-window (centred on
-        the DC pixel, index n//2 after the shift) and averaged over every detector bin"""
-        kxs = np.fft.fftshift(np.fft.fftfreq(self.nx, self.sampling)).astype(np.float32)
-        kys = np.fft.fftshift(np.fft.fftfreq(self.ny, self.sampling)).astype(np.float32)
+        the DC pixel, index n//2 after the shift) and averaged over every detector bin.  Of a cropped PRISM run: the axes of the
+        cropped grid, h / (n_c d) -- the full axes at prism.crop_index"""
+        nx, ny = self._result_grid()
+        kxs = np.fft.fftshift(np.fft.fftfreq(nx, self.sampling)).astype(np.float32)
+        kys = np.fft.fftshift(np.fft.fftfreq(ny, self.sampling)).astype(np.float32)
         if self._k_window is not None:
             wx, wy = self._k_window
-            x0, y0 = self.nx // 2 - wx // 2, self.ny // 2 - wy // 2
+            x0, y0 = nx // 2 - wx // 2, ny // 2 - wy // 2
             kxs, kys = kxs[x0:x0 + wx], kys[y0:y0 + wy]
         if self._k_bin is not None:
             kxs = kxs.reshape(-1, self._k_bin[0]).mean(axis=1).astype(np.float32)

@@ -242,6 +242,7 @@ struct msl_handle {
     DevBuf<float2> sm_S, sm_c;
     int sm_fx = 0, sm_fy = 0, sm_Bm = 0;
     bool sm_open = false, sm_built = false;
+    hipEvent_t sm_ev[2] = {nullptr, nullptr};      // msl_smatrix_probes_cropped, on the source: orders the two handles' streams, both ways
     DevBuf<double> d_abcd, d_lo, d_hi;
     bool have_kirkland = false, have_slices = false, have_probes = false, have_potential = false, have_exit = false;
     int frames_done = 0;
@@ -2607,6 +2608,7 @@ int msl_destroy(msl_handle* h) {
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     for (auto& s : h->ring) for (auto e : s.ev) (void)hipEventDestroy(e);
     for (auto& st : h->stage) { if (st.ev) (void)hipEventDestroy(st.ev); if (st.buf) (void)hipHostFree(st.buf); }
+    for (auto e : h->sm_ev) if (e) (void)hipEventDestroy(e);
     const hipStream_t stream = h->stream;
     delete h;                                               // the stream is idle: every DevBuf of the handle frees its memory
     if (stream) (void)hipStreamDestroy(stream);
@@ -3318,6 +3320,44 @@ static void launch_synth(msl_handle* h, bool vec, int win_x, int win_y) {
                             c.n_probes, h->sm_Bm, c.nx, c.ny, h->pitch, win_x, win_y, c.dx, c.dy, h->psi.p, h->psi0.p);
 }
 
+// c[p, b] of the n_probes positions in d_xy into sm_c (both hold that many), with the aberrations of the handle: one timed launch
+static int smatrix_coefficients(msl_handle* h, int n_probes) {
+    const msl_config& c = h->cfg;
+    ProbeAberrations ab{};
+    if (h->have_aberr) {
+        // (a, b) = C (cos, sin)(m phi) / ((n + 1) lambda), as msl_set_probes: the kernel's polynomial gives chi / (2 pi) in turns
+        static const int term_n[14] = {1, 1, 2, 2, 3, 3, 3, 4, 4, 4, 5, 5, 5, 5}, term_m[14] = {0, 2, 1, 3, 0, 2, 4, 1, 3, 5, 0, 2, 4, 6};
+        for (int k = 0; k < 14; ++k) {
+            const double w = h->aberr_polar[k][0] / ((term_n[k] + 1) * c.wavelength);
+            ab.a[k] = term_m[k] ? w * cos(term_m[k] * h->aberr_polar[k][1]) : w;
+            ab.b[k] = term_m[k] ? w * sin(term_m[k] * h->aberr_polar[k][1]) : 0.0;
+        }
+    }
+    const long long nc = (long long)n_probes * h->sm_Bm;
+    const float scale = (float)((double)h->sm_fx * h->sm_fy / ((double)c.nx * c.ny));
+    hipLaunchKernelGGL(smatrix_coeff_kernel, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, h->stream, h->sm_c.p, (const double*)h->d_xy.p,
+                       (const int2*)h->sm_beams.p, n_probes, h->sm_Bm, c.nx, c.ny, 1.0 / (c.nx * c.dx), 1.0 / (c.ny * c.dy), 1.0 / (c.nx * c.dx),
+                       1.0 / (c.ny * c.dy), c.wavelength, scale, (int)h->have_aberr, ab);
+    HIPCHK(h, hipGetLastError());
+    return mark_launch(h, K_OTHER);
+}
+
+// fftshift(fft2(.)) of the n_probes waves in the probe buffer into the frame slot: the row transform along y, then the exit
+// epilogue -- the sequence of the layer tap
+static int smatrix_spectra(msl_handle* h, int n_probes, int slot) {
+    int rc;
+    if (h->Ry) {
+        RowJob r = row_job(h, h->psi0, n_probes, h->pitch);
+        r.do_fft = true;
+        rc = launch_row_fast(h, r, K_OTHER);
+    } else {
+        LineArgs r = row_args(h, h->psi0, h->psi0, n_probes, h->pitch);
+        r.fft1 = +1;
+        rc = launch_lines(h, h->plan_y, r, K_OTHER);
+    }
+    return rc ? rc : epilogue_x_pass(h, slot, 1, h->psi0);
+}
+
 int msl_smatrix_probes(msl_handle* h, const double* xy, int32_t n_probes, int32_t slot) {
     if (!h || !xy) return fail(h, MSL_ERR_INVALID, "msl_smatrix_probes: null argument");
     const msl_config& c = h->cfg;
@@ -3335,23 +3375,7 @@ int msl_smatrix_probes(msl_handle* h, const double* xy, int32_t n_probes, int32_
     EventPair timer;
     if (c.launch_timing && (rc = timer.begin(h))) return rc;
     if ((rc = begin_timed(h, 8))) return rc;
-    ProbeAberrations ab{};
-    if (h->have_aberr) {
-        // (a, b) = C (cos, sin)(m phi) / ((n + 1) lambda), as msl_set_probes: the kernel's polynomial gives chi / (2 pi) in turns
-        static const int term_n[14] = {1, 1, 2, 2, 3, 3, 3, 4, 4, 4, 5, 5, 5, 5}, term_m[14] = {0, 2, 1, 3, 0, 2, 4, 1, 3, 5, 0, 2, 4, 6};
-        for (int k = 0; k < 14; ++k) {
-            const double w = h->aberr_polar[k][0] / ((term_n[k] + 1) * c.wavelength);
-            ab.a[k] = term_m[k] ? w * cos(term_m[k] * h->aberr_polar[k][1]) : w;
-            ab.b[k] = term_m[k] ? w * sin(term_m[k] * h->aberr_polar[k][1]) : 0.0;
-        }
-    }
-    const long long nc = (long long)n_probes * h->sm_Bm;
-    const float scale = (float)((double)h->sm_fx * h->sm_fy / ((double)c.nx * c.ny));
-    hipLaunchKernelGGL(smatrix_coeff_kernel, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, h->stream, h->sm_c.p, (const double*)h->d_xy.p,
-                       (const int2*)h->sm_beams.p, n_probes, h->sm_Bm, c.nx, c.ny, 1.0 / (c.nx * c.dx), 1.0 / (c.ny * c.dy), 1.0 / (c.nx * c.dx),
-                       1.0 / (c.ny * c.dy), c.wavelength, scale, (int)h->have_aberr, ab);
-    HIPCHK(h, hipGetLastError());
-    if ((rc = mark_launch(h, K_OTHER))) return rc;
+    if ((rc = smatrix_coefficients(h, n_probes))) return rc;
     // the synthesised waves go to the work buffer (MSL_BUF_EXIT) and to the probe buffer, which the spectrum transform consumes
     h->have_probes = false;
     const bool vec = c.ny % 2 == 0 && h->pitch % 2 == 0;
@@ -3360,21 +3384,78 @@ int msl_smatrix_probes(msl_handle* h, const double* xy, int32_t n_probes, int32_
     HIPCHK(h, hipGetLastError());
     if ((rc = mark_launch(h, K_OTHER))) return rc;
     h->have_exit = true;
-    // fftshift(fft2(.)) into the frame slot: the row transform along y, then the exit epilogue -- the sequence of the layer tap
-    if (h->Ry) {
-        RowJob r = row_job(h, h->psi0, n_probes, h->pitch);
-        r.do_fft = true;
-        rc = launch_row_fast(h, r, K_OTHER);
-    } else {
-        LineArgs r = row_args(h, h->psi0, h->psi0, n_probes, h->pitch);
-        r.fft1 = +1;
-        rc = launch_lines(h, h->plan_y, r, K_OTHER);
-    }
-    if (rc || (rc = epilogue_x_pass(h, slot, 1, h->psi0))) return rc;
+    if ((rc = smatrix_spectra(h, n_probes, slot))) return rc;
     h->cur = nullptr;
     const uint64_t img = (uint64_t)c.nx * c.ny * 8ull;
     h->ctr.algorithmic_bytes += (uint64_t)h->sm_Bm * img * (uint64_t)((n_probes + 7) / 8) + (uint64_t)n_probes * (img * 4 + (uint64_t)h->wpix * 8ull);
     return c.launch_timing ? timer.end(h, &h->ctr.ms_propagate) : MSL_OK;
+}
+
+extern "C++" template <int G>
+static void launch_synth_crop(msl_handle* src, msl_handle* dst, bool vec, int n_probes) {
+    const msl_config& c = src->cfg;
+    const int lanes_y = vec ? c.ny / 2 : c.ny;
+    const dim3 grid((unsigned)((n_probes + G - 1) / G), (unsigned)((c.nx + SM_TILE_ROWS - 1) / SM_TILE_ROWS), (unsigned)((lanes_y + SM_TILE_LANES - 1) / SM_TILE_LANES));
+    if (vec) hipLaunchKernelGGL((smatrix_synth_crop_kernel<G, true>), grid, dim3(256), 0, src->stream, (const float2*)src->sm_S.p, (const float2*)src->sm_c.p,
+                                (const double*)src->d_xy.p, n_probes, src->sm_Bm, c.nx, c.ny, dst->pitch, dst->cfg.nx, dst->cfg.ny, c.dx, c.dy, dst->psi.p, dst->psi0.p);
+    else hipLaunchKernelGGL((smatrix_synth_crop_kernel<G, false>), grid, dim3(256), 0, src->stream, (const float2*)src->sm_S.p, (const float2*)src->sm_c.p,
+                            (const double*)src->d_xy.p, n_probes, src->sm_Bm, c.nx, c.ny, dst->pitch, dst->cfg.nx, dst->cfg.ny, c.dx, c.dy, dst->psi.p, dst->psi0.p);
+}
+
+int msl_smatrix_probes_cropped(msl_handle* src, msl_handle* dst, const double* xy, int32_t n_probes, int32_t slot) {
+    const char* me = "msl_smatrix_probes_cropped";
+    if (!src || !dst || !xy) return fail(src ? src : dst, MSL_ERR_INVALID, "%s: null argument", me);
+    const msl_config& c = src->cfg;
+    const msl_config& d = dst->cfg;
+    if (src == dst) return fail(src, MSL_ERR_INVALID, "%s: the source and the result handle are the same", me);
+    if (c.device != d.device) return fail(src, MSL_ERR_INVALID, "%s: the handles are on devices %d and %d", me, c.device, d.device);
+    if (!src->sm_built) return fail(src, MSL_ERR_STATE, "%s: no S-matrix on the source (msl_smatrix_begin, msl_smatrix_build)", me);
+    if (d.nx * src->sm_fx != c.nx || d.ny * src->sm_fy != c.ny)
+        return fail(src, MSL_ERR_INVALID, "%s: the result grid %d x %d is not the source's %d x %d divided by its interpolation (%d, %d)", me, d.nx, d.ny,
+                    c.nx, c.ny, src->sm_fx, src->sm_fy);
+    auto differ = [](double a, double b) { return !(fabs(a - b) <= 1e-12 * fabs(a)); };
+    if (differ(c.dx, d.dx) || differ(c.dy, d.dy) || differ(c.wavelength, d.wavelength))
+        return fail(src, MSL_ERR_INVALID, "%s: the handles differ in pixel size or wavelength", me);
+    if (n_probes != d.n_probes) return fail(src, MSL_ERR_INVALID, "%s: %d probes, the result handle has %d", me, n_probes, d.n_probes);
+    if (!dst->wf) return fail(src, MSL_ERR_STATE, "%s: result handle created with n_frames == 0", me);
+    if (slot < 0 || slot >= d.n_frames) return fail(src, MSL_ERR_INVALID, "%s: slot %d out of range [0,%d)", me, slot, d.n_frames);
+    for (int k = 0; k < 2 * n_probes; ++k)
+        if (!std::isfinite(xy[k])) return fail(src, MSL_ERR_INVALID, "%s: position value %d is not finite", me, k);
+    HIPCHK(src, hipSetDevice(c.device));
+    int rc;
+    // the source's probe count only sets the chunk of msl_smatrix_build: c and the positions are held for the result's count
+    if ((rc = src->sm_c.reserve(src, (size_t)src->sm_Bm * n_probes)) || (rc = src->d_xy.reserve(src, (size_t)2 * n_probes))) return rc;
+    for (auto& e : src->sm_ev)
+        if (!e) HIPCHK(src, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    HIPCHK(src, hipMemcpyAsync(src->d_xy, xy, 2 * sizeof(double) * n_probes, hipMemcpyHostToDevice, src->stream));
+    HIPCHK(src, hipStreamSynchronize(src->stream));         // xy is the caller's memory: read before the call returns
+    EventPair timer;
+    if (d.launch_timing && (rc = timer.begin(dst))) return rc;
+    if ((rc = begin_timed(src, 4)) || (rc = begin_timed(dst, 4))) return rc;
+    if ((rc = smatrix_coefficients(src, n_probes))) return rc;
+    // the result handle's earlier work (the reductions of its last batch read the frame slots; its transform the probe buffer) is
+    // done before the synthesis, on the source's stream, overwrites its exit and probe buffers
+    HIPCHK(src, hipEventRecord(src->sm_ev[0], dst->stream));
+    HIPCHK(src, hipStreamWaitEvent(src->stream, src->sm_ev[0], 0));
+    dst->have_probes = false;
+    // VEC: ny, the cropped ny and the result's work pitch even (the S-matrix is dense: its rows are ny long)
+    const bool vec = c.ny % 2 == 0 && d.ny % 2 == 0 && dst->pitch % 2 == 0;
+    if (n_probes > 8) launch_synth_crop<16>(src, dst, vec, n_probes);
+    else launch_synth_crop<8>(src, dst, vec, n_probes);
+    HIPCHK(src, hipGetLastError());
+    if ((rc = mark_launch(src, K_OTHER))) return rc;
+    src->cur = nullptr;
+    // and the synthesis is done before the result handle's transform reads the probe buffer
+    HIPCHK(src, hipEventRecord(src->sm_ev[1], src->stream));
+    HIPCHK(src, hipStreamWaitEvent(dst->stream, src->sm_ev[1], 0));
+    dst->have_exit = true;
+    if ((rc = smatrix_spectra(dst, n_probes, slot))) return rc;
+    dst->cur = nullptr;
+    // S over the windows once per probe group, the folded waves written twice; the transform reads and writes the copy twice and
+    // writes the spectra -- all on the cropped image
+    const uint64_t img = (uint64_t)d.nx * d.ny * 8ull;
+    dst->ctr.algorithmic_bytes += (uint64_t)src->sm_Bm * img * (uint64_t)((n_probes + 7) / 8) + (uint64_t)n_probes * (img * 4 + (uint64_t)dst->wpix * 8ull);
+    return d.launch_timing ? timer.end(dst, &dst->ctr.ms_propagate) : MSL_OK;
 }
 
 int msl_smatrix_end(msl_handle* h) {

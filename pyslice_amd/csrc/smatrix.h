@@ -194,4 +194,107 @@ __global__ void __launch_bounds__(256) smatrix_synth_kernel(const float2* __rest
     }
 }
 
+// The cropped synthesis (msl_smatrix_probes_cropped): the window of probe p is wx = nx/fx consecutive pixels modulo nx and wx divides
+// nx, so i -> i mod wx maps it one-to-one onto [0, wx) (likewise y).  The folded wave psi_c[i mod wx, j mod wy] = psi_p[i, j], (i, j)
+// inside W_p, has fft2(psi_c)[m, n] = fft2(psi_p)[fx m, fy n] exactly, with no phase ramp: exp(-2 pi i m (i mod wx) / wx) =
+// exp(-2 pi i (fx m) i / nx).  Tiling, probe groups, the LDS chunks of c, the beam order and the membership test are those of
+// smatrix_synth_kernel, over the same absolute pixels; the value of probe p at absolute pixel (row, col) is stored at
+// ((p wx + row mod wx) pitch_c + col mod wy) of the two outputs, (P, wx, pitch_c).  Nothing is stored for a pixel outside the window,
+// and a tile no window of the group touches leaves before any load or store: every cropped pixel is written exactly once (no zero
+// fill), pad pixels are neither read nor written.  VEC (16-byte accesses) needs ny, wy and pitch_c even: col even then implies
+// col mod wy even, and the pair stays adjacent and aligned; a pair the window edge cuts stores its inside pixel alone (the other
+// slot belongs to the pixel wy columns away).  64-bit indexing; no atomics: repeated calls are bitwise equal.
+// S: (Bm, nx, ny) dense; c: (P, Bm); out / out2: (P, win_x, pitch_c).  grid = (ceil(P / G), ceil(nx / 8), ceil(ny / PXL / 32))
+template <int G, bool VEC>
+__global__ void __launch_bounds__(256) smatrix_synth_crop_kernel(const float2* __restrict__ S, const float2* __restrict__ c, const double* __restrict__ xy,
+                                                                 int P, int Bm, int nx, int ny, int pitch_c, int win_x, int win_y, double dx, double dy,
+                                                                 float2* __restrict__ out, float2* __restrict__ out2) {
+    constexpr int PXL = VEC ? 2 : 1;
+    __shared__ float2 s_c[SM_BEAM_CHUNK][G];
+    __shared__ int s_cx[G], s_cy[G];
+    const int tid = threadIdx.x;
+    const int p0 = blockIdx.x * G;
+    const int row = blockIdx.y * SM_TILE_ROWS + tid / SM_TILE_LANES;
+    const int col = (blockIdx.z * SM_TILE_LANES + tid % SM_TILE_LANES) * PXL;
+    const bool valid = row < nx && col < ny;            // (VEC: ny is even, the pair is inside with its first pixel)
+    if (tid < G) {
+        const int p = p0 + tid;
+        s_cx[tid] = p < P ? smatrix_window_centre(nx, dx, xy[2 * p]) : -1;
+        s_cy[tid] = p < P ? smatrix_window_centre(ny, dy, xy[2 * p + 1]) : -1;
+    }
+    __syncthreads();
+    unsigned m0 = 0, m1 = 0;                            // bit g: the lane's first / second pixel is inside the window of probe p0 + g
+    if (valid) {
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+            if (s_cx[g] < 0) continue;
+            const bool in_x = smatrix_inside(row, s_cx[g], win_x, nx);
+            if (in_x && smatrix_inside(col, s_cy[g], win_y, ny)) m0 |= 1u << g;
+            if (VEC && in_x && smatrix_inside(col + 1, s_cy[g], win_y, ny)) m1 |= 1u << g;
+        }
+    }
+    const bool active = (m0 | m1) != 0;
+    if (__syncthreads_or(active) == 0) return;          // (uniform over the workgroup) no window of the group touches the tile
+    float2 a0[G], a1[G];
+#pragma unroll
+    for (int g = 0; g < G; ++g) { a0[g] = make_float2(0.f, 0.f); a1[g] = make_float2(0.f, 0.f); }
+    const float2* s_px = S + (long long)row * ny + col;
+    const long long beam_stride = (long long)nx * ny;
+    for (int bc0 = 0; bc0 < Bm; bc0 += SM_BEAM_CHUNK) {
+        __syncthreads();
+        for (int idx = tid; idx < SM_BEAM_CHUNK * G; idx += 256) {
+            const int g = idx / SM_BEAM_CHUNK, bb = idx - g * SM_BEAM_CHUNK;
+            const int p = p0 + g, b = bc0 + bb;
+            s_c[bb][g] = (p < P && b < Bm) ? c[(long long)p * Bm + b] : make_float2(0.f, 0.f);
+        }
+        __syncthreads();
+        if (!active) continue;
+        const int nb = Bm - bc0 < SM_BEAM_CHUNK ? Bm - bc0 : SM_BEAM_CHUNK;
+#pragma unroll 4
+        for (int bb = 0; bb < nb; ++bb) {
+            const float2* sp = s_px + (long long)(bc0 + bb) * beam_stride;
+            float2 v0, v1 = make_float2(0.f, 0.f);
+            if constexpr (VEC) {
+                const float4 v = *reinterpret_cast<const float4*>(sp);
+                v0 = make_float2(v.x, v.y); v1 = make_float2(v.z, v.w);
+            } else {
+                v0 = *sp;
+            }
+#pragma unroll
+            for (int g = 0; g < G; ++g) {
+                const float2 w = s_c[bb][g];
+                a0[g].x = fmaf(w.x, v0.x, a0[g].x); a0[g].x = fmaf(-w.y, v0.y, a0[g].x);
+                a0[g].y = fmaf(w.x, v0.y, a0[g].y); a0[g].y = fmaf(w.y, v0.x, a0[g].y);
+                if constexpr (VEC) {
+                    a1[g].x = fmaf(w.x, v1.x, a1[g].x); a1[g].x = fmaf(-w.y, v1.y, a1[g].x);
+                    a1[g].y = fmaf(w.x, v1.y, a1[g].y); a1[g].y = fmaf(w.y, v1.x, a1[g].y);
+                }
+            }
+        }
+    }
+    if (!active) return;
+    // (row mod wx, col mod wy) of the lane's first pixel; VEC: col and wy even, so the second pixel is the next one of the same row
+    const long long o_lane = (long long)(row % win_x) * pitch_c + col % win_y;
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+        const bool i0 = (m0 >> g) & 1u, i1 = (m1 >> g) & 1u;
+        if (!(i0 || i1)) continue;                      // (a probe past P has no bit)
+        const long long o = (long long)(p0 + g) * win_x * pitch_c + o_lane;
+        if constexpr (VEC) {
+            if (i0 && i1) {
+                const float4 v = make_float4(a0[g].x, a0[g].y, a1[g].x, a1[g].y);
+                *reinterpret_cast<float4*>(out + o) = v;
+                *reinterpret_cast<float4*>(out2 + o) = v;
+            } else if (i0) {
+                out[o] = a0[g]; out2[o] = a0[g];
+            } else {
+                out[o + 1] = a1[g]; out2[o + 1] = a1[g];
+            }
+        } else {
+            out[o] = a0[g];
+            out2[o] = a0[g];
+        }
+    }
+}
+
 }  // namespace msl

@@ -15,6 +15,17 @@ elsewhere.  At interpolation (1, 1) W = 1 and psi_p IS the multislice exit wave 
 physics (the probe tails outside the window are dropped and the beams are thinned), not the arithmetic.  The device builds S
 with one slice loop per beam and frame (msl_smatrix_build) and every probe batch as one skinny complex GEMM
 (msl_smatrix_probes); `prism_waves` below is the float64 NumPy statement of the same formula, which the tests compare against.
+
+Prism(f, crop=True) synthesises the probes on PRISM's own (nx/fx) x (ny/fy) grid (msl_smatrix_probes_cropped).  The window of
+probe p along x is wx = nx/fx consecutive pixels modulo nx and wx divides nx, so i -> i mod wx maps it one-to-one onto [0, wx).
+Fold the windowed wave that way, psi_c[i mod wx, j mod wy] = psi_p[i, j] for (i, j) inside W_p (`prism_waves_cropped`); then
+
+    fft2(psi_c)[m, n] = fft2(psi_p)[fx m, fy n]
+
+exactly, with no phase ramp, because exp(-2 pi i m (i mod wx) / wx) = exp(-2 pi i (fx m) i / nx).  In stored (fftshifted) order
+the cropped pixel (a, b) is the full pixel (nx//2 + fx (a - wx//2), ny//2 + fy (b - wy//2)) (`crop_index`): the cropped spectrum
+is the full-grid one at every (fx, fy)-th pixel, value for value.  Nothing is rescaled: a sum over a region of the cropped
+pattern is about 1 / (fx fy) of the uncropped run's sum over the same region, each cropped pixel standing for fx fy full pixels.
 """
 from __future__ import annotations
 
@@ -23,9 +34,12 @@ import numpy as np
 
 class Prism:
     """MultisliceCalculator(prism=Prism(interpolation)): interpolation = f or (fx, fy), positive integers that divide the grid
-    (checked in setup()).  Prism(1) reproduces the multislice run from Bm slice loops per frame instead of one per probe."""
+    (checked in setup()).  Prism(1) reproduces the multislice run from Bm slice loops per frame instead of one per probe.
+    crop=True: every probe is synthesised, transformed and reduced on the cropped (nx / fx) x (ny / fy) grid -- the results are
+    the uncropped run's spectra at the pixels crop_index names, not rescaled, on that grid's own k axes (.prism_crop = (fx, fy));
+    at interpolation (1, 1) there is nothing to crop and the run is the one of crop=False."""
 
-    def __init__(self, interpolation=1):
+    def __init__(self, interpolation=1, crop=False):
         f = interpolation
         if isinstance(f, (bool, np.bool_)):
             raise ValueError(f"Prism: interpolation must be a positive integer or a pair of them, got {f!r}")
@@ -37,10 +51,18 @@ class Prism:
             raise ValueError(f"Prism: interpolation must be a positive integer or a pair of them, got {interpolation!r}") from None
         if len(f) != 2 or any(isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or int(v) < 1 for v in f):
             raise ValueError(f"Prism: interpolation must be a positive integer or a pair of them, got {interpolation!r}")
+        if not isinstance(crop, (bool, np.bool_)):
+            raise ValueError(f"Prism: crop must be True or False, got {crop!r}")
         self.interpolation = (int(f[0]), int(f[1]))
+        self.crop = bool(crop)
+
+    @property
+    def cropped(self):
+        """does a run with this object use the cropped grid?  (crop=True at interpolation (1, 1) runs as crop=False)"""
+        return self.crop and self.interpolation != (1, 1)
 
     def __repr__(self):
-        return f"Prism(interpolation={self.interpolation})"
+        return f"Prism(interpolation={self.interpolation}, crop={self.crop})"
 
 
 def signed_freq(n):
@@ -111,4 +133,31 @@ def prism_waves(S, hxhy, xy, dx, dy, f=(1, 1), wavelength=None, aberrations=None
     out = np.tensordot(c, S.astype(np.complex128, copy=False), axes=(1, 0))
     for p, (px, py) in enumerate(xy):
         out[p] *= window_mask(nx, dx, px, int(f[0]))[:, None] & window_mask(ny, dy, py, int(f[1]))[None, :]
+    return out
+
+
+def crop_index(n, f):
+    """(n // f,) int64: the stored (fftshifted) full-grid index of every stored pixel of the cropped axis, n//2 + f (a - (n//f)//2)
+    -- the DC pixel maps to the DC pixel, and every index exists for odd and even lengths alike"""
+    n, f = int(n), int(f)
+    if f < 1 or n % f:
+        raise ValueError(f"crop_index: the interpolation {f} must be positive and divide the axis of {n} pixels")
+    w = n // f
+    return n // 2 + f * (np.arange(w, dtype=np.int64) - w // 2)
+
+
+def prism_waves_cropped(S, hxhy, xy, dx, dy, f=(1, 1), wavelength=None, aberrations=None):
+    """(P, nx // fx, ny // fy) complex128: prism_waves folded onto the cropped grid, psi_c[i mod wx, j mod wy] = psi_p[i, j] for
+    (i, j) inside the window of probe p (one-to-one: the window is wx consecutive pixels modulo nx and wx divides nx) -- the
+    definition of what msl_smatrix_probes_cropped computes, in float64.  fft2(psi_c) == fft2(psi_p)[::fx, ::fy]."""
+    full = prism_waves(S, hxhy, xy, dx, dy, f, wavelength, aberrations)
+    P, nx, ny = full.shape
+    fx, fy = int(f[0]), int(f[1])
+    wx, wy = nx // fx, ny // fy
+    xy = np.asarray(xy, dtype=np.float64).reshape(-1, 2)
+    out = np.zeros((P, wx, wy), dtype=np.complex128)
+    for p, (px, py) in enumerate(xy):
+        ix = np.nonzero(window_mask(nx, dx, px, fx))[0]
+        iy = np.nonzero(window_mask(ny, dy, py, fy))[0]
+        out[p][np.ix_(ix % wx, iy % wy)] = full[p][np.ix_(ix, iy)]
     return out
