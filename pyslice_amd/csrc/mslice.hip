@@ -185,17 +185,16 @@ struct msl_handle {
     DevBuf<float> V;
     DevBuf<float> intensity;
     DevBuf<float2> pxt, pyt;    // exp(-i pi lambda dz kx^2)/nx
-    // specimen tilt (msl_set_tilt): tan(theta) along x and y; once set, every propagator table is written on the device
-    // (fill_propagator_device) and tilt_work holds the float64 tables of its convolution sums.  Never set: the host tables, as ever
-    double tilt_tan[2] = {0.0, 0.0};
-    bool tilt_set = false;
-    DevBuf<double2> tilt_work;
-    // band limit (msl_set_bandlimit): the largest kept |frequency index| per axis (-1: none).  While bl_on every
-    // propagator table is written on the device and masked (fill_propagator_device), and every transmission stack is low-passed after
-    // its build (bandlimit_built) with the weight vectors bl_mx, bl_my = mask / n (bandlimit.h)
-    int bl_cut[2] = {-1, -1};
-    bool bl_on = false;
-    DevBuf<float2> bl_mx, bl_my;
+    // the settings that, with the beam in cfg, decide the propagator tables, the loop mode and the low-pass of the stacks (DESIGN.md
+    // section 4.25) -- one value: a setter copies it, changes it, refreshes, and on a refusal puts the copy back
+    struct Settings {
+        double tilt_tan[2] = {0.0, 0.0};   // specimen tilt (msl_set_tilt): tan(theta) along x and y
+        bool tilt_set = false;             // msl_set_tilt has been called (never cleared: (0, 0) is a tilt like any other)
+        int bl_cut[2] = {-1, -1};          // band limit (msl_set_bandlimit): the largest kept |frequency index| per axis
+        bool bl_on = false;                // (-1 and false: none)
+    } set;
+    DevBuf<double2> tilt_work;     // fill_propagator_device: the float64 tables of its convolution sums
+    DevBuf<float2> bl_mx, bl_my;   // while set.bl_on: the weight vectors mask / n of bandlimit_lowpass (bandlimit.h)
     // the result, (L, P, T_local, wpitch) with L = 1 + the layers of a thickness series (msl_set_layers): `layers` owns it for every
     // L, wf is a view of its last block, the exit waves.  layer_block: result block of every slice (-1: not a layer); tap: the
     // natural-order image set the layer tap transforms (FB * P images, psi's layout); tap_cx / tap_cy: the unscaled conjugate
@@ -1442,140 +1441,6 @@ int slice_loop_tds(msl_handle* h, int fused_slot, int groups, int first_group) {
 int conv_len(const msl_handle::OpDir& o) { return o.base == AX_CONV ? o.R * o.R : o.base == AX_CONV2K ? 2048 : o.base == AX_CONV4K ? 4096 : 0; }
 size_t conv_filter_entries(const msl_handle::OpDir& o) { return o.base == AX_CONV4K ? 2052 : (size_t)conv_len(o) / 2 + 2; }
 
-// Filter of that convolution for n points of spacing d: a = ifft_n(P) (float64), wrapped to the cyclic length M, filter = FFT_M(a) / M,
-// stored as its first half + 1 (NH + 2 entries, rowTB / rowTB2), or for M = 4096 in the split order of rowTC2_pass_kernel (even
-// entries 0..1024, odd entries from 1026)
-int fill_conv_filter(msl_handle* h, const msl_handle::OpDir& o, double d) {
-    const msl_config& c = h->cfg;
-    const int n = o.n, M = conv_len(o), NH = M / 2;
-    std::vector<double> pr(n), pi(n), er(n), ei(n), qr(M, 0.0), qi(M, 0.0);
-    for (int m = 0; m < n; ++m) {
-        const int f = (m < (n + 1) / 2) ? m : m - n;
-        const double k = f * (1.0 / (n * d));
-        const double ph = -M_PI * c.wavelength * c.dz * k * k;
-        pr[m] = cos(ph); pi[m] = sin(ph);
-        const double a = 2.0 * M_PI * (double)m / (double)n;
-        er[m] = cos(a); ei[m] = sin(a);
-    }
-    for (int j = 0; j < n; ++j) {                      // a[j] = (1/n) sum_m P[m] e^{+2 pi i m j / n}
-        double sr = 0.0, si = 0.0;
-        long long t = 0;
-        for (int m = 0; m < n; ++m) {
-            sr += pr[m] * er[t] - pi[m] * ei[t];
-            si += pr[m] * ei[t] + pi[m] * er[t];
-            t += j; if (t >= n) t -= n;
-        }
-        sr /= n; si /= n;
-        qr[j] = sr; qi[j] = si;                         // lag +j
-        if (j) { qr[M - n + j] = sr; qi[M - n + j] = si; }   // lag j - n  (M - (n - j))
-    }
-    host_fft_pow2(qr, qi);
-    std::vector<float2> qf(conv_filter_entries(o), make_float2(0.f, 0.f));
-    if (o.base == AX_CONV4K) {
-        for (int k = 0; k <= 1024; ++k) qf[k] = make_float2((float)(qr[2 * k] / M), (float)(qi[2 * k] / M));
-        for (int k = 0; k < 1024; ++k) qf[1026 + k] = make_float2((float)(qr[2 * k + 1] / M), (float)(qi[2 * k + 1] / M));
-    } else {
-        for (int j = 0; j <= NH; ++j) qf[j] = make_float2((float)(qr[j] / M), (float)(qi[j] / M));
-    }
-    return copy_table(h, o.qf, qf);
-}
-
-// Fresnel propagator, separable: P[kx,ky] = exp(-i pi lambda dz kx^2) * exp(-i pi lambda dz ky^2)
-// (multislice.py:273-275), with the 1/(nx ny) of the inverse FFT folded in.
-int fill_propagator(msl_handle* h) {
-    const msl_config& c = h->cfg;
-    auto fill = [&](float2* dst, int n, double d) -> int {
-        std::vector<float2> v(n);
-        for (int m = 0; m < n; ++m) {
-            int f = (m < (n + 1) / 2) ? m : m - n;
-            double k = f * (1.0 / (n * d));
-            double ph = -M_PI * c.wavelength * c.dz * k * k;
-            v[m] = make_float2((float)(cos(ph) / n), (float)(sin(ph) / n));
-        }
-        return copy_table(h, dst, v);
-    };
-    int rc = fill(h->pxt, c.nx, c.dx);
-    if (rc) return rc;
-    if ((rc = fill(h->pyt, c.ny, c.dy))) return rc;
-    // the layer tap's conj(P), unscaled: exp(+i pi lambda dz k^2)
-    auto fill_conj = [&](float2* dst, int n, double d) -> int {
-        std::vector<float2> v(n);
-        for (int m = 0; m < n; ++m) {
-            const int f = (m < (n + 1) / 2) ? m : m - n;
-            const double k = f * (1.0 / (n * d));
-            const double ph = M_PI * c.wavelength * c.dz * k * k;
-            v[m] = make_float2((float)cos(ph), (float)sin(ph));
-        }
-        return copy_table(h, dst, v);
-    };
-    if ((rc = fill_conj(h->tap_cx, c.nx, c.dx))) return rc;
-    if ((rc = fill_conj(h->tap_cy, c.ny, c.dy))) return rc;
-    // split-order copies for the 2R^2 kernels: entry [b*R^2 + k] = P[2k + b]
-    auto fill_split = [&](float2* dst, int n, double d) -> int {
-        std::vector<float2> v(n);
-        for (int b = 0; b < 2; ++b)
-            for (int k = 0; k < n / 2; ++k) {
-                const int m = 2 * k + b;
-                const int f = (m < (n + 1) / 2) ? m : m - n;
-                const double kk = f * (1.0 / (n * d));
-                const double ph = -M_PI * c.wavelength * c.dz * kk * kk;
-                v[b * (n / 2) + k] = make_float2((float)(cos(ph) / n), (float)(sin(ph) / n));
-            }
-        return copy_table(h, dst, v);
-    };
-    for (const msl_handle::OpDir* o : {&h->opx, &h->opy}) {
-        const double d = (o == &h->opx) ? c.dx : c.dy;
-        if (o->base == AX_TWO && (rc = fill_split(o->ptab, o->n, d))) return rc;
-        // convolution kinds: filter of the zero-padded cyclic convolution that IS the propagation along the axis
-        if (conv_len(*o) && (rc = fill_conv_filter(h, *o, d))) return rc;
-    }
-    return MSL_OK;
-}
-
-// The same tables with the tilt factor exp(-2 pi i dz tan(theta) k), written by the kernels of propagator.h on the handle's stream:
-// no host table, no copy and no wait, so a change of tilt is ordered behind the passes of the tilt before it.
-int fill_propagator_device(msl_handle* h) {
-    const msl_config& c = h->cfg;
-    size_t work = 0;                                        // float64 entries of the convolution sums: P, E (n each), q, W (M each)
-    for (const msl_handle::OpDir* o : {&h->opx, &h->opy})
-        if (conv_len(*o)) work = std::max(work, 2 * (size_t)o->n + 2 * (size_t)conv_len(*o));
-    int rc = h->tilt_work.reserve(h, work);
-    if (rc) return rc;
-    for (int axis = 0; axis < 2; ++axis) {
-        const msl_handle::OpDir& o = axis ? h->opy : h->opx;
-        const int n = axis ? c.ny : c.nx, M = conv_len(o);
-        const double d = axis ? c.dy : c.dx;
-        // the half-spectrum layout holds the filter of an even table only, and no pass reads qf under a tilted axis (set_loop_mode has
-        // the two-pass loop on, a mixed axis reads the plain table): the filter is written at a zero tangent, which every way back to
-        // the convolution pass goes through (msl_set_tilt with 0 along the axis)
-        const bool filter = M && h->tilt_tan[axis] == 0.0;
-        double2* Pd = filter ? (double2*)h->tilt_work : nullptr;
-        double2* Ed = filter ? Pd + n : nullptr;
-        double2* q = filter ? Ed + n : nullptr;
-        double2* Wd = filter ? q + M : nullptr;
-        float2* split = o.base == AX_TWO ? (float2*)o.ptab : nullptr;
-        const int lanes = filter ? std::max(n, M) : n;
-        hipLaunchKernelGGL(propagator_tables_kernel, dim3((unsigned)((lanes + PROP_BLOCK - 1) / PROP_BLOCK)), dim3(PROP_BLOCK), 0, h->stream,
-                           n, M, 1.0 / (n * d), 0.5 * c.wavelength * c.dz, c.dz * h->tilt_tan[axis], axis ? h->pyt : h->pxt, split,
-                           axis ? h->tap_cy : h->tap_cx, Pd, Ed, Wd);
-        HIPCHK(h, hipGetLastError());
-        if (h->bl_on) {                                     // the band limit: before the filter sums, which then see the masked table
-            hipLaunchKernelGGL(propagator_bandlimit_kernel, dim3((unsigned)((n + PROP_BLOCK - 1) / PROP_BLOCK)), dim3(PROP_BLOCK), 0, h->stream,
-                               n, h->bl_cut[axis], axis ? h->pyt : h->pxt, split, axis ? h->tap_cy : h->tap_cx, Pd);
-            HIPCHK(h, hipGetLastError());
-        }
-        if (!filter) continue;
-        const int gap = M - 2 * n + 1, entries = (int)conv_filter_entries(o);
-        hipLaunchKernelGGL(conv_lag_kernel, dim3((unsigned)(n + (gap + PROP_BLOCK - 1) / PROP_BLOCK)), dim3(PROP_BLOCK), 0, h->stream, n, M,
-                           Pd, Ed, q);
-        HIPCHK(h, hipGetLastError());
-        hipLaunchKernelGGL(conv_filter_kernel, dim3((unsigned)entries), dim3(PROP_BLOCK), 0, h->stream, n, M, entries,
-                           o.base == AX_CONV4K ? 1 : 0, q, Wd, (float2*)o.qf);
-        HIPCHK(h, hipGetLastError());
-    }
-    return MSL_OK;
-}
-
 // ---- axis planning ----------------------------------------------------------------------------------
 // The kind of the slice loop's pass along an axis of n points (n_other lines per image; Rfast = the four-step radix of the axis or 0;
 // plan_M = the length of its generic plan, > n for a Bluestein plan).  want = false (two-pass loop asked for): no one-pass kind.
@@ -2160,16 +2025,357 @@ int bandlimit_lowpass(msl_handle* h, int slot, int count) {
     return launch_lines(h, h->plan_x, k, K_OTHER);
 }
 
-// The same for stacks a build has left in the order of the slice loop: the slices the one-pass loop keeps transposed come back to
-// natural order first and are transposed again afterwards (both are no-ops on the two-pass loop), so the stack is limited once, in one
-// orientation, whatever the loop is.
-int bandlimit_built(msl_handle* h, int slot, int count) {
+// ==== handle settings: what each setter re-derives ============================
+// One function per derived state -- refresh_propagator, set_loop_mode(allowed_onepass), remake_transmission / drop_potential,
+// drop_smatrix_result -- and the five setters, each of which changes its setting and calls those.
+
+// ---- propagator tables ----
+// float64 cos and sin of sign * pi lambda dz k^2 at the n frequencies of an axis of spacing d, in FFT order
+void host_phase_table(const msl_config& c, int n, double d, double sign, std::vector<double>& re, std::vector<double>& im) {
+    re.resize(n); im.resize(n);
+    for (int m = 0; m < n; ++m) {
+        const int f = (m < (n + 1) / 2) ? m : m - n;
+        const double k = f * (1.0 / (n * d));
+        const double ph = sign * M_PI * c.wavelength * c.dz * k * k;
+        re[m] = cos(ph); im[m] = sin(ph);
+    }
+}
+
+// Filter of the convolution that is the propagation along a convolution axis (conv_len) of n points, from its float64 table P = pr + i pi:
+// a = ifft_n(P) (float64), wrapped to the cyclic length M, filter = FFT_M(a) / M, stored as its first half + 1 (NH + 2 entries,
+// rowTB / rowTB2), or for M = 4096 in the split order of rowTC2_pass_kernel (even entries 0..1024, odd entries from 1026)
+int fill_conv_filter(msl_handle* h, const msl_handle::OpDir& o, const std::vector<double>& pr, const std::vector<double>& pi) {
+    const int n = o.n, M = conv_len(o), NH = M / 2;
+    std::vector<double> er(n), ei(n), qr(M, 0.0), qi(M, 0.0);
+    for (int m = 0; m < n; ++m) {
+        const double a = 2.0 * M_PI * (double)m / (double)n;
+        er[m] = cos(a); ei[m] = sin(a);
+    }
+    for (int j = 0; j < n; ++j) {                      // a[j] = (1/n) sum_m P[m] e^{+2 pi i m j / n}
+        double sr = 0.0, si = 0.0;
+        long long t = 0;
+        for (int m = 0; m < n; ++m) {
+            sr += pr[m] * er[t] - pi[m] * ei[t];
+            si += pr[m] * ei[t] + pi[m] * er[t];
+            t += j; if (t >= n) t -= n;
+        }
+        sr /= n; si /= n;
+        qr[j] = sr; qi[j] = si;                         // lag +j
+        if (j) { qr[M - n + j] = sr; qi[M - n + j] = si; }   // lag j - n  (M - (n - j))
+    }
+    host_fft_pow2(qr, qi);
+    std::vector<float2> qf(conv_filter_entries(o), make_float2(0.f, 0.f));
+    if (o.base == AX_CONV4K) {
+        for (int k = 0; k <= 1024; ++k) qf[k] = make_float2((float)(qr[2 * k] / M), (float)(qi[2 * k] / M));
+        for (int k = 0; k < 1024; ++k) qf[1026 + k] = make_float2((float)(qr[2 * k + 1] / M), (float)(qi[2 * k + 1] / M));
+    } else {
+        for (int j = 0; j <= NH; ++j) qf[j] = make_float2((float)(qr[j] / M), (float)(qi[j] / M));
+    }
+    return copy_table(h, o.qf, qf);
+}
+
+// Fresnel propagator, separable: P[kx,ky] = exp(-i pi lambda dz kx^2) * exp(-i pi lambda dz ky^2) (multislice.py:273-275), written on
+// the host, axis by axis: the plain table, the layer tap's conjugate, and from the plain table's values the split-order copy of a
+// 2R^2 axis and the filter of a convolution axis
+int fill_propagator(msl_handle* h) {
+    const msl_config& c = h->cfg;
+    std::vector<double> re, im, cr, ci;
+    int rc;
+    for (int a = 0; a < 2; ++a) {
+        const msl_handle::OpDir& o = a ? h->opy : h->opx;
+        const int n = a ? c.ny : c.nx;
+        const double d = a ? c.dy : c.dx;
+        std::vector<float2> plain(n), conj(n), split(n);
+        host_phase_table(c, n, d, -1.0, re, im);
+        host_phase_table(c, n, d, +1.0, cr, ci);
+        for (int m = 0; m < n; ++m) {
+            plain[m] = make_float2((float)(re[m] / n), (float)(im[m] / n));      // with the 1/n of the inverse FFT folded in
+            conj[m] = make_float2((float)cr[m], (float)ci[m]);                    // exp(+i pi lambda dz k^2), unscaled
+        }
+        for (int b = 0; b < 2; ++b)                                               // entry [b*R^2 + k] = P[2k + b]
+            for (int k = 0; k < n / 2; ++k) split[b * (n / 2) + k] = plain[2 * k + b];
+        if ((rc = copy_table(h, a ? h->pyt : h->pxt, plain)) || (rc = copy_table(h, a ? h->tap_cy : h->tap_cx, conj)) ||
+            (o.base == AX_TWO && (rc = copy_table(h, o.ptab, split))) || (conv_len(o) && (rc = fill_conv_filter(h, o, re, im)))) return rc;
+    }
+    return MSL_OK;
+}
+
+// The same tables with the tilt factor exp(-2 pi i dz tan(theta) k) and the mask of the band limit, written by the kernels of
+// propagator.h on the handle's stream: no host table, no copy and no wait, so a change is ordered behind the passes queued before it.
+int fill_propagator_device(msl_handle* h) {
+    const msl_config& c = h->cfg;
+    size_t work = 0;                                        // float64 entries of the convolution sums: P, E (n each), q, W (M each)
+    for (const msl_handle::OpDir* o : {&h->opx, &h->opy})
+        if (conv_len(*o)) work = std::max(work, 2 * (size_t)o->n + 2 * (size_t)conv_len(*o));
+    int rc = h->tilt_work.reserve(h, work);
+    if (rc) return rc;
+    for (int axis = 0; axis < 2; ++axis) {
+        const msl_handle::OpDir& o = axis ? h->opy : h->opx;
+        const int n = axis ? c.ny : c.nx, M = conv_len(o);
+        const double d = axis ? c.dy : c.dx;
+        // the half-spectrum layout holds the filter of an even table only, and no pass reads qf under a tilted axis (set_loop_mode has
+        // the two-pass loop on, a mixed axis reads the plain table): the filter is written at a zero tangent, which every way back to
+        // the convolution pass goes through (msl_set_tilt with 0 along the axis)
+        const bool filter = M && h->set.tilt_tan[axis] == 0.0;
+        double2* Pd = filter ? (double2*)h->tilt_work : nullptr;
+        double2* Ed = filter ? Pd + n : nullptr;
+        double2* q = filter ? Ed + n : nullptr;
+        double2* Wd = filter ? q + M : nullptr;
+        float2* split = o.base == AX_TWO ? (float2*)o.ptab : nullptr;
+        const int lanes = filter ? std::max(n, M) : n;
+        hipLaunchKernelGGL(propagator_tables_kernel, dim3((unsigned)((lanes + PROP_BLOCK - 1) / PROP_BLOCK)), dim3(PROP_BLOCK), 0, h->stream,
+                           n, M, 1.0 / (n * d), 0.5 * c.wavelength * c.dz, c.dz * h->set.tilt_tan[axis], axis ? h->pyt : h->pxt, split,
+                           axis ? h->tap_cy : h->tap_cx, Pd, Ed, Wd);
+        HIPCHK(h, hipGetLastError());
+        if (h->set.bl_on) {                                     // the band limit: before the filter sums, which then see the masked table
+            hipLaunchKernelGGL(propagator_bandlimit_kernel, dim3((unsigned)((n + PROP_BLOCK - 1) / PROP_BLOCK)), dim3(PROP_BLOCK), 0, h->stream,
+                               n, h->set.bl_cut[axis], axis ? h->pyt : h->pxt, split, axis ? h->tap_cy : h->tap_cx, Pd);
+            HIPCHK(h, hipGetLastError());
+        }
+        if (!filter) continue;
+        const int gap = M - 2 * n + 1, entries = (int)conv_filter_entries(o);
+        hipLaunchKernelGGL(conv_lag_kernel, dim3((unsigned)(n + (gap + PROP_BLOCK - 1) / PROP_BLOCK)), dim3(PROP_BLOCK), 0, h->stream, n, M,
+                           Pd, Ed, q);
+        HIPCHK(h, hipGetLastError());
+        hipLaunchKernelGGL(conv_filter_kernel, dim3((unsigned)entries), dim3(PROP_BLOCK), 0, h->stream, n, M, entries,
+                           o.base == AX_CONV4K ? 1 : 0, q, Wd, (float2*)o.qf);
+        HIPCHK(h, hipGetLastError());
+    }
+    return MSL_OK;
+}
+
+// The only caller of the two fillers and the only place that chooses between them.  A handle on which msl_set_tilt was never called
+// and which has no band limit runs on the host tables, every other one on the device tables (equal up to one float rounding per
+// entry).  The rule is there for the way back: a run without either setting, and one whose limit was set and cleared again, give bit
+// for bit what they gave before the settings existed (test_untilted_outputs_unchanged, test_off_is_off, tests/test_gpu_settings_order.py).
+int refresh_propagator(msl_handle* h) { return (h->set.tilt_set || h->set.bl_on) ? fill_propagator_device(h) : fill_propagator(h); }
+
+// ---- loop mode ----
+// The convolution passes keep the first half of their filter and mirror the rest (Q[M - k] = Q[k]), and the 2048-point wave kernel
+// reads its Fresnel factors the same way: both hold for an even table only, which a tilted axis does not have.  The direct kernels
+// (four-step, 2 R^2, mixed radix) read whole tables and take any tilt; so does the two-pass loop, on the plain tables.
+bool tilt_needs_two_pass(const msl_handle* h, double tan_x, double tan_y) {
+    auto even_only = [](const msl_handle::OpDir& o) { return o.kind == AX_CONV || o.kind == AX_CONV2K || o.kind == AX_CONV4K || o.kind == AX_WAVE2K; };
+    return (tan_x != 0.0 && even_only(h->opx)) || (tan_y != 0.0 && even_only(h->opy));
+}
+
+// The loop a handle may run under the tangents (tan_x, tan_y): the one msl_create planned, unless the TDS signal (slice_loop_tds runs
+// on the two-pass loop) or the tilt asks for the two-pass loop
+bool allowed_onepass(const msl_handle* h, double tan_x, double tan_y) {
+    return h->onepass_planned && !h->tds_on && !tilt_needs_two_pass(h, tan_x, tan_y);
+}
+
+// Switch a handle planned for the one-pass loop to the two-pass loop and back, on the stream.  The two-pass loop and the potential
+// build next to it (PI_LINES, untransposed stores) read and write `trans` in natural order only; the one-pass loop keeps every second
+// slice transposed in transT.  The stacks a potential build has filled are carried over, every batch slot.
+int set_loop_mode(msl_handle* h, bool onepass) {
+    if (onepass == h->onepass) return MSL_OK;
     int rc = MSL_OK;
-    for (int f = 0; f < count && rc == MSL_OK; ++f) rc = restore_natural_slices(h, slot + f);
-    if (rc || (rc = bandlimit_lowpass(h, slot, count))) return rc;
+    for (int f = 0; !onepass && h->have_potential && f < h->FB && rc == MSL_OK; ++f) rc = restore_natural_slices(h, f);
+    if (rc) return rc;
+    h->onepass = onepass;
+    h->pot_ifft = onepass ? plan_pot_ifft(h) : PI_LINES;
+    for (int f = 0; onepass && h->have_potential && f < h->FB && rc == MSL_OK; ++f) rc = transpose_odd_slices(h, f);
+    return rc;
+}
+
+// ---- transmission stacks ----
+// t = exp(i sigma V) of one stack with the handle's sigma, from V (nz, nx, ny) into batch slot `slot` in natural order
+int transmission_from_V(msl_handle* h, const float* V, int slot) {
+    const size_t n = (size_t)h->cfg.nx * h->cfg.ny * h->cfg.nz;
+    hipLaunchKernelGGL(transmission_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->trans + (size_t)slot * n, V,
+                       (long long)n, (float)h->cfg.sigma);
+    HIPCHK(h, hipGetLastError());
+    return MSL_OK;
+}
+
+// What `count` stacks just written in natural order from batch slot `slot` on still need: the low-pass while a band limit is on, and
+// the transposed copies of the slices the one-pass loop reads along x
+int finish_stacks(msl_handle* h, int slot, int count) {
+    int rc = h->set.bl_on ? bandlimit_lowpass(h, slot, count) : MSL_OK;
     for (int f = 0; f < count && rc == MSL_OK; ++f) rc = transpose_odd_slices(h, slot + f);
     return rc;
 }
+
+// The low-pass of stacks a build has left in the order of the slice loop (build_potentials, while a band limit is on): the transposed
+// slices come back to natural order first (a no-op on the two-pass loop), so the stack is limited once, in one orientation
+int bandlimit_built(msl_handle* h, int slot, int count) {
+    int rc = MSL_OK;
+    for (int f = 0; f < count && rc == MSL_OK; ++f) rc = restore_natural_slices(h, slot + f);
+    return rc ? rc : finish_stacks(h, slot, count);
+}
+
+// The stacks again from what is resident, with the handle's sigma and under its limit: from the two absorptive stacks, every batch slot
+// (and the TDS weights, which carry 2 sigma^2, from themselves), or else from the kept V (keep_potential runs at a frame batch of 1:
+// one stack, slot 0).  The caller has checked that one of the two is there.  Waits for the stream.
+int remake_transmission(msl_handle* h) {
+    int rc;
+    if (h->abs_built) {
+        // finish_stacks with the weights between its two steps, where msl_set_beam has always queued them
+        if ((rc = absorptive_transmission(h, 0, h->FB))) return rc;
+        if (h->set.bl_on && (rc = bandlimit_lowpass(h, 0, h->FB))) return rc;
+        if (h->tds_on && h->tds_W && (rc = tds_weights(h, false))) return rc;
+        for (int f = 0; f < h->FB; ++f) if ((rc = transpose_odd_slices(h, f))) return rc;
+    } else if ((rc = transmission_from_V(h, h->V, 0)) || (rc = finish_stacks(h, 0, 1))) return rc;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return MSL_OK;
+}
+
+// ---- invalidations ----
+// The resident potential no longer counts (msl_propagate is MSL_ERR_STATE until the next build or upload)
+void drop_potential(msl_handle* h) { h->have_potential = false; h->abs_built = false; }
+
+// A built S-matrix belongs to the tables and the stack it was built with: it has to be built again (the beams stay)
+void drop_smatrix_result(msl_handle* h) { h->sm_built = false; }
+
+// PRISM: free S, the beams and the coefficients (the stream is idle)
+void smatrix_release(msl_handle* h) {
+    h->sm_S.release(); h->sm_c.release(); h->sm_beams.release();
+    h->sm_h.clear();
+    h->sm_fx = h->sm_fy = h->sm_Bm = 0;
+    h->sm_open = h->sm_built = false;
+}
+
+// TDS off: its buffers freed, and the handle back on the loop its tilt allows
+int tds_clear(msl_handle* h) {
+    if (!h->tds_on) return MSL_OK;
+    h->tds_on = h->tds_have = false;
+    h->tds_n = 0;
+    h->tds_bits.release(); h->tds_g.release(); h->tds_W.release(); h->tds_acc.release(); h->tds_part.release();
+    return set_loop_mode(h, allowed_onepass(h, h->set.tilt_tan[0], h->set.tilt_tan[1]));
+}
+
+}  // namespace
+
+// ---- the setters ----
+extern "C" {
+
+int msl_set_beam(msl_handle* h, double wavelength, double sigma, double dz) {
+    if (!h) return fail(h, MSL_ERR_INVALID, "null handle");
+    if (!(wavelength > 0)) return fail(h, MSL_ERR_INVALID, "msl_set_beam: wavelength must be positive");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    h->cfg.wavelength = wavelength; h->cfg.sigma = sigma; h->cfg.dz = dz;
+    if (h->sm_open) {                                       // the wavelength changes the beam set
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        smatrix_release(h);
+    }
+    const int rc = refresh_propagator(h);                   // a tilt and a band limit stay on the handle
+    if (rc || !h->have_potential) return rc;
+    if (!h->abs_built && !h->V)
+        return fail(h, MSL_ERR_STATE, "msl_set_beam: potential present but V not kept (keep_potential=0); rebuild the potential");
+    return remake_transmission(h);
+}
+
+int msl_set_tilt(msl_handle* h, double tan_x, double tan_y) {
+    if (!h) return fail(h, MSL_ERR_INVALID, "null handle");
+    if (!std::isfinite(tan_x) || !std::isfinite(tan_y)) return fail(h, MSL_ERR_INVALID, "msl_set_tilt: tan_x and tan_y must be finite");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    int rc = set_loop_mode(h, allowed_onepass(h, tan_x, tan_y));      // the loop that can run this tilt; a refused switch leaves the handle as it was
+    if (rc) return rc;
+    const msl_handle::Settings old = h->set;
+    h->set.tilt_tan[0] = tan_x; h->set.tilt_tan[1] = tan_y; h->set.tilt_set = true;
+    if ((rc = refresh_propagator(h))) { h->set = old; return rc; }
+    drop_smatrix_result(h);
+    return MSL_OK;
+}
+
+int msl_get_tilt(const msl_handle* h, double* tan_xy) {
+    if (!h || !tan_xy) return MSL_ERR_INVALID;
+    tan_xy[0] = h->set.tilt_tan[0]; tan_xy[1] = h->set.tilt_tan[1];
+    return MSL_OK;
+}
+
+int msl_set_bandlimit(msl_handle* h, int32_t cut_x, int32_t cut_y) {
+    if (!h) return fail(h, MSL_ERR_INVALID, "null handle");
+    const msl_config& c = h->cfg;
+    const bool clear = cut_x < 0 && cut_y < 0;
+    if (!clear) {
+        if (cut_x < 1 || cut_y < 1)
+            return fail(h, MSL_ERR_INVALID, "msl_set_bandlimit: cuts (%d, %d): both at least 1, or both negative to clear", cut_x, cut_y);
+        if (3LL * cut_x >= c.nx || 3LL * cut_y >= c.ny)
+            return fail(h, MSL_ERR_INVALID, "msl_set_bandlimit: cuts (%d, %d) are not alias-free on the %d x %d grid (3 cut < n)", cut_x, cut_y,
+                        c.nx, c.ny);
+    }
+    if (clear && !h->set.bl_on) return MSL_OK;              // never set: the tables and the stacks stay what they are
+    HIPCHK(h, hipSetDevice(c.device));
+    int rc;
+    if (!clear) {
+        if ((rc = h->bl_mx.reserve(h, (size_t)c.nx)) || (rc = h->bl_my.reserve(h, (size_t)c.ny))) return rc;
+        hipLaunchKernelGGL(bandlimit_mask_kernel, dim3((unsigned)((c.nx + BL_BLOCK - 1) / BL_BLOCK)), dim3(BL_BLOCK), 0, h->stream, c.nx, cut_x,
+                           h->bl_mx.p);
+        hipLaunchKernelGGL(bandlimit_mask_kernel, dim3((unsigned)((c.ny + BL_BLOCK - 1) / BL_BLOCK)), dim3(BL_BLOCK), 0, h->stream, c.ny, cut_y,
+                           h->bl_my.p);
+        HIPCHK(h, hipGetLastError());
+    }
+    const msl_handle::Settings old = h->set;
+    h->set.bl_on = !clear;
+    h->set.bl_cut[0] = clear ? -1 : cut_x; h->set.bl_cut[1] = clear ? -1 : cut_y;
+    if ((rc = refresh_propagator(h))) { h->set = old; return rc; }
+    drop_smatrix_result(h);
+    // a kept V without absorption: the stack again from it under the new limit (what Propagate(..., bandlimit=) relies on).  Absorptive
+    // stacks and a potential whose V was not kept belong to the limit they were built under: dropped, the next build makes them
+    if (h->have_potential && h->V && !h->abs_built) return remake_transmission(h);
+    drop_potential(h);
+    return MSL_OK;
+}
+
+int msl_get_bandlimit(const msl_handle* h, int32_t* cut_xy) {
+    if (!h || !cut_xy) return MSL_ERR_INVALID;
+    cut_xy[0] = h->set.bl_cut[0]; cut_xy[1] = h->set.bl_cut[1];
+    return MSL_OK;
+}
+
+// absorptive potential
+int msl_set_absorption(msl_handle* h, const double* u_by_Z, int32_t absorb) {
+    if (!h) return fail(h, MSL_ERR_INVALID, "msl_set_absorption: null handle");
+    for (int z = 0; u_by_Z && z < 103; ++z)
+        if (!std::isfinite(u_by_Z[z]) || !(u_by_Z[z] >= 0.0))
+            return fail(h, MSL_ERR_INVALID, "msl_set_absorption: width %g of atomic number %d is not a finite number >= 0", u_by_Z[z], z + 1);
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));          // a queued build still reads the tables and the stacks
+    h->ff_n = 0;                                         // d_ff holds f or f D: the next build makes its table again
+    drop_potential(h);                                   // (Omega kept or left out, other widths: nothing msl_set_beam could remake t from)
+    int rc;
+    if ((!u_by_Z || !absorb) && (rc = tds_clear(h))) return rc;      // the TDS signal is that of the absorption: it goes with it
+    if (!u_by_Z) {
+        h->abs_on = h->abs_absorb = false;
+        h->d_abs_u.release(); h->d_ffa.release(); h->abs_V.release(); h->abs_O.release();
+        return MSL_OK;
+    }
+    if (!h->d_abs_u && (rc = h->d_abs_u.alloc(h, (size_t)103))) return rc;
+    HIPCHK(h, hipMemcpy(h->d_abs_u, u_by_Z, 103 * sizeof(double), hipMemcpyHostToDevice));
+    h->abs_on = true;
+    h->abs_absorb = absorb != 0;
+    return MSL_OK;
+}
+
+// TDS detector signal
+int msl_set_tds(msl_handle* h, const uint16_t* member_bits, int32_t n_det) {
+    if (!h) return fail(h, MSL_ERR_INVALID, "msl_set_tds: null handle");
+    const bool clear = !member_bits || n_det == 0;
+    if (!clear && (n_det < 1 || n_det > TDS_MAX)) return fail(h, MSL_ERR_INVALID, "msl_set_tds: %d detectors outside [1, %d]", n_det, TDS_MAX);
+    if (!clear && !(h->abs_on && h->abs_absorb))
+        return fail(h, MSL_ERR_STATE, "msl_set_tds: no absorption (call msl_set_absorption(.., absorb != 0) first)");
+    if (!clear && h->FB > 1) return fail(h, MSL_ERR_UNSUPPORTED, "msl_set_tds: a frame batch of %d (the weight stack is that of one frame)", h->FB);
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));          // a queued build or loop still reads the tables and the stacks
+    h->ff_n = 0;                                         // as msl_set_absorption: the next build makes the tables again
+    drop_potential(h);
+    int rc = tds_clear(h);
+    if (rc || clear) return rc;
+    const size_t npix = (size_t)h->cfg.nx * h->cfg.ny;
+    if ((rc = h->tds_bits.alloc(h, npix))) return rc;
+    HIPCHK(h, hipMemcpy(h->tds_bits, member_bits, npix * sizeof(uint16_t), hipMemcpyHostToDevice));
+    h->tds_n = n_det;
+    h->tds_on = true;
+    rc = set_loop_mode(h, allowed_onepass(h, h->set.tilt_tan[0], h->set.tilt_tan[1]));
+    if (rc) { h->tds_on = false; h->tds_n = 0; h->tds_bits.release(); }      // a refused switch: no TDS, as after the tds_clear above
+    return rc;
+}
+
+}  // extern "C"
+
+namespace {
 
 // Projected potentials + transmission functions of `count` MD frames (the same atoms, `count` sets of positions) into the batch
 // slots first_slot .. first_slot + count - 1: ONE launch each of the atom preparation, the stable counting sort (keys = frame x
@@ -2246,7 +2452,7 @@ int build_potentials(msl_handle* h, const double* pos, const int32_t* Z, int64_t
         if ((rc = h->abs_on ? absorptive_group(h, p, n > 0 && p.nsp > 0) : potential_ifft(h, p))) return rc;
     }
     h->n_species = p.nsp;
-    if (h->bl_on && (rc = bandlimit_built(h, first_slot, count))) return rc;
+    if (h->set.bl_on && (rc = bandlimit_built(h, first_slot, count))) return rc;
     if ((rc = timer.end(h, &h->ctr.ms_potential))) return rc;
     h->have_potential = true;
     h->abs_built = h->abs_on;
@@ -2456,14 +2662,6 @@ static int welch_resident(msl_handle* h, const float2* block, int32_t L, int32_t
     return welch_run(h, block, h->intensity, c.n_probes, c.n_frames, (int64_t)h->wpitch, L, hop, S, g);
 }
 
-// PRISM: free S, the beams and the coefficients (the stream is idle)
-static void smatrix_release(msl_handle* h) {
-    h->sm_S.release(); h->sm_c.release(); h->sm_beams.release();
-    h->sm_h.clear();
-    h->sm_fx = h->sm_fy = h->sm_Bm = 0;
-    h->sm_open = h->sm_built = false;
-}
-
 // The work buffers sized by the probe count (FB frames of n_probes images each; pitch, pitchT, onepass and need_psi0T are set)
 static int alloc_probe_buffers(msl_handle* h, int n_probes) {
     const msl_config& c = h->cfg;
@@ -2597,7 +2795,7 @@ int msl_create(const msl_config* cfg, msl_handle** out) {
     if ((rc = h->pxt.alloc(h, (size_t)cfg->nx)) || (rc = h->pyt.alloc(h, (size_t)cfg->ny)) || (rc = h->tap_cx.alloc(h, (size_t)cfg->nx)) ||
         (rc = h->tap_cy.alloc(h, (size_t)cfg->ny)) || (rc = h->d_lo.alloc(h, (size_t)cfg->nz)) || (rc = h->d_hi.alloc(h, (size_t)cfg->nz)) ||
         (rc = h->d_abcd.alloc(h, (size_t)103 * 12)) || (rc = h->d_z2s.alloc(h, (size_t)104)) || (rc = h->d_species.alloc(h, (size_t)104)) ||
-        (rc = fill_propagator(h))) return bail(rc);
+        (rc = refresh_propagator(h))) return bail(rc);
     *out = h;
     return MSL_OK;
 }
@@ -2636,155 +2834,6 @@ int msl_set_slices(msl_handle* h, const double* lo, const double* hi) {
     HIPCHK(h, hipMemcpyAsync(h->d_hi, hi, h->cfg.nz * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     h->have_slices = true;
-    return MSL_OK;
-}
-
-int msl_set_beam(msl_handle* h, double wavelength, double sigma, double dz) {
-    if (!h) return fail(h, MSL_ERR_INVALID, "null handle");
-    if (!(wavelength > 0)) return fail(h, MSL_ERR_INVALID, "msl_set_beam: wavelength must be positive");
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    h->cfg.wavelength = wavelength; h->cfg.sigma = sigma; h->cfg.dz = dz;
-    if (h->sm_open) {                                       // the wavelength changes the beam set
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        smatrix_release(h);
-    }
-    int rc = (h->tilt_set || h->bl_on) ? fill_propagator_device(h) : fill_propagator(h);      // a tilt and a band limit stay on the handle
-    if (rc) return rc;
-    if (h->have_potential && h->abs_built) {
-        // an absorptive build keeps its two real stacks: t of every batch slot again, with the new sigma
-        if ((rc = absorptive_transmission(h, 0, h->FB))) return rc;
-        if (h->bl_on && (rc = bandlimit_lowpass(h, 0, h->FB))) return rc;
-        if (h->tds_on && h->tds_W && (rc = tds_weights(h, false))) return rc;       // and the TDS weights, which carry 2 sigma^2
-        for (int f = 0; f < h->FB; ++f) if ((rc = transpose_odd_slices(h, f))) return rc;
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-    } else if (h->have_potential) {
-        if (!h->V) return fail(h, MSL_ERR_STATE, "msl_set_beam: potential present but V not kept (keep_potential=0); rebuild the potential");
-        const size_t n = (size_t)h->cfg.nx * h->cfg.ny * h->cfg.nz;
-        hipLaunchKernelGGL(transmission_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->trans, h->V,
-                           (long long)n, (float)sigma);
-        HIPCHK(h, hipGetLastError());
-        if (h->bl_on && (rc = bandlimit_lowpass(h, 0, 1))) return rc;
-        if ((rc = transpose_odd_slices(h, h->cur_batch))) return rc;
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-    }
-    return MSL_OK;
-}
-
-namespace {
-
-// The convolution passes keep the first half of their filter and mirror the rest (Q[M - k] = Q[k]), and the 2048-point wave kernel
-// reads its Fresnel factors the same way: both hold for an even table only, which a tilted axis does not have.  The direct kernels
-// (four-step, 2 R^2, mixed radix) read whole tables and take any tilt; so does the two-pass loop, on the plain tables.
-bool tilt_needs_two_pass(const msl_handle* h, double tan_x, double tan_y) {
-    auto even_only = [](const msl_handle::OpDir& o) { return o.kind == AX_CONV || o.kind == AX_CONV2K || o.kind == AX_CONV4K || o.kind == AX_WAVE2K; };
-    return (tan_x != 0.0 && even_only(h->opx)) || (tan_y != 0.0 && even_only(h->opy));
-}
-
-// Switch a handle planned for the one-pass loop to the two-pass loop and back, on the stream.  The two-pass loop and the potential
-// build next to it (PI_LINES, untransposed stores) read and write `trans` in natural order only; the one-pass loop keeps every second
-// slice transposed in transT.  The stacks a potential build has filled are carried over, every batch slot.
-int set_loop_mode(msl_handle* h, bool onepass) {
-    if (onepass == h->onepass) return MSL_OK;
-    int rc = MSL_OK;
-    if (!onepass) {
-        for (int f = 0; h->have_potential && f < h->FB && rc == MSL_OK; ++f) rc = restore_natural_slices(h, f);
-        if (rc) return rc;
-        h->onepass = false;
-        h->pot_ifft = PI_LINES;
-        return MSL_OK;
-    }
-    h->onepass = true;
-    h->pot_ifft = plan_pot_ifft(h);
-    for (int f = 0; h->have_potential && f < h->FB && rc == MSL_OK; ++f) rc = transpose_odd_slices(h, f);
-    return rc;
-}
-
-// TDS off: its buffers freed, and the handle back on the loop its tilt allows
-int tds_clear(msl_handle* h) {
-    if (!h->tds_on) return MSL_OK;
-    h->tds_on = h->tds_have = false;
-    h->tds_n = 0;
-    h->tds_bits.release(); h->tds_g.release(); h->tds_W.release(); h->tds_acc.release(); h->tds_part.release();
-    return set_loop_mode(h, h->onepass_planned && !tilt_needs_two_pass(h, h->tilt_tan[0], h->tilt_tan[1]));
-}
-
-}  // namespace
-
-int msl_set_tilt(msl_handle* h, double tan_x, double tan_y) {
-    if (!h) return fail(h, MSL_ERR_INVALID, "null handle");
-    if (!std::isfinite(tan_x) || !std::isfinite(tan_y)) return fail(h, MSL_ERR_INVALID, "msl_set_tilt: tan_x and tan_y must be finite");
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    {   // the loop that can run this tilt; a refused switch leaves the handle as it was
-        const int rc = set_loop_mode(h, h->onepass_planned && !h->tds_on && !tilt_needs_two_pass(h, tan_x, tan_y));
-        if (rc) return rc;
-    }
-    const double old[2] = {h->tilt_tan[0], h->tilt_tan[1]};
-    h->tilt_tan[0] = tan_x; h->tilt_tan[1] = tan_y;
-    const int rc = fill_propagator_device(h);
-    if (rc) { h->tilt_tan[0] = old[0]; h->tilt_tan[1] = old[1]; return rc; }
-    h->tilt_set = true;
-    h->sm_built = false;                                    // an S-matrix belongs to the tilt it was built at
-    return MSL_OK;
-}
-
-int msl_set_bandlimit(msl_handle* h, int32_t cut_x, int32_t cut_y) {
-    if (!h) return fail(h, MSL_ERR_INVALID, "null handle");
-    const msl_config& c = h->cfg;
-    const bool clear = cut_x < 0 && cut_y < 0;
-    if (!clear) {
-        if (cut_x < 1 || cut_y < 1)
-            return fail(h, MSL_ERR_INVALID, "msl_set_bandlimit: cuts (%d, %d): both at least 1, or both negative to clear", cut_x, cut_y);
-        if (3LL * cut_x >= c.nx || 3LL * cut_y >= c.ny)
-            return fail(h, MSL_ERR_INVALID, "msl_set_bandlimit: cuts (%d, %d) are not alias-free on the %d x %d grid (3 cut < n)", cut_x, cut_y,
-                        c.nx, c.ny);
-    }
-    if (clear && !h->bl_on) return MSL_OK;                  // never set: the tables and the stacks stay what they are
-    HIPCHK(h, hipSetDevice(c.device));
-    int rc;
-    if (!clear) {
-        if ((rc = h->bl_mx.reserve(h, (size_t)c.nx)) || (rc = h->bl_my.reserve(h, (size_t)c.ny))) return rc;
-        hipLaunchKernelGGL(bandlimit_mask_kernel, dim3((unsigned)((c.nx + BL_BLOCK - 1) / BL_BLOCK)), dim3(BL_BLOCK), 0, h->stream, c.nx, cut_x,
-                           h->bl_mx.p);
-        hipLaunchKernelGGL(bandlimit_mask_kernel, dim3((unsigned)((c.ny + BL_BLOCK - 1) / BL_BLOCK)), dim3(BL_BLOCK), 0, h->stream, c.ny, cut_y,
-                           h->bl_my.p);
-        HIPCHK(h, hipGetLastError());
-    }
-    const bool old_on = h->bl_on;
-    const int old_cut[2] = {h->bl_cut[0], h->bl_cut[1]};
-    h->bl_on = !clear;
-    h->bl_cut[0] = clear ? -1 : cut_x; h->bl_cut[1] = clear ? -1 : cut_y;
-    // cleared on a handle without a tilt: the host tables again, bit for bit those of msl_create / msl_set_beam
-    if ((rc = (h->tilt_set || h->bl_on) ? fill_propagator_device(h) : fill_propagator(h))) {
-        h->bl_on = old_on; h->bl_cut[0] = old_cut[0]; h->bl_cut[1] = old_cut[1];       // a refused call leaves the handle's state as it was
-        return rc;
-    }
-    h->sm_built = false;                                    // an S-matrix belongs to the tables and the stack it was built with
-    if (h->have_potential && h->V && !h->abs_built) {
-        // a kept V (keep_potential, which runs at a frame batch of 1: one stack, slot 0): the transmission functions again from it,
-        // as msl_set_beam makes them, under the new limit
-        const size_t n = (size_t)c.nx * c.ny * c.nz;
-        hipLaunchKernelGGL(transmission_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->trans, h->V, (long long)n,
-                           (float)c.sigma);
-        HIPCHK(h, hipGetLastError());
-        if (h->bl_on && (rc = bandlimit_lowpass(h, 0, 1))) return rc;
-        if ((rc = transpose_odd_slices(h, h->cur_batch))) return rc;
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        return MSL_OK;
-    }
-    h->have_potential = false;                              // no V to make them from: the stacks belong to the limit they were built
-    h->abs_built = false;                                   // under, and the next build makes them
-    return MSL_OK;
-}
-
-int msl_get_bandlimit(const msl_handle* h, int32_t* cut_xy) {
-    if (!h || !cut_xy) return MSL_ERR_INVALID;
-    cut_xy[0] = h->bl_cut[0]; cut_xy[1] = h->bl_cut[1];
-    return MSL_OK;
-}
-
-int msl_get_tilt(const msl_handle* h, double* tan_xy) {
-    if (!h || !tan_xy) return MSL_ERR_INVALID;
-    tan_xy[0] = h->tilt_tan[0]; tan_xy[1] = h->tilt_tan[1];
     return MSL_OK;
 }
 
@@ -3048,58 +3097,7 @@ int msl_set_modes(msl_handle* h, const int32_t* basis_index, int64_t n_atoms, in
     return MSL_OK;
 }
 
-// ---- absorptive potential ----------------------------------------------------
-int msl_set_absorption(msl_handle* h, const double* u_by_Z, int32_t absorb) {
-    if (!h) return fail(h, MSL_ERR_INVALID, "msl_set_absorption: null handle");
-    for (int z = 0; u_by_Z && z < 103; ++z)
-        if (!std::isfinite(u_by_Z[z]) || !(u_by_Z[z] >= 0.0))
-            return fail(h, MSL_ERR_INVALID, "msl_set_absorption: width %g of atomic number %d is not a finite number >= 0", u_by_Z[z], z + 1);
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    HIPCHK(h, hipStreamSynchronize(h->stream));          // a queued build still reads the tables and the stacks
-    h->ff_n = 0;                                         // d_ff holds f or f D: the next build makes its table again
-    // the stacks of an earlier build no longer say what msl_set_beam should make of them (Omega kept or left out, other widths):
-    // the potential counts as not built until the next build
-    h->abs_built = false;
-    h->have_potential = false;
-    int rc;
-    if ((!u_by_Z || !absorb) && (rc = tds_clear(h))) return rc;      // the TDS signal is that of the absorption: it goes with it
-    if (!u_by_Z) {
-        h->abs_on = h->abs_absorb = false;
-        h->d_abs_u.release(); h->d_ffa.release(); h->abs_V.release(); h->abs_O.release();
-        return MSL_OK;
-    }
-    if (!h->d_abs_u && (rc = h->d_abs_u.alloc(h, (size_t)103))) return rc;
-    HIPCHK(h, hipMemcpy(h->d_abs_u, u_by_Z, 103 * sizeof(double), hipMemcpyHostToDevice));
-    h->abs_on = true;
-    h->abs_absorb = absorb != 0;
-    return MSL_OK;
-}
-
-// ---- TDS detector signal -----------------------------------------------------
-int msl_set_tds(msl_handle* h, const uint16_t* member_bits, int32_t n_det) {
-    if (!h) return fail(h, MSL_ERR_INVALID, "msl_set_tds: null handle");
-    const bool clear = !member_bits || n_det == 0;
-    if (!clear && (n_det < 1 || n_det > TDS_MAX)) return fail(h, MSL_ERR_INVALID, "msl_set_tds: %d detectors outside [1, %d]", n_det, TDS_MAX);
-    if (!clear && !(h->abs_on && h->abs_absorb))
-        return fail(h, MSL_ERR_STATE, "msl_set_tds: no absorption (call msl_set_absorption(.., absorb != 0) first)");
-    if (!clear && h->FB > 1) return fail(h, MSL_ERR_UNSUPPORTED, "msl_set_tds: a frame batch of %d (the weight stack is that of one frame)", h->FB);
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    HIPCHK(h, hipStreamSynchronize(h->stream));          // a queued build or loop still reads the tables and the stacks
-    // as msl_set_absorption: the tables are made again by the next build, and the potential counts as not built until then
-    h->ff_n = 0;
-    h->abs_built = false;
-    h->have_potential = false;
-    int rc = tds_clear(h);
-    if (rc || clear) return rc;
-    const size_t npix = (size_t)h->cfg.nx * h->cfg.ny;
-    if ((rc = h->tds_bits.alloc(h, npix))) return rc;
-    HIPCHK(h, hipMemcpy(h->tds_bits, member_bits, npix * sizeof(uint16_t), hipMemcpyHostToDevice));
-    if ((rc = set_loop_mode(h, false))) { h->tds_bits.release(); return rc; }
-    h->tds_n = n_det;
-    h->tds_on = true;
-    return MSL_OK;
-}
-
+// ---- TDS detector signal (msl_set_absorption and msl_set_tds stand with the handle settings) ----
 int msl_tds_fetch(msl_handle* h, int32_t B, double* out) {
     if (!h || !out) return fail(h, MSL_ERR_INVALID, "msl_tds_fetch: null argument");
     if (!h->tds_on || !h->tds_have) return fail(h, MSL_ERR_STATE, "msl_tds_fetch: no TDS sums (msl_set_tds, then a slice loop)");
@@ -3174,11 +3172,8 @@ int msl_upload_potential(msl_handle* h, const float* V) {
     DevBuf<float> tmp;
     if (!dst) { int rc = tmp.alloc(h, n); if (rc) return rc; dst = tmp; }
     HIPCHK(h, hipMemcpyAsync(dst, V, n * sizeof(float), hipMemcpyHostToDevice, h->stream));
-    hipLaunchKernelGGL(transmission_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->trans + (size_t)h->cur_batch * n, dst,
-                       (long long)n, (float)c.sigma);
-    HIPCHK(h, hipGetLastError());
-    if (h->bl_on) { int rc = bandlimit_lowpass(h, h->cur_batch, 1); if (rc) return rc; }
-    { int rc = transpose_odd_slices(h, h->cur_batch); if (rc) return rc; }
+    int rc = transmission_from_V(h, dst, h->cur_batch);
+    if (rc || (rc = finish_stacks(h, h->cur_batch, 1))) return rc;
     HIPCHK(h, hipStreamSynchronize(h->stream));
     h->have_potential = true;
     h->abs_built = false;
