@@ -6,7 +6,13 @@ figures per kernel family.
 
 With tilt=(tan_x, tan_y) the same cases run on the tables msl_set_tilt writes, which are not even in k (P[m] != P[n - m]), against
 the float64 definition of pyslice_amd/tilt.py: tests/test_gpu_white_tilt.py imports the TILT_* lists, and the script measures them
-into a second report.  usage: python tools/white_parity.py [out.txt [tilt_out.txt]], or --tilt-only [tilt_out.txt]"""
+into a second report.
+
+output_case() extends the contract to the layer taps (msl_set_layers) and to the stored form of every spectrum -- k-window, detector
+bin, frame-batch scatter -- on untilted tables: tests/test_gpu_white_output.py imports the OUT_* lists and tap_layout(), the pure
+restatement of which line order, row FFT and column pass a tap takes.
+usage: python tools/white_parity.py [out.txt [tilt_out.txt]], or --tilt-only [tilt_out.txt], or --output-only [output_out.txt]"""
+import collections
 import functools
 import math
 import os
@@ -85,6 +91,7 @@ TILT_LAYER_CASES = [(nx, ny, 4, TILT, (0, 1, 2)) for nx, ny in ((600, 135), (135
                    [(501, 144, 4, TILT_X, (0, 1, 2))]
 
 
+@functools.lru_cache(maxsize=None)
 def _mixed_groups():
     """length -> lanes per line of its mixed-radix kernel, from the instantiation lists of csrc/rowtm_launch.h"""
     src = open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "pyslice_amd", "csrc", "rowtm_launch.h")).read()
@@ -177,9 +184,9 @@ def metrics(got, want):
     return float(e_img), float(e_line), float(e_pix)
 
 
-def engine(nx, ny, nz, P, n_frames=1, fft_path=0, frame_batch=1):
+def engine(nx, ny, nz, P, n_frames=1, fft_path=0, frame_batch=1, window=None, k_bin=None):
     return _native.Engine(nx, ny, nz, DX, DY, DZ, orc.wavelength(EV), orc.interaction_sigma(EV), n_probes=P, n_frames=n_frames,
-                          fft_path=fft_path, frame_batch=frame_batch)
+                          fft_path=fft_path, frame_batch=frame_batch, window=window, k_bin=k_bin)
 
 
 @functools.lru_cache(maxsize=1)
@@ -392,7 +399,319 @@ def tilt_main(out_path):
     return 1 if bad else 0
 
 
+# ---- layer taps and the windowed, binned output (tests/test_gpu_white_output.py, tests/test_white_output_host.py) ----------------
+OutputCase = collections.namedtuple("OutputCase", "nx ny nz P layers window k_bin frame_batch fft_path")
+
+
+def _oc(nx, ny, nz=4, P=2, layers=None, window=None, k_bin=None, frame_batch=1, fft_path=0):
+    """a case of output_case(): every slice but the last is tapped unless layers says otherwise"""
+    return OutputCase(nx, ny, nz, P, tuple(range(nz - 1)) if layers is None else tuple(layers), window, k_bin, frame_batch, fft_path)
+
+
+def output_id(c):
+    s = f"{c.nx}x{c.ny}x{c.nz}-P{c.P}"
+    s += ("-win%dx%d" % tuple(c.window) if c.window else "") + ("-bin%dx%d" % tuple(c.k_bin) if c.k_bin else "")
+    return s + (f"-fb{c.frame_batch}" if c.frame_batch > 1 else "") + ("-two_pass" if c.fft_path else "")
+
+
+# the grids of TILT_LAYER_CASES without a tilt: the conjugate tables fill_propagator derives on the host.  501 x 144 is then
+# one-pass, the tap behind a convolution axis
+OUT_UNTILTED_CASES = [_oc(c[0], c[1]) for c in TILT_LAYER_CASES]
+# alternating scheme: nz = 5 is the other parity (interleaved order up to k = nz - 3, natural at nz - 2); rp 16 and 32 in one run
+# and COL_MULPX on both radices; ny % 32 = 16 sends the tap's column pass to the generic kernel with MUL_VEC
+OUT_ALTERNATING_CASES = [_oc(256, 256, 5), _oc(1024, 256), _oc(256, 1024), _oc(256, 144)]
+# scheme B, interleaved order between a 512-point axis and a 256 / 1024-point one
+OUT_SCHEME_B_CASES = [_oc(512, 256), _oc(256, 512), _oc(1024, 512), _oc(512, 1024)]
+OUT_PAIRED_CASES = [_oc(2048, 2048, P=1)]                       # both axes on the wave kernel: the paired-lines gather
+OUT_WAVE_NATURAL_CASES = [_oc(2048, 144), _oc(144, 2048)]       # natural order out of the wave kernel
+OUT_ROWTM2_CASES = [_oc(1000, 135), _oc(135, 1000)]             # G = 64: one wave per line
+OUT_MIXED16_CASES = [_oc(max(n for n, g in _mixed_groups().items() if g == 16), 135)]
+# a convolution of every cyclic length M = 256, 1024, 2048, 4096 against 144 lines, on both axes
+OUT_CONV_LENGTHS = [127, 501, 997, 1025]
+OUT_CONV_CASES = [c for n in OUT_CONV_LENGTHS for c in (_oc(n, 144), _oc(144, n))]
+OUT_GENERIC_CASES = [_oc(32, 135), _oc(135, 32), _oc(143, 144), _oc(144, 143)]
+# the tapped two-pass loop (slice_loop, begin_timed(2 nz + 2)): generic kernels on both axes, a Bluestein-free pair, power-of-two axes
+OUT_TWO_PASS_CASES = [_oc(96, 80, fft_path=1), _oc(45, 63, fft_path=1), _oc(256, 144, fft_path=1), _oc(512, 512, fft_path=1)]
+# the other tapped two-pass loop (slice_loop_tds, begin_timed(5 nz + 2)) runs while msl_set_tds is on, which needs a built absorptive
+# potential: tds_loop_case() below.  Smallest grids: 45 x 63 for either loop (nothing in them depends on the size)
+OUT_TDS_LOOP_CASES = [(45, 63, 4)]
+OUT_PROBE_CHUNK_CASES = [_oc(600, 135, P=17), _oc(256, 256, P=33)]
+OUT_WINDOW_BIN_CASES = [_oc(256, 256, window=(64, 96)),                          # fast column kernel, wy % 32 = 0
+                        _oc(256, 256, window=(50, 40)),                          # generic pass
+                        _oc(256, 256, k_bin=(4, 4)),
+                        _oc(256, 256, window=(64, 96), k_bin=(2, 8)),
+                        _oc(1024, 256, window=(256, 64), k_bin=(16, 1)),
+                        _oc(600, 135, window=(150, 45), k_bin=(5, 3)),           # generic epilogue
+                        _oc(45, 63, window=(15, 21), k_bin=(5, 7), fft_path=1)]  # two-pass
+# two batch slots, a white potential each: out_group on the fast column kernel, on the generic pass, and bin_frames regrouping by frame
+OUT_FRAME_BATCH_CASES = [_oc(256, 256, frame_batch=2), _oc(600, 135, frame_batch=2),
+                         _oc(256, 256, window=(64, 96), k_bin=(2, 8), frame_batch=2)]
+OUT_WIDE_CASE = _oc(256, 144)
+OUTPUT_LISTS = (("untilted", OUT_UNTILTED_CASES), ("alternating", OUT_ALTERNATING_CASES), ("scheme B", OUT_SCHEME_B_CASES),
+                ("paired", OUT_PAIRED_CASES), ("wave natural", OUT_WAVE_NATURAL_CASES), ("rowTM2", OUT_ROWTM2_CASES),
+                ("mixed G16", OUT_MIXED16_CASES), ("convolution", OUT_CONV_CASES), ("generic", OUT_GENERIC_CASES),
+                ("two-pass", OUT_TWO_PASS_CASES), ("probe chunks", OUT_PROBE_CHUNK_CASES), ("window / bin", OUT_WINDOW_BIN_CASES),
+                ("frame batch", OUT_FRAME_BATCH_CASES))
+
+AxisPlan = collections.namedtuple("AxisPlan", "kind base R")
+
+
+def _plan_M(n):
+    """mslice.hip, make_plan: the length of the generic plan, n itself when 13-smooth, else the Bluestein power of two >= 2 n - 1"""
+    if _smooth13(n):
+        return n
+    M = 1
+    while M < 2 * n - 1:
+        M <<= 1
+    return M
+
+
+def plan_radices(nx, ny, fft_path=0):
+    """(Rx, Ry) of msl_create: the four-step radix of the exit / tap column kernel and of the fast row FFT, 0 = the generic kernel"""
+    if fft_path:
+        return 0, 0
+    radix = {1024: 32, 256: 16}
+    ry, rx = radix.get(ny, 0), radix.get(nx, 0)
+    return (rx if rx and ny % 16 == 0 and ny >= 32 else 0), (ry if ry and nx % (256 // ry) == 0 else 0)
+
+
+def axis_plan(n, n_other, rfast, want=True):
+    """mslice.hip, plan_axis_kind: (kind, base, R) of the one-pass kernel along an axis of n points with n_other lines"""
+    base = None
+    if not want:
+        pass
+    elif rfast and n_other % 16 == 0:
+        base = "fourstep"
+    elif n in (512, 2048) and n_other % 16 == 0:
+        base = "two" if n == 512 else "wave2k"
+    elif 33 <= n <= 512 and (n <= 128 or n >= 192 or _plan_M(n) != n):
+        base = "conv"
+    elif 513 <= n <= 1024:
+        base = "conv2k"
+    elif 1025 <= n <= 2047:
+        base = "conv4k"
+    elif _plan_M(n) <= 1024:
+        base = "generic"
+    mixed = want and base not in ("fourstep", "two", "wave2k") and n in _mixed_groups()
+    R = {"fourstep": rfast, "two": 16, "conv": 16 if n <= 128 else 32, "wave2k": 32, "conv2k": 32, "conv4k": 32}.get(base, 0)
+    return AxisPlan("mixed" if mixed else base, base, R)
+
+
+def grid_plan(nx, ny, fft_path=0):
+    """(plan of x, plan of y, one_pass) as msl_create plans a grid"""
+    Rx, Ry = plan_radices(nx, ny, fft_path)
+    px, py = axis_plan(nx, ny, Rx, not fft_path), axis_plan(ny, nx, Ry, not fft_path)
+    return px, py, px.base is not None and py.base is not None
+
+
+def tap_layout(nx, ny, nz, k, one_pass=True, window=None, fft_path=0):
+    """(axis, order, rp, row_fft, column_pass) of the tap after slice k: the axis of tap_axis(); the line order of the work buffer it
+    gathers ("natural", "interleaved" with rp = R' of the reading kernel, "paired"; rp = 0 otherwise); the row FFT and the column
+    pass of the tap, "fast" (row_pass_pf / col_pass_kernel) or "generic" (line_fft_kernel).  Restates slice_loop_onepass,
+    slice_loop_onepass_b, tap_order and the fast_ok of epilogue_x_pass (mslice.hip)"""
+    Rx, Ry = plan_radices(nx, ny, fft_path)
+    wx, wy = window if window else (nx, ny)
+    windowed = wx != nx or wy != ny
+    row_fft = "fast" if Ry else "generic"
+    column = "fast" if Rx and ny % 32 == 0 and (not windowed or wy % 32 == 0) else "generic"
+    if not one_pass:
+        return "two-pass", "natural", 0, row_fft, column
+    px, py, planned = grid_plan(nx, ny, fft_path)
+    assert planned, "no one-pass plan for this grid"
+    interleaves = lambda o: o.kind in ("fourstep", "two")
+    if px.kind == "fourstep" and py.kind == "fourstep":                 # slice_loop_onepass: the last pass runs along y, in place
+        along_y = not ((nz - 1 - k) & 1)
+        order = "interleaved" if k < nz - 2 else "natural"
+        rp = 32 if (Rx if along_y else Ry) == 32 else 16
+    else:                                                               # slice_loop_onepass_b: even passes along y
+        along_y = not (k & 1)
+        reader = px if along_y else py
+        if px.kind == "wave2k" and py.kind == "wave2k":
+            order, rp = "paired", 0
+        elif interleaves(px) and interleaves(py):
+            order, rp = "interleaved", 32 if reader.R == 32 else 16
+        else:
+            order, rp = "natural", 0
+    return "y" if along_y else "x", order, rp if order == "interleaved" else 0, row_fft, column
+
+
+def loop_bytes(nx, ny, nz, P, groups, n_taps, wpix, one_pass):
+    """algorithmic_bytes of one fused, tapped slice loop of `groups` frames (mslice.hip: count_slice_loop, layer_tap): the one-pass
+    loop moves 16 bytes per pixel and slice-step and its tap five images, the two-pass loop 32 and three"""
+    npix, images = nx * ny, P * groups
+    loop = images * nz * (16 if one_pass else 32) * npix + groups * nz * 8 * npix + images * 16 * npix
+    return loop + n_taps * images * (npix * 8 * (5 if one_pass else 3) + wpix * 8)
+
+
+def stored(spec, nx, ny, window=None, k_bin=None):
+    """full fftshifted spectra (..., nx, ny) -> what the engine stores: the k-window [n/2 - w/2, n/2 - w/2 + w) on both axes, then the
+    coherent sum of every bx x by block (the definition test_k_bin_is_a_block_sum_of_the_full_spectrum uses)"""
+    wx, wy = window if window else (nx, ny)
+    bx, by = k_bin if k_bin else (1, 1)
+    x0, y0 = nx // 2 - wx // 2, ny // 2 - wy // 2
+    win = spec[..., x0:x0 + wx, y0:y0 + wy]
+    return win.reshape(win.shape[:-2] + (wx // bx, bx, wy // by, by)).sum(axis=(-3, -1))
+
+
+@functools.lru_cache(maxsize=1)
+def output_data(nx, ny, nz, P, layers, frames):
+    """white probes, one white potential per batch slot and per slot the float64 (exit spectrum, {k: tap spectrum}), full size"""
+    probes, V = white_input(nx, ny, nz, P, frames=frames)
+    return probes, V, [reference(probes, V[b], nx, ny, nz, None, layers)[1:] for b in range(frames)]
+
+
+def output_case(nx, ny, nz, P=2, layers=(), window=None, k_bin=None, frame_batch=1, fft_path=0, wide=False):
+    """one engine, white probes, a white potential per batch slot: set_layers, propagate_frame / propagate_frames, layers_c64() and
+    wavefunction(), against the float64 reference cropped to the window and block-summed ->
+    dict(taps={(slot, k): (E_img, E_line, E_pix)}, exit={slot: (...)}, exit_is_last_block=bool, bytes=algorithmic_bytes of the loop,
+    one_pass=True / False / None (the byte count of the one-pass loop, of the two-pass loop, of neither)).
+    frame_batch = 2 adds cross={k or "exit": rel-L2 of slot 0 against slot 1's reference} (about sqrt 2); wide adds
+    wide_equal = layers_c128() is the complex64 blocks widened, bit for bit."""
+    layers, fb = tuple(layers), int(frame_batch)
+    probes, V, want = output_data(nx, ny, nz, P, layers, fb)
+    eng = engine(nx, ny, nz, P, n_frames=fb, fft_path=fft_path, frame_batch=fb, window=window, k_bin=k_bin)
+    try:
+        assert eng.frame_batch == fb
+        eng.upload_probes(probes)
+        for b in range(fb):
+            if fb > 1:
+                eng.select_batch_slot(b)
+            eng.upload_potential(V[b])
+        eng.set_layers(list(layers))
+        eng.reset_counters()
+        if fb > 1:
+            eng.propagate_frames(0, fb)
+        else:
+            eng.propagate_frame(0)
+        got = eng.layers_c64()                                  # (L, P, frames, wx, wy): the taps, then the exit
+        got_exit = eng.wavefunction()                           # (P, frames, wx, wy)
+        n_bytes = eng.counters()["algorithmic_bytes"]
+        got_wide = eng.layers_c128() if wide else None
+    finally:
+        eng.close()
+    wpix = got.shape[-2] * got.shape[-1]
+    res = dict(taps={}, exit={}, bytes=int(n_bytes), exit_is_last_block=bool(np.array_equal(got[len(layers)], got_exit)))
+    res["one_pass"] = {loop_bytes(nx, ny, nz, P, fb, len(layers), wpix, True): True,
+                       loop_bytes(nx, ny, nz, P, fb, len(layers), wpix, False): False}.get(res["bytes"])
+    ref = [(stored(w[0], nx, ny, window, k_bin), {k: stored(w[1][k], nx, ny, window, k_bin) for k in layers}) for w in want]
+    for b in range(fb):
+        for i, k in enumerate(layers):
+            res["taps"][(b, k)] = metrics(got[i][:, b], ref[b][1][k])
+        res["exit"][b] = metrics(got_exit[:, b], ref[b][0])
+    if fb > 1:
+        res["cross"] = {k: _rel_l2(got[i][:, 0], ref[1][1][k]) for i, k in enumerate(layers)}
+        res["cross"]["exit"] = _rel_l2(got_exit[:, 0], ref[1][0])
+    if wide:
+        res["wide_equal"] = bool(np.array_equal(got_wide, np.moveaxis(got, 0, -1).astype(np.complex128)))
+        res["wide_nonzero"] = float(np.count_nonzero(got_wide)) / got_wide.size
+    return res
+
+
+def tds_loop_bytes(nx, ny, nz, P, n_taps, wpix, n_det=1):
+    """algorithmic_bytes of one fused, tapped slice_loop_tds (56 bytes per pixel and slice-step, the weights once per slice)"""
+    npix = nx * ny
+    return P * nz * 56 * npix + nz * 8 * npix + P * 16 * npix + nz * n_det * 4 * npix + n_taps * P * (npix * 8 * 3 + wpix * 8)
+
+
+def tds_loop_case(nx, ny, nz, P=2, layers=None):
+    """the taps of slice_loop_tds: msl_set_tds needs an absorptive potential built from atoms, so the stack is a few atoms under
+    absorption, downloaded, and the float64 reference runs on the device's own t; the probes are white as everywhere here ->
+    dict(taps={k: metrics}, exit=metrics, tds_loop=bool: the byte count is that of slice_loop_tds)"""
+    import pyslice_amd as ps
+    from pyslice_amd.potentials import slice_edges
+    layers = tuple(range(nz - 1)) if layers is None else tuple(layers)
+    probes = white_input(nx, ny, nz, P)[0]
+    rng = np.random.default_rng(nx * 4099 + ny)
+    pos = rng.random((12, 3)) * [nx * DX, ny * DY, nz * DZ]
+    Z = np.where(np.arange(12) % 2, 14, 8).astype(np.int32)
+    eng = engine(nx, ny, nz, P)
+    try:
+        eng.set_kirkland(ps.loadKirkland())
+        eng.set_slices(*slice_edges(np.arange(nz) * DZ))
+        eng.set_absorption(np.full(103, 0.08), True)
+        eng.set_tds(np.ones((nx, ny), dtype=np.uint16), 1)
+        eng.build_potential(pos, Z)
+        eng.upload_probes(probes)
+        t = eng.transmission().astype(np.complex128)
+        eng.set_layers(list(layers))
+        eng.reset_counters()
+        eng.propagate_frame(0)
+        got = eng.layers_c64()[:, :, 0]
+        n_bytes = eng.counters()["algorithmic_bytes"]
+    finally:
+        eng.close()
+    ex, taps = propagate_tilted(probes, t, DX, DY, orc.wavelength(EV), DZ, Tilt(), layers=layers)
+    return dict(taps={k: metrics(got[i], _spectrum(taps[k])) for i, k in enumerate(layers)}, exit=metrics(got[len(layers)], _spectrum(ex)),
+                tds_loop=int(n_bytes) == tds_loop_bytes(nx, ny, nz, P, len(layers), nx * ny), t_range=float(np.abs(t - 1).max()))
+
+
+def case_bounds(c, k=None):
+    """bounds of a tap (k) or of the exit of an OutputCase: the white-noise contract, the two-pass one on the two-pass loop"""
+    tol = two_pass_tolerance(c.nx, c.ny) if c.fft_path else None
+    return bounds(c.nx, c.ny, c.nz, True, layer=k, tol=tol)
+
+
+def output_main(out_path):
+    """every OUT_* case -> the worst figures per list and tap path, in the form of main()'s report"""
+    worst, bad, n_cases = {}, 0, 0
+
+    def note(key, m, b, ok_extra=True):
+        nonlocal bad
+        ok = all(v <= lim for v, lim in zip(m, b)) and ok_extra
+        bad += not ok
+        w = worst.setdefault(key, [0.0] * 7)
+        for i in range(3):
+            w[i] = max(w[i], m[i])
+            w[3 + i] = max(w[3 + i], m[i] / b[i])
+        w[6] += 1
+        return " ".join(f"{v:.2e}" for v in m) + ("" if ok else " <-- ABOVE")
+
+    for lname, cases in OUTPUT_LISTS:
+        for c in cases:
+            res = output_case(*c)
+            n_cases += 1
+            line = f"{lname:13s} {output_id(c):44s} one-pass {res['one_pass']}"
+            for (b, k), m in sorted(res["taps"].items()):
+                lay = tap_layout(c.nx, c.ny, c.nz, k, bool(res["one_pass"]), c.window, c.fft_path)
+                path = "tap %s, %s, row %s, column %s" % (lay[0], lay[1] + (f" rp {lay[2]}" if lay[2] else ""), lay[3], lay[4])
+                line += f" | slot {b} tap {k} " + note((lname, path), m, case_bounds(c, k), res["one_pass"] == (not c.fft_path))
+            for b, m in sorted(res["exit"].items()):
+                line += f" | slot {b} exit " + note((lname, "exit"), m, case_bounds(c), res["exit_is_last_block"])
+            if "cross" in res:
+                bad += not min(res["cross"].values()) > 1.0
+                line += " | cross " + " ".join(f"{v:.2f}" for v in res["cross"].values())
+            print(line, flush=True)
+    for nx, ny, nz in OUT_TDS_LOOP_CASES:
+        res = tds_loop_case(nx, ny, nz)
+        n_cases += 1
+        tol = two_pass_tolerance(nx, ny)
+        for k, m in sorted(res["taps"].items()):
+            note(("tds loop", "tap two-pass, natural, row generic, column generic"), m, bounds(nx, ny, nz, True, layer=k, tol=tol), res["tds_loop"])
+        note(("tds loop", "exit"), res["exit"], bounds(nx, ny, nz, True, tol=tol))
+    wide = output_case(*OUT_WIDE_CASE, wide=True)
+    bad += not wide["wide_equal"]
+    rows = ["White-spectrum parity of the layer taps and the windowed, binned output (tools/white_parity.py --output-only): white-noise",
+            "probes through unit-modulus random phase screens, every tap and every stored spectrum against the float64 reference cropped to",
+            "the k-window and block-summed.  Worst figure per list and path of the tap (axis of the pass it reads, line order it gathers, row",
+            "FFT and column pass of the tap).  E_img, E_line, E_pix and 'of bound' as in white_spectrum_parity.txt: tol sqrt(n_t) x (1, 2, 10),",
+            "n_t = 2 k + 1 for the tap after slice k.  The bounds of tests/test_gpu_white_output.py are not taken from this file.", "",
+            f"{'list':13s} {'path':58s} {'n':>4s} {'E_img':>9s} {'E_line':>9s} {'E_pix':>9s}   of bound: img  line   pix"]
+    for (lname, path), w in sorted(worst.items()):
+        rows.append(f"{lname:13s} {path:58s} {int(w[6]):4d} {w[0]:9.2e} {w[1]:9.2e} {w[2]:9.2e}            {w[3]:5.2f} {w[4]:5.2f} {w[5]:5.2f}")
+    rows += ["", f"layers_c128() equals the complex64 blocks widened: {wide['wide_equal']} ({output_id(OUT_WIDE_CASE)})",
+             f"{n_cases} cases, {bad} results above their bound, on the wrong loop or not separated by batch slot"]
+    text = "\n".join(rows) + "\n"
+    print(text)
+    if out_path:
+        with open(out_path, "w") as f:
+            f.write(text)
+    return 1 if bad else 0
+
+
 if __name__ == "__main__":
+    if "--output-only" in sys.argv[1:]:
+        args = [a for a in sys.argv[1:] if a != "--output-only"]
+        sys.exit(output_main(args[0] if args else None))
     args = [a for a in sys.argv[1:] if a != "--tilt-only"]
     if "--tilt-only" in sys.argv[1:]:
         sys.exit(tilt_main(args[0] if args else None))
