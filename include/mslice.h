@@ -94,7 +94,9 @@ typedef enum {
     MSL_BUF_FORMFACTOR_ABS = 13, /* (n_species,nx,ny) f32 the absorptive tables g of the last build with msl_set_absorption(.., absorb != 0) */
     MSL_BUF_ABSORPTION = 14,   /* (nz,nx,ny) f32    Omega of the last build with msl_set_absorption(.., absorb != 0) */
     MSL_BUF_FORMFACTOR_TDS = 15, /* (n_det,n_species,nx,ny) f32 the detector-restricted tables g_det of the last build with msl_set_tds */
-    MSL_BUF_TDS_WEIGHT = 16    /* (n_det,nz,nx,ny) f32 the TDS weights w = 1 - exp(-2 sigma^2 Omega_det) of the last build with msl_set_tds */
+    MSL_BUF_TDS_WEIGHT = 16,   /* (n_det,nz,nx,ny) f32 the TDS weights w = 1 - exp(-2 sigma^2 Omega_det) of the last build with msl_set_tds */
+    MSL_BUF_FORMFACTOR_FINITE = 17 /* (n_species*(2R+1)*J,nx,ny) f32 the channel tables F_Z(k; alpha, beta) of the last build under
+                                * msl_set_projection(R, J), species-major, then m = -R J .. (R+1) J - 1; MSL_BUF_FORMFACTOR is then empty */
 } msl_buffer;
 
 typedef struct {
@@ -697,6 +699,31 @@ int  msl_reset_counters(msl_handle* h);
 /* Batched 2-D FFT self-test entry (parity tests of the FFT kernels alone): in/out host (B,nx,ny) c64,
  * dir=+1 forward / -1 inverse (1/(nx*ny) normalised), path as msl_config.fft_path. */
 int  msl_fft2_host(msl_handle* h, const float* in_c64, float* out_c64, int32_t batch, int32_t dir);
+
+/* ---- finite projection: atomic potentials spread over neighbouring slices ----
+ * Without it every build is an infinite projection: the whole projected form factor f_Z(k^2) of an atom goes to the one slice whose
+ * [lo, hi) holds its z.  With reach_slices = R > 0 and nodes = J every later msl_build_potential / msl_build_potentials /
+ * msl_build_thermal / msl_build_modes deposits in slice s the part of the atom's 3D Kirkland potential that lies in that slice
+ * (pyslice_amd/projection.py is the definition):
+ *   - slabs are uniform, slab s = [e0 + s dz, e0 + (s+1) dz) with dz the handle's dz and e0 = c_0 - dz/2 the lower edge the reference's
+ *     slice rule gives the interior slices (taken from the edges of msl_set_slices: lo[1] - dz; with one slice hi[0] - 3 dz / 2);
+ *   - each slab holds J node planes at spacing h = dz / J; an atom at z becomes two partial atoms on the nodes n0 = floor((z - e0) / h)
+ *     and n0 + 1 with the weights 1 - w and w, w = (z - e0) / h - n0 (total and z-centroid kept; w = 0: one atom);
+ *   - node n gives slab s, m = n - s J in [-R J, (R+1) J), the in-plane transform of the slab zeta in [-m h, -m h + dz) of the atom,
+ *         F_Z(k; a, b) = sum_j a_j / (2 kappa_j^2) [S(b, kappa_j) - S(a, kappa_j)] + c_j exp(-d_j k^2) 1/2 [erf(pi b / sqrt d_j) - erf(pi a / sqrt d_j)],
+ *         kappa_j = sqrt(k^2 + b_j),  S(zeta, kappa) = sgn(zeta) (1 - exp(-2 pi kappa |zeta|)),
+ *     with a = -infinity in the lowest slab reached and b = +infinity in the highest: the 2 R + 1 tables of a node sum to f_Z(k^2);
+ *   - an atom counts iff it counts without the option (lo[0] <= z < hi[nz-1], known species); what it would give to slabs below 0 or
+ *     above nz - 1 is dropped (as an atom that leaves the stack is dropped).
+ * The build makes n_species (2 R + 1) J channel tables (MSL_BUF_FORMFACTOR_FINITE) once per species list, and 2 (2 R + 1) weighted
+ * rows per atom through the sort, the phase tables and the structure factor of the ordinary build; the inverse transform and the
+ * slice loop are unchanged.  reach_slices = 0 (the default; nodes is then only stored) turns it off: the builds of a handle the call
+ * was never made on, bit for bit.  Every change of (R, J) makes the next build compute its tables again.
+ * MSL_ERR_INVALID: nodes outside [1, 16], reach_slices outside [0, 32].  MSL_ERR_UNSUPPORTED: while msl_set_absorption or msl_set_tds
+ * is set (and msl_set_absorption is MSL_ERR_UNSUPPORTED while this is on); at build time, when an interior slice is not dz thick.
+ * msl_get_projection: reach_nodes[0..1] = (reach_slices, nodes), (0, 1) before the first call.  Not in the reference. */
+int  msl_set_projection(msl_handle* h, int32_t reach_slices, int32_t nodes);
+int  msl_get_projection(const msl_handle* h, int32_t* reach_nodes);
 
 #ifdef __cplusplus
 }

@@ -17,7 +17,7 @@ ABI_VERSION = 3          # include/mslice.h: MSL_ABI_VERSION
 MSL_OK, MSL_ERR_INVALID, MSL_ERR_HIP, MSL_ERR_UNSUPPORTED, MSL_ERR_STATE, MSL_ERR_NOMEM = 0, -1, -2, -3, -4, -5
 (BUF_PROBES, BUF_EXIT, BUF_POTENTIAL, BUF_TRANSMISSION, BUF_WAVEFUNCTION, BUF_INTENSITY, BUF_FORMFACTOR,
  BUF_STREAM_ACC, BUF_STREAM_S1, BUF_STREAM_S2, BUF_STREAM_REF, BUF_LAYERS, BUF_SMATRIX, BUF_FORMFACTOR_ABS,
- BUF_ABSORPTION, BUF_FORMFACTOR_TDS, BUF_TDS_WEIGHT) = range(17)
+ BUF_ABSORPTION, BUF_FORMFACTOR_TDS, BUF_TDS_WEIGHT, BUF_FORMFACTOR_FINITE) = range(18)
 TDS_MAX_DETECTORS = 4      # include/mslice.h: msl_set_tds
 
 EXPORTS = [
@@ -47,6 +47,7 @@ EXPORTS = [
     "msl_set_bandlimit", "msl_get_bandlimit",
     "msl_set_absorption",
     "msl_set_tds", "msl_tds_fetch", "msl_tds_reduce",
+    "msl_set_projection", "msl_get_projection",
 ]
 DET_SIGNALS = {"intensity": 0, "amplitude": 1, "com_x": 2, "com_y": 3}      # include/mslice.h: MSL_DET_*
 POLAR_NONE, POLAR_MAX_BINS = 0xFFFF, 4096                                  # include/mslice.h: MSL_POLAR_*
@@ -176,6 +177,8 @@ def load():
         "msl_get_tilt": (C.c_int, [vp, vp]),
         "msl_set_bandlimit": (C.c_int, [vp, i32, i32]),
         "msl_get_bandlimit": (C.c_int, [vp, vp]),
+        "msl_set_projection": (C.c_int, [vp, i32, i32]),
+        "msl_get_projection": (C.c_int, [vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -355,6 +358,17 @@ class Engine:
         """(cut_x, cut_y) of the last set_bandlimit, (-1, -1) without a limit (msl_get_bandlimit)"""
         c = np.zeros(2, dtype=np.int32)
         self._chk(self._lib.msl_get_bandlimit(self._h, _ptr(c)))
+        return int(c[0]), int(c[1])
+
+    def set_projection(self, reach_slices, nodes=1):
+        """finite projection (msl_set_projection; the definition is projection.py): every later build spreads an atom's potential
+        over the reach_slices slices on either side of its own, z resolved on `nodes` planes per slice; reach_slices = 0 turns it off"""
+        self._chk(self._lib.msl_set_projection(self._h, int(reach_slices), int(nodes)))
+
+    def get_projection(self):
+        """(reach_slices, nodes) of the last set_projection, (0, 1) before the first (msl_get_projection)"""
+        c = np.zeros(2, dtype=np.int32)
+        self._chk(self._lib.msl_get_projection(self._h, _ptr(c)))
         return int(c[0]), int(c[1])
 
     def resize_probes(self, n_probes):
@@ -953,6 +967,10 @@ class Engine:
 
     def form_factors(self, n_species):
         return self.download(BUF_FORMFACTOR, np.float32, (n_species, self.nx, self.ny))
+
+    def form_factors_finite(self, n_channels):
+        """the channel tables (n_species * (2 R + 1) * J, nx, ny) of the last build under set_projection"""
+        return self.download(BUF_FORMFACTOR_FINITE, np.float32, (n_channels, self.nx, self.ny))
 
     def form_factors_abs(self, n_species):
         """the absorptive tables g of the last build with set_absorption(.., absorb=True)"""

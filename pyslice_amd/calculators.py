@@ -24,6 +24,7 @@ import numpy as np
 from . import _native, distributed
 from .aberrations import Aberrations
 from .bandlimit import as_bandlimit
+from .projection import as_projection
 from .multislice import Probe, interaction_sigma, wavelength
 from .prism import Prism, beams as prism_beams
 from .potentials import (TORCH_AVAILABLE, _as_tensor, _device_index, atomic_numbers_of, gridFromTrajectory, loadKirkland, slice_edges,
@@ -133,7 +134,8 @@ class MultisliceCalculator:
     def __init__(self, device=None, force_cpu=False, *, output="host", dtype="complex128", progress=True,
                  gather="rank0", cache=False, k_window=None, frame_batch=None, k_bin=None, stream_tile=None, layers=None,
                  detectors=None, probe_batch=None, diffraction=None, aberrations=None, imaging=None, prism=None,
-                 spectroscopy=None, polar=None, thickness=None, tilt=None, precession=None, tds=False, bandlimit=None):
+                 spectroscopy=None, polar=None, thickness=None, tilt=None, precession=None, tds=False, bandlimit=None,
+                 projection=None):
         """
         device / force_cpu: as the reference (calculators.py:41).  There is no CPU path here, so
         force_cpu=True raises.  Keyword-only extras (not in the reference):
@@ -254,6 +256,14 @@ class MultisliceCalculator:
                    aperture beyond it is a ValueError.  The exit spectrum is alias-free inside the band and not zero outside
                    it (bandlimit.propagate_bandlimited).  None: every output is bit for bit that of a run without the argument.
                    Not built with layers, thickness, tds, prism, cache, stream_tile or several ranks.
+          projection a projection.Projection(reach = 2.0 A, nodes = 4), or "finite" for that default: the finite projection of DESIGN.md
+                   section 4.26.  Every potential build deposits in a slice the part of each atom's 3D Kirkland potential that lies in
+                   it -- over R = ceil(reach / slice thickness) slices on either side, z resolved on `nodes` planes per slice
+                   (msl_set_projection) -- instead of the whole projected atom in the slice that holds its z.  setup() sets
+                   projection_slices (R) and projection_node_spacing (A).  The build costs about 2 (2 R + 1) times the infinite
+                   one; the slice loop is unchanged, so every run mode, MD trajectories, FrozenPhonons and PhononModes carry it.
+                   None or "infinite": every output is bit for bit that of a run without the argument.  Refused (ValueError): an
+                   AbsorptivePotential, tds, cache, stream_tile, several ranks.
         """
         if force_cpu:
             raise NotImplementedError("pyslice_amd has no CPU path (force_cpu=True): use the reference for CPU runs")
@@ -407,6 +417,15 @@ class MultisliceCalculator:
                 if val:
                     raise NotImplementedError(f"bandlimit: {what} is not built")
         self.band_limit_mrad = None             # setup(): the largest scattering angle the band limit keeps
+        self._projection = as_projection(projection)
+        if self._projection is not None:
+            # tds: its tables are those of the absorptive potential; cache: the key does not carry the projection; stream_tile: the
+            # streaming run shards frames over ranks with engines of its own set-up
+            for what, val in (("tds", self._tds), ("cache", cache), ("stream_tile", stream_tile is not None)):
+                if val:
+                    raise ValueError(f"projection cannot be combined with {what}")
+        self.projection_slices = None           # setup(): R, the reach in slices
+        self.projection_node_spacing = None     # setup(): dz / nodes in Angstrom
         self._precessing = False                # inside the tilt loop of a precession run
         self._layers = None                     # validated slice indices (setup), nz - 1 last
         self._engine = None
@@ -475,6 +494,12 @@ class MultisliceCalculator:
                               ("spectroscopy (one frame has no spectrum)", self._spectroscopy is not None)):
                 if val:
                     raise NotImplementedError(f"absorptive potential: {what} is not built")
+        if getattr(self, "_projection", None) is not None:
+            if self._absorptive is not None:
+                raise ValueError("projection cannot be combined with an AbsorptivePotential: its Debye-Waller and absorptive tables are "
+                                 "infinite projections")
+            if distributed.rank_world()[1] > 1:
+                raise ValueError("projection cannot be combined with a run over several ranks")
         if getattr(self, "_tds", False):
             if self._absorptive is None or not self._absorptive.absorption:
                 raise ValueError("tds=True needs an absorptive.AbsorptivePotential(absorption=True) in setup(): the TDS signal is what "
@@ -710,6 +735,15 @@ class MultisliceCalculator:
         # slice coordinates follow the slice axis (potentials.py:241-245); the Fresnel step uses zs (multislice.py:266)
         self._slice_coords = np.asarray([self.xs, self.ys, self.zs][slice_axis], dtype=np.float64)
         self._dz = self.zs[1] - self.zs[0] if self.nz > 1 else 0.5
+        if getattr(self, "_projection", None) is not None:
+            # the slabs are the slices: their thickness is the spacing of the slice coordinates, which must be the engine's dz
+            sc = self._slice_coords
+            spacing = float(sc[1] - sc[0]) if len(sc) > 1 else 0.5
+            if abs(spacing - self._dz) > 1e-9 * abs(self._dz):
+                raise ValueError(f"projection: slice_axis={slice_axis} gives slices {spacing:g} A thick but the propagator steps "
+                                 f"{self._dz:g} A (the spacing of zs): the finite projection needs the two equal")
+            self.projection_slices = self._projection.reach_slices(spacing)
+            self.projection_node_spacing = spacing / self._projection.nodes
         self._Z = (atomic_numbers_of(trajectory.atom_types) if (self._generated is not None or self._absorptive is not None)
                    else np.asarray(trajectory.atom_types, dtype=np.int32))
         # A previous run's WFData (and zero-copy device views of its buffers) may still hold the old engine: drop our
@@ -861,6 +895,8 @@ class MultisliceCalculator:
             eng.set_tilt(*self._tilt.tangents)
         if self._bl_cuts is not None:                           # (no limit: no call, the tables and the builds of today)
             eng.set_bandlimit(*self._bl_cuts)
+        if self._projection is not None:                        # before the first build: its tables are the channel tables
+            eng.set_projection(self.projection_slices, self._projection.nodes)
         if self._absorptive is not None:                        # before the first build: its tables are f D and g
             eng.set_absorption(self._absorptive.u_by_Z, self._absorptive.absorption)
         src = self._generated

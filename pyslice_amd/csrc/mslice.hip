@@ -19,6 +19,7 @@
 #include "rowtm_pass.h"
 #include "potential.h"
 #include "absorptive.h"
+#include "finite.h"
 #include "tds.h"
 #include "thermal.h"
 #include "phonons.h"
@@ -255,6 +256,14 @@ struct msl_handle {
     int n_species = 0;
     int ff_species[104] = {0};     // species list the resident form-factor table was computed for (frame-invariant: computed once per run)
     int ff_n = 0;
+    // finite projection (msl_set_projection, finite.h): reach in slices (0 = off) and nodes per slice; while it is
+    // on, d_ff holds the fin_nch = species x (2 R + 1) J channel tables made for the slab thickness ff_dz, every atom becomes
+    // 2 (2 R + 1) weighted rows (d_wgt next to d_u1 / d_u2) and the bins are (frame, slice, channel).  h_lo / h_hi: the host's copy of
+    // the slice edges (the slab lattice and the build-time check of the interior slices)
+    int fin_R = 0, fin_J = 1, fin_nch = 0;
+    double ff_dz = 0.0;
+    DevBuf<float> d_wgt;
+    std::vector<double> h_lo, h_hi;
     // absorptive potential (msl_set_absorption, absorptive.h): the rms width per atomic number on the host and the device; while
     // abs_on, d_ff holds f D and d_ffa the absorptive tables g (abs_absorb), and every build goes through the two real stacks abs_V
     // (Vbar) and abs_O (Omega), (FB, nz, nx, ny) float32, allocated by the first such build and released when absorption is cleared.
@@ -1276,10 +1285,11 @@ int slice_loop_onepass(msl_handle* h, int fused_slot, int groups, int first_grou
 
 // n atoms of a frame group; `rows` rows of the sorted phase tables (the atoms plus the padding of every bin to SF_ALIGN rows)
 int ensure_atoms(msl_handle* h, size_t n, size_t rows) {
-    if (rows <= h->atom_cap) return MSL_OK;
+    int rc;
+    if (rows <= h->atom_cap) return (h->fin_R > 0 && h->d_wgt.n < h->atom_cap) ? h->d_wgt.alloc(h, h->atom_cap) : MSL_OK;
     (void)n;
     size_t cap = std::max<size_t>(rows, h->atom_cap * 3 / 2 + 1024);
-    int rc;
+    if (h->fin_R > 0 && (rc = h->d_wgt.alloc(h, cap))) return rc;         // (the weight of every row of a finite-projection build)
     if ((rc = h->d_pos.alloc(h, cap * 3)) || (rc = h->d_Z.alloc(h, cap)) || (rc = h->d_key.alloc(h, cap)) || (rc = h->d_order.alloc(h, cap)) ||
         (rc = h->d_u1.alloc(h, cap)) || (rc = h->d_u2.alloc(h, cap))) return rc;
     // phase tables: the quadrant kernel reads the columns 0 .. n/2 only
@@ -1567,10 +1577,13 @@ struct PotGroup {
     int z2s[104], species[104], nsp;    // species present, sorted ascending like np.unique: z2s[Z] = index into species, -1 where Z does not occur
     int64_t n; int32_t ax1, ax2, axs;   // atoms per frame; the axes the caller's positions are read along
     int keys_per_frame;             // (slice, species) bins per frame
+    // finite projection: rep = 2 (2 R + 1) rows per atom and ntab = nsp (2 R + 1) J channel tables; without it rep = 1 and ntab = nsp.
+    // The tables are the "species" of the sort and of the structure factor; z2s / species stay indexed by species
+    int rep, ntab; bool finite;
     int cx, cy; float vscale;       // table columns the quadrant kernel reads: the frequencies 0 .. n/2
     bool half_rows, sf_stream;      // pot_half_rows; many atoms per bin: the streaming structure-factor kernel, whose bins are padded to whole half-trips
     int g, slot, n_slices, nkeys;   // frames, first batch slot, slices and bins of the group
-    long long rows, rows_pad;       // atoms of the group; sorted table rows at most: every bin padded to SF_ALIGN
+    long long rows, rows_pad;       // rows (atoms x rep) of the group; sorted table rows at most: every bin padded to SF_ALIGN
     float2* TR; float2* TRT;        // batch slots this group's stacks go to (trans, transT)
 };
 
@@ -1598,7 +1611,7 @@ int stage_atoms(msl_handle* h, const PotGroup& p, const double* pos, const int32
     msl_handle::HostStage& st = h->stage[h->stage_pos++ & 1];
     if (!st.ev) HIPCHK(h, hipEventCreateWithFlags(&st.ev, hipEventDisableTiming));
     if (st.used) HIPCHK(h, hipEventSynchronize(st.ev));            // the copies queued from this slot two calls ago
-    const size_t z_bytes = (size_t)p.n * sizeof(int), pos_bytes = (size_t)p.rows * 3 * sizeof(double);
+    const size_t z_bytes = (size_t)p.n * sizeof(int), pos_bytes = (size_t)p.n * p.g * 3 * sizeof(double);
     const size_t off_sp = sizeof p.z2s, off_Z = (off_sp + sizeof p.species + 7) & ~(size_t)7;
     const size_t off_pos = (off_Z + z_bytes + 7) & ~(size_t)7, need = off_pos + pos_bytes;
     if (need > st.bytes) {
@@ -1642,7 +1655,7 @@ int stage_resident_maps(msl_handle* h, const PotGroup& p) {
 int stage_thermal(msl_handle* h, const PotGroup& p, uint64_t seed, uint64_t first_config, bool send_maps) {
     int rc;
     if (send_maps && (rc = stage_resident_maps(h, p))) return rc;
-    hipLaunchKernelGGL(thermal_positions_kernel, dim3((unsigned)((p.rows + 255) / 256)), dim3(256), 0, h->stream, h->th_pos0, h->th_sigma,
+    hipLaunchKernelGGL(thermal_positions_kernel, dim3((unsigned)(((long long)p.n * p.g + 255) / 256)), dim3(256), 0, h->stream, h->th_pos0, h->th_sigma,
                        (long long)p.n, p.g, (unsigned long long)seed, (unsigned long long)first_config, h->d_pos);
     HIPCHK(h, hipGetLastError());
     return MSL_OK;
@@ -1691,27 +1704,45 @@ int bin_atoms(msl_handle* h, const PotGroup& p) {
     const double lx = c.nx * c.dx, ly = c.ny * c.dy;
     // f_Z(q^2) depends on the grid and the species only (potentials.py:283-293 recomputes it per frame): build the table
     // when the species list changes, i.e. once per run
-    if (nsp != h->ff_n || memcmp(p.species, h->ff_species, nsp * sizeof(int)) != 0) {
+    if (nsp != h->ff_n || memcmp(p.species, h->ff_species, nsp * sizeof(int)) != 0 || (p.finite && h->ff_dz != c.dz)) {
         long long tot = (long long)c.nx * c.ny * nsp;
-        if (!h->abs_on)                                  // (absorptive_tables writes f D there itself)
+        if (p.finite) {                                  // the channel tables, once per (species list, grid, R, J, slab thickness)
+            const long long tot_ch = (long long)c.nx * c.ny * p.ntab;
+            hipLaunchKernelGGL(finite_formfactor_kernel, dim3((unsigned)((tot_ch + 255) / 256)), dim3(256), 0, h->stream, h->d_ff, h->d_abcd,
+                               h->d_species, nsp, h->fin_R, h->fin_J, c.dz, c.nx, c.ny, 1.0 / lx, 1.0 / ly);
+            h->ff_dz = c.dz;
+        } else if (!h->abs_on)                           // (absorptive_tables writes f D there itself)
             hipLaunchKernelGGL(formfactor_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, h->stream, h->d_ff, h->d_abcd,
                                h->d_species, nsp, c.nx, c.ny, 1.0 / lx, 1.0 / ly);
         memcpy(h->ff_species, p.species, nsp * sizeof(int));
         h->ff_n = nsp;
         if (h->abs_on) { const int rc = absorptive_tables(h, nsp); if (rc) { h->ff_n = 0; return rc; } }
     }
-    hipLaunchKernelGGL(atom_prep_kernel, dim3((unsigned)((p.rows + 255) / 256)), dim3(256), 0, h->stream, h->d_pos, h->d_Z,
-                       (long long)p.n, p.g, h->d_z2s, h->d_lo, h->d_hi, c.nz, nsp, p.ax1, p.ax2, p.axs, 1.0 / lx, 1.0 / ly, h->d_key,
-                       h->d_u1, h->d_u2, h->d_counts);
+    const long long atoms = (long long)p.n * p.g;
+    if (p.finite) {
+        // the slab lattice of the reference's slice rule: slab 0 = [c_0 - dz/2, c_0 + dz/2) although slice 0 counts atoms from lo[0] on
+        const double dz = c.dz;
+        const double e0 = c.nz > 1 ? h->h_lo[1] - dz : h->h_hi[0] - 1.5 * dz;
+        hipLaunchKernelGGL(atom_prep_finite_kernel, dim3((unsigned)((atoms + 255) / 256)), dim3(256), 0, h->stream, h->d_pos, h->d_Z,
+                           (long long)p.n, p.g, h->d_z2s, h->h_lo[0], h->h_hi[c.nz - 1], e0, dz / h->fin_J, c.nz, nsp, h->fin_R, h->fin_J,
+                           p.ax1, p.ax2, p.axs, 1.0 / lx, 1.0 / ly, h->d_key, h->d_wgt, h->d_u1, h->d_u2, h->d_counts);
+    } else
+        hipLaunchKernelGGL(atom_prep_kernel, dim3((unsigned)((atoms + 255) / 256)), dim3(256), 0, h->stream, h->d_pos, h->d_Z,
+                           (long long)p.n, p.g, h->d_z2s, h->d_lo, h->d_hi, c.nz, nsp, p.ax1, p.ax2, p.axs, 1.0 / lx, 1.0 / ly, h->d_key,
+                           h->d_u1, h->d_u2, h->d_counts);
     hipLaunchKernelGGL(bin_scan_kernel, dim3(1), dim3(1024), 0, h->stream, h->d_counts, h->d_start, p.nkeys, p.sf_stream ? SF_ALIGN : 1);
-    hipLaunchKernelGGL(bin_fill_kernel, dim3(p.nkeys), dim3(1024), 0, h->stream, h->d_key, (long long)p.n, p.keys_per_frame, h->d_start, h->d_order);
+    hipLaunchKernelGGL(bin_fill_kernel, dim3(p.nkeys), dim3(1024), 0, h->stream, h->d_key, (long long)p.n * p.rep, p.keys_per_frame, h->d_start, h->d_order);
     HIPCHK(h, hipGetLastError());
     // atoms that fell into a slice: d_start[nkeys], read by the kernels themselves (grids sized for all atoms of the group)
     const int* n_sorted = h->d_start + p.nkeys;
     if (p.rows_pad > 0x7fffffffLL) return fail(h, MSL_ERR_INVALID, "msl_build_potentials: %lld padded table rows in one group exceed 2^31", p.rows_pad);
     const long long tx = p.rows_pad * p.cx, ty = p.rows_pad * p.cy;
-    hipLaunchKernelGGL(phase_table_kernel, dim3((unsigned)((tx + 255) / 256)), dim3(256), 0, h->stream, h->d_ex, h->d_u1,
-                       h->d_order, n_sorted, c.nx, p.cx, p.cx);
+    if (p.finite)                                        // the weight of the partial atom rides on the x table alone
+        hipLaunchKernelGGL(phase_table_weighted_kernel, dim3((unsigned)((tx + 255) / 256)), dim3(256), 0, h->stream, h->d_ex, h->d_u1,
+                           h->d_wgt, h->d_order, n_sorted, c.nx, p.cx, p.cx);
+    else
+        hipLaunchKernelGGL(phase_table_kernel, dim3((unsigned)((tx + 255) / 256)), dim3(256), 0, h->stream, h->d_ex, h->d_u1,
+                           h->d_order, n_sorted, c.nx, p.cx, p.cx);
     hipLaunchKernelGGL(phase_table_kernel, dim3((unsigned)((ty + 255) / 256)), dim3(256), 0, h->stream, h->d_ey, h->d_u2,
                        h->d_order, n_sorted, c.ny, p.cy, p.cy);
     return MSL_OK;
@@ -1723,7 +1754,7 @@ int bin_atoms(msl_handle* h, const PotGroup& p) {
 int launch_structure_factor(msl_handle* h, const PotGroup& p, const float* table = nullptr) {
     const msl_config& c = h->cfg;
     const float* ff = table ? table : h->d_ff.p;             // (the absorptive build runs it a second time, on d_ffa)
-    const int cx = p.cx, cy = p.cy, nsp = p.nsp, n_slices = p.n_slices, full_rows = p.half_rows ? 0 : 1;
+    const int cx = p.cx, cy = p.cy, nsp = p.ntab, n_slices = p.n_slices, full_rows = p.half_rows ? 0 : 1;     // (channel tables as species)
     const bool edge_x = (c.nx % 2 == 0) && (cx % 32 == 1) && cx > 1, edge_y = (c.ny % 2 == 0) && (cy % 32 == 1) && cy > 1;
     const int tiles_x = edge_x ? cx / 32 : (cx + 31) / 32, tiles_y = edge_y ? cy / 32 : (cy + 31) / 32;
     const int n_tiles = tiles_x * tiles_y, wg_per_slice = (n_tiles + 3) / 4;
@@ -2331,6 +2362,8 @@ int msl_set_absorption(msl_handle* h, const double* u_by_Z, int32_t absorb) {
     for (int z = 0; u_by_Z && z < 103; ++z)
         if (!std::isfinite(u_by_Z[z]) || !(u_by_Z[z] >= 0.0))
             return fail(h, MSL_ERR_INVALID, "msl_set_absorption: width %g of atomic number %d is not a finite number >= 0", u_by_Z[z], z + 1);
+    if (u_by_Z && h->fin_R > 0)
+        return fail(h, MSL_ERR_UNSUPPORTED, "msl_set_absorption: absorptive tables are not built under finite projection (msl_set_projection)");
     HIPCHK(h, hipSetDevice(h->cfg.device));
     HIPCHK(h, hipStreamSynchronize(h->stream));          // a queued build still reads the tables and the stacks
     h->ff_n = 0;                                         // d_ff holds f or f D: the next build makes its table again
@@ -2403,13 +2436,29 @@ int build_potentials(msl_handle* h, const double* pos, const int32_t* Z, int64_t
     // with launch timing off the call only queues work: no event, no host wait (the frames of a run pipeline on the stream)
     EventPair timer;
     if (c.launch_timing && (rc = timer.begin(h))) return rc;
-    if (p.nsp > h->ff_species_cap) {
-        if ((rc = h->d_ff.alloc(h, npix * p.nsp))) return rc;
-        h->ff_species_cap = p.nsp;
+    // finite projection: every atom is rep weighted rows, every species (2 R + 1) J channel tables
+    p.finite = h->fin_R > 0;
+    p.rep = p.finite ? 2 * (2 * h->fin_R + 1) : 1;
+    p.ntab = p.finite ? p.nsp * (2 * h->fin_R + 1) * h->fin_J : p.nsp;
+    if (p.finite) {
+        if (h->abs_on) return fail(h, MSL_ERR_UNSUPPORTED, "finite projection: absorptive or TDS tables are not built with it");
+        if ((int)h->h_lo.size() != c.nz) return fail(h, MSL_ERR_STATE, "finite projection: msl_set_slices has not been called");
+        for (int s = 1; s + 1 < c.nz; ++s)
+            if (!(std::fabs((h->h_hi[s] - h->h_lo[s]) - c.dz) <= 1e-9 * std::fabs(c.dz)))
+                return fail(h, MSL_ERR_UNSUPPORTED, "finite projection: slice %d is %.12g thick, the handle's dz is %.12g (uniform slices only)",
+                            s, h->h_hi[s] - h->h_lo[s], c.dz);
+        if (!(c.dz > 0)) return fail(h, MSL_ERR_UNSUPPORTED, "finite projection: dz must be positive");
+        if ((long long)n * p.rep > 0x7fffffffLL || (long long)c.nz * p.ntab * std::max(1, count) > 0x7fffffffLL)
+            return fail(h, MSL_ERR_UNSUPPORTED, "finite projection: %lld rows per frame or %lld bins exceed 2^31", (long long)n * p.rep,
+                        (long long)c.nz * p.ntab * count);
+    }
+    if (p.ntab > h->ff_species_cap) {
+        if ((rc = h->d_ff.alloc(h, npix * p.ntab))) return rc;
+        h->ff_species_cap = p.ntab;
         h->ff_n = 0;
     }
     p.n = n; p.ax1 = ax1; p.ax2 = ax2; p.axs = axs;
-    p.cx = c.nx / 2 + 1; p.cy = c.ny / 2 + 1; p.keys_per_frame = c.nz * std::max(p.nsp, 1);
+    p.cx = c.nx / 2 + 1; p.cy = c.ny / 2 + 1; p.keys_per_frame = c.nz * std::max(p.ntab, 1);
     p.half_rows = pot_half_rows(h);
     if (h->abs_on) {
         // the absorptive build inverse-transforms with ifft_inplace's passes whatever pot_ifft is: half rows where those mirror them
@@ -2424,23 +2473,24 @@ int build_potentials(msl_handle* h, const double* pos, const int32_t* Z, int64_t
             HIPCHK(h, hipMemsetAsync(h->abs_O, 0, stacks * sizeof(float), h->stream));
         }
     }
-    p.sf_stream = (double)n / std::max(1, p.keys_per_frame) >= 128.0 && !dbg_env("MSL_SF_TILED");
+    const size_t frame_rows = (size_t)n * p.rep;            // rows of the sort and of the phase tables per frame
+    p.sf_stream = (double)frame_rows / std::max(1, p.keys_per_frame) >= 128.0 && !dbg_env("MSL_SF_TILED");
     p.vscale = (float)(1.0 / ((double)c.nx * c.ny) / (c.dx * c.dx * c.dy * c.dy));
     // frames per group: the phase tables of a group (n atoms x (nx/2 + 1 + ny/2 + 1) x 8 bytes per frame) stay under 6 GB
-    const size_t table_bytes_per_frame = std::max<size_t>(1, (size_t)n * (size_t)(p.cx + p.cy) * sizeof(float2));
+    const size_t table_bytes_per_frame = std::max<size_t>(1, frame_rows * (size_t)(p.cx + p.cy) * sizeof(float2));
     const int G = (int)std::max<size_t>(1, std::min<size_t>((size_t)count, (size_t)6e9 / table_bytes_per_frame));
     const int nkeys_cap = p.keys_per_frame * G;
     if (nkeys_cap > h->keys_cap) {
         if ((rc = h->d_counts.alloc(h, (size_t)nkeys_cap + 1)) || (rc = h->d_start.alloc(h, (size_t)nkeys_cap + 1))) return rc;
         h->keys_cap = nkeys_cap;
     }
-    if ((rc = ensure_atoms(h, (size_t)n * G, (size_t)n * G + (size_t)(SF_ALIGN - 1) * nkeys_cap))) return rc;
+    if ((rc = ensure_atoms(h, frame_rows * G, frame_rows * G + (size_t)(SF_ALIGN - 1) * nkeys_cap))) return rc;
     for (int f0 = 0; f0 < count; f0 += G) {
         p.g = std::min(G, count - f0); p.slot = first_slot + f0;
         p.TR = h->trans + (size_t)p.slot * c.nz * npix;
         p.TRT = h->transT ? h->transT + (size_t)p.slot * c.nz * npix : nullptr;
         p.n_slices = c.nz * p.g; p.nkeys = p.keys_per_frame * p.g;
-        p.rows = (long long)n * p.g; p.rows_pad = p.rows + (long long)(SF_ALIGN - 1) * p.nkeys;
+        p.rows = (long long)frame_rows * p.g; p.rows_pad = p.rows + (long long)(SF_ALIGN - 1) * p.nkeys;
         if (n > 0 && p.nsp > 0) {
             rc = !th ? stage_atoms(h, p, pos + (size_t)f0 * n * 3, Z, f0 == 0)
                  : th->modes ? stage_modes(h, p, th->seed, th->first + (uint64_t)f0, f0 == 0)
@@ -2452,6 +2502,7 @@ int build_potentials(msl_handle* h, const double* pos, const int32_t* Z, int64_t
         if ((rc = h->abs_on ? absorptive_group(h, p, n > 0 && p.nsp > 0) : potential_ifft(h, p))) return rc;
     }
     h->n_species = p.nsp;
+    h->fin_nch = p.finite ? p.ntab : 0;
     if (h->set.bl_on && (rc = bandlimit_built(h, first_slot, count))) return rc;
     if ((rc = timer.end(h, &h->ctr.ms_potential))) return rc;
     h->have_potential = true;
@@ -2833,7 +2884,30 @@ int msl_set_slices(msl_handle* h, const double* lo, const double* hi) {
     HIPCHK(h, hipMemcpyAsync(h->d_lo, lo, h->cfg.nz * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemcpyAsync(h->d_hi, hi, h->cfg.nz * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
+    h->h_lo.assign(lo, lo + h->cfg.nz);
+    h->h_hi.assign(hi, hi + h->cfg.nz);
     h->have_slices = true;
+    return MSL_OK;
+}
+
+// finite projection
+int msl_set_projection(msl_handle* h, int32_t reach_slices, int32_t nodes) {
+    if (!h) return fail(h, MSL_ERR_INVALID, "msl_set_projection: null handle");
+    if (nodes < 1 || nodes > 16) return fail(h, MSL_ERR_INVALID, "msl_set_projection: %d nodes per slice outside [1, 16]", nodes);
+    if (reach_slices < 0 || reach_slices > 32) return fail(h, MSL_ERR_INVALID, "msl_set_projection: a reach of %d slices outside [0, 32]", reach_slices);
+    if (reach_slices > 0 && (h->abs_on || h->tds_on))
+        return fail(h, MSL_ERR_UNSUPPORTED, "msl_set_projection: absorptive and TDS tables are not built under finite projection");
+    if (reach_slices == h->fin_R && (reach_slices == 0 || nodes == h->fin_J)) { h->fin_J = nodes; return MSL_OK; }     // nothing changes
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));          // a queued build still reads the tables
+    h->fin_R = reach_slices; h->fin_J = nodes;
+    h->ff_n = 0;                                         // d_ff holds f or the channel tables: the next build makes its table again
+    return MSL_OK;
+}
+
+int msl_get_projection(const msl_handle* h, int32_t* reach_nodes) {
+    if (!h || !reach_nodes) return MSL_ERR_INVALID;
+    reach_nodes[0] = h->fin_R; reach_nodes[1] = h->fin_J;
     return MSL_OK;
 }
 
@@ -3611,7 +3685,8 @@ size_t msl_buffer_bytes(const msl_handle* h, msl_buffer what) {
         case MSL_BUF_TRANSMISSION: return npix * c.nz * 8;
         case MSL_BUF_WAVEFUNCTION: return h->wf ? h->wpitch * c.n_probes * c.n_frames * 8 : 0;
         case MSL_BUF_INTENSITY: return h->intensity.n * 4;
-        case MSL_BUF_FORMFACTOR: return npix * h->n_species * 4;
+        case MSL_BUF_FORMFACTOR: return h->fin_nch ? 0 : npix * h->n_species * 4;      // (under finite projection d_ff holds the channel tables)
+        case MSL_BUF_FORMFACTOR_FINITE: return (h->fin_nch && h->ff_n > 0) ? npix * (size_t)h->fin_nch * 4 : 0;
         case MSL_BUF_STREAM_ACC: return (h->st_open && h->st_acc) ? h->wpix * c.n_probes * (size_t)h->st_F * 8 : 0;
         case MSL_BUF_STREAM_S1: return (h->st_open && h->st_s1) ? h->wpix * c.n_probes * 16 : 0;
         case MSL_BUF_STREAM_S2: return (h->st_open && h->st_s2) ? h->wpix * c.n_probes * 8 : 0;
@@ -3643,6 +3718,7 @@ void* msl_device_ptr(msl_handle* h, msl_buffer what) {
         case MSL_BUF_WAVEFUNCTION: return h->wf;
         case MSL_BUF_INTENSITY: return h->intensity;
         case MSL_BUF_FORMFACTOR: return h->d_ff;
+        case MSL_BUF_FORMFACTOR_FINITE: return h->fin_nch ? h->d_ff.p : nullptr;
         case MSL_BUF_STREAM_ACC: return h->st_open ? h->st_acc.p : nullptr;
         case MSL_BUF_STREAM_S1: return h->st_open ? h->st_s1.p : nullptr;
         case MSL_BUF_STREAM_S2: return h->st_open ? h->st_s2.p : nullptr;

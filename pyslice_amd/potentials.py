@@ -144,7 +144,11 @@ def _as_tensor(a):
 
 
 class Potential:
-    def __init__(self, xs, ys, zs, positions, atomTypes, kind="kirkland", device=None, slice_axis=2):
+    def __init__(self, xs, ys, zs, positions, atomTypes, kind="kirkland", device=None, slice_axis=2, projection=None):
+        """projection (not in the reference): a projection.Projection or "finite" -- the slab-integrated potential of DESIGN.md
+        section 4.26 instead of the infinite projection; None / "infinite": the build of a call without the argument."""
+        from .projection import as_projection
+        projection = as_projection(projection, "Potential: projection")
         if kind != "kirkland":
             raise NotImplementedError("only kind='kirkland' is implemented (the reference's 'gauss' branch is dead code)")
         xs = np.asarray(xs, dtype=np.float64)
@@ -169,11 +173,17 @@ class Potential:
         self._nx, self._ny, self._dz = nx, ny, dz
         # The beam is unknown here (the reference's Potential takes no energy): sigma = 0 now,
         # Propagate() calls set_beam() and the library re-derives exp(i sigma V) from the kept V.
-        self._engine = _native.Engine(nx, ny, self.n_slices, dx, dy, dz, wavelength=1.0, sigma=0.0, n_probes=1,
-                                      n_frames=0, device=_device_index(device), keep_potential=True)
+        # (the engine's dz is the propagator's, which Propagate() sets again; under finite projection it is the slab thickness of the build)
+        self._engine = _native.Engine(nx, ny, self.n_slices, dx, dy, dz if projection is None else self.slice_spacing, wavelength=1.0,
+                                      sigma=0.0, n_probes=1, n_frames=0, device=_device_index(device), keep_potential=True)
         self._engine.set_kirkland(loadKirkland())
         lo, hi = slice_edges(np.asarray(self.slice_coords, dtype=np.float64))
         self._engine.set_slices(lo, hi)
+        self.projection = projection
+        if projection is not None:
+            self.projection_slices = projection.reach_slices(self.slice_spacing)
+            self.projection_node_spacing = self.slice_spacing / projection.nodes
+            self._engine.set_projection(self.projection_slices, projection.nodes)
         self._engine.build_potential(np.asarray(positions, dtype=np.float64), atomic_numbers_of(atomTypes), slice_axis)
         self._array = None
 
