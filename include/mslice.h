@@ -95,8 +95,9 @@ typedef enum {
     MSL_BUF_ABSORPTION = 14,   /* (nz,nx,ny) f32    Omega of the last build with msl_set_absorption(.., absorb != 0) */
     MSL_BUF_FORMFACTOR_TDS = 15, /* (n_det,n_species,nx,ny) f32 the detector-restricted tables g_det of the last build with msl_set_tds */
     MSL_BUF_TDS_WEIGHT = 16,   /* (n_det,nz,nx,ny) f32 the TDS weights w = 1 - exp(-2 sigma^2 Omega_det) of the last build with msl_set_tds */
-    MSL_BUF_FORMFACTOR_FINITE = 17 /* (n_species*(2R+1)*J,nx,ny) f32 the channel tables F_Z(k; alpha, beta) of the last build under
+    MSL_BUF_FORMFACTOR_FINITE = 17, /* (n_species*(2R+1)*J,nx,ny) f32 the channel tables F_Z(k; alpha, beta) of the last build under
                                 * msl_set_projection(R, J), species-major, then m = -R J .. (R+1) J - 1; MSL_BUF_FORMFACTOR is then empty */
+    MSL_BUF_IONIZATION_WEIGHT = 18 /* (n,nz,nx,ny) f32  the ionisation weights W_e,s of the last build with msl_set_ionization */
 } msl_buffer;
 
 typedef struct {
@@ -351,6 +352,34 @@ int  msl_set_absorption(msl_handle* h, const double* u_by_Z_103, int32_t absorb)
 int  msl_set_tds(msl_handle* h, const uint16_t* member_bits, int32_t n_det);
 int  msl_tds_fetch(msl_handle* h, int32_t B, double* out);
 int  msl_tds_reduce(msl_handle* h, int32_t slice, int32_t reps, double* out, double* ms_reduce);
+
+/* ---- element maps: channelling-weighted ionisation signal per element ----
+ * What an EDX or core-loss EELS map records, in the local approximation (pyslice_amd/ionization.py is the definition): per channel e
+ * -- an atomic number Z_e, a Gaussian of rms width w_e (Angstrom) and a cross-section c_e (Angstrom^2) -- and slice s, with A_e,s
+ * the atoms of that element the build puts into slice s (its own slice rule),
+ *     W_e,s(r) = Re ifft2( c_e exp(-2 pi^2 w_e^2 |k|^2) sum_{i in A_e,s} exp(-2 pi i k r_i) ) / (dx dy)      (sum_r W dx dy = c_e |A_e,s|)
+ *     I[p, e, s] = sum_r |psi_p,s(r)|^2 W_e,s(r) / sum_r |psi_p,0(r)|^2,       psi_p,s = the wave arriving at slice s
+ * the ionisation probability per incident electron in slice s.  The elastic wave is not depleted and the ionised electrons are not
+ * followed.
+ * msl_set_ionization:  1 <= n <= 8 channels (two may name one element); n = 0 or a NULL array clears it and frees its buffers.
+ *   Independent of msl_set_absorption.  MSL_ERR_INVALID: n > 8, an atomic number outside 1..103, a width that is not finite and
+ *   positive, a cross-section that is not finite and >= 0.  MSL_ERR_UNSUPPORTED at a frame batch above 1 and under
+ *   msl_set_projection (which is MSL_ERR_UNSUPPORTED while this is set).  MSL_ERR_STATE while msl_set_tds is set (and msl_set_tds is
+ *   MSL_ERR_STATE while this is set): a handle runs one per-slice reduction.  Drops the potential as msl_set_tds does: the next
+ *   build (msl_build_potential, msl_build_thermal, msl_build_modes) makes, per channel, a table that is non-zero for its species
+ *   only and with it one more structure factor and inverse transform of the positions it has just placed, into the weight stack
+ *   (MSL_BUF_IONIZATION_WEIGHT); a channel whose element the structure does not hold gives zeros.  While it is set every
+ *   msl_propagate* runs the two-pass loop with the row step of each slice in two launches and the reduction between them, as under
+ *   msl_set_tds; the exit waves and spectra are those of the two-pass loop, bit for bit.  Synchronous.
+ * msl_ionization_fetch:  after one stream synchronisation, I of the last slice loop for the first B probes (B <= 0: n_probes) as
+ *   (nz, B, n) float64 on the host.  MSL_ERR_STATE before the first loop.
+ * msl_ionization_reduce:  the reduction alone, of the work buffer as the last slice loop left it (MSL_BUF_EXIT) against the weights
+ *   of `slice`: the tile kernel `reps` times between two events and the finishing sum once.  out (n_probes, n) float64 -- the sums
+ *   sum_r |psi|^2 W, not divided by a norm -- and ms_reduce, the mean device time of one repeat in ms, may be NULL.  For benchmarks.
+ *   Not in the reference. */
+int  msl_set_ionization(msl_handle* h, int32_t n, const int32_t* Z, const double* width, const double* cross_section);
+int  msl_ionization_fetch(msl_handle* h, int32_t B, double* out);
+int  msl_ionization_reduce(msl_handle* h, int32_t slice, int32_t reps, double* out, double* ms_reduce);
 
 /* TACAW: intensity[p,w,kx,ky] = | fftshift_t fft_t( Psi - <Psi>_t ) |^2 over a (B,T,npix) c64 device
  * array.  src == NULL uses the handle's own wavefunction buffer (B=P, T=T_local, npix=nx*ny) and
@@ -719,8 +748,8 @@ int  msl_fft2_host(msl_handle* h, const float* in_c64, float* out_c64, int32_t b
  * rows per atom through the sort, the phase tables and the structure factor of the ordinary build; the inverse transform and the
  * slice loop are unchanged.  reach_slices = 0 (the default; nodes is then only stored) turns it off: the builds of a handle the call
  * was never made on, bit for bit.  Every change of (R, J) makes the next build compute its tables again.
- * MSL_ERR_INVALID: nodes outside [1, 16], reach_slices outside [0, 32].  MSL_ERR_UNSUPPORTED: while msl_set_absorption or msl_set_tds
- * is set (and msl_set_absorption is MSL_ERR_UNSUPPORTED while this is on); at build time, when an interior slice is not dz thick.
+ * MSL_ERR_INVALID: nodes outside [1, 16], reach_slices outside [0, 32].  MSL_ERR_UNSUPPORTED: while msl_set_absorption, msl_set_tds
+ * or msl_set_ionization is set (and msl_set_absorption is MSL_ERR_UNSUPPORTED while this is on); at build time, when an interior slice is not dz thick.
  * msl_get_projection: reach_nodes[0..1] = (reach_slices, nodes), (0, 1) before the first call.  Not in the reference. */
 int  msl_set_projection(msl_handle* h, int32_t reach_slices, int32_t nodes);
 int  msl_get_projection(const msl_handle* h, int32_t* reach_nodes);

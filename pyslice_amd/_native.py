@@ -17,8 +17,9 @@ ABI_VERSION = 3          # include/mslice.h: MSL_ABI_VERSION
 MSL_OK, MSL_ERR_INVALID, MSL_ERR_HIP, MSL_ERR_UNSUPPORTED, MSL_ERR_STATE, MSL_ERR_NOMEM = 0, -1, -2, -3, -4, -5
 (BUF_PROBES, BUF_EXIT, BUF_POTENTIAL, BUF_TRANSMISSION, BUF_WAVEFUNCTION, BUF_INTENSITY, BUF_FORMFACTOR,
  BUF_STREAM_ACC, BUF_STREAM_S1, BUF_STREAM_S2, BUF_STREAM_REF, BUF_LAYERS, BUF_SMATRIX, BUF_FORMFACTOR_ABS,
- BUF_ABSORPTION, BUF_FORMFACTOR_TDS, BUF_TDS_WEIGHT, BUF_FORMFACTOR_FINITE) = range(18)
+ BUF_ABSORPTION, BUF_FORMFACTOR_TDS, BUF_TDS_WEIGHT, BUF_FORMFACTOR_FINITE, BUF_IONIZATION_WEIGHT) = range(19)
 TDS_MAX_DETECTORS = 4      # include/mslice.h: msl_set_tds
+IONIZATION_MAX_CHANNELS = 8     # include/mslice.h: msl_set_ionization
 
 EXPORTS = [
     "msl_abi_version", "msl_line_kernel_class", "msl_last_error", "msl_create", "msl_destroy", "msl_set_kirkland", "msl_set_slices",
@@ -47,6 +48,7 @@ EXPORTS = [
     "msl_set_bandlimit", "msl_get_bandlimit",
     "msl_set_absorption",
     "msl_set_tds", "msl_tds_fetch", "msl_tds_reduce",
+    "msl_set_ionization", "msl_ionization_fetch", "msl_ionization_reduce",
     "msl_set_projection", "msl_get_projection",
 ]
 DET_SIGNALS = {"intensity": 0, "amplitude": 1, "com_x": 2, "com_y": 3}      # include/mslice.h: MSL_DET_*
@@ -163,6 +165,9 @@ def load():
         "msl_set_tds": (C.c_int, [vp, vp, i32]),
         "msl_tds_fetch": (C.c_int, [vp, i32, vp]),
         "msl_tds_reduce": (C.c_int, [vp, i32, i32, vp, vp]),
+        "msl_set_ionization": (C.c_int, [vp, i32, vp, vp, vp]),
+        "msl_ionization_fetch": (C.c_int, [vp, i32, vp]),
+        "msl_ionization_reduce": (C.c_int, [vp, i32, i32, vp, vp]),
         "msl_thermal_positions": (C.c_int, [vp, C.c_uint64, i64, vp]),
         "msl_set_modes": (C.c_int, [vp, vp, i64, i32, vp, vp, vp, i32, i32]),
         "msl_build_modes": (C.c_int, [vp, C.c_uint64, i64, i32]),
@@ -326,6 +331,37 @@ class Engine:
         out = np.empty((self.n_probes, getattr(self, "n_tds", 0)), dtype=np.float64)
         ms = C.c_double(0.0)
         self._chk(self._lib.msl_tds_reduce(self._h, int(slice_index), int(reps), _ptr(out), C.byref(ms)))
+        return out, float(ms.value)
+
+    def set_ionization(self, channels=None):
+        """element maps (msl_set_ionization; the definition is ionization.py): channels = a list of ionization.Ionization (1 to 8), or
+        of (Z, width, cross_section) triples; None or an empty list clears it.  Before the build, which then also makes the weight
+        stack.  Every later slice loop runs on the two-pass loop and leaves the per-slice sums for ionization_fetch()."""
+        if not channels:
+            self._chk(self._lib.msl_set_ionization(self._h, 0, None, None, None))
+            self.n_ionization = 0
+            return
+        rows = [(c.Z, c.width, c.cross_section) if hasattr(c, "cross_section") else tuple(c) for c in channels]
+        Z = np.ascontiguousarray([r[0] for r in rows], dtype=np.int32)
+        w = np.ascontiguousarray([r[1] for r in rows], dtype=np.float64)
+        cs = np.ascontiguousarray([r[2] for r in rows], dtype=np.float64)
+        self._chk(self._lib.msl_set_ionization(self._h, len(rows), _ptr(Z), _ptr(w), _ptr(cs)))
+        self.n_ionization = len(rows)
+
+    def ionization_fetch(self, B=None):
+        """I[s, p, e] of the last slice loop, (nz, B, n) float64: the ionisation probability per incident electron of channel e in
+        slice s, for the first B probes (msl_ionization_fetch; one wait for the stream)"""
+        b = int(B) if B else self.n_probes
+        out = np.empty((self.nz, b, getattr(self, "n_ionization", 0)), dtype=np.float64)
+        self._chk(self._lib.msl_ionization_fetch(self._h, b, _ptr(out)))
+        return out
+
+    def ionization_reduce(self, slice_index=0, reps=1):
+        """the ionisation reduction alone, of the work buffer the last slice loop left against the weights of one slice
+        (msl_ionization_reduce) -> (sums (n_probes, n) float64, not divided by a norm; mean device time of one repeat in ms)"""
+        out = np.empty((self.n_probes, getattr(self, "n_ionization", 0)), dtype=np.float64)
+        ms = C.c_double(0.0)
+        self._chk(self._lib.msl_ionization_reduce(self._h, int(slice_index), int(reps), _ptr(out), C.byref(ms)))
         return out, float(ms.value)
 
     def set_slices(self, lo, hi):
@@ -987,6 +1023,10 @@ class Engine:
     def tds_weight(self):
         """w = 1 - exp(-2 sigma^2 Omega_det), (n_det, nz, nx, ny), of the last build with set_tds"""
         return self.download(BUF_TDS_WEIGHT, np.float32, (self.n_tds, self.nz, self.nx, self.ny))
+
+    def ionization_weight(self):
+        """W_e,s, (n, nz, nx, ny), of the last build with set_ionization"""
+        return self.download(BUF_IONIZATION_WEIGHT, np.float32, (self.n_ionization, self.nz, self.nx, self.ny))
 
     def synchronize(self):
         self._chk(self._lib.msl_synchronize(self._h))

@@ -135,7 +135,7 @@ class MultisliceCalculator:
                  gather="rank0", cache=False, k_window=None, frame_batch=None, k_bin=None, stream_tile=None, layers=None,
                  detectors=None, probe_batch=None, diffraction=None, aberrations=None, imaging=None, prism=None,
                  spectroscopy=None, polar=None, thickness=None, tilt=None, precession=None, tds=False, bandlimit=None,
-                 projection=None):
+                 projection=None, ionization=None):
         """
         device / force_cpu: as the reference (calculators.py:41).  There is no CPU path here, so
         force_cpu=True raises.  Keyword-only extras (not in the reference):
@@ -264,6 +264,15 @@ class MultisliceCalculator:
                    one; the slice loop is unchanged, so every run mode, MD trajectories, FrozenPhonons and PhononModes carry it.
                    None or "infinite": every output is bit for bit that of a run without the argument.  Refused (ValueError): an
                    AbsorptivePotential, tds, cache, stream_tile, several ranks.
+          ionization a list of 1 to 8 ionization.Ionization(element, width, cross_section, name): element maps.  run_element_maps()
+                   returns, per probe position, channel and slice, the ionisation probability per incident electron in the local
+                   approximation -- |psi|^2 inside the specimen against a Gaussian of the channel's width on every atom of its
+                   element (ionization.py is the definition) -- as ElementMapData: what an EDX or core-loss EELS map records, and
+                   slice by slice the beam-channelling curve.  The scan runs on the two-pass loop with a reduction of |psi|^2 per
+                   slice (msl_set_ionization), at a frame batch of 1.  With MD trajectories, FrozenPhonons, PhononModes,
+                   AbsorptivePotential, aberrations, tilt, bandlimit and probe_batch.  Not built (NotImplementedError): tds, prism,
+                   precession, projection, detectors, polar, diffraction, imaging, spectroscopy, layers, thickness, k_window,
+                   k_bin, cache, stream_tile, frame_batch > 1, several ranks.  None: every run is what it is without the argument.
         """
         if force_cpu:
             raise NotImplementedError("pyslice_amd has no CPU path (force_cpu=True): use the reference for CPU runs")
@@ -273,6 +282,21 @@ class MultisliceCalculator:
             raise ValueError("dtype must be 'complex128' or 'complex64'")
         if gather not in ("rank0", "all", "none"):
             raise ValueError("gather must be 'rank0', 'all' or 'none'")
+        self._ionization = None
+        if ionization is not None:
+            from .ionization import check_ionization
+            self._ionization = check_ionization(ionization)
+            # a mode of its own on the probe-batch loop: the reductions of the exit spectra, the loops that are not the two-pass
+            # loop of one frame, and the stores that keep something else than the per-slice sums are not fed from its pass
+            for what, val in (("tds", bool(tds)), ("prism", prism is not None), ("precession", precession is not None),
+                              ("projection", projection is not None), ("detectors", detectors is not None), ("polar", polar is not None),
+                              ("diffraction", diffraction is not None), ("imaging", imaging is not None),
+                              ("spectroscopy", spectroscopy is not None), ("layers", layers is not None),
+                              ("thickness", thickness is not None), ("k_window", k_window is not None), ("k_bin", k_bin is not None),
+                              ("cache", bool(cache)), ("stream_tile", stream_tile is not None),
+                              ("frame_batch > 1", frame_batch is not None and int(frame_batch) > 1)):
+                if val:
+                    raise NotImplementedError(f"ionization: {what} is not built")
         self.device = device
         self._output, self._dtype, self._progress, self._gather = output, dtype, progress, gather
         self._cache = bool(cache)
@@ -344,7 +368,7 @@ class MultisliceCalculator:
                                           "PRISM waves")
         self._prism = prism
         if (probe_batch is not None and detectors is None and diffraction is None and imaging is None and spectroscopy is None
-                and polar is None):
+                and polar is None and ionization is None):
             raise ValueError("probe_batch applies to detector and diffraction runs only: give detectors=[...] or diffraction=Diffraction(...)")
         if probe_batch is not None and int(probe_batch) < 1:
             raise ValueError("probe_batch must be a positive probe count")
@@ -506,6 +530,8 @@ class MultisliceCalculator:
                                  "its absorption takes out of the elastic wave")
             if distributed.rank_world()[1] > 1:
                 raise NotImplementedError("tds: a run over several ranks is not built")
+        if getattr(self, "_ionization", None) is not None and distributed.rank_world()[1] > 1:
+            raise NotImplementedError("ionization: a run over several ranks is not built")
         self.trajectory = trajectory
         self.aperture = aperture
         self.voltage_eV = voltage_eV
@@ -559,7 +585,8 @@ class MultisliceCalculator:
         if self._spectroscopy is not None:
             self._setup_spectrum_image(trajectory, slice_axis)
             return
-        if self._detectors is not None or self._diffraction is not None or self._imaging is not None or self._polar is not None:
+        if (self._detectors is not None or self._diffraction is not None or self._imaging is not None or self._polar is not None
+                or self._ionization is not None):
             self._setup_probe_batches(trajectory, slice_axis)
             return
         n_slices = self._setup_run(trajectory, slice_axis)
@@ -645,7 +672,8 @@ class MultisliceCalculator:
         auto = self._probe_batch is None
         Pc = min(self.n_probes, 256 if auto else self._probe_batch)
         batch = self._frame_batch if self._frame_batch is not None else default_frame_batch(Pc, n_slices, self.nx, self.ny)
-        batch = 1 if self._prism is not None else max(1, min(batch, self.n_frames))     # (the S-matrix holds one frame)
+        # (the S-matrix holds one frame; so does the weight stack of the ionisation channels)
+        batch = 1 if (self._prism is not None or self._ionization is not None) else max(1, min(batch, self.n_frames))
         free_b = _free_device_bytes(self.device) if auto else None
         if free_b is not None:
             Pc = self._fit_probe_batch(free_b, Pc, batch)
@@ -670,6 +698,8 @@ class MultisliceCalculator:
                 from .tds import tds_members
                 self._engine.set_tds(tds_members(self._detectors, self.nx, self.ny, self.dx, self.dy, wavelength(self.voltage_eV)),
                                      len(self._detectors))
+            if self._ionization is not None:                    # (before the first build, which then makes the weight stack)
+                self._engine.set_ionization(self._ionization)
             if self._polar is not None:
                 self._engine.set_polar(self._polar_bins.reshape(-1), self._polar.n_bins)
             if self._thickness is not None and len(self._thickness) > 1:    # (the exit wave alone needs no tap: the plain reductions)
@@ -818,6 +848,8 @@ class MultisliceCalculator:
         smatrix = 8.0 * getattr(self, "_prism_Bm", 0) * nx * ny       # the S-matrix of a PRISM run, (Bm, nx, ny) complex64
         if getattr(self, "_tds", False):                            # (a fixed cost like the S-matrix: the weight stack of every detector)
             smatrix += 4.0 * len(self._detectors) * n_slices * nx * ny
+        if getattr(self, "_ionization", None) is not None:          # (the same: the weight stack and the table of every channel)
+            smatrix += 4.0 * len(self._ionization) * (n_slices + 8) * nx * ny
         polar = 8.0 * self._polar.n_bins if self._polar is not None else 0.0
         series = 0.0
         if self._thickness is not None and len(self._thickness) > 1:
@@ -1301,6 +1333,31 @@ class MultisliceCalculator:
         self.frames_computed, self.frames_cached = T, 0
         return self._stem_data(signals, tds)
 
+    def run_element_maps(self):
+        """Element maps (ionization.py is the definition): the loop of run_detectors() at a frame batch of 1 -- per frame the
+        potential and with it the weight stack of every channel, then every probe batch through the two-pass slice loop, which
+        reduces |psi|^2 against the weights slice by slice (msl_set_ionization); the sums of every frame are fetched and added on
+        the host in float64 and divided by the number of frames.  -> ElementMapData with per_slice (P, E, nz)."""
+        if self._ionization is None:
+            raise RuntimeError("run_element_maps() needs MultisliceCalculator(ionization=[Ionization(...), ...])")
+        if self._engine is None:
+            raise RuntimeError("call setup() before run_element_maps()")
+        from .element_map_data import ElementMapData
+        eng = self._engine
+        t0 = time.time()
+        P, T, E = self.n_probes, self.n_frames, len(self._ionization)
+        per_slice = np.zeros((P, E, len(self._slice_coords)), dtype=np.float64)
+
+        def reduce_batch(p0, real, s0, n):
+            per_slice[p0:p0 + real] += np.moveaxis(eng.ionization_fetch(B=real), 0, -1)      # (nz, real, E) of the frame that just ran
+        self._probe_batch_loop(reduce_batch)
+        per_slice /= float(T)
+        self.elapsed = time.time() - t0
+        self.frames_computed, self.frames_cached = T, 0
+        lo, hi = slice_edges(self._slice_coords)
+        return ElementMapData(per_slice=per_slice, channels=list(self._ionization), probe_positions=self.probe_positions,
+                              thickness=hi - lo[0], n_frames=T)
+
     def run_polar(self):
         """Polar-detector signals of every probe position: the loop of run_detectors(); msl_polar_detect reduces the exit spectra of
         every probe batch to (real, n, R * A) float64 -- |Psi|^2 summed over the pixels of each ring x sector bin, frame by frame --
@@ -1398,6 +1455,8 @@ class MultisliceCalculator:
             raise RuntimeError("spectroscopy is set: the device holds one probe batch at a time -- call run_spectrum_image()")
         if self._polar is not None:
             raise RuntimeError("polar is set: the device holds one probe batch at a time -- call run_polar()")
+        if self._ionization is not None:
+            raise RuntimeError("ionization is set: the device holds one probe batch at a time -- call run_element_maps()")
         if self._engine is None:
             raise RuntimeError("call setup() before run()")
         if self._stream_tile is not None:

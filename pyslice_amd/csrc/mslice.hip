@@ -21,6 +21,7 @@
 #include "absorptive.h"
 #include "finite.h"
 #include "tds.h"
+#include "ionization.h"
 #include "thermal.h"
 #include "phonons.h"
 #include "reduce.h"
@@ -281,6 +282,16 @@ struct msl_handle {
     DevBuf<uint16_t> tds_bits;
     DevBuf<float> tds_g, tds_W;
     DevBuf<double> tds_acc, tds_part;
+    // element maps (msl_set_ionization, ionization.h): the channels (atomic number, width, cross-section),
+    // their tables (ion_n, n_species, nx, ny) for the species list ion_species (ion_nsp = 0: to be made), the weight stack W
+    // (ion_n, nz, nx, ny) of the last build (ion_built), an image of ones for the norm of the incident waves, the per-slice sums
+    // (nz, n_probes, ion_n) and the norms (n_probes) of the last slice loop (ion_have) and the slab of its float32 partials.  While
+    // ion_on the handle runs slice_loop_tds, on the two-pass loop (set_loop_mode)
+    bool ion_on = false, ion_built = false, ion_have = false;
+    int ion_n = 0, ion_Z[ION_MAX] = {0}, ion_species[104] = {0}, ion_nsp = 0;
+    double ion_width[ION_MAX] = {0}, ion_cross[ION_MAX] = {0};
+    DevBuf<float> ion_tab, ion_W, ion_ones, ion_part;
+    DevBuf<double> ion_acc, ion_norm;
     // frozen phonons (msl_set_structure): the base structure resident on the device -- positions (n, 3), widths, Z and the species
     // maps that stage_atoms sends per call -- with the host's copy of the maps and the axes; msl_build_thermal generates the
     // positions of any configuration from it (thermal_positions_kernel), so no per-frame array and no caller pointer is kept
@@ -1381,20 +1392,70 @@ int tds_reduce_queue(msl_handle* h, const float2* psi, int P, int z, double* dst
     return reps == 1 ? mark_launch(h, K_OTHER) : MSL_OK;
 }
 
-// The slice loop while TDS is on: the two-pass loop with the row step of every slice issued as two launches of its own kernels --
+// ---- element maps (ionization.h) ----
+// The reduction of P images at `psi` (the work buffers' layout) against n images of weights at w, w_es values apart, into dst (P, n)
+// float64, queued: the tile kernel into the slab of float32 partials, then the sums over the tiles in float64.  reps > 1 repeats the
+// tile kernel (msl_ionization_reduce's timing).
+int ion_reduce_queue(msl_handle* h, const float2* psi, int P, const float* w, size_t w_es, int n, double* dst, int reps = 1) {
+    const msl_config& c = h->cfg;
+    const long long pairs = (long long)c.nx * ((c.ny + 1) / 2), n_tiles = (pairs + ION_TILE - 1) / ION_TILE;
+    if (n_tiles > 0x7fffffffLL) return fail(h, MSL_ERR_UNSUPPORTED, "ionization: too many tiles");
+    const int ne = n <= 1 ? 1 : n <= 2 ? 2 : n <= 4 ? 4 : 8;        // channel slots of the kernel: the next power of two
+    int rc = h->ion_part.reserve(h, (size_t)n_tiles * P * ION_MAX);   // (for any n: the slab is not reallocated between two launches of a loop)
+    if (rc) return rc;
+    // images per workgroup: as many as possible (the weights are loaded once per workgroup) while every slot still has a workgroup
+    const long long slots = (long long)h->n_cus * 8;
+    int pc = P;
+    while (pc > 1 && n_tiles * ((P + pc - 1) / pc) < slots) pc = (pc + 1) / 2;
+    while ((P + pc - 1) / pc > 65535) ++pc;
+    const bool vec = (h->pitch % 2 == 0) && (((uintptr_t)psi & 15) == 0);
+    const dim3 grid((unsigned)n_tiles, (unsigned)((P + pc - 1) / pc));
+    for (int r = 0; r < reps; ++r) {
+        with_int<1, 2, 4, 8>(ne, [&](auto k) { with_bool(vec, [&](auto v) {
+            hipLaunchKernelGGL((ion_reduce_kernel<decltype(k)::value, decltype(v)::value>), grid, dim3(256), 0, h->stream, psi, w, (long long)w_es, n,
+                               c.nx, c.ny, h->pitch, P, pc, h->ion_part.p);
+        }); });
+        HIPCHK(h, hipGetLastError());
+        if (reps == 1 && (rc = mark_launch(h, K_OTHER))) return rc;
+    }
+    with_int<1, 2, 4, 8>(ne, [&](auto k) {
+        hipLaunchKernelGGL(ion_finish_kernel<decltype(k)::value>, dim3((unsigned)(((long long)P * ne + 255) / 256)), dim3(256), 0, h->stream,
+                           h->ion_part.p, n_tiles, P, n, dst);
+    });
+    HIPCHK(h, hipGetLastError());
+    return reps == 1 ? mark_launch(h, K_OTHER) : MSL_OK;
+}
+
+// What the two-pass loop queues between the two launches of a slice's row step, where psi holds the wave arriving at slice z in real
+// space: the TDS sums of the slice, or the ionisation sums
+int tds_slice_queue(msl_handle* h, int P, int z) { return tds_reduce_queue(h, h->psi, P, z, h->tds_acc + (size_t)z * P * h->tds_n); }
+int ion_slice_queue(msl_handle* h, int P, int z) {
+    const size_t npix = (size_t)h->cfg.nx * h->cfg.ny;
+    return ion_reduce_queue(h, h->psi, P, h->ion_W + (size_t)z * npix, npix * h->cfg.nz, h->ion_n, h->ion_acc + (size_t)z * P * h->ion_n);
+}
+
+// The slice loop while a per-slice reduction is on (the TDS signal it was written for, or else the ionisation signal): the two-pass
+// loop with the row step of every slice issued as two launches of its own kernels --
 // the inverse y-transform alone, as fft2_inplace issues it, then t_s, the forward transform and P_y -- so that between them psi holds
 // psi_s in real space at its true scale, where the reduction is queued (at s = 0 psi is psi0).  Every elastic launch computes what
-// slice_loop's computes; the per-slice sums go to tds_acc (nz, P, tds_n).
+// slice_loop's computes; the per-slice sums go to tds_acc (nz, P, tds_n) or ion_acc (nz, P, ion_n), and for the ionisation signal
+// the norms of the incident waves, the same kernel against an image of ones, to ion_norm.
 int slice_loop_tds(msl_handle* h, int fused_slot, int groups, int first_group) {
     const msl_config& c = h->cfg;
-    if (groups != 1 || h->onepass) return fail(h, MSL_ERR_STATE, "tds: the slice loop needs one frame per launch on the two-pass loop");
-    if (!h->tds_W || !h->abs_built) return fail(h, MSL_ERR_STATE, "tds: no weight stack (build the potential after msl_set_tds)");
-    const int P = c.n_probes, nz = c.nz;
+    const bool ion = !h->tds_on;
+    if (groups != 1 || h->onepass)
+        return fail(h, MSL_ERR_STATE, "%s: the slice loop needs one frame per launch on the two-pass loop", ion ? "ionization" : "tds");
+    if (!ion && (!h->tds_W || !h->abs_built)) return fail(h, MSL_ERR_STATE, "tds: no weight stack (build the potential after msl_set_tds)");
+    if (ion && (!h->ion_W || !h->ion_built))
+        return fail(h, MSL_ERR_STATE, "ionization: no weight stack (build the potential after msl_set_ionization)");
+    const int P = c.n_probes, nz = c.nz, n_sums = ion ? h->ion_n : h->tds_n;
     const size_t npix = (size_t)c.nx * c.ny;
     const size_t toff = (size_t)first_group * c.nz * npix;
-    int rc = h->tds_acc.reserve(h, (size_t)nz * P * h->tds_n);
+    int rc = (ion ? h->ion_acc : h->tds_acc).reserve(h, (size_t)nz * P * n_sums);
     if (rc) return rc;
+    if (ion && (rc = h->ion_norm.reserve(h, (size_t)P))) return rc;
     HIPCHK(h, hipMemcpyAsync(h->psi, h->psi0, (size_t)P * c.nx * h->pitch * sizeof(float2), hipMemcpyDeviceToDevice, h->stream));
+    if (ion && (rc = ion_reduce_queue(h, h->psi, P, h->ion_ones, npix, 1, h->ion_norm))) return rc;     // (ahead of the timed launches)
     const bool fused = fused_slot >= 0;
     if ((rc = begin_timed(h, 5 * nz + 2 + (fused ? tap_launches(h) : 0)))) return rc;
     for (int z = 0; z < nz; ++z) {
@@ -1411,7 +1472,7 @@ int slice_loop_tds(msl_handle* h, int fused_slot, int groups, int first_group) {
             }
             if (rc) return rc;
         }
-        if ((rc = tds_reduce_queue(h, h->psi, P, z, h->tds_acc + (size_t)z * P * h->tds_n))) return rc;
+        if ((rc = (ion ? ion_slice_queue : tds_slice_queue)(h, P, z))) return rc;
         if (h->Ry) {
             RowJob r = row_job(h, h->psi, P, h->pitch);
             r.trans = h->trans + toff + (size_t)z * npix;
@@ -1440,10 +1501,11 @@ int slice_loop_tds(msl_handle* h, int fused_slot, int groups, int first_group) {
         }
     }
     if (fused && (rc = epilogue_x_pass(h, fused_slot, groups))) return rc;
-    h->tds_have = true;
+    (ion ? h->ion_have : h->tds_have) = true;
     // 16 B more per pixel and slice-step for the split row step, 8 for the reduction's read, and the weights once per image chunk
     count_slice_loop(h, P, groups, fused, 32 + 16 + 8);
-    h->ctr.algorithmic_bytes += (uint64_t)nz * h->tds_n * 4ull * npix;
+    if (!ion) h->ctr.algorithmic_bytes += (uint64_t)nz * h->tds_n * 4ull * npix;
+    else h->ctr.algorithmic_bytes += (uint64_t)nz * h->ion_n * 4ull * npix + 8ull * P * npix;      // (and the norm's read of psi0)
     return MSL_OK;
 }
 
@@ -1970,6 +2032,49 @@ int absorptive_ifft(msl_handle* h, const PotGroup& p, float* out_real) {
     return launch_lines(h, h->plan_x, k, K_OTHER);
 }
 
+// ---- element maps: the weight stack (ionization.h) ----
+// The tables of the channels, (ion_n, n_species, nx, ny): made when the species list of a build is not the one they were made for
+// (msl_set_ionization forgets it).  Each is non-zero for the species of its channel only, so the structure factor of the build sums
+// the atoms of that element and no others, in the slices its own sort has put them in.
+int ion_tables(msl_handle* h, const PotGroup& p) {
+    const msl_config& c = h->cfg;
+    if (p.nsp == h->ion_nsp && memcmp(p.species, h->ion_species, p.nsp * sizeof(int)) == 0) return MSL_OK;
+    const long long tot = (long long)c.nx * c.ny * p.nsp;
+    h->ion_nsp = 0;
+    const int rc = h->ion_tab.reserve(h, (size_t)tot * h->ion_n);
+    if (rc) return rc;
+    for (int e = 0; e < h->ion_n; ++e)
+        hipLaunchKernelGGL(ion_table_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, h->stream, h->ion_tab + (size_t)e * tot, p.nsp,
+                           p.z2s[h->ion_Z[e]], c.nx, c.ny, 1.0 / (c.nx * c.dx), 1.0 / (c.ny * c.dy), h->ion_width[e], h->ion_cross[e] * c.dx * c.dy);
+    HIPCHK(h, hipGetLastError());
+    memcpy(h->ion_species, p.species, p.nsp * sizeof(int));
+    h->ion_nsp = p.nsp;
+    return MSL_OK;
+}
+
+// The weight stack of a group whose atoms bin_atoms has sorted (`atoms` false: none, the stack is zero), before the potential of the
+// group is made: per channel the structure factor with the channel's table and absorptive_ifft's two passes into ion_W, through the
+// group's own transmission slot, which the build overwrites afterwards.  A channel whose element the structure does not hold is zero.
+int ionization_group(msl_handle* h, const PotGroup& p, bool atoms) {
+    const msl_config& c = h->cfg;
+    const size_t npix = (size_t)c.nx * c.ny, stack = npix * c.nz;
+    if (p.g != 1 || p.finite || h->pot_ifft != PI_LINES)
+        return fail(h, MSL_ERR_UNSUPPORTED, "ionization: the weight stack is that of one frame, built on the two-pass loop without finite projection");
+    int rc;
+    h->cur = nullptr;
+    if (!h->ion_W && (rc = h->ion_W.alloc(h, stack * h->ion_n))) return rc;
+    if (atoms && (rc = ion_tables(h, p))) return rc;
+    for (int e = 0; e < h->ion_n; ++e) {
+        float* W = h->ion_W + (size_t)e * stack;
+        if (!atoms || p.z2s[h->ion_Z[e]] < 0) {
+            HIPCHK(h, hipMemsetAsync(W, 0, stack * sizeof(float), h->stream));
+            continue;
+        }
+        if ((rc = launch_structure_factor(h, p, h->ion_tab + (size_t)e * npix * p.nsp)) || (rc = absorptive_ifft(h, p, W))) return rc;
+    }
+    return MSL_OK;
+}
+
 // t = exp(i sigma Vbar - sigma^2 Omega) of the stacks in the batch slots slot .. slot + count - 1, from abs_V / abs_O into trans
 // (natural order), with the handle's current sigma
 int absorptive_transmission(msl_handle* h, int slot, int count) {
@@ -2190,10 +2295,10 @@ bool tilt_needs_two_pass(const msl_handle* h, double tan_x, double tan_y) {
     return (tan_x != 0.0 && even_only(h->opx)) || (tan_y != 0.0 && even_only(h->opy));
 }
 
-// The loop a handle may run under the tangents (tan_x, tan_y): the one msl_create planned, unless the TDS signal (slice_loop_tds runs
-// on the two-pass loop) or the tilt asks for the two-pass loop
+// The loop a handle may run under the tangents (tan_x, tan_y): the one msl_create planned, unless the TDS signal, the ionisation signal
+// (slice_loop_tds runs on the two-pass loop) or the tilt asks for the two-pass loop
 bool allowed_onepass(const msl_handle* h, double tan_x, double tan_y) {
-    return h->onepass_planned && !h->tds_on && !tilt_needs_two_pass(h, tan_x, tan_y);
+    return h->onepass_planned && !h->tds_on && !h->ion_on && !tilt_needs_two_pass(h, tan_x, tan_y);
 }
 
 // Switch a handle planned for the one-pass loop to the two-pass loop and back, on the stream.  The two-pass loop and the potential
@@ -2254,7 +2359,7 @@ int remake_transmission(msl_handle* h) {
 
 // ---- invalidations ----
 // The resident potential no longer counts (msl_propagate is MSL_ERR_STATE until the next build or upload)
-void drop_potential(msl_handle* h) { h->have_potential = false; h->abs_built = false; }
+void drop_potential(msl_handle* h) { h->have_potential = false; h->abs_built = false; h->ion_built = false; }
 
 // A built S-matrix belongs to the tables and the stack it was built with: it has to be built again (the beams stay)
 void drop_smatrix_result(msl_handle* h) { h->sm_built = false; }
@@ -2273,6 +2378,15 @@ int tds_clear(msl_handle* h) {
     h->tds_on = h->tds_have = false;
     h->tds_n = 0;
     h->tds_bits.release(); h->tds_g.release(); h->tds_W.release(); h->tds_acc.release(); h->tds_part.release();
+    return set_loop_mode(h, allowed_onepass(h, h->set.tilt_tan[0], h->set.tilt_tan[1]));
+}
+
+// Ionisation off: its buffers freed, and the handle back on the loop its tilt allows
+int ion_clear(msl_handle* h) {
+    if (!h->ion_on) return MSL_OK;
+    h->ion_on = h->ion_built = h->ion_have = false;
+    h->ion_n = h->ion_nsp = 0;
+    h->ion_tab.release(); h->ion_W.release(); h->ion_ones.release(); h->ion_part.release(); h->ion_acc.release(); h->ion_norm.release();
     return set_loop_mode(h, allowed_onepass(h, h->set.tilt_tan[0], h->set.tilt_tan[1]));
 }
 
@@ -2390,6 +2504,7 @@ int msl_set_tds(msl_handle* h, const uint16_t* member_bits, int32_t n_det) {
     if (!clear && !(h->abs_on && h->abs_absorb))
         return fail(h, MSL_ERR_STATE, "msl_set_tds: no absorption (call msl_set_absorption(.., absorb != 0) first)");
     if (!clear && h->FB > 1) return fail(h, MSL_ERR_UNSUPPORTED, "msl_set_tds: a frame batch of %d (the weight stack is that of one frame)", h->FB);
+    if (!clear && h->ion_on) return fail(h, MSL_ERR_STATE, "msl_set_tds: msl_set_ionization is set (one per-slice reduction per handle)");
     HIPCHK(h, hipSetDevice(h->cfg.device));
     HIPCHK(h, hipStreamSynchronize(h->stream));          // a queued build or loop still reads the tables and the stacks
     h->ff_n = 0;                                         // as msl_set_absorption: the next build makes the tables again
@@ -2403,6 +2518,43 @@ int msl_set_tds(msl_handle* h, const uint16_t* member_bits, int32_t n_det) {
     h->tds_on = true;
     rc = set_loop_mode(h, allowed_onepass(h, h->set.tilt_tan[0], h->set.tilt_tan[1]));
     if (rc) { h->tds_on = false; h->tds_n = 0; h->tds_bits.release(); }      // a refused switch: no TDS, as after the tds_clear above
+    return rc;
+}
+
+// element maps
+int msl_set_ionization(msl_handle* h, int32_t n, const int32_t* Z, const double* width, const double* cross_section) {
+    if (!h) return fail(h, MSL_ERR_INVALID, "msl_set_ionization: null handle");
+    const bool clear = n == 0 || !Z || !width || !cross_section;
+    if (!clear && (n < 1 || n > ION_MAX)) return fail(h, MSL_ERR_INVALID, "msl_set_ionization: %d channels outside [1, %d]", n, ION_MAX);
+    for (int e = 0; !clear && e < n; ++e) {
+        if (Z[e] < 1 || Z[e] > 103) return fail(h, MSL_ERR_INVALID, "msl_set_ionization: atomic number %d of channel %d out of 1..103", Z[e], e);
+        if (!std::isfinite(width[e]) || !(width[e] > 0.0))
+            return fail(h, MSL_ERR_INVALID, "msl_set_ionization: width %g of channel %d is not a finite number > 0", width[e], e);
+        if (!std::isfinite(cross_section[e]) || !(cross_section[e] >= 0.0))
+            return fail(h, MSL_ERR_INVALID, "msl_set_ionization: cross-section %g of channel %d is not a finite number >= 0", cross_section[e], e);
+    }
+    if (clear && !h->ion_on) return MSL_OK;                 // never set: the handle stays what it is
+    if (!clear && h->FB > 1)
+        return fail(h, MSL_ERR_UNSUPPORTED, "msl_set_ionization: a frame batch of %d (the weight stack is that of one frame)", h->FB);
+    if (!clear && h->tds_on) return fail(h, MSL_ERR_STATE, "msl_set_ionization: msl_set_tds is set (one per-slice reduction per handle)");
+    if (!clear && h->fin_R > 0)
+        return fail(h, MSL_ERR_UNSUPPORTED, "msl_set_ionization: the weight stack is not built under finite projection (msl_set_projection)");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));          // a queued build or loop still reads the tables and the stacks
+    drop_potential(h);
+    int rc = ion_clear(h);
+    if (rc || clear) return rc;
+    const size_t npix = (size_t)h->cfg.nx * h->cfg.ny;
+    if ((rc = h->ion_ones.alloc(h, npix))) return rc;
+    const float one = 1.0f;
+    int one_bits;
+    memcpy(&one_bits, &one, sizeof one_bits);
+    HIPCHK(h, hipMemsetD32Async((hipDeviceptr_t)h->ion_ones.p, one_bits, npix, h->stream));
+    for (int e = 0; e < n; ++e) { h->ion_Z[e] = Z[e]; h->ion_width[e] = width[e]; h->ion_cross[e] = cross_section[e]; }
+    h->ion_n = n;
+    h->ion_on = true;
+    rc = set_loop_mode(h, allowed_onepass(h, h->set.tilt_tan[0], h->set.tilt_tan[1]));
+    if (rc) { h->ion_on = false; h->ion_n = 0; h->ion_ones.release(); }     // a refused switch: no ionisation, as after the ion_clear above
     return rc;
 }
 
@@ -2495,9 +2647,11 @@ int build_potentials(msl_handle* h, const double* pos, const int32_t* Z, int64_t
             rc = !th ? stage_atoms(h, p, pos + (size_t)f0 * n * 3, Z, f0 == 0)
                  : th->modes ? stage_modes(h, p, th->seed, th->first + (uint64_t)f0, f0 == 0)
                              : stage_thermal(h, p, th->seed, th->first + (uint64_t)f0, f0 == 0);
-            if (rc || (rc = bin_atoms(h, p)) || (!h->abs_on && (rc = launch_structure_factor(h, p)))) return rc;
-        } else if (!h->abs_on) {
-            HIPCHK(h, hipMemsetAsync(p.TR, 0, npix * p.n_slices * sizeof(float2), h->stream));
+            if (rc || (rc = bin_atoms(h, p)) || (h->ion_on && (rc = ionization_group(h, p, true))) ||
+                (!h->abs_on && (rc = launch_structure_factor(h, p)))) return rc;
+        } else {
+            if (h->ion_on && (rc = ionization_group(h, p, false))) return rc;
+            if (!h->abs_on) HIPCHK(h, hipMemsetAsync(p.TR, 0, npix * p.n_slices * sizeof(float2), h->stream));
         }
         if ((rc = h->abs_on ? absorptive_group(h, p, n > 0 && p.nsp > 0) : potential_ifft(h, p))) return rc;
     }
@@ -2507,6 +2661,7 @@ int build_potentials(msl_handle* h, const double* pos, const int32_t* Z, int64_t
     if ((rc = timer.end(h, &h->ctr.ms_potential))) return rc;
     h->have_potential = true;
     h->abs_built = h->abs_on;
+    h->ion_built = h->ion_on;
     return MSL_OK;
 }
 
@@ -2897,6 +3052,8 @@ int msl_set_projection(msl_handle* h, int32_t reach_slices, int32_t nodes) {
     if (reach_slices < 0 || reach_slices > 32) return fail(h, MSL_ERR_INVALID, "msl_set_projection: a reach of %d slices outside [0, 32]", reach_slices);
     if (reach_slices > 0 && (h->abs_on || h->tds_on))
         return fail(h, MSL_ERR_UNSUPPORTED, "msl_set_projection: absorptive and TDS tables are not built under finite projection");
+    if (reach_slices > 0 && h->ion_on)
+        return fail(h, MSL_ERR_UNSUPPORTED, "msl_set_projection: the ionisation weights are not built under finite projection");
     if (reach_slices == h->fin_R && (reach_slices == 0 || nodes == h->fin_J)) { h->fin_J = nodes; return MSL_OK; }     // nothing changes
     HIPCHK(h, hipSetDevice(h->cfg.device));
     HIPCHK(h, hipStreamSynchronize(h->stream));          // a queued build still reads the tables
@@ -3210,6 +3367,53 @@ int msl_tds_reduce(msl_handle* h, int32_t slice, int32_t reps, double* out, doub
     return MSL_OK;
 }
 
+// ---- element maps (msl_set_ionization stands with the handle settings) ----
+int msl_ionization_fetch(msl_handle* h, int32_t B, double* out) {
+    if (!h || !out) return fail(h, MSL_ERR_INVALID, "msl_ionization_fetch: null argument");
+    if (!h->ion_on || !h->ion_have) return fail(h, MSL_ERR_STATE, "msl_ionization_fetch: no sums (msl_set_ionization, then a slice loop)");
+    const int P = h->cfg.n_probes, n = h->ion_n, nz = h->cfg.nz;
+    if (B <= 0) B = P;
+    if (B > P) return fail(h, MSL_ERR_INVALID, "msl_ionization_fetch: %d probes, the handle has %d", B, P);
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    std::vector<double> norm((size_t)B);
+    HIPCHK(h, hipMemcpy2DAsync(out, (size_t)B * n * sizeof(double), h->ion_acc, (size_t)P * n * sizeof(double), (size_t)B * n * sizeof(double),
+                               (size_t)nz, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(norm.data(), h->ion_norm, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    for (int z = 0; z < nz; ++z)                            // per incident electron: over the norm of the probe, in float64
+        for (int p = 0; p < B; ++p)
+            for (int e = 0; e < n; ++e) out[((size_t)z * B + p) * n + e] /= norm[p];
+    return MSL_OK;
+}
+
+int msl_ionization_reduce(msl_handle* h, int32_t slice, int32_t reps, double* out, double* ms_reduce) {
+    if (!h) return fail(h, MSL_ERR_INVALID, "msl_ionization_reduce: null handle");
+    if (!h->ion_on || !h->ion_W || !h->ion_built)
+        return fail(h, MSL_ERR_STATE, "msl_ionization_reduce: no weight stack (msl_set_ionization, then a build)");
+    if (slice < 0 || slice >= h->cfg.nz) return fail(h, MSL_ERR_INVALID, "msl_ionization_reduce: slice %d outside [0, %d)", slice, h->cfg.nz);
+    if (reps < 1) return fail(h, MSL_ERR_INVALID, "msl_ionization_reduce: reps must be positive");
+    const float2* src = h->psi.p;                       // MSL_BUF_EXIT: whatever the last slice loop left there
+    const int P = h->cfg.n_probes, n = h->ion_n;
+    const size_t npix = (size_t)h->cfg.nx * h->cfg.ny;
+    const float* w = h->ion_W + (size_t)slice * npix;
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    DevBuf<double> dst;
+    int rc = dst.alloc(h, (size_t)P * n);
+    if (rc) return rc;
+    h->cur = nullptr;
+    // the timed launches run between two events of their own, after one untimed pass has sized the slab
+    if (reps > 1 && (rc = ion_reduce_queue(h, src, P, w, npix * h->cfg.nz, n, dst))) return rc;
+    double ms = 0.0;
+    EventPair timer;
+    if ((rc = timer.begin(h)) || (rc = ion_reduce_queue(h, src, P, w, npix * h->cfg.nz, n, dst, reps)) || (rc = timer.end(h, &ms))) {
+        (void)hipStreamSynchronize(h->stream);          // nothing queued reads dst when it is freed
+        return rc;
+    }
+    if (ms_reduce) *ms_reduce = ms / reps;              // (the one finishing sum of the call is in it: take reps large)
+    if (out) HIPCHK(h, hipMemcpy(out, dst, (size_t)P * n * sizeof(double), hipMemcpyDeviceToHost));
+    return MSL_OK;
+}
+
 int msl_build_modes(msl_handle* h, uint64_t seed, int64_t first_frame, int32_t count) {
     return build_generated(h, "msl_build_modes", true, seed, first_frame, count);
 }
@@ -3251,6 +3455,7 @@ int msl_upload_potential(msl_handle* h, const float* V) {
     HIPCHK(h, hipStreamSynchronize(h->stream));
     h->have_potential = true;
     h->abs_built = false;
+    h->ion_built = false;                               // (an uploaded potential has no atoms to make the ionisation weights from)
     return MSL_OK;
 }
 
@@ -3262,6 +3467,12 @@ static int run_loop(msl_handle* h, int slot, int groups, int first_group) {
     // the reduce mode: the exit block is the last layer, reduced behind the epilogue like every tapped one
     const bool reduce = h->lr_on && slot >= 0;
     int rc;
+    if (h->ion_on) {                                        // the loop of the TDS signal, with the ionisation sums on its hook
+        EventPair timer;
+        if ((h->cfg.launch_timing && (rc = timer.begin(h))) || (rc = slice_loop_tds(h, slot, groups, first_group))) return rc;
+        if (reduce && (rc = layer_reduce_queue(h, n_taps(h), h->wf, slot, groups))) return rc;
+        return h->cfg.launch_timing ? timer.end(h, &h->ctr.ms_propagate) : MSL_OK;
+    }
     if (!h->cfg.launch_timing) {                                                         // queued; msl_synchronize / msl_download wait for it
         if ((rc = (h->tds_on ? slice_loop_tds : slice_loop)(h, slot, groups, first_group)) || !reduce) return rc;
         return layer_reduce_queue(h, n_taps(h), h->wf, slot, groups);
@@ -3697,6 +3908,7 @@ size_t msl_buffer_bytes(const msl_handle* h, msl_buffer what) {
         case MSL_BUF_ABSORPTION: return (h->abs_built && h->abs_absorb && h->abs_O) ? npix * c.nz * 4 : 0;
         case MSL_BUF_FORMFACTOR_TDS: return (h->tds_on && h->tds_g && h->ff_n > 0) ? npix * h->n_species * h->tds_n * 4 : 0;
         case MSL_BUF_TDS_WEIGHT: return (h->tds_on && h->abs_built && h->tds_W) ? npix * c.nz * h->tds_n * 4 : 0;
+        case MSL_BUF_IONIZATION_WEIGHT: return (h->ion_on && h->ion_built && h->ion_W) ? npix * c.nz * h->ion_n * 4 : 0;
     }
     return 0;
 }
@@ -3729,6 +3941,7 @@ void* msl_device_ptr(msl_handle* h, msl_buffer what) {
         case MSL_BUF_ABSORPTION: return h->abs_O ? h->abs_O + (size_t)h->cur_batch * h->cfg.nz * h->cfg.nx * h->cfg.ny : nullptr;
         case MSL_BUF_FORMFACTOR_TDS: return h->tds_g;
         case MSL_BUF_TDS_WEIGHT: return h->tds_W;
+        case MSL_BUF_IONIZATION_WEIGHT: return h->ion_W;
     }
     return nullptr;
 }
