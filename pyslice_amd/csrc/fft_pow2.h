@@ -489,6 +489,7 @@ __global__ void __launch_bounds__(256, 2) row_pass2_kernel(Row2Job job) {
     }
 }
 
+constexpr int rowTB_cs(int R) { return R * (R + 1) + 2; }      // tile line pitch: even (16-byte aligned rows for the wide exchange), conflict-free staging
 // ---- lines of ANY length N <= R^2/2: propagation as a zero-padded cyclic convolution on the register FFTs -------------------------
 // The reference's grids are n = int(L/sampling) + 1 points (potentials.py:123-125; its own probe test uses 501 x 491,
 // src/unittests/00_probe.py:7-8), almost never a power of two.  The generic LDS Stockham kernel (fft_generic.h) serves them at
@@ -501,14 +502,13 @@ __global__ void __launch_bounds__(256, 2) row_pass2_kernel(Row2Job job) {
 // three table products per line, for ANY length: a 501 x 491 grid runs at the speed of a 1024 x 1024 one instead of 3.5 x slower.
 // (Round 2's first form evaluated every N-point DFT by Bluestein's chirp-z -- eight FFTs and eleven products per pass; the
 // chirp-z tables live on in the potential's inverse transform, ifftTB_kernel, which does need the spectrum.)
-// Everything else -- prefetch of the next line, t_k in registers across a chunk of probes, 16-line tile, 128-byte transposed
-// segments -- is rowT_pass_kernel's.  The number of lines need not be a multiple of 16: the last tile re-reads the last line and
+// Everything else -- the walk over the work items with t_k in registers across a chunk of probes, the 16-line tile and its
+// 128-byte transposed segments -- is the frame of rowt_frame.h; the next line is prefetched in halves.  The number of lines need not be a multiple of 16: the last tile re-reads the last line and
 // its surplus columns land in the row padding of the output (pitch >= n_lines rounded up to 16), which no pass reads.
 template <int R>
 __global__ void __launch_bounds__(16 * R, (R == 32) ? 2 : 4) rowTB_pass_kernel(RowTJob job) {
     constexpr int M = R * R, H = R / 2, NH = M / 2, LINES = 16, NT = LINES * R, TCH = 8;
-    constexpr int CS = R * (R + 1) + 2;               // even (16-byte aligned rows for the wide exchange), conflict-free staging
-    constexpr int TPS = LINES / 2, POS_PER_IT = NT / TPS, NIT = NH / POS_PER_IT;
+    constexpr int CS = rowTB_cs(R);
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     float2* tw = reinterpret_cast<float2*>(smem_raw);         // M: four-step twiddles
     float2* bf = tw + M;                                      // NH + 2: filter Q, first half
@@ -519,7 +519,6 @@ __global__ void __launch_bounds__(16 * R, (R == 32) ? 2 : 4) rowTB_pass_kernel(R
     for (int i = tid; i <= NH; i += NT) bf[i] = job.bf[i];
     __syncthreads();
     const int grp = tid / R, ln = tid % R;
-    const int q = tid % TPS, r0 = tid / TPS;
     float2* myrow = tile + grp * CS;
     // exchange scratch of the wave (ds_write_addtid_b32 stores): starts at the first tile row of the wave's 64 / R lines
     const float* wscr = reinterpret_cast<const float*>(tile + (grp - grp % (64 / R)) * CS);
@@ -537,47 +536,35 @@ __global__ void __launch_bounds__(16 * R, (R == 32) ? 2 : 4) rowTB_pass_kernel(R
             __builtin_amdgcn_sched_barrier(0);
         }
     };
-    const int lblocks = (job.n_lines + LINES - 1) / LINES;
-    const int PC = job.pchunk;
-    const int pchunks = (job.n_images + PC - 1) / PC;
-    const int n_items = lblocks * pchunks;
-    const int step_lb = (int)gridDim.x / pchunks, step_pc = (int)gridDim.x % pchunks;
-    auto line_ptr = [&](int lbb, int pcc, int kk) {
-        const int L = min(lbb * LINES + grp, job.n_lines - 1);
-        return job.in + (long long)(pcc * PC + kk) * job.in_image_stride + (long long)L * job.in_pitch;
+    auto line_of = [&](int lbb) { return min(lbb * LINES + grp, job.n_lines - 1); };
+    auto line_ptr = [&](const RowTCursor& c) {
+        return job.in + (long long)c.image() * job.in_image_stride + (long long)line_of(c.lb) * job.in_pitch;
     };
-    int item = blockIdx.x;
-    int lb = item / pchunks, pc = item - lb * pchunks, k = 0;
+    RowTCursor cur = RowTCursor::first(job, (job.n_lines + LINES - 1) / LINES);
     float2 vn[H];
-    if (item < n_items) {
-        const float2* r = line_ptr(lb, pc, 0);
+    if (cur.valid()) {
+        const float2* r = line_ptr(cur);
 #pragma unroll
         for (int j = 0; j < H; ++j) vn[j] = (j * R + ln < N) ? r[j * R + ln] : make_float2(0.f, 0.f);
     }
     float2 tv[H];
-    while (item < n_items) {
+    while (cur.valid()) {
         float2 v[R];
 #pragma unroll
         for (int j = 0; j < H; ++j) v[j] = vn[j];
 #pragma unroll
         for (int j = H; j < R; ++j) v[j] = make_float2(0.f, 0.f);
-        const int p = pc * PC + k;
-        const int cur_lb = lb;
-        if (k == 0) {
-            const float2* trow = job.trans + frame_off(job, pc * PC) + (long long)min(lb * LINES + grp, job.n_lines - 1) * N;
+        if (cur.k == 0) {
+            const float2* trow = rowt_trans_row(job, cur, line_of(cur.lb), N);
 #pragma unroll
             for (int j = 0; j < H; ++j) tv[j] = (j * R + ln < N) ? trow[j * R + ln] : make_float2(0.f, 0.f);
         }
-        int nitem = item, nlb = lb, npc = pc, nk = k + 1;
-        if (nk >= min(PC, job.n_images - pc * PC)) {
-            nk = 0; nitem = item + (int)gridDim.x; nlb = lb + step_lb; npc = pc + step_pc;
-            if (npc >= pchunks) { npc -= pchunks; ++nlb; }
-        }
+        const RowTCursor nxt = cur.next();
         auto prefetch_part = [&](auto lo_c, auto hi_c) {
             constexpr int LO = decltype(lo_c)::value, HI = decltype(hi_c)::value;
             __builtin_amdgcn_sched_barrier(0);
-            if (nitem < n_items) {
-                const float2* r = line_ptr(nlb, npc, nk);
+            if (nxt.valid()) {
+                const float2* r = line_ptr(nxt);
 #pragma unroll
                 for (int j = LO; j < HI; ++j) vn[j] = (j * R + ln < N) ? r[j * R + ln] : make_float2(0.f, 0.f);
             }
@@ -603,22 +590,14 @@ __global__ void __launch_bounds__(16 * R, (R == 32) ? 2 : 4) rowTB_pass_kernel(R
 #pragma unroll
         for (int j = 0; j < H; ++j) myrow[j * R + ln] = v[j];
         lds_barrier();
-        float2* dst = job.out + (long long)p * job.out_image_stride + cur_lb * LINES;
-        int off0 = 2 * q + r0 * job.out_pitch;
-        asm volatile("" : "+v"(off0));
-        const int ostep = POS_PER_IT * job.out_pitch;
-#pragma unroll
-        for (int i = 0; i < NIT; ++i) {
-            const int pos = r0 + POS_PER_IT * i;
-            if (pos < N) {
-                const float2 a = tile[(2 * q) * CS + pos], b = tile[(2 * q + 1) * CS + pos];
-                *reinterpret_cast<float4*>(dst + (off0 + i * ostep)) = make_float4(a.x, a.y, b.x, b.y);       // (streaming stores measured 1.8 % slower here)
-            }
-        }
+        // (a plain store: streaming stores measured 1.8 % slower here)
+        tile_store_transposed<LINES, NT, CS, NH, true, false>(tile, rowt_out_image(job, cur) + cur.lb * LINES, job.out_pitch, N, tid);
         lds_barrier();
-        item = nitem; lb = nlb; pc = npc; k = nk;
+        cur = nxt;
     }
 }
+// LDS bytes of a workgroup of rowTB_pass_kernel<R>
+constexpr size_t rowTB_lds_bytes(int R) { return ((size_t)R * R + R * R / 2 + 2 + (size_t)16 * rowTB_cs(R)) * 8; }
 
 // ---- 2048-point register FFT, one wave per line; lines of any length 513..1024 by the cyclic convolution on it ------------------------------
 // A line of M = 2048 points in ONE wave: 64 lanes x 32 registers, element index = reg * 64 + lam(lane), where
@@ -644,6 +623,7 @@ __device__ __forceinline__ float dpp_swap_pair(float x) {          // value of t
     return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0xB1 /* quad_perm [1,0,3,2] */, 0xF, 0xF, true));
 }
 constexpr int W2K_PITCH = 97;               // floats per k1 row of the transpose scratch: n2 < 32 at [0,32), n2 >= 32 at [48,80); 97 = 1 mod 32
+constexpr int W2K_RS = (32 * W2K_PITCH) / 2 + 1;       // tile row of the passes on fft2048_wave in float2 (1553: the transpose scratch; >= 1024 positions; = 17 mod 32)
 
 // tw: LDS table T[k1 * 64 + n2] = exp(-2 pi i k1 n2 / 2048) stored at lds_pos64 (lane L reads tw[k1 * 64 + L]); w64: LDS table [h * 32 + m] = (h ? exp(-2 pi i m / 64) : 1);
 // scr: this wave's scratch of 32 * W2K_PITCH floats; L = lane, la = lam64(L), sgn = (L & 1) ? -1 : +1
@@ -820,7 +800,7 @@ __device__ __forceinline__ void fft2048_wave_io(float2 (&v)[32], float* scr, uns
 template <bool IN_P, bool OUT_P>
 __global__ void __launch_bounds__(512, 2) rowTB2_pass_kernel(RowTJob job) {
     constexpr int R = 32, M = 2048, H = 16, NH = M / 2, LINES = 8, NT = 512, TCH = 8;
-    constexpr int RS = (R * W2K_PITCH) / 2 + 1;        // tile row in float2 (1553: the transpose scratch; >= NH positions; = 17 mod 32)
+    constexpr int RS = W2K_RS;
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     float2* tw = reinterpret_cast<float2*>(smem_raw);         // 2048
     float2* w64 = tw + M;                                     // 64
@@ -849,49 +829,38 @@ __global__ void __launch_bounds__(512, 2) rowTB2_pass_kernel(RowTJob job) {
             __builtin_amdgcn_sched_barrier(0);
         }
     };
-    const int lblocks = (job.n_lines + LINES - 1) / LINES;
-    const int PC = job.pchunk;
-    const int pchunks = (job.n_images + PC - 1) / PC;
-    const int n_items = lblocks * pchunks;
-    const int step_lb = (int)gridDim.x / pchunks, step_pc = (int)gridDim.x % pchunks;
     constexpr int ES = IN_P ? 2 : 1;
-    auto line_ptr = [&](int lbb, int pcc, int kk) {
-        const int Lc = min(lbb * LINES + wv, job.n_lines - 1);
+    auto line_of = [&](int lbb) { return min(lbb * LINES + wv, job.n_lines - 1); };
+    auto line_ptr = [&](const RowTCursor& c) {
+        const int Lc = line_of(c.lb);
         const long long off = IN_P ? (long long)(Lc >> 1) * (2 * job.in_pitch) + (Lc & 1) : (long long)Lc * job.in_pitch;
-        return job.in + (long long)(pcc * PC + kk) * job.in_image_stride + off;
+        return job.in + (long long)c.image() * job.in_image_stride + off;
     };
-    int item = blockIdx.x;
-    int lb = item / pchunks, pc = item - lb * pchunks, k = 0;
+    RowTCursor cur = RowTCursor::first(job, (job.n_lines + LINES - 1) / LINES);
     float2 vn[H];
-    if (item < n_items) {
-        const float2* r = line_ptr(lb, pc, 0);
+    if (cur.valid()) {
+        const float2* r = line_ptr(cur);
 #pragma unroll
         for (int j = 0; j < H; ++j) vn[j] = (j * 64 + la < N) ? ld_stream(r + ((j * 64 + la) * ES)) : make_float2(0.f, 0.f);
     }
     float2 tv[H];
-    while (item < n_items) {
+    while (cur.valid()) {
         float2 v[R];
 #pragma unroll
         for (int j = 0; j < H; ++j) v[j] = vn[j];
 #pragma unroll
         for (int j = H; j < R; ++j) v[j] = make_float2(0.f, 0.f);
-        const int p = pc * PC + k;
-        const int cur_lb = lb;
-        if (k == 0) {
-            const float2* trow = job.trans + frame_off(job, pc * PC) + (long long)min(lb * LINES + wv, job.n_lines - 1) * N;
+        if (cur.k == 0) {
+            const float2* trow = rowt_trans_row(job, cur, line_of(cur.lb), N);
 #pragma unroll
             for (int j = 0; j < H; ++j) tv[j] = (j * 64 + la < N) ? trow[j * 64 + la] : make_float2(0.f, 0.f);
         }
-        int nitem = item, nlb = lb, npc = pc, nk = k + 1;
-        if (nk >= min(PC, job.n_images - pc * PC)) {
-            nk = 0; nitem = item + (int)gridDim.x; nlb = lb + step_lb; npc = pc + step_pc;
-            if (npc >= pchunks) { npc -= pchunks; ++nlb; }
-        }
+        const RowTCursor nxt = cur.next();
         auto prefetch_part = [&](auto lo_c, auto hi_c) {
             constexpr int LO = decltype(lo_c)::value, HI = decltype(hi_c)::value;
             __builtin_amdgcn_sched_barrier(0);
-            if (nitem < n_items) {
-                const float2* r = line_ptr(nlb, npc, nk);
+            if (nxt.valid()) {
+                const float2* r = line_ptr(nxt);
 #pragma unroll
                 for (int j = LO; j < HI; ++j) vn[j] = (j * 64 + la < N) ? ld_stream(r + ((j * 64 + la) * ES)) : make_float2(0.f, 0.f);
             }
@@ -922,7 +891,7 @@ __global__ void __launch_bounds__(512, 2) rowTB2_pass_kernel(RowTJob job) {
             const int i = tid & 7, oct = tid >> 3, q = oct & 3, hh = oct >> 2;
             const int mm0 = (hh & 3) + 4 * q + 16 * (hh >> 2);             // 0 .. 63
             const float2* src = tile + i * RS + 2 * mm0;
-            float2* dst = job.out + (long long)p * job.out_image_stride + 2 * (cur_lb * LINES + i);
+            float2* dst = rowt_out_image(job, cur) + 2 * (cur.lb * LINES + i);
             int off0 = mm0 * 2 * job.out_pitch;
             asm volatile("" : "+v"(off0));
             const int ostep = 64 * 2 * job.out_pitch;
@@ -933,25 +902,15 @@ __global__ void __launch_bounds__(512, 2) rowTB2_pass_kernel(RowTJob job) {
                     st_stream(dst + (off0 + it * ostep), a.x, a.y, b.x, b.y);
                 }
             }
-        } else {
-            const int q4 = tid & 3, e0 = tid >> 2;                         // natural output: 8 lines = 64-byte segments
-            float2* dst = job.out + (long long)p * job.out_image_stride + cur_lb * LINES + 2 * q4;
-            int off0 = e0 * job.out_pitch;
-            asm volatile("" : "+v"(off0));
-            const int ostep = (NT / 4) * job.out_pitch;
-#pragma unroll
-            for (int it = 0; it < NH / (NT / 4); ++it) {
-                const int e = e0 + (NT / 4) * it;
-                if (e < N) {
-                    const float2 a = tile[(2 * q4) * RS + e], b = tile[(2 * q4 + 1) * RS + e];
-                    st_stream(dst + (off0 + it * ostep), a.x, a.y, b.x, b.y);
-                }
-            }
+        } else {                                                           // natural output: 8 lines = 64-byte segments
+            tile_store_transposed<LINES, NT, RS, NH, true, true>(tile, rowt_out_image(job, cur) + cur.lb * LINES, job.out_pitch, N, tid);
         }
         lds_barrier();
-        item = nitem; lb = nlb; pc = npc; k = nk;
+        cur = nxt;
     }
 }
+// LDS bytes of a workgroup of rowTB2_pass_kernel
+constexpr size_t rowTB2_lds_bytes() { return ((size_t)2048 + 64 + 1024 + 2 + (size_t)8 * W2K_RS) * 8; }
 
 // Transposing pass A . t_k . A for lines of 1025 .. 2047 points: the convolution form of rowTB2_pass_kernel with the cyclic length
 // M = 4096, the 4096-point transforms built from fft2048_wave by one radix-2 step that the zero padding makes half trivial:
@@ -967,7 +926,7 @@ __global__ void __launch_bounds__(512, 2) rowTB2_pass_kernel(RowTJob job) {
 // job.bf: Q[2k] (k = 0..1024, padded to 1026) followed by Q[2k+1] (k = 0..1023); job.bw: W_4096^n, n < 2048; job.n_line = N.
 __global__ void __launch_bounds__(512, 2) rowTC2_pass_kernel(RowTJob job) {
     constexpr int R = 32, M2 = 2048, LINES = 4, NT = 512, TCH = 8;
-    constexpr int RS = (R * W2K_PITCH) / 2 + 1;
+    constexpr int RS = W2K_RS;
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     float2* tw = reinterpret_cast<float2*>(smem_raw);         // 2048, lane order
     float2* w64 = tw + M2;                                    // 64
@@ -1085,15 +1044,18 @@ __global__ void __launch_bounds__(512, 2) rowTC2_pass_kernel(RowTJob job) {
         lds_barrier();
     }
 }
+// LDS bytes of a workgroup of rowTC2_pass_kernel
+constexpr size_t rowTC2_lds_bytes() { return ((size_t)2048 + 64 + 2048 + 2 * 1026 + (size_t)8 * W2K_RS) * 8; }
 
+constexpr int ROWTW_RS = 2048 + 1;                            // tile row in float2 (>= the 32 x 97 floats of transpose scratch; = 1 mod 32)
+constexpr int ROWTW_NHT = 2048 / 2 + 64;                      // Fresnel table: N/2 + 2 entries; the last block is stored in lane order too
 // Transposing pass A . t_k . A for 2048-point lines on fft2048_wave: one wave per line, 8 lines per workgroup, the next line
-// prefetched in registers, t_k in registers across a chunk of probes (rowT_pass_kernel's scheme; the 2 R^2 layout of
+// prefetched in registers, t_k in registers across a chunk of probes (the frame of rowt_frame.h; the 2 R^2 layout of
 // rowT2_pass_kernel<32> has room for neither).  IN_P / OUT_P: paired-lines layout of the work buffers between two passes.
 template <bool IN_P, bool OUT_P>
 __global__ void __launch_bounds__(512, 2) rowTW_pass_kernel(RowTJob job) {
     constexpr int R = 32, N = 2048, H = 16, LINES = 8, NT = 512, TCH = 8;
-    constexpr int RS = N + 1;                                 // tile row in float2 (>= the 32 x 97 floats of transpose scratch; = 1 mod 32)
-    constexpr int NHT = N / 2 + 64;                           // N/2 + 2 entries; the last block is stored in lane order too
+    constexpr int RS = ROWTW_RS, NHT = ROWTW_NHT;
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     float2* tw = reinterpret_cast<float2*>(smem_raw);         // 2048
     float2* w64 = tw + N;                                     // 64
@@ -1122,11 +1084,6 @@ __global__ void __launch_bounds__(512, 2) rowTW_pass_kernel(RowTJob job) {
             __builtin_amdgcn_sched_barrier(0);
         }
     };
-    const int lblocks = job.n_lines / LINES;
-    const int PC = job.pchunk;
-    const int pchunks = (job.n_images + PC - 1) / PC;
-    const int n_items = lblocks * pchunks;
-    const int step_lb = (int)gridDim.x / pchunks, step_pc = (int)gridDim.x % pchunks;
     // The work buffer between two of these passes (IN_P / OUT_P): lines in pairs -- the pair L/2 shares a row of 2 x pitch entries --
     // and inside a pair the elements in chunks of 128: entry 256 (e >> 7) + ((2 (e & 63) + (L & 1)) * 2 + ((e >> 6) & 1)) holds element
     // e of line L.  A lane's registers 2 jp and 2 jp + 1 (elements 128 jp + la and 128 jp + 64 + la) are adjacent: 16-byte loads, a
@@ -1138,10 +1095,10 @@ __global__ void __launch_bounds__(512, 2) rowTW_pass_kernel(RowTJob job) {
         if constexpr (OUT_P) return 128 * (lbb >> 4) + 64 * (wv & 1) + 4 * (lbb & 15) + (wv >> 1);
         else return lbb * LINES + wv;
     };
-    auto line_ptr = [&](int lbb, int pcc, int kk) {
-        const int Ln = line_of(lbb);
+    auto line_ptr = [&](const RowTCursor& c) {
+        const int Ln = line_of(c.lb);
         const long long off = IN_P ? (long long)(Ln >> 1) * (2 * job.in_pitch) + (2 * L + (Ln & 1)) * 2 : (long long)Ln * job.in_pitch + L;     // identity layout: element 64 j + L
-        return job.in + (long long)(pcc * PC + kk) * job.in_image_stride + off;
+        return job.in + (long long)c.image() * job.in_image_stride + off;
     };
     auto load_regs = [&](float2 (&dst)[R], const float2* r, auto lo_c, auto hi_c) {
         constexpr int LO = decltype(lo_c)::value, HI = decltype(hi_c)::value;
@@ -1156,16 +1113,15 @@ __global__ void __launch_bounds__(512, 2) rowTW_pass_kernel(RowTJob job) {
             for (int j = LO; j < HI; ++j) dst[j] = ld_stream(r + j * 64);
         }
     };
-    int item = blockIdx.x;
-    int lb = item / pchunks, pc = item - lb * pchunks, k = 0;
+    RowTCursor cur = RowTCursor::first(job, job.n_lines / LINES);
     float2 vn[R];
-    if (item < n_items) load_regs(vn, line_ptr(lb, pc, 0), MSL_IC(0), MSL_IC(R));
+    if (cur.valid()) load_regs(vn, line_ptr(cur), MSL_IC(0), MSL_IC(R));
     __builtin_amdgcn_s_waitcnt(0x0F70);               // vmcnt(0): nothing in flight at the loop entry, see rowT_pass_kernel
     float2 tv[R];
 #ifdef MSL_CLOCK
     const unsigned long long clk0 = __builtin_amdgcn_s_memtime(), rt0 = __builtin_amdgcn_s_memrealtime();
 #endif
-    while (item < n_items) {
+    while (cur.valid()) {
         // (No stagger of the waves here.  This pass is not at the power limit -- 1 210-1 280 W, 2.29 GHz -- but its eight waves run in
         // lockstep between the two barriers of an iteration and meet at every exchange: without the tile, the barriers and the store
         // phase an iteration takes 28.9 k cycles, with the two barriers alone 40.0 k, complete 44.5 k (tools/rowtw_bench.hip,
@@ -1180,21 +1136,14 @@ __global__ void __launch_bounds__(512, 2) rowTW_pass_kernel(RowTJob job) {
         float2 v[R];
 #pragma unroll
         for (int j = 0; j < R; ++j) v[j] = vn[j];
-        const int p = pc * PC + k;
-        const int cur_lb = lb;
-        if (k == 0) {
-            const float2* trow = job.trans + frame_off(job, pc * PC) + (long long)line_of(lb) * N + L;
+        if (cur.k == 0) {
+            const float2* trow = rowt_trans_row(job, cur, line_of(cur.lb), N) + L;
 #pragma unroll
             for (int j = 0; j < R; ++j) tv[j] = trow[j * 64];
         }
-        int nitem = item, nlb = lb, npc = pc, nk = k + 1;
-        if (nk >= min(PC, job.n_images - pc * PC)) {
-            nk = 0; nitem = item + (int)gridDim.x; nlb = lb + step_lb; npc = pc + step_pc;
-            if (npc >= pchunks) { npc -= pchunks; ++nlb; }
-        }
+        const RowTCursor nxt = cur.next();
         // unconditional prefetch (past the last item: the current line again), one address per iteration
-        const bool more = nitem < n_items;
-        const float2* nptr = line_ptr(more ? nlb : lb, more ? npc : pc, more ? nk : k);
+        const float2* nptr = line_ptr(cur.prefetch_target(nxt));
         auto prefetch_part = [&](auto lo_c, auto hi_c) {
             constexpr int LO = decltype(lo_c)::value, HI = decltype(hi_c)::value;
             __builtin_amdgcn_sched_barrier(0);
@@ -1223,49 +1172,39 @@ __global__ void __launch_bounds__(512, 2) rowTW_pass_kernel(RowTJob job) {
 #pragma unroll
             for (int j = 0; j < R; ++j) acc += v[j].x + v[j].y;
             if (acc == 1.2345e-30f) job.out[tid] = make_float2(acc, acc);
-            item = nitem; lb = nlb; pc = npc; k = nk;
-            continue;
-        }
-        wave_lds_fence();
-        if constexpr (!(MSL_ABL2 & 128)) {
-#pragma unroll
-        for (int j = 0; j < R; ++j) myrow[j * 64 + lam64_inv(L)] = v[j];          // element 64 j + L at lds_pos64
-        }
-        lds_barrier();
-        if constexpr (MSL_ABL2 & 64) {
-        } else if constexpr (OUT_P) {
-            // one 16-byte store = position 2 mm + c of the tile rows 2 i and 2 i + 1 (blocks 2 jp / 2 jp + 1 of the output line pair
-            // mm); eight lanes (i, c) make a 128-byte run; the four octets of a half-wave take pairs 8 positions apart (LDS banks)
-            const int i8 = tid & 7, i = i8 >> 1, c = i8 & 1, oct = tid >> 3, q = oct & 3, hh = oct >> 2;
-            const int mm0 = 2 * q + (hh & 1) + 8 * ((hh >> 1) & 1) + 16 * ((hh >> 2) & 1) + 32 * (hh >> 3);
-            const float2* src = tile + (2 * i) * RS + lds_pos64(2 * mm0 + c);
-            float2* dst = job.out + (long long)p * job.out_image_stride + 256 * (cur_lb >> 4) + (2 * (4 * (cur_lb & 15) + i) + c) * 2;
-            int off0 = mm0 * 2 * job.out_pitch;
-            asm volatile("" : "+v"(off0));
-            const int ostep = 64 * 2 * job.out_pitch;
-#pragma unroll
-            for (int it = 0; it < N / 2 / 64; ++it) {
-                const float2 a = src[it * 128], b = src[RS + it * 128];
-#if MSL_ABL2 & 2
-                if (a.x == 1.2345e-30f)
-#endif
-                st_stream(dst + (off0 + it * ostep), a.x, a.y, b.x, b.y);
-            }
         } else {
-            const int q4 = tid & 3, e0 = tid >> 2;
-            float2* dst = job.out + (long long)p * job.out_image_stride + cur_lb * LINES + 2 * q4;
-            int off0 = e0 * job.out_pitch;
-            asm volatile("" : "+v"(off0));
-            const int ostep = (NT / 4) * job.out_pitch;
+            wave_lds_fence();
+            if constexpr (!(MSL_ABL2 & 128)) {
 #pragma unroll
-            for (int it = 0; it < N / (NT / 4); ++it) {
-                const int e = e0 + (NT / 4) * it;
-                const float2 a = tile[(2 * q4) * RS + lds_pos64(e)], b = tile[(2 * q4 + 1) * RS + lds_pos64(e)];
-                st_stream(dst + (off0 + it * ostep), a.x, a.y, b.x, b.y);
+            for (int j = 0; j < R; ++j) myrow[j * 64 + lam64_inv(L)] = v[j];          // element 64 j + L at lds_pos64
             }
+            lds_barrier();
+            if constexpr (MSL_ABL2 & 64) {
+            } else if constexpr (OUT_P) {
+                // one 16-byte store = position 2 mm + c of the tile rows 2 i and 2 i + 1 (blocks 2 jp / 2 jp + 1 of the output line pair
+                // mm); eight lanes (i, c) make a 128-byte run; the four octets of a half-wave take pairs 8 positions apart (LDS banks)
+                const int i8 = tid & 7, i = i8 >> 1, c = i8 & 1, oct = tid >> 3, q = oct & 3, hh = oct >> 2;
+                const int mm0 = 2 * q + (hh & 1) + 8 * ((hh >> 1) & 1) + 16 * ((hh >> 2) & 1) + 32 * (hh >> 3);
+                const float2* src = tile + (2 * i) * RS + lds_pos64(2 * mm0 + c);
+                float2* dst = rowt_out_image(job, cur) + 256 * (cur.lb >> 4) + (2 * (4 * (cur.lb & 15) + i) + c) * 2;
+                int off0 = mm0 * 2 * job.out_pitch;
+                asm volatile("" : "+v"(off0));
+                const int ostep = 64 * 2 * job.out_pitch;
+#pragma unroll
+                for (int it = 0; it < N / 2 / 64; ++it) {
+                    const float2 a = src[it * 128], b = src[RS + it * 128];
+#if MSL_ABL2 & 2
+                    if (a.x == 1.2345e-30f)
+#endif
+                    st_stream(dst + (off0 + it * ostep), a.x, a.y, b.x, b.y);
+                }
+            } else {
+                tile_store_transposed<LINES, NT, RS, N, false, true>(tile, rowt_out_image(job, cur) + cur.lb * LINES, job.out_pitch, N, tid,
+                                                                     [](int e) { return lds_pos64(e); });
+            }
+            lds_barrier();
         }
-        lds_barrier();
-        item = nitem; lb = nlb; pc = npc; k = nk;
+        cur = nxt;
     }
 #ifdef MSL_CLOCK
     if (tid == 0 && job.clk) {
@@ -1274,6 +1213,8 @@ __global__ void __launch_bounds__(512, 2) rowTW_pass_kernel(RowTJob job) {
     }
 #endif
 }
+// LDS bytes of a workgroup of rowTW_pass_kernel
+constexpr size_t rowTW_lds_bytes() { return ((size_t)2048 + 64 + ROWTW_NHT + (size_t)8 * ROWTW_RS) * 8; }
 
 // ---- lines of N = 2 R^2 points (512 = 2*16^2) ---------------------------------------------------------------
 // One radix-2 step wrapped around two four-step transforms.  A group of R lanes holds two register sets; in the
@@ -1327,8 +1268,9 @@ __device__ __forceinline__ void line2_transform(float2 (&v)[2 * R], float* scrat
     }
 }
 
-// Transposing pass A . t_k . A for N = 2 R^2 with R = 16 (N = 512): next line prefetched and t_k kept in registers like
-// rowT_pass_kernel, full-line tile.  (2048 = 2 * 32^2 holds 64 complex per lane in this layout, with room for neither: 2048-point
+constexpr int rowT2_cs(int R) { return 2 * R * R + 2; }         // tile line pitch: 2 mod 32 -- conflict-free staging
+// Transposing pass A . t_k . A for N = 2 R^2 with R = 16 (N = 512): next line prefetched and t_k kept in registers (the frame of
+// rowt_frame.h), full-line tile.  (2048 = 2 * 32^2 holds 64 complex per lane in this layout, with room for neither: 2048-point
 // lines run on the wave-per-line transform, rowTW_pass_kernel.)
 // IN_P / OUT_P: interleaved line order of the work buffer on the input / output side (see rowT_pass_kernel): 16-byte loads.
 template <int R, bool IN_P = false, bool OUT_P = false>
@@ -1336,9 +1278,7 @@ __global__ void __launch_bounds__(16 * R, 2) rowT2_pass_kernel(RowTJob job) {   
     static_assert(R == 16, "the 2 R^2 layout is used for 512-point lines only");
     constexpr int N2 = R * R, N = 2 * N2, NT = 16 * R;
     constexpr int XM = 2;                              // exchange: 16-byte reads and add-tid stores (rows 16-byte aligned: even pitch)
-    constexpr int CS = N + 2;                          // tile line pitch: 2 mod 32 -- conflict-free staging
-    constexpr int POS_PER_IT = NT / 8;
-    constexpr int NIT = N / POS_PER_IT;
+    constexpr int CS = rowT2_cs(R);
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     float2* tw = reinterpret_cast<float2*>(smem_raw);            // N2: four-step twiddles
     float2* tw2 = tw + N2;                                       // N2: W_N^m of the outer radix-2 step
@@ -1349,17 +1289,10 @@ __global__ void __launch_bounds__(16 * R, 2) rowT2_pass_kernel(RowTJob job) {   
     for (int i = tid; i < N; i += NT) pl[i] = job.pl[i];
     __syncthreads();
     const int grp = tid / R, ln = tid % R;
-    const int q = tid & 7, r0 = tid >> 3;
     float* scratch = reinterpret_cast<float*>(tile + grp * CS);
     const float* wscr = reinterpret_cast<const float*>(tile + (grp - grp % (64 / R)) * CS);     // the wave's shared exchange scratch
     const unsigned wscr_lds = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(tile + (grp - grp % (64 / R)) * CS));
-    const int lblocks = job.n_lines / 16;
-    const int PC = job.pchunk;
-    const int pchunks = (job.n_images + PC - 1) / PC;
-    const int n_items = lblocks * pchunks;
-    const int step_lb = (int)gridDim.x / pchunks, step_pc = (int)gridDim.x % pchunks;
-    int item = blockIdx.x;
-    int lb = item / pchunks, pc = item % pchunks, k = 0;
+    RowTCursor cur = RowTCursor::first(job, job.n_lines / 16);
     // input line of tile row g in line block lbb (OUT_P: 8 lines of block 2 jp and the same 8 of block 2 jp + 1 of the reader's
     // 2 R' chunks; the thread index is re-derived at every use: the kernel sits at its register limit)
     auto line_of = [&](int lbb, int g) {
@@ -1370,7 +1303,7 @@ __global__ void __launch_bounds__(16 * R, 2) rowT2_pass_kernel(RowTJob job) {   
             return lbb * 16 + g;
         }
     };
-    auto image_base = [&](int pcc, int kk) { return job.in + (long long)(pcc * PC + kk) * job.in_image_stride; };
+    auto image_base = [&](const RowTCursor& c) { return job.in + (long long)c.image() * job.in_image_stride; };
     auto load_line = [&](float2 (&dst)[2 * R], const float2* img, int lbb) {
         int t = tid;
         asm volatile("" : "+v"(t));
@@ -1389,26 +1322,20 @@ __global__ void __launch_bounds__(16 * R, 2) rowT2_pass_kernel(RowTJob job) {   
     };
     float2 vn[2 * R];
     float2 tv[2 * R];
-    if (item < n_items) load_line(vn, image_base(pc, 0), lb);
-    while (item < n_items) {
+    if (cur.valid()) load_line(vn, image_base(cur), cur.lb);
+    while (cur.valid()) {
         float2 v[2 * R];
 #pragma unroll
         for (int j = 0; j < 2 * R; ++j) v[j] = vn[j];
-        const int p = pc * PC + k;
-        const int cur_lb = lb;
-        if (k == 0) {
+        if (cur.k == 0) {
             int toff = tid;                               // re-derived here (one chunk of probes in PC): not worth a register across the loop
             asm volatile("" : "+v"(toff));
-            const float2* trow = job.trans + frame_off(job, pc * PC) + (long long)line_of(lb, toff / R) * N + (toff % R);
+            const float2* trow = rowt_trans_row(job, cur, line_of(cur.lb, toff / R), N) + (toff % R);
 #pragma unroll
             for (int j = 0; j < 2 * R; ++j) tv[j] = trow[j * R];
         }
-        int nitem = item, nlb = lb, npc = pc, nk = k + 1;
-        if (nk >= min(PC, job.n_images - pc * PC)) {
-            nk = 0; nitem = item + (int)gridDim.x; nlb = lb + step_lb; npc = pc + step_pc;
-            if (npc >= pchunks) { npc -= pchunks; ++nlb; }
-        }
-        if (nitem < n_items) load_line(vn, image_base(npc, nk), nlb);      // (a mid-iteration prefetch as in rowT_pass_kernel measured 3% slower here)
+        const RowTCursor nxt = cur.next();
+        if (nxt.valid()) load_line(vn, image_base(nxt), nxt.lb);      // (a mid-iteration prefetch as in rowT_pass_kernel measured 3% slower here)
         if (job.flags & P2_PRE_A) {
             line2_transform<R, false, XM>(v, scratch, tw, tw2, ln, wscr, wscr_lds, tid & 63);
             mul_table<2 * R, 0, false, R>(v, pl, ln);
@@ -1421,25 +1348,18 @@ __global__ void __launch_bounds__(16 * R, 2) rowT2_pass_kernel(RowTJob job) {   
             mul_table<2 * R, 0, false, R>(v, pl, ln);
             line2_transform<R, true, XM>(v, scratch, tw, tw2, ln, wscr, wscr_lds, tid & 63);
         }
-        float2* dst = job.out + ((long long)p * job.out_image_stride + cur_lb * 16);
-        int off0 = 2 * q + r0 * job.out_pitch;
-        asm volatile("" : "+v"(off0));
-        const int ostep = POS_PER_IT * job.out_pitch;
         wave_lds_fence();
         float2* myrow = tile + grp * CS;
 #pragma unroll
         for (int j = 0; j < N / R; ++j) myrow[j * R + ln] = v[j];
         lds_barrier();
-#pragma unroll
-        for (int i = 0; i < NIT; ++i) {
-            const int pos = r0 + POS_PER_IT * i;
-            const float2 a = tile[(2 * q) * CS + pos], b = tile[(2 * q + 1) * CS + pos];
-            st_stream(dst + (off0 + i * ostep), a.x, a.y, b.x, b.y);
-        }
+        tile_store_transposed<16, NT, CS, N, false, true>(tile, rowt_out_image(job, cur) + cur.lb * 16, job.out_pitch, N, tid);
         lds_barrier();
-        item = nitem; lb = nlb; pc = npc; k = nk;
+        cur = nxt;
     }
 }
+// LDS bytes of a workgroup of rowT2_pass_kernel<R>
+constexpr size_t rowT2_lds_bytes(int R) { return ((size_t)2 * R * R + 2 * R * R + (size_t)16 * rowT2_cs(R)) * 8; }
 
 // out[img][c][r] = in[img][r][c]  (rows x cols -> cols x rows), 32x32 tiles through LDS
 __global__ void __launch_bounds__(256) transpose_kernel(const float2* __restrict__ in, float2* __restrict__ out, int rows,

@@ -1049,8 +1049,8 @@ int paired_dispatch(const RowTJob& job, F&& launch) {
 // lines of 2 R^2 = 512 points
 template <bool IN_P, bool OUT_P>
 int launch_rowT2_io(msl_handle* h, RowTJob job, int kind) {
-    constexpr int R = 16, N2 = R * R, N = 2 * N2;
-    const size_t lds = ((size_t)2 * N2 + N + (size_t)16 * (N + 2)) * 8;
+    constexpr int R = 16;
+    const size_t lds = rowT2_lds_bytes(R);
     const int per_cu = std::max(1, std::min(2, (int)((size_t)h->lds_limit / lds)));
     const int grid = chunked_grid(h, job, job.n_lines / 16, (long long)h->n_cus * per_cu);
     return launch_lds(h, rowT2_pass_kernel<R, IN_P, OUT_P>, dim3(grid), dim3(16 * R), lds, kind, job);
@@ -1059,8 +1059,7 @@ int launch_rowT2_io(msl_handle* h, RowTJob job, int kind) {
 // lines of any length <= R^2/2: zero-padded cyclic convolution on the register FFTs
 template <int R>
 int launch_rowTB_r(msl_handle* h, RowTJob job, int kind) {
-    constexpr int M = R * R, NH = M / 2, CS = R * (R + 1) + 2;
-    const size_t lds = ((size_t)M + NH + 2 + (size_t)16 * CS) * 8;
+    const size_t lds = rowTB_lds_bytes(R);
     const int per_cu = std::max(1, std::min(R == 16 ? 4 : 1, (int)((size_t)h->lds_limit / lds)));
     const int grid = chunked_grid(h, job, (job.n_lines + 15) / 16, (long long)h->n_cus * per_cu);
     return launch_lds(h, rowTB_pass_kernel<R>, dim3(grid), dim3(16 * R), lds, kind, job);
@@ -1069,19 +1068,15 @@ int launch_rowTB_r(msl_handle* h, RowTJob job, int kind) {
 // lines of 513..1024 points: the same convolution on the wave-per-line 2048-point register FFT
 template <bool IN_P, bool OUT_P>
 int launch_rowTB2_io(msl_handle* h, RowTJob job, int kind) {
-    constexpr int M = 2048, NH = M / 2, RS = (32 * W2K_PITCH) / 2 + 1;
-    const size_t lds = ((size_t)M + 64 + NH + 2 + (size_t)8 * RS) * 8;
     const int grid = chunked_grid(h, job, (job.n_lines + 7) / 8, h->n_cus);
-    return launch_lds(h, rowTB2_pass_kernel<IN_P, OUT_P>, dim3(grid), dim3(512), lds, kind, job);
+    return launch_lds(h, rowTB2_pass_kernel<IN_P, OUT_P>, dim3(grid), dim3(512), rowTB2_lds_bytes(), kind, job);
 }
 
 // 2048-point lines, one wave per line (fft2048_wave)
 template <bool IN_P, bool OUT_P>
 int launch_rowTW_io(msl_handle* h, RowTJob job, int kind) {
-    constexpr int N = 2048;
-    const size_t lds = ((size_t)N + 64 + N / 2 + 64 + (size_t)8 * (N + 1)) * 8;
     const int grid = chunked_grid(h, job, job.n_lines / 8, h->n_cus);
-    return launch_lds(h, rowTW_pass_kernel<IN_P, OUT_P>, dim3(grid), dim3(512), lds, kind, job);
+    return launch_lds(h, rowTW_pass_kernel<IN_P, OUT_P>, dim3(grid), dim3(512), rowTW_lds_bytes(), kind, job);
 }
 
 // lines of a smooth length A * B (A, B <= 32; G = 16 / 32 lanes per line) or 2 A * B (G = 64: one wave per line, tiles of 8 lines):
@@ -1139,12 +1134,10 @@ int launch_rowT_dir(msl_handle* h, const msl_handle::OpDir& o, RowTJob job, int 
     case AX_CONV4K: {                       // 1025 .. 2047 points: cyclic convolution of length 4096, two waves per line
         job.n_line = o.n;
         job.tw = o.tw; job.tw2 = o.tw2; job.bf = o.qf; job.bw = o.bw; job.pl = nullptr;
-        constexpr int RS = (32 * W2K_PITCH) / 2 + 1;
-        const size_t lds = ((size_t)2048 + 64 + 2048 + 2052 + (size_t)8 * RS) * 8;
         job.pchunk = 1;
         const long long items2 = (long long)((job.n_lines + 3) / 4) * job.n_images;
         const int grid2 = (int)std::min<long long>(items2, (long long)h->n_cus);
-        return launch_lds(h, rowTC2_pass_kernel, dim3(grid2), dim3(512), lds, kind, job);
+        return launch_lds(h, rowTC2_pass_kernel, dim3(grid2), dim3(512), rowTC2_lds_bytes(), kind, job);
     }
     case AX_CONV:                           // A as one cyclic convolution of length M (two FFTs); bf = its filter
     case AX_CONV2K:

@@ -14,13 +14,8 @@
 #include <hip/hip_runtime.h>
 #include "fft_regs.h"
 #include "kernel_util.h"
+#include "rowt_frame.h"
 
-// Ablation switches of tools/rowt_bench.hip (timing experiments on this pass; wrong results): 1 = no prefetch loads, 2 = no
-// global stores (the tile reads stay), 4 = no lane <-> register exchanges, 8 = no transforms at all, 16 = one table entry instead
-// of the table reads (the Fresnel factors and the twiddles that are not kept in registers), 32 = no tile write / barriers / store phase.  Never set in the library.
-#ifndef MSL_ABL2
-#define MSL_ABL2 0
-#endif
 #ifndef MSL_TW_LDS
 #define MSL_TW_LDS 0            // 1: the inter-FFT twiddles are read from the LDS table in every transform (the form before the register column)
 #endif
@@ -36,42 +31,6 @@
 #define MSL_IC(x) std::integral_constant<int, (x)>{}
 
 namespace msl {
-
-enum { P2_PRE_A = 1, P2_POST_A = 2, P2_POST_F = 4, P2_IN_PAIRED = 8, P2_OUT_PAIRED = 16 };
-
-struct RowTJob {
-    const float2* in;       // (P, n_lines, in_pitch): lines along the transform axis
-    float2* out;            // (P, N, out_pitch): transposed
-    const float2* trans;    // t_k in the input orientation, (n_lines, N) unpadded
-    const float2* pl;       // (N) Fresnel factor along the line axis, 1/N folded in (split order for N = 2R^2)
-    const float2* tw;
-    const float2* tw2;      // N = 2R^2 only: W_N^m, m < R^2
-    long long in_image_stride, out_image_stride;
-    int in_pitch, out_pitch, n_lines, n_images, flags, pchunk;
-    int t_group;            // frame batching: images [g t_group, (g+1) t_group) use the stack trans + g t_stride (0: one stack)
-    unsigned t_magic;       // floor(2^32 / t_group) + 1
-    long long t_stride;
-    // rowTB_pass_kernel (lines of any length N <= R^2/2 by Bluestein's chirp-z on the register FFTs of length M = R^2):
-    const float2* bf;       // (M/2 + 1) filter FFT_M(conj chirp, wrapped) / M -- an even sequence, first half stored
-    const float2* bw;       // (M/2) chirp w[n] = exp(-i pi n^2 / N), zero for n >= N
-    int n_line;             // N
-    int perm_shift;         // rowT_pass_kernel<.., OUT_P>: log2(R' / 8), R' = radix of the kernel that reads the output lines
-#ifdef MSL_CLOCK
-    unsigned long long* clk;    // tools/rowt_bench.hip -DMSL_CLOCK: per workgroup, shader cycles and 100 MHz ticks spent in the item loop
-#endif
-};
-
-// transmission stack of the frame that image p belongs to: job.trans + frame_off(job, p).  p is wave-uniform and the
-// frame number p / t_group is computed in scalar registers only -- a multiply-high by t_magic = floor(2^32 / t_group) + 1,
-// exact while p * t_group < 2^32 -- because these kernels run within a few VGPRs of the 256 that two waves per SIMD allow:
-// a vector temporary here pushed rowT2_pass_kernel<16> into the AGPRs and halved its occupancy (81 -> 117 us per pass).
-template <typename Job>
-__device__ __forceinline__ long long frame_off(const Job& job, int p) {
-    if (job.t_group <= 0) return 0;
-    const unsigned up = (unsigned)__builtin_amdgcn_readfirstlane(p);
-    const unsigned f = job.t_group == 1 ? up : __umulhi(up, job.t_magic);        // (the magic number of 1 does not fit 32 bits)
-    return (long long)f * job.t_stride;
-}
 
 // ---- four-step transform on the decimation-in-time network of fft_regs.h (fused multiply-adds) --------------------------------
 // A line of N = R^2 points lives in a group of R lanes x R registers, element n = reg R + lane before and after a transform:
@@ -167,7 +126,8 @@ constexpr int rowT_tw_reg_leaves(int R, int FL) { return (!MSL_TW_LDS && R == 32
 constexpr int ROWT_TW_REG_LCH = 4;
 
 // ---- the kernel -------------------------------------------------------------------------------------------------------------------
-// Work item = (block of 16 lines, chunk of `pchunk` images that share t_k): the t_k lines stay in registers across the chunk.
+// Work item = (block of 16 lines, chunk of `pchunk` images that share t_k): the t_k lines stay in registers across the chunk
+// (RowTCursor, rowt_frame.h).
 //
 // IN_P / OUT_P: between two transposing passes the work buffer holds every line in the INTERLEAVED order
 //     position 2 R' (j >> 1) + 2 l + (j & 1)   <->   element R' j + l          (R' = radix of the kernel that reads the line)
@@ -183,16 +143,14 @@ constexpr int ROWT_TW_REG_LCH = 4;
 // stack), or -1 = read them from the job.  With both halves unconditional the body needs 234 VGPRs (R = 32: 249 with half of the
 // twiddle column in registers, see twr); with branches around them the allocator spills the t_k line (272 bytes per lane) -- only
 // the rarely used combinations are compiled that way (slice_pass.hip), and they keep every twiddle in the table.
+// tile line pitch in float2: the R^2 positions of a line (the wave's exchange scratch, R x 68 floats over 64 / R lines, is
+// smaller); 2 mod 32: rows 16-byte aligned for the exchange's wide reads, conflict-free staging
+constexpr int rowT_cs(int R) { return (R * R + 33) / 32 * 32 + 2; }
 template <int R, int LINES, bool IN_P, bool OUT_P, int FL>
 __global__ void __launch_bounds__(LINES * R, (R == 16) ? 3 : 2) rowT_pass_kernel(RowTJob job) {
     constexpr int N = R * R;
     constexpr int NT = LINES * R;
-    // tile line pitch in float2: the R^2 positions of a line (the wave's exchange scratch, R x 68 floats over 64 / R lines, is
-    // smaller); 2 mod 32: rows 16-byte aligned for the exchange's wide reads, conflict-free staging
-    constexpr int CS = (R * R + 33) / 32 * 32 + 2;
-    constexpr int TPS = LINES / 2;                    // threads (16 B = 2 lines each) per output segment of LINES*8 bytes
-    constexpr int POS_PER_IT = NT / TPS;
-    constexpr int NIT = N / POS_PER_IT;
+    constexpr int CS = rowT_cs(R);
     // TWK > 0: the twiddles of the first TWK leaf butterflies live in registers for the whole kernel (see twr below)
     constexpr int TWK = rowT_tw_reg_leaves(R, FL), LRW = dit_leaf_radix(R);
     constexpr bool TWR = TWK > 0;
@@ -220,21 +178,13 @@ __global__ void __launch_bounds__(LINES * R, (R == 16) ? 3 : 2) rowT_pass_kernel
         for (int i = 0; i < LRW * TWK; ++i) twr[i] = tw[((i % TWK) + (i / TWK) * dit_leaf_count(R)) * R + ln];
         pin_all(twr);
     }
-    const int q = tid % TPS, r0 = tid / TPS;
     const int l64 = tid & 63;
     float2* myrow = tile + grp * CS;
     // add-tid exchange: the groups of a wave share the scratch that starts at the first of their tile rows
     const float* wscr = reinterpret_cast<const float*>(tile + (grp - grp % (64 / R)) * CS);
     const unsigned wscr_lds = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(tile + (grp - grp % (64 / R)) * CS));
-    const int lblocks = job.n_lines / LINES;
-    const int PC = job.pchunk;
-    const int pchunks = (job.n_images + PC - 1) / PC;
-    const int n_items = lblocks * pchunks;
     const bool pre_a = (MSL_ABL2 & 8) ? false : FL >= 0 ? (FL & P2_PRE_A) != 0 : (job.flags & P2_PRE_A) != 0;
     const bool post_a = (MSL_ABL2 & 8) ? false : FL >= 0 ? (FL & P2_POST_A) != 0 : (job.flags & P2_POST_A) != 0;
-    // work item = (line block lb, probe chunk pc), item = lb * pchunks + pc; the cursor (item, lb, pc, k) advances
-    // incrementally -- a division per iteration costs ~0.3 us of scalar work on the critical path
-    const int step_lb = (int)gridDim.x / pchunks, step_pc = (int)gridDim.x % pchunks;
     // input line of this thread's tile row in line block lbb
     auto line_of = [&](int lbb) {
         if constexpr (OUT_P) {
@@ -244,8 +194,8 @@ __global__ void __launch_bounds__(LINES * R, (R == 16) ? 3 : 2) rowT_pass_kernel
             return lbb * LINES + grp;
         }
     };
-    auto line_ptr = [&](int lbb, int pcc, int kk) {
-        return job.in + (long long)(pcc * PC + kk) * job.in_image_stride + (long long)line_of(lbb) * job.in_pitch;
+    auto line_ptr = [&](const RowTCursor& c) {
+        return job.in + (long long)c.image() * job.in_image_stride + (long long)line_of(c.lb) * job.in_pitch;
     };
     // registers [LO, HI) of the next line: 8-byte loads of elements j R + ln, or (interleaved input) 16-byte loads of the pairs
     auto load_regs = [&](float2 (&dst)[R], const float2* r, auto lo_c, auto hi_c) {
@@ -262,10 +212,9 @@ __global__ void __launch_bounds__(LINES * R, (R == 16) ? 3 : 2) rowT_pass_kernel
             for (int j = LO; j < HI; ++j) dst[j] = ld_stream(r + (j * R + ln));
         }
     };
-    int item = blockIdx.x;
-    int lb = item / pchunks, pc = item - lb * pchunks, k = 0;
+    RowTCursor cur = RowTCursor::first(job, job.n_lines / LINES);
     float2 vn[R];
-    if (item < n_items) load_regs(vn, line_ptr(lb, pc, 0), MSL_IC(0), MSL_IC(R));
+    if (cur.valid()) load_regs(vn, line_ptr(cur), MSL_IC(0), MSL_IC(R));
     // The wait for the prefetched line.  vmcnt counts loads and stores together, in issue order, and inside the loop the 16 stores
     // of an iteration are YOUNGER than the loads of the next line: the wave may start on that line with its stores still in
     // flight (s_waitcnt vmcnt(16 + ...)).  The compiler's counter model merges the loop's back edge with the loop entry, where
@@ -277,7 +226,7 @@ __global__ void __launch_bounds__(LINES * R, (R == 16) ? 3 : 2) rowT_pass_kernel
 #ifdef MSL_CLOCK
     const unsigned long long clk0 = __builtin_amdgcn_s_memtime(), rt0 = __builtin_amdgcn_s_memrealtime();
 #endif
-    while (item < n_items) {
+    while (cur.valid()) {
         // The waves of a workgroup reach every lane <-> register exchange together and the LDS serves eight exchanges at once.
         // Waves on different SIMDs start an iteration MSL_STAGGER x 64 cycles apart (waves w and w + 4 share a SIMD and stay
         // together: delaying one against its partner only costs the delay): 3.7 % fewer cycles per pass, 1.3-1.5 % less time
@@ -285,26 +234,19 @@ __global__ void __launch_bounds__(LINES * R, (R == 16) ? 3 : 2) rowT_pass_kernel
         if constexpr (MSL_STAGGER > 0)
             for (int i = __builtin_amdgcn_readfirstlane(tid >> 6) & 3; i > 0; --i) __builtin_amdgcn_s_sleep(MSL_STAGGER);
         float2 v[R];
-        const int p = pc * PC + k;
-        const int cur_lb = lb;
-        if (k == 0) {
-            const float2* trow = job.trans + frame_off(job, pc * PC) + (long long)line_of(lb) * N;
+        if (cur.k == 0) {
+            const float2* trow = rowt_trans_row(job, cur, line_of(cur.lb), N);
 #pragma unroll
             for (int j = 0; j < R; ++j) tv[j] = ld_stream(trow + j * R + ln);       // read once per launch too (+0.4 %)
         }
-        int nitem = item, nlb = lb, npc = pc, nk = k + 1;
-        if (nk >= min(PC, job.n_images - pc * PC)) {
-            nk = 0; nitem = item + (int)gridDim.x; nlb = lb + step_lb; npc = pc + step_pc;
-            if (npc >= pchunks) { npc -= pchunks; ++nlb; }
-        }
+        const RowTCursor nxt = cur.next();
         // Prefetch of the next line: one sixteenth (R/16 registers, whole 16-byte pairs) after the leaf level and after the upper
         // levels of each of the eight register transforms, unconditional (past the last item the loads re-read the current line),
         // one address per iteration.  The memory pipeline accepts a wave's loads at the rate HBM returns data (about 32 KB in
         // flight per CU) and a burst blocks the in-order wave until it is accepted: per 1024^2 pass 322 us with all loads at the top
         // of the iteration, 306 us all after the third transform, 294 us in halves, 287 us in quarters (rounds 1-3), and with
         // the staggered waves the sixteenths are another 3 % against the quarters.
-        const bool more = nitem < n_items;
-        const float2* nptr = line_ptr(more ? nlb : lb, more ? npc : pc, more ? nk : k);
+        const float2* nptr = line_ptr(cur.prefetch_target(nxt));
         auto pfx = [&](auto i_c) {
             constexpr int I = decltype(i_c)::value;
             constexpr int LO = (R * I / 16) & ~1, HI = (R * (I + 1) / 16) & ~1;
@@ -361,30 +303,15 @@ __global__ void __launch_bounds__(LINES * R, (R == 16) ? 3 : 2) rowT_pass_kernel
 #pragma unroll
             for (int j = 0; j < R; ++j) acc += v[j].x + v[j].y;
             if (acc == 1.2345e-30f) job.out[tid] = make_float2(acc, acc);        // keeps the transforms alive
-            item = nitem; lb = nlb; pc = npc; k = nk;
-            continue;
-        }
-        wave_lds_fence();
+        } else {
+            wave_lds_fence();
 #pragma unroll
-        for (int j = 0; j < R; ++j) myrow[j * R + ln] = v[j];
-        lds_barrier();
-        // uniform 64-bit base + per-thread 32-bit element offset, re-derived every iteration (the asm keeps the
-        // compiler from hoisting 16 loop-invariant 64-bit addresses into registers for the whole kernel)
-        float2* dst = job.out + (long long)p * job.out_image_stride + cur_lb * LINES;
-        int off0 = 2 * q + r0 * job.out_pitch;
-        asm volatile("" : "+v"(off0));
-        const int ostep = POS_PER_IT * job.out_pitch;
-#pragma unroll
-        for (int i = 0; i < NIT; ++i) {
-            const int pos = r0 + POS_PER_IT * i;
-            const float2 a = tile[(2 * q) * CS + pos], b = tile[(2 * q + 1) * CS + pos];
-#if MSL_ABL2 & 2
-            if (a.x == 1.2345e-30f)                 // never true: the LDS reads stay, the store goes
-#endif
-            st_stream(dst + (off0 + i * ostep), a.x, a.y, b.x, b.y);
+            for (int j = 0; j < R; ++j) myrow[j * R + ln] = v[j];
+            lds_barrier();
+            tile_store_transposed<LINES, NT, CS, N, false, true>(tile, rowt_out_image(job, cur) + cur.lb * LINES, job.out_pitch, N, tid);
+            lds_barrier();
         }
-        lds_barrier();
-        item = nitem; lb = nlb; pc = npc; k = nk;
+        cur = nxt;
     }
 #ifdef MSL_CLOCK
     if (tid == 0 && job.clk) {
@@ -395,7 +322,7 @@ __global__ void __launch_bounds__(LINES * R, (R == 16) ? 3 : 2) rowT_pass_kernel
 }
 
 // LDS bytes of a workgroup of rowT_pass_kernel<R, 16, ...>
-constexpr size_t rowT_lds_bytes(int R) { return ((size_t)2 * R * R + (size_t)16 * ((R * R + 33) / 32 * 32 + 2)) * 8; }
+constexpr size_t rowT_lds_bytes(int R) { return ((size_t)2 * R * R + (size_t)16 * rowT_cs(R)) * 8; }
 
 // launch of the instantiation for (R, job.flags) on `stream` (slice_pass.hip); false: R is not 16 or 32
 bool rowT_launch(int R, const RowTJob& job, int grid, size_t lds_limit, hipStream_t stream);

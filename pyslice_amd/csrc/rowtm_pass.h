@@ -12,8 +12,9 @@
 // inverse:  A-point inverse over k1 -> n1 | x conj W_N^{n1 k2} | exchange back | B-point inverse over k2 -> r
 // Lanes beyond A (layout 1) or B (layout 2) mirror the last active lane (same addresses, same values): no divergence anywhere.
 // The exchange goes through the line's own tile row (8-byte accesses; pitches A | 1 and B | 1 are odd: conflict-free both ways).
-// Everything around the transform -- next line prefetched in registers, t_k in registers across a chunk of probes, 16-line tile,
-// 128-byte transposed segments, ragged last tile -- is rowTB_pass_kernel's.
+// Everything around the transform -- the walk over the work items with t_k in registers across a chunk of probes, the 16-line
+// tile and its 128-byte transposed segments, the ragged last tile -- is the frame of rowt_frame.h; the next line is prefetched
+// in registers, in quarters.
 #pragma once
 #include "rowt_pass.h"
 
@@ -100,43 +101,30 @@ __global__ void __launch_bounds__(16 * G, 2) rowTM_pass_kernel(RowTJob job) {
     const int lnA = ln < A ? ln : A - 1, lnB = ln < B ? ln : B - 1;
     const int q = tid % TPS, r0 = tid / TPS;
     float2* myrow = tile + grp * CS;
-    const int lblocks = (job.n_lines + LINES - 1) / LINES;
-    const int PC = job.pchunk;
-    const int pchunks = (job.n_images + PC - 1) / PC;
-    const int n_items = lblocks * pchunks;
-    const int step_lb = (int)gridDim.x / pchunks, step_pc = (int)gridDim.x % pchunks;
-    auto line_ptr = [&](int lbb, int pcc, int kk) {
-        const int L = min(lbb * LINES + grp, job.n_lines - 1);
-        return job.in + (long long)(pcc * PC + kk) * job.in_image_stride + (long long)L * job.in_pitch + lnA;
+    auto line_of = [&](int lbb) { return min(lbb * LINES + grp, job.n_lines - 1); };
+    auto line_ptr = [&](const RowTCursor& c) {
+        return job.in + (long long)c.image() * job.in_image_stride + (long long)line_of(c.lb) * job.in_pitch + lnA;
     };
-    int item = blockIdx.x;
-    int lb = item / pchunks, pc = item - lb * pchunks, k = 0;
+    RowTCursor cur = RowTCursor::first(job, (job.n_lines + LINES - 1) / LINES);
     float2 vn[B];
-    if (item < n_items) {
-        const float2* r = line_ptr(lb, pc, 0);
+    if (cur.valid()) {
+        const float2* r = line_ptr(cur);
 #pragma unroll
         for (int j = 0; j < B; ++j) vn[j] = ld_stream(r + j * A);
     }
     float2 tv[B];
-    while (item < n_items) {
+    while (cur.valid()) {
         float2 v[RM];
 #pragma unroll
         for (int j = 0; j < B; ++j) v[j] = vn[j];
-        const int p = pc * PC + k;
-        const int cur_lb = lb;
-        if (k == 0) {
-            const float2* trow = job.trans + frame_off(job, pc * PC) + (long long)min(lb * LINES + grp, job.n_lines - 1) * N + lnA;
+        if (cur.k == 0) {
+            const float2* trow = rowt_trans_row(job, cur, line_of(cur.lb), N) + lnA;
 #pragma unroll
             for (int j = 0; j < B; ++j) tv[j] = ld_stream(trow + j * A);
         }
-        int nitem = item, nlb = lb, npc = pc, nk = k + 1;
-        if (nk >= min(PC, job.n_images - pc * PC)) {
-            nk = 0; nitem = item + (int)gridDim.x; nlb = lb + step_lb; npc = pc + step_pc;
-            if (npc >= pchunks) { npc -= pchunks; ++nlb; }
-        }
+        const RowTCursor nxt = cur.next();
         // prefetch of the next line in four parts, unconditional (past the last item the loads re-read the current line)
-        const bool more = nitem < n_items;
-        const float2* nptr = line_ptr(more ? nlb : lb, more ? npc : pc, more ? nk : k);
+        const float2* nptr = line_ptr(cur.prefetch_target(nxt));
         auto pfx = [&](auto i_c) {
             constexpr int I = decltype(i_c)::value;
             constexpr int LO = I < MSL_TM_PFQ ? B * I / MSL_TM_PFQ : B, HI = I < MSL_TM_PFQ ? B * (I + 1) / MSL_TM_PFQ : B;
@@ -169,27 +157,28 @@ __global__ void __launch_bounds__(16 * G, 2) rowTM_pass_kernel(RowTJob job) {
 #pragma unroll
             for (int j = 1; j < B; ++j) { acc.x += v[j].x; acc.y += v[j].y; }
             if (acc.x == 12345.678f) job.out[tid] = acc;
-            item = nitem; lb = nlb; pc = npc; k = nk;
-            continue;
-        }
-        wave_lds_fence();
+        } else {
+            wave_lds_fence();
 #pragma unroll
-        for (int j = 0; j < B; ++j) myrow[j * A + lnA] = v[j];
-        lds_barrier();
-        float2* dst = job.out + (long long)p * job.out_image_stride + cur_lb * LINES;
-        int off0 = 2 * q + r0 * job.out_pitch;
-        asm volatile("" : "+v"(off0));
-        const int ostep = POS_PER_IT * job.out_pitch;
+            for (int j = 0; j < B; ++j) myrow[j * A + lnA] = v[j];
+            lds_barrier();
+            // tile_store_transposed's text, kept in the kernel: through the call these instantiations are scheduled differently, one
+            // VGPR more in most and private memory in rowTM_pass_kernel<30, 28, 32>, which had none (profiles/slice_pass_frame.txt)
+            float2* dst = rowt_out_image(job, cur) + cur.lb * LINES;
+            int off0 = 2 * q + r0 * job.out_pitch;
+            asm volatile("" : "+v"(off0));
+            const int ostep = POS_PER_IT * job.out_pitch;
 #pragma unroll
-        for (int i = 0; i < NIT; ++i) {
-            const int pos = r0 + POS_PER_IT * i;
-            if (pos < N) {
-                const float2 a = tile[(2 * q) * CS + pos], b = tile[(2 * q + 1) * CS + pos];
-                st_stream(dst + (off0 + i * ostep), a.x, a.y, b.x, b.y);
+            for (int i = 0; i < NIT; ++i) {
+                const int pos = r0 + POS_PER_IT * i;
+                if (pos < N) {
+                    const float2 a = tile[(2 * q) * CS + pos], b = tile[(2 * q + 1) * CS + pos];
+                    st_stream(dst + (off0 + i * ostep), a.x, a.y, b.x, b.y);
+                }
             }
+            lds_barrier();
         }
-        lds_barrier();
-        item = nitem; lb = nlb; pc = npc; k = nk;
+        cur = nxt;
     }
 }
 
@@ -253,42 +242,29 @@ __global__ void __launch_bounds__(512, 2) rowTM2_pass_kernel(RowTJob job) {
     const float2* x1r = myrow + k2c * P1 + hh * AH;
     float2* x2w = myrow + hh * A * P2 + k2c;                  // exchange 2: write [m P2], read [k2]
     const float2* x2r = myrow + n1c * P2;
-    const int lblocks = (job.n_lines + LINES - 1) / LINES;
-    const int PC = job.pchunk;
-    const int pchunks = (job.n_images + PC - 1) / PC;
-    const int n_items = lblocks * pchunks;
-    const int step_lb = (int)gridDim.x / pchunks, step_pc = (int)gridDim.x % pchunks;
-    auto line_ptr = [&](int lbb, int pcc, int kk) {
-        const int Ln = min(lbb * LINES + wv, job.n_lines - 1);
-        return job.in + (long long)(pcc * PC + kk) * job.in_image_stride + (long long)Ln * job.in_pitch + n1c;
+    auto line_of = [&](int lbb) { return min(lbb * LINES + wv, job.n_lines - 1); };
+    auto line_ptr = [&](const RowTCursor& c) {
+        return job.in + (long long)c.image() * job.in_image_stride + (long long)line_of(c.lb) * job.in_pitch + n1c;
     };
-    int item = blockIdx.x;
-    int lb = item / pchunks, pc = item - lb * pchunks, k = 0;
+    RowTCursor cur = RowTCursor::first(job, (job.n_lines + LINES - 1) / LINES);
     float2 vn[B];
-    if (item < n_items) {
-        const float2* r = line_ptr(lb, pc, 0);
+    if (cur.valid()) {
+        const float2* r = line_ptr(cur);
 #pragma unroll
         for (int j = 0; j < B; ++j) vn[j] = ld_stream(r + j * A2);
     }
     float2 tv[B];
-    while (item < n_items) {
+    while (cur.valid()) {
         float2 v[RM];
 #pragma unroll
         for (int j = 0; j < B; ++j) v[j] = vn[j];
-        const int p = pc * PC + k;
-        const int cur_lb = lb;
-        if (k == 0) {
-            const float2* trow = job.trans + frame_off(job, pc * PC) + (long long)min(lb * LINES + wv, job.n_lines - 1) * N + n1c;
+        if (cur.k == 0) {
+            const float2* trow = rowt_trans_row(job, cur, line_of(cur.lb), N) + n1c;
 #pragma unroll
             for (int j = 0; j < B; ++j) tv[j] = ld_stream(trow + j * A2);
         }
-        int nitem = item, nlb = lb, npc = pc, nk = k + 1;
-        if (nk >= min(PC, job.n_images - pc * PC)) {
-            nk = 0; nitem = item + (int)gridDim.x; nlb = lb + step_lb; npc = pc + step_pc;
-            if (npc >= pchunks) { npc -= pchunks; ++nlb; }
-        }
-        const bool more = nitem < n_items;
-        const float2* nptr = line_ptr(more ? nlb : lb, more ? npc : pc, more ? nk : k);
+        const RowTCursor nxt = cur.next();
+        const float2* nptr = line_ptr(cur.prefetch_target(nxt));
         auto pfx = [&](auto i_c) {
             constexpr int I = decltype(i_c)::value;
             constexpr int LO = I < MSL_TM_PFQ ? B * I / MSL_TM_PFQ : B, HI = I < MSL_TM_PFQ ? B * (I + 1) / MSL_TM_PFQ : B;
@@ -358,27 +334,27 @@ __global__ void __launch_bounds__(512, 2) rowTM2_pass_kernel(RowTJob job) {
 #pragma unroll
             for (int j = 1; j < B; ++j) { acc.x += v[j].x; acc.y += v[j].y; }
             if (acc.x == 12345.678f) job.out[tid] = acc;
-            item = nitem; lb = nlb; pc = npc; k = nk;
-            continue;
-        }
-        wave_lds_fence();
+        } else {
+            wave_lds_fence();
 #pragma unroll
-        for (int j = 0; j < B; ++j) myrow[j * A2 + n1c] = v[j];
-        lds_barrier();
-        float2* dst = job.out + (long long)p * job.out_image_stride + cur_lb * LINES;
-        int off0 = 2 * q + r0 * job.out_pitch;
-        asm volatile("" : "+v"(off0));
-        const int ostep = POS_PER_IT * job.out_pitch;
+            for (int j = 0; j < B; ++j) myrow[j * A2 + n1c] = v[j];
+            lds_barrier();
+            // (kept in the kernel, see rowTM_pass_kernel)
+            float2* dst = rowt_out_image(job, cur) + cur.lb * LINES;
+            int off0 = 2 * q + r0 * job.out_pitch;
+            asm volatile("" : "+v"(off0));
+            const int ostep = POS_PER_IT * job.out_pitch;
 #pragma unroll
-        for (int i = 0; i < NIT; ++i) {
-            const int pos = r0 + POS_PER_IT * i;
-            if (pos < N) {
-                const float2 a = tile[(2 * q) * CS + pos], b = tile[(2 * q + 1) * CS + pos];
-                st_stream(dst + (off0 + i * ostep), a.x, a.y, b.x, b.y);
+            for (int i = 0; i < NIT; ++i) {
+                const int pos = r0 + POS_PER_IT * i;
+                if (pos < N) {
+                    const float2 a = tile[(2 * q) * CS + pos], b = tile[(2 * q + 1) * CS + pos];
+                    st_stream(dst + (off0 + i * ostep), a.x, a.y, b.x, b.y);
+                }
             }
+            lds_barrier();
         }
-        lds_barrier();
-        item = nitem; lb = nlb; pc = npc; k = nk;
+        cur = nxt;
     }
 }
 

@@ -651,6 +651,25 @@ def test_many_probes_per_launch(ps, orc, nx, ny, nz, P):
     assert fmp.case(nx, ny, nz, P) < WAVE_TOL
 
 
+@pytest.mark.parametrize("nx,ny,nz,P", [(997, 64, 3, 100), (1200, 64, 3, 100)])
+def test_item_loop_wraps_on_a_ragged_probe_chunk(ps, orc, monkeypatch, nx, ny, nz, P):
+    """The work-item loop of rowTB2_pass_kernel (997 points: 513..1024, not smooth) and of rowTM2_pass_kernel (1200 = 2 x 25 x 24),
+    which test_many_probes_per_launch does not reach, with a second item per workgroup and a ragged last probe chunk.
+    Both kernels take the 64 lines of the long axis in 8 line blocks on 256 workgroups (one per CU).  choose_pchunk's cost
+    ceil(8 ceil(100 / pc) / 256) pc is 4 for pc = 1 (800 items, 4 rounds), 2 (400, 2) and 4 (200, 1), more for every other chunk,
+    and ties go to the larger: pc = 4, 200 items on 200 workgroups -- no second item, and 100 % 4 = 0.  So the chunk is set to 3
+    (MSL_ROW_PCHUNK, read when the engine is created): 34 chunks, 8 x 34 = 272 items > 256 workgroups, so workgroups 0..15 take
+    a second item, and 100 % 3 = 1: the last chunk of every line block holds one probe."""
+    import importlib.util
+    import os
+    monkeypatch.setenv("MSL_DEBUG", "1")
+    monkeypatch.setenv("MSL_ROW_PCHUNK", "3")
+    spec = importlib.util.spec_from_file_location("fmp", os.path.join(os.path.dirname(__file__), "..", "tools", "fuzz_many_probes.py"))
+    fmp = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(fmp)
+    assert fmp.case(nx, ny, nz, P) < WAVE_TOL
+
+
 @pytest.mark.parametrize("nx,ny,nz,window,kbin,fb", [(256, 256, 3, None, (4, 4), 1), (256, 256, 4, (64, 96), (2, 8), 2),
                                                      (96, 80, 3, None, (3, 5), 1), (512, 512, 3, (128, 128), (4, 2), 3),
                                                      (1024, 256, 2, (256, 64), (16, 1), 1), (45, 63, 2, (15, 21), (5, 7), 2)])

@@ -5,7 +5,7 @@
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -fno-slp-vectorize [-DMSL_CLOCK] [-DMSL_ABL2=bits] [-DMSL_STAGGER=n] [-DBENCH_R=16] \
 //         -o tools/bin/rowt_bench tools/rowt_bench.hip
 //   tools/bin/rowt_bench [launches [zero]]      zero = 1: all-zero waves and transmission functions (same instructions, less switching)
-// -DMSL_CLOCK: in-kernel clock (s_memtime / s_memrealtime around the item loop); -DMSL_ABL2: ablations, see rowt_pass.h.
+// -DMSL_CLOCK: in-kernel clock (s_memtime / s_memrealtime around the item loop); -DMSL_ABL2: ablations, see rowt_frame.h.
 // -DMSL_TW_LDS=1: every inter-FFT twiddle from the LDS table (the form before the register twiddles), for a same-binary-family A/B.
 #include <hip/hip_runtime.h>
 #include <cmath>
@@ -27,7 +27,7 @@ using namespace msl;
 #endif
 constexpr int R = BENCH_R, N = R * R;
 #define KERNEL(IP, OP) rowT_pass_kernel<R, 16, IP, OP, BENCH_FL>
-constexpr int CS_K = (R * R + 33) / 32 * 32 + 2;
+constexpr int CS_K = rowT_cs(R);
 
 typedef std::complex<double> cd;
 static void dft(std::vector<cd>& x, bool inv) {          // in-place radix-2, double
@@ -69,7 +69,7 @@ int main(int argc, char** argv) {
     job.n_lines = N; job.n_images = IMG; job.flags = P2_PRE_A | P2_POST_A; job.pchunk = (R == 32) ? P : 32;
     job.t_group = P; job.t_magic = (unsigned)((1ull << 32) / (unsigned)P + 1); job.t_stride = (long long)N * N;
     job.perm_shift = (R == 32) ? 2 : 1;
-    const size_t lds = ((size_t)2 * N + (size_t)16 * CS_K) * 8;
+    const size_t lds = rowT_lds_bytes(R);
     CK(hipFuncSetAttribute((const void*)KERNEL(false, false), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     CK(hipFuncSetAttribute((const void*)KERNEL(true, true), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     // ---- correctness: natural order in and out, sampled lines against float64 ----

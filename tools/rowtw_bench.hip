@@ -1,7 +1,7 @@
 // Stand-alone bench of the 2048-point transposing pass (rowTW_pass_kernel, BASELINE C5's grid) on bench.py's launch shape for
 // `--grid 2048 --probes 16` (4 frames x 16 probes x 2048 lines, items of 8 lines x 16 probes): float64 check of the natural-order
 // instantiation, steady-state timing of the paired-layout one, in-kernel clock (-DMSL_CLOCK), ablations (-DMSL_ABL2=bits, see
-// rowt_pass.h).   hipcc --offload-arch=gfx950 -O3 -std=c++17 -fno-slp-vectorize [-DMSL_CLOCK] [-DMSL_ABL2=n] -o tools/bin/rowtw_bench tools/rowtw_bench.hip
+// rowt_frame.h).   hipcc --offload-arch=gfx950 -O3 -std=c++17 -fno-slp-vectorize [-DMSL_CLOCK] [-DMSL_ABL2=n] -o tools/bin/rowtw_bench tools/rowtw_bench.hip
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cmath>
@@ -49,7 +49,7 @@ int main(int argc, char** argv) {
     job.in_image_stride = job.out_image_stride = (long long)img; job.in_pitch = job.out_pitch = PITCH;
     job.n_lines = N; job.n_images = IMG; job.flags = P2_PRE_A | P2_POST_A; job.pchunk = P;
     job.t_group = P; job.t_magic = (unsigned)((1ull << 32) / (unsigned)P + 1); job.t_stride = (long long)N * N;
-    const size_t lds = ((size_t)N + 64 + N / 2 + 64 + (size_t)8 * (N + 1)) * 8;
+    const size_t lds = rowTW_lds_bytes();
     CK(hipFuncSetAttribute((const void*)rowTW_pass_kernel<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     CK(hipFuncSetAttribute((const void*)rowTW_pass_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     CK(hipMemset(out, 0, img * IMG * 8));
