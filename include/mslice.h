@@ -553,6 +553,29 @@ int  msl_coherent_reset(msl_handle* h, int64_t B);
 int  msl_coherent_add(msl_handle* h, const void* d_src_c64, int64_t B, int64_t T, int64_t K, int64_t ld, int32_t t0, int32_t count);
 int  msl_coherent_finish(msl_handle* h, int64_t B, int32_t n, int32_t wx, int32_t wy, int32_t bx, int32_t by, double* out);
 
+/* ---- finite dose: Poisson counts of the frame-summed patterns of a probe batch, drawn on the device ----
+ * The handle owns one accumulator, (B, mx*my) float64, and a uint32 staging of the counts; both only grow and are freed with the handle.
+ * msl_dose_reset: sizes the accumulator for B probes (B <= 0: n_probes) of mx x my detector pixels and zeroes it on the handle's stream.
+ *   MSL_ERR_INVALID for mx < 1 or my < 1.
+ * msl_dose_add: acc[b, ix*my + iy] += msl_diffract's out[(b*mx + ix)*my + iy], with msl_diffract's arguments, reads, bin modes and
+ *   summation order; one launch, queued on the stream (no wait), no atomics: the calls since the reset are added in call order, and
+ *   repeated sequences are bitwise equal.  MSL_ERR_STATE before a reset; MSL_ERR_INVALID for what msl_diffract refuses (a bin that does
+ *   not divide the window ...), for B beyond the reset and for wx/bx x wy/by other than the reset's mx x my.
+ * msl_dose_counts: counts_out[b*mx*my + i] = the Poisson draw of lam = acc[b, i] * scale (one float64 multiply) from the stream of
+ *   pixel i, probe probe0 + b under the 64-bit key seed: Philox-4x32-10 with the counter (i, probe0 + b, attempt, 0), inversion below
+ *   lam = 10 and Hoermann's PTRS from there on, every loop bounded -- the definition, word for word, is pyslice_amd/dose.py.  scale is
+ *   the electrons per unit of the accumulator, N_e / I_incident for the accumulator's frame SUM over n frames divided by n:
+ *   N_e / (n * I_incident).  One launch, one thread per pixel; the counts go to the device staging and from there to counts_out, HOST
+ *   memory of B*mx*my uint32 (B <= 0: the B of the reset); with intensity_out != NULL the accumulator itself is copied there, HOST
+ *   memory of B*mx*my float64.  Counts saturate at 2^32 - 1.  MSL_ERR_STATE before a reset; MSL_ERR_INVALID for B beyond the reset, a
+ *   negative or non-finite scale, probes outside [0, 2^32) and for a lam that is negative or not finite (found by the kernel; the
+ *   outputs are then not to be used).  The accumulator is left as it is.
+ *   Not in the reference, which returns noise-free intensities. */
+int  msl_dose_reset(msl_handle* h, int64_t B, int32_t mx, int32_t my);
+int  msl_dose_add(msl_handle* h, const void* d_src_c64, int64_t B, int64_t T, int64_t K, int64_t ld, int32_t t0, int32_t count, int32_t wx, int32_t wy,
+                  int32_t bx, int32_t by);
+int  msl_dose_counts(msl_handle* h, int64_t B, double scale, uint64_t seed, int64_t probe0, uint32_t* counts_out, double* intensity_out);
+
 /* ---- images through an objective lens (HRTEM, focal series): frame-accumulated |psi|^2 in the image plane, per probe batch ----
  * For probe b and the frames j of a call
  *     I[first + b*stride](r) += weight * sum_{j<count} | ifft2( ifftshift(Psi[b, t0+j]) * H )(r) |^2,

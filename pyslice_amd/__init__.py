@@ -29,6 +29,7 @@ from .bandlimit import BandLimit
 from .projection import Projection
 from .ionization import Ionization, ionization_weights, ionization_signal
 from .element_map_data import ElementMapData
+from .dose import Dose, poisson_counts
 
 __all__ = ["Trajectory", "FrozenPhonons", "sigma_from_B", "PhononModes", "AbsorptivePotential", "absorptive_tables",
            "absorptive_transmission", "mean_transmission_exact", "tds_tables", "tds_weight", "tds_signal", "WFData", "Potential", "gridFromTrajectory", "getZfromElementName", "loadKirkland",
@@ -36,5 +37,6 @@ __all__ = ["Trajectory", "FrozenPhonons", "sigma_from_B", "PhononModes", "Absorp
            "MultisliceCalculator", "TACAWData", "HAADFData", "Detector", "STEMData", "Diffraction", "DiffractionData",
            "PolarDetector", "PolarData", "polar_bins", "polar_signals", "Thickness",
            "Aberrations", "scherzer_defocus", "Imaging", "ImageData", "Spectroscopy", "SpectrumImageData",
-           "Tilt", "Precession", "BandLimit", "Projection", "Ionization", "ionization_weights", "ionization_signal", "ElementMapData"]
+           "Tilt", "Precession", "BandLimit", "Projection", "Ionization", "ionization_weights", "ionization_signal", "ElementMapData",
+           "Dose", "poisson_counts"]
 __version__ = "0.1.0"

@@ -36,6 +36,7 @@ EXPORTS = [
     "msl_set_detectors", "msl_detect", "msl_spectrum_detect", "msl_diffract",
     "msl_polar_layout", "msl_set_polar", "msl_polar_detect",
     "msl_coherent_reset", "msl_coherent_add", "msl_coherent_finish",
+    "msl_dose_reset", "msl_dose_add", "msl_dose_counts",
     "msl_image_reset", "msl_image_add", "msl_image_download",
     "msl_smatrix_begin", "msl_smatrix_beams", "msl_smatrix_build", "msl_smatrix_probes", "msl_smatrix_probes_cropped",
     "msl_smatrix_end",
@@ -147,6 +148,9 @@ def load():
         "msl_coherent_reset": (C.c_int, [vp, i64]),
         "msl_coherent_add": (C.c_int, [vp, vp, i64, i64, i64, i64, i32, i32]),
         "msl_coherent_finish": (C.c_int, [vp, i64, i32, i32, i32, i32, i32, vp]),
+        "msl_dose_reset": (C.c_int, [vp, i64, i32, i32]),
+        "msl_dose_add": (C.c_int, [vp, vp, i64, i64, i64, i64, i32, i32, i32, i32, i32, i32]),
+        "msl_dose_counts": (C.c_int, [vp, i64, dbl, C.c_uint64, i64, vp, vp]),
         "msl_image_reset": (C.c_int, [vp, i64]),
         "msl_image_add": (C.c_int, [vp, vp, i64, i64, i64, i32, i32, vp, dbl, dbl, i64, i64]),
         "msl_image_download": (C.c_int, [vp, i64, i64, vp]),
@@ -880,6 +884,38 @@ class Engine:
         out = np.empty((max(b, 0), wx // bx, wy // by) if ok and b > 0 else (1,), dtype=np.float64)
         self._chk(self._lib.msl_coherent_finish(self._h, b, int(n), wx, wy, bx, by, _ptr(out)))
         return out
+
+    # -- finite dose (msl_dose_reset / msl_dose_add / msl_dose_counts)
+    def dose_reset(self, B=None, shape=None):
+        """size the handle's float64 pattern accumulator for B probes (None: n_probes) of shape = (mx, my) detector pixels (None:
+        the stored spectrum) and zero it"""
+        mx, my = (self.wx, self.wy) if shape is None else (int(shape[0]), int(shape[1]))
+        self._dose_shape = None
+        self._chk(self._lib.msl_dose_reset(self._h, int(B) if B else 0, mx, my))
+        self._dose_shape = (int(B) if B else self.n_probes, mx, my)
+
+    def dose_add(self, t0=0, count=None, B=None, bin=(1, 1), src=None):
+        """accumulator += what diffract() returns for the same arguments, on the device.  Queued on the handle's stream."""
+        bx, by = int(bin[0]), int(bin[1])
+        wx, wy = (self.wx, self.wy) if src is None else (int(src[3]), int(src[4]))
+        p, b, T, k, ld, count = self._rows(None if src is None else (*src[:3], wx * wy, *src[5:]), B, self.n_frames, t0, count)
+        self._chk(self._lib.msl_dose_add(self._h, p, b, T, k, ld, int(t0), count, wx, wy, bx, by))
+
+    def dose_counts(self, scale, seed, probe0=0, B=None, keep_intensity=False):
+        """(counts (B, mx, my) uint32, acc (B, mx, my) float64 or None): the Poisson draws of acc * scale (dose.poisson_counts with
+        the probe indices probe0 .. probe0 + B - 1) and, with keep_intensity, the accumulator itself.  B = None: every probe of the
+        last dose_reset."""
+        shape = getattr(self, "_dose_shape", None)
+        if shape is None:                                           # (the output is sized from the reset this wrapper made)
+            raise RuntimeError("dose_counts: no accumulator (call dose_reset)")
+        b = int(B) if B else shape[0]
+        ok = 0 < b <= shape[0]                                      # (else the library refuses: no output is written)
+        dims = (b, shape[1], shape[2]) if ok else (1,)
+        counts = np.empty(dims, dtype=np.uint32)
+        acc = np.empty(dims, dtype=np.float64) if keep_intensity else None
+        self._chk(self._lib.msl_dose_counts(self._h, b, float(scale), int(seed), int(probe0), _ptr(counts),
+                                            None if acc is None else _ptr(acc)))
+        return counts, acc
 
     # -- images through an objective lens (msl_image_reset / msl_image_add / msl_image_download)
     def image_reset(self, n):

@@ -169,6 +169,9 @@ class MultisliceCalculator:
                    propagation feeds both.  setup() raises ValueError when the bin does not divide the stored spectrum.
                    Diffraction(bin, split=True) also returns the elastic part |<Psi>|^2 of every pattern (and the thermal
                    diffuse rest), at the price of one potential build per probe batch and frame (run_diffraction).
+                   Diffraction(bin, dose=dose.Dose(...)) returns Poisson counts at that dose, (P, wx/bx, wy/by) uint32, drawn on
+                   the device from the frame sums (dose.py is the definition), at the same price.  Not with split=True, thickness,
+                   prism, precession, polar, cache, stream_tile or several ranks: NotImplementedError("dose: ... is not built").
           polar    polar-detector mode: a polar_data.PolarDetector(outer, step, inner, n_azimuthal, rotation, per_frame).
                    run_polar() streams the probes through the device as run_detectors() does and reduces every exit spectrum,
                    there (msl_polar_detect), to |Psi|^2 summed over R rings x A sectors: (P, R, A) float64 on the host, the mean
@@ -297,6 +300,15 @@ class MultisliceCalculator:
                               ("frame_batch > 1", frame_batch is not None and int(frame_batch) > 1)):
                 if val:
                     raise NotImplementedError(f"ionization: {what} is not built")
+        self._dose = getattr(diffraction, "dose", None)
+        self.electrons_per_probe = None         # setup(): the electrons per probe position of a dose run
+        if self._dose is not None:
+            # counts are drawn from the per-probe frame sums of the exit patterns on the device: the modes that reduce elsewhere, keep
+            # their own result loop or average over several scans are not fed from that accumulator
+            for what, val in (("thickness", thickness is not None), ("prism", prism is not None), ("precession", precession is not None),
+                              ("polar", polar is not None), ("cache", bool(cache)), ("stream_tile", stream_tile is not None)):
+                if val:
+                    raise NotImplementedError(f"dose: {what} is not built")
         self.device = device
         self._output, self._dtype, self._progress, self._gather = output, dtype, progress, gather
         self._cache = bool(cache)
@@ -638,6 +650,12 @@ class MultisliceCalculator:
         engine of Pc <= P probes x one frame batch of result slots, then the detector memberships and the polar bin map onto it"""
         if self._world > 1 and self._thickness_arg is not None:
             raise NotImplementedError("thickness: runs over several ranks are not built")
+        if self._world > 1 and self._dose is not None:
+            raise NotImplementedError("dose: several ranks is not built")
+        if self._dose is not None:                              # (per_area: ValueError for a scan that is no regular raster)
+            self.electrons_per_probe = float(self._dose.electrons(self.probe_positions))
+            if len(self.probe_positions) > 2 ** 32:
+                raise ValueError("dose: the probe index is a 32-bit word of the counter")
         if self._world > 1:
             mode = "detectors" if self._detectors is not None else ("diffraction" if self._diffraction is not None else
                                                                     ("polar" if self._polar is not None else "imaging"))
@@ -843,6 +861,8 @@ class MultisliceCalculator:
         pitch = self._stored_shape()[2]
         tables = self._phase_table_bytes(batch)
         coh = 16.0 * pitch if self._diffraction is not None and self._diffraction.split else 0.0
+        if getattr(self, "_dose", None) is not None:                # (the float64 frame sums and the uint32 counts of a probe's pattern)
+            coh = 12.0 * pitch
         if self._imaging is not None:
             coh = 8.0 * nx * ny * len(self._layers) * len(self._imaging.defocus_series)
         smatrix = 8.0 * getattr(self, "_prism_Bm", 0) * nx * ny       # the S-matrix of a PRISM run, (Bm, nx, ny) complex64
@@ -1161,7 +1181,12 @@ class MultisliceCalculator:
         With Diffraction(split=True) the result also carries `elastic`, |<Psi>|^2 summed over each bin (and .tds, .part()): the
         run then takes the other loop order (_frames_inside_loop: probe batches outside, every frame of a probe added into a
         float64 accumulator on the device), which builds the potentials of every frame once per probe batch instead of once, and
-        the host holds a second (P, mx, my) array.  intensity and stem are computed by the same calls as without the split."""
+        the host holds a second (P, mx, my) array.  intensity and stem are computed by the same calls as without the split.
+        With Diffraction(dose=Dose(...)) the run takes that loop order too: per probe batch msl_dose_reset, per frame batch
+        msl_dose_add (the pattern pass, added into the float64 accumulator on the device), then msl_dose_counts draws the Poisson
+        counts there (dose.py) and downloads 4 bytes per detector pixel -> .counts (P, mx, my) uint32; .intensity only with
+        Dose(keep_intensity=True).  The counts do not depend on probe_batch (the draws are keyed by the
+        probe's index in the scan)."""
         from .diffraction_data import DiffractionData, bin_centres
         if self._spectroscopy is not None:
             raise RuntimeError("spectroscopy is set: the device holds one probe batch at a time -- call run_spectrum_image()")
@@ -1176,10 +1201,26 @@ class MultisliceCalculator:
         P, T = self.n_probes, self.n_frames
         bx, by = self._diffraction.bin
         pacbed = self._thickness is not None and self._thickness_arg.patterns == "pacbed"
-        acc = self._layered((eng.wx // bx, eng.wy // by) if pacbed else (P, eng.wx // bx, eng.wy // by))
+        dose = self._dose
+        mx, my = eng.wx // bx, eng.wy // by
+        keep = dose is None or dose.keep_intensity
+        acc = self._layered(((mx, my) if pacbed else (P, mx, my)) if keep else (0,))
         signals = None if self._detectors is None else self._layered((P, T, len(self._detectors)))
+        counts = incident = None
+        if dose is not None:
+            from .dose import incident_intensity
+            counts = np.zeros((P, mx, my), dtype=np.uint32)
+            incident = incident_intensity(self.nx, self.ny, self.dx, self.dy, self.aperture, wavelength(self.voltage_eV))
+            dose_scale = self.electrons_per_probe / (T * incident)      # electrons per unit of the frame SUM
 
         def reduce_batch(p0, real, s0, n):
+            if dose is not None:                                # the frame sums stay on the device until finish_batch
+                if s0 == 0:
+                    eng.dose_reset(real, (mx, my))
+                eng.dose_add(0, n, B=real, bin=(bx, by))
+                if signals is not None:
+                    signals[p0:p0 + real, s0:s0 + n] = eng.detect(0, n, B=real)
+                return
             if self._thickness is not None:
                 det = (self._pacbed_batch if pacbed else self._position_batch)(acc, p0, real, n, signals is not None)
                 if signals is not None:
@@ -1195,6 +1236,12 @@ class MultisliceCalculator:
             def finish_batch(p0, real):
                 elastic[p0:p0 + real] = eng.coherent_finish(T, B=real, bin=(bx, by))
             self._frames_inside_loop(reduce_batch, finish_batch)
+        elif dose is not None:
+            def finish_batch(p0, real):
+                counts[p0:p0 + real], sums = eng.dose_counts(dose_scale, dose.seed, probe0=p0, B=real, keep_intensity=keep)
+                if keep:
+                    acc[p0:p0 + real] = sums
+            self._frames_inside_loop(reduce_batch, finish_batch, coherent=False)
         elif self._prism is not None:
             self._prism_loop(reduce_batch)
         else:
@@ -1203,10 +1250,13 @@ class MultisliceCalculator:
         self.elapsed = time.time() - t0
         self.frames_computed, self.frames_cached = T, 0
         kxs, kys = self._k_axes()
-        return self._tag_crop(DiffractionData(intensity=acc, kxs=_as_tensor(bin_centres(kxs, bx)), kys=_as_tensor(bin_centres(kys, by)),
+        return self._tag_crop(DiffractionData(intensity=acc if keep else None, kxs=_as_tensor(bin_centres(kxs, bx)),
+                                              kys=_as_tensor(bin_centres(kys, by)),
                                               bin=(bx, by), n_frames=T, probe_positions=self.probe_positions, probe=self.base_probe,
                                               stem=None if signals is None else self._stem_data(signals), elastic=elastic,
-                                              patterns="pacbed" if pacbed else "position", **self._layer_fields()))
+                                              patterns="pacbed" if pacbed else "position", counts=counts, dose=dose,
+                                              electrons_per_probe=self.electrons_per_probe if dose is not None else None,
+                                              incident=incident, **self._layer_fields()))
 
     def run_images(self):
         """Frame-averaged images behind the objective lens (HRTEM, focal series), for every probe: probe batches outside, frame

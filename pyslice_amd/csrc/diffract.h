@@ -14,6 +14,8 @@
 //                exchange, the bin's first lane stores;
 //   DIFF_LDS     any other divisor of wy (3, 5, 7, 25 ...): column sums through LDS (wy doubles), lane iy adds bin iy in order.
 // No atomics, fixed summation order in every mode: the same input gives bitwise the same output.
+// ACC (msl_dose_add): every bin's sum is ADDED to out instead of stored -- a bin has one owner lane in every mode, so the adds
+// of successive launches on one stream land in launch order, without atomics.  ACC = false is msl_diffract's kernel as it was.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -24,7 +26,7 @@ namespace msl {
 constexpr int DIFF_ROWS = 8;                    // rows in flight per lane = fp32 addends per column before the float64 sum (tail: 4, 2, 1)
 enum { DIFF_DIRECT = 0, DIFF_SHFL = 1, DIFF_LDS = 2 };
 
-template <int MODE, bool VEC>
+template <int MODE, bool VEC, bool ACC = false>
 __global__ void __launch_bounds__(256) diffract_kernel(const float2* __restrict__ src, long long T, long long t0, int count, long long ld,
                                                        int wx, int wy, int bx, int by, long long strips, int strips_per_wg,
                                                        double* __restrict__ out) {
@@ -85,14 +87,20 @@ __global__ void __launch_bounds__(256) diffract_kernel(const float2* __restrict_
             if ((rows - r) & 1) batch(std::integral_constant<int, 1>{});
             if constexpr (MODE == DIFF_DIRECT) {
                 if (live) {
-                    if constexpr (VEC) *reinterpret_cast<double2*>(orow + y) = make_double2(d0, d1);
+                    if constexpr (ACC) {
+                        orow[y] += d0;
+                        if constexpr (VEC) orow[y + 1] += d1;
+                    } else if constexpr (VEC) *reinterpret_cast<double2*>(orow + y) = make_double2(d0, d1);
                     else orow[y] = d0;
                 }
             } else if constexpr (MODE == DIFF_SHFL) {
                 const int g = by / PXL;                          // lanes per bin: a power of two <= 64 that divides the wave
                 double v = VEC ? d0 + d1 : d0;
                 for (int o = g >> 1; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-                if (live && (tid & (g - 1)) == 0) orow[y / by] = v;
+                if (live && (tid & (g - 1)) == 0) {
+                    if constexpr (ACC) orow[y / by] += v;
+                    else orow[y / by] = v;
+                }
             } else {
                 if (live) {
                     diff_col[y] = d0;
@@ -106,7 +114,8 @@ __global__ void __launch_bounds__(256) diffract_kernel(const float2* __restrict_
                 const double* c = diff_col + iy * by;
                 double v = 0.0;
                 for (int i = 0; i < by; ++i) v += c[i];
-                orow[iy] = v;
+                if constexpr (ACC) orow[iy] += v;
+                else orow[iy] = v;
             }
             __syncthreads();                                     // the next strip overwrites the column sums
         }

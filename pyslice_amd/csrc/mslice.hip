@@ -36,6 +36,7 @@
 #include "spectrum_detect.h"
 #include "diffract.h"
 #include "coherent.h"
+#include "dose.h"
 #include "image.h"
 #include "smatrix.h"
 #include "propagator.h"
@@ -233,6 +234,12 @@ struct msl_handle {
     // length of the adds since the last reset (0: none yet)
     DevBuf<double2> coh_acc;
     int64_t coh_B = 0, coh_K = 0;
+    // finite dose (msl_dose_reset / _add / _counts): the (dose_B, dose_K = mx * my) float64 frame sums of a probe batch and the uint32
+    // staging of their counts with the flag word behind them, both grown on demand; dose_B = 0: no reset yet
+    DevBuf<double> dose_acc;
+    DevBuf<uint32_t> dose_cnt;
+    int64_t dose_B = 0, dose_K = 0;
+    int dose_mx = 0, dose_my = 0;
     // image accumulator (msl_image_reset / _add / _download): (img_n, nx * ny) float64, grown on demand
     DevBuf<double> img_acc;
     int64_t img_n = 0;
@@ -4303,24 +4310,25 @@ int msl_spectrum_detect(msl_handle* h, const void* d_src_f32, int64_t B, int64_t
 
 // ---- diffraction patterns (diffract.h) --------------------------------------------------------------------
 // the pattern pass of msl_diffract over resolved rows, queued as one timed launch: the (B, mx, my) float64 result goes to d_dst, or
-// with d_dst == NULL to h->diff_out; *d_res / *res_bytes name it
+// with d_dst == NULL to h->diff_out; *d_res / *res_bytes name it.  d_acc (msl_dose_add) takes the place of both: the result is added
+// to the (B, mx, my) float64 array there
 static int diffract_launch(msl_handle* h, const Rows& r, int32_t t0, int32_t count, int32_t wx, int32_t wy, int32_t bx, int32_t by, double* d_dst,
-                           double** d_res, size_t* res_bytes) {
+                           double** d_res, size_t* res_bytes, const char* who = "msl_diffract", double* d_acc = nullptr) {
     int rc;
-    if ((rc = check_window_bin(h, "msl_diffract", wx, wy, bx, by))) return rc;
-    if ((int64_t)wx * wy != r.K) return fail(h, MSL_ERR_INVALID, "msl_diffract: window %d x %d over rows of %lld pixels", wx, wy, (long long)r.K);
-    if ((rc = check_slots(h, "msl_diffract", "frame slots", t0, count, r.R))) return rc;
+    if ((rc = check_window_bin(h, who, wx, wy, bx, by))) return rc;
+    if ((int64_t)wx * wy != r.K) return fail(h, MSL_ERR_INVALID, "%s: window %d x %d over rows of %lld pixels", who, wx, wy, (long long)r.K);
+    if ((rc = check_slots(h, who, "frame slots", t0, count, r.R))) return rc;
     const int mx = wx / bx, my = wy / by;
     const int64_t strips = r.B * mx;                             // one row of bins of one probe
-    if ((int64_t)count * bx > 0x3fffffffLL) return fail(h, MSL_ERR_UNSUPPORTED, "msl_diffract: more than 2^30 rows per bin");
+    if ((int64_t)count * bx > 0x3fffffffLL) return fail(h, MSL_ERR_UNSUPPORTED, "%s: more than 2^30 rows per bin", who);
     const bool pow2 = (by & (by - 1)) == 0;
     const int mode = by == 1 ? DIFF_DIRECT : (pow2 && by <= 64 ? DIFF_SHFL : DIFF_LDS);
     const size_t lds = mode == DIFF_LDS ? (size_t)wy * sizeof(double) : 0;
-    if (lds > 64u * 1024u) return fail(h, MSL_ERR_UNSUPPORTED, "msl_diffract: bin %d of rows of %d pixels needs %zu bytes of LDS", by, wy, lds);
+    if (lds > 64u * 1024u) return fail(h, MSL_ERR_UNSUPPORTED, "%s: bin %d of rows of %d pixels needs %zu bytes of LDS", who, by, wy, lds);
     HIPCHK(h, hipSetDevice(h->cfg.device));
     const size_t n_out = (size_t)strips * my;
-    if (!d_dst && (rc = h->diff_out.reserve(h, n_out))) return rc;
-    double* d_out = d_dst ? d_dst : h->diff_out.p;
+    if (!d_acc && !d_dst && (rc = h->diff_out.reserve(h, n_out))) return rc;
+    double* d_out = d_acc ? d_acc : (d_dst ? d_dst : h->diff_out.p);
     // 16-byte loads need every row to start on 16 bytes: base, image pitch and row length even in pixels
     const bool vec = (r.ld % 2 == 0) && (wy % 2 == 0) && (((uintptr_t)r.p & 15) == 0);
     const int cols = vec ? (wy + 1) / 2 : wy;
@@ -4331,11 +4339,11 @@ static int diffract_launch(msl_handle* h, const Rows& r, int32_t t0, int32_t cou
     per = std::max<int64_t>(1, std::min<int64_t>(per, strips / 4096));
     per = std::max<int64_t>(per, (strips + 0x7ffffffeLL) / 0x7fffffffLL);
     const unsigned grid = (unsigned)((strips + per - 1) / per);
-    with_int<DIFF_DIRECT, DIFF_SHFL, DIFF_LDS>(mode, [&](auto m) { with_bool(vec, [&](auto v) {
-        hipLaunchKernelGGL((diffract_kernel<decltype(m)::value, decltype(v)::value>), dim3(grid), dim3(threads), lds, h->stream, (const float2*)r.p,
-                           (long long)r.R, (long long)t0, (int)count, (long long)r.ld, (int)wx, (int)wy, (int)bx, (int)by, (long long)strips, (int)per,
-                           d_out);
-    }); });
+    with_int<DIFF_DIRECT, DIFF_SHFL, DIFF_LDS>(mode, [&](auto m) { with_bool(vec, [&](auto v) { with_bool(d_acc != nullptr, [&](auto acc) {
+        hipLaunchKernelGGL((diffract_kernel<decltype(m)::value, decltype(v)::value, decltype(acc)::value>), dim3(grid), dim3(threads), lds, h->stream,
+                           (const float2*)r.p, (long long)r.R, (long long)t0, (int)count, (long long)r.ld, (int)wx, (int)wy, (int)bx, (int)by,
+                           (long long)strips, (int)per, d_out);
+    }); }); });
     HIPCHK(h, hipGetLastError());
     if ((rc = mark_launch(h, K_OTHER))) return rc;
     h->ctr.algorithmic_bytes += 8ull * (uint64_t)r.K * (uint64_t)r.B * (uint64_t)count;
@@ -4424,6 +4432,72 @@ int msl_coherent_finish(msl_handle* h, int64_t B, int32_t n, int32_t wx, int32_t
                        mx, my, (int)bx, (int)by, L, (double)n * (double)n, h->diff_out.p);
     HIPCHK(h, hipGetLastError());
     return download_sync(h, out, h->diff_out, (size_t)bins * sizeof(double));
+}
+
+// ---- finite dose (dose.h) ---------------------------------------------------------------------------------
+int msl_dose_reset(msl_handle* h, int64_t B, int32_t mx, int32_t my) {
+    if (!h) return fail(h, MSL_ERR_INVALID, "msl_dose_reset: null handle");
+    if (B < 1) B = h->cfg.n_probes;
+    if (mx < 1 || my < 1) return fail(h, MSL_ERR_INVALID, "msl_dose_reset: pattern of %d x %d pixels", mx, my);
+    const int64_t K = (int64_t)mx * my;
+    if (K > 0xffffffffLL || B > 0xffffffffLL) return fail(h, MSL_ERR_UNSUPPORTED, "msl_dose_reset: more than 2^32 pixels per pattern or probes");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    h->dose_B = 0; h->dose_K = 0;
+    const size_t n = (size_t)B * (size_t)K;
+    int rc = h->dose_acc.reserve(h, n);
+    if (rc) return rc;
+    HIPCHK(h, hipMemsetAsync(h->dose_acc, 0, n * sizeof(double), h->stream));
+    h->dose_B = B; h->dose_K = K; h->dose_mx = mx; h->dose_my = my;
+    return MSL_OK;
+}
+
+int msl_dose_add(msl_handle* h, const void* d_src_c64, int64_t B, int64_t T, int64_t K, int64_t ld, int32_t t0, int32_t count, int32_t wx, int32_t wy,
+                 int32_t bx, int32_t by) {
+    if (!h) return fail(h, MSL_ERR_INVALID, "msl_dose_add: null handle");
+    if (h->dose_B == 0) return fail(h, MSL_ERR_STATE, "msl_dose_add: no accumulator (call msl_dose_reset)");
+    const bool resident = !d_src_c64;
+    Rows r{d_src_c64, B, T, K, ld};
+    int rc = resolve_rows(h, "msl_dose_add", SRC_WAVEFUNCTION | SRC_FIRST_B, &r);
+    if (rc) return rc;
+    if (resident && (wx != h->wx / h->bx || wy != h->wy / h->by))
+        return fail(h, MSL_ERR_INVALID, "msl_dose_add: window %d x %d, the handle stores %d x %d", wx, wy, h->wx / h->bx, h->wy / h->by);
+    if ((rc = check_window_bin(h, "msl_dose_add", wx, wy, bx, by))) return rc;
+    if (r.B > h->dose_B || wx / bx != h->dose_mx || wy / by != h->dose_my)
+        return fail(h, MSL_ERR_INVALID, "msl_dose_add: %lld probes of %d x %d detector pixels, the last msl_dose_reset sized %lld of %d x %d", (long long)r.B,
+                    wx / bx, wy / by, (long long)h->dose_B, h->dose_mx, h->dose_my);
+    double* d_out = nullptr;
+    size_t out_bytes = 0;
+    if ((rc = begin_timed(h, 1))) return rc;
+    return diffract_launch(h, r, t0, count, wx, wy, bx, by, nullptr, &d_out, &out_bytes, "msl_dose_add", h->dose_acc.p);
+}
+
+int msl_dose_counts(msl_handle* h, int64_t B, double scale, uint64_t seed, int64_t probe0, uint32_t* counts_out, double* intensity_out) {
+    if (!h || !counts_out) return fail(h, MSL_ERR_INVALID, "msl_dose_counts: null argument");
+    if (h->dose_B == 0) return fail(h, MSL_ERR_STATE, "msl_dose_counts: no accumulator (call msl_dose_reset)");
+    if (B < 1) B = h->dose_B;
+    if (B > h->dose_B) return fail(h, MSL_ERR_INVALID, "msl_dose_counts: %lld probes, the last msl_dose_reset sized %lld", (long long)B, (long long)h->dose_B);
+    if (!std::isfinite(scale) || scale < 0) return fail(h, MSL_ERR_INVALID, "msl_dose_counts: scale %g is not a finite number >= 0", scale);
+    if (probe0 < 0 || probe0 + B > 0x100000000LL) return fail(h, MSL_ERR_INVALID, "msl_dose_counts: probes [%lld, %lld) outside [0, 2^32)", (long long)probe0, (long long)(probe0 + B));
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    const int64_t n = B * h->dose_K;
+    const int64_t blocks = (n + 255) / 256;
+    if (blocks > 0x7fffffffLL) return fail(h, MSL_ERR_UNSUPPORTED, "msl_dose_counts: too many detector pixels");
+    int rc = h->dose_cnt.reserve(h, (size_t)n + 1);              // the counts, then the flag word
+    if (rc) return rc;
+    uint32_t* d_flag = h->dose_cnt.p + n;
+    HIPCHK(h, hipMemsetAsync(d_flag, 0, sizeof(uint32_t), h->stream));
+    if ((rc = begin_timed(h, 1))) return rc;
+    hipLaunchKernelGGL(dose_counts_kernel, dim3((unsigned)blocks), dim3(256), 0, h->stream, (const double*)h->dose_acc.p, (long long)n, (long long)h->dose_K,
+                       scale, (uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)probe0, h->dose_cnt.p, d_flag);
+    HIPCHK(h, hipGetLastError());
+    if ((rc = mark_launch(h, K_OTHER))) return rc;
+    uint32_t flag = 0;
+    HIPCHK(h, hipMemcpyAsync(counts_out, h->dose_cnt.p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(&flag, d_flag, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    if (intensity_out) HIPCHK(h, hipMemcpyAsync(intensity_out, h->dose_acc.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (flag) return fail(h, MSL_ERR_INVALID, "msl_dose_counts: an expected count (accumulator x scale %g) is negative or not finite", scale);
+    return MSL_OK;
 }
 
 // ---- images through an objective lens (image.h) -----------------------------------------------------------

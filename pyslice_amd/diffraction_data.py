@@ -19,9 +19,11 @@ from .stem_data import Detector, STEMData, scan_axes, scan_image
 class Diffraction:
     """The request: bin=(bx, by) stored pixels per detector pixel along kx and ky (both must divide the stored spectrum);
     split=True also asks for the elastic part |<Psi>|^2 of every pattern (DiffractionData.elastic / .tds), which costs one
-    potential build per probe batch and frame instead of one per frame (MultisliceCalculator.run_diffraction)."""
+    potential build per probe batch and frame instead of one per frame (MultisliceCalculator.run_diffraction).
+    dose=dose.Dose(...) asks for Poisson-counted patterns at that dose, drawn on the device (DiffractionData.counts); it takes the
+    loop order of the split, at the same price, and is not built together with it."""
 
-    def __init__(self, bin=(1, 1), split=False):
+    def __init__(self, bin=(1, 1), split=False, dose=None):
         try:
             ok = len(bin) == 2 and all(isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_)) and int(v) >= 1 for v in bin)
         except TypeError:
@@ -30,11 +32,19 @@ class Diffraction:
             raise ValueError(f"Diffraction: bin must be two positive integers (bx, by), got {bin!r}")
         if not isinstance(split, (bool, np.bool_)):
             raise ValueError(f"Diffraction: split must be True or False, got {split!r}")
+        if dose is not None:
+            from .dose import Dose
+            if not isinstance(dose, Dose):
+                raise ValueError(f"Diffraction: dose must be a Dose object, got {dose!r}")
+            if split:
+                raise NotImplementedError("dose: split=True is not built")
         self.bin = (int(bin[0]), int(bin[1]))
         self.split = bool(split)
+        self.dose = dose
 
     def __repr__(self):
-        return f"Diffraction(bin={self.bin}, split=True)" if self.split else f"Diffraction(bin={self.bin})"
+        return (f"Diffraction(bin={self.bin}" + (", split=True" if self.split else "")
+                + (f", dose={self.dose!r}" if self.dose is not None else "") + ")")
 
 
 def bin_centres(axis, b):
@@ -61,8 +71,13 @@ class DiffractionData:
     `thickness` the depth in Angstrom at the exit side of each slice, at(i) is the ordinary DiffractionData of entry i (its stem
     too), and pacbed / virtual / image / pattern take layer=-1, the exit wave.  With Thickness(patterns="pacbed") only the
     position-averaged pattern was kept: intensity is (mx, my, L) -- (mx, my) after at(i) -- which pacbed() returns and the
-    per-position methods refuse."""
-    intensity: np.ndarray
+    per-position methods refuse.
+    With Diffraction(dose=Dose(...)) `counts` (P, mx, my) uint32 holds the electrons every detector pixel recorded at
+    `electrons_per_probe` incident electrons per position (dose.py is the definition of the draw; `dose` the request, `incident` the
+    spectrum-intensity sum of the incident probe, so that the expected count of a pixel is intensity * electrons_per_probe /
+    incident); `intensity` is the noise-free mean only with Dose(keep_intensity=True), None otherwise.  pacbed / virtual / image /
+    pattern then work on the counts, in electrons as float64, and take part="counts" | "intensity" when both are there."""
+    intensity: Optional[np.ndarray]
     kxs: Any
     kys: Any
     bin: Tuple[int, int]
@@ -78,10 +93,21 @@ class DiffractionData:
     thickness: Optional[np.ndarray] = None
     patterns: str = "position"
     tilts: Optional[list] = None            # the tilt.Tilt of every run of a precession average (tilt order); None otherwise
+    counts: Optional[np.ndarray] = None
+    dose: Any = None
+    electrons_per_probe: Optional[float] = None
+    incident: Optional[float] = None
 
     def __post_init__(self):
         if self.patterns not in ("position", "pacbed"):
             raise ValueError(f"patterns must be 'position' or 'pacbed', got {self.patterns!r}")
+        if self.intensity is None and self.counts is None:
+            raise ValueError("DiffractionData needs intensity or counts")
+        if self.counts is not None:
+            if self.layer is not None or self.patterns != "position" or np.ndim(self.counts) != 3:
+                raise ValueError("counts are per-position patterns (P, mx, my) without a thickness axis")
+            if self.intensity is not None and np.shape(self.intensity) != np.shape(self.counts):
+                raise ValueError(f"counts have shape {np.shape(self.counts)}, intensity {np.shape(self.intensity)}")
         want = (3 if self.patterns == "position" else 2) + (self.layer is not None)
         if (self.layer is not None or self.patterns == "pacbed") and (
                 np.ndim(self.intensity) != want or (self.layer is not None and np.shape(self.intensity)[-1] != len(self.layer))):
@@ -102,6 +128,19 @@ class DiffractionData:
         j = entry(self.layer, i)
         return replace(self, intensity=self.intensity[..., j], layer=None, thickness=None,
                        stem=None if self.stem is None else self.stem.at(j))
+
+    def _data(self, part=None):
+        """the array the reductions read: part=None is the intensity as ever, and the counts (as float64 electrons) when there is
+        no intensity; "counts" / "intensity" name one"""
+        if part not in (None, "counts", "intensity"):
+            raise ValueError(f"part must be 'counts' or 'intensity', got {part!r}")
+        if part is None:
+            part = "intensity" if self.intensity is not None else "counts"
+        arr = self.counts if part == "counts" else self.intensity
+        if arr is None:
+            raise ValueError("this DiffractionData has no counts: run with Diffraction(dose=Dose(...))" if part == "counts" else
+                             "this DiffractionData has no intensity: run with Dose(keep_intensity=True)")
+        return arr.astype(np.float64) if part == "counts" else arr
 
     def _per_position(self, what):
         if self.patterns != "position":
@@ -126,11 +165,12 @@ class DiffractionData:
         arr = {"total": self.intensity, "elastic": self.elastic, "tds": None}[name]
         return replace(self, intensity=self.tds if arr is None else arr, elastic=None)
 
-    def pacbed(self, layer=-1) -> np.ndarray:
+    def pacbed(self, layer=-1, part=None) -> np.ndarray:
         """(mx, my): position-averaged pattern, the mean over the probes; of thickness entry `layer` when there is a thickness axis"""
         if self.layer is not None:
-            return self.at(layer).pacbed()
-        return self.intensity if self.patterns == "pacbed" else self.intensity.mean(axis=0)
+            return self.at(layer).pacbed(part=part)
+        data = self._data(part)
+        return data if self.patterns == "pacbed" else data.mean(axis=0)
 
     def member(self, detector: Detector) -> np.ndarray:
         """(mx, my) bool: the detector pixels whose CENTRE lies in `detector` (its member() on the bin-centre axes)"""
@@ -142,22 +182,22 @@ class DiffractionData:
             raise ValueError("DiffractionData has neither a probe nor a wavelength: detector angles cannot be turned into k")
         return detector.member(_np(self.kxs), _np(self.kys), self.wavelength)
 
-    def virtual(self, detector: Detector, layer=-1) -> np.ndarray:
+    def virtual(self, detector: Detector, layer=-1, part=None) -> np.ndarray:
         """(P,): the virtual detector chosen after the run -- sum of the detector pixels inside `detector`"""
         if self.layer is not None:
-            return self.at(layer).virtual(detector)
+            return self.at(layer).virtual(detector, part=part)
         self._per_position("virtual()")
         m = self.member(detector)
-        return (self.intensity * m[None].astype(np.float64)).sum(axis=(-2, -1))
+        return (self._data(part) * m[None].astype(np.float64)).sum(axis=(-2, -1))
 
-    def image(self, detector: Detector, layer=-1) -> np.ndarray:
+    def image(self, detector: Detector, layer=-1, part=None) -> np.ndarray:
         """(len(xs), len(ys)) scan image of virtual(detector): every scan point takes its nearest probe's value (STEMData.image)"""
-        return scan_image(self.virtual(detector, layer), self.probe_positions, self.xs, self.ys)
+        return scan_image(self.virtual(detector, layer, part), self.probe_positions, self.xs, self.ys)
 
-    def pattern(self, x: float, y: float, layer=-1) -> np.ndarray:
+    def pattern(self, x: float, y: float, layer=-1, part=None) -> np.ndarray:
         """(mx, my): the pattern of the probe nearest to (x, y)"""
         if self.layer is not None:
-            return self.at(layer).pattern(x, y)
+            return self.at(layer).pattern(x, y, part=part)
         self._per_position("pattern()")
         pp = np.asarray(self.probe_positions, dtype=np.float64).reshape(-1, 2)
-        return self.intensity[int(np.argmin(((pp - np.array([x, y])[None, :]) ** 2).sum(axis=1)))]
+        return self._data(part)[int(np.argmin(((pp - np.array([x, y])[None, :]) ** 2).sum(axis=1)))]

@@ -179,6 +179,17 @@ class PolarData:
         return replace(self, signals=self.signals[..., j], layer=None, thickness=None,
                        stem=None if self.stem is None else self.stem.at(j))
 
+    def poisson(self, dose, seed=None) -> np.ndarray:
+        """uint32 of the shape of `signals`: the electrons every bin counts at `dose` (electrons per probe position, or a
+        dose.Dose), drawn on the host by dose.poisson_counts from the signals per incident electron; probe p keyed by its index, the
+        pixel index the row-major index of the rest (per_frame: every frame is an exposure of its own at that dose).  seed=None: the
+        Dose's seed (0 for a number)."""
+        from .dose import Dose, poisson_signals, probe_incident
+        n_e = dose.electrons(self.probe_positions) if isinstance(dose, Dose) else dose
+        if seed is None:
+            seed = dose.seed if isinstance(dose, Dose) else 0
+        return poisson_signals(self.signals, n_e, probe_incident(self.probe), seed)
+
     def _edge(self, what, angle) -> int:
         e = np.asarray(self.edges, dtype=np.float64)
         i = int(np.argmin(np.abs(e - angle)))

@@ -162,6 +162,20 @@ class STEMData:
         """signals + tds: the elastic part and the thermal diffuse part of every detector"""
         return self.signals + self.tds
 
+    def poisson(self, dose, seed=None) -> np.ndarray:
+        """(P, D) uint32 -- (P, D, L) with a thickness axis: the electrons every detector counts at `dose` (electrons per probe
+        position, or a dose.Dose), drawn on the host by dose.poisson_counts from the frame mean of the signals per incident electron;
+        probe p keyed by its index, the pixel index the row-major index of the rest.  seed=None: the Dose's seed (0 for a number).
+        Intensity detectors only: an amplitude or a centre of mass is no count."""
+        from .dose import Dose, poisson_signals, probe_incident
+        bad = [d.name for d in self.detectors if d.signal != "intensity"]
+        if bad:
+            raise ValueError(f"poisson(): detectors {bad} do not have the intensity signal; counts are defined for intensities only")
+        n_e = dose.electrons(self.probe_positions) if isinstance(dose, Dose) else dose
+        if seed is None:
+            seed = dose.seed if isinstance(dose, Dose) else 0
+        return poisson_signals(np.asarray(self.signals, dtype=np.float64).mean(axis=1), n_e, probe_incident(self.probe), seed)
+
     def index(self, name: str) -> int:
         for d, det in enumerate(self.detectors):
             if det.name == name:
