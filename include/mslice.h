@@ -777,6 +777,31 @@ int  msl_fft2_host(msl_handle* h, const float* in_c64, float* out_c64, int32_t b
 int  msl_set_projection(msl_handle* h, int32_t reach_slices, int32_t nodes);
 int  msl_get_projection(const msl_handle* h, int32_t* reach_nodes);
 
+/* ---- detector response: point spread, gain, dark offset, readout noise, uint16 frames ----
+ * What a camera writes for the electron counts of a probe batch; the definition, word for word, is pyslice_amd/camera.py.  For pixel
+ * (ix, iy) of the mx x my pattern of probe p, with c the counts as float64 and zero outside the pattern:
+ *     s = 0;  for a = -r .. r:  for b = -r .. r:  s = s + psf[(a+r)*(2r+1) + (b+r)] * c[ix-a, iy-b]      (a convolution, zero boundary)
+ *     e = gain * s;  e = e + offset;  readout_noise > 0 only:  e = e + readout_noise * sqrt(-2 ln u) * cos(2 pi v)
+ *     frame = clip(rint(e), 0, 2^bits - 1) as uint16
+ * every product and sum rounded on its own in float64; (u, v) = U(x0, x1), U(x2, x3) of Philox-4x32-10 under the 64-bit key seed with
+ * the counter (ix*my + iy, p, 0, 1) -- word 3 = 1, the Poisson draws of msl_dose_counts use 0 -- and the U of msl_dose_counts.
+ * msl_set_camera: copies the (2 radius + 1)^2 weights (HOST memory, row-major [a+r][b+r]; NULL only with radius 0: the weight 1) to the
+ *   device and stores the scalars.  radius < 0 clears the camera.  MSL_ERR_INVALID for a radius above 8, a NULL table with radius > 0, a
+ *   negative or non-finite weight, a gain not finite and > 0, a negative or non-finite offset or readout_noise, bits outside 1 .. 16;
+ *   the camera set before is then kept.  Touches nothing else on the handle.
+ * msl_camera_frames: uploads B*mx*my counts from HOST memory into the count staging of msl_dose_counts, runs the pass for the probes
+ *   probe0 .. probe0 + B - 1 (one launch) and downloads B*mx*my uint16 to frames_out, HOST memory.  MSL_ERR_STATE without a camera;
+ *   MSL_ERR_INVALID for a NULL pointer, B < 1, mx < 1 or my < 1, probes outside [0, 2^32).  The accumulator of msl_dose_reset is not touched.
+ * msl_dose_frames: the draw of msl_dose_counts into the staging (its arguments, checks and flag word) and the pass on the same stream,
+ *   then one download of 2 bytes per pixel to frames_out; the counts (B*mx*my uint32) and the accumulator (B*mx*my float64) come back
+ *   only where their pointers are not NULL.  MSL_ERR_STATE before a msl_dose_reset or without a camera.
+ * Without readout noise the frames are the definition's bit for bit; with it they may differ by one unit where the device's log, sqrt
+ * or cos differ from the host's in the last place and e lies that close to a half-integer.  Not in the reference. */
+int  msl_set_camera(msl_handle* h, int32_t radius, const double* psf, double gain, double offset, double readout_noise, int32_t bits);
+int  msl_camera_frames(msl_handle* h, const uint32_t* counts_host, int64_t B, int32_t mx, int32_t my, uint64_t seed, int64_t probe0, uint16_t* frames_out);
+int  msl_dose_frames(msl_handle* h, int64_t B, double scale, uint64_t seed, int64_t probe0, uint16_t* frames_out, uint32_t* counts_out_or_null,
+                     double* intensity_out_or_null);
+
 #ifdef __cplusplus
 }
 #endif

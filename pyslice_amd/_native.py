@@ -37,6 +37,7 @@ EXPORTS = [
     "msl_polar_layout", "msl_set_polar", "msl_polar_detect",
     "msl_coherent_reset", "msl_coherent_add", "msl_coherent_finish",
     "msl_dose_reset", "msl_dose_add", "msl_dose_counts",
+    "msl_set_camera", "msl_camera_frames", "msl_dose_frames",
     "msl_image_reset", "msl_image_add", "msl_image_download",
     "msl_smatrix_begin", "msl_smatrix_beams", "msl_smatrix_build", "msl_smatrix_probes", "msl_smatrix_probes_cropped",
     "msl_smatrix_end",
@@ -151,6 +152,9 @@ def load():
         "msl_dose_reset": (C.c_int, [vp, i64, i32, i32]),
         "msl_dose_add": (C.c_int, [vp, vp, i64, i64, i64, i64, i32, i32, i32, i32, i32, i32]),
         "msl_dose_counts": (C.c_int, [vp, i64, dbl, C.c_uint64, i64, vp, vp]),
+        "msl_set_camera": (C.c_int, [vp, i32, vp, dbl, dbl, dbl, i32]),
+        "msl_camera_frames": (C.c_int, [vp, vp, i64, i32, i32, C.c_uint64, i64, vp]),
+        "msl_dose_frames": (C.c_int, [vp, i64, dbl, C.c_uint64, i64, vp, vp, vp]),
         "msl_image_reset": (C.c_int, [vp, i64]),
         "msl_image_add": (C.c_int, [vp, vp, i64, i64, i64, i32, i32, vp, dbl, dbl, i64, i64]),
         "msl_image_download": (C.c_int, [vp, i64, i64, vp]),
@@ -916,6 +920,43 @@ class Engine:
         self._chk(self._lib.msl_dose_counts(self._h, b, float(scale), int(seed), int(probe0), _ptr(counts),
                                             None if acc is None else _ptr(acc)))
         return counts, acc
+
+    # -- detector response (msl_set_camera / msl_camera_frames / msl_dose_frames)
+    def set_camera(self, camera):
+        """the camera.Camera whose frames camera_frames() / dose_frames() compute; None clears it.  Nothing else on the handle changes."""
+        if camera is None:
+            self._chk(self._lib.msl_set_camera(self._h, -1, None, 1.0, 0.0, 0.0, 16))
+            return
+        psf = np.ascontiguousarray(camera.psf, dtype=np.float64)
+        self._chk(self._lib.msl_set_camera(self._h, int(camera.radius), _ptr(psf), float(camera.gain), float(camera.offset),
+                                           float(camera.readout_noise), int(camera.bits)))
+
+    def camera_frames(self, counts, seed=0, probe0=0):
+        """(B, mx, my) uint16: the device's camera.camera_frames of the caller's counts (B, mx, my) -- any unsigned integers up to
+        2^32 - 1 -- for the probes probe0 .. probe0 + B - 1"""
+        c = np.ascontiguousarray(counts, dtype=np.uint32)
+        if c.ndim != 3:
+            raise ValueError(f"camera_frames: counts must be (B, mx, my), got shape {c.shape}")
+        frames = np.empty(c.shape if c.size else (1,), dtype=np.uint16)
+        self._chk(self._lib.msl_camera_frames(self._h, _ptr(c) if c.size else None, c.shape[0], c.shape[1], c.shape[2], int(seed), int(probe0),
+                                              _ptr(frames)))
+        return frames
+
+    def dose_frames(self, scale, seed, probe0=0, B=None, keep_counts=False, keep_intensity=False):
+        """(frames (B, mx, my) uint16, counts (B, mx, my) uint32 or None, acc (B, mx, my) float64 or None): dose_counts() followed by
+        the camera on the device; the counts and the accumulator are downloaded only when asked for"""
+        shape = getattr(self, "_dose_shape", None)
+        if shape is None:                                           # (the output is sized from the reset this wrapper made)
+            raise RuntimeError("dose_frames: no accumulator (call dose_reset)")
+        b = int(B) if B else shape[0]
+        ok = 0 < b <= shape[0]                                      # (else the library refuses: no output is written)
+        dims = (b, shape[1], shape[2]) if ok else (1,)
+        frames = np.empty(dims, dtype=np.uint16)
+        counts = np.empty(dims, dtype=np.uint32) if keep_counts else None
+        acc = np.empty(dims, dtype=np.float64) if keep_intensity else None
+        self._chk(self._lib.msl_dose_frames(self._h, b, float(scale), int(seed), int(probe0), _ptr(frames),
+                                            None if counts is None else _ptr(counts), None if acc is None else _ptr(acc)))
+        return frames, counts, acc
 
     # -- images through an objective lens (msl_image_reset / msl_image_add / msl_image_download)
     def image_reset(self, n):

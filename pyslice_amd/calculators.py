@@ -301,6 +301,7 @@ class MultisliceCalculator:
                 if val:
                     raise NotImplementedError(f"ionization: {what} is not built")
         self._dose = getattr(diffraction, "dose", None)
+        self._camera = getattr(diffraction, "camera", None)     # (only with a dose: Diffraction refuses it otherwise, so it inherits the refusals below)
         self.electrons_per_probe = None         # setup(): the electrons per probe position of a dose run
         if self._dose is not None:
             # counts are drawn from the per-probe frame sums of the exit patterns on the device: the modes that reduce elsewhere, keep
@@ -862,7 +863,7 @@ class MultisliceCalculator:
         tables = self._phase_table_bytes(batch)
         coh = 16.0 * pitch if self._diffraction is not None and self._diffraction.split else 0.0
         if getattr(self, "_dose", None) is not None:                # (the float64 frame sums and the uint32 counts of a probe's pattern)
-            coh = 12.0 * pitch
+            coh = (14.0 if getattr(self, "_camera", None) is not None else 12.0) * pitch     # (and the uint16 frames of a camera)
         if self._imaging is not None:
             coh = 8.0 * nx * ny * len(self._layers) * len(self._imaging.defocus_series)
         smatrix = 8.0 * getattr(self, "_prism_Bm", 0) * nx * ny       # the S-matrix of a PRISM run, (Bm, nx, ny) complex64
@@ -1186,7 +1187,10 @@ class MultisliceCalculator:
         msl_dose_add (the pattern pass, added into the float64 accumulator on the device), then msl_dose_counts draws the Poisson
         counts there (dose.py) and downloads 4 bytes per detector pixel -> .counts (P, mx, my) uint32; .intensity only with
         Dose(keep_intensity=True).  The counts do not depend on probe_batch (the draws are keyed by the
-        probe's index in the scan)."""
+        probe's index in the scan).
+        With Diffraction(dose=..., camera=Camera(...)) msl_dose_frames takes the place of msl_dose_counts: the draw, then the camera's
+        response to the counts on the device (camera.py), and 2 bytes per detector pixel downloaded -> .frames (P, mx, my) uint16;
+        .counts only with Camera(keep_counts=True).  The readout noise is keyed as the draws are: no dependence on probe_batch."""
         from .diffraction_data import DiffractionData, bin_centres
         if self._spectroscopy is not None:
             raise RuntimeError("spectroscopy is set: the device holds one probe batch at a time -- call run_spectrum_image()")
@@ -1206,10 +1210,15 @@ class MultisliceCalculator:
         keep = dose is None or dose.keep_intensity
         acc = self._layered(((mx, my) if pacbed else (P, mx, my)) if keep else (0,))
         signals = None if self._detectors is None else self._layered((P, T, len(self._detectors)))
-        counts = incident = None
+        counts = incident = frames = None
+        camera = self._camera
         if dose is not None:
             from .dose import incident_intensity
-            counts = np.zeros((P, mx, my), dtype=np.uint32)
+            if camera is None or camera.keep_counts:
+                counts = np.zeros((P, mx, my), dtype=np.uint32)
+            if camera is not None:
+                frames = np.zeros((P, mx, my), dtype=np.uint16)
+                eng.set_camera(camera)
             incident = incident_intensity(self.nx, self.ny, self.dx, self.dy, self.aperture, wavelength(self.voltage_eV))
             dose_scale = self.electrons_per_probe / (T * incident)      # electrons per unit of the frame SUM
 
@@ -1238,7 +1247,13 @@ class MultisliceCalculator:
             self._frames_inside_loop(reduce_batch, finish_batch)
         elif dose is not None:
             def finish_batch(p0, real):
-                counts[p0:p0 + real], sums = eng.dose_counts(dose_scale, dose.seed, probe0=p0, B=real, keep_intensity=keep)
+                if camera is not None:
+                    frames[p0:p0 + real], cnt, sums = eng.dose_frames(dose_scale, dose.seed, probe0=p0, B=real,
+                                                                      keep_counts=camera.keep_counts, keep_intensity=keep)
+                    if cnt is not None:
+                        counts[p0:p0 + real] = cnt
+                else:
+                    counts[p0:p0 + real], sums = eng.dose_counts(dose_scale, dose.seed, probe0=p0, B=real, keep_intensity=keep)
                 if keep:
                     acc[p0:p0 + real] = sums
             self._frames_inside_loop(reduce_batch, finish_batch, coherent=False)
@@ -1256,7 +1271,7 @@ class MultisliceCalculator:
                                               stem=None if signals is None else self._stem_data(signals), elastic=elastic,
                                               patterns="pacbed" if pacbed else "position", counts=counts, dose=dose,
                                               electrons_per_probe=self.electrons_per_probe if dose is not None else None,
-                                              incident=incident, **self._layer_fields()))
+                                              incident=incident, frames=frames, camera=camera, **self._layer_fields()))
 
     def run_images(self):
         """Frame-averaged images behind the objective lens (HRTEM, focal series), for every probe: probe batches outside, frame

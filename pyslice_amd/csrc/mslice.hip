@@ -37,6 +37,7 @@
 #include "diffract.h"
 #include "coherent.h"
 #include "dose.h"
+#include "camera.h"
 #include "image.h"
 #include "smatrix.h"
 #include "propagator.h"
@@ -240,6 +241,12 @@ struct msl_handle {
     DevBuf<uint32_t> dose_cnt;
     int64_t dose_B = 0, dose_K = 0;
     int dose_mx = 0, dose_my = 0;
+    // detector response (msl_set_camera; camera.h): the weights padded to the radius class, the scalars of the response, and the uint16
+    // staging of the frames, grown on demand; cam_radius < 0: no camera
+    DevBuf<double> cam_psf;
+    DevBuf<uint16_t> cam_frames;
+    int cam_radius = -1, cam_class = 0, cam_bits = 16;
+    double cam_gain = 1.0, cam_offset = 0.0, cam_noise = 0.0;
     // image accumulator (msl_image_reset / _add / _download): (img_n, nx * ny) float64, grown on demand
     DevBuf<double> img_acc;
     int64_t img_n = 0;
@@ -4471,33 +4478,129 @@ int msl_dose_add(msl_handle* h, const void* d_src_c64, int64_t B, int64_t T, int
     return diffract_launch(h, r, t0, count, wx, wy, bx, by, nullptr, &d_out, &out_bytes, "msl_dose_add", h->dose_acc.p);
 }
 
-int msl_dose_counts(msl_handle* h, int64_t B, double scale, uint64_t seed, int64_t probe0, uint32_t* counts_out, double* intensity_out) {
-    if (!h || !counts_out) return fail(h, MSL_ERR_INVALID, "msl_dose_counts: null argument");
-    if (h->dose_B == 0) return fail(h, MSL_ERR_STATE, "msl_dose_counts: no accumulator (call msl_dose_reset)");
-    if (B < 1) B = h->dose_B;
-    if (B > h->dose_B) return fail(h, MSL_ERR_INVALID, "msl_dose_counts: %lld probes, the last msl_dose_reset sized %lld", (long long)B, (long long)h->dose_B);
-    if (!std::isfinite(scale) || scale < 0) return fail(h, MSL_ERR_INVALID, "msl_dose_counts: scale %g is not a finite number >= 0", scale);
-    if (probe0 < 0 || probe0 + B > 0x100000000LL) return fail(h, MSL_ERR_INVALID, "msl_dose_counts: probes [%lld, %lld) outside [0, 2^32)", (long long)probe0, (long long)(probe0 + B));
+// the draw of msl_dose_counts / msl_dose_frames into the count staging (the counts, then the flag word): checks, launch, no download
+static int dose_draw(msl_handle* h, const char* who, int64_t* B, double scale, uint64_t seed, int64_t probe0) {
+    if (h->dose_B == 0) return fail(h, MSL_ERR_STATE, "%s: no accumulator (call msl_dose_reset)", who);
+    if (*B < 1) *B = h->dose_B;
+    if (*B > h->dose_B) return fail(h, MSL_ERR_INVALID, "%s: %lld probes, the last msl_dose_reset sized %lld", who, (long long)*B, (long long)h->dose_B);
+    if (!std::isfinite(scale) || scale < 0) return fail(h, MSL_ERR_INVALID, "%s: scale %g is not a finite number >= 0", who, scale);
+    if (probe0 < 0 || probe0 + *B > 0x100000000LL)
+        return fail(h, MSL_ERR_INVALID, "%s: probes [%lld, %lld) outside [0, 2^32)", who, (long long)probe0, (long long)(probe0 + *B));
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    const int64_t n = B * h->dose_K;
+    const int64_t n = *B * h->dose_K;
     const int64_t blocks = (n + 255) / 256;
-    if (blocks > 0x7fffffffLL) return fail(h, MSL_ERR_UNSUPPORTED, "msl_dose_counts: too many detector pixels");
+    if (blocks > 0x7fffffffLL) return fail(h, MSL_ERR_UNSUPPORTED, "%s: too many detector pixels", who);
     int rc = h->dose_cnt.reserve(h, (size_t)n + 1);              // the counts, then the flag word
     if (rc) return rc;
     uint32_t* d_flag = h->dose_cnt.p + n;
     HIPCHK(h, hipMemsetAsync(d_flag, 0, sizeof(uint32_t), h->stream));
-    if ((rc = begin_timed(h, 1))) return rc;
+    if ((rc = begin_timed(h, 2))) return rc;
     hipLaunchKernelGGL(dose_counts_kernel, dim3((unsigned)blocks), dim3(256), 0, h->stream, (const double*)h->dose_acc.p, (long long)n, (long long)h->dose_K,
                        scale, (uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)probe0, h->dose_cnt.p, d_flag);
     HIPCHK(h, hipGetLastError());
-    if ((rc = mark_launch(h, K_OTHER))) return rc;
+    return mark_launch(h, K_OTHER);
+}
+
+// what follows the draw: the downloads asked for (null: none), the flag word, one wait
+static int dose_collect(msl_handle* h, const char* who, int64_t n, double scale, uint32_t* counts_out, double* intensity_out, uint16_t* frames_out) {
     uint32_t flag = 0;
-    HIPCHK(h, hipMemcpyAsync(counts_out, h->dose_cnt.p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(&flag, d_flag, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    if (frames_out) HIPCHK(h, hipMemcpyAsync(frames_out, h->cam_frames.p, (size_t)n * sizeof(uint16_t), hipMemcpyDeviceToHost, h->stream));
+    if (counts_out) HIPCHK(h, hipMemcpyAsync(counts_out, h->dose_cnt.p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(&flag, h->dose_cnt.p + n, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
     if (intensity_out) HIPCHK(h, hipMemcpyAsync(intensity_out, h->dose_acc.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (flag) return fail(h, MSL_ERR_INVALID, "msl_dose_counts: an expected count (accumulator x scale %g) is negative or not finite", scale);
+    if (flag) return fail(h, MSL_ERR_INVALID, "%s: an expected count (accumulator x scale %g) is negative or not finite", who, scale);
     return MSL_OK;
+}
+
+int msl_dose_counts(msl_handle* h, int64_t B, double scale, uint64_t seed, int64_t probe0, uint32_t* counts_out, double* intensity_out) {
+    if (!h || !counts_out) return fail(h, MSL_ERR_INVALID, "msl_dose_counts: null argument");
+    int rc = dose_draw(h, "msl_dose_counts", &B, scale, seed, probe0);
+    if (rc) return rc;
+    return dose_collect(h, "msl_dose_counts", B * h->dose_K, scale, counts_out, intensity_out, nullptr);
+}
+
+// ---- detector response (camera.h) -------------------------------------------------------------------------
+static int camera_class(int radius) { return radius <= 0 ? 0 : radius <= 1 ? 1 : radius <= 2 ? 2 : radius <= 4 ? 4 : CAM_RADIUS_MAX; }
+
+int msl_set_camera(msl_handle* h, int32_t radius, const double* psf, double gain, double offset, double readout_noise, int32_t bits) {
+    if (!h) return fail(h, MSL_ERR_INVALID, "msl_set_camera: null handle");
+    if (radius < 0) { h->cam_radius = -1; return MSL_OK; }
+    if (radius > CAM_RADIUS_MAX) return fail(h, MSL_ERR_INVALID, "msl_set_camera: radius %d is above %d", radius, CAM_RADIUS_MAX);
+    if (!psf && radius != 0) return fail(h, MSL_ERR_INVALID, "msl_set_camera: no table for radius %d", radius);
+    const int w = 2 * radius + 1;
+    for (int i = 0; psf && i < w * w; ++i)
+        if (!std::isfinite(psf[i]) || psf[i] < 0) return fail(h, MSL_ERR_INVALID, "msl_set_camera: weight %d (%g) is negative or not finite", i, psf[i]);
+    if (!std::isfinite(gain) || !(gain > 0)) return fail(h, MSL_ERR_INVALID, "msl_set_camera: gain %g is not a finite number > 0", gain);
+    if (!std::isfinite(offset) || offset < 0) return fail(h, MSL_ERR_INVALID, "msl_set_camera: offset %g is not a finite number >= 0", offset);
+    if (!std::isfinite(readout_noise) || readout_noise < 0)
+        return fail(h, MSL_ERR_INVALID, "msl_set_camera: readout noise %g is not a finite number >= 0", readout_noise);
+    if (bits < 1 || bits > 16) return fail(h, MSL_ERR_INVALID, "msl_set_camera: %d bits, outside 1 .. 16", bits);
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    const int rc_ = camera_class(radius), wc = 2 * rc_ + 1;      // the table of the class: zero weights around the caller's
+    std::vector<double> tab((size_t)wc * wc, 0.0);
+    for (int a = 0; a < w; ++a)
+        for (int b = 0; b < w; ++b) tab[(size_t)(a + rc_ - radius) * wc + (b + rc_ - radius)] = psf ? psf[a * w + b] + 0.0 : 1.0;
+    h->cam_radius = -1;
+    int rc = h->cam_psf.reserve(h, (size_t)(2 * CAM_RADIUS_MAX + 1) * (2 * CAM_RADIUS_MAX + 1));
+    if (rc) return rc;
+    HIPCHK(h, hipMemcpyAsync(h->cam_psf.p, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));                  // (tab leaves scope)
+    h->cam_radius = radius; h->cam_class = rc_; h->cam_bits = bits;
+    h->cam_gain = gain; h->cam_offset = offset; h->cam_noise = readout_noise;
+    return MSL_OK;
+}
+
+// the camera pass over the B patterns of mx x my counts at the head of the count staging -> the frame staging; one launch
+static int camera_launch(msl_handle* h, const char* who, int64_t B, int mx, int my, uint64_t seed, int64_t probe0) {
+    CameraArgs g;
+    g.tiles_x = (mx + CAM_TX - 1) / CAM_TX; g.tiles_y = (my + CAM_TY - 1) / CAM_TY;
+    const int64_t per = (int64_t)g.tiles_x * g.tiles_y;
+    if (per > 0x7fffffffLL || B > 0x7fffffffLL / per) return fail(h, MSL_ERR_UNSUPPORTED, "%s: too many detector pixels", who);
+    int rc = h->cam_frames.reserve(h, (size_t)B * mx * my);
+    if (rc) return rc;
+    g.counts = h->dose_cnt.p; g.psf = h->cam_psf.p; g.frames = h->cam_frames.p;
+    g.mx = mx; g.my = my;
+    g.gain = h->cam_gain; g.offset = h->cam_offset; g.noise = h->cam_noise; g.full = (double)((1 << h->cam_bits) - 1);
+    g.k0 = (uint32_t)seed; g.k1 = (uint32_t)(seed >> 32); g.probe0 = (uint32_t)probe0;
+    const dim3 grid((unsigned)(B * per)), block(256);
+    switch (h->cam_class) {
+        case 0: hipLaunchKernelGGL(camera_frames_kernel<0>, grid, block, 0, h->stream, g); break;
+        case 1: hipLaunchKernelGGL(camera_frames_kernel<1>, grid, block, 0, h->stream, g); break;
+        case 2: hipLaunchKernelGGL(camera_frames_kernel<2>, grid, block, 0, h->stream, g); break;
+        case 4: hipLaunchKernelGGL(camera_frames_kernel<4>, grid, block, 0, h->stream, g); break;
+        default: hipLaunchKernelGGL(camera_frames_kernel<CAM_RADIUS_MAX>, grid, block, 0, h->stream, g); break;
+    }
+    HIPCHK(h, hipGetLastError());
+    return mark_launch(h, K_OTHER);
+}
+
+int msl_camera_frames(msl_handle* h, const uint32_t* counts_host, int64_t B, int32_t mx, int32_t my, uint64_t seed, int64_t probe0, uint16_t* frames_out) {
+    if (!h || !counts_host || !frames_out) return fail(h, MSL_ERR_INVALID, "msl_camera_frames: null argument");
+    if (h->cam_radius < 0) return fail(h, MSL_ERR_STATE, "msl_camera_frames: no camera (call msl_set_camera)");
+    if (B < 1 || mx < 1 || my < 1) return fail(h, MSL_ERR_INVALID, "msl_camera_frames: %lld patterns of %d x %d pixels", (long long)B, mx, my);
+    if (probe0 < 0 || probe0 + B > 0x100000000LL)
+        return fail(h, MSL_ERR_INVALID, "msl_camera_frames: probes [%lld, %lld) outside [0, 2^32)", (long long)probe0, (long long)(probe0 + B));
+    const int64_t K = (int64_t)mx * my;
+    if (K > 0xffffffffLL) return fail(h, MSL_ERR_UNSUPPORTED, "msl_camera_frames: more than 2^32 pixels per pattern");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    const size_t n = (size_t)B * (size_t)K;
+    int rc = h->dose_cnt.reserve(h, n + 1);                      // (sized as msl_dose_counts sizes it: the flag word behind the counts)
+    if (rc) return rc;
+    HIPCHK(h, hipMemcpyAsync(h->dose_cnt.p, counts_host, n * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+    if ((rc = begin_timed(h, 1))) return rc;
+    if ((rc = camera_launch(h, "msl_camera_frames", B, mx, my, seed, probe0))) return rc;
+    return download_sync(h, frames_out, h->cam_frames.p, n * sizeof(uint16_t));
+}
+
+int msl_dose_frames(msl_handle* h, int64_t B, double scale, uint64_t seed, int64_t probe0, uint16_t* frames_out, uint32_t* counts_out_or_null,
+                    double* intensity_out_or_null) {
+    if (!h || !frames_out) return fail(h, MSL_ERR_INVALID, "msl_dose_frames: null argument");
+    if (h->cam_radius < 0) return fail(h, MSL_ERR_STATE, "msl_dose_frames: no camera (call msl_set_camera)");
+    int rc = dose_draw(h, "msl_dose_frames", &B, scale, seed, probe0);
+    if (rc) return rc;
+    if ((rc = camera_launch(h, "msl_dose_frames", B, h->dose_mx, h->dose_my, seed, probe0))) return rc;
+    return dose_collect(h, "msl_dose_frames", B * h->dose_K, scale, counts_out_or_null, intensity_out_or_null, frames_out);
 }
 
 // ---- images through an objective lens (image.h) -----------------------------------------------------------

@@ -21,9 +21,11 @@ class Diffraction:
     split=True also asks for the elastic part |<Psi>|^2 of every pattern (DiffractionData.elastic / .tds), which costs one
     potential build per probe batch and frame instead of one per frame (MultisliceCalculator.run_diffraction).
     dose=dose.Dose(...) asks for Poisson-counted patterns at that dose, drawn on the device (DiffractionData.counts); it takes the
-    loop order of the split, at the same price, and is not built together with it."""
+    loop order of the split, at the same price, and is not built together with it.
+    camera=camera.Camera(...), with a dose, turns the counts into the uint16 frames a camera writes, on the device
+    (DiffractionData.frames)."""
 
-    def __init__(self, bin=(1, 1), split=False, dose=None):
+    def __init__(self, bin=(1, 1), split=False, dose=None, camera=None):
         try:
             ok = len(bin) == 2 and all(isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_)) and int(v) >= 1 for v in bin)
         except TypeError:
@@ -38,13 +40,21 @@ class Diffraction:
                 raise ValueError(f"Diffraction: dose must be a Dose object, got {dose!r}")
             if split:
                 raise NotImplementedError("dose: split=True is not built")
+        if camera is not None:
+            from .camera import Camera
+            if not isinstance(camera, Camera):
+                raise ValueError(f"Diffraction: camera must be a Camera object, got {camera!r}")
+            if dose is None:
+                raise ValueError("Diffraction: a camera records the counts of a dose: give dose=Dose(...) as well")
         self.bin = (int(bin[0]), int(bin[1]))
         self.split = bool(split)
         self.dose = dose
+        self.camera = camera
 
     def __repr__(self):
         return (f"Diffraction(bin={self.bin}" + (", split=True" if self.split else "")
-                + (f", dose={self.dose!r}" if self.dose is not None else "") + ")")
+                + (f", dose={self.dose!r}" if self.dose is not None else "")
+                + (f", camera={self.camera!r}" if self.camera is not None else "") + ")")
 
 
 def bin_centres(axis, b):
@@ -76,7 +86,11 @@ class DiffractionData:
     `electrons_per_probe` incident electrons per position (dose.py is the definition of the draw; `dose` the request, `incident` the
     spectrum-intensity sum of the incident probe, so that the expected count of a pixel is intensity * electrons_per_probe /
     incident); `intensity` is the noise-free mean only with Dose(keep_intensity=True), None otherwise.  pacbed / virtual / image /
-    pattern then work on the counts, in electrons as float64, and take part="counts" | "intensity" when both are there."""
+    pattern then work on the counts, in electrons as float64, and take part="counts" | "intensity" when both are there.
+    With Diffraction(dose=..., camera=Camera(...)) `frames` (P, mx, my) uint16 holds what the camera wrote (camera.py is the
+    definition; `camera` the request); `counts` is there only with Camera(keep_counts=True).  part="frames" reads the frames back in
+    electrons, (frames - offset) / gain as float64, and is the default when frames are all there is.  datacube() is the
+    (sx, sy, mx, my) array of a raster scan."""
     intensity: Optional[np.ndarray]
     kxs: Any
     kys: Any
@@ -97,12 +111,22 @@ class DiffractionData:
     dose: Any = None
     electrons_per_probe: Optional[float] = None
     incident: Optional[float] = None
+    frames: Optional[np.ndarray] = None
+    camera: Any = None
 
     def __post_init__(self):
         if self.patterns not in ("position", "pacbed"):
             raise ValueError(f"patterns must be 'position' or 'pacbed', got {self.patterns!r}")
-        if self.intensity is None and self.counts is None:
+        if self.intensity is None and self.counts is None and self.frames is None:
             raise ValueError("DiffractionData needs intensity or counts")
+        if self.frames is not None:
+            if self.layer is not None or self.patterns != "position" or np.ndim(self.frames) != 3:
+                raise ValueError("frames are per-position patterns (P, mx, my) without a thickness axis")
+            if self.camera is None:
+                raise ValueError("frames need the camera that wrote them")
+            for name, other in (("counts", self.counts), ("intensity", self.intensity)):
+                if other is not None and np.shape(other) != np.shape(self.frames):
+                    raise ValueError(f"frames have shape {np.shape(self.frames)}, {name} {np.shape(other)}")
         if self.counts is not None:
             if self.layer is not None or self.patterns != "position" or np.ndim(self.counts) != 3:
                 raise ValueError("counts are per-position patterns (P, mx, my) without a thickness axis")
@@ -130,12 +154,18 @@ class DiffractionData:
                        stem=None if self.stem is None else self.stem.at(j))
 
     def _data(self, part=None):
-        """the array the reductions read: part=None is the intensity as ever, and the counts (as float64 electrons) when there is
-        no intensity; "counts" / "intensity" name one"""
-        if part not in (None, "counts", "intensity"):
-            raise ValueError(f"part must be 'counts' or 'intensity', got {part!r}")
+        """the array the reductions read: part=None is the intensity as ever, the counts (as float64 electrons) when there is
+        no intensity, and the frames (read back in electrons) when they are all there is; "counts" / "intensity" / "frames" name one"""
+        if part not in (None, "counts", "intensity", "frames"):
+            raise ValueError(f"part must be 'counts' or 'intensity', got {part!r}" if self.frames is None else
+                             f"part must be 'counts', 'intensity' or 'frames', got {part!r}")
         if part is None:
-            part = "intensity" if self.intensity is not None else "counts"
+            part = "intensity" if self.intensity is not None else "counts" if self.counts is not None or self.frames is None else "frames"
+        if part == "frames":
+            if self.frames is None:
+                raise ValueError("this DiffractionData has no frames: run with Diffraction(dose=Dose(...), camera=Camera(...))")
+            from .camera import electrons
+            return electrons(self.frames, self.camera)
         arr = self.counts if part == "counts" else self.intensity
         if arr is None:
             raise ValueError("this DiffractionData has no counts: run with Diffraction(dose=Dose(...))" if part == "counts" else
@@ -201,3 +231,25 @@ class DiffractionData:
         self._per_position("pattern()")
         pp = np.asarray(self.probe_positions, dtype=np.float64).reshape(-1, 2)
         return self._data(part)[int(np.argmin(((pp - np.array([x, y])[None, :]) ** 2).sum(axis=1)))]
+
+    def datacube(self, part=None) -> np.ndarray:
+        """(len(xs), len(ys), mx, my): the patterns of a scan on a regular raster, ordered by scan position -- the 4D array that
+        4D-STEM packages load.  part=None: the array as it was recorded (frames uint16, else counts uint32, else the intensity);
+        "frames" / "counts" / "intensity" name one, as recorded too (no conversion to electrons).  ValueError unless every raster
+        point (xs[i], ys[j]) holds exactly one probe."""
+        self._per_position("datacube()")
+        if self.layer is not None:
+            raise ValueError("datacube(): take one thickness entry first (at(i))")
+        if part not in (None, "counts", "intensity", "frames"):
+            raise ValueError(f"part must be 'counts', 'intensity' or 'frames', got {part!r}")
+        if part is None:
+            part = "frames" if self.frames is not None else "counts" if self.counts is not None else "intensity"
+        arr = {"frames": self.frames, "counts": self.counts, "intensity": self.intensity}[part]
+        if arr is None:
+            raise ValueError(f"this DiffractionData has no {part}")
+        pp = np.asarray(self.probe_positions, dtype=np.float64).reshape(-1, 2)
+        sx, sy = len(self.xs), len(self.ys)
+        if sx * sy != len(pp) or len({(x, y) for x, y in pp}) != len(pp):
+            raise ValueError(f"datacube(): {len(pp)} probe positions are not a full {sx} x {sy} raster of their coordinates")
+        index = scan_image(np.arange(len(pp), dtype=np.float64), pp, self.xs, self.ys).astype(np.int64)
+        return arr[index.reshape(-1)].reshape((sx, sy) + arr.shape[1:])

@@ -33,8 +33,9 @@ Every product and sum rounds on its own (no fused multiply-add), on the host and
 The device may differ from this file only where its exp / log / lgamma differ from the host's in the last place AND that flips
 one of the comparisons above: about 1e-13 per pixel.
 
-Not built: detector MTF / DQE, readout noise, uint16 output, dose on the device for polar and STEM-detector signals (their arrays
-are small: poisson_signals below, on the host), dose under PRISM, thickness series and precession.
+The detector's response to these counts -- point spread, gain, offset, readout noise, uint16 frames -- is camera.py.
+Not built: dose on the device for polar and STEM-detector signals (their arrays are small: poisson_signals below, on the host), dose
+under PRISM, thickness series and precession.
 """
 from __future__ import annotations
 
