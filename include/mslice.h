@@ -208,6 +208,14 @@ int  msl_set_probes(msl_handle* h, double mrad, const double* xy, int32_t n_prob
  * the caller, ignore the aberrations. */
 int  msl_set_aberrations(msl_handle* h, const double* polar, int32_t n_terms);
 
+/* Member probes of a partially coherent scan (pyslice_amd/coherence.py): msl_set_probes with a defocus of its own for every probe,
+ *     psi0[p] = ifft2(mask * ramp_p * exp(-i chi_p(k))),   chi_p = the handle's chi with C10 + defocus[p]
+ * (defocus = n_probes doubles in Angstrom, in the sense of C10: +dz is the reference's Probe.defocus(dz)); every other term comes from
+ * msl_set_aberrations.  Same aperture rule, ramp and float64 polynomial of chi / (2 pi) in turns, reduced to one turn before the fp32
+ * sincos.  MSL_ERR_INVALID for mrad == 0 (plane waves have no defocus), a non-finite defocus and what msl_set_probes refuses.  With
+ * every defocus[p] == 0 the call IS msl_set_probes(h, mrad, xy, n_probes), bit for bit. */
+int  msl_set_probe_members(msl_handle* h, double mrad, const double* xy, const double* defocus, int32_t n_probes);
+
 /* Upload arbitrary initial waves (P,nx,ny) c64 (used when a caller hands Propagate() a
  * Probe built from its own array, multislice.py:104-109). */
 int  msl_upload_probes(msl_handle* h, const float* c64, int32_t n_probes);
@@ -575,6 +583,26 @@ int  msl_dose_reset(msl_handle* h, int64_t B, int32_t mx, int32_t my);
 int  msl_dose_add(msl_handle* h, const void* d_src_c64, int64_t B, int64_t T, int64_t K, int64_t ld, int32_t t0, int32_t count, int32_t wx, int32_t wy,
                   int32_t bx, int32_t by);
 int  msl_dose_counts(msl_handle* h, int64_t B, double scale, uint64_t seed, int64_t probe0, uint32_t* counts_out, double* intensity_out);
+
+/* ---- member ensembles: the patterns of the G member probes of every scan position folded on the device (partial coherence) ----
+ * The B waves of the source are Q = B / G positions of G members each, wave b = q*G + g; weights = G doubles on the HOST, each finite
+ * and >= 0 (the caller normalises them); they travel with the launch as kernel arguments and are not read after the call returns.
+ * msl_diffract_members: out[(q*mx + ix)*my + iy] = sum_{g<G} weights[g] * D[q*G + g, ix, iy], D being msl_diffract's result for that
+ *   wave with the same arguments: its loads, its fp32 partial sums of at most 8 addends, its bin modes and owner lanes; the product
+ *   and the sum over g are float64, each rounded on its own, in member order -- bit for bit the host's fold of msl_diffract's output,
+ *   and with G = 1, weights = {1} msl_diffract itself.  One launch, every complex value read once, no atomics.  out is HOST memory,
+ *   Q*mx*my float64.  MSL_ERR_INVALID for G outside [1, MSL_MEMBERS_MAX], B not a multiple of G, a negative or non-finite weight and
+ *   everything msl_diffract refuses.
+ * msl_dose_add_members: the same totals ADDED to the accumulator of msl_dose_reset, which was sized for (at least) Q positions, as
+ *   msl_dose_add adds msl_diffract's; msl_dose_counts / msl_dose_frames then run as they are, with B = Q and probe0 the index of the
+ *   first position in the scan: the draw is made from the averaged pattern.  Queued on the stream like msl_dose_add (no wait).
+ *   MSL_ERR_STATE before a reset; MSL_ERR_INVALID as above
+ *   and for what msl_dose_add refuses. */
+#define MSL_MEMBERS_MAX 128
+int  msl_diffract_members(msl_handle* h, const void* d_src_c64, int64_t B, int64_t T, int64_t K, int64_t ld, int32_t t0, int32_t count, int32_t wx,
+                          int32_t wy, int32_t bx, int32_t by, int32_t G, const double* weights, double* out);
+int  msl_dose_add_members(msl_handle* h, const void* d_src_c64, int64_t B, int64_t T, int64_t K, int64_t ld, int32_t t0, int32_t count, int32_t wx,
+                          int32_t wy, int32_t bx, int32_t by, int32_t G, const double* weights);
 
 /* ---- images through an objective lens (HRTEM, focal series): frame-accumulated |psi|^2 in the image plane, per probe batch ----
  * For probe b and the frames j of a call

@@ -52,8 +52,10 @@ EXPORTS = [
     "msl_set_tds", "msl_tds_fetch", "msl_tds_reduce",
     "msl_set_ionization", "msl_ionization_fetch", "msl_ionization_reduce",
     "msl_set_projection", "msl_get_projection",
+    "msl_set_probe_members", "msl_diffract_members", "msl_dose_add_members",
 ]
 DET_SIGNALS = {"intensity": 0, "amplitude": 1, "com_x": 2, "com_y": 3}      # include/mslice.h: MSL_DET_*
+MEMBERS_MAX = 128                                                          # include/mslice.h: MSL_MEMBERS_MAX
 POLAR_NONE, POLAR_MAX_BINS = 0xFFFF, 4096                                  # include/mslice.h: MSL_POLAR_*
 LR_DETECT, LR_POLAR, LR_DIFFRACT, LR_PACBED = 1, 2, 4, 8                   # include/mslice.h: MSL_LR_*
 LR_BYTES_BLOCK, LR_BYTES_TAP, LR_BYTES_STAGING = 0, 1, 2                   # include/mslice.h: MSL_LR_BYTES_*
@@ -104,6 +106,7 @@ def load():
         "msl_resize_probes": (C.c_int, [vp, i32]),
         "msl_set_probes": (C.c_int, [vp, dbl, vp, i32]),
         "msl_set_aberrations": (C.c_int, [vp, vp, i32]),
+        "msl_set_probe_members": (C.c_int, [vp, dbl, vp, vp, i32]),
         "msl_upload_probes": (C.c_int, [vp, vp, i32]),
         "msl_shift_probes": (C.c_int, [vp, vp, vp, i32]),
         "msl_build_potential": (C.c_int, [vp, vp, vp, i64, i32, i32, i32]),
@@ -152,6 +155,8 @@ def load():
         "msl_dose_reset": (C.c_int, [vp, i64, i32, i32]),
         "msl_dose_add": (C.c_int, [vp, vp, i64, i64, i64, i64, i32, i32, i32, i32, i32, i32]),
         "msl_dose_counts": (C.c_int, [vp, i64, dbl, C.c_uint64, i64, vp, vp]),
+        "msl_diffract_members": (C.c_int, [vp, vp, i64, i64, i64, i64, i32, i32, i32, i32, i32, i32, i32, vp, vp]),
+        "msl_dose_add_members": (C.c_int, [vp, vp, i64, i64, i64, i64, i32, i32, i32, i32, i32, i32, i32, vp]),
         "msl_set_camera": (C.c_int, [vp, i32, vp, dbl, dbl, dbl, i32]),
         "msl_camera_frames": (C.c_int, [vp, vp, i64, i32, i32, C.c_uint64, i64, vp]),
         "msl_dose_frames": (C.c_int, [vp, i64, dbl, C.c_uint64, i64, vp, vp, vp]),
@@ -422,6 +427,15 @@ class Engine:
     def set_probes(self, mrad, xy):
         xy = np.ascontiguousarray(xy, dtype=np.float64).reshape(-1, 2)
         self._chk(self._lib.msl_set_probes(self._h, float(mrad), _ptr(xy), xy.shape[0]))
+
+    def set_probe_members(self, mrad, xy, defocus):
+        """set_probes with a defocus (Angstrom, added to the handle's C10) of its own for every probe (msl_set_probe_members): the
+        member probes of a partially coherent scan.  All zero: set_probes, bit for bit"""
+        xy = np.ascontiguousarray(xy, dtype=np.float64).reshape(-1, 2)
+        df = np.ascontiguousarray(defocus, dtype=np.float64).reshape(-1)
+        if df.size != xy.shape[0]:
+            raise ValueError(f"set_probe_members: {df.size} defocus values for {xy.shape[0]} probes")
+        self._chk(self._lib.msl_set_probe_members(self._h, float(mrad), _ptr(xy), _ptr(df), xy.shape[0]))
 
     def set_aberrations(self, aberrations):
         """aberration function of every later set_probes (msl_set_aberrations): an aberrations.Aberrations, or None to clear.
@@ -920,6 +934,31 @@ class Engine:
         self._chk(self._lib.msl_dose_counts(self._h, b, float(scale), int(seed), int(probe0), _ptr(counts),
                                             None if acc is None else _ptr(acc)))
         return counts, acc
+
+    # -- member ensembles (msl_diffract_members / msl_dose_add_members; the definition is coherence.py)
+    def diffract_members(self, weights, t0=0, count=None, B=None, bin=(1, 1), src=None):
+        """(B / G, wx/bx, wy/by) float64: what diffract() returns for the same arguments with the G = len(weights) member waves of
+        every position folded on the device, sum_g weights[g] * pattern[q * G + g].  B counts WAVES (a multiple of G)"""
+        w = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
+        bx, by = int(bin[0]), int(bin[1])
+        wx, wy = (self.wx, self.wy) if src is None else (int(src[3]), int(src[4]))
+        p, b, T, k, ld, count = self._rows(None if src is None else (*src[:3], wx * wy, *src[5:]), B, self.n_frames, t0, count)
+        ok = (bx > 0 and by > 0 and wx > 0 and wy > 0 and wx % bx == 0 and wy % by == 0 and w.size > 0
+              and b > 0 and b % w.size == 0)                        # (else the library refuses: no output is read)
+        out = np.empty((b // w.size, wx // bx, wy // by) if ok else (1,), dtype=np.float64)
+        self._chk(self._lib.msl_diffract_members(self._h, p, b, T, k, ld, int(t0), count, wx, wy, bx, by, int(w.size),
+                                                 _ptr(w) if w.size else None, _ptr(out)))
+        return out
+
+    def dose_add_members(self, weights, t0=0, count=None, B=None, bin=(1, 1), src=None):
+        """accumulator += what diffract_members() returns for the same arguments, on the device; the accumulator was reset for
+        B / G positions"""
+        w = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
+        bx, by = int(bin[0]), int(bin[1])
+        wx, wy = (self.wx, self.wy) if src is None else (int(src[3]), int(src[4]))
+        p, b, T, k, ld, count = self._rows(None if src is None else (*src[:3], wx * wy, *src[5:]), B, self.n_frames, t0, count)
+        self._chk(self._lib.msl_dose_add_members(self._h, p, b, T, k, ld, int(t0), count, wx, wy, bx, by, int(w.size),
+                                                 _ptr(w) if w.size else None))
 
     # -- detector response (msl_set_camera / msl_camera_frames / msl_dose_frames)
     def set_camera(self, camera):

@@ -135,7 +135,7 @@ class MultisliceCalculator:
                  gather="rank0", cache=False, k_window=None, frame_batch=None, k_bin=None, stream_tile=None, layers=None,
                  detectors=None, probe_batch=None, diffraction=None, aberrations=None, imaging=None, prism=None,
                  spectroscopy=None, polar=None, thickness=None, tilt=None, precession=None, tds=False, bandlimit=None,
-                 projection=None, ionization=None):
+                 projection=None, ionization=None, coherence=None):
         """
         device / force_cpu: as the reference (calculators.py:41).  There is no CPU path here, so
         force_cpu=True raises.  Keyword-only extras (not in the reference):
@@ -276,6 +276,21 @@ class MultisliceCalculator:
                    AbsorptivePotential, aberrations, tilt, bandlimit and probe_batch.  Not built (NotImplementedError): tds, prism,
                    precession, projection, detectors, polar, diffraction, imaging, spectroscopy, layers, thickness, k_window,
                    k_bin, cache, stream_tile, frame_batch > 1, several ranks.  None: every run is what it is without the argument.
+          coherence a coherence.Coherence(focal_spread, focal_points, source_size, source_points): partial coherence of the probe.
+                   Every scan position of run_diffraction() (plain, with Dose, with Dose + Camera), run_detectors() and run_polar()
+                   is an ensemble of G = focal_points x source_points^2 member probes, member g at xy + d_g with C10 + delta_g and
+                   weight w_g (coherence_members, after setup()), and every result is the weighted sum of the members' INTENSITIES.
+                   The members go through the slice loop as ordinary probes of the batch (wave q G + g; msl_set_probe_members);
+                   msl_diffract_members / msl_dose_add_members fold the G patterns of a position on the device -- the Poisson draw
+                   of a dose run is made from the averaged pattern --, the detector and polar signals are folded on the host in
+                   float64, in member order.  The results keep their shapes and carry .coherence.  The cost: G slice loops per
+                   position (the potentials are built as often as without); for a source size alone, on a regular raster, without
+                   a dose, STEMData.source_blurred(sigma) / coherence.blur_scan is the cheap route.  probe_batch then counts waves:
+                   it is rounded down to a multiple of G (ValueError below G), as is the automatic one.  Needs aperture > 0.  With
+                   Trajectory, FrozenPhonons, PhononModes, AbsorptivePotential, aberrations, tilt, bandlimit, projection, k_window,
+                   probe_batch and frame_batch.  Not built (NotImplementedError): Diffraction(split=True), thickness, layers, prism,
+                   precession, tds, ionization, spectroscopy, imaging, run(), run_streaming_tacaw(), cache, stream_tile, several
+                   ranks.  Coherence() is off: every run is bit for bit the one without the argument.
         """
         if force_cpu:
             raise NotImplementedError("pyslice_amd has no CPU path (force_cpu=True): use the reference for CPU runs")
@@ -300,6 +315,25 @@ class MultisliceCalculator:
                               ("frame_batch > 1", frame_batch is not None and int(frame_batch) > 1)):
                 if val:
                     raise NotImplementedError(f"ionization: {what} is not built")
+        self._coherence = None                  # a Coherence with more than one member; None: the coherent probe of today
+        self.coherence_members = None           # (offsets (G, 2), defocus (G,), weights (G,)) of the members; None when off
+        if coherence is not None:
+            from .coherence import Coherence
+            if not isinstance(coherence, Coherence):
+                raise ValueError(f"coherence: expected a Coherence object, got {coherence!r}")
+            if not coherence.is_off:
+                # the members are waves of the probe batch, folded by the reductions of the exit patterns: the modes that reduce
+                # elsewhere, hold every wave, synthesise their probes or average over several scans are not fed from that fold
+                for what, val in (("Diffraction(split=True)", getattr(diffraction, "split", False)), ("thickness", thickness is not None),
+                                  ("layers", layers is not None), ("prism", prism is not None), ("precession", precession is not None),
+                                  ("tds", bool(tds)), ("ionization", ionization is not None), ("spectroscopy", spectroscopy is not None),
+                                  ("imaging", imaging is not None), ("cache", bool(cache)), ("stream_tile", stream_tile is not None),
+                                  ("run() / run_streaming_tacaw() (give detectors=[...], polar=PolarDetector(...) or "
+                                   "diffraction=Diffraction(...))", detectors is None and diffraction is None and polar is None)):
+                    if val:
+                        raise NotImplementedError(f"coherence: {what} is not built")
+                self._coherence = coherence
+                self.coherence_members = coherence.members()
         self._dose = getattr(diffraction, "dose", None)
         self._camera = getattr(diffraction, "camera", None)     # (only with a dose: Diffraction refuses it otherwise, so it inherits the refusals below)
         self.electrons_per_probe = None         # setup(): the electrons per probe position of a dose run
@@ -545,6 +579,12 @@ class MultisliceCalculator:
                 raise NotImplementedError("tds: a run over several ranks is not built")
         if getattr(self, "_ionization", None) is not None and distributed.rank_world()[1] > 1:
             raise NotImplementedError("ionization: a run over several ranks is not built")
+        if getattr(self, "_coherence", None) is not None:
+            if distributed.rank_world()[1] > 1:
+                raise NotImplementedError("coherence: a run over several ranks is not built")
+            if not aperture > 0:
+                raise ValueError("coherence needs a convergent probe: setup(aperture > 0) (a plane wave has neither a defocus nor a "
+                                 "position)")
         self.trajectory = trajectory
         self.aperture = aperture
         self.voltage_eV = voltage_eV
@@ -689,19 +729,23 @@ class MultisliceCalculator:
         # Pc x frame batch near the ~256 images per launch of default_frame_batch: 256 probes x 1 frame for a scan, all probes x
         # ceil(256 / P) frames for a few (an explicit probe_batch is honoured as is)
         auto = self._probe_batch is None
-        Pc = min(self.n_probes, 256 if auto else self._probe_batch)
+        # with a Coherence the engine's probes are WAVES, G members per position: whole positions per batch
+        G = self._members_G()
+        if not auto and self._probe_batch < G:
+            raise ValueError(f"coherence: probe_batch={self._probe_batch} is below the G = {G} member probes of one position")
+        Pc = min(self.n_probes * G, 256 if auto else self._probe_batch) // G * G
         batch = self._frame_batch if self._frame_batch is not None else default_frame_batch(Pc, n_slices, self.nx, self.ny)
         # (the S-matrix holds one frame; so does the weight stack of the ionisation channels)
         batch = 1 if (self._prism is not None or self._ionization is not None) else max(1, min(batch, self.n_frames))
         free_b = _free_device_bytes(self.device) if auto else None
         if free_b is not None:
-            Pc = self._fit_probe_batch(free_b, Pc, batch)
+            Pc = max(G, self._fit_probe_batch(free_b, Pc, batch) // G * G)
 
         def shrink(Pc, slots, batch):                           # the probe batch first, then the frame batch and with it the ring
-            if not auto or (Pc <= 1 and batch <= 1):
+            if not auto or (Pc <= G and batch <= 1):
                 return None
-            if Pc > 1:
-                Pc = max(1, Pc // 2)
+            if Pc > G:
+                Pc = max(G, Pc // 2 // G * G)
             else:
                 batch = max(1, batch // 2)
             logger.info(f"device memory: probe batch {Pc}, frame batch {batch}")
@@ -990,17 +1034,48 @@ class MultisliceCalculator:
         B = self._engine.frame_batch
         return [(s0, min(B, self.n_frames - s0)) for s0 in range(0, self.n_frames, B)]
 
+    def _members_G(self):
+        """waves per scan position: the members of the Coherence, 1 without"""
+        return 1 if getattr(self, "_coherence", None) is None else len(self.coherence_members[2])
+
     def _probe_batches(self):
         """(p0, real, xy) per probe batch: probes p0 .. p0+real-1, and their positions padded to the engine's probe count by
-        repeating the last one"""
-        Pc = self._engine.n_probes
+        repeating the last one.  With a Coherence the engine's probes are waves, G per position: p0 and real count POSITIONS, a
+        batch holds n_probes / G of them, and xy holds the G member positions of each, xy[q G + g] = position q + offset g"""
+        G = self._members_G()
+        Pc = self._engine.n_probes // G
         pos = np.asarray(self.probe_positions, dtype=np.float64).reshape(-1, 2)
         for p0 in range(0, self.n_probes, Pc):
             xy = pos[p0:p0 + Pc]
             real = len(xy)
             if real < Pc:
                 xy = np.concatenate([xy, np.repeat(xy[-1:], Pc - real, axis=0)])
+            if G > 1:
+                xy = (xy[:, None, :] + self.coherence_members[0][None, :, :]).reshape(-1, 2)
             yield p0, real, xy
+
+    def _set_probes(self, xy):
+        """the probes of one batch of _probe_batches onto the engine: set_probes, or with a Coherence set_probe_members with the
+        defocus offsets of the members repeated for every position of the batch"""
+        if getattr(self, "_coherence", None) is None:
+            self._engine.set_probes(self.aperture, xy)
+        else:
+            self._engine.set_probe_members(self.aperture, xy, np.tile(self.coherence_members[1], len(xy) // self._members_G()))
+
+    def _detect(self, n, real):
+        """(real, n, D): msl_detect of the n frames that just ran for the first `real` positions; with a Coherence the signals of
+        the real x G waves, folded on the host in float64 in member order"""
+        if getattr(self, "_coherence", None) is None:
+            return self._engine.detect(0, n, B=real)
+        from .coherence import fold_members
+        return fold_members(self._engine.detect(0, n, B=real * self._members_G()), self.coherence_members[2])
+
+    def _polar_detect(self, n, real):
+        """(real, n, n_bins): msl_polar_detect likewise"""
+        if getattr(self, "_coherence", None) is None:
+            return self._engine.polar_detect(0, n, B=real)
+        from .coherence import fold_members
+        return fold_members(self._engine.polar_detect(0, n, B=real * self._members_G()), self.coherence_members[2])
 
     def _probe_batch_loop(self, reduce_batch):
         """The pass of run_detectors() / run_diffraction(): frame batches outside (the potentials of a batch are built once), probe
@@ -1010,7 +1085,7 @@ class MultisliceCalculator:
         for s0, n in self._frame_batches():
             self._build_and_propagate(s0, n, 0, propagate=False)
             for p0, real, xy in self._probe_batches():
-                self._engine.set_probes(self.aperture, xy)
+                self._set_probes(xy)
                 self._build_and_propagate(s0, n, 0, build=False)
                 reduce_batch(p0, real, s0, n)
             bar.update(n)
@@ -1063,12 +1138,12 @@ class MultisliceCalculator:
         batch s0 goes to result slots s0 .. s0+n-1 instead of 0 .. n-1, so that all T frames of the probe batch are in the ring when
         finish_batch runs."""
         eng, batches = self._engine, self._frame_batches()
-        bar = _Progress(self._progress, -(-self.n_probes // eng.n_probes) * self.n_frames)
+        bar = _Progress(self._progress, -(-self.n_probes // (eng.n_probes // self._members_G())) * self.n_frames)
         once = self.n_frames <= eng.frame_batch
         if once:
             self._build_and_propagate(0, self.n_frames, 0, propagate=False)
         for p0, real, xy in self._probe_batches():
-            eng.set_probes(self.aperture, xy)
+            self._set_probes(xy)
             if coherent:
                 eng.coherent_reset()
             for s0, n in batches:
@@ -1085,7 +1160,8 @@ class MultisliceCalculator:
         kxs, kys = self._k_axes()
         return self._tag_crop(STEMData(signals=signals, detectors=list(self._detectors), probe_positions=self.probe_positions,
                                        time=np.arange(self.n_frames) * self.trajectory.timestep, kxs=_as_tensor(kxs), kys=_as_tensor(kys),
-                                       probe=self.base_probe, tds_per_slice=tds_per_slice, **self._layer_fields()))
+                                       probe=self.base_probe, tds_per_slice=tds_per_slice, coherence=getattr(self, "_coherence", None),
+                                       **self._layer_fields()))
 
     def _tag_crop(self, result):
         """a result of a Prism(f, crop=True) run carries .prism_crop = (fx, fy): its pixels are the uncropped run's at
@@ -1206,6 +1282,7 @@ class MultisliceCalculator:
         bx, by = self._diffraction.bin
         pacbed = self._thickness is not None and self._thickness_arg.patterns == "pacbed"
         dose = self._dose
+        members = None if getattr(self, "_coherence", None) is None else self.coherence_members
         mx, my = eng.wx // bx, eng.wy // by
         keep = dose is None or dose.keep_intensity
         acc = self._layered(((mx, my) if pacbed else (P, mx, my)) if keep else (0,))
@@ -1226,18 +1303,24 @@ class MultisliceCalculator:
             if dose is not None:                                # the frame sums stay on the device until finish_batch
                 if s0 == 0:
                     eng.dose_reset(real, (mx, my))
-                eng.dose_add(0, n, B=real, bin=(bx, by))
+                if members is None:
+                    eng.dose_add(0, n, B=real, bin=(bx, by))
+                else:                                           # (the G member patterns of a position, folded into its one row)
+                    eng.dose_add_members(members[2], 0, n, B=real * len(members[2]), bin=(bx, by))
                 if signals is not None:
-                    signals[p0:p0 + real, s0:s0 + n] = eng.detect(0, n, B=real)
+                    signals[p0:p0 + real, s0:s0 + n] = self._detect(n, real)
                 return
             if self._thickness is not None:
                 det = (self._pacbed_batch if pacbed else self._position_batch)(acc, p0, real, n, signals is not None)
                 if signals is not None:
                     signals[p0:p0 + real, s0:s0 + n] = np.moveaxis(det, 0, -1)
                 return
-            acc[p0:p0 + real] += eng.diffract(0, n, B=real, bin=(bx, by))
+            if members is None:
+                acc[p0:p0 + real] += eng.diffract(0, n, B=real, bin=(bx, by))
+            else:
+                acc[p0:p0 + real] += eng.diffract_members(members[2], 0, n, B=real * len(members[2]), bin=(bx, by))
             if signals is not None:
-                signals[p0:p0 + real, s0:s0 + n] = eng.detect(0, n, B=real)
+                signals[p0:p0 + real, s0:s0 + n] = self._detect(n, real)
         elastic = None
         if self._diffraction.split:
             elastic = np.zeros_like(acc)
@@ -1271,7 +1354,8 @@ class MultisliceCalculator:
                                               stem=None if signals is None else self._stem_data(signals), elastic=elastic,
                                               patterns="pacbed" if pacbed else "position", counts=counts, dose=dose,
                                               electrons_per_probe=self.electrons_per_probe if dose is not None else None,
-                                              incident=incident, frames=frames, camera=camera, **self._layer_fields()))
+                                              incident=incident, frames=frames, camera=camera, coherence=getattr(self, "_coherence", None),
+                                              **self._layer_fields()))
 
     def run_images(self):
         """Frame-averaged images behind the objective lens (HRTEM, focal series), for every probe: probe batches outside, frame
@@ -1389,7 +1473,7 @@ class MultisliceCalculator:
             if self._thickness is not None:
                 signals[p0:p0 + real, s0:s0 + n] = np.moveaxis(self._layer_signals(real, n)[0], 0, -1)
                 return
-            signals[p0:p0 + real, s0:s0 + n] = eng.detect(0, n, B=real)
+            signals[p0:p0 + real, s0:s0 + n] = self._detect(n, real)
         if self._prism is not None:
             self._prism_loop(reduce_batch)
         else:
@@ -1456,13 +1540,13 @@ class MultisliceCalculator:
                 if signals is not None:
                     signals[p0:p0 + real, s0:s0 + n] = np.moveaxis(det, 0, -1)
                 return
-            got = eng.polar_detect(0, n, B=real)
+            got = self._polar_detect(n, real)
             if pol.per_frame:
                 acc[p0:p0 + real, s0:s0 + n] = got
             else:
                 acc[p0:p0 + real] += got.sum(axis=1)
             if signals is not None:
-                signals[p0:p0 + real, s0:s0 + n] = eng.detect(0, n, B=real)
+                signals[p0:p0 + real, s0:s0 + n] = self._detect(n, real)
         if self._prism is not None:
             self._prism_loop(reduce_batch)
         else:
@@ -1479,7 +1563,8 @@ class MultisliceCalculator:
         return self._tag_crop(PolarData(signals=acc, polar=pol, counts=self._polar_counts.reshape(R, A), edges=pol.edges,
                                         probe_positions=self.probe_positions, time=np.arange(T) * self.trajectory.timestep,
                                         kxs=_as_tensor(kxs), kys=_as_tensor(kys), probe=self.base_probe,
-                                        stem=None if signals is None else self._stem_data(signals), **self._layer_fields()))
+                                        stem=None if signals is None else self._stem_data(signals), coherence=getattr(self, "_coherence", None),
+                                        **self._layer_fields()))
 
     def _check_layers(self, n_slices, world):
         """the `layers` argument -> sorted unique slice indices with n_slices - 1 last (before any device work)"""
@@ -1510,6 +1595,9 @@ class MultisliceCalculator:
 
     def run(self) -> WFData:
         """reference calculators.py:163-250: all frames, then pack WFData."""
+        if getattr(self, "_coherence", None) is not None:
+            raise NotImplementedError("coherence: run() is not built (a partially coherent probe has no single exit wave): call "
+                                      "run_detectors(), run_polar() or run_diffraction()")
         if self._detectors is not None:
             raise RuntimeError("detectors are set: the device holds one probe batch at a time -- call run_detectors()")
         if self._diffraction is not None:
@@ -1613,6 +1701,8 @@ class MultisliceCalculator:
         for the reductions), plus `total_diffraction` (P,wx,wy): the sum over ALL T bins (Parseval), i.e. what
         TACAWData.diffraction() of the full transform returns, without the transform being stored."""
         from .tacaw_data import TACAWData
+        if getattr(self, "_coherence", None) is not None:
+            raise NotImplementedError("coherence: run_streaming_tacaw() is not built")
         if self._engine is None:
             raise RuntimeError("call setup() before run_streaming_tacaw()")
         if self._stream_tile is None:

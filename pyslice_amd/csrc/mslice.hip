@@ -35,6 +35,7 @@
 #include "polar.h"
 #include "spectrum_detect.h"
 #include "diffract.h"
+#include "ensemble.h"
 #include "coherent.h"
 #include "dose.h"
 #include "camera.h"
@@ -241,6 +242,8 @@ struct msl_handle {
     DevBuf<uint32_t> dose_cnt;
     int64_t dose_B = 0, dose_K = 0;
     int dose_mx = 0, dose_my = 0;
+    // member probes (ensemble.h): the C10 coefficient of every probe of msl_set_probe_members, grown on demand
+    DevBuf<double> mem_a0;
     // detector response (msl_set_camera; camera.h): the weights padded to the radius class, the scalars of the response, and the uint16
     // staging of the frames, grown on demand; cam_radius < 0: no camera
     DevBuf<double> cam_psf;
@@ -3171,6 +3174,48 @@ int msl_set_probes(msl_handle* h, double mrad, const double* xy, int32_t n_probe
     return MSL_OK;
 }
 
+int msl_set_probe_members(msl_handle* h, double mrad, const double* xy, const double* defocus, int32_t n_probes) {
+    if (!h || !xy || !defocus) return fail(h, MSL_ERR_INVALID, "msl_set_probe_members: null argument");
+    if (n_probes != h->cfg.n_probes) return fail(h, MSL_ERR_INVALID, "msl_set_probe_members: %d probes, handle has %d", n_probes, h->cfg.n_probes);
+    if (mrad < 0) return fail(h, MSL_ERR_INVALID, "msl_set_probe_members: negative aperture");
+    if (mrad == 0) return fail(h, MSL_ERR_INVALID, "msl_set_probe_members: plane waves (mrad == 0) have no defocus");
+    bool any = false;
+    for (int p = 0; p < n_probes; ++p) {
+        if (!std::isfinite(defocus[p])) return fail(h, MSL_ERR_INVALID, "msl_set_probe_members: defocus %d is not finite", p);
+        if (defocus[p] != 0) any = true;
+    }
+    if (!any) return msl_set_probes(h, mrad, xy, n_probes);     // every member at the handle's own C10: that call, bit for bit
+    const msl_config& c = h->cfg;
+    HIPCHK(h, hipSetDevice(c.device));
+    int rc = h->mem_a0.reserve(h, (size_t)n_probes);
+    if (rc) return rc;
+    // (a, b) = C (cos, sin)(m phi) / ((n + 1) lambda) as msl_set_probes; the C10 term of probe p is (C10 + defocus[p]) / (2 lambda)
+    static const int term_n[14] = {1, 1, 2, 2, 3, 3, 3, 4, 4, 4, 5, 5, 5, 5}, term_m[14] = {0, 2, 1, 3, 0, 2, 4, 1, 3, 5, 0, 2, 4, 6};
+    ProbeAberrations ab;
+    for (int k = 0; k < 14; ++k) {
+        const double w = h->aberr_polar[k][0] / ((term_n[k] + 1) * c.wavelength);
+        ab.a[k] = term_m[k] ? w * cos(term_m[k] * h->aberr_polar[k][1]) : w;
+        ab.b[k] = term_m[k] ? w * sin(term_m[k] * h->aberr_polar[k][1]) : 0.0;
+    }
+    std::vector<double> a0((size_t)n_probes);
+    for (int p = 0; p < n_probes; ++p) a0[p] = (h->aberr_polar[0][0] + defocus[p]) / (2 * c.wavelength);
+    HIPCHK(h, hipMemcpyAsync(h->d_xy, xy, 2 * sizeof(double) * n_probes, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->mem_a0.p, a0.data(), sizeof(double) * n_probes, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));                 // (a0 is this call's own: copied before it goes)
+    const long long total = (long long)c.nx * c.ny * n_probes;
+    const double lx = c.nx * c.dx, ly = c.ny * c.dy;
+    hipLaunchKernelGGL(probe_kspace_member_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, h->psi0, h->d_xy,
+                       (const double*)h->mem_a0.p, n_probes, c.nx, c.ny, h->pitch, 1.0 / lx, 1.0 / ly, 1.0 / (c.nx * c.dx), 1.0 / (c.ny * c.dy),
+                       (mrad * 1e-3) / c.wavelength, c.wavelength, ab);
+    HIPCHK(h, hipGetLastError());
+    rc = fft2_inplace(h, h->psi0, n_probes, -1, 1.0f / ((float)c.nx * (float)c.ny), h->pitch);
+    if (rc) return rc;
+    if ((rc = transpose_probes(h))) return rc;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    h->have_probes = true;
+    return MSL_OK;
+}
+
 int msl_upload_probes(msl_handle* h, const float* c64, int32_t n_probes) {
     if (!h || !c64) return fail(h, MSL_ERR_INVALID, "msl_upload_probes: null argument");
     if (n_probes != h->cfg.n_probes) return fail(h, MSL_ERR_INVALID, "msl_upload_probes: %d probes, handle has %d", n_probes, h->cfg.n_probes);
@@ -4319,37 +4364,58 @@ int msl_spectrum_detect(msl_handle* h, const void* d_src_f32, int64_t B, int64_t
 // the pattern pass of msl_diffract over resolved rows, queued as one timed launch: the (B, mx, my) float64 result goes to d_dst, or
 // with d_dst == NULL to h->diff_out; *d_res / *res_bytes name it.  d_acc (msl_dose_add) takes the place of both: the result is added
 // to the (B, mx, my) float64 array there
-static int diffract_launch(msl_handle* h, const Rows& r, int32_t t0, int32_t count, int32_t wx, int32_t wy, int32_t bx, int32_t by, double* d_dst,
-                           double** d_res, size_t* res_bytes, const char* who = "msl_diffract", double* d_acc = nullptr) {
+// What the pattern pass of msl_diffract and of msl_diffract_members share, checked and computed in one place: the window, the bin
+// and the frame slots against the rows, then the bin mode, the load width and the launch shape for `waves_per_strip` waves of the source
+// per strip (1: a strip is a row of bins of one probe; G: of one position, ensemble.h) and `lds_totals` more doubles of LDS per bin of a
+// strip in the LDS mode.
+struct DiffractPlan {
+    int mx, my, mode;
+    bool vec;
+    int64_t strips, per;
+    size_t lds, n_out;
+    unsigned threads, grid;
+};
+
+static int plan_diffract(msl_handle* h, const char* who, const Rows& r, int32_t t0, int32_t count, int32_t wx, int32_t wy, int32_t bx, int32_t by,
+                         int waves_per_strip, int lds_totals, DiffractPlan* p) {
     int rc;
     if ((rc = check_window_bin(h, who, wx, wy, bx, by))) return rc;
     if ((int64_t)wx * wy != r.K) return fail(h, MSL_ERR_INVALID, "%s: window %d x %d over rows of %lld pixels", who, wx, wy, (long long)r.K);
     if ((rc = check_slots(h, who, "frame slots", t0, count, r.R))) return rc;
-    const int mx = wx / bx, my = wy / by;
-    const int64_t strips = r.B * mx;                             // one row of bins of one probe
+    p->mx = wx / bx; p->my = wy / by;
+    p->strips = r.B / waves_per_strip * p->mx;
     if ((int64_t)count * bx > 0x3fffffffLL) return fail(h, MSL_ERR_UNSUPPORTED, "%s: more than 2^30 rows per bin", who);
     const bool pow2 = (by & (by - 1)) == 0;
-    const int mode = by == 1 ? DIFF_DIRECT : (pow2 && by <= 64 ? DIFF_SHFL : DIFF_LDS);
-    const size_t lds = mode == DIFF_LDS ? (size_t)wy * sizeof(double) : 0;
-    if (lds > 64u * 1024u) return fail(h, MSL_ERR_UNSUPPORTED, "%s: bin %d of rows of %d pixels needs %zu bytes of LDS", who, by, wy, lds);
+    p->mode = by == 1 ? DIFF_DIRECT : (pow2 && by <= 64 ? DIFF_SHFL : DIFF_LDS);
+    p->lds = p->mode == DIFF_LDS ? ((size_t)wy + (size_t)lds_totals * p->my) * sizeof(double) : 0;
+    if (p->lds > 64u * 1024u) return fail(h, MSL_ERR_UNSUPPORTED, "%s: bin %d of rows of %d pixels needs %zu bytes of LDS", who, by, wy, p->lds);
+    p->n_out = (size_t)p->strips * p->my;
+    // 16-byte loads need every row to start on 16 bytes: base, image pitch and row length even in pixels
+    p->vec = (r.ld % 2 == 0) && (wy % 2 == 0) && (((uintptr_t)r.p & 15) == 0);
+    const int cols = p->vec ? (wy + 1) / 2 : wy;
+    p->threads = (unsigned)std::min(256, std::max(64, (cols + 63) / 64 * 64));
+    // strips per workgroup: about 64 KB of reads each, but at least 4096 workgroups while there are that many strips
+    const int64_t strip_bytes = (int64_t)waves_per_strip * count * bx * wy * 8;
+    int64_t per = std::max<int64_t>(1, 65536 / strip_bytes);
+    per = std::max<int64_t>(1, std::min<int64_t>(per, p->strips / 4096));
+    p->per = std::max<int64_t>(per, (p->strips + 0x7ffffffeLL) / 0x7fffffffLL);
+    p->grid = (unsigned)((p->strips + p->per - 1) / p->per);
+    return MSL_OK;
+}
+
+static int diffract_launch(msl_handle* h, const Rows& r, int32_t t0, int32_t count, int32_t wx, int32_t wy, int32_t bx, int32_t by, double* d_dst,
+                           double** d_res, size_t* res_bytes, const char* who = "msl_diffract", double* d_acc = nullptr) {
+    int rc;
+    DiffractPlan pl;
+    if ((rc = plan_diffract(h, who, r, t0, count, wx, wy, bx, by, 1, 0, &pl))) return rc;
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    const size_t n_out = (size_t)strips * my;
+    const size_t n_out = pl.n_out;
     if (!d_acc && !d_dst && (rc = h->diff_out.reserve(h, n_out))) return rc;
     double* d_out = d_acc ? d_acc : (d_dst ? d_dst : h->diff_out.p);
-    // 16-byte loads need every row to start on 16 bytes: base, image pitch and row length even in pixels
-    const bool vec = (r.ld % 2 == 0) && (wy % 2 == 0) && (((uintptr_t)r.p & 15) == 0);
-    const int cols = vec ? (wy + 1) / 2 : wy;
-    const unsigned threads = (unsigned)std::min(256, std::max(64, (cols + 63) / 64 * 64));
-    // strips per workgroup: about 64 KB of reads each, but at least 4096 workgroups while there are that many strips
-    const int64_t strip_bytes = (int64_t)count * bx * wy * 8;
-    int64_t per = std::max<int64_t>(1, 65536 / strip_bytes);
-    per = std::max<int64_t>(1, std::min<int64_t>(per, strips / 4096));
-    per = std::max<int64_t>(per, (strips + 0x7ffffffeLL) / 0x7fffffffLL);
-    const unsigned grid = (unsigned)((strips + per - 1) / per);
-    with_int<DIFF_DIRECT, DIFF_SHFL, DIFF_LDS>(mode, [&](auto m) { with_bool(vec, [&](auto v) { with_bool(d_acc != nullptr, [&](auto acc) {
-        hipLaunchKernelGGL((diffract_kernel<decltype(m)::value, decltype(v)::value, decltype(acc)::value>), dim3(grid), dim3(threads), lds, h->stream,
-                           (const float2*)r.p, (long long)r.R, (long long)t0, (int)count, (long long)r.ld, (int)wx, (int)wy, (int)bx, (int)by,
-                           (long long)strips, (int)per, d_out);
+    with_int<DIFF_DIRECT, DIFF_SHFL, DIFF_LDS>(pl.mode, [&](auto m) { with_bool(pl.vec, [&](auto v) { with_bool(d_acc != nullptr, [&](auto acc) {
+        hipLaunchKernelGGL((diffract_kernel<decltype(m)::value, decltype(v)::value, decltype(acc)::value>), dim3(pl.grid), dim3(pl.threads), pl.lds,
+                           h->stream, (const float2*)r.p, (long long)r.R, (long long)t0, (int)count, (long long)r.ld, (int)wx, (int)wy, (int)bx, (int)by,
+                           (long long)pl.strips, (int)pl.per, d_out);
     }); }); });
     HIPCHK(h, hipGetLastError());
     if ((rc = mark_launch(h, K_OTHER))) return rc;
@@ -4476,6 +4542,80 @@ int msl_dose_add(msl_handle* h, const void* d_src_c64, int64_t B, int64_t T, int
     size_t out_bytes = 0;
     if ((rc = begin_timed(h, 1))) return rc;
     return diffract_launch(h, r, t0, count, wx, wy, bx, by, nullptr, &d_out, &out_bytes, "msl_dose_add", h->dose_acc.p);
+}
+
+// ---- member ensembles (ensemble.h) ------------------------------------------------------------------------
+// the pattern pass of msl_diffract_members over resolved rows of Q * G waves, queued as one timed launch: the (Q, mx, my) float64
+// totals go to h->diff_out, or are added to d_acc (msl_dose_add_members); *d_res / *res_bytes name the result
+static int members_launch(msl_handle* h, const char* who, const Rows& r, int32_t t0, int32_t count, int32_t wx, int32_t wy, int32_t bx, int32_t by,
+                          int32_t G, const double* weights, double* d_acc, double** d_res, size_t* res_bytes) {
+    int rc;
+    DiffractPlan pl;                                             // (strips of G waves; the LDS mode keeps the my totals of a strip there too)
+    if ((rc = plan_diffract(h, who, r, t0, count, wx, wy, bx, by, G, 1, &pl))) return rc;
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    if (!d_acc && (rc = h->diff_out.reserve(h, pl.n_out))) return rc;
+    double* d_out = d_acc ? d_acc : h->diff_out.p;
+    MemberWeights mw;                                            // by value: the caller's array is not read after this function
+    for (int g = 0; g < MEMBERS_MAX; ++g) mw.w[g] = g < G ? weights[g] : 0.0;
+    with_int<DIFF_DIRECT, DIFF_SHFL, DIFF_LDS>(pl.mode, [&](auto m) { with_bool(pl.vec, [&](auto v) { with_bool(d_acc != nullptr, [&](auto acc) {
+        hipLaunchKernelGGL((diffract_members_kernel<decltype(m)::value, decltype(v)::value, decltype(acc)::value>), dim3(pl.grid), dim3(pl.threads),
+                           pl.lds, h->stream, (const float2*)r.p, (long long)r.R, (long long)t0, (int)count, (long long)r.ld, (int)wx, (int)wy, (int)bx,
+                           (int)by, (int)G, mw, (long long)pl.strips, (int)pl.per, d_out);
+    }); }); });
+    HIPCHK(h, hipGetLastError());
+    if ((rc = mark_launch(h, K_OTHER))) return rc;
+    h->ctr.algorithmic_bytes += 8ull * (uint64_t)r.K * (uint64_t)r.B * (uint64_t)count;
+    *d_res = d_out; *res_bytes = pl.n_out * sizeof(double);
+    return MSL_OK;
+}
+
+// what both member calls check before the source is resolved, and after: G, the weights, whole positions
+static int check_members(msl_handle* h, const char* who, int32_t G, const double* weights) {
+    if (!weights) return fail(h, MSL_ERR_INVALID, "%s: null argument", who);
+    if (G < 1 || G > MSL_MEMBERS_MAX) return fail(h, MSL_ERR_INVALID, "%s: %d members outside [1, %d]", who, G, MSL_MEMBERS_MAX);
+    for (int g = 0; g < G; ++g)
+        if (!std::isfinite(weights[g]) || weights[g] < 0) return fail(h, MSL_ERR_INVALID, "%s: weight %d is negative or not finite", who, g);
+    return MSL_OK;
+}
+
+int msl_diffract_members(msl_handle* h, const void* d_src_c64, int64_t B, int64_t T, int64_t K, int64_t ld, int32_t t0, int32_t count, int32_t wx,
+                         int32_t wy, int32_t bx, int32_t by, int32_t G, const double* weights, double* out) {
+    if (!h || !out) return fail(h, MSL_ERR_INVALID, "msl_diffract_members: null argument");
+    int rc = check_members(h, "msl_diffract_members", G, weights);
+    if (rc) return rc;
+    const bool resident = !d_src_c64;
+    Rows r{d_src_c64, B, T, K, ld};
+    if ((rc = resolve_rows(h, "msl_diffract_members", SRC_WAVEFUNCTION | SRC_FIRST_B, &r))) return rc;
+    if (r.B % G) return fail(h, MSL_ERR_INVALID, "msl_diffract_members: %lld waves are no multiple of %d members", (long long)r.B, G);
+    if (resident && (wx != h->wx / h->bx || wy != h->wy / h->by))
+        return fail(h, MSL_ERR_INVALID, "msl_diffract_members: window %d x %d, the handle stores %d x %d", wx, wy, h->wx / h->bx, h->wy / h->by);
+    double* d_out = nullptr;
+    size_t out_bytes = 0;
+    if ((rc = begin_timed(h, 1)) || (rc = members_launch(h, "msl_diffract_members", r, t0, count, wx, wy, bx, by, G, weights, nullptr, &d_out, &out_bytes)))
+        return rc;
+    return download_sync(h, out, d_out, out_bytes);
+}
+
+int msl_dose_add_members(msl_handle* h, const void* d_src_c64, int64_t B, int64_t T, int64_t K, int64_t ld, int32_t t0, int32_t count, int32_t wx,
+                         int32_t wy, int32_t bx, int32_t by, int32_t G, const double* weights) {
+    if (!h) return fail(h, MSL_ERR_INVALID, "msl_dose_add_members: null handle");
+    if (h->dose_B == 0) return fail(h, MSL_ERR_STATE, "msl_dose_add_members: no accumulator (call msl_dose_reset)");
+    int rc = check_members(h, "msl_dose_add_members", G, weights);
+    if (rc) return rc;
+    const bool resident = !d_src_c64;
+    Rows r{d_src_c64, B, T, K, ld};
+    if ((rc = resolve_rows(h, "msl_dose_add_members", SRC_WAVEFUNCTION | SRC_FIRST_B, &r))) return rc;
+    if (r.B % G) return fail(h, MSL_ERR_INVALID, "msl_dose_add_members: %lld waves are no multiple of %d members", (long long)r.B, G);
+    if (resident && (wx != h->wx / h->bx || wy != h->wy / h->by))
+        return fail(h, MSL_ERR_INVALID, "msl_dose_add_members: window %d x %d, the handle stores %d x %d", wx, wy, h->wx / h->bx, h->wy / h->by);
+    if ((rc = check_window_bin(h, "msl_dose_add_members", wx, wy, bx, by))) return rc;
+    if (r.B / G > h->dose_B || wx / bx != h->dose_mx || wy / by != h->dose_my)
+        return fail(h, MSL_ERR_INVALID, "msl_dose_add_members: %lld positions of %d x %d detector pixels, the last msl_dose_reset sized %lld of %d x %d",
+                    (long long)(r.B / G), wx / bx, wy / by, (long long)h->dose_B, h->dose_mx, h->dose_my);
+    double* d_out = nullptr;
+    size_t out_bytes = 0;
+    if ((rc = begin_timed(h, 1))) return rc;
+    return members_launch(h, "msl_dose_add_members", r, t0, count, wx, wy, bx, by, G, weights, h->dose_acc.p, &d_out, &out_bytes);
 }
 
 // the draw of msl_dose_counts / msl_dose_frames into the count staging (the counts, then the flag word): checks, launch, no download

@@ -113,6 +113,7 @@ class DiffractionData:
     incident: Optional[float] = None
     frames: Optional[np.ndarray] = None
     camera: Any = None
+    coherence: Any = None                   # the coherence.Coherence of the run (None: a coherent probe)
 
     def __post_init__(self):
         if self.patterns not in ("position", "pacbed"):

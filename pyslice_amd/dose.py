@@ -161,9 +161,9 @@ def incident_intensity(nx, ny, dx, dy, mrad, wavelength):
     return float(len(beams(int(nx), int(ny), float(dx), float(dy), float(mrad), float(wavelength))))
 
 
-def scan_step_area(probe_positions):
-    """the area (Angstrom^2) one probe position stands for in a regular raster scan: the product of the steps of
-    stem_data.scan_axes.  ValueError for anything else (missing raster points, uneven steps, a single row or column)."""
+def raster_steps(probe_positions, who, hint=""):
+    """(step_x, step_y) of a scan that is a full regular raster of its coordinates (stem_data.scan_axes).  ValueError, opened with
+    `who` and closed with `hint`, for anything else (missing raster points, uneven steps, a single row or column)."""
     from .stem_data import scan_axes
     pp = np.asarray(probe_positions, dtype=np.float64).reshape(-1, 2)
     xs, ys = scan_axes(pp)
@@ -171,11 +171,18 @@ def scan_step_area(probe_positions):
     for name, ax in (("x", xs), ("y", ys)):
         d = np.diff(ax)
         if d.size < 1 or not np.allclose(d, d[0], rtol=1e-6, atol=1e-9):
-            raise ValueError(f"Dose(per_area=...): the scan is not a regular raster along {name} (give electrons_per_probe)")
+            raise ValueError(f"{who}: the scan is not a regular raster along {name}{hint}")
         steps.append(float(d[0]))
     if len(xs) * len(ys) != len(pp) or len({(x, y) for x, y in pp}) != len(pp):
-        raise ValueError("Dose(per_area=...): the probe positions are not a full raster of their coordinates (give electrons_per_probe)")
-    return steps[0] * steps[1]
+        raise ValueError(f"{who}: the probe positions are not a full raster of their coordinates{hint}")
+    return steps[0], steps[1]
+
+
+def scan_step_area(probe_positions):
+    """the area (Angstrom^2) one probe position stands for in a regular raster scan: the product of the steps of
+    stem_data.scan_axes.  ValueError for anything else (missing raster points, uneven steps, a single row or column)."""
+    sx, sy = raster_steps(probe_positions, "Dose(per_area=...)", " (give electrons_per_probe)")
+    return sx * sy
 
 
 def _dose_number(name, v):

@@ -156,6 +156,15 @@ class PolarData:
     layer: Optional[np.ndarray] = None
     thickness: Optional[np.ndarray] = None
     tilts: Optional[list] = None            # the tilt.Tilt of every run of a precession average (tilt order); None otherwise
+    coherence: Any = None                   # the coherence.Coherence of the run (None: a coherent probe)
+
+    def source_blurred(self, sigma, periodic=True) -> "PolarData":
+        """this result with the signals (and those of .stem) convolved over the scan with a Gaussian source of rms width sigma
+        (Angstrom) per axis (coherence.blur_scan).  The probe positions must form a full regular raster (ValueError otherwise);
+        periodic=True when the raster covers a periodic cell."""
+        from .coherence import blur_positions
+        return replace(self, signals=blur_positions(self.signals, self.probe_positions, sigma, periodic),
+                       stem=None if self.stem is None else self.stem.source_blurred(sigma, periodic))
 
     def __post_init__(self):
         R, A = self.polar.n_rings, self.polar.n_azimuthal

@@ -130,6 +130,16 @@ class STEMData:
     thickness: Optional[np.ndarray] = None
     tilts: Optional[list] = None            # the tilt.Tilt of every run of a precession average (tilt order); None otherwise
     tds_per_slice: Optional[np.ndarray] = None
+    coherence: Any = None                   # the coherence.Coherence of the run (None: a coherent probe)
+
+    def source_blurred(self, sigma, periodic=True) -> "STEMData":
+        """this result with the signals convolved over the scan with a Gaussian source of rms width sigma (Angstrom) per axis
+        (coherence.blur_scan): the cheap route to a finite source size.  The probe positions must form a full regular raster
+        (ValueError otherwise); periodic=True when the raster covers a periodic cell."""
+        from .coherence import blur_positions
+        return replace(self, signals=blur_positions(self.signals, self.probe_positions, sigma, periodic),
+                       tds_per_slice=None if self.tds_per_slice is None else blur_positions(self.tds_per_slice, self.probe_positions,
+                                                                                           sigma, periodic))
 
     def __post_init__(self):
         if self.xs is None or self.ys is None:
