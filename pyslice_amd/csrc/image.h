@@ -6,7 +6,7 @@
 // transform of fft2_inplace in place, image_accumulate_kernel into the handle's (n_images, nx * ny) float64 accumulator.
 //
 // lens_apply_kernel: a lane owns one pixel (VEC: one column pair) of the UNSHIFTED (nx, ny) grid.  It evaluates H once -- kx, ky, the
-// aperture test and the Cartesian float64 polynomial of chi in turns exactly as probe_kspace_aberr_kernel (potential.h), reduced to
+// aperture test as probe_kspace_aberr_kernel (potential.h), the Cartesian float64 polynomial of chi in turns of aberration.h, reduced to
 // one turn in float64 before the one float sincospif -- and reuses it for every image of the launch it walks.  Outside the aperture
 // it stores zeros and neither reads the source nor does float64 work.  The source pixel of (mx, my) is ((mx + nx/2) % nx,
 // (my + ny/2) % ny) of the shifted spectrum, which is ifftshift for odd lengths too.  VEC (16-byte loads and stores) needs ny and
@@ -20,32 +20,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-namespace msl {
+#include "aberration.h"
+#include "potential.h"
 
-// chi / (2 pi) in turns at alpha = (ax, ay) = lambda k: the polynomial of probe_kspace_aberr_kernel, term by term in its order
-__device__ __forceinline__ double lens_chi_turns(double ax, double ay, const ProbeAberrations& ab) {
-    const double r2 = fma(ax, ax, ay * ay);
-    // z^m = (ax + i ay)^m, m = 2 .. 6
-    const double c2 = fma(ax, ax, -ay * ay), s2 = 2.0 * ax * ay;
-    const double c3 = fma(c2, ax, -s2 * ay), s3 = fma(c2, ay, s2 * ax);
-    const double c4 = fma(c3, ax, -s3 * ay), s4 = fma(c3, ay, s3 * ax);
-    const double c5 = fma(c4, ax, -s4 * ay), s5 = fma(c4, ay, s4 * ax);
-    const double c6 = fma(c5, ax, -s5 * ay), s6 = fma(c5, ay, s5 * ax);
-    double chi = r2 * fma(r2, fma(r2, ab.a[10], ab.a[4]), ab.a[0]);
-    chi = fma(ax, r2 * fma(r2, ab.a[7], ab.a[2]), chi);
-    chi = fma(ay, r2 * fma(r2, ab.b[7], ab.b[2]), chi);
-    chi = fma(c2, fma(r2, fma(r2, ab.a[11], ab.a[5]), ab.a[1]), chi);
-    chi = fma(s2, fma(r2, fma(r2, ab.b[11], ab.b[5]), ab.b[1]), chi);
-    chi = fma(c3, fma(r2, ab.a[8], ab.a[3]), chi);
-    chi = fma(s3, fma(r2, ab.b[8], ab.b[3]), chi);
-    chi = fma(c4, fma(r2, ab.a[12], ab.a[6]), chi);
-    chi = fma(s4, fma(r2, ab.b[12], ab.b[6]), chi);
-    chi = fma(c5, ab.a[9], chi);
-    chi = fma(s5, ab.b[9], chi);
-    chi = fma(c6, ab.a[13], chi);
-    chi = fma(s6, ab.b[13], chi);
-    return chi;
-}
+namespace msl {
 
 // H at the unshifted pixel (mx, my); false outside the aperture (radius <= 0: no aperture)
 __device__ __forceinline__ bool lens_transfer(int mx, int my, int nx, int ny, double kfreq_x, double kfreq_y, double radius, double wavelength,
@@ -54,7 +32,7 @@ __device__ __forceinline__ bool lens_transfer(int mx, int my, int nx, int ny, do
     const double kx = fx * kfreq_x, ky = fy * kfreq_y;       // fftfreq value = index * (1/(n*d))
     if (radius > 0.0 && !(sqrt(kx * kx + ky * ky) < radius)) return false;
     if (!has_chi) { *H = make_float2(1.f, 0.f); return true; }
-    double t = -lens_chi_turns(wavelength * kx, wavelength * ky, ab);
+    double t = -aberration_chi_turns(wavelength * kx, wavelength * ky, ab, ab.a[0]);
     t -= rint(t);
     float sn, cs;
     sincospif((float)(2.0 * t), &sn, &cs);

@@ -3139,6 +3139,22 @@ int msl_set_aberrations(msl_handle* h, const double* polar, int32_t n_terms) {
     return MSL_OK;
 }
 
+// the tail of every call that fills the probe buffer: the transposed copy the slice loop starts from, one wait, the flag
+static int finish_probes(msl_handle* h) {
+    int rc = transpose_probes(h);
+    if (rc) return rc;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    h->have_probes = true;
+    return MSL_OK;
+}
+
+// ... of msl_set_probes and msl_set_probe_members, whose kernel has just been queued: reciprocal-space probes to real space first
+static int finish_kspace_probes(msl_handle* h, int32_t n_probes) {
+    HIPCHK(h, hipGetLastError());
+    const int rc = fft2_inplace(h, h->psi0, n_probes, -1, 1.0f / ((float)h->cfg.nx * (float)h->cfg.ny), h->pitch);
+    return rc ? rc : finish_probes(h);
+}
+
 int msl_set_probes(msl_handle* h, double mrad, const double* xy, int32_t n_probes) {
     if (!h || !xy) return fail(h, MSL_ERR_INVALID, "msl_set_probes: null argument");
     if (n_probes != h->cfg.n_probes) return fail(h, MSL_ERR_INVALID, "msl_set_probes: %d probes, handle has %d", n_probes, h->cfg.n_probes);
@@ -3149,29 +3165,15 @@ int msl_set_probes(msl_handle* h, double mrad, const double* xy, int32_t n_probe
     const long long total = (long long)c.nx * c.ny * n_probes;
     const double lx = c.nx * c.dx, ly = c.ny * c.dy;
     if (h->have_aberr && mrad != 0) {
-        // (a, b) = C (cos, sin)(m phi) / ((n + 1) lambda): the kernel's polynomial then gives chi / (2 pi) in turns
-        static const int term_n[14] = {1, 1, 2, 2, 3, 3, 3, 4, 4, 4, 5, 5, 5, 5}, term_m[14] = {0, 2, 1, 3, 0, 2, 4, 1, 3, 5, 0, 2, 4, 6};
-        ProbeAberrations ab;
-        for (int k = 0; k < 14; ++k) {
-            const double w = h->aberr_polar[k][0] / ((term_n[k] + 1) * c.wavelength);
-            ab.a[k] = term_m[k] ? w * cos(term_m[k] * h->aberr_polar[k][1]) : w;
-            ab.b[k] = term_m[k] ? w * sin(term_m[k] * h->aberr_polar[k][1]) : 0.0;
-        }
-        hipLaunchKernelGGL(probe_kspace_aberr_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, h->psi0, h->d_xy,
-                           n_probes, c.nx, c.ny, h->pitch, 1.0 / lx, 1.0 / ly, 1.0 / (c.nx * c.dx), 1.0 / (c.ny * c.dy),
-                           (mrad * 1e-3) / c.wavelength, c.wavelength, ab);
+        hipLaunchKernelGGL(probe_kspace_aberr_kernel<false>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, h->psi0, h->d_xy,
+                           (const double*)nullptr, n_probes, c.nx, c.ny, h->pitch, 1.0 / lx, 1.0 / ly, 1.0 / (c.nx * c.dx), 1.0 / (c.ny * c.dy),
+                           (mrad * 1e-3) / c.wavelength, c.wavelength, probe_aberrations(h->aberr_polar[0], c.wavelength));
     } else {
         hipLaunchKernelGGL(probe_kspace_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, h->psi0, h->d_xy,
                            n_probes, c.nx, c.ny, h->pitch, 1.0 / lx, 1.0 / ly, 1.0 / (c.nx * c.dx), 1.0 / (c.ny * c.dy),
                            (mrad * 1e-3) / c.wavelength, mrad == 0 ? 1 : 0);
     }
-    HIPCHK(h, hipGetLastError());
-    int rc = fft2_inplace(h, h->psi0, n_probes, -1, 1.0f / ((float)c.nx * (float)c.ny), h->pitch);
-    if (rc) return rc;
-    if ((rc = transpose_probes(h))) return rc;
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    h->have_probes = true;
-    return MSL_OK;
+    return finish_kspace_probes(h, n_probes);
 }
 
 int msl_set_probe_members(msl_handle* h, double mrad, const double* xy, const double* defocus, int32_t n_probes) {
@@ -3189,14 +3191,7 @@ int msl_set_probe_members(msl_handle* h, double mrad, const double* xy, const do
     HIPCHK(h, hipSetDevice(c.device));
     int rc = h->mem_a0.reserve(h, (size_t)n_probes);
     if (rc) return rc;
-    // (a, b) = C (cos, sin)(m phi) / ((n + 1) lambda) as msl_set_probes; the C10 term of probe p is (C10 + defocus[p]) / (2 lambda)
-    static const int term_n[14] = {1, 1, 2, 2, 3, 3, 3, 4, 4, 4, 5, 5, 5, 5}, term_m[14] = {0, 2, 1, 3, 0, 2, 4, 1, 3, 5, 0, 2, 4, 6};
-    ProbeAberrations ab;
-    for (int k = 0; k < 14; ++k) {
-        const double w = h->aberr_polar[k][0] / ((term_n[k] + 1) * c.wavelength);
-        ab.a[k] = term_m[k] ? w * cos(term_m[k] * h->aberr_polar[k][1]) : w;
-        ab.b[k] = term_m[k] ? w * sin(term_m[k] * h->aberr_polar[k][1]) : 0.0;
-    }
+    // the C10 coefficient of probe p is (C10 + defocus[p]) / (2 lambda), every other one is the handle's
     std::vector<double> a0((size_t)n_probes);
     for (int p = 0; p < n_probes; ++p) a0[p] = (h->aberr_polar[0][0] + defocus[p]) / (2 * c.wavelength);
     HIPCHK(h, hipMemcpyAsync(h->d_xy, xy, 2 * sizeof(double) * n_probes, hipMemcpyHostToDevice, h->stream));
@@ -3204,16 +3199,10 @@ int msl_set_probe_members(msl_handle* h, double mrad, const double* xy, const do
     HIPCHK(h, hipStreamSynchronize(h->stream));                 // (a0 is this call's own: copied before it goes)
     const long long total = (long long)c.nx * c.ny * n_probes;
     const double lx = c.nx * c.dx, ly = c.ny * c.dy;
-    hipLaunchKernelGGL(probe_kspace_member_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, h->psi0, h->d_xy,
+    hipLaunchKernelGGL(probe_kspace_aberr_kernel<true>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, h->psi0, h->d_xy,
                        (const double*)h->mem_a0.p, n_probes, c.nx, c.ny, h->pitch, 1.0 / lx, 1.0 / ly, 1.0 / (c.nx * c.dx), 1.0 / (c.ny * c.dy),
-                       (mrad * 1e-3) / c.wavelength, c.wavelength, ab);
-    HIPCHK(h, hipGetLastError());
-    rc = fft2_inplace(h, h->psi0, n_probes, -1, 1.0f / ((float)c.nx * (float)c.ny), h->pitch);
-    if (rc) return rc;
-    if ((rc = transpose_probes(h))) return rc;
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    h->have_probes = true;
-    return MSL_OK;
+                       (mrad * 1e-3) / c.wavelength, c.wavelength, probe_aberrations(h->aberr_polar[0], c.wavelength));
+    return finish_kspace_probes(h, n_probes);
 }
 
 int msl_upload_probes(msl_handle* h, const float* c64, int32_t n_probes) {
@@ -3222,10 +3211,7 @@ int msl_upload_probes(msl_handle* h, const float* c64, int32_t n_probes) {
     HIPCHK(h, hipSetDevice(h->cfg.device));
     HIPCHK(h, hipMemcpy2DAsync(h->psi0, (size_t)h->pitch * sizeof(float2), c64, (size_t)h->cfg.ny * sizeof(float2),
                                (size_t)h->cfg.ny * sizeof(float2), (size_t)n_probes * h->cfg.nx, hipMemcpyHostToDevice, h->stream));
-    { int rc = transpose_probes(h); if (rc) return rc; }
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    h->have_probes = true;
-    return MSL_OK;
+    return finish_probes(h);
 }
 
 static int check_potential_args(msl_handle* h, const char* who, const double* pos, const int32_t* Z, int64_t n, int32_t ax1, int32_t ax2, int32_t axs) {
@@ -3655,16 +3641,7 @@ static void launch_synth(msl_handle* h, bool vec, int win_x, int win_y) {
 // c[p, b] of the n_probes positions in d_xy into sm_c (both hold that many), with the aberrations of the handle: one timed launch
 static int smatrix_coefficients(msl_handle* h, int n_probes) {
     const msl_config& c = h->cfg;
-    ProbeAberrations ab{};
-    if (h->have_aberr) {
-        // (a, b) = C (cos, sin)(m phi) / ((n + 1) lambda), as msl_set_probes: the kernel's polynomial gives chi / (2 pi) in turns
-        static const int term_n[14] = {1, 1, 2, 2, 3, 3, 3, 4, 4, 4, 5, 5, 5, 5}, term_m[14] = {0, 2, 1, 3, 0, 2, 4, 1, 3, 5, 0, 2, 4, 6};
-        for (int k = 0; k < 14; ++k) {
-            const double w = h->aberr_polar[k][0] / ((term_n[k] + 1) * c.wavelength);
-            ab.a[k] = term_m[k] ? w * cos(term_m[k] * h->aberr_polar[k][1]) : w;
-            ab.b[k] = term_m[k] ? w * sin(term_m[k] * h->aberr_polar[k][1]) : 0.0;
-        }
-    }
+    const ProbeAberrations ab = h->have_aberr ? probe_aberrations(h->aberr_polar[0], c.wavelength) : ProbeAberrations{};
     const long long nc = (long long)n_probes * h->sm_Bm;
     const float scale = (float)((double)h->sm_fx * h->sm_fy / ((double)c.nx * c.ny));
     hipLaunchKernelGGL(smatrix_coeff_kernel, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, h->stream, h->sm_c.p, (const double*)h->d_xy.p,
@@ -4361,9 +4338,6 @@ int msl_spectrum_detect(msl_handle* h, const void* d_src_f32, int64_t B, int64_t
 }
 
 // ---- diffraction patterns (diffract.h) --------------------------------------------------------------------
-// the pattern pass of msl_diffract over resolved rows, queued as one timed launch: the (B, mx, my) float64 result goes to d_dst, or
-// with d_dst == NULL to h->diff_out; *d_res / *res_bytes name it.  d_acc (msl_dose_add) takes the place of both: the result is added
-// to the (B, mx, my) float64 array there
 // What the pattern pass of msl_diffract and of msl_diffract_members share, checked and computed in one place: the window, the bin
 // and the frame slots against the rows, then the bin mode, the load width and the launch shape for `waves_per_strip` waves of the source
 // per strip (1: a strip is a row of bins of one probe; G: of one position, ensemble.h) and `lds_totals` more doubles of LDS per bin of a
@@ -4403,40 +4377,84 @@ static int plan_diffract(msl_handle* h, const char* who, const Rows& r, int32_t 
     return MSL_OK;
 }
 
-static int diffract_launch(msl_handle* h, const Rows& r, int32_t t0, int32_t count, int32_t wx, int32_t wy, int32_t bx, int32_t by, double* d_dst,
-                           double** d_res, size_t* res_bytes, const char* who = "msl_diffract", double* d_acc = nullptr) {
+// the G member waves per position and their weights of a members call (ensemble.h); a null pointer to it: the plain call
+struct Members {
+    int32_t G;
+    const double* weights;
+};
+
+// the pattern pass over resolved rows, queued as one timed launch: msl_diffract's (B, mx, my) float64 result, or with `m` the
+// (B / G, mx, my) member totals of msl_diffract_members.  It is added to d_acc (the dose accumulator) where that is given, else stored
+// to d_dst, else to h->diff_out; *d_res / *res_bytes name it.
+static int pattern_launch(msl_handle* h, const char* who, const Rows& r, int32_t t0, int32_t count, int32_t wx, int32_t wy, int32_t bx, int32_t by,
+                          const Members* m, double* d_dst, double* d_acc, double** d_res, size_t* res_bytes) {
     int rc;
-    DiffractPlan pl;
-    if ((rc = plan_diffract(h, who, r, t0, count, wx, wy, bx, by, 1, 0, &pl))) return rc;
+    DiffractPlan pl;                                             // (members: strips of G waves; the LDS mode keeps the my totals of a strip there too)
+    if ((rc = plan_diffract(h, who, r, t0, count, wx, wy, bx, by, m ? m->G : 1, m ? 1 : 0, &pl))) return rc;
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    const size_t n_out = pl.n_out;
-    if (!d_acc && !d_dst && (rc = h->diff_out.reserve(h, n_out))) return rc;
+    if (!d_acc && !d_dst && (rc = h->diff_out.reserve(h, pl.n_out))) return rc;
     double* d_out = d_acc ? d_acc : (d_dst ? d_dst : h->diff_out.p);
-    with_int<DIFF_DIRECT, DIFF_SHFL, DIFF_LDS>(pl.mode, [&](auto m) { with_bool(pl.vec, [&](auto v) { with_bool(d_acc != nullptr, [&](auto acc) {
-        hipLaunchKernelGGL((diffract_kernel<decltype(m)::value, decltype(v)::value, decltype(acc)::value>), dim3(pl.grid), dim3(pl.threads), pl.lds,
-                           h->stream, (const float2*)r.p, (long long)r.R, (long long)t0, (int)count, (long long)r.ld, (int)wx, (int)wy, (int)bx, (int)by,
-                           (long long)pl.strips, (int)pl.per, d_out);
+    MemberWeights mw;                                            // by value: the caller's array is not read after this function
+    for (int g = 0; m && g < MEMBERS_MAX; ++g) mw.w[g] = g < m->G ? m->weights[g] : 0.0;
+    with_int<DIFF_DIRECT, DIFF_SHFL, DIFF_LDS>(pl.mode, [&](auto mode) { with_bool(pl.vec, [&](auto vec) { with_bool(d_acc != nullptr, [&](auto acc) {
+        constexpr int MODE = decltype(mode)::value;
+        constexpr bool VEC = decltype(vec)::value, ACC = decltype(acc)::value;
+        if (m) hipLaunchKernelGGL((diffract_members_kernel<MODE, VEC, ACC>), dim3(pl.grid), dim3(pl.threads), pl.lds, h->stream, (const float2*)r.p,
+                                  (long long)r.R, (long long)t0, (int)count, (long long)r.ld, (int)wx, (int)wy, (int)bx, (int)by, (int)m->G, mw,
+                                  (long long)pl.strips, (int)pl.per, d_out);
+        else hipLaunchKernelGGL((diffract_kernel<MODE, VEC, ACC>), dim3(pl.grid), dim3(pl.threads), pl.lds, h->stream, (const float2*)r.p,
+                                (long long)r.R, (long long)t0, (int)count, (long long)r.ld, (int)wx, (int)wy, (int)bx, (int)by, (long long)pl.strips,
+                                (int)pl.per, d_out);
     }); }); });
     HIPCHK(h, hipGetLastError());
     if ((rc = mark_launch(h, K_OTHER))) return rc;
     h->ctr.algorithmic_bytes += 8ull * (uint64_t)r.K * (uint64_t)r.B * (uint64_t)count;
-    *d_res = d_out; *res_bytes = n_out * sizeof(double);
+    *d_res = d_out; *res_bytes = pl.n_out * sizeof(double);
     return MSL_OK;
+}
+
+// G, the weights of a members call
+static int check_members(msl_handle* h, const char* who, int32_t G, const double* weights) {
+    if (!weights) return fail(h, MSL_ERR_INVALID, "%s: null argument", who);
+    if (G < 1 || G > MSL_MEMBERS_MAX) return fail(h, MSL_ERR_INVALID, "%s: %d members outside [1, %d]", who, G, MSL_MEMBERS_MAX);
+    for (int g = 0; g < G; ++g)
+        if (!std::isfinite(weights[g]) || weights[g] < 0) return fail(h, MSL_ERR_INVALID, "%s: weight %d is negative or not finite", who, g);
+    return MSL_OK;
+}
+
+// One call of the pattern pass for the four entry points msl_diffract, msl_dose_add (dose: into the dose accumulator) and their members
+// variants (m): the argument and state checks, the members, the source rows (whole positions), the resident window, the accumulator's
+// shape, then the timed launch.  `out`: the host array of the two calls that download, which the dose calls do not have.
+static int pattern_call(msl_handle* h, const char* who, const void* d_src_c64, int64_t B, int64_t T, int64_t K, int64_t ld, int32_t t0, int32_t count,
+                        int32_t wx, int32_t wy, int32_t bx, int32_t by, const Members* m, bool dose, double* out) {
+    if (dose && !h) return fail(h, MSL_ERR_INVALID, "%s: null handle", who);
+    if (!dose && (!h || !out)) return fail(h, MSL_ERR_INVALID, "%s: null argument", who);
+    if (dose && h->dose_B == 0) return fail(h, MSL_ERR_STATE, "%s: no accumulator (call msl_dose_reset)", who);
+    int rc;
+    if (m && (rc = check_members(h, who, m->G, m->weights))) return rc;
+    const bool resident = !d_src_c64;
+    Rows r{d_src_c64, B, T, K, ld};
+    if ((rc = resolve_rows(h, who, SRC_WAVEFUNCTION | SRC_FIRST_B, &r))) return rc;
+    if (m && r.B % m->G) return fail(h, MSL_ERR_INVALID, "%s: %lld waves are no multiple of %d members", who, (long long)r.B, m->G);
+    if (resident && (wx != h->wx / h->bx || wy != h->wy / h->by))
+        return fail(h, MSL_ERR_INVALID, "%s: window %d x %d, the handle stores %d x %d", who, wx, wy, h->wx / h->bx, h->wy / h->by);
+    if (dose) {
+        if ((rc = check_window_bin(h, who, wx, wy, bx, by))) return rc;
+        const int64_t n = m ? r.B / m->G : r.B;
+        if (n > h->dose_B || wx / bx != h->dose_mx || wy / by != h->dose_my)
+            return fail(h, MSL_ERR_INVALID, "%s: %lld %s of %d x %d detector pixels, the last msl_dose_reset sized %lld of %d x %d", who, (long long)n,
+                        m ? "positions" : "probes", wx / bx, wy / by, (long long)h->dose_B, h->dose_mx, h->dose_my);
+    }
+    double* d_out = nullptr;
+    size_t out_bytes = 0;
+    if ((rc = begin_timed(h, 1)) || (rc = pattern_launch(h, who, r, t0, count, wx, wy, bx, by, m, nullptr, dose ? h->dose_acc.p : nullptr, &d_out, &out_bytes)))
+        return rc;
+    return dose ? MSL_OK : download_sync(h, out, d_out, out_bytes);
 }
 
 int msl_diffract(msl_handle* h, const void* d_src_c64, int64_t B, int64_t T, int64_t K, int64_t ld, int32_t t0, int32_t count, int32_t wx, int32_t wy,
                  int32_t bx, int32_t by, double* out) {
-    if (!h || !out) return fail(h, MSL_ERR_INVALID, "msl_diffract: null argument");
-    const bool resident = !d_src_c64;
-    Rows r{d_src_c64, B, T, K, ld};
-    int rc = resolve_rows(h, "msl_diffract", SRC_WAVEFUNCTION | SRC_FIRST_B, &r);
-    if (rc) return rc;
-    if (resident && (wx != h->wx / h->bx || wy != h->wy / h->by))
-        return fail(h, MSL_ERR_INVALID, "msl_diffract: window %d x %d, the handle stores %d x %d", wx, wy, h->wx / h->bx, h->wy / h->by);
-    double* d_out = nullptr;
-    size_t out_bytes = 0;
-    if ((rc = begin_timed(h, 1)) || (rc = diffract_launch(h, r, t0, count, wx, wy, bx, by, nullptr, &d_out, &out_bytes))) return rc;
-    return download_sync(h, out, d_out, out_bytes);
+    return pattern_call(h, "msl_diffract", d_src_c64, B, T, K, ld, t0, count, wx, wy, bx, by, nullptr, false, out);
 }
 
 // ---- coherent frame sums (coherent.h) ---------------------------------------------------------------------
@@ -4526,96 +4544,20 @@ int msl_dose_reset(msl_handle* h, int64_t B, int32_t mx, int32_t my) {
 
 int msl_dose_add(msl_handle* h, const void* d_src_c64, int64_t B, int64_t T, int64_t K, int64_t ld, int32_t t0, int32_t count, int32_t wx, int32_t wy,
                  int32_t bx, int32_t by) {
-    if (!h) return fail(h, MSL_ERR_INVALID, "msl_dose_add: null handle");
-    if (h->dose_B == 0) return fail(h, MSL_ERR_STATE, "msl_dose_add: no accumulator (call msl_dose_reset)");
-    const bool resident = !d_src_c64;
-    Rows r{d_src_c64, B, T, K, ld};
-    int rc = resolve_rows(h, "msl_dose_add", SRC_WAVEFUNCTION | SRC_FIRST_B, &r);
-    if (rc) return rc;
-    if (resident && (wx != h->wx / h->bx || wy != h->wy / h->by))
-        return fail(h, MSL_ERR_INVALID, "msl_dose_add: window %d x %d, the handle stores %d x %d", wx, wy, h->wx / h->bx, h->wy / h->by);
-    if ((rc = check_window_bin(h, "msl_dose_add", wx, wy, bx, by))) return rc;
-    if (r.B > h->dose_B || wx / bx != h->dose_mx || wy / by != h->dose_my)
-        return fail(h, MSL_ERR_INVALID, "msl_dose_add: %lld probes of %d x %d detector pixels, the last msl_dose_reset sized %lld of %d x %d", (long long)r.B,
-                    wx / bx, wy / by, (long long)h->dose_B, h->dose_mx, h->dose_my);
-    double* d_out = nullptr;
-    size_t out_bytes = 0;
-    if ((rc = begin_timed(h, 1))) return rc;
-    return diffract_launch(h, r, t0, count, wx, wy, bx, by, nullptr, &d_out, &out_bytes, "msl_dose_add", h->dose_acc.p);
+    return pattern_call(h, "msl_dose_add", d_src_c64, B, T, K, ld, t0, count, wx, wy, bx, by, nullptr, true, nullptr);
 }
 
 // ---- member ensembles (ensemble.h) ------------------------------------------------------------------------
-// the pattern pass of msl_diffract_members over resolved rows of Q * G waves, queued as one timed launch: the (Q, mx, my) float64
-// totals go to h->diff_out, or are added to d_acc (msl_dose_add_members); *d_res / *res_bytes name the result
-static int members_launch(msl_handle* h, const char* who, const Rows& r, int32_t t0, int32_t count, int32_t wx, int32_t wy, int32_t bx, int32_t by,
-                          int32_t G, const double* weights, double* d_acc, double** d_res, size_t* res_bytes) {
-    int rc;
-    DiffractPlan pl;                                             // (strips of G waves; the LDS mode keeps the my totals of a strip there too)
-    if ((rc = plan_diffract(h, who, r, t0, count, wx, wy, bx, by, G, 1, &pl))) return rc;
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    if (!d_acc && (rc = h->diff_out.reserve(h, pl.n_out))) return rc;
-    double* d_out = d_acc ? d_acc : h->diff_out.p;
-    MemberWeights mw;                                            // by value: the caller's array is not read after this function
-    for (int g = 0; g < MEMBERS_MAX; ++g) mw.w[g] = g < G ? weights[g] : 0.0;
-    with_int<DIFF_DIRECT, DIFF_SHFL, DIFF_LDS>(pl.mode, [&](auto m) { with_bool(pl.vec, [&](auto v) { with_bool(d_acc != nullptr, [&](auto acc) {
-        hipLaunchKernelGGL((diffract_members_kernel<decltype(m)::value, decltype(v)::value, decltype(acc)::value>), dim3(pl.grid), dim3(pl.threads),
-                           pl.lds, h->stream, (const float2*)r.p, (long long)r.R, (long long)t0, (int)count, (long long)r.ld, (int)wx, (int)wy, (int)bx,
-                           (int)by, (int)G, mw, (long long)pl.strips, (int)pl.per, d_out);
-    }); }); });
-    HIPCHK(h, hipGetLastError());
-    if ((rc = mark_launch(h, K_OTHER))) return rc;
-    h->ctr.algorithmic_bytes += 8ull * (uint64_t)r.K * (uint64_t)r.B * (uint64_t)count;
-    *d_res = d_out; *res_bytes = pl.n_out * sizeof(double);
-    return MSL_OK;
-}
-
-// what both member calls check before the source is resolved, and after: G, the weights, whole positions
-static int check_members(msl_handle* h, const char* who, int32_t G, const double* weights) {
-    if (!weights) return fail(h, MSL_ERR_INVALID, "%s: null argument", who);
-    if (G < 1 || G > MSL_MEMBERS_MAX) return fail(h, MSL_ERR_INVALID, "%s: %d members outside [1, %d]", who, G, MSL_MEMBERS_MAX);
-    for (int g = 0; g < G; ++g)
-        if (!std::isfinite(weights[g]) || weights[g] < 0) return fail(h, MSL_ERR_INVALID, "%s: weight %d is negative or not finite", who, g);
-    return MSL_OK;
-}
-
 int msl_diffract_members(msl_handle* h, const void* d_src_c64, int64_t B, int64_t T, int64_t K, int64_t ld, int32_t t0, int32_t count, int32_t wx,
                          int32_t wy, int32_t bx, int32_t by, int32_t G, const double* weights, double* out) {
-    if (!h || !out) return fail(h, MSL_ERR_INVALID, "msl_diffract_members: null argument");
-    int rc = check_members(h, "msl_diffract_members", G, weights);
-    if (rc) return rc;
-    const bool resident = !d_src_c64;
-    Rows r{d_src_c64, B, T, K, ld};
-    if ((rc = resolve_rows(h, "msl_diffract_members", SRC_WAVEFUNCTION | SRC_FIRST_B, &r))) return rc;
-    if (r.B % G) return fail(h, MSL_ERR_INVALID, "msl_diffract_members: %lld waves are no multiple of %d members", (long long)r.B, G);
-    if (resident && (wx != h->wx / h->bx || wy != h->wy / h->by))
-        return fail(h, MSL_ERR_INVALID, "msl_diffract_members: window %d x %d, the handle stores %d x %d", wx, wy, h->wx / h->bx, h->wy / h->by);
-    double* d_out = nullptr;
-    size_t out_bytes = 0;
-    if ((rc = begin_timed(h, 1)) || (rc = members_launch(h, "msl_diffract_members", r, t0, count, wx, wy, bx, by, G, weights, nullptr, &d_out, &out_bytes)))
-        return rc;
-    return download_sync(h, out, d_out, out_bytes);
+    const Members m{G, weights};
+    return pattern_call(h, "msl_diffract_members", d_src_c64, B, T, K, ld, t0, count, wx, wy, bx, by, &m, false, out);
 }
 
 int msl_dose_add_members(msl_handle* h, const void* d_src_c64, int64_t B, int64_t T, int64_t K, int64_t ld, int32_t t0, int32_t count, int32_t wx,
                          int32_t wy, int32_t bx, int32_t by, int32_t G, const double* weights) {
-    if (!h) return fail(h, MSL_ERR_INVALID, "msl_dose_add_members: null handle");
-    if (h->dose_B == 0) return fail(h, MSL_ERR_STATE, "msl_dose_add_members: no accumulator (call msl_dose_reset)");
-    int rc = check_members(h, "msl_dose_add_members", G, weights);
-    if (rc) return rc;
-    const bool resident = !d_src_c64;
-    Rows r{d_src_c64, B, T, K, ld};
-    if ((rc = resolve_rows(h, "msl_dose_add_members", SRC_WAVEFUNCTION | SRC_FIRST_B, &r))) return rc;
-    if (r.B % G) return fail(h, MSL_ERR_INVALID, "msl_dose_add_members: %lld waves are no multiple of %d members", (long long)r.B, G);
-    if (resident && (wx != h->wx / h->bx || wy != h->wy / h->by))
-        return fail(h, MSL_ERR_INVALID, "msl_dose_add_members: window %d x %d, the handle stores %d x %d", wx, wy, h->wx / h->bx, h->wy / h->by);
-    if ((rc = check_window_bin(h, "msl_dose_add_members", wx, wy, bx, by))) return rc;
-    if (r.B / G > h->dose_B || wx / bx != h->dose_mx || wy / by != h->dose_my)
-        return fail(h, MSL_ERR_INVALID, "msl_dose_add_members: %lld positions of %d x %d detector pixels, the last msl_dose_reset sized %lld of %d x %d",
-                    (long long)(r.B / G), wx / bx, wy / by, (long long)h->dose_B, h->dose_mx, h->dose_my);
-    double* d_out = nullptr;
-    size_t out_bytes = 0;
-    if ((rc = begin_timed(h, 1))) return rc;
-    return members_launch(h, "msl_dose_add_members", r, t0, count, wx, wy, bx, by, G, weights, h->dose_acc.p, &d_out, &out_bytes);
+    const Members m{G, weights};
+    return pattern_call(h, "msl_dose_add_members", d_src_c64, B, T, K, ld, t0, count, wx, wy, bx, by, &m, true, nullptr);
 }
 
 // the draw of msl_dose_counts / msl_dose_frames into the count staging (the counts, then the flag word): checks, launch, no download
@@ -4787,16 +4729,7 @@ int msl_image_add(msl_handle* h, const void* d_src_c64, int64_t B, int64_t T, in
     const int64_t cap = (int64_t)c.n_probes * h->FB;
     if (B > cap) return fail(h, MSL_ERR_INVALID, "msl_image_add: %lld probes, the work buffer holds %lld images", (long long)B, (long long)cap);
     HIPCHK(h, hipSetDevice(c.device));
-    ProbeAberrations ab{};
-    if (has_chi) {
-        // (a, b) = C (cos, sin)(m phi) / ((n + 1) lambda), as msl_set_probes: the kernel's polynomial gives chi / (2 pi) in turns
-        static const int term_n[14] = {1, 1, 2, 2, 3, 3, 3, 4, 4, 4, 5, 5, 5, 5}, term_m[14] = {0, 2, 1, 3, 0, 2, 4, 1, 3, 5, 0, 2, 4, 6};
-        for (int k = 0; k < 14; ++k) {
-            const double w = polar14x2[2 * k] / ((term_n[k] + 1) * c.wavelength);
-            ab.a[k] = term_m[k] ? w * cos(term_m[k] * polar14x2[2 * k + 1]) : w;
-            ab.b[k] = term_m[k] ? w * sin(term_m[k] * polar14x2[2 * k + 1]) : 0.0;
-        }
-    }
+    const ProbeAberrations ab = has_chi ? probe_aberrations(polar14x2, c.wavelength) : ProbeAberrations{};
     const float2* src = (const float2*)r.p + (int64_t)t0 * ld;
     const bool pitch_even = h->pitch % 2 == 0;
     // 16-byte accesses: an even column maps to an even shifted column and the pair does not wrap (ny, ny / 2 even), every image and row starts on 16 bytes
@@ -5137,7 +5070,8 @@ int layer_reduce_queue(msl_handle* h, int l, const float2* block, int slot, int 
         h->ctr.algorithmic_bytes += 8ull * (uint64_t)r.K * (uint64_t)r.B * (uint64_t)count;
     }
     if (h->lr_what & (LR_DIFFRACT | LR_PACBED)) {
-        if ((rc = diffract_launch(h, r, slot, count, h->wx / h->bx, h->wy / h->by, h->lr_bx, h->lr_by, h->lr_stage + y.diff(l), &d_res, &bytes))) return rc;
+        if ((rc = pattern_launch(h, "msl_diffract", r, slot, count, h->wx / h->bx, h->wy / h->by, h->lr_bx, h->lr_by, nullptr, h->lr_stage + y.diff(l), nullptr, &d_res, &bytes)))
+            return rc;
     }
     h->lr_slot = slot; h->lr_count = count;
     return MSL_OK;

@@ -9,6 +9,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "aberration.h"
 #include "kernel_util.h"
 
 namespace msl {
@@ -703,20 +704,15 @@ __global__ void probe_kspace_kernel(float2* __restrict__ psik, const double* __r
     psik[o] = make_float2(cs, sn);
 }
 
-// Aberration function of the probe-forming lens in Cartesian form, in the order of include/mslice.h (msl_set_aberrations):
-// C10 C12 C21 C23 C30 C32 C34 C41 C43 C45 C50 C52 C54 C56.  With alpha = lambda k and z = alpha_x + i alpha_y
-//   chi / (2 pi) = sum_nm (alpha^2)^((n+1-m)/2) (a_nm Re z^m + b_nm Im z^m),   (a_nm, b_nm) = C_nm (cos, sin)(m phi_nm) / ((n+1) lambda)
-// in turns; n + 1 - m is even for every term, so the sum is a polynomial in alpha_x, alpha_y.  Passed to the kernel by value.
-struct ProbeAberrations {
-    double a[14], b[14];
-};
-
-// probe_kspace_kernel with the aberration phase: psik = mask * exp(2 pi i (t_ramp - chi / (2 pi))).  The phase is summed and reduced
-// to one turn in float64 before the one float sincospif, so the fp32 error does not grow with the size of the aberration (Cs = 1 mm
-// at 30 mrad, 100 kV is 54 turns).  Only pixels inside the aperture do the float64 work; never launched for plane waves (chi(0) = 0).
-__global__ void probe_kspace_aberr_kernel(float2* __restrict__ psik, const double* __restrict__ xy, int P, int nx, int ny,
-                                          int pitch, double inv_lx, double inv_ly, double kfreq_x, double kfreq_y, double radius,
-                                          double wavelength, ProbeAberrations ab) {
+// probe_kspace_kernel with the aberration phase: psik = mask * exp(2 pi i (t_ramp - chi / (2 pi))), chi the polynomial of aberration.h.
+// The phase is summed and reduced to one turn in float64 before the one float sincospif, so the fp32 error does not grow with the size
+// of the aberration (Cs = 1 mm at 30 mrad, 100 kV is 54 turns).  Only pixels inside the aperture do the float64 work; never launched
+// for plane waves (chi(0) = 0).  OWN_C10 (msl_set_probe_members, ensemble.h): the C10 coefficient of probe p is a0[p] instead of ab.a[0];
+// a0 is not read otherwise.
+template <bool OWN_C10>
+__global__ void probe_kspace_aberr_kernel(float2* __restrict__ psik, const double* __restrict__ xy, const double* __restrict__ a0, int P,
+                                          int nx, int ny, int pitch, double inv_lx, double inv_ly, double kfreq_x, double kfreq_y,
+                                          double radius, double wavelength, ProbeAberrations ab) {
     long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     long long npix = (long long)nx * ny;
     if (i >= npix * P) return;
@@ -729,29 +725,7 @@ __global__ void probe_kspace_aberr_kernel(float2* __restrict__ psik, const doubl
     bool inside = sqrt(kx * kx + ky * ky) < radius;
     if (!inside) { psik[o] = make_float2(0.f, 0.f); return; }
     double t = fx * ((double)(nx / 2) / nx + xy[2 * p] * inv_lx) + fy * ((double)(ny / 2) / ny + xy[2 * p + 1] * inv_ly);
-    const double ax = wavelength * kx, ay = wavelength * ky;
-    const double r2 = fma(ax, ax, ay * ay);
-    // z^m = (ax + i ay)^m, m = 2 .. 6
-    const double c2 = fma(ax, ax, -ay * ay), s2 = 2.0 * ax * ay;
-    const double c3 = fma(c2, ax, -s2 * ay), s3 = fma(c2, ay, s2 * ax);
-    const double c4 = fma(c3, ax, -s3 * ay), s4 = fma(c3, ay, s3 * ax);
-    const double c5 = fma(c4, ax, -s4 * ay), s5 = fma(c4, ay, s4 * ax);
-    const double c6 = fma(c5, ax, -s5 * ay), s6 = fma(c5, ay, s5 * ax);
-    // radial factors, Horner in alpha^2: m = 0: C10 C30 C50, 1: C21 C41, 2: C12 C32 C52, 3: C23 C43, 4: C34 C54, 5: C45, 6: C56
-    double chi = r2 * fma(r2, fma(r2, ab.a[10], ab.a[4]), ab.a[0]);
-    chi = fma(ax, r2 * fma(r2, ab.a[7], ab.a[2]), chi);
-    chi = fma(ay, r2 * fma(r2, ab.b[7], ab.b[2]), chi);
-    chi = fma(c2, fma(r2, fma(r2, ab.a[11], ab.a[5]), ab.a[1]), chi);
-    chi = fma(s2, fma(r2, fma(r2, ab.b[11], ab.b[5]), ab.b[1]), chi);
-    chi = fma(c3, fma(r2, ab.a[8], ab.a[3]), chi);
-    chi = fma(s3, fma(r2, ab.b[8], ab.b[3]), chi);
-    chi = fma(c4, fma(r2, ab.a[12], ab.a[6]), chi);
-    chi = fma(s4, fma(r2, ab.b[12], ab.b[6]), chi);
-    chi = fma(c5, ab.a[9], chi);
-    chi = fma(s5, ab.b[9], chi);
-    chi = fma(c6, ab.a[13], chi);
-    chi = fma(s6, ab.b[13], chi);
-    t -= chi;
+    t -= aberration_chi_turns(wavelength * kx, wavelength * ky, ab, OWN_C10 ? a0[p] : ab.a[0]);
     t -= rint(t);
     float sn, cs;
     sincospif((float)(2.0 * t), &sn, &cs);

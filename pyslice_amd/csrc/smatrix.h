@@ -10,8 +10,8 @@
 // reduced in integers ((hx i) mod nx is exact), summed in float64 turns and reduced again before the one float sincospif.  Image p
 // takes beam b0 + min(p, count - 1): the images of a padded last chunk repeat its last beam.
 // smatrix_coeff_kernel: a lane owns one c[p, b]; the phase is the ramp of probe_kspace_kernel term by term, minus chi in turns (the
-// Cartesian float64 polynomial of probe_kspace_aberr_kernel, copied so that the probe kernels stay what they are), reduced to one
-// turn in float64 before the one float sincospif.
+// Cartesian float64 polynomial the probe kernels evaluate, aberration.h), reduced to one turn in float64 before the one float
+// sincospif.
 // smatrix_synth_kernel<G, VEC>: a workgroup of 256 lanes owns a tile of 8 rows x 32 lanes of absolute pixels (VEC: a lane owns the
 // column pair, 16-byte accesses -- ny and the work pitch even; else one pixel, 8-byte accesses) and a group of G probes.  A lane
 // holds G complex fp32 accumulators per pixel and walks the beams in index order: one load of S_b per beam, shared by the G probes,
@@ -25,35 +25,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "aberration.h"
+#include "potential.h"
+
 namespace msl {
 
 constexpr int SM_BEAM_CHUNK = 32;       // beams of c staged in LDS per round
 constexpr int SM_TILE_ROWS = 8, SM_TILE_LANES = 32;
-
-// chi / (2 pi) in turns at alpha = (ax, ay) = lambda k: the polynomial of probe_kspace_aberr_kernel, term by term in its order
-__device__ __forceinline__ double smatrix_chi_turns(double ax, double ay, const ProbeAberrations& ab) {
-    const double r2 = fma(ax, ax, ay * ay);
-    // z^m = (ax + i ay)^m, m = 2 .. 6
-    const double c2 = fma(ax, ax, -ay * ay), s2 = 2.0 * ax * ay;
-    const double c3 = fma(c2, ax, -s2 * ay), s3 = fma(c2, ay, s2 * ax);
-    const double c4 = fma(c3, ax, -s3 * ay), s4 = fma(c3, ay, s3 * ax);
-    const double c5 = fma(c4, ax, -s4 * ay), s5 = fma(c4, ay, s4 * ax);
-    const double c6 = fma(c5, ax, -s5 * ay), s6 = fma(c5, ay, s5 * ax);
-    double chi = r2 * fma(r2, fma(r2, ab.a[10], ab.a[4]), ab.a[0]);
-    chi = fma(ax, r2 * fma(r2, ab.a[7], ab.a[2]), chi);
-    chi = fma(ay, r2 * fma(r2, ab.b[7], ab.b[2]), chi);
-    chi = fma(c2, fma(r2, fma(r2, ab.a[11], ab.a[5]), ab.a[1]), chi);
-    chi = fma(s2, fma(r2, fma(r2, ab.b[11], ab.b[5]), ab.b[1]), chi);
-    chi = fma(c3, fma(r2, ab.a[8], ab.a[3]), chi);
-    chi = fma(s3, fma(r2, ab.b[8], ab.b[3]), chi);
-    chi = fma(c4, fma(r2, ab.a[12], ab.a[6]), chi);
-    chi = fma(s4, fma(r2, ab.b[12], ab.b[6]), chi);
-    chi = fma(c5, ab.a[9], chi);
-    chi = fma(s5, ab.b[9], chi);
-    chi = fma(c6, ab.a[13], chi);
-    chi = fma(s6, ab.b[13], chi);
-    return chi;
-}
 
 // psi0[p][i][j] = exp(2 pi i (hx i / nx + hy j / ny)), (hx, hy) = beams[b0 + min(p, count - 1)]
 __global__ void __launch_bounds__(256) plane_wave_kernel(float2* __restrict__ psi0, const int2* __restrict__ beams, int b0, int count, int P,
@@ -84,7 +62,7 @@ __global__ void __launch_bounds__(256) smatrix_coeff_kernel(float2* __restrict__
     double t = fx * ((double)(nx / 2) / nx + xy[2 * p] * inv_lx) + fy * ((double)(ny / 2) / ny + xy[2 * p + 1] * inv_ly);
     if (has_chi) {
         const double kx = fx * kfreq_x, ky = fy * kfreq_y;       // fftfreq value = index * (1/(n*d))
-        t -= smatrix_chi_turns(wavelength * kx, wavelength * ky, ab);
+        t -= aberration_chi_turns(wavelength * kx, wavelength * ky, ab, ab.a[0]);
     }
     t -= rint(t);
     float sn, cs;

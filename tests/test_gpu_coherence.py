@@ -79,6 +79,32 @@ def test_member_probes_match_numpy(ps, tag, aberrated):
         eng.close()
 
 
+@pytest.mark.parametrize("tag", ["64", "75x63"])
+def test_one_defocus_on_every_member_is_set_probes_at_that_c10(ps, tag):
+    """msl_set_probe_members with one non-zero defocus d on every probe against msl_set_probes with C10 + d, all 14 terms non-zero:
+    the same kernel body with the C10 coefficient (C10 + d) / (2 lambda) from the device array or from the handle -- bit for bit"""
+    from pyslice_amd import _native
+    xs, ys = (np.arange(64) * 0.1, np.arange(64) * 0.1) if tag == "64" else (np.arange(75) * 0.1, np.arange(63) * 0.11)
+    mrad, d = 30.0, 37.5
+    lx, ly = len(xs) * (xs[1] - xs[0]), len(ys) * (ys[1] - ys[0])
+    pp = [tuple(v) for v in np.random.default_rng(7).random((3, 2)) * [lx, ly]]
+    assert len(set(pp)) == 3
+    ab = all_terms(ps)
+    assert np.all(ab.as_polar()[:, 0] != 0)
+    eng = _native.Engine(len(xs), len(ys), 1, xs[1] - xs[0], ys[1] - ys[0], 0.5, ps.wavelength(EV), 0.0, n_probes=3, n_frames=0)
+    try:
+        eng.set_aberrations(ab)
+        eng.set_probe_members(mrad, pp, np.full(3, d))
+        members = eng.probes()
+        eng.set_aberrations(with_defocus(ps, ab, d))
+        eng.set_probes(mrad, pp)
+        plain = eng.probes()
+        assert not np.array_equal(members[0], members[1])
+        assert np.array_equal(members, plain)
+    finally:
+        eng.close()
+
+
 # ------------------------------------------------------------------ 2. msl_diffract_members
 def block_sum(I, bx, by):
     wx, wy = I.shape[-2:]
