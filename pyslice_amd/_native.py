@@ -333,17 +333,25 @@ class Engine:
     def tds_fetch(self, B=None):
         """I[s, p, d] of the last slice loop, (nz, B, n_det) float64: the TDS generated in slice s that lands on detector d, for the
         first B probes (msl_tds_fetch; one wait for the stream)"""
-        b = int(B) if B else self.n_probes
-        out = np.empty((self.nz, b, getattr(self, "n_tds", 0)), dtype=np.float64)
-        self._chk(self._lib.msl_tds_fetch(self._h, b, _ptr(out)))
-        return out
+        return self._slice_sums_fetch(self._lib.msl_tds_fetch, getattr(self, "n_tds", 0), B)
 
     def tds_reduce(self, slice_index=0, reps=1):
         """the TDS reduction alone, of the work buffer the last slice loop left against the weights of one slice (msl_tds_reduce) ->
         (sums (n_probes, n_det) float64, mean device time of one of the `reps` repeats in ms)"""
-        out = np.empty((self.n_probes, getattr(self, "n_tds", 0)), dtype=np.float64)
+        return self._slice_sums_reduce(self._lib.msl_tds_reduce, getattr(self, "n_tds", 0), slice_index, reps)
+
+    def _slice_sums_fetch(self, fetch, n, B):
+        """(nz, B, n) float64 of the per-slice sums through msl_tds_fetch / msl_ionization_fetch"""
+        b = int(B) if B else self.n_probes
+        out = np.empty((self.nz, b, n), dtype=np.float64)
+        self._chk(fetch(self._h, b, _ptr(out)))
+        return out
+
+    def _slice_sums_reduce(self, reduce, n, slice_index, reps):
+        """((n_probes, n) float64, ms per repeat) through msl_tds_reduce / msl_ionization_reduce"""
+        out = np.empty((self.n_probes, n), dtype=np.float64)
         ms = C.c_double(0.0)
-        self._chk(self._lib.msl_tds_reduce(self._h, int(slice_index), int(reps), _ptr(out), C.byref(ms)))
+        self._chk(reduce(self._h, int(slice_index), int(reps), _ptr(out), C.byref(ms)))
         return out, float(ms.value)
 
     def set_ionization(self, channels=None):
@@ -364,18 +372,12 @@ class Engine:
     def ionization_fetch(self, B=None):
         """I[s, p, e] of the last slice loop, (nz, B, n) float64: the ionisation probability per incident electron of channel e in
         slice s, for the first B probes (msl_ionization_fetch; one wait for the stream)"""
-        b = int(B) if B else self.n_probes
-        out = np.empty((self.nz, b, getattr(self, "n_ionization", 0)), dtype=np.float64)
-        self._chk(self._lib.msl_ionization_fetch(self._h, b, _ptr(out)))
-        return out
+        return self._slice_sums_fetch(self._lib.msl_ionization_fetch, getattr(self, "n_ionization", 0), B)
 
     def ionization_reduce(self, slice_index=0, reps=1):
         """the ionisation reduction alone, of the work buffer the last slice loop left against the weights of one slice
         (msl_ionization_reduce) -> (sums (n_probes, n) float64, not divided by a norm; mean device time of one repeat in ms)"""
-        out = np.empty((self.n_probes, getattr(self, "n_ionization", 0)), dtype=np.float64)
-        ms = C.c_double(0.0)
-        self._chk(self._lib.msl_ionization_reduce(self._h, int(slice_index), int(reps), _ptr(out), C.byref(ms)))
-        return out, float(ms.value)
+        return self._slice_sums_reduce(self._lib.msl_ionization_reduce, getattr(self, "n_ionization", 0), slice_index, reps)
 
     def set_slices(self, lo, hi):
         lo = np.ascontiguousarray(lo, dtype=np.float64)

@@ -22,6 +22,7 @@
 #include "finite.h"
 #include "tds.h"
 #include "ionization.h"
+#include "slice_sums.h"
 #include "thermal.h"
 #include "phonons.h"
 #include "reduce.h"
@@ -292,7 +293,7 @@ struct msl_handle {
     // TDS detector signal (msl_set_tds, tds.h): the memberships on the fft-order grid, the tables g_det
     // (tds_n, n_species, nx, ny) next to d_ffa, the weight stack w (tds_n, nz, nx, ny) made with the interaction constant tds_sigma,
     // the per-slice sums (nz, n_probes, tds_n) of the last slice loop (tds_have) and the slab of its partials.  While tds_on the
-    // handle runs slice_loop_tds, on the two-pass loop (set_loop_mode)
+    // handle runs slice_loop with the split row step and the reduction between its halves, on the two-pass loop (set_loop_mode)
     bool tds_on = false, tds_have = false;
     int tds_n = 0;
     double tds_sigma = 0.0;
@@ -303,7 +304,7 @@ struct msl_handle {
     // their tables (ion_n, n_species, nx, ny) for the species list ion_species (ion_nsp = 0: to be made), the weight stack W
     // (ion_n, nz, nx, ny) of the last build (ion_built), an image of ones for the norm of the incident waves, the per-slice sums
     // (nz, n_probes, ion_n) and the norms (n_probes) of the last slice loop (ion_have) and the slab of its float32 partials.  While
-    // ion_on the handle runs slice_loop_tds, on the two-pass loop (set_loop_mode)
+    // ion_on the handle runs slice_loop as it does while tds_on, on the two-pass loop (set_loop_mode)
     bool ion_on = false, ion_built = false, ion_have = false;
     int ion_n = 0, ion_Z[ION_MAX] = {0}, ion_species[104] = {0}, ion_nsp = 0;
     double ion_width[ION_MAX] = {0}, ion_cross[ION_MAX] = {0};
@@ -1319,33 +1320,173 @@ int ensure_atoms(msl_handle* h, size_t n, size_t rows) {
     return MSL_OK;
 }
 
-// The slice loop (generic kernels).  fused_slot < 0: leave real-space exit waves in psi.
-int slice_loop(msl_handle* h, int fused_slot, int groups, int first_group) {
-    if (h->onepass) return slice_loop_onepass(h, fused_slot, groups, first_group);
+// ---- per-slice sums: the TDS detector signal and the element maps (4.27); slice_sums.h ----
+// A signal as the host sees it: the kernel policy plus its name in messages, the template slots N of a count n with their dispatch,
+// the slots a (tile, image) of its slab is reserved with, and where the handle keeps its settings, weights and slab.
+struct TdsSignal : TdsSums {
+    static constexpr const char* name = "tds";
+    static constexpr const char* setter = "msl_set_tds";
+    static int slots(int n) { return n; }
+    static int slab_slots(int n) { return n; }
+    template <typename F> static void with_slots(int k, F&& f) { with_int<1, 2, 3, 4>(k, f); }
+    static bool on(const msl_handle* h) { return h->tds_on; }
+    static bool built(const msl_handle* h) { return h->tds_W && h->abs_built; }
+    static int n(const msl_handle* h) { return h->tds_n; }
+    static const float* weights(const msl_handle* h) { return h->tds_W; }
+    static DevBuf<double>& slab(msl_handle* h) { return h->tds_part; }
+};
+struct IonSignal : IonSums {
+    static constexpr const char* name = "ionization";
+    static constexpr const char* setter = "msl_set_ionization";
+    static int slots(int n) { return n <= 1 ? 1 : n <= 2 ? 2 : n <= 4 ? 4 : 8; }       // the next power of two
+    static int slab_slots(int) { return ION_MAX; }          // (for any n: the slab is not reallocated between two launches of a loop)
+    template <typename F> static void with_slots(int k, F&& f) { with_int<1, 2, 4, 8>(k, f); }
+    static bool on(const msl_handle* h) { return h->ion_on; }
+    static bool built(const msl_handle* h) { return h->ion_W && h->ion_built; }
+    static int n(const msl_handle* h) { return h->ion_n; }
+    static const float* weights(const msl_handle* h) { return h->ion_W; }
+    static DevBuf<float>& slab(msl_handle* h) { return h->ion_part; }
+};
+
+// The reduction of P images at `psi` (the work buffers' layout) against n images of weights at w, w_cs values apart, into dst (P, n)
+// float64, queued: the tile kernel into the signal's slab of partials, then the sums over the tiles in float64.  reps > 1 repeats the
+// tile kernel (the timing of msl_tds_reduce / msl_ionization_reduce).
+template <class S>
+int slice_sums_queue(msl_handle* h, const float2* psi, int P, const float* w, size_t w_cs, int n, double* dst, int reps = 1) {
     const msl_config& c = h->cfg;
+    const long long pairs = (long long)c.nx * ((c.ny + 1) / 2), n_tiles = (pairs + S::TILE - 1) / S::TILE;
+    if (n_tiles > 0x7fffffffLL) return fail(h, MSL_ERR_UNSUPPORTED, "%s: too many tiles", S::name);
+    const int slots = S::slots(n);
+    auto& part = S::slab(h);
+    int rc = part.reserve(h, (size_t)n_tiles * P * S::slab_slots(n));
+    if (rc) return rc;
+    // images per workgroup: as many as possible (the weights are loaded once per workgroup) while every slot still has a workgroup
+    const long long wg_slots = (long long)h->n_cus * 8;
+    int pc = P;
+    while (pc > 1 && n_tiles * ((P + pc - 1) / pc) < wg_slots) pc = (pc + 1) / 2;
+    while ((P + pc - 1) / pc > 65535) ++pc;
+    const bool vec = (h->pitch % 2 == 0) && (((uintptr_t)psi & 15) == 0);
+    const dim3 grid((unsigned)n_tiles, (unsigned)((P + pc - 1) / pc));
+    for (int r = 0; r < reps; ++r) {
+        S::with_slots(slots, [&](auto k) { with_bool(vec, [&](auto v) {
+            hipLaunchKernelGGL((slice_sums_kernel<typename S::kernel_policy, decltype(k)::value, decltype(v)::value>), grid, dim3(256), 0, h->stream,
+                               psi, w, (long long)w_cs, n, c.nx, c.ny, h->pitch, P, pc, part.p);
+        }); });
+        HIPCHK(h, hipGetLastError());
+        if (reps == 1 && (rc = mark_launch(h, K_OTHER))) return rc;
+    }
+    S::with_slots(slots, [&](auto k) {
+        hipLaunchKernelGGL((slice_sums_finish_kernel<typename S::acc_t, decltype(k)::value>), dim3((unsigned)(((long long)P * slots + 255) / 256)),
+                           dim3(256), 0, h->stream, part.p, n_tiles, P, n, dst);
+    });
+    HIPCHK(h, hipGetLastError());
+    return reps == 1 ? mark_launch(h, K_OTHER) : MSL_OK;
+}
+
+// The sums of signal S for P images at `psi` against the weights of slice z, into dst (P, n)
+template <class S>
+int slice_sums_of_slice(msl_handle* h, const float2* psi, int P, int z, double* dst, int reps = 1) {
+    const size_t npix = (size_t)h->cfg.nx * h->cfg.ny;
+    return slice_sums_queue<S>(h, psi, P, S::weights(h) + (size_t)z * npix, npix * h->cfg.nz, S::n(h), dst, reps);
+}
+// What the two-pass loop queues between the two launches of a slice's row step, where psi holds the wave arriving at slice z in real
+// space: the sums of the active signal, into row z of its (nz, P, n) sums
+int slice_sums_hook(msl_handle* h, int P, int z) {
+    return h->tds_on ? slice_sums_of_slice<TdsSignal>(h, h->psi, P, z, h->tds_acc + (size_t)z * P * h->tds_n)
+                     : slice_sums_of_slice<IonSignal>(h, h->psi, P, z, h->ion_acc + (size_t)z * P * h->ion_n);
+}
+
+// out (nz, B, n) <- the sums (nz, n_probes, n) of the last slice loop, for the first B probes (B <= 0: all; *B is the count taken),
+// queued on the stream: the caller waits for it
+int slice_sums_fetch(msl_handle* h, const char* who, const double* sums, int n, int32_t* B, double* out) {
+    const int P = h->cfg.n_probes;
+    if (*B <= 0) *B = P;
+    if (*B > P) return fail(h, MSL_ERR_INVALID, "%s: %d probes, the handle has %d", who, *B, P);
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    HIPCHK(h, hipMemcpy2DAsync(out, (size_t)*B * n * sizeof(double), sums, (size_t)P * n * sizeof(double), (size_t)*B * n * sizeof(double),
+                               (size_t)h->cfg.nz, hipMemcpyDeviceToHost, h->stream));
+    return MSL_OK;
+}
+
+// The reduction alone: the work buffer against the weights of one slice, `reps` times between two events
+template <class S>
+int slice_sums_reduce(msl_handle* h, const char* who, int32_t slice, int32_t reps, double* out, double* ms_reduce) {
+    if (!h) return fail(h, MSL_ERR_INVALID, "%s: null handle", who);
+    if (!S::on(h) || !S::built(h)) return fail(h, MSL_ERR_STATE, "%s: no weight stack (%s, then a build)", who, S::setter);
+    if (slice < 0 || slice >= h->cfg.nz) return fail(h, MSL_ERR_INVALID, "%s: slice %d outside [0, %d)", who, slice, h->cfg.nz);
+    if (reps < 1) return fail(h, MSL_ERR_INVALID, "%s: reps must be positive", who);
+    const float2* src = h->psi.p;                       // MSL_BUF_EXIT: whatever the last slice loop left there
+    const int P = h->cfg.n_probes, n = S::n(h);
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    DevBuf<double> dst;
+    int rc = dst.alloc(h, (size_t)P * n);
+    if (rc) return rc;
+    h->cur = nullptr;
+    // the timed launches run between two events of their own, after one untimed pass has sized the slab
+    if (reps > 1 && (rc = slice_sums_of_slice<S>(h, src, P, slice, dst))) return rc;
+    double ms = 0.0;
+    EventPair timer;
+    if ((rc = timer.begin(h)) || (rc = slice_sums_of_slice<S>(h, src, P, slice, dst, reps)) || (rc = timer.end(h, &ms))) {
+        (void)hipStreamSynchronize(h->stream);          // nothing queued reads dst when it is freed
+        return rc;
+    }
+    if (ms_reduce) *ms_reduce = ms / reps;              // (the one finishing sum of the call is in it: take reps large)
+    if (out) HIPCHK(h, hipMemcpy(out, dst, (size_t)P * n * sizeof(double), hipMemcpyDeviceToHost));
+    return MSL_OK;
+}
+
+// The slice loop (generic kernels).  fused_slot < 0: leave real-space exit waves in psi.
+// While a per-slice signal is on (msl_set_tds or msl_set_ionization) the row step of every slice is issued as two launches of its own
+// kernels -- the inverse y-transform alone, as fft2_inplace issues it, then t_s, the forward transform and P_y -- so that between them
+// psi holds psi_s in real space at its true scale, where the reduction is queued (at s = 0 psi is psi0).  Every elastic launch computes
+// what the single launch computes; the per-slice sums go to tds_acc (nz, P, tds_n) or ion_acc (nz, P, ion_n), and for the ionisation
+// signal the norms of the incident waves, the same kernel against an image of ones, to ion_norm.  `sums` is run_loop's alone: every
+// other caller (msl_smatrix_build) runs the plain loop and leaves the sums of the last probe loop alone, whatever the handle's setting.
+int slice_loop(msl_handle* h, int fused_slot, int groups, int first_group, bool sums = false) {
+    const msl_config& c = h->cfg;
+    const bool tds = sums && h->tds_on, ion = sums && !tds;
+    if (sums && (groups != 1 || h->onepass))
+        return fail(h, MSL_ERR_STATE, "%s: the slice loop needs one frame per launch on the two-pass loop", ion ? "ionization" : "tds");
+    if (tds && !TdsSignal::built(h)) return fail(h, MSL_ERR_STATE, "tds: no weight stack (build the potential after msl_set_tds)");
+    if (ion && !IonSignal::built(h))
+        return fail(h, MSL_ERR_STATE, "ionization: no weight stack (build the potential after msl_set_ionization)");
+    if (h->onepass) return slice_loop_onepass(h, fused_slot, groups, first_group);
     const int P = c.n_probes * groups, nz = c.nz;
     const size_t npix = (size_t)c.nx * c.ny;
     const size_t toff = (size_t)first_group * c.nz * npix;
+    int rc;
+    if (sums && (rc = (ion ? h->ion_acc : h->tds_acc).reserve(h, (size_t)nz * P * (ion ? h->ion_n : h->tds_n)))) return rc;
+    if (ion && (rc = h->ion_norm.reserve(h, (size_t)P))) return rc;
     HIPCHK(h, hipMemcpyAsync(h->psi, h->psi0, (size_t)P * c.nx * h->pitch * sizeof(float2), hipMemcpyDeviceToDevice, h->stream));
+    if (ion && (rc = slice_sums_queue<IonSignal>(h, h->psi, P, h->ion_ones, npix, 1, h->ion_norm))) return rc;     // (ahead of the timed launches)
     const bool fused = fused_slot >= 0;
-    int rc = begin_timed(h, 2 * nz + 2 + (fused ? tap_launches(h) : 0));
-    if (rc) return rc;
-    for (int z = 0; z < nz; ++z) {
+    if ((rc = begin_timed(h, (sums ? 5 : 2) * nz + 2 + (fused ? tap_launches(h) : 0)))) return rc;
+    // the row step of slice z, or one of its halves: the inverse y-transform of the previous step; t_z, the forward transform and P_y
+    auto row_step = [&](int z, bool inverse, bool forward) {
         const bool last = (z == nz - 1);
         if (h->Ry) {
             RowJob r = row_job(h, h->psi, P, h->pitch);
-            r.do_ifft = z > 0; r.trans = h->trans + toff + (size_t)z * npix;
-            r.do_fft = (!last || fused); r.py = last ? nullptr : h->pyt;
+            r.do_ifft = inverse;
+            if (forward) { r.trans = h->trans + toff + (size_t)z * npix; r.do_fft = (!last || fused); r.py = last ? nullptr : h->pyt; }
             set_frame_groups(h, r, groups);
-            if ((rc = launch_row_fast(h, r, K_ROW))) return rc;
-        } else {
-            LineArgs r = row_args(h, h->psi, h->psi, P, h->pitch);
-            r.fft1 = (z > 0) ? -1 : 0;
+            return launch_row_fast(h, r, K_ROW);
+        }
+        LineArgs r = row_args(h, h->psi, h->psi, P, h->pitch);
+        r.fft1 = inverse ? -1 : 0;
+        if (groups > 1) { r.group = c.n_probes; r.m_gs = (long long)c.nz * npix; r.out_gs = (long long)c.n_probes * r.out_is; }
+        if (forward) {
             r.m1_kind = MUL_ARRAY; r.m1 = h->trans + toff + (size_t)z * npix; r.m1_ls = c.ny;
-            if (groups > 1) { r.group = c.n_probes; r.m_gs = (long long)c.nz * npix; r.out_gs = (long long)c.n_probes * r.out_is; }
             if (!last) { r.fft2 = +1; r.m2_kind = MUL_VEC; r.m2 = h->pyt; }
             else if (fused) { r.fft2 = +1; }
-            if ((rc = launch_lines(h, h->plan_y, r, K_ROW))) return rc;
+        }
+        return launch_lines(h, h->plan_y, r, K_ROW);
+    };
+    for (int z = 0; z < nz; ++z) {
+        const bool last = (z == nz - 1);
+        if (sums) {
+            if ((z > 0 && (rc = row_step(z, true, false))) || (rc = slice_sums_hook(h, P, z)) || (rc = row_step(z, false, true))) return rc;
+        } else if ((rc = row_step(z, z > 0, true))) {
+            return rc;
         }
         if (!last && (rc = tap_step(h, z, fused_slot, groups, h->psi, false, TAP_NATURAL, 8, 2))) return rc;
         if (!last) {
@@ -1364,153 +1505,10 @@ int slice_loop(msl_handle* h, int fused_slot, int groups, int first_group) {
         // epilogue: fft along x, fftshift both axes, scatter into (P, T_local, nx, ny)
         if ((rc = epilogue_x_pass(h, fused_slot, groups))) return rc;
     }
-    count_slice_loop(h, P, groups, fused, 32);
-    return MSL_OK;
-}
-
-// ---- TDS detector signal (tds.h) ----
-// The reduction of P images at `psi` (the work buffers' layout) against the weights of slice z into dst (P, tds_n) float64, queued:
-// the tile kernel into the slab of partials, then the sums over the tiles.  reps > 1 repeats the tile kernel (msl_tds_reduce's timing).
-int tds_reduce_queue(msl_handle* h, const float2* psi, int P, int z, double* dst, int reps = 1) {
-    const msl_config& c = h->cfg;
-    const long long pairs = (long long)c.nx * ((c.ny + 1) / 2), n_tiles = (pairs + TDS_TILE - 1) / TDS_TILE;
-    if (n_tiles > 0x7fffffffLL) return fail(h, MSL_ERR_UNSUPPORTED, "tds: too many tiles");
-    int rc = h->tds_part.reserve(h, (size_t)n_tiles * P * h->tds_n);
-    if (rc) return rc;
-    // images per workgroup: as many as possible (the weights are loaded once per workgroup) while every slot still has a workgroup
-    const long long slots = (long long)h->n_cus * 8;
-    int pc = P;
-    while (pc > 1 && n_tiles * ((P + pc - 1) / pc) < slots) pc = (pc + 1) / 2;
-    while ((P + pc - 1) / pc > 65535) ++pc;
-    const size_t stack = (size_t)c.nx * c.ny * c.nz;
-    const float* w = h->tds_W + (size_t)z * c.nx * c.ny;
-    const bool vec = (h->pitch % 2 == 0) && (((uintptr_t)psi & 15) == 0);
-    const dim3 grid((unsigned)n_tiles, (unsigned)((P + pc - 1) / pc));
-    for (int r = 0; r < reps; ++r) {
-        with_int<1, 2, 3, 4>(h->tds_n, [&](auto nd) { with_bool(vec, [&](auto v) {
-            hipLaunchKernelGGL((tds_reduce_kernel<decltype(nd)::value, decltype(v)::value>), grid, dim3(256), 0, h->stream, psi, w, (long long)stack,
-                               c.nx, c.ny, h->pitch, P, pc, h->tds_part.p);
-        }); });
-        HIPCHK(h, hipGetLastError());
-        if (reps == 1 && (rc = mark_launch(h, K_OTHER))) return rc;
+    if (!sums) {
+        count_slice_loop(h, P, groups, fused, 32);
+        return MSL_OK;
     }
-    with_int<1, 2, 3, 4>(h->tds_n, [&](auto nd) {
-        hipLaunchKernelGGL(tds_finish_kernel<decltype(nd)::value>, dim3((unsigned)(((long long)P * h->tds_n + 255) / 256)), dim3(256), 0, h->stream,
-                           h->tds_part.p, n_tiles, P, h->tds_n, dst);
-    });
-    HIPCHK(h, hipGetLastError());
-    return reps == 1 ? mark_launch(h, K_OTHER) : MSL_OK;
-}
-
-// ---- element maps (ionization.h) ----
-// The reduction of P images at `psi` (the work buffers' layout) against n images of weights at w, w_es values apart, into dst (P, n)
-// float64, queued: the tile kernel into the slab of float32 partials, then the sums over the tiles in float64.  reps > 1 repeats the
-// tile kernel (msl_ionization_reduce's timing).
-int ion_reduce_queue(msl_handle* h, const float2* psi, int P, const float* w, size_t w_es, int n, double* dst, int reps = 1) {
-    const msl_config& c = h->cfg;
-    const long long pairs = (long long)c.nx * ((c.ny + 1) / 2), n_tiles = (pairs + ION_TILE - 1) / ION_TILE;
-    if (n_tiles > 0x7fffffffLL) return fail(h, MSL_ERR_UNSUPPORTED, "ionization: too many tiles");
-    const int ne = n <= 1 ? 1 : n <= 2 ? 2 : n <= 4 ? 4 : 8;        // channel slots of the kernel: the next power of two
-    int rc = h->ion_part.reserve(h, (size_t)n_tiles * P * ION_MAX);   // (for any n: the slab is not reallocated between two launches of a loop)
-    if (rc) return rc;
-    // images per workgroup: as many as possible (the weights are loaded once per workgroup) while every slot still has a workgroup
-    const long long slots = (long long)h->n_cus * 8;
-    int pc = P;
-    while (pc > 1 && n_tiles * ((P + pc - 1) / pc) < slots) pc = (pc + 1) / 2;
-    while ((P + pc - 1) / pc > 65535) ++pc;
-    const bool vec = (h->pitch % 2 == 0) && (((uintptr_t)psi & 15) == 0);
-    const dim3 grid((unsigned)n_tiles, (unsigned)((P + pc - 1) / pc));
-    for (int r = 0; r < reps; ++r) {
-        with_int<1, 2, 4, 8>(ne, [&](auto k) { with_bool(vec, [&](auto v) {
-            hipLaunchKernelGGL((ion_reduce_kernel<decltype(k)::value, decltype(v)::value>), grid, dim3(256), 0, h->stream, psi, w, (long long)w_es, n,
-                               c.nx, c.ny, h->pitch, P, pc, h->ion_part.p);
-        }); });
-        HIPCHK(h, hipGetLastError());
-        if (reps == 1 && (rc = mark_launch(h, K_OTHER))) return rc;
-    }
-    with_int<1, 2, 4, 8>(ne, [&](auto k) {
-        hipLaunchKernelGGL(ion_finish_kernel<decltype(k)::value>, dim3((unsigned)(((long long)P * ne + 255) / 256)), dim3(256), 0, h->stream,
-                           h->ion_part.p, n_tiles, P, n, dst);
-    });
-    HIPCHK(h, hipGetLastError());
-    return reps == 1 ? mark_launch(h, K_OTHER) : MSL_OK;
-}
-
-// What the two-pass loop queues between the two launches of a slice's row step, where psi holds the wave arriving at slice z in real
-// space: the TDS sums of the slice, or the ionisation sums
-int tds_slice_queue(msl_handle* h, int P, int z) { return tds_reduce_queue(h, h->psi, P, z, h->tds_acc + (size_t)z * P * h->tds_n); }
-int ion_slice_queue(msl_handle* h, int P, int z) {
-    const size_t npix = (size_t)h->cfg.nx * h->cfg.ny;
-    return ion_reduce_queue(h, h->psi, P, h->ion_W + (size_t)z * npix, npix * h->cfg.nz, h->ion_n, h->ion_acc + (size_t)z * P * h->ion_n);
-}
-
-// The slice loop while a per-slice reduction is on (the TDS signal it was written for, or else the ionisation signal): the two-pass
-// loop with the row step of every slice issued as two launches of its own kernels --
-// the inverse y-transform alone, as fft2_inplace issues it, then t_s, the forward transform and P_y -- so that between them psi holds
-// psi_s in real space at its true scale, where the reduction is queued (at s = 0 psi is psi0).  Every elastic launch computes what
-// slice_loop's computes; the per-slice sums go to tds_acc (nz, P, tds_n) or ion_acc (nz, P, ion_n), and for the ionisation signal
-// the norms of the incident waves, the same kernel against an image of ones, to ion_norm.
-int slice_loop_tds(msl_handle* h, int fused_slot, int groups, int first_group) {
-    const msl_config& c = h->cfg;
-    const bool ion = !h->tds_on;
-    if (groups != 1 || h->onepass)
-        return fail(h, MSL_ERR_STATE, "%s: the slice loop needs one frame per launch on the two-pass loop", ion ? "ionization" : "tds");
-    if (!ion && (!h->tds_W || !h->abs_built)) return fail(h, MSL_ERR_STATE, "tds: no weight stack (build the potential after msl_set_tds)");
-    if (ion && (!h->ion_W || !h->ion_built))
-        return fail(h, MSL_ERR_STATE, "ionization: no weight stack (build the potential after msl_set_ionization)");
-    const int P = c.n_probes, nz = c.nz, n_sums = ion ? h->ion_n : h->tds_n;
-    const size_t npix = (size_t)c.nx * c.ny;
-    const size_t toff = (size_t)first_group * c.nz * npix;
-    int rc = (ion ? h->ion_acc : h->tds_acc).reserve(h, (size_t)nz * P * n_sums);
-    if (rc) return rc;
-    if (ion && (rc = h->ion_norm.reserve(h, (size_t)P))) return rc;
-    HIPCHK(h, hipMemcpyAsync(h->psi, h->psi0, (size_t)P * c.nx * h->pitch * sizeof(float2), hipMemcpyDeviceToDevice, h->stream));
-    if (ion && (rc = ion_reduce_queue(h, h->psi, P, h->ion_ones, npix, 1, h->ion_norm))) return rc;     // (ahead of the timed launches)
-    const bool fused = fused_slot >= 0;
-    if ((rc = begin_timed(h, 5 * nz + 2 + (fused ? tap_launches(h) : 0)))) return rc;
-    for (int z = 0; z < nz; ++z) {
-        const bool last = (z == nz - 1);
-        if (z > 0) {
-            if (h->Ry) {
-                RowJob r = row_job(h, h->psi, P, h->pitch);
-                r.do_ifft = 1;
-                rc = launch_row_fast(h, r, K_ROW);
-            } else {
-                LineArgs r = row_args(h, h->psi, h->psi, P, h->pitch);
-                r.fft1 = -1;
-                rc = launch_lines(h, h->plan_y, r, K_ROW);
-            }
-            if (rc) return rc;
-        }
-        if ((rc = (ion ? ion_slice_queue : tds_slice_queue)(h, P, z))) return rc;
-        if (h->Ry) {
-            RowJob r = row_job(h, h->psi, P, h->pitch);
-            r.trans = h->trans + toff + (size_t)z * npix;
-            r.do_fft = (!last || fused); r.py = last ? nullptr : h->pyt;
-            rc = launch_row_fast(h, r, K_ROW);
-        } else {
-            LineArgs r = row_args(h, h->psi, h->psi, P, h->pitch);
-            r.m1_kind = MUL_ARRAY; r.m1 = h->trans + toff + (size_t)z * npix; r.m1_ls = c.ny;
-            if (!last) { r.fft2 = +1; r.m2_kind = MUL_VEC; r.m2 = h->pyt; }
-            else if (fused) { r.fft2 = +1; }
-            rc = launch_lines(h, h->plan_y, r, K_ROW);
-        }
-        if (rc) return rc;
-        if (!last && (rc = tap_step(h, z, fused_slot, groups, h->psi, false, TAP_NATURAL, 8, 2))) return rc;
-        if (!last) {
-            if (h->Rx) {
-                ColJob k = col_job(h, h->psi, h->psi, P, h->pitch, h->pitch);
-                k.px = h->pxt; k.flags = COL_FWD | COL_MULPX | COL_INV;
-                rc = launch_col_fast(h, k, K_COL);
-            } else {
-                LineArgs k = col_args(h, h->psi, h->psi, P, h->pitch, h->pitch);
-                k.fft1 = +1; k.m1_kind = MUL_VEC; k.m1 = h->pxt; k.fft2 = -1;
-                rc = launch_lines(h, h->plan_x, k, K_COL);
-            }
-            if (rc) return rc;
-        }
-    }
-    if (fused && (rc = epilogue_x_pass(h, fused_slot, groups))) return rc;
     (ion ? h->ion_have : h->tds_have) = true;
     // 16 B more per pixel and slice-step for the split row step, 8 for the reduction's read, and the weights once per image chunk
     count_slice_loop(h, P, groups, fused, 32 + 16 + 8);
@@ -2306,7 +2304,7 @@ bool tilt_needs_two_pass(const msl_handle* h, double tan_x, double tan_y) {
 }
 
 // The loop a handle may run under the tangents (tan_x, tan_y): the one msl_create planned, unless the TDS signal, the ionisation signal
-// (slice_loop_tds runs on the two-pass loop) or the tilt asks for the two-pass loop
+// (slice_loop takes them on the two-pass loop only) or the tilt asks for the two-pass loop
 bool allowed_onepass(const msl_handle* h, double tan_x, double tan_y) {
     return h->onepass_planned && !h->tds_on && !h->ion_on && !tilt_needs_two_pass(h, tan_x, tan_y);
 }
@@ -3366,56 +3364,28 @@ int msl_set_modes(msl_handle* h, const int32_t* basis_index, int64_t n_atoms, in
     return MSL_OK;
 }
 
-// ---- TDS detector signal (msl_set_absorption and msl_set_tds stand with the handle settings) ----
+// ---- per-slice sums: TDS detector signal and element maps (DESIGN.md sections 4.23, 4.27; msl_set_absorption, msl_set_tds and
+// msl_set_ionization stand with the handle settings; slice_sums_fetch and slice_sums_reduce with the queue) ----
 int msl_tds_fetch(msl_handle* h, int32_t B, double* out) {
     if (!h || !out) return fail(h, MSL_ERR_INVALID, "msl_tds_fetch: null argument");
     if (!h->tds_on || !h->tds_have) return fail(h, MSL_ERR_STATE, "msl_tds_fetch: no TDS sums (msl_set_tds, then a slice loop)");
-    const int P = h->cfg.n_probes, n = h->tds_n;
-    if (B <= 0) B = P;
-    if (B > P) return fail(h, MSL_ERR_INVALID, "msl_tds_fetch: %d probes, the handle has %d", B, P);
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    HIPCHK(h, hipMemcpy2DAsync(out, (size_t)B * n * sizeof(double), h->tds_acc, (size_t)P * n * sizeof(double), (size_t)B * n * sizeof(double),
-                               (size_t)h->cfg.nz, hipMemcpyDeviceToHost, h->stream));
+    int rc = slice_sums_fetch(h, "msl_tds_fetch", h->tds_acc, h->tds_n, &B, out);
+    if (rc) return rc;
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return MSL_OK;
 }
 
 int msl_tds_reduce(msl_handle* h, int32_t slice, int32_t reps, double* out, double* ms_reduce) {
-    if (!h) return fail(h, MSL_ERR_INVALID, "msl_tds_reduce: null handle");
-    if (!h->tds_on || !h->tds_W || !h->abs_built) return fail(h, MSL_ERR_STATE, "msl_tds_reduce: no weight stack (msl_set_tds, then a build)");
-    if (slice < 0 || slice >= h->cfg.nz) return fail(h, MSL_ERR_INVALID, "msl_tds_reduce: slice %d outside [0, %d)", slice, h->cfg.nz);
-    if (reps < 1) return fail(h, MSL_ERR_INVALID, "msl_tds_reduce: reps must be positive");
-    const float2* src = h->psi.p;                       // MSL_BUF_EXIT: whatever the last slice loop left there
-    const int P = h->cfg.n_probes;
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    DevBuf<double> dst;
-    int rc = dst.alloc(h, (size_t)P * h->tds_n);
-    if (rc) return rc;
-    h->cur = nullptr;
-    // the timed launches run between two events of their own, after one untimed pass has sized the slab
-    if (reps > 1 && (rc = tds_reduce_queue(h, src, P, slice, dst))) return rc;
-    double ms = 0.0;
-    EventPair timer;
-    if ((rc = timer.begin(h)) || (rc = tds_reduce_queue(h, src, P, slice, dst, reps)) || (rc = timer.end(h, &ms))) {
-        (void)hipStreamSynchronize(h->stream);          // nothing queued reads dst when it is freed
-        return rc;
-    }
-    if (ms_reduce) *ms_reduce = ms / reps;              // (the one finishing sum of the call is in it: take reps large)
-    if (out) HIPCHK(h, hipMemcpy(out, dst, (size_t)P * h->tds_n * sizeof(double), hipMemcpyDeviceToHost));
-    return MSL_OK;
+    return slice_sums_reduce<TdsSignal>(h, "msl_tds_reduce", slice, reps, out, ms_reduce);
 }
 
-// ---- element maps (msl_set_ionization stands with the handle settings) ----
 int msl_ionization_fetch(msl_handle* h, int32_t B, double* out) {
     if (!h || !out) return fail(h, MSL_ERR_INVALID, "msl_ionization_fetch: null argument");
     if (!h->ion_on || !h->ion_have) return fail(h, MSL_ERR_STATE, "msl_ionization_fetch: no sums (msl_set_ionization, then a slice loop)");
-    const int P = h->cfg.n_probes, n = h->ion_n, nz = h->cfg.nz;
-    if (B <= 0) B = P;
-    if (B > P) return fail(h, MSL_ERR_INVALID, "msl_ionization_fetch: %d probes, the handle has %d", B, P);
-    HIPCHK(h, hipSetDevice(h->cfg.device));
+    const int n = h->ion_n, nz = h->cfg.nz;
+    int rc = slice_sums_fetch(h, "msl_ionization_fetch", h->ion_acc, n, &B, out);
+    if (rc) return rc;
     std::vector<double> norm((size_t)B);
-    HIPCHK(h, hipMemcpy2DAsync(out, (size_t)B * n * sizeof(double), h->ion_acc, (size_t)P * n * sizeof(double), (size_t)B * n * sizeof(double),
-                               (size_t)nz, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipMemcpyAsync(norm.data(), h->ion_norm, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     for (int z = 0; z < nz; ++z)                            // per incident electron: over the norm of the probe, in float64
@@ -3425,31 +3395,7 @@ int msl_ionization_fetch(msl_handle* h, int32_t B, double* out) {
 }
 
 int msl_ionization_reduce(msl_handle* h, int32_t slice, int32_t reps, double* out, double* ms_reduce) {
-    if (!h) return fail(h, MSL_ERR_INVALID, "msl_ionization_reduce: null handle");
-    if (!h->ion_on || !h->ion_W || !h->ion_built)
-        return fail(h, MSL_ERR_STATE, "msl_ionization_reduce: no weight stack (msl_set_ionization, then a build)");
-    if (slice < 0 || slice >= h->cfg.nz) return fail(h, MSL_ERR_INVALID, "msl_ionization_reduce: slice %d outside [0, %d)", slice, h->cfg.nz);
-    if (reps < 1) return fail(h, MSL_ERR_INVALID, "msl_ionization_reduce: reps must be positive");
-    const float2* src = h->psi.p;                       // MSL_BUF_EXIT: whatever the last slice loop left there
-    const int P = h->cfg.n_probes, n = h->ion_n;
-    const size_t npix = (size_t)h->cfg.nx * h->cfg.ny;
-    const float* w = h->ion_W + (size_t)slice * npix;
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    DevBuf<double> dst;
-    int rc = dst.alloc(h, (size_t)P * n);
-    if (rc) return rc;
-    h->cur = nullptr;
-    // the timed launches run between two events of their own, after one untimed pass has sized the slab
-    if (reps > 1 && (rc = ion_reduce_queue(h, src, P, w, npix * h->cfg.nz, n, dst))) return rc;
-    double ms = 0.0;
-    EventPair timer;
-    if ((rc = timer.begin(h)) || (rc = ion_reduce_queue(h, src, P, w, npix * h->cfg.nz, n, dst, reps)) || (rc = timer.end(h, &ms))) {
-        (void)hipStreamSynchronize(h->stream);          // nothing queued reads dst when it is freed
-        return rc;
-    }
-    if (ms_reduce) *ms_reduce = ms / reps;              // (the one finishing sum of the call is in it: take reps large)
-    if (out) HIPCHK(h, hipMemcpy(out, dst, (size_t)P * n * sizeof(double), hipMemcpyDeviceToHost));
-    return MSL_OK;
+    return slice_sums_reduce<IonSignal>(h, "msl_ionization_reduce", slice, reps, out, ms_reduce);
 }
 
 int msl_build_modes(msl_handle* h, uint64_t seed, int64_t first_frame, int32_t count) {
@@ -3504,21 +3450,12 @@ static int run_loop(msl_handle* h, int slot, int groups, int first_group) {
     HIPCHK(h, hipSetDevice(h->cfg.device));
     // the reduce mode: the exit block is the last layer, reduced behind the epilogue like every tapped one
     const bool reduce = h->lr_on && slot >= 0;
-    int rc;
-    if (h->ion_on) {                                        // the loop of the TDS signal, with the ionisation sums on its hook
-        EventPair timer;
-        if ((h->cfg.launch_timing && (rc = timer.begin(h))) || (rc = slice_loop_tds(h, slot, groups, first_group))) return rc;
-        if (reduce && (rc = layer_reduce_queue(h, n_taps(h), h->wf, slot, groups))) return rc;
-        return h->cfg.launch_timing ? timer.end(h, &h->ctr.ms_propagate) : MSL_OK;
-    }
-    if (!h->cfg.launch_timing) {                                                         // queued; msl_synchronize / msl_download wait for it
-        if ((rc = (h->tds_on ? slice_loop_tds : slice_loop)(h, slot, groups, first_group)) || !reduce) return rc;
-        return layer_reduce_queue(h, n_taps(h), h->wf, slot, groups);
-    }
+    const bool timed = h->cfg.launch_timing;            // else queued; msl_synchronize / msl_download wait for it
     EventPair timer;
-    if ((rc = timer.begin(h)) || (rc = (h->tds_on ? slice_loop_tds : slice_loop)(h, slot, groups, first_group))) return rc;
+    int rc;
+    if ((timed && (rc = timer.begin(h))) || (rc = slice_loop(h, slot, groups, first_group, h->tds_on || h->ion_on))) return rc;
     if (reduce && (rc = layer_reduce_queue(h, n_taps(h), h->wf, slot, groups))) return rc;
-    return timer.end(h, &h->ctr.ms_propagate);
+    return timed ? timer.end(h, &h->ctr.ms_propagate) : MSL_OK;
 }
 
 int msl_propagate(msl_handle* h) {

@@ -21,6 +21,7 @@ import pytest
 
 from oracle import multislice_oracle as orc
 from test_gpu_absorptive import stack_from_tables
+from test_gpu_tds import check_streaming, streaming_probe_count
 
 pytestmark = pytest.mark.gpu
 
@@ -261,6 +262,46 @@ def test_engine_loop_for_one_to_eight_channels(ps, grid, n, monkeypatch):
     fresh.set_probes(30.0, np.asarray(c["pp"]))
     fresh.propagate()
     assert eng.exit_waves().tobytes() == fresh.exit_waves().tobytes()
+
+
+@pytest.mark.parametrize("which", ["odd", "ragged"])
+def test_reduction_streams_chunks_of_images_with_a_short_last_chunk(ps, which):
+    """64 x 45: 64 x 23 = 1472 pixel pairs, 3 tiles of 512 with a partial last one; 5 channels in the 8 slots of the kernel"""
+    c, chs = cell(*ODD_NY), channels(5)
+    P = streaming_probe_count(3, which)
+    eng = make_engine(ps, c, chs, n_probes=P)
+    eng.build_potential(c["frames"][0], c["Z"])
+    eng.set_probes(30.0, np.asarray([c["pp"][p % 3] for p in range(P)]))
+    eng.propagate()
+    n0 = (np.abs(probes64(c)) ** 2).sum(axis=(1, 2))
+    check_streaming(eng, eng.ionization_reduce, eng.ionization_weight().astype(np.float64)[:, 0], n0)
+
+
+def test_smatrix_build_under_ionization_runs_the_plain_loop_and_keeps_the_sums(ps, monkeypatch):
+    """msl_smatrix_build goes through the slice loop too: with the setting on it issues the launches of a handle without it (the
+    two-pass loop the setting forces) and leaves the sums of the last probe loop where they are"""
+    c = cell(*GRIDS[1])
+    eng = make_engine(ps, c, channels(3), n_frames=1)
+    eng.build_potential(c["frames"][0], c["Z"])
+    eng.set_probes(30.0, np.asarray(c["pp"]))
+    eng.propagate()
+    sums, c0 = eng.ionization_fetch(), eng.counters()
+    n_beams = eng.smatrix_begin((1, 1), 30.0)
+    eng.smatrix_build()
+    S, c1 = eng.smatrix(), eng.counters()
+    assert eng.ionization_fetch().tobytes() == sums.tobytes()
+    monkeypatch.setenv("MSL_DEBUG", "1")
+    monkeypatch.setenv("MSL_SLICE_PATH", "2")
+    plain = make_engine(ps, c, None, n_frames=1)
+    plain.build_potential(c["frames"][0], c["Z"])
+    plain.set_probes(30.0, np.asarray(c["pp"]))
+    p0 = plain.counters()
+    assert plain.smatrix_begin((1, 1), 30.0) == n_beams
+    plain.smatrix_build()
+    p1 = plain.counters()
+    assert plain.smatrix().tobytes() == S.tobytes() and np.abs(S).max() > 0
+    for k in ("row_launches", "col_launches", "slice_kernel_launches", "slice_steps", "algorithmic_bytes"):
+        assert c1[k] - c0[k] == p1[k] - p0[k], k
 
 
 def test_without_ionization_the_calculator_runs_as_before(ps):

@@ -22,6 +22,7 @@ pytestmark = pytest.mark.gpu
 
 GRIDS = [(256, 64, 3), (64, 256, 3), (96, 80, 4), (101, 97, 3)]
 PP = [(3.05, 4.4), (1.7, 1.25), (4.1, 2.2)]
+DEVICE = 0                                  # (the device of every engine here: Engine's default)
 ANNULI = [(40.0, 120.0), (0.0, 40.0), (120.0, 200.0), (20.0, None)]         # mrad
 
 
@@ -75,8 +76,9 @@ def resized(ps, grid, dets, **kw):
     from pyslice_amd.potentials import slice_edges
     ap, w = source(*grid), want(*grid)
     xs, ys, zs = w["xs"], w["ys"], w["zs"]
+    kw.setdefault("n_probes", len(PP))
     eng = _native.Engine(len(xs), len(ys), len(zs), xs[1] - xs[0], ys[1] - ys[0], zs[1] - zs[0], orc.wavelength(EV),
-                         orc.interaction_sigma(EV), n_probes=len(PP), **kw)
+                         orc.interaction_sigma(EV), **kw)
     eng.set_kirkland(ps.loadKirkland())
     eng.set_slices(*slice_edges(zs))
     eng.set_absorption(ap.u_by_Z, True)
@@ -144,6 +146,55 @@ def test_per_slice_sums_against_the_float64_loop_on_the_device_stacks(ps, grid, 
     ex_dev = eng.exit_waves().astype(np.complex128)
     ref_alone = np.einsum("pxy,dxy->pd", np.abs(ex_dev) ** 2, W[:, 0])
     assert np.abs(alone - ref_alone).max() <= 1e-6 * n0.max() * np.abs(W[:, 0]).max()
+
+
+def streaming_probe_count(n_tiles, which):
+    """A probe count at which the reduction's workgroups stream two or more images each.  The queue halves the images per workgroup
+    (pc -> (pc + 1) / 2, from P) until n_tiles * ceil(P / pc) reaches 8 workgroups per CU, so with S = ceil(8 CUs / n_tiles) a count
+    of a few S ends above one image.  "odd": 4 S + 1.  "ragged": 8 S - 1, for the devices on which 4 S + 1 happens to be a multiple of
+    its chunk (256 CUs: 2049 = 683 * 3 and 2733 = 911 * 3; 4095 = 511 * 8 + 7 and 5463 = 910 * 6 + 3 are not)."""
+    import torch
+    cus = torch.cuda.get_device_properties(DEVICE).multi_processor_count
+    S = -(-8 * cus // n_tiles)
+    P = 4 * S + 1 if which == "odd" else 8 * S - 1
+    pc = P
+    while pc > 1 and n_tiles * -(-P // pc) < 8 * cus:
+        pc = (pc + 1) // 2
+    print(f"streaming: {cus} CUs, {n_tiles} tiles, P = {P}: {pc} images per workgroup, {P % pc or pc} in the last chunk")
+    assert pc >= 2, (cus, P, pc)                                # else the test streams nothing: choose other counts for this device
+    assert which != "ragged" or P % pc, (cus, P, pc)
+    return P
+
+
+def check_streaming(eng, reduce, W0, n0):
+    """eng has propagated probes whose positions cycle over three, p % 3; reduce = its stand-alone reduction; W0 (n, nx, ny) float64
+    the weights of slice 0; n0 the norms of the three probes.  Equal probes give bitwise equal exit waves within a batch, so their
+    sums are bitwise equal wherever they stand in a chunk, the short last chunk included."""
+    ex = eng.exit_waves()
+    bits = ex.view(np.uint64)                                   # (one complex64 pixel)
+    for r in range(3):
+        assert (bits[r::3] == bits[r]).all(), r
+    alone, _ = reduce(0, 1)
+    for r in range(3):
+        assert (alone[r::3].view(np.uint64) == alone[r].view(np.uint64)).all(), r
+    ref = np.einsum("pxy,cxy->pc", np.abs(ex[:3].astype(np.complex128)) ** 2, W0)
+    err, bound = np.abs(alone[:3] - ref).max(), 1e-6 * n0.max() * np.abs(W0).max()
+    print(f"streaming: |alone - float64 sum| {err:.3e} (bound {bound:.3e}), largest sum {np.abs(ref).max():.3e}")
+    assert err <= bound
+    assert np.abs(ref).max() > 0
+    assert reduce(0, 1)[0].tobytes() == alone.tobytes()
+
+
+@pytest.mark.parametrize("which", ["odd", "ragged"])
+def test_reduction_streams_chunks_of_images_with_a_short_last_chunk(ps, which):
+    """96 x 80: 3840 pixel pairs, 4 tiles of 1024 with a partial last one; 4 detectors"""
+    grid = GRIDS[2]
+    P = streaming_probe_count(4, which)
+    eng = resized(ps, grid, detectors(4), n_probes=P)
+    eng.set_probes(30.0, np.asarray([PP[p % 3] for p in range(P)]))
+    eng.propagate()
+    n0 = (np.abs(probes64(want(*grid))) ** 2).sum(axis=(1, 2))
+    check_streaming(eng, eng.tds_reduce, eng.tds_weight().astype(np.float64)[:, 0], n0)
 
 
 @pytest.mark.parametrize("grid", [GRIDS[0], GRIDS[2], GRIDS[3]])

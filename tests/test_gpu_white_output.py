@@ -144,7 +144,7 @@ def test_taps_of_the_two_pass_loop(c):
 
 @pytest.mark.parametrize("nx,ny,nz", wp.OUT_TDS_LOOP_CASES, ids=["x".join(map(str, g)) for g in wp.OUT_TDS_LOOP_CASES])
 def test_taps_of_the_tds_two_pass_loop(nx, ny, nz):
-    """slice_loop_tds: the split row step of the handle while msl_set_tds is on.  The stack is built from atoms under absorption (the
+    """slice_loop with the split row step of the handle while msl_set_tds is on.  The stack is built from atoms under absorption (the
     loop needs its weights), the float64 reference runs on the device's own transmission, the probes are white"""
     res = wp.tds_loop_case(nx, ny, nz)
     tol = wp.two_pass_tolerance(nx, ny)
@@ -153,7 +153,7 @@ def test_taps_of_the_tds_two_pass_loop(nx, ny, nz):
         above += _within(f"tap after slice {k}", m, wp.bounds(nx, ny, nz, True, layer=k, tol=tol))
     above += _within("exit", res["exit"], wp.bounds(nx, ny, nz, True, tol=tol))
     assert sorted(res["taps"]) == list(range(nz - 1))
-    assert res["tds_loop"], "the byte count is not that of slice_loop_tds"
+    assert res["tds_loop"], "the byte count is not that of the split row step"
     assert res["t_range"] > 0.1, "the built stack is (nearly) vacuum"
     assert not above, above
 

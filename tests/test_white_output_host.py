@@ -130,9 +130,10 @@ def test_tap_layout_restates_the_loops_the_tap_order_and_fast_ok():
                  "} else if (n >= 513 && n <= 1024 && !dbg_env(\"MSL_NO_BLUESTEIN_REG\")) {",
                  "} else if (n >= 1025 && n <= 2047 && !dbg_env(\"MSL_NO_CONV4096\") && !dbg_env(\"MSL_NO_BLUESTEIN_REG\")) {",
                  "} else if (plan_M <= 1024 && !dbg_env(\"MSL_NO_GENERIC_ONEPASS\")) {",
-                 "int rc = begin_timed(h, 2 * nz + 2 + (fused ? tap_launches(h) : 0));",
-                 "if ((rc = begin_timed(h, 5 * nz + 2 + (fused ? tap_launches(h) : 0)))) return rc;",
-                 "if ((rc = (h->tds_on ? slice_loop_tds : slice_loop)(h, slot, groups, first_group)) || !reduce) return rc;"):
+                 "if ((rc = begin_timed(h, (sums ? 5 : 2) * nz + 2 + (fused ? tap_launches(h) : 0)))) return rc;",
+                 "if ((z > 0 && (rc = row_step(z, true, false))) || (rc = slice_sums_hook(h, P, z)) || (rc = row_step(z, false, true))) return rc;",
+                 "if ((timed && (rc = timer.begin(h))) || (rc = slice_loop(h, slot, groups, first_group, h->tds_on || h->ion_on))) return rc;",
+                 "if ((rc = transpose_probes(h)) || (rc = slice_loop(h, -1, 1, h->cur_batch))) return rc;"):
         assert line in SRC, line
     # alternating scheme: interleaved up to k = nz - 3 in the order of the READING kernel, natural at nz - 2, at both parities
     assert [wp.tap_layout(256, 256, 4, k) for k in range(3)] == [("x", "interleaved", 16, "fast", "fast"), ("y", "interleaved", 16, "fast", "fast"),
@@ -214,7 +215,7 @@ def test_the_lists_together_reach_every_path():
     assert {("row", "y", "fast"), ("row", "y", "generic")} <= seen                  # conj(P_y) in the fast and in the generic row FFT
     assert {("column", "x", "fast"), ("column", "x", "generic")} <= seen            # conj(P_x): COL_MULPX, and MUL_VEC of the generic pass
     assert {("alternating parity", p, o) for p in (0, 1) for o in ("interleaved", "natural")} <= seen
-    assert {("loop", True), ("loop", False)} <= seen and len(wp.OUT_TDS_LOOP_CASES) >= 1      # both two-pass loops: slice_loop, slice_loop_tds
+    assert {("loop", True), ("loop", False)} <= seen and len(wp.OUT_TDS_LOOP_CASES) >= 1      # both forms of the two-pass loop: the plain row step and the split one
     assert {(col, what) for col in ("fast", "generic") for what in ("window", "bin", "frame scatter")} <= stage
     # the untilted grids include the tap behind a convolution axis, the two-pass window / bin case is there, and a frame batch is binned
     assert wp.grid_plan(501, 144)[0].kind == "conv" and any((c.nx, c.ny) == (501, 144) for c in wp.OUT_UNTILTED_CASES)

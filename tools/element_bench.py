@@ -3,7 +3,7 @@ against run_detectors() on the same scan; written to profiles/element_signals.tx
 
     python tools/element_bench.py [--out profiles/element_signals.txt] [--repeat 3] [--grid 1024] [--probes 64] [--slices 20] [--scan 8]
 
-1. The reduction: msl_ionization_reduce repeats ion_reduce_kernel 200 times between two events on the `probes` waves the last slice
+1. The reduction: msl_ionization_reduce repeats the tile kernel (slice_sums_kernel<IonSums>) 200 times between two events on the `probes` waves the last slice
    loop left, against the weights of one slice.  Bytes the algorithm needs per launch: 8 per pixel and image (psi, read once) and 4
    per pixel and channel (the weights, read once per chunk of images; counted once).  The share of the HBM peak is those bytes over
    the time, over 8 TB/s.  Next to it torch's device-to-device copy of the same buffer (8 bytes read and 8 written per pixel).

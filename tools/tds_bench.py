@@ -5,7 +5,7 @@ and the reduction kernel alone against a device copy of the buffer it reads.
 
 The scan: scan x scan probe positions, grid^2 pixels of 0.1 A, `slices` slices of 1 A with 40 atoms of Si and O each, probe_batch=64,
 two detectors.  The two runs alternate in one session, the calculators set up once each; the figure is the median of run_detectors().
-The reduction: msl_tds_reduce repeats tds_reduce_kernel 200 times between two events on the 64 exit waves the last slice loop left
+The reduction: msl_tds_reduce repeats the tile kernel (slice_sums_kernel<TdsSums>) 200 times between two events on the 64 exit waves the last slice loop left
 (8 bytes per pixel and image read); the copy is torch's device-to-device copy of a buffer of the same size (8 bytes read and 8
 written), timed the same way in the same session."""
 import argparse

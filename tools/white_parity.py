@@ -432,7 +432,7 @@ OUT_CONV_CASES = [c for n in OUT_CONV_LENGTHS for c in (_oc(n, 144), _oc(144, n)
 OUT_GENERIC_CASES = [_oc(32, 135), _oc(135, 32), _oc(143, 144), _oc(144, 143)]
 # the tapped two-pass loop (slice_loop, begin_timed(2 nz + 2)): generic kernels on both axes, a Bluestein-free pair, power-of-two axes
 OUT_TWO_PASS_CASES = [_oc(96, 80, fft_path=1), _oc(45, 63, fft_path=1), _oc(256, 144, fft_path=1), _oc(512, 512, fft_path=1)]
-# the other tapped two-pass loop (slice_loop_tds, begin_timed(5 nz + 2)) runs while msl_set_tds is on, which needs a built absorptive
+# the other tapped two-pass loop (slice_loop with the split row step, begin_timed(5 nz + 2)) runs while msl_set_tds is on, which needs a built absorptive
 # potential: tds_loop_case() below.  Smallest grids: 45 x 63 for either loop (nothing in them depends on the size)
 OUT_TDS_LOOP_CASES = [(45, 63, 4)]
 OUT_PROBE_CHUNK_CASES = [_oc(600, 135, P=17), _oc(256, 256, P=33)]
@@ -608,15 +608,15 @@ def output_case(nx, ny, nz, P=2, layers=(), window=None, k_bin=None, frame_batch
 
 
 def tds_loop_bytes(nx, ny, nz, P, n_taps, wpix, n_det=1):
-    """algorithmic_bytes of one fused, tapped slice_loop_tds (56 bytes per pixel and slice-step, the weights once per slice)"""
+    """algorithmic_bytes of one fused, tapped slice_loop under msl_set_tds (56 bytes per pixel and slice-step, the weights once per slice)"""
     npix = nx * ny
     return P * nz * 56 * npix + nz * 8 * npix + P * 16 * npix + nz * n_det * 4 * npix + n_taps * P * (npix * 8 * 3 + wpix * 8)
 
 
 def tds_loop_case(nx, ny, nz, P=2, layers=None):
-    """the taps of slice_loop_tds: msl_set_tds needs an absorptive potential built from atoms, so the stack is a few atoms under
+    """the taps of slice_loop under msl_set_tds: msl_set_tds needs an absorptive potential built from atoms, so the stack is a few atoms under
     absorption, downloaded, and the float64 reference runs on the device's own t; the probes are white as everywhere here ->
-    dict(taps={k: metrics}, exit=metrics, tds_loop=bool: the byte count is that of slice_loop_tds)"""
+    dict(taps={k: metrics}, exit=metrics, tds_loop=bool: the byte count is that of the split row step)"""
     import pyslice_amd as ps
     from pyslice_amd.potentials import slice_edges
     layers = tuple(range(nz - 1)) if layers is None else tuple(layers)
