@@ -389,6 +389,39 @@ int  msl_set_ionization(msl_handle* h, int32_t n, const int32_t* Z, const double
 int  msl_ionization_fetch(msl_handle* h, int32_t B, double* out);
 int  msl_ionization_reduce(msl_handle* h, int32_t slice, int32_t reps, double* out, double* ms_reduce);
 
+/* ---- gradients: the slice loop backwards ----
+ * The derivative of a data-fit loss of the exit patterns I = |Psi|^2, Psi = fft2(t_nz-1 psi_nz-1), against measured patterns D with
+ * respect to the slice potentials (pyslice_amd/adjoint.py is the definition).  With G = dL/dPsi* (dL = 2 Re sum conj(G) dPsi) and an
+ * optional detector weight w >= 0:
+ *     MSL_ADJ_AMPLITUDE  L = sum w (sqrt I - sqrt D)^2          G = w (1 - sqrt D / max(|Psi|, sqrt eps)) Psi
+ *     MSL_ADJ_INTENSITY  L = 1/2 sum w (I - D)^2                G = w (I - D) Psi
+ *     MSL_ADJ_POISSON    L = sum w (I - D log(I + eps))         G = w (1 - D / (I + eps)) Psi
+ * Backwards: g = nx ny ifft2(G); for s = nz - 1 .. 0: dL/dV_s += 2 sigma sum_p Im(g_p conj(t_s psi_p,s)), g <- conj(t_s) g, and for
+ * s > 0 g <- ifft2(conj(P) fft2 g) with the handle's own propagator tables (a tilt is carried).  After s = 0, g is dL/dpsi_0*.
+ * msl_set_adjoint:  loss_kind = MSL_ADJ_OFF switches it off and frees its buffers.  Else allocates the wave stack (nz - 1, n_probes,
+ *   nx, pitch) c64 (psi_0 is the probe buffer), the float64 accumulator (nz, nx, ny), zeroed, and the data of one probe batch, and
+ *   puts the handle on the two-pass loop; weight: (nx, ny) f32 in the layout of D, or NULL.  MSL_ERR_UNSUPPORTED under a band limit,
+ *   an absorptive potential, a frame batch above 1, layers or a layer reduction; MSL_ERR_STATE under msl_set_tds / msl_set_ionization
+ *   (which are MSL_ERR_STATE while this is set); MSL_ERR_NOMEM names the bytes wanted: a handle of fewer probes makes the stack fit.
+ *   While it is set msl_propagate* run the plain two-pass loop.  Synchronous.
+ * msl_adjoint_reset:  zeroes the accumulator (queued).
+ * msl_adjoint_add:  for the handle's probes and potential: the forward loop, which keeps psi_s between the two launches of every row
+ *   step, the exit FFT, the residual against data (B, nx, ny) f32 on the host -- the fftshifted layout and the units of msl_diffract
+ *   at bin 1 without a k-window -- and the backward loop, added into the accumulator.  Takes the first B <= n_probes probes;
+ *   loss_out (B) float64; probe_grad (B, nx, ny) c64 or NULL.  No atomics: the same calls give the same bits.  The work buffer ends
+ *   as the probe gradient (MSL_BUF_EXIT is stale).  Synchronous.
+ * msl_adjoint_download:  the accumulator, (nz, nx, ny) float64.  Synchronous.
+ * msl_adjoint_step_time:  the step kernel of `slice` alone over the n_probes images of the work buffer as the last call left it, once
+ *   untimed and then `reps` times between two events; ms_step = the mean device time of one launch in ms.  It adds into row `slice`
+ *   of the accumulator and rewrites the work buffer: msl_adjoint_reset afterwards.  For benchmarks, as msl_tds_reduce is.
+ * Not in the reference. */
+enum { MSL_ADJ_OFF = 0, MSL_ADJ_AMPLITUDE = 1, MSL_ADJ_INTENSITY = 2, MSL_ADJ_POISSON = 3 };
+int  msl_set_adjoint(msl_handle* h, int32_t loss_kind, double epsilon, const float* weight);
+int  msl_adjoint_reset(msl_handle* h);
+int  msl_adjoint_add(msl_handle* h, const float* data, int32_t B, double* loss_out, void* probe_grad);
+int  msl_adjoint_download(msl_handle* h, double* grad);
+int  msl_adjoint_step_time(msl_handle* h, int32_t slice, int32_t reps, double* ms_step);
+
 /* TACAW: intensity[p,w,kx,ky] = | fftshift_t fft_t( Psi - <Psi>_t ) |^2 over a (B,T,npix) c64 device
  * array.  src == NULL uses the handle's own wavefunction buffer (B=P, T=T_local, npix=nx*ny) and
  * its own intensity buffer.  With src/dst given (device pointers, e.g. the output of an RCCL

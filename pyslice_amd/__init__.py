@@ -32,6 +32,8 @@ from .element_map_data import ElementMapData
 from .dose import Dose, poisson_counts
 from .camera import Camera, camera_frames, gaussian_psf, psf_from_mtf
 from .coherence import Coherence, blur_scan, chromatic_focal_spread, fwhm_to_sigma
+from .adjoint import Gradient, potential_gradient
+from .gradient_data import GradientData
 
 __all__ = ["Trajectory", "FrozenPhonons", "sigma_from_B", "PhononModes", "AbsorptivePotential", "absorptive_tables",
            "absorptive_transmission", "mean_transmission_exact", "tds_tables", "tds_weight", "tds_signal", "WFData", "Potential", "gridFromTrajectory", "getZfromElementName", "loadKirkland",
@@ -41,5 +43,5 @@ __all__ = ["Trajectory", "FrozenPhonons", "sigma_from_B", "PhononModes", "Absorp
            "Aberrations", "scherzer_defocus", "Imaging", "ImageData", "Spectroscopy", "SpectrumImageData",
            "Tilt", "Precession", "BandLimit", "Projection", "Ionization", "ionization_weights", "ionization_signal", "ElementMapData",
            "Dose", "poisson_counts", "Camera", "camera_frames", "gaussian_psf", "psf_from_mtf",
-           "Coherence", "blur_scan", "chromatic_focal_spread", "fwhm_to_sigma"]
+           "Coherence", "blur_scan", "chromatic_focal_spread", "fwhm_to_sigma", "Gradient", "potential_gradient", "GradientData"]
 __version__ = "0.1.0"

@@ -53,6 +53,7 @@ EXPORTS = [
     "msl_set_ionization", "msl_ionization_fetch", "msl_ionization_reduce",
     "msl_set_projection", "msl_get_projection",
     "msl_set_probe_members", "msl_diffract_members", "msl_dose_add_members",
+    "msl_set_adjoint", "msl_adjoint_reset", "msl_adjoint_add", "msl_adjoint_download", "msl_adjoint_step_time",
 ]
 DET_SIGNALS = {"intensity": 0, "amplitude": 1, "com_x": 2, "com_y": 3}      # include/mslice.h: MSL_DET_*
 MEMBERS_MAX = 128                                                          # include/mslice.h: MSL_MEMBERS_MAX
@@ -178,6 +179,11 @@ def load():
         "msl_set_tds": (C.c_int, [vp, vp, i32]),
         "msl_tds_fetch": (C.c_int, [vp, i32, vp]),
         "msl_tds_reduce": (C.c_int, [vp, i32, i32, vp, vp]),
+        "msl_set_adjoint": (C.c_int, [vp, i32, dbl, vp]),
+        "msl_adjoint_reset": (C.c_int, [vp]),
+        "msl_adjoint_add": (C.c_int, [vp, vp, i32, vp, vp]),
+        "msl_adjoint_download": (C.c_int, [vp, vp]),
+        "msl_adjoint_step_time": (C.c_int, [vp, i32, i32, vp]),
         "msl_set_ionization": (C.c_int, [vp, i32, vp, vp, vp]),
         "msl_ionization_fetch": (C.c_int, [vp, i32, vp]),
         "msl_ionization_reduce": (C.c_int, [vp, i32, i32, vp, vp]),
@@ -378,6 +384,46 @@ class Engine:
         """the ionisation reduction alone, of the work buffer the last slice loop left against the weights of one slice
         (msl_ionization_reduce) -> (sums (n_probes, n) float64, not divided by a norm; mean device time of one repeat in ms)"""
         return self._slice_sums_reduce(self._lib.msl_ionization_reduce, getattr(self, "n_ionization", 0), slice_index, reps)
+
+    def set_adjoint(self, loss_kind=0, epsilon=1e-20, weight=None):
+        """gradients (msl_set_adjoint; the definition is adjoint.py): loss_kind = adjoint.LOSSES[...] allocates the wave stack, the
+        float64 accumulator (zeroed) and the data of one probe batch and puts the handle on the two-pass loop; 0 switches it off.
+        weight: (nx, ny) >= 0 in the detector's (fftshifted) layout, or None."""
+        w = None
+        if loss_kind and weight is not None:
+            w = np.ascontiguousarray(weight, dtype=np.float32)
+            if w.shape != (self.nx, self.ny):
+                raise ValueError(f"weight must be ({self.nx},{self.ny}), got {w.shape}")
+        self._chk(self._lib.msl_set_adjoint(self._h, int(loss_kind), float(epsilon), None if w is None else _ptr(w)))
+
+    def adjoint_reset(self):
+        """zero the gradient accumulator (msl_adjoint_reset)"""
+        self._chk(self._lib.msl_adjoint_reset(self._h))
+
+    def adjoint_add(self, data, B=None, probe=False):
+        """the forward loop, the residual against data (B, nx, ny) in the detector's layout and the backward loop for the first B
+        probes, added into the accumulator (msl_adjoint_add) -> (loss (B,) float64, probe gradient (B, nx, ny) complex64 or None)"""
+        b = int(B) if B else self.n_probes
+        d = np.ascontiguousarray(data, dtype=np.float32)
+        if d.shape != (b, self.nx, self.ny):
+            raise ValueError(f"data must be ({b},{self.nx},{self.ny}), got {d.shape}")
+        loss = np.empty(b, dtype=np.float64)
+        pg = np.empty((b, self.nx, self.ny), dtype=np.complex64) if probe else None
+        self._chk(self._lib.msl_adjoint_add(self._h, _ptr(d), b, _ptr(loss), None if pg is None else _ptr(pg)))
+        return loss, pg
+
+    def adjoint_step_time(self, slice_index=0, reps=1):
+        """the step kernel of one slice alone over the work buffer the last adjoint_add left (msl_adjoint_step_time) -> mean device
+        time of one of the `reps` launches in ms.  It adds into the accumulator: adjoint_reset() afterwards."""
+        ms = C.c_double(0.0)
+        self._chk(self._lib.msl_adjoint_step_time(self._h, int(slice_index), int(reps), C.byref(ms)))
+        return float(ms.value)
+
+    def adjoint_download(self):
+        """the gradient accumulator, (nz, nx, ny) float64 (msl_adjoint_download)"""
+        out = np.empty((self.nz, self.nx, self.ny), dtype=np.float64)
+        self._chk(self._lib.msl_adjoint_download(self._h, _ptr(out)))
+        return out
 
     def set_slices(self, lo, hi):
         lo = np.ascontiguousarray(lo, dtype=np.float64)

@@ -135,7 +135,7 @@ class MultisliceCalculator:
                  gather="rank0", cache=False, k_window=None, frame_batch=None, k_bin=None, stream_tile=None, layers=None,
                  detectors=None, probe_batch=None, diffraction=None, aberrations=None, imaging=None, prism=None,
                  spectroscopy=None, polar=None, thickness=None, tilt=None, precession=None, tds=False, bandlimit=None,
-                 projection=None, ionization=None, coherence=None):
+                 projection=None, ionization=None, coherence=None, gradient=None):
         """
         device / force_cpu: as the reference (calculators.py:41).  There is no CPU path here, so
         force_cpu=True raises.  Keyword-only extras (not in the reference):
@@ -276,6 +276,11 @@ class MultisliceCalculator:
                    AbsorptivePotential, aberrations, tilt, bandlimit and probe_batch.  Not built (NotImplementedError): tds, prism,
                    precession, projection, detectors, polar, diffraction, imaging, spectroscopy, layers, thickness, k_window,
                    k_bin, cache, stream_tile, frame_batch > 1, several ranks.  None: every run is what it is without the argument.
+          gradient an adjoint.Gradient(loss, weight, epsilon, probe): run_gradient(data, frame, potential) then returns the derivative
+                   of the data-fit loss of the exit patterns with respect to the slice potentials (GradientData; adjoint.py is the
+                   definition).  The probes stream in probe_batch; the forward loop keeps the wave arriving at every slice, the
+                   residual and the backward loop run on the device (msl_set_adjoint / msl_adjoint_*).  With aberrations, tilt and
+                   probe_batch; every other mode: NotImplementedError("gradient: ... is not built").
           coherence a coherence.Coherence(focal_spread, focal_points, source_size, source_points): partial coherence of the probe.
                    Every scan position of run_diffraction() (plain, with Dose, with Dose + Camera), run_detectors() and run_polar()
                    is an ensemble of G = focal_points x source_points^2 member probes, member g at xy + d_g with C10 + delta_g and
@@ -300,6 +305,25 @@ class MultisliceCalculator:
             raise ValueError("dtype must be 'complex128' or 'complex64'")
         if gather not in ("rank0", "all", "none"):
             raise ValueError("gather must be 'rank0', 'all' or 'none'")
+        self._gradient = None
+        if gradient is not None:
+            from .adjoint import Gradient
+            if not isinstance(gradient, Gradient):
+                raise ValueError(f"gradient: expected a Gradient object, got {gradient!r}")
+            # the adjoint differentiates the plain two-pass loop of one frame, exp(i sigma V) and the full unbinned pattern: every mode
+            # that changes the forward model, reduces the patterns or keeps another result has no backward pass
+            for what, val in (("dose", getattr(diffraction, "dose", None) is not None), ("bandlimit", bandlimit is not None),
+                              ("projection", projection is not None), ("prism", prism is not None), ("coherence", coherence is not None),
+                              ("precession", precession is not None), ("k_window", k_window is not None), ("k_bin", k_bin is not None),
+                              ("layers", layers is not None), ("thickness", thickness is not None), ("tds", bool(tds)),
+                              ("ionization", ionization is not None), ("spectroscopy", spectroscopy is not None),
+                              ("imaging", imaging is not None), ("detectors", detectors is not None),
+                              ("diffraction", diffraction is not None), ("polar", polar is not None), ("cache", bool(cache)),
+                              ("stream_tile", stream_tile is not None),
+                              ("frame_batch > 1", frame_batch is not None and int(frame_batch) > 1)):
+                if val:
+                    raise NotImplementedError(f"gradient: {what} is not built")
+            self._gradient = gradient
         self._ionization = None
         if ionization is not None:
             from .ionization import check_ionization
@@ -415,7 +439,7 @@ class MultisliceCalculator:
                                           "PRISM waves")
         self._prism = prism
         if (probe_batch is not None and detectors is None and diffraction is None and imaging is None and spectroscopy is None
-                and polar is None and ionization is None):
+                and polar is None and ionization is None and gradient is None):
             raise ValueError("probe_batch applies to detector and diffraction runs only: give detectors=[...] or diffraction=Diffraction(...)")
         if probe_batch is not None and int(probe_batch) < 1:
             raise ValueError("probe_batch must be a positive probe count")
@@ -579,6 +603,12 @@ class MultisliceCalculator:
                 raise NotImplementedError("tds: a run over several ranks is not built")
         if getattr(self, "_ionization", None) is not None and distributed.rank_world()[1] > 1:
             raise NotImplementedError("ionization: a run over several ranks is not built")
+        if getattr(self, "_gradient", None) is not None:
+            for what, val in (("FrozenPhonons", isinstance(trajectory, FrozenPhonons)), ("PhononModes", isinstance(trajectory, PhononModes)),
+                              ("AbsorptivePotential", isinstance(trajectory, AbsorptivePotential)),
+                              ("a run over several ranks", distributed.rank_world()[1] > 1)):
+                if val:
+                    raise NotImplementedError(f"gradient: {what} is not built")
         if getattr(self, "_coherence", None) is not None:
             if distributed.rank_world()[1] > 1:
                 raise NotImplementedError("coherence: a run over several ranks is not built")
@@ -639,7 +669,7 @@ class MultisliceCalculator:
             self._setup_spectrum_image(trajectory, slice_axis)
             return
         if (self._detectors is not None or self._diffraction is not None or self._imaging is not None or self._polar is not None
-                or self._ionization is not None):
+                or self._ionization is not None or getattr(self, "_gradient", None) is not None):
             self._setup_probe_batches(trajectory, slice_axis)
             return
         n_slices = self._setup_run(trajectory, slice_axis)
@@ -723,6 +753,9 @@ class MultisliceCalculator:
             if not self._polar_counts.any():
                 raise ValueError(f"polar: no stored pixel of the {len(pkx)} x {len(pky)} spectrum lies between {self._polar.inner:g} and "
                                  f"{self._polar.edges[-1]:g} mrad")
+        grad = getattr(self, "_gradient", None)
+        if grad is not None and grad.weight is not None and grad.weight.shape != (self.nx, self.ny):
+            raise ValueError(f"gradient: weight {grad.weight.shape} does not match the {self.nx} x {self.ny} pattern")
         n_slices = self._setup_run(trajectory, slice_axis)
         self._frames = list(range(self.n_frames))
         self._thickness = None if self._thickness_arg is None else self._thickness_arg.resolve(n_slices)
@@ -736,7 +769,7 @@ class MultisliceCalculator:
         Pc = min(self.n_probes * G, 256 if auto else self._probe_batch) // G * G
         batch = self._frame_batch if self._frame_batch is not None else default_frame_batch(Pc, n_slices, self.nx, self.ny)
         # (the S-matrix holds one frame; so does the weight stack of the ionisation channels)
-        batch = 1 if (self._prism is not None or self._ionization is not None) else max(1, min(batch, self.n_frames))
+        batch = 1 if (self._prism is not None or self._ionization is not None or grad is not None) else max(1, min(batch, self.n_frames))
         free_b = _free_device_bytes(self.device) if auto else None
         if free_b is not None:
             Pc = max(G, self._fit_probe_batch(free_b, Pc, batch) // G * G)
@@ -765,6 +798,8 @@ class MultisliceCalculator:
                 self._engine.set_ionization(self._ionization)
             if self._polar is not None:
                 self._engine.set_polar(self._polar_bins.reshape(-1), self._polar.n_bins)
+            if grad is not None:                                # (the wave stack of the probe batch: what a smaller batch makes fit)
+                self._engine.set_adjoint(grad.kind, grad.epsilon, grad.weight)
             if self._thickness is not None and len(self._thickness) > 1:    # (the exit wave alone needs no tap: the plain reductions)
                 pacbed = self._diffraction is not None and self._thickness_arg.patterns == "pacbed"
                 what = ((_native.LR_DETECT if self._detectors is not None else 0) | (_native.LR_POLAR if self._polar is not None else 0)
@@ -917,6 +952,9 @@ class MultisliceCalculator:
             smatrix += 4.0 * len(self._ionization) * (n_slices + 8) * nx * ny
         polar = 8.0 * self._polar.n_bins if self._polar is not None else 0.0
         series = 0.0
+        if getattr(self, "_gradient", None) is not None:            # (per image the waves of every slice and the data; the accumulator once)
+            series = 8.0 * n_slices * nx * ny + 4.0 * nx * ny
+            smatrix += 8.0 * n_slices * nx * ny
         if self._thickness is not None and len(self._thickness) > 1:
             # the thickness series: per image one more block of the ring, the tap buffer and the detector and polar rows of every
             # entry in the float64 staging (the plain polar scratch is in `polar`); per probe the patterns of every entry
@@ -1356,6 +1394,54 @@ class MultisliceCalculator:
                                               electrons_per_probe=self.electrons_per_probe if dose is not None else None,
                                               incident=incident, frames=frames, camera=camera, coherence=getattr(self, "_coherence", None),
                                               **self._layer_fields()))
+
+    def run_gradient(self, data, frame=0, potential=None):
+        """The derivative of the data-fit loss of MultisliceCalculator(gradient=Gradient(...)) with respect to the slice potentials
+        (adjoint.py is the definition): per probe batch msl_adjoint_add runs the forward loop, which keeps the wave arriving at every
+        slice, the residual of the exit patterns against `data` and the loop backwards, and adds into a float64 accumulator on the
+        device (no atomics: repeats give the same bits; another probe_batch changes the order of the float64 sums only).
+        data: (P, nx, ny) in the layout and units of DiffractionData.intensity of an unbinned, unwindowed run, or such a
+        DiffractionData.  frame: the trajectory frame whose potential is built.  potential: (nx, ny, nz) -- the caller's estimate,
+        uploaded in place of the build (what an iterative reconstruction passes at every step).  -> GradientData."""
+        from .gradient_data import GradientData
+        grad = getattr(self, "_gradient", None)
+        if grad is None:
+            raise RuntimeError("run_gradient() needs MultisliceCalculator(gradient=Gradient(...))")
+        if self._engine is None:
+            raise RuntimeError("call setup() before run_gradient()")
+        eng = self._engine
+        if hasattr(data, "intensity"):
+            if tuple(getattr(data, "bin", (1, 1))) != (1, 1):
+                raise ValueError("gradient: the data must be unbinned patterns (Diffraction(bin=(1, 1)))")
+            data = data.intensity
+        data = np.asarray(data.detach().cpu().numpy() if hasattr(data, "detach") else data)
+        nz = len(self._slice_coords)
+        if data.shape != (self.n_probes, self.nx, self.ny):
+            raise ValueError(f"gradient: data {data.shape} does not match ({self.n_probes}, {self.nx}, {self.ny}): the unbinned, unwindowed "
+                             "pattern of every probe position")
+        if not 0 <= int(frame) < self.n_frames:
+            raise ValueError(f"gradient: frame {frame} outside [0, {self.n_frames})")
+        t0 = time.time()
+        if potential is not None:
+            V = np.asarray(potential)
+            if V.shape != (self.nx, self.ny, nz):
+                raise ValueError(f"gradient: potential {V.shape} does not match ({self.nx}, {self.ny}, {nz})")
+            eng.upload_potential(np.ascontiguousarray(np.moveaxis(V, 2, 0), dtype=np.float32))
+        else:
+            self._build(int(frame), 1)
+        eng.adjoint_reset()
+        loss = np.zeros(self.n_probes, dtype=np.float64)
+        probe = np.zeros((self.n_probes, self.nx, self.ny), dtype=np.complex64) if grad.probe else None
+        for p0, real, xy in self._probe_batches():
+            self._set_probes(xy)
+            l, pg = eng.adjoint_add(data[p0:p0 + real], B=real, probe=grad.probe)
+            loss[p0:p0 + real] = l
+            if probe is not None:
+                probe[p0:p0 + real] = pg
+        g = np.ascontiguousarray(np.moveaxis(eng.adjoint_download(), 0, 2))
+        self.elapsed = time.time() - t0
+        return GradientData(potential=g, loss=loss, sigma=interaction_sigma(self.voltage_eV), xs=self.xs, ys=self.ys, zs=self._slice_coords,
+                            probe=probe, kind=grad.loss, frame=int(frame), probe_positions=self.probe_positions)
 
     def run_images(self):
         """Frame-averaged images behind the objective lens (HRTEM, focal series), for every probe: probe batches outside, frame

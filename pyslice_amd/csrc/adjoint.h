@@ -1,0 +1,174 @@
+// The slice loop backwards (pyslice_amd/adjoint.py is the definition): for a data-fit loss L of the exit
+// patterns I = |Psi|^2 against measured patterns D, the derivative with respect to the slice potentials,
+//     dL/dV_s(r) = 2 sigma sum_p Im( g_p,s(r) conj(phi_p,s(r)) ),     phi_p,s = t_s psi_p,s,
+// with the adjoint wave g: g = N ifft2(G) at the exit, G = dL/dPsi* the residual, then per slice g <- conj(t_s) g and, for s > 0,
+// g <- ifft2(conj(P) fft2 g).  The kernels here: the residual pass over the exit spectra, the per-slice step, and the conjugate
+// propagator between the two transforms of fft2_inplace.  The waves psi_s are the forward loop's, kept by its store hook.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace msl {
+
+enum AdjointLoss { ADJ_OFF = 0, ADJ_AMPLITUDE = 1, ADJ_INTENSITY = 2, ADJ_POISSON = 3 };
+
+constexpr int ADJ_RES_PER = 4, ADJ_RES_TILE = 256 * ADJ_RES_PER;       // pixels per lane and per tile of the residual pass
+constexpr int ADJ_SL = 2, ADJ_TILE = 256 * ADJ_SL;                     // pixel pairs per lane and per tile of the step
+
+// The residual pass.  spec: (B, nx, pitch) c64, the exit spectra Psi in the transform's own order, rewritten in place with G; D:
+// (B, nx, ny) f32 and w: (nx, ny) f32 or null, both in the detector's layout (fftshifted: detector pixel i holds frequency index
+// (i - n / 2) mod n), which the index maps -- no shift pass.  A workgroup owns tile blockIdx.x of the nx * ny pixels of image
+// blockIdx.y; the loss terms are formed and summed in float64 (lane, wave by shuffles, the four waves through the LDS in wave
+// order) and thread 0 stores part[tile * B + image].  No atomics: the same input gives the same bits.
+template <int LOSS>
+__global__ void __launch_bounds__(256) adjoint_residual_kernel(float2* __restrict__ spec, const float* __restrict__ D, const float* __restrict__ w,
+                                                               int nx, int ny, int pitch, int B, float eps, double* __restrict__ part) {
+    __shared__ double lds[4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int p = blockIdx.y;
+    const long long npix = (long long)nx * ny;
+    float2* img = spec + (long long)p * nx * pitch;
+    const float* Dp = D + (long long)p * npix;
+    const float sqrt_eps = sqrtf(eps);
+    double loss = 0.0;
+#pragma unroll
+    for (int s = 0; s < ADJ_RES_PER; ++s) {
+        const long long q = (long long)blockIdx.x * ADJ_RES_TILE + (long long)s * 256 + threadIdx.x;
+        if (q >= npix) continue;
+        const int x = (int)(q / ny), y = (int)(q - (long long)x * ny);
+        int xs = x + nx / 2, ys = y + ny / 2;               // the detector pixel of frequency index (x, y)
+        if (xs >= nx) xs -= nx;
+        if (ys >= ny) ys -= ny;
+        const long long k = (long long)xs * ny + ys;
+        const float d = Dp[k], wk = w ? w[k] : 1.f;
+        const float2 v = img[(long long)x * pitch + y];
+        const float I = v.x * v.x + v.y * v.y;
+        float f;                                            // G = f Psi
+        if constexpr (LOSS == ADJ_AMPLITUDE) {
+            const float a = sqrtf(I), sd = sqrtf(d);
+            f = wk * (1.f - sd / fmaxf(a, sqrt_eps));
+            const double r = (double)a - (double)sd;
+            loss += (double)wk * r * r;
+        } else if constexpr (LOSS == ADJ_INTENSITY) {
+            f = wk * (I - d);
+            const double r = (double)I - (double)d;
+            loss += 0.5 * (double)wk * r * r;
+        } else {
+            f = wk * (1.f - d / (I + eps));
+            loss += (double)wk * ((double)I - (double)d * log((double)I + (double)eps));
+        }
+        img[(long long)x * pitch + y] = make_float2(f * v.x, f * v.y);
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) loss += __shfl_xor(loss, o, 64);
+    if (lane == 0) lds[wave] = loss;
+    __syncthreads();
+    if (threadIdx.x == 0) part[(long long)blockIdx.x * B + p] = ((lds[0] + lds[1]) + lds[2]) + lds[3];
+}
+
+// The step of slice s.  g: (B, nx, pitch) c64, the adjoint waves behind slice s, rewritten with conj(t_s) g; psi: (B, nx, pitch) c64,
+// the waves psi_s arriving at the slice; t: (nx, ny) c64, t_s; grad: (nx, ny) float64, row s of the accumulator.  The pixels of an
+// image are taken in pairs along y as slice_sums_kernel takes them (ppr = (ny + 1) / 2 pairs per row; the second pixel of the last
+// pair of an odd row does not exist): a workgroup owns tile blockIdx.x, loads t_s of its pairs once into registers and streams all B
+// images of g and psi through them with the next image's loads in flight.  Per image phi = t psi, Im(g conj phi) is added into the
+// lane's f32 sum in image order, and conj(t) g is stored.  At the end the lane adds 2 sigma x its sums to its pixels of grad: a plain
+// load, add and store -- a pixel has one owner and the batches are serial on the stream, so no atomics and the same bits every run.
+// VEC: pitch even and g, psi on 16 bytes -- one 16-byte access per pair (an odd row's last pair loads its pad pixel and drops it,
+// and stores 8 bytes); else 8-byte accesses.
+template <bool VEC>
+__global__ void __launch_bounds__(256) adjoint_step_kernel(float2* __restrict__ g, const float2* __restrict__ psi, const float2* __restrict__ t,
+                                                           int nx, int ny, int pitch, int B, double two_sigma, double* __restrict__ grad) {
+    constexpr int SL = ADJ_SL;
+    const int ppr = (ny + 1) >> 1;
+    const long long pairs = (long long)nx * ppr;
+    const long long image_stride = (long long)nx * pitch;
+
+    long long off[SL];                  // element offset of the pair inside an image, -1: no such pair
+    long long pix[SL];                  // its first pixel in the dense (nx, ny) images
+    bool two[SL];                       // the pair has its second pixel
+    float4 tt[SL];
+    float acc[SL][2];
+#pragma unroll
+    for (int s = 0; s < SL; ++s) {
+        const long long q = (long long)blockIdx.x * ADJ_TILE + (long long)s * 256 + threadIdx.x;
+        off[s] = -1; pix[s] = 0; two[s] = false;
+        tt[s] = make_float4(0.f, 0.f, 0.f, 0.f);
+        acc[s][0] = acc[s][1] = 0.f;
+        if (q < pairs) {
+            const int x = (int)(q / ppr), y = 2 * (int)(q - (long long)x * ppr);
+            off[s] = (long long)x * pitch + y;
+            pix[s] = (long long)x * ny + y;
+            two[s] = y + 1 < ny;
+            const float2 a = t[pix[s]];
+            tt[s].x = a.x; tt[s].y = a.y;
+            if (two[s]) { const float2 b = t[pix[s] + 1]; tt[s].z = b.x; tt[s].w = b.y; }
+        }
+    }
+
+    auto load = [&](const float2* img, float4 (&v)[SL]) {
+#pragma unroll
+        for (int s = 0; s < SL; ++s) {
+            v[s] = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (off[s] < 0) continue;
+            if constexpr (VEC) {
+                const float4 r = *reinterpret_cast<const float4*>(img + off[s]);     // (a pad pixel behind an odd row is read and dropped)
+                v[s].x = r.x; v[s].y = r.y;
+                if (two[s]) { v[s].z = r.z; v[s].w = r.w; }
+            } else {
+                const float2 a = img[off[s]];
+                v[s].x = a.x; v[s].y = a.y;
+                if (two[s]) { const float2 b = img[off[s] + 1]; v[s].z = b.x; v[s].w = b.y; }
+            }
+        }
+    };
+
+    float4 gn[SL], pn[SL];
+    if (B > 0) { load(g, gn); load(psi, pn); }
+    for (int p = 0; p < B; ++p) {
+        float4 gv[SL], pv[SL];
+#pragma unroll
+        for (int s = 0; s < SL; ++s) { gv[s] = gn[s]; pv[s] = pn[s]; }
+        if (p + 1 < B) { load(g + (long long)(p + 1) * image_stride, gn); load(psi + (long long)(p + 1) * image_stride, pn); }
+        float2* out = g + (long long)p * image_stride;
+#pragma unroll
+        for (int s = 0; s < SL; ++s) {
+            if (off[s] < 0) continue;
+            // phi = t psi; Im(g conj phi) = g.y phi.x - g.x phi.y; g <- conj(t) g
+            const float f0x = tt[s].x * pv[s].x - tt[s].y * pv[s].y, f0y = tt[s].x * pv[s].y + tt[s].y * pv[s].x;
+            const float f1x = tt[s].z * pv[s].z - tt[s].w * pv[s].w, f1y = tt[s].z * pv[s].w + tt[s].w * pv[s].z;
+            acc[s][0] += gv[s].y * f0x - gv[s].x * f0y;
+            acc[s][1] += gv[s].w * f1x - gv[s].z * f1y;
+            const float o0x = tt[s].x * gv[s].x + tt[s].y * gv[s].y, o0y = tt[s].x * gv[s].y - tt[s].y * gv[s].x;
+            const float o1x = tt[s].z * gv[s].z + tt[s].w * gv[s].w, o1y = tt[s].z * gv[s].w - tt[s].w * gv[s].z;
+            if (VEC && two[s]) {
+                *reinterpret_cast<float4*>(out + off[s]) = make_float4(o0x, o0y, o1x, o1y);
+            } else {
+                out[off[s]] = make_float2(o0x, o0y);
+                if (two[s]) out[off[s] + 1] = make_float2(o1x, o1y);
+            }
+        }
+    }
+#pragma unroll
+    for (int s = 0; s < SL; ++s) {
+        if (off[s] < 0) continue;
+        grad[pix[s]] = grad[pix[s]] + two_sigma * (double)acc[s][0];
+        if (two[s]) grad[pix[s] + 1] = grad[pix[s] + 1] + two_sigma * (double)acc[s][1];
+    }
+}
+
+// g(kx, ky) <- conj(px[kx] py[ky]) g(kx, ky) over B images (nx, pitch) between fft2_inplace(+1) and fft2_inplace(-1): px and py are the
+// handle's own propagator tables, which carry its tilt and the 1 / nx and 1 / ny of the inverse transform
+__global__ void __launch_bounds__(256) adjoint_conjprop_kernel(float2* __restrict__ g, const float2* __restrict__ px, const float2* __restrict__ py,
+                                                               int nx, int ny, int pitch, long long total) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    const long long row = i / ny;
+    const int y = (int)(i - row * ny), x = (int)(row % nx);
+    const float2 a = px[x], b = py[y];
+    const float2 c = make_float2(a.x * b.x - a.y * b.y, -(a.x * b.y + a.y * b.x));      // conj(px py)
+    float2* q = g + row * pitch + y;
+    const float2 v = *q;
+    *q = make_float2(c.x * v.x - c.y * v.y, c.x * v.y + c.y * v.x);
+}
+
+}  // namespace msl

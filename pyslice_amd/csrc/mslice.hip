@@ -23,6 +23,7 @@
 #include "tds.h"
 #include "ionization.h"
 #include "slice_sums.h"
+#include "adjoint.h"
 #include "thermal.h"
 #include "phonons.h"
 #include "reduce.h"
@@ -310,6 +311,16 @@ struct msl_handle {
     double ion_width[ION_MAX] = {0}, ion_cross[ION_MAX] = {0};
     DevBuf<float> ion_tab, ion_W, ion_ones, ion_part;
     DevBuf<double> ion_acc, ion_norm;
+    // gradients (msl_set_adjoint, adjoint.h): the loss (AdjointLoss) with its epsilon, the detector weight
+    // (nx, ny) in the detector's layout (empty: none), the data of one probe batch (adj_P, nx, ny), the waves psi_1 .. psi_nz-1 of the
+    // forward loop (nz - 1, adj_P, nx, pitch) -- psi_0 is psi0 --, the float64 accumulator (nz, nx, ny), the slab of the loss
+    // partials and the losses of a batch.  While adj_on the handle is on the two-pass loop (set_loop_mode); msl_adjoint_add runs
+    // slice_loop with the split row step and the store between its halves
+    int adj_on = ADJ_OFF, adj_P = 0;
+    float adj_eps = 0.f;
+    DevBuf<float> adj_w, adj_D;
+    DevBuf<float2> adj_stack;
+    DevBuf<double> adj_grad, adj_part, adj_loss;
     // frozen phonons (msl_set_structure): the base structure resident on the device -- positions (n, 3), widths, Z and the species
     // maps that stage_atoms sends per call -- with the host's copy of the maps and the axes; msl_build_thermal generates the
     // positions of any configuration from it (thermal_positions_kernel), so no per-frame array and no caller pointer is kept
@@ -1389,9 +1400,18 @@ int slice_sums_of_slice(msl_handle* h, const float2* psi, int P, int z, double* 
     const size_t npix = (size_t)h->cfg.nx * h->cfg.ny;
     return slice_sums_queue<S>(h, psi, P, S::weights(h) + (size_t)z * npix, npix * h->cfg.nz, S::n(h), dst, reps);
 }
+// The store of msl_adjoint_add, queued where the reduction of a signal is: psi_z into slab z - 1 of the stack (psi_0 is psi0, which the
+// loop leaves alone)
+int adjoint_store_hook(msl_handle* h, int P, int z) {
+    if (z == 0) return MSL_OK;
+    const size_t slab = (size_t)P * h->cfg.nx * h->pitch;
+    HIPCHK(h, hipMemcpyAsync(h->adj_stack + (size_t)(z - 1) * slab, h->psi, slab * sizeof(float2), hipMemcpyDeviceToDevice, h->stream));
+    return mark_launch(h, K_OTHER);
+}
 // What the two-pass loop queues between the two launches of a slice's row step, where psi holds the wave arriving at slice z in real
 // space: the sums of the active signal, into row z of its (nz, P, n) sums
 int slice_sums_hook(msl_handle* h, int P, int z) {
+    if (h->adj_on) return adjoint_store_hook(h, P, z);     // (msl_adjoint_add's loop: no signal is set next to the adjoint)
     return h->tds_on ? slice_sums_of_slice<TdsSignal>(h, h->psi, P, z, h->tds_acc + (size_t)z * P * h->tds_n)
                      : slice_sums_of_slice<IonSignal>(h, h->psi, P, z, h->ion_acc + (size_t)z * P * h->ion_n);
 }
@@ -1440,12 +1460,16 @@ int slice_sums_reduce(msl_handle* h, const char* who, int32_t slice, int32_t rep
 // kernels -- the inverse y-transform alone, as fft2_inplace issues it, then t_s, the forward transform and P_y -- so that between them
 // psi holds psi_s in real space at its true scale, where the reduction is queued (at s = 0 psi is psi0).  Every elastic launch computes
 // what the single launch computes; the per-slice sums go to tds_acc (nz, P, tds_n) or ion_acc (nz, P, ion_n), and for the ionisation
-// signal the norms of the incident waves, the same kernel against an image of ones, to ion_norm.  `sums` is run_loop's alone: every
+// signal the norms of the incident waves, the same kernel against an image of ones, to ion_norm.  `signal` is run_loop's alone: every
 // other caller (msl_smatrix_build) runs the plain loop and leaves the sums of the last probe loop alone, whatever the handle's setting.
-int slice_loop(msl_handle* h, int fused_slot, int groups, int first_group, bool sums = false) {
+// `store` is msl_adjoint_add's alone: the same split row step, where the hook then copies psi into the wave stack (never with `signal`).
+int slice_loop(msl_handle* h, int fused_slot, int groups, int first_group, bool signal = false, bool store = false) {
     const msl_config& c = h->cfg;
-    const bool tds = sums && h->tds_on, ion = sums && !tds;
-    if (sums && (groups != 1 || h->onepass))
+    const bool tds = signal && h->tds_on, ion = signal && !tds;
+    const bool sums = signal || store;                      // the split row step with the hook between its halves
+    if (store && (signal || !h->adj_on || groups != 1 || h->onepass))
+        return fail(h, MSL_ERR_STATE, "adjoint: the slice loop needs one frame per launch on the two-pass loop");
+    if (signal && (groups != 1 || h->onepass))
         return fail(h, MSL_ERR_STATE, "%s: the slice loop needs one frame per launch on the two-pass loop", ion ? "ionization" : "tds");
     if (tds && !TdsSignal::built(h)) return fail(h, MSL_ERR_STATE, "tds: no weight stack (build the potential after msl_set_tds)");
     if (ion && !IonSignal::built(h))
@@ -1455,7 +1479,7 @@ int slice_loop(msl_handle* h, int fused_slot, int groups, int first_group, bool 
     const size_t npix = (size_t)c.nx * c.ny;
     const size_t toff = (size_t)first_group * c.nz * npix;
     int rc;
-    if (sums && (rc = (ion ? h->ion_acc : h->tds_acc).reserve(h, (size_t)nz * P * (ion ? h->ion_n : h->tds_n)))) return rc;
+    if (signal && (rc = (ion ? h->ion_acc : h->tds_acc).reserve(h, (size_t)nz * P * (ion ? h->ion_n : h->tds_n)))) return rc;
     if (ion && (rc = h->ion_norm.reserve(h, (size_t)P))) return rc;
     HIPCHK(h, hipMemcpyAsync(h->psi, h->psi0, (size_t)P * c.nx * h->pitch * sizeof(float2), hipMemcpyDeviceToDevice, h->stream));
     if (ion && (rc = slice_sums_queue<IonSignal>(h, h->psi, P, h->ion_ones, npix, 1, h->ion_norm))) return rc;     // (ahead of the timed launches)
@@ -1505,8 +1529,8 @@ int slice_loop(msl_handle* h, int fused_slot, int groups, int first_group, bool 
         // epilogue: fft along x, fftshift both axes, scatter into (P, T_local, nx, ny)
         if ((rc = epilogue_x_pass(h, fused_slot, groups))) return rc;
     }
-    if (!sums) {
-        count_slice_loop(h, P, groups, fused, 32);
+    if (!signal) {
+        count_slice_loop(h, P, groups, fused, store ? 32 + 16 + 16 : 32);      // (the split row step, and the copy into the stack)
         return MSL_OK;
     }
     (ion ? h->ion_have : h->tds_have) = true;
@@ -1514,6 +1538,72 @@ int slice_loop(msl_handle* h, int fused_slot, int groups, int first_group, bool 
     count_slice_loop(h, P, groups, fused, 32 + 16 + 8);
     if (!ion) h->ctr.algorithmic_bytes += (uint64_t)nz * h->tds_n * 4ull * npix;
     else h->ctr.algorithmic_bytes += (uint64_t)nz * h->ion_n * 4ull * npix + 8ull * P * npix;      // (and the norm's read of psi0)
+    return MSL_OK;
+}
+
+// ---- gradients: the slice loop backwards; adjoint.h ----
+// The step of slice s for the first B images of g (the work buffer's layout), queued: psi_s from the stack (psi0 at s = 0), t_s of the
+// current batch slot, row s of the accumulator
+int adjoint_step_launch(msl_handle* h, float2* g, int s, int B) {
+    const msl_config& c = h->cfg;
+    const size_t npix = (size_t)c.nx * c.ny, slab = (size_t)c.n_probes * c.nx * h->pitch;
+    const long long pairs = (long long)c.nx * ((c.ny + 1) / 2), step_tiles = (pairs + ADJ_TILE - 1) / ADJ_TILE;
+    const bool vec = (h->pitch % 2 == 0) && (((uintptr_t)g & 15) == 0) && (((uintptr_t)h->psi0.p & 15) == 0) && (((uintptr_t)h->adj_stack.p & 15) == 0);
+    const float2* psi_s = s == 0 ? h->psi0.p : h->adj_stack.p + (size_t)(s - 1) * slab;
+    const float2* t = h->trans + ((size_t)h->cur_batch * c.nz + s) * npix;
+    double* grad = h->adj_grad + (size_t)s * npix;
+    if (vec) hipLaunchKernelGGL(adjoint_step_kernel<true>, dim3((unsigned)step_tiles), dim3(256), 0, h->stream, g, psi_s, t, c.nx, c.ny, h->pitch, B, 2.0 * c.sigma, grad);
+    else hipLaunchKernelGGL(adjoint_step_kernel<false>, dim3((unsigned)step_tiles), dim3(256), 0, h->stream, g, psi_s, t, c.nx, c.ny, h->pitch, B, 2.0 * c.sigma, grad);
+    HIPCHK(h, hipGetLastError());
+    return MSL_OK;
+}
+
+// One probe batch: the forward loop with the store, the exit FFT, the residual pass against the data D (B, nx, ny) on the host, and the
+// backward loop, which adds the batch's share into the accumulator.  loss_out (B) float64; probe_grad (B, nx, ny) c64 or null.  Waits
+// for the stream.
+int adjoint_add(msl_handle* h, const float* data, int B, double* loss_out, float2* probe_grad) {
+    const msl_config& c = h->cfg;
+    const int P = c.n_probes, nz = c.nz;
+    const size_t npix = (size_t)c.nx * c.ny;
+    const long long res_tiles = ((long long)npix + ADJ_RES_TILE - 1) / ADJ_RES_TILE;
+    const long long pairs = (long long)c.nx * ((c.ny + 1) / 2), step_tiles = (pairs + ADJ_TILE - 1) / ADJ_TILE;
+    if (res_tiles > 0x7fffffffLL || step_tiles > 0x7fffffffLL || B > 65535) return fail(h, MSL_ERR_UNSUPPORTED, "msl_adjoint_add: too many tiles");
+    int rc;
+    if ((rc = h->adj_part.reserve(h, (size_t)res_tiles * P))) return rc;
+    HIPCHK(h, hipMemcpyAsync(h->adj_D, data, (size_t)B * npix * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    if ((rc = slice_loop(h, -1, 1, h->cur_batch, false, true))) return rc;
+    h->have_exit = false;                                   // psi ends as the probe gradient
+    float2* g = h->psi;
+    if ((rc = fft2_inplace(h, g, B, +1, 1.0f, h->pitch))) return rc;
+    const dim3 res_grid((unsigned)res_tiles, (unsigned)B);
+    const float* w = h->adj_w;
+    switch (h->adj_on) {
+        case ADJ_AMPLITUDE: hipLaunchKernelGGL(adjoint_residual_kernel<ADJ_AMPLITUDE>, res_grid, dim3(256), 0, h->stream, g, (const float*)h->adj_D, w, c.nx, c.ny, h->pitch, B, h->adj_eps, h->adj_part.p); break;
+        case ADJ_INTENSITY: hipLaunchKernelGGL(adjoint_residual_kernel<ADJ_INTENSITY>, res_grid, dim3(256), 0, h->stream, g, (const float*)h->adj_D, w, c.nx, c.ny, h->pitch, B, h->adj_eps, h->adj_part.p); break;
+        default: hipLaunchKernelGGL(adjoint_residual_kernel<ADJ_POISSON>, res_grid, dim3(256), 0, h->stream, g, (const float*)h->adj_D, w, c.nx, c.ny, h->pitch, B, h->adj_eps, h->adj_part.p); break;
+    }
+    hipLaunchKernelGGL((slice_sums_finish_kernel<double, 1>), dim3((unsigned)((B + 255) / 256)), dim3(256), 0, h->stream, (const double*)h->adj_part.p,
+                       res_tiles, B, 1, h->adj_loss.p);
+    HIPCHK(h, hipGetLastError());
+    if ((rc = fft2_inplace(h, g, B, -1, 1.0f, h->pitch))) return rc;     // g = N ifft2(G): the adjoint of the unnormalised transform
+    const long long total = (long long)B * c.nx * c.ny;
+    for (int s = nz - 1; s >= 0; --s) {
+        if ((rc = adjoint_step_launch(h, g, s, B))) return rc;
+        if (s == 0) break;
+        if ((rc = fft2_inplace(h, g, B, +1, 1.0f, h->pitch))) return rc;
+        hipLaunchKernelGGL(adjoint_conjprop_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, g, (const float2*)h->pxt.p,
+                           (const float2*)h->pyt.p, c.nx, c.ny, h->pitch, total);
+        HIPCHK(h, hipGetLastError());
+        if ((rc = fft2_inplace(h, g, B, -1, 1.0f, h->pitch))) return rc;
+    }
+    // per image: the two exit transforms (64 B per pixel), the residual (16 + 4), per slice the step (24) and per propagation the
+    // product and its two transforms (16 + 64); per call t_s and the accumulator (8 + 16 per pixel and slice)
+    h->ctr.algorithmic_bytes += (uint64_t)B * npix * (84ull + 24ull * nz + 80ull * (nz - 1)) + 24ull * nz * npix;
+    HIPCHK(h, hipMemcpyAsync(loss_out, h->adj_loss, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (probe_grad)
+        HIPCHK(h, hipMemcpy2DAsync(probe_grad, (size_t)c.ny * sizeof(float2), g, (size_t)h->pitch * sizeof(float2), (size_t)c.ny * sizeof(float2),
+                                   (size_t)B * c.nx, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
     return MSL_OK;
 }
 
@@ -2303,10 +2393,10 @@ bool tilt_needs_two_pass(const msl_handle* h, double tan_x, double tan_y) {
     return (tan_x != 0.0 && even_only(h->opx)) || (tan_y != 0.0 && even_only(h->opy));
 }
 
-// The loop a handle may run under the tangents (tan_x, tan_y): the one msl_create planned, unless the TDS signal, the ionisation signal
-// (slice_loop takes them on the two-pass loop only) or the tilt asks for the two-pass loop
+// The loop a handle may run under the tangents (tan_x, tan_y): the one msl_create planned, unless the TDS signal, the ionisation signal,
+// the adjoint (slice_loop takes them on the two-pass loop only) or the tilt asks for the two-pass loop
 bool allowed_onepass(const msl_handle* h, double tan_x, double tan_y) {
-    return h->onepass_planned && !h->tds_on && !h->ion_on && !tilt_needs_two_pass(h, tan_x, tan_y);
+    return h->onepass_planned && !h->tds_on && !h->ion_on && !h->adj_on && !tilt_needs_two_pass(h, tan_x, tan_y);
 }
 
 // Switch a handle planned for the one-pass loop to the two-pass loop and back, on the stream.  The two-pass loop and the potential
@@ -2395,6 +2485,14 @@ int ion_clear(msl_handle* h) {
     h->ion_on = h->ion_built = h->ion_have = false;
     h->ion_n = h->ion_nsp = 0;
     h->ion_tab.release(); h->ion_W.release(); h->ion_ones.release(); h->ion_part.release(); h->ion_acc.release(); h->ion_norm.release();
+    return set_loop_mode(h, allowed_onepass(h, h->set.tilt_tan[0], h->set.tilt_tan[1]));
+}
+
+// The adjoint off: its buffers freed, and the handle back on the loop its tilt allows
+int adj_clear(msl_handle* h) {
+    if (!h->adj_on) return MSL_OK;
+    h->adj_on = ADJ_OFF; h->adj_P = 0;
+    h->adj_w.release(); h->adj_D.release(); h->adj_stack.release(); h->adj_grad.release(); h->adj_part.release(); h->adj_loss.release();
     return set_loop_mode(h, allowed_onepass(h, h->set.tilt_tan[0], h->set.tilt_tan[1]));
 }
 
@@ -2513,6 +2611,7 @@ int msl_set_tds(msl_handle* h, const uint16_t* member_bits, int32_t n_det) {
         return fail(h, MSL_ERR_STATE, "msl_set_tds: no absorption (call msl_set_absorption(.., absorb != 0) first)");
     if (!clear && h->FB > 1) return fail(h, MSL_ERR_UNSUPPORTED, "msl_set_tds: a frame batch of %d (the weight stack is that of one frame)", h->FB);
     if (!clear && h->ion_on) return fail(h, MSL_ERR_STATE, "msl_set_tds: msl_set_ionization is set (one per-slice reduction per handle)");
+    if (!clear && h->adj_on) return fail(h, MSL_ERR_STATE, "msl_set_tds: msl_set_adjoint is set (its store takes the place of the reduction)");
     HIPCHK(h, hipSetDevice(h->cfg.device));
     HIPCHK(h, hipStreamSynchronize(h->stream));          // a queued build or loop still reads the tables and the stacks
     h->ff_n = 0;                                         // as msl_set_absorption: the next build makes the tables again
@@ -2545,6 +2644,7 @@ int msl_set_ionization(msl_handle* h, int32_t n, const int32_t* Z, const double*
     if (!clear && h->FB > 1)
         return fail(h, MSL_ERR_UNSUPPORTED, "msl_set_ionization: a frame batch of %d (the weight stack is that of one frame)", h->FB);
     if (!clear && h->tds_on) return fail(h, MSL_ERR_STATE, "msl_set_ionization: msl_set_tds is set (one per-slice reduction per handle)");
+    if (!clear && h->adj_on) return fail(h, MSL_ERR_STATE, "msl_set_ionization: msl_set_adjoint is set (its store takes the place of the reduction)");
     if (!clear && h->fin_R > 0)
         return fail(h, MSL_ERR_UNSUPPORTED, "msl_set_ionization: the weight stack is not built under finite projection (msl_set_projection)");
     HIPCHK(h, hipSetDevice(h->cfg.device));
@@ -2564,6 +2664,108 @@ int msl_set_ionization(msl_handle* h, int32_t n, const int32_t* Z, const double*
     rc = set_loop_mode(h, allowed_onepass(h, h->set.tilt_tan[0], h->set.tilt_tan[1]));
     if (rc) { h->ion_on = false; h->ion_n = 0; h->ion_ones.release(); }     // a refused switch: no ionisation, as after the ion_clear above
     return rc;
+}
+
+// gradients
+int msl_set_adjoint(msl_handle* h, int32_t loss_kind, double epsilon, const float* weight) {
+    if (!h) return fail(h, MSL_ERR_INVALID, "msl_set_adjoint: null handle");
+    const bool clear = loss_kind == ADJ_OFF;
+    if (!clear && (loss_kind < ADJ_AMPLITUDE || loss_kind > ADJ_POISSON))
+        return fail(h, MSL_ERR_INVALID, "msl_set_adjoint: loss %d outside [0, %d]", loss_kind, (int)ADJ_POISSON);
+    // (the kernels hold epsilon in float32: one that rounds to zero there would divide by zero where |Psi| = 0)
+    if (!clear && (!std::isfinite(epsilon) || !((float)epsilon > 0.f) || !std::isfinite((float)epsilon)))
+        return fail(h, MSL_ERR_INVALID, "msl_set_adjoint: epsilon %g is not a finite float32 number > 0", epsilon);
+    if (clear && !h->adj_on) return MSL_OK;                 // never set: the handle stays what it is
+    const msl_config& c = h->cfg;
+    if (!clear) {
+        if (h->set.bl_on) return fail(h, MSL_ERR_UNSUPPORTED, "msl_set_adjoint: a band limit is set (its low-pass of t has no adjoint here)");
+        if (h->abs_on) return fail(h, MSL_ERR_UNSUPPORTED, "msl_set_adjoint: an absorptive potential is set (t is not exp(i sigma V))");
+        if (h->FB > 1) return fail(h, MSL_ERR_UNSUPPORTED, "msl_set_adjoint: a frame batch of %d (the wave stack is that of one frame)", h->FB);
+        if (n_taps(h) > 0 || h->lr_on) return fail(h, MSL_ERR_UNSUPPORTED, "msl_set_adjoint: layers or a layer reduction are set");
+        if (h->tds_on || h->ion_on) return fail(h, MSL_ERR_STATE, "msl_set_adjoint: a per-slice reduction is set (msl_set_tds / msl_set_ionization)");
+    }
+    HIPCHK(h, hipSetDevice(c.device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));          // a queued loop still reads the stacks
+    int rc = adj_clear(h);
+    if (rc || clear) return rc;
+    const size_t npix = (size_t)c.nx * c.ny, P = (size_t)c.n_probes, slab = P * c.nx * h->pitch;
+    const size_t want = (size_t)(c.nz - 1) * slab * sizeof(float2) + (size_t)c.nz * npix * sizeof(double) + P * npix * sizeof(float);
+    if ((rc = h->adj_stack.alloc(h, (size_t)(c.nz - 1) * slab)) || (rc = h->adj_grad.alloc(h, (size_t)c.nz * npix)) ||
+        (rc = h->adj_D.alloc(h, P * npix)) || (rc = h->adj_loss.alloc(h, P)) || (weight && (rc = h->adj_w.alloc(h, npix)))) {
+        const std::string why = h->err;
+        h->adj_on = ADJ_AMPLITUDE;                          // (so that adj_clear frees what was allocated)
+        (void)adj_clear(h);
+        return fail(h, rc, "msl_set_adjoint: the wave stack, the accumulator and the data of %d probes want %zu bytes (a smaller probe batch makes "
+                           "the stack fit): %s", c.n_probes, want, why.c_str());
+    }
+    hipError_t e = weight ? hipMemcpy(h->adj_w, weight, npix * sizeof(float), hipMemcpyHostToDevice) : hipSuccess;
+    if (e == hipSuccess) e = hipMemsetAsync(h->adj_grad, 0, (size_t)c.nz * npix * sizeof(double), h->stream);
+    if (e != hipSuccess) {                                  // nothing stays allocated behind a failed set-up
+        h->adj_on = ADJ_AMPLITUDE;
+        (void)adj_clear(h);
+        return fail(h, MSL_ERR_HIP, "msl_set_adjoint: the weight copy or the accumulator reset failed: %s", hipGetErrorString(e));
+    }
+    h->adj_eps = (float)epsilon;
+    h->adj_P = c.n_probes;
+    h->adj_on = loss_kind;
+    rc = set_loop_mode(h, allowed_onepass(h, h->set.tilt_tan[0], h->set.tilt_tan[1]));
+    if (rc) {                                               // a refused switch: no adjoint, as after the adj_clear above
+        h->adj_on = ADJ_OFF; h->adj_P = 0;
+        h->adj_w.release(); h->adj_D.release(); h->adj_stack.release(); h->adj_grad.release(); h->adj_loss.release();
+    }
+    return rc;
+}
+
+int msl_adjoint_reset(msl_handle* h) {
+    if (!h) return fail(h, MSL_ERR_INVALID, "msl_adjoint_reset: null handle");
+    if (!h->adj_on) return fail(h, MSL_ERR_STATE, "msl_adjoint_reset: no adjoint (msl_set_adjoint)");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    HIPCHK(h, hipMemsetAsync(h->adj_grad, 0, h->adj_grad.n * sizeof(double), h->stream));
+    return MSL_OK;
+}
+
+int msl_adjoint_add(msl_handle* h, const float* data, int32_t B, double* loss_out, void* probe_grad) {
+    if (!h) return fail(h, MSL_ERR_INVALID, "msl_adjoint_add: null handle");
+    if (!h->adj_on) return fail(h, MSL_ERR_STATE, "msl_adjoint_add: no adjoint (msl_set_adjoint)");
+    if (!data || !loss_out) return fail(h, MSL_ERR_INVALID, "msl_adjoint_add: null argument");
+    if (h->adj_P != h->cfg.n_probes)
+        return fail(h, MSL_ERR_STATE, "msl_adjoint_add: the stack holds %d probes, the handle has %d (msl_set_adjoint after msl_resize_probes)", h->adj_P, h->cfg.n_probes);
+    if (B < 1 || B > h->cfg.n_probes) return fail(h, MSL_ERR_INVALID, "msl_adjoint_add: %d probes, the handle has %d", B, h->cfg.n_probes);
+    if (h->set.bl_on || h->abs_on || h->abs_built || n_taps(h) > 0 || h->lr_on)
+        return fail(h, MSL_ERR_UNSUPPORTED, "msl_adjoint_add: a band limit, an absorptive potential or layers were set after msl_set_adjoint");
+    if (!h->have_probes) return fail(h, MSL_ERR_STATE, "msl_adjoint_add: no probes (msl_set_probes / msl_upload_probes)");
+    if (!h->have_potential) return fail(h, MSL_ERR_STATE, "msl_adjoint_add: no potential (msl_build_potential / msl_upload_potential)");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    const int rc = adjoint_add(h, data, B, loss_out, (float2*)probe_grad);
+    if (rc) (void)hipStreamSynchronize(h->stream);
+    return rc;
+}
+
+int msl_adjoint_step_time(msl_handle* h, int32_t slice, int32_t reps, double* ms_step) {
+    if (!h) return fail(h, MSL_ERR_INVALID, "msl_adjoint_step_time: null handle");
+    if (!h->adj_on || h->adj_P != h->cfg.n_probes) return fail(h, MSL_ERR_STATE, "msl_adjoint_step_time: no adjoint (msl_set_adjoint)");
+    if (!h->have_probes || !h->have_potential) return fail(h, MSL_ERR_STATE, "msl_adjoint_step_time: no probes or no potential");
+    if (slice < 0 || slice >= h->cfg.nz) return fail(h, MSL_ERR_INVALID, "msl_adjoint_step_time: slice %d outside [0, %d)", slice, h->cfg.nz);
+    if (reps < 1) return fail(h, MSL_ERR_INVALID, "msl_adjoint_step_time: reps must be positive");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    h->cur = nullptr;
+    double ms = 0.0;
+    EventPair timer;
+    int rc = adjoint_step_launch(h, h->psi, slice, h->cfg.n_probes);            // one untimed launch first
+    if (rc || (rc = timer.begin(h))) return rc;
+    for (int r = 0; r < reps && rc == MSL_OK; ++r) rc = adjoint_step_launch(h, h->psi, slice, h->cfg.n_probes);
+    if (rc || (rc = timer.end(h, &ms))) { (void)hipStreamSynchronize(h->stream); return rc; }
+    if (ms_step) *ms_step = ms / reps;
+    return MSL_OK;
+}
+
+int msl_adjoint_download(msl_handle* h, double* grad) {
+    if (!h || !grad) return fail(h, MSL_ERR_INVALID, "msl_adjoint_download: null argument");
+    if (!h->adj_on) return fail(h, MSL_ERR_STATE, "msl_adjoint_download: no adjoint (msl_set_adjoint)");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    HIPCHK(h, hipMemcpyAsync(grad, h->adj_grad, h->adj_grad.n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return MSL_OK;
 }
 
 }  // extern "C"

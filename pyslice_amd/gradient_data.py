@@ -1,0 +1,38 @@
+"""GradientData: what MultisliceCalculator.run_gradient() returns (the definition is adjoint.py)."""
+from __future__ import annotations
+
+from dataclasses import dataclass
+from typing import Any, Optional
+
+import numpy as np
+
+
+@dataclass
+class GradientData:
+    """potential  (nx, ny, nz) float64: dL/dV of the total loss, in the layout of Potential.array and of run_gradient(potential=...)
+    loss       (P,) float64: the loss of every probe position
+    probe      (P, nx, ny) complex64: dL/dpsi_0* per probe with Gradient(probe=True), else None
+    sigma      the interaction constant the transmission functions were made with
+    xs, ys, zs the axes of `potential`; kind: the loss ("amplitude", "intensity", "poisson"); frame: the frame it was taken at"""
+    potential: np.ndarray
+    loss: np.ndarray
+    sigma: float
+    xs: Any = None
+    ys: Any = None
+    zs: Any = None
+    probe: Optional[np.ndarray] = None
+    kind: str = "amplitude"
+    frame: int = 0
+    probe_positions: Any = None
+
+    @property
+    def total(self) -> float:
+        """the loss summed over the probe positions"""
+        return float(np.sum(self.loss))
+
+    def descent_step(self, V, rate):
+        """V - rate * dL/dV for an estimate V (nx, ny, nz): one step of plain gradient descent, float64"""
+        V = np.asarray(V, dtype=np.float64)
+        if V.shape != self.potential.shape:
+            raise ValueError(f"descent_step: V {V.shape} does not match the gradient {self.potential.shape}")
+        return V - float(rate) * self.potential
