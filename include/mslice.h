@@ -422,6 +422,34 @@ int  msl_adjoint_add(msl_handle* h, const float* data, int32_t B, double* loss_o
 int  msl_adjoint_download(msl_handle* h, double* grad);
 int  msl_adjoint_step_time(msl_handle* h, int32_t slice, int32_t reps, double* ms_step);
 
+/* ---- gradients with respect to atom positions: the potential build backwards ----
+ * The build is V_s = Re ifft2( sum_Z f_Z sum_{a in Z, s} e^{-2 pi i (kx x_a + ky y_a)} ) / (dx^2 dy^2) on the fftfreq grid.  With
+ * Gamma_s = dL/dV_s, B_s = fft2(Gamma_s) and c = 2 pi / (nx ny dx^2 dy^2), for atom a of species Z in slice s
+ *     dL/dx_a = c sum_{kx, ky} kx f_Z(k) Im( conj(B_s(k)) e^{-2 pi i kx x_a} e^{-2 pi i ky y_a} ),     dL/dy_a: the same with ky,
+ * over the full grid (pyslice_amd/adjoint.py: position_gradient is the definition).  The derivative along the slice axis is zero (an
+ * atom is binned, not spread); an atom in no slice gets zeros.
+ * msl_adjoint_positions:  gamma == NULL takes Gamma from the accumulator of msl_adjoint_add (MSL_ERR_STATE without msl_set_adjoint);
+ *   else gamma is the caller's (nz, nx, ny) float64 dL/dV on the host, uploaded -- msl_set_adjoint is not needed then.  out: (n, 3)
+ *   float64 on the host, in the order and the axes of the positions msl_build_potential was given: columns ax1 and ax2 hold the two
+ *   components, column axs is zero.  Reads the sorted phase tables, the order, the bin starts and the form-factor tables that the
+ *   last msl_build_potential left on the device: MSL_ERR_STATE, naming the missing build, when no single-frame build is resident --
+ *   before the first build, and after msl_build_potentials of more than one frame, msl_build_thermal, msl_build_modes,
+ *   msl_upload_potential, msl_set_projection, msl_set_absorption (and what drops the potential with them: msl_set_tds,
+ *   msl_set_ionization), or a build under finite projection or absorption.  Gamma is rounded to float32, transformed by the handle's
+ *   own 2-D FFT, and position_gradient_kernel gathers at the atoms in exact float32 products with float64 sums; no atomics: the same
+ *   calls give the same bits.  Leaves the work buffer, the potential and the accumulator as they are.  Synchronous.
+ *   A build under a band limit (msl_set_bandlimit) does not count either: its V is low-passed behind the structure factor.
+ *   Device memory of its own, grown on demand and freed by msl_set_adjoint(MSL_ADJ_OFF) and msl_destroy: the images of a chunk of
+ *   slices (at most 256 MB, or one image), an uploaded gamma (8 nz nx ny bytes), the tile list and the result.
+ * msl_adjoint_positions_rows:  the rows n that msl_adjoint_positions would write now, or -1 where it would be MSL_ERR_STATE for want
+ *   of a build: what a caller sizes `out` by.
+ * msl_adjoint_positions_time:  the chain on the accumulator (conversion, transforms, kernel), once untimed and then `reps` times
+ *   between two events; ms_chain = the mean device time of one chain in ms.  For benchmarks.
+ * Not in the reference. */
+int  msl_adjoint_positions(msl_handle* h, const double* gamma, double* out);
+int64_t msl_adjoint_positions_rows(const msl_handle* h);
+int  msl_adjoint_positions_time(msl_handle* h, int32_t reps, double* ms_chain);
+
 /* TACAW: intensity[p,w,kx,ky] = | fftshift_t fft_t( Psi - <Psi>_t ) |^2 over a (B,T,npix) c64 device
  * array.  src == NULL uses the handle's own wavefunction buffer (B=P, T=T_local, npix=nx*ny) and
  * its own intensity buffer.  With src/dst given (device pointers, e.g. the output of an RCCL

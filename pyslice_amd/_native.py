@@ -54,6 +54,7 @@ EXPORTS = [
     "msl_set_projection", "msl_get_projection",
     "msl_set_probe_members", "msl_diffract_members", "msl_dose_add_members",
     "msl_set_adjoint", "msl_adjoint_reset", "msl_adjoint_add", "msl_adjoint_download", "msl_adjoint_step_time",
+    "msl_adjoint_positions", "msl_adjoint_positions_rows", "msl_adjoint_positions_time",
 ]
 DET_SIGNALS = {"intensity": 0, "amplitude": 1, "com_x": 2, "com_y": 3}      # include/mslice.h: MSL_DET_*
 MEMBERS_MAX = 128                                                          # include/mslice.h: MSL_MEMBERS_MAX
@@ -184,6 +185,9 @@ def load():
         "msl_adjoint_add": (C.c_int, [vp, vp, i32, vp, vp]),
         "msl_adjoint_download": (C.c_int, [vp, vp]),
         "msl_adjoint_step_time": (C.c_int, [vp, i32, i32, vp]),
+        "msl_adjoint_positions": (C.c_int, [vp, vp, vp]),
+        "msl_adjoint_positions_rows": (C.c_int64, [vp]),
+        "msl_adjoint_positions_time": (C.c_int, [vp, i32, vp]),
         "msl_set_ionization": (C.c_int, [vp, i32, vp, vp, vp]),
         "msl_ionization_fetch": (C.c_int, [vp, i32, vp]),
         "msl_ionization_reduce": (C.c_int, [vp, i32, i32, vp, vp]),
@@ -424,6 +428,27 @@ class Engine:
         out = np.empty((self.nz, self.nx, self.ny), dtype=np.float64)
         self._chk(self._lib.msl_adjoint_download(self._h, _ptr(out)))
         return out
+
+    def adjoint_positions(self, gamma=None):
+        """dL/dr_a of the atoms of the last build_potential, (n_atoms, 3) float64 in the caller's order and axes, the slice-axis column
+        zero (msl_adjoint_positions; the definition is adjoint.position_gradient): from gamma (nz, nx, ny) float64 = dL/dV, or from
+        the gradient accumulator with gamma=None"""
+        g = None
+        if gamma is not None:
+            g = np.ascontiguousarray(gamma, dtype=np.float64)
+            if g.shape != (self.nz, self.nx, self.ny):
+                raise ValueError(f"gamma must be ({self.nz},{self.nx},{self.ny}), got {g.shape}")
+        n = max(0, int(self._lib.msl_adjoint_positions_rows(self._h)))       # (-1: no build; the call below says which)
+        out = np.zeros((max(n, 1), 3), dtype=np.float64)                     # (the handle writes n rows)
+        self._chk(self._lib.msl_adjoint_positions(self._h, None if g is None else _ptr(g), _ptr(out)))
+        return out[:n]
+
+    def adjoint_positions_time(self, reps=1):
+        """the chain of adjoint_positions() on the accumulator alone (msl_adjoint_positions_time) -> mean device time of one of the
+        `reps` chains in ms"""
+        ms = C.c_double(0.0)
+        self._chk(self._lib.msl_adjoint_positions_time(self._h, int(reps), C.byref(ms)))
+        return float(ms.value)
 
     def set_slices(self, lo, hi):
         lo = np.ascontiguousarray(lo, dtype=np.float64)

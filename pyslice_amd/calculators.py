@@ -280,7 +280,9 @@ class MultisliceCalculator:
                    of the data-fit loss of the exit patterns with respect to the slice potentials (GradientData; adjoint.py is the
                    definition).  The probes stream in probe_batch; the forward loop keeps the wave arriving at every slice, the
                    residual and the backward loop run on the device (msl_set_adjoint / msl_adjoint_*).  With aberrations, tilt and
-                   probe_batch; every other mode: NotImplementedError("gradient: ... is not built").
+                   probe_batch; every other mode: NotImplementedError("gradient: ... is not built").  Gradient(positions=True) adds
+                   GradientData.positions, dL/dr_a per atom (msl_adjoint_positions: the potential build backwards), and
+                   run_gradient(positions=...) builds from the caller's coordinates.
           coherence a coherence.Coherence(focal_spread, focal_points, source_size, source_points): partial coherence of the probe.
                    Every scan position of run_diffraction() (plain, with Dose, with Dose + Camera), run_detectors() and run_polar()
                    is an ensemble of G = focal_points x source_points^2 member probes, member g at xy + d_g with C10 + delta_g and
@@ -1395,14 +1397,18 @@ class MultisliceCalculator:
                                               incident=incident, frames=frames, camera=camera, coherence=getattr(self, "_coherence", None),
                                               **self._layer_fields()))
 
-    def run_gradient(self, data, frame=0, potential=None):
+    def run_gradient(self, data, frame=0, potential=None, positions=None):
         """The derivative of the data-fit loss of MultisliceCalculator(gradient=Gradient(...)) with respect to the slice potentials
         (adjoint.py is the definition): per probe batch msl_adjoint_add runs the forward loop, which keeps the wave arriving at every
         slice, the residual of the exit patterns against `data` and the loop backwards, and adds into a float64 accumulator on the
         device (no atomics: repeats give the same bits; another probe_batch changes the order of the float64 sums only).
         data: (P, nx, ny) in the layout and units of DiffractionData.intensity of an unbinned, unwindowed run, or such a
         DiffractionData.  frame: the trajectory frame whose potential is built.  potential: (nx, ny, nz) -- the caller's estimate,
-        uploaded in place of the build (what an iterative reconstruction passes at every step).  -> GradientData."""
+        uploaded in place of the build (what an iterative reconstruction passes at every step).  positions: (n_atoms, 3) -- the
+        caller's current coordinates, built in place of the trajectory frame (what a structure refinement passes at every step).
+        With Gradient(positions=True) the chain goes on through the potential build (msl_adjoint_positions, on the accumulator and
+        the phase tables the build left on the device): GradientData.positions is dL/dr_a, (n_atoms, 3) float64, the slice-axis
+        column zero.  potential= has no atoms: ValueError with positions= or with Gradient(positions=True).  -> GradientData."""
         from .gradient_data import GradientData
         grad = getattr(self, "_gradient", None)
         if grad is None:
@@ -1421,12 +1427,22 @@ class MultisliceCalculator:
                              "pattern of every probe position")
         if not 0 <= int(frame) < self.n_frames:
             raise ValueError(f"gradient: frame {frame} outside [0, {self.n_frames})")
+        if potential is not None and positions is not None:
+            raise ValueError("gradient: potential= and positions= are two sources of the same stack: pass one")
+        if potential is not None and grad.positions:
+            raise ValueError("gradient: Gradient(positions=True) differentiates the potential build, and potential= does not come from atoms")
+        if positions is not None:
+            positions = np.ascontiguousarray(positions, dtype=np.float64)
+            if positions.shape != (len(self._Z), 3) or not np.isfinite(positions).all():
+                raise ValueError(f"gradient: positions {positions.shape} must be finite ({len(self._Z)}, 3) coordinates, one row per atom")
         t0 = time.time()
         if potential is not None:
             V = np.asarray(potential)
             if V.shape != (self.nx, self.ny, nz):
                 raise ValueError(f"gradient: potential {V.shape} does not match ({self.nx}, {self.ny}, {nz})")
             eng.upload_potential(np.ascontiguousarray(np.moveaxis(V, 2, 0), dtype=np.float32))
+        elif positions is not None:
+            eng.build_potential(positions, self._Z, self.slice_axis)
         else:
             self._build(int(frame), 1)
         eng.adjoint_reset()
@@ -1439,9 +1455,10 @@ class MultisliceCalculator:
             if probe is not None:
                 probe[p0:p0 + real] = pg
         g = np.ascontiguousarray(np.moveaxis(eng.adjoint_download(), 0, 2))
+        pos_grad = eng.adjoint_positions() if grad.positions else None
         self.elapsed = time.time() - t0
         return GradientData(potential=g, loss=loss, sigma=interaction_sigma(self.voltage_eV), xs=self.xs, ys=self.ys, zs=self._slice_coords,
-                            probe=probe, kind=grad.loss, frame=int(frame), probe_positions=self.probe_positions)
+                            probe=probe, kind=grad.loss, frame=int(frame), probe_positions=self.probe_positions, positions=pos_grad)
 
     def run_images(self):
         """Frame-averaged images behind the objective lens (HRTEM, focal series), for every probe: probe batches outside, frame

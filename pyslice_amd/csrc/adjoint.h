@@ -171,4 +171,122 @@ __global__ void __launch_bounds__(256) adjoint_conjprop_kernel(float2* __restric
     *q = make_float2(c.x * v.x - c.y * v.y, c.x * v.y + c.y * v.x);
 }
 
+// ---- gradients with respect to atom positions: the potential build backwards ----
+// With Gamma_s = dL/dV_s, B_s = fft2(Gamma_s) and c = 2 pi / (N dx^2 dy^2), for atom a of species Z in slice s
+//     dL/dx_a = c sum_{mx, my} kx(mx) f_Z(mx, my) Im( conj(B_s(mx, my)) ex_a(mx) ey_a(my) ),     dL/dy_a: the same with ky(my),
+// over the FULL grid of fftfreq indices -- the structure factor's sum over atoms x k-bins run the other way, gathering at the atoms.
+// ex, ey are the sorted phase tables the build left (columns 0 .. n/2; a negative frequency m > n/2 is the conjugate of column n - m;
+// on an even length column n/2 IS the grid's one Nyquist frequency -n/2, so no line is folded and none counts twice).
+
+constexpr int PG_ATOMS = 8;                     // atoms (sorted table rows) per tile
+constexpr int PG_ROWS = 256 / PG_ATOMS;         // kx rows whose x phases are staged in the LDS at a time: one entry per thread
+
+// Gamma (n_images, nx, ny) float64 -> c64 images of pitch ny, imaginary part zero
+__global__ void __launch_bounds__(256) position_gamma_kernel(const double* __restrict__ gamma, float2* __restrict__ img, long long total) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < total) img[i] = make_float2((float)gamma[i], 0.f);
+}
+
+// A workgroup owns tile blockIdx.x: rows a0 .. a0 + na - 1 (na <= PG_ATOMS) of the sorted tables, all of one (slice, species) bin --
+// tiles[t] = (slice, species, a0, na).  Thread t owns the columns my = t, t + 256, ...; per column block it walks the rows mx of
+// W = f_Z conj(B_s) once (coalesced along my), PG_ROWS at a time: the x phases of the tile's atoms at those rows, and kx times them,
+// are staged in the LDS (every lane reads the same entry: a broadcast), and every loaded element of W feeds both components of all
+// atoms of the tile -- eight FMAs per atom and element into per-lane f32 sums  sum_mx kx W ex  and  sum_mx W ex.  After each block
+// of PG_ROWS rows the lane multiplies by its own ey_a(my) (and ky), takes the imaginary part and adds it into its float64 sums; at
+// the end the float64 sums are combined over the lanes of a wave by shuffles and over the four waves through the LDS in wave
+// order, scaled by c and stored to out[order[row]][ax1 / ax2] -- a row has one owner: no atomics, the same bits every run.  Padding
+// rows of a bin (order < 0, zero phases) are computed and not stored.
+// img: the images B_s of the slices s_base .. (pitch ny); kfx = 1 / (nx dx), kfy = 1 / (ny dy).
+__global__ void __launch_bounds__(256) position_gradient_kernel(const int4* __restrict__ tiles, const float2* __restrict__ img, int s_base,
+                                                                const float2* __restrict__ ex, const float2* __restrict__ ey,
+                                                                const float* __restrict__ ff, const int* __restrict__ order, int nx, int ny,
+                                                                int cx, int cy, float kfx, float kfy, double c, int ax1, int ax2,
+                                                                double* __restrict__ out) {
+    constexpr int TA = PG_ATOMS, RC = PG_ROWS;
+    __shared__ float4 sh_ex[RC][TA];            // (ex, kx ex) of row r and atom a
+    __shared__ double sh_red[4][TA][2];
+    const int4 tile = tiles[blockIdx.x];
+    const int s = tile.x, sp = tile.y, a0 = tile.z, na = tile.w;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int hx = nx / 2, hy = ny / 2;
+    const float2* Bs = img + (size_t)(s - s_base) * nx * ny;
+    const float* f = ff + (size_t)sp * nx * ny;
+    double gx[TA], gy[TA];
+#pragma unroll
+    for (int a = 0; a < TA; ++a) { gx[a] = 0.0; gy[a] = 0.0; }
+    for (int y0 = 0; y0 < ny; y0 += 256) {
+        const int my = y0 + (int)threadIdx.x;
+        const bool live = my < ny;
+        const int col = my <= hy ? my : ny - my;
+        const float kyw = live ? (float)(my < (ny + 1) / 2 ? my : my - ny) * kfy : 0.f;
+        float2 eyv[TA];
+#pragma unroll
+        for (int a = 0; a < TA; ++a) {
+            eyv[a] = make_float2(0.f, 0.f);
+            if (live && a < na) {
+                eyv[a] = ey[(size_t)(a0 + a) * cy + col];
+                if (my > hy) eyv[a].y = -eyv[a].y;
+            }
+        }
+        for (int x0 = 0; x0 < nx; x0 += RC) {
+            __syncthreads();                                    // the readers of the previous block are done
+            {
+                const int r = threadIdx.x / TA, a = threadIdx.x % TA, mx = x0 + r;
+                float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (mx < nx && a < na) {
+                    float2 e = ex[(size_t)(a0 + a) * cx + (mx <= hx ? mx : nx - mx)];
+                    if (mx > hx) e.y = -e.y;
+                    const float kxw = (float)(mx < (nx + 1) / 2 ? mx : mx - nx) * kfx;
+                    v = make_float4(e.x, e.y, kxw * e.x, kxw * e.y);
+                }
+                sh_ex[r][a] = v;
+            }
+            __syncthreads();
+            if (!live) continue;
+            float px[TA][2], py[TA][2];                         // sum_mx kx W ex and sum_mx W ex of this block of rows
+#pragma unroll
+            for (int a = 0; a < TA; ++a) { px[a][0] = px[a][1] = 0.f; py[a][0] = py[a][1] = 0.f; }
+            const int rows = min(RC, nx - x0);
+            for (int r = 0; r < rows; ++r) {
+                const size_t q = (size_t)(x0 + r) * ny + my;
+                const float2 b = Bs[q];
+                const float w = f[q];
+                const float wr = w * b.x, wi = -(w * b.y);      // W = f conj(B)
+#pragma unroll
+                for (int a = 0; a < TA; ++a) {
+                    const float4 e = sh_ex[r][a];
+                    py[a][0] = fmaf(wr, e.x, fmaf(-wi, e.y, py[a][0]));
+                    py[a][1] = fmaf(wr, e.y, fmaf(wi, e.x, py[a][1]));
+                    px[a][0] = fmaf(wr, e.z, fmaf(-wi, e.w, px[a][0]));
+                    px[a][1] = fmaf(wr, e.w, fmaf(wi, e.z, px[a][1]));
+                }
+            }
+#pragma unroll
+            for (int a = 0; a < TA; ++a) {                      // Im(p ey) = p.re ey.im + p.im ey.re
+                gx[a] += (double)fmaf(px[a][0], eyv[a].y, px[a][1] * eyv[a].x);
+                gy[a] += (double)(kyw * fmaf(py[a][0], eyv[a].y, py[a][1] * eyv[a].x));
+            }
+        }
+    }
+#pragma unroll
+    for (int a = 0; a < TA; ++a) {
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) { gx[a] += __shfl_xor(gx[a], o, 64); gy[a] += __shfl_xor(gy[a], o, 64); }
+    }
+    __syncthreads();
+    if (lane == 0) {
+#pragma unroll
+        for (int a = 0; a < TA; ++a) { sh_red[wave][a][0] = gx[a]; sh_red[wave][a][1] = gy[a]; }
+    }
+    __syncthreads();
+    if (threadIdx.x < 2 * TA) {
+        const int a = threadIdx.x >> 1, comp = threadIdx.x & 1;
+        if (a < na) {
+            const int atom = order[a0 + a];
+            if (atom >= 0)
+                out[(size_t)atom * 3 + (comp ? ax2 : ax1)] = c * (((sh_red[0][a][comp] + sh_red[1][a][comp]) + sh_red[2][a][comp]) + sh_red[3][a][comp]);
+        }
+    }
+}
+
 }  // namespace msl

@@ -321,6 +321,16 @@ struct msl_handle {
     DevBuf<float> adj_w, adj_D;
     DevBuf<float2> adj_stack;
     DevBuf<double> adj_grad, adj_part, adj_loss;
+    // gradients with respect to atom positions (msl_adjoint_positions): pg_valid while the sorted phase tables,
+    // the order, the bin starts and the form-factor tables are those of a single-frame msl_build_potential of pg_n atoms and pg_nsp
+    // species read along pg_ax1 / pg_ax2 (drop_position_tables clears it); the tile list, the images B_s of a chunk of slices (pitch
+    // ny), an uploaded Gamma and the result (pg_n, 3), grown on demand
+    bool pg_valid = false;
+    int64_t pg_n = 0;
+    int pg_nsp = 0, pg_ax1 = 0, pg_ax2 = 1;
+    DevBuf<int4> pg_tiles;
+    DevBuf<float2> pg_img;
+    DevBuf<double> pg_gamma, pg_out;
     // frozen phonons (msl_set_structure): the base structure resident on the device -- positions (n, 3), widths, Z and the species
     // maps that stage_atoms sends per call -- with the host's copy of the maps and the axes; msl_build_thermal generates the
     // positions of any configuration from it (thermal_positions_kernel), so no per-frame array and no caller pointer is kept
@@ -1607,6 +1617,86 @@ int adjoint_add(msl_handle* h, const float* data, int B, double* loss_out, float
     return MSL_OK;
 }
 
+// ---- gradients with respect to atom positions: the potential build backwards; adjoint.h ----
+// The tiles of position_gradient_kernel from the bin starts of the resident build (a small download: the call is synchronous anyway):
+// every (slice, species) bin in PG_ATOMS rows at a time, in bin order, so that the tiles of a slice are neighbours.  tile_of[s] = the
+// first tile of slice s (tile_of[nz] = all of them); bins_used = bins that hold rows
+int position_tiles(msl_handle* h, std::vector<int>& tile_of, int& bins_used, int& rows) {
+    const int nz = h->cfg.nz, nsp = h->pg_nsp, nkeys = nz * nsp;
+    tile_of.assign((size_t)nz + 1, 0);
+    bins_used = rows = 0;
+    if (h->pg_n == 0 || nsp == 0) return MSL_OK;         // (a build without atoms sorts nothing)
+    std::vector<int> start((size_t)nkeys + 1);
+    HIPCHK(h, hipMemcpyAsync(start.data(), h->d_start, start.size() * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    std::vector<int4> tiles;
+    for (int s = 0; s < nz; ++s) {
+        tile_of[s] = (int)tiles.size();
+        for (int sp = 0; sp < nsp; ++sp) {
+            const int a0 = start[(size_t)s * nsp + sp], a1 = start[(size_t)s * nsp + sp + 1];
+            if (a1 > a0) ++bins_used;
+            for (int a = a0; a < a1; a += PG_ATOMS) tiles.push_back(make_int4(s, sp, a, std::min(PG_ATOMS, a1 - a)));
+        }
+    }
+    tile_of[nz] = (int)tiles.size();
+    rows = start[nkeys];
+    int rc;
+    if ((rc = h->pg_tiles.reserve(h, tiles.size()))) return rc;
+    if (!tiles.empty()) {
+        HIPCHK(h, hipMemcpyAsync(h->pg_tiles, tiles.data(), tiles.size() * sizeof(int4), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));        // (the list is a local of this call)
+    }
+    return MSL_OK;
+}
+
+// Gamma (nz, nx, ny) float64 on the device -> pg_out (pg_n, 3), queued: per chunk of slices the c64 images, fft2_inplace(+1) and the
+// tiles of those slices
+int position_chain(msl_handle* h, const double* d_gamma, const std::vector<int>& tile_of) {
+    const msl_config& c = h->cfg;
+    const size_t npix = (size_t)c.nx * c.ny;
+    const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)c.nz, ((size_t)256 << 20) / (npix * sizeof(float2))));
+    int rc;
+    if ((rc = h->pg_img.reserve(h, (size_t)chunk * npix))) return rc;
+    HIPCHK(h, hipMemsetAsync(h->pg_out, 0, (size_t)std::max<int64_t>(1, h->pg_n) * 3 * sizeof(double), h->stream));
+    const double cc = 2.0 * M_PI / ((double)npix * c.dx * c.dx * c.dy * c.dy);
+    for (int s0 = 0; s0 < c.nz; s0 += chunk) {
+        const int ns = std::min(chunk, c.nz - s0), t0 = tile_of[s0], t1 = tile_of[s0 + ns];
+        if (t1 == t0) continue;
+        const long long total = (long long)ns * (long long)npix;
+        hipLaunchKernelGGL(position_gamma_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, d_gamma + (size_t)s0 * npix,
+                           h->pg_img.p, total);
+        HIPCHK(h, hipGetLastError());
+        if ((rc = fft2_inplace(h, h->pg_img, ns, +1, 1.0f, c.ny))) return rc;
+        hipLaunchKernelGGL(position_gradient_kernel, dim3((unsigned)(t1 - t0)), dim3(256), 0, h->stream, (const int4*)h->pg_tiles.p + t0,
+                           (const float2*)h->pg_img.p, s0, (const float2*)h->d_ex.p, (const float2*)h->d_ey.p, (const float*)h->d_ff.p,
+                           (const int*)h->d_order.p, c.nx, c.ny, c.nx / 2 + 1, c.ny / 2 + 1, (float)(1.0 / (c.nx * c.dx)), (float)(1.0 / (c.ny * c.dy)),
+                           cc, h->pg_ax1, h->pg_ax2, h->pg_out.p);
+        HIPCHK(h, hipGetLastError());
+        if ((rc = mark_launch(h, K_OTHER))) return rc;
+    }
+    return MSL_OK;
+}
+
+// the state both entry points need; d_gamma: the accumulator, or the caller's Gamma uploaded
+int position_prepare(msl_handle* h, const char* who, const double* gamma, const double** d_gamma) {
+    if (!h->pg_valid || !h->have_potential)
+        return fail(h, MSL_ERR_STATE, "%s: no single-frame msl_build_potential is resident (its phase tables, order and bins are what the "
+                                      "chain reads: a later build of several frames, msl_build_thermal / msl_build_modes, msl_upload_potential, "
+                                      "msl_set_projection or msl_set_absorption dropped them)", who);
+    if (!gamma && !h->adj_on) return fail(h, MSL_ERR_STATE, "%s: gamma == NULL needs the accumulator of msl_set_adjoint", who);
+    const msl_config& c = h->cfg;
+    const size_t npix = (size_t)c.nx * c.ny;
+    int rc;
+    if ((rc = h->pg_out.reserve(h, (size_t)std::max<int64_t>(1, h->pg_n) * 3))) return rc;
+    if (gamma) {
+        if ((rc = h->pg_gamma.reserve(h, (size_t)c.nz * npix))) return rc;
+        HIPCHK(h, hipMemcpyAsync(h->pg_gamma, gamma, (size_t)c.nz * npix * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));        // (the caller's memory is pageable)
+    }
+    *d_gamma = gamma ? h->pg_gamma.p : h->adj_grad.p;
+    return MSL_OK;
+}
+
 // cyclic length of the convolution that IS the propagation along an axis of a convolution kind (0: none), and the entries of its filter qf
 int conv_len(const msl_handle::OpDir& o) { return o.base == AX_CONV ? o.R * o.R : o.base == AX_CONV2K ? 2048 : o.base == AX_CONV4K ? 4096 : 0; }
 size_t conv_filter_entries(const msl_handle::OpDir& o) { return o.base == AX_CONV4K ? 2052 : (size_t)conv_len(o) / 2 + 2; }
@@ -2457,7 +2547,7 @@ int remake_transmission(msl_handle* h) {
 
 // ---- invalidations ----
 // The resident potential no longer counts (msl_propagate is MSL_ERR_STATE until the next build or upload)
-void drop_potential(msl_handle* h) { h->have_potential = false; h->abs_built = false; h->ion_built = false; }
+void drop_potential(msl_handle* h) { h->have_potential = false; h->abs_built = false; h->ion_built = false; h->pg_valid = false; }
 
 // A built S-matrix belongs to the tables and the stack it was built with: it has to be built again (the beams stay)
 void drop_smatrix_result(msl_handle* h) { h->sm_built = false; }
@@ -2493,6 +2583,7 @@ int adj_clear(msl_handle* h) {
     if (!h->adj_on) return MSL_OK;
     h->adj_on = ADJ_OFF; h->adj_P = 0;
     h->adj_w.release(); h->adj_D.release(); h->adj_stack.release(); h->adj_grad.release(); h->adj_part.release(); h->adj_loss.release();
+    h->pg_tiles.release(); h->pg_img.release(); h->pg_gamma.release(); h->pg_out.release();      // (the position chain's own: grown again on demand)
     return set_loop_mode(h, allowed_onepass(h, h->set.tilt_tan[0], h->set.tilt_tan[1]));
 }
 
@@ -2768,6 +2859,58 @@ int msl_adjoint_download(msl_handle* h, double* grad) {
     return MSL_OK;
 }
 
+// gradients with respect to atom positions
+int msl_adjoint_positions(msl_handle* h, const double* gamma, double* out) {
+    if (!h || !out) return fail(h, MSL_ERR_INVALID, "msl_adjoint_positions: null argument");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    const double* d_gamma = nullptr;
+    int rc = position_prepare(h, "msl_adjoint_positions", gamma, &d_gamma);
+    if (rc) return rc;
+    h->cur = nullptr;
+    std::vector<int> tile_of;
+    int bins_used = 0, rows = 0;
+    if ((rc = position_tiles(h, tile_of, bins_used, rows)) || (rc = position_chain(h, d_gamma, tile_of))) {
+        (void)hipStreamSynchronize(h->stream);
+        return rc;
+    }
+    const msl_config& c = h->cfg;
+    const uint64_t npix = (uint64_t)c.nx * c.ny;
+    // per slice the conversion and the transform (8 + 8 + 32 B per pixel); per bin with atoms one read of B_s and f_Z (12); per table
+    // row its phases; the result
+    h->ctr.algorithmic_bytes += (uint64_t)c.nz * npix * 48ull + (uint64_t)bins_used * npix * 12ull +
+                                (uint64_t)rows * (uint64_t)(c.nx / 2 + 1 + c.ny / 2 + 1) * 8ull + (uint64_t)h->pg_n * 24ull;
+    if (h->pg_n > 0)
+        HIPCHK(h, hipMemcpyAsync(out, h->pg_out, (size_t)h->pg_n * 3 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return MSL_OK;
+}
+
+int64_t msl_adjoint_positions_rows(const msl_handle* h) {
+    return (h && h->pg_valid && h->have_potential) ? h->pg_n : -1;
+}
+
+int msl_adjoint_positions_time(msl_handle* h, int32_t reps, double* ms_chain) {
+    if (!h) return fail(h, MSL_ERR_INVALID, "msl_adjoint_positions_time: null handle");
+    if (reps < 1) return fail(h, MSL_ERR_INVALID, "msl_adjoint_positions_time: reps must be positive");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    const double* d_gamma = nullptr;
+    int rc = position_prepare(h, "msl_adjoint_positions_time", nullptr, &d_gamma);
+    if (rc) return rc;
+    h->cur = nullptr;
+    std::vector<int> tile_of;
+    int bins_used = 0, rows = 0;
+    double ms = 0.0;
+    EventPair timer;
+    if ((rc = position_tiles(h, tile_of, bins_used, rows)) || (rc = position_chain(h, d_gamma, tile_of)) || (rc = timer.begin(h))) {
+        (void)hipStreamSynchronize(h->stream);
+        return rc;
+    }
+    for (int r = 0; r < reps && rc == MSL_OK; ++r) rc = position_chain(h, d_gamma, tile_of);
+    if (rc || (rc = timer.end(h, &ms))) { (void)hipStreamSynchronize(h->stream); return rc; }
+    if (ms_chain) *ms_chain = ms / reps;
+    return MSL_OK;
+}
+
 }  // extern "C"
 
 namespace {
@@ -2787,6 +2930,7 @@ int build_potentials(msl_handle* h, const double* pos, const int32_t* Z, int64_t
     const size_t npix = (size_t)c.nx * c.ny;
     PotGroup p{};
     int rc = MSL_OK;
+    h->pg_valid = false;                                 // the tables are rewritten: msl_adjoint_positions needs this build to finish
     if (th) {
         memcpy(p.z2s, h->th_map_z2s, sizeof p.z2s);
         memcpy(p.species, h->th_map_species, sizeof p.species);
@@ -2872,6 +3016,10 @@ int build_potentials(msl_handle* h, const double* pos, const int32_t* Z, int64_t
     h->have_potential = true;
     h->abs_built = h->abs_on;
     h->ion_built = h->ion_on;
+    // the tables of one frame of the caller's atoms, plain projection: what msl_adjoint_positions differentiates
+    // (a band limit low-passes V behind the structure factor: the chain would differentiate the unfiltered build)
+    h->pg_valid = !th && count == 1 && !p.finite && !h->abs_on && !h->set.bl_on;
+    h->pg_n = n; h->pg_nsp = p.nsp; h->pg_ax1 = ax1; h->pg_ax2 = ax2;
     return MSL_OK;
 }
 
@@ -3268,6 +3416,7 @@ int msl_set_projection(msl_handle* h, int32_t reach_slices, int32_t nodes) {
     HIPCHK(h, hipSetDevice(h->cfg.device));
     HIPCHK(h, hipStreamSynchronize(h->stream));          // a queued build still reads the tables
     h->fin_R = reach_slices; h->fin_J = nodes;
+    h->pg_valid = false;
     h->ff_n = 0;                                         // d_ff holds f or the channel tables: the next build makes its table again
     return MSL_OK;
 }
@@ -3641,6 +3790,7 @@ int msl_upload_potential(msl_handle* h, const float* V) {
     HIPCHK(h, hipStreamSynchronize(h->stream));
     h->have_potential = true;
     h->abs_built = false;
+    h->pg_valid = false;                                // (nor atoms to differentiate with respect to)
     h->ion_built = false;                               // (an uploaded potential has no atoms to make the ionisation weights from)
     return MSL_OK;
 }

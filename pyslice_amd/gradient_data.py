@@ -24,6 +24,7 @@ class GradientData:
     kind: str = "amplitude"
     frame: int = 0
     probe_positions: Any = None
+    positions: Optional[np.ndarray] = None      # (n_atoms, 3) float64: dL/dr_a with Gradient(positions=True) (slice-axis column zero), else None
 
     @property
     def total(self) -> float:
@@ -36,3 +37,13 @@ class GradientData:
         if V.shape != self.potential.shape:
             raise ValueError(f"descent_step: V {V.shape} does not match the gradient {self.potential.shape}")
         return V - float(rate) * self.potential
+
+    def position_step(self, pos, rate):
+        """pos - rate * dL/dr for coordinates pos (n_atoms, 3): one step of plain gradient descent on the atoms, float64 (what the
+        next run_gradient(positions=...) takes)"""
+        if self.positions is None:
+            raise ValueError("position_step: no position gradient (MultisliceCalculator(gradient=Gradient(positions=True)))")
+        pos = np.asarray(pos, dtype=np.float64)
+        if pos.shape != self.positions.shape:
+            raise ValueError(f"position_step: pos {pos.shape} does not match the gradient {self.positions.shape}")
+        return pos - float(rate) * self.positions

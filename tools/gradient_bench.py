@@ -31,8 +31,61 @@ def source(n, nz):
     return ps.Trajectory(atom_types=Z, positions=pos[None], velocities=np.zeros((1, len(pos), 3)), box_matrix=box, timestep=1.0), box
 
 
+def position_leg(a, src, kw, data):
+    """--positions: run_gradient() with and without Gradient(positions=True), alternating, and the chain
+    alone (msl_adjoint_positions_time on the accumulator of the last run) next to the forward build of the same frame"""
+    import pyslice_amd as ps
+    plain = ps.MultisliceCalculator(device=0, progress=False, gradient=ps.Gradient(), probe_batch=a.probe_batch)
+    plain.setup(src, **kw)
+    with_pos = ps.MultisliceCalculator(device=0, progress=False, gradient=ps.Gradient(positions=True), probe_batch=a.probe_batch)
+    with_pos.setup(src, **kw)
+    plain.run_gradient(data)
+    res = with_pos.run_gradient(data)
+    times = {"plain": [], "positions": []}
+    for _ in range(a.repeat):
+        for name, calc in (("plain", plain), ("positions", with_pos)):
+            t0 = time.perf_counter()
+            res = calc.run_gradient(data)
+            times[name].append(time.perf_counter() - t0)
+    p, q = float(np.median(times["plain"])), float(np.median(times["positions"]))
+    eng = with_pos._engine
+    reps = 10
+    ms_chain = eng.adjoint_positions_time(reps)
+    # the forward build of the same frame by the handle's own event pair around it (msl_config.launch_timing -> counters ms_potential):
+    # a handle of its own with one probe, the calculator's grid and slices
+    from pyslice_amd import _native
+    from pyslice_amd.potentials import loadKirkland, slice_edges
+    from oracle import multislice_oracle as orc
+    pos, Z = src.positions[0], src.atom_types
+    xs, ys, zs = with_pos.xs, with_pos.ys, with_pos._slice_coords
+    timed = _native.Engine(a.grid, a.grid, a.slices, xs[1] - xs[0], ys[1] - ys[0], zs[1] - zs[0], orc.wavelength(EV), orc.interaction_sigma(EV),
+                           n_probes=1, launch_timing=True)
+    timed.set_kirkland(loadKirkland())
+    timed.set_slices(*slice_edges(zs))
+    timed.build_potential(pos, Z)                               # (untimed: the form-factor tables and the allocations)
+    timed.synchronize()
+    timed.reset_counters()
+    for _ in range(reps):
+        timed.build_potential(pos, Z)
+    timed.synchronize()
+    ms_build = float(timed.counters()["ms_potential"]) / reps
+    timed.close()
+    nz, n = a.slices, len(Z)
+    flops = 16.0 * n * a.grid * a.grid                           # 8 FMAs per atom and k-bin
+    lines = [f"{a.scan} x {a.scan} scan, {a.grid}^2 x {a.slices} slices, {n} atoms, probe_batch={a.probe_batch} (median of {a.repeat}, s; all runs)",
+             f"  run_gradient()                 {p:8.3f}   {' '.join(f'{t:.3f}' for t in times['plain'])}",
+             f"  run_gradient(), positions=True {q:8.3f}   {' '.join(f'{t:.3f}' for t in times['positions'])}",
+             f"  max |dL/dr| {np.abs(res.positions).max():.4e}",
+             f"chain alone (Gamma -> c64, {nz} transforms, position_gradient_kernel), {reps} chains between two events",
+             f"  chain {ms_chain:8.3f} ms   the kernel's 16 flops per atom and k-bin (full grid) over the WHOLE chain time: "
+             f"{flops / (ms_chain * 1e-3) / 1e12:6.2f} TFLOP/s, a lower bound of the kernel's rate",
+             f"  forward build of the same frame (event pair around the build, mean of {reps}) {ms_build:8.3f} ms   ratio chain / build {ms_chain / ms_build:5.2f}"]
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--positions", action="store_true", help="the position leg alone, into profiles/position_gradient.txt")
     ap.add_argument("--out", default=os.path.join("profiles", "gradient.txt"))
     ap.add_argument("--repeat", type=int, default=3)
     ap.add_argument("--grid", type=int, default=512)
@@ -52,6 +105,15 @@ def main():
     res = grad.run_gradient(data)                               # warm-up
     # the data of the timed runs: V's own patterns give a zero residual, so they are flattened a little -- a residual of ordinary size
     data = data * 0.81 + 0.19 * data.mean(axis=(1, 2), keepdims=True)
+    if a.positions:
+        del grad
+        text = "\n".join(position_leg(a, src, kw, data)) + "\n"
+        print(text, end="")
+        out = a.out if a.out != os.path.join("profiles", "gradient.txt") else os.path.join("profiles", "position_gradient.txt")
+        os.makedirs(os.path.dirname(out) or ".", exist_ok=True)
+        with open(out, "w") as f:
+            f.write(text)
+        return
     times = {"diffraction": [], "gradient": []}
     for _ in range(a.repeat):
         t0 = time.perf_counter()
