@@ -414,6 +414,9 @@ int  msl_ionization_reduce(msl_handle* h, int32_t slice, int32_t reps, double* o
  * msl_adjoint_step_time:  the step kernel of `slice` alone over the n_probes images of the work buffer as the last call left it, once
  *   untimed and then `reps` times between two events; ms_step = the mean device time of one launch in ms.  It adds into row `slice`
  *   of the accumulator and rewrites the work buffer: msl_adjoint_reset afterwards.  For benchmarks, as msl_tds_reduce is.
+ * msl_adjoint_layout:  read-only, for tests: *pitch = the row pitch of the work buffer and the wave stack in elements, *vec = 1 where
+ *   msl_adjoint_add launches the 16-byte variant of the step kernel (an even pitch, buffers on 16 bytes), 0 for the 8-byte one.  Either
+ *   pointer may be NULL.  MSL_ERR_STATE without msl_set_adjoint (no message is set: the handle is const).
  * Not in the reference. */
 enum { MSL_ADJ_OFF = 0, MSL_ADJ_AMPLITUDE = 1, MSL_ADJ_INTENSITY = 2, MSL_ADJ_POISSON = 3 };
 int  msl_set_adjoint(msl_handle* h, int32_t loss_kind, double epsilon, const float* weight);
@@ -421,6 +424,7 @@ int  msl_adjoint_reset(msl_handle* h);
 int  msl_adjoint_add(msl_handle* h, const float* data, int32_t B, double* loss_out, void* probe_grad);
 int  msl_adjoint_download(msl_handle* h, double* grad);
 int  msl_adjoint_step_time(msl_handle* h, int32_t slice, int32_t reps, double* ms_step);
+int  msl_adjoint_layout(const msl_handle* h, int32_t* pitch, int32_t* vec);
 
 /* ---- gradients with respect to atom positions: the potential build backwards ----
  * The build is V_s = Re ifft2( sum_Z f_Z sum_{a in Z, s} e^{-2 pi i (kx x_a + ky y_a)} ) / (dx^2 dy^2) on the fftfreq grid.  With

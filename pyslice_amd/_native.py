@@ -53,7 +53,7 @@ EXPORTS = [
     "msl_set_ionization", "msl_ionization_fetch", "msl_ionization_reduce",
     "msl_set_projection", "msl_get_projection",
     "msl_set_probe_members", "msl_diffract_members", "msl_dose_add_members",
-    "msl_set_adjoint", "msl_adjoint_reset", "msl_adjoint_add", "msl_adjoint_download", "msl_adjoint_step_time",
+    "msl_set_adjoint", "msl_adjoint_reset", "msl_adjoint_add", "msl_adjoint_download", "msl_adjoint_step_time", "msl_adjoint_layout",
     "msl_adjoint_positions", "msl_adjoint_positions_rows", "msl_adjoint_positions_time",
 ]
 DET_SIGNALS = {"intensity": 0, "amplitude": 1, "com_x": 2, "com_y": 3}      # include/mslice.h: MSL_DET_*
@@ -185,6 +185,7 @@ def load():
         "msl_adjoint_add": (C.c_int, [vp, vp, i32, vp, vp]),
         "msl_adjoint_download": (C.c_int, [vp, vp]),
         "msl_adjoint_step_time": (C.c_int, [vp, i32, i32, vp]),
+        "msl_adjoint_layout": (C.c_int, [vp, vp, vp]),
         "msl_adjoint_positions": (C.c_int, [vp, vp, vp]),
         "msl_adjoint_positions_rows": (C.c_int64, [vp]),
         "msl_adjoint_positions_time": (C.c_int, [vp, i32, vp]),
@@ -422,6 +423,14 @@ class Engine:
         ms = C.c_double(0.0)
         self._chk(self._lib.msl_adjoint_step_time(self._h, int(slice_index), int(reps), C.byref(ms)))
         return float(ms.value)
+
+    def adjoint_layout(self):
+        """(pitch, vec): the row pitch of the work buffer and the wave stack in elements, and whether adjoint_add launches the 16-byte
+        variant of the step kernel (msl_adjoint_layout; read-only, for tests)"""
+        pitch, vec = C.c_int32(0), C.c_int32(0)
+        if self._lib.msl_adjoint_layout(self._h, C.byref(pitch), C.byref(vec)):
+            raise RuntimeError("adjoint_layout: no adjoint (set_adjoint)")
+        return int(pitch.value), bool(vec.value)
 
     def adjoint_download(self):
         """the gradient accumulator, (nz, nx, ny) float64 (msl_adjoint_download)"""

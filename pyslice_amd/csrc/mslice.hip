@@ -1554,11 +1554,15 @@ int slice_loop(msl_handle* h, int fused_slot, int groups, int first_group, bool 
 // ---- gradients: the slice loop backwards; adjoint.h ----
 // The step of slice s for the first B images of g (the work buffer's layout), queued: psi_s from the stack (psi0 at s = 0), t_s of the
 // current batch slot, row s of the accumulator
+// adjoint_step_kernel<VEC> or not: an even pitch and g, psi0 and the stack on 16 bytes
+bool adjoint_step_vec(const msl_handle* h, const float2* g) {
+    return (h->pitch % 2 == 0) && (((uintptr_t)g & 15) == 0) && (((uintptr_t)h->psi0.p & 15) == 0) && (((uintptr_t)h->adj_stack.p & 15) == 0);
+}
 int adjoint_step_launch(msl_handle* h, float2* g, int s, int B) {
     const msl_config& c = h->cfg;
     const size_t npix = (size_t)c.nx * c.ny, slab = (size_t)c.n_probes * c.nx * h->pitch;
     const long long pairs = (long long)c.nx * ((c.ny + 1) / 2), step_tiles = (pairs + ADJ_TILE - 1) / ADJ_TILE;
-    const bool vec = (h->pitch % 2 == 0) && (((uintptr_t)g & 15) == 0) && (((uintptr_t)h->psi0.p & 15) == 0) && (((uintptr_t)h->adj_stack.p & 15) == 0);
+    const bool vec = adjoint_step_vec(h, g);
     const float2* psi_s = s == 0 ? h->psi0.p : h->adj_stack.p + (size_t)(s - 1) * slab;
     const float2* t = h->trans + ((size_t)h->cur_batch * c.nz + s) * npix;
     double* grad = h->adj_grad + (size_t)s * npix;
@@ -2847,6 +2851,13 @@ int msl_adjoint_step_time(msl_handle* h, int32_t slice, int32_t reps, double* ms
     for (int r = 0; r < reps && rc == MSL_OK; ++r) rc = adjoint_step_launch(h, h->psi, slice, h->cfg.n_probes);
     if (rc || (rc = timer.end(h, &ms))) { (void)hipStreamSynchronize(h->stream); return rc; }
     if (ms_step) *ms_step = ms / reps;
+    return MSL_OK;
+}
+
+int msl_adjoint_layout(const msl_handle* h, int32_t* pitch, int32_t* vec) {
+    if (!h || !h->adj_on) return MSL_ERR_STATE;
+    if (pitch) *pitch = h->pitch;
+    if (vec) *vec = adjoint_step_vec(h, h->psi.p) ? 1 : 0;
     return MSL_OK;
 }
 

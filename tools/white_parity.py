@@ -11,7 +11,12 @@ into a second report.
 output_case() extends the contract to the layer taps (msl_set_layers) and to the stored form of every spectrum -- k-window, detector
 bin, frame-batch scatter -- on untilted tables: tests/test_gpu_white_output.py imports the OUT_* lists and tap_layout(), the pure
 restatement of which line order, row FFT and column pass a tap takes.
-usage: python tools/white_parity.py [out.txt [tilt_out.txt]], or --tilt-only [tilt_out.txt], or --output-only [output_out.txt]"""
+
+gradient_case() takes it to the slice loop backwards (msl_set_adjoint / msl_adjoint_add): white probes, potentials, data and weights
+against pyslice_amd/adjoint.py in float64, the probe gradient, every slice of the accumulator and the loss, under a tilt too:
+tests/test_gpu_white_gradient.py imports the GRAD_* lists, tests/test_white_gradient_host.py checks the bounds' margins and what they see.
+usage: python tools/white_parity.py [out.txt [tilt_out.txt]], or --tilt-only [tilt_out.txt], or --output-only [output_out.txt], or
+--gradient-only [gradient_out.txt]"""
 import collections
 import functools
 import math
@@ -708,7 +713,293 @@ def output_main(out_path):
     return 1 if bad else 0
 
 
+# ---- the slice loop backwards (tests/test_gpu_white_gradient.py, tests/test_white_gradient_host.py) -------
+# A case: an engine of P probes on the two-pass loop (msl_set_adjoint puts it there), `adds` = the batch sizes of its adjoint_add calls,
+# each on P new white probes (the first B of them are used); loss, a white weight or none, a tilt or none.
+GradCase = collections.namedtuple("GradCase", "nx ny nz P loss weighted tilt fft_path adds")
+GRAD_LOSSES = ("amplitude", "intensity", "poisson")
+U_RANGE = 0.5                           # sqrt D = |Psi_ref| (1 + U_RANGE u), u uniform in [-1, 1]
+KAPPA_CAP = 4.0                         # the condition on the inputs: kappa_loss of every case and probe
+F32_ULP = 2.0 ** -24
+
+
+def _gcase(nx, ny, nz, P=2, loss="amplitude", weighted=False, tilt="auto", fft_path=0, adds=None):
+    """a case of gradient_case(): the tilt TILT on every grid with a propagator (nz > 1) unless tilt says otherwise"""
+    tilt = (TILT if nz > 1 else None) if tilt == "auto" else tilt
+    return GradCase(nx, ny, nz, P, loss, bool(weighted), tilt, fft_path, (P,) if adds is None else tuple(adds))
+
+
+def gradient_id(c):
+    s = f"{c.nx}x{c.ny}x{c.nz}-P{c.P}-{c.loss}" + ("-w" if c.weighted else "") + ("-tilt" if c.tilt else "")
+    return s + ("-two_pass" if c.fft_path else "") + ("" if c.adds == (c.P,) else "-adds" + "+".join(map(str, c.adds)))
+
+
+# one partial tile in the residual pass (480 of 1024 pixels) and in the step (240 of 512 pairs); nz = 1: no propagator, no stack
+GRAD_SINGLE_TILE_CASES = [_gcase(24, 20, 1)]
+# 45 x 63 (fft_path=1: pitch 63, the 8-byte step, 2.8 step tiles, odd lengths in the shift mapping of both axes) and 101 x 97 (pitch
+# 114: the 16-byte step with its pad pixel and the 8-byte tail store): every loss, the white weight, the tilt
+GRAD_ODD_CASES = [_gcase(45, 63, 3, loss=l, weighted=True, fft_path=1) for l in GRAD_LOSSES] + \
+                 [_gcase(101, 97, 3, loss=l, weighted=True) for l in GRAD_LOSSES]
+# generic lines; the fast row kernel on either axis; 525 pairs per row: the boundaries of the 512-pair tiles fall inside rows
+GRAD_GRID_CASES = [_gcase(96, 80, 4), _gcase(256, 64, 2), _gcase(64, 256, 3), _gcase(12, 1050, 2)]
+# P = 3: a full add, new probes, a ragged add of 2 on the P-strided stack behind it; P = 1: no prefetch of a next image in flight
+GRAD_BATCH_CASES = [_gcase(45, 63, 3, P=3, weighted=True, fft_path=1, adds=(3, 2)), _gcase(101, 97, 3, P=3, weighted=True, adds=(3, 2)),
+                    _gcase(45, 63, 3, P=1, weighted=True, fft_path=1), _gcase(101, 97, 3, P=1, weighted=True)]
+GRAD_RESTORE_CASE = _gcase(101, 97, 3, weighted=True)           # then set_tilt(0, 0) on the same handle, against the untilted case
+GRADIENT_LISTS = (("single tile", GRAD_SINGLE_TILE_CASES), ("odd grids", GRAD_ODD_CASES), ("grids", GRAD_GRID_CASES),
+                  ("batches", GRAD_BATCH_CASES))
+
+
+def step_layout(nx, ny, fft_path=0):
+    """(pitch, vec) of msl_adjoint_add on a grid: mslice.hip's pitch (ny, + 16 where a fast kernel or the one-pass loop is planned,
+    then even on a one-pass plan) and the 16-byte step on an even pitch (the buffers are on 16 bytes)"""
+    Rx, Ry = plan_radices(nx, ny, fft_path)
+    pitch = ny + (16 if Rx or Ry else 0)
+    if grid_plan(nx, ny, fft_path)[2]:
+        pitch = ny + 16 if pitch == ny else pitch
+        pitch += pitch & 1
+    return pitch, pitch % 2 == 0
+
+
+def kappa_loss(Psi, D, loss, weight, eps):
+    """(P,): the Lipschitz factor of the residual pass, relative: with k(r) = |dG/dPsi| + |dG/dPsi*| per pixel (the norm of the
+    real-linear map dPsi -> dG), kappa = rms_r(k) rms(Psi) / rms(G): a homogeneous error of e rms(Psi) on Psi leaves at most
+    kappa e rms(G) on G.  With a = |Psi|, I = a^2 (Psi, D unshifted; D (P, nx, ny), weight (nx, ny) or None, both already unshifted):
+        amplitude   dG/dPsi = w (1 - sqrt D / (2 a)),                       |dG/dPsi*| = w sqrt D / (2 a)
+        intensity   dG/dPsi = w (2 I - D),                                  |dG/dPsi*| = w I
+        poisson     dG/dPsi = w (1 - D / (I + eps) + D I / (I + eps)^2),    |dG/dPsi*| = w D I / (I + eps)^2"""
+    a = np.abs(Psi)
+    I = a * a
+    w = 1.0 if weight is None else weight[None]
+    if loss == "amplitude":
+        r = np.sqrt(D) / (2.0 * np.maximum(a, np.sqrt(eps)))
+        k, G = w * (np.abs(1.0 - r) + r), w * (1.0 - 2.0 * r) * a
+    elif loss == "intensity":
+        k, G = w * (np.abs(2.0 * I - D) + I), w * (I - D) * a
+    else:
+        r = D / (I + eps)
+        k, G = w * (np.abs(1.0 - r + r * I / (I + eps)) + r * I / (I + eps)), w * (1.0 - r) * a
+    ms = lambda v: (np.abs(v) ** 2).mean(axis=(1, 2))
+    return np.sqrt(ms(k) * ms(a) / ms(G))
+
+
+def white_loss_bound(Psi, D, L, loss, eps, e):
+    """(P,): the algebra of tests/gradient_cases.py's loss_bound for exit amplitudes a = |Psi| that move by delta with
+    ||delta||_2 <= e ||a||_2 (S = sum I; D unshifted):
+        amplitude   2 e sqrt(L S) + e^2 S
+        intensity   E = 2 e max(a) sqrt(S) + e^2 S;  sqrt(2 L0) E + E^2 / 2,  L0 the unweighted loss
+        poisson     2 e sqrt(S) (sqrt(S) + ||D a / (I + eps)||_2) + e^2 S (1 + 6 max(D / (I + eps))),  which needs eps >= 4 e^2 S
+    A weight 0 <= w <= 1 only takes terms out."""
+    I = np.abs(Psi) ** 2
+    S = I.sum(axis=(1, 2))
+    L = np.abs(L)
+    if loss == "amplitude":
+        return 2.0 * e * np.sqrt(L * S) + e * e * S
+    if loss == "intensity":
+        E = 2.0 * e * np.sqrt(I.max(axis=(1, 2))) * np.sqrt(S) + e * e * S
+        return np.sqrt(((I - D) ** 2).sum(axis=(1, 2))) * E + 0.5 * E * E
+    assert (eps >= 4.0 * e * e * S).all()
+    r = D / (I + eps)
+    return 2.0 * e * np.sqrt(S) * (np.sqrt(S) + np.sqrt(((r * np.sqrt(I)) ** 2).sum(axis=(1, 2)))) + e * e * S * (1.0 + 6.0 * r.max(axis=(1, 2)))
+
+
+def gradient_inputs(c):
+    """the inputs of a case, nothing computed from them yet: V (nz, nx, ny) float32; the weight (nx, ny) float32 in the detector's
+    layout -- uniform in [0, 1], about a quarter of the pixels exactly 0, not symmetric under i -> n - i -- or None; per add the
+    (P, nx, ny) complex64 probes and the u (B, nx, ny) of its data"""
+    seed = (c.nx * 4099 + c.ny) * 64 + c.nz * 8 + c.P
+    probes, V = white_input(c.nx, c.ny, c.nz, c.P)
+    rng = np.random.default_rng(seed + 977)
+    w = None
+    if c.weighted:
+        w = rng.random((c.nx, c.ny)).astype(np.float32)
+        w[rng.random((c.nx, c.ny)) < 0.25] = 0.0
+    adds = []
+    for a, B in enumerate(c.adds):
+        pr = probes if a == 0 else white_input(c.nx, c.ny, c.nz, c.P, seed=seed + 31 * a)[0]
+        adds.append((pr, rng.uniform(-1.0, 1.0, (B, c.nx, c.ny))))
+    return V[0], w, adds
+
+
+@functools.lru_cache(maxsize=4)
+def gradient_data(c):
+    """inputs, float64 reference (pyslice_amd/adjoint.py under the case's tilted propagator, on the float32 V widened) and bounds of
+    a case; nothing of the device.  The data: sqrt D = |Psi_ref| (1 + U_RANGE u) in the detector's layout, rounded to float32 (what
+    is uploaded and what the reference reads): G is then a white field for all three losses and sqrt D / |Psi| stays in
+    [1 - U_RANGE, 1 + U_RANGE] at the Rayleigh field's near-zeros.  epsilon: 1e-20, for the Poisson loss 1e-6 of the first pattern's sum
+    (gradient_cases.poisson_epsilon), as float32.
+
+    Bounds, composed from the white-noise contract (tol = two_pass_tolerance per 2-D transform, in quadrature over the transforms, x
+    LINE_FACTOR for a line, x PIXEL_FACTOR for a pixel):
+        phi_s carries 2 s transforms:                    e_phi(s) = tol sqrt(max(2 s, 1))
+        Psi carries n_f = 2 (nz - 1) + 1, the residual pass multiplies that error by kappa (kappa_loss, on the reference's own Psi and
+        D), and g behind slice s carries 1 + 2 (nz - 1 - s) more:
+                                                         e_g(s) = tol sqrt(kappa^2 n_f + 1 + 2 (nz - 1 - s))
+        probe gradient (metrics()):                      e_g(0) x (1, LINE_FACTOR, PIXEL_FACTOR)
+        accumulator, slice s, with m(f) = mean |f|^2, the sums over the adds a and their probes p, acc(r) the float32 sums of the step
+        kernel (B products and B additions of an add, each within an ulp of sum_p |g_p| |phi_p|: (B + 4) ulp):
+            image   2 sigma sqrt( sum (e_g^2 + e_phi^2 + e_g^2 e_phi^2) m(g_p) m(phi_p) ) + rms_r acc(r)
+            line    LINE_FACTOR x the image bound
+            pixel   2 sigma sum F e_g rms(g_p) |phi_p(r)| + F e_phi rms(phi_p) |g_p(r)| + F^2 e_g e_phi rms(g_p) rms(phi_p),  F = PIXEL_FACTOR,
+                    + acc(r)
+        all three figures are stated over the norm 2 sigma sqrt( sum m(g_p) m(phi_p) )
+        loss per probe:                                  white_loss_bound at e = tol sqrt(n_f)"""
+    from pyslice_amd import adjoint as adj
+    from pyslice_amd.tilt import tilted_propagator
+    nx, ny, nz = c.nx, c.ny, c.nz
+    sigma = orc.interaction_sigma(EV)
+    V32, w32, add_in = gradient_inputs(c)
+    V = V32.astype(np.float64)
+    prop = tilted_propagator(nx, ny, DX, DY, orc.wavelength(EV), DZ, tilt_object(c.tilt))
+    w = None if w32 is None else w32.astype(np.float64)
+    wu = None if w is None else np.fft.ifftshift(w)
+    tol, n_f = two_pass_tolerance(nx, ny), 2 * (nz - 1) + 1
+    e_phi = tol * np.sqrt(np.maximum(2.0 * np.arange(nz), 1.0))
+    adds, eps = [], None
+    for probes, u in add_in:
+        B = len(u)
+        psis, phis, Psi = adj.forward_waves(probes[:B], V, sigma, prop)
+        D = (np.fft.fftshift(np.abs(Psi) * (1.0 + U_RANGE * u), axes=(-2, -1)) ** 2).astype(np.float32)
+        if eps is None:
+            eps = float(np.float32(1e-6 * float(D[0].astype(np.float64).sum()))) if c.loss == "poisson" else 1e-20
+        L, G = adj.loss_and_residual(Psi, D, c.loss, w, eps)
+        grad, pg, pairs = adj.backward(G, psis, V, sigma, prop)
+        Du = np.fft.ifftshift(D.astype(np.float64), axes=(-2, -1))
+        kappa = kappa_loss(Psi, Du, c.loss, wu, eps)
+        e_g = tol * np.sqrt(kappa.max() ** 2 * n_f + 1.0 + 2.0 * (nz - 1 - np.arange(nz)))
+        adds.append(dict(probes=probes, B=B, D=D, loss=L, grad=grad, probe=pg, pairs=pairs, kappa=kappa, e_g=e_g,
+                         loss_bound=white_loss_bound(Psi, Du, L, c.loss, eps, tol * np.sqrt(n_f))))
+    ms = lambda f: (np.abs(f) ** 2).mean(axis=(1, 2))
+    norm, img, pix = np.zeros(nz), np.zeros(nz), np.zeros((nz, nx, ny))
+    for s in range(nz):
+        q = q_err = 0.0
+        acc = np.zeros((nx, ny))
+        for a in adds:
+            g, phi = a["pairs"][s]
+            mg, mp, eg, ep = ms(g), ms(phi), a["e_g"][s], e_phi[s]
+            q += (mg * mp).sum()
+            q_err += (eg * eg + ep * ep + eg * eg * ep * ep) * (mg * mp).sum()
+            F = PIXEL_FACTOR
+            pix[s] += 2.0 * sigma * (F * eg * np.sqrt(mg)[:, None, None] * np.abs(phi) + F * ep * np.sqrt(mp)[:, None, None] * np.abs(g)
+                                     + F * F * eg * ep * np.sqrt(mg * mp)[:, None, None]).sum(axis=0)
+            acc += 2.0 * sigma * (a["B"] + 4) * F32_ULP * (np.abs(g) * np.abs(phi)).sum(axis=0)
+        norm[s] = 2.0 * sigma * np.sqrt(q)
+        img[s] = 2.0 * sigma * np.sqrt(q_err) + np.sqrt((acc ** 2).mean())
+        pix[s] += acc
+    out = dict(V=V32, weight=w32, epsilon=eps, sigma=sigma, adds=adds, grad=sum(a["grad"] for a in adds), norm=norm, img_bound=img,
+               pix_bound=pix, kappa=max(float(a["kappa"].max()) for a in adds))
+    return out
+
+
+def gradient_compare(c, data, acc, probe_grads, losses):
+    """the accumulator (nz, nx, ny) and per add the probe gradient (B, nx, ny) and the losses (B,) of a run against gradient_data ->
+    dict(slices=[(E_img, E_line, E_pix) over the norm], slices_of=[their ratios to the bounds], probe=[metrics() per add],
+    probe_of=[ratios], loss_of=[per add, (B,) ratios], worst=the largest ratio)"""
+    res = dict(slices=[], slices_of=[], probe=[], probe_of=[], loss_of=[])
+    for s in range(c.nz):
+        d = np.abs(np.asarray(acc[s], dtype=np.float64) - data["grad"][s])
+        line = max(np.sqrt((d ** 2).mean(axis=0)).max(), np.sqrt((d ** 2).mean(axis=1)).max())
+        rms = np.sqrt((d ** 2).mean())
+        res["slices"].append((rms / data["norm"][s], line / data["norm"][s], d.max() / data["norm"][s]))
+        res["slices_of"].append((rms / data["img_bound"][s], line / (LINE_FACTOR * data["img_bound"][s]), (d / data["pix_bound"][s]).max()))
+    for a, pg, L in zip(data["adds"], probe_grads, losses):
+        m = metrics(pg, a["probe"])
+        res["probe"].append(m)
+        res["probe_of"].append(tuple(v / (f * a["e_g"][0]) for v, f in zip(m, (1.0, LINE_FACTOR, PIXEL_FACTOR))))
+        res["loss_of"].append(np.abs(np.asarray(L) - a["loss"]) / a["loss_bound"])
+    res["worst"] = float(max([max(r) for r in res["slices_of"] + res["probe_of"]] + [r.max() for r in res["loss_of"]]))
+    return res
+
+
+def _gradient_run(eng, c, data):
+    probe_grads, losses = [], []
+    for a in data["adds"]:
+        eng.upload_probes(a["probes"])
+        L, pg = eng.adjoint_add(a["D"], B=a["B"], probe=True)
+        losses.append(L)
+        probe_grads.append(pg)
+    return eng.adjoint_download(), probe_grads, losses
+
+
+def gradient_case(c, restore=False):
+    """one engine: upload_potential, set_tilt (a tilted case), set_adjoint, then per add upload_probes and adjoint_add, and
+    adjoint_download -> gradient_compare's dict, with pitch and vec (adjoint_layout: the row pitch and whether the 16-byte step ran),
+    kappa, and for a tilted case moved = (rel-L2 of the accumulator, of the first probe gradient) against the UNTILTED reference on the
+    same data.  restore: then set_tilt(0, 0) and adjoint_reset on the same handle and the untilted case of the same grid ->
+    restored = its dict"""
+    from pyslice_amd.adjoint import LOSSES
+    data = gradient_data(c)
+    eng = engine(c.nx, c.ny, c.nz, c.P, fft_path=c.fft_path)
+    try:
+        eng.upload_probes(data["adds"][0]["probes"])
+        eng.upload_potential(data["V"])
+        if c.tilt is not None:
+            eng.set_tilt(*c.tilt)
+        eng.set_adjoint(LOSSES[c.loss], data["epsilon"], data["weight"])
+        pitch, vec = eng.adjoint_layout()
+        got = _gradient_run(eng, c, data)
+        res = gradient_compare(c, data, *got)
+        res.update(pitch=pitch, vec=vec, kappa=data["kappa"])
+        if c.tilt is not None:
+            res["moved"] = gradient_moved(c, data, got[0], got[1][0])
+        if restore:
+            flat = c._replace(tilt=None)
+            fdata = gradient_data(flat)
+            assert fdata["epsilon"] == data["epsilon"] or c.loss != "poisson"
+            eng.set_tilt(0.0, 0.0)
+            eng.adjoint_reset()
+            res["restored"] = gradient_compare(flat, fdata, *_gradient_run(eng, flat, fdata))
+    finally:
+        eng.close()
+    return res
+
+
+def gradient_moved(c, data, acc, probe_grad):
+    """(rel-L2 of an accumulator, of the first add's probe gradients) against the float64 definition WITHOUT the tilt on the case's
+    own probes, potential, data and weight: what a tilt that never reached the backward loop -- or the forward one -- would give"""
+    from pyslice_amd import adjoint as adj
+    from pyslice_amd.tilt import tilted_propagator
+    prop = tilted_propagator(c.nx, c.ny, DX, DY, orc.wavelength(EV), DZ, None)
+    w = None if data["weight"] is None else data["weight"].astype(np.float64)
+    grad, pg0 = 0.0, None
+    for a in data["adds"]:
+        g, _, pg = adj.potential_gradient(a["probes"][:a["B"]], data["V"].astype(np.float64), a["D"], data["sigma"], prop, c.loss, w, data["epsilon"])
+        grad, pg0 = grad + g, pg if pg0 is None else pg0
+    return _rel_l2(acc, grad), _rel_l2(probe_grad, pg0)
+
+
+def gradient_main(out_path):
+    """every GRAD_* case -> the figures and their ratios to the bounds, per case"""
+    rows = ["White-spectrum parity of the slice loop backwards (tools/white_parity.py --gradient-only): white probes, white potentials, white",
+            "data and weights through msl_adjoint_add against pyslice_amd/adjoint.py in float64.  Per case the worst figure over the slices",
+            "of the accumulator (E_img, E_line, E_pix over 2 sigma sqrt(sum_p mean|g_p|^2 mean|phi_p|^2)), over the probe gradients",
+            "(metrics()) and the largest ratio of each to its bound (gradient_data's docstring); loss: the largest |got - want| / bound.",
+            "The bounds of tests/test_gpu_white_gradient.py are not taken from this file.", "",
+            f"{'list':12s} {'case':44s} {'pitch':>5s} {'vec':>5s} {'kappa':>5s}   acc: E_img E_line E_pix   of bound: img line pix | probe of bound: img line pix | loss | moved"]
+    bad = 0
+    cases = [(name, c, False) for name, cases in GRADIENT_LISTS for c in cases] + [("restore", GRAD_RESTORE_CASE, True)]
+    for name, c, restore in cases:
+        res = gradient_case(c, restore=restore)
+        for tag, r in ((gradient_id(c), res),) + ((("(0, 0) again", res["restored"]),) if restore else ()):
+            sl, so = np.max(r["slices"], axis=0), np.max(r["slices_of"], axis=0)
+            po, lo = np.max(r["probe_of"], axis=0), max(v.max() for v in r["loss_of"])
+            bad += not r["worst"] <= 1.0
+            moved = " ".join(f"{v:.2f}" for v in res["moved"]) if "moved" in res and r is res else "-"
+            rows.append(f"{name:12s} {tag:44s} {res['pitch']:5d} {str(res['vec']):>5s} {res['kappa']:5.2f}   " + " ".join(f"{v:.2e}" for v in sl) + "   " +
+                        " ".join(f"{v:.3f}" for v in so) + " | " + " ".join(f"{v:.3f}" for v in po) + f" | {lo:.3f} | {moved}" + ("" if r["worst"] <= 1.0 else " <-- ABOVE"))
+            print(rows[-1], flush=True)
+    rows += ["", f"{len(cases)} cases, {bad} results above a bound"]
+    text = "\n".join(rows) + "\n"
+    if out_path:
+        with open(out_path, "w") as f:
+            f.write(text)
+    return 1 if bad else 0
+
+
 if __name__ == "__main__":
+    if "--gradient-only" in sys.argv[1:]:
+        args = [a for a in sys.argv[1:] if a != "--gradient-only"]
+        sys.exit(gradient_main(args[0] if args else None))
     if "--output-only" in sys.argv[1:]:
         args = [a for a in sys.argv[1:] if a != "--output-only"]
         sys.exit(output_main(args[0] if args else None))
