@@ -454,6 +454,31 @@ int  msl_adjoint_positions(msl_handle* h, const double* gamma, double* out);
 int64_t msl_adjoint_positions_rows(const msl_handle* h);
 int  msl_adjoint_positions_time(msl_handle* h, int32_t reps, double* ms_chain);
 
+/* ---- gradients with respect to scan positions and probe aberrations: the probe recipe backwards ----
+ * msl_set_probes builds psi0_p = ifft2(Phi_p), Phi_p(k) = A(k) exp(2 pi i (t_ramp,p(k) - chi(k) / 2 pi)): the strict aperture |k| < radius,
+ * t_ramp,p = fx (floor(nx/2)/nx + x_p/Lx) + fy (floor(ny/2)/ny + y_p/Ly) on signed frequency indices, and chi / 2 pi = sum_j (a_j A_j(k) +
+ * b_j B_j(k)) in the Cartesian form of msl_set_aberrations' fourteen terms.  With g0 = dL/dpsi0_p*, ghat = fft2(g0) (unnormalised),
+ * N = nx ny and m_p(k) = Im(conj(ghat(k)) Phi_p(k)),
+ *     dL/dx_p = -(4 pi / N) sum_k kx m_p(k),     dL/da_j = +(4 pi / N) sum_k A_j(k) m_p(k)     (ky, B_j likewise)
+ * (pyslice_amd/adjoint.py: probe_parameter_gradient is the definition).
+ * msl_adjoint_probe_params:  out: (B, 30) float64 on the host; per probe dL/dx, dL/dy (per Angstrom), then fourteen pairs (dL/da_j,
+ *   dL/db_j) of that probe's share, b of the three m = 0 terms zero -- the lens is shared, so the derivative of the total loss is the
+ *   sum over the probes.  g0 == NULL takes the probe gradient that the last msl_adjoint_add left in the work buffer (MSL_ERR_STATE
+ *   without one of at least B images); else g0 is the caller's (B, nx, ny) c64 on the host, uploaded into the work buffer at its
+ *   pitch -- msl_set_adjoint is not needed then.  Runs the handle's own 2-D FFT on the work buffer and probe_moment_kernel over the
+ *   aperture's bounding box, float64 sums, no atomics: the same calls give the same bits.  The work buffer ends as the transforms
+ *   (MSL_BUF_EXIT is stale, and so is the probe gradient).  Synchronous.
+ *   Only probes built by msl_set_probes with mrad > 0 have a recipe: MSL_ERR_STATE, naming the missing call, after
+ *   msl_upload_probes, msl_shift_probes, msl_set_probe_members, msl_smatrix_build / msl_smatrix_probes, msl_resize_probes, a later
+ *   msl_set_aberrations or a changed wavelength (msl_set_beam) until the next msl_set_probes, and for plane waves.  The kernel reads
+ *   the coefficients, the wavelength and the positions that msl_set_probes used, kept with the flag.  B outside [1, n_probes] or a
+ *   NULL out: MSL_ERR_INVALID.
+ * msl_adjoint_probe_params_time:  the chain (transform, kernel, sums) on the n_probes images of the work buffer as it stands, once
+ *   untimed and then `reps` times between two events; ms_chain = the mean device time of one chain in ms.  For benchmarks.
+ * Not in the reference. */
+int  msl_adjoint_probe_params(msl_handle* h, const void* g0_c64_or_null, int32_t B, double* out);
+int  msl_adjoint_probe_params_time(msl_handle* h, int32_t reps, double* ms_chain);
+
 /* TACAW: intensity[p,w,kx,ky] = | fftshift_t fft_t( Psi - <Psi>_t ) |^2 over a (B,T,npix) c64 device
  * array.  src == NULL uses the handle's own wavefunction buffer (B=P, T=T_local, npix=nx*ny) and
  * its own intensity buffer.  With src/dst given (device pointers, e.g. the output of an RCCL

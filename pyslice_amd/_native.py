@@ -55,6 +55,7 @@ EXPORTS = [
     "msl_set_probe_members", "msl_diffract_members", "msl_dose_add_members",
     "msl_set_adjoint", "msl_adjoint_reset", "msl_adjoint_add", "msl_adjoint_download", "msl_adjoint_step_time", "msl_adjoint_layout",
     "msl_adjoint_positions", "msl_adjoint_positions_rows", "msl_adjoint_positions_time",
+    "msl_adjoint_probe_params", "msl_adjoint_probe_params_time",
 ]
 DET_SIGNALS = {"intensity": 0, "amplitude": 1, "com_x": 2, "com_y": 3}      # include/mslice.h: MSL_DET_*
 MEMBERS_MAX = 128                                                          # include/mslice.h: MSL_MEMBERS_MAX
@@ -189,6 +190,8 @@ def load():
         "msl_adjoint_positions": (C.c_int, [vp, vp, vp]),
         "msl_adjoint_positions_rows": (C.c_int64, [vp]),
         "msl_adjoint_positions_time": (C.c_int, [vp, i32, vp]),
+        "msl_adjoint_probe_params": (C.c_int, [vp, vp, i32, vp]),
+        "msl_adjoint_probe_params_time": (C.c_int, [vp, i32, vp]),
         "msl_set_ionization": (C.c_int, [vp, i32, vp, vp, vp]),
         "msl_ionization_fetch": (C.c_int, [vp, i32, vp]),
         "msl_ionization_reduce": (C.c_int, [vp, i32, i32, vp, vp]),
@@ -457,6 +460,29 @@ class Engine:
         `reps` chains in ms"""
         ms = C.c_double(0.0)
         self._chk(self._lib.msl_adjoint_positions_time(self._h, int(reps), C.byref(ms)))
+        return float(ms.value)
+
+    def adjoint_probe_params(self, g0=None, B=None):
+        """(B, 30) float64: per probe dL/dx, dL/dy, then the fourteen pairs (dL/da_j, dL/db_j) of its share (msl_adjoint_probe_params;
+        the definition is adjoint.probe_parameter_gradient) for the probes the last set_probes built: from g0 (B, nx, ny) complex64 =
+        dL/dpsi0*, or with g0=None from the probe gradient the last adjoint_add left in the work buffer"""
+        g = None
+        if g0 is not None:
+            g = np.ascontiguousarray(g0, dtype=np.complex64)
+            if g.ndim == 2:
+                g = g[None]
+            if g.shape[1:] != (self.nx, self.ny) or (B is not None and int(B) != g.shape[0]):
+                raise ValueError(f"g0 must be ({'B' if B is None else int(B)},{self.nx},{self.ny}), got {g.shape}")
+        b = g.shape[0] if g is not None else (int(B) if B else self.n_probes)
+        out = np.zeros((max(b, 1), 30), dtype=np.float64)
+        self._chk(self._lib.msl_adjoint_probe_params(self._h, None if g is None else _ptr(g), b, _ptr(out)))
+        return out[:b]
+
+    def adjoint_probe_params_time(self, reps=1):
+        """the chain of adjoint_probe_params() alone on the work buffer as it stands (msl_adjoint_probe_params_time) -> mean device
+        time of one of the `reps` chains in ms"""
+        ms = C.c_double(0.0)
+        self._chk(self._lib.msl_adjoint_probe_params_time(self._h, int(reps), C.byref(ms)))
         return float(ms.value)
 
     def set_slices(self, lo, hi):

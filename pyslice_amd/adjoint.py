@@ -228,13 +228,154 @@ def position_directional_check(xs, ys, zs, positions, Z, probes, data, sigma, pr
     return fd, float((position_gradient(xs, ys, zs, pos, Z, dLdV, slice_axis) * d).sum())
 
 
+# ---- gradients with respect to scan positions and probe aberrations: the probe recipe backwards ----
+# The device builds (probe_kspace_kernel / probe_kspace_aberr_kernel) psi0_p = ifft2(Phi_p),
+#     Phi_p(k) = A(k) exp(2 pi i (t_p(k) - chi(k) / 2 pi)),
+#     A          the strict aperture rule sqrt(kx^2 + ky^2) < mrad 1e-3 / lambda, kx = fx / Lx, ky = fy / Ly on signed indices fx, fy
+#                (fftfreq's: on an even length the Nyquist line is f = -n/2),
+#     t_p        = fx (floor(nx/2)/nx + x_p/Lx) + fy (floor(ny/2)/ny + y_p/Ly),
+#     chi / 2 pi = sum_j a_j A_j(k) + b_j B_j(k),   A_j = (alpha^2)^((n+1-m)/2) Re z^m,  B_j = ... Im z^m,  z = lambda (kx + i ky),
+#     (a_j, b_j) = C_nm (cos, sin)(m phi_nm) / ((n + 1) lambda)                                        (aberration.h, fourteen terms).
+# With g0 = dL/dpsi0* (dL = 2 Re sum_r conj(g0) dpsi0), ghat = fft2(g0) and N = nx ny: dpsi0 = ifft2(dPhi) gives
+# dL = (2/N) Re sum_k conj(ghat) dPhi.  dPhi/dx_p = 2 pi i kx Phi, dPhi/da_j = -2 pi i A_j Phi, and Re(i w) = -Im(w), so with the real
+# field m_p(k) = Im(conj(ghat(k)) Phi_p(k))
+#     dL/dx_p = -(4 pi / N) sum_k kx m_p(k),     dL/da_j = +(4 pi / N) sum_p sum_k A_j(k) m_p(k)     (ky and B_j likewise);
+#     dL/dC_nm   = (cos(m phi) dL/da + sin(m phi) dL/db) / ((n + 1) lambda),
+#     dL/dphi_nm = m C_nm / ((n + 1) lambda) (-sin(m phi) dL/da + cos(m phi) dL/db).
+# The ramp is differentiated as it is built: on an even length the Nyquist line carries kx = -n/(2 Lx) and no mirror image.
+
+def _probe_grid(nx, ny, dx, dy):
+    fx = np.rint(np.fft.fftfreq(nx, 1.0 / nx))[:, None]
+    fy = np.rint(np.fft.fftfreq(ny, 1.0 / ny))[None, :]
+    return fx, fy, fx * (1.0 / (nx * dx)), fy * (1.0 / (ny * dy))
+
+
+def aberration_cartesian(aberrations, wavelength):
+    """(14, 2) float64: (a_j, b_j) of an Aberrations (None: zeros), as probe_aberrations (aberration.h) makes them"""
+    from .aberrations import TERMS
+    out = np.zeros((14, 2), dtype=np.float64)
+    if aberrations is not None:
+        for j, ((name, n, m), (c, phi)) in enumerate(zip(TERMS, aberrations.as_polar())):
+            w = c / ((n + 1) * wavelength)
+            out[j] = (w * np.cos(m * phi), w * np.sin(m * phi)) if m else (w, 0.0)
+    return out
+
+
+def aberration_basis(kx, ky, wavelength):
+    """(14, 2, nx, ny) float64: A_j(k) and B_j(k), the factors of a_j and b_j in chi / 2 pi (B of an m = 0 term is zero)"""
+    from .aberrations import TERMS
+    z = wavelength * (kx + 1j * ky)
+    r2 = np.abs(z) ** 2
+    out = np.zeros((14, 2) + z.shape, dtype=np.float64)
+    for j, (name, n, m) in enumerate(TERMS):
+        zm = r2 ** ((n + 1 - m) // 2) * z ** m
+        out[j, 0], out[j, 1] = zm.real, zm.imag
+    return out
+
+
+def probe_aperture(nx, ny, dx, dy, wavelength, mrad):
+    """(nx, ny) bool: the strict aperture rule of the probe kernels"""
+    _, _, kx, ky = _probe_grid(nx, ny, dx, dy)
+    return np.sqrt(kx * kx + ky * ky) < (mrad * 1e-3) / wavelength
+
+
+def probe_spectrum(nx, ny, dx, dy, wavelength, mrad, xy, aberrations=None, cartesian=None):
+    """Phi (P, nx, ny) complex128 of the probes at xy (P, 2): ifft2 of it is what msl_set_probes builds.  aberrations: an Aberrations
+    or None; cartesian: (14, 2) coefficients (a_j, b_j) in its place"""
+    xy = np.asarray(xy, dtype=np.float64).reshape(-1, 2)
+    fx, fy, kx, ky = _probe_grid(nx, ny, dx, dy)
+    ab = aberration_cartesian(aberrations, wavelength) if cartesian is None else np.asarray(cartesian, dtype=np.float64)
+    chi = np.tensordot(ab, aberration_basis(kx, ky, wavelength), axes=([0, 1], [0, 1]))
+    t = (fx * ((nx // 2) / nx + xy[:, 0, None, None] / (nx * dx)) + fy * ((ny // 2) / ny + xy[:, 1, None, None] / (ny * dy))) - chi[None]
+    return probe_aperture(nx, ny, dx, dy, wavelength, mrad)[None] * np.exp(2j * np.pi * (t - np.rint(t)))
+
+
+def _probe_moment_fields(g0, nx, ny, dx, dy, wavelength, mrad, xy, aberrations, cartesian):
+    g0 = np.asarray(g0, dtype=np.complex128)
+    if g0.ndim == 2:
+        g0 = g0[None]
+    Phi = probe_spectrum(nx, ny, dx, dy, wavelength, mrad, xy, aberrations, cartesian)
+    if g0.shape != Phi.shape:
+        raise ValueError(f"probe_parameter_gradient: g0 {g0.shape} does not match the probes {Phi.shape}")
+    _, _, kx, ky = _probe_grid(nx, ny, dx, dy)
+    ghat = np.fft.fft2(g0, axes=_AX)
+    return ghat, Phi, kx + 0 * ky, ky + 0 * kx, aberration_basis(kx, ky, wavelength)
+
+
+def probe_parameter_gradient(g0, nx, ny, dx, dy, wavelength, mrad, xy, aberrations=None, cartesian=None):
+    """g0 (P, nx, ny) complex = dL/dpsi0* -> (pos (P, 2) = dL/d(x_p, y_p), cart (14, 2) = dL/d(a_j, b_j) summed over the probes, which
+    share the lens, per_probe (P, 14, 2)), float64, by the formulas above"""
+    ghat, Phi, kx, ky, basis = _probe_moment_fields(g0, nx, ny, dx, dy, wavelength, mrad, xy, aberrations, cartesian)
+    m = (np.conj(ghat) * Phi).imag
+    c = 4.0 * np.pi / (nx * ny)
+    pos = -c * np.stack([(kx[None] * m).sum(axis=_AX), (ky[None] * m).sum(axis=_AX)], axis=1)
+    per = c * np.einsum("jcxy,pxy->pjc", basis, m)
+    return pos, per.sum(axis=0), per
+
+
+def probe_parameter_bound(g0, nx, ny, dx, dy, wavelength, mrad, tol, ghat=None):
+    """(pos (P, 2), cart (P, 14, 2)): (4 pi / N) ||b A||_2 tol ||ghat_p||_2 + 1e-12 sum_k |b| |ghat_p| over the aperture A, per probe and
+    basis function b (kx, ky, A_j, B_j) -- Cauchy-Schwarz on the moment of a transform that carries the relative L2 error tol; the
+    second term is the float64 sum's own.  ghat: the transforms themselves in place of g0"""
+    if ghat is None:
+        ghat = np.fft.fft2(np.asarray(g0, dtype=np.complex128), axes=_AX)
+    ghat = np.abs(ghat if ghat.ndim == 3 else ghat[None])
+    _, _, kx, ky = _probe_grid(nx, ny, dx, dy)
+    A = probe_aperture(nx, ny, dx, dy, wavelength, mrad)
+    b = np.concatenate([np.stack([kx + 0 * ky, ky + 0 * kx]), aberration_basis(kx, ky, wavelength).reshape(28, nx, ny)]) * A[None]
+    norm = np.sqrt((ghat ** 2).sum(axis=_AX))
+    out = (4.0 * np.pi / (nx * ny)) * np.sqrt((b ** 2).sum(axis=_AX))[None, :] * tol * norm[:, None] \
+        + 1e-12 * np.einsum("bxy,pxy->pb", np.abs(b), ghat)
+    return out[:, :2], out[:, 2:].reshape(-1, 14, 2)
+
+
+def aberration_polar_gradient(cart, aberrations, wavelength):
+    """cart (14, 2) = dL/d(a_j, b_j) -> (dC (14,), dphi (14,)): dL/dC_nm per Angstrom and dL/dphi_nm per radian at `aberrations`
+    (None: all zero, where dphi is zero and dC is dL/da)"""
+    from .aberrations import TERMS
+    cart = np.asarray(cart, dtype=np.float64)
+    polar = np.zeros((14, 2)) if aberrations is None else aberrations.as_polar()
+    dC, dphi = np.zeros(14), np.zeros(14)
+    for j, (name, n, m) in enumerate(TERMS):
+        c, phi = polar[j]
+        w = 1.0 / ((n + 1) * wavelength)
+        dC[j] = (np.cos(m * phi) * cart[j, 0] + np.sin(m * phi) * cart[j, 1]) * w
+        dphi[j] = m * c * w * (-np.sin(m * phi) * cart[j, 0] + np.cos(m * phi) * cart[j, 1])
+    return dC, dphi
+
+
+def probe_loss(nx, ny, dx, dy, wavelength, mrad, xy, V, data, sigma, prop, aberrations=None, cartesian=None, loss="amplitude",
+               weight=None, epsilon=1e-20):
+    """the total loss of the patterns of the probes of this recipe"""
+    probes = np.fft.ifft2(probe_spectrum(nx, ny, dx, dy, wavelength, mrad, xy, aberrations, cartesian), axes=_AX)
+    return total_loss(probes, V, data, sigma, prop, loss, weight, epsilon)
+
+
+def probe_directional_check(nx, ny, dx, dy, wavelength, mrad, xy, V, data, sigma, prop, d_xy, d_cart, h, aberrations=None, cartesian=None,
+                            loss="amplitude", weight=None, epsilon=1e-20):
+    """(fd, inner): the central difference of the total loss under xy +- h d_xy (P, 2) and Cartesian coefficients +- h d_cart (14, 2),
+    and <grad, d> from probe_parameter_gradient of potential_gradient's probe gradient"""
+    xy = np.asarray(xy, dtype=np.float64).reshape(-1, 2)
+    ab = aberration_cartesian(aberrations, wavelength) if cartesian is None else np.asarray(cartesian, dtype=np.float64)
+    d_xy, d_cart = np.asarray(d_xy, dtype=np.float64), np.asarray(d_cart, dtype=np.float64)
+    kw = dict(loss=loss, weight=weight, epsilon=epsilon)
+    L = lambda s: probe_loss(nx, ny, dx, dy, wavelength, mrad, xy + s * d_xy, V, data, sigma, prop, cartesian=ab + s * d_cart, **kw)
+    fd = (L(h) - L(-h)) / (2.0 * h)
+    probes = np.fft.ifft2(probe_spectrum(nx, ny, dx, dy, wavelength, mrad, xy, cartesian=ab), axes=_AX)
+    g0 = potential_gradient(probes, V, data, sigma, prop, **kw)[2]
+    pos, cart, _ = probe_parameter_gradient(g0, nx, ny, dx, dy, wavelength, mrad, xy, cartesian=ab)
+    return fd, float((pos * d_xy).sum() + (cart * d_cart).sum())
+
+
 class Gradient:
     """MultisliceCalculator(gradient=Gradient(...)): run_gradient(data) returns dL/dV of the loss between the run's exit patterns
     and `data`.  loss: "amplitude", "intensity" or "poisson"; weight: (nx, ny) >= 0 in the detector's layout, or None; epsilon: the
     floor of |Psi|^2 in the amplitude and Poisson residuals; probe=True also returns dL/dpsi_0* per probe; positions=True also
-    returns dL/dr_a per atom (GradientData.positions: the potential build backwards, section 4.32)."""
+    returns dL/dr_a per atom (GradientData.positions: the potential build backwards, section 4.32); probe_positions=True and
+    aberrations=True also return dL/d(x_p, y_p) per scan position and dL/dC_nm, dL/dphi_nm of the probe-forming lens
+    (GradientData.probe_position_gradient / .aberration_gradient: the probe recipe backwards, section 4.33)."""
 
-    def __init__(self, loss="amplitude", weight=None, epsilon=1e-20, probe=False, positions=False):
+    def __init__(self, loss="amplitude", weight=None, epsilon=1e-20, probe=False, positions=False, probe_positions=False, aberrations=False):
         _check_loss(loss)
         with np.errstate(over="ignore", under="ignore"):
             e32 = np.float32(epsilon)                           # (what the kernels hold: it must not round to zero or overflow there)
@@ -247,6 +388,12 @@ class Gradient:
             weight.setflags(write=False)
         self.loss, self.weight, self.epsilon, self.probe = loss, weight, float(epsilon), bool(probe)
         self.positions = bool(positions)
+        self.probe_positions, self.aberrations = bool(probe_positions), bool(aberrations)
+
+    @property
+    def probe_params(self):
+        """the run goes on through the probe recipe (msl_adjoint_probe_params)"""
+        return self.probe_positions or self.aberrations
 
     @property
     def kind(self):
@@ -254,4 +401,5 @@ class Gradient:
 
     def __repr__(self):
         return (f"Gradient(loss={self.loss!r}, weight={'None' if self.weight is None else self.weight.shape}, epsilon={self.epsilon:g}, "
-                f"probe={self.probe}" + (", positions=True" if self.positions else "") + ")")
+                f"probe={self.probe}" + (", positions=True" if self.positions else "")
+                + (", probe_positions=True" if self.probe_positions else "") + (", aberrations=True" if self.aberrations else "") + ")")

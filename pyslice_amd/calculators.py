@@ -1078,13 +1078,13 @@ class MultisliceCalculator:
         """waves per scan position: the members of the Coherence, 1 without"""
         return 1 if getattr(self, "_coherence", None) is None else len(self.coherence_members[2])
 
-    def _probe_batches(self):
-        """(p0, real, xy) per probe batch: probes p0 .. p0+real-1, and their positions padded to the engine's probe count by
-        repeating the last one.  With a Coherence the engine's probes are waves, G per position: p0 and real count POSITIONS, a
+    def _probe_batches(self, positions=None):
+        """(p0, real, xy) per probe batch: probes p0 .. p0+real-1, and their positions (self.probe_positions, or `positions` in their
+        place) padded to the engine's probe count by repeating the last one.  With a Coherence the engine's probes are waves, G per position: p0 and real count POSITIONS, a
         batch holds n_probes / G of them, and xy holds the G member positions of each, xy[q G + g] = position q + offset g"""
         G = self._members_G()
         Pc = self._engine.n_probes // G
-        pos = np.asarray(self.probe_positions, dtype=np.float64).reshape(-1, 2)
+        pos = np.asarray(self.probe_positions if positions is None else positions, dtype=np.float64).reshape(-1, 2)
         for p0 in range(0, self.n_probes, Pc):
             xy = pos[p0:p0 + Pc]
             real = len(xy)
@@ -1397,7 +1397,7 @@ class MultisliceCalculator:
                                               incident=incident, frames=frames, camera=camera, coherence=getattr(self, "_coherence", None),
                                               **self._layer_fields()))
 
-    def run_gradient(self, data, frame=0, potential=None, positions=None):
+    def run_gradient(self, data, frame=0, potential=None, positions=None, probe_positions=None, aberrations=None):
         """The derivative of the data-fit loss of MultisliceCalculator(gradient=Gradient(...)) with respect to the slice potentials
         (adjoint.py is the definition): per probe batch msl_adjoint_add runs the forward loop, which keeps the wave arriving at every
         slice, the residual of the exit patterns against `data` and the loop backwards, and adds into a float64 accumulator on the
@@ -1408,7 +1408,13 @@ class MultisliceCalculator:
         caller's current coordinates, built in place of the trajectory frame (what a structure refinement passes at every step).
         With Gradient(positions=True) the chain goes on through the potential build (msl_adjoint_positions, on the accumulator and
         the phase tables the build left on the device): GradientData.positions is dL/dr_a, (n_atoms, 3) float64, the slice-axis
-        column zero.  potential= has no atoms: ValueError with positions= or with Gradient(positions=True).  -> GradientData."""
+        column zero.  potential= has no atoms: ValueError with positions= or with Gradient(positions=True).
+        With Gradient(probe_positions=True) / Gradient(aberrations=True) the chain also goes back through the probe recipe
+        (msl_adjoint_probe_params per batch, on the probe gradient msl_adjoint_add left on the device):
+        GradientData.probe_position_gradient is dL/d(x_p, y_p), (P, 2) float64 per Angstrom, and .aberration_gradient maps the names of
+        the Aberrations fields to dL/dC_nm per Angstrom and dL/dphi_nm per radian (section 4.33).  probe_positions: (P, 2) scan
+        positions and aberrations: an Aberrations, in place of those of setup() for this call (what a refinement passes at every
+        step); the engine's aberrations are put back afterwards, so a later run is what it was.  -> GradientData."""
         from .gradient_data import GradientData
         grad = getattr(self, "_gradient", None)
         if grad is None:
@@ -1435,6 +1441,19 @@ class MultisliceCalculator:
             positions = np.ascontiguousarray(positions, dtype=np.float64)
             if positions.shape != (len(self._Z), 3) or not np.isfinite(positions).all():
                 raise ValueError(f"gradient: positions {positions.shape} must be finite ({len(self._Z)}, 3) coordinates, one row per atom")
+        if grad.probe_params and not self.aperture > 0:
+            raise NotImplementedError("gradient: probe_positions / aberrations of plane-wave illumination (aperture=0) is not built")
+        scan = np.asarray(self.probe_positions, dtype=np.float64).reshape(-1, 2)
+        if probe_positions is not None:
+            try:
+                scan = np.ascontiguousarray(probe_positions, dtype=np.float64)
+            except (TypeError, ValueError):
+                raise ValueError(f"gradient: probe_positions must be ({self.n_probes}, 2) finite scan positions") from None
+            if scan.shape != (self.n_probes, 2) or not np.isfinite(scan).all():
+                raise ValueError(f"gradient: probe_positions {scan.shape} must be finite ({self.n_probes}, 2) scan positions, one row per probe")
+        if aberrations is not None and not isinstance(aberrations, Aberrations):
+            raise ValueError(f"gradient: aberrations: expected an Aberrations object, got {aberrations!r}")
+        lens = self._aberrations if aberrations is None else aberrations
         t0 = time.time()
         if potential is not None:
             V = np.asarray(potential)
@@ -1448,17 +1467,42 @@ class MultisliceCalculator:
         eng.adjoint_reset()
         loss = np.zeros(self.n_probes, dtype=np.float64)
         probe = np.zeros((self.n_probes, self.nx, self.ny), dtype=np.complex64) if grad.probe else None
-        for p0, real, xy in self._probe_batches():
-            self._set_probes(xy)
-            l, pg = eng.adjoint_add(data[p0:p0 + real], B=real, probe=grad.probe)
-            loss[p0:p0 + real] = l
-            if probe is not None:
-                probe[p0:p0 + real] = pg
+        params = np.zeros((self.n_probes, 30), dtype=np.float64) if grad.probe_params else None
+        if aberrations is not None:
+            eng.set_aberrations(aberrations)
+        try:
+            for p0, real, xy in self._probe_batches(None if probe_positions is None else scan):
+                self._set_probes(xy)
+                l, pg = eng.adjoint_add(data[p0:p0 + real], B=real, probe=grad.probe)
+                loss[p0:p0 + real] = l
+                if probe is not None:
+                    probe[p0:p0 + real] = pg
+                if params is not None:
+                    params[p0:p0 + real] = eng.adjoint_probe_params(B=real)
+        finally:
+            if aberrations is not None:
+                eng.set_aberrations(self._aberrations)
         g = np.ascontiguousarray(np.moveaxis(eng.adjoint_download(), 0, 2))
         pos_grad = eng.adjoint_positions() if grad.positions else None
         self.elapsed = time.time() - t0
+        extra = {}
+        if params is not None:
+            from .adjoint import aberration_polar_gradient
+            from .aberrations import TERMS
+            if grad.probe_positions:
+                extra["probe_position_gradient"] = np.ascontiguousarray(params[:, :2])
+            if grad.aberrations:
+                cart = params[:, 2:].sum(axis=0).reshape(14, 2)
+                dC, dphi = aberration_polar_gradient(cart, lens, wavelength(self.voltage_eV))
+                named = {}
+                for j, (name, n, m) in enumerate(TERMS):
+                    named[name] = float(dC[j])
+                    if m:
+                        named["phi" + name[1:]] = float(dphi[j])
+                extra.update(aberration_gradient=named, aberration_gradient_cartesian=cart)
         return GradientData(potential=g, loss=loss, sigma=interaction_sigma(self.voltage_eV), xs=self.xs, ys=self.ys, zs=self._slice_coords,
-                            probe=probe, kind=grad.loss, frame=int(frame), probe_positions=self.probe_positions, positions=pos_grad)
+                            probe=probe, kind=grad.loss, frame=int(frame),
+                            probe_positions=self.probe_positions if probe_positions is None else scan, positions=pos_grad, **extra)
 
     def run_images(self):
         """Frame-averaged images behind the objective lens (HRTEM, focal series), for every probe: probe batches outside, frame

@@ -7,6 +7,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "aberration.h"
 
 namespace msl {
 
@@ -286,6 +287,81 @@ __global__ void __launch_bounds__(256) position_gradient_kernel(const int4* __re
             if (atom >= 0)
                 out[(size_t)atom * 3 + (comp ? ax2 : ax1)] = c * (((sh_red[0][a][comp] + sh_red[1][a][comp]) + sh_red[2][a][comp]) + sh_red[3][a][comp]);
         }
+    }
+}
+
+// ---- gradients with respect to scan positions and probe aberrations: the probe recipe backwards ----
+// msl_set_probes builds psi0_p = ifft2(Phi_p), Phi_p(k) = A(k) exp(2 pi i (t_ramp,p(k) - chi(k) / 2 pi)) (probe_kspace_aberr_kernel).  With
+// g0 = dL/dpsi0_p*, ghat = fft2(g0) (unnormalised) and the real field m_p(k) = Im(conj(ghat(k)) Phi_p(k)) over the aperture,
+//     dL/dx_p = -(4 pi / N) sum_k kx m_p(k),     dL/da_j = +(4 pi / N) sum_k A_j(k) m_p(k)     (and ky, B_j likewise),
+// A_j, B_j the factors of the coefficients in chi / 2 pi (aberration_basis).  The kernel forms the 27 sums without the factor: kx, ky, the
+// fourteen A_j and the eleven B_j of the terms with m > 0, in that order (PM_SLOTS).
+
+constexpr int PM_SLOTS = 27;
+constexpr int PM_B_TERM[11] = {1, 2, 3, 5, 6, 7, 8, 9, 11, 12, 13};     // the terms with m > 0: slot 16 + k holds B of term PM_B_TERM[k]
+constexpr int PM_PER = 4, PM_TILE = 256 * PM_PER;      // box pixels per lane and per tile
+
+// the aperture's bounding box in wrapped index space: the signed frequencies lo .. lo + w - 1 of an axis
+struct ProbeBox {
+    int x_lo, wx, y_lo, wy;
+};
+
+// ghat: (B, nx, pitch) c64.  A workgroup owns tile blockIdx.x of the box's wx * wy pixels (rows of the box in order) of probe
+// blockIdx.y; a lane takes PM_PER of them, recomputes Phi_p(k) in float64 as probe_kspace_aberr_kernel does (the same ramp, the same
+// polynomial, the same reduction to one turn, the same aperture test; ab is all zero without aberrations) and adds m and its
+// products with the basis into 27 float64 sums.  The sums are combined over a wave by shuffles and over the four waves through the
+// LDS in wave order; part[(tile * B + probe) * 27 + slot].  No atomics: the same input gives the same bits.
+__global__ void __launch_bounds__(256) probe_moment_kernel(const float2* __restrict__ ghat, const double* __restrict__ xy, int B, int nx, int ny,
+                                                           int pitch, ProbeBox box, double inv_lx, double inv_ly, double kfreq_x, double kfreq_y,
+                                                           double radius, double wavelength, ProbeAberrations ab, double* __restrict__ part) {
+    __shared__ double lds[4][PM_SLOTS];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int p = blockIdx.y;
+    const long long nbox = (long long)box.wx * box.wy;
+    const float2* img = ghat + (long long)p * nx * pitch;
+    const double px = xy[2 * p], py = xy[2 * p + 1];
+    double acc[PM_SLOTS];
+#pragma unroll
+    for (int k = 0; k < PM_SLOTS; ++k) acc[k] = 0.0;
+    for (int s = 0; s < PM_PER; ++s) {
+        const long long q = (long long)blockIdx.x * PM_TILE + (long long)s * 256 + threadIdx.x;
+        if (q >= nbox) continue;
+        const int i = (int)(q / box.wy), j = (int)(q - (long long)i * box.wy);
+        const int fx = box.x_lo + i, fy = box.y_lo + j;                 // signed frequency indices
+        const int mx = fx < 0 ? fx + nx : fx, my = fy < 0 ? fy + ny : fy;
+        const double kx = fx * kfreq_x, ky = fy * kfreq_y;
+        if (!(sqrt(kx * kx + ky * ky) < radius)) continue;
+        const double ax = wavelength * kx, ay = wavelength * ky;
+        const AberrationPowers w = aberration_powers(ax, ay);
+        double t = fx * ((double)(nx / 2) / nx + px * inv_lx) + fy * ((double)(ny / 2) / ny + py * inv_ly);
+        t -= aberration_chi_turns(w, ax, ay, ab, ab.a[0]);
+        t -= rint(t);
+        double sn, cs;
+        sincospi(2.0 * t, &sn, &cs);
+        const float2 g = img[(long long)mx * pitch + my];
+        const double m = (double)g.x * sn - (double)g.y * cs;          // Im(conj(ghat) Phi)
+        double A[14], Bm[14];
+        aberration_basis(w, A, Bm);
+        acc[0] = fma(kx, m, acc[0]);
+        acc[1] = fma(ky, m, acc[1]);
+#pragma unroll
+        for (int k = 0; k < 14; ++k) acc[2 + k] = fma(A[k], m, acc[2 + k]);
+#pragma unroll
+        for (int k = 0; k < 11; ++k) acc[16 + k] = fma(Bm[PM_B_TERM[k]], m, acc[16 + k]);
+    }
+#pragma unroll
+    for (int k = 0; k < PM_SLOTS; ++k) {
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) acc[k] += __shfl_xor(acc[k], o, 64);
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < PM_SLOTS; ++k) lds[wave][k] = acc[k];
+    }
+    __syncthreads();
+    if (threadIdx.x < PM_SLOTS) {
+        const int k = threadIdx.x;
+        part[((long long)blockIdx.x * B + p) * PM_SLOTS + k] = ((lds[0][k] + lds[1][k]) + lds[2][k]) + lds[3][k];
     }
 }
 

@@ -331,6 +331,17 @@ struct msl_handle {
     DevBuf<int4> pg_tiles;
     DevBuf<float2> pg_img;
     DevBuf<double> pg_gamma, pg_out;
+    // gradients with respect to scan positions and aberrations (msl_adjoint_probe_params): pm_valid while the
+    // probe buffer holds what msl_set_probes built at a convergent aperture (drop_probe_recipe clears it), with the recipe that call
+    // used -- the aperture, the wavelength, the Cartesian coefficients (all zero without aberrations) and the positions (pm_dxy, on the device) -- so that a
+    // later msl_set_aberrations or msl_set_beam cannot come between the probes and their derivative; pm_g: the images of the work
+    // buffer that hold the probe gradient of the last msl_adjoint_add (0: none); the partial rows and the sums (B, PM_SLOTS), grown
+    // on demand
+    bool pm_valid = false;
+    int pm_g = 0;
+    double pm_mrad = 0.0, pm_wavelength = 0.0;
+    ProbeAberrations pm_ab{};
+    DevBuf<double> pm_dxy, pm_part, pm_sums;
     // frozen phonons (msl_set_structure): the base structure resident on the device -- positions (n, 3), widths, Z and the species
     // maps that stage_atoms sends per call -- with the host's copy of the maps and the axes; msl_build_thermal generates the
     // positions of any configuration from it (thermal_positions_kernel), so no per-frame array and no caller pointer is kept
@@ -1477,6 +1488,7 @@ int slice_loop(msl_handle* h, int fused_slot, int groups, int first_group, bool 
     const msl_config& c = h->cfg;
     const bool tds = signal && h->tds_on, ion = signal && !tds;
     const bool sums = signal || store;                      // the split row step with the hook between its halves
+    h->pm_g = 0;                                            // the work buffer is rewritten
     if (store && (signal || !h->adj_on || groups != 1 || h->onepass))
         return fail(h, MSL_ERR_STATE, "adjoint: the slice loop needs one frame per launch on the two-pass loop");
     if (signal && (groups != 1 || h->onepass))
@@ -1618,6 +1630,7 @@ int adjoint_add(msl_handle* h, const float* data, int B, double* loss_out, float
         HIPCHK(h, hipMemcpy2DAsync(probe_grad, (size_t)c.ny * sizeof(float2), g, (size_t)h->pitch * sizeof(float2), (size_t)c.ny * sizeof(float2),
                                    (size_t)B * c.nx, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
+    h->pm_g = B;                                            // the probe gradient of B images: what msl_adjoint_probe_params(NULL) reads
     return MSL_OK;
 }
 
@@ -2600,6 +2613,7 @@ int msl_set_beam(msl_handle* h, double wavelength, double sigma, double dz) {
     if (!h) return fail(h, MSL_ERR_INVALID, "null handle");
     if (!(wavelength > 0)) return fail(h, MSL_ERR_INVALID, "msl_set_beam: wavelength must be positive");
     HIPCHK(h, hipSetDevice(h->cfg.device));
+    if (wavelength != h->cfg.wavelength) h->pm_valid = false;      // until the next msl_set_probes
     h->cfg.wavelength = wavelength; h->cfg.sigma = sigma; h->cfg.dz = dz;
     if (h->sm_open) {                                       // the wavelength changes the beam set
         HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -2844,6 +2858,7 @@ int msl_adjoint_step_time(msl_handle* h, int32_t slice, int32_t reps, double* ms
     if (reps < 1) return fail(h, MSL_ERR_INVALID, "msl_adjoint_step_time: reps must be positive");
     HIPCHK(h, hipSetDevice(h->cfg.device));
     h->cur = nullptr;
+    h->pm_g = 0;
     double ms = 0.0;
     EventPair timer;
     int rc = adjoint_step_launch(h, h->psi, slice, h->cfg.n_probes);            // one untimed launch first
@@ -2917,6 +2932,114 @@ int msl_adjoint_positions_time(msl_handle* h, int32_t reps, double* ms_chain) {
         return rc;
     }
     for (int r = 0; r < reps && rc == MSL_OK; ++r) rc = position_chain(h, d_gamma, tile_of);
+    if (rc || (rc = timer.end(h, &ms))) { (void)hipStreamSynchronize(h->stream); return rc; }
+    if (ms_chain) *ms_chain = ms / reps;
+    return MSL_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// ---- gradients with respect to scan positions and probe aberrations: the probe recipe backwards; adjoint.h ----
+// the aperture's bounding box on one axis: signed frequencies |f| <= radius / kfreq (one more on either side against the rounding of
+// the quotient -- the kernel's own test decides), cut to the axis' own range -(n / 2) .. (n - 1) / 2
+void probe_box_axis(int n, double kfreq, double radius, int* lo, int* w) {
+    const double q = radius / kfreq;
+    const int reach = q < (double)n ? (int)q + 1 : n;
+    const int a = std::max(-reach, -(n / 2)), b = std::min(reach, (n - 1) / 2);
+    *lo = a; *w = b - a + 1;
+}
+
+struct ProbeChain {
+    ProbeBox box;
+    long long tiles;
+};
+
+int probe_params_prepare(msl_handle* h, const char* who, int B, ProbeChain* pc) {
+    if (B < 1 || B > h->cfg.n_probes) return fail(h, MSL_ERR_INVALID, "%s: %d probes, the handle has %d", who, B, h->cfg.n_probes);
+    if (!h->pm_valid || !h->have_probes)
+        return fail(h, MSL_ERR_STATE, "%s: the probe buffer does not hold probes of msl_set_probes at a convergent aperture (mrad > 0) with the "
+                                      "aberrations and the wavelength of today: call msl_set_probes (msl_upload_probes, msl_shift_probes, "
+                                      "msl_set_probe_members, the PRISM calls, msl_resize_probes, msl_set_aberrations and a changed wavelength "
+                                      "drop the recipe this call differentiates)", who);
+    const msl_config& c = h->cfg;
+    const double radius = (h->pm_mrad * 1e-3) / h->pm_wavelength;
+    probe_box_axis(c.nx, 1.0 / (c.nx * c.dx), radius, &pc->box.x_lo, &pc->box.wx);
+    probe_box_axis(c.ny, 1.0 / (c.ny * c.dy), radius, &pc->box.y_lo, &pc->box.wy);
+    pc->tiles = ((long long)pc->box.wx * pc->box.wy + PM_TILE - 1) / PM_TILE;
+    if (pc->tiles > 0x7fffffffLL) return fail(h, MSL_ERR_UNSUPPORTED, "%s: too many tiles", who);
+    if (B > 65535) return fail(h, MSL_ERR_UNSUPPORTED, "%s: %d probes in one call, the grid takes 65535", who, B);
+    int rc;
+    if ((rc = h->pm_part.reserve(h, (size_t)pc->tiles * c.n_probes * PM_SLOTS)) || (rc = h->pm_sums.reserve(h, (size_t)c.n_probes * PM_SLOTS)))
+        return rc;
+    return MSL_OK;
+}
+
+// the work buffer's first B images -> their transforms in place, then pm_sums (B, PM_SLOTS): queued
+int probe_params_chain(msl_handle* h, int B, const ProbeChain& pc) {
+    const msl_config& c = h->cfg;
+    int rc;
+    if ((rc = fft2_inplace(h, h->psi, B, +1, 1.0f, h->pitch))) return rc;
+    hipLaunchKernelGGL(probe_moment_kernel, dim3((unsigned)pc.tiles, (unsigned)B), dim3(256), 0, h->stream, (const float2*)h->psi.p,
+                       (const double*)h->pm_dxy.p, B, c.nx, c.ny, h->pitch, pc.box, 1.0 / (c.nx * c.dx), 1.0 / (c.ny * c.dy), 1.0 / (c.nx * c.dx),
+                       1.0 / (c.ny * c.dy), (h->pm_mrad * 1e-3) / h->pm_wavelength, h->pm_wavelength, h->pm_ab, h->pm_part.p);
+    hipLaunchKernelGGL((slice_sums_finish_kernel<double, PM_SLOTS>), dim3((unsigned)((B * PM_SLOTS + 255) / 256)), dim3(256), 0, h->stream,
+                       (const double*)h->pm_part.p, pc.tiles, B, PM_SLOTS, h->pm_sums.p);
+    HIPCHK(h, hipGetLastError());
+    return mark_launch(h, K_OTHER);
+}
+
+}  // namespace
+
+extern "C" {
+
+int msl_adjoint_probe_params(msl_handle* h, const void* g0, int32_t B, double* out) {
+    if (!h || !out) return fail(h, MSL_ERR_INVALID, "msl_adjoint_probe_params: null argument");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    const msl_config& c = h->cfg;
+    ProbeChain pc;
+    int rc = probe_params_prepare(h, "msl_adjoint_probe_params", B, &pc);
+    if (rc) return rc;
+    if (!g0 && (h->pm_g < B || h->have_exit))
+        return fail(h, MSL_ERR_STATE, "msl_adjoint_probe_params: g0 == NULL needs the probe gradient of %d images that msl_adjoint_add leaves in the "
+                                      "work buffer (it holds %d)", B, h->have_exit ? 0 : h->pm_g);
+    h->cur = nullptr;
+    h->pm_g = 0; h->have_exit = false;                      // the work buffer ends as the transforms
+    if (g0)
+        HIPCHK(h, hipMemcpy2DAsync(h->psi, (size_t)h->pitch * sizeof(float2), g0, (size_t)c.ny * sizeof(float2), (size_t)c.ny * sizeof(float2),
+                                   (size_t)B * c.nx, hipMemcpyHostToDevice, h->stream));
+    if ((rc = probe_params_chain(h, B, pc))) { (void)hipStreamSynchronize(h->stream); return rc; }
+    std::vector<double> sums((size_t)B * PM_SLOTS);
+    HIPCHK(h, hipMemcpyAsync(sums.data(), h->pm_sums, sums.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    // per image the transform (32 B per pixel), the box's read of it, the partial rows and their sum
+    h->ctr.algorithmic_bytes += (uint64_t)B * ((uint64_t)c.nx * c.ny * 32ull + (uint64_t)pc.box.wx * pc.box.wy * 8ull + (uint64_t)pc.tiles * PM_SLOTS * 16ull);
+    const double f = 4.0 * M_PI / ((double)c.nx * c.ny);
+    for (int p = 0; p < B; ++p) {
+        const double* s = sums.data() + (size_t)p * PM_SLOTS;
+        double* o = out + (size_t)p * 30;
+        o[0] = -f * s[0]; o[1] = -f * s[1];
+        for (int j = 0; j < 14; ++j) { o[2 + 2 * j] = f * s[2 + j]; o[3 + 2 * j] = 0.0; }
+        for (int k = 0; k < 11; ++k) o[3 + 2 * PM_B_TERM[k]] = f * s[16 + k];
+    }
+    return MSL_OK;
+}
+
+int msl_adjoint_probe_params_time(msl_handle* h, int32_t reps, double* ms_chain) {
+    if (!h) return fail(h, MSL_ERR_INVALID, "msl_adjoint_probe_params_time: null handle");
+    if (reps < 1) return fail(h, MSL_ERR_INVALID, "msl_adjoint_probe_params_time: reps must be positive");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    ProbeChain pc;
+    const int B = h->cfg.n_probes;
+    int rc = probe_params_prepare(h, "msl_adjoint_probe_params_time", B, &pc);
+    if (rc) return rc;
+    h->cur = nullptr;
+    h->pm_g = 0; h->have_exit = false;
+    double ms = 0.0;
+    EventPair timer;
+    if ((rc = probe_params_chain(h, B, pc)) || (rc = timer.begin(h))) { (void)hipStreamSynchronize(h->stream); return rc; }
+    for (int r = 0; r < reps && rc == MSL_OK; ++r) rc = probe_params_chain(h, B, pc);
     if (rc || (rc = timer.end(h, &ms))) { (void)hipStreamSynchronize(h->stream); return rc; }
     if (ms_chain) *ms_chain = ms / reps;
     return MSL_OK;
@@ -3449,6 +3572,7 @@ int msl_resize_probes(msl_handle* h, int32_t n_probes) {
     if (rc) return rc;
     h->cfg.n_probes = n_probes;
     h->have_probes = false; h->have_exit = false;
+    h->pm_valid = false; h->pm_g = 0;
     return MSL_OK;
 }
 
@@ -3457,6 +3581,7 @@ int msl_shift_probes(msl_handle* h, const float* base, const double* xy, int32_t
     if (n_probes != h->cfg.n_probes) return fail(h, MSL_ERR_INVALID, "msl_shift_probes: %d probes, handle has %d", n_probes, h->cfg.n_probes);
     const msl_config& c = h->cfg;
     HIPCHK(h, hipSetDevice(c.device));
+    h->pm_valid = false;                                 // an array probe has no recipe to differentiate
     const size_t npix = (size_t)c.nx * c.ny;
     DevBuf<float2> bk;
     int rc = bk.alloc(h, npix);
@@ -3482,6 +3607,7 @@ int msl_shift_probes(msl_handle* h, const float* base, const double* xy, int32_t
 
 int msl_set_aberrations(msl_handle* h, const double* polar, int32_t n_terms) {
     if (!h) return fail(h, MSL_ERR_INVALID, "null handle");
+    h->pm_valid = false;                                 // the probes on the device are those of the earlier coefficients
     if (n_terms == 0) {
         memset(h->aberr_polar, 0, sizeof(h->aberr_polar));
         h->have_aberr = false;
@@ -3501,6 +3627,7 @@ int msl_set_aberrations(msl_handle* h, const double* polar, int32_t n_terms) {
 
 // the tail of every call that fills the probe buffer: the transposed copy the slice loop starts from, one wait, the flag
 static int finish_probes(msl_handle* h) {
+    h->pm_valid = false;                                 // (msl_set_probes sets it again behind this)
     int rc = transpose_probes(h);
     if (rc) return rc;
     HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -3533,7 +3660,19 @@ int msl_set_probes(msl_handle* h, double mrad, const double* xy, int32_t n_probe
                            n_probes, c.nx, c.ny, h->pitch, 1.0 / lx, 1.0 / ly, 1.0 / (c.nx * c.dx), 1.0 / (c.ny * c.dy),
                            (mrad * 1e-3) / c.wavelength, mrad == 0 ? 1 : 0);
     }
-    return finish_kspace_probes(h, n_probes);
+    const int rc = finish_kspace_probes(h, n_probes);
+    if (rc == MSL_OK && mrad > 0) {                      // the recipe of these probes, for msl_adjoint_probe_params
+        h->pm_mrad = mrad; h->pm_wavelength = c.wavelength;
+        if (h->have_aberr) h->pm_ab = probe_aberrations(h->aberr_polar[0], c.wavelength);
+        else h->pm_ab = ProbeAberrations{};
+        // the positions on the device, a copy of the chain's own: d_xy is rewritten by calls that do not touch the probe buffer
+        int rc2 = h->pm_dxy.reserve(h, (size_t)2 * n_probes);
+        if (rc2) return rc2;
+        HIPCHK(h, hipMemcpyAsync(h->pm_dxy, h->d_xy, (size_t)2 * n_probes * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        h->pm_valid = true;
+    }
+    return rc;
 }
 
 int msl_set_probe_members(msl_handle* h, double mrad, const double* xy, const double* defocus, int32_t n_probes) {
@@ -3546,7 +3685,11 @@ int msl_set_probe_members(msl_handle* h, double mrad, const double* xy, const do
         if (!std::isfinite(defocus[p])) return fail(h, MSL_ERR_INVALID, "msl_set_probe_members: defocus %d is not finite", p);
         if (defocus[p] != 0) any = true;
     }
-    if (!any) return msl_set_probes(h, mrad, xy, n_probes);     // every member at the handle's own C10: that call, bit for bit
+    if (!any) {                                                 // every member at the handle's own C10: that call, bit for bit
+        const int rc0 = msl_set_probes(h, mrad, xy, n_probes);
+        h->pm_valid = false;                                    // (member probes are not differentiated)
+        return rc0;
+    }
     const msl_config& c = h->cfg;
     HIPCHK(h, hipSetDevice(c.device));
     int rc = h->mem_a0.reserve(h, (size_t)n_probes);
@@ -3909,6 +4052,7 @@ int msl_smatrix_build(msl_handle* h) {
     int rc;
     if (c.launch_timing && (rc = timer.begin(h))) return rc;
     h->have_probes = false; h->have_exit = false; h->sm_built = false;      // the probe and work buffers carry the beams
+    h->pm_valid = false; h->pm_g = 0;
     const int P = c.n_probes;
     const long long total = (long long)c.nx * c.ny * P;
     const size_t row = (size_t)c.ny * sizeof(float2);
@@ -3987,6 +4131,7 @@ int msl_smatrix_probes(msl_handle* h, const double* xy, int32_t n_probes, int32_
     if ((rc = smatrix_coefficients(h, n_probes))) return rc;
     // the synthesised waves go to the work buffer (MSL_BUF_EXIT) and to the probe buffer, which the spectrum transform consumes
     h->have_probes = false;
+    h->pm_valid = false; h->pm_g = 0;
     const bool vec = c.ny % 2 == 0 && h->pitch % 2 == 0;
     if (n_probes > 8) launch_synth<16>(h, vec, c.nx / h->sm_fx, c.ny / h->sm_fy);
     else launch_synth<8>(h, vec, c.nx / h->sm_fx, c.ny / h->sm_fy);
@@ -4047,6 +4192,7 @@ int msl_smatrix_probes_cropped(msl_handle* src, msl_handle* dst, const double* x
     HIPCHK(src, hipEventRecord(src->sm_ev[0], dst->stream));
     HIPCHK(src, hipStreamWaitEvent(src->stream, src->sm_ev[0], 0));
     dst->have_probes = false;
+    dst->pm_valid = false; dst->pm_g = 0;
     // VEC: ny, the cropped ny and the result's work pitch even (the S-matrix is dense: its rows are ny long)
     const bool vec = c.ny % 2 == 0 && d.ny % 2 == 0 && dst->pitch % 2 == 0;
     if (n_probes > 8) launch_synth_crop<16>(src, dst, vec, n_probes);
@@ -5042,6 +5188,7 @@ int msl_image_add(msl_handle* h, const void* d_src_c64, int64_t B, int64_t T, in
     const float scale = 1.0f / ((float)c.nx * (float)c.ny);
     if ((rc = begin_timed(h, (int)std::min<int64_t>(8 * ((count + per - 1) / per), 4096)))) return rc;
     h->have_exit = false;                                        // MSL_BUF_EXIT is consumed
+    h->pm_g = 0;
     for (int64_t j0 = 0; j0 < count; j0 += per) {
         const int64_t n = std::min<int64_t>(per, count - j0), images = n * B;
         // about 4096 workgroups: H is evaluated once per lane and reused for the images the lane walks

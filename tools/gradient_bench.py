@@ -83,9 +83,42 @@ def position_leg(a, src, kw, data):
     return lines
 
 
+def probe_params_leg(a, src, kw, data):
+    """--probe-params: run_gradient() with and without Gradient(probe_positions=True, aberrations=True),
+    alternating, and the chain alone (msl_adjoint_probe_params_time on the work buffer of the last batch)"""
+    import pyslice_amd as ps
+    plain = ps.MultisliceCalculator(device=0, progress=False, gradient=ps.Gradient(), probe_batch=a.probe_batch)
+    plain.setup(src, **kw)
+    with_par = ps.MultisliceCalculator(device=0, progress=False, gradient=ps.Gradient(probe_positions=True, aberrations=True),
+                                       probe_batch=a.probe_batch)
+    with_par.setup(src, **kw)
+    plain.run_gradient(data)
+    res = with_par.run_gradient(data)
+    times = {"plain": [], "params": []}
+    for _ in range(a.repeat):
+        for name, calc in (("plain", plain), ("params", with_par)):
+            t0 = time.perf_counter()
+            res = calc.run_gradient(data)
+            times[name].append(time.perf_counter() - t0)
+    p, q = float(np.median(times["plain"])), float(np.median(times["params"]))
+    eng = with_par._engine
+    reps = 10
+    ms_chain = eng.adjoint_probe_params_time(reps)
+    nz, B = a.slices, eng.n_probes
+    expect = 32.0 / (168.0 * nz)                                 # one 2-D transform of the batch against the gradient's bytes per pixel
+    return [f"{a.scan} x {a.scan} scan, {a.grid}^2 x {a.slices} slices, probe_batch={a.probe_batch} (median of {a.repeat}, s; all runs)",
+            f"  run_gradient()                                          {p:8.3f}   {' '.join(f'{t:.3f}' for t in times['plain'])}",
+            f"  run_gradient(), probe_positions=True, aberrations=True  {q:8.3f}   {' '.join(f'{t:.3f}' for t in times['params'])}",
+            f"  ratio {q / p:6.4f}   expected from the bytes (32 B per pixel and image once, against 168 B per slice) {1.0 + expect:6.4f}",
+            f"  max |dL/dxy| {np.abs(res.probe_position_gradient).max():.4e}  dL/dC10 {res.aberration_gradient['C10']:.4e}",
+            f"chain alone (the transform of {B} images, probe_moment_kernel over the aperture's box, the sums), {reps} chains between two events",
+            f"  chain {ms_chain:8.3f} ms   {32.0 * B * a.grid * a.grid / (ms_chain * 1e-3) / 1e12:6.2f} TB/s of the transform's 32 B per pixel and image"]
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--positions", action="store_true", help="the position leg alone, into profiles/position_gradient.txt")
+    ap.add_argument("--probe-params", action="store_true", help="the probe-parameter leg alone, into profiles/probe_gradient.txt")
     ap.add_argument("--out", default=os.path.join("profiles", "gradient.txt"))
     ap.add_argument("--repeat", type=int, default=3)
     ap.add_argument("--grid", type=int, default=512)
@@ -110,6 +143,15 @@ def main():
         text = "\n".join(position_leg(a, src, kw, data)) + "\n"
         print(text, end="")
         out = a.out if a.out != os.path.join("profiles", "gradient.txt") else os.path.join("profiles", "position_gradient.txt")
+        os.makedirs(os.path.dirname(out) or ".", exist_ok=True)
+        with open(out, "w") as f:
+            f.write(text)
+        return
+    if a.probe_params:
+        del grad
+        text = "\n".join(probe_params_leg(a, src, kw, data)) + "\n"
+        print(text, end="")
+        out = a.out if a.out != os.path.join("profiles", "gradient.txt") else os.path.join("profiles", "probe_gradient.txt")
         os.makedirs(os.path.dirname(out) or ".", exist_ok=True)
         with open(out, "w") as f:
             f.write(text)
